@@ -342,6 +342,26 @@ def secondary_line(dev, label, model, H, W, b, t, lt, precision, x3, steps, warm
     return line
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, frames):
+    """--dump-outputs: the frames the last timed step returned ([b*t, 3, H, W] fp32, or the all-gathered uint8 [B*t, H, W, 3]), as
+    float32.  What exceeds DUMP_LIMIT_BYTES is replaced by a sample: DUMP_LIMIT_BYTES / 8 flat indices drawn with a fixed seed
+    (numpy default_rng(0), sorted: the same indices for the same arguments) -> frames_sample.npy, 1-D."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for f in ("frames.npy", "frames_sample.npy"):          # a stale file of an earlier run must not pass for this one's
+        if os.path.exists(os.path.join(d, f)):
+            os.remove(os.path.join(d, f))
+    if frames.numel() * 4 <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(d, "frames.npy"), frames.float().cpu().numpy())
+        return
+    idx = np.sort(np.random.default_rng(0).integers(0, frames.numel(), size=DUMP_LIMIT_BYTES // 8))
+    sample = frames.reshape(-1)[torch.from_numpy(idx).to(frames.device)].float().cpu().numpy()
+    np.save(os.path.join(d, "frames_sample.npy"), sample)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -372,7 +392,13 @@ def main():
     ap.add_argument("--no-secondary", action="store_true",
                     help="skip the BASELINE configs[3] / [4] lines (e2fgvi_hq 720x1296 T=10 and 1080x1944 T=20, bf16) that the "
                          "default single-GPU invocation times after the headline and attaches as `secondary`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the frames the last timed step returned to DIR/frames.npy (float32; "
+                         "all ranks' frames when gathering, rank 0 writes); above %d MB a fixed, seeded sample of them goes to "
+                         "DIR/frames_sample.npy instead (dump_outputs())" % (DUMP_LIMIT_BYTES >> 20))
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -474,7 +500,7 @@ def main():
     ev0.record()
     for _ in range(args.steps):
         step.run()
-    step.finish()                         # the last step's (pipelined) all-gather joins the timed region
+    last_frames = step.finish()           # the last step's (pipelined) all-gather joins the timed region
     ev1.record()
     torch.cuda.synchronize()
     if dist is not None:
@@ -482,6 +508,9 @@ def main():
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     dev_ms = ev0.elapsed_time(ev1)
+    if args.dump_outputs and rank == 0:
+        # before anything else runs on the GPU: the returned buffer is valid until the step's next run()
+        dump_outputs(args.dump_outputs, last_frames)
     if dist is not None:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)

@@ -297,6 +297,7 @@ class Engine(BF16Path):
             self.autotune_x = autotune
             self._init_x(f)
         self._side = None
+        self._given = None         # (flows, encoder output) of segment graphs: runner.ShardedStep._capture_segments
         torch.cuda.synchronize(self.device)
 
     # ------------------------------------------------------------------ helpers
@@ -324,6 +325,19 @@ class Engine(BF16Path):
                 walk(list(vars(o).values()))
         walk(list(vars(self).values()))
         return total
+
+    def _fork_ok(self):
+        """Whether this forward may fork work onto a side stream: eager forwards only.  A forward being captured into a HIP graph
+        stays on the capture stream, so that no captured graph has parallel branches -- the HIP runtime assigns a graph's branches
+        to streams of its own at launch, and with a process's hardware queues at the runtime's default (4) replays of such graphs
+        after earlier graphs were destroyed corrupted its state: the SIGSEGV in hip::Graph::UpdateStreams of DESIGN.md C8, and a
+        host-heap corruption (`free(): invalid next size`) in a later capture of `bench.py`'s secondary lines.  Forwards in flight
+        still overlap: each pipeline's graph replays whole on a stream of its own (runner.ShardedStep)."""
+        return self.overlap_flows and not torch.cuda.is_current_stream_capturing()
+
+    def encode_any(self, frames):
+        """the encoder of this engine's precision, as forward() / forward_x() run it"""
+        return self.encode_x(frames) if self.bf16 else self.encode(frames)
 
     def _side_stream(self):
         """The side stream that belongs to the CURRENT stream: one per main stream a forward has been issued on.  With a single
@@ -439,7 +453,7 @@ class Engine(BF16Path):
         # step 0 of a direction (backbone only, needed at once) keeps the whole layer
         split = bool(self.prop_split) and b == 1 and l_t >= 3
         main = torch.cuda.current_stream()
-        side = self._side_stream() if (split and self.overlap_flows) else None
+        side = self._side_stream() if (split and self._fork_ok()) else None
         pre, ready = {}, {}
         if split:
             n1 = (l_t - 1) * b
@@ -586,15 +600,16 @@ class Engine(BF16Path):
         frames = ops._chk(frames.float().contiguous(), "masked_frames")
         if self.bf16:
             return self.forward_x(frames, l_t, b, t, h, w, fh, fw, trace)
-        if l_t == 1:
+        if self._given is not None:
+            (fwd, bwd), enc = self._given
+        elif l_t == 1:
             # a one-frame local window (test.py on a 1-frame video): the reference's flow tensors are empty
             # [b,0,2,h,w] and each propagation direction is backbone(cat(x, 0)) (feat_prop.py:105,131-137)
             fwd = bwd = torch.empty((b, 0, h, w, 2), dtype=torch.float32, device=frames.device)
             enc = self.encode(frames)
-        elif self.overlap_flows:
+        elif self._fork_ok():
             # SPyNet (many short, small-channel launches) and the encoder (few large launches) are independent:
-            # run them on two HIP streams so the flow pyramid fills the gaps of the encoder (fork/join is
-            # captured as two branches when the forward is recorded into a HIP graph)
+            # run them on two HIP streams so the flow pyramid fills the gaps of the encoder (eager forwards only: _fork_ok)
             main = torch.cuda.current_stream()
             side = self._side_stream()
             side.wait_stream(main)

@@ -241,10 +241,12 @@ class BF16Path:
 
     # ------------------------------------------------------------------ whole forward (e2fgvi_hq.py:235-263)
     def forward_x(self, frames, l_t, b, t, h, w, fh, fw, trace=None):
-        if l_t == 1:
+        if self._given is not None:
+            (fwd, bwd), enc = self._given
+        elif l_t == 1:
             fwd = bwd = torch.empty((b, 0, h, w, 2), dtype=torch.float32, device=frames.device)
             enc = self.encode_x(frames)
-        elif self.overlap_flows:
+        elif self._fork_ok():
             main = torch.cuda.current_stream()
             side = self._side_stream()
             side.wait_stream(main)

@@ -63,6 +63,24 @@ class whole_propagation:
         return False
 
 
+class SegmentGraphs:
+    """ShardedStep's captured forward in segments (ShardedStep._capture_segments): replay() launches them on the current stream and
+    its side stream -- the side stream waits for what the caller has enqueued, the rest waits for the side stream."""
+
+    def __init__(self, flows_graph, encoder_graph, rest_graph, side, static):
+        self.gf, self.ga, self.gb, self.side = flows_graph, encoder_graph, rest_graph, side
+        self.static = static                  # the flows and the encoder output the rest reads: kept alive with the graphs
+
+    def replay(self):
+        cur = torch.cuda.current_stream()
+        self.side.wait_stream(cur)
+        with torch.cuda.stream(self.side):
+            self.gf.replay()
+        self.ga.replay()
+        cur.wait_stream(self.side)
+        self.gb.replay()
+
+
 class ShardedStep:
     """One benchmark / serving step: forward of this rank's clips (+ optional uint8 packing) + all-gather of the frames.
 
@@ -121,6 +139,10 @@ class ShardedStep:
             # --no-cpu-baseline`, first secondary line, 5 of 5 runs).  On `s` both streams of the capture have run the
             # same forward eagerly one statement earlier.
             # thread_local: RCCL's watchdog thread may query events while this thread captures
+            segments = self._capture_segments(s)
+            if segments is not None:
+                self.graph, self.graphed = segments, True
+                return
             with torch.cuda.graph(g, stream=s, capture_error_mode="thread_local"):
                 self.out = self._forward()
             self.graph, self.graphed = g, True
@@ -129,6 +151,39 @@ class ShardedStep:
             self.use_graph = False
             self.graph = None
             torch.cuda.synchronize()
+
+    def _engine(self):
+        eng = getattr(self.net, "engine", None)
+        try:
+            return eng() if callable(eng) else None
+        except Exception:
+            return None
+
+    def _capture_segments(self, s):
+        """The forward as three graphs without parallel branches (Engine._fork_ok: a captured forward forks nothing): SPyNet on a
+        side stream with its own memory pool, the encoder on `s`, the rest on `s` reading both (the pool of the encoder's graph).
+        SegmentGraphs.replay() forks and joins the two streams around the launches, so SPyNet fills the encoder's gaps as the eager
+        forward's side stream does.  None when the forward would not fork (one local frame, overlap off): one graph then."""
+        eng = self._engine()
+        if eng is None or not eng.overlap_flows or self.lt < 2 or torch.cuda.is_current_stream_capturing():
+            return None
+        side = torch.cuda.Stream()
+        side.wait_stream(s)
+        with torch.cuda.stream(side):                 # DESIGN.md C8: no stream meets a capture before it has run eager work
+            eng.flows(self.x, self.lt)
+        torch.cuda.synchronize()
+        gf, ga, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gf, stream=side, capture_error_mode="thread_local"):
+            flows = eng.flows(self.x, self.lt)
+        with torch.cuda.graph(ga, stream=s, capture_error_mode="thread_local"):
+            enc = eng.encode_any(self.x)
+        eng._given = (flows, enc)
+        try:
+            with torch.cuda.graph(gb, stream=s, pool=ga.pool(), capture_error_mode="thread_local"):
+                self.out = self._forward()
+        finally:
+            eng._given = None
+        return SegmentGraphs(gf, ga, gb, side, (flows, enc))
 
     def _sync_decisions(self):
         """Every rank replays rank 0's tile decisions: same kernels, same accumulation order, bit-identical frames from every

@@ -326,6 +326,46 @@ def test_graph_replay_equals_eager(dev):
     assert torch.equal(a, eager) and torch.equal(b, eager) and torch.equal(c, eager)
 
 
+def test_captured_forward_forks_no_side_stream(dev):
+    """a forward captured into a HIP graph stays on the capture stream (Engine._fork_ok): no graph bench.py replays has
+    parallel branches, which the HIP runtime runs on streams of its own at launch.  The overlap of SPyNet and the
+    encoder comes from three segment graphs on two streams instead (runner.SegmentGraphs).  The replayed frames are those of
+    the eager forward, whose SPyNet runs on the side stream.  Headline shape, one and two forwards in flight."""
+    import importlib
+    from e2fgvi_amd import runner
+    from e2fgvi_amd.synth import synth_clip, synth_state_dict
+    for model, precision in (("e2fgvi", "fp32"), ("e2fgvi_hq", "bf16")):
+        net = importlib.import_module("model." + model).InpaintGenerator()
+        net.load_state_dict(synth_state_dict(model, "stress", 0))
+        net = net.to(dev).eval()
+        net.precision = precision
+        x = synth_clip(1, 10, 240, 432, seed=43, moving=True)[0].to(dev)
+        eager = {1: net(x, 10)[0]}
+        with runner.whole_propagation(net):                    # what the pipelines capture (runner.ShardedStep)
+            eager[2] = net(x, 10)[0]
+        eng = net.engine()
+        assert eng._fork_ok()
+        in_capture = []
+        side = eng._side_stream
+
+        def watched():
+            in_capture.append(torch.cuda.is_current_stream_capturing())
+            return side()
+        eng._side_stream = watched
+        try:
+            for in_flight in (1, 2):
+                step = runner.ShardedStep(net, x, 10, use_graph=True, in_flight=in_flight)
+                got = [step.run() for _ in range(5)]
+                graphs = [p[0] for p in step._pipes] if step._pipes is not None else [step.graph]
+                assert len(graphs) == in_flight and all(isinstance(g, runner.SegmentGraphs) for g in graphs)
+                assert torch.equal(step.finish(), eager[in_flight])
+                assert all(torch.equal(g, eager[in_flight]) for g in got if g is not None)
+                del step
+        finally:
+            del eng._side_stream
+        assert in_capture and not any(in_capture), in_capture       # the eager warm-ups forked, no capture did
+
+
 def test_stream_overlap_is_bit_identical_to_serial(dev):
     """SPyNet runs on a side stream next to the encoder (Engine.overlap_flows), in the fp32 and in the bf16 mode: the
     two-stream schedule must give exactly the single-stream result, every time.  Tripwire for the cross-stream corruption
