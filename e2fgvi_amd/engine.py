@@ -12,8 +12,19 @@ stage can be checked against the oracle on the same inputs:
     compose()    tfocal_transformer.py:65-72 (+ e2fgvi.py:258)
     decode()     e2fgvi.py:126-150, :261-262
 
-All activations are NHWC fp32; nothing here computes on the CPU or through torch ops -- torch only
-owns the buffers (and does index-only copies when clips are batched).
+Nothing here computes on the CPU or through torch ops -- torch only owns the buffers (and does index-only copies when clips
+are batched).  The precision is data: the layer classes a checkpoint layer gets, the dtype of the activations and the input
+padding; both precisions run the same stage methods.
+
+  * fp32 (the default and the parity configuration): all activations are NHWC fp32.
+  * bf16 (BASELINE.json configs 4 / 5: e2fgvi_hq at 720p / 1080p, "bf16 MFMA"): activations are bf16 NHWC tensors in HBM (half
+    the traffic of the fp32 path), every conv / linear runs in csrc/conv_bf16x.hip (bf16 operands by LDS-DMA,
+    v_mfma_f32_32x32x16_bf16, fp32 accumulation and epilogue).  Kept in fp32: the SPyNet flow pyramid and the flows (sub-pixel
+    sampling positions), the DCN offsets / masks (output of conv_offset.6 incl. its 10 tanh + flow post-processing), the token
+    residual stream between transformer blocks (LayerNorm input) and the output frames; the recurrent propagation features are
+    ONE bf16 tensor per step (conv source, flow-warp source, and -- re-laid out [group][pixel][16] -- the deformable conv's
+    gather source).  LayerNorm, window pooling, fold / unfold + GELU, SoftComp fold and the x2 upsamples read / write bf16 and
+    compute in fp32 (typed variants of the fp32 kernels, csrc/misc.hip).
 """
 import numpy as np
 import os
@@ -21,21 +32,25 @@ import os
 import torch
 
 from . import ops
-from .engine_x import BF16Path
-from .ops import ACT_DCNPOST, ACT_LRELU, ACT_NONE, ACT_RELU, ACT_TANH, PackedConv, PackedConvX, PackedDcn, PackedLinear
+from .ops import ACT_DCNPOST, ACT_LRELU, ACT_RELU, ACT_TANH, PackedConvX
 
+BF16 = torch.bfloat16
 # fp32 path: the FFN's second Linear as a conv of the folded tensor (as the bf16 path runs it).  Measured neutral on the fp32
 # MFMA kernels (15.785 vs 15.775 ms, profiles/r02_fc2_conv.txt: the 16-byte tap-packed fetches cost what the unfold kernel
 # saved); with the split-operand kernels (ops.X3_ENABLED) the conv form wins -- 743 -> 750 frames/s, same box, two runs each
 # (profiles/r03_fc2_conv_x3.txt) -- and is the default
 FC2_CONV = ops.X3_ENABLED          # (bench.py's E2FGVI_X3=0 secondary line sets both to False for its engine)
+# bf16 path, settled in rounds 2-5 and no longer switchable (round 6): decoder.6 on csrc/conv_tail.hip; the deformable conv gathers
+# from [group][pixel][16] copies of the propagated features; the recurrent propagation state and the flow-warp sources are the bf16
+# copies (an fp32 state changes the end-to-end error by < 1 % of itself: tools/bf16_error_growth.py); the FFN's second Linear is
+# the 7x7 / stride-3 conv of the folded tensor; SoftComp (HQ) runs in gather form.
 WIN = (5, 9)
 # where the side stream (SPyNet) joins the main one: in front of encoder.layers.<JOIN_AT> (18 = behind the encoder).  Round 4 joined in
 # front of layer 10 (its wide-tile kernel was fenced to layers with the chip to themselves); with encoder.layers.2 / 6 / 8 on that
 # kernel the main stream reaches layer 10 before SPyNet has finished and waited there: 787.9 frames/s joined at 10, 801-808 joined
 # at 12 ... 18, best at 16 (same box, two runs each: profiles/r05_join_position.txt)
 # With several clips per forward the batched encoder layers fill the chip on their own and the early join is 0.5 % ahead (8 clips: 974.7
-# vs 969.5 frames/s), so: 16 at one clip, 10 otherwise; E2FGVI_JOIN_AT overrides both.
+# vs 969.5 frames/s), so: 16 at one clip, 10 otherwise; E2FGVI_JOIN_AT overrides both.  (The bf16 path joins behind the encoder.)
 JOIN_AT = int(os.environ.get("E2FGVI_JOIN_AT", "0") or 0)
 if JOIN_AT not in (0, 10, 12, 14, 16, 18):
     raise ValueError("E2FGVI_JOIN_AT=%d: the join sits in front of encoder.layers.10 / 12 / 14 / 16 or behind the encoder (18)" % JOIN_AT)
@@ -96,26 +111,16 @@ def split_prop_weights(w_off0, w_bb0, ch=128):
                 bb_rec=w_bb0[:, -ch:].contiguous(), bb_pre=w_bb0[:, :-ch].contiguous())
 
 
-class _NotBuilt:
-    """stands in for an fp32 layer in the bf16 mode (names / flags may be set on it; calling it is a bug)"""
-
-    def __init__(self, *a, **k):
-        self.name = "not built"
-
-    def __call__(self, *a, **k):
-        raise RuntimeError("fp32 layer %r was not built: this engine runs the bf16 data path" % self.name)
-
-
-class Engine(BF16Path):
+class Engine:
     def __init__(self, state_dict, model="e2fgvi", device="cuda", precision="fp32", winograd=True, autotune=True):
         """precision="fp32": fp32 tensors, every contraction with fp32-level rounding (the default and the parity configuration):
         on the fp32 MFMA instructions (bit-equivalent to an fp32 FMA chain) or -- ops.X3_ENABLED, the default -- on the bf16 matrix
         pipe with exactly split operands (three bf16 pieces per fp32 value, six of the nine cross terms, fp32 accumulation: fp32-
         level, not bit-identical to an FMA chain; tests/test_gpu_x3.py).  Which of the two a layer runs comes from the decision
         table (ops.py); E2FGVI_X3=0 gives the pure fp32-MFMA configuration.
-        precision="bf16": the bf16 data path of engine_x.py (BASELINE.json HQ configurations): bf16 activations in HBM,
-        every conv / linear / attention product on bf16 MFMA with fp32 accumulation; SPyNet, the flows, the DCN offsets
-        and masks, the deformable conv's arithmetic and the token residual stream stay fp32."""
+        precision="bf16": the bf16 data path (BASELINE.json HQ configurations): bf16 activations in HBM, every conv / linear /
+        attention product on bf16 MFMA with fp32 accumulation; SPyNet, the flows, the DCN offsets and masks, the deformable conv's
+        arithmetic and the token residual stream stay fp32."""
         if precision not in ("fp32", "bf16"):
             raise ValueError("precision must be 'fp32' or 'bf16'")
         self.precision = precision
@@ -124,80 +129,114 @@ class Engine(BF16Path):
         sd = {k: v.detach().to(self.device) for k, v in state_dict.items()}
         self.sd = sd
         f = lambda k: sd[k].float().contiguous()
-        self.bf16 = precision == "bf16"
-        # bf16 mode: the fp32 layers are never called (forward_x reads only the LayerNorm / pooling parameters, the key
-        # tables and sc.bias from this constructor) -- do not pack their weights: several hundred MB of device memory (both
-        # the implicit-GEMM and the Winograd packings) and the start-up time of ~150 pack launches
-        PackedConv, PackedLinear, PackedDcn, PackedConvX, PackedTail = (
-            (_NotBuilt,) * 5 if self.bf16 else (ops.PackedConv, ops.PackedLinear, ops.PackedDcn, ops.PackedConvX, ops.PackedTailConv))
-        pw = dict(precision="fp32")
-        # wide 3x3 / stride-1 layers: fp32 Winograd F(2x2,3x3) whenever the call qualifies (even H, W), else implicit GEMM
-        ww = dict(precision="fp32", algo="auto" if winograd else "igemm")
+        self.bf16 = bf16 = precision == "bf16"
+        self.dtype = BF16 if bf16 else torch.float32          # of the activations between the layers
+        x3 = not bf16 and ops.X3_ENABLED
+        # wide 3x3 / stride-1 layers: fp32 Winograd F(2x2,3x3) whenever the call qualifies (even H, W), else implicit GEMM (the
+        # other geometries stay on the implicit GEMM under algo="auto": ops.PackedConv)
+        algo = "auto" if winograd else "igemm"
 
-        # ---- encoder (e2fgvi.py:75-94)
-        w0 = torch.zeros(64, 4, 3, 3, device=self.device)
+        def layer(name, key, cpg=None, w=None, b=None, tune=False, nopk=False, **geom):
+            """One checkpoint layer in this engine's precision: weights <key>.weight / <key>.bias unless `w` / `b` are given (key
+            None: both are); cpg None: a Linear.  fp32: ops.PackedConv / PackedLinear, or PackedConvX on fp32 operands when `taps`
+            is given; bf16: ops.PackedConvX / PackedLinearX.
+            tune (fp32): the GEMM-shaped layers (token Linears, soft split / composite): the best implicit-GEMM tile depends on
+            the token count; their tile code comes from the decision table of ops.py (e2fgvi_amd/tile_table.py by default, timed on
+            the first eager call of each size class under E2FGVI_AUTOTUNE=1).  (Winograd block shapes are NOT tuned at run time:
+            measured in round 2, the timing-based choice between the 16x16 / 8x16-pixel blocks moved the forward by -1 ... -2 % and
+            added run-to-run variance; the static rule of e2fgvi_conv3x3_winograd stays.)  In bf16 every layer is tuned: the best
+            tile of conv_bf16x depends on the layer's M x N x K and on how many tiles that makes for 256 CUs (timed on the first
+            eager call of each size class, never under graph capture).
+            try_x3: every fp32 conv / linear may run on the bf16 matrix pipe instead (ops.PackedConvX x3: operands split exactly
+            into three bf16 pieces, six bf16 MFMA terms per product, fp32-level rounding): timed against the layer's fp32 kernel
+            on the first eager call of each size class, kept where it is faster (the GEMM-shaped layers: token Linears, soft split
+            / composite, the stride-2 and 1x1 convs; the Winograd layers mostly keep Winograd).  SPyNet's 7x7 layers are candidates
+            too since round 5 (the split-operand GEMM is built without packed-fp32 VALU like every kernel that can run on the side
+            stream): the two wide layers of the upper levels take it, 221 -> 199 and 239 -> 223 us alone and -- what matters beside
+            the encoder -- at a third of the matrix-pipe time (profiles/r05_spynet_x3.txt).
+            nopk (fp32): the side stream's layers run the build without packed-fp32 VALU (build.py; every bf16 kernel is built so)."""
+            if key is not None:
+                w = f(key + ".weight") if w is None else w
+                b = f(key + ".bias") if b is None else b
+            if cpg is None:
+                c = ops.PackedLinearX(w, b) if bf16 else ops.PackedLinear(w, b, precision="fp32")
+            elif bf16 or "taps" in geom:
+                c = ops.PackedConvX(w, b, cpg, dtype=self.dtype, **geom)
+            else:
+                c = ops.PackedConv(w, b, cpg, precision="fp32", algo=algo, **geom)
+            c.name = name
+            c.tune = autotune and (bf16 or tune)
+            c.try_x3 = x3
+            if nopk and not bf16:
+                c.nopk = True
+            return c
+
+        # ---- encoder (e2fgvi.py:75-94): the 3-channel frames are carried as 4 fp32 / 8 bf16 channels (16-byte pixels), layer 0's
+        # weight is zero-padded to match
+        cin0 = 8 if bf16 else 4
+        w0 = torch.zeros(64, cin0, 3, 3, device=self.device)
         w0[:, :3] = f("encoder.layers.0.weight")
-        enc = [PackedConv(w0, f("encoder.layers.0.bias"), [4], stride=2, pad=1)]
+        self.enc = [layer("encoder.layers.0", "encoder.layers.0", [cin0], w=w0, stride=2, pad=1)]
         for i, (cpg, g, s) in zip((2, 4, 6, 8, 10, 12, 14, 16),
                                   (([64], 1, 1), ([64], 1, 2), ([128], 1, 1), ([256], 1, 1), ([128, 192], 2, 1),
                                    ([64, 128], 4, 1), ([32, 48], 8, 1), ([256, 256], 1, 1))):
-            enc.append(PackedConv(f("encoder.layers.%d.weight" % i), f("encoder.layers.%d.bias" % i), cpg, groups=g,
-                                  stride=s, pad=1, **(ww if s == 1 else pw)))
-        self.enc = enc
+            self.enc.append(layer("encoder.layers.%d" % i, "encoder.layers.%d" % i, cpg, groups=g, stride=s, pad=1))
 
-        # ---- decoder (e2fgvi.py:143-150)
-        self.dec = [PackedConv(f("decoder.0.conv.weight"), f("decoder.0.conv.bias"), [128], pad=1, **ww),
-                    PackedConv(f("decoder.2.weight"), f("decoder.2.bias"), [128], pad=1, **ww),
-                    PackedConv(f("decoder.4.conv.weight"), f("decoder.4.conv.bias"), [64], pad=1, **ww),
-                    PackedTail(f("decoder.6.weight"), f("decoder.6.bias"))]
+        # ---- decoder (e2fgvi.py:143-150); decoder.6 (64 -> 3) on csrc/conv_tail.hip, reading the activations' dtype
+        self.dec = [layer(n, n, [c], pad=1) for n, c in (("decoder.0.conv", 128), ("decoder.2", 128), ("decoder.4.conv", 64))]
+        tail = ops.PackedTailConv(f("decoder.6.weight"), f("decoder.6.bias"), dtype=self.dtype)
+        tail.name = "decoder.6"
+        if bf16 and autotune:
+            tail.tune = True
+        self.dec.append(tail)
 
         # ---- propagation (feat_prop.py:61-79, :15-33)
         # conv_offset.0 and backbone.0 are linear in their input channels, and a third / a half / two thirds of those do not
         # depend on the recurrence (the current frame's features, the other direction's result): at one clip per forward that
         # part is computed for all frames at once on the side stream, beside the chain of one-frame launches that leaves most
         # of the chip idle, and enters the per-step layer -- now 260 / 128 input channels instead of 388 / 256 / 384 -- as its
-        # residual (PROP_SPLIT, propagate()).  Round 2 measured the same split as a net loss (42 -> 34 and 37 -> 26 us per step
-        # against 537 us of batched launches in the critical path, profiles/r02_c2_layer_fp32_base.md): the batched half was
-        # four fp32-MFMA launches on the main stream then, it is three split-operand launches beside the chain now.
+        # residual (PROP_SPLIT, propagate(); fp32 only).  Round 2 measured the same split as a net loss (42 -> 34 and 37 -> 26 us
+        # per step against 537 us of batched launches in the critical path, profiles/r02_c2_layer_fp32_base.md): the batched half
+        # was four fp32-MFMA launches on the main stream then, it is three split-operand launches beside the chain now.
         self.prop = {}
         self.prop_split = {}
         for d, nparts in (("backward_", 2), ("forward_", 3)):
             p = "feat_prop_module.deform_align.%s." % d
-            # conv_offset.0 input = cat(cond_n1, cur, cond_n2, flow_1, flow_2): sources (cond|0), cur, (cond|128), flows4
-            off = [PackedConv(f(p + "conv_offset.0.weight"), f(p + "conv_offset.0.bias"), [128, 128, 128, 4], pad=1, **ww),
-                   PackedConv(f(p + "conv_offset.2.weight"), f(p + "conv_offset.2.bias"), [128], pad=1, **ww),
-                   PackedConv(f(p + "conv_offset.4.weight"), f(p + "conv_offset.4.bias"), [128], pad=1, **ww),
-                   PackedConv(f(p + "conv_offset.6.weight"), f(p + "conv_offset.6.bias"), [128], pad=1,
-                              algo=ww["algo"])]
-            # (split-operand MFMA with the other x3 kernels: ops.X3_ENABLED)
-            dcn = PackedDcn(f(p + "weight"), f(p + "bias"), 16, pad=1, mfma="x3" if (precision == "fp32" and ops.X3_ENABLED) else "fp32")
             b = "feat_prop_module.backbone.%s." % d
-            bb = [PackedConv(f(b + "0.weight"), f(b + "0.bias"), [128] * nparts, pad=1, **ww),
-                  PackedConv(f(b + "2.weight"), f(b + "2.bias"), [128], pad=1, **ww)]
+            # conv_offset.0 input = cat(cond_n1, cur, cond_n2, flow_1, flow_2): sources (cond|0), cur, (cond|128), flows (4 fp32
+            # channels; 8 bf16 channels, the weight zero-padded to match)
+            w_off0 = f(p + "conv_offset.0.weight")
+            if bf16:
+                w_off0 = torch.cat([w_off0, w_off0.new_zeros(128, 4, 3, 3)], 1)
+            off = [layer("deform_align.%sconv_offset.0" % d, p + "conv_offset.0", [128, 128, 128, 8 if bf16 else 4], w=w_off0, pad=1)]
+            off += [layer("deform_align.%sconv_offset.%d" % (d, k), p + "conv_offset.%d" % k, [128], pad=1) for k in (2, 4, 6)]
+            # the deformable conv: split-operand MFMA with the other x3 kernels (ops.X3_ENABLED); bf16 products in the bf16 path
+            dcn = ops.PackedDcn(f(p + "weight"), f(p + "bias"), 16, pad=1, mfma="bf16" if bf16 else ("x3" if x3 else "fp32"))
+            dcn.name = "deform_align.%sdcn" % d
+            bb = [layer("backbone.%s0" % d, b + "0", [128] * nparts, pad=1), layer("backbone.%s2" % d, b + "2", [128], pad=1)]
             self.prop[d] = (off, dcn, bb)
-            if PROP_SPLIT and precision == "fp32":
+            if PROP_SPLIT and not bf16:
                 ws = split_prop_weights(f(p + "conv_offset.0.weight"), f(b + "0.weight"))
-                sp = dict(off_rec=PackedConv(ws["off_rec"], f(p + "conv_offset.0.bias"), [128, 128, 4], pad=1, **ww),
-                          off_cur=PackedConv(ws["off_cur"], None, [128], pad=1, **ww),
-                          bb_rec=PackedConv(ws["bb_rec"], f(b + "0.bias"), [128], pad=1, **ww),
-                          bb_pre=PackedConv(ws["bb_pre"], None, [128] * (nparts - 1), pad=1, **ww))
-                sp["off_rec"].name, sp["off_cur"].name = "deform_align.%sconv_offset.0 (recurrent part)" % d, "deform_align.%sconv_offset.0 (current-frame part)" % d
-                sp["bb_rec"].name, sp["bb_pre"].name = "backbone.%s0 (recurrent part)" % d, "backbone.%s0 (non-recurrent part)" % d
-                self.prop_split[d] = sp
-        self.fusion = PackedConv(f("feat_prop_module.fusion.weight"), f("feat_prop_module.fusion.bias"), [128, 128], **pw)
+                self.prop_split[d] = dict(
+                    off_rec=layer("deform_align.%sconv_offset.0 (recurrent part)" % d, None, [128, 128, 4], w=ws["off_rec"],
+                                  b=f(p + "conv_offset.0.bias"), pad=1),
+                    off_cur=layer("deform_align.%sconv_offset.0 (current-frame part)" % d, None, [128], w=ws["off_cur"], pad=1),
+                    bb_rec=layer("backbone.%s0 (recurrent part)" % d, None, [128], w=ws["bb_rec"], b=f(b + "0.bias"), pad=1),
+                    bb_pre=layer("backbone.%s0 (non-recurrent part)" % d, None, [128] * (nparts - 1), w=ws["bb_pre"], pad=1))
+        self.fusion = layer("fusion", "feat_prop_module.fusion", [128, 128], tune=True)
 
         # ---- soft split / composite (tfocal_transformer.py:19-72)
-        self.ss = PackedConv(f("ss.embedding.weight").view(512, 128, 7, 7), f("ss.embedding.bias"), [128], stride=3, pad=3,
-                             **pw)
+        self.ss = layer("ss.embedding", "ss.embedding", [128], w=f("ss.embedding.weight").view(512, 128, 7, 7), stride=3, pad=3,
+                        tune=True)
         # patch channel order c*49+tap -> tap*128+c (private layout of the fold kernels)
         wsc = f("sc.embedding.weight").view(128, 49, 512).permute(1, 0, 2).reshape(6272, 512).contiguous()
         bsc = f("sc.embedding.bias").view(128, 49).t().reshape(6272).contiguous()
-        self.sc = PackedLinear(wsc, bsc, **pw)
-        if self.hq:
-            self.sc_bias_conv = PackedConv(f("sc.bias_conv.weight"), f("sc.bias_conv.bias"), [128], pad=1, **ww)
-            self.sc_bias_hwc = None
-        else:
-            self.sc_bias_hwc = f("sc.bias").permute(1, 2, 0).contiguous()
+        self.sc = layer("sc.embedding", None, w=wsc, b=bsc, tune=True)
+        self.sc_bias_conv = layer("sc.bias_conv", "sc.bias_conv", [128], pad=1) if self.hq else None
+        self.sc_bias_hwc = None if self.hq else f("sc.bias").permute(1, 2, 0).contiguous()
+        # bf16 HQ: SoftComp in gather form (nine phase convolutions writing the folded image directly: no [tokens, 6272] tensor,
+        # 813 MB at 720p T=10, and no fold kernel); other token grids than 3 x the feature size take the Linear + fold pair
+        self.sc_gather = (ops.SoftCompGather(f("sc.embedding.weight"), f("sc.embedding.bias"), 128) if bf16 and self.hq else None)
 
         # ---- transformer blocks
         self.blocks = []
@@ -205,29 +244,29 @@ class Engine(BF16Path):
             p = "transformer.%d." % i
             w1 = f(p + "mlp.conv1.0.weight").view(40, 49, 512).permute(1, 0, 2).reshape(1960, 512).contiguous()
             b1 = f(p + "mlp.conv1.0.bias").view(40, 49).t().reshape(1960).contiguous()
-            w2 = f(p + "mlp.conv2.1.weight").view(512, 40, 49).permute(0, 2, 1).reshape(512, 1960).contiguous()
+            if FC2_CONV or bf16:
+                # fc2: Linear(1960 -> 512) of the unfolded 7x7 patches == the 7x7 / stride 3 / pad 3 convolution of the folded
+                # [F, H, W, 40] tensor (tfocal_transformer.py:81,95-97): no unfold kernel, no [rows, 1960] tensor
+                fc2 = layer(p + "fc2", p + "mlp.conv2.1", [40], w=f(p + "mlp.conv2.1.weight").view(512, 40, 7, 7), stride=3, pad=3,
+                            taps=True, tune=True)
+            else:
+                w2 = f(p + "mlp.conv2.1.weight").view(512, 40, 49).permute(0, 2, 1).reshape(512, 1960).contiguous()
+                fc2 = layer(p + "fc2", p + "mlp.conv2.1", w=w2, tune=True)
             self.blocks.append(dict(
                 pool_w=f(p + "pool_layers.0.weight").view(45), pool_b=f(p + "pool_layers.0.bias"),
                 n1w=f(p + "norm1.weight"), n1b=f(p + "norm1.bias"), n2w=f(p + "norm2.weight"), n2b=f(p + "norm2.bias"),
-                qkv=PackedLinear(f(p + "attn.qkv.weight"), f(p + "attn.qkv.bias"), **pw),
-                proj=PackedLinear(f(p + "attn.proj.weight"), f(p + "attn.proj.bias"), **pw),
-                fc1=PackedLinear(w1, b1, **pw),
-                # fc2: Linear(1960 -> 512) of the unfolded 7x7 patches == the 7x7 / stride 3 / pad 3 convolution of the folded
-                # [F, H, W, 40] tensor (tfocal_transformer.py:81,95-97): no unfold kernel, no [rows, 1960] tensor
-                fc2=(PackedConvX(f(p + "mlp.conv2.1.weight").view(512, 40, 7, 7), f(p + "mlp.conv2.1.bias"), [40], stride=3,
-                                 pad=3, dtype=torch.float32, taps=True) if FC2_CONV and precision == "fp32" else
-                     PackedLinear(w2, f(p + "mlp.conv2.1.bias"), **pw)),
+                qkv=layer(p + "qkv", p + "attn.qkv", tune=True),
+                proj=layer(p + "proj", p + "attn.proj", tune=True),
+                fc1=layer(p + "fc1", None, w=w1, b=b1, tune=True),
+                fc2=fc2,
                 valid=sd[p + "attn.valid_ind_rolled"].cpu().tolist()))
 
-        # ---- SPyNet (flow_comp.py:49-82,172-215)
-        self.spy = []
-        for lv in range(6):
-            convs = []
-            for j, cin in enumerate((8, 32, 64, 32, 16)):
-                p = "update_spynet.basic_module.%d.basic_module.%d.conv." % (lv, j)
-                convs.append(PackedConv(f(p + "weight"), f(p + "bias"), [cin], pad=3))
-                convs[-1].nopk = True      # SPyNet runs on a side stream: the build without packed-fp32 VALU (build.py)
-            self.spy.append(convs)
+        # ---- SPyNet (flow_comp.py:49-82,172-215).  In bf16 the conv stacks of the six pyramid levels run on bf16 MFMA (they are
+        # 15 % of the 720p forward in fp32); the geometry stays fp32 -- pyramid images, warps, the flow itself and the residual sum
+        # flow = up(flow) + net(...) (the last conv of a level adds the fp32 upsampled flow and stores fp32).
+        self.spy = [[layer("spynet.%d.%d" % (lv, j), "update_spynet.basic_module.%d.basic_module.%d.conv" % (lv, j), [cin], pad=3,
+                           nopk=True)
+                     for j, cin in enumerate((8, 32, 64, 32, 16))] for lv in range(6)]
         mean = f("update_spynet.mean").view(3)
         std = f("update_spynet.std").view(3)
         one = torch.ones(1, device=self.device)
@@ -236,66 +275,11 @@ class Engine(BF16Path):
         self.half = torch.full((4,), 0.5, device=self.device)
         self._tables = {}
         self._zeros = {}
-        # checkpoint names on the layers (launch traces: tools/layer_table.py, bench.py's FLOP accounting)
-        for k, i in enumerate((0, 2, 4, 6, 8, 10, 12, 14, 16)):
-            self.enc[k].name = "encoder.layers.%d" % i
-        for k, n in enumerate(("decoder.0.conv", "decoder.2", "decoder.4.conv", "decoder.6")):
-            self.dec[k].name = n
-        for d, (off, dcn, bb) in self.prop.items():
-            for k, c in enumerate(off):
-                c.name = "deform_align.%sconv_offset.%d" % (d, 2 * k)
-            dcn.name = "deform_align.%sdcn" % d
-            bb[0].name, bb[1].name = "backbone.%s0" % d, "backbone.%s2" % d
-        self.fusion.name, self.ss.name, self.sc.name = "fusion", "ss.embedding", "sc.embedding"
-        if self.hq:
-            self.sc_bias_conv.name = "sc.bias_conv"
-        for i, blk in enumerate(self.blocks):
-            for k in ("qkv", "proj", "fc1", "fc2"):
-                blk[k].name = "transformer.%d.%s" % (i, k)
-        for lv, convs in enumerate(self.spy):
-            for j, c in enumerate(convs):
-                c.name = "spynet.%d.%d" % (lv, j)
-        if autotune and precision == "fp32":
-            # GEMM-shaped layers (token Linears, soft split / composite): the best implicit-GEMM tile depends on the
-            # token count; their tile code comes from the decision table of ops.py (e2fgvi_amd/tile_table.py by default,
-            # timed on the first eager call of each size class under E2FGVI_AUTOTUNE=1)
-            for blk in self.blocks:
-                for k in ("qkv", "proj", "fc1", "fc2"):
-                    blk[k].tune = True
-            self.ss.tune = self.sc.tune = self.fusion.tune = True
-            # (Winograd block shapes are NOT tuned at run time: measured in round 2, the timing-based choice between the
-            # 16x16 / 8x16-pixel blocks moved the forward by -1 ... -2 % and added run-to-run variance; the static rule of
-            # e2fgvi_conv3x3_winograd stays.)
-        if precision == "fp32" and ops.X3_ENABLED:
-            # Every fp32 conv / linear of the MAIN stream may run on the bf16 matrix pipe instead (ops.PackedConvX x3: operands
-            # split exactly into three bf16 pieces, six bf16 MFMA terms per product, fp32-level rounding): timed against the
-            # layer's fp32 kernel on the first eager call of each size class, kept where it is faster (the GEMM-shaped layers:
-            # token Linears, soft split / composite, the stride-2 and 1x1 convs; the Winograd layers mostly keep Winograd).
-            # SPyNet's 7x7 layers are candidates too since round 5 (the split-operand GEMM is built without packed-fp32 VALU like every
-            # kernel that can run on the side stream): the two wide layers of the upper levels take it, 221 -> 199 and 239 -> 223 us
-            # alone and -- what matters beside the encoder -- at a third of the matrix-pipe time (profiles/r05_spynet_x3.txt).
-            for layer in self.enc + self.dec[:3] + [self.fusion, self.ss, self.sc] + ([self.sc_bias_conv] if self.hq else []):
-                layer.try_x3 = True
-            for convs in self.spy:
-                for layer in convs:
-                    layer.try_x3 = True
-            for off, _dcn, bb in self.prop.values():
-                for layer in off + bb:
-                    layer.try_x3 = True
-            for sp in self.prop_split.values():
-                for layer in sp.values():
-                    layer.try_x3 = True
-            for blk in self.blocks:
-                for k in ("qkv", "proj", "fc1", "fc2"):
-                    blk[k].try_x3 = True
         # SPyNet runs on a side stream next to the encoder, in both precision modes.  Round 1 found the side stream's
         # kernels corrupted beside bf16 MFMA tiles; round 2 traced it to packed-fp32 VALU instructions consuming freshly
         # loaded registers (tools/probe/overlap_probe.hip, DESIGN.md "Stream overlap"): every kernel that can run on the
         # side stream is built without them (csrc/misc.hip and the `nopk` build of conv.hip, e2fgvi_amd/build.py).
         self.overlap_flows = True
-        if self.bf16:
-            self.autotune_x = autotune
-            self._init_x(f)
         self._side = None
         self._given = None         # (flows, encoder output) of segment graphs: runner.ShardedStep._capture_segments
         torch.cuda.synchronize(self.device)
@@ -335,10 +319,6 @@ class Engine(BF16Path):
         still overlap: each pipeline's graph replays whole on a stream of its own (runner.ShardedStep)."""
         return self.overlap_flows and not torch.cuda.is_current_stream_capturing()
 
-    def encode_any(self, frames):
-        """the encoder of this engine's precision, as forward() / forward_x() run it"""
-        return self.encode_x(frames) if self.bf16 else self.encode(frames)
-
     def _side_stream(self):
         """The side stream that belongs to the CURRENT stream: one per main stream a forward has been issued on.  With a single
         shared side stream, two eager forwards on two main streams (video.inpaint_video(in_flight=2)) raced through the caching
@@ -355,10 +335,10 @@ class Engine(BF16Path):
             self._side[key] = torch.cuda.Stream(device=self.device)
         return self._side[key]
 
-    def _zero(self, shape):
-        key = tuple(shape)
+    def _zero(self, shape, dtype=torch.float32):
+        key = (dtype,) + tuple(shape)
         if key not in self._zeros:
-            self._zeros[key] = torch.zeros(key, dtype=torch.float32, device=self.device)
+            self._zeros[key] = torch.zeros(tuple(shape), dtype=dtype, device=self.device)
         return self._zeros[key]
 
     def _table(self, fh, fw, blk):
@@ -399,16 +379,17 @@ class Engine(BF16Path):
         ref_idx, supp_idx, sc = self._tables[key]
         flow = None
         for lv in range(6):
+            # the fp32 level input (images, warped support image, upsampled flow); the bf16 path's convs read its bf16 copy
             if self.bf16:
-                flow = self.spynet_level_x(lv, pyr[lv], ref_idx, supp_idx, flow)
-                continue
-            inp = ops.spynet_level_input(pyr[lv], ref_idx, supp_idx, flow)
+                inp, x = ops.spynet_level_input(pyr[lv], ref_idx, supp_idx, flow, bf16_copy=True)
+            else:
+                inp = x = ops.spynet_level_input(pyr[lv], ref_idx, supp_idx, flow)
             cv = self.spy[lv]
-            x = cv[0]([inp], act=ACT_RELU)
+            x = cv[0]([x], act=ACT_RELU)
             x = cv[1]([x], act=ACT_RELU)
             x = cv[2]([x], act=ACT_RELU)
             x = cv[3]([x], act=ACT_RELU)
-            flow = cv[4]([x], residual=inp, res_coff=6)
+            flow = cv[4]([x], out_dtype=torch.float32, residual=inp, res_coff=6)          # + fp32 upsampled flow
         flow = ops.resize_bilinear(flow, (h, w), False, scale=sc)
         fwd = flow[:nf].view(b, l_t - 1, h, w, 2)
         bwd = flow[nf:].view(b, l_t - 1, h, w, 2)
@@ -416,9 +397,10 @@ class Engine(BF16Path):
 
     # ------------------------------------------------------------------ encoder
     def encode(self, frames, join=None):
-        """join: called in front of encoder.layers.<join_at> (16 at one clip: the fork's other branch, SPyNet, overlaps layers 0 .. 14)"""
+        """join: called in front of encoder.layers.<join_at> (16 at one clip: the fork's other branch, SPyNet, overlaps layers 0 .. 14;
+        the bf16 path joins behind the encoder)"""
         b, t, c, H, W = frames.shape
-        x = ops.nchw_to_nhwc(frames.reshape(b * t, c, H, W).contiguous(), ld=4)
+        x = ops.nchw_to_nhwc(frames.reshape(b * t, c, H, W).contiguous(), ld=8 if self.bf16 else 4, out_dtype=self.dtype)
         e = self.enc
         lr = dict(act=ACT_LRELU, slope=0.2)
         x = e[0]([x], **lr)
@@ -426,7 +408,7 @@ class Engine(BF16Path):
         x = e[2]([x], **lr)
         x0 = e[3]([x], **lr)
         x = e[4]([x0], **lr)
-        join_at = JOIN_AT or (16 if b == 1 else 10)
+        join_at = 18 if self.bf16 else (JOIN_AT or (16 if b == 1 else 10))
         joined = join is None
         if not joined and join_at <= 10:
             join()
@@ -440,14 +422,19 @@ class Engine(BF16Path):
 
     # ------------------------------------------------------------------ propagation
     def propagate(self, loc, flows_a, flows_b, inplace=False):
-        """loc: [l_t, b, h, w, 128] frame-major local features.  flows_a / flows_b: NHWC [b,l_t-1,h,w,2]; they are
+        """loc: [l_t, b, h, w, 128] frame-major local features.  flows_a / flows_b: fp32 NHWC [b,l_t-1,h,w,2]; they are
         bound positionally like the reference (e2fgvi.py:249-250): flows_a drives 'backward_', flows_b 'forward_'.
         Returns the propagated features [l_t, b, h, w, 128]; inplace: written over `loc` (the fusion layer's residual is `loc`
         itself: its epilogue reads a residual element and writes the same element in the same thread)."""
         l_t, b, h, w, ch = loc.shape
         dev = loc.device
+        bf16 = self.bf16
         feats = {}
-        zero = self._zero((b, h, w, ch))
+        zero = self._zero((b, h, w, ch), self.dtype)
+        # bf16: the deformable conv gathers from copies of the propagated features re-laid out [group][pixel][16]: the 32-byte runs a
+        # deform group's samples fetch are then adjacent for neighbouring pixels and share cache lines (NHWC: one run per 256-byte
+        # pixel) -- tools/dcn_bench_x.py
+        zero_dcn = self._zero((ch // 16, b, h, w, 16), BF16) if bf16 else zero
         lk = dict(act=ACT_LRELU, slope=0.1)
         # the non-recurrent parts of conv_offset.0 / backbone.0 for the frames of steps 1 .. l_t - 1, all at once (see __init__);
         # step 0 of a direction (backbone only, needed at once) keeps the whole layer
@@ -487,38 +474,44 @@ class Engine(BF16Path):
             sp = self.prop_split.get(name) if split else None
             if sp is not None and name == "forward_":
                 beside([("bb forward_", sp["bb_pre"], [lf, flat(feats["backward_"][1:])])])
-            store = torch.empty((l_t, b, h, w, ch), dtype=torch.float32, device=dev)
+            store = torch.empty((l_t, b, h, w, ch), dtype=self.dtype, device=dev)
             order = list(range(l_t))
             if name == "backward_":
                 order = order[::-1]
             img_stride = (l_t - 1) * h * w * 2
-            hist = []                       # feature tensors in processing order
-            feat_prop = zero
+            hist = []                       # the propagated features in processing order: conv and flow-warp sources
+            hist_dcn = [] if bf16 else hist     # ... and the deformable conv's (bf16: the [group][pixel][16] copies)
+            aligned = zero
             for i, idx in enumerate(order):
                 cur = loc[idx]
                 if i > 0:
                     flow_a = flows[0, i - 1]
                     flow_b = flows[0, i - 2] if i > 1 else None
                     feat_n2 = hist[-2] if i > 1 else None
-                    cond, fl = ops.prop_cond(feat_prop, feat_n2, flow_a, flow_b, img_stride)
+                    if bf16:        # bf16 warped features, and the flows as an 8-channel bf16 source of conv_offset.0
+                        cond, fl, fl_src = ops.prop_cond(hist[-1], feat_n2, flow_a, flow_b, img_stride, cond_dtype=BF16, flows8=True)
+                    else:
+                        cond, fl = ops.prop_cond(hist[-1], feat_n2, flow_a, flow_b, img_stride)
+                        fl_src = fl
                     if sp is not None:
                         slot = idx if name == "backward_" else idx - 1
                         x = sp["off_rec"]([(cond, 0), (cond, ch), fl], residual=partial("off " + name, slot), **lk)
                     else:
-                        x = off_convs[0]([(cond, 0), cur, (cond, ch), fl], **lk)
+                        x = off_convs[0]([(cond, 0), cur, (cond, ch), fl_src], **lk)
                     x = off_convs[1]([x], **lk)
                     x = off_convs[2]([x], **lk)
                     # 10*tanh + flow.flip / sigmoid (feat_prop.py:38-53) applied in the epilogue of the last conv_offset
-                    # layer: the deformable conv then reads finished offsets and masks
-                    offs = off_convs[3]([x], residual=fl, act=ACT_DCNPOST, slope=10.0)
-                    feat_prop = dcn([feat_prop, feat_n2 if feat_n2 is not None else zero], offs)
+                    # layer: the deformable conv then reads finished (fp32) offsets and masks
+                    offs = off_convs[3]([x], out_dtype=torch.float32, residual=fl, act=ACT_DCNPOST, slope=10.0)
+                    aligned = dcn([hist_dcn[-1], hist_dcn[-2] if i > 1 else zero_dcn], offs, out_dtype=self.dtype, planar=bf16)
                 if sp is not None and i > 0:
-                    y = sp["bb_rec"]([feat_prop], residual=partial("bb " + name, idx if name == "backward_" else idx - 1), **lk)
+                    y = sp["bb_rec"]([aligned], residual=partial("bb " + name, idx if name == "backward_" else idx - 1), **lk)
                 else:
-                    srcs = [cur, feats["backward_"][idx], feat_prop] if name == "forward_" else [cur, feat_prop]
+                    srcs = [cur, feats["backward_"][idx], aligned] if name == "forward_" else [cur, aligned]
                     y = bb[0](srcs, **lk)
-                feat_prop = bb[1]([y], residual=feat_prop, out=store[idx])
-                hist.append(feat_prop)
+                hist.append(bb[1]([y], residual=aligned, out=store[idx]))
+                if bf16 and i + 1 < l_t:
+                    hist_dcn.append(ops.to_planar16(store[idx]))
             feats[name] = store
         out = self.fusion([feats["backward_"].view(l_t * b, h, w, ch), feats["forward_"].view(l_t * b, h, w, ch)],
                           residual=loc.view(l_t * b, h, w, ch), out=loc.view(l_t * b, h, w, ch) if inplace else None)
@@ -526,10 +519,11 @@ class Engine(BF16Path):
 
     # ------------------------------------------------------------------ transformer
     def soft_split(self, feat):
-        return self.ss([feat])                               # [b*t, fh, fw, 512]
+        return self.ss([feat], out_dtype=torch.float32)     # [b*t, fh, fw, 512] fp32 tokens
 
-    def block(self, i, x, b, t, fh, fw, hw):
-        """x: [b*t*fh*fw, 512] tokens in (b,t,y,x) order."""
+    def block(self, i, x, b, t, fh, fw, hw, out2=None):
+        """x: fp32 [b*t*fh*fw, 512] tokens in (b,t,y,x) order (the residual stream).  Returns (x_out fp32, attention-branch output
+        fp32).  out2: a bf16 [b*t*fh*fw, 512] buffer that receives a bf16 copy of x_out (the bf16 path's compose() source)."""
         blk = self.blocks[i]
         H, W = hw
         tab, nk = self._table(fh, fw, blk)
@@ -537,10 +531,13 @@ class Engine(BF16Path):
         # (and one buffer resource in the attention kernel)
         rows = x.shape[0]
         prow = b * t * (fh // 5) * (fw // 9)
-        nbuf = torch.empty((rows + prow, 512), dtype=torch.float32, device=x.device)
+        nbuf = torch.empty((rows + prow, 512), dtype=self.dtype, device=x.device)
         n1 = ops.layernorm(x, blk["n1w"], blk["n1b"], out=nbuf[:rows])
         ops.window_pool(n1, blk["pool_w"], blk["pool_b"], b * t, fh, fw, out=nbuf[rows:])
-        if ops.attention_x3_applies(b, t, fh, fw):
+        if self.bf16:
+            both = blk["qkv"](nbuf)                                   # bf16 [rows + prow, 1536]
+            att = ops.focal_attention_bf16(both[:rows], both[rows:], tab, nk, b, t, fh, fw)
+        elif ops.attention_x3_applies(b, t, fh, fw):
             # both products on the bf16 matrix pipe (exactly split operands).  The k / v columns of all rows as three bf16 planes:
             # written by the qkv GEMM's epilogue when the split-operand GEMM runs it (round 5: no separate pass over the rows, and
             # the fp32 K / V columns are never stored), by e2fgvi_split3_kv otherwise (ops.PackedConv.__call__, kv_planes)
@@ -550,21 +547,26 @@ class Engine(BF16Path):
         else:
             both = blk["qkv"](nbuf)
             att = ops.focal_attention(both[:rows], both[rows:], tab, nk, b, t, fh, fw)
-        x1 = blk["proj"](att, residual=x)
-        n2 = ops.layernorm(x1, blk["n2w"], blk["n2b"])
+        x1 = blk["proj"](att, out_dtype=torch.float32, residual=x)
+        n2 = ops.layernorm(x1, blk["n2w"], blk["n2b"], out_dtype=self.dtype)
         hid = blk["fc1"](n2)
         # GELU in front of the unfold (a gather with zero padding: GELU commutes with it, 5.4x fewer erf evaluations)
         folded = ops.ffn_fold_gelu(hid, b * t, fh, fw, H, W, 40)
         if isinstance(blk["fc2"], PackedConvX):
-            y = torch.empty((x1.shape[0], 512), dtype=torch.float32, device=x1.device)
-            blk["fc2"]([folded], out=y.view(b * t, fh, fw, 512), residual=x1.view(b * t, fh, fw, 512))
+            y = torch.empty((rows, 512), dtype=torch.float32, device=x.device)
+            blk["fc2"]([folded], out=y.view(b * t, fh, fw, 512), residual=x1.view(b * t, fh, fw, 512),
+                       out2=None if out2 is None else out2.view(b * t, fh, fw, 512))
             return y, x1
         unf = ops.ffn_unfold(folded, fh, fw, out=hid)
         return blk["fc2"](unf, residual=x1), x1
 
     def compose(self, tokens, enc, b, t, fh, fw):
-        """SoftComp + residual with the encoder features (tfocal_transformer.py:65-72, e2fgvi.py:258)."""
+        """SoftComp + residual with the encoder features (tfocal_transformer.py:65-72, e2fgvi.py:258).  tokens: in the
+        activations' dtype."""
         _, h, w, ch = enc.shape
+        if self.sc_gather is not None and (h, w) == (3 * fh, 3 * fw):
+            folded = self.sc_gather(tokens.view(b * t, fh, fw, 512))
+            return self.sc_bias_conv([folded], residual=enc)
         emb = self.sc(tokens)
         if self.hq:
             folded = ops.softcomp_fold(emb, b * t, fh, fw, h, w, ch)
@@ -581,10 +583,11 @@ class Engine(BF16Path):
         x = d[1]([x], **lr)
         x = ops.resize_bilinear(x, (4 * h, 4 * w), True)
         x = d[2]([x], **lr)
-        return d[3]([x], act=ACT_TANH, out_nchw=True)
+        return d[3]([x], act=ACT_TANH, out_nchw=True)             # 64 -> 3, tanh, fp32 NCHW frames
 
-    # ------------------------------------------------------------------ whole forward
+    # ------------------------------------------------------------------ whole forward (e2fgvi_hq.py:235-263)
     def forward(self, frames, l_t, trace=None):
+        """trace: a dict that receives fp32 copies of the stage outputs (flows, encoder, propagation, tokens, decoder input)"""
         b, t, c, H, W = frames.shape
         if H % 4 or W % 4:
             raise ValueError("H and W must be multiples of 4")
@@ -598,8 +601,6 @@ class Engine(BF16Path):
         if not (1 <= l_t <= t):
             raise ValueError("num_local_frames must be in [1, t]")
         frames = ops._chk(frames.float().contiguous(), "masked_frames")
-        if self.bf16:
-            return self.forward_x(frames, l_t, b, t, h, w, fh, fw, trace)
         if self._given is not None:
             (fwd, bwd), enc = self._given
         elif l_t == 1:
@@ -621,13 +622,13 @@ class Engine(BF16Path):
             enc = self.encode(frames)
         ch = enc.shape[3]
         if trace is not None:
-            trace["flow_fwd"], trace["flow_bwd"], trace["enc"] = fwd, bwd, enc.clone()
+            trace["flow_fwd"], trace["flow_bwd"], trace["enc"] = fwd, bwd, enc.to(torch.float32, copy=True)
         enc5 = enc.view(b, t, h, w, ch)
         if b == 1:
             loc = enc5[0, :l_t].unsqueeze(1)                 # view: [l_t, 1, h, w, C]
-            # one clip: the local frames are a view of the encoder output and the propagated features replace them in place (no
-            # 33 MB copy; under E2FGVI_AUTOTUNE=1 the fusion layer writes a fresh tensor so that its candidates can be timed)
-            inplace = not ops.AUTOTUNE
+            # one clip, fp32: the local frames are a view of the encoder output and the propagated features replace them in place
+            # (no 33 MB copy; under E2FGVI_AUTOTUNE=1 the fusion layer writes a fresh tensor so that its candidates can be timed)
+            inplace = not (ops.AUTOTUNE or self.bf16)
             prop = self.propagate(loc, fwd, bwd, inplace=inplace)
             if not inplace:
                 enc5[0, :l_t].copy_(prop[:, 0])
@@ -636,18 +637,21 @@ class Engine(BF16Path):
             prop = self.propagate(loc, fwd, bwd)
             enc5[:, :l_t].copy_(prop.permute(1, 0, 2, 3, 4))
         if trace is not None:
-            trace["prop"] = enc.clone()
+            trace["prop"] = enc.to(torch.float32, copy=True)
         tok = self.soft_split(enc).view(b * t * fh * fw, 512)
         if trace is not None:
             trace["tokens0"] = tok.clone()
+        tok16 = None
         for i in range(8):
-            tok, x1 = self.block(i, tok, b, t, fh, fw, (h, w))
+            if self.bf16 and i == 7:        # the bf16 path's compose() reads a bf16 copy of the last block's tokens
+                tok16 = torch.empty((b * t * fh * fw, 512), dtype=BF16, device=tok.device)
+            tok, x1 = self.block(i, tok, b, t, fh, fw, (h, w), out2=tok16)
             if trace is not None:
                 trace["block%d_attn_out" % i] = x1
                 trace["tokens%d" % (i + 1)] = tok
-        dec_in = self.compose(tok, enc, b, t, fh, fw)
+        dec_in = self.compose(tok if tok16 is None else tok16, enc, b, t, fh, fw)
         if trace is not None:
-            trace["dec_in"] = dec_in
+            trace["dec_in"] = dec_in.float()
         out = self.decode(dec_in)
         if l_t == 1:
             empty = torch.empty((b, 0, 2, h, w), dtype=torch.float32, device=out.device)

@@ -423,11 +423,14 @@ class PackedConv:
             N, H, W, cin_g * self.groups, self.Cout, self.KH, self.stride, self.groups), macs=macs, issued=issued)
 
     def __call__(self, sources, out=None, out_coff=0, residual=None, res_coff=0, act=ACT_NONE, slope=0.0,
-                 out_nchw=False, tile=0, kv_planes=None):
+                 out_nchw=False, tile=0, kv_planes=None, out_dtype=None):
         """sources: list of NHWC tensors or (tensor, channel_offset) pairs, one per cpg entry.
+        out_dtype: None or torch.float32 (the keyword of PackedConvX, so that callers pass the same ones to both).
         kv_planes (a qkv Linear, Cout = 1536): [3, rows, 1024] bf16 -- the K / V columns as the three exact planes the split-operand
         attention reads.  When the decision table hands the call to the split-operand GEMM its epilogue writes them (and skips the
         fp32 K / V columns); any other kernel writes the fp32 rows and e2fgvi_split3_kv makes the planes from them."""
+        if out_dtype not in (None, torch.float32):
+            raise ValueError("PackedConv writes fp32 results")
         lib = _L.load()
         d = _L.ConvDesc()
         srcs = [(s, 0) if isinstance(s, torch.Tensor) else s for s in sources]
@@ -993,7 +996,9 @@ class PackedLinear(PackedConv):
     def __init__(self, weight, bias, bk=None, precision="fp32"):
         super().__init__(weight, bias, [weight.shape[1]], bk=bk, precision=precision)
 
-    def __call__(self, x, out=None, residual=None, act=ACT_NONE, slope=0.0, tile=0, kv_planes=None):
+    def __call__(self, x, out=None, residual=None, act=ACT_NONE, slope=0.0, tile=0, kv_planes=None, out_dtype=None):
+        if out_dtype not in (None, torch.float32):
+            raise ValueError("PackedLinear writes fp32 results")
         _chk(x, "x")
         rows = x.numel() // x.shape[-1]
         x4 = x.view(rows, 1, 1, x.shape[-1])

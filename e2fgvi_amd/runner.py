@@ -176,7 +176,7 @@ class ShardedStep:
         with torch.cuda.graph(gf, stream=side, capture_error_mode="thread_local"):
             flows = eng.flows(self.x, self.lt)
         with torch.cuda.graph(ga, stream=s, capture_error_mode="thread_local"):
-            enc = eng.encode_any(self.x)
+            enc = eng.encode(self.x)
         eng._given = (flows, enc)
         try:
             with torch.cuda.graph(gb, stream=s, pool=ga.pool(), capture_error_mode="thread_local"):

@@ -3,7 +3,7 @@ product-side rewrite replaces a reference expression by an equal one, and these 
 
   * FusionFeedForward (model/modules/tfocal_transformer.py:75-99): Linear(1960 -> 512) applied to nn.Unfold(7, stride 3,
     padding 3) of the folded tensor == a 7x7 / stride-3 / pad-3 convolution of that tensor with the same weights viewed
-    [512, 40, 7, 7] (engine_x.py runs it that way: no unfold kernel, no [rows, 1960] tensor);
+    [512, 40, 7, 7] (engine.py runs it that way: no unfold kernel, no [rows, 1960] tensor);
   * GELU applied before the unfold == after it (the unfold is a gather with zero padding and GELU(0) = 0);
   * the decoder's Conv2d(64, 3, 3, padding=1) (model/e2fgvi.py:99-103) == one [pixels x 64] x [64 x 27] product followed
     by a shifted nine-term sum (csrc/conv_tail.hip)."""

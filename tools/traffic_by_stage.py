@@ -41,7 +41,6 @@ def workload(a):
     b, t = 1, a.t
     h, w = H // 4, W // 4
     fh, fw = token_grid(h, w)
-    bf16 = a.precision == "bf16"
 
     def mark():
         torch.arange(17, device=dev)
@@ -50,29 +49,26 @@ def workload(a):
         mark()
         fwd, bwd = eng.flows(x, lt)
         mark()
-        enc = eng.encode_x(x) if bf16 else eng.encode(x)
+        enc = eng.encode(x)
         mark()
         ch = enc.shape[3]
         enc5 = enc.view(b, t, h, w, ch)
         loc = enc5[0, :lt].unsqueeze(1)
-        if bf16:
-            prop = eng.propagate_x(loc, fwd, bwd)
+        prop = eng.propagate(loc, fwd, bwd, inplace=not eng.bf16)     # as Engine.forward: bf16 writes a fresh tensor
+        if eng.bf16:
             enc5[0, :lt].copy_(prop[:, 0])
-        else:
-            eng.propagate(loc, fwd, bwd, inplace=True)
         mark()
-        tok = (eng.xss([enc], out_dtype=torch.float32) if bf16 else eng.soft_split(enc)).view(b * t * fh * fw, 512)
+        tok = eng.soft_split(enc).view(b * t * fh * fw, 512)
         mark()
         tok16 = None
         for i in range(8):
-            if bf16:
-                tok, _, tok16 = eng.block_x(i, tok, b, t, fh, fw, (h, w), want_bf16_copy=(i == 7))
-            else:
-                tok, _ = eng.block(i, tok, b, t, fh, fw, (h, w))
+            if eng.bf16 and i == 7:
+                tok16 = torch.empty((b * t * fh * fw, 512), dtype=torch.bfloat16, device=dev)
+            tok, _ = eng.block(i, tok, b, t, fh, fw, (h, w), out2=tok16)
             mark()
-        dec_in = eng.compose_x(tok16, enc, b, t, fh, fw) if bf16 else eng.compose(tok, enc, b, t, fh, fw)
+        dec_in = eng.compose(tok if tok16 is None else tok16, enc, b, t, fh, fw)
         mark()
-        out = eng.decode_x(dec_in) if bf16 else eng.decode(dec_in)
+        out = eng.decode(dec_in)
         mark()
         torch.cuda.synchronize()
     print("frames", tuple(out.shape), float(out.abs().mean()))
