@@ -12,9 +12,13 @@ configuration that maximises propagation work), inputs already 
                      `--gpus 1 --clips-per-gpu 8`, not the 1-clip default of N = 1.
     --model e2fgvi_hq --hw 720x1296 --precision bf16      BASELINE.json configs[3] (and [4] with --hw 1080x1944 --t 20)
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the headline
+(`value`, `ms_per_step`, the configuration, memory).  Everything else the benchmark measures or checks runs only with --full:
+the FLOP trace and roofline (`config.kernels`, `roofline`, the dominant-kernel probe, PMC traffic), the one-at-a-time
+`sequential` number, `single_gpu_same_work`, the CPU baseline with its `parity` against the oracle, and the `secondary` lines.
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --full                      # the whole record: roofline, sequential, cpu_baseline, parity, secondary
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port P \\
         bench.py --gpus 8 --steps 20 --warmup 3
 """
@@ -375,23 +379,26 @@ def main():
     ap.add_argument("--t", type=int, default=10)
     ap.add_argument("--lt", type=int, default=0, help="local frames (default: all t)")
     ap.add_argument("--gather", default="u8", choices=("u8", "f32"), help="dtype of the frames in the all-gather")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: FLOP trace and roofline, the dominant-kernel "
+                         "probe, `sequential` / `single_gpu_same_work`, the CPU baseline with its parity, the `secondary` lines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and its parity")
     ap.add_argument("--no-graph", action="store_true", help="disable HIP-graph replay of the forward")
     ap.add_argument("--in-flight", type=int, default=0,
                     help="forwards in flight on one GPU (runner.ShardedStep(in_flight=K): K HIP graphs of the same one-clip forward "
                          "replayed round-robin on K streams -- step n + 1 starts while step n is in its latency-bound propagation "
                          "chain; every step returns the bits of the sequential forward).  Default: 2 on a single GPU without a "
-                         "gather (the line then also carries `sequential`: one graph replayed back to back, rounds 1-5's headline "
-                         "mode, timed in the same process), 1 with a gather (N > 1 / --force-dist)")
+                         "gather (with --full the line then also carries `sequential`: one graph replayed back to back, rounds "
+                         "1-5's headline mode, timed in the same process), 1 with a gather (N > 1 / --force-dist)")
     ap.add_argument("--force-dist", action="store_true", help="initialise RCCL and run the gather even with one rank (self-test)")
     ap.add_argument("--no-dominant-probe", action="store_true",
-                    help="skip the 21 extra launches of encoder.layers.10 behind the timed region (PMC passes count whole processes: "
+                    help="with --full: skip the 21 extra launches of encoder.layers.10 behind the timed region (PMC passes count whole processes: "
                          "tools/pmc.sh divides by the number of forwards)")
     ap.add_argument("--launcher", action="store_true",
                     help="start the ranks through torch.distributed.run even for one GPU (the N > 1 launch path, testable on one GPU)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the BASELINE configs[3] / [4] lines (e2fgvi_hq 720x1296 T=10 and 1080x1944 T=20, bf16) that the "
-                         "default single-GPU invocation times after the headline and attaches as `secondary`")
+                    help="with --full: skip the lines (BASELINE configs[3] / [4] among them) that the default single-GPU "
+                         "configuration times after the headline and attaches as `secondary`")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the frames the last timed step returned to DIR/frames.npy (float32; "
                          "all ranks' frames when gathering, rank 0 writes); above %d MB a fixed, seeded sample of them goes to "
@@ -442,15 +449,16 @@ def main():
     net(x, lt)
     torch.cuda.synchronize()
     want_in_flight = 1 if (world > 1 or args.force_dist or args.no_graph) else (args.in_flight or 2)
-    if want_in_flight > 1:
+    # --full: one more eager forward with launch tracing, for `roofline` and `config.kernels`
+    if args.full and want_in_flight > 1:
         with runner.whole_propagation(net):                         # what the pipelines' graphs run (runner.ShardedStep._pipeline_setup)
             gflop_alg, gflop_issued, nlaunch = traced_work(net, x, lt)
-    else:
+    elif args.full:
         gflop_alg, gflop_issued, nlaunch = traced_work(net, x, lt)      # per forward of b clips
     gflop_useful = USEFUL_GFLOP
     kernels = dict(KERNELS)
     same_work = None
-    if world > 1 or args.force_dist:
+    if args.full and (world > 1 or args.force_dist):
         # the like-for-like single-GPU number of this job's per-GPU work: the same clips, the same HIP-graph replay, no
         # collective, timed on this GPU before RCCL comes up (a scaling efficiency can then be read off ONE record)
         sw_steps = max(3, min(args.steps, 10))
@@ -477,7 +485,7 @@ def main():
     # the forward replays from a HIP graph in every mode; the collective stays outside the graph (runner.ShardedStep)
     in_flight = 1 if (dist is not None or args.no_graph) else (args.in_flight or 2)
     sequential = None
-    if in_flight > 1:
+    if args.full and in_flight > 1:
         # rounds 1-5's headline mode on this box, in this process: ONE graph replayed back to back
         sq_steps = max(5, min(args.steps, 20))
         el, _, _ = time_local(net, x, lt, sq_steps, 3)
@@ -519,12 +527,7 @@ def main():
     frames = world * b * t * args.steps
     value = frames / elapsed
     ms_per_step = 1e3 * elapsed / args.steps
-    peak = PEAK_TFLOPS[args.precision]
-    analytic = b * flops_per_clip(H, W, t, lt, hq)
-    secs = dev_ms * 1e-3 / args.steps
-    tf_alg, tf_iss = gflop_alg / secs / 1e3, gflop_issued / secs / 1e3          # this rank, device-timed
     arith = "bf16" if args.precision == "bf16" else ("fp32+x3" if ops.X3_ENABLED else "fp32")
-    eff_peak = EFFECTIVE_PEAK[arith]
     config_no = 2 if (world == 1 and b == 1) else 3
     if hq:
         config_no = 4 if t <= 10 else 5
@@ -538,72 +541,79 @@ def main():
                                % (config_no - 1, args.model, W, H, t, lt, b, b * world),
                    "clips_per_gpu": b, "precision": args.precision,
                    "arithmetic": ARITHMETIC[arith],
-                   "kernels": kernels,
                    "kernel_selection": ("timed on this box (E2FGVI_AUTOTUNE=1)" if ops.AUTOTUNE else
                                         "e2fgvi_amd/tile_table.py (checked in, deterministic: ops.py)"),
                    "parallelism": "clip-shard x%d + all-gather of the %s frames" % (world, args.gather) if dist is not None
                                   else ("single GPU, no collective" + ("; %d forwards in flight (that many HIP graphs of the one-clip "
-                                        "forward replayed round-robin on as many streams, bit-identical steps; `sequential` = one at a time)"
-                                        % step.in_flight if step.in_flight > 1 else "")),
+                                        "forward replayed round-robin on as many streams, bit-identical steps%s)"
+                                        % (step.in_flight, "; `sequential` = one at a time" if args.full else "")
+                                        if step.in_flight > 1 else "")),
                    "hip_graph": bool(step.graphed), "forwards_in_flight": step.in_flight},
-        "roofline": {"bound": "mfma", "achieved": round(tf_iss, 3), "peak": peak, "unit": "TFLOP/s",
-                     "frac": round(tf_iss / peak, 4), "frac_useful": round(gflop_useful / secs / 1e3 / peak, 4),
-                     "achieved_algorithmic": round(tf_alg, 3), "effective_peak": round(eff_peak, 1),
-                     "frac_effective": round(tf_alg / eff_peak, 4),
-                     "gflop_per_forward": {"algorithmic": round(gflop_alg, 1), "issued": round(gflop_issued, 1),
-                                           "useful": round(gflop_useful, 1),
-                                           "analytic_survey_8d": round(analytic, 1), "mfma_launches": nlaunch},
-                     "traffic": None,
-                     "note": "whole forward, device time of one forward (hip events on the launch stream). `achieved` / `frac` count "
-                             "the FLOPs ISSUED to the matrix pipe (the Winograd F(2x2,3x3) layers issue 16/36 of their direct-"
-                             "convolution multiplies, plus block / channel padding: per-launch accounting of ops.PackedConv._work), "
-                             "`frac_useful` the same without the tile / channel padding (lib.useful_macs).  fp32 layers that run on "
-                             "the bf16 matrix pipe with exactly split operands (six bf16 MFMA terms per fp32 product, fp32-level "
-                             "rounding: tests/test_gpu_x3.py) are counted in fp32-MFMA equivalents (bf16 MACs x 157.3 / 2500), so "
-                             "`frac` is the share of the time the matrix pipe is busy at its peak rate (what rocprofv3's "
-                             "SQ_VALU_MFMA_BUSY_CYCLES measures).  `achieved_algorithmic` counts the reference's direct-convolution "
-                             "FLOPs (SURVEY.md 8d); `frac_effective` prices them against `effective_peak`, the rate at which the "
-                             "matrix pipe can retire fp32 products in this arithmetic (157.3 TF as fp32 MFMA, 2500 / 6 = 416.7 TF as "
-                             "six bf16 terms, 2500 TF on the bf16 data path) -- Winograd's saved multiplies count in its favour, "
-                             "so it is an efficiency against the direct algorithm, not a pipe utilisation"},
     }
-    # HBM-side traffic of one forward: rocprofv3 PMC passes (tools/pmc.sh) cannot run inside the timed process; the summary of the
-    # last collection is committed under profiles/ TOGETHER WITH the key of the library it measured (lib.library_key()), and it is
-    # quoted here only when that key is the key of the library this process has just timed -- a figure of an older library is
-    # named in the note and NOT reported as this tree's traffic (round 4's line carried round 3's number)
-    from e2fgvi_amd import lib as _lib
-    lib_key = _lib.library_key()
-    out["library_sha16"] = lib_key
-    traffic_cfg = None
-    if b == 1 and (t, lt) == (10, 10) and not hq and args.precision == "fp32":
-        traffic_cfg = ""
-    elif b == 1 and (t, lt) == (10, 10) and hq and (H, W) == (720, 1296) and args.precision == "bf16":
-        traffic_cfg = "_hq720_bf16"
-    elif b == 1 and (t, lt) == (20, 20) and hq and (H, W) == (1080, 1944) and args.precision == "bf16":
-        traffic_cfg = "_hq1080_bf16"
-    if traffic_cfg is not None:
-        import glob
-        stale = []
-        for tfile in sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]_hbm_traffic%s.json" % traffic_cfg)), reverse=True):
-            try:
-                tj = json.load(open(tfile))
-            except Exception:
-                continue
-            if tj.get("library_sha16") != lib_key:
-                stale.append(os.path.basename(tfile))
-                continue
-            out["roofline"]["traffic"] = round(tj["hbm_bytes_per_forward"])
-            out["roofline"]["traffic_note"] = ("FETCH_SIZE x2 (gfx950 correction) + WRITE_SIZE per forward, rocprofv3 --pmc, separate "
-                                               "passes (profiles/%s, measured on this library: sha16 %s); fabric-side, includes Infinity-"
-                                               "Cache hits; compulsory minimum (input + weights + output) is %s GB/clip; counted on eager one-at-a-time forwards "
-                                               "(PMC passes serialise the kernels), the same kernels the in-flight graphs replay"
-                                               % (os.path.basename(tfile), lib_key, "0.19" if not hq else "0.39"))
-            break
-        else:
-            out["roofline"]["traffic_note"] = ("no PMC collection of this library (sha16 %s) under profiles/: bash tools/pmc.sh <tag>; "
-                                               "collections of other builds, not quoted: %s" % (lib_key, ", ".join(stale) or "none"))
+    if args.full:
+        out["config"]["kernels"] = kernels
+        peak = PEAK_TFLOPS[args.precision]
+        analytic = b * flops_per_clip(H, W, t, lt, hq)
+        secs = dev_ms * 1e-3 / args.steps
+        tf_alg, tf_iss = gflop_alg / secs / 1e3, gflop_issued / secs / 1e3          # this rank, device-timed
+        eff_peak = EFFECTIVE_PEAK[arith]
+        out["roofline"] = {"bound": "mfma", "achieved": round(tf_iss, 3), "peak": peak, "unit": "TFLOP/s",
+                           "frac": round(tf_iss / peak, 4), "frac_useful": round(gflop_useful / secs / 1e3 / peak, 4),
+                           "achieved_algorithmic": round(tf_alg, 3), "effective_peak": round(eff_peak, 1),
+                           "frac_effective": round(tf_alg / eff_peak, 4),
+                           "gflop_per_forward": {"algorithmic": round(gflop_alg, 1), "issued": round(gflop_issued, 1),
+                                                 "useful": round(gflop_useful, 1),
+                                                 "analytic_survey_8d": round(analytic, 1), "mfma_launches": nlaunch},
+                           "traffic": None,
+                           "note": "whole forward, device time of one forward (hip events on the launch stream). `achieved` / `frac` count "
+                                   "the FLOPs ISSUED to the matrix pipe (the Winograd F(2x2,3x3) layers issue 16/36 of their direct-"
+                                   "convolution multiplies, plus block / channel padding: per-launch accounting of ops.PackedConv._work), "
+                                   "`frac_useful` the same without the tile / channel padding (lib.useful_macs).  fp32 layers that run on "
+                                   "the bf16 matrix pipe with exactly split operands (six bf16 MFMA terms per fp32 product, fp32-level "
+                                   "rounding: tests/test_gpu_x3.py) are counted in fp32-MFMA equivalents (bf16 MACs x 157.3 / 2500), so "
+                                   "`frac` is the share of the time the matrix pipe is busy at its peak rate (what rocprofv3's "
+                                   "SQ_VALU_MFMA_BUSY_CYCLES measures).  `achieved_algorithmic` counts the reference's direct-convolution "
+                                   "FLOPs (SURVEY.md 8d); `frac_effective` prices them against `effective_peak`, the rate at which the "
+                                   "matrix pipe can retire fp32 products in this arithmetic (157.3 TF as fp32 MFMA, 2500 / 6 = 416.7 TF as "
+                                   "six bf16 terms, 2500 TF on the bf16 data path) -- Winograd's saved multiplies count in its favour, "
+                                   "so it is an efficiency against the direct algorithm, not a pipe utilisation"}
+        # HBM-side traffic of one forward: rocprofv3 PMC passes (tools/pmc.sh) cannot run inside the timed process; the summary of the
+        # last collection is committed under profiles/ TOGETHER WITH the key of the library it measured (lib.library_key()), and it is
+        # quoted here only when that key is the key of the library this process has just timed -- a figure of an older library is
+        # named in the note and NOT reported as this tree's traffic (round 4's line carried round 3's number)
+        from e2fgvi_amd import lib as _lib
+        lib_key = _lib.library_key()
+        out["library_sha16"] = lib_key
+        traffic_cfg = None
+        if b == 1 and (t, lt) == (10, 10) and not hq and args.precision == "fp32":
+            traffic_cfg = ""
+        elif b == 1 and (t, lt) == (10, 10) and hq and (H, W) == (720, 1296) and args.precision == "bf16":
+            traffic_cfg = "_hq720_bf16"
+        elif b == 1 and (t, lt) == (20, 20) and hq and (H, W) == (1080, 1944) and args.precision == "bf16":
+            traffic_cfg = "_hq1080_bf16"
+        if traffic_cfg is not None:
+            import glob
+            stale = []
+            for tfile in sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]_hbm_traffic%s.json" % traffic_cfg)), reverse=True):
+                try:
+                    tj = json.load(open(tfile))
+                except Exception:
+                    continue
+                if tj.get("library_sha16") != lib_key:
+                    stale.append(os.path.basename(tfile))
+                    continue
+                out["roofline"]["traffic"] = round(tj["hbm_bytes_per_forward"])
+                out["roofline"]["traffic_note"] = ("FETCH_SIZE x2 (gfx950 correction) + WRITE_SIZE per forward, rocprofv3 --pmc, separate "
+                                                   "passes (profiles/%s, measured on this library: sha16 %s); fabric-side, includes Infinity-"
+                                                   "Cache hits; compulsory minimum (input + weights + output) is %s GB/clip; counted on eager one-at-a-time forwards "
+                                                   "(PMC passes serialise the kernels), the same kernels the in-flight graphs replay"
+                                                   % (os.path.basename(tfile), lib_key, "0.19" if not hq else "0.39"))
+                break
+            else:
+                out["roofline"]["traffic_note"] = ("no PMC collection of this library (sha16 %s) under profiles/: bash tools/pmc.sh <tag>; "
+                                                   "collections of other builds, not quoted: %s" % (lib_key, ", ".join(stale) or "none"))
     if rank == 0:
-        if not hq and args.precision == "fp32" and not args.no_dominant_probe:
+        if args.full and not hq and args.precision == "fp32" and not args.no_dominant_probe:
             dom = runner.dominant_kernel_probe(net, dev)
             dom["traffic"] = None
             # PMC traffic of the kernel that runs: the newest profiles/*dominant_kernel_traffic*.json whose kernel_tag is this
@@ -626,7 +636,7 @@ def main():
             # packed weights the layers hold after the timed run (each layer packs what the kernels it runs need) next to the checkpoint
             out["weight_memory_gb"] = {"packed": round(eng.weight_bytes() / 2 ** 30, 3),
                                        "checkpoint_fp32": round(sum(p.numel() * 4 for p in net.parameters()) / 2 ** 30, 3)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # the frames of the timed configuration (clip 0 of this rank = the oracle's clip: synth_clip seed 0), computed by the
             # very engine / kernel decisions / HIP graph that were timed
             hip_frames = step.finish()
@@ -650,12 +660,13 @@ def main():
         out["single_gpu_same_work"] = same_work
     if sequential is not None:
         out["sequential"] = sequential
+    if in_flight > 1:
         out["config"]["stream_window"] = getattr(step, "stream_window", None)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
     default_headline = (world == 1 and not args.force_dist and not hq and args.precision == "fp32" and b == 1 and (t, lt) == (10, 10))
-    if rank == 0 and default_headline and not args.no_secondary:
+    if rank == 0 and default_headline and args.full and not args.no_secondary:
         del step, net, x
         torch.cuda.empty_cache()
         out["secondary"] = []

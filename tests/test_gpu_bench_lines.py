@@ -1,7 +1,7 @@
-"""bench.py's contract on the GPU box, as subprocesses (what the driver runs): the default single-GPU line carries the
-BASELINE configs[3] / [4] lines as `secondary`; the N > 1 flow -- RCCL process group, HIP-graph replay, uint8 all-gather
-pipelined under the next forward, 8 clips per GPU (BASELINE configs[2]'s per-GPU work) -- runs here with world size 1
-(--force-dist) and reports the like-for-like single-GPU number of the same work."""
+"""bench.py's contract on the GPU box, as subprocesses (what the driver runs): a plain run prints the headline alone; with
+--full the default single-GPU line carries the BASELINE configs[3] / [4] lines as `secondary`; the N > 1 flow -- RCCL process
+group, HIP-graph replay, uint8 all-gather pipelined under the next forward, 8 clips per GPU (BASELINE configs[2]'s per-GPU
+work) -- runs here with world size 1 (--force-dist) and reports the like-for-like single-GPU number of the same work."""
 import json
 import os
 import subprocess
@@ -38,17 +38,33 @@ def _fracs(node, path=""):
             yield from _fracs(v, "%s[%d]" % (path, i))
 
 
+def test_plain_run_prints_the_headline_alone(dev, tmp_path):
+    """`python bench.py --gpus 1 --steps N --warmup W`: the headline fields, the dumped frames of the last timed step, and none
+    of what --full adds (no FLOP trace, no `sequential`, no CPU baseline, no `secondary`)"""
+    import numpy as np
+    j = _bench("--gpus", "1", "--steps", "4", "--warmup", "2", "--dump-outputs", str(tmp_path))
+    assert j["metric"] == "inpainted frames/sec at 432x240 T=10" and j["unit"] == "frames/s" and j["higher_is_better"] is True
+    assert j["dtype"] == "f32" and j["steps"] == 4 and j["warmup"] == 2 and j["value"] > 30
+    assert abs(j["value"] - 10 * 4 / (j["ms_per_step"] * 4e-3)) <= 1e-2 * j["value"]
+    assert j["config"]["forwards_in_flight"] == 2 and j["config"]["hip_graph"] is True and j["config"]["stream_window"]
+    for k in ("roofline", "sequential", "cpu_baseline", "parity", "secondary", "single_gpu_same_work", "library_sha16"):
+        assert k not in j, k
+    assert "kernels" not in j["config"]
+    frames = np.load(os.path.join(str(tmp_path), "frames.npy"))
+    assert frames.shape == (10, 3, 240, 432) and frames.dtype == np.float32 and np.isfinite(frames).all()
+
+
 def test_plain_gpus_flag_launches_the_ranks_itself(dev):
     """`python bench.py --gpus N` with no launcher around it (the driver's 8-GPU form minus torch.distributed.run) must start its
     own ranks: --launcher takes the same path with one GPU (torch.distributed.run -> one rank, RCCL group, gather, JSON line)"""
-    j = _bench("--gpus", "1", "--launcher", "--clips-per-gpu", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline")
+    j = _bench("--gpus", "1", "--launcher", "--clips-per-gpu", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline")
     assert j["n_gpus"] == 1 and j["config"]["clips_per_gpu"] == 2 and "all-gather" in j["config"]["parallelism"]
     assert j["single_gpu_same_work"]["value"] > 0 and j["value"] > 30
 
 
 def test_multi_gpu_flow_with_one_rank(dev):
     """config 3's per-GPU flow: `bench.py --force-dist --clips-per-gpu 8`"""
-    j = _bench("--force-dist", "--clips-per-gpu", "8", "--steps", "3", "--warmup", "1", "--no-cpu-baseline")
+    j = _bench("--force-dist", "--clips-per-gpu", "8", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline")
     assert j["n_gpus"] == 1 and j["unit"] == "frames/s" and j["scaling"] == "weak" and j["dtype"] == "f32"
     assert j["config"]["clips_per_gpu"] == 8 and j["config"]["hip_graph"] is True
     assert "all-gather of the u8 frames" in j["config"]["parallelism"]
@@ -61,10 +77,10 @@ def test_multi_gpu_flow_with_one_rank(dev):
 
 
 def test_default_line_carries_the_hq_configs(dev):
-    """`python bench.py` (what the driver records): headline fields incl. its own arithmetic tag and kernel map, and `secondary` =
+    """`python bench.py --full`: headline fields incl. its own arithmetic tag and kernel map, and `secondary` =
     the pure fp32-MFMA configuration (E2FGVI_X3=0), SURVEY.md 8(d)'s second split (T=10, l_t=5), config 3's per-GPU work on one
     GPU (8 clips), e2fgvi_hq 720x1296 T=10 and 1080x1944 T=20 in bf16"""
-    j = _bench("--steps", "3", "--warmup", "1", "--no-cpu-baseline")
+    j = _bench("--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline")
     assert j["metric"].startswith("inpainted frames/sec at 432x240 T=10") and j["dtype"] == "f32" and j["value"] > 30
     assert j["roofline"]["bound"] == "mfma" and 0 < j["roofline"]["frac"] < 1
     # round 6: no fraction above 1 anywhere on the line (round 5 printed direct-convolution FLOPs over the fp32 peak as a `frac_*`)
@@ -104,7 +120,7 @@ def test_default_line_carries_the_hq_configs(dev):
 def test_bench_line_carries_its_own_parity(dev):
     """with the CPU baseline on, the line compares the frames of the TIMED configuration with the oracle's on the same clip
     (`parity`), and bench.py exits non-zero above the north-star bound"""
-    j = _bench("--steps", "3", "--warmup", "1", "--no-secondary")
+    j = _bench("--steps", "3", "--warmup", "1", "--full", "--no-secondary")
     p = j["parity"]
     assert p["bound_max_abs"] == 1e-3 and 0 <= p["max_abs"] <= 1e-3 and p["max_abs_over_rms"] <= 2e-3, p
     # round 5: the default-init weights (conv_offset[-1] == 0: offsets = flow, mask = 0.5) AND the stress weights

@@ -6,7 +6,7 @@ OUT=gpurun_out/driver_$TAG
 mkdir -p $OUT
 timeout 1200 python -m pytest tests/ -x -q -m gpu > $OUT/pytest.log 2>&1; echo "pytest rc=$? : $(grep -a -E "passed|failed" $OUT/pytest.log | tail -1)"
 timeout 600 python -c "import __graft_entry__ as g; g.smoke(); print('__SMOKE_OK__')" > $OUT/smoke.log 2>&1; echo "smoke rc=$? : $(grep -a "smoke:" $OUT/smoke.log | tail -1)"
-timeout 900 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+timeout 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
 python - "$OUT" <<'PY'
 import json, sys
 j = json.loads(open(sys.argv[1] + "/bench.json").read().strip().splitlines()[-1])

@@ -10,7 +10,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 # kernel selection is the checked-in table (e2fgvi_amd/tile_table.py): the counted forwards run the benchmark's kernels, no tuning launches
 for C in FETCH_SIZE WRITE_SIZE; do
-  timeout 300 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/$C -o pmc -- python $REPO/bench.py --no-cpu-baseline --no-secondary --no-dominant-probe --no-graph --steps 2 --warmup 2 "$@" > $OUT/$C.log 2>&1 || true
+  timeout 300 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/$C -o pmc -- python $REPO/bench.py --full --no-cpu-baseline --no-secondary --no-dominant-probe --no-graph --steps 2 --warmup 2 "$@" > $OUT/$C.log 2>&1 || true
 done
 cd $REPO
 python - "$OUT" <<'PY'

@@ -7,7 +7,7 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}; cd $REPO; OUT=gpurun_out/r6z; mkdir -p $OUT
 T0=$(date +%s); lap() { echo "== $1: $(( $(date +%s) - T0 )) s"; }
 timeout 1500 python -m pytest tests/ -x -q -m gpu -p no:cacheprovider > $OUT/pytest.log 2>&1; echo "pytest rc=$? : $(grep -a -E 'passed|failed' $OUT/pytest.log | tail -1)"; lap suite
 timeout 600 python -c "import __graft_entry__ as g; g.smoke(); print('__SMOKE_OK__')" > $OUT/smoke.log 2>&1; echo "smoke rc=$? : $(grep -a 'smoke:' $OUT/smoke.log | tail -1)"; lap smoke
-timeout 900 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+timeout 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
 python - "$OUT" <<'PY'
 import json, sys
 try:
@@ -34,7 +34,7 @@ bash tools/pmc.sh r06_hq1080_bf16 $HQ 2>&1 | tail -1 | cut -c1-200; lap pmc_hq10
 timeout 200 python tools/layer_table.py --out $OUT/layer_table_fp32 > $OUT/layer_table_fp32.log 2>&1; lap table_fp32
 timeout 300 python tools/layer_table.py --model e2fgvi_hq --hw 720x1296 --precision bf16 --out $OUT/layer_table_hq720_bf16 > $OUT/layer_table_hq720.log 2>&1; lap table_hq720
 bash tools/profile_graph.sh r06_fp32 2>&1 | tail -1; lap timeline
-timeout 300 python bench.py --force-dist --clips-per-gpu 8 --steps 20 --warmup 3 --no-cpu-baseline > $OUT/bench_8clips_forced_gather.json 2> $OUT/bench_8clips.err; python - "$OUT" <<'PY'
+timeout 300 python bench.py --force-dist --clips-per-gpu 8 --steps 20 --warmup 3 --full --no-cpu-baseline > $OUT/bench_8clips_forced_gather.json 2> $OUT/bench_8clips.err; python - "$OUT" <<'PY'
 import json, sys
 try:
     j = json.loads(open(sys.argv[1] + "/bench_8clips_forced_gather.json").read().strip().splitlines()[-1])
