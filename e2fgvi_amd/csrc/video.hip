@@ -80,6 +80,51 @@ __global__ void composite_kernel(const float* __restrict__ pred, const int* __re
     comp[pix * 3 + c] = first[i] ? v : comp[pix * 3 + c] * 0.5f + v * 0.5f;
 }
 
+// Frame resize (test.py:97-104,127, core/dataset.py:115): one separable pass of Pillow's 8-bit BICUBIC resample along H
+// (VERTICAL) or W of uint8 [L,H,W,3].  Output o of the axis reads taps bounds[o] = (first, count) of the source axis with the
+// fixed-point weights coeffs[o][*] (22 fraction bits, built by e2fgvi_amd/video.py::bicubic_tables like Pillow's
+// precompute_coeffs) and stores clamp((2^21 + sum) >> 22, 0, 255) from an int32 accumulator, as Pillow does per pass.
+// One block per output row (l, y) at a time, its threads along the row's x*3+c bytes: coalesced stores; the vertical pass
+// also reads rows coalesced, the horizontal one reads a row's bytes at stride 3 per tap (L1 hits).
+template <bool VERTICAL>
+__global__ void resample_u8_kernel(const unsigned char* __restrict__ src, unsigned char* __restrict__ dst, int L, int H, int W,
+                                   int n_out, const int* __restrict__ bounds, const int* __restrict__ coeffs, int ksize) {
+    const int Ho = VERTICAL ? n_out : H;
+    const int Wo = VERTICAL ? W : n_out;
+    const int n_in = VERTICAL ? H : W;
+    const int row = Wo * 3;
+    const long long rows = (long long)L * Ho;
+    for (long long r = blockIdx.x; r < rows; r += gridDim.x) {
+        const int y = (int)(r % Ho);
+        const long long l = r / Ho;
+        unsigned char* d = dst + r * row;
+        for (int xc = threadIdx.x; xc < row; xc += blockDim.x) {
+            const int x = xc / 3;
+            const int o = VERTICAL ? y : x;
+            // the tap range is clipped to the source axis, so the loads stay in bounds whatever the tables hold
+            int first = bounds[2 * o];
+            first = first < 0 ? 0 : (first > n_in ? n_in : first);
+            int taps = bounds[2 * o + 1];
+            taps = taps < ksize ? taps : ksize;
+            taps = taps < n_in - first ? taps : n_in - first;
+            const int* k = coeffs + (long long)o * ksize;
+            const unsigned char* s;
+            long long step;
+            if (VERTICAL) {
+                s = src + (l * H + first) * (long long)W * 3 + xc;
+                step = (long long)W * 3;
+            } else {
+                s = src + (l * H + y) * (long long)W * 3 + first * 3 + (xc - 3 * x);
+                step = 3;
+            }
+            int acc = 1 << 21;
+            for (int j = 0; j < taps; ++j) acc += (int)s[j * step] * k[j];
+            acc >>= 22;
+            d[xc] = (unsigned char)(acc < 0 ? 0 : (acc > 255 ? 255 : acc));
+        }
+    }
+}
+
 __global__ void float_to_u8_kernel(const float* __restrict__ src, unsigned char* __restrict__ dst, long long n) {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx < n) dst[idx] = (unsigned char)(int)src[idx];
@@ -128,6 +173,25 @@ extern "C" int e2fgvi_composite(const float* pred, const int32_t* ids, const uin
     hipLaunchKernelGGL(composite_kernel, dim3(blocks_for((long long)n * H * W * 3)), dim3(NTH), 0, (hipStream_t)stream, pred, ids,
                        first, frames, masks, comp, n, H, W, Hp, Wp);
     E2_LAUNCH_CHECK("composite");
+    return 0;
+}
+
+extern "C" int e2fgvi_resample_u8(const uint8_t* src, uint8_t* dst, int32_t L, int32_t H, int32_t W, int32_t n_out, int32_t axis,
+                                  const int32_t* bounds, const int32_t* coeffs, int32_t ksize, void* stream) {
+    E2_REQUIRE(src && dst && bounds && coeffs && L > 0 && H > 0 && W > 0 && n_out > 0 && ksize > 0, E2FGVI_EINVAL,
+               "resample_u8: bad arguments");
+    E2_REQUIRE(axis == 1 || axis == 2, E2FGVI_EINVAL, "resample_u8: axis must be 1 (H) or 2 (W), got %d", axis);
+    const long long Wo = axis == 2 ? n_out : W;
+    E2_REQUIRE(W * 3LL <= 0x7fffffffLL && Wo * 3 <= 0x7fffffffLL, E2FGVI_EINVAL, "resample_u8: rows too wide");
+    const long long rows = (long long)L * (axis == 1 ? n_out : H);
+    const unsigned grid = (unsigned)(rows < (1LL << 20) ? rows : (1LL << 20));      // the kernel strides over the rest
+    if (axis == 1)
+        hipLaunchKernelGGL(resample_u8_kernel<true>, dim3(grid), dim3(NTH), 0, (hipStream_t)stream, src, dst, L, H, W, n_out, bounds,
+                           coeffs, ksize);
+    else
+        hipLaunchKernelGGL(resample_u8_kernel<false>, dim3(grid), dim3(NTH), 0, (hipStream_t)stream, src, dst, L, H, W, n_out, bounds,
+                           coeffs, ksize);
+    E2_LAUNCH_CHECK("resample_u8");
     return 0;
 }
 

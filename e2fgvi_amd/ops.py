@@ -1532,6 +1532,31 @@ def composite(pred, ids, first, frames_u8, masks01, comp):
     return comp
 
 
+def resample_u8(frames_u8, n_out, axis, bounds, coeffs):
+    """frames_u8 [L,H,W,3] uint8 -> uint8 with dimension `axis` (1: H, 2: W) resized to n_out: one bicubic pass of PIL's
+    Image.resize with the tables of video.bicubic_tables (bounds int32 [n_out,2], coeffs int32 [n_out,ksize])."""
+    lib = _L.load()
+    _u8(frames_u8, "frames"); _chk(bounds, "bounds", torch.int32); _chk(coeffs, "coeffs", torch.int32)
+    if frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
+        raise ValueError("frames must be [L,H,W,3], got %s" % (tuple(frames_u8.shape),))
+    if axis not in (1, 2):
+        raise ValueError("axis must be 1 (H) or 2 (W), got %r" % (axis,))
+    if bounds.device != frames_u8.device or coeffs.device != frames_u8.device:
+        raise ValueError("frames, bounds and coeffs must be on one device")
+    if bounds.dim() != 2 or tuple(bounds.shape) != (n_out, 2) or coeffs.dim() != 2 or coeffs.shape[0] != n_out:
+        raise ValueError("bounds must be [n_out,2] and coeffs [n_out,ksize] for n_out = %d" % n_out)
+    L, H, W, _ = frames_u8.shape
+    n_in = frames_u8.shape[axis]
+    ksize = coeffs.shape[1]
+    if ksize != 2 * math.ceil(2.0 * max(n_in / n_out, 1.0)) + 1:
+        raise ValueError("coeffs of %d taps do not belong to a %d -> %d resize" % (ksize, n_in, n_out))
+    shape = (L, n_out, W, 3) if axis == 1 else (L, H, n_out, 3)
+    out = torch.empty(shape, dtype=torch.uint8, device=frames_u8.device)
+    _L.check(lib.e2fgvi_resample_u8(_ptr(frames_u8), _ptr(out), L, H, W, n_out, axis, _ptr(bounds), _ptr(coeffs), ksize, _stream()),
+             "resample_u8")
+    return out
+
+
 def float_to_u8(x):
     lib = _L.load()
     _chk(x, "x")

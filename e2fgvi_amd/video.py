@@ -1,12 +1,14 @@
 """Sliding-window video inpainting driver on device.
 
 Mirrors the reference's demo loop -- ``test.py:39-53`` (reference-frame selection), ``:56-69`` (mask NEAREST resize,
-binarise, 4x cross dilation), ``:146-179`` (neighbour window of +-stride frames every ``stride`` frames, mirror padding
-to multiples of (60,108), compositing with the mask, 0.5/0.5 blending of overlapping predictions) -- without cv2 /
-torchvision / PIL: frames and masks come in as uint8 arrays, everything after the upload runs in HIP kernels
-(csrc/video.hip) and only the finished uint8 frames are copied back.  The window planning below is host logic; the byte
+binarise, 4x cross dilation), ``:97-104,127`` (bicubic frame resize, with ``size=``), ``:146-179`` (neighbour window of
++-stride frames every ``stride`` frames, mirror padding to multiples of (60,108), compositing with the mask, 0.5/0.5
+blending of overlapping predictions) -- without cv2 / torchvision / PIL: frames and masks come in as uint8 arrays,
+everything after the upload runs in HIP kernels (csrc/video.hip) and only the finished uint8 frames are copied back.  The window planning below is host logic; the byte
 arithmetic has no CPU path.
 """
+import math
+
 import numpy as np
 import torch
 
@@ -56,6 +58,65 @@ def nearest_table(n_in, n_out):
     return np.minimum(pos.astype(np.int64), n_in - 1).astype(np.int32)
 
 
+def _bicubic(x):
+    """Pillow's bicubic_filter (a = -0.5), elementwise in float64 and in its operation order."""
+    a = -0.5
+    x = np.abs(x)
+    near = ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    far = (((x - 5) * x + 8) * x - 4) * a
+    return np.where(x < 1.0, near, np.where(x < 2.0, far, 0.0))
+
+
+def bicubic_tables(n_in, n_out):
+    """Taps of one axis of PIL's ``Image.resize(size)`` (BICUBIC, Pillow's default for RGB; test.py:97-104,
+    core/dataset.py:115), computed like Pillow's precompute_coeffs + normalize_coeffs_8bpc in double precision.
+    Returns ``bounds`` int32 [n_out,2] = (first source index, tap count) and ``coeffs`` int32 [n_out,ksize]: the
+    normalised weights in fixed point with 22 fraction bits, rounded half away from zero, zero past the tap count.
+    Output o of a pass is clamp((2**21 + sum_j src[first + j] * coeffs[o,j]) >> 22, 0, 255) (csrc/video.hip)."""
+    scale = float(n_in) / float(n_out)
+    fs = max(scale, 1.0)
+    support = 2.0 * fs
+    ksize = int(math.ceil(support)) * 2 + 1
+    ss = 1.0 / fs
+    center = (np.arange(n_out, dtype=np.float64) + 0.5) * scale
+    xmin = np.maximum((center - support + 0.5).astype(np.int64), 0)          # astype truncates toward zero, like (int)
+    xmax = np.minimum((center + support + 0.5).astype(np.int64), n_in) - xmin
+    j = np.arange(ksize)
+    w = _bicubic((j[None, :] + xmin[:, None] - center[:, None] + 0.5) * ss)
+    w = np.where(j[None, :] < xmax[:, None], w, 0.0)
+    ww = np.zeros(n_out)
+    for k in range(ksize):                        # summed tap by tap, in Pillow's order (np.sum would sum pairwise)
+        ww = ww + w[:, k]
+    w = np.divide(w, ww[:, None], out=w.copy(), where=ww[:, None] != 0.0)
+    fixed = w * float(1 << 22)
+    coeffs = np.where(w < 0, fixed - 0.5, fixed + 0.5).astype(np.int32)      # truncation toward zero, like (int)
+    bounds = np.stack([xmin, xmax], 1).astype(np.int32)
+    return bounds, coeffs
+
+
+def resize_frames(frames_u8, size, device=None):
+    """PIL ``Image.resize(size)`` of every frame on the device (BICUBIC, Pillow's default for RGB): test.py:97-104,127
+    (resize_frames) and core/dataset.py:115, where evaluate.py's DAVIS / YouTube-VOS frames -- the ground truth of
+    metrics.calc_psnr_and_ssim -- are resized to (432, 240).  ``size`` is (width, height), PIL's and test.py's order,
+    not the (h, w) of prepare_masks.  frames_u8: uint8 [L,H,W,3], a numpy array or a tensor (uploaded unless it is on the
+    device already).  Returns device uint8 [L,height,width,3], bit-exact with Pillow: the width pass first, then the
+    height pass, each only if that dimension changes; with neither the frames come back as uploaded (no copy)."""
+    if isinstance(frames_u8, torch.Tensor) and frames_u8.is_cuda:
+        x = frames_u8.contiguous() if device is None else frames_u8.to(device).contiguous()
+    else:
+        x = torch.as_tensor(np.ascontiguousarray(frames_u8)).to(device if device is not None else torch.device("cuda"))
+    if x.dim() != 4 or x.shape[3] != 3:
+        raise ValueError("frames must be uint8 [L,H,W,3], got %s" % (tuple(x.shape),))
+    w, h = (int(v) for v in size)
+    if w <= 0 or h <= 0:
+        raise ValueError("size must be a positive (width, height), got %r" % (size,))
+    for n_out, axis in ((w, 2), (h, 1)):
+        if x.shape[axis] != n_out:
+            bounds, coeffs = bicubic_tables(x.shape[axis], n_out)
+            x = ops.resample_u8(x, n_out, axis, torch.from_numpy(bounds).to(x.device), torch.from_numpy(coeffs).to(x.device))
+    return x
+
+
 def prepare_masks(masks_u8, size_hw, device, dilate=True):
     """uint8 masks [L,Hin,Win] (any size, any non-zero = hole) -> device uint8 [L,H,W] of 0/1 like test.py:56-69."""
     m = torch.as_tensor(np.ascontiguousarray(masks_u8)).to(device)
@@ -67,10 +128,14 @@ def prepare_masks(masks_u8, size_hw, device, dilate=True):
 
 @torch.no_grad()
 def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, num_ref=-1, dilate=True,
-                  device=None, pad=True, batch_windows=1, keep_float=False, in_flight=1):
+                  device=None, pad=True, batch_windows=1, keep_float=False, in_flight=1, size=None):
     """frames_u8: uint8 [L,H,W,3]; masks_u8: [L,Hm,Wm] (non-zero = hole; resized to the frames with NEAREST like
     read_mask).  Returns uint8 [L,H,W,3] composited frames, computed like test.py:129-179.
     ``model(masked[b,t,3,H',W'], n_local) -> (pred[b*t,3,H',W'], _)`` on the device.
+
+    ``size`` = (width, height) resizes the uploaded frames on the device first, as test.py:97-104,127 does with PIL
+    (resize_frames: bicubic, bit-exact); the masks are then NEAREST-resized straight to that size and the returned frames
+    have it.  test.py uses (432, 240) for ``e2fgvi`` and (--width, --height) for ``e2fgvi_hq`` with --set_size.
 
     ``batch_windows`` > 1 runs windows of equal shape (same number of local and reference frames) as one forward of
     b clips -- clips are independent, so the predictions are the same; the compositing / blending is still applied in
@@ -88,6 +153,8 @@ def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, 
     if device.type != "cuda":
         raise RuntimeError("inpaint_video runs on the MI355X (cuda) device only; there is no CPU path")
     frames_d = torch.as_tensor(np.ascontiguousarray(frames_u8)).to(device)
+    if size is not None:
+        frames_d = resize_frames(frames_d, size)        # on the caller's stream, before any stream below waits on it
     L, h, w, _ = frames_d.shape
     masks01 = prepare_masks(masks_u8, (h, w), device, dilate)
     Hp, Wp = padded_size(h, w) if pad else (h, w)

@@ -48,6 +48,13 @@ int e2fgvi_masked_clip(const uint8_t* frames, const uint8_t* masks, const int32_
  * img = uint8((pred+1)/2*255) * mask + frame * (1-mask); comp[ids[i]] = first[i] ? img : comp*0.5 + img*0.5 (float [L,H,W,3]). */
 int e2fgvi_composite(const float* pred, const int32_t* ids, const uint8_t* first, int32_t n, const uint8_t* frames,
                      const uint8_t* masks, float* comp, int32_t H, int32_t W, int32_t Hp, int32_t Wp, void* stream);
+/* test.py:97-104,127 resize_frames and core/dataset.py:115: PIL Image.resize(size) of RGB frames (BICUBIC), one separable pass
+ * of uint8 [L,H,W,3] -> dst along `axis` (1: H -> n_out rows, 2: W -> n_out columns).  bounds[n_out][2] = (first source index,
+ * tap count), coeffs[n_out][ksize] = fixed-point weights with 22 fraction bits (Pillow's precompute_coeffs +
+ * normalize_coeffs_8bpc, e2fgvi_amd/video.py::bicubic_tables); dst = clamp((2^21 + sum src * coeff) >> 22, 0, 255).
+ * Pillow runs the W pass first and each pass only if that dimension changes. */
+int e2fgvi_resample_u8(const uint8_t* src, uint8_t* dst, int32_t L, int32_t H, int32_t W, int32_t n_out, int32_t axis,
+                       const int32_t* bounds, const int32_t* coeffs, int32_t ksize, void* stream);
 /* ndarray.astype(uint8) of the blended frames (truncation) */
 int e2fgvi_float_to_u8(const float* src, uint8_t* dst, int64_t n, void* stream);
 /* model output [N,3,Hp,Wp] in (-1,1) -> uint8 NHWC [N,H,W,3] = uint8((pred+1)/2*255): the form the clip-sharded runner
