@@ -1,5 +1,5 @@
-// Fused temporal focal window attention of the bf16 data path (gfx950): bf16 qkv rows in HBM, both products on
-// v_mfma_f32_32x32x16_bf16, fp32 online softmax, bf16 output.  Same operator, key tables and reference call sites as
+// Fused temporal focal window attention of the 16-bit data path (gfx950): bf16 (or fp16, the F16 instantiations) qkv rows in
+// HBM, both products on v_mfma_f32_32x32x16_bf16 (_f16), fp32 online softmax, bf16 (fp16) output.  Same operator, key tables and reference call sites as
 // attention.hip (tfocal_transformer.py:226-396, tfocal_transformer_hq.py:231-425).
 //
 //   S^T[key][query] = K_tile . Q^T       A = K rows from LDS (one ds_read_b128 = 8 consecutive d), B = the wave's Q rows,
@@ -39,12 +39,15 @@ __device__ __forceinline__ u32x4 buf_load4u(__amdgpu_buffer_rsrc_t r, unsigned b
     return __builtin_amdgcn_raw_buffer_load_b128(r, (int)byte_off, 0, 0);
 }
 
-template <int NW>
-__global__ __launch_bounds__(64 * NW) void focal_attn_bf16_kernel(const __bf16* __restrict__ qkv, const int* __restrict__ key_tab,
+// F16: the same kernel on fp16 qkv / out (fp16 MFMA, P rounded to fp16 for the PV product)
+template <int NW, bool F16 = false>
+__global__ __launch_bounds__(64 * NW) void focal_attn_bf16_kernel(const typename e2_h16<F16>::T* __restrict__ qkv, const int* __restrict__ key_tab,
                                                                   int tab_ld, const int* __restrict__ nkeys,
-                                                                  __bf16* __restrict__ out, int B, int T, int fh, int fw,
+                                                                  typename e2_h16<F16>::T* __restrict__ out, int B, int T, int fh, int fw,
                                                                   const char* lo_base, unsigned lo_bytes, unsigned q_rel,
                                                                   unsigned p_rel) {
+    typedef typename e2_h16<F16>::T E16;
+    typedef typename e2_h16<F16>::V8 e16x8;
     constexpr int NT = 64 * NW;
     constexpr int ITEMS = TK * 16;                 // 16-byte items of one K (or V) tile
     constexpr int L_IT = ITEMS / NT;
@@ -76,12 +79,12 @@ __global__ __launch_bounds__(64 * NW) void focal_attn_bf16_kernel(const __bf16* 
         const int py = pp / WS1, px = pp - py * WS1;
         q_row = (long long)(b * T + t) * ntok + (wy * WS0 + py) * fw + (wx * WS1 + px);
     }
-    bf16x8 q[8];
+    e16x8 q[8];
 #pragma unroll
     for (int kk = 0; kk < 8; ++kk) {
         u32x4 v = {0u, 0u, 0u, 0u};
         if (q_ok) v = *reinterpret_cast<const u32x4*>(qkv + q_row * CQ + head * HD + kk * 16 + h * 8);
-        q[kk] = __builtin_bit_cast(bf16x8, v);
+        q[kk] = __builtin_bit_cast(e16x8, v);
     }
     const float qscale = 0.08838834764831845f * LOG2E;       // 128^-0.5 * log2(e), applied to the fp32 scores
 
@@ -177,8 +180,8 @@ __global__ __launch_bounds__(64 * NW) void focal_attn_bf16_kernel(const __bf16* 
             for (int r = 0; r < 16; ++r) s[r] = 0.f;
 #pragma unroll
             for (int kk = 0; kk < 8; ++kk) {
-                const bf16x8 a = *reinterpret_cast<const bf16x8*>(cK + i * 256 + (((2 * kk + h) ^ (i & 15)) << 4));
-                s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, q[kk], s, 0, 0, 0);
+                const e16x8 a = *reinterpret_cast<const e16x8*>(cK + i * 256 + (((2 * kk + h) ^ (i & 15)) << 4));
+                s = e2_mfma16(a, q[kk], s);
             }
         }
         commit_k(sK0 + (cur ^ 1) * K_BYTES);
@@ -211,14 +214,14 @@ __global__ __launch_bounds__(64 * NW) void focal_attn_bf16_kernel(const __bf16* 
             }
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk) {
-                bf16x8 p;
+                e16x8 p;
 #pragma unroll
-                for (int e = 0; e < 8; ++e) p[e] = (__bf16)s[kk * 8 + e];
+                for (int e = 0; e < 8; ++e) p[e] = (E16)s[kk * 8 + e];
 #pragma unroll
                 for (int dt = 0; dt < 4; ++dt) {
                     const int d = dt * 32 + i;
-                    const bf16x8 a = *reinterpret_cast<const bf16x8*>(cV + d * VROW + (((2 * kk + h) ^ ((d >> 4) & 3)) << 4));
-                    acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, p, acc[dt], 0, 0, 0);
+                    const e16x8 a = *reinterpret_cast<const e16x8*>(cV + d * VROW + (((2 * kk + h) ^ ((d >> 4) & 3)) << 4));
+                    acc[dt] = e2_mfma16(a, p, acc[dt]);
                 }
             }
         }
@@ -233,15 +236,15 @@ __global__ __launch_bounds__(64 * NW) void focal_attn_bf16_kernel(const __bf16* 
         l += nmask * __builtin_amdgcn_exp2f(-100.f * LOG2E - m_run);
         const float inv = 1.f / l;
         if (q_ok) {
-            __bf16* op = out + q_row * (NH * HD) + head * HD;
+            E16* op = out + q_row * (NH * HD) + head * HD;
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
                 for (int rq = 0; rq < 4; ++rq) {
-                    typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-                    bf16x4 v = {(__bf16)(acc[dt][rq * 4 + 0] * inv), (__bf16)(acc[dt][rq * 4 + 1] * inv),
-                                (__bf16)(acc[dt][rq * 4 + 2] * inv), (__bf16)(acc[dt][rq * 4 + 3] * inv)};
-                    *reinterpret_cast<bf16x4*>(op + dt * 32 + 8 * rq + 4 * h) = v;      // MFMA rows (r&3) + 8 (r>>2) + 4 h
+                    typedef E16 e16x4 __attribute__((ext_vector_type(4)));
+                    e16x4 v = {(E16)(acc[dt][rq * 4 + 0] * inv), (E16)(acc[dt][rq * 4 + 1] * inv),
+                                (E16)(acc[dt][rq * 4 + 2] * inv), (E16)(acc[dt][rq * 4 + 3] * inv)};
+                    *reinterpret_cast<e16x4*>(op + dt * 32 + 8 * rq + 4 * h) = v;      // MFMA rows (r&3) + 8 (r>>2) + 4 h
                 }
         }
     }
@@ -303,13 +306,15 @@ __device__ __forceinline__ v2_i32x4 v2_rsrc_words(const void* base, unsigned byt
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) s16x4 v2_lds_s16x4;
 
-template <int NW, int QB>
-__global__ __launch_bounds__(64 * NW, (QB == 1 ? 3 : 2)) void focal_attn_bf16_v2_kernel(const __bf16* __restrict__ qkv, const int* __restrict__ key_tab,
+template <int NW, int QB, bool F16 = false>
+__global__ __launch_bounds__(64 * NW, (QB == 1 ? 3 : 2)) void focal_attn_bf16_v2_kernel(const typename e2_h16<F16>::T* __restrict__ qkv, const int* __restrict__ key_tab,
                                                                      int tab_ld, const int* __restrict__ nkeys,
-                                                                     __bf16* __restrict__ out, int B, int T, int fh, int fw,
+                                                                     typename e2_h16<F16>::T* __restrict__ out, int B, int T, int fh, int fw,
                                                                      const char* lo_base, unsigned lo_bytes, unsigned q_rel,
                                                                      unsigned p_rel, int xcd) {
 #if defined(__HIP_DEVICE_COMPILE__)
+    typedef typename e2_h16<F16>::T E16;
+    typedef typename e2_h16<F16>::V8 e16x8;
     constexpr int NT = 64 * NW;
     constexpr int PIECES = 8 / NW;                 // 1-KiB DMA pieces of a K (and of a V) tile per wave
     // table entry of a key row past the end: still out of the buffer's range after the in-row byte offset (< 2 KiB) is added,
@@ -377,7 +382,7 @@ __global__ __launch_bounds__(64 * NW, (QB == 1 ? 3 : 2)) void focal_attn_bf16_v2
         const int py = pp / WS1, px = pp - py * WS1;
         return (long long)(b * T + t) * ntok + (wy * WS0 + py) * fw + (wx * WS1 + px);
     };
-    bf16x8 q[QB][8];
+    e16x8 q[QB][8];
 #pragma unroll
     for (int j = 0; j < QB; ++j) {
         bool ok;
@@ -386,7 +391,7 @@ __global__ __launch_bounds__(64 * NW, (QB == 1 ? 3 : 2)) void focal_attn_bf16_v2
         for (int kk = 0; kk < 8; ++kk) {
             u32x4 v = {0u, 0u, 0u, 0u};
             if (ok) v = *reinterpret_cast<const u32x4*>(qkv + row * CQ + head * HD + kk * 16 + h * 8);
-            q[j][kk] = __builtin_bit_cast(bf16x8, v);
+            q[j][kk] = __builtin_bit_cast(e16x8, v);
         }
     }
     const float qscale = 0.08838834764831845f * LOG2E;       // 128^-0.5 * log2(e)
@@ -469,9 +474,9 @@ __global__ __launch_bounds__(64 * NW, (QB == 1 ? 3 : 2)) void focal_attn_bf16_v2
             if (E2_ATT_SETPRIO) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
             for (int kk = 0; kk < 8; ++kk) {
-                const bf16x8 a = *reinterpret_cast<const bf16x8*>(cK + (k_base ^ (32 * kk)));
+                const e16x8 a = *reinterpret_cast<const e16x8*>(cK + (k_base ^ (32 * kk)));
 #pragma unroll
-                for (int j = 0; j < QB; ++j) s[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, q[j][kk], s[j], 0, 0, 0);
+                for (int j = 0; j < QB; ++j) s[j] = e2_mfma16(a, q[j][kk], s[j]);
             }
             if (E2_ATT_SETPRIO) __builtin_amdgcn_s_setprio(0);
             if (kt == ntiles - 1) {                             // rows past the last key: out of the softmax
@@ -483,7 +488,7 @@ __global__ __launch_bounds__(64 * NW, (QB == 1 ? 3 : 2)) void focal_attn_bf16_v2
                         if (kt * TK + krow >= NK) s[j][r] = -1e30f;
                     }
             }
-            bf16x8 pk[QB][2];
+            e16x8 pk[QB][2];
 #pragma unroll
             for (int j = 0; j < QB; ++j) {
                 float mx = s[j][0];
@@ -514,7 +519,7 @@ __global__ __launch_bounds__(64 * NW, (QB == 1 ? 3 : 2)) void focal_attn_bf16_v2
 #pragma unroll
                 for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) pk[j][kk][e] = (__bf16)s[j][kk * 8 + e];
+                    for (int e = 0; e < 8; ++e) pk[j][kk][e] = (E16)s[j][kk * 8 + e];
             }
             if (E2_ATT_SETPRIO) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -526,9 +531,9 @@ __global__ __launch_bounds__(64 * NW, (QB == 1 ? 3 : 2)) void focal_attn_bf16_v2
                     const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((v2_lds_s16x4*)(vp + 8 * 256));
                     typedef short s16x8 __attribute__((ext_vector_type(8)));
                     const s16x8 av = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                    const bf16x8 a = __builtin_bit_cast(bf16x8, av);
+                    const e16x8 a = __builtin_bit_cast(e16x8, av);
 #pragma unroll
-                    for (int j = 0; j < QB; ++j) acc[j][dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, pk[j][kk], acc[j][dt], 0, 0, 0);
+                    for (int j = 0; j < QB; ++j) acc[j][dt] = e2_mfma16(a, pk[j][kk], acc[j][dt]);
                 }
             if (E2_ATT_SETPRIO) __builtin_amdgcn_s_setprio(0);
         }
@@ -547,15 +552,15 @@ __global__ __launch_bounds__(64 * NW, (QB == 1 ? 3 : 2)) void focal_attn_bf16_v2
             bool ok;
             const long long row = query_row(j, ok);
             if (ok) {
-                __bf16* op = out + row * (NH * HD) + head * HD;
+                E16* op = out + row * (NH * HD) + head * HD;
 #pragma unroll
                 for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
                     for (int rq = 0; rq < 4; ++rq) {
-                        typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-                        bf16x4 v = {(__bf16)(acc[j][dt][rq * 4 + 0] * inv), (__bf16)(acc[j][dt][rq * 4 + 1] * inv),
-                                    (__bf16)(acc[j][dt][rq * 4 + 2] * inv), (__bf16)(acc[j][dt][rq * 4 + 3] * inv)};
-                        *reinterpret_cast<bf16x4*>(op + dt * 32 + 8 * rq + 4 * h) = v;
+                        typedef E16 e16x4 __attribute__((ext_vector_type(4)));
+                        e16x4 v = {(E16)(acc[j][dt][rq * 4 + 0] * inv), (E16)(acc[j][dt][rq * 4 + 1] * inv),
+                                    (E16)(acc[j][dt][rq * 4 + 2] * inv), (E16)(acc[j][dt][rq * 4 + 3] * inv)};
+                        *reinterpret_cast<e16x4*>(op + dt * 32 + 8 * rq + 4 * h) = v;
                     }
             }
         }
@@ -573,15 +578,17 @@ extern "C" int e2fgvi_focal_attention_bf16_variant(int variant) {
     return prev;
 }
 
-extern "C" int e2fgvi_focal_attention_bf16(const void* qkv, const void* kv_pool, const int32_t* key_tab, int32_t tab_ld,
-                                           const int32_t* nkeys, void* out, int32_t B, int32_t T, int32_t fh, int32_t fw,
-                                           void* stream) {
-    E2_REQUIRE(qkv && kv_pool && key_tab && nkeys && out, E2FGVI_EINVAL, "focal_attention_bf16: null pointer");
+template <bool F16>
+static int focal_attention_16(const void* qkv, const void* kv_pool, const int32_t* key_tab, int32_t tab_ld, const int32_t* nkeys,
+                              void* out, int32_t B, int32_t T, int32_t fh, int32_t fw, void* stream) {
+    typedef typename e2_h16<F16>::T E16;
+    const char* nm = F16 ? "focal_attention_f16" : "focal_attention_bf16";
+    E2_REQUIRE(qkv && kv_pool && key_tab && nkeys && out, E2FGVI_EINVAL, "%s: null pointer", nm);
     E2_REQUIRE(B > 0 && T > 0 && fh > 0 && fw > 0 && fh % WS0 == 0 && fw % WS1 == 0, E2FGVI_EINVAL,
-               "focal_attention_bf16: token grid %dx%d must be a positive multiple of (5,9)", fh, fw);
-    E2_REQUIRE(tab_ld >= SLOTS, E2FGVI_EINVAL, "focal_attention_bf16: tab_ld < 210");
+               "%s: token grid %dx%d must be a positive multiple of (5,9)", nm, fh, fw);
+    E2_REQUIRE(tab_ld >= SLOTS, E2FGVI_EINVAL, "%s: tab_ld < 210", nm);
     E2_REQUIRE(((uintptr_t)qkv & 15) == 0 && ((uintptr_t)kv_pool & 15) == 0 && ((uintptr_t)out & 15) == 0, E2FGVI_EINVAL,
-               "focal_attention_bf16: buffers must be 16-byte aligned");
+               "%s: buffers must be 16-byte aligned", nm);
     const int qtiles = cdiv(T * WTOK, 32);
     const int nWin = (fh / WS0) * (fw / WS1);
     const long long qb = (long long)B * T * fh * fw * CQ * 2, pb = (long long)B * T * nWin * CQ * 2;
@@ -590,7 +597,7 @@ extern "C" int e2fgvi_focal_attention_bf16(const void* qkv, const void* kv_pool,
     const char* lo = cq < cp ? cq : cp;
     const long long hi_end = (cq + qb > cp + pb ? cq + qb : cp + pb) - lo;
     E2_REQUIRE(hi_end < 0xFFFFF000LL, E2FGVI_EUNSUP,
-               "focal_attention_bf16: qkv and kv_pool must lie within one 4 GiB window (allocate them back to back / split the batch)");
+               "%s: qkv and kv_pool must lie within one 4 GiB window (allocate them back to back / split the batch)", nm);
     // Variant (e2fgvi_focal_attention_bf16_variant): 10 * QB + NW selects the round-3 kernel with NW waves of QB x 32 queries per
     // workgroup (12, 14, 18, 22, 24); 1 = round 2's kernel; 0 = automatic.
     constexpr int xcd_env = 0;
@@ -608,19 +615,19 @@ extern "C" int e2fgvi_focal_attention_bf16(const void* qkv, const void* kv_pool,
     if (variant != 1 && !v2_fits) variant = 1;                            // very long windows (T > 150): round 2's kernel
     if (variant != 1) {
         const int nw = variant % 10, qb = variant / 10;
-        E2_REQUIRE((nw == 2 || nw == 4 || nw == 8) && (qb == 1 || qb == 2), E2FGVI_EINVAL, "focal_attention_bf16: unknown variant %d", variant);
+        E2_REQUIRE((nw == 2 || nw == 4 || nw == 8) && (qb == 1 || qb == 2), E2FGVI_EINVAL, "%s: unknown variant %d", nm, variant);
         const long long nblk = (long long)cdiv(T * WTOK, 32 * qb * nw) * nWin * NH * B;
-        E2_REQUIRE(nblk < 2147483647LL, E2FGVI_EUNSUP, "focal_attention_bf16: more than 2^31 workgroups");
+        E2_REQUIRE(nblk < 2147483647LL, E2FGVI_EUNSUP, "%s: more than 2^31 workgroups", nm);
         dim3 grid((unsigned)nblk), block(64 * nw);
 #define E2_ATT_V2(NW_, QB_)                                                                                                       \
         do {                                                                                                                      \
             if (dyn + 2 * V2_KB + 2 * V2_VB + 1024 > 64 * 1024) {                                                                 \
-                hipError_t ea = hipFuncSetAttribute((const void*)focal_attn_bf16_v2_kernel<NW_, QB_>,                             \
+                hipError_t ea = hipFuncSetAttribute((const void*)focal_attn_bf16_v2_kernel<NW_, QB_, F16>,                             \
                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);                         \
-                E2_REQUIRE(ea == hipSuccess, (int)ea, "focal_attention_bf16: cannot reserve %zu bytes of dynamic LDS", dyn);      \
+                E2_REQUIRE(ea == hipSuccess, (int)ea, "%s: cannot reserve %zu bytes of dynamic LDS", nm, dyn);      \
             }                                                                                                                     \
-            hipLaunchKernelGGL((focal_attn_bf16_v2_kernel<NW_, QB_>), grid, block, dyn, (hipStream_t)stream, (const __bf16*)qkv, \
-                               key_tab, tab_ld, nkeys, (__bf16*)out, B, T, fh, fw, lo, (unsigned)hi_end, (unsigned)(cq - lo),      \
+            hipLaunchKernelGGL((focal_attn_bf16_v2_kernel<NW_, QB_, F16>), grid, block, dyn, (hipStream_t)stream, (const E16*)qkv, \
+                               key_tab, tab_ld, nkeys, (E16*)out, B, T, fh, fw, lo, (unsigned)hi_end, (unsigned)(cq - lo),      \
                                (unsigned)(cp - lo), xcd_env);                                                                     \
         } while (0)
         if (qb == 1 && nw == 2) E2_ATT_V2(2, 1);
@@ -630,7 +637,7 @@ extern "C" int e2fgvi_focal_attention_bf16(const void* qkv, const void* kv_pool,
         else if (qb == 2 && nw == 4) E2_ATT_V2(4, 2);
         else E2_ATT_V2(8, 2);
 #undef E2_ATT_V2
-        E2_LAUNCH_CHECK("focal_attention_bf16 (v2)");
+        E2_LAUNCH_CHECK(nm);
         return 0;
     }
     // eight query waves per workgroup when a window has enough query tiles (720p T=10: 15): every staged K / V tile then
@@ -638,14 +645,26 @@ extern "C" int e2fgvi_focal_attention_bf16(const void* qkv, const void* kv_pool,
     const int nw = qtiles >= 12 ? 8 : 4;
     dim3 grid(cdiv(qtiles, nw), nWin * NH, B), block(64 * nw);
     if (nw == 8)
-        hipLaunchKernelGGL(focal_attn_bf16_kernel<8>, grid, block, 0, (hipStream_t)stream, (const __bf16*)qkv, key_tab, tab_ld, nkeys,
-                           (__bf16*)out, B, T, fh, fw, lo, (unsigned)hi_end, (unsigned)(cq - lo), (unsigned)(cp - lo));
-    else if (nw == 2)
-        hipLaunchKernelGGL(focal_attn_bf16_kernel<2>, grid, block, 0, (hipStream_t)stream, (const __bf16*)qkv, key_tab, tab_ld, nkeys,
-                           (__bf16*)out, B, T, fh, fw, lo, (unsigned)hi_end, (unsigned)(cq - lo), (unsigned)(cp - lo));
-    else
-    hipLaunchKernelGGL(focal_attn_bf16_kernel<4>, grid, block, 0, (hipStream_t)stream, (const __bf16*)qkv, key_tab, tab_ld, nkeys,
-                       (__bf16*)out, B, T, fh, fw, lo, (unsigned)hi_end, (unsigned)(cq - lo), (unsigned)(cp - lo));
-    E2_LAUNCH_CHECK("focal_attention_bf16");
+        hipLaunchKernelGGL((focal_attn_bf16_kernel<8, F16>), grid, block, 0, (hipStream_t)stream, (const E16*)qkv, key_tab, tab_ld, nkeys,
+                           (E16*)out, B, T, fh, fw, lo, (unsigned)hi_end, (unsigned)(cq - lo), (unsigned)(cp - lo));
+    else if (nw == 4)
+        hipLaunchKernelGGL((focal_attn_bf16_kernel<4, F16>), grid, block, 0, (hipStream_t)stream, (const E16*)qkv, key_tab, tab_ld,
+                           nkeys, (E16*)out, B, T, fh, fw, lo, (unsigned)hi_end, (unsigned)(cq - lo), (unsigned)(cp - lo));
+    else if constexpr (!F16)      // (never selected: the rule above takes 8 or 4; fp16 has no instantiation)
+        hipLaunchKernelGGL(focal_attn_bf16_kernel<2>, grid, block, 0, (hipStream_t)stream, (const E16*)qkv, key_tab, tab_ld, nkeys,
+                           (E16*)out, B, T, fh, fw, lo, (unsigned)hi_end, (unsigned)(cq - lo), (unsigned)(cp - lo));
+    E2_LAUNCH_CHECK(nm);
     return 0;
+}
+
+extern "C" int e2fgvi_focal_attention_bf16(const void* qkv, const void* kv_pool, const int32_t* key_tab, int32_t tab_ld,
+                                           const int32_t* nkeys, void* out, int32_t B, int32_t T, int32_t fh, int32_t fw,
+                                           void* stream) {
+    return focal_attention_16<false>(qkv, kv_pool, key_tab, tab_ld, nkeys, out, B, T, fh, fw, stream);
+}
+/* fp16 qkv / kv_pool / out: the same kernels on fp16 MFMA (P rounded to fp16 for the PV product) */
+extern "C" int e2fgvi_focal_attention_f16(const void* qkv, const void* kv_pool, const int32_t* key_tab, int32_t tab_ld,
+                                          const int32_t* nkeys, void* out, int32_t B, int32_t T, int32_t fh, int32_t fw,
+                                          void* stream) {
+    return focal_attention_16<true>(qkv, kv_pool, key_tab, tab_ld, nkeys, out, B, T, fh, fw, stream);
 }

@@ -127,6 +127,29 @@ __device__ __forceinline__ void e2_split8(const f32x4& v0, const f32x4& v1, e2_b
     lo = __builtin_bit_cast(e2_bf16x8, L);
 }
 
+// ---------------------------------------------------------------------------------------------
+// The two 16-bit element types of the 16-bit data path: bf16 (E2FGVI_BF16) and IEEE half (E2FGVI_F16).  Both feed the same
+// 32x32x16 MFMA shape at the same rate with the same A / B lane map and C / D layout, so every 16-bit kernel is ONE body with
+// the element type as a parameter: e2_h16<F16>::T / ::V8 and e2_mfma16 (overloaded on the operand type).
+// fp32 -> fp16 conversions are plain casts (v_cvt_f16_f32: round to nearest even, +-inf past 65504, subnormals kept, the
+// bits of torch's .half()); never the round-toward-zero packed conversion.
+// ---------------------------------------------------------------------------------------------
+typedef _Float16 e2_f16x8 __attribute__((ext_vector_type(8)));
+template <bool F16> struct e2_h16;
+template <> struct e2_h16<false> { typedef __bf16 T; typedef e2_bf16x8 V8; };
+template <> struct e2_h16<true> { typedef _Float16 T; typedef e2_f16x8 V8; };
+__device__ __forceinline__ f32x16 e2_mfma16(e2_bf16x8 a, e2_bf16x8 b, f32x16 c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+}
+__device__ __forceinline__ f32x16 e2_mfma16(e2_f16x8 a, e2_f16x8 b, f32x16 c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+}
+// one 16-bit value (raw bits) -> fp32, exact
+template <bool F16> __device__ __forceinline__ float e2_h16_to_f32(unsigned short b) {
+    if constexpr (F16) return (float)__builtin_bit_cast(_Float16, b);
+    else return __builtin_bit_cast(float, (unsigned)b << 16);
+}
+
 __device__ __forceinline__ float apply_act(float v, int act, float slope) {
     if (act == E2FGVI_ACT_RELU) return fmaxf(v, 0.f);
     if (act == E2FGVI_ACT_LRELU) return v > 0.f ? v : v * slope;

@@ -44,7 +44,7 @@ struct ConvXParams {
     const void* w;
     const float* bias;
     const void* res;
-    int res_ld, res_coff, res_bf16;
+    int res_ld, res_coff, res_bf16;       // (res_bf16 / dst_bf16 / dst2: the 16-bit type of the mode -- fp16 in MODE 3)
     void* dst;
     int dst_ld, dst_coff, dst_bf16, dst_nchw;
     __bf16* dst2;
@@ -70,7 +70,6 @@ __device__ __forceinline__ float dcn_post(float v, int co, int C, const f32x4& f
     return max_residue * e2_fast_tanh(v) + fl[which + ((co & 1) ? 0 : 1)];
 }
 
-__device__ __forceinline__ float bf16_bits_to_f32(unsigned short b) { return __builtin_bit_cast(float, (unsigned)b << 16); }
 
 // x = hi + mid + lo with bf16 pieces (common.h, e2_split8).  Non-finite inputs give NaN.
 __device__ __forceinline__ void split8(const f32x4& v0, const f32x4& v1, bf16x8& hi, bf16x8& mid, bf16x8& lo) {
@@ -125,13 +124,17 @@ __device__ __forceinline__ void pp_dma16(pp_i32x4 rsrc, unsigned lds_dst, unsign
 // are in complementary segments; with one barrier per step both waves split, then both multiply.  Same products in the same order:
 // BIT-IDENTICAL to tiles 7 / 8 (tests/test_gpu_x3.py).  Measured (tools/probe/pp_ab.py, alternating rounds, one process): fc1 94.3 ->
 // 85.0 us, qkv 70.5 -> 66.7, sc 253.0 -> 240.2; the interval timeline: tools/probe/pp_probe.py, profiles/r06_x3_gemm_pingpong.txt.
+// MODE 3 (F16): MODE 0 with fp16 in place of bf16 -- fp16 sources and packed weights, v_mfma_f32_32x32x16_f16 (same rate, same
+// operand and result layouts), fp16 16-bit residual / dst / dst2.  Same tiles, same data movement; no split planes.
 template <int BM, int BN, int WGM, int WGN, bool S3, int MODE, bool PP = false>
 __global__ __launch_bounds__(64 * WGM * WGN) void conv_bf16x_kernel(const ConvXParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)      // the LDS-DMA builtin takes an address_space(3) pointer the host pass cannot form
-    constexpr bool F32 = MODE == 1, X3 = MODE == 2;
+    constexpr bool F32 = MODE == 1, X3 = MODE == 2, F16 = MODE == 3;
+    typedef typename e2_h16<F16>::T E16;                        // the 16-bit element type (operands, 16-bit residual / dst / dst2)
+    typedef typename e2_h16<F16>::V8 e16x8;
     static_assert(!PP || (X3 && !S3 && WGM * WGN == 8), "ping-pong halves: split-operand mode, 8 waves, no row-shift stages");
     constexpr int NT = 64 * WGM * WGN;
-    constexpr int ESZ = MODE ? 4 : 2;                           // activation element size
+    constexpr int ESZ = (F32 || X3) ? 4 : 2;                    // activation element size
     constexpr int CH = 16 / ESZ;                                // channels per 16-byte chunk
     constexpr int KC = 8 * CH;                                  // channels per K-step (128-byte rows)
     constexpr int TM = BM / (32 * WGM), TN = BN / (32 * WGN);
@@ -360,25 +363,25 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_bf16x_kernel(const ConvXP
                         for (int tn = 0; tn < TN; ++tn)
                             acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[tm][e], b[tn][e], acc[tm][tn], 0, 0, 0);
             } else {
-                bf16x8 a[TM], b[TN];
+                e16x8 a[TM], b[TN];
 #pragma unroll
                 for (int tm = 0; tm < TM; ++tm) {
-                    a[tm] = *reinterpret_cast<const bf16x8*>(st + a_rd[tm] + (((2 * kk + h) ^ a_key[tm]) << 4));
+                    a[tm] = *reinterpret_cast<const e16x8*>(st + a_rd[tm] + (((2 * kk + h) ^ a_key[tm]) << 4));
                     if (S3) {
                         u32x4 q = __builtin_bit_cast(u32x4, a[tm]);
 #pragma unroll
                         for (int e = 0; e < 4; ++e) q[e] = zero[tm] ? 0u : q[e];
-                        a[tm] = __builtin_bit_cast(bf16x8, q);
+                        a[tm] = __builtin_bit_cast(e16x8, q);
                     }
                 }
 #pragma unroll
                 for (int tn = 0; tn < TN; ++tn)
-                    b[tn] = *reinterpret_cast<const bf16x8*>(stb + b_rd[tn] + (2 * kk + h) * (BN * 16));
+                    b[tn] = *reinterpret_cast<const e16x8*>(stb + b_rd[tn] + (2 * kk + h) * (BN * 16));
 #pragma unroll
                 for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
                     for (int tn = 0; tn < TN; ++tn)
-                        acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[tm], b[tn], acc[tm][tn], 0, 0, 0);
+                        acc[tm][tn] = e2_mfma16(a[tm], b[tn], acc[tm][tn]);
             }
         }
         }
@@ -651,7 +654,11 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_bf16x_kernel(const ConvXP
             f32x4 v1 = *reinterpret_cast<const f32x4*>(E + row * LDE + col0 + 4) + b1;
             if (p.res) {
                 const long long ro = mr * p.res_ld + p.res_coff + co;
-                if (p.res_bf16) {
+                if (p.res_bf16 && F16) {
+                    const e16x8 q = *reinterpret_cast<const e16x8*>(reinterpret_cast<const E16*>(p.res) + ro);
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) { v0[c] += (float)q[c]; v1[c] += (float)q[4 + c]; }
+                } else if (p.res_bf16) {
                     const u32x4 q = *reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned short*>(p.res) + ro);
                     v0[0] += __builtin_bit_cast(float, q[0] << 16); v0[1] += __builtin_bit_cast(float, q[0] & 0xFFFF0000u);
                     v0[2] += __builtin_bit_cast(float, q[1] << 16); v0[3] += __builtin_bit_cast(float, q[1] & 0xFFFF0000u);
@@ -668,7 +675,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_bf16x_kernel(const ConvXP
                 v0[c] = v0[c] > 0.f ? v0[c] : v0[c] * neg;
                 v1[c] = v1[c] > 0.f ? v1[c] : v1[c] * neg;
             }
-            if (p.split_plane && co >= p.split_from) {
+            if (!F16 && p.split_plane && co >= p.split_from) {
                 // the K / V columns of a qkv Linear: the operand planes of the split-operand attention, not the fp32 rows
                 bf16x8 sh, sm, sl;
                 e2_split8(v0, v1, sh, sm, sl);
@@ -678,16 +685,17 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_bf16x_kernel(const ConvXP
                 *reinterpret_cast<bf16x8*>(o + 2 * p.split_plane) = sl;
                 continue;
             }
-            bf16x8 hv = {(__bf16)v0[0], (__bf16)v0[1], (__bf16)v0[2], (__bf16)v0[3], (__bf16)v1[0], (__bf16)v1[1], (__bf16)v1[2], (__bf16)v1[3]};
+            e16x8 hv = {(E16)v0[0], (E16)v0[1], (E16)v0[2], (E16)v0[3], (E16)v1[0], (E16)v1[1], (E16)v1[2], (E16)v1[3]};
             const long long dof = m * p.dst_ld + p.dst_coff + co;
             if (p.dst_bf16) {
-                *reinterpret_cast<bf16x8*>(reinterpret_cast<__bf16*>(p.dst) + dof) = hv;
+                *reinterpret_cast<e16x8*>(reinterpret_cast<E16*>(p.dst) + dof) = hv;
             } else {
                 float* o = reinterpret_cast<float*>(p.dst) + dof;
                 *reinterpret_cast<f32x4*>(o) = v0;
                 *reinterpret_cast<f32x4*>(o + 4) = v1;
             }
-            if (p.dst2 && !p.split_plane) *reinterpret_cast<bf16x8*>(p.dst2 + m * p.dst2_ld + p.dst2_coff + co) = hv;
+            if (p.dst2 && !p.split_plane)
+                *reinterpret_cast<e16x8*>(reinterpret_cast<E16*>(p.dst2) + m * p.dst2_ld + p.dst2_coff + co) = hv;
         }
         continue;
     }
@@ -724,7 +732,11 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_bf16x_kernel(const ConvXP
                     const long long ro = mr * p.res_ld + p.res_coff + co;
                     if (p.res_bf16) {
                         const unsigned short* rp = reinterpret_cast<const unsigned short*>(p.res) + ro;
-                        if (vec_r) {
+                        if (vec_r && F16) {
+                            const e16x8 q = *reinterpret_cast<const e16x8*>(rp);
+#pragma unroll
+                            for (int c = 0; c < 8; ++c) v[c] += (float)q[c];
+                        } else if (vec_r) {
                             const u32x4 q = *reinterpret_cast<const u32x4*>(rp);
 #pragma unroll
                             for (int c = 0; c < 4; ++c) {
@@ -733,7 +745,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_bf16x_kernel(const ConvXP
                             }
                         } else {
 #pragma unroll
-                            for (int c = 0; c < 8; ++c) if (full || n + c < p.Cout_g) v[c] += bf16_bits_to_f32(rp[c]);
+                            for (int c = 0; c < 8; ++c) if (full || n + c < p.Cout_g) v[c] += e2_h16_to_f32<F16>(rp[c]);
                         }
                     } else {
                         const float* rp = reinterpret_cast<const float*>(p.res) + ro;
@@ -750,7 +762,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_bf16x_kernel(const ConvXP
 #pragma unroll
                 for (int c = 0; c < 8; ++c) v[c] = apply_act(v[c], p.act, p.slope);
             }
-            if (p.split_plane && co >= p.split_from) {       // (the launcher guarantees Cout % 8 == 0 and 16-byte addressable planes)
+            if (!F16 && p.split_plane && co >= p.split_from) {       // (the launcher guarantees Cout % 8 == 0 and 16-byte addressable planes)
                 const f32x4 s0 = {v[0], v[1], v[2], v[3]}, s1 = {v[4], v[5], v[6], v[7]};
                 bf16x8 sh, sm, sl;
                 e2_split8(s0, s1, sh, sm, sl);
@@ -760,9 +772,9 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_bf16x_kernel(const ConvXP
                 *reinterpret_cast<bf16x8*>(o + 2 * p.split_plane) = sl;
                 continue;
             }
-            bf16x8 hv;
+            e16x8 hv;
 #pragma unroll
-            for (int c = 0; c < 8; ++c) hv[c] = (__bf16)v[c];
+            for (int c = 0; c < 8; ++c) hv[c] = (E16)v[c];
             const long long dof = (long long)m * p.dst_ld + p.dst_coff + co;
             if ((p.dbg_noload & 8) && v[0] != 123.456f) continue;          // measurement aid: everything but the global stores
             if (p.dst_nchw) {                      // plain fp32 NCHW [N,Cout,Ho,Wo] (the decoder's last layer: 3 channels)
@@ -771,8 +783,8 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_bf16x_kernel(const ConvXP
 #pragma unroll
                 for (int c = 0; c < 8; ++c) if (full || n + c < p.Cout_g) o[(long long)c * HoWo] = v[c];
             } else if (p.dst_bf16) {
-                __bf16* o = reinterpret_cast<__bf16*>(p.dst) + dof;
-                if (vec_d) *reinterpret_cast<bf16x8*>(o) = hv;
+                E16* o = reinterpret_cast<E16*>(p.dst) + dof;
+                if (vec_d) *reinterpret_cast<e16x8*>(o) = hv;
                 else {
 #pragma unroll
                     for (int c = 0; c < 8; ++c) if (full || n + c < p.Cout_g) o[c] = hv[c];
@@ -789,8 +801,8 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_bf16x_kernel(const ConvXP
                 }
             }
             if (p.dst2 && !p.split_plane) {
-                __bf16* o = p.dst2 + (long long)m * p.dst2_ld + p.dst2_coff + co;
-                if (vec_2) *reinterpret_cast<bf16x8*>(o) = hv;
+                E16* o = reinterpret_cast<E16*>(p.dst2) + (long long)m * p.dst2_ld + p.dst2_coff + co;
+                if (vec_2) *reinterpret_cast<e16x8*>(o) = hv;
                 else {
 #pragma unroll
                     for (int c = 0; c < 8; ++c) if (full || n + c < p.Cout_g) o[c] = hv[c];
@@ -913,7 +925,7 @@ int launch_x(ConvXParams& p, int groups, hipStream_t st, int mode = 0) {
         e2fgvi_set_error("conv2d_bf16x: the row-shift tiles (11..17) are for 3x3 stride-1 pad-1 layers");
         return E2FGVI_EINVAL;
     }
-    if (mode) {
+    if (mode == 1 || mode == 2) {
         if constexpr (!S3) {
             if (mode == 2)
                 hipLaunchKernelGGL((conv_bf16x_kernel<BM, BN, WGM, WGN, false, 2>), dim3(p.tilesM * p.tilesN, groups, 1), dim3(64 * WGM * WGN), 0, st, p);
@@ -923,6 +935,8 @@ int launch_x(ConvXParams& p, int groups, hipStream_t st, int mode = 0) {
             e2fgvi_set_error("conv2d_f32x: the row-shift tiles (11..18) take bf16 operands only");
             return E2FGVI_EUNSUP;
         }
+    } else if (mode == 3) {
+        hipLaunchKernelGGL((conv_bf16x_kernel<BM, BN, WGM, WGN, S3, 3>), dim3(p.tilesM * p.tilesN, groups, 1), dim3(64 * WGM * WGN), 0, st, p);
     } else {
         hipLaunchKernelGGL((conv_bf16x_kernel<BM, BN, WGM, WGN, S3, 0>), dim3(p.tilesM * p.tilesN, groups, 1), dim3(64 * WGM * WGN), 0, st, p);
     }
@@ -951,6 +965,22 @@ extern "C" int e2fgvi_pack_conv_weight_bf16x(const float* w, void* wpacked, int3
     hipLaunchKernelGGL(pack_conv_weight_x_kernel<__bf16>, dim3((unsigned)cdiv64(q.total, 256)), dim3(256), 0, (hipStream_t)stream,
                        w, (__bf16*)wpacked, q);
     E2_LAUNCH_CHECK("pack_conv_weight_bf16x");
+    return 0;
+}
+
+/* fp16: the bf16 layout and element count, fp16 elements */
+extern "C" int64_t e2fgvi_packed_conv_weight_f16x_size(int32_t Cout, int32_t groups, int32_t KH, int32_t KW, int32_t nsrc,
+                                                       const int32_t* src_cpg) {
+    return e2fgvi_packed_conv_weight_bf16x_size(Cout, groups, KH, KW, nsrc, src_cpg);
+}
+extern "C" int e2fgvi_pack_conv_weight_f16x(const float* w, void* wpacked, int32_t Cout, int32_t groups, int32_t KH,
+                                            int32_t KW, int32_t nsrc, const int32_t* src_cpg, void* stream) {
+    PackX q;
+    E2_REQUIRE(w && wpacked && src_cpg, E2FGVI_EINVAL, "pack_conv_weight_f16x: null pointer");
+    E2_REQUIRE(geometry_x(Cout, groups, KH, KW, nsrc, src_cpg, &q), E2FGVI_EINVAL, "pack_conv_weight_f16x: bad geometry");
+    hipLaunchKernelGGL(pack_conv_weight_x_kernel<_Float16>, dim3((unsigned)cdiv64(q.total, 256)), dim3(256), 0, (hipStream_t)stream,
+                       w, (_Float16*)wpacked, q);
+    E2_LAUNCH_CHECK("pack_conv_weight_f16x");
     return 0;
 }
 
@@ -1028,6 +1058,20 @@ extern "C" int e2fgvi_pack_conv_weight_bf16x_taps(const float* w, void* wpacked,
     return 0;
 }
 
+extern "C" int64_t e2fgvi_packed_conv_weight_f16x_taps_size(int32_t Cout, int32_t KH, int32_t KW, int32_t cin) {
+    return e2fgvi_packed_conv_weight_bf16x_taps_size(Cout, KH, KW, cin);
+}
+extern "C" int e2fgvi_pack_conv_weight_f16x_taps(const float* w, void* wpacked, int32_t Cout, int32_t KH, int32_t KW, int32_t cin,
+                                                 void* stream) {
+    PackX q;
+    E2_REQUIRE(w && wpacked, E2FGVI_EINVAL, "pack_conv_weight_f16x_taps: null pointer");
+    E2_REQUIRE(geometry_taps(Cout, KH, KW, cin, &q), E2FGVI_EINVAL, "pack_conv_weight_f16x_taps: bad geometry");
+    hipLaunchKernelGGL(pack_conv_weight_x_kernel<_Float16>, dim3((unsigned)cdiv64(q.total, 256)), dim3(256), 0, (hipStream_t)stream,
+                       w, (_Float16*)wpacked, q);
+    E2_LAUNCH_CHECK("pack_conv_weight_f16x_taps");
+    return 0;
+}
+
 extern "C" int64_t e2fgvi_packed_conv_weight_f32x_taps_size(int32_t Cout, int32_t KH, int32_t KW, int32_t cin) {
     PackX q;
     if (!geometry_taps(Cout, KH, KW, cin, &q, true)) {
@@ -1069,7 +1113,8 @@ extern "C" int e2fgvi_pack_conv_weight_f32x3_taps(const float* w, void* wpacked,
 }
 
 static int conv2d_x(const e2fgvi_convx_desc* d, void* stream, int mode) {
-    const bool f32 = mode != 0;           // fp32 activations (MODE 1: fp32 weights too; MODE 2: three bf16 planes per weight)
+    const bool f32 = mode == 1 || mode == 2;   // fp32 activations (MODE 1: fp32 weights too; MODE 2: three bf16 planes per weight)
+    const int dt16 = mode == 3 ? E2FGVI_F16 : E2FGVI_BF16;   // the 16-bit storage type of dst / residual (MODE 3: fp16)
     E2_REQUIRE(d, E2FGVI_EINVAL, "conv2d_bf16x: null descriptor");
     PackX q;
     const int esz = f32 ? 4 : 2;
@@ -1098,8 +1143,9 @@ static int conv2d_x(const e2fgvi_convx_desc* d, void* stream, int mode) {
     E2_REQUIRE((long long)d->N * d->Ho * d->Wo < 2147483647LL, E2FGVI_EUNSUP, "conv2d_bf16x: more than 2^31 output pixels");
     E2_REQUIRE(d->KH <= 8 && d->KW <= 8, E2FGVI_EUNSUP, "conv2d_bf16x: kernels larger than 8x8 are not supported");
     E2_REQUIRE(d->wpacked && d->dst, E2FGVI_EINVAL, "conv2d_bf16x: null weight/dst");
-    E2_REQUIRE((d->dst_dtype == E2FGVI_F32 || d->dst_dtype == E2FGVI_BF16) && (d->res_dtype == E2FGVI_F32 || d->res_dtype == E2FGVI_BF16),
-               E2FGVI_EINVAL, "conv2d_bf16x: dtype must be E2FGVI_F32 or E2FGVI_BF16");
+    E2_REQUIRE((d->dst_dtype == E2FGVI_F32 || d->dst_dtype == dt16) && (d->res_dtype == E2FGVI_F32 || d->res_dtype == dt16),
+               E2FGVI_EINVAL, mode == 3 ? "conv2d_f16x: dtype must be E2FGVI_F32 or E2FGVI_F16"
+                                        : "conv2d_bf16x: dtype must be E2FGVI_F32 or E2FGVI_BF16");
     ConvXParams p;
     for (int s = 0; s < E2FGVI_MAX_SRC; ++s) { p.src[s] = nullptr; p.ld[s] = 0; p.coff[s] = 0; p.cpg[s] = 0; p.src_bytes[s] = 0; }
     for (int s = 0; s < d->nsrc; ++s) {
@@ -1121,6 +1167,7 @@ static int conv2d_x(const e2fgvi_convx_desc* d, void* stream, int mode) {
         E2_REQUIRE(d->dst_coff >= 0 && d->dst_coff + d->Cout <= d->dst_ld, E2FGVI_EINVAL, "conv2d_bf16x: dst slice exceeds dst_ld");
     E2_REQUIRE(((uintptr_t)d->dst & 15) == 0 && (!d->dst2 || ((uintptr_t)d->dst2 & 15) == 0) &&
                (!d->residual || ((uintptr_t)d->residual & 15) == 0), E2FGVI_EINVAL, "conv2d_bf16x: dst / dst2 / residual not 16-byte aligned");
+    E2_REQUIRE(mode != 3 || !d->dst2_plane_stride, E2FGVI_EINVAL, "conv2d_f16x: no split planes (dst2 is an fp16 copy)");
     if (d->dst2_plane_stride) {
         // ABI 8: channels from dst2_split_from on as three exact bf16 planes (16-byte stores of 8 channels)
         E2_REQUIRE(d->dst2 && d->dst2_plane_stride > 0 && d->dst_dtype == E2FGVI_F32 && !d->dst_nchw && d->groups == 1 &&
@@ -1159,8 +1206,8 @@ static int conv2d_x(const e2fgvi_convx_desc* d, void* stream, int mode) {
     }
     p.wgroup_elems = q.wgroup_elems; p.wgroup_bytes = (unsigned)(q.wgroup_elems * wbytes_num);
     p.w = d->wpacked; p.bias = d->bias;
-    p.res = d->residual; p.res_ld = d->res_ld; p.res_coff = d->res_coff; p.res_bf16 = d->res_dtype == E2FGVI_BF16;
-    p.dst = d->dst; p.dst_ld = d->dst_ld; p.dst_coff = d->dst_coff; p.dst_bf16 = d->dst_dtype == E2FGVI_BF16;
+    p.res = d->residual; p.res_ld = d->res_ld; p.res_coff = d->res_coff; p.res_bf16 = d->res_dtype == dt16;
+    p.dst = d->dst; p.dst_ld = d->dst_ld; p.dst_coff = d->dst_coff; p.dst_bf16 = d->dst_dtype == dt16;
     p.dst_nchw = d->dst_nchw;
     p.dst2 = (__bf16*)d->dst2; p.dst2_ld = d->dst2_ld; p.dst2_coff = d->dst2_coff;
     p.split_from = d->dst2_split_from; p.split_plane = d->dst2_plane_stride;
@@ -1210,3 +1257,5 @@ extern "C" int e2fgvi_conv2d_bf16x(const e2fgvi_convx_desc* d, void* stream) { r
 extern "C" int e2fgvi_conv2d_f32x(const e2fgvi_convx_desc* d, void* stream) { return conv2d_x(d, stream, 1); }
 /* fp32 NHWC sources, e2fgvi_pack_conv_weight_f32x3 weights: fp32 products as six exact bf16 MFMA terms (kernel MODE 2) */
 extern "C" int e2fgvi_conv2d_f32x3(const e2fgvi_convx_desc* d, void* stream) { return conv2d_x(d, stream, 2); }
+/* MODE 0 with fp16 operands (kernel MODE 3): fp16 sources, e2fgvi_pack_conv_weight_f16x weights, fp16 MFMA */
+extern "C" int e2fgvi_conv2d_f16x(const e2fgvi_convx_desc* d, void* stream) { return conv2d_x(d, stream, 3); }

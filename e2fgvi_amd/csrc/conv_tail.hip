@@ -19,7 +19,6 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int TH = 16, TW = 32, ZH = TH + 2, ZW = TW + 2, ZPIX = ZH * ZW;   // 612
 constexpr int NBLK = 5;                    // MFMA row blocks (32 pixels) per wave: 4 waves x 5 x 32 = 640 >= 612
@@ -49,8 +48,10 @@ __global__ void pack_tail_weight_kernel(const float* __restrict__ w, T* __restri
     wp[idx] = (T)(n < 27 ? w[(co * 64 + ch) * 9 + tap] : 0.f);
 }
 
-template <bool F32>
+// F16 (16-bit sources): fp16 sources and weights on v_mfma_f32_32x32x16_f16 instead of bf16
+template <bool F32, bool F16 = false>
 __global__ __launch_bounds__(256) void conv_tail_kernel(const TailParams p) {
+    typedef typename e2_h16<F16>::V8 e16x8;
     __shared__ float Z[4 * NBLK * 32 * ZS];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 31, h = lane >> 5;
     int bid = xcd_remap(blockIdx.x, gridDim.x);
@@ -105,8 +106,7 @@ __global__ __launch_bounds__(256) void conv_tail_kernel(const TailParams p) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(f[k][e], bw[k][e], acc, 0, 0, 0);
             } else {
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, f[k]), __builtin_bit_cast(bf16x8, bw[k]),
-                                                              acc, 0, 0, 0);
+                acc = e2_mfma16(__builtin_bit_cast(e16x8, f[k]), __builtin_bit_cast(e16x8, bw[k]), acc);
             }
         }
         if (blk + DEPTH < NBLK) load(fr[blk % DEPTH], blk + DEPTH);
@@ -156,9 +156,12 @@ extern "C" int64_t e2fgvi_packed_tail_weight_size(int32_t Cout, int32_t Cin) {
 extern "C" int e2fgvi_pack_tail_weight(const float* w, void* wpacked, int32_t Cout, int32_t Cin, int32_t dtype, void* stream) {
     E2_REQUIRE(w && wpacked, E2FGVI_EINVAL, "pack_tail_weight: null pointer");
     E2_REQUIRE(Cout == 3 && Cin == 64, E2FGVI_EUNSUP, "pack_tail_weight: the tail kernel is for 64 -> 3 channels (got %d -> %d)", Cin, Cout);
-    E2_REQUIRE(dtype == E2FGVI_F32 || dtype == E2FGVI_BF16, E2FGVI_EINVAL, "pack_tail_weight: dtype must be E2FGVI_F32 or E2FGVI_BF16");
+    E2_REQUIRE(dtype == E2FGVI_F32 || dtype == E2FGVI_BF16 || dtype == E2FGVI_F16, E2FGVI_EINVAL,
+               "pack_tail_weight: dtype must be E2FGVI_F32, E2FGVI_BF16 or E2FGVI_F16");
     if (dtype == E2FGVI_F32)
         hipLaunchKernelGGL((pack_tail_weight_kernel<float, true>), dim3(8), dim3(256), 0, (hipStream_t)stream, w, (float*)wpacked);
+    else if (dtype == E2FGVI_F16)
+        hipLaunchKernelGGL((pack_tail_weight_kernel<_Float16, false>), dim3(8), dim3(256), 0, (hipStream_t)stream, w, (_Float16*)wpacked);
     else
         hipLaunchKernelGGL((pack_tail_weight_kernel<__bf16, false>), dim3(8), dim3(256), 0, (hipStream_t)stream, w, (__bf16*)wpacked);
     E2_LAUNCH_CHECK("pack_tail_weight");
@@ -168,7 +171,8 @@ extern "C" int e2fgvi_pack_tail_weight(const float* w, void* wpacked, int32_t Co
 extern "C" int e2fgvi_conv3x3_tail(const void* src, int32_t src_dtype, int32_t src_ld, const void* wpacked, const float* bias,
                                    float* dst, int32_t N, int32_t H, int32_t W, int32_t act, float slope, void* stream) {
     E2_REQUIRE(src && wpacked && dst, E2FGVI_EINVAL, "conv3x3_tail: null pointer");
-    E2_REQUIRE(src_dtype == E2FGVI_F32 || src_dtype == E2FGVI_BF16, E2FGVI_EINVAL, "conv3x3_tail: src_dtype must be E2FGVI_F32 or E2FGVI_BF16");
+    E2_REQUIRE(src_dtype == E2FGVI_F32 || src_dtype == E2FGVI_BF16 || src_dtype == E2FGVI_F16, E2FGVI_EINVAL,
+               "conv3x3_tail: src_dtype must be E2FGVI_F32, E2FGVI_BF16 or E2FGVI_F16 (wpacked packed with the same dtype)");
     E2_REQUIRE(N > 0 && H > 0 && W > 0 && src_ld >= 64, E2FGVI_EINVAL, "conv3x3_tail: bad shape");
     E2_REQUIRE(src_ld % (src_dtype == E2FGVI_F32 ? 4 : 8) == 0 && ((uintptr_t)src & 15) == 0 && ((uintptr_t)wpacked & 15) == 0, E2FGVI_EINVAL,
                "conv3x3_tail: source rows must be 16-byte aligned");
@@ -181,6 +185,8 @@ extern "C" int e2fgvi_conv3x3_tail(const void* src, int32_t src_dtype, int32_t s
     E2_REQUIRE(nblk < (1ll << 31), E2FGVI_EINVAL, "conv3x3_tail: too many tiles");
     if (src_dtype == E2FGVI_F32)
         hipLaunchKernelGGL((conv_tail_kernel<true>), dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, p);
+    else if (src_dtype == E2FGVI_F16)
+        hipLaunchKernelGGL((conv_tail_kernel<false, true>), dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, p);
     else
         hipLaunchKernelGGL((conv_tail_kernel<false>), dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, p);
     E2_LAUNCH_CHECK("conv3x3_tail");

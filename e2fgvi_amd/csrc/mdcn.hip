@@ -102,10 +102,15 @@ constexpr bool mdcn_fits_lds() {
     return mdcn_smem_floats<BM, BN, WGM, WGN, KS, BF, X3>() * 4 + MAX_UNITS * 8 * 4 + KS * 2 * (2 * BM) * 8 * 4 + 1024 <= 160 * 1024;
 }
 
-template <int BM, int BN, int WGM, int WGN, int KS, bool BF, bool S16, bool X3 = false>
+// F16 (with BF and S16): the same kernel with fp16 in place of bf16 -- fp16 sources, slab, weights and MFMA (v_mfma_f32_32x32x16_f16),
+// fp16 16-bit dst
+template <int BM, int BN, int WGM, int WGN, int KS, bool BF, bool S16, bool X3 = false, bool F16 = false>
 __global__ __launch_bounds__(64 * WGM * WGN * KS) void mdcn_kernel(const DcnParams p) {
     static_assert(BF || !S16, "bf16 sources only with the bf16 MFMA slab");
     static_assert(!X3 || (BF && !S16), "the split-operand variant: bf16 LDS images of fp32 sources");
+    static_assert(!F16 || (BF && S16 && !X3), "fp16: fp16 sources and products");
+    typedef typename e2_h16<F16>::T E16;                // the 16-bit element type (slab, weights, 16-bit dst)
+    typedef typename e2_h16<F16>::V8 e16x8;
     constexpr int NP = X3 ? 3 : 1;                    // bf16 planes per operand
     constexpr int SB = S16 ? 2 : 4;                   // source element size
     constexpr int CQ = S16 ? 2 : 4;                   // 16-byte corner fetches per (row, unit): 16 channels
@@ -188,8 +193,7 @@ __global__ __launch_bounds__(64 * WGM * WGN * KS) void mdcn_kernel(const DcnPara
     f32x4 c00[2][A_IT], c01[2][A_IT], c10[2][A_IT], c11[2][A_IT];
     float w00[2][A_IT], w01[2][A_IT], w10[2][A_IT], w11[2][A_IT];
     f32x4 rb[2][B_IT];                                // fp32 MFMA path: staged weights
-    typedef __bf16 dcn_bf16x8 __attribute__((ext_vector_type(8)));
-    dcn_bf16x8 bfr[2][NP][2][TN];                     // bf16 products: B fragments [set][plane][k-step][column tile]
+    e16x8 bfr[2][NP][2][TN];                     // bf16 products: B fragments [set][plane][k-step][column tile]
 
     // ---- unit decode through a table in LDS.  A K-chunk is two units (uu = 0 / 1 by lane); unit u = ((g * KK) + tap) * cgq + cq.
     // Everything a lane needs from (g, tap, cq) -- offset / mask / flow word offsets, the tap's (ky, kx) * dilation, the
@@ -344,7 +348,7 @@ __global__ __launch_bounds__(64 * WGM * WGN * KS) void mdcn_kernel(const DcnPara
                 for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
                     for (int tn = 0; tn < TN; ++tn)
-                        bfr[S][pl][kk][tn] = __builtin_bit_cast(dcn_bf16x8, __builtin_amdgcn_raw_buffer_load_b128(
+                        bfr[S][pl][kk][tn] = __builtin_bit_cast(e16x8, __builtin_amdgcn_raw_buffer_load_b128(
                             r_w, (int)vo, (int)((unsigned)(pl * 2) * bf_oct2 + (unsigned)kk * bf_oct2 + bf_tn[tn]), 0));
         } else {
             const bool tile_ok = kt < KT;
@@ -359,7 +363,17 @@ __global__ __launch_bounds__(64 * WGM * WGN * KS) void mdcn_kernel(const DcnPara
 #pragma unroll
         for (int ia = 0; ia < A_IT; ++ia) {
             if (A_ITEMS % NG == 0 || (tid + ia * NG) < A_ITEMS) {
-                if constexpr (S16) {
+                if constexpr (F16) {         // fp16 corners: 8 channels per 16-byte fetch, blended in fp32 in the bf16 order
+                    const e16x8 h00 = __builtin_bit_cast(e16x8, c00[S][ia]), h01 = __builtin_bit_cast(e16x8, c01[S][ia]),
+                                h10 = __builtin_bit_cast(e16x8, c10[S][ia]), h11 = __builtin_bit_cast(e16x8, c11[S][ia]);
+                    e16x8 hv;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e)
+                        hv[e] = (E16)((float)h00[e] * w00[S][ia] + (float)h01[e] * w01[S][ia] + (float)h10[e] * w10[S][ia] +
+                                      (float)h11[e] * w11[S][ia]);
+                    *reinterpret_cast<e16x8*>(reinterpret_cast<E16*>(sA) + it_row[ia] * LDA16 + it_uu[ia] * 16 + it_c4[ia] * 8) = hv;
+                    continue;
+                } else if constexpr (S16) {
                     typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
                     const u32x4 q00 = __builtin_bit_cast(u32x4, c00[S][ia]), q01 = __builtin_bit_cast(u32x4, c01[S][ia]),
                                 q10 = __builtin_bit_cast(u32x4, c10[S][ia]), q11 = __builtin_bit_cast(u32x4, c11[S][ia]);
@@ -476,22 +490,21 @@ __global__ __launch_bounds__(64 * WGM * WGN * KS) void mdcn_kernel(const DcnPara
                                 acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[PA[t6]][tm], b[PB[t6]][tn], acc[tm][tn], 0, 0, 0);
                 }
             } else if (BF) {
-                typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-                const __bf16* sA16 = reinterpret_cast<const __bf16*>(sbase + cur * STAGE);
+                const E16* sA16 = reinterpret_cast<const E16*>(sbase + cur * STAGE);
                 const int li = lane & 31, lh = lane >> 5;
 #pragma unroll
                 for (int kk = 0; kk < 2; ++kk) {
-                    bf16x8 a[TM], b[TN];
+                    e16x8 a[TM], b[TN];
 #pragma unroll
                     for (int tm = 0; tm < TM; ++tm)
-                        a[tm] = *reinterpret_cast<const bf16x8*>(sA16 + ((wm * TM + tm) * 32 + li) * LDA16 + (2 * kk + lh) * 8);
+                        a[tm] = *reinterpret_cast<const e16x8*>(sA16 + ((wm * TM + tm) * 32 + li) * LDA16 + (2 * kk + lh) * 8);
 #pragma unroll
                     for (int tn = 0; tn < TN; ++tn) b[tn] = bfr[par][0][kk][tn];
 #pragma unroll
                     for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
                         for (int tn = 0; tn < TN; ++tn)
-                            acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[tm], b[tn], acc[tm][tn], 0, 0, 0);
+                            acc[tm][tn] = e2_mfma16(a[tm], b[tn], acc[tm][tn]);
                 }
             } else {
                 mma_ktile<TM, TN, BK, LDA, BN>(sbase + cur * STAGE, sbase + cur * STAGE + BM * LDA, acc, wm * TM * 32,
@@ -555,7 +568,7 @@ __global__ __launch_bounds__(64 * WGM * WGN * KS) void mdcn_kernel(const DcnPara
                 }
                 if (ok) {
                     const long long o = (long long)m * p.dst_ld + p.dst_coff + n;
-                    if (p.dst_bf16) reinterpret_cast<__bf16*>(p.dst)[o] = (__bf16)(acc[tm][tn][r] + bv);
+                    if (p.dst_bf16) reinterpret_cast<E16*>(p.dst)[o] = (E16)(acc[tm][tn][r] + bv);
                     else p.dst[o] = acc[tm][tn][r] + bv;
                 }
             }
@@ -582,8 +595,9 @@ __global__ void pack_dcn_weight_kernel(const float* __restrict__ w, float* __res
     wp[idx] = v;
 }
 
-// bf16 weights of the BF variant: [chunk][4 k-octets][Npad][8], k inside a chunk = (unit in chunk) * 16 + channel, like above
-__global__ void pack_dcn_weight_bf16_kernel(const float* __restrict__ w, __bf16* __restrict__ wp, int Cout, int C, int KK,
+// bf16 (fp16) weights of the BF variant: [chunk][4 k-octets][Npad][8], k inside a chunk = (unit in chunk) * 16 + channel, like above
+template <typename T>
+__global__ void pack_dcn_weight_bf16_kernel(const float* __restrict__ w, T* __restrict__ wp, int Cout, int C, int KK,
                                             int cg, int Npad, long long total) {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= total) return;
@@ -600,7 +614,7 @@ __global__ void pack_dcn_weight_bf16_kernel(const float* __restrict__ w, __bf16*
     const int ch = g * cg + cq * 16 + c;
     float v = 0.f;
     if (ch < C && n < Cout && g * cg < C) v = w[((long long)n * C + ch) * KK + tap];
-    wp[idx] = (__bf16)v;
+    wp[idx] = (T)v;
 }
 
 // split-operand weights (X3): [chunk][plane hi, mid, lo][4 k-octets][Npad][8] bf16; `total` counts the fp32 values
@@ -640,7 +654,7 @@ long long dcn_packed_size(int Cout, int C, int KH, int KW) {
 }
 
 template <int BM, int BN, int WGM, int WGN, int KS>
-int launch_dcn(DcnParams& p, hipStream_t st, bool bf, bool s16, bool x3 = false) {
+int launch_dcn(DcnParams& p, hipStream_t st, bool bf, bool s16, bool x3 = false, bool f16 = false) {
     p.tilesM = cdiv(p.M, BM);
     if (p.sw) {
         p.swX = cdiv(p.Wo, 8);
@@ -658,7 +672,9 @@ int launch_dcn(DcnParams& p, hipStream_t st, bool bf, bool s16, bool x3 = false)
         }
     } else if (s16 || bf) {
         if constexpr (mdcn_fits_lds<BM, BN, WGM, WGN, KS, true, false>()) {
-            if (s16)
+            if (f16)              // (fp16 products take fp16 sources only: the engine's form)
+                hipLaunchKernelGGL((mdcn_kernel<BM, BN, WGM, WGN, KS, true, true, false, true>), dim3(p.tilesM * p.tilesN), dim3(64 * WGM * WGN * KS), 0, st, p);
+            else if (s16)
                 hipLaunchKernelGGL((mdcn_kernel<BM, BN, WGM, WGN, KS, true, true>), dim3(p.tilesM * p.tilesN), dim3(64 * WGM * WGN * KS), 0, st, p);
             else
                 hipLaunchKernelGGL((mdcn_kernel<BM, BN, WGM, WGN, KS, true, false>), dim3(p.tilesM * p.tilesN), dim3(64 * WGM * WGN * KS), 0, st, p);
@@ -708,9 +724,21 @@ extern "C" int e2fgvi_pack_dcn_weight_bf16(const float* w, void* wpacked, int32_
     E2_REQUIRE(Cout > 0 && C > 0 && deform_groups > 0 && C % deform_groups == 0 && (C / deform_groups) % 16 == 0,
                E2FGVI_EUNSUP, "pack_dcn_weight_bf16: channels per deform group must be a multiple of 16");
     const long long total = dcn_packed_size(Cout, C, KH, KW);
-    hipLaunchKernelGGL(pack_dcn_weight_bf16_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, (hipStream_t)stream, w,
+    hipLaunchKernelGGL(pack_dcn_weight_bf16_kernel<__bf16>, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, (hipStream_t)stream, w,
                        (__bf16*)wpacked, Cout, C, KH * KW, C / deform_groups, round_up(Cout, 32), total);
     E2_LAUNCH_CHECK("pack_dcn_weight_bf16");
+    return 0;
+}
+/* fp16 weights for mfma_dtype = E2FGVI_F16: the bf16 layout, fp16 elements */
+extern "C" int e2fgvi_pack_dcn_weight_f16(const float* w, void* wpacked, int32_t Cout, int32_t C, int32_t KH, int32_t KW,
+                                          int32_t deform_groups, void* stream) {
+    E2_REQUIRE(w && wpacked, E2FGVI_EINVAL, "pack_dcn_weight_f16: null pointer");
+    E2_REQUIRE(Cout > 0 && C > 0 && deform_groups > 0 && C % deform_groups == 0 && (C / deform_groups) % 16 == 0,
+               E2FGVI_EUNSUP, "pack_dcn_weight_f16: channels per deform group must be a multiple of 16");
+    const long long total = dcn_packed_size(Cout, C, KH, KW);
+    hipLaunchKernelGGL(pack_dcn_weight_bf16_kernel<_Float16>, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, (hipStream_t)stream, w,
+                       (_Float16*)wpacked, Cout, C, KH * KW, C / deform_groups, round_up(Cout, 32), total);
+    E2_LAUNCH_CHECK("pack_dcn_weight_f16");
     return 0;
 }
 
@@ -732,12 +760,19 @@ extern "C" int e2fgvi_mdcn_nhwc(const e2fgvi_mdcn_desc* d, void* stream) {
     E2_REQUIRE(d->nsrc == 1 || d->nsrc == 2, E2FGVI_EINVAL, "mdcn: nsrc must be 1 or 2");
     DcnParams p;
     int C = 0;
-    E2_REQUIRE(d->src_dtype == E2FGVI_F32 || (d->src_dtype == E2FGVI_BF16 && d->mfma_dtype == E2FGVI_BF16), E2FGVI_EINVAL,
-               "mdcn: src_dtype must be E2FGVI_F32, or E2FGVI_BF16 together with mfma_dtype = E2FGVI_BF16");
-    E2_REQUIRE(d->mfma_dtype == E2FGVI_F32 || d->mfma_dtype == E2FGVI_BF16 || d->mfma_dtype == E2FGVI_BF16X3, E2FGVI_EINVAL,
-               "mdcn: mfma_dtype must be E2FGVI_F32, E2FGVI_BF16 or E2FGVI_BF16X3");
+    E2_REQUIRE(d->src_dtype == E2FGVI_F32 || (d->src_dtype == E2FGVI_BF16 && d->mfma_dtype == E2FGVI_BF16) ||
+                   (d->src_dtype == E2FGVI_F16 && d->mfma_dtype == E2FGVI_F16), E2FGVI_EINVAL,
+               "mdcn: src_dtype must be E2FGVI_F32, or E2FGVI_BF16 / E2FGVI_F16 together with the same mfma_dtype");
+    E2_REQUIRE(d->mfma_dtype == E2FGVI_F32 || d->mfma_dtype == E2FGVI_BF16 || d->mfma_dtype == E2FGVI_BF16X3 ||
+                   d->mfma_dtype == E2FGVI_F16, E2FGVI_EINVAL,
+               "mdcn: mfma_dtype must be E2FGVI_F32, E2FGVI_BF16, E2FGVI_BF16X3 or E2FGVI_F16");
     const bool x3 = d->mfma_dtype == E2FGVI_BF16X3;
-    const bool s16 = d->src_dtype == E2FGVI_BF16;
+    const bool f16 = d->mfma_dtype == E2FGVI_F16;
+    E2_REQUIRE(!f16 || d->src_dtype == E2FGVI_F16, E2FGVI_EUNSUP, "mdcn: fp16 products take fp16 sources");
+    E2_REQUIRE(d->dst_dtype == E2FGVI_F32 || d->dst_dtype == (f16 ? E2FGVI_F16 : E2FGVI_BF16), E2FGVI_EINVAL,
+               f16 ? "mdcn: dst_dtype must be E2FGVI_F32 or E2FGVI_F16 with fp16 products"
+                   : "mdcn: dst_dtype must be E2FGVI_F32 or E2FGVI_BF16");
+    const bool s16 = d->src_dtype == E2FGVI_BF16 || f16;
     const int sb = s16 ? 2 : 4;
     for (int s = 0; s < 2; ++s) { p.src[s] = nullptr; p.ld[s] = 0; p.c[s] = 0; }
     for (int s = 0; s < d->nsrc; ++s) {
@@ -763,7 +798,7 @@ extern "C" int e2fgvi_mdcn_nhwc(const e2fgvi_mdcn_desc* d, void* stream) {
                    (d->nsrc == 1 || d->src_ld[1] * 4 < (1 << 24)),
                E2FGVI_EUNSUP, "mdcn: more than 2^24 input pixels per call (split the batch)");
     E2_REQUIRE(!d->flows || d->deform_groups % 2 == 0, E2FGVI_EINVAL, "mdcn: fused flows need an even group count");
-    E2_REQUIRE(!d->src_planar || (s16 && cg == 16), E2FGVI_EUNSUP, "mdcn: src_planar needs bf16 sources and 16 channels per deform group");
+    E2_REQUIRE(!d->src_planar || (s16 && cg == 16), E2FGVI_EUNSUP, "mdcn: src_planar needs 16-bit sources and 16 channels per deform group");
     p.planar = d->src_planar ? 1 : 0;
     p.plane_bytes = (unsigned)((long long)d->N * d->H * d->W * 32);
     if (p.planar) { p.ld[0] = d->src_c[0]; p.ld[1] = d->nsrc == 2 ? d->src_c[1] : p.ld[0]; }      // byte bounds below: c / 16 planes
@@ -777,13 +812,13 @@ extern "C" int e2fgvi_mdcn_nhwc(const e2fgvi_mdcn_desc* d, void* stream) {
     p.off = d->offset; p.off_ld = d->off_ld; p.msk = d->mask; p.msk_ld = d->mask_ld;
     p.flows = d->flows; p.max_residue = d->max_residue;
     p.w = d->wpacked; p.bias = d->bias;
-    p.dst = d->dst; p.dst_ld = d->dst_ld; p.dst_coff = d->dst_coff; p.dst_bf16 = d->dst_dtype == E2FGVI_BF16;
+    p.dst = d->dst; p.dst_ld = d->dst_ld; p.dst_coff = d->dst_coff; p.dst_bf16 = d->dst_dtype != E2FGVI_F32;
     // buffer bounds (all < 4 GiB) and the source split
     {
         const long long P = (long long)d->N * d->Ho * d->Wo;
         const long long sb0 = (long long)d->N * d->H * d->W * p.ld[0] * sb, sb1 = (long long)d->N * d->H * d->W * p.ld[1] * sb;
         const long long ob = P * d->off_ld * 4, mb = P * d->mask_ld * 4,
-                        wb = dcn_packed_size(d->Cout, C, d->KH, d->KW) * (d->mfma_dtype == E2FGVI_BF16 ? 2 : x3 ? 6 : 4);
+                        wb = dcn_packed_size(d->Cout, C, d->KH, d->KW) * ((d->mfma_dtype == E2FGVI_BF16 || f16) ? 2 : x3 ? 6 : 4);
         E2_REQUIRE(sb0 < 2147483392LL && sb1 < 2147483392LL && ob < 4294967295LL && mb < 4294967295LL && wb < 4294967295LL,
                    E2FGVI_EUNSUP, "mdcn: a source spans >= 2 GiB (or offsets / masks >= 4 GiB); buffer addressing needs less (split the batch)");
         p.src_bytes[0] = (unsigned)sb0; p.src_bytes[1] = (unsigned)sb1;
@@ -807,21 +842,21 @@ extern "C" int e2fgvi_mdcn_nhwc(const e2fgvi_mdcn_desc* d, void* stream) {
         // inside the forward, where the offsets follow the smooth flow field (34.46 / 34.57 vs 34.42 / 34.58 ms, same box,
         // profiles/r02_dcn_sampler.txt): off by default, tile codes 101 ... 106 select it
         // (planar sources: the single K group wins, 143 vs 156 us on a smooth offset field, 170 vs 178 on random offsets)
-        if (tile == 1 && d->mfma_dtype == E2FGVI_BF16 && !p.planar) {
+        if (tile == 1 && (d->mfma_dtype == E2FGVI_BF16 || f16) && !p.planar) {
             tile = 6;
         }
     }
-    const bool bf = d->mfma_dtype == E2FGVI_BF16;
+    const bool bf = d->mfma_dtype == E2FGVI_BF16 || f16;
     // (round 5: with the weights out of the LDS the three-K-group tile fits with split operands too: 53.0 vs 56.0 us at 60x108,
     //  profiles/r05_dcn_tiles.txt)
-    if (tile == 1) return launch_dcn<64, 128, 2, 2, 1>(p, (hipStream_t)stream, bf, s16, x3);
-    if (tile == 2) return launch_dcn<32, 128, 1, 4, 1>(p, (hipStream_t)stream, bf, s16, x3);
-    if (tile == 3) return launch_dcn<32, 64, 1, 2, 1>(p, (hipStream_t)stream, bf, s16, x3);
-    if (tile == 4) return launch_dcn<32, 128, 1, 4, 2>(p, (hipStream_t)stream, bf, s16, x3);
-    if (tile == 5) return launch_dcn<32, 128, 1, 4, 3>(p, (hipStream_t)stream, bf, s16, x3);
-    if (tile == 6) return launch_dcn<64, 128, 2, 2, 2>(p, (hipStream_t)stream, bf, s16, x3);
+    if (tile == 1) return launch_dcn<64, 128, 2, 2, 1>(p, (hipStream_t)stream, bf, s16, x3, f16);
+    if (tile == 2) return launch_dcn<32, 128, 1, 4, 1>(p, (hipStream_t)stream, bf, s16, x3, f16);
+    if (tile == 3) return launch_dcn<32, 64, 1, 2, 1>(p, (hipStream_t)stream, bf, s16, x3, f16);
+    if (tile == 4) return launch_dcn<32, 128, 1, 4, 2>(p, (hipStream_t)stream, bf, s16, x3, f16);
+    if (tile == 5) return launch_dcn<32, 128, 1, 4, 3>(p, (hipStream_t)stream, bf, s16, x3, f16);
+    if (tile == 6) return launch_dcn<64, 128, 2, 2, 2>(p, (hipStream_t)stream, bf, s16, x3, f16);
     // four K groups (round 5: with the weights out of the LDS a stage is the A slab alone): bf16 products only
-    if (tile == 7 && (bf || x3)) return launch_dcn<32, 128, 1, 4, 4>(p, (hipStream_t)stream, bf, s16, x3);
+    if (tile == 7 && (bf || x3)) return launch_dcn<32, 128, 1, 4, 4>(p, (hipStream_t)stream, bf, s16, x3, f16);
     e2fgvi_set_error("mdcn: unknown tile %d", tile);
     return E2FGVI_EINVAL;
 }

@@ -4,14 +4,19 @@
 // channel axis (NHWC) and no intermediate copies.  Reference call sites: include/e2fgvi_hip.h.
 #include "common.h"
 
+#include <type_traits>
+
 namespace {
 
 constexpr int NTH = 256;
 
-// 4 consecutive channels as fp32, from / to fp32 (16 bytes) or bf16 (8 bytes) tensors -- the bf16 data path
-// (BASELINE.json configs 4 / 5) keeps its activations in HBM as bf16, every kernel here computes in fp32
+// 4 consecutive channels as fp32, from / to fp32 (16 bytes) or 16-bit (8 bytes) tensors -- the 16-bit data path
+// (BASELINE.json configs 4 / 5) keeps its activations in HBM as bf16 or fp16, every kernel here computes in fp32.
+// fp32 -> 16 bit rounds to nearest even (fp16: overflow to +-inf, subnormals kept, the rounding of torch's .half())
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 template <typename T> __device__ __forceinline__ f32x4 ld4(const T* p);
 template <> __device__ __forceinline__ f32x4 ld4<float>(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 template <> __device__ __forceinline__ f32x4 ld4<__bf16>(const __bf16* p) {
@@ -20,12 +25,18 @@ template <> __device__ __forceinline__ f32x4 ld4<__bf16>(const __bf16* p) {
                __builtin_bit_cast(float, q[1] << 16), __builtin_bit_cast(float, q[1] & 0xFFFF0000u)};
     return v;
 }
-// channels per thread: 4 for fp32 tensors, 8 for bf16 tensors -- a 16-byte access either way.  ldv / stv move VT<T>::N
+template <> __device__ __forceinline__ f32x4 ld4<_Float16>(const _Float16* p) {
+    const f16x4 h = *reinterpret_cast<const f16x4*>(p);
+    f32x4 v = {(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
+    return v;
+}
+// channels per thread: 4 for fp32 tensors, 8 for 16-bit tensors -- a 16-byte access either way.  ldv / stv move VT<T>::N
 // consecutive channels as VT<T>::Q fp32 quads; ldf loads the same channel count from an fp32 tensor.
 typedef unsigned int u32x4m __attribute__((ext_vector_type(4)));
 template <typename T> struct VT;
 template <> struct VT<float> { static constexpr int N = 4, Q = 1; };
 template <> struct VT<__bf16> { static constexpr int N = 8, Q = 2; };
+template <> struct VT<_Float16> { static constexpr int N = 8, Q = 2; };
 template <typename T> __device__ __forceinline__ void ldv(const T* p, f32x4 (&v)[VT<T>::Q]);
 template <> __device__ __forceinline__ void ldv<float>(const float* p, f32x4 (&v)[1]) { v[0] = *reinterpret_cast<const f32x4*>(p); }
 template <> __device__ __forceinline__ void ldv<__bf16>(const __bf16* p, f32x4 (&v)[2]) {
@@ -36,6 +47,11 @@ template <> __device__ __forceinline__ void ldv<__bf16>(const __bf16* p, f32x4 (
         v[i][2] = __builtin_bit_cast(float, q[2 * i + 1] << 16); v[i][3] = __builtin_bit_cast(float, q[2 * i + 1] & 0xFFFF0000u);
     }
 }
+template <> __device__ __forceinline__ void ldv<_Float16>(const _Float16* p, f32x4 (&v)[2]) {
+    const f16x8 h = *reinterpret_cast<const f16x8*>(p);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) v[i] = f32x4{(float)h[4 * i], (float)h[4 * i + 1], (float)h[4 * i + 2], (float)h[4 * i + 3]};
+}
 template <typename T> __device__ __forceinline__ void stv(T* p, const f32x4 (&v)[VT<T>::Q]);
 template <> __device__ __forceinline__ void stv<float>(float* p, const f32x4 (&v)[1]) { *reinterpret_cast<f32x4*>(p) = v[0]; }
 template <> __device__ __forceinline__ void stv<__bf16>(__bf16* p, const f32x4 (&v)[2]) {
@@ -43,6 +59,11 @@ template <> __device__ __forceinline__ void stv<__bf16>(__bf16* p, const f32x4 (
     bf16x8m h = {(__bf16)v[0][0], (__bf16)v[0][1], (__bf16)v[0][2], (__bf16)v[0][3],
                  (__bf16)v[1][0], (__bf16)v[1][1], (__bf16)v[1][2], (__bf16)v[1][3]};
     *reinterpret_cast<bf16x8m*>(p) = h;
+}
+template <> __device__ __forceinline__ void stv<_Float16>(_Float16* p, const f32x4 (&v)[2]) {
+    f16x8 h = {(_Float16)v[0][0], (_Float16)v[0][1], (_Float16)v[0][2], (_Float16)v[0][3],
+               (_Float16)v[1][0], (_Float16)v[1][1], (_Float16)v[1][2], (_Float16)v[1][3]};
+    *reinterpret_cast<f16x8*>(p) = h;
 }
 template <int Q> __device__ __forceinline__ void ldf(const float* p, f32x4 (&v)[Q]) {
 #pragma unroll
@@ -53,6 +74,10 @@ template <> __device__ __forceinline__ void st4<float>(float* p, f32x4 v) { *rei
 template <> __device__ __forceinline__ void st4<__bf16>(__bf16* p, f32x4 v) {
     bf16x4 h = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
     *reinterpret_cast<bf16x4*>(p) = h;
+}
+template <> __device__ __forceinline__ void st4<_Float16>(_Float16* p, f32x4 v) {
+    f16x4 h = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
+    *reinterpret_cast<f16x4*>(p) = h;
 }
 
 // Flat thread index -> coordinates.  A 64-bit division by a run-time value is ~100 instructions on this ISA, a 32-bit
@@ -237,10 +262,11 @@ __global__ void avgpool2_kernel(const float* __restrict__ src, float* __restrict
 }
 
 // ------------------------------------------------------------------------------------------ SPyNet
-// one thread per (pair, y, x)
+// one thread per (pair, y, x); T16: the element type of the 16-bit copy
+template <typename T16>
 __global__ void spynet_level_input_kernel(const float* __restrict__ pyr, const int* __restrict__ ref_idx,
                                           const int* __restrict__ supp_idx, const float* __restrict__ flow_prev,
-                                          float* __restrict__ out, __bf16* __restrict__ out16, int Np, int h, int w) {
+                                          float* __restrict__ out, T16* __restrict__ out16, int Np, int h, int w) {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (long long)Np * h * w) return;
     FlatIdx fi(idx, (long long)Np * h * w);
@@ -285,7 +311,7 @@ __global__ void spynet_level_input_kernel(const float* __restrict__ pyr, const i
     f32x4 o1 = {sv[1], sv[2], fu, fv};
     *reinterpret_cast<f32x4*>(o) = o0;
     *reinterpret_cast<f32x4*>(o + 4) = o1;
-    if (out16) {                           // the same 8 channels as the bf16 source of the level's conv stack
+    if (out16) {                           // the same 8 channels as the 16-bit source of the level's conv stack
         st4(out16 + idx * 8, o0);
         st4(out16 + idx * 8 + 4, o1);
     }
@@ -319,13 +345,15 @@ template <typename TS, int Q> __device__ __forceinline__ void ld_src(const TS* p
 template <> __device__ __forceinline__ void ld_src<float, 1>(const float* p, f32x4 (&v)[1]) { ldf<1>(p, v); }
 template <> __device__ __forceinline__ void ld_src<float, 2>(const float* p, f32x4 (&v)[2]) { ldf<2>(p, v); }
 template <> __device__ __forceinline__ void ld_src<__bf16, 2>(const __bf16* p, f32x4 (&v)[2]) { ldv<__bf16>(p, v); }
+template <> __device__ __forceinline__ void ld_src<_Float16, 2>(const _Float16* p, f32x4 (&v)[2]) { ldv<_Float16>(p, v); }
 
-// thread = (pixel, 4-channel chunk); C/4 threads per pixel
-template <typename TC, typename TS>
+// thread = (pixel, 4-channel chunk); C/4 threads per pixel.  T8: the element type of the flows8 copy (the cond's when it is
+// 16-bit, bf16 beside an fp32 cond)
+template <typename TC, typename TS, typename T8 = TC>
 __global__ void prop_cond_kernel(const TS* __restrict__ fp, int fp_ld, const TS* __restrict__ f2, int f2_ld,
                                  const float* __restrict__ flow_a, const float* __restrict__ flow_b,
                                  long long flow_img_stride, TC* __restrict__ cond, float* __restrict__ flows,
-                                 __bf16* __restrict__ flows8, int N, int H, int W, int C) {
+                                 T8* __restrict__ flows8, int N, int H, int W, int C) {
     constexpr int NV = VT<TC>::N, Q = VT<TC>::Q;
     const int cq = C / NV;
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -372,7 +400,7 @@ __global__ void prop_cond_kernel(const TS* __restrict__ fp, int fp_ld, const TS*
     if (c4 == 0) {
         f32x4 fo = {f1.x, f1.y, fl2.x, fl2.y};
         *reinterpret_cast<f32x4*>(flows + pix * 4) = fo;
-        if (flows8) {                      // the same four values as a bf16 conv source, padded to 8 channels
+        if (flows8) {                      // the same four values as a 16-bit conv source, padded to 8 channels
             const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
             st4(flows8 + pix * 8, fo);
             st4(flows8 + pix * 8 + 4, z4);
@@ -552,7 +580,7 @@ __global__ void unfold_gelu_kernel(const T* __restrict__ folded, T* __restrict__
     stv(out + idx * NV, v);
 }
 
-// fp32 <-> bf16 element conversion (4 elements per thread)
+// fp32 <-> bf16 / fp16 element conversion (4 elements per thread)
 template <typename TI, typename TO>
 __global__ void cast_kernel(const TI* __restrict__ src, TO* __restrict__ dst, long long n4) {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -561,9 +589,18 @@ __global__ void cast_kernel(const TI* __restrict__ src, TO* __restrict__ dst, lo
 
 inline unsigned blocks_for(long long total) { return (unsigned)cdiv64(total, NTH); }
 
+// f((T*)nullptr) with T the element type of dtype: float, __bf16 or _Float16 (the typed helpers' one launch site per kernel)
+template <typename Fn> void with_dtype(int dt, Fn&& f) {
+    if (dt == E2FGVI_BF16) f((__bf16*)nullptr);
+    else if (dt == E2FGVI_F16) f((_Float16*)nullptr);
+    else f((float*)nullptr);
+}
+#define E2_ELEM(z) std::remove_pointer_t<decltype(z)>
+
 }  // namespace
 
-#define E2_DT_OK(dt) ((dt) == E2FGVI_F32 || (dt) == E2FGVI_BF16)
+#define E2_DT_OK(dt) ((dt) == E2FGVI_F32 || (dt) == E2FGVI_BF16 || (dt) == E2FGVI_F16)
+#define E2_DT16(dt) ((dt) == E2FGVI_BF16 || (dt) == E2FGVI_F16)
 
 extern "C" int e2fgvi_nchw_to_nhwc_x(const float* src, void* dst, int32_t dst_dtype, int32_t N, int32_t C, int32_t H, int32_t W,
                                      int32_t ld, float scale, float shift, void* stream) {
@@ -571,31 +608,27 @@ extern "C" int e2fgvi_nchw_to_nhwc_x(const float* src, void* dst, int32_t dst_dt
                "nchw_to_nhwc: bad arguments");
     if (ld == 8 && C <= 8 && ((uintptr_t)dst & 15) == 0) {
         const long long total = (long long)N * H * W;
-        if (dst_dtype == E2FGVI_BF16)
-            hipLaunchKernelGGL(nchw_small_to_nhwc8_kernel<__bf16>, dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream, src,
-                               (__bf16*)dst, C, H * W, scale, shift, total);
-        else
-            hipLaunchKernelGGL(nchw_small_to_nhwc8_kernel<float>, dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream, src,
-                               (float*)dst, C, H * W, scale, shift, total);
+        with_dtype(dst_dtype, [&](auto z) {
+            hipLaunchKernelGGL(nchw_small_to_nhwc8_kernel<E2_ELEM(z)>, dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream, src,
+                               (E2_ELEM(z)*)dst, C, H * W, scale, shift, total);
+        });
         E2_LAUNCH_CHECK("nchw_to_nhwc8");
         return 0;
     }
     if (ld == 4 && C <= 4 && ((uintptr_t)dst & 15) == 0) {
         const long long total = (long long)N * H * W;
-        if (dst_dtype == E2FGVI_BF16)
-            hipLaunchKernelGGL(nchw_small_to_nhwc4_kernel<__bf16>, dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream, src,
-                               (__bf16*)dst, C, H * W, scale, shift, total);
-        else
-            hipLaunchKernelGGL(nchw_small_to_nhwc4_kernel<float>, dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream, src,
-                               (float*)dst, C, H * W, scale, shift, total);
+        with_dtype(dst_dtype, [&](auto z) {
+            hipLaunchKernelGGL(nchw_small_to_nhwc4_kernel<E2_ELEM(z)>, dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream, src,
+                               (E2_ELEM(z)*)dst, C, H * W, scale, shift, total);
+        });
         E2_LAUNCH_CHECK("nchw_to_nhwc4");
         return 0;
     }
     dim3 grid(cdiv(H * W, 32), cdiv(ld, 32), N), block(32, 8);
-    if (dst_dtype == E2FGVI_BF16)
-        hipLaunchKernelGGL(nchw_to_nhwc_kernel<__bf16>, grid, block, 0, (hipStream_t)stream, src, (__bf16*)dst, C, H * W, ld, scale, shift);
-    else
-        hipLaunchKernelGGL(nchw_to_nhwc_kernel<float>, grid, block, 0, (hipStream_t)stream, src, (float*)dst, C, H * W, ld, scale, shift);
+    with_dtype(dst_dtype, [&](auto z) {
+        hipLaunchKernelGGL(nchw_to_nhwc_kernel<E2_ELEM(z)>, grid, block, 0, (hipStream_t)stream, src, (E2_ELEM(z)*)dst, C, H * W, ld,
+                           scale, shift);
+    });
     E2_LAUNCH_CHECK("nchw_to_nhwc");
     return 0;
 }
@@ -647,19 +680,28 @@ extern "C" int e2fgvi_resize_bilinear(const float* src, int32_t src_nchw, int32_
     return 0;
 }
 
-extern "C" int e2fgvi_resize_bilinear_bf16(const void* src, int32_t src_ld, void* dst, int32_t dst_ld, int32_t N, int32_t C,
-                                           int32_t H, int32_t W, int32_t Ho, int32_t Wo, int32_t align_corners, void* stream) {
+template <typename T>
+static int resize_bilinear_16(const char* name, const void* src, int32_t src_ld, void* dst, int32_t dst_ld, int32_t N, int32_t C,
+                              int32_t H, int32_t W, int32_t Ho, int32_t Wo, int32_t align_corners, void* stream) {
     E2_REQUIRE(src && dst && N > 0 && C > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0 && dst_ld >= C && src_ld >= C && C % 8 == 0 &&
                    src_ld % 8 == 0 && dst_ld % 8 == 0 && (((uintptr_t)src | (uintptr_t)dst) & 15) == 0,
-               E2FGVI_EINVAL, "resize_bilinear_bf16: bad arguments (NHWC bf16, channels in multiples of 8)");
+               E2FGVI_EINVAL, "%s: bad arguments (NHWC 16-bit, channels in multiples of 8)", name);
     float sh, sw;
     resize_scales(H, W, Ho, Wo, align_corners, sh, sw);
     const long long total4 = (long long)N * Ho * Wo * (C / 8);
-    hipLaunchKernelGGL(resize_bilinear_vec4_kernel<__bf16>, dim3(blocks_for(total4)), dim3(NTH), 0, (hipStream_t)stream,
-                       (const __bf16*)src, src_ld, (__bf16*)dst, dst_ld, N, C / 8, H, W, Ho, Wo, align_corners, sh, sw,
+    hipLaunchKernelGGL(resize_bilinear_vec4_kernel<T>, dim3(blocks_for(total4)), dim3(NTH), 0, (hipStream_t)stream,
+                       (const T*)src, src_ld, (T*)dst, dst_ld, N, C / 8, H, W, Ho, Wo, align_corners, sh, sw,
                        (const float*)nullptr, (const float*)nullptr, total4);
-    E2_LAUNCH_CHECK("resize_bilinear_bf16");
+    E2_LAUNCH_CHECK(name);
     return 0;
+}
+extern "C" int e2fgvi_resize_bilinear_bf16(const void* src, int32_t src_ld, void* dst, int32_t dst_ld, int32_t N, int32_t C,
+                                           int32_t H, int32_t W, int32_t Ho, int32_t Wo, int32_t align_corners, void* stream) {
+    return resize_bilinear_16<__bf16>("resize_bilinear_bf16", src, src_ld, dst, dst_ld, N, C, H, W, Ho, Wo, align_corners, stream);
+}
+extern "C" int e2fgvi_resize_bilinear_f16(const void* src, int32_t src_ld, void* dst, int32_t dst_ld, int32_t N, int32_t C,
+                                          int32_t H, int32_t W, int32_t Ho, int32_t Wo, int32_t align_corners, void* stream) {
+    return resize_bilinear_16<_Float16>("resize_bilinear_f16", src, src_ld, dst, dst_ld, N, C, H, W, Ho, Wo, align_corners, stream);
 }
 
 extern "C" int e2fgvi_avgpool2_nhwc(const float* src, float* dst, int32_t N, int32_t H, int32_t W, int32_t C,
@@ -678,8 +720,20 @@ extern "C" int e2fgvi_spynet_level_input_x(const float* pyr, const int32_t* ref_
     E2_REQUIRE(pyr && ref_idx && supp_idx && out && Np > 0 && h > 0 && w > 0, E2FGVI_EINVAL, "spynet_level_input: bad arguments");
     E2_REQUIRE(!flow_prev || (h % 2 == 0 && w % 2 == 0), E2FGVI_EINVAL, "spynet_level_input: odd level size");
     const long long total = (long long)Np * h * w;
-    hipLaunchKernelGGL(spynet_level_input_kernel, dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream, pyr, ref_idx,
+    hipLaunchKernelGGL(spynet_level_input_kernel<__bf16>, dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream, pyr, ref_idx,
                        supp_idx, flow_prev, out, (__bf16*)out_bf16, Np, h, w);
+    E2_LAUNCH_CHECK("spynet_level_input");
+    return 0;
+}
+/* ... with the 16-bit copy as fp16 */
+extern "C" int e2fgvi_spynet_level_input_x_f16(const float* pyr, const int32_t* ref_idx, const int32_t* supp_idx,
+                                               const float* flow_prev, float* out, void* out_f16, int32_t Np, int32_t h, int32_t w,
+                                               void* stream) {
+    E2_REQUIRE(pyr && ref_idx && supp_idx && out && Np > 0 && h > 0 && w > 0, E2FGVI_EINVAL, "spynet_level_input: bad arguments");
+    E2_REQUIRE(!flow_prev || (h % 2 == 0 && w % 2 == 0), E2FGVI_EINVAL, "spynet_level_input: odd level size");
+    const long long total = (long long)Np * h * w;
+    hipLaunchKernelGGL(spynet_level_input_kernel<_Float16>, dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream, pyr, ref_idx,
+                       supp_idx, flow_prev, out, (_Float16*)out_f16, Np, h, w);
     E2_LAUNCH_CHECK("spynet_level_input");
     return 0;
 }
@@ -696,15 +750,19 @@ extern "C" int e2fgvi_prop_cond_xs(const void* feat_prop, int32_t fp_ld, const v
     if (src_dtype == E2FGVI_F32)
         return e2fgvi_prop_cond_x((const float*)feat_prop, fp_ld, (const float*)feat_n2, f2_ld, flow_a, flow_b, flow_img_stride, cond,
                                   cond_dtype, flows, flows8_bf16, N, H, W, C, stream);
-    E2_REQUIRE(src_dtype == E2FGVI_BF16 && cond_dtype == E2FGVI_BF16, E2FGVI_EINVAL, "prop_cond: bf16 sources need a bf16 cond");
+    E2_REQUIRE(E2_DT16(src_dtype) && cond_dtype == src_dtype, E2FGVI_EINVAL, "prop_cond: 16-bit sources need a cond of their type");
     E2_REQUIRE(feat_prop && flow_a && cond && flows && N > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0 && fp_ld % 8 == 0 &&
                    ((uintptr_t)feat_prop & 15) == 0,
                E2FGVI_EINVAL, "prop_cond: bad arguments");
     E2_REQUIRE(!flow_b || (feat_n2 && f2_ld % 8 == 0 && ((uintptr_t)feat_n2 & 15) == 0), E2FGVI_EINVAL, "prop_cond: flow_b needs feat_n2");
     const long long total = (long long)N * H * W * (C / 8);
-    hipLaunchKernelGGL((prop_cond_kernel<__bf16, __bf16>), dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream,
-                       (const __bf16*)feat_prop, fp_ld, (const __bf16*)feat_n2, f2_ld, flow_a, flow_b, (long long)flow_img_stride,
-                       (__bf16*)cond, flows, (__bf16*)flows8_bf16, N, H, W, C);
+    with_dtype(src_dtype, [&](auto z) {
+        using T = E2_ELEM(z);
+        if constexpr (!std::is_same_v<T, float>)
+            hipLaunchKernelGGL((prop_cond_kernel<T, T>), dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream,
+                               (const T*)feat_prop, fp_ld, (const T*)feat_n2, f2_ld, flow_a, flow_b, (long long)flow_img_stride,
+                               (T*)cond, flows, (T*)flows8_bf16, N, H, W, C);
+    });
     E2_LAUNCH_CHECK("prop_cond");
     return 0;
 }
@@ -717,15 +775,19 @@ extern "C" int e2fgvi_prop_cond_x(const float* feat_prop, int32_t fp_ld, const f
                    E2_DT_OK(cond_dtype),
                E2FGVI_EINVAL, "prop_cond: bad arguments");
     E2_REQUIRE(!flow_b || (feat_n2 && f2_ld % 4 == 0), E2FGVI_EINVAL, "prop_cond: flow_b needs feat_n2");
-    const int nv = cond_dtype == E2FGVI_BF16 ? 8 : 4;             // channels per thread
+    const int nv = E2_DT16(cond_dtype) ? 8 : 4;                   // channels per thread
     E2_REQUIRE(C % nv == 0, E2FGVI_EINVAL, "prop_cond: C must be a multiple of %d", nv);
     const long long total = (long long)N * H * W * (C / nv);
     if (cond_dtype == E2FGVI_BF16)
         hipLaunchKernelGGL((prop_cond_kernel<__bf16, float>), dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream, feat_prop, fp_ld,
                            feat_n2, f2_ld, flow_a, flow_b, (long long)flow_img_stride, (__bf16*)cond, flows,
                            (__bf16*)flows8_bf16, N, H, W, C);
+    else if (cond_dtype == E2FGVI_F16)
+        hipLaunchKernelGGL((prop_cond_kernel<_Float16, float>), dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream, feat_prop,
+                           fp_ld, feat_n2, f2_ld, flow_a, flow_b, (long long)flow_img_stride, (_Float16*)cond, flows,
+                           (_Float16*)flows8_bf16, N, H, W, C);
     else
-        hipLaunchKernelGGL((prop_cond_kernel<float, float>), dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream, feat_prop, fp_ld,
+        hipLaunchKernelGGL((prop_cond_kernel<float, float, __bf16>), dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream, feat_prop, fp_ld,
                            feat_n2, f2_ld, flow_a, flow_b, (long long)flow_img_stride, (float*)cond, flows,
                            (__bf16*)flows8_bf16, N, H, W, C);
     E2_LAUNCH_CHECK("prop_cond");
@@ -755,8 +817,9 @@ extern "C" int e2fgvi_layernorm_x(const float* x, const float* gamma, const floa
                                   int32_t C, void* stream) {
     E2_REQUIRE(x && gamma && beta && y && rows > 0 && E2_DT_OK(y_dtype), E2FGVI_EINVAL, "layernorm: bad arguments");
     E2_REQUIRE(C == 256 || C == 512 || C == 768 || C == 1024, E2FGVI_EUNSUP, "layernorm: C must be 256/512/768/1024");
-    return y_dtype == E2FGVI_BF16 ? layernorm_launch(x, gamma, beta, (__bf16*)y, rows, C, (hipStream_t)stream)
-                                  : layernorm_launch(x, gamma, beta, (float*)y, rows, C, (hipStream_t)stream);
+    int rc = 0;
+    with_dtype(y_dtype, [&](auto z) { rc = layernorm_launch(x, gamma, beta, (E2_ELEM(z)*)y, rows, C, (hipStream_t)stream); });
+    return rc;
 }
 extern "C" int e2fgvi_layernorm(const float* x, const float* gamma, const float* beta, float* y, int64_t rows, int32_t C,
                                 void* stream) {
@@ -768,14 +831,13 @@ extern "C" int e2fgvi_window_pool_x(const void* x, int32_t dtype, const float* w
     E2_REQUIRE(x && w45 && bias1 && pooled && BT > 0 && fh > 0 && fw > 0 && fh % 5 == 0 && fw % 9 == 0 && C % 4 == 0 &&
                    E2_DT_OK(dtype),
                E2FGVI_EINVAL, "window_pool: bad arguments");
-    E2_REQUIRE(dtype == E2FGVI_F32 || C % 8 == 0, E2FGVI_EINVAL, "window_pool: bf16 needs C %% 8 == 0");
-    const long long total = (long long)BT * (fh / 5) * (fw / 9) * (C / (dtype == E2FGVI_BF16 ? 8 : 4));
-    if (dtype == E2FGVI_BF16)
-        hipLaunchKernelGGL(window_pool_kernel<__bf16>, dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream,
-                           (const __bf16*)x, w45, bias1, (__bf16*)pooled, BT, fh, fw, C);
-    else
-        hipLaunchKernelGGL(window_pool_kernel<float>, dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream,
-                           (const float*)x, w45, bias1, (float*)pooled, BT, fh, fw, C);
+    E2_REQUIRE(dtype == E2FGVI_F32 || C % 8 == 0, E2FGVI_EINVAL, "window_pool: 16-bit needs C %% 8 == 0");
+    const long long total = (long long)BT * (fh / 5) * (fw / 9) * (C / (E2_DT16(dtype) ? 8 : 4));
+    with_dtype(dtype, [&](auto z) {
+        using T = E2_ELEM(z);
+        hipLaunchKernelGGL(window_pool_kernel<T>, dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream,
+                           (const T*)x, w45, bias1, (T*)pooled, BT, fh, fw, C);
+    });
     E2_LAUNCH_CHECK("window_pool");
     return 0;
 }
@@ -795,14 +857,13 @@ extern "C" int e2fgvi_ffn_fold_x(const void* hid, void* folded, int32_t dtype, i
                                  int32_t W, int32_t C, void* stream) {
     E2_REQUIRE(hid && folded && E2_DT_OK(dtype), E2FGVI_EINVAL, "ffn_fold: bad arguments");
     if (int rc = check_fold("ffn_fold", F, fh, fw, H, W, C)) return rc;
-    E2_REQUIRE(dtype == E2FGVI_F32 || C % 8 == 0, E2FGVI_EINVAL, "ffn_fold: bf16 needs C %% 8 == 0");
-    const long long total = (long long)F * H * W * (C / (dtype == E2FGVI_BF16 ? 8 : 4));
-    if (dtype == E2FGVI_BF16)
-        hipLaunchKernelGGL((fold_kernel<true, __bf16, __bf16, __bf16>), dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream,
-                           (const __bf16*)hid, (const float*)nullptr, (const __bf16*)nullptr, (__bf16*)folded, F, fh, fw, H, W, C);
-    else
-        hipLaunchKernelGGL((fold_kernel<true, float, float, float>), dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream,
-                           (const float*)hid, (const float*)nullptr, (const float*)nullptr, (float*)folded, F, fh, fw, H, W, C);
+    E2_REQUIRE(dtype == E2FGVI_F32 || C % 8 == 0, E2FGVI_EINVAL, "ffn_fold: 16-bit needs C %% 8 == 0");
+    const long long total = (long long)F * H * W * (C / (E2_DT16(dtype) ? 8 : 4));
+    with_dtype(dtype, [&](auto z) {
+        using T = E2_ELEM(z);
+        hipLaunchKernelGGL((fold_kernel<true, T, T, T>), dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream,
+                           (const T*)hid, (const float*)nullptr, (const T*)nullptr, (T*)folded, F, fh, fw, H, W, C);
+    });
     E2_LAUNCH_CHECK("ffn_fold");
     return 0;
 }
@@ -815,14 +876,13 @@ extern "C" int e2fgvi_ffn_unfold_gelu_x(const void* folded, void* out, int32_t d
                                         int32_t H, int32_t W, int32_t C, void* stream) {
     E2_REQUIRE(folded && out && E2_DT_OK(dtype), E2FGVI_EINVAL, "ffn_unfold_gelu: bad arguments");
     if (int rc = check_fold("ffn_unfold_gelu", F, fh, fw, H, W, C)) return rc;
-    E2_REQUIRE(dtype == E2FGVI_F32 || C % 8 == 0, E2FGVI_EINVAL, "ffn_unfold_gelu: bf16 needs C %% 8 == 0");
-    const long long total = (long long)F * fh * fw * 49 * (C / (dtype == E2FGVI_BF16 ? 8 : 4));
-    if (dtype == E2FGVI_BF16)
-        hipLaunchKernelGGL(unfold_gelu_kernel<__bf16>, dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream,
-                           (const __bf16*)folded, (__bf16*)out, F, fh, fw, H, W, C);
-    else
-        hipLaunchKernelGGL(unfold_gelu_kernel<float>, dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream,
-                           (const float*)folded, (float*)out, F, fh, fw, H, W, C);
+    E2_REQUIRE(dtype == E2FGVI_F32 || C % 8 == 0, E2FGVI_EINVAL, "ffn_unfold_gelu: 16-bit needs C %% 8 == 0");
+    const long long total = (long long)F * fh * fw * 49 * (C / (E2_DT16(dtype) ? 8 : 4));
+    with_dtype(dtype, [&](auto z) {
+        using T = E2_ELEM(z);
+        hipLaunchKernelGGL(unfold_gelu_kernel<T>, dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream,
+                           (const T*)folded, (T*)out, F, fh, fw, H, W, C);
+    });
     E2_LAUNCH_CHECK("ffn_unfold_gelu");
     return 0;
 }
@@ -837,14 +897,13 @@ extern "C" int e2fgvi_ffn_fold_gelu_x(const void* hid, void* folded, int32_t dty
                                       int32_t W, int32_t C, void* stream) {
     E2_REQUIRE(hid && folded && E2_DT_OK(dtype), E2FGVI_EINVAL, "ffn_fold_gelu: bad arguments");
     if (int rc = check_fold("ffn_fold_gelu", F, fh, fw, H, W, C)) return rc;
-    E2_REQUIRE(dtype == E2FGVI_F32 || C % 8 == 0, E2FGVI_EINVAL, "ffn_fold_gelu: bf16 needs C %% 8 == 0");
-    const long long total = (long long)F * H * W * (C / (dtype == E2FGVI_BF16 ? 8 : 4));
-    if (dtype == E2FGVI_BF16)
-        hipLaunchKernelGGL((fold_kernel<true, __bf16, __bf16, __bf16, true>), dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream,
-                           (const __bf16*)hid, (const float*)nullptr, (const __bf16*)nullptr, (__bf16*)folded, F, fh, fw, H, W, C);
-    else
-        hipLaunchKernelGGL((fold_kernel<true, float, float, float, true>), dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream,
-                           (const float*)hid, (const float*)nullptr, (const float*)nullptr, (float*)folded, F, fh, fw, H, W, C);
+    E2_REQUIRE(dtype == E2FGVI_F32 || C % 8 == 0, E2FGVI_EINVAL, "ffn_fold_gelu: 16-bit needs C %% 8 == 0");
+    const long long total = (long long)F * H * W * (C / (E2_DT16(dtype) ? 8 : 4));
+    with_dtype(dtype, [&](auto z) {
+        using T = E2_ELEM(z);
+        hipLaunchKernelGGL((fold_kernel<true, T, T, T, true>), dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream,
+                           (const T*)hid, (const float*)nullptr, (const T*)nullptr, (T*)folded, F, fh, fw, H, W, C);
+    });
     E2_LAUNCH_CHECK("ffn_fold_gelu");
     return 0;
 }
@@ -852,14 +911,13 @@ extern "C" int e2fgvi_ffn_unfold_x(const void* folded, void* out, int32_t dtype,
                                    int32_t W, int32_t C, void* stream) {
     E2_REQUIRE(folded && out && E2_DT_OK(dtype), E2FGVI_EINVAL, "ffn_unfold: bad arguments");
     if (int rc = check_fold("ffn_unfold", F, fh, fw, H, W, C)) return rc;
-    E2_REQUIRE(dtype == E2FGVI_F32 || C % 8 == 0, E2FGVI_EINVAL, "ffn_unfold: bf16 needs C %% 8 == 0");
-    const long long total = (long long)F * fh * fw * 49 * (C / (dtype == E2FGVI_BF16 ? 8 : 4));
-    if (dtype == E2FGVI_BF16)
-        hipLaunchKernelGGL((unfold_gelu_kernel<__bf16, false>), dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream,
-                           (const __bf16*)folded, (__bf16*)out, F, fh, fw, H, W, C);
-    else
-        hipLaunchKernelGGL((unfold_gelu_kernel<float, false>), dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream,
-                           (const float*)folded, (float*)out, F, fh, fw, H, W, C);
+    E2_REQUIRE(dtype == E2FGVI_F32 || C % 8 == 0, E2FGVI_EINVAL, "ffn_unfold: 16-bit needs C %% 8 == 0");
+    const long long total = (long long)F * fh * fw * 49 * (C / (E2_DT16(dtype) ? 8 : 4));
+    with_dtype(dtype, [&](auto z) {
+        using T = E2_ELEM(z);
+        hipLaunchKernelGGL((unfold_gelu_kernel<T, false>), dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream,
+                           (const T*)folded, (T*)out, F, fh, fw, H, W, C);
+    });
     E2_LAUNCH_CHECK("ffn_unfold");
     return 0;
 }
@@ -874,34 +932,51 @@ extern "C" int e2fgvi_softcomp_fold(const float* emb, const float* bias_hwc, con
     E2_LAUNCH_CHECK("softcomp_fold");
     return 0;
 }
-/* bf16 data path: emb, residual and dst are bf16 (bias_hwc stays fp32) */
+/* 16-bit data path: emb, residual and dst are bf16 / fp16 (bias_hwc stays fp32) */
+template <typename T>
+static int softcomp_fold_16(const char* name, const void* emb, const float* bias_hwc, const void* residual, void* dst, int32_t F,
+                            int32_t fh, int32_t fw, int32_t H, int32_t W, int32_t C, void* stream) {
+    E2_REQUIRE(emb && dst, E2FGVI_EINVAL, "%s: null pointer", name);
+    if (int rc = check_fold(name, F, fh, fw, H, W, C)) return rc;
+    E2_REQUIRE(C % 8 == 0, E2FGVI_EINVAL, "%s: C %% 8 != 0", name);
+    const long long total = (long long)F * H * W * (C / 8);
+    hipLaunchKernelGGL((fold_kernel<false, T, T, T>), dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream,
+                       (const T*)emb, bias_hwc, (const T*)residual, (T*)dst, F, fh, fw, H, W, C);
+    E2_LAUNCH_CHECK(name);
+    return 0;
+}
 extern "C" int e2fgvi_softcomp_fold_bf16(const void* emb, const float* bias_hwc, const void* residual, void* dst, int32_t F,
                                          int32_t fh, int32_t fw, int32_t H, int32_t W, int32_t C, void* stream) {
-    E2_REQUIRE(emb && dst, E2FGVI_EINVAL, "softcomp_fold_bf16: null pointer");
-    if (int rc = check_fold("softcomp_fold_bf16", F, fh, fw, H, W, C)) return rc;
-    E2_REQUIRE(C % 8 == 0, E2FGVI_EINVAL, "softcomp_fold_bf16: C %% 8 != 0");
-    const long long total = (long long)F * H * W * (C / 8);
-    hipLaunchKernelGGL((fold_kernel<false, __bf16, __bf16, __bf16>), dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream,
-                       (const __bf16*)emb, bias_hwc, (const __bf16*)residual, (__bf16*)dst, F, fh, fw, H, W, C);
-    E2_LAUNCH_CHECK("softcomp_fold_bf16");
-    return 0;
+    return softcomp_fold_16<__bf16>("softcomp_fold_bf16", emb, bias_hwc, residual, dst, F, fh, fw, H, W, C, stream);
+}
+extern "C" int e2fgvi_softcomp_fold_f16(const void* emb, const float* bias_hwc, const void* residual, void* dst, int32_t F,
+                                        int32_t fh, int32_t fw, int32_t H, int32_t W, int32_t C, void* stream) {
+    return softcomp_fold_16<_Float16>("softcomp_fold_f16", emb, bias_hwc, residual, dst, F, fh, fw, H, W, C, stream);
 }
 
 extern "C" int e2fgvi_cast(const void* src, int32_t src_dtype, void* dst, int32_t dst_dtype, int64_t n, void* stream) {
-    E2_REQUIRE(src && dst && n > 0 && n % 4 == 0 && E2_DT_OK(src_dtype) && E2_DT_OK(dst_dtype) && src_dtype != dst_dtype &&
-                   (((uintptr_t)src | (uintptr_t)dst) & 7) == 0,
-               E2FGVI_EINVAL, "cast: bad arguments (n must be a multiple of 4, dtypes must differ)");
+    E2_REQUIRE(src && dst && n > 0 && n % 4 == 0 && E2_DT_OK(src_dtype) && E2_DT_OK(dst_dtype) &&
+                   (src_dtype == E2FGVI_F32) != (dst_dtype == E2FGVI_F32) && (((uintptr_t)src | (uintptr_t)dst) & 7) == 0,
+               E2FGVI_EINVAL, "cast: bad arguments (n must be a multiple of 4, one side fp32, the other bf16 / fp16)");
     if (src_dtype == E2FGVI_F32)
-        hipLaunchKernelGGL((cast_kernel<float, __bf16>), dim3(blocks_for(n / 4)), dim3(NTH), 0, (hipStream_t)stream,
-                           (const float*)src, (__bf16*)dst, (long long)(n / 4));
+        with_dtype(dst_dtype, [&](auto z) {
+            using T = E2_ELEM(z);
+            if constexpr (!std::is_same_v<T, float>)
+                hipLaunchKernelGGL((cast_kernel<float, T>), dim3(blocks_for(n / 4)), dim3(NTH), 0, (hipStream_t)stream,
+                                   (const float*)src, (T*)dst, (long long)(n / 4));
+        });
     else
-        hipLaunchKernelGGL((cast_kernel<__bf16, float>), dim3(blocks_for(n / 4)), dim3(NTH), 0, (hipStream_t)stream,
-                           (const __bf16*)src, (float*)dst, (long long)(n / 4));
+        with_dtype(src_dtype, [&](auto z) {
+            using T = E2_ELEM(z);
+            if constexpr (!std::is_same_v<T, float>)
+                hipLaunchKernelGGL((cast_kernel<T, float>), dim3(blocks_for(n / 4)), dim3(NTH), 0, (hipStream_t)stream,
+                                   (const T*)src, (float*)dst, (long long)(n / 4));
+        });
     E2_LAUNCH_CHECK("cast");
     return 0;
 }
 
-// ---- bf16 NHWC [P][C] -> [C / 16][P][16]: the planar source layout of the deformable conv (mdcn.hip, src_planar)
+// ---- 16-bit NHWC [P][C] -> [C / 16][P][16]: the planar source layout of the deformable conv (mdcn.hip, src_planar)
 namespace {
 __global__ void nhwc_to_planar16_kernel(const uint4* __restrict__ src, uint4* __restrict__ dst, long long P, int C8) {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;      // one 16-byte octet of 8 channels

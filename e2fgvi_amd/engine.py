@@ -25,6 +25,9 @@ padding; both precisions run the same stage methods.
     ONE bf16 tensor per step (conv source, flow-warp source, and -- re-laid out [group][pixel][16] -- the deformable conv's
     gather source).  LayerNorm, window pooling, fold / unfold + GELU, SoftComp fold and the x2 upsamples read / write bf16 and
     compute in fp32 (typed variants of the fp32 kernels, csrc/misc.hip).
+  * fp16: the bf16 data path with IEEE half as the 16-bit type -- the same stage methods, layers, tiles and fp32 tensors
+    (self.x16 is the 16-bit data path, self.dtype its element type); the kernels' fp16 instantiations run fp16 MFMA.  8x finer
+    rounding than bf16 (11 significand bits against 8); range: profiles/fp16_range.txt, DESIGN.md section 1.
 """
 import numpy as np
 import os
@@ -35,6 +38,7 @@ from . import ops
 from .ops import ACT_DCNPOST, ACT_LRELU, ACT_RELU, ACT_TANH, PackedConvX
 
 BF16 = torch.bfloat16
+F16 = torch.float16
 # fp32 path: the FFN's second Linear as a conv of the folded tensor (as the bf16 path runs it).  Measured neutral on the fp32
 # MFMA kernels (15.785 vs 15.775 ms, profiles/r02_fc2_conv.txt: the 16-byte tap-packed fetches cost what the unfold kernel
 # saved); with the split-operand kernels (ops.X3_ENABLED) the conv form wins -- 743 -> 750 frames/s, same box, two runs each
@@ -120,18 +124,19 @@ class Engine:
         table (ops.py); E2FGVI_X3=0 gives the pure fp32-MFMA configuration.
         precision="bf16": the bf16 data path (BASELINE.json HQ configurations): bf16 activations in HBM, every conv / linear /
         attention product on bf16 MFMA with fp32 accumulation; SPyNet, the flows, the DCN offsets and masks, the deformable conv's
-        arithmetic and the token residual stream stay fp32."""
-        if precision not in ("fp32", "bf16"):
-            raise ValueError("precision must be 'fp32' or 'bf16'")
+        arithmetic and the token residual stream stay fp32.
+        precision="fp16": the same data path with fp16 in place of bf16 (fp16 MFMA, same fp32 tensors)."""
+        if precision not in ("fp32", "bf16", "fp16"):
+            raise ValueError("precision must be 'fp32', 'bf16' or 'fp16'")
         self.precision = precision
         self.hq = model == "e2fgvi_hq"
         self.device = torch.device(device)
         sd = {k: v.detach().to(self.device) for k, v in state_dict.items()}
         self.sd = sd
         f = lambda k: sd[k].float().contiguous()
-        self.bf16 = bf16 = precision == "bf16"
-        self.dtype = BF16 if bf16 else torch.float32          # of the activations between the layers
-        x3 = not bf16 and ops.X3_ENABLED
+        self.x16 = x16 = precision in ("bf16", "fp16")        # the 16-bit data path (bf16 or fp16 activations)
+        self.dtype = {"bf16": BF16, "fp16": F16}.get(precision, torch.float32)     # of the activations between the layers
+        x3 = not x16 and ops.X3_ENABLED
         # wide 3x3 / stride-1 layers: fp32 Winograd F(2x2,3x3) whenever the call qualifies (even H, W), else implicit GEMM (the
         # other geometries stay on the implicit GEMM under algo="auto": ops.PackedConv)
         algo = "auto" if winograd else "igemm"
@@ -139,7 +144,7 @@ class Engine:
         def layer(name, key, cpg=None, w=None, b=None, tune=False, nopk=False, **geom):
             """One checkpoint layer in this engine's precision: weights <key>.weight / <key>.bias unless `w` / `b` are given (key
             None: both are); cpg None: a Linear.  fp32: ops.PackedConv / PackedLinear, or PackedConvX on fp32 operands when `taps`
-            is given; bf16: ops.PackedConvX / PackedLinearX.
+            is given; 16-bit: ops.PackedConvX / PackedLinearX.
             tune (fp32): the GEMM-shaped layers (token Linears, soft split / composite): the best implicit-GEMM tile depends on
             the token count; their tile code comes from the decision table of ops.py (e2fgvi_amd/tile_table.py by default, timed on
             the first eager call of each size class under E2FGVI_AUTOTUNE=1).  (Winograd block shapes are NOT tuned at run time:
@@ -159,21 +164,21 @@ class Engine:
                 w = f(key + ".weight") if w is None else w
                 b = f(key + ".bias") if b is None else b
             if cpg is None:
-                c = ops.PackedLinearX(w, b) if bf16 else ops.PackedLinear(w, b, precision="fp32")
-            elif bf16 or "taps" in geom:
+                c = ops.PackedLinearX(w, b, dtype=self.dtype) if x16 else ops.PackedLinear(w, b, precision="fp32")
+            elif x16 or "taps" in geom:
                 c = ops.PackedConvX(w, b, cpg, dtype=self.dtype, **geom)
             else:
                 c = ops.PackedConv(w, b, cpg, precision="fp32", algo=algo, **geom)
             c.name = name
-            c.tune = autotune and (bf16 or tune)
+            c.tune = autotune and (x16 or tune)
             c.try_x3 = x3
-            if nopk and not bf16:
+            if nopk and not x16:
                 c.nopk = True
             return c
 
         # ---- encoder (e2fgvi.py:75-94): the 3-channel frames are carried as 4 fp32 / 8 bf16 channels (16-byte pixels), layer 0's
         # weight is zero-padded to match
-        cin0 = 8 if bf16 else 4
+        cin0 = 8 if x16 else 4
         w0 = torch.zeros(64, cin0, 3, 3, device=self.device)
         w0[:, :3] = f("encoder.layers.0.weight")
         self.enc = [layer("encoder.layers.0", "encoder.layers.0", [cin0], w=w0, stride=2, pad=1)]
@@ -186,7 +191,7 @@ class Engine:
         self.dec = [layer(n, n, [c], pad=1) for n, c in (("decoder.0.conv", 128), ("decoder.2", 128), ("decoder.4.conv", 64))]
         tail = ops.PackedTailConv(f("decoder.6.weight"), f("decoder.6.bias"), dtype=self.dtype)
         tail.name = "decoder.6"
-        if bf16 and autotune:
+        if x16 and autotune:
             tail.tune = True
         self.dec.append(tail)
 
@@ -206,16 +211,16 @@ class Engine:
             # conv_offset.0 input = cat(cond_n1, cur, cond_n2, flow_1, flow_2): sources (cond|0), cur, (cond|128), flows (4 fp32
             # channels; 8 bf16 channels, the weight zero-padded to match)
             w_off0 = f(p + "conv_offset.0.weight")
-            if bf16:
+            if x16:
                 w_off0 = torch.cat([w_off0, w_off0.new_zeros(128, 4, 3, 3)], 1)
-            off = [layer("deform_align.%sconv_offset.0" % d, p + "conv_offset.0", [128, 128, 128, 8 if bf16 else 4], w=w_off0, pad=1)]
+            off = [layer("deform_align.%sconv_offset.0" % d, p + "conv_offset.0", [128, 128, 128, 8 if x16 else 4], w=w_off0, pad=1)]
             off += [layer("deform_align.%sconv_offset.%d" % (d, k), p + "conv_offset.%d" % k, [128], pad=1) for k in (2, 4, 6)]
             # the deformable conv: split-operand MFMA with the other x3 kernels (ops.X3_ENABLED); bf16 products in the bf16 path
-            dcn = ops.PackedDcn(f(p + "weight"), f(p + "bias"), 16, pad=1, mfma="bf16" if bf16 else ("x3" if x3 else "fp32"))
+            dcn = ops.PackedDcn(f(p + "weight"), f(p + "bias"), 16, pad=1, mfma=precision if x16 else ("x3" if x3 else "fp32"))
             dcn.name = "deform_align.%sdcn" % d
             bb = [layer("backbone.%s0" % d, b + "0", [128] * nparts, pad=1), layer("backbone.%s2" % d, b + "2", [128], pad=1)]
             self.prop[d] = (off, dcn, bb)
-            if PROP_SPLIT and not bf16:
+            if PROP_SPLIT and not x16:
                 ws = split_prop_weights(f(p + "conv_offset.0.weight"), f(b + "0.weight"))
                 self.prop_split[d] = dict(
                     off_rec=layer("deform_align.%sconv_offset.0 (recurrent part)" % d, None, [128, 128, 4], w=ws["off_rec"],
@@ -236,7 +241,8 @@ class Engine:
         self.sc_bias_hwc = None if self.hq else f("sc.bias").permute(1, 2, 0).contiguous()
         # bf16 HQ: SoftComp in gather form (nine phase convolutions writing the folded image directly: no [tokens, 6272] tensor,
         # 813 MB at 720p T=10, and no fold kernel); other token grids than 3 x the feature size take the Linear + fold pair
-        self.sc_gather = (ops.SoftCompGather(f("sc.embedding.weight"), f("sc.embedding.bias"), 128) if bf16 and self.hq else None)
+        self.sc_gather = (ops.SoftCompGather(f("sc.embedding.weight"), f("sc.embedding.bias"), 128, dtype=self.dtype)
+                          if x16 and self.hq else None)
 
         # ---- transformer blocks
         self.blocks = []
@@ -244,7 +250,7 @@ class Engine:
             p = "transformer.%d." % i
             w1 = f(p + "mlp.conv1.0.weight").view(40, 49, 512).permute(1, 0, 2).reshape(1960, 512).contiguous()
             b1 = f(p + "mlp.conv1.0.bias").view(40, 49).t().reshape(1960).contiguous()
-            if FC2_CONV or bf16:
+            if FC2_CONV or x16:
                 # fc2: Linear(1960 -> 512) of the unfolded 7x7 patches == the 7x7 / stride 3 / pad 3 convolution of the folded
                 # [F, H, W, 40] tensor (tfocal_transformer.py:81,95-97): no unfold kernel, no [rows, 1960] tensor
                 fc2 = layer(p + "fc2", p + "mlp.conv2.1", [40], w=f(p + "mlp.conv2.1.weight").view(512, 40, 7, 7), stride=3, pad=3,
@@ -380,8 +386,8 @@ class Engine:
         flow = None
         for lv in range(6):
             # the fp32 level input (images, warped support image, upsampled flow); the bf16 path's convs read its bf16 copy
-            if self.bf16:
-                inp, x = ops.spynet_level_input(pyr[lv], ref_idx, supp_idx, flow, bf16_copy=True)
+            if self.x16:
+                inp, x = ops.spynet_level_input(pyr[lv], ref_idx, supp_idx, flow, copy_dtype=self.dtype)
             else:
                 inp = x = ops.spynet_level_input(pyr[lv], ref_idx, supp_idx, flow)
             cv = self.spy[lv]
@@ -400,7 +406,7 @@ class Engine:
         """join: called in front of encoder.layers.<join_at> (16 at one clip: the fork's other branch, SPyNet, overlaps layers 0 .. 14;
         the bf16 path joins behind the encoder)"""
         b, t, c, H, W = frames.shape
-        x = ops.nchw_to_nhwc(frames.reshape(b * t, c, H, W).contiguous(), ld=8 if self.bf16 else 4, out_dtype=self.dtype)
+        x = ops.nchw_to_nhwc(frames.reshape(b * t, c, H, W).contiguous(), ld=8 if self.x16 else 4, out_dtype=self.dtype)
         e = self.enc
         lr = dict(act=ACT_LRELU, slope=0.2)
         x = e[0]([x], **lr)
@@ -408,7 +414,7 @@ class Engine:
         x = e[2]([x], **lr)
         x0 = e[3]([x], **lr)
         x = e[4]([x0], **lr)
-        join_at = 18 if self.bf16 else (JOIN_AT or (16 if b == 1 else 10))
+        join_at = 18 if self.x16 else (JOIN_AT or (16 if b == 1 else 10))
         joined = join is None
         if not joined and join_at <= 10:
             join()
@@ -428,13 +434,13 @@ class Engine:
         itself: its epilogue reads a residual element and writes the same element in the same thread)."""
         l_t, b, h, w, ch = loc.shape
         dev = loc.device
-        bf16 = self.bf16
+        x16 = self.x16
         feats = {}
         zero = self._zero((b, h, w, ch), self.dtype)
-        # bf16: the deformable conv gathers from copies of the propagated features re-laid out [group][pixel][16]: the 32-byte runs a
+        # 16-bit: the deformable conv gathers from copies of the propagated features re-laid out [group][pixel][16]: the 32-byte runs a
         # deform group's samples fetch are then adjacent for neighbouring pixels and share cache lines (NHWC: one run per 256-byte
         # pixel) -- tools/dcn_bench_x.py
-        zero_dcn = self._zero((ch // 16, b, h, w, 16), BF16) if bf16 else zero
+        zero_dcn = self._zero((ch // 16, b, h, w, 16), self.dtype) if x16 else zero
         lk = dict(act=ACT_LRELU, slope=0.1)
         # the non-recurrent parts of conv_offset.0 / backbone.0 for the frames of steps 1 .. l_t - 1, all at once (see __init__);
         # step 0 of a direction (backbone only, needed at once) keeps the whole layer
@@ -480,7 +486,7 @@ class Engine:
                 order = order[::-1]
             img_stride = (l_t - 1) * h * w * 2
             hist = []                       # the propagated features in processing order: conv and flow-warp sources
-            hist_dcn = [] if bf16 else hist     # ... and the deformable conv's (bf16: the [group][pixel][16] copies)
+            hist_dcn = [] if x16 else hist     # ... and the deformable conv's (16-bit: the [group][pixel][16] copies)
             aligned = zero
             for i, idx in enumerate(order):
                 cur = loc[idx]
@@ -488,8 +494,8 @@ class Engine:
                     flow_a = flows[0, i - 1]
                     flow_b = flows[0, i - 2] if i > 1 else None
                     feat_n2 = hist[-2] if i > 1 else None
-                    if bf16:        # bf16 warped features, and the flows as an 8-channel bf16 source of conv_offset.0
-                        cond, fl, fl_src = ops.prop_cond(hist[-1], feat_n2, flow_a, flow_b, img_stride, cond_dtype=BF16, flows8=True)
+                    if x16:        # 16-bit warped features, and the flows as an 8-channel 16-bit source of conv_offset.0
+                        cond, fl, fl_src = ops.prop_cond(hist[-1], feat_n2, flow_a, flow_b, img_stride, cond_dtype=self.dtype, flows8=True)
                     else:
                         cond, fl = ops.prop_cond(hist[-1], feat_n2, flow_a, flow_b, img_stride)
                         fl_src = fl
@@ -503,14 +509,14 @@ class Engine:
                     # 10*tanh + flow.flip / sigmoid (feat_prop.py:38-53) applied in the epilogue of the last conv_offset
                     # layer: the deformable conv then reads finished (fp32) offsets and masks
                     offs = off_convs[3]([x], out_dtype=torch.float32, residual=fl, act=ACT_DCNPOST, slope=10.0)
-                    aligned = dcn([hist_dcn[-1], hist_dcn[-2] if i > 1 else zero_dcn], offs, out_dtype=self.dtype, planar=bf16)
+                    aligned = dcn([hist_dcn[-1], hist_dcn[-2] if i > 1 else zero_dcn], offs, out_dtype=self.dtype, planar=x16)
                 if sp is not None and i > 0:
                     y = sp["bb_rec"]([aligned], residual=partial("bb " + name, idx if name == "backward_" else idx - 1), **lk)
                 else:
                     srcs = [cur, feats["backward_"][idx], aligned] if name == "forward_" else [cur, aligned]
                     y = bb[0](srcs, **lk)
                 hist.append(bb[1]([y], residual=aligned, out=store[idx]))
-                if bf16 and i + 1 < l_t:
+                if x16 and i + 1 < l_t:
                     hist_dcn.append(ops.to_planar16(store[idx]))
             feats[name] = store
         out = self.fusion([feats["backward_"].view(l_t * b, h, w, ch), feats["forward_"].view(l_t * b, h, w, ch)],
@@ -534,7 +540,7 @@ class Engine:
         nbuf = torch.empty((rows + prow, 512), dtype=self.dtype, device=x.device)
         n1 = ops.layernorm(x, blk["n1w"], blk["n1b"], out=nbuf[:rows])
         ops.window_pool(n1, blk["pool_w"], blk["pool_b"], b * t, fh, fw, out=nbuf[rows:])
-        if self.bf16:
+        if self.x16:
             both = blk["qkv"](nbuf)                                   # bf16 [rows + prow, 1536]
             att = ops.focal_attention_bf16(both[:rows], both[rows:], tab, nk, b, t, fh, fw)
         elif ops.attention_x3_applies(b, t, fh, fw):
@@ -628,7 +634,7 @@ class Engine:
             loc = enc5[0, :l_t].unsqueeze(1)                 # view: [l_t, 1, h, w, C]
             # one clip, fp32: the local frames are a view of the encoder output and the propagated features replace them in place
             # (no 33 MB copy; under E2FGVI_AUTOTUNE=1 the fusion layer writes a fresh tensor so that its candidates can be timed)
-            inplace = not (ops.AUTOTUNE or self.bf16)
+            inplace = not (ops.AUTOTUNE or self.x16)
             prop = self.propagate(loc, fwd, bwd, inplace=inplace)
             if not inplace:
                 enc5[0, :l_t].copy_(prop[:, 0])
@@ -643,8 +649,8 @@ class Engine:
             trace["tokens0"] = tok.clone()
         tok16 = None
         for i in range(8):
-            if self.bf16 and i == 7:        # the bf16 path's compose() reads a bf16 copy of the last block's tokens
-                tok16 = torch.empty((b * t * fh * fw, 512), dtype=BF16, device=tok.device)
+            if self.x16 and i == 7:        # the 16-bit path's compose() reads a 16-bit copy of the last block's tokens
+                tok16 = torch.empty((b * t * fh * fw, 512), dtype=self.dtype, device=tok.device)
             tok, x1 = self.block(i, tok, b, t, fh, fw, (h, w), out2=tok16)
             if trace is not None:
                 trace["block%d_attn_out" % i] = x1

@@ -168,7 +168,9 @@ class _InpaintGeneratorBase(nn.Module):
                 if isinstance(m, SecondOrderDeformableAlignment):
                     m.init_offset()
         self.update_spynet = SPyNet()        # built after init_weights, like the reference (e2fgvi.py:208)
-        # "fp32" (default, the parity configuration) or "bf16" (optional bf16-MFMA mode for the HQ configurations)
+        # "fp32" (default, the parity configuration), "bf16" (the 16-bit data path with bf16 activations and bf16 MFMA) or
+        # "fp16" (the same path with IEEE half: the bf16 speed at 8x finer rounding).  This attribute is the precision switch:
+        # .half() / .to(torch.float16) only convert the module's parameters (the engine reads them back as fp32), as before.
         self.precision = "fp32"
 
     def init_weights(self, init_type="normal", gain=0.02):

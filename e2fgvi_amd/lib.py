@@ -13,6 +13,7 @@ ABI_VERSION = 8        # the struct layouts / symbols below; csrc/error.hip e2fg
 MAX_SRC = 4
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH, ACT_DCNPOST = 0, 1, 2, 3, 4
 DT_F32, DT_BF16 = 0, 1
+DT_F16 = 3                        # IEEE half: the fp16 data path
 
 _fp = C.c_void_p   # device pointers travel as plain addresses
 
@@ -80,6 +81,11 @@ SYMBOLS = {
     "e2fgvi_pack_conv_weight_bf16x": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i32), _fp]),
     "e2fgvi_packed_conv_weight_bf16x_taps_size": (_i64, [_i32, _i32, _i32, _i32]),
     "e2fgvi_pack_conv_weight_bf16x_taps": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _fp]),
+    "e2fgvi_conv2d_f16x": (C.c_int, [C.POINTER(ConvXDesc), _fp]),
+    "e2fgvi_packed_conv_weight_f16x_size": (_i64, [_i32, _i32, _i32, _i32, _i32, C.POINTER(_i32)]),
+    "e2fgvi_pack_conv_weight_f16x": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i32), _fp]),
+    "e2fgvi_packed_conv_weight_f16x_taps_size": (_i64, [_i32, _i32, _i32, _i32]),
+    "e2fgvi_pack_conv_weight_f16x_taps": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _fp]),
     "e2fgvi_packed_conv_weight_f32x_taps_size": (_i64, [_i32, _i32, _i32, _i32]),
     "e2fgvi_pack_conv_weight_f32x_taps": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _fp]),
     "e2fgvi_conv2d_f32x": (C.c_int, [C.POINTER(ConvXDesc), _fp]),
@@ -106,6 +112,7 @@ SYMBOLS = {
     "e2fgvi_packed_dcn_weight_size": (_i64, [_i32, _i32, _i32, _i32]),
     "e2fgvi_pack_dcn_weight": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, _fp]),
     "e2fgvi_pack_dcn_weight_bf16": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, _fp]),
+    "e2fgvi_pack_dcn_weight_f16": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, _fp]),
     "e2fgvi_pack_dcn_weight_x3": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, _fp]),
     "e2fgvi_focal_attention": (C.c_int, [_fp, _fp, _fp, _i32, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _fp]),
     "e2fgvi_split3_kv": (C.c_int, [_fp, _fp, _i64, _fp]),
@@ -131,11 +138,14 @@ SYMBOLS = {
     "e2fgvi_softcomp_fold": (C.c_int, [_fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _fp]),
     "e2fgvi_focal_attention_bf16": (C.c_int, [_fp, _fp, _fp, _i32, _fp, _fp, _i32, _i32, _i32, _i32, _fp]),
     "e2fgvi_focal_attention_bf16_variant": (C.c_int, [C.c_int]),
+    "e2fgvi_focal_attention_f16": (C.c_int, [_fp, _fp, _fp, _i32, _fp, _fp, _i32, _i32, _i32, _i32, _fp]),
     "e2fgvi_nchw_to_nhwc_x": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _f, _f, _fp]),
     "e2fgvi_resize_bilinear_bf16": (C.c_int, [_fp, _i32, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _fp]),
+    "e2fgvi_resize_bilinear_f16": (C.c_int, [_fp, _i32, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _fp]),
     "e2fgvi_prop_cond_x": (C.c_int, [_fp, _i32, _fp, _i32, _fp, _fp, _i64, _fp, _i32, _fp, _fp, _i32, _i32, _i32, _i32, _fp]),
     "e2fgvi_prop_cond_xs": (C.c_int, [_fp, _i32, _fp, _i32, _i32, _fp, _fp, _i64, _fp, _i32, _fp, _fp, _i32, _i32, _i32, _i32, _fp]),
     "e2fgvi_spynet_level_input_x": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _i32, _i32, _i32, _fp]),
+    "e2fgvi_spynet_level_input_x_f16": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _i32, _i32, _i32, _fp]),
     "e2fgvi_layernorm_x": (C.c_int, [_fp, _fp, _fp, _fp, _i32, _i64, _i32, _fp]),
     "e2fgvi_window_pool_x": (C.c_int, [_fp, _i32, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _fp]),
     "e2fgvi_ffn_fold_x": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _fp]),
@@ -143,6 +153,7 @@ SYMBOLS = {
     "e2fgvi_ffn_fold_gelu_x": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _fp]),
     "e2fgvi_ffn_unfold_x": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _fp]),
     "e2fgvi_softcomp_fold_bf16": (C.c_int, [_fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _fp]),
+    "e2fgvi_softcomp_fold_f16": (C.c_int, [_fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _fp]),
     "e2fgvi_cast": (C.c_int, [_fp, _i32, _fp, _i32, _i64, _fp]),
 }
 

@@ -623,12 +623,25 @@ class PackedConv:
         return out
 
 
+HALF16 = (torch.bfloat16, torch.float16)     # the two element types of the 16-bit data path
+
+
 def _dt(t):
     if t.dtype == torch.float32:
         return _L.DT_F32
     if t.dtype == torch.bfloat16:
         return _L.DT_BF16
-    raise TypeError("tensor must be float32 or bfloat16, got %s" % t.dtype)
+    if t.dtype == torch.float16:
+        return _L.DT_F16
+    raise TypeError("tensor must be float32, bfloat16 or float16, got %s" % t.dtype)
+
+
+def _dt_key(t):
+    """the element-type field of a tuning key: fp16 layers share the bf16 entries (same kernels, same tiles, same data movement:
+    conv_bf16x.hip MODE 3 is MODE 0 with another MFMA instruction and conversion).  On purpose, also under E2FGVI_AUTOTUNE=1: an
+    fp16 layer that times its tiles records the winner under the bf16 key and may replace a bf16 decision held in memory (or in
+    the tune file) -- the measurement is one of the same kernel body on the same shape, so it is as valid for bf16 as for fp16."""
+    return _L.DT_BF16 if t.dtype == torch.float16 else _dt(t)
 
 
 def _chk_any(t, name):
@@ -645,6 +658,8 @@ class PackedConvX:
 
     dtype=torch.bfloat16 (default): the bf16 data path -- bf16 NHWC sources (virtual concat, channels per source in
     multiples of 8), bf16 packed weights, v_mfma_f32_32x32x16_bf16 with fp32 accumulation.
+    dtype=torch.float16: the same with fp16 sources / weights / 16-bit results on v_mfma_f32_32x32x16_f16 (e2fgvi_conv2d_f16x),
+    same tiles; its tuning keys are the bf16 ones.
     dtype=torch.float32: the same kernel on fp32 operands (channels in multiples of 4, exact fp32 MFMA) -- the fp32 path's
     tuning alternative to PackedConv's register-staged implicit GEMM.
     Either way: fp32 epilogue (bias, fp32 / bf16 residual, activation or the DCN offset post-processing), bf16 or fp32
@@ -669,7 +684,11 @@ class PackedConvX:
         self.x3 = bool(x3)
         if self.x3 and not self.f32:
             raise ValueError("x3 splitting is for fp32 sources")
-        self._fn = (lib.e2fgvi_conv2d_f32x3 if self.x3 else lib.e2fgvi_conv2d_f32x) if self.f32 else lib.e2fgvi_conv2d_bf16x
+        self.f16 = dtype == torch.float16
+        if not self.f32 and dtype not in HALF16:
+            raise TypeError("PackedConvX: dtype must be float32, bfloat16 or float16")
+        self._fn = ((lib.e2fgvi_conv2d_f32x3 if self.x3 else lib.e2fgvi_conv2d_f32x) if self.f32 else
+                    lib.e2fgvi_conv2d_f16x if self.f16 else lib.e2fgvi_conv2d_bf16x)
         wdtype = torch.bfloat16 if self.x3 else dtype
         self.name = "conv"
         self.tune = False          # time XTUNE_CANDIDATES on the first call of every new size class and keep the fastest
@@ -707,9 +726,10 @@ class PackedConvX:
         arr = (C.c_int32 * len(self.cpg))(*self.cpg)
         if self.taps:
             size_fn = ((lib.e2fgvi_packed_conv_weight_f32x3_taps_size if self.x3 else lib.e2fgvi_packed_conv_weight_f32x_taps_size)
-                       if self.f32 else lib.e2fgvi_packed_conv_weight_bf16x_taps_size)
+                       if self.f32 else lib.e2fgvi_packed_conv_weight_f16x_taps_size if self.f16
+                       else lib.e2fgvi_packed_conv_weight_bf16x_taps_size)
             pack_fn = ((lib.e2fgvi_pack_conv_weight_f32x3_taps if self.x3 else lib.e2fgvi_pack_conv_weight_f32x_taps)
-                       if self.f32 else lib.e2fgvi_pack_conv_weight_bf16x_taps)
+                       if self.f32 else lib.e2fgvi_pack_conv_weight_f16x_taps if self.f16 else lib.e2fgvi_pack_conv_weight_bf16x_taps)
             n = size_fn(self.Cout, self.KH, self.KW, self.cpg[0])
             if n < 0:
                 _L.check(int(n), "packed_conv_weight_x_taps_size")
@@ -720,9 +740,9 @@ class PackedConvX:
                      "pack_conv_weight_x_taps")
         else:
             size_fn = ((lib.e2fgvi_packed_conv_weight_f32x3_size if self.x3 else lib.e2fgvi_packed_conv_weight_f32x_size)
-                       if self.f32 else lib.e2fgvi_packed_conv_weight_bf16x_size)
+                       if self.f32 else lib.e2fgvi_packed_conv_weight_f16x_size if self.f16 else lib.e2fgvi_packed_conv_weight_bf16x_size)
             pack_fn = ((lib.e2fgvi_pack_conv_weight_f32x3 if self.x3 else lib.e2fgvi_pack_conv_weight_f32x)
-                       if self.f32 else lib.e2fgvi_pack_conv_weight_bf16x)
+                       if self.f32 else lib.e2fgvi_pack_conv_weight_f16x if self.f16 else lib.e2fgvi_pack_conv_weight_bf16x)
             n = size_fn(self.Cout, self.groups, self.KH, self.KW, len(self.cpg), arr)
             if n < 0:
                 _L.check(int(n), "packed_conv_weight_x_size")
@@ -771,7 +791,7 @@ class PackedConvX:
                 raise ValueError("out shape %s != [%d,%d,%d,*]" % (tuple(out.shape), N, Ho, Wo))
             d.dst, d.dst_ld, d.dst_coff, d.dst_dtype = out.data_ptr(), out.shape[3], out_coff, _dt(out)
         if out2 is not None:
-            _chk(out2, "out2", torch.bfloat16)
+            _chk(out2, "out2", torch.float16 if self.f16 else torch.bfloat16)
             if out2.dim() != 4 or tuple(out2.shape[:3]) != (N, Ho, Wo):
                 raise ValueError("out2 shape %s != [%d,%d,%d,*]" % (tuple(out2.shape), N, Ho, Wo))
             d.dst2, d.dst2_ld, d.dst2_coff = out2.data_ptr(), out2.shape[3], 0
@@ -826,7 +846,7 @@ class PackedConvX:
         x3 = self.try_x3 and X3_ENABLED and self.f32 and not self.x3
         if tile == 0 and self.tune and N * Ho * Wo >= 2048:
             key = (("x3" if self.x3 else ("x32+3" if x3 else "x32")) if self.f32 else "x", self.Cout, tuple(self.cpg), self.KH, self.KW, self.stride, self.pad, self.groups,
-                   int(4.0 * math.log2(N * Ho * Wo)), _dt(out), out_nchw, self.taps)
+                   int(4.0 * math.log2(N * Ho * Wo)), _dt_key(out), out_nchw, self.taps)
             best = _decision(key)
             if best is None and AUTOTUNE and not torch.cuda.is_current_stream_capturing() and (
                     residual is None or residual.data_ptr() != out.data_ptr()):
@@ -850,7 +870,8 @@ class PackedConvX:
             cin_p = sum(-(-c // kc) * kc for c in self.cpg)
             if self.taps:                                   # K-steps of several taps: issued K = steps * 64
                 cin_p = -(-K2 * (self.cpg[0] // (4 if self.f32 else 8)) // 8) * kc / K2
-            _L.annotate(layer=self.name, kernel="conv_%s tile=%d%s" % (("f32x3" if self.x3 else "f32x") if self.f32 else "bf16x", tile,
+            _L.annotate(layer=self.name, kernel="conv_%s tile=%d%s" % (("f32x3" if self.x3 else "f32x") if self.f32 else
+                                                                      "f16x" if self.f16 else "bf16x", tile,
                                                                       " taps" if self.taps else ""),
                         shape="N%d %dx%d %d->%d k%d s%d g%d" % (N, H, W, cin_g * self.groups, self.Cout, self.KH, self.stride, self.groups),
                         macs=N * Ho * Wo * self.Cout * cin_g * K2,
@@ -966,7 +987,7 @@ class SoftCompGather:
             if _L.TRACE is not None:
                 kc = 32 if layer.f32 else 64
                 macs = F_ * fh * fw * self.C * hid * layer.KH * layer.KW
-                _L.annotate(layer=layer.name, kernel="conv_%s (gather-form SoftComp)" % ("f32x" if layer.f32 else "bf16x"),
+                _L.annotate(layer=layer.name, kernel="conv_%s (gather-form SoftComp)" % ("f32x" if layer.f32 else "f16x" if layer.f16 else "bf16x"),
                             shape="N%d %dx%d %d->%d k%dx%d scatter s3" % (F_, fh, fw, hid, self.C, layer.KH, layer.KW),
                             macs=macs, issued=macs // hid * (-(-hid // kc) * kc))
             _L.check(layer._fn(C.byref(d), _stream()), "conv2d_x (SoftComp phase)")
@@ -1012,7 +1033,7 @@ class PackedLinear(PackedConv):
 
 class PackedTailConv:
     """The decoder's last layer, Conv2d(64, 3, 3, padding=1) + activation -> fp32 NCHW frames (csrc/conv_tail.hip): the nine
-    taps on the N side of one [pixels x 64] x [64 x 27] GEMM, shifted sum in LDS.  dtype = the source's (fp32 / bf16)."""
+    taps on the N side of one [pixels x 64] x [64 x 27] GEMM, shifted sum in LDS.  dtype = the source's (fp32 / bf16 / fp16)."""
 
     def __init__(self, weight, bias, dtype=torch.float32):
         lib = _L.load()
@@ -1059,9 +1080,10 @@ class PackedDcn:
         mfma="x3": the fp32 layer on the bf16 matrix pipe -- blended values and weights split exactly into three bf16 pieces,
         six bf16 MFMA terms per product (fp32-level rounding; fp32 sources)."""
         lib = _L.load()
-        if mfma not in ("fp32", "bf16", "x3"):
-            raise ValueError("mfma must be 'fp32', 'bf16' or 'x3'")
+        if mfma not in ("fp32", "bf16", "fp16", "x3"):
+            raise ValueError("mfma must be 'fp32', 'bf16', 'fp16' or 'x3'")
         self.mfma_bf16 = mfma == "bf16"
+        self.mfma_f16 = mfma == "fp16"            # the same on fp16 (fp16 sources, products and 16-bit result)
         self.mfma_x3 = mfma == "x3"
         w = _chk(weight.detach().float().contiguous(), "weight")
         self.Cout, self.C, self.KH, self.KW = w.shape
@@ -1077,6 +1099,10 @@ class PackedDcn:
             self.wpacked = torch.empty(int(n), dtype=torch.bfloat16, device=w.device)
             _L.check(lib.e2fgvi_pack_dcn_weight_bf16(_ptr(w), _ptr(self.wpacked), self.Cout, self.C, self.KH, self.KW,
                                                      deform_groups, _stream()), "pack_dcn_weight_bf16")
+        elif self.mfma_f16:
+            self.wpacked = torch.empty(int(n), dtype=torch.float16, device=w.device)
+            _L.check(lib.e2fgvi_pack_dcn_weight_f16(_ptr(w), _ptr(self.wpacked), self.Cout, self.C, self.KH, self.KW,
+                                                    deform_groups, _stream()), "pack_dcn_weight_f16")
         else:
             self.wpacked = torch.empty(int(n), dtype=torch.float32, device=w.device)
             _L.check(lib.e2fgvi_pack_dcn_weight(_ptr(w), _ptr(self.wpacked), self.Cout, self.C, self.KH, self.KW,
@@ -1139,10 +1165,10 @@ class PackedDcn:
             out = torch.empty((N, Ho, Wo, self.Cout), dtype=out_dtype, device=sources[0].device)
         _chk_any(out, "out")
         d.dst, d.dst_ld, d.dst_coff, d.tile, d.dst_dtype = out.data_ptr(), out.shape[3], 0, tile, _dt(out)
-        d.mfma_dtype = 2 if self.mfma_x3 else (_L.DT_BF16 if self.mfma_bf16 else _L.DT_F32)
+        d.mfma_dtype = 2 if self.mfma_x3 else (_L.DT_BF16 if self.mfma_bf16 else _L.DT_F16 if self.mfma_f16 else _L.DT_F32)
         if _L.TRACE is not None:
             m = N * Ho * Wo * self.Cout * self.C * K
-            _L.annotate(layer=self.name, kernel="mdcn_x3" if self.mfma_x3 else ("mdcn_bf16" if self.mfma_bf16 else "mdcn"),
+            _L.annotate(layer=self.name, kernel="mdcn_x3" if self.mfma_x3 else ("mdcn_bf16" if self.mfma_bf16 else "mdcn_f16" if self.mfma_f16 else "mdcn"),
                         shape="N%d %dx%d %d->%d dg%d" % (N, H, W, self.C, self.Cout, self.dg),
                         macs=m, issued=int(m * 6 * 157.3 / 2500.0) if self.mfma_x3 else m)
         _L.check(lib.e2fgvi_mdcn_nhwc(C.byref(d), _stream()), "mdcn_nhwc")
@@ -1242,7 +1268,8 @@ def attention_x3_applies(B, T, fh, fw):
 
 
 def focal_attention_bf16(qkv, kv_pool, key_tab, nkeys, B, T, fh, fw, out=None, variant=None):
-    """bf16 data path: qkv [rows,1536] / kv_pool [B*T*nWin,1536] / out [rows,512] are bf16.
+    """16-bit data path: qkv [rows,1536] / kv_pool [B*T*nWin,1536] / out [rows,512] are bf16 -- or all fp16
+    (e2fgvi_focal_attention_f16: the same kernels on fp16 MFMA).
     variant (tests / A-B measurements): kernel variant for this call (see e2fgvi_focal_attention_bf16_variant)"""
     lib = _L.load()
     if variant is not None:
@@ -1251,7 +1278,8 @@ def focal_attention_bf16(qkv, kv_pool, key_tab, nkeys, B, T, fh, fw, out=None, v
             return focal_attention_bf16(qkv, kv_pool, key_tab, nkeys, B, T, fh, fw, out=out)
         finally:
             lib.e2fgvi_focal_attention_bf16_variant(prev)
-    _chk(qkv, "qkv", torch.bfloat16); _chk(kv_pool, "kv_pool", torch.bfloat16)
+    dt = qkv.dtype if isinstance(qkv, torch.Tensor) and qkv.dtype == torch.float16 else torch.bfloat16
+    _chk(qkv, "qkv", dt); _chk(kv_pool, "kv_pool", dt)
     _chk(key_tab, "key_tab", torch.int32); _chk(nkeys, "nkeys", torch.int32)
     rows = B * T * fh * fw
     nwin = (fh // 5) * (fw // 9)
@@ -1260,16 +1288,18 @@ def focal_attention_bf16(qkv, kv_pool, key_tab, nkeys, B, T, fh, fw, out=None, v
     if key_tab.shape[0] != nwin or nkeys.shape[0] != nwin:
         raise ValueError("key table must have %d rows" % nwin)
     if out is None:
-        out = torch.empty((rows, 512), dtype=torch.bfloat16, device=qkv.device)
-    _chk(out, "out", torch.bfloat16)
+        out = torch.empty((rows, 512), dtype=dt, device=qkv.device)
+    _chk(out, "out", dt)
     if _L.TRACE is not None:
         nkl = nkeys.tolist()
         alg = B * nwin * 4 * (45 * T) * (210 * T) * 128 * 2
         qpad = -(-(45 * T) // 32) * 32
         iss = B * 4 * qpad * 128 * 2 * sum(-(-(T * k) // 32) * 32 for k in nkl)
-        _L.annotate(layer="attention", kernel="focal_attn_bf16", shape="B%d T%d grid %dx%d" % (B, T, fh, fw), macs=alg, issued=iss)
-    _L.check(lib.e2fgvi_focal_attention_bf16(_ptr(qkv), _ptr(kv_pool), _ptr(key_tab), key_tab.shape[1], _ptr(nkeys), _ptr(out),
-                                             B, T, fh, fw, _stream()), "focal_attention_bf16")
+        _L.annotate(layer="attention", kernel="focal_attn_f16" if dt == torch.float16 else "focal_attn_bf16",
+                    shape="B%d T%d grid %dx%d" % (B, T, fh, fw), macs=alg, issued=iss)
+    fn = lib.e2fgvi_focal_attention_f16 if dt == torch.float16 else lib.e2fgvi_focal_attention_bf16
+    _L.check(fn(_ptr(qkv), _ptr(kv_pool), _ptr(key_tab), key_tab.shape[1], _ptr(nkeys), _ptr(out), B, T, fh, fw, _stream()),
+             "focal_attention_f16" if dt == torch.float16 else "focal_attention_bf16")
     return out
 
 
@@ -1285,7 +1315,8 @@ def nchw_to_nhwc(x, ld=None, scale=1.0, shift=0.0, out_dtype=torch.float32):
 
 
 def cast(x, dtype):
-    """fp32 <-> bf16 copy of a tensor (round to nearest even); numel must be a multiple of 4"""
+    """fp32 <-> bf16 / fp16 copy of a tensor (round to nearest even; fp16: the bits of torch's .half()); numel must be a
+    multiple of 4"""
     lib = _L.load()
     _chk_any(x, "x")
     out = torch.empty(x.shape, dtype=dtype, device=x.device)
@@ -1305,14 +1336,15 @@ def nhwc_to_nchw(x, channels=None):
 
 def resize_bilinear(x, out_hw, align_corners, src_nchw=False, channels=None, out_ld=None, scale=None, shift=None):
     lib = _L.load()
-    if isinstance(x, torch.Tensor) and x.dtype == torch.bfloat16:         # bf16 data path: NHWC -> NHWC only
-        _chk(x, "x", torch.bfloat16)
+    if isinstance(x, torch.Tensor) and x.dtype in HALF16:                # 16-bit data path: NHWC -> NHWC only
+        _chk(x, "x", x.dtype)
         if src_nchw or scale is not None or shift is not None or channels is not None or out_ld is not None:
-            raise ValueError("bf16 resize: plain NHWC -> NHWC only")
+            raise ValueError("16-bit resize: plain NHWC -> NHWC only")
         N, H, W, Cc = x.shape
-        out = torch.empty((N, out_hw[0], out_hw[1], Cc), dtype=torch.bfloat16, device=x.device)
-        _L.check(lib.e2fgvi_resize_bilinear_bf16(_ptr(x), Cc, _ptr(out), Cc, N, Cc, H, W, out_hw[0], out_hw[1],
-                                                 int(align_corners), _stream()), "resize_bilinear_bf16")
+        out = torch.empty((N, out_hw[0], out_hw[1], Cc), dtype=x.dtype, device=x.device)
+        fn = lib.e2fgvi_resize_bilinear_f16 if x.dtype == torch.float16 else lib.e2fgvi_resize_bilinear_bf16
+        _L.check(fn(_ptr(x), Cc, _ptr(out), Cc, N, Cc, H, W, out_hw[0], out_hw[1], int(align_corners), _stream()),
+                 "resize_bilinear_16")
         return out
     _chk(x, "x")
     if src_nchw:
@@ -1346,7 +1378,9 @@ def avgpool2(x):
     return out
 
 
-def spynet_level_input(pyr, ref_idx, supp_idx, flow_prev, bf16_copy=False):
+def spynet_level_input(pyr, ref_idx, supp_idx, flow_prev, copy_dtype=None):
+    """copy_dtype (torch.bfloat16 / torch.float16): also return the 8 channels as a 16-bit copy of that type, the source of the
+    level's 16-bit conv stack"""
     lib = _L.load()
     _chk(pyr, "pyr"); _chk(ref_idx, "ref_idx", torch.int32); _chk(supp_idx, "supp_idx", torch.int32)
     F_, h, w, c = pyr.shape
@@ -1358,18 +1392,22 @@ def spynet_level_input(pyr, ref_idx, supp_idx, flow_prev, bf16_copy=False):
         if tuple(flow_prev.shape) != (Np, h // 2, w // 2, 2):
             raise ValueError("flow_prev must be [%d,%d,%d,2], got %s" % (Np, h // 2, w // 2, tuple(flow_prev.shape)))
     out = empty_nhwc(Np, h, w, 8, pyr.device)
-    out16 = torch.empty((Np, h, w, 8), dtype=torch.bfloat16, device=pyr.device) if bf16_copy else None
-    _L.check(lib.e2fgvi_spynet_level_input_x(_ptr(pyr), _ptr(ref_idx), _ptr(supp_idx), _ptr(flow_prev), _ptr(out), _ptr(out16),
-                                             Np, h, w, _stream()), "spynet_level_input")
-    return (out, out16) if bf16_copy else out
+    if copy_dtype not in (None,) + HALF16:
+        raise TypeError("copy_dtype must be None, torch.bfloat16 or torch.float16")
+    f16 = copy_dtype == torch.float16
+    out16 = torch.empty((Np, h, w, 8), dtype=copy_dtype, device=pyr.device) if copy_dtype is not None else None
+    fn = lib.e2fgvi_spynet_level_input_x_f16 if f16 else lib.e2fgvi_spynet_level_input_x
+    _L.check(fn(_ptr(pyr), _ptr(ref_idx), _ptr(supp_idx), _ptr(flow_prev), _ptr(out), _ptr(out16), Np, h, w, _stream()),
+             "spynet_level_input")
+    return (out, out16) if copy_dtype is not None else out
 
 
 def prop_cond(feat_prop, feat_n2, flow_a, flow_b, flow_img_stride, cond=None, flows=None, cond_dtype=torch.float32,
               flows8=False):
     """flow_a / flow_b: tensors whose data_ptr is image 0's [H,W,2] flow; image n is at +n*flow_img_stride floats.
-    cond_dtype=torch.bfloat16 writes the warped features as bf16 (bf16 data path); flows8=True additionally returns the
-    four flow values as a bf16 [N,H,W,8] conv source (channels 4..7 zero).  bf16 feat_prop / feat_n2 (with a bf16 cond):
-    the warp reads the bf16 copies of the features -- half the gather bytes."""
+    cond_dtype=torch.bfloat16 / torch.float16 writes the warped features as 16-bit (16-bit data path); flows8=True additionally
+    returns the four flow values as a [N,H,W,8] conv source (channels 4..7 zero) of the cond's 16-bit type (bf16 beside an fp32
+    cond).  16-bit feat_prop / feat_n2 (with a cond of their type): the warp reads the 16-bit copies -- half the gather bytes."""
     lib = _L.load()
     _chk_any(feat_prop, "feat_prop")
     N, H, W, Cc = feat_prop.shape
@@ -1377,7 +1415,8 @@ def prop_cond(feat_prop, feat_n2, flow_a, flow_b, flow_img_stride, cond=None, fl
         cond = torch.empty((N, H, W, 2 * Cc), dtype=cond_dtype, device=feat_prop.device)
     if flows is None:
         flows = empty_nhwc(N, H, W, 4, feat_prop.device)
-    fl8 = torch.empty((N, H, W, 8), dtype=torch.bfloat16, device=feat_prop.device) if flows8 else None
+    fl8 = (torch.empty((N, H, W, 8), dtype=cond.dtype if cond.dtype == torch.float16 else torch.bfloat16, device=feat_prop.device)
+           if flows8 else None)
     f2_ld = 0
     if flow_b is not None:
         _chk(feat_n2, "feat_n2", feat_prop.dtype)
@@ -1424,12 +1463,13 @@ def ffn_fold(hid, F_, fh, fw, H, W, Cc):
 
 
 def to_planar16(x, out=None):
-    """bf16 NHWC [N,H,W,C] -> [C/16, N, H, W, 16]: the deformable conv's planar source layout (PackedDcn(..., planar=True))"""
-    _chk(x, "x", torch.bfloat16)
+    """16-bit NHWC [N,H,W,C] -> [C/16, N, H, W, 16]: the deformable conv's planar source layout (PackedDcn(..., planar=True))"""
+    dt = x.dtype if isinstance(x, torch.Tensor) and x.dtype == torch.float16 else torch.bfloat16
+    _chk(x, "x", dt)
     N, H, W, Cc = x.shape
     if out is None:
-        out = torch.empty((Cc // 16, N, H, W, 16), dtype=torch.bfloat16, device=x.device)
-    _chk(out, "out", torch.bfloat16)
+        out = torch.empty((Cc // 16, N, H, W, 16), dtype=dt, device=x.device)
+    _chk(out, "out", dt)
     _L.check(_L.load().e2fgvi_nhwc_to_planar16(_ptr(x), _ptr(out), N * H * W, Cc, _stream()), "nhwc_to_planar16")
     return out
 
@@ -1467,15 +1507,15 @@ def ffn_unfold(folded, fh, fw, out=None):
 
 def softcomp_fold(emb, F_, fh, fw, H, W, Cc, bias_hwc=None, residual=None):
     lib = _L.load()
-    if isinstance(emb, torch.Tensor) and emb.dtype == torch.bfloat16:     # bf16 data path: emb, residual, result bf16
-        _chk(emb, "emb", torch.bfloat16)
-        out = torch.empty((F_, H, W, Cc), dtype=torch.bfloat16, device=emb.device)
+    if isinstance(emb, torch.Tensor) and emb.dtype in HALF16:            # 16-bit data path: emb, residual, result 16-bit
+        _chk(emb, "emb", emb.dtype)
+        out = torch.empty((F_, H, W, Cc), dtype=emb.dtype, device=emb.device)
         if bias_hwc is not None:
             _chk(bias_hwc, "bias_hwc")
         if residual is not None:
-            _chk(residual, "residual", torch.bfloat16)
-        _L.check(lib.e2fgvi_softcomp_fold_bf16(_ptr(emb), _ptr(bias_hwc), _ptr(residual), _ptr(out), F_, fh, fw, H, W, Cc,
-                                               _stream()), "softcomp_fold_bf16")
+            _chk(residual, "residual", emb.dtype)
+        fn = lib.e2fgvi_softcomp_fold_f16 if emb.dtype == torch.float16 else lib.e2fgvi_softcomp_fold_bf16
+        _L.check(fn(_ptr(emb), _ptr(bias_hwc), _ptr(residual), _ptr(out), F_, fh, fw, H, W, Cc, _stream()), "softcomp_fold_16")
         return out
     _chk(emb, "emb")
     out = empty_nhwc(F_, H, W, Cc, emb.device)

@@ -78,10 +78,12 @@ int e2fgvi_psnr_ssim(const float* img1, const float* img2, int32_t N, int32_t H,
 
 #define E2FGVI_MAX_SRC 4
 
-/* element types of the tensors of the bf16 data path (see the end of this header) */
+/* element types of the tensors of the 16-bit data path (see the end of this header) */
 #define E2FGVI_F32 0
 #define E2FGVI_BF16 1
 #define E2FGVI_BF16X3 2      /* mdcn mfma_dtype (ABI 7): fp32 sources and results, the MFMA operands as three bf16 pieces each, six exact terms per product */
+#define E2FGVI_F16 3         /* IEEE half: accepted wherever E2FGVI_BF16 names a storage type (dst / res / src / mfma / tail / helper
+                              * dtypes, e2fgvi_cast); fp32 -> fp16 rounds to nearest even, +-inf past 65504, subnormals kept */
 
 const char* e2fgvi_last_error(void);
 int e2fgvi_abi_version(void);
@@ -162,7 +164,7 @@ int e2fgvi_conv3x3_winograd4(const e2fgvi_conv_desc* d, int32_t fy, void* stream
  * (model/e2fgvi.py:99-103,261 / model/e2fgvi_hq.py:99-103,263).  With 3 output channels the nine taps move to the N side of
  * ONE [pixels x 64] x [64 x 27] GEMM (every input pixel read once, 9x fewer matrix instructions than the implicit GEMM),
  * followed by the shifted 9-term sum in LDS.  src: NHWC [N,H,W,src_ld >= 64] of src_dtype (E2FGVI_F32: exact fp32 MFMA;
- * E2FGVI_BF16: bf16 MFMA, fp32 accumulation), 16-byte aligned rows; wpacked: 64 x 32 elements of src_dtype from
+ * E2FGVI_BF16 / E2FGVI_F16: bf16 / fp16 MFMA, fp32 accumulation), 16-byte aligned rows; wpacked: 64 x 32 elements of src_dtype from
  * e2fgvi_pack_tail_weight (w: fp32 OIHW [3,64,3,3]); bias fp32 [3] or NULL; dst fp32 NCHW [N,3,H,W]; act: E2FGVI_ACT_*.
  * Only Cin = 64, Cout = 3 is built (E2FGVI_EUNSUP otherwise). */
 int64_t e2fgvi_packed_tail_weight_size(int32_t Cout, int32_t Cin);
@@ -222,8 +224,12 @@ int e2fgvi_pack_dcn_weight_x3(const float* w, void* wpacked, int32_t Cout, int32
 /* bf16 packing (e2fgvi_packed_dcn_weight_size elements of 2 bytes) for mfma_dtype = E2FGVI_BF16 */
 int e2fgvi_pack_dcn_weight_bf16(const float* w, void* wpacked, int32_t Cout, int32_t C, int32_t KH,
                                 int32_t KW, int32_t deform_groups, void* stream);
+/* ... and the fp16 packing for mfma_dtype = E2FGVI_F16 (then src_dtype must be E2FGVI_F16 -- fp16 products take fp16 sources --
+ * and dst_dtype is E2FGVI_F32 or E2FGVI_F16) */
+int e2fgvi_pack_dcn_weight_f16(const float* w, void* wpacked, int32_t Cout, int32_t C, int32_t KH,
+                               int32_t KW, int32_t deform_groups, void* stream);
 
-/* bf16 NHWC [P pixels][C] (C a multiple of 16) -> [C / 16][P][16]: the deformable conv's planar source layout (src_planar) */
+/* 16-bit NHWC [P pixels][C] (C a multiple of 16) -> [C / 16][P][16]: the deformable conv's planar source layout (src_planar) */
 int e2fgvi_nhwc_to_planar16(const void* src, void* dst, int64_t P, int32_t C, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
@@ -377,6 +383,18 @@ int e2fgvi_pack_conv_weight_bf16x(const float* w, void* wpacked, int32_t Cout, i
 int64_t e2fgvi_packed_conv_weight_bf16x_taps_size(int32_t Cout, int32_t KH, int32_t KW, int32_t cin);
 int e2fgvi_pack_conv_weight_bf16x_taps(const float* w, void* wpacked, int32_t Cout, int32_t KH, int32_t KW, int32_t cin,
                                        void* stream);
+/* The fp16 data path (the _f16 siblings of the four entry points above): the same kernel, tiles (tile codes 1-8, 11-18) and descriptor with fp16 operands on
+ * v_mfma_f32_32x32x16_f16 (same rate and operand / result layout as the bf16 instruction).  16-bit sources, the 16-bit residual,
+ * dst (dst_dtype = E2FGVI_F16) and dst2 are fp16; res_dtype / dst_dtype take E2FGVI_F32 or E2FGVI_F16; no split planes.
+ * The packers and sizes are the bf16 ones with fp16 elements (same layouts, same element counts). */
+int e2fgvi_conv2d_f16x(const e2fgvi_convx_desc* d, void* stream);
+int64_t e2fgvi_packed_conv_weight_f16x_size(int32_t Cout, int32_t groups, int32_t KH, int32_t KW, int32_t nsrc,
+                                            const int32_t* src_cpg);
+int e2fgvi_pack_conv_weight_f16x(const float* w, void* wpacked, int32_t Cout, int32_t groups, int32_t KH, int32_t KW,
+                                 int32_t nsrc, const int32_t* src_cpg, void* stream);
+int64_t e2fgvi_packed_conv_weight_f16x_taps_size(int32_t Cout, int32_t KH, int32_t KW, int32_t cin);
+int e2fgvi_pack_conv_weight_f16x_taps(const float* w, void* wpacked, int32_t Cout, int32_t KH, int32_t KW, int32_t cin,
+                                      void* stream);
 int64_t e2fgvi_packed_conv_weight_f32x_taps_size(int32_t Cout, int32_t KH, int32_t KW, int32_t cin);
 int e2fgvi_pack_conv_weight_f32x_taps(const float* w, float* wpacked, int32_t Cout, int32_t KH, int32_t KW, int32_t cin,
                                       void* stream);
@@ -436,25 +454,37 @@ int e2fgvi_focal_attention_bf16(const void* qkv, const void* kv_pool, const int3
  * (2 / 4 / 8) waves of QB (1 / 2) x 32 queries per workgroup.  Returns the previous setting (-1: environment default,
  * E2FGVI_ATT_VARIANT).  Same operator and results up to fp32 summation order in every variant. */
 int e2fgvi_focal_attention_bf16_variant(int variant);
+/* The same attention with fp16 qkv / kv_pool / out (fp16 MFMA, P rounded to fp16 for the PV product); the variant setting
+ * above selects its kernel too. */
+int e2fgvi_focal_attention_f16(const void* qkv, const void* kv_pool, const int32_t* key_tab, int32_t tab_ld,
+                               const int32_t* nkeys, void* out, int32_t B, int32_t T, int32_t fh, int32_t fw,
+                               void* stream);
 
-/* Typed variants of the HBM-bound helpers for the bf16 data path: same operators and reference call sites as the fp32
- * entry points above, tensors marked `void*` are fp32 or bf16 as the dtype argument says; all arithmetic is fp32. */
+/* Typed variants of the HBM-bound helpers for the 16-bit data path: same operators and reference call sites as the fp32
+ * entry points above, tensors marked `void*` are fp32, bf16 or fp16 as the dtype argument says; all arithmetic is fp32.
+ * The entry points named _bf16 have an _f16 sibling with the same arguments and fp16 tensors. */
 int e2fgvi_nchw_to_nhwc_x(const float* src, void* dst, int32_t dst_dtype, int32_t N, int32_t C, int32_t H, int32_t W,
                           int32_t ld, float scale, float shift, void* stream);
 int e2fgvi_resize_bilinear_bf16(const void* src, int32_t src_ld, void* dst, int32_t dst_ld, int32_t N, int32_t C, int32_t H,
                                 int32_t W, int32_t Ho, int32_t Wo, int32_t align_corners, void* stream);
-/* flows8_bf16 (optional): the [P,4] flows again as a bf16 [P,8] conv source (channels 4..7 zero) */
+int e2fgvi_resize_bilinear_f16(const void* src, int32_t src_ld, void* dst, int32_t dst_ld, int32_t N, int32_t C, int32_t H,
+                               int32_t W, int32_t Ho, int32_t Wo, int32_t align_corners, void* stream);
+/* flows8_bf16 (optional): the [P,4] flows again as a 16-bit [P,8] conv source (channels 4..7 zero) of the cond's type
+ * (bf16 beside an fp32 cond) */
 int e2fgvi_prop_cond_x(const float* feat_prop, int32_t fp_ld, const float* feat_n2, int32_t f2_ld, const float* flow_a,
                        const float* flow_b, int64_t flow_img_stride, void* cond, int32_t cond_dtype, float* flows,
                        void* flows8_bf16, int32_t N, int32_t H, int32_t W, int32_t C, void* stream);
-/* ... with the warp sources of src_dtype: E2FGVI_F32 (= e2fgvi_prop_cond_x) or E2FGVI_BF16 (bf16 NHWC features, bf16 cond:
- * half the gather bytes; the bf16 path warps the bf16 copies of the propagated features) */
+/* ... with the warp sources of src_dtype: E2FGVI_F32 (= e2fgvi_prop_cond_x) or E2FGVI_BF16 / E2FGVI_F16 (16-bit NHWC features,
+ * a cond of the same type: half the gather bytes; the 16-bit path warps the 16-bit copies of the propagated features) */
 int e2fgvi_prop_cond_xs(const void* feat_prop, int32_t fp_ld, const void* feat_n2, int32_t f2_ld, int32_t src_dtype,
                         const float* flow_a, const float* flow_b, int64_t flow_img_stride, void* cond, int32_t cond_dtype,
                         float* flows, void* flows8_bf16, int32_t N, int32_t H, int32_t W, int32_t C, void* stream);
 /* out_bf16 (optional): the 8 input channels again as bf16 [Np,h,w,8], the source of the level's bf16 conv stack */
 int e2fgvi_spynet_level_input_x(const float* pyr, const int32_t* ref_idx, const int32_t* supp_idx, const float* flow_prev,
                                 float* out, void* out_bf16, int32_t Np, int32_t h, int32_t w, void* stream);
+/* ... with the copy in fp16 */
+int e2fgvi_spynet_level_input_x_f16(const float* pyr, const int32_t* ref_idx, const int32_t* supp_idx, const float* flow_prev,
+                                    float* out, void* out_f16, int32_t Np, int32_t h, int32_t w, void* stream);
 int e2fgvi_layernorm_x(const float* x, const float* gamma, const float* beta, void* y, int32_t y_dtype, int64_t rows,
                        int32_t C, void* stream);
 int e2fgvi_window_pool_x(const void* x, int32_t dtype, const float* w45, const float* bias1, void* pooled, int32_t BT,
@@ -472,7 +502,10 @@ int e2fgvi_ffn_unfold_x(const void* folded, void* out, int32_t dtype, int32_t F,
                         int32_t C, void* stream);
 int e2fgvi_softcomp_fold_bf16(const void* emb, const float* bias_hwc, const void* residual, void* dst, int32_t F, int32_t fh,
                               int32_t fw, int32_t H, int32_t W, int32_t C, void* stream);
-/* element-wise fp32 <-> bf16 conversion (round to nearest even), n a multiple of 4 */
+int e2fgvi_softcomp_fold_f16(const void* emb, const float* bias_hwc, const void* residual, void* dst, int32_t F, int32_t fh,
+                             int32_t fw, int32_t H, int32_t W, int32_t C, void* stream);
+/* element-wise fp32 <-> bf16 / fp16 conversion (round to nearest even; fp16: the bits of torch's .half(), overflow to +-inf,
+ * subnormals kept), n a multiple of 4 */
 int e2fgvi_cast(const void* src, int32_t src_dtype, void* dst, int32_t dst_dtype, int64_t n, void* stream);
 
 #ifdef __cplusplus

@@ -54,16 +54,16 @@ def workload(a):
         ch = enc.shape[3]
         enc5 = enc.view(b, t, h, w, ch)
         loc = enc5[0, :lt].unsqueeze(1)
-        prop = eng.propagate(loc, fwd, bwd, inplace=not eng.bf16)     # as Engine.forward: bf16 writes a fresh tensor
-        if eng.bf16:
+        prop = eng.propagate(loc, fwd, bwd, inplace=not eng.x16)     # as Engine.forward: the 16-bit path writes a fresh tensor
+        if eng.x16:
             enc5[0, :lt].copy_(prop[:, 0])
         mark()
         tok = eng.soft_split(enc).view(b * t * fh * fw, 512)
         mark()
         tok16 = None
         for i in range(8):
-            if eng.bf16 and i == 7:
-                tok16 = torch.empty((b * t * fh * fw, 512), dtype=torch.bfloat16, device=dev)
+            if eng.x16 and i == 7:
+                tok16 = torch.empty((b * t * fh * fw, 512), dtype=eng.dtype, device=dev)
             tok, _ = eng.block(i, tok, b, t, fh, fw, (h, w), out2=tok16)
             mark()
         dec_in = eng.compose(tok if tok16 is None else tok16, enc, b, t, fh, fw)
