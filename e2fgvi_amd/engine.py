@@ -342,10 +342,9 @@ class Engine:
         return self._side[key]
 
     def _zero(self, shape, dtype=torch.float32):
-        key = (dtype,) + tuple(shape)
-        if key not in self._zeros:
-            self._zeros[key] = torch.zeros(tuple(shape), dtype=dtype, device=self.device)
-        return self._zeros[key]
+        """a shared all-zero buffer (read-only), filled on first use: ops._lazy orders the fill before readers on other streams"""
+        return ops._lazy(self._zeros, (dtype,) + tuple(shape), "zero buffer %s" % (tuple(shape),),
+                         lambda: torch.zeros(tuple(shape), dtype=dtype, device=self.device))
 
     def _table(self, fh, fw, blk):
         key = (fh, fw, tuple(blk["valid"]))

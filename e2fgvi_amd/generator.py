@@ -255,6 +255,7 @@ class _InpaintGeneratorBase(nn.Module):
         return (str(ps[0].device), tuple(p._version for p in ps), tuple(p.data_ptr() for p in ps), self.precision)
 
     def engine(self):
+        from . import ops
         from .engine import Engine
         key = self._fingerprint()
         if self._engine is None or key != self._engine_key:
@@ -262,9 +263,12 @@ class _InpaintGeneratorBase(nn.Module):
             if dev.type != "cuda":
                 raise RuntimeError("InpaintGenerator runs only on an MI355X (ROCm 'cuda') device: move the module "
                                    "with .to('cuda'); there is no CPU path")
-            self._engine = Engine(self.state_dict(), self.MODEL, dev, precision=self.precision)
+            self._engine = None
             self._engine_key = key
-        return self._engine
+        # built and fetched through the seam of all lazily built device state (ops._lazy): the uploads, conversions and weight
+        # packings of the construction run on the stream of the first forward, later forwards may come from any stream
+        return ops._lazy(vars(self), "_engine", "the engine (first forward of this module)",
+                         lambda: Engine(self.state_dict(), self.MODEL, dev, precision=self.precision))
 
     def forward_bidirect_flow(self, masked_local_frames):
         """[b,l_t,3,H,W] in [0,1] -> (flows_forward, flows_backward), each [b,l_t-1,2,H/4,W/4]."""

@@ -189,6 +189,50 @@ def _no_capture(what):
                            "same shapes before capturing (runner.ShardedStep does)" % what)
 
 
+# Lazily built device state (weight packings, zero buffers, bias images, the engine itself) is built on whatever stream is current
+# at its first use and then read by kernels of ANY stream: video.inpaint_video(in_flight=K) runs consecutive windows on K streams
+# that nothing orders with each other.  Every such object is built and fetched through _lazy(), the one seam: the build records
+# an event on its stream, and a fetch on another stream makes that stream wait for it.  Once the event has
+# completed the entry is dropped, so a warm forward pays one truth test of an empty list per fetch and nothing else.
+_PENDING = []    # [id of the producer's stream, event recorded behind the producer, ids of the streams that wait on it already]
+
+
+def _await_pending():
+    """The current stream waits for every lazily built object whose producer (on another stream) may not have run yet: device-side
+    waits, never a host synchronisation.  Under graph capture nothing is pending by contract: torch.cuda.graph synchronises
+    the device before it begins to capture, and _lazy() builds nothing under capture."""
+    if torch.cuda.is_current_stream_capturing():
+        return
+    cur = torch.cuda.current_stream()
+    live = []
+    for ent in _PENDING:
+        sid, ev, waiting = ent
+        if ev.query():
+            continue
+        live.append(ent)
+        if sid != cur.cuda_stream and cur.cuda_stream not in waiting:
+            cur.wait_event(ev)
+            waiting.add(cur.cuda_stream)
+    _PENDING[:] = live
+
+
+def _lazy(store, key, what, build):
+    """``store[key]``, built by ``build()`` on the current stream if it is not there yet (never under HIP-graph capture:
+    _no_capture), and safe to hand to a kernel on the current stream either way.  ``store`` is a dict, or ``vars(obj)`` for an
+    attribute that starts out as None."""
+    obj = store.get(key)
+    if obj is None:
+        _no_capture(what)
+        obj = store[key] = build()
+        if torch.cuda.is_available():
+            ev = torch.cuda.Event()
+            ev.record()
+            _PENDING.append([torch.cuda.current_stream().cuda_stream, ev, set()])
+    elif _PENDING:
+        _await_pending()
+    return obj
+
+
 class PackedConv:
     """A conv / linear layer with weights re-laid-out once for the MFMA kernel.
 
@@ -254,9 +298,10 @@ class PackedConv:
     @property
     def wino_packed(self):
         """packed weights of the fp32 F(2x2,3x3) kernel (conv_wino.hip), built on first use"""
-        t = self._own.get("wino")
-        if t is None and self.algo in ("winograd", "auto"):
-            _no_capture(self.name + " (Winograd F(2x2,3x3) weights)")
+        if self.algo not in ("winograd", "auto"):
+            return None
+
+        def build():
             lib = _L.load()
             arr = (C.c_int32 * len(self.cpg))(*self.cpg)
             n = lib.e2fgvi_packed_winograd_weight_size(self.Cout, self.groups, len(self.cpg), arr)
@@ -265,15 +310,16 @@ class PackedConv:
             t = torch.empty(int(n), dtype=torch.float32, device=self._w_raw.device)
             _L.check(lib.e2fgvi_pack_winograd_weight(_ptr(self._w_raw), _ptr(t), self.Cout, self.groups, len(self.cpg), arr,
                                                      _stream()), "pack_winograd_weight")
-            self._own["wino"] = t
-        return t
+            return t
+        return _lazy(self._own, "wino", self.name + " (Winograd F(2x2,3x3) weights)", build)
 
     @property
     def wpacked(self):
         """packed weights of the register-staged implicit GEMM (conv.hip), built on first use"""
-        t = self._own.get("igemm")
-        if t is None and self.algo != "winograd":
-            _no_capture(self.name + " (implicit-GEMM weights)")
+        if self.algo == "winograd":
+            return None
+
+        def build():
             lib = _L.load()
             arr = (C.c_int32 * len(self.cpg))(*self.cpg)
             n = lib.e2fgvi_packed_conv_weight_size(self.Cout, self.groups, self.KH, self.KW, len(self.cpg), arr, self.bk)
@@ -282,8 +328,8 @@ class PackedConv:
             t = torch.empty(int(n), dtype=torch.float32, device=self._w_raw.device)
             _L.check(lib.e2fgvi_pack_conv_weight(_ptr(self._w_raw), _ptr(t), self.Cout, self.groups, self.KH, self.KW,
                                                  len(self.cpg), arr, self.bk, _stream()), "pack_conv_weight")
-            self._own["igemm"] = t
-        return t
+            return t
+        return _lazy(self._own, "igemm", self.name + " (implicit-GEMM weights)", build)
 
     def weight_bytes(self):
         """device bytes of the packings this layer holds right now (the checkpoint tensor _w_raw not counted)"""
@@ -292,9 +338,7 @@ class PackedConv:
 
     def _wino4(self, fy):
         """packed weights of the wide-tile Winograd kernel (conv_wino4.hip), built on first use"""
-        t = self._w4.get(fy)
-        if t is None:
-            _no_capture(self.name + " (Winograd F(%dx4,3x3) weights)" % fy)
+        def build():
             lib = _L.load()
             arr = (C.c_int32 * len(self.cpg))(*self.cpg)
             n = lib.e2fgvi_packed_winograd4_weight_size(self.Cout, self.groups, len(self.cpg), arr, fy)
@@ -303,8 +347,8 @@ class PackedConv:
             t = torch.empty(int(n), dtype=torch.float32, device=self._w_oihw.device)
             _L.check(lib.e2fgvi_pack_winograd4_weight(_ptr(self._w_oihw), _ptr(t), self.Cout, self.groups, len(self.cpg), arr, fy,
                                                       _stream()), "pack_winograd4_weight")
-            self._w4[fy] = t
-        return t
+            return t
+        return _lazy(self._w4, fy, self.name + " (Winograd F(%dx4,3x3) weights)" % fy, build)
 
     def _wino4_rule(self, N, H, W):
         """tile code of the wide-tile Winograd variant for this call, or 0 for the F(2x2,3x3) kernel"""
@@ -320,35 +364,44 @@ class PackedConv:
 
     def _alt(self):
         """the LDS-DMA fp32 kernel (conv_bf16x.hip, F32 variant) as a tuning alternative of the implicit GEMM"""
-        if self.alt is None and getattr(self, "_w_raw", None) is not None:
-            _no_capture(self.name + " (LDS-DMA fp32 alternative)")
-            self.alt = PackedConvX(self._w_raw, self.bias, self.cpg, groups=self.groups, stride=self.stride, pad=self.pad,
-                                   dtype=torch.float32)
-            self.alt.name = self.name
-        return self.alt
+        if getattr(self, "_w_raw", None) is None:
+            return self.alt
+
+        def build():
+            alt = PackedConvX(self._w_raw, self.bias, self.cpg, groups=self.groups, stride=self.stride, pad=self.pad,
+                              dtype=torch.float32)
+            alt.name = self.name
+            return alt
+        return _lazy(vars(self), "alt", self.name + " (LDS-DMA fp32 alternative)", build)
 
     def _wino_x3(self):
         """packed weights of the split-bf16 Winograd kernel (three bf16 planes of the transformed weights), built on first use"""
-        if getattr(self, "_w3", None) is None and self._w_oihw is not None:
-            _no_capture(self.name + " (split-operand Winograd weights)")
+        if self._w_oihw is None:
+            return None
+
+        def build():
             lib = _L.load()
             arr = (C.c_int32 * len(self.cpg))(*self.cpg)
             n = lib.e2fgvi_packed_winograd_weight_x3_size(self.Cout, self.groups, len(self.cpg), arr)
             if n < 0:
                 _L.check(int(n), "packed_winograd_weight_x3_size")
-            self._w3 = torch.empty(int(n), dtype=torch.bfloat16, device=self._w_oihw.device)
-            _L.check(lib.e2fgvi_pack_winograd_weight_x3(_ptr(self._w_oihw), _ptr(self._w3), self.Cout, self.groups, len(self.cpg), arr,
+            t = torch.empty(int(n), dtype=torch.bfloat16, device=self._w_oihw.device)
+            _L.check(lib.e2fgvi_pack_winograd_weight_x3(_ptr(self._w_oihw), _ptr(t), self.Cout, self.groups, len(self.cpg), arr,
                                                         _stream()), "pack_winograd_weight_x3")
-        return getattr(self, "_w3", None)
+            return t
+        return _lazy(vars(self), "_w3", self.name + " (split-operand Winograd weights)", build)
 
     def _alt3(self):
         """the same layer on the bf16 matrix pipe (three-way split operands, six exact bf16 MFMA terms per product)"""
-        if self.alt3 is None and getattr(self, "_w_raw", None) is not None and not any(c % 4 for c in self.cpg):
-            _no_capture(self.name + " (split-operand GEMM alternative)")
-            self.alt3 = PackedConvX(self._w_raw, self.bias, self.cpg, groups=self.groups, stride=self.stride, pad=self.pad,
-                                    dtype=torch.float32, x3=True)
-            self.alt3.name = self.name
-        return self.alt3
+        if getattr(self, "_w_raw", None) is None or any(c % 4 for c in self.cpg):
+            return self.alt3
+
+        def build():
+            alt3 = PackedConvX(self._w_raw, self.bias, self.cpg, groups=self.groups, stride=self.stride, pad=self.pad,
+                               dtype=torch.float32, x3=True)
+            alt3.name = self.name
+            return alt3
+        return _lazy(vars(self), "alt3", self.name + " (split-operand GEMM alternative)", build)
 
     def _autotune(self, lib, d, wino=False):
         """Device time of every candidate tile code on this exact call (2 launches each, hip events); the launches
@@ -712,10 +765,7 @@ class PackedConvX:
     @property
     def wpacked(self):
         """packed weights; an fp32 layer (whose split-operand alternative alt3 may be what runs) packs its own on first use"""
-        if self._wp is None:
-            _no_capture(self.name + " (LDS-DMA GEMM weights)")
-            self._wp = self._pack(self._w_raw)
-        return self._wp
+        return _lazy(vars(self), "_wp", self.name + " (LDS-DMA GEMM weights)", lambda: self._pack(self._w_raw))
 
     def weight_bytes(self):
         return (0 if self._wp is None else self._wp.numel() * self._wp.element_size()) + (self.alt3.weight_bytes() if self.alt3 is not None else 0)
@@ -758,12 +808,15 @@ class PackedConvX:
 
     def _alt3(self):
         """this fp32 layer on the bf16 matrix pipe (x3=True), built on first use"""
-        if self.alt3 is None and self._w_raw is not None:
-            _no_capture(self.name + " (split-operand GEMM alternative)")
-            self.alt3 = PackedConvX(self._w_raw, self.bias, self.cpg, groups=self.groups, stride=self.stride, pad=self.pad,
-                                    dtype=torch.float32, taps=self._taps_arg, x3=True)
-            self.alt3.name = self.name
-        return self.alt3
+        if self._w_raw is None:
+            return self.alt3
+
+        def build():
+            alt3 = PackedConvX(self._w_raw, self.bias, self.cpg, groups=self.groups, stride=self.stride, pad=self.pad,
+                               dtype=torch.float32, taps=self._taps_arg, x3=True)
+            alt3.name = self.name
+            return alt3
+        return _lazy(vars(self), "alt3", self.name + " (split-operand GEMM alternative)", build)
 
     def _desc(self, srcs, out, out_coff, residual, res_coff, act, slope, out2, out_nchw):
         """the C descriptor of one call (srcs: list of (tensor, channel offset))"""
@@ -947,11 +1000,13 @@ class SoftCompGather:
 
     def bias_image(self, fh, fw):
         """fold of the Linear's bias: [3 fh, 3 fw, C] fp32 (computed once per token grid with the fold kernel)"""
-        key = (fh, fw)
-        if key not in self._bias_img and self.bias is not None:
+        if self.bias is None:
+            return None
+
+        def build():
             rows = self.bias.view(self.C, 49).t().reshape(1, 49 * self.C).expand(fh * fw, 49 * self.C).contiguous()
-            self._bias_img[key] = softcomp_fold(rows, 1, fh, fw, 3 * fh, 3 * fw, self.C)[0].contiguous()
-        return self._bias_img.get(key)
+            return softcomp_fold(rows, 1, fh, fw, 3 * fh, 3 * fw, self.C)[0].contiguous()
+        return _lazy(self._bias_img, (fh, fw), "sc.embedding (folded bias image)", build)
 
     def __call__(self, tokens, out=None, out_dtype=None):
         """tokens [F, fh, fw, hidden] -> folded [F, 3 fh, 3 fw, C]"""

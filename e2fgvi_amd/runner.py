@@ -91,17 +91,26 @@ class ShardedStep:
     those of the last one; a returned buffer is valid until the next ``run()`` (two gather buffers alternate).
     Without a gather ``run()`` / ``finish()`` return this step's frames directly.
 
-    in_flight = K > 1 (without a gather; round 6): K HIP graphs of the same forward, each with its own static buffers and its own
-    stream, replayed round-robin -- step n + 1 starts while step n is still in its latency-bound propagation chain (the engine's
-    state is read-only under replay: weights, key tables, zero buffers).  ``run()`` then returns the frames of the step issued
-    K - 1 calls earlier (None for the first K - 1 calls), valid until the next ``run()``; ``finish()`` drains the pipelines and
-    returns the last step's frames.  Ordering: a pipeline's replay waits for everything the caller has enqueued on the current
-    stream so far (the consumer of the buffer it is about to overwrite), the current stream waits for the step it hands out."""
+    in_flight = K > 1 (without a gather; round 6): K HIP graphs of the same forward, each with its own static buffers -- input
+    included -- and its own stream, replayed round-robin -- step n + 1 starts while step n is still in its latency-bound propagation
+    chain (the engine's state is read-only under replay: weights, key tables, zero buffers).  ``run()`` then returns the frames of
+    the step issued K - 1 calls earlier (None for the first K - 1 calls), valid until the next ``run()``; ``finish()`` drains the
+    pipelines and returns the last step's frames.  Ordering: a pipeline's replay waits for everything the caller has enqueued on
+    the current stream so far (the consumer of the buffer it is about to overwrite), the current stream waits for the step it
+    hands out.
+
+    Feeding a step: ``x`` (the tensor given to the constructor, ``step.x``) is the input of the NEXT ``run()``.  A caller with
+    changing clips writes the next clip into it on the current stream -- ``step.x.copy_(clip)`` -- and calls ``run()``; the
+    frames come back in the order of the calls, one result per call, none skipped or repeated (the first call runs eagerly and
+    returns its own frames at once; with in_flight = K the frames of call n >= 2 come back from call n + K - 1, the last K - 1
+    from further calls or, the very last, from ``finish()``).  With in_flight > 1 ``run()`` copies ``x`` into the pipeline's
+    private input before it replays, and the current stream waits for that copy: ``x`` may be overwritten as soon as ``run()``
+    returns, while up to K - 1 earlier steps are still in flight."""
 
     def __init__(self, net, x, lt, group_world=1, use_graph=True, force_gather=False, pack_u8=False, group=None, in_flight=1):
         self.net, self.x, self.lt, self.world = net, x, lt, group_world
         self.in_flight = max(1, int(in_flight))
-        self._pipes = None         # in_flight > 1: [(graph, static output, stream, event)]
+        self._pipes = None         # in_flight > 1: [graph, static output, stream, event, issued, static input, its copy's event]
         self.gather = group_world > 1 or force_gather
         self.pack_u8, self.group = pack_u8, group
         self.graph = None
@@ -214,11 +223,17 @@ class ShardedStep:
         with whole_propagation(self.net):
             for _ in range(self.in_flight):
                 self.graph = None
-                self._capture()
+                # a private static input per pipeline: the graph is captured on it, run() copies x into it.  With one shared x a
+                # caller who refreshed it before run() wrote under the up to K - 1 earlier steps still reading it.
+                shared, self.x = self.x, self.x.clone()
+                try:
+                    self._capture()
+                finally:
+                    private, self.x = self.x, shared
                 if self.graph is None:                 # capture unsupported: sequential eager steps
                     self.in_flight, self.out = 1, keep
                     return False
-                graphs.append((self.graph, self.out))
+                graphs.append((self.graph, self.out, private))
         K = self.in_flight
         cand = [torch.cuda.Stream() for _ in range(K + 9)]
         cur = torch.cuda.current_stream()
@@ -248,7 +263,7 @@ class ShardedStep:
             if best_t is None or min(ts) < best_t:
                 best, best_t = off, min(ts)
         self.stream_window = (best, round(1e3 * best_t / (2 * K), 3))
-        self._pipes = [[g, o, cand[best + k], torch.cuda.Event(), False] for k, (g, o) in enumerate(graphs)]
+        self._pipes = [[g, o, cand[best + k], torch.cuda.Event(), False, xin, torch.cuda.Event()] for k, (g, o, xin) in enumerate(graphs)]
         self._issued = 0
         return True
 
@@ -257,11 +272,14 @@ class ShardedStep:
             return self.run()
         K, n = self.in_flight, self._issued
         cur = torch.cuda.current_stream()
-        g, out, st, ev, _ = self._pipes[n % K]
-        st.wait_stream(cur)                            # the consumer of the buffer this replay overwrites
+        g, out, st, ev, _, xin, copied = self._pipes[n % K]
+        st.wait_stream(cur)                            # the consumer of the buffer this replay overwrites, the producer of x
         with torch.cuda.stream(st):
+            xin.copy_(self.x)                          # this pipeline's previous replay, the last reader of xin, is ahead on st
+            copied.record(st)
             g.replay()
             ev.record(st)
+        cur.wait_event(copied)                         # x is the caller's again once run() returns
         self._pipes[n % K][4] = True
         self._issued = n + 1
         self._calls += 1
