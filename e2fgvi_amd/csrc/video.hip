@@ -144,7 +144,71 @@ __global__ void pred_to_u8_kernel(const float* __restrict__ pred, unsigned char*
     dst[idx] = (unsigned char)(int)(((p + 1.0f) / 2.0f) * 255.0f);
 }
 
+// Frame slabs between a cache and a window (test.py:152: the frames of a window are picked by id out of the whole video;
+// with reuse=True their encoder features and flows are picked out of a cache instead).  row i of `rows` [n][slab] pairs with
+// slab ids[i] of `cache` [slots][slab]; SCATTER: cache[ids[i]] = rows[i], else rows[i] = cache[ids[i]].  A pure HBM copy:
+// blockIdx.y is the row, the threads of a block walk the slab in consecutive V-sized words (V = uint4 whenever the slab and
+// both bases are 16-byte multiples: one 1 KiB contiguous run per wave and instruction).  An id outside [0, slots) moves
+// nothing (gather: the row is zero-filled), so the kernel stays in bounds whatever the table holds.
+template <typename V, bool SCATTER>
+__global__ void slab_copy_kernel(V* __restrict__ cache, V* __restrict__ rows, const int* __restrict__ ids, int slots,
+                                 long long words) {
+    const int i = blockIdx.y;
+    const int id = ids[i];
+    const bool ok = id >= 0 && id < slots;
+    if (SCATTER && !ok) return;
+    V* r = rows + (long long)i * words;
+    V* c = cache + (long long)(ok ? id : 0) * words;
+    const long long step = (long long)gridDim.x * blockDim.x;
+    for (long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x; k < words; k += step) {
+        if (SCATTER) c[k] = r[k];
+        else r[k] = ok ? c[k] : V{};
+    }
+}
+
+template <bool SCATTER>
+int slab_copy(const void* cache, const void* rows, const int32_t* ids, int32_t n, int32_t slots, int64_t slab_bytes, void* stream,
+              const char* what) {
+    E2_REQUIRE(cache && rows && ids && n > 0 && n <= 65535 && slots > 0 && slab_bytes > 0, E2FGVI_EINVAL, "%s: bad arguments", what);
+    E2_REQUIRE(slab_bytes % 4 == 0, E2FGVI_EINVAL, "%s: slabs must be whole 32-bit words, got %lld bytes", what, (long long)slab_bytes);
+    const unsigned long long align = (unsigned long long)(uintptr_t)cache | (unsigned long long)(uintptr_t)rows |
+                                     (unsigned long long)slab_bytes;
+    E2_REQUIRE(align % 4 == 0, E2FGVI_EINVAL, "%s: buffers must be 4-byte aligned", what);
+    const int vec = align % 16 == 0 ? 16 : (align % 8 == 0 ? 8 : 4);
+    const long long words = slab_bytes / vec;
+    // enough blocks per slab to fill the chip with a few rows, at most 4 words per thread and launch dimension
+    long long bx = (words + NTH * 4 - 1) / (NTH * 4);
+    bx = bx < 1 ? 1 : (bx > 4096 ? 4096 : bx);
+    const dim3 grid((unsigned)bx, (unsigned)n);
+    if (vec == 16)
+        hipLaunchKernelGGL((slab_copy_kernel<uint4, SCATTER>), grid, dim3(NTH), 0, (hipStream_t)stream, (uint4*)cache, (uint4*)rows, ids,
+                           slots, words);
+    else if (vec == 8)
+        hipLaunchKernelGGL((slab_copy_kernel<uint2, SCATTER>), grid, dim3(NTH), 0, (hipStream_t)stream, (uint2*)cache, (uint2*)rows, ids,
+                           slots, words);
+    else
+        hipLaunchKernelGGL((slab_copy_kernel<unsigned, SCATTER>), grid, dim3(NTH), 0, (hipStream_t)stream, (unsigned*)cache,
+                           (unsigned*)rows, ids, slots, words);
+    return 0;
+}
+
 }  // namespace
+
+extern "C" int e2fgvi_gather_slabs(const void* cache, int32_t slots, const int32_t* ids, int32_t n, int64_t slab_bytes, void* window,
+                                   void* stream) {
+    const int rc = slab_copy<false>(cache, window, ids, n, slots, slab_bytes, stream, "gather_slabs");
+    if (rc) return rc;
+    E2_LAUNCH_CHECK("gather_slabs");
+    return 0;
+}
+
+extern "C" int e2fgvi_scatter_slabs(const void* rows, const int32_t* ids, int32_t n, int64_t slab_bytes, void* cache, int32_t slots,
+                                    void* stream) {
+    const int rc = slab_copy<true>(cache, rows, ids, n, slots, slab_bytes, stream, "scatter_slabs");
+    if (rc) return rc;
+    E2_LAUNCH_CHECK("scatter_slabs");
+    return 0;
+}
 
 extern "C" int e2fgvi_mask_prepare(const uint8_t* masks, int32_t L, int32_t Hin, int32_t Win, const int32_t* ytab,
                                    const int32_t* xtab, uint8_t* out, int32_t H, int32_t W, int32_t iterations, void* stream) {

@@ -288,6 +288,9 @@ class Engine:
         self.overlap_flows = True
         self._side = None
         self._given = None         # (flows, encoder output) of segment graphs: runner.ShardedStep._capture_segments
+        # frames through the encoder and the decoder, pairs through SPyNet, since construction (host integers: what
+        # video.inpaint_video(reuse=True) saves is counted, not timed)
+        self.counters = {"encoder_frames": 0, "flow_pairs": 0, "decoder_frames": 0}
         torch.cuda.synchronize(self.device)
 
     # ------------------------------------------------------------------ helpers
@@ -354,6 +357,14 @@ class Engine:
         return self._tables[key]
 
     # ------------------------------------------------------------------ flows
+    def pair_table(self, pairs):
+        """Device index tables of SPyNet runs for `pairs`, a host list of (i, j) frame positions: int32 [2, 2 P] -- row 0 the
+        reference image and row 1 the support image of 2 P flow computations, the P flows i -> j first, then the P flows j -> i
+        (e2fgvi.py:222-229 batches both directions the same way).  An upload: build it before the forwards that use it."""
+        ref = [int(i) for i, _ in pairs]
+        supp = [int(j) for _, j in pairs]
+        return torch.tensor([ref + supp, supp + ref], dtype=torch.int32, device=self.device)
+
     def flows(self, frames, l_t):
         """frames: [b,t,3,H,W] in [-1,1].  Returns (fwd, bwd) NHWC [b, l_t-1, h, w, 2]."""
         b, t, c, H, W = frames.shape
@@ -361,7 +372,22 @@ class Engine:
         local = frames[:, :l_t].reshape(b * l_t, c, H, W)
         if not local.is_contiguous():
             local = local.contiguous()
-        small = ops.resize_bilinear(local, (h, w), True, src_nchw=True, out_ld=4, scale=self.half, shift=self.half)
+        key = ("pairs", b, l_t)
+        if key not in self._tables:          # host->device uploads happen once (HIP-graph capture safe)
+            self._tables[key] = self.pair_table([(bi * l_t + i, bi * l_t + i + 1) for bi in range(b) for i in range(l_t - 1)])
+        fwd, bwd = self.pair_flows(local, self._tables[key])
+        return fwd.view(b, l_t - 1, h, w, 2), bwd.view(b, l_t - 1, h, w, 2)
+
+    def pair_flows(self, frames, pairs):
+        """SPyNet on explicit pairs of a flat list of frames (the body of flows(): flow_comp.py:84-169, one pair at a time and
+        independent of every other pair).  frames: [n,3,H,W] in [-1,1]; pairs: int32 device [2, 2 P] as pair_table() builds it
+        (positions into `frames`).  Returns (forward, backward) NHWC fp32 [P, h, w, 2]: the flows i -> j and j -> i of pair (i, j)."""
+        ops._chk(pairs, "pairs", torch.int32)
+        if pairs.dim() != 2 or pairs.shape[0] != 2 or pairs.shape[1] % 2 or pairs.shape[1] == 0:
+            raise ValueError("pairs must be int32 [2, 2 P] (Engine.pair_table), got %s" % (tuple(pairs.shape),))
+        n, c, H, W = frames.shape
+        h, w = H // 4, W // 4
+        small = ops.resize_bilinear(frames, (h, w), True, src_nchw=True, out_ld=4, scale=self.half, shift=self.half)
         w_up = w if w % 32 == 0 else 32 * (w // 32 + 1)
         h_up = h if h % 32 == 0 else 32 * (h // 32 + 1)
         pyr = [ops.resize_bilinear(small, (h_up, w_up), False, channels=3, out_ld=4, scale=self.spy_scale,
@@ -369,19 +395,13 @@ class Engine:
         for _ in range(5):
             pyr.append(ops.avgpool2(pyr[-1]))
         pyr = pyr[::-1]
-        nf = b * (l_t - 1)
-        key = ("pairs", b, l_t, h, w)
+        nf = pairs.shape[1] // 2
+        self.counters["flow_pairs"] += nf
+        key = ("flow scale", h, w)
         if key not in self._tables:          # host->device uploads happen once (HIP-graph capture safe)
-            ref, supp = [], []
-            for bi in range(b):
-                for i in range(l_t - 1):
-                    ref.append(bi * l_t + i); supp.append(bi * l_t + i + 1)
-            ref, supp = ref + supp, supp + ref
-            self._tables[key] = (torch.tensor(ref, dtype=torch.int32, device=self.device),
-                                 torch.tensor(supp, dtype=torch.int32, device=self.device),
-                                 torch.tensor([float(w) / float(w_up), float(h) / float(h_up)], dtype=torch.float32,
-                                              device=self.device))
-        ref_idx, supp_idx, sc = self._tables[key]
+            self._tables[key] = torch.tensor([float(w) / float(w_up), float(h) / float(h_up)], dtype=torch.float32, device=self.device)
+        sc = self._tables[key]
+        ref_idx, supp_idx = pairs[0], pairs[1]
         flow = None
         for lv in range(6):
             # the fp32 level input (images, warped support image, upsampled flow); the bf16 path's convs read its bf16 copy
@@ -396,16 +416,23 @@ class Engine:
             x = cv[3]([x], act=ACT_RELU)
             flow = cv[4]([x], out_dtype=torch.float32, residual=inp, res_coff=6)          # + fp32 upsampled flow
         flow = ops.resize_bilinear(flow, (h, w), False, scale=sc)
-        fwd = flow[:nf].view(b, l_t - 1, h, w, 2)
-        bwd = flow[nf:].view(b, l_t - 1, h, w, 2)
-        return fwd, bwd
+        return flow[:nf], flow[nf:]
 
     # ------------------------------------------------------------------ encoder
     def encode(self, frames, join=None):
         """join: called in front of encoder.layers.<join_at> (16 at one clip: the fork's other branch, SPyNet, overlaps layers 0 .. 14;
         the bf16 path joins behind the encoder)"""
         b, t, c, H, W = frames.shape
-        x = ops.nchw_to_nhwc(frames.reshape(b * t, c, H, W).contiguous(), ld=8 if self.x16 else 4, out_dtype=self.dtype)
+        return self._encode(frames.reshape(b * t, c, H, W).contiguous(), b, join)
+
+    def encode_frames(self, frames):
+        """The encoder on a flat list of frames (e2fgvi.py:96-109 sees one frame at a time): [n,3,H,W] in [-1,1] ->
+        [n, H/4, W/4, 128] in the engine's dtype."""
+        return self._encode(ops._chk(frames, "frames"), 1, None)
+
+    def _encode(self, frames, b, join):
+        self.counters["encoder_frames"] += frames.shape[0]
+        x = ops.nchw_to_nhwc(frames, ld=8 if self.x16 else 4, out_dtype=self.dtype)
         e = self.enc
         lr = dict(act=ACT_LRELU, slope=0.2)
         x = e[0]([x], **lr)
@@ -423,7 +450,7 @@ class Engine:
             if not joined and (join_at <= 2 * k + 2 or k == 8):        # never leave the encoder with the fork open
                 join()
                 joined = True
-        return x                                            # [b*t, h, w, 128]
+        return x                                            # [n, h, w, 128]
 
     # ------------------------------------------------------------------ propagation
     def propagate(self, loc, flows_a, flows_b, inplace=False):
@@ -581,6 +608,7 @@ class Engine:
     # ------------------------------------------------------------------ decoder
     def decode(self, x):
         n, h, w, _ = x.shape
+        self.counters["decoder_frames"] += n
         lr = dict(act=ACT_LRELU, slope=0.2)
         d = self.dec
         x = ops.resize_bilinear(x, (2 * h, 2 * w), True)
@@ -591,9 +619,28 @@ class Engine:
         return d[3]([x], act=ACT_TANH, out_nchw=True)             # 64 -> 3, tanh, fp32 NCHW frames
 
     # ------------------------------------------------------------------ whole forward (e2fgvi_hq.py:235-263)
-    def forward(self, frames, l_t, trace=None):
-        """trace: a dict that receives fp32 copies of the stage outputs (flows, encoder, propagation, tokens, decoder input)"""
-        b, t, c, H, W = frames.shape
+    def forward(self, frames, l_t, trace=None, given=None, decode_local=False):
+        """trace: a dict that receives fp32 copies of the stage outputs (flows, encoder, propagation, tokens, decoder input)
+
+        given = ((fwd, bwd), enc): the per-pair and per-frame stages computed by the caller -- flows fp32 NHWC [b, l_t-1, h, w, 2]
+        (pair_flows / flows) and encoder features [b*t, h, w, 128] in the engine's dtype (encode_frames / encode) -- instead of
+        running SPyNet and the encoder here; no side-stream fork then.  `enc` is CONSUMED: at one clip the propagated features
+        are written over its local frames, so hand in a copy of anything that is to be used again (video.inpaint_video(reuse=True)
+        gathers a fresh window tensor from its cache).  `frames` may then be None: only its shape is used.
+
+        decode_local=True: compose and decode only the first l_t frames of the clip -- all t frames still pass through the
+        transformer -- and return [l_t,3,H,W] frames.  One clip only: at b == 1 the local frames' tokens are the leading rows;
+        b > 1 raises ValueError."""
+        if given is None:
+            given = self._given
+        if frames is None:
+            if given is None:
+                raise ValueError("frames may be None only with given=((fwd, bwd), enc)")
+            (g_fwd, _), g_enc = given
+            b = g_fwd.shape[0]
+            t, c, H, W = g_enc.shape[0] // b, 3, 4 * g_enc.shape[1], 4 * g_enc.shape[2]
+        else:
+            b, t, c, H, W = frames.shape
         if H % 4 or W % 4:
             raise ValueError("H and W must be multiples of 4")
         h, w = H // 4, W // 4
@@ -605,9 +652,16 @@ class Engine:
             raise ValueError("model 'e2fgvi' is fixed to 432x240 inputs (sc.bias is [128,60,108]); use e2fgvi_hq")
         if not (1 <= l_t <= t):
             raise ValueError("num_local_frames must be in [1, t]")
-        frames = ops._chk(frames.float().contiguous(), "masked_frames")
-        if self._given is not None:
-            (fwd, bwd), enc = self._given
+        if decode_local and b != 1:
+            raise ValueError("decode_local=True takes one clip per forward (b == 1), got b = %d" % b)
+        if frames is not None:
+            frames = ops._chk(frames.float().contiguous(), "masked_frames")
+        if given is not None:
+            (fwd, bwd), enc = given
+            ops._chk(fwd, "given flows (forward)"); ops._chk(bwd, "given flows (backward)"); ops._chk(enc, "given encoder features", self.dtype)
+            if tuple(fwd.shape) != (b, l_t - 1, h, w, 2) or tuple(bwd.shape) != tuple(fwd.shape) or tuple(enc.shape) != (b * t, h, w, 128):
+                raise ValueError("given: flows must be [%d,%d,%d,%d,2] and the encoder features [%d,%d,%d,128], got %s, %s and %s"
+                                 % (b, l_t - 1, h, w, b * t, h, w, tuple(fwd.shape), tuple(bwd.shape), tuple(enc.shape)))
         elif l_t == 1:
             # a one-frame local window (test.py on a 1-frame video): the reference's flow tensors are empty
             # [b,0,2,h,w] and each propagation direction is backbone(cat(x, 0)) (feat_prop.py:105,131-137)
@@ -654,7 +708,11 @@ class Engine:
             if trace is not None:
                 trace["block%d_attn_out" % i] = x1
                 trace["tokens%d" % (i + 1)] = tok
-        dec_in = self.compose(tok if tok16 is None else tok16, enc, b, t, fh, fw)
+        last = tok if tok16 is None else tok16
+        if decode_local:                   # b == 1: the local frames are the leading rows of the tokens and of `enc`
+            dec_in = self.compose(last[:l_t * fh * fw], enc[:l_t], 1, l_t, fh, fw)
+        else:
+            dec_in = self.compose(last, enc, b, t, fh, fw)
         if trace is not None:
             trace["dec_in"] = dec_in.float()
         out = self.decode(dec_in)

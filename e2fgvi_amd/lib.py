@@ -133,6 +133,8 @@ SYMBOLS = {
     "e2fgvi_resample_u8": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, _fp, _fp, _i32, _fp]),
     "e2fgvi_float_to_u8": (C.c_int, [_fp, _fp, _i64, _fp]),
     "e2fgvi_pred_to_u8": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, _fp]),
+    "e2fgvi_gather_slabs": (C.c_int, [_fp, _i32, _fp, _i32, _i64, _fp, _fp]),
+    "e2fgvi_scatter_slabs": (C.c_int, [_fp, _fp, _i32, _i64, _fp, _i32, _fp]),
     "e2fgvi_psnr_ssim_workspace": (_i64, [_i32, _i32, _i32]),
     "e2fgvi_psnr_ssim": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _fp, _fp, _fp]),
     "e2fgvi_softcomp_fold": (C.c_int, [_fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _fp]),
@@ -228,7 +230,11 @@ def load():
             "fallback exists).  Build them: python -m e2fgvi_amd.build" % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in SYMBOLS.items():
-        fn = getattr(lib, name)          # AttributeError if the ABI is incomplete
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            # a library built before the symbol was added (the version number covers layouts; added entry points are caught here)
+            raise HipLibraryMissing("%s does not export %s: rebuild it (python -m e2fgvi_amd.build)" % (LIB_PATH, name)) from None
         fn.restype = res
         fn.argtypes = args
         if args and args[-1] is _fp and res is C.c_int:      # asynchronous launch on a stream

@@ -1671,3 +1671,36 @@ def pred_to_u8(pred, H=None, W=None):
     out = torch.empty((N, H, W, 3), dtype=torch.uint8, device=pred.device)
     _L.check(lib.e2fgvi_pred_to_u8(_ptr(pred), _ptr(out), N, H, W, Hp, Wp, _stream()), "pred_to_u8")
     return out
+
+
+def _slabs(cache, rows, ids, what):
+    _chk_any(cache, "cache"); _chk(rows, "rows", cache.dtype); _chk(ids, "ids", torch.int32)
+    if cache.dim() < 2 or rows.dim() != cache.dim() or tuple(rows.shape[1:]) != tuple(cache.shape[1:]):
+        raise ValueError("%s: cache [slots, ...] and rows [n, ...] must agree past the first dimension, got %s and %s"
+                         % (what, tuple(cache.shape), tuple(rows.shape)))
+    if ids.dim() != 1 or ids.numel() != rows.shape[0] or rows.shape[0] == 0:
+        raise ValueError("%s: ids must be int32 [%d]" % (what, rows.shape[0]))
+    if ids.device != cache.device or rows.device != cache.device:
+        raise ValueError("%s: cache, rows and ids must be on one device" % what)
+    return rows[0].numel() * rows.element_size()
+
+
+def gather_slabs(cache, ids, out=None):
+    """out[i] = cache[ids[i]]: cache [slots, ...] (fp32 / bf16 / fp16), ids device int32 [n] -> [n, ...], a fresh tensor
+    unless `out` is given.  test.py:152 on cached per-frame results; no host read, capturable (csrc/video.hip)."""
+    lib = _L.load()
+    _chk_any(cache, "cache")
+    if out is None:
+        out = torch.empty((ids.numel(),) + tuple(cache.shape[1:]), dtype=cache.dtype, device=cache.device)
+    slab = _slabs(cache, out, ids, "gather_slabs")
+    _L.check(lib.e2fgvi_gather_slabs(_ptr(cache), cache.shape[0], _ptr(ids), ids.numel(), slab, _ptr(out), _stream()), "gather_slabs")
+    return out
+
+
+def scatter_slabs(rows, ids, cache):
+    """cache[ids[i]] = rows[i] (ids distinct): the mirror of gather_slabs.  Returns cache."""
+    lib = _L.load()
+    slab = _slabs(cache, rows, ids, "scatter_slabs")
+    _L.check(lib.e2fgvi_scatter_slabs(_ptr(rows), _ptr(ids), ids.numel(), slab, _ptr(cache), cache.shape[0], _stream()),
+             "scatter_slabs")
+    return cache

@@ -42,6 +42,87 @@ def plan_windows(length, neighbor_stride=5, ref_length=10, num_ref=-1):
     return windows
 
 
+class ReusePlan:
+    """What plan_reuse returns: ``windows`` -- one dict per window of plan_windows, in its order -- and the cache sizes the plan
+    needs: ``slots`` encoder-cache slots (one frame's features each) and ``pair_slots`` flow-cache slots (the two flows of one
+    adjacent pair each), both the peak number live at once.  Keys of a window's dict (ids are video frame numbers):
+
+      neighbors, refs   plan_windows's ids
+      encode            ids encoded in this window (their first use), in window order
+      clip              ids whose masked frame is built now: ``encode``, then the frames only this window's new pairs need
+      pairs             adjacent pairs (j, j + 1) whose flows are computed now (first window in which both are local)
+      pair_pos          the same pairs as positions into ``clip``
+      new_slots         cache slot of every id of ``encode``
+      enc_slots         cache slot of every id of the window, neighbours first (the order of the forward's frames)
+      new_pair_slots    flow-cache slot of every pair of ``pairs``
+      flow_slots        flow-cache slot of every adjacent pair of ``neighbors``, in order
+      free, free_pairs  slots released after this window (the last use of what they hold)"""
+
+    def __init__(self, windows, slots, pair_slots):
+        self.windows, self.slots, self.pair_slots = windows, slots, pair_slots
+
+    def cache_bytes(self, h, w, element_size):
+        """device bytes of the two caches for features of h x w pixels: [slots,h,w,128] of element_size bytes and twice
+        [pair_slots,h,w,2] fp32"""
+        return self.slots * h * w * 128 * element_size + 2 * self.pair_slots * h * w * 2 * 4
+
+
+def plan_reuse(windows):
+    """The static cache plan of inpaint_video(reuse=True), from plan_windows's list: every frame of the video goes through the
+    encoder once -- in the first window that lists it, as a neighbour or as a reference, so with num_ref == -1 the first window
+    encodes every ref_length-th frame of the whole video -- and every adjacent pair that is local in some window goes through
+    SPyNet once.  A result keeps its slot until the last window that lists it and the slot is handed out again afterwards (lowest
+    free slot first), so the encoder cache peaks at the references held across the video plus the frames of two overlapping
+    windows: at most ceil(L / ref_length) + 2 * neighbor_stride + 1 slots with num_ref == -1; for other num_ref the bound is the
+    plan's own ``slots``.  Host logic only; see ReusePlan for the fields."""
+    last, last_pair = {}, {}
+    for k, (nb, rf) in enumerate(windows):
+        for j in nb + rf:
+            last[j] = k
+        for a, b in zip(nb[:-1], nb[1:]):
+            last_pair[(a, b)] = k
+
+    class _Slots:
+        def __init__(self):
+            self.of, self.free, self.count = {}, [], 0
+
+        def take(self, key):
+            if self.free:
+                self.free.sort()
+                s = self.free.pop(0)
+            else:
+                s = self.count
+                self.count += 1
+            self.of[key] = s
+            return s
+
+        def release(self, keys):
+            out = [self.of.pop(key) for key in keys]
+            self.free += out
+            return out
+
+    enc, flo = _Slots(), _Slots()
+    plan = []
+    for k, (nb, rf) in enumerate(windows):
+        ids = nb + rf
+        encode = [j for j in ids if j not in enc.of]
+        new_slots = [enc.take(j) for j in encode]
+        pairs = [pr for pr in zip(nb[:-1], nb[1:]) if pr not in flo.of]
+        new_pair_slots = [flo.take(pr) for pr in pairs]
+        clip = list(encode)
+        for pr in pairs:
+            for j in pr:
+                if j not in clip:
+                    clip.append(j)
+        plan.append(dict(neighbors=list(nb), refs=list(rf), encode=encode, clip=clip, pairs=pairs,
+                         pair_pos=[(clip.index(a), clip.index(b)) for a, b in pairs], new_slots=new_slots,
+                         enc_slots=[enc.of[j] for j in ids], new_pair_slots=new_pair_slots,
+                         flow_slots=[flo.of[pr] for pr in zip(nb[:-1], nb[1:])],
+                         free=enc.release([j for j in ids if last[j] == k]),
+                         free_pairs=flo.release([pr for pr in zip(nb[:-1], nb[1:]) if last_pair[pr] == k])))
+    return ReusePlan(plan, enc.count, flo.count)
+
+
 def padded_size(h, w, mod_h=60, mod_w=108):
     """test.py:156-159: H, W rounded up to multiples of (60,108)."""
     return h + (mod_h - h % mod_h) % mod_h, w + (mod_w - w % mod_w) % mod_w
@@ -128,7 +209,7 @@ def prepare_masks(masks_u8, size_hw, device, dilate=True):
 
 @torch.no_grad()
 def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, num_ref=-1, dilate=True,
-                  device=None, pad=True, batch_windows=1, keep_float=False, in_flight=1, size=None):
+                  device=None, pad=True, batch_windows=1, keep_float=False, in_flight=1, size=None, reuse=False):
     """frames_u8: uint8 [L,H,W,3]; masks_u8: [L,Hm,Wm] (non-zero = hole; resized to the frames with NEAREST like
     read_mask).  Returns uint8 [L,H,W,3] composited frames, computed like test.py:129-179.
     ``model(masked[b,t,3,H',W'], n_local) -> (pred[b*t,3,H',W'], _)`` on the device.
@@ -146,7 +227,25 @@ def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, 
 
     ``in_flight`` = K > 1 (round 6, with batch_windows = 1): the forwards of K consecutive windows run on K streams -- window
     i + 1's encoder fills the CUs window i's one-frame propagation chain leaves idle -- while the compositing
-    stays on the caller's stream in the reference's window order: the same kernels on the same data, the same bytes."""
+    stays on the caller's stream in the reference's window order: the same kernels on the same data, the same bytes.
+
+    ``reuse`` = True: consecutive windows share most of their frames, and the encoder, SPyNet and the decoder work on one frame
+    (or one adjacent pair) at a time -- so every frame is encoded once and every pair's flows are computed once, kept in device
+    caches by the static plan of plan_reuse, each window's features and flows are gathered from the caches on the device
+    (ops.gather_slabs), and only the window's local frames are composed and decoded (the others' predictions are dropped by
+    the loop anyway).  Propagation and the transformer see the whole window as before.  ``model`` must then be the generator
+    (an object with ``engine()``; anything else raises TypeError).  The launches on a few new frames can pick other kernels from
+    the size-class table than those on a whole window, and different kernels round differently: the result is the reference
+    loop's within the driver's usual tolerance, not the bytes of reuse=False.  One window at a time: reuse=True with
+    batch_windows > 1 or in_flight > 1 raises ValueError (the caches are filled and read in window order on one stream)."""
+    if reuse:
+        if batch_windows > 1:
+            raise ValueError("reuse=True runs one window per forward: batch_windows must be 1, got %d" % batch_windows)
+        if in_flight > 1:
+            raise ValueError("reuse=True runs one window at a time: in_flight must be 1, got %d" % in_flight)
+        if not callable(getattr(model, "engine", None)):
+            raise TypeError("reuse=True needs the InpaintGenerator (its engine runs the encoder, SPyNet and the rest of the "
+                            "forward as separate pieces), got %s" % type(model).__name__)
     if device is None:
         device = next(model.parameters()).device if hasattr(model, "parameters") else torch.device("cuda")
     device = torch.device(device)
@@ -182,7 +281,49 @@ def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, 
         n = len(windows[i][0])
         ops.composite(pred.contiguous(), ids_dev[i][:n], first_dev[i], frames_d, masks01, comp)
 
-    if batch_windows <= 1 and in_flight > 1:
+    if reuse:
+        eng = model.engine()
+        h4, w4 = Hp // 4, Wp // 4
+        plan = plan_reuse(windows)
+        i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=device) if len(v) else None
+        # the plan's tables are uploads too: all of them before the first forward
+        tabs = [dict(clip=i32(p["clip"]), new_slots=i32(p["new_slots"]), enc_slots=i32(p["enc_slots"]),
+                     pairs=eng.pair_table(p["pair_pos"]) if p["pairs"] else None, new_pair_slots=i32(p["new_pair_slots"]),
+                     flow_slots=i32(p["flow_slots"])) for p in plan.windows]
+        enc_cache = torch.empty((plan.slots, h4, w4, 128), dtype=eng.dtype, device=device)
+        fwd_cache = torch.empty((max(plan.pair_slots, 1), h4, w4, 2), dtype=torch.float32, device=device)
+        bwd_cache = torch.empty_like(fwd_cache)
+        for i, (p, tb) in enumerate(zip(plan.windows, tabs)):
+            n = len(p["neighbors"])
+            if p["clip"]:
+                x = ops.masked_clip(frames_d, masks01, tb["clip"], Hp, Wp)[0]
+                flows = None
+                main = torch.cuda.current_stream(device)
+                fork = bool(p["pairs"]) and bool(p["encode"]) and eng._fork_ok()
+                if fork:                                # the new pairs' SPyNet beside the new frames' encoder, as in Engine.forward
+                    side = eng._side_stream()
+                    side.wait_stream(main)
+                    with torch.cuda.stream(side):
+                        flows = eng.pair_flows(x, tb["pairs"])
+                if p["encode"]:
+                    ops.scatter_slabs(eng.encode_frames(x[:len(p["encode"])]), tb["new_slots"], enc_cache)
+                if fork:
+                    main.wait_stream(side)
+                elif p["pairs"]:
+                    flows = eng.pair_flows(x, tb["pairs"])
+                if flows is not None:
+                    ops.scatter_slabs(flows[0], tb["new_pair_slots"], fwd_cache)
+                    ops.scatter_slabs(flows[1], tb["new_pair_slots"], bwd_cache)
+            # the window's tensors are copies: propagation overwrites the local frames' features in place
+            feats = ops.gather_slabs(enc_cache, tb["enc_slots"])
+            if n > 1:
+                fl = (ops.gather_slabs(fwd_cache, tb["flow_slots"]).view(1, n - 1, h4, w4, 2),
+                      ops.gather_slabs(bwd_cache, tb["flow_slots"]).view(1, n - 1, h4, w4, 2))
+            else:
+                fl = (torch.empty((1, 0, h4, w4, 2), dtype=torch.float32, device=device),) * 2
+            pred, _ = eng.forward(None, n, given=(fl, feats), decode_local=True)
+            composite(i, pred)
+    elif batch_windows <= 1 and in_flight > 1:
         cur = torch.cuda.current_stream(device)
         streams = [torch.cuda.Stream(device=device) for _ in range(in_flight)]
         for st in streams:

@@ -60,6 +60,17 @@ int e2fgvi_float_to_u8(const float* src, uint8_t* dst, int64_t n, void* stream);
 /* model output [N,3,Hp,Wp] in (-1,1) -> uint8 NHWC [N,H,W,3] = uint8((pred+1)/2*255): the form the clip-sharded runner
  * gathers over xGMI (4x fewer bytes than fp32). */
 int e2fgvi_pred_to_u8(const float* pred, uint8_t* dst, int32_t N, int32_t H, int32_t W, int32_t Hp, int32_t Wp, void* stream);
+/* test.py:152 (selected_imgs = imgs[:1, neighbor_ids + ref_ids]) for a driver that keeps per-frame results instead of
+ * recomputing them in every window (video.inpaint_video(reuse=True)): window[i] = cache[ids[i]], i < n, for slabs of
+ * slab_bytes bytes each -- cache [slots][slab], window [n][slab], any element type: encoder features [h,w,128] in fp32 /
+ * bf16 / fp16 and flows [h,w,2] alike.  slab_bytes a multiple of 4; 16-byte loads and stores whenever slab_bytes and both
+ * bases are multiples of 16 (8-byte ones at multiples of 8).  ids are device int32 and nothing is read on the host; an id
+ * outside [0, slots) zero-fills its window slab (gather) or is skipped (scatter).  n <= 65535. */
+int e2fgvi_gather_slabs(const void* cache, int32_t slots, const int32_t* ids, int32_t n, int64_t slab_bytes, void* window,
+                        void* stream);
+/* the mirror: cache[ids[i]] = rows[i] -- newly encoded frames / newly computed flows into their cache slots (ids distinct) */
+int e2fgvi_scatter_slabs(const void* rows, const int32_t* ids, int32_t n, int64_t slab_bytes, void* cache, int32_t slots,
+                         void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * evaluate.py metrics (core/metrics.py:20-56): per image pair of fp32 NHWC [N,H,W,3] frames in
