@@ -572,7 +572,7 @@ __global__ __launch_bounds__(64 * NW, (QB == 1 ? 3 : 2)) void focal_attn_bf16_v2
 
 static int g_att_variant = 0;        // 0: automatic; set through the ABI (tools / tests), never from the environment (round 6)
 
-extern "C" int e2fgvi_focal_attention_bf16_variant(int variant) {
+extern "C" int e2fgvi_focal_attention_16_variant(int variant) {
     const int prev = g_att_variant;
     g_att_variant = variant;
     return prev;
@@ -598,7 +598,7 @@ static int focal_attention_16(const void* qkv, const void* kv_pool, const int32_
     const long long hi_end = (cq + qb > cp + pb ? cq + qb : cp + pb) - lo;
     E2_REQUIRE(hi_end < 0xFFFFF000LL, E2FGVI_EUNSUP,
                "%s: qkv and kv_pool must lie within one 4 GiB window (allocate them back to back / split the batch)", nm);
-    // Variant (e2fgvi_focal_attention_bf16_variant): 10 * QB + NW selects the round-3 kernel with NW waves of QB x 32 queries per
+    // Variant (e2fgvi_focal_attention_16_variant): 10 * QB + NW selects the round-3 kernel with NW waves of QB x 32 queries per
     // workgroup (12, 14, 18, 22, 24); 1 = round 2's kernel; 0 = automatic.
     constexpr int xcd_env = 0;
     int variant = g_att_variant;
@@ -657,14 +657,11 @@ static int focal_attention_16(const void* qkv, const void* kv_pool, const int32_
     return 0;
 }
 
-extern "C" int e2fgvi_focal_attention_bf16(const void* qkv, const void* kv_pool, const int32_t* key_tab, int32_t tab_ld,
-                                           const int32_t* nkeys, void* out, int32_t B, int32_t T, int32_t fh, int32_t fw,
-                                           void* stream) {
-    return focal_attention_16<false>(qkv, kv_pool, key_tab, tab_ld, nkeys, out, B, T, fh, fw, stream);
-}
-/* fp16 qkv / kv_pool / out: the same kernels on fp16 MFMA (P rounded to fp16 for the PV product) */
-extern "C" int e2fgvi_focal_attention_f16(const void* qkv, const void* kv_pool, const int32_t* key_tab, int32_t tab_ld,
-                                          const int32_t* nkeys, void* out, int32_t B, int32_t T, int32_t fh, int32_t fw,
-                                          void* stream) {
-    return focal_attention_16<true>(qkv, kv_pool, key_tab, tab_ld, nkeys, out, B, T, fh, fw, stream);
+/* qkv / kv_pool / out of dtype E2FGVI_BF16 or E2FGVI_F16: the same kernels on bf16 / fp16 MFMA (fp16: P rounded to fp16 for the PV product) */
+extern "C" int e2fgvi_focal_attention_16(const void* qkv, const void* kv_pool, const int32_t* key_tab, int32_t tab_ld,
+                                         const int32_t* nkeys, void* out, int32_t dtype, int32_t B, int32_t T, int32_t fh, int32_t fw,
+                                         void* stream) {
+    E2_REQUIRE(dtype == E2FGVI_BF16 || dtype == E2FGVI_F16, E2FGVI_EINVAL, "focal_attention_16: dtype must be E2FGVI_BF16 or E2FGVI_F16");
+    return dtype == E2FGVI_F16 ? focal_attention_16<true>(qkv, kv_pool, key_tab, tab_ld, nkeys, out, B, T, fh, fw, stream)
+                               : focal_attention_16<false>(qkv, kv_pool, key_tab, tab_ld, nkeys, out, B, T, fh, fw, stream);
 }

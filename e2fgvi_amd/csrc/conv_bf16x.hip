@@ -922,7 +922,7 @@ int launch_x(ConvXParams& p, int groups, hipStream_t st, int mode = 0) {
         return 0;
     } else {
     if (S3 && !(p.KH == 3 && p.KW == 3 && p.stride == 1 && p.pad == 1)) {
-        e2fgvi_set_error("conv2d_bf16x: the row-shift tiles (11..17) are for 3x3 stride-1 pad-1 layers");
+        e2fgvi_set_error("conv2d_x: the row-shift tiles (11..17) are for 3x3 stride-1 pad-1 layers");
         return E2FGVI_EINVAL;
     }
     if (mode == 1 || mode == 2) {
@@ -932,7 +932,7 @@ int launch_x(ConvXParams& p, int groups, hipStream_t st, int mode = 0) {
             else
                 hipLaunchKernelGGL((conv_bf16x_kernel<BM, BN, WGM, WGN, false, 1>), dim3(p.tilesM * p.tilesN, groups, 1), dim3(64 * WGM * WGN), 0, st, p);
         } else {
-            e2fgvi_set_error("conv2d_f32x: the row-shift tiles (11..18) take bf16 operands only");
+            e2fgvi_set_error("conv2d_x: the row-shift tiles (11..18) take bf16 operands only");
             return E2FGVI_EUNSUP;
         }
     } else if (mode == 3) {
@@ -947,86 +947,6 @@ int launch_x(ConvXParams& p, int groups, hipStream_t st, int mode = 0) {
 
 }  // namespace
 
-extern "C" int64_t e2fgvi_packed_conv_weight_bf16x_size(int32_t Cout, int32_t groups, int32_t KH, int32_t KW, int32_t nsrc,
-                                                        const int32_t* src_cpg) {
-    PackX q;
-    if (!src_cpg || !geometry_x(Cout, groups, KH, KW, nsrc, src_cpg, &q)) {
-        e2fgvi_set_error("packed_conv_weight_bf16x_size: bad geometry (channels per source must be multiples of 8)");
-        return E2FGVI_EINVAL;
-    }
-    return q.total;
-}
-
-extern "C" int e2fgvi_pack_conv_weight_bf16x(const float* w, void* wpacked, int32_t Cout, int32_t groups, int32_t KH,
-                                             int32_t KW, int32_t nsrc, const int32_t* src_cpg, void* stream) {
-    PackX q;
-    E2_REQUIRE(w && wpacked && src_cpg, E2FGVI_EINVAL, "pack_conv_weight_bf16x: null pointer");
-    E2_REQUIRE(geometry_x(Cout, groups, KH, KW, nsrc, src_cpg, &q), E2FGVI_EINVAL, "pack_conv_weight_bf16x: bad geometry");
-    hipLaunchKernelGGL(pack_conv_weight_x_kernel<__bf16>, dim3((unsigned)cdiv64(q.total, 256)), dim3(256), 0, (hipStream_t)stream,
-                       w, (__bf16*)wpacked, q);
-    E2_LAUNCH_CHECK("pack_conv_weight_bf16x");
-    return 0;
-}
-
-/* fp16: the bf16 layout and element count, fp16 elements */
-extern "C" int64_t e2fgvi_packed_conv_weight_f16x_size(int32_t Cout, int32_t groups, int32_t KH, int32_t KW, int32_t nsrc,
-                                                       const int32_t* src_cpg) {
-    return e2fgvi_packed_conv_weight_bf16x_size(Cout, groups, KH, KW, nsrc, src_cpg);
-}
-extern "C" int e2fgvi_pack_conv_weight_f16x(const float* w, void* wpacked, int32_t Cout, int32_t groups, int32_t KH,
-                                            int32_t KW, int32_t nsrc, const int32_t* src_cpg, void* stream) {
-    PackX q;
-    E2_REQUIRE(w && wpacked && src_cpg, E2FGVI_EINVAL, "pack_conv_weight_f16x: null pointer");
-    E2_REQUIRE(geometry_x(Cout, groups, KH, KW, nsrc, src_cpg, &q), E2FGVI_EINVAL, "pack_conv_weight_f16x: bad geometry");
-    hipLaunchKernelGGL(pack_conv_weight_x_kernel<_Float16>, dim3((unsigned)cdiv64(q.total, 256)), dim3(256), 0, (hipStream_t)stream,
-                       w, (_Float16*)wpacked, q);
-    E2_LAUNCH_CHECK("pack_conv_weight_f16x");
-    return 0;
-}
-
-extern "C" int64_t e2fgvi_packed_conv_weight_f32x_size(int32_t Cout, int32_t groups, int32_t KH, int32_t KW, int32_t nsrc,
-                                                       const int32_t* src_cpg) {
-    PackX q;
-    if (!src_cpg || !geometry_x(Cout, groups, KH, KW, nsrc, src_cpg, &q, true)) {
-        e2fgvi_set_error("packed_conv_weight_f32x_size: bad geometry (channels per source must be multiples of 4)");
-        return E2FGVI_EINVAL;
-    }
-    return q.total;
-}
-
-extern "C" int e2fgvi_pack_conv_weight_f32x(const float* w, float* wpacked, int32_t Cout, int32_t groups, int32_t KH,
-                                            int32_t KW, int32_t nsrc, const int32_t* src_cpg, void* stream) {
-    PackX q;
-    E2_REQUIRE(w && wpacked && src_cpg, E2FGVI_EINVAL, "pack_conv_weight_f32x: null pointer");
-    E2_REQUIRE(geometry_x(Cout, groups, KH, KW, nsrc, src_cpg, &q, true), E2FGVI_EINVAL, "pack_conv_weight_f32x: bad geometry");
-    hipLaunchKernelGGL(pack_conv_weight_x_kernel<float>, dim3((unsigned)cdiv64(q.total, 256)), dim3(256), 0, (hipStream_t)stream,
-                       w, wpacked, q);
-    E2_LAUNCH_CHECK("pack_conv_weight_f32x");
-    return 0;
-}
-
-/* X3 (fp32 on the bf16 matrix pipe): the fp32 geometry, three bf16 planes per weight -> 3 x the element count, in bf16 */
-extern "C" int64_t e2fgvi_packed_conv_weight_f32x3_size(int32_t Cout, int32_t groups, int32_t KH, int32_t KW, int32_t nsrc,
-                                                        const int32_t* src_cpg) {
-    PackX q;
-    if (!src_cpg || !geometry_x(Cout, groups, KH, KW, nsrc, src_cpg, &q, true)) {
-        e2fgvi_set_error("packed_conv_weight_f32x3_size: bad geometry (channels per source must be multiples of 4)");
-        return E2FGVI_EINVAL;
-    }
-    return 3 * q.total;
-}
-
-extern "C" int e2fgvi_pack_conv_weight_f32x3(const float* w, void* wpacked, int32_t Cout, int32_t groups, int32_t KH,
-                                             int32_t KW, int32_t nsrc, const int32_t* src_cpg, void* stream) {
-    PackX q;
-    E2_REQUIRE(w && wpacked && src_cpg, E2FGVI_EINVAL, "pack_conv_weight_f32x3: null pointer");
-    E2_REQUIRE(geometry_x(Cout, groups, KH, KW, nsrc, src_cpg, &q, true), E2FGVI_EINVAL, "pack_conv_weight_f32x3: bad geometry");
-    hipLaunchKernelGGL(pack_conv_weight_x3_kernel, dim3((unsigned)cdiv64(q.total, 256)), dim3(256), 0, (hipStream_t)stream,
-                       w, (unsigned short*)wpacked, q);
-    E2_LAUNCH_CHECK("pack_conv_weight_f32x3");
-    return 0;
-}
-
 // tap-packed variant of the packing: one source of fewer channels than two K-steps (a multiple of the chunk), no groups, KW >= 2
 static bool geometry_taps(int Cout, int KH, int KW, int cin, PackX* q, bool f32 = false) {
     const int32_t cpg[1] = {cin};
@@ -1038,151 +958,139 @@ static bool geometry_taps(int Cout, int KH, int KW, int cin, PackX* q, bool f32 
     return true;
 }
 
-extern "C" int64_t e2fgvi_packed_conv_weight_bf16x_taps_size(int32_t Cout, int32_t KH, int32_t KW, int32_t cin) {
-    PackX q;
-    if (!geometry_taps(Cout, KH, KW, cin, &q)) {
-        e2fgvi_set_error("packed_conv_weight_bf16x_taps_size: one source of 8 ... 56 channels (multiple of 8), KW >= 2");
-        return E2FGVI_EINVAL;
+// The public element code of an entry point -> the MODE numbering of conv_bf16x_kernel / launch_x (0 = bf16, 1 = fp32, 2 = fp32
+// as three bf16 planes, 3 = fp16); -1 with the message set for anything else.
+static int mode_x(const char* who, int32_t code) {
+    switch (code) {
+        case E2FGVI_BF16: return 0;
+        case E2FGVI_F32: return 1;
+        case E2FGVI_BF16X3: return 2;
+        case E2FGVI_F16: return 3;
+        default: break;
     }
-    return q.total;
+    e2fgvi_set_error("%s: mode %d is none of E2FGVI_F32 (0), E2FGVI_BF16 (1), E2FGVI_BF16X3 (2), E2FGVI_F16 (3)", who, code);
+    return -1;
 }
 
-extern "C" int e2fgvi_pack_conv_weight_bf16x_taps(const float* w, void* wpacked, int32_t Cout, int32_t KH, int32_t KW, int32_t cin,
-                                                  void* stream) {
-    PackX q;
-    E2_REQUIRE(w && wpacked, E2FGVI_EINVAL, "pack_conv_weight_bf16x_taps: null pointer");
-    E2_REQUIRE(geometry_taps(Cout, KH, KW, cin, &q), E2FGVI_EINVAL, "pack_conv_weight_bf16x_taps: bad geometry");
-    hipLaunchKernelGGL(pack_conv_weight_x_kernel<__bf16>, dim3((unsigned)cdiv64(q.total, 256)), dim3(256), 0, (hipStream_t)stream,
-                       w, (__bf16*)wpacked, q);
-    E2_LAUNCH_CHECK("pack_conv_weight_bf16x_taps");
-    return 0;
-}
-
-extern "C" int64_t e2fgvi_packed_conv_weight_f16x_taps_size(int32_t Cout, int32_t KH, int32_t KW, int32_t cin) {
-    return e2fgvi_packed_conv_weight_bf16x_taps_size(Cout, KH, KW, cin);
-}
-extern "C" int e2fgvi_pack_conv_weight_f16x_taps(const float* w, void* wpacked, int32_t Cout, int32_t KH, int32_t KW, int32_t cin,
-                                                 void* stream) {
-    PackX q;
-    E2_REQUIRE(w && wpacked, E2FGVI_EINVAL, "pack_conv_weight_f16x_taps: null pointer");
-    E2_REQUIRE(geometry_taps(Cout, KH, KW, cin, &q), E2FGVI_EINVAL, "pack_conv_weight_f16x_taps: bad geometry");
-    hipLaunchKernelGGL(pack_conv_weight_x_kernel<_Float16>, dim3((unsigned)cdiv64(q.total, 256)), dim3(256), 0, (hipStream_t)stream,
-                       w, (_Float16*)wpacked, q);
-    E2_LAUNCH_CHECK("pack_conv_weight_f16x_taps");
-    return 0;
-}
-
-extern "C" int64_t e2fgvi_packed_conv_weight_f32x_taps_size(int32_t Cout, int32_t KH, int32_t KW, int32_t cin) {
-    PackX q;
-    if (!geometry_taps(Cout, KH, KW, cin, &q, true)) {
-        e2fgvi_set_error("packed_conv_weight_f32x_taps_size: one source of 4 ... 56 channels (multiple of 4), KW >= 2");
-        return E2FGVI_EINVAL;
+// geometry of a packing (internal mode), plain or tap-packed; false with the message set
+static bool pack_geometry(const char* who, int mode, int tap_packed, int Cout, int groups, int KH, int KW, int nsrc,
+                          const int32_t* src_cpg, PackX* q) {
+    const bool f32 = mode == 1 || mode == 2;
+    const int ch = f32 ? 4 : 8;
+    if (!src_cpg) {
+        e2fgvi_set_error("%s: null src_cpg", who);
+        return false;
     }
-    return q.total;
-}
-
-extern "C" int e2fgvi_pack_conv_weight_f32x_taps(const float* w, float* wpacked, int32_t Cout, int32_t KH, int32_t KW, int32_t cin,
-                                                 void* stream) {
-    PackX q;
-    E2_REQUIRE(w && wpacked, E2FGVI_EINVAL, "pack_conv_weight_f32x_taps: null pointer");
-    E2_REQUIRE(geometry_taps(Cout, KH, KW, cin, &q, true), E2FGVI_EINVAL, "pack_conv_weight_f32x_taps: bad geometry");
-    hipLaunchKernelGGL(pack_conv_weight_x_kernel<float>, dim3((unsigned)cdiv64(q.total, 256)), dim3(256), 0, (hipStream_t)stream,
-                       w, wpacked, q);
-    E2_LAUNCH_CHECK("pack_conv_weight_f32x_taps");
-    return 0;
-}
-
-extern "C" int64_t e2fgvi_packed_conv_weight_f32x3_taps_size(int32_t Cout, int32_t KH, int32_t KW, int32_t cin) {
-    PackX q;
-    if (!geometry_taps(Cout, KH, KW, cin, &q, true)) {
-        e2fgvi_set_error("packed_conv_weight_f32x3_taps_size: one source of 4 ... 56 channels (multiple of 4), KW >= 2");
-        return E2FGVI_EINVAL;
+    if (tap_packed) {
+        if (groups == 1 && nsrc == 1 && geometry_taps(Cout, KH, KW, src_cpg[0], q, f32)) return true;
+        e2fgvi_set_error("%s: tap-packed weights: one source of %d ... 56 channels (multiple of %d), no groups, KW >= 2", who, ch, ch);
+        return false;
     }
-    return 3 * q.total;
+    if (geometry_x(Cout, groups, KH, KW, nsrc, src_cpg, q, f32)) return true;
+    e2fgvi_set_error("%s: bad geometry (channels per source must be multiples of %d)", who, ch);
+    return false;
 }
 
-extern "C" int e2fgvi_pack_conv_weight_f32x3_taps(const float* w, void* wpacked, int32_t Cout, int32_t KH, int32_t KW, int32_t cin,
-                                                  void* stream) {
+/* elements of the packed weight buffer: 16-bit ones for E2FGVI_BF16 / E2FGVI_F16 (one layout, one count), fp32 ones for E2FGVI_F32,
+ * and for E2FGVI_BF16X3 three bf16 planes per weight of the fp32 geometry -> 3 x the fp32 count */
+extern "C" int64_t e2fgvi_packed_conv_weight_x_size(int32_t mode, int32_t tap_packed, int32_t Cout, int32_t groups, int32_t KH,
+                                                    int32_t KW, int32_t nsrc, const int32_t* src_cpg) {
     PackX q;
-    E2_REQUIRE(w && wpacked, E2FGVI_EINVAL, "pack_conv_weight_f32x3_taps: null pointer");
-    E2_REQUIRE(geometry_taps(Cout, KH, KW, cin, &q, true), E2FGVI_EINVAL, "pack_conv_weight_f32x3_taps: bad geometry");
-    hipLaunchKernelGGL(pack_conv_weight_x3_kernel, dim3((unsigned)cdiv64(q.total, 256)), dim3(256), 0, (hipStream_t)stream,
-                       w, (unsigned short*)wpacked, q);
-    E2_LAUNCH_CHECK("pack_conv_weight_f32x3_taps");
+    const int m = mode_x("packed_conv_weight_x_size", mode);
+    if (m < 0 || !pack_geometry("packed_conv_weight_x_size", m, tap_packed, Cout, groups, KH, KW, nsrc, src_cpg, &q)) return E2FGVI_EINVAL;
+    return m == 2 ? 3 * q.total : q.total;
+}
+
+/* w: fp32 [Cout, sum(cpg), KH, KW] (torch OIHW) */
+extern "C" int e2fgvi_pack_conv_weight_x(const float* w, void* wpacked, int32_t mode, int32_t tap_packed, int32_t Cout, int32_t groups,
+                                         int32_t KH, int32_t KW, int32_t nsrc, const int32_t* src_cpg, void* stream) {
+    PackX q;
+    E2_REQUIRE(w && wpacked, E2FGVI_EINVAL, "pack_conv_weight_x: null pointer");
+    const int m = mode_x("pack_conv_weight_x", mode);
+    if (m < 0 || !pack_geometry("pack_conv_weight_x", m, tap_packed, Cout, groups, KH, KW, nsrc, src_cpg, &q)) return E2FGVI_EINVAL;
+    const dim3 grid((unsigned)cdiv64(q.total, 256)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    switch (m) {
+        case 0: hipLaunchKernelGGL(pack_conv_weight_x_kernel<__bf16>, grid, block, 0, st, w, (__bf16*)wpacked, q); break;
+        case 1: hipLaunchKernelGGL(pack_conv_weight_x_kernel<float>, grid, block, 0, st, w, (float*)wpacked, q); break;
+        case 2: hipLaunchKernelGGL(pack_conv_weight_x3_kernel, grid, block, 0, st, w, (unsigned short*)wpacked, q); break;
+        default: hipLaunchKernelGGL(pack_conv_weight_x_kernel<_Float16>, grid, block, 0, st, w, (_Float16*)wpacked, q); break;
+    }
+    E2_LAUNCH_CHECK("pack_conv_weight_x");
     return 0;
 }
 
 static int conv2d_x(const e2fgvi_convx_desc* d, void* stream, int mode) {
     const bool f32 = mode == 1 || mode == 2;   // fp32 activations (MODE 1: fp32 weights too; MODE 2: three bf16 planes per weight)
     const int dt16 = mode == 3 ? E2FGVI_F16 : E2FGVI_BF16;   // the 16-bit storage type of dst / residual (MODE 3: fp16)
-    E2_REQUIRE(d, E2FGVI_EINVAL, "conv2d_bf16x: null descriptor");
+    E2_REQUIRE(d, E2FGVI_EINVAL, "conv2d_x: null descriptor");
     PackX q;
     const int esz = f32 ? 4 : 2;
     const int wbytes_num = mode == 2 ? 6 : esz;       // packed bytes per weight
     E2_REQUIRE(geometry_x(d->Cout, d->groups, d->KH, d->KW, d->nsrc, d->src_cpg, &q, f32), E2FGVI_EINVAL,
-               "conv2d_bf16x: bad geometry (channels per source must be multiples of 8 bf16 / 4 fp32)");
+               "conv2d_x: bad geometry (channels per source must be multiples of 8 bf16 / 4 fp32)");
     E2_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Ho > 0 && d->Wo > 0 && d->stride > 0 && d->pad >= 0, E2FGVI_EINVAL,
-               "conv2d_bf16x: bad sizes");
+               "conv2d_x: bad sizes");
     if (d->out_grid) {
         // explicit output grid: `pad` rows above / `pad_left` columns left of the image, whatever the kernel reaches below /
         // right of it reads as zeros; Ho x Wo as given (the phase convolutions of SoftComp: 2-tap kernels with the zero row
         // on one side only); optionally scattered into a larger image
         E2_REQUIRE(d->pad_left >= 0 && d->act != E2FGVI_ACT_DCNPOST && !d->dst_nchw && !d->tap_packed && (d->tile < 10 || d->tile > 20),
-                   E2FGVI_EINVAL, "conv2d_bf16x: explicit output grids take plain NHWC tiles only");
+                   E2FGVI_EINVAL, "conv2d_x: explicit output grids take plain NHWC tiles only");
         if (d->out_sy || d->out_sx)
             E2_REQUIRE(d->out_sy > 0 && d->out_sx > 0 && d->out_py >= 0 && d->out_px >= 0 && d->out_H > 0 && d->out_W > 0 &&
                        (d->Ho - 1) * d->out_sy + d->out_py < d->out_H && (d->Wo - 1) * d->out_sx + d->out_px < d->out_W &&
                        (long long)d->N * d->out_H * d->out_W < 2147483647LL,
-                       E2FGVI_EINVAL, "conv2d_bf16x: the output scatter leaves the [N, out_H, out_W] image");
+                       E2FGVI_EINVAL, "conv2d_x: the output scatter leaves the [N, out_H, out_W] image");
     } else {
         E2_REQUIRE(d->Ho == (d->H + 2 * d->pad - d->KH) / d->stride + 1 && d->Wo == (d->W + 2 * d->pad - d->KW) / d->stride + 1,
-                   E2FGVI_EINVAL, "conv2d_bf16x: Ho/Wo inconsistent with H/W/k/stride/pad");
-        E2_REQUIRE(!d->out_sy && !d->out_sx && !d->pad_left, E2FGVI_EINVAL, "conv2d_bf16x: pad_left / out_s* need out_grid = 1");
+                   E2FGVI_EINVAL, "conv2d_x: Ho/Wo inconsistent with H/W/k/stride/pad");
+        E2_REQUIRE(!d->out_sy && !d->out_sx && !d->pad_left, E2FGVI_EINVAL, "conv2d_x: pad_left / out_s* need out_grid = 1");
     }
-    E2_REQUIRE(!d->res_bcast || (d->residual && d->act != E2FGVI_ACT_DCNPOST), E2FGVI_EINVAL, "conv2d_bf16x: res_bcast without a residual");
-    E2_REQUIRE((long long)d->N * d->Ho * d->Wo < 2147483647LL, E2FGVI_EUNSUP, "conv2d_bf16x: more than 2^31 output pixels");
-    E2_REQUIRE(d->KH <= 8 && d->KW <= 8, E2FGVI_EUNSUP, "conv2d_bf16x: kernels larger than 8x8 are not supported");
-    E2_REQUIRE(d->wpacked && d->dst, E2FGVI_EINVAL, "conv2d_bf16x: null weight/dst");
+    E2_REQUIRE(!d->res_bcast || (d->residual && d->act != E2FGVI_ACT_DCNPOST), E2FGVI_EINVAL, "conv2d_x: res_bcast without a residual");
+    E2_REQUIRE((long long)d->N * d->Ho * d->Wo < 2147483647LL, E2FGVI_EUNSUP, "conv2d_x: more than 2^31 output pixels");
+    E2_REQUIRE(d->KH <= 8 && d->KW <= 8, E2FGVI_EUNSUP, "conv2d_x: kernels larger than 8x8 are not supported");
+    E2_REQUIRE(d->wpacked && d->dst, E2FGVI_EINVAL, "conv2d_x: null weight/dst");
     E2_REQUIRE((d->dst_dtype == E2FGVI_F32 || d->dst_dtype == dt16) && (d->res_dtype == E2FGVI_F32 || d->res_dtype == dt16),
-               E2FGVI_EINVAL, mode == 3 ? "conv2d_f16x: dtype must be E2FGVI_F32 or E2FGVI_F16"
-                                        : "conv2d_bf16x: dtype must be E2FGVI_F32 or E2FGVI_BF16");
+               E2FGVI_EINVAL, mode == 3 ? "conv2d_x: dtype must be E2FGVI_F32 or E2FGVI_F16"
+                                        : "conv2d_x: dtype must be E2FGVI_F32 or E2FGVI_BF16");
     ConvXParams p;
     for (int s = 0; s < E2FGVI_MAX_SRC; ++s) { p.src[s] = nullptr; p.ld[s] = 0; p.coff[s] = 0; p.cpg[s] = 0; p.src_bytes[s] = 0; }
     for (int s = 0; s < d->nsrc; ++s) {
-        E2_REQUIRE(d->src[s], E2FGVI_EINVAL, "conv2d_bf16x: null source %d", s);
+        E2_REQUIRE(d->src[s], E2FGVI_EINVAL, "conv2d_x: null source %d", s);
         E2_REQUIRE(d->src_ld[s] % q.ch == 0 && d->src_coff[s] % q.ch == 0 && ((uintptr_t)d->src[s] & 15) == 0, E2FGVI_EINVAL,
-                   "conv2d_bf16x: source %d not 16-byte addressable (ld / coff multiples of 8 bf16 / 4 fp32)", s);
+                   "conv2d_x: source %d not 16-byte addressable (ld / coff multiples of 8 bf16 / 4 fp32)", s);
         E2_REQUIRE(d->src_coff[s] + d->groups * d->src_cpg[s] <= d->src_ld[s], E2FGVI_EINVAL,
-                   "conv2d_bf16x: source %d channel range exceeds its pixel stride", s);
+                   "conv2d_x: source %d channel range exceeds its pixel stride", s);
         const long long bytes = (long long)d->N * d->H * d->W * d->src_ld[s] * esz;
-        E2_REQUIRE(bytes < 4294967295LL, E2FGVI_EUNSUP, "conv2d_bf16x: source %d spans >= 4 GiB (split the batch)", s);
+        E2_REQUIRE(bytes < 4294967295LL, E2FGVI_EUNSUP, "conv2d_x: source %d spans >= 4 GiB (split the batch)", s);
         p.src[s] = d->src[s]; p.ld[s] = d->src_ld[s]; p.coff[s] = d->src_coff[s]; p.cpg[s] = d->src_cpg[s];
         p.src_bytes[s] = (unsigned)bytes;
     }
-    E2_REQUIRE(q.wgroup_elems * wbytes_num < 4294967295LL, E2FGVI_EUNSUP, "conv2d_bf16x: packed weight group >= 4 GiB");
-    E2_REQUIRE(((uintptr_t)d->wpacked & 15) == 0, E2FGVI_EINVAL, "conv2d_bf16x: packed weight not 16-byte aligned");
+    E2_REQUIRE(q.wgroup_elems * wbytes_num < 4294967295LL, E2FGVI_EUNSUP, "conv2d_x: packed weight group >= 4 GiB");
+    E2_REQUIRE(((uintptr_t)d->wpacked & 15) == 0, E2FGVI_EINVAL, "conv2d_x: packed weight not 16-byte aligned");
     if (d->dst_nchw)
-        E2_REQUIRE(d->dst_dtype == E2FGVI_F32 && !d->dst2, E2FGVI_EINVAL, "conv2d_bf16x: the NCHW destination is fp32, without a second copy");
+        E2_REQUIRE(d->dst_dtype == E2FGVI_F32 && !d->dst2, E2FGVI_EINVAL, "conv2d_x: the NCHW destination is fp32, without a second copy");
     else
-        E2_REQUIRE(d->dst_coff >= 0 && d->dst_coff + d->Cout <= d->dst_ld, E2FGVI_EINVAL, "conv2d_bf16x: dst slice exceeds dst_ld");
+        E2_REQUIRE(d->dst_coff >= 0 && d->dst_coff + d->Cout <= d->dst_ld, E2FGVI_EINVAL, "conv2d_x: dst slice exceeds dst_ld");
     E2_REQUIRE(((uintptr_t)d->dst & 15) == 0 && (!d->dst2 || ((uintptr_t)d->dst2 & 15) == 0) &&
-               (!d->residual || ((uintptr_t)d->residual & 15) == 0), E2FGVI_EINVAL, "conv2d_bf16x: dst / dst2 / residual not 16-byte aligned");
-    E2_REQUIRE(mode != 3 || !d->dst2_plane_stride, E2FGVI_EINVAL, "conv2d_f16x: no split planes (dst2 is an fp16 copy)");
+               (!d->residual || ((uintptr_t)d->residual & 15) == 0), E2FGVI_EINVAL, "conv2d_x: dst / dst2 / residual not 16-byte aligned");
+    E2_REQUIRE(mode != 3 || !d->dst2_plane_stride, E2FGVI_EINVAL, "conv2d_x: no split planes (dst2 is an fp16 copy)");
     if (d->dst2_plane_stride) {
         // ABI 8: channels from dst2_split_from on as three exact bf16 planes (16-byte stores of 8 channels)
         E2_REQUIRE(d->dst2 && d->dst2_plane_stride > 0 && d->dst_dtype == E2FGVI_F32 && !d->dst_nchw && d->groups == 1 &&
                        !(d->out_grid && d->out_sy), E2FGVI_EINVAL,
-                   "conv2d_bf16x: split planes need dst2, an fp32 NHWC dst, groups = 1 and no output scatter");
+                   "conv2d_x: split planes need dst2, an fp32 NHWC dst, groups = 1 and no output scatter");
         E2_REQUIRE(d->Cout % 8 == 0 && d->dst2_split_from >= 0 && d->dst2_split_from <= d->Cout && d->dst2_split_from % 8 == 0 &&
                        d->dst2_ld % 8 == 0 && d->dst2_coff % 8 == 0 && d->dst2_plane_stride % 8 == 0 && d->dst2_coff >= 0 &&
                        d->dst2_coff + d->Cout - d->dst2_split_from <= d->dst2_ld, E2FGVI_EINVAL,
-                   "conv2d_bf16x: split planes: Cout, dst2_split_from, dst2_ld, dst2_coff and dst2_plane_stride in multiples of 8, "
+                   "conv2d_x: split planes: Cout, dst2_split_from, dst2_ld, dst2_coff and dst2_plane_stride in multiples of 8, "
                    "the split channels inside dst2_ld");
     } else if (d->dst2)
-        E2_REQUIRE(d->dst2_coff >= 0 && d->dst2_coff + d->Cout <= d->dst2_ld, E2FGVI_EINVAL, "conv2d_bf16x: dst2 slice exceeds dst2_ld");
+        E2_REQUIRE(d->dst2_coff >= 0 && d->dst2_coff + d->Cout <= d->dst2_ld, E2FGVI_EINVAL, "conv2d_x: dst2 slice exceeds dst2_ld");
     if (d->act == E2FGVI_ACT_DCNPOST)
         E2_REQUIRE(d->residual && d->res_dtype == E2FGVI_F32 && d->Cout % 3 == 0 && d->groups == 1, E2FGVI_EINVAL,
-                   "conv2d_bf16x: ACT_DCNPOST needs the fp32 [pixel][4] flows as residual, Cout %% 3 == 0, groups == 1");
+                   "conv2d_x: ACT_DCNPOST needs the fp32 [pixel][4] flows as residual, Cout %% 3 == 0, groups == 1");
     p.nsrc = d->nsrc;
     p.N = d->N; p.H = d->H; p.W = d->W; p.Ho = d->Ho; p.Wo = d->Wo;
     p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad;
@@ -1196,8 +1104,8 @@ static int conv2d_x(const e2fgvi_convx_desc* d, void* stream, int mode) {
     if (d->tap_packed) {
         PackX qt;
         E2_REQUIRE(d->nsrc == 1 && d->groups == 1 && geometry_taps(d->Cout, d->KH, d->KW, d->src_cpg[0], &qt, f32), E2FGVI_EINVAL,
-                   "conv2d_bf16x: tap-packed weights are for one source of <= 56 channels, no groups, KW >= 2");
-        E2_REQUIRE(d->tile < 10 || d->tile > 20, E2FGVI_EUNSUP, "conv2d_bf16x: the row-shift tiles do not take tap-packed weights");
+                   "conv2d_x: tap-packed weights are for one source of <= 56 channels, no groups, KW >= 2");
+        E2_REQUIRE(d->tile < 10 || d->tile > 20, E2FGVI_EUNSUP, "conv2d_x: the row-shift tiles do not take tap-packed weights");
         q.wgroup_elems = qt.wgroup_elems;
         p.tp_cq = qt.tp_cq;
         p.tp_magic = 0xFFFFFFFFu / (unsigned)d->KW + 1u;
@@ -1248,14 +1156,13 @@ static int conv2d_x(const e2fgvi_convx_desc* d, void* stream, int mode) {
         case 18: return launch_x<256, 64, 4, 2, true>(p, d->groups, st, mode);       // all of their traffic, a third of it here
         default: break;
     }
-    e2fgvi_set_error("conv2d_bf16x: unknown tile %d", tile);
+    e2fgvi_set_error("conv2d_x: unknown tile %d", tile);
     return E2FGVI_EINVAL;
 }
 
-extern "C" int e2fgvi_conv2d_bf16x(const e2fgvi_convx_desc* d, void* stream) { return conv2d_x(d, stream, 0); }
-/* the same kernel on fp32 operands (fp32 NHWC sources, e2fgvi_pack_conv_weight_f32x weights, exact fp32 MFMA) */
-extern "C" int e2fgvi_conv2d_f32x(const e2fgvi_convx_desc* d, void* stream) { return conv2d_x(d, stream, 1); }
-/* fp32 NHWC sources, e2fgvi_pack_conv_weight_f32x3 weights: fp32 products as six exact bf16 MFMA terms (kernel MODE 2) */
-extern "C" int e2fgvi_conv2d_f32x3(const e2fgvi_convx_desc* d, void* stream) { return conv2d_x(d, stream, 2); }
-/* MODE 0 with fp16 operands (kernel MODE 3): fp16 sources, e2fgvi_pack_conv_weight_f16x weights, fp16 MFMA */
-extern "C" int e2fgvi_conv2d_f16x(const e2fgvi_convx_desc* d, void* stream) { return conv2d_x(d, stream, 3); }
+/* mode: E2FGVI_BF16 / E2FGVI_F16 (16-bit sources and weights on bf16 / fp16 MFMA), E2FGVI_F32 (fp32 sources and weights, exact fp32
+ * MFMA), E2FGVI_BF16X3 (fp32 sources, weights as three bf16 planes: fp32 products as six exact bf16 MFMA terms) */
+extern "C" int e2fgvi_conv2d_x(const e2fgvi_convx_desc* d, int32_t mode, void* stream) {
+    const int m = mode_x("conv2d_x", mode);
+    return m < 0 ? E2FGVI_EINVAL : conv2d_x(d, stream, m);
+}

@@ -697,61 +697,37 @@ int launch_dcn(DcnParams& p, hipStream_t st, bool bf, bool s16, bool x3 = false,
 
 }  // namespace
 
-extern "C" int64_t e2fgvi_packed_dcn_weight_size(int32_t Cout, int32_t C, int32_t KH, int32_t KW) {
-    if (Cout <= 0 || C <= 0 || C % 16 || KH <= 0 || KW <= 0) {
-        e2fgvi_set_error("packed_dcn_weight_size: bad geometry");
+#define E2_MFMA_DT_OK(dt) ((dt) == E2FGVI_F32 || (dt) == E2FGVI_BF16 || (dt) == E2FGVI_BF16X3 || (dt) == E2FGVI_F16)
+
+/* elements of the packing for mfma_dtype: one per weight (4 bytes fp32, 2 bytes bf16 / fp16), three bf16 planes for E2FGVI_BF16X3 */
+extern "C" int64_t e2fgvi_packed_dcn_weight_size(int32_t mfma_dtype, int32_t Cout, int32_t C, int32_t KH, int32_t KW) {
+    if (!E2_MFMA_DT_OK(mfma_dtype) || Cout <= 0 || C <= 0 || C % 16 || KH <= 0 || KW <= 0) {
+        e2fgvi_set_error("packed_dcn_weight_size: bad geometry, or an mfma_dtype that is none of E2FGVI_F32, E2FGVI_BF16, E2FGVI_BF16X3, E2FGVI_F16");
         return E2FGVI_EINVAL;
     }
-    return dcn_packed_size(Cout, C, KH, KW);
+    return (mfma_dtype == E2FGVI_BF16X3 ? 3 : 1) * dcn_packed_size(Cout, C, KH, KW);
 }
 
-extern "C" int e2fgvi_pack_dcn_weight(const float* w, float* wpacked, int32_t Cout, int32_t C, int32_t KH, int32_t KW,
-                                      int32_t deform_groups, void* stream) {
+/* w: fp32 [Cout, C, KH, KW]; wpacked: e2fgvi_packed_dcn_weight_size(mfma_dtype, ...) elements.  The bf16 and fp16 packings share one
+ * layout; E2FGVI_BF16X3 stores every weight as three bf16 planes whose sum is the fp32 weight. */
+extern "C" int e2fgvi_pack_dcn_weight(const float* w, void* wpacked, int32_t mfma_dtype, int32_t Cout, int32_t C, int32_t KH,
+                                      int32_t KW, int32_t deform_groups, void* stream) {
     E2_REQUIRE(w && wpacked, E2FGVI_EINVAL, "pack_dcn_weight: null pointer");
+    E2_REQUIRE(E2_MFMA_DT_OK(mfma_dtype), E2FGVI_EINVAL,
+               "pack_dcn_weight: mfma_dtype must be E2FGVI_F32, E2FGVI_BF16, E2FGVI_BF16X3 or E2FGVI_F16");
     E2_REQUIRE(Cout > 0 && C > 0 && deform_groups > 0 && C % deform_groups == 0 && (C / deform_groups) % 16 == 0,
                E2FGVI_EUNSUP, "pack_dcn_weight: channels per deform group must be a multiple of 16");
     const long long total = dcn_packed_size(Cout, C, KH, KW);
-    hipLaunchKernelGGL(pack_dcn_weight_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, (hipStream_t)stream, w,
-                       wpacked, Cout, C, KH * KW, C / deform_groups, round_up(Cout, 32), total);
+    const dim3 grid((unsigned)cdiv64(total, 256)), block(256);
+    const int K = KH * KW, cg = C / deform_groups, Npad = round_up(Cout, 32);
+    hipStream_t st = (hipStream_t)stream;
+    switch (mfma_dtype) {
+        case E2FGVI_F32: hipLaunchKernelGGL(pack_dcn_weight_kernel, grid, block, 0, st, w, (float*)wpacked, Cout, C, K, cg, Npad, total); break;
+        case E2FGVI_BF16: hipLaunchKernelGGL(pack_dcn_weight_bf16_kernel<__bf16>, grid, block, 0, st, w, (__bf16*)wpacked, Cout, C, K, cg, Npad, total); break;
+        case E2FGVI_F16: hipLaunchKernelGGL(pack_dcn_weight_bf16_kernel<_Float16>, grid, block, 0, st, w, (_Float16*)wpacked, Cout, C, K, cg, Npad, total); break;
+        default: hipLaunchKernelGGL(pack_dcn_weight_x3_kernel, grid, block, 0, st, w, (unsigned short*)wpacked, Cout, C, K, cg, Npad, total); break;
+    }
     E2_LAUNCH_CHECK("pack_dcn_weight");
-    return 0;
-}
-
-/* bf16 weights for mfma_dtype = E2FGVI_BF16: same element count as the fp32 packing, 2 bytes each */
-extern "C" int e2fgvi_pack_dcn_weight_bf16(const float* w, void* wpacked, int32_t Cout, int32_t C, int32_t KH, int32_t KW,
-                                           int32_t deform_groups, void* stream) {
-    E2_REQUIRE(w && wpacked, E2FGVI_EINVAL, "pack_dcn_weight_bf16: null pointer");
-    E2_REQUIRE(Cout > 0 && C > 0 && deform_groups > 0 && C % deform_groups == 0 && (C / deform_groups) % 16 == 0,
-               E2FGVI_EUNSUP, "pack_dcn_weight_bf16: channels per deform group must be a multiple of 16");
-    const long long total = dcn_packed_size(Cout, C, KH, KW);
-    hipLaunchKernelGGL(pack_dcn_weight_bf16_kernel<__bf16>, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, (hipStream_t)stream, w,
-                       (__bf16*)wpacked, Cout, C, KH * KW, C / deform_groups, round_up(Cout, 32), total);
-    E2_LAUNCH_CHECK("pack_dcn_weight_bf16");
-    return 0;
-}
-/* fp16 weights for mfma_dtype = E2FGVI_F16: the bf16 layout, fp16 elements */
-extern "C" int e2fgvi_pack_dcn_weight_f16(const float* w, void* wpacked, int32_t Cout, int32_t C, int32_t KH, int32_t KW,
-                                          int32_t deform_groups, void* stream) {
-    E2_REQUIRE(w && wpacked, E2FGVI_EINVAL, "pack_dcn_weight_f16: null pointer");
-    E2_REQUIRE(Cout > 0 && C > 0 && deform_groups > 0 && C % deform_groups == 0 && (C / deform_groups) % 16 == 0,
-               E2FGVI_EUNSUP, "pack_dcn_weight_f16: channels per deform group must be a multiple of 16");
-    const long long total = dcn_packed_size(Cout, C, KH, KW);
-    hipLaunchKernelGGL(pack_dcn_weight_bf16_kernel<_Float16>, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, (hipStream_t)stream, w,
-                       (_Float16*)wpacked, Cout, C, KH * KW, C / deform_groups, round_up(Cout, 32), total);
-    E2_LAUNCH_CHECK("pack_dcn_weight_f16");
-    return 0;
-}
-
-/* split-operand weights for mfma_dtype = E2FGVI_BF16X3: 3 x e2fgvi_packed_dcn_weight_size elements of 2 bytes (ABI 7) */
-extern "C" int e2fgvi_pack_dcn_weight_x3(const float* w, void* wpacked, int32_t Cout, int32_t C, int32_t KH, int32_t KW,
-                                         int32_t deform_groups, void* stream) {
-    E2_REQUIRE(w && wpacked, E2FGVI_EINVAL, "pack_dcn_weight_x3: null pointer");
-    E2_REQUIRE(Cout > 0 && C > 0 && deform_groups > 0 && C % deform_groups == 0 && (C / deform_groups) % 16 == 0,
-               E2FGVI_EUNSUP, "pack_dcn_weight_x3: channels per deform group must be a multiple of 16");
-    const long long total = dcn_packed_size(Cout, C, KH, KW);
-    hipLaunchKernelGGL(pack_dcn_weight_x3_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, (hipStream_t)stream, w,
-                       (unsigned short*)wpacked, Cout, C, KH * KW, C / deform_groups, round_up(Cout, 32), total);
-    E2_LAUNCH_CHECK("pack_dcn_weight_x3");
     return 0;
 }
 
@@ -763,8 +739,7 @@ extern "C" int e2fgvi_mdcn_nhwc(const e2fgvi_mdcn_desc* d, void* stream) {
     E2_REQUIRE(d->src_dtype == E2FGVI_F32 || (d->src_dtype == E2FGVI_BF16 && d->mfma_dtype == E2FGVI_BF16) ||
                    (d->src_dtype == E2FGVI_F16 && d->mfma_dtype == E2FGVI_F16), E2FGVI_EINVAL,
                "mdcn: src_dtype must be E2FGVI_F32, or E2FGVI_BF16 / E2FGVI_F16 together with the same mfma_dtype");
-    E2_REQUIRE(d->mfma_dtype == E2FGVI_F32 || d->mfma_dtype == E2FGVI_BF16 || d->mfma_dtype == E2FGVI_BF16X3 ||
-                   d->mfma_dtype == E2FGVI_F16, E2FGVI_EINVAL,
+    E2_REQUIRE(E2_MFMA_DT_OK(d->mfma_dtype), E2FGVI_EINVAL,
                "mdcn: mfma_dtype must be E2FGVI_F32, E2FGVI_BF16, E2FGVI_BF16X3 or E2FGVI_F16");
     const bool x3 = d->mfma_dtype == E2FGVI_BF16X3;
     const bool f16 = d->mfma_dtype == E2FGVI_F16;

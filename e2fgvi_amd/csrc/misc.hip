@@ -602,8 +602,8 @@ template <typename Fn> void with_dtype(int dt, Fn&& f) {
 #define E2_DT_OK(dt) ((dt) == E2FGVI_F32 || (dt) == E2FGVI_BF16 || (dt) == E2FGVI_F16)
 #define E2_DT16(dt) ((dt) == E2FGVI_BF16 || (dt) == E2FGVI_F16)
 
-extern "C" int e2fgvi_nchw_to_nhwc_x(const float* src, void* dst, int32_t dst_dtype, int32_t N, int32_t C, int32_t H, int32_t W,
-                                     int32_t ld, float scale, float shift, void* stream) {
+extern "C" int e2fgvi_nchw_to_nhwc(const float* src, void* dst, int32_t dst_dtype, int32_t N, int32_t C, int32_t H, int32_t W,
+                                   int32_t ld, float scale, float shift, void* stream) {
     E2_REQUIRE(src && dst && N > 0 && C > 0 && H > 0 && W > 0 && ld >= C && E2_DT_OK(dst_dtype), E2FGVI_EINVAL,
                "nchw_to_nhwc: bad arguments");
     if (ld == 8 && C <= 8 && ((uintptr_t)dst & 15) == 0) {
@@ -632,10 +632,6 @@ extern "C" int e2fgvi_nchw_to_nhwc_x(const float* src, void* dst, int32_t dst_dt
     E2_LAUNCH_CHECK("nchw_to_nhwc");
     return 0;
 }
-extern "C" int e2fgvi_nchw_to_nhwc(const float* src, float* dst, int32_t N, int32_t C, int32_t H, int32_t W, int32_t ld,
-                                   float scale, float shift, void* stream) {
-    return e2fgvi_nchw_to_nhwc_x(src, dst, E2FGVI_F32, N, C, H, W, ld, scale, shift, stream);
-}
 
 extern "C" int e2fgvi_nhwc_to_nchw(const float* src, int32_t ld, float* dst, int32_t N, int32_t C, int32_t H, int32_t W,
                                    void* stream) {
@@ -656,52 +652,45 @@ static void resize_scales(int H, int W, int Ho, int Wo, int align_corners, float
     }
 }
 
-extern "C" int e2fgvi_resize_bilinear(const float* src, int32_t src_nchw, int32_t src_ld, float* dst, int32_t dst_ld,
+extern "C" int e2fgvi_resize_bilinear(const void* src, int32_t dtype, int32_t src_nchw, int32_t src_ld, void* dst, int32_t dst_ld,
                                       int32_t N, int32_t C, int32_t H, int32_t W, int32_t Ho, int32_t Wo,
                                       int32_t align_corners, const float* scale, const float* shift, void* stream) {
     E2_REQUIRE(src && dst && N > 0 && C > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0 && dst_ld >= C &&
-                   (src_nchw || src_ld >= C),
+                   (src_nchw || src_ld >= C) && E2_DT_OK(dtype),
                E2FGVI_EINVAL, "resize_bilinear: bad arguments");
     float sh, sw;
     resize_scales(H, W, Ho, Wo, align_corners, sh, sw);
+    if (E2_DT16(dtype)) {
+        E2_REQUIRE(!src_nchw && !scale && !shift, E2FGVI_EUNSUP, "resize_bilinear: 16-bit tensors are resized NHWC -> NHWC without an affine");
+        E2_REQUIRE(C % 8 == 0 && src_ld % 8 == 0 && dst_ld % 8 == 0 && (((uintptr_t)src | (uintptr_t)dst) & 15) == 0, E2FGVI_EINVAL,
+                   "resize_bilinear: bad arguments (NHWC 16-bit, channels in multiples of 8)");
+        const long long total4 = (long long)N * Ho * Wo * (C / 8);
+        with_dtype(dtype, [&](auto z) {
+            using T = E2_ELEM(z);
+            if constexpr (!std::is_same_v<T, float>)
+                hipLaunchKernelGGL(resize_bilinear_vec4_kernel<T>, dim3(blocks_for(total4)), dim3(NTH), 0, (hipStream_t)stream,
+                                   (const T*)src, src_ld, (T*)dst, dst_ld, N, C / 8, H, W, Ho, Wo, align_corners, sh, sw,
+                                   (const float*)nullptr, (const float*)nullptr, total4);
+        });
+        E2_LAUNCH_CHECK("resize_bilinear_16");
+        return 0;
+    }
+    const float* s32 = (const float*)src;
+    float* d32 = (float*)dst;
     const bool vec = !src_nchw && C % 4 == 0 && src_ld % 4 == 0 && dst_ld % 4 == 0 && (((uintptr_t)src | (uintptr_t)dst) & 15) == 0 &&
                      (!scale || ((uintptr_t)scale & 15) == 0) && (!shift || ((uintptr_t)shift & 15) == 0);
     if (vec) {
         const long long total4 = (long long)N * Ho * Wo * (C / 4);
-        hipLaunchKernelGGL(resize_bilinear_vec4_kernel<float>, dim3(blocks_for(total4)), dim3(NTH), 0, (hipStream_t)stream, src,
-                           src_ld, dst, dst_ld, N, C / 4, H, W, Ho, Wo, align_corners, sh, sw, scale, shift, total4);
+        hipLaunchKernelGGL(resize_bilinear_vec4_kernel<float>, dim3(blocks_for(total4)), dim3(NTH), 0, (hipStream_t)stream, s32,
+                           src_ld, d32, dst_ld, N, C / 4, H, W, Ho, Wo, align_corners, sh, sw, scale, shift, total4);
         E2_LAUNCH_CHECK("resize_bilinear_vec4");
         return 0;
     }
     const long long total = (long long)N * Ho * Wo * C;
-    hipLaunchKernelGGL(resize_bilinear_kernel, dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream, src, src_nchw,
-                       src_ld, dst, dst_ld, N, C, H, W, Ho, Wo, align_corners, sh, sw, scale, shift, total);
+    hipLaunchKernelGGL(resize_bilinear_kernel, dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream, s32, src_nchw,
+                       src_ld, d32, dst_ld, N, C, H, W, Ho, Wo, align_corners, sh, sw, scale, shift, total);
     E2_LAUNCH_CHECK("resize_bilinear");
     return 0;
-}
-
-template <typename T>
-static int resize_bilinear_16(const char* name, const void* src, int32_t src_ld, void* dst, int32_t dst_ld, int32_t N, int32_t C,
-                              int32_t H, int32_t W, int32_t Ho, int32_t Wo, int32_t align_corners, void* stream) {
-    E2_REQUIRE(src && dst && N > 0 && C > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0 && dst_ld >= C && src_ld >= C && C % 8 == 0 &&
-                   src_ld % 8 == 0 && dst_ld % 8 == 0 && (((uintptr_t)src | (uintptr_t)dst) & 15) == 0,
-               E2FGVI_EINVAL, "%s: bad arguments (NHWC 16-bit, channels in multiples of 8)", name);
-    float sh, sw;
-    resize_scales(H, W, Ho, Wo, align_corners, sh, sw);
-    const long long total4 = (long long)N * Ho * Wo * (C / 8);
-    hipLaunchKernelGGL(resize_bilinear_vec4_kernel<T>, dim3(blocks_for(total4)), dim3(NTH), 0, (hipStream_t)stream,
-                       (const T*)src, src_ld, (T*)dst, dst_ld, N, C / 8, H, W, Ho, Wo, align_corners, sh, sw,
-                       (const float*)nullptr, (const float*)nullptr, total4);
-    E2_LAUNCH_CHECK(name);
-    return 0;
-}
-extern "C" int e2fgvi_resize_bilinear_bf16(const void* src, int32_t src_ld, void* dst, int32_t dst_ld, int32_t N, int32_t C,
-                                           int32_t H, int32_t W, int32_t Ho, int32_t Wo, int32_t align_corners, void* stream) {
-    return resize_bilinear_16<__bf16>("resize_bilinear_bf16", src, src_ld, dst, dst_ld, N, C, H, W, Ho, Wo, align_corners, stream);
-}
-extern "C" int e2fgvi_resize_bilinear_f16(const void* src, int32_t src_ld, void* dst, int32_t dst_ld, int32_t N, int32_t C,
-                                          int32_t H, int32_t W, int32_t Ho, int32_t Wo, int32_t align_corners, void* stream) {
-    return resize_bilinear_16<_Float16>("resize_bilinear_f16", src, src_ld, dst, dst_ld, N, C, H, W, Ho, Wo, align_corners, stream);
 }
 
 extern "C" int e2fgvi_avgpool2_nhwc(const float* src, float* dst, int32_t N, int32_t H, int32_t W, int32_t C,
@@ -714,63 +703,26 @@ extern "C" int e2fgvi_avgpool2_nhwc(const float* src, float* dst, int32_t N, int
     return 0;
 }
 
-extern "C" int e2fgvi_spynet_level_input_x(const float* pyr, const int32_t* ref_idx, const int32_t* supp_idx,
-                                           const float* flow_prev, float* out, void* out_bf16, int32_t Np, int32_t h, int32_t w,
-                                           void* stream) {
+extern "C" int e2fgvi_spynet_level_input(const float* pyr, const int32_t* ref_idx, const int32_t* supp_idx, const float* flow_prev,
+                                         float* out, void* out16, int32_t out16_dtype, int32_t Np, int32_t h, int32_t w, void* stream) {
     E2_REQUIRE(pyr && ref_idx && supp_idx && out && Np > 0 && h > 0 && w > 0, E2FGVI_EINVAL, "spynet_level_input: bad arguments");
     E2_REQUIRE(!flow_prev || (h % 2 == 0 && w % 2 == 0), E2FGVI_EINVAL, "spynet_level_input: odd level size");
+    E2_REQUIRE(!out16 || E2_DT16(out16_dtype), E2FGVI_EINVAL, "spynet_level_input: the 16-bit copy is E2FGVI_BF16 or E2FGVI_F16");
     const long long total = (long long)Np * h * w;
-    hipLaunchKernelGGL(spynet_level_input_kernel<__bf16>, dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream, pyr, ref_idx,
-                       supp_idx, flow_prev, out, (__bf16*)out_bf16, Np, h, w);
-    E2_LAUNCH_CHECK("spynet_level_input");
-    return 0;
-}
-/* ... with the 16-bit copy as fp16 */
-extern "C" int e2fgvi_spynet_level_input_x_f16(const float* pyr, const int32_t* ref_idx, const int32_t* supp_idx,
-                                               const float* flow_prev, float* out, void* out_f16, int32_t Np, int32_t h, int32_t w,
-                                               void* stream) {
-    E2_REQUIRE(pyr && ref_idx && supp_idx && out && Np > 0 && h > 0 && w > 0, E2FGVI_EINVAL, "spynet_level_input: bad arguments");
-    E2_REQUIRE(!flow_prev || (h % 2 == 0 && w % 2 == 0), E2FGVI_EINVAL, "spynet_level_input: odd level size");
-    const long long total = (long long)Np * h * w;
-    hipLaunchKernelGGL(spynet_level_input_kernel<_Float16>, dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream, pyr, ref_idx,
-                       supp_idx, flow_prev, out, (_Float16*)out_f16, Np, h, w);
-    E2_LAUNCH_CHECK("spynet_level_input");
-    return 0;
-}
-extern "C" int e2fgvi_spynet_level_input(const float* pyr, const int32_t* ref_idx, const int32_t* supp_idx,
-                                         const float* flow_prev, float* out, int32_t Np, int32_t h, int32_t w,
-                                         void* stream) {
-    return e2fgvi_spynet_level_input_x(pyr, ref_idx, supp_idx, flow_prev, out, nullptr, Np, h, w, stream);
-}
-
-extern "C" int e2fgvi_prop_cond_xs(const void* feat_prop, int32_t fp_ld, const void* feat_n2, int32_t f2_ld, int32_t src_dtype,
-                                   const float* flow_a, const float* flow_b, int64_t flow_img_stride, void* cond,
-                                   int32_t cond_dtype, float* flows, void* flows8_bf16, int32_t N, int32_t H, int32_t W,
-                                   int32_t C, void* stream) {
-    if (src_dtype == E2FGVI_F32)
-        return e2fgvi_prop_cond_x((const float*)feat_prop, fp_ld, (const float*)feat_n2, f2_ld, flow_a, flow_b, flow_img_stride, cond,
-                                  cond_dtype, flows, flows8_bf16, N, H, W, C, stream);
-    E2_REQUIRE(E2_DT16(src_dtype) && cond_dtype == src_dtype, E2FGVI_EINVAL, "prop_cond: 16-bit sources need a cond of their type");
-    E2_REQUIRE(feat_prop && flow_a && cond && flows && N > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0 && fp_ld % 8 == 0 &&
-                   ((uintptr_t)feat_prop & 15) == 0,
-               E2FGVI_EINVAL, "prop_cond: bad arguments");
-    E2_REQUIRE(!flow_b || (feat_n2 && f2_ld % 8 == 0 && ((uintptr_t)feat_n2 & 15) == 0), E2FGVI_EINVAL, "prop_cond: flow_b needs feat_n2");
-    const long long total = (long long)N * H * W * (C / 8);
-    with_dtype(src_dtype, [&](auto z) {
+    with_dtype(out16 ? out16_dtype : E2FGVI_BF16, [&](auto z) {      // (without a copy: the bf16 instantiation, which then stores none)
         using T = E2_ELEM(z);
         if constexpr (!std::is_same_v<T, float>)
-            hipLaunchKernelGGL((prop_cond_kernel<T, T>), dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream,
-                               (const T*)feat_prop, fp_ld, (const T*)feat_n2, f2_ld, flow_a, flow_b, (long long)flow_img_stride,
-                               (T*)cond, flows, (T*)flows8_bf16, N, H, W, C);
+            hipLaunchKernelGGL(spynet_level_input_kernel<T>, dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream, pyr, ref_idx,
+                               supp_idx, flow_prev, out, (T*)out16, Np, h, w);
     });
-    E2_LAUNCH_CHECK("prop_cond");
+    E2_LAUNCH_CHECK("spynet_level_input");
     return 0;
 }
 
-extern "C" int e2fgvi_prop_cond_x(const float* feat_prop, int32_t fp_ld, const float* feat_n2, int32_t f2_ld,
-                                  const float* flow_a, const float* flow_b, int64_t flow_img_stride, void* cond,
-                                  int32_t cond_dtype, float* flows, void* flows8_bf16, int32_t N, int32_t H, int32_t W,
-                                  int32_t C, void* stream) {
+// fp32 warp sources; the cond fp32 or 16-bit
+static int prop_cond_f32(const float* feat_prop, int32_t fp_ld, const float* feat_n2, int32_t f2_ld, const float* flow_a,
+                         const float* flow_b, int64_t flow_img_stride, void* cond, int32_t cond_dtype, float* flows,
+                         void* flows8_bf16, int32_t N, int32_t H, int32_t W, int32_t C, void* stream) {
     E2_REQUIRE(feat_prop && flow_a && cond && flows && N > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0 && fp_ld % 4 == 0 &&
                    E2_DT_OK(cond_dtype),
                E2FGVI_EINVAL, "prop_cond: bad arguments");
@@ -793,11 +745,28 @@ extern "C" int e2fgvi_prop_cond_x(const float* feat_prop, int32_t fp_ld, const f
     E2_LAUNCH_CHECK("prop_cond");
     return 0;
 }
-extern "C" int e2fgvi_prop_cond(const float* feat_prop, int32_t fp_ld, const float* feat_n2, int32_t f2_ld,
-                                const float* flow_a, const float* flow_b, int64_t flow_img_stride, float* cond,
-                                float* flows, int32_t N, int32_t H, int32_t W, int32_t C, void* stream) {
-    return e2fgvi_prop_cond_x(feat_prop, fp_ld, feat_n2, f2_ld, flow_a, flow_b, flow_img_stride, cond, E2FGVI_F32, flows,
-                              nullptr, N, H, W, C, stream);
+extern "C" int e2fgvi_prop_cond(const void* feat_prop, int32_t fp_ld, const void* feat_n2, int32_t f2_ld, int32_t src_dtype,
+                                const float* flow_a, const float* flow_b, int64_t flow_img_stride, void* cond,
+                                int32_t cond_dtype, float* flows, void* flows8_bf16, int32_t N, int32_t H, int32_t W,
+                                int32_t C, void* stream) {
+    if (src_dtype == E2FGVI_F32)
+        return prop_cond_f32((const float*)feat_prop, fp_ld, (const float*)feat_n2, f2_ld, flow_a, flow_b, flow_img_stride, cond,
+                             cond_dtype, flows, flows8_bf16, N, H, W, C, stream);
+    E2_REQUIRE(E2_DT16(src_dtype) && cond_dtype == src_dtype, E2FGVI_EINVAL, "prop_cond: 16-bit sources need a cond of their type");
+    E2_REQUIRE(feat_prop && flow_a && cond && flows && N > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0 && fp_ld % 8 == 0 &&
+                   ((uintptr_t)feat_prop & 15) == 0,
+               E2FGVI_EINVAL, "prop_cond: bad arguments");
+    E2_REQUIRE(!flow_b || (feat_n2 && f2_ld % 8 == 0 && ((uintptr_t)feat_n2 & 15) == 0), E2FGVI_EINVAL, "prop_cond: flow_b needs feat_n2");
+    const long long total = (long long)N * H * W * (C / 8);
+    with_dtype(src_dtype, [&](auto z) {
+        using T = E2_ELEM(z);
+        if constexpr (!std::is_same_v<T, float>)
+            hipLaunchKernelGGL((prop_cond_kernel<T, T>), dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream,
+                               (const T*)feat_prop, fp_ld, (const T*)feat_n2, f2_ld, flow_a, flow_b, (long long)flow_img_stride,
+                               (T*)cond, flows, (T*)flows8_bf16, N, H, W, C);
+    });
+    E2_LAUNCH_CHECK("prop_cond");
+    return 0;
 }
 
 template <typename TO>
@@ -813,21 +782,17 @@ static int layernorm_launch(const float* x, const float* gamma, const float* bet
     E2_LAUNCH_CHECK("layernorm");
     return 0;
 }
-extern "C" int e2fgvi_layernorm_x(const float* x, const float* gamma, const float* beta, void* y, int32_t y_dtype, int64_t rows,
-                                  int32_t C, void* stream) {
+extern "C" int e2fgvi_layernorm(const float* x, const float* gamma, const float* beta, void* y, int32_t y_dtype, int64_t rows,
+                                int32_t C, void* stream) {
     E2_REQUIRE(x && gamma && beta && y && rows > 0 && E2_DT_OK(y_dtype), E2FGVI_EINVAL, "layernorm: bad arguments");
     E2_REQUIRE(C == 256 || C == 512 || C == 768 || C == 1024, E2FGVI_EUNSUP, "layernorm: C must be 256/512/768/1024");
     int rc = 0;
     with_dtype(y_dtype, [&](auto z) { rc = layernorm_launch(x, gamma, beta, (E2_ELEM(z)*)y, rows, C, (hipStream_t)stream); });
     return rc;
 }
-extern "C" int e2fgvi_layernorm(const float* x, const float* gamma, const float* beta, float* y, int64_t rows, int32_t C,
-                                void* stream) {
-    return e2fgvi_layernorm_x(x, gamma, beta, y, E2FGVI_F32, rows, C, stream);
-}
 
-extern "C" int e2fgvi_window_pool_x(const void* x, int32_t dtype, const float* w45, const float* bias1, void* pooled,
-                                    int32_t BT, int32_t fh, int32_t fw, int32_t C, void* stream) {
+extern "C" int e2fgvi_window_pool(const void* x, int32_t dtype, const float* w45, const float* bias1, void* pooled,
+                                  int32_t BT, int32_t fh, int32_t fw, int32_t C, void* stream) {
     E2_REQUIRE(x && w45 && bias1 && pooled && BT > 0 && fh > 0 && fw > 0 && fh % 5 == 0 && fw % 9 == 0 && C % 4 == 0 &&
                    E2_DT_OK(dtype),
                E2FGVI_EINVAL, "window_pool: bad arguments");
@@ -841,10 +806,6 @@ extern "C" int e2fgvi_window_pool_x(const void* x, int32_t dtype, const float* w
     E2_LAUNCH_CHECK("window_pool");
     return 0;
 }
-extern "C" int e2fgvi_window_pool(const float* x, const float* w45, const float* bias1, float* pooled, int32_t BT,
-                                  int32_t fh, int32_t fw, int32_t C, void* stream) {
-    return e2fgvi_window_pool_x(x, E2FGVI_F32, w45, bias1, pooled, BT, fh, fw, C, stream);
-}
 
 static int check_fold(const char* name, int F, int fh, int fw, int H, int W, int C) {
     E2_REQUIRE(F > 0 && C > 0 && C % 4 == 0, E2FGVI_EINVAL, "%s: bad arguments", name);
@@ -853,105 +814,64 @@ static int check_fold(const char* name, int F, int fh, int fw, int H, int W, int
     return 0;
 }
 
-extern "C" int e2fgvi_ffn_fold_x(const void* hid, void* folded, int32_t dtype, int32_t F, int32_t fh, int32_t fw, int32_t H,
-                                 int32_t W, int32_t C, void* stream) {
-    E2_REQUIRE(hid && folded && E2_DT_OK(dtype), E2FGVI_EINVAL, "ffn_fold: bad arguments");
-    if (int rc = check_fold("ffn_fold", F, fh, fw, H, W, C)) return rc;
-    E2_REQUIRE(dtype == E2FGVI_F32 || C % 8 == 0, E2FGVI_EINVAL, "ffn_fold: 16-bit needs C %% 8 == 0");
-    const long long total = (long long)F * H * W * (C / (E2_DT16(dtype) ? 8 : 4));
-    with_dtype(dtype, [&](auto z) {
-        using T = E2_ELEM(z);
-        hipLaunchKernelGGL((fold_kernel<true, T, T, T>), dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream,
-                           (const T*)hid, (const float*)nullptr, (const T*)nullptr, (T*)folded, F, fh, fw, H, W, C);
-    });
-    E2_LAUNCH_CHECK("ffn_fold");
-    return 0;
-}
-extern "C" int e2fgvi_ffn_fold(const float* hid, float* folded, int32_t F, int32_t fh, int32_t fw, int32_t H, int32_t W,
-                               int32_t C, void* stream) {
-    return e2fgvi_ffn_fold_x(hid, folded, E2FGVI_F32, F, fh, fw, H, W, C, stream);
-}
-
-extern "C" int e2fgvi_ffn_unfold_gelu_x(const void* folded, void* out, int32_t dtype, int32_t F, int32_t fh, int32_t fw,
-                                        int32_t H, int32_t W, int32_t C, void* stream) {
-    E2_REQUIRE(folded && out && E2_DT_OK(dtype), E2FGVI_EINVAL, "ffn_unfold_gelu: bad arguments");
-    if (int rc = check_fold("ffn_unfold_gelu", F, fh, fw, H, W, C)) return rc;
-    E2_REQUIRE(dtype == E2FGVI_F32 || C % 8 == 0, E2FGVI_EINVAL, "ffn_unfold_gelu: 16-bit needs C %% 8 == 0");
-    const long long total = (long long)F * fh * fw * 49 * (C / (E2_DT16(dtype) ? 8 : 4));
-    with_dtype(dtype, [&](auto z) {
-        using T = E2_ELEM(z);
-        hipLaunchKernelGGL(unfold_gelu_kernel<T>, dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream,
-                           (const T*)folded, (T*)out, F, fh, fw, H, W, C);
-    });
-    E2_LAUNCH_CHECK("ffn_unfold_gelu");
-    return 0;
-}
-extern "C" int e2fgvi_ffn_unfold_gelu(const float* folded, float* out, int32_t F, int32_t fh, int32_t fw, int32_t H,
-                                      int32_t W, int32_t C, void* stream) {
-    return e2fgvi_ffn_unfold_gelu_x(folded, out, E2FGVI_F32, F, fh, fw, H, W, C, stream);
-}
-
-// The same pair with the GELU moved in front of the unfold (see fold_kernel): folded = GELU(fold(hid) / count), then a pure
-// gather.  fp32: bit-identical to ffn_fold + ffn_unfold_gelu; bf16: one rounding less (GELU sees the unrounded fold).
-extern "C" int e2fgvi_ffn_fold_gelu_x(const void* hid, void* folded, int32_t dtype, int32_t F, int32_t fh, int32_t fw, int32_t H,
-                                      int32_t W, int32_t C, void* stream) {
-    E2_REQUIRE(hid && folded && E2_DT_OK(dtype), E2FGVI_EINVAL, "ffn_fold_gelu: bad arguments");
-    if (int rc = check_fold("ffn_fold_gelu", F, fh, fw, H, W, C)) return rc;
-    E2_REQUIRE(dtype == E2FGVI_F32 || C % 8 == 0, E2FGVI_EINVAL, "ffn_fold_gelu: 16-bit needs C %% 8 == 0");
-    const long long total = (long long)F * H * W * (C / (E2_DT16(dtype) ? 8 : 4));
-    with_dtype(dtype, [&](auto z) {
-        using T = E2_ELEM(z);
-        hipLaunchKernelGGL((fold_kernel<true, T, T, T, true>), dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream,
-                           (const T*)hid, (const float*)nullptr, (const T*)nullptr, (T*)folded, F, fh, fw, H, W, C);
-    });
-    E2_LAUNCH_CHECK("ffn_fold_gelu");
-    return 0;
-}
-extern "C" int e2fgvi_ffn_unfold_x(const void* folded, void* out, int32_t dtype, int32_t F, int32_t fh, int32_t fw, int32_t H,
-                                   int32_t W, int32_t C, void* stream) {
-    E2_REQUIRE(folded && out && E2_DT_OK(dtype), E2FGVI_EINVAL, "ffn_unfold: bad arguments");
-    if (int rc = check_fold("ffn_unfold", F, fh, fw, H, W, C)) return rc;
-    E2_REQUIRE(dtype == E2FGVI_F32 || C % 8 == 0, E2FGVI_EINVAL, "ffn_unfold: 16-bit needs C %% 8 == 0");
-    const long long total = (long long)F * fh * fw * 49 * (C / (E2_DT16(dtype) ? 8 : 4));
-    with_dtype(dtype, [&](auto z) {
-        using T = E2_ELEM(z);
-        hipLaunchKernelGGL((unfold_gelu_kernel<T, false>), dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream,
-                           (const T*)folded, (T*)out, F, fh, fw, H, W, C);
-    });
-    E2_LAUNCH_CHECK("ffn_unfold");
-    return 0;
-}
-
-extern "C" int e2fgvi_softcomp_fold(const float* emb, const float* bias_hwc, const float* residual, float* dst, int32_t F,
-                                    int32_t fh, int32_t fw, int32_t H, int32_t W, int32_t C, void* stream) {
-    E2_REQUIRE(emb && dst, E2FGVI_EINVAL, "softcomp_fold: null pointer");
-    if (int rc = check_fold("softcomp_fold", F, fh, fw, H, W, C)) return rc;
-    const long long total = (long long)F * H * W * (C / 4);
-    hipLaunchKernelGGL((fold_kernel<false, float, float, float>), dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream, emb,
-                       bias_hwc, residual, dst, F, fh, fw, H, W, C);
-    E2_LAUNCH_CHECK("softcomp_fold");
-    return 0;
-}
-/* 16-bit data path: emb, residual and dst are bf16 / fp16 (bias_hwc stays fp32) */
-template <typename T>
-static int softcomp_fold_16(const char* name, const void* emb, const float* bias_hwc, const void* residual, void* dst, int32_t F,
-                            int32_t fh, int32_t fw, int32_t H, int32_t W, int32_t C, void* stream) {
-    E2_REQUIRE(emb && dst, E2FGVI_EINVAL, "%s: null pointer", name);
+// FusionFeedForward middle.  gelu = 0: folded = fold(hid) / count, and the unfold applies the GELU to what it gathers.  gelu = 1: the
+// GELU moves in front of the unfold (see fold_kernel): folded = GELU(fold(hid) / count), then a pure gather.  fp32: bit-identical
+// either way; 16-bit: one rounding less with gelu = 1 on the fold (GELU sees the unrounded fold).
+extern "C" int e2fgvi_ffn_fold(const void* hid, void* folded, int32_t dtype, int32_t gelu, int32_t F, int32_t fh, int32_t fw,
+                               int32_t H, int32_t W, int32_t C, void* stream) {
+    const char* name = gelu ? "ffn_fold_gelu" : "ffn_fold";
+    E2_REQUIRE(hid && folded && E2_DT_OK(dtype), E2FGVI_EINVAL, "%s: bad arguments", name);
     if (int rc = check_fold(name, F, fh, fw, H, W, C)) return rc;
-    E2_REQUIRE(C % 8 == 0, E2FGVI_EINVAL, "%s: C %% 8 != 0", name);
-    const long long total = (long long)F * H * W * (C / 8);
-    hipLaunchKernelGGL((fold_kernel<false, T, T, T>), dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream,
-                       (const T*)emb, bias_hwc, (const T*)residual, (T*)dst, F, fh, fw, H, W, C);
+    E2_REQUIRE(dtype == E2FGVI_F32 || C % 8 == 0, E2FGVI_EINVAL, "%s: 16-bit needs C %% 8 == 0", name);
+    const long long total = (long long)F * H * W * (C / (E2_DT16(dtype) ? 8 : 4));
+    with_dtype(dtype, [&](auto z) {
+        using T = E2_ELEM(z);
+        if (gelu)
+            hipLaunchKernelGGL((fold_kernel<true, T, T, T, true>), dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream,
+                               (const T*)hid, (const float*)nullptr, (const T*)nullptr, (T*)folded, F, fh, fw, H, W, C);
+        else
+            hipLaunchKernelGGL((fold_kernel<true, T, T, T>), dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream,
+                               (const T*)hid, (const float*)nullptr, (const T*)nullptr, (T*)folded, F, fh, fw, H, W, C);
+    });
     E2_LAUNCH_CHECK(name);
     return 0;
 }
-extern "C" int e2fgvi_softcomp_fold_bf16(const void* emb, const float* bias_hwc, const void* residual, void* dst, int32_t F,
-                                         int32_t fh, int32_t fw, int32_t H, int32_t W, int32_t C, void* stream) {
-    return softcomp_fold_16<__bf16>("softcomp_fold_bf16", emb, bias_hwc, residual, dst, F, fh, fw, H, W, C, stream);
+
+extern "C" int e2fgvi_ffn_unfold(const void* folded, void* out, int32_t dtype, int32_t gelu, int32_t F, int32_t fh, int32_t fw,
+                                 int32_t H, int32_t W, int32_t C, void* stream) {
+    const char* name = gelu ? "ffn_unfold_gelu" : "ffn_unfold";
+    E2_REQUIRE(folded && out && E2_DT_OK(dtype), E2FGVI_EINVAL, "%s: bad arguments", name);
+    if (int rc = check_fold(name, F, fh, fw, H, W, C)) return rc;
+    E2_REQUIRE(dtype == E2FGVI_F32 || C % 8 == 0, E2FGVI_EINVAL, "%s: 16-bit needs C %% 8 == 0", name);
+    const long long total = (long long)F * fh * fw * 49 * (C / (E2_DT16(dtype) ? 8 : 4));
+    with_dtype(dtype, [&](auto z) {
+        using T = E2_ELEM(z);
+        if (gelu)
+            hipLaunchKernelGGL(unfold_gelu_kernel<T>, dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream,
+                               (const T*)folded, (T*)out, F, fh, fw, H, W, C);
+        else
+            hipLaunchKernelGGL((unfold_gelu_kernel<T, false>), dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream,
+                               (const T*)folded, (T*)out, F, fh, fw, H, W, C);
+    });
+    E2_LAUNCH_CHECK(name);
+    return 0;
 }
-extern "C" int e2fgvi_softcomp_fold_f16(const void* emb, const float* bias_hwc, const void* residual, void* dst, int32_t F,
-                                        int32_t fh, int32_t fw, int32_t H, int32_t W, int32_t C, void* stream) {
-    return softcomp_fold_16<_Float16>("softcomp_fold_f16", emb, bias_hwc, residual, dst, F, fh, fw, H, W, C, stream);
+
+/* emb, residual and dst are of dtype (bias_hwc stays fp32) */
+extern "C" int e2fgvi_softcomp_fold(const void* emb, const float* bias_hwc, const void* residual, void* dst, int32_t dtype, int32_t F,
+                                    int32_t fh, int32_t fw, int32_t H, int32_t W, int32_t C, void* stream) {
+    E2_REQUIRE(emb && dst, E2FGVI_EINVAL, "softcomp_fold: null pointer");
+    E2_REQUIRE(E2_DT_OK(dtype), E2FGVI_EINVAL, "softcomp_fold: dtype must be E2FGVI_F32, E2FGVI_BF16 or E2FGVI_F16");
+    if (int rc = check_fold("softcomp_fold", F, fh, fw, H, W, C)) return rc;
+    E2_REQUIRE(dtype == E2FGVI_F32 || C % 8 == 0, E2FGVI_EINVAL, "softcomp_fold: C %% 8 != 0");
+    const long long total = (long long)F * H * W * (C / (E2_DT16(dtype) ? 8 : 4));
+    with_dtype(dtype, [&](auto z) {
+        using T = E2_ELEM(z);
+        hipLaunchKernelGGL((fold_kernel<false, T, T, T>), dim3(blocks_for(total)), dim3(NTH), 0, (hipStream_t)stream,
+                           (const T*)emb, bias_hwc, (const T*)residual, (T*)dst, F, fh, fw, H, W, C);
+    });
+    E2_LAUNCH_CHECK("softcomp_fold");
+    return 0;
 }
 
 extern "C" int e2fgvi_cast(const void* src, int32_t src_dtype, void* dst, int32_t dst_dtype, int64_t n, void* stream) {

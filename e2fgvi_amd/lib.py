@@ -9,10 +9,11 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("E2FGVI_LIB") or os.path.join(_HERE, "csrc", "libe2fgvi_hip.so")    # E2FGVI_LIB: A/B builds
 
-ABI_VERSION = 8        # the struct layouts / symbols below; csrc/error.hip e2fgvi_abi_version() must agree (checked in load())
+ABI_VERSION = 9        # the struct layouts / symbols below; csrc/error.hip e2fgvi_abi_version() must agree (checked in load())
 MAX_SRC = 4
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH, ACT_DCNPOST = 0, 1, 2, 3, 4
 DT_F32, DT_BF16 = 0, 1
+DT_BF16X3 = 2                     # fp32 tensors, MFMA operands as three bf16 pieces (mode of conv2d_x / its packers, mfma_dtype of the deformable conv)
 DT_F16 = 3                        # IEEE half: the fp16 data path
 
 _fp = C.c_void_p   # device pointers travel as plain addresses
@@ -43,11 +44,11 @@ class ConvXDesc(C.Structure):
         ("dst", _fp), ("dst_ld", C.c_int32), ("dst_coff", C.c_int32), ("dst_dtype", C.c_int32),
         ("dst2", _fp), ("dst2_ld", C.c_int32), ("dst2_coff", C.c_int32),
         ("act", C.c_int32), ("slope", C.c_float), ("tile", C.c_int32), ("dst_nchw", C.c_int32), ("tap_packed", C.c_int32),
-        # ABI version 6: explicit output grid / output scatter / broadcast residual (SoftComp in gather form)
+        # explicit output grid / output scatter / broadcast residual (SoftComp in gather form)
         ("out_grid", C.c_int32), ("pad_left", C.c_int32),
         ("out_sy", C.c_int32), ("out_sx", C.c_int32), ("out_py", C.c_int32), ("out_px", C.c_int32),
         ("out_H", C.c_int32), ("out_W", C.c_int32), ("res_bcast", C.c_int32),
-        # ABI version 8: output channels from dst2_split_from on as three exact bf16 planes in dst2 (the qkv Linear -> attention_x3)
+        # output channels from dst2_split_from on as three exact bf16 planes in dst2 (the qkv Linear -> attention_x3)
         ("dst2_split_from", C.c_int32), ("dst2_plane_stride", C.c_int64),
     ]
 
@@ -74,28 +75,11 @@ SYMBOLS = {
     "e2fgvi_nhwc_to_planar16": (C.c_int, [_fp, _fp, _i64, _i32, _fp]),
     "e2fgvi_conv2d_nhwc": (C.c_int, [C.POINTER(ConvDesc), _fp]),
     "e2fgvi_conv2d_nhwc_nopk": (C.c_int, [C.POINTER(ConvDesc), _fp]),
+    "e2fgvi_conv2d_x": (C.c_int, [C.POINTER(ConvXDesc), _i32, _fp]),
+    "e2fgvi_packed_conv_weight_x_size": (_i64, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i32)]),
+    "e2fgvi_pack_conv_weight_x": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i32), _fp]),
     "e2fgvi_packed_conv_weight_size": (_i64, [_i32, _i32, _i32, _i32, _i32, C.POINTER(_i32), _i32]),
     "e2fgvi_pack_conv_weight": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i32), _i32, _fp]),
-    "e2fgvi_conv2d_bf16x": (C.c_int, [C.POINTER(ConvXDesc), _fp]),
-    "e2fgvi_packed_conv_weight_bf16x_size": (_i64, [_i32, _i32, _i32, _i32, _i32, C.POINTER(_i32)]),
-    "e2fgvi_pack_conv_weight_bf16x": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i32), _fp]),
-    "e2fgvi_packed_conv_weight_bf16x_taps_size": (_i64, [_i32, _i32, _i32, _i32]),
-    "e2fgvi_pack_conv_weight_bf16x_taps": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _fp]),
-    "e2fgvi_conv2d_f16x": (C.c_int, [C.POINTER(ConvXDesc), _fp]),
-    "e2fgvi_packed_conv_weight_f16x_size": (_i64, [_i32, _i32, _i32, _i32, _i32, C.POINTER(_i32)]),
-    "e2fgvi_pack_conv_weight_f16x": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i32), _fp]),
-    "e2fgvi_packed_conv_weight_f16x_taps_size": (_i64, [_i32, _i32, _i32, _i32]),
-    "e2fgvi_pack_conv_weight_f16x_taps": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _fp]),
-    "e2fgvi_packed_conv_weight_f32x_taps_size": (_i64, [_i32, _i32, _i32, _i32]),
-    "e2fgvi_pack_conv_weight_f32x_taps": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _fp]),
-    "e2fgvi_conv2d_f32x": (C.c_int, [C.POINTER(ConvXDesc), _fp]),
-    "e2fgvi_packed_conv_weight_f32x_size": (_i64, [_i32, _i32, _i32, _i32, _i32, C.POINTER(_i32)]),
-    "e2fgvi_pack_conv_weight_f32x": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i32), _fp]),
-    "e2fgvi_conv2d_f32x3": (C.c_int, [C.POINTER(ConvXDesc), _fp]),
-    "e2fgvi_packed_conv_weight_f32x3_size": (_i64, [_i32, _i32, _i32, _i32, _i32, C.POINTER(_i32)]),
-    "e2fgvi_pack_conv_weight_f32x3": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i32), _fp]),
-    "e2fgvi_packed_conv_weight_f32x3_taps_size": (_i64, [_i32, _i32, _i32, _i32]),
-    "e2fgvi_pack_conv_weight_f32x3_taps": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _fp]),
     "e2fgvi_packed_winograd_weight_size": (_i64, [_i32, _i32, _i32, C.POINTER(_i32)]),
     "e2fgvi_pack_winograd_weight": (C.c_int, [_fp, _fp, _i32, _i32, _i32, C.POINTER(_i32), _fp]),
     "e2fgvi_conv3x3_winograd": (C.c_int, [C.POINTER(ConvDesc), _fp]),
@@ -109,24 +93,21 @@ SYMBOLS = {
     "e2fgvi_pack_tail_weight": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _fp]),
     "e2fgvi_conv3x3_tail": (C.c_int, [_fp, _i32, _i32, _fp, _fp, _fp, _i32, _i32, _i32, _i32, C.c_float, _fp]),
     "e2fgvi_mdcn_nhwc": (C.c_int, [C.POINTER(MdcnDesc), _fp]),
-    "e2fgvi_packed_dcn_weight_size": (_i64, [_i32, _i32, _i32, _i32]),
-    "e2fgvi_pack_dcn_weight": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, _fp]),
-    "e2fgvi_pack_dcn_weight_bf16": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, _fp]),
-    "e2fgvi_pack_dcn_weight_f16": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, _fp]),
-    "e2fgvi_pack_dcn_weight_x3": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, _fp]),
+    "e2fgvi_packed_dcn_weight_size": (_i64, [_i32, _i32, _i32, _i32, _i32]),
+    "e2fgvi_pack_dcn_weight": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _fp]),
     "e2fgvi_focal_attention": (C.c_int, [_fp, _fp, _fp, _i32, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _fp]),
     "e2fgvi_split3_kv": (C.c_int, [_fp, _fp, _i64, _fp]),
     "e2fgvi_focal_attention_x3": (C.c_int, [_fp, _fp, _fp, _i32, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _fp]),
-    "e2fgvi_nchw_to_nhwc": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, _f, _f, _fp]),
+    "e2fgvi_nchw_to_nhwc": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _f, _f, _fp]),
     "e2fgvi_nhwc_to_nchw": (C.c_int, [_fp, _i32, _fp, _i32, _i32, _i32, _i32, _fp]),
-    "e2fgvi_resize_bilinear": (C.c_int, [_fp, _i32, _i32, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _fp, _fp, _fp]),
+    "e2fgvi_resize_bilinear": (C.c_int, [_fp, _i32, _i32, _i32, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _fp, _fp, _fp]),
     "e2fgvi_avgpool2_nhwc": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _fp]),
-    "e2fgvi_spynet_level_input": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _i32, _i32, _i32, _fp]),
-    "e2fgvi_prop_cond": (C.c_int, [_fp, _i32, _fp, _i32, _fp, _fp, _i64, _fp, _fp, _i32, _i32, _i32, _i32, _fp]),
-    "e2fgvi_layernorm": (C.c_int, [_fp, _fp, _fp, _fp, _i64, _i32, _fp]),
-    "e2fgvi_window_pool": (C.c_int, [_fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _fp]),
-    "e2fgvi_ffn_fold": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _fp]),
-    "e2fgvi_ffn_unfold_gelu": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _fp]),
+    "e2fgvi_spynet_level_input": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _fp]),
+    "e2fgvi_prop_cond": (C.c_int, [_fp, _i32, _fp, _i32, _i32, _fp, _fp, _i64, _fp, _i32, _fp, _fp, _i32, _i32, _i32, _i32, _fp]),
+    "e2fgvi_layernorm": (C.c_int, [_fp, _fp, _fp, _fp, _i32, _i64, _i32, _fp]),
+    "e2fgvi_window_pool": (C.c_int, [_fp, _i32, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _fp]),
+    "e2fgvi_ffn_fold": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _fp]),
+    "e2fgvi_ffn_unfold": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _fp]),
     "e2fgvi_mask_prepare": (C.c_int, [_fp, _i32, _i32, _i32, _fp, _fp, _fp, _i32, _i32, _i32, _fp]),
     "e2fgvi_masked_clip": (C.c_int, [_fp, _fp, _fp, _i32, _i32, _i32, _fp, _i32, _i32, _fp]),
     "e2fgvi_composite": (C.c_int, [_fp, _fp, _fp, _i32, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _fp]),
@@ -137,25 +118,9 @@ SYMBOLS = {
     "e2fgvi_scatter_slabs": (C.c_int, [_fp, _fp, _i32, _i64, _fp, _i32, _fp]),
     "e2fgvi_psnr_ssim_workspace": (_i64, [_i32, _i32, _i32]),
     "e2fgvi_psnr_ssim": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _fp, _fp, _fp]),
-    "e2fgvi_softcomp_fold": (C.c_int, [_fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _fp]),
-    "e2fgvi_focal_attention_bf16": (C.c_int, [_fp, _fp, _fp, _i32, _fp, _fp, _i32, _i32, _i32, _i32, _fp]),
-    "e2fgvi_focal_attention_bf16_variant": (C.c_int, [C.c_int]),
-    "e2fgvi_focal_attention_f16": (C.c_int, [_fp, _fp, _fp, _i32, _fp, _fp, _i32, _i32, _i32, _i32, _fp]),
-    "e2fgvi_nchw_to_nhwc_x": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _f, _f, _fp]),
-    "e2fgvi_resize_bilinear_bf16": (C.c_int, [_fp, _i32, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _fp]),
-    "e2fgvi_resize_bilinear_f16": (C.c_int, [_fp, _i32, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _fp]),
-    "e2fgvi_prop_cond_x": (C.c_int, [_fp, _i32, _fp, _i32, _fp, _fp, _i64, _fp, _i32, _fp, _fp, _i32, _i32, _i32, _i32, _fp]),
-    "e2fgvi_prop_cond_xs": (C.c_int, [_fp, _i32, _fp, _i32, _i32, _fp, _fp, _i64, _fp, _i32, _fp, _fp, _i32, _i32, _i32, _i32, _fp]),
-    "e2fgvi_spynet_level_input_x": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _i32, _i32, _i32, _fp]),
-    "e2fgvi_spynet_level_input_x_f16": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _i32, _i32, _i32, _fp]),
-    "e2fgvi_layernorm_x": (C.c_int, [_fp, _fp, _fp, _fp, _i32, _i64, _i32, _fp]),
-    "e2fgvi_window_pool_x": (C.c_int, [_fp, _i32, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _fp]),
-    "e2fgvi_ffn_fold_x": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _fp]),
-    "e2fgvi_ffn_unfold_gelu_x": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _fp]),
-    "e2fgvi_ffn_fold_gelu_x": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _fp]),
-    "e2fgvi_ffn_unfold_x": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _fp]),
-    "e2fgvi_softcomp_fold_bf16": (C.c_int, [_fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _fp]),
-    "e2fgvi_softcomp_fold_f16": (C.c_int, [_fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _fp]),
+    "e2fgvi_softcomp_fold": (C.c_int, [_fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _fp]),
+    "e2fgvi_focal_attention_16": (C.c_int, [_fp, _fp, _fp, _i32, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _fp]),
+    "e2fgvi_focal_attention_16_variant": (C.c_int, [C.c_int]),
     "e2fgvi_cast": (C.c_int, [_fp, _i32, _fp, _i32, _i64, _fp]),
 }
 

@@ -679,14 +679,14 @@ class PackedConv:
 HALF16 = (torch.bfloat16, torch.float16)     # the two element types of the 16-bit data path
 
 
+_DT_CODE = {torch.float32: _L.DT_F32, torch.bfloat16: _L.DT_BF16, torch.float16: _L.DT_F16}      # the C ABI's element codes
+
+
 def _dt(t):
-    if t.dtype == torch.float32:
-        return _L.DT_F32
-    if t.dtype == torch.bfloat16:
-        return _L.DT_BF16
-    if t.dtype == torch.float16:
-        return _L.DT_F16
-    raise TypeError("tensor must be float32, bfloat16 or float16, got %s" % t.dtype)
+    try:
+        return _DT_CODE[t.dtype]
+    except KeyError:
+        raise TypeError("tensor must be float32, bfloat16 or float16, got %s" % t.dtype) from None
 
 
 def _dt_key(t):
@@ -711,7 +711,7 @@ class PackedConvX:
 
     dtype=torch.bfloat16 (default): the bf16 data path -- bf16 NHWC sources (virtual concat, channels per source in
     multiples of 8), bf16 packed weights, v_mfma_f32_32x32x16_bf16 with fp32 accumulation.
-    dtype=torch.float16: the same with fp16 sources / weights / 16-bit results on v_mfma_f32_32x32x16_f16 (e2fgvi_conv2d_f16x),
+    dtype=torch.float16: the same with fp16 sources / weights / 16-bit results on v_mfma_f32_32x32x16_f16 (mode E2FGVI_F16),
     same tiles; its tuning keys are the bf16 ones.
     dtype=torch.float32: the same kernel on fp32 operands (channels in multiples of 4, exact fp32 MFMA) -- the fp32 path's
     tuning alternative to PackedConv's register-staged implicit GEMM.
@@ -740,8 +740,9 @@ class PackedConvX:
         self.f16 = dtype == torch.float16
         if not self.f32 and dtype not in HALF16:
             raise TypeError("PackedConvX: dtype must be float32, bfloat16 or float16")
-        self._fn = ((lib.e2fgvi_conv2d_f32x3 if self.x3 else lib.e2fgvi_conv2d_f32x) if self.f32 else
-                    lib.e2fgvi_conv2d_f16x if self.f16 else lib.e2fgvi_conv2d_bf16x)
+        self._mode = mode = _L.DT_BF16X3 if self.x3 else _DT_CODE[dtype]      # the `mode` of e2fgvi_conv2d_x and of its packers
+        conv2d_x = lib.e2fgvi_conv2d_x
+        self._fn = lambda desc_ref, stream: conv2d_x(desc_ref, mode, stream)
         wdtype = torch.bfloat16 if self.x3 else dtype
         self.name = "conv"
         self.tune = False          # time XTUNE_CANDIDATES on the first call of every new size class and keep the fastest
@@ -749,7 +750,6 @@ class PackedConvX:
         self.alt3 = None
         self._w_raw = w if (self.f32 and not self.x3) else None
         self._taps_arg = taps
-        arr = (C.c_int32 * len(self.cpg))(*self.cpg)
         # narrow single-source layers (SPyNet's 7x7 stacks, the encoder's first layer): K-steps that carry several taps
         # (fp32 operands: only on request -- the one fp32 user is the FFN's second Linear as a conv, engine.py)
         self.taps = (len(self.cpg) == 1 and groups == 1 and self.cpg[0] <= 56 and self.KW > 1
@@ -774,33 +774,14 @@ class PackedConvX:
         lib = _L.load()
         wdtype = self._wdtype
         arr = (C.c_int32 * len(self.cpg))(*self.cpg)
-        if self.taps:
-            size_fn = ((lib.e2fgvi_packed_conv_weight_f32x3_taps_size if self.x3 else lib.e2fgvi_packed_conv_weight_f32x_taps_size)
-                       if self.f32 else lib.e2fgvi_packed_conv_weight_f16x_taps_size if self.f16
-                       else lib.e2fgvi_packed_conv_weight_bf16x_taps_size)
-            pack_fn = ((lib.e2fgvi_pack_conv_weight_f32x3_taps if self.x3 else lib.e2fgvi_pack_conv_weight_f32x_taps)
-                       if self.f32 else lib.e2fgvi_pack_conv_weight_f16x_taps if self.f16 else lib.e2fgvi_pack_conv_weight_bf16x_taps)
-            n = size_fn(self.Cout, self.KH, self.KW, self.cpg[0])
-            if n < 0:
-                _L.check(int(n), "packed_conv_weight_x_taps_size")
-            if dry:
-                return None
-            t = torch.empty(int(n), dtype=wdtype, device=w.device)
-            _L.check(pack_fn(_ptr(w), _ptr(t), self.Cout, self.KH, self.KW, self.cpg[0], _stream()),
-                     "pack_conv_weight_x_taps")
-        else:
-            size_fn = ((lib.e2fgvi_packed_conv_weight_f32x3_size if self.x3 else lib.e2fgvi_packed_conv_weight_f32x_size)
-                       if self.f32 else lib.e2fgvi_packed_conv_weight_f16x_size if self.f16 else lib.e2fgvi_packed_conv_weight_bf16x_size)
-            pack_fn = ((lib.e2fgvi_pack_conv_weight_f32x3 if self.x3 else lib.e2fgvi_pack_conv_weight_f32x)
-                       if self.f32 else lib.e2fgvi_pack_conv_weight_f16x if self.f16 else lib.e2fgvi_pack_conv_weight_bf16x)
-            n = size_fn(self.Cout, self.groups, self.KH, self.KW, len(self.cpg), arr)
-            if n < 0:
-                _L.check(int(n), "packed_conv_weight_x_size")
-            if dry:
-                return None
-            t = torch.empty(int(n), dtype=wdtype, device=w.device)
-            _L.check(pack_fn(_ptr(w), _ptr(t), self.Cout, self.groups, self.KH, self.KW, len(self.cpg), arr, _stream()),
-                     "pack_conv_weight_x")
+        geom = (self._mode, int(self.taps), self.Cout, self.groups, self.KH, self.KW, len(self.cpg), arr)
+        n = lib.e2fgvi_packed_conv_weight_x_size(*geom)
+        if n < 0:
+            _L.check(int(n), "packed_conv_weight_x_size")
+        if dry:
+            return None
+        t = torch.empty(int(n), dtype=wdtype, device=w.device)
+        _L.check(lib.e2fgvi_pack_conv_weight_x(_ptr(w), _ptr(t), *geom, _stream()), "pack_conv_weight_x")
         return t
 
     def out_hw(self, H, W):
@@ -1128,6 +1109,11 @@ class PackedTailConv:
 
 
 # ------------------------------------------------------------------------------------------ deformable conv
+# PackedDcn(mfma=...) -> (mfma_dtype of the C ABI, element type of the packed weights)
+_DCN_PACKING = {"fp32": (_L.DT_F32, torch.float32), "bf16": (_L.DT_BF16, torch.bfloat16), "fp16": (_L.DT_F16, torch.float16),
+                "x3": (_L.DT_BF16X3, torch.bfloat16)}
+
+
 class PackedDcn:
     def __init__(self, weight, bias, deform_groups, stride=1, pad=0, dil=1, mfma="fp32"):
         """mfma="bf16": the sampled columns and the weights are rounded to bf16 for the MFMA (bf16 data path); the gather,
@@ -1135,7 +1121,7 @@ class PackedDcn:
         mfma="x3": the fp32 layer on the bf16 matrix pipe -- blended values and weights split exactly into three bf16 pieces,
         six bf16 MFMA terms per product (fp32-level rounding; fp32 sources)."""
         lib = _L.load()
-        if mfma not in ("fp32", "bf16", "fp16", "x3"):
+        if mfma not in _DCN_PACKING:
             raise ValueError("mfma must be 'fp32', 'bf16', 'fp16' or 'x3'")
         self.mfma_bf16 = mfma == "bf16"
         self.mfma_f16 = mfma == "fp16"            # the same on fp16 (fp16 sources, products and 16-bit result)
@@ -1143,25 +1129,13 @@ class PackedDcn:
         w = _chk(weight.detach().float().contiguous(), "weight")
         self.Cout, self.C, self.KH, self.KW = w.shape
         self.dg, self.stride, self.pad, self.dil = deform_groups, stride, pad, dil
-        n = lib.e2fgvi_packed_dcn_weight_size(self.Cout, self.C, self.KH, self.KW)
+        code, wdtype = _DCN_PACKING[mfma]
+        n = lib.e2fgvi_packed_dcn_weight_size(code, self.Cout, self.C, self.KH, self.KW)
         if n < 0:
             _L.check(int(n), "packed_dcn_weight_size")
-        if self.mfma_x3:
-            self.wpacked = torch.empty(3 * int(n), dtype=torch.bfloat16, device=w.device)
-            _L.check(lib.e2fgvi_pack_dcn_weight_x3(_ptr(w), _ptr(self.wpacked), self.Cout, self.C, self.KH, self.KW,
-                                                   deform_groups, _stream()), "pack_dcn_weight_x3")
-        elif self.mfma_bf16:
-            self.wpacked = torch.empty(int(n), dtype=torch.bfloat16, device=w.device)
-            _L.check(lib.e2fgvi_pack_dcn_weight_bf16(_ptr(w), _ptr(self.wpacked), self.Cout, self.C, self.KH, self.KW,
-                                                     deform_groups, _stream()), "pack_dcn_weight_bf16")
-        elif self.mfma_f16:
-            self.wpacked = torch.empty(int(n), dtype=torch.float16, device=w.device)
-            _L.check(lib.e2fgvi_pack_dcn_weight_f16(_ptr(w), _ptr(self.wpacked), self.Cout, self.C, self.KH, self.KW,
-                                                    deform_groups, _stream()), "pack_dcn_weight_f16")
-        else:
-            self.wpacked = torch.empty(int(n), dtype=torch.float32, device=w.device)
-            _L.check(lib.e2fgvi_pack_dcn_weight(_ptr(w), _ptr(self.wpacked), self.Cout, self.C, self.KH, self.KW,
-                                                deform_groups, _stream()), "pack_dcn_weight")
+        self.wpacked = torch.empty(int(n), dtype=wdtype, device=w.device)
+        _L.check(lib.e2fgvi_pack_dcn_weight(_ptr(w), _ptr(self.wpacked), code, self.Cout, self.C, self.KH, self.KW,
+                                            deform_groups, _stream()), "pack_dcn_weight")
         self.bias = None if bias is None else _chk(bias.detach().float().contiguous(), "bias")
         self.name = "dcn"
 
@@ -1324,15 +1298,15 @@ def attention_x3_applies(B, T, fh, fw):
 
 def focal_attention_bf16(qkv, kv_pool, key_tab, nkeys, B, T, fh, fw, out=None, variant=None):
     """16-bit data path: qkv [rows,1536] / kv_pool [B*T*nWin,1536] / out [rows,512] are bf16 -- or all fp16
-    (e2fgvi_focal_attention_f16: the same kernels on fp16 MFMA).
-    variant (tests / A-B measurements): kernel variant for this call (see e2fgvi_focal_attention_bf16_variant)"""
+    (the same kernels on fp16 MFMA).
+    variant (tests / A-B measurements): kernel variant for this call (see e2fgvi_focal_attention_16_variant)"""
     lib = _L.load()
     if variant is not None:
-        prev = lib.e2fgvi_focal_attention_bf16_variant(int(variant))
+        prev = lib.e2fgvi_focal_attention_16_variant(int(variant))
         try:
             return focal_attention_bf16(qkv, kv_pool, key_tab, nkeys, B, T, fh, fw, out=out)
         finally:
-            lib.e2fgvi_focal_attention_bf16_variant(prev)
+            lib.e2fgvi_focal_attention_16_variant(prev)
     dt = qkv.dtype if isinstance(qkv, torch.Tensor) and qkv.dtype == torch.float16 else torch.bfloat16
     _chk(qkv, "qkv", dt); _chk(kv_pool, "kv_pool", dt)
     _chk(key_tab, "key_tab", torch.int32); _chk(nkeys, "nkeys", torch.int32)
@@ -1352,8 +1326,8 @@ def focal_attention_bf16(qkv, kv_pool, key_tab, nkeys, B, T, fh, fw, out=None, v
         iss = B * 4 * qpad * 128 * 2 * sum(-(-(T * k) // 32) * 32 for k in nkl)
         _L.annotate(layer="attention", kernel="focal_attn_f16" if dt == torch.float16 else "focal_attn_bf16",
                     shape="B%d T%d grid %dx%d" % (B, T, fh, fw), macs=alg, issued=iss)
-    fn = lib.e2fgvi_focal_attention_f16 if dt == torch.float16 else lib.e2fgvi_focal_attention_bf16
-    _L.check(fn(_ptr(qkv), _ptr(kv_pool), _ptr(key_tab), key_tab.shape[1], _ptr(nkeys), _ptr(out), B, T, fh, fw, _stream()),
+    _L.check(lib.e2fgvi_focal_attention_16(_ptr(qkv), _ptr(kv_pool), _ptr(key_tab), key_tab.shape[1], _ptr(nkeys), _ptr(out),
+                                           _dt(qkv), B, T, fh, fw, _stream()),
              "focal_attention_f16" if dt == torch.float16 else "focal_attention_bf16")
     return out
 
@@ -1365,7 +1339,7 @@ def nchw_to_nhwc(x, ld=None, scale=1.0, shift=0.0, out_dtype=torch.float32):
     N, Cc, H, W = x.shape
     ld = Cc if ld is None else ld
     out = torch.empty((N, H, W, ld), dtype=out_dtype, device=x.device)
-    _L.check(lib.e2fgvi_nchw_to_nhwc_x(_ptr(x), _ptr(out), _dt(out), N, Cc, H, W, ld, scale, shift, _stream()), "nchw_to_nhwc")
+    _L.check(lib.e2fgvi_nchw_to_nhwc(_ptr(x), _ptr(out), _dt(out), N, Cc, H, W, ld, scale, shift, _stream()), "nchw_to_nhwc")
     return out
 
 
@@ -1397,9 +1371,8 @@ def resize_bilinear(x, out_hw, align_corners, src_nchw=False, channels=None, out
             raise ValueError("16-bit resize: plain NHWC -> NHWC only")
         N, H, W, Cc = x.shape
         out = torch.empty((N, out_hw[0], out_hw[1], Cc), dtype=x.dtype, device=x.device)
-        fn = lib.e2fgvi_resize_bilinear_f16 if x.dtype == torch.float16 else lib.e2fgvi_resize_bilinear_bf16
-        _L.check(fn(_ptr(x), Cc, _ptr(out), Cc, N, Cc, H, W, out_hw[0], out_hw[1], int(align_corners), _stream()),
-                 "resize_bilinear_16")
+        _L.check(lib.e2fgvi_resize_bilinear(_ptr(x), _dt(x), 0, Cc, _ptr(out), Cc, N, Cc, H, W, out_hw[0], out_hw[1],
+                                            int(align_corners), None, None, _stream()), "resize_bilinear_16")
         return out
     _chk(x, "x")
     if src_nchw:
@@ -1419,7 +1392,7 @@ def resize_bilinear(x, out_hw, align_corners, src_nchw=False, channels=None, out
             _chk(v, nm)
             if v.numel() < Cc:
                 raise ValueError("%s needs %d entries" % (nm, Cc))
-    _L.check(lib.e2fgvi_resize_bilinear(_ptr(x), int(src_nchw), src_ld, _ptr(out), out_ld, N, Cc, H, W, Ho, Wo,
+    _L.check(lib.e2fgvi_resize_bilinear(_ptr(x), _L.DT_F32, int(src_nchw), src_ld, _ptr(out), out_ld, N, Cc, H, W, Ho, Wo,
                                         int(align_corners), _ptr(scale), _ptr(shift), _stream()), "resize_bilinear")
     return out
 
@@ -1449,10 +1422,9 @@ def spynet_level_input(pyr, ref_idx, supp_idx, flow_prev, copy_dtype=None):
     out = empty_nhwc(Np, h, w, 8, pyr.device)
     if copy_dtype not in (None,) + HALF16:
         raise TypeError("copy_dtype must be None, torch.bfloat16 or torch.float16")
-    f16 = copy_dtype == torch.float16
     out16 = torch.empty((Np, h, w, 8), dtype=copy_dtype, device=pyr.device) if copy_dtype is not None else None
-    fn = lib.e2fgvi_spynet_level_input_x_f16 if f16 else lib.e2fgvi_spynet_level_input_x
-    _L.check(fn(_ptr(pyr), _ptr(ref_idx), _ptr(supp_idx), _ptr(flow_prev), _ptr(out), _ptr(out16), Np, h, w, _stream()),
+    _L.check(lib.e2fgvi_spynet_level_input(_ptr(pyr), _ptr(ref_idx), _ptr(supp_idx), _ptr(flow_prev), _ptr(out), _ptr(out16),
+                                           _dt(out16) if out16 is not None else _L.DT_F32, Np, h, w, _stream()),
              "spynet_level_input")
     return (out, out16) if copy_dtype is not None else out
 
@@ -1476,10 +1448,10 @@ def prop_cond(feat_prop, feat_n2, flow_a, flow_b, flow_img_stride, cond=None, fl
     if flow_b is not None:
         _chk(feat_n2, "feat_n2", feat_prop.dtype)
         f2_ld = feat_n2.shape[3]
-    _L.check(lib.e2fgvi_prop_cond_xs(_ptr(feat_prop), Cc, _ptr(feat_n2) if flow_b is not None else None, f2_ld, _dt(feat_prop),
-                                    C.c_void_p(flow_a.data_ptr()),
-                                    C.c_void_p(flow_b.data_ptr()) if flow_b is not None else None,
-                                    flow_img_stride, _ptr(cond), _dt(cond), _ptr(flows), _ptr(fl8), N, H, W, Cc, _stream()),
+    _L.check(lib.e2fgvi_prop_cond(_ptr(feat_prop), Cc, _ptr(feat_n2) if flow_b is not None else None, f2_ld, _dt(feat_prop),
+                                  C.c_void_p(flow_a.data_ptr()),
+                                  C.c_void_p(flow_b.data_ptr()) if flow_b is not None else None,
+                                  flow_img_stride, _ptr(cond), _dt(cond), _ptr(flows), _ptr(fl8), N, H, W, Cc, _stream()),
              "prop_cond")
     return (cond, flows, fl8) if flows8 else (cond, flows)
 
@@ -1492,7 +1464,7 @@ def layernorm(x, gamma, beta, out=None, out_dtype=torch.float32):
     if out is None:
         out = torch.empty(x.shape, dtype=out_dtype, device=x.device)
     _chk_any(out, "out")
-    _L.check(lib.e2fgvi_layernorm_x(_ptr(x), _ptr(gamma), _ptr(beta), _ptr(out), _dt(out), rows, Cc, _stream()), "layernorm")
+    _L.check(lib.e2fgvi_layernorm(_ptr(x), _ptr(gamma), _ptr(beta), _ptr(out), _dt(out), rows, Cc, _stream()), "layernorm")
     return out
 
 
@@ -1505,7 +1477,7 @@ def window_pool(x, w45, bias1, BT, fh, fw, out=None):
         out = torch.empty((rows, Cc), dtype=x.dtype, device=x.device)
     elif tuple(_chk(out, "out", x.dtype).shape) != (rows, Cc):
         raise ValueError("window_pool out must be [%d,%d]" % (rows, Cc))
-    _L.check(lib.e2fgvi_window_pool_x(_ptr(x), _dt(x), _ptr(w45), _ptr(bias1), _ptr(out), BT, fh, fw, Cc, _stream()), "window_pool")
+    _L.check(lib.e2fgvi_window_pool(_ptr(x), _dt(x), _ptr(w45), _ptr(bias1), _ptr(out), BT, fh, fw, Cc, _stream()), "window_pool")
     return out
 
 
@@ -1513,7 +1485,7 @@ def ffn_fold(hid, F_, fh, fw, H, W, Cc):
     lib = _L.load()
     _chk_any(hid, "hid")
     out = torch.empty((F_, H, W, Cc), dtype=hid.dtype, device=hid.device)
-    _L.check(lib.e2fgvi_ffn_fold_x(_ptr(hid), _ptr(out), _dt(hid), F_, fh, fw, H, W, Cc, _stream()), "ffn_fold")
+    _L.check(lib.e2fgvi_ffn_fold(_ptr(hid), _ptr(out), _dt(hid), 0, F_, fh, fw, H, W, Cc, _stream()), "ffn_fold")
     return out
 
 
@@ -1536,7 +1508,7 @@ def ffn_unfold_gelu(folded, fh, fw, out=None):
     if out is None:
         out = torch.empty((F_ * fh * fw, 49 * Cc), dtype=folded.dtype, device=folded.device)
     _chk(out, "out", folded.dtype)
-    _L.check(lib.e2fgvi_ffn_unfold_gelu_x(_ptr(folded), _ptr(out), _dt(folded), F_, fh, fw, H, W, Cc, _stream()), "ffn_unfold_gelu")
+    _L.check(lib.e2fgvi_ffn_unfold(_ptr(folded), _ptr(out), _dt(folded), 1, F_, fh, fw, H, W, Cc, _stream()), "ffn_unfold_gelu")
     return out
 
 
@@ -1545,7 +1517,7 @@ def ffn_fold_gelu(hid, F_, fh, fw, H, W, Cc):
     lib = _L.load()
     _chk_any(hid, "hid")
     out = torch.empty((F_, H, W, Cc), dtype=hid.dtype, device=hid.device)
-    _L.check(lib.e2fgvi_ffn_fold_gelu_x(_ptr(hid), _ptr(out), _dt(hid), F_, fh, fw, H, W, Cc, _stream()), "ffn_fold_gelu")
+    _L.check(lib.e2fgvi_ffn_fold(_ptr(hid), _ptr(out), _dt(hid), 1, F_, fh, fw, H, W, Cc, _stream()), "ffn_fold_gelu")
     return out
 
 
@@ -1556,29 +1528,21 @@ def ffn_unfold(folded, fh, fw, out=None):
     if out is None:
         out = torch.empty((F_ * fh * fw, 49 * Cc), dtype=folded.dtype, device=folded.device)
     _chk(out, "out", folded.dtype)
-    _L.check(lib.e2fgvi_ffn_unfold_x(_ptr(folded), _ptr(out), _dt(folded), F_, fh, fw, H, W, Cc, _stream()), "ffn_unfold")
+    _L.check(lib.e2fgvi_ffn_unfold(_ptr(folded), _ptr(out), _dt(folded), 0, F_, fh, fw, H, W, Cc, _stream()), "ffn_unfold")
     return out
 
 
 def softcomp_fold(emb, F_, fh, fw, H, W, Cc, bias_hwc=None, residual=None):
+    """emb, residual and the result share one element type (fp32, or bf16 / fp16 on the 16-bit data path); bias_hwc is fp32"""
     lib = _L.load()
-    if isinstance(emb, torch.Tensor) and emb.dtype in HALF16:            # 16-bit data path: emb, residual, result 16-bit
-        _chk(emb, "emb", emb.dtype)
-        out = torch.empty((F_, H, W, Cc), dtype=emb.dtype, device=emb.device)
-        if bias_hwc is not None:
-            _chk(bias_hwc, "bias_hwc")
-        if residual is not None:
-            _chk(residual, "residual", emb.dtype)
-        fn = lib.e2fgvi_softcomp_fold_f16 if emb.dtype == torch.float16 else lib.e2fgvi_softcomp_fold_bf16
-        _L.check(fn(_ptr(emb), _ptr(bias_hwc), _ptr(residual), _ptr(out), F_, fh, fw, H, W, Cc, _stream()), "softcomp_fold_16")
-        return out
-    _chk(emb, "emb")
-    out = empty_nhwc(F_, H, W, Cc, emb.device)
+    dt = emb.dtype if isinstance(emb, torch.Tensor) and emb.dtype in HALF16 else torch.float32
+    _chk(emb, "emb", dt)
+    out = torch.empty((F_, H, W, Cc), dtype=dt, device=emb.device)
     if bias_hwc is not None:
         _chk(bias_hwc, "bias_hwc")
     if residual is not None:
-        _chk(residual, "residual")
-    _L.check(lib.e2fgvi_softcomp_fold(_ptr(emb), _ptr(bias_hwc), _ptr(residual), _ptr(out), F_, fh, fw, H, W, Cc,
+        _chk(residual, "residual", dt)
+    _L.check(lib.e2fgvi_softcomp_fold(_ptr(emb), _ptr(bias_hwc), _ptr(residual), _ptr(out), _dt(out), F_, fh, fw, H, W, Cc,
                                       _stream()), "softcomp_fold")
     return out
 

@@ -92,11 +92,14 @@ int e2fgvi_psnr_ssim(const float* img1, const float* img2, int32_t N, int32_t H,
 /* element types of the tensors of the 16-bit data path (see the end of this header) */
 #define E2FGVI_F32 0
 #define E2FGVI_BF16 1
-#define E2FGVI_BF16X3 2      /* mdcn mfma_dtype (ABI 7): fp32 sources and results, the MFMA operands as three bf16 pieces each, six exact terms per product */
+#define E2FGVI_BF16X3 2      /* not a storage type: fp32 sources and results, the MFMA operands as three bf16 pieces each, six exact terms
+                              * per product (mfma_dtype of the deformable conv, mode of e2fgvi_conv2d_x and of the weight packers) */
 #define E2FGVI_F16 3         /* IEEE half: accepted wherever E2FGVI_BF16 names a storage type (dst / res / src / mfma / tail / helper
                               * dtypes, e2fgvi_cast); fp32 -> fp16 rounds to nearest even, +-inf past 65504, subnormals kept */
 
 const char* e2fgvi_last_error(void);
+/* 9.  Version 9 consolidated the per-type entry points of versions 2-8 (suffixes _x, _xs, _bf16, _f16, _f32x, _f32x3, _taps): one
+ * entry point per operation, the element type an E2FGVI_* argument. */
 int e2fgvi_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -207,38 +210,31 @@ typedef struct {
     const float* mask;   int32_t mask_ld;
     const float* flows;                /* optional [P,4]                                           */
     float max_residue;
-    const float* wpacked;              /* e2fgvi_pack_dcn_weight                                   */
+    const float* wpacked;              /* e2fgvi_pack_dcn_weight for mfma_dtype (of its type)      */
     const float* bias;
     float* dst; int32_t dst_ld, dst_coff;
     int32_t tile;
-    int32_t dst_dtype;                 /* E2FGVI_F32 (0, default) or E2FGVI_BF16: dst is a bf16 NHWC tensor        */
-    int32_t mfma_dtype;                /* E2FGVI_F32 (0, default): fp32 MFMA, wpacked from e2fgvi_pack_dcn_weight;
-                                          E2FGVI_BF16: the sampled slab is rounded to bf16 and multiplied on bf16 MFMA
-                                          (fp32 gather / blend / accumulation), wpacked from e2fgvi_pack_dcn_weight_bf16 */
-    int32_t src_dtype;                 /* E2FGVI_F32 (0, default); E2FGVI_BF16 (needs mfma_dtype = E2FGVI_BF16): the sources
-                                          are bf16 NHWC (src_ld multiple of 8): half the gather fetches                 */
-    int32_t src_planar;                /* 1 (ABI version 4; bf16 sources, 16 channels per deform group): source s is laid out
+    int32_t dst_dtype;                 /* E2FGVI_F32 (0, default) or E2FGVI_BF16 / E2FGVI_F16: dst is a 16-bit NHWC tensor */
+    int32_t mfma_dtype;                /* the type wpacked was packed for.  E2FGVI_F32 (0, default): fp32 MFMA;
+                                          E2FGVI_BF16 / E2FGVI_F16: the sampled slab is rounded to 16 bits and multiplied on
+                                          bf16 / fp16 MFMA (fp32 gather / blend / accumulation; E2FGVI_F16 needs src_dtype =
+                                          E2FGVI_F16 and dst_dtype E2FGVI_F32 or E2FGVI_F16); E2FGVI_BF16X3: fp32 sources and
+                                          results, blended values and weights as three bf16 pieces, six exact terms per product */
+    int32_t src_dtype;                 /* E2FGVI_F32 (0, default); E2FGVI_BF16 / E2FGVI_F16 (with the same mfma_dtype): the
+                                          sources are 16-bit NHWC (src_ld multiple of 8): half the gather fetches           */
+    int32_t src_planar;                /* 1 (16-bit sources, 16 channels per deform group): source s is laid out
                                           [src_c[s] / 16 groups][N*H*W pixels][16 channels] (e2fgvi_nhwc_to_planar16) instead
                                           of NHWC -- the 32-byte runs of neighbouring pixels of one group are then adjacent in
                                           memory, so the corner fetches of neighbouring output pixels share cache lines       */
 } e2fgvi_mdcn_desc;
 
 int e2fgvi_mdcn_nhwc(const e2fgvi_mdcn_desc* d, void* stream);
-int64_t e2fgvi_packed_dcn_weight_size(int32_t Cout, int32_t C, int32_t KH, int32_t KW);
-/* w: [Cout, C, KH, KW] */
-int e2fgvi_pack_dcn_weight(const float* w, float* wpacked, int32_t Cout, int32_t C, int32_t KH,
-                           int32_t KW, int32_t deform_groups, void* stream);
-/* split-operand packing (3 x e2fgvi_packed_dcn_weight_size elements of 2 bytes: three bf16 planes whose sum is the fp32 weight)
- * for mfma_dtype = E2FGVI_BF16X3 -- the fp32 deformable conv (feat_prop.py:55-58) on the bf16 matrix pipe, fp32-level rounding */
-int e2fgvi_pack_dcn_weight_x3(const float* w, void* wpacked, int32_t Cout, int32_t C, int32_t KH, int32_t KW,
-                              int32_t deform_groups, void* stream);
-/* bf16 packing (e2fgvi_packed_dcn_weight_size elements of 2 bytes) for mfma_dtype = E2FGVI_BF16 */
-int e2fgvi_pack_dcn_weight_bf16(const float* w, void* wpacked, int32_t Cout, int32_t C, int32_t KH,
-                                int32_t KW, int32_t deform_groups, void* stream);
-/* ... and the fp16 packing for mfma_dtype = E2FGVI_F16 (then src_dtype must be E2FGVI_F16 -- fp16 products take fp16 sources --
- * and dst_dtype is E2FGVI_F32 or E2FGVI_F16) */
-int e2fgvi_pack_dcn_weight_f16(const float* w, void* wpacked, int32_t Cout, int32_t C, int32_t KH,
-                               int32_t KW, int32_t deform_groups, void* stream);
+/* elements of the packing for mfma_dtype: one per weight slot (4 bytes for E2FGVI_F32, 2 for E2FGVI_BF16 / E2FGVI_F16, the same
+ * count for all three), three bf16 planes whose sum is the fp32 weight for E2FGVI_BF16X3 (3 x that count) */
+int64_t e2fgvi_packed_dcn_weight_size(int32_t mfma_dtype, int32_t Cout, int32_t C, int32_t KH, int32_t KW);
+/* w: fp32 [Cout, C, KH, KW] */
+int e2fgvi_pack_dcn_weight(const float* w, void* wpacked, int32_t mfma_dtype, int32_t Cout, int32_t C, int32_t KH, int32_t KW,
+                           int32_t deform_groups, void* stream);
 
 /* 16-bit NHWC [P pixels][C] (C a multiple of 16) -> [C / 16][P][16]: the deformable conv's planar source layout (src_planar) */
 int e2fgvi_nhwc_to_planar16(const void* src, void* dst, int64_t P, int32_t C, void* stream);
@@ -263,8 +259,9 @@ int e2fgvi_focal_attention(const float* qkv, const float* kv_pool, const int32_t
 /* ------------------------------------------------------------------------------------------------
  * Small HBM-bound kernels
  * ---------------------------------------------------------------------------------------------- */
-/* [N,C,H,W] -> NHWC with pixel stride ld (channels C..ld-1 zero-filled); y = x*scale + shift */
-int e2fgvi_nchw_to_nhwc(const float* src, float* dst, int32_t N, int32_t C, int32_t H, int32_t W,
+/* Tensors marked `void*` are fp32, bf16 or fp16 as the dtype argument beside them says; all arithmetic is fp32. */
+/* fp32 [N,C,H,W] -> NHWC of dst_dtype with pixel stride ld (channels C..ld-1 zero-filled); y = x*scale + shift */
+int e2fgvi_nchw_to_nhwc(const float* src, void* dst, int32_t dst_dtype, int32_t N, int32_t C, int32_t H, int32_t W,
                         int32_t ld, float scale, float shift, void* stream);
 int e2fgvi_nhwc_to_nchw(const float* src, int32_t ld, float* dst, int32_t N, int32_t C, int32_t H,
                         int32_t W, void* stream);
@@ -272,8 +269,9 @@ int e2fgvi_nhwc_to_nchw(const float* src, int32_t ld, float* dst, int32_t N, int
 /* Bilinear resize (torch F.interpolate semantics, align_corners 0/1), NHWC or NCHW source ->
  * NHWC destination, followed by a per-channel affine y = v*scale[c] + shift[c] (scale/shift may be
  * NULL).  Replaces e2fgvi.py:214-219 (1/4 downsample), flow_comp.py:150-167 (SPyNet resizes and
- * flow rescale), :121-124 (flow x2) and e2fgvi.py:126-129 (decoder x2). */
-int e2fgvi_resize_bilinear(const float* src, int32_t src_nchw, int32_t src_ld, float* dst,
+ * flow rescale), :121-124 (flow x2) and e2fgvi.py:126-129 (decoder x2).  src and dst are of dtype; the 16-bit types take
+ * NHWC sources with channels and strides in multiples of 8 and no affine (E2FGVI_EUNSUP with src_nchw, scale or shift). */
+int e2fgvi_resize_bilinear(const void* src, int32_t dtype, int32_t src_nchw, int32_t src_ld, void* dst,
                            int32_t dst_ld, int32_t N, int32_t C, int32_t H, int32_t W, int32_t Ho,
                            int32_t Wo, int32_t align_corners, const float* scale,
                            const float* shift, void* stream);
@@ -285,52 +283,75 @@ int e2fgvi_avgpool2_nhwc(const float* src, float* dst, int32_t N, int32_t H, int
 /* SPyNet level input (flow_comp.py:117-132): for pair n, out[n,y,x,0:8] =
  * [ref(3), warp_border(supp, flow_up)(3), flow_up(2)], flow_up = 2 * up2x_align_corners(flow_prev)
  * (zeros when flow_prev == NULL).  pyr: [F,h,w,4] per-frame pyramid level; ref_idx/supp_idx: [Np]
- * frame indices; flow_prev: [Np,h/2,w/2,2]. */
+ * frame indices; flow_prev: [Np,h/2,w/2,2].  out16 (optional, NULL = none): the 8 channels again as [Np,h,w,8] of out16_dtype
+ * (E2FGVI_BF16 / E2FGVI_F16), the source of the level's 16-bit conv stack. */
 int e2fgvi_spynet_level_input(const float* pyr, const int32_t* ref_idx, const int32_t* supp_idx,
-                              const float* flow_prev, float* out, int32_t Np, int32_t h, int32_t w,
-                              void* stream);
+                              const float* flow_prev, float* out, void* out16, int32_t out16_dtype, int32_t Np,
+                              int32_t h, int32_t w, void* stream);
 
 /* Propagation step conditions (feat_prop.py:110-123): given feat_prop, feat_n2 [N,H,W,C] and the
  * flow fields flow_a (=flows[:,i-1]) and flow_b (=flows[:,i-2] or NULL), all NHWC, writes
  *   cond  [N,H,W,2C] = warp0(feat_prop, flow_n1) | warp0(feat_n2, flow_n2)   (zeros padding)
  *   flows [N,H,W,4]  = flow_n1 | flow_n2,  flow_n2 = flow_n1 + warp0(flow_b, flow_n1) (0 if NULL)
- * Each of the N images has its own flow image: flow_x + n*flow_img_stride. */
-int e2fgvi_prop_cond(const float* feat_prop, int32_t fp_ld, const float* feat_n2, int32_t f2_ld,
-                     const float* flow_a, const float* flow_b, int64_t flow_img_stride,
-                     float* cond, float* flows, int32_t N, int32_t H, int32_t W, int32_t C,
-                     void* stream);
+ * Each of the N images has its own flow image: flow_x + n*flow_img_stride.
+ * The warp sources are of src_dtype: E2FGVI_F32 (cond of any cond_dtype) or E2FGVI_BF16 / E2FGVI_F16 (16-bit NHWC features, a cond
+ * of the same type: half the gather bytes).  flows8_bf16 (optional): the [P,4] flows again as a 16-bit [P,8] conv source
+ * (channels 4..7 zero) of the cond's type (bf16 beside an fp32 cond). */
+int e2fgvi_prop_cond(const void* feat_prop, int32_t fp_ld, const void* feat_n2, int32_t f2_ld, int32_t src_dtype,
+                     const float* flow_a, const float* flow_b, int64_t flow_img_stride, void* cond, int32_t cond_dtype,
+                     float* flows, void* flows8_bf16, int32_t N, int32_t H, int32_t W, int32_t C, void* stream);
 
-/* LayerNorm over the last dim (C multiple of 64, eps 1e-5, biased variance); tfocal_transformer.py
- * :452,463,470,533 */
-int e2fgvi_layernorm(const float* x, const float* gamma, const float* beta, float* y, int64_t rows,
+/* LayerNorm over the last dim (C = 256, 512, 768 or 1024, eps 1e-5, biased variance) of fp32 rows, y of y_dtype;
+ * tfocal_transformer.py:452,463,470,533 */
+int e2fgvi_layernorm(const float* x, const float* gamma, const float* beta, void* y, int32_t y_dtype, int64_t rows,
                      int32_t C, void* stream);
 
 /* Window pooling Linear(45->1) (tfocal_transformer.py:508-516): x [B*T,fh,fw,C] tokens ->
- * pooled [B*T, fh/5, fw/9, C] */
-int e2fgvi_window_pool(const float* x, const float* w45, const float* bias1, float* pooled,
+ * pooled [B*T, fh/5, fw/9, C], both of dtype */
+int e2fgvi_window_pool(const void* x, int32_t dtype, const float* w45, const float* bias1, void* pooled,
                        int32_t BT, int32_t fh, int32_t fw, int32_t C, void* stream);
 
-/* FusionFeedForward middle (tfocal_transformer.py:92-97): hid [F*fh*fw, C*49] ->
- * fold(7,3,3) / overlap count -> folded [F,H,W,C];  then unfold + exact GELU -> [F*fh*fw, C*49] */
-int e2fgvi_ffn_fold(const float* hid, float* folded, int32_t F, int32_t fh, int32_t fw, int32_t H,
+/* FusionFeedForward middle (tfocal_transformer.py:82,92-97), all tensors of dtype: hid [F*fh*fw, C*49] ->
+ * fold(7,3,3) / overlap count -> folded [F,H,W,C];  then unfold -> [F*fh*fw, C*49].  `gelu` says which of the two applies the
+ * exact GELU: e2fgvi_ffn_fold(gelu = 0) + e2fgvi_ffn_unfold(gelu = 1) is the reference's order; fold(gelu = 1) + unfold(gelu = 0)
+ * puts the GELU in front of the unfold (a gather with zero padding commutes with GELU, GELU(0) = 0): 5.4x fewer erf evaluations.
+ * fp32: bit-identical either way; 16-bit: with the second order GELU sees the unrounded fold. */
+int e2fgvi_ffn_fold(const void* hid, void* folded, int32_t dtype, int32_t gelu, int32_t F, int32_t fh, int32_t fw, int32_t H,
                     int32_t W, int32_t C, void* stream);
-int e2fgvi_ffn_unfold_gelu(const float* folded, float* out, int32_t F, int32_t fh, int32_t fw,
-                           int32_t H, int32_t W, int32_t C, void* stream);
+int e2fgvi_ffn_unfold(const void* folded, void* out, int32_t dtype, int32_t gelu, int32_t F, int32_t fh, int32_t fw,
+                      int32_t H, int32_t W, int32_t C, void* stream);
 
 /* SoftComp fold (tfocal_transformer.py:70-71): emb [F*fh*fw, C*49] -> overlap-ADD fold ->
- * [F,H,W,C] + bias_hwc[H,W,C] (optional) + residual (optional, NHWC ld = C) */
-int e2fgvi_softcomp_fold(const float* emb, const float* bias_hwc, const float* residual,
-                         float* dst, int32_t F, int32_t fh, int32_t fw, int32_t H, int32_t W,
+ * [F,H,W,C] + bias_hwc[H,W,C] (optional, fp32) + residual (optional, NHWC ld = C); emb, residual and dst of dtype */
+int e2fgvi_softcomp_fold(const void* emb, const float* bias_hwc, const void* residual,
+                         void* dst, int32_t dtype, int32_t F, int32_t fh, int32_t fw, int32_t H, int32_t W,
                          int32_t C, void* stream);
+/* element-wise fp32 <-> bf16 / fp16 conversion (round to nearest even; fp16: the bits of torch's .half(), overflow to +-inf,
+ * subnormals kept), n a multiple of 4 */
+int e2fgvi_cast(const void* src, int32_t src_dtype, void* dst, int32_t dst_dtype, int64_t n, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
- * bf16 data path (BASELINE.json configs 4 / 5: e2fgvi_hq at 720p / 1080p, "bf16 MFMA").
- * Activations live in HBM as bf16 NHWC (element (n,y,x,c) at ((n*H+y)*W+x)*ld + c, ld in ELEMENTS), weights are packed
- * bf16, every product runs on v_mfma_f32_32x32x16_bf16 with fp32 accumulation; bias / residual / activation are applied
- * in fp32 and the result is stored as bf16 and / or fp32.  Same operators and call sites as e2fgvi_conv2d_nhwc.
+ * LDS-DMA implicit-GEMM convolution / linear layer (csrc/conv_bf16x.hip): the 16-bit data paths (BASELINE.json configs 4 / 5:
+ * e2fgvi_hq at 720p / 1080p, "bf16 MFMA") and the fp32 path's GEMM-shaped layers.  Same operators and call sites as
+ * e2fgvi_conv2d_nhwc.  Activations are NHWC (element (n,y,x,c) at ((n*H+y)*W+x)*ld + c, ld in ELEMENTS); bias / residual /
+ * activation are applied in fp32 and the result is stored as 16-bit and / or fp32.  `mode` of e2fgvi_conv2d_x and of the
+ * packers names the operands:
+ *   E2FGVI_BF16   bf16 sources (channels per source in multiples of 8), bf16 packed weights, v_mfma_f32_32x32x16_bf16, fp32
+ *                 accumulation; 16-bit residual / dst / dst2 are bf16;
+ *   E2FGVI_F16    the same with fp16 everywhere (v_mfma_f32_32x32x16_f16: same rate and layouts; tile codes 1-8, 11-18):
+ *                 res_dtype / dst_dtype take E2FGVI_F32 or E2FGVI_F16, no split planes;
+ *   E2FGVI_F32    fp32 sources (channels in multiples of 4), fp32 packed weights, v_mfma_f32_32x32x2_f32 (exact fp32, a K-step =
+ *                 32 channels): the token Linears and SoftSplit / SoftComp, where it beats e2fgvi_conv2d_nhwc's register-staged
+ *                 pipeline;
+ *   E2FGVI_BF16X3 fp32 sources; every weight is stored as three bf16 numbers whose sum is the fp32 weight bit for bit (hi / mid /
+ *                 lo, 8 significand bits each), every activation is split the same way in registers, and of the nine bf16
+ *                 products of a*b the six largest are accumulated by v_mfma_f32_32x32x16_bf16 in fp32 (the three dropped ones
+ *                 are < 2^-22 |a*b| together): fp32-level rounding at 2.7x the fp32 MFMA rate.  Tile codes 1..8 and 107 / 108
+ *                 (the 256x256 / 256x192 tiles with the two halves of the workgroup one K-half-step apart: same bits as 7 / 8,
+ *                 not for tap-packed weights).
  * ---------------------------------------------------------------------------------------------- */
 typedef struct {
-    const void* src[E2FGVI_MAX_SRC];   /* bf16 NHWC sources of the virtual concat (fp32 for e2fgvi_conv2d_f32x) */
+    const void* src[E2FGVI_MAX_SRC];   /* NHWC sources of the virtual concat, of the mode's source type         */
     int32_t src_ld[E2FGVI_MAX_SRC];    /* pixel stride, elements (multiple of 8)                           */
     int32_t src_coff[E2FGVI_MAX_SRC];  /* first channel used by group 0 (multiple of 8)                    */
     int32_t src_cpg[E2FGVI_MAX_SRC];   /* channels per group taken from this source (multiple of 8)        */
@@ -339,13 +360,13 @@ typedef struct {
     int32_t KH, KW, stride, pad;
     int32_t groups;
     int32_t Cout;
-    const void* wpacked;               /* e2fgvi_pack_conv_weight_bf16x                                     */
+    const void* wpacked;               /* e2fgvi_pack_conv_weight_x with the same mode and tap_packed       */
     const float* bias;                 /* fp32 [Cout] or NULL                                               */
     const void* residual;              /* NHWC [N,Ho,Wo,*] of res_dtype, or the fp32 [P,4] flows of ACT_DCNPOST */
     int32_t res_ld, res_coff, res_dtype;
     void* dst;                         /* NHWC [N,Ho,Wo,dst_ld] of dst_dtype                                */
     int32_t dst_ld, dst_coff, dst_dtype;
-    void* dst2;                        /* optional second copy of the result as bf16 NHWC, or NULL          */
+    void* dst2;                        /* optional second copy of the result as 16-bit NHWC, or NULL        */
     int32_t dst2_ld, dst2_coff;
     int32_t act;
     float slope;
@@ -353,8 +374,8 @@ typedef struct {
                                         * 4 = 64x128, 5 = 64x64, 6 = 256x128, 7 = 256x256, 8 = 256x192; + 10 (11-14, 16-18):
                                         * 3x3 stride-1 layers with one A stage per kernel row (bf16 operands only)      */
     int32_t dst_nchw;                  /* 1: dst is plain fp32 NCHW [N,Cout,Ho,Wo] (dst_ld / dst_coff ignored)  */
-    int32_t tap_packed;                /* 1: wpacked comes from e2fgvi_pack_conv_weight_bf16x_taps (ABI version 3)  */
-    /* ABI version 6 (zero = the behaviour of version 5).  out_grid = 1: Ho x Wo are taken as given, `pad` rows lie above and
+    int32_t tap_packed;                /* 1: wpacked was packed with tap_packed = 1; the row-shift tile codes do not apply */
+    /* out_grid = 1 (zero: plain padding): Ho x Wo are taken as given, `pad` rows lie above and
      * `pad_left` columns left of the image and whatever else the KH x KW kernel reaches reads as zeros; with out_sy / out_sx > 0
      * output pixel (n, oy, ox) is stored -- and the residual read -- at pixel (oy*out_sy + out_py, ox*out_sx + out_px) of image n
      * of an [N, out_H, out_W] tensor.  res_bcast = 1: `residual` is ONE image ([out_H*out_W] or [Ho*Wo] rows) added to every
@@ -364,7 +385,7 @@ typedef struct {
     int32_t out_grid, pad_left;
     int32_t out_sy, out_sx, out_py, out_px, out_H, out_W;
     int32_t res_bcast;
-    /* ABI version 8 (zero = the behaviour of version 7).  dst2_plane_stride > 0 (fp32 dst, groups = 1, no NCHW / scatter):
+    /* dst2_plane_stride > 0 (zero: dst2 is a plain copy; fp32 dst, groups = 1, no NCHW / scatter, not E2FGVI_F16):
      * output channels co >= dst2_split_from are NOT stored to dst; their EXACT three-way bf16 split (hi + mid + lo == the fp32
      * result, csrc/common.h e2_split2) goes to dst2 instead -- plane pl (0 = hi, 1 = mid, 2 = lo) of row m, channel co at
      * dst2[pl * dst2_plane_stride + m * dst2_ld + dst2_coff + co - dst2_split_from] (elements) -- and channels below
@@ -375,64 +396,23 @@ typedef struct {
     int64_t dst2_plane_stride;
 } e2fgvi_convx_desc;
 
-int e2fgvi_conv2d_bf16x(const e2fgvi_convx_desc* d, void* stream);
-/* number of bf16 elements of the packed weight buffer: [group][K-step][8 k-octets][Npad][8], a K-step = 64 input
- * channels of one (tap, source), sources padded to 64, Npad = Cout/groups rounded up to 32 */
-int64_t e2fgvi_packed_conv_weight_bf16x_size(int32_t Cout, int32_t groups, int32_t KH, int32_t KW, int32_t nsrc,
-                                             const int32_t* src_cpg);
+int e2fgvi_conv2d_x(const e2fgvi_convx_desc* d, int32_t mode, void* stream);
+/* Number of elements of the packed weight buffer for `mode`: 16-bit ones for E2FGVI_BF16 / E2FGVI_F16 (one layout, one count), fp32
+ * ones for E2FGVI_F32, bf16 ones for E2FGVI_BF16X3 (3 x the E2FGVI_F32 count); negative for a geometry or a mode it rejects.
+ * tap_packed = 0: [group][K-step][8 k-octets][Npad][8] (fp32: [4]; split: [K-step][plane][4 k-octets][Npad][8]), a K-step = 64
+ * (fp32 sources: 32) input channels of one (tap, source), sources padded to a K-step, Npad = Cout/groups rounded up to 32.
+ * tap_packed = 1, for narrow layers (groups == 1, nsrc == 1, src_cpg[0] = 8 ... 56 channels -- from 4 with fp32 sources --, KW >= 2:
+ * SPyNet's 7x7 stacks model/modules/flow_comp.py:180-215, the encoder's first layer e2fgvi.py:76, the FFN's second Linear read as a
+ * 7x7 stride-3 convolution of the folded tensor tfocal_transformer.py:81,95-97): the (tap, 8-channel chunk) pairs form one stream
+ * cut into K-steps of 8 chunks -- 49 taps of 8 / 16 / 32 / 40 channels in 7 / 13 / 25 / 31 steps instead of 49 zero-padded ones
+ * (fp32 sources: chunks of 4 channels, K-steps of 32: 40 channels = 10 chunks per tap, 62 steps instead of 98). */
+int64_t e2fgvi_packed_conv_weight_x_size(int32_t mode, int32_t tap_packed, int32_t Cout, int32_t groups, int32_t KH, int32_t KW,
+                                         int32_t nsrc, const int32_t* src_cpg);
 /* w: fp32 [Cout, sum(cpg), KH, KW] (torch OIHW) */
-int e2fgvi_pack_conv_weight_bf16x(const float* w, void* wpacked, int32_t Cout, int32_t groups, int32_t KH, int32_t KW,
-                                  int32_t nsrc, const int32_t* src_cpg, void* stream);
+int e2fgvi_pack_conv_weight_x(const float* w, void* wpacked, int32_t mode, int32_t tap_packed, int32_t Cout, int32_t groups,
+                              int32_t KH, int32_t KW, int32_t nsrc, const int32_t* src_cpg, void* stream);
 
-/* Tap-packed weights for narrow layers (ONE bf16 source of 8 ... 56 channels, no groups, KW >= 2: SPyNet's 7x7 stacks
- * model/modules/flow_comp.py:180-215, the encoder's first layer e2fgvi.py:76, the FFN's second Linear read as a 7x7 stride-3
- * convolution of the folded tensor tfocal_transformer.py:81,95-97): the (tap, 8-channel chunk) pairs form one stream cut into
- * K-steps of 8 chunks -- 49 taps of 8 / 16 / 32 / 40 channels in 7 / 13 / 25 / 31 steps instead of 49 zero-padded ones.
- * Set tap_packed = 1 in the descriptor; the row-shift tile codes do not apply.  The _f32x_ pair is the same layout for
- * e2fgvi_conv2d_f32x (chunks of 4 fp32 channels, K-steps of 32: the fp32 path's FFN second Linear, 40 channels = 10 chunks
- * per tap, 62 steps instead of 98). */
-int64_t e2fgvi_packed_conv_weight_bf16x_taps_size(int32_t Cout, int32_t KH, int32_t KW, int32_t cin);
-int e2fgvi_pack_conv_weight_bf16x_taps(const float* w, void* wpacked, int32_t Cout, int32_t KH, int32_t KW, int32_t cin,
-                                       void* stream);
-/* The fp16 data path (the _f16 siblings of the four entry points above): the same kernel, tiles (tile codes 1-8, 11-18) and descriptor with fp16 operands on
- * v_mfma_f32_32x32x16_f16 (same rate and operand / result layout as the bf16 instruction).  16-bit sources, the 16-bit residual,
- * dst (dst_dtype = E2FGVI_F16) and dst2 are fp16; res_dtype / dst_dtype take E2FGVI_F32 or E2FGVI_F16; no split planes.
- * The packers and sizes are the bf16 ones with fp16 elements (same layouts, same element counts). */
-int e2fgvi_conv2d_f16x(const e2fgvi_convx_desc* d, void* stream);
-int64_t e2fgvi_packed_conv_weight_f16x_size(int32_t Cout, int32_t groups, int32_t KH, int32_t KW, int32_t nsrc,
-                                            const int32_t* src_cpg);
-int e2fgvi_pack_conv_weight_f16x(const float* w, void* wpacked, int32_t Cout, int32_t groups, int32_t KH, int32_t KW,
-                                 int32_t nsrc, const int32_t* src_cpg, void* stream);
-int64_t e2fgvi_packed_conv_weight_f16x_taps_size(int32_t Cout, int32_t KH, int32_t KW, int32_t cin);
-int e2fgvi_pack_conv_weight_f16x_taps(const float* w, void* wpacked, int32_t Cout, int32_t KH, int32_t KW, int32_t cin,
-                                      void* stream);
-int64_t e2fgvi_packed_conv_weight_f32x_taps_size(int32_t Cout, int32_t KH, int32_t KW, int32_t cin);
-int e2fgvi_pack_conv_weight_f32x_taps(const float* w, float* wpacked, int32_t Cout, int32_t KH, int32_t KW, int32_t cin,
-                                      void* stream);
-
-/* The same LDS-DMA kernel on fp32 operands: fp32 NHWC sources (channels per source in multiples of 4), fp32 packed weights,
- * v_mfma_f32_32x32x2_f32 (exact fp32, a K-step = 32 channels).  Same descriptor; used by the fp32 path for its GEMM-shaped
- * layers (token Linears, SoftSplit / SoftComp) where it beats e2fgvi_conv2d_nhwc's register-staged pipeline. */
-int e2fgvi_conv2d_f32x(const e2fgvi_convx_desc* d, void* stream);
-int64_t e2fgvi_packed_conv_weight_f32x_size(int32_t Cout, int32_t groups, int32_t KH, int32_t KW, int32_t nsrc,
-                                            const int32_t* src_cpg);
-int e2fgvi_pack_conv_weight_f32x(const float* w, float* wpacked, int32_t Cout, int32_t groups, int32_t KH, int32_t KW,
-                                 int32_t nsrc, const int32_t* src_cpg, void* stream);
-
-/* ABI version 7.  fp32 layers on the bf16 matrix pipe by exact operand splitting ("x3"): fp32 NHWC sources as for
- * e2fgvi_conv2d_f32x; every weight is stored as three bf16 numbers whose sum is the fp32 weight bit for bit (hi / mid / lo,
- * 8 significand bits each), every activation is split the same way in registers, and of the nine bf16 products of a*b the six
- * largest are accumulated by v_mfma_f32_32x32x16_bf16 in fp32 (the three dropped ones are < 2^-22 |a*b| together): fp32-level
- * rounding at 2.7x the fp32 MFMA rate.  Same descriptor, tile codes 1..8 and 107 / 108 (the 256x256 / 256x192 tiles with the two
- * halves of the workgroup one K-half-step apart: same bits as 7 / 8, not for tap-packed weights); wpacked holds 3 x the fp32 element count, in bf16
- * ([group][K-step][plane][4 k-octets][Npad][8]).  Replaces the same reference calls as e2fgvi_conv2d_nhwc (nn.Conv2d /
- * nn.Linear of model/e2fgvi_hq.py, model/modules/tfocal_transformer_hq.py). */
-int e2fgvi_conv2d_f32x3(const e2fgvi_convx_desc* d, void* stream);
-int64_t e2fgvi_packed_conv_weight_f32x3_size(int32_t Cout, int32_t groups, int32_t KH, int32_t KW, int32_t nsrc,
-                                             const int32_t* src_cpg);
-int e2fgvi_pack_conv_weight_f32x3(const float* w, void* wpacked, int32_t Cout, int32_t groups, int32_t KH, int32_t KW,
-                                  int32_t nsrc, const int32_t* src_cpg, void* stream);
-/* ... and the Winograd F(2x2,3x3) kernel the same way (csrc/conv_wino.hip, X3 build): the transformed input and the
+/* The Winograd F(2x2,3x3) kernel with split operands like E2FGVI_BF16X3 above (csrc/conv_wino.hip, X3 build): the transformed input and the
  * transformed weights are split exactly into three bf16 pieces each, six bf16 MFMA terms per product.  Same descriptor and
  * epilogues as e2fgvi_conv3x3_winograd; tile 0 (auto), 32, 132, 164; wpacked holds
  * e2fgvi_packed_winograd_weight_x3_size() bf16 elements ([group][16-channel stage][16 positions][plane][h][Npad][8]). */
@@ -440,11 +420,8 @@ int e2fgvi_conv3x3_winograd_x3(const e2fgvi_conv_desc* d, void* stream);
 int64_t e2fgvi_packed_winograd_weight_x3_size(int32_t Cout, int32_t groups, int32_t nsrc, const int32_t* src_cpg);
 int e2fgvi_pack_winograd_weight_x3(const float* w, void* wpacked, int32_t Cout, int32_t groups, int32_t nsrc,
                                    const int32_t* src_cpg, void* stream);
-int64_t e2fgvi_packed_conv_weight_f32x3_taps_size(int32_t Cout, int32_t KH, int32_t KW, int32_t cin);
-int e2fgvi_pack_conv_weight_f32x3_taps(const float* w, void* wpacked, int32_t Cout, int32_t KH, int32_t KW, int32_t cin,
-                                       void* stream);
 
-/* ABI version 7: e2fgvi_focal_attention (fp32 in, fp32 softmax, fp32 out; tfocal_transformer.py:226-396) with both matrix
+/* e2fgvi_focal_attention (fp32 in, fp32 softmax, fp32 out; tfocal_transformer.py:226-396) with both matrix
  * products on the bf16 matrix pipe as six exact bf16 terms of three-way split operands (csrc/attention_x3.hip).
  * e2fgvi_split3_kv: the k / v columns (512 .. 1535) of `rows` consecutive fp32 qkv rows -- the B*T*fh*fw token rows FOLLOWED by
  * the B*T*nWin pooled rows -- as three bf16 planes planes[3][rows][1024] whose sum is the fp32 value bit for bit.
@@ -454,70 +431,17 @@ int e2fgvi_split3_kv(const float* qkv_rows, void* planes, int64_t rows, void* st
 int e2fgvi_focal_attention_x3(const float* qkv, const void* planes, const int32_t* key_tab, int32_t tab_ld, const int32_t* nkeys,
                               float* out, int32_t B, int32_t T, int32_t fh, int32_t fw, int32_t waves, void* stream);
 
-/* Fused temporal focal window attention on bf16 MFMA: qkv / kv_pool / out are bf16 with the layouts of
- * e2fgvi_focal_attention; scores, softmax statistics and accumulation are fp32.  qkv and kv_pool must lie within one
- * 4 GiB window (the engine allocates them back to back). */
-int e2fgvi_focal_attention_bf16(const void* qkv, const void* kv_pool, const int32_t* key_tab, int32_t tab_ld,
-                                const int32_t* nkeys, void* out, int32_t B, int32_t T, int32_t fh, int32_t fw,
-                                void* stream);
-/* Kernel variant of e2fgvi_focal_attention_bf16 for the following calls of this process (A/B measurements and the tests of
- * every instantiation): 0 = automatic, 1 = round 2's register-staged kernel, 10 * QB + NW = the LDS-DMA kernel with NW
- * (2 / 4 / 8) waves of QB (1 / 2) x 32 queries per workgroup.  Returns the previous setting (-1: environment default,
- * E2FGVI_ATT_VARIANT).  Same operator and results up to fp32 summation order in every variant. */
-int e2fgvi_focal_attention_bf16_variant(int variant);
-/* The same attention with fp16 qkv / kv_pool / out (fp16 MFMA, P rounded to fp16 for the PV product); the variant setting
- * above selects its kernel too. */
-int e2fgvi_focal_attention_f16(const void* qkv, const void* kv_pool, const int32_t* key_tab, int32_t tab_ld,
-                               const int32_t* nkeys, void* out, int32_t B, int32_t T, int32_t fh, int32_t fw,
-                               void* stream);
-
-/* Typed variants of the HBM-bound helpers for the 16-bit data path: same operators and reference call sites as the fp32
- * entry points above, tensors marked `void*` are fp32, bf16 or fp16 as the dtype argument says; all arithmetic is fp32.
- * The entry points named _bf16 have an _f16 sibling with the same arguments and fp16 tensors. */
-int e2fgvi_nchw_to_nhwc_x(const float* src, void* dst, int32_t dst_dtype, int32_t N, int32_t C, int32_t H, int32_t W,
-                          int32_t ld, float scale, float shift, void* stream);
-int e2fgvi_resize_bilinear_bf16(const void* src, int32_t src_ld, void* dst, int32_t dst_ld, int32_t N, int32_t C, int32_t H,
-                                int32_t W, int32_t Ho, int32_t Wo, int32_t align_corners, void* stream);
-int e2fgvi_resize_bilinear_f16(const void* src, int32_t src_ld, void* dst, int32_t dst_ld, int32_t N, int32_t C, int32_t H,
-                               int32_t W, int32_t Ho, int32_t Wo, int32_t align_corners, void* stream);
-/* flows8_bf16 (optional): the [P,4] flows again as a 16-bit [P,8] conv source (channels 4..7 zero) of the cond's type
- * (bf16 beside an fp32 cond) */
-int e2fgvi_prop_cond_x(const float* feat_prop, int32_t fp_ld, const float* feat_n2, int32_t f2_ld, const float* flow_a,
-                       const float* flow_b, int64_t flow_img_stride, void* cond, int32_t cond_dtype, float* flows,
-                       void* flows8_bf16, int32_t N, int32_t H, int32_t W, int32_t C, void* stream);
-/* ... with the warp sources of src_dtype: E2FGVI_F32 (= e2fgvi_prop_cond_x) or E2FGVI_BF16 / E2FGVI_F16 (16-bit NHWC features,
- * a cond of the same type: half the gather bytes; the 16-bit path warps the 16-bit copies of the propagated features) */
-int e2fgvi_prop_cond_xs(const void* feat_prop, int32_t fp_ld, const void* feat_n2, int32_t f2_ld, int32_t src_dtype,
-                        const float* flow_a, const float* flow_b, int64_t flow_img_stride, void* cond, int32_t cond_dtype,
-                        float* flows, void* flows8_bf16, int32_t N, int32_t H, int32_t W, int32_t C, void* stream);
-/* out_bf16 (optional): the 8 input channels again as bf16 [Np,h,w,8], the source of the level's bf16 conv stack */
-int e2fgvi_spynet_level_input_x(const float* pyr, const int32_t* ref_idx, const int32_t* supp_idx, const float* flow_prev,
-                                float* out, void* out_bf16, int32_t Np, int32_t h, int32_t w, void* stream);
-/* ... with the copy in fp16 */
-int e2fgvi_spynet_level_input_x_f16(const float* pyr, const int32_t* ref_idx, const int32_t* supp_idx, const float* flow_prev,
-                                    float* out, void* out_f16, int32_t Np, int32_t h, int32_t w, void* stream);
-int e2fgvi_layernorm_x(const float* x, const float* gamma, const float* beta, void* y, int32_t y_dtype, int64_t rows,
-                       int32_t C, void* stream);
-int e2fgvi_window_pool_x(const void* x, int32_t dtype, const float* w45, const float* bias1, void* pooled, int32_t BT,
-                         int32_t fh, int32_t fw, int32_t C, void* stream);
-int e2fgvi_ffn_fold_x(const void* hid, void* folded, int32_t dtype, int32_t F, int32_t fh, int32_t fw, int32_t H, int32_t W,
-                      int32_t C, void* stream);
-int e2fgvi_ffn_unfold_gelu_x(const void* folded, void* out, int32_t dtype, int32_t F, int32_t fh, int32_t fw, int32_t H,
-                             int32_t W, int32_t C, void* stream);
-/* The FFN middle with the GELU in front of the unfold (a gather with zero padding commutes with GELU, GELU(0) = 0):
- * folded = GELU(fold(hid) / count) [F,H,W,C], then a pure unfold -- 5.4x fewer erf evaluations than ffn_unfold_gelu
- * (tfocal_transformer.py:82,92-97).  fp32: bit-identical to the pair above; bf16: GELU sees the unrounded fold. */
-int e2fgvi_ffn_fold_gelu_x(const void* hid, void* folded, int32_t dtype, int32_t F, int32_t fh, int32_t fw, int32_t H, int32_t W,
-                           int32_t C, void* stream);
-int e2fgvi_ffn_unfold_x(const void* folded, void* out, int32_t dtype, int32_t F, int32_t fh, int32_t fw, int32_t H, int32_t W,
-                        int32_t C, void* stream);
-int e2fgvi_softcomp_fold_bf16(const void* emb, const float* bias_hwc, const void* residual, void* dst, int32_t F, int32_t fh,
-                              int32_t fw, int32_t H, int32_t W, int32_t C, void* stream);
-int e2fgvi_softcomp_fold_f16(const void* emb, const float* bias_hwc, const void* residual, void* dst, int32_t F, int32_t fh,
-                             int32_t fw, int32_t H, int32_t W, int32_t C, void* stream);
-/* element-wise fp32 <-> bf16 / fp16 conversion (round to nearest even; fp16: the bits of torch's .half(), overflow to +-inf,
- * subnormals kept), n a multiple of 4 */
-int e2fgvi_cast(const void* src, int32_t src_dtype, void* dst, int32_t dst_dtype, int64_t n, void* stream);
+/* Fused temporal focal window attention on 16-bit MFMA: qkv / kv_pool / out are of dtype (E2FGVI_BF16 or E2FGVI_F16; fp16: P
+ * rounded to fp16 for the PV product) with the layouts of e2fgvi_focal_attention; scores, softmax statistics and accumulation
+ * are fp32.  qkv and kv_pool must lie within one 4 GiB window (the engine allocates them back to back). */
+int e2fgvi_focal_attention_16(const void* qkv, const void* kv_pool, const int32_t* key_tab, int32_t tab_ld,
+                              const int32_t* nkeys, void* out, int32_t dtype, int32_t B, int32_t T, int32_t fh, int32_t fw,
+                              void* stream);
+/* Kernel variant of e2fgvi_focal_attention_16 for the following calls of this process (A/B measurements and the tests of
+ * every instantiation): 0 = automatic, 1 = the register-staged kernel, 10 * QB + NW = the LDS-DMA kernel with NW
+ * (2 / 4 / 8) waves of QB (1 / 2) x 32 queries per workgroup.  Returns the previous setting.  Same operator and results up to
+ * fp32 summation order in every variant. */
+int e2fgvi_focal_attention_16_variant(int variant);
 
 #ifdef __cplusplus
 }

@@ -172,7 +172,7 @@ def test_linear_f16x_and_bad_arguments(dev):
     d.wpacked = layer.wpacked.data_ptr()
     with pytest.raises(HipError):
         from e2fgvi_amd import lib as _L
-        _L.check(layer._fn(__import__("ctypes").byref(d), None), "conv2d_f16x split planes")
+        _L.check(layer._fn(__import__("ctypes").byref(d), None), "conv2d_x (fp16) split planes")
 
 
 # ------------------------------------------------------------------------------------------------------------- attention
@@ -215,7 +215,7 @@ def _attention_ref(qkv, kvp, tab, nk, B, T, fh, fw):
                                                  (1, 10, 10, 18, (0, 1, 18, 28)),
                                                  (1, 152, 5, 9, (0,))])        # T > 150: only the register-staged kernel fits
 def test_focal_attention_f16(dev, B, T, fh, fw, variants):
-    """every kernel variant e2fgvi_focal_attention_bf16_variant can select, on fp16 rows (P rounded to fp16 for the PV product,
+    """every kernel variant e2fgvi_focal_attention_16_variant can select, on fp16 rows (P rounded to fp16 for the PV product,
     the output rounded once): elementwise within 2^-10 relative + 2e-3 x rms -- a sixth of the bf16 kernel's allowance"""
     from e2fgvi_amd import ops
     from e2fgvi_amd.engine import build_key_table

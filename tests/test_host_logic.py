@@ -100,7 +100,7 @@ def test_abi_exports_every_declared_symbol():
     so = ctypes.CDLL(lib.LIB_PATH)
     for name in declared:
         assert hasattr(so, name), name
-    assert lib.load().e2fgvi_abi_version() == 8
+    assert lib.load().e2fgvi_abi_version() == 9
 
 
 def test_packing_size_functions_and_argument_checks_run_without_a_gpu():
@@ -110,12 +110,14 @@ def test_packing_size_functions_and_argument_checks_run_without_a_gpu():
         pytest.skip("library not built yet (python -m e2fgvi_amd.build)")
     L = lib.load()
     # tap-packed K-steps: (tap, 8-channel chunk) pairs cut into steps of 8 chunks of 64 x Npad elements
-    assert L.e2fgvi_packed_conv_weight_bf16x_taps_size(512, 7, 7, 40) == 31 * 64 * 512       # FFN fc2 as a conv: 49 * 5 / 8 -> 31 steps
-    assert L.e2fgvi_packed_conv_weight_bf16x_taps_size(32, 7, 7, 8) == 7 * 64 * 32           # SPyNet .0: 8 taps per step
-    assert L.e2fgvi_packed_conv_weight_bf16x_taps_size(64, 3, 3, 24) == 4 * 64 * 64          # 9 taps x 3 chunks -> 4 steps
-    assert L.e2fgvi_packed_conv_weight_f32x_taps_size(512, 7, 7, 40) == 62 * 32 * 512        # fp32: chunks of 4 channels, steps of 32
-    assert L.e2fgvi_packed_conv_weight_bf16x_taps_size(64, 3, 3, 64) < 0                      # a full K-step per tap: nothing to pack
-    assert L.e2fgvi_packed_conv_weight_bf16x_taps_size(64, 1, 1, 16) < 0                      # one tap
+    def taps_size(mode, cout, kh, kw, cin):
+        return L.e2fgvi_packed_conv_weight_x_size(mode, 1, cout, 1, kh, kw, 1, (ctypes.c_int32 * 1)(cin))
+    assert taps_size(lib.DT_BF16, 512, 7, 7, 40) == 31 * 64 * 512       # FFN fc2 as a conv: 49 * 5 / 8 -> 31 steps
+    assert taps_size(lib.DT_BF16, 32, 7, 7, 8) == 7 * 64 * 32           # SPyNet .0: 8 taps per step
+    assert taps_size(lib.DT_BF16, 64, 3, 3, 24) == 4 * 64 * 64          # 9 taps x 3 chunks -> 4 steps
+    assert taps_size(lib.DT_F32, 512, 7, 7, 40) == 62 * 32 * 512        # fp32: chunks of 4 channels, steps of 32
+    assert taps_size(lib.DT_BF16, 64, 3, 3, 64) < 0                      # a full K-step per tap: nothing to pack
+    assert taps_size(lib.DT_BF16, 64, 1, 1, 16) < 0                      # one tap
     assert b"56" in L.e2fgvi_last_error()
     # decoder tail: only 64 -> 3 is built
     assert L.e2fgvi_packed_tail_weight_size(3, 64) == 64 * 32

@@ -194,7 +194,9 @@ __global__ __launch_bounds__(256) void spin_valu(float* sink, int iters) {
 typedef int (*conv_fn)(const e2fgvi_conv_desc*, void*);
 typedef int64_t (*size_bf_fn)(int32_t, int32_t, int32_t, int32_t, int32_t, const int32_t*);
 typedef int (*pack_bf_fn)(const float*, void*, int32_t, int32_t, int32_t, int32_t, int32_t, const int32_t*, void*);
-typedef int (*convx_fn)(const e2fgvi_convx_desc*, void*);
+typedef int64_t (*size_x_fn)(int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, const int32_t*);
+typedef int (*pack_x_fn)(const float*, void*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, const int32_t*, void*);
+typedef int (*convx_fn)(const e2fgvi_convx_desc*, int32_t, void*);
 typedef int64_t (*size_fn)(int32_t, int32_t, int32_t, int32_t, int32_t, const int32_t*, int32_t);
 typedef int (*pack_fn)(const float*, float*, int32_t, int32_t, int32_t, int32_t, int32_t, const int32_t*, int32_t, void*);
 
@@ -216,9 +218,9 @@ int main(int argc, char** argv) {
     pack_bf_fn pack_bf = (pack_bf_fn)dlsym(L1, "e2fgvi_pack_conv_weight_bf16");
     size_fn size_f = (size_fn)dlsym(L, "e2fgvi_packed_conv_weight_size");
     pack_fn pack_f = (pack_fn)dlsym(L, "e2fgvi_pack_conv_weight");
-    convx_fn conv_x = (convx_fn)dlsym(L, "e2fgvi_conv2d_bf16x");
-    size_bf_fn size_x = (size_bf_fn)dlsym(L, "e2fgvi_packed_conv_weight_bf16x_size");
-    pack_bf_fn pack_x = (pack_bf_fn)dlsym(L, "e2fgvi_pack_conv_weight_bf16x");
+    convx_fn conv_x = (convx_fn)dlsym(L, "e2fgvi_conv2d_x");
+    size_x_fn size_x = (size_x_fn)dlsym(L, "e2fgvi_packed_conv_weight_x_size");
+    pack_x_fn pack_x = (pack_x_fn)dlsym(L, "e2fgvi_pack_conv_weight_x");
     hipStream_t sa, sb;
     CK(hipStreamCreate(&sa)); CK(hipStreamCreate(&sb));
 
@@ -257,9 +259,9 @@ int main(int argc, char** argv) {
     e2fgvi_convx_desc dx; memset(&dx, 0, sizeof(dx));
     void* wpx = nullptr; float* coutx = nullptr;
     if (conv_x) {
-        const int64_t nx = size_x(Cout, groups, 3, 3, 2, cpg);
+        const int64_t nx = size_x(E2FGVI_BF16, 0, Cout, groups, 3, 3, 2, cpg);
         CK(hipMalloc(&wpx, nx * 2)); CK(hipMalloc(&coutx, (size_t)cN * cH * cW * Cout * 4));
-        if (pack_x(wraw, wpx, Cout, groups, 3, 3, 2, cpg, 0)) { printf("pack_x failed\n"); return 1; }
+        if (pack_x(wraw, wpx, E2FGVI_BF16, 0, Cout, groups, 3, 3, 2, cpg, 0)) { printf("pack_x failed\n"); return 1; }
         CK(hipDeviceSynchronize());
         dx.src[0] = x0; dx.src[1] = x1; dx.src_ld[0] = 256; dx.src_ld[1] = 384; dx.src_cpg[0] = 128; dx.src_cpg[1] = 192; dx.nsrc = 2;
         dx.N = cN; dx.H = cH; dx.W = cW; dx.Ho = cH; dx.Wo = cW; dx.KH = 3; dx.KW = 3; dx.stride = 1; dx.pad = 1; dx.groups = groups; dx.Cout = Cout;
@@ -292,8 +294,8 @@ int main(int argc, char** argv) {
             case 9: d.wpacked = (const float*)wpb; d.tile = 3; for (int k = 0; k < 6; ++k) conv_bf16(&d, st); break;
             case 10: hipLaunchKernelGGL(mfma_lds_aggr<1>, dim3(512), dim3(256), 0, st, big, sink, 6000); break;
             case 11: hipLaunchKernelGGL(mfma_lds_aggr<2>, dim3(512), dim3(256), 0, st, big, sink, 6000); break;
-            case 13: if (conv_x) { dx.tile = 1; for (int k = 0; k < 8; ++k) conv_x(&dx, st); } break;
-            case 14: if (conv_x) { dx.tile = 2; for (int k = 0; k < 8; ++k) conv_x(&dx, st); } break;
+            case 13: if (conv_x) { dx.tile = 1; for (int k = 0; k < 8; ++k) conv_x(&dx, E2FGVI_BF16, st); } break;
+            case 14: if (conv_x) { dx.tile = 2; for (int k = 0; k < 8; ++k) conv_x(&dx, E2FGVI_BF16, st); } break;
             case 12: hipLaunchKernelGGL(mfma_lds_aggr<3>, dim3(512), dim3(256), 0, st, big, sink, 6000); break;
             default: break;
         }
