@@ -173,6 +173,10 @@ def _traced(name, fn):
         e0.record()
         rc = fn(*args)
         e1.record()
+        if name.startswith("e2fgvi_pack_"):
+            # a weight packing built lazily between annotate() and the launch it announced: the metadata stays with the launch
+            TRACE.append({"symbol": name, "e0": e0, "e1": e1, "meta": None})
+            return rc
         TRACE.append({"symbol": name, "e0": e0, "e1": e1, "meta": NEXT_META})
         NEXT_META = None
         return rc

@@ -441,6 +441,7 @@ class PackedConv:
         Implicit GEMM: output channels padded to 32, every source's channels to the K granule."""
         cin_g, cout_g, K2 = sum(self.cpg), self.Cout // self.groups, self.KH * self.KW
         macs = N * Ho * Wo * self.Cout * cin_g * K2
+        asked = int(tile)                      # the tile code handed to the launcher (W3_BASE + block shape for the split Winograd kernel)
         if use_wino and tile in W4_CODES:
             fy, bn = W4_CODES[tile]
             pix = N * (-(-H // (8 * fy)) * 8 * fy) * (-(-W // 16) * 16)
@@ -473,7 +474,7 @@ class PackedConv:
             issued = N * Ho * Wo * (-(-cout_g // 32) * 32) * self.groups * cin_p * K2
             kern = "conv_igemm/halo tile=%d" % tile
         return dict(layer=self.name, kernel=kern, shape="N%d %dx%d %d->%d k%d s%d g%d" % (
-            N, H, W, cin_g * self.groups, self.Cout, self.KH, self.stride, self.groups), macs=macs, issued=issued)
+            N, H, W, cin_g * self.groups, self.Cout, self.KH, self.stride, self.groups), macs=macs, issued=issued, tile=asked)
 
     def __call__(self, sources, out=None, out_coff=0, residual=None, res_coff=0, act=ACT_NONE, slope=0.0,
                  out_nchw=False, tile=0, kv_planes=None, out_dtype=None):
@@ -908,7 +909,7 @@ class PackedConvX:
                                                                       "f16x" if self.f16 else "bf16x", tile,
                                                                       " taps" if self.taps else ""),
                         shape="N%d %dx%d %d->%d k%d s%d g%d" % (N, H, W, cin_g * self.groups, self.Cout, self.KH, self.stride, self.groups),
-                        macs=N * Ho * Wo * self.Cout * cin_g * K2,
+                        macs=N * Ho * Wo * self.Cout * cin_g * K2, tile=int(tile),
                         # x3: six bf16 MACs per product, counted in fp32-pipe equivalents (a bf16 MAC occupies the matrix
                         # pipe for 157.3 / 2500 of the time of an fp32 MAC): `issued / fp32 peak` stays matrix-pipe time
                         issued=int(N * Ho * Wo * (-(-cout_g // 32) * 32) * self.groups * cin_p * K2 * (6 * 157.3 / 2500.0 if self.x3 else 1)))

@@ -6,7 +6,7 @@ unaccompanied launch.  The static side of the same guarantee is build.verify_exi
 import pytest
 import torch
 
-from tests.util import gen
+from tests.util import assert_one_conv_launch, gen, launch_trace
 
 pytestmark = pytest.mark.gpu
 
@@ -40,9 +40,14 @@ def test_winograd_kernels_beside_device_copies_return_the_bits_of_the_launch_alo
     for code in _codes():
         ref = torch.empty(n, 60, 108, cout, device=dev)
         try:
-            layer(srcs, out=ref, act=ops.ACT_LRELU, slope=0.2, tile=code)
+            with launch_trace() as trace:
+                layer(srcs, out=ref, act=ops.ACT_LRELU, slope=0.2, tile=code)
         except L.HipError:
             continue                                    # a block shape this geometry rejects (e.g. F(4x4) needs H % 4 == 0)
+        # the kernel the code names, in one launch: a split-operand block shape that the launcher refuses does not raise, the
+        # fp32 Winograd kernel runs in its place -- and would be what the 200 launches below exercise
+        assert_one_conv_launch(trace, "e2fgvi_conv3x3_winograd_x3" if code >= ops.W3_BASE else "e2fgvi_conv3x3_winograd4"
+                               if code in ops.W4_CODES else "e2fgvi_conv3x3_winograd", tile=code, what="%s, tile code %d" % (name, code))
         torch.cuda.synchronize()
         outs = [torch.empty_like(ref) for _ in range(PER_ROUND)]
         bad = 0

@@ -10,7 +10,7 @@ import torch
 import torch.nn.functional as F
 
 from tests.test_gpu_bf16x import CASES, F32_TAP_CASES, conv64
-from tests.util import assert_close, fp32_tol, gen as _gen, name_seed, nchw, nhwc
+from tests.util import assert_close, assert_one_conv_launch, fp32_tol, gen as _gen, launch_trace, name_seed, nchw, nhwc
 
 pytestmark = pytest.mark.gpu
 
@@ -245,12 +245,17 @@ def test_conv3x3_winograd_x3(dev, case):
     src_d = [nhwc(s_).to(dev) for s_ in srcs]
     fp32 = layer(src_d, act=act, slope=0.2, tile=132)
     for shape in (132, 164, 32, 5132, 6064):
-        if dst_ld is None:
-            out = layer(src_d, act=act, slope=0.2, tile=ops.W3_BASE + shape)
-        else:
-            full = torch.full((N, H, W, dst_ld), 7.0, device=dev)
-            layer(src_d, out=full, out_coff=dst_coff, act=act, slope=0.2, tile=ops.W3_BASE + shape)
-            out = full[..., dst_coff:dst_coff + Cout]
+        # (one launch, through the split kernel's entry point: a block shape the launcher refused would be replaced by the fp32
+        #  Winograd kernel without an error, and every bound below would still hold)
+        with launch_trace() as trace:
+            if dst_ld is None:
+                out = layer(src_d, act=act, slope=0.2, tile=ops.W3_BASE + shape)
+            else:
+                full = torch.full((N, H, W, dst_ld), 7.0, device=dev)
+                layer(src_d, out=full, out_coff=dst_coff, act=act, slope=0.2, tile=ops.W3_BASE + shape)
+                out = full[..., dst_coff:dst_coff + Cout]
+        assert_one_conv_launch(trace, "e2fgvi_conv3x3_winograd_x3", tile=ops.W3_BASE + shape, what="winograd x3 shape %d %s" % (shape, case))
+        if dst_ld is not None:
             rest = torch.cat([full[..., :dst_coff], full[..., dst_coff + Cout:]], 3)
             assert (rest == 7.0).all(), "winograd x3 wrote outside its channel slice"
         _pattern_on_mismatch(out, fp32, shape, case)
@@ -271,7 +276,9 @@ def test_conv3x3_winograd_x3_epilogues(dev, shape):
         resfull = torch.randn(2, 30, 54, res_ld, generator=g)
         res = resfull[..., res_coff:res_coff + 128]
         ref = F.leaky_relu(conv64(x, w, b, padding=1) + nchw(res), 0.1)
-        out = layer([nhwc(x).to(dev)], residual=resfull.to(dev), res_coff=res_coff, act=2, slope=0.1, tile=ops.W3_BASE + shape)
+        with launch_trace() as trace:
+            out = layer([nhwc(x).to(dev)], residual=resfull.to(dev), res_coff=res_coff, act=2, slope=0.1, tile=ops.W3_BASE + shape)
+        assert_one_conv_launch(trace, "e2fgvi_conv3x3_winograd_x3", tile=ops.W3_BASE + shape, what="winograd x3 + residual, shape %d" % shape)
         assert_close(nchw(out.cpu()), ref, 3e-5, "winograd x3 + residual (ld %d coff %d) shape %d" % (res_ld, res_coff, shape))
     w2 = torch.randn(432, 128, 3, 3, generator=g) / math.sqrt(128 * 9)
     b2 = torch.randn(432, generator=g) * 0.1
@@ -283,7 +290,9 @@ def test_conv3x3_winograd_x3_epilogues(dev, shape):
     off1, off2 = torch.chunk(off, 2, 1)
     ref = torch.cat([off1 + f1.flip(1).repeat(1, 72, 1, 1), off2 + f2.flip(1).repeat(1, 72, 1, 1), torch.sigmoid(m)], 1)
     wl = ops.PackedConv(w2.to(dev), b2.to(dev), [128], pad=1, algo="winograd")
-    first = wl([nhwc(x).to(dev)], residual=fl.to(dev), act=ops.ACT_DCNPOST, slope=10.0, tile=ops.W3_BASE + shape)
+    with launch_trace() as trace:
+        first = wl([nhwc(x).to(dev)], residual=fl.to(dev), act=ops.ACT_DCNPOST, slope=10.0, tile=ops.W3_BASE + shape)
+    assert_one_conv_launch(trace, "e2fgvi_conv3x3_winograd_x3", tile=ops.W3_BASE + shape, what="winograd x3 DCNPOST, shape %d" % shape)
     assert_close(nchw(first.cpu()), ref, 5e-5, "winograd x3 DCNPOST shape %d" % shape)
     first = first.clone()
     bad = sum(int(not torch.equal(wl([nhwc(x).to(dev)], residual=fl.to(dev), act=ops.ACT_DCNPOST, slope=10.0,

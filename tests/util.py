@@ -124,3 +124,73 @@ def golden_case(path):
     else:
         x, _ = synth_clip(b, t, H, W, seed=seed, moving=True)
     return z, str(z["model"]), str(z["kind"]), x, lt, so, sf
+
+
+# ---------------------------------------------------------------------------------------------- which kernel ran
+@contextlib.contextmanager
+def launch_trace():
+    """the launch trace of e2fgvi_amd.lib for the duration of the block: yields the list that every C-ABI launch appends its record
+    to ({"symbol", "meta", ...}; "meta" is what the operator layer announced: layer, kernel, shape, MACs, tile code); the previous
+    state of the trace comes back on exit, whatever the block raised"""
+    from e2fgvi_amd import lib
+    saved = lib.TRACE
+    lib.TRACE = trace = []
+    lib.NEXT_META = None
+    try:
+        yield trace
+    finally:
+        lib.TRACE = saved
+        lib.NEXT_META = None
+
+
+def conv_launches(trace):
+    """the conv / linear launches of a trace (a weight packing, e2fgvi_pack_*, or a helper such as e2fgvi_split3_kv is none)"""
+    return [r for r in trace if r["symbol"].startswith("e2fgvi_conv")]
+
+
+def assert_one_conv_launch(trace, symbol, tile=None, kernel=None, what=""):
+    """the traced call launched exactly one conv kernel, through the entry point `symbol`, with tile code `tile` (and the kernel
+    family `kernel`, the first word of the announced kernel name).  A rejected launch is traced like an accepted one, so a launcher
+    that refused the asked-for kernel and the default that ran in its place show up as two records: the silent fallback of
+    ops.PackedConv / PackedConvX fails here."""
+    got = conv_launches(trace)
+    desc = [(r["symbol"], (r["meta"] or {}).get("kernel"), (r["meta"] or {}).get("tile")) for r in got]
+    assert len(got) == 1, "%s: expected one conv launch through %s, the trace holds %d: %s" % (what, symbol, len(got), desc)
+    assert got[0]["symbol"] == symbol, "%s: ran %s, not %s" % (what, desc[0], symbol)
+    meta = got[0]["meta"]
+    assert meta is not None, "%s: the launch carries no announced metadata" % what
+    if tile is not None:
+        assert meta.get("tile") == tile, "%s: tile code %r reached the launcher, not %r" % (what, meta.get("tile"), tile)
+    if kernel is not None:
+        assert str(meta.get("kernel", "")).split(" ")[0] == kernel, "%s: kernel %r, not %s" % (what, meta.get("kernel"), kernel)
+    return meta
+
+
+@contextlib.contextmanager
+def tabled(rows, w4_minpix=None):
+    """the decision table replaced by `rows` ({key: tile code}) for the duration of the block, table-driven selection whatever the
+    environment says (no timing, the split-operand alternatives allowed); yields the list of (key, decision) pairs the layers
+    looked up meanwhile.  w4_minpix: the pixel floor of PackedConv._wino4_rule (small test shapes of the layers whose static
+    kernel is the wide-tile Winograd one).  Everything is restored on exit, as in timed_tuning()."""
+    from e2fgvi_amd import ops
+    saved = (ops.AUTOTUNE, dict(ops._TUNED), dict(ops._NEAREST), ops._W4_MINPIX, ops.X3_ENABLED, ops._decision)
+    decide, asked = ops._decision, []
+
+    def spy(key):
+        best = decide(key)
+        asked.append((key, best))
+        return best
+    ops.AUTOTUNE, ops.X3_ENABLED, ops._decision = False, True, spy
+    ops._TUNED.clear()
+    ops._TUNED.update(rows)
+    ops._NEAREST.clear()
+    if w4_minpix is not None:
+        ops._W4_MINPIX = w4_minpix
+    try:
+        yield asked
+    finally:
+        ops.AUTOTUNE, _, _, ops._W4_MINPIX, ops.X3_ENABLED, ops._decision = saved
+        ops._TUNED.clear()
+        ops._TUNED.update(saved[1])
+        ops._NEAREST.clear()
+        ops._NEAREST.update(saved[2])
