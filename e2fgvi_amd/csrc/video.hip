@@ -192,7 +192,229 @@ int slab_copy(const void* cache, const void* rows, const int32_t* ids, int32_t n
     return 0;
 }
 
+// Paste-back at source resolution (what a front end does after test.py:168-179 when the frames were resized on the way in):
+//   out = where(NEAREST(mask_lo) != 0, BICUBIC(lo), src)
+// with Pillow's two 8-bit passes for the upscale -- width first, its uint8 result clamped, then height -- and Pillow's NEAREST
+// tables for the mask, fused: nothing of source size is written but `out`.  A workgroup owns an RT_W x RT_H tile of output pixels
+// of one frame (384-byte row segments: three 128-byte lines when the row pitch allows it).  It gathers the tile's mask bits
+// first; the OR over the block decides, block-uniformly, between
+//   * no hole pixel: the tile's row segments are copied src -> out with the widest words the two addresses share (16 bytes with
+//     byte head / tail when both have the same phase, as slab_copy chooses per buffer), 32 lanes per row;
+//   * otherwise: the rows / columns of `lo` the tile's taps reach (block min / max of the clipped bounds) are staged in LDS, the
+//     horizontal pass of those rows runs LDS -> LDS (uint8, clamped, the intermediate Pillow keeps), and every thread does the
+//     vertical pass for four output bytes and selects per pixel between it and src.  For an upscale the patch is smaller than
+//     the tile (<= RT_H / scale + 4 rows).  A patch beyond the fixed LDS budget (a strongly shrinking axis) takes the direct
+//     path: the same arithmetic with the horizontal values recomputed from global memory per vertical tap.
+// Every table entry is clipped before it is used as an index, so the kernel stays in bounds whatever the tables hold.
+constexpr int RT_W = 128, RT_H = 8, RT_WB = RT_W * 3;
+constexpr int RT_ROWS = 24;                    // horizontal-pass rows kept in LDS (RT_ROWS * RT_WB bytes)
+constexpr int RT_PATCH = 8192;                 // bytes of `lo` staged in LDS
+static_assert(NTH == RT_H * 32, "the copy path gives every tile row 32 lanes");
+
+__device__ __forceinline__ void clipped_taps(const int* __restrict__ bounds, int o, int n_in, int ksize, int& first, int& taps) {
+    first = bounds[2 * o];
+    first = first < 0 ? 0 : (first > n_in ? n_in : first);
+    taps = bounds[2 * o + 1];
+    taps = taps < ksize ? taps : ksize;
+    taps = taps < n_in - first ? taps : n_in - first;
+}
+
+__device__ __forceinline__ unsigned char pillow_clip8(int acc) {
+    acc >>= 22;
+    return (unsigned char)(acc < 0 ? 0 : (acc > 255 ? 255 : acc));
+}
+
+template <typename V>
+__device__ __forceinline__ void copy_segment(const unsigned char* __restrict__ s, unsigned char* __restrict__ d, int n, int lane,
+                                             int lanes) {
+    constexpr int B = (int)sizeof(V);
+    int head = (int)((B - (int)((uintptr_t)d & (B - 1))) & (B - 1));
+    head = head < n ? head : n;
+    const int body = (n - head) / B, t0 = head + body * B;
+    for (int k = lane; k < head; k += lanes) d[k] = s[k];
+    const V* sv = reinterpret_cast<const V*>(s + head);
+    V* dv = reinterpret_cast<V*>(d + head);
+    for (int k = lane; k < body; k += lanes) dv[k] = sv[k];
+    for (int k = t0 + lane; k < n; k += lanes) d[k] = s[k];
+}
+
+// horizontal pass of one value straight from global memory (the direct path)
+__device__ __forceinline__ int restore_hpass_global(const unsigned char* __restrict__ lo_row, int w, const int* __restrict__ bx,
+                                                    const int* __restrict__ cx, int kx, int x, int c) {
+    int f, n;
+    clipped_taps(bx, x, w, kx, f, n);
+    const int* k = cx + (long long)x * kx;
+    const unsigned char* p = lo_row + (long long)f * 3 + c;
+    int acc = 1 << 21;
+#pragma unroll 1
+    for (int j = 0; j < n; ++j) acc += (int)p[3 * j] * k[j];
+    return pillow_clip8(acc);
+}
+
+template <bool STAGED>
+__device__ __forceinline__ void restore_vpass(const unsigned char* __restrict__ lo_l, const unsigned char* __restrict__ src,
+                                              unsigned char* __restrict__ out, const unsigned char* s_m, const unsigned char* s_h,
+                                              int r0, long long frame_off, int h, int w, int W, int x0, int y0, int nb, int th,
+                                              const int* __restrict__ bx, const int* __restrict__ cx, int kx,
+                                              const int* __restrict__ by, const int* __restrict__ cy, int ky) {
+    for (int u = threadIdx.x; u < th * (RT_WB / 4); u += NTH) {
+        const int ty = u / (RT_WB / 4), xc0 = (u - ty * (RT_WB / 4)) * 4;
+        if (xc0 >= nb) continue;
+        const int y = y0 + ty;
+        const int n4 = nb - xc0 < 4 ? nb - xc0 : 4;
+        const long long off = frame_off + ((long long)y * W + x0) * 3 + xc0;
+        unsigned char v[4] = {0, 0, 0, 0};
+        if (n4 == 4 && ((uintptr_t)(src + off) & 3) == 0) {
+            const unsigned q = *reinterpret_cast<const unsigned*>(src + off);
+            v[0] = (unsigned char)q; v[1] = (unsigned char)(q >> 8); v[2] = (unsigned char)(q >> 16); v[3] = (unsigned char)(q >> 24);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (k < n4) v[k] = src[off + k];
+        }
+        int fy, ny;
+        clipped_taps(by, y, h, ky, fy, ny);
+        const int* kyp = cy + (long long)y * ky;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int xc = xc0 + k, x = xc / 3, c = xc - 3 * x;
+            if (k >= n4 || !s_m[ty * RT_W + x]) continue;
+            int acc = 1 << 21;
+#pragma unroll 1
+            for (int j = 0; j < ny; ++j) {
+                const int r = fy + j;
+                const int hv = STAGED ? (int)s_h[(r - r0) * RT_WB + xc]
+                                      : restore_hpass_global(lo_l + (long long)r * w * 3, w, bx, cx, kx, x0 + x, c);
+                acc += hv * kyp[j];
+            }
+            v[k] = pillow_clip8(acc);
+        }
+        if (n4 == 4 && ((uintptr_t)(out + off) & 3) == 0) {
+            *reinterpret_cast<unsigned*>(out + off) = (unsigned)v[0] | ((unsigned)v[1] << 8) | ((unsigned)v[2] << 16) | ((unsigned)v[3] << 24);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (k < n4) out[off + k] = v[k];
+        }
+    }
+}
+
+__global__ __launch_bounds__(NTH) void restore_u8_kernel(
+    const unsigned char* __restrict__ lo, const unsigned char* __restrict__ mask, const unsigned char* __restrict__ src,
+    unsigned char* __restrict__ out, int L, int h, int w, int H, int W, const int* __restrict__ ytab, const int* __restrict__ xtab,
+    const int* __restrict__ bx, const int* __restrict__ cx, int kx, const int* __restrict__ by, const int* __restrict__ cy, int ky) {
+    __shared__ unsigned char s_m[RT_H * RT_W];
+    __shared__ __align__(16) unsigned char s_patch[RT_PATCH];
+    __shared__ __align__(16) unsigned char s_h[RT_ROWS * RT_WB];
+    __shared__ int s_rng[4];
+    const int tid = threadIdx.x;
+    const int x0 = blockIdx.x * RT_W, y0 = blockIdx.y * RT_H;
+    const int tw = W - x0 < RT_W ? W - x0 : RT_W, th = H - y0 < RT_H ? H - y0 : RT_H;
+    const int nb = tw * 3;
+    for (int l = blockIdx.z; l < L; l += gridDim.z) {
+        // the tile's mask bits through the two NEAREST tables; any hole pixel?
+        const unsigned char* ml = mask + (long long)l * h * w;
+        int any = 0;
+        for (int i = tid; i < RT_H * RT_W; i += NTH) {
+            const int ty = i / RT_W, tx = i % RT_W;
+            unsigned char m = 0;
+            if (ty < th && tx < tw) {
+                int my = ytab[y0 + ty], mx = xtab[x0 + tx];
+                my = my < 0 ? 0 : (my > h - 1 ? h - 1 : my);
+                mx = mx < 0 ? 0 : (mx > w - 1 ? w - 1 : mx);
+                m = ml[(long long)my * w + mx] != 0;
+            }
+            s_m[i] = m;
+            any |= m;
+        }
+        any = __syncthreads_or(any);
+        const long long frame_off = (long long)l * H * W * 3;
+        if (!any) {
+            const int ty = tid >> 5, lane = tid & 31;
+            if (ty < th) {
+                const long long off = frame_off + ((long long)(y0 + ty) * W + x0) * 3;
+                const unsigned char* s = src + off;
+                unsigned char* d = out + off;
+                const unsigned phase = (unsigned)((uintptr_t)s ^ (uintptr_t)d);
+                if ((phase & 15) == 0) copy_segment<uint4>(s, d, nb, lane, 32);
+                else if ((phase & 3) == 0) copy_segment<unsigned>(s, d, nb, lane, 32);
+                else copy_segment<unsigned char>(s, d, nb, lane, 32);
+            }
+            continue;                                   // s_m is not read on this path: the next frame may overwrite it
+        }
+        // rows [r0, r1) and columns [c0, c1) of lo that the tile's taps reach
+        if (tid < 4) s_rng[tid] = (tid & 1) ? 0 : 0x7fffffff;
+        __syncthreads();
+        if (tid < th) {
+            int f, n;
+            clipped_taps(by, y0 + tid, h, ky, f, n);
+            if (n > 0) { atomicMin(&s_rng[0], f); atomicMax(&s_rng[1], f + n); }
+        }
+        if (tid < tw) {
+            int f, n;
+            clipped_taps(bx, x0 + tid, w, kx, f, n);
+            if (n > 0) { atomicMin(&s_rng[2], f); atomicMax(&s_rng[3], f + n); }
+        }
+        __syncthreads();
+        int r0 = s_rng[0], c0 = s_rng[2];
+        const int pr = s_rng[1] > r0 ? s_rng[1] - r0 : 0, pc = s_rng[3] > c0 ? s_rng[3] - c0 : 0;
+        if (!pr) r0 = 0;
+        if (!pc) c0 = 0;
+        const unsigned char* lo_l = lo + (long long)l * h * w * 3;
+        if (pr <= RT_ROWS && (long long)pr * pc * 3 <= RT_PATCH) {
+            const int pb = pc * 3;
+            for (int i = tid; i < pr * pb; i += NTH) {
+                const int r = i / pb;
+                s_patch[i] = lo_l[((long long)(r0 + r) * w + c0) * 3 + (i - r * pb)];
+            }
+            __syncthreads();
+            for (int i = tid; i < pr * nb; i += NTH) {
+                const int r = i / nb, xc = i - r * nb, x = xc / 3, c = xc - 3 * x;
+                int f, n;
+                clipped_taps(bx, x0 + x, w, kx, f, n);
+                const int* k = cx + (long long)(x0 + x) * kx;
+                const unsigned char* p = s_patch + r * pb + (f - c0) * 3 + c;        // n > 0 implies c0 <= f, f + n <= c0 + pc
+                int acc = 1 << 21;
+#pragma unroll 1
+                for (int j = 0; j < n; ++j) acc += (int)p[3 * j] * k[j];
+                s_h[r * RT_WB + xc] = pillow_clip8(acc);
+            }
+            __syncthreads();
+            restore_vpass<true>(lo_l, src, out, s_m, s_h, r0, frame_off, h, w, W, x0, y0, nb, th, bx, cx, kx, by, cy, ky);
+        } else {
+            restore_vpass<false>(lo_l, src, out, s_m, s_h, r0, frame_off, h, w, W, x0, y0, nb, th, bx, cx, kx, by, cy, ky);
+        }
+        __syncthreads();                                // s_m, s_h are rewritten for the next frame
+    }
+}
+
+inline bool ranges_overlap(const void* a, long long na, const void* b, long long nb) {
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return pa < pb + (uintptr_t)nb && pb < pa + (uintptr_t)na;
+}
+
 }  // namespace
+
+extern "C" int e2fgvi_restore_u8(const uint8_t* lo, const uint8_t* mask_lo, const uint8_t* src, uint8_t* out, int32_t L, int32_t h,
+                                 int32_t w, int32_t H, int32_t W, const int32_t* ytab, const int32_t* xtab, const int32_t* bounds_x,
+                                 const int32_t* coeffs_x, int32_t ksize_x, const int32_t* bounds_y, const int32_t* coeffs_y,
+                                 int32_t ksize_y, void* stream) {
+    E2_REQUIRE(lo && mask_lo && src && out && ytab && xtab && bounds_x && coeffs_x && bounds_y && coeffs_y, E2FGVI_EINVAL,
+               "restore_u8: null pointer");
+    E2_REQUIRE(L > 0 && h > 0 && w > 0 && H > 0 && W > 0 && ksize_x >= 1 && ksize_y >= 1, E2FGVI_EINVAL,
+               "restore_u8: sizes and tap counts must be positive");
+    E2_REQUIRE(W * 3LL <= 0x7fffffffLL && w * 3LL <= 0x7fffffffLL && (H + RT_H - 1) / RT_H <= 65535, E2FGVI_EINVAL,
+               "restore_u8: frames too large");
+    const long long n_out = (long long)L * H * W * 3, n_lo = (long long)L * h * w * 3;
+    E2_REQUIRE(!ranges_overlap(out, n_out, src, n_out) && !ranges_overlap(out, n_out, lo, n_lo) &&
+                   !ranges_overlap(out, n_out, mask_lo, n_lo / 3),
+               E2FGVI_EINVAL, "restore_u8: out must not overlap src, lo or mask_lo");
+    const dim3 grid((unsigned)((W + RT_W - 1) / RT_W), (unsigned)((H + RT_H - 1) / RT_H), (unsigned)(L < 1024 ? L : 1024));
+    hipLaunchKernelGGL(restore_u8_kernel, grid, dim3(NTH), 0, (hipStream_t)stream, lo, mask_lo, src, out, L, h, w, H, W, ytab, xtab,
+                       bounds_x, coeffs_x, ksize_x, bounds_y, coeffs_y, ksize_y);
+    E2_LAUNCH_CHECK("restore_u8");
+    return 0;
+}
 
 extern "C" int e2fgvi_gather_slabs(const void* cache, int32_t slots, const int32_t* ids, int32_t n, int64_t slab_bytes, void* window,
                                    void* stream) {

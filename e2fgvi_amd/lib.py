@@ -112,6 +112,7 @@ SYMBOLS = {
     "e2fgvi_masked_clip": (C.c_int, [_fp, _fp, _fp, _i32, _i32, _i32, _fp, _i32, _i32, _fp]),
     "e2fgvi_composite": (C.c_int, [_fp, _fp, _fp, _i32, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _fp]),
     "e2fgvi_resample_u8": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, _fp, _fp, _i32, _fp]),
+    "e2fgvi_restore_u8": (C.c_int, [_fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _fp, _fp, _fp, _fp, _i32, _fp, _fp, _i32, _fp]),
     "e2fgvi_float_to_u8": (C.c_int, [_fp, _fp, _i64, _fp]),
     "e2fgvi_pred_to_u8": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, _fp]),
     "e2fgvi_gather_slabs": (C.c_int, [_fp, _i32, _fp, _i32, _i64, _fp, _fp]),

@@ -1617,6 +1617,44 @@ def resample_u8(frames_u8, n_out, axis, bounds, coeffs):
     return out
 
 
+def restore_u8(lo, mask_lo, src, ytab, xtab, bx, cx, by, cy, out=None):
+    """out = where(NEAREST(mask_lo) != 0, BICUBIC(lo), src) at the size of src, one fused launch (csrc/video.hip): lo [L,h,w,3]
+    finished frames, mask_lo [L,h,w] of 0 / 1, src [L,H,W,3], all uint8; ytab int32 [H] / xtab int32 [W] from video.nearest_table;
+    bx int32 [W,2], cx int32 [W,kx] and by int32 [H,2], cy int32 [H,ky] from video.bicubic_tables, or the one-tap identity for an
+    axis that keeps its size.  Returns a fresh uint8 [L,H,W,3] unless `out` is given; out must not overlap the inputs."""
+    lib = _L.load()
+    _u8(lo, "lo"); _u8(mask_lo, "mask_lo"); _u8(src, "src")
+    tabs = (("ytab", ytab), ("xtab", xtab), ("bx", bx), ("cx", cx), ("by", by), ("cy", cy))
+    for name, t in tabs:
+        _chk(t, name, torch.int32)
+    if lo.dim() != 4 or lo.shape[3] != 3 or src.dim() != 4 or src.shape[3] != 3 or mask_lo.dim() != 3:
+        raise ValueError("lo and src must be [L,.,.,3] and mask_lo [L,.,.], got %s, %s and %s"
+                         % (tuple(lo.shape), tuple(src.shape), tuple(mask_lo.shape)))
+    L, h, w, _ = lo.shape
+    H, W = src.shape[1], src.shape[2]
+    if src.shape[0] != L or tuple(mask_lo.shape) != (L, h, w) or min(L, h, w, H, W) < 1:
+        raise ValueError("lo %s, mask_lo %s and src %s do not belong to one video" % (tuple(lo.shape), tuple(mask_lo.shape),
+                                                                                       tuple(src.shape)))
+    if any(t.device != lo.device for t in (mask_lo, src) + tuple(t for _, t in tabs)):
+        raise ValueError("lo, mask_lo, src and the tables must be on one device")
+    if ytab.dim() != 1 or ytab.numel() != H or xtab.dim() != 1 or xtab.numel() != W:
+        raise ValueError("ytab / xtab must have H = %d / W = %d entries" % (H, W))
+    for n_in, n_out, b, c, ax in ((w, W, bx, cx, "x"), (h, H, by, cy, "y")):
+        if tuple(b.shape) != (n_out, 2) or c.dim() != 2 or c.shape[0] != n_out:
+            raise ValueError("b%s must be [%d,2] and c%s [%d,ksize]" % (ax, n_out, ax, n_out))
+        if c.shape[1] != 2 * math.ceil(2.0 * max(n_in / n_out, 1.0)) + 1 and not (n_in == n_out and c.shape[1] == 1):
+            raise ValueError("c%s of %d taps does not belong to a %d -> %d resize" % (ax, c.shape[1], n_in, n_out))
+    if out is None:
+        out = torch.empty((L, H, W, 3), dtype=torch.uint8, device=src.device)
+    else:
+        _u8(out, "out")
+        if tuple(out.shape) != (L, H, W, 3) or out.device != src.device:
+            raise ValueError("out must be uint8 %s on the device of src" % ((L, H, W, 3),))
+    _L.check(lib.e2fgvi_restore_u8(_ptr(lo), _ptr(mask_lo), _ptr(src), _ptr(out), L, h, w, H, W, _ptr(ytab), _ptr(xtab), _ptr(bx),
+                                   _ptr(cx), cx.shape[1], _ptr(by), _ptr(cy), cy.shape[1], _stream()), "restore_u8")
+    return out
+
+
 def float_to_u8(x):
     lib = _L.load()
     _chk(x, "x")

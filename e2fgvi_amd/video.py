@@ -198,6 +198,42 @@ def resize_frames(frames_u8, size, device=None):
     return x
 
 
+def _axis_tables(n_in, n_out):
+    """bicubic_tables, or the one-tap identity for an axis that keeps its size (Pillow runs no pass over it)"""
+    if n_in == n_out:
+        return np.stack([np.arange(n_out), np.ones(n_out)], 1).astype(np.int32), np.full((n_out, 1), 1 << 22, np.int32)
+    return bicubic_tables(n_in, n_out)
+
+
+def restore_frames(lo_u8, masks01_lo, src_u8, device=None):
+    """The finished frames back at the size of the caller's video: every frame of ``lo_u8`` (uint8 [L,h,w,3], what
+    inpaint_video(size=...) returns) is upscaled like PIL ``Image.resize((W, H))`` (BICUBIC) and pasted into ``src_u8`` (uint8
+    [L,H,W,3]) where the mask the model saw -- ``masks01_lo`` uint8 [L,h,w] of 0 / 1, prepare_masks's output -- is set after PIL's
+    ``resize((W, H), Image.NEAREST)``; every other byte of the result is the byte of src_u8.  One fused launch (ops.restore_u8:
+    tiles without a hole pixel are plain copies), bit-exact with the three PIL / numpy lines it replaces; with (H, W) == (h, w)
+    it is where(mask, lo, src).  Arrays and tensors alike, uploaded unless on the device already.  Returns device uint8
+    [L,H,W,3]."""
+    def up(a):
+        if isinstance(a, torch.Tensor) and a.is_cuda:
+            return a.contiguous() if device is None else a.to(device).contiguous()
+        return torch.as_tensor(np.ascontiguousarray(a)).to(device if device is not None else torch.device("cuda"))
+
+    for name, a, nd in (("lo", lo_u8, 4), ("masks", masks01_lo, 3), ("src", src_u8, 4)):
+        shape = tuple(a.shape)
+        if len(shape) != nd or (nd == 4 and shape[3] != 3):
+            raise ValueError("%s must be uint8 %s, got %s" % (name, "[L,.,.,3]" if nd == 4 else "[L,.,.]", shape))
+    if not (lo_u8.shape[0] == masks01_lo.shape[0] == src_u8.shape[0]):
+        raise ValueError("lo, masks and src must hold the same number of frames, got %d, %d and %d"
+                         % (lo_u8.shape[0], masks01_lo.shape[0], src_u8.shape[0]))
+    if tuple(masks01_lo.shape[1:]) != tuple(lo_u8.shape[1:3]):
+        raise ValueError("masks %s do not have the size of lo %s" % (tuple(masks01_lo.shape), tuple(lo_u8.shape)))
+    lo, m, src = up(lo_u8), up(masks01_lo), up(src_u8)
+    (h, w), (H, W) = lo.shape[1:3], src.shape[1:3]
+    dev = src.device
+    tabs = [nearest_table(h, H), nearest_table(w, W)] + list(_axis_tables(w, W)) + list(_axis_tables(h, H))
+    return ops.restore_u8(lo, m, src, *[torch.from_numpy(t).to(dev) for t in tabs])
+
+
 def prepare_masks(masks_u8, size_hw, device, dilate=True):
     """uint8 masks [L,Hin,Win] (any size, any non-zero = hole) -> device uint8 [L,H,W] of 0/1 like test.py:56-69."""
     m = torch.as_tensor(np.ascontiguousarray(masks_u8)).to(device)
@@ -209,7 +245,7 @@ def prepare_masks(masks_u8, size_hw, device, dilate=True):
 
 @torch.no_grad()
 def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, num_ref=-1, dilate=True,
-                  device=None, pad=True, batch_windows=1, keep_float=False, in_flight=1, size=None, reuse=False):
+                  device=None, pad=True, batch_windows=1, keep_float=False, in_flight=1, size=None, reuse=False, restore=False):
     """frames_u8: uint8 [L,H,W,3]; masks_u8: [L,Hm,Wm] (non-zero = hole; resized to the frames with NEAREST like
     read_mask).  Returns uint8 [L,H,W,3] composited frames, computed like test.py:129-179.
     ``model(masked[b,t,3,H',W'], n_local) -> (pred[b*t,3,H',W'], _)`` on the device.
@@ -237,7 +273,20 @@ def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, 
     (an object with ``engine()``; anything else raises TypeError).  The launches on a few new frames can pick other kernels from
     the size-class table than those on a whole window, and different kernels round differently: the result is the reference
     loop's within the driver's usual tolerance, not the bytes of reuse=False.  One window at a time: reuse=True with
-    batch_windows > 1 or in_flight > 1 raises ValueError (the caches are filled and read in window order on one stream)."""
+    batch_windows > 1 or in_flight > 1 raises ValueError (the caches are filled and read in window order on one stream).
+
+    ``restore`` = True (with ``size``): the result comes back at the size of ``frames_u8`` instead of ``size`` -- the finished
+    frames are upscaled like PIL ``Image.resize`` (BICUBIC) and pasted into the hole of the caller's frames, the mask the model
+    saw (after the dilation) scaled up with NEAREST; every byte outside it is the caller's (restore_frames, one fused launch
+    after the window loop of whichever driver ran).  The caller's frames stay on the device beside the resized ones and are not
+    modified.  restore=True without size, or with keep_float=True (the paste works on the bytes test.py would have written),
+    raises ValueError."""
+    if restore:
+        if size is None:
+            raise ValueError("restore=True pastes the result back into frames that size= resized: without size there is nothing "
+                             "to restore")
+        if keep_float:
+            raise ValueError("restore=True returns uint8 frames at the source size: keep_float must be False")
     if reuse:
         if batch_windows > 1:
             raise ValueError("reuse=True runs one window per forward: batch_windows must be 1, got %d" % batch_windows)
@@ -251,7 +300,11 @@ def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, 
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError("inpaint_video runs on the MI355X (cuda) device only; there is no CPU path")
-    frames_d = torch.as_tensor(np.ascontiguousarray(frames_u8)).to(device)
+    if isinstance(frames_u8, torch.Tensor) and frames_u8.is_cuda:
+        frames_d = frames_u8.to(device).contiguous()
+    else:
+        frames_d = torch.as_tensor(np.ascontiguousarray(frames_u8)).to(device)
+    source = frames_d                                   # restore=True: kept beside the resized frames, only read
     if size is not None:
         frames_d = resize_frames(frames_d, size)        # on the caller's stream, before any stream below waits on it
     L, h, w, _ = frames_d.shape
@@ -371,4 +424,6 @@ def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, 
         assert not pending and nxt == len(windows)
     if keep_float:
         return comp
+    if restore:
+        return restore_frames(ops.float_to_u8(comp), masks01, source).cpu().numpy()
     return ops.float_to_u8(comp).cpu().numpy()

@@ -55,6 +55,19 @@ int e2fgvi_composite(const float* pred, const int32_t* ids, const uint8_t* first
  * Pillow runs the W pass first and each pass only if that dimension changes. */
 int e2fgvi_resample_u8(const uint8_t* src, uint8_t* dst, int32_t L, int32_t H, int32_t W, int32_t n_out, int32_t axis,
                        const int32_t* bounds, const int32_t* coeffs, int32_t ksize, void* stream);
+/* The paste-back that follows test.py:168-179 when test.py:97-104,127 resized the frames on the way in (the reference stops at
+ * the resized video; a front end writes the result at source size): for every frame
+ *   out = where(Image.fromarray(mask_lo * 255).resize((W, H), NEAREST) != 0, Image.fromarray(lo).resize((W, H)), src)
+ * lo [L,h,w,3] finished frames, mask_lo [L,h,w] of 0 / 1 (e2fgvi_mask_prepare's output), src / out [L,H,W,3], all uint8.  One
+ * fused launch: tiles of `out` without a hole pixel are copied src -> out, the others recompute Pillow's two BICUBIC passes
+ * (width first, its uint8 result clamped, then height) from a patch of lo.  ytab[H] / xtab[W]: NEAREST tables as for
+ * e2fgvi_mask_prepare; bounds_x[W][2], coeffs_x[W][ksize_x] and bounds_y[H][2], coeffs_y[H][ksize_y]: tap tables as for
+ * e2fgvi_resample_u8; an axis that keeps its size takes the identity -- bounds (o, 1), coeffs 1 << 22, ksize 1 -- as Pillow
+ * skips that pass.  Table entries are clipped in the kernel.  out must not overlap src, lo or mask_lo (E2FGVI_EINVAL). */
+int e2fgvi_restore_u8(const uint8_t* lo, const uint8_t* mask_lo, const uint8_t* src, uint8_t* out, int32_t L, int32_t h, int32_t w,
+                      int32_t H, int32_t W, const int32_t* ytab, const int32_t* xtab, const int32_t* bounds_x,
+                      const int32_t* coeffs_x, int32_t ksize_x, const int32_t* bounds_y, const int32_t* coeffs_y, int32_t ksize_y,
+                      void* stream);
 /* ndarray.astype(uint8) of the blended frames (truncation) */
 int e2fgvi_float_to_u8(const float* src, uint8_t* dst, int64_t n, void* stream);
 /* model output [N,3,Hp,Wp] in (-1,1) -> uint8 NHWC [N,H,W,3] = uint8((pred+1)/2*255): the form the clip-sharded runner
