@@ -5,6 +5,7 @@ hand-written HIP kernels behind the C ABI (include/e2fgvi_hip.h).  Activations a
 ``[N, H, W, ld]`` fp32 contiguous CUDA tensors.  Every wrapper validates device / dtype / layout
 and raises on error -- there is no eager fallback.
 """
+import collections
 import ctypes as C
 import math
 import os
@@ -56,7 +57,7 @@ XTUNE_ROWSHIFT = (11, 16, 17, 12, 13, 18)
 # fp32 layers on the bf16 matrix pipe by exact operand splitting (conv_bf16x.hip MODE 2, PackedConvX(x3=True)): a tuning
 # alternative of every fp32 layer that asks for it (PackedConv.try_x3 / PackedConvX.try_x3); taken when its best tile beats
 # the fp32 kernel of the call by more than X3_MARGIN.  Tile codes X3_BASE + tile in the decision table (clear of the Winograd
-# code 2464 and of the 2000 + tile codes of the LDS-DMA fp32 kernel).  E2FGVI_X3=0: never.
+# code 2464 and of the DMA_BASE + tile codes of the LDS-DMA fp32 kernel).  E2FGVI_X3=0: never.
 X3_ENABLED = os.environ.get("E2FGVI_X3", "1") != "0"
 X3_MARGIN = 0.97
 X3_BASE = 30000
@@ -75,6 +76,28 @@ W3_CANDIDATES = (132, 164, 32, 5132, 6064)
 #  are gone since round 6; what remains selectable from the environment is listed once)
 W3_WIDE = 6064
 W3_WIDE_FALLBACK = 164
+# the LDS-DMA fp32 GEMM (PackedConvX on fp32 operands) as the alternative of a tuned PackedConv: codes DMA_BASE + its tile
+DMA_BASE = 2000
+
+
+def _decode(code):
+    """(family, arg) of a tile code -- the one place that knows the number space of the decision table and of the `tile` argument:
+    "own"  the layer's own kernel, arg = its tile (0: the library's static choice; Winograd block shapes; halo ids from 10000)
+    "w4"   the wide-tile fp32 Winograd kernel, arg = the code itself, a key of W4_CODES
+    "dma"  the LDS-DMA fp32 GEMM, arg = code - DMA_BASE, its tile
+    "x3"   the split-operand GEMM, arg = code - X3_BASE, its tile
+    "w3"   the split-operand Winograd kernel, arg = code - W3_BASE, its block shape"""
+    if code >= W3_BASE:
+        return "w3", code - W3_BASE
+    if code >= X3_BASE:
+        return "x3", code - X3_BASE
+    if code in W4_CODES:
+        return "w4", code
+    if DMA_BASE <= code < DMA_BASE + 100:
+        return "dma", code - DMA_BASE
+    return "own", code
+
+
 _TUNED = {}      # (layer geometry, input size class) -> tile code; shared by all layers of the same geometry (the 8 blocks)
 # Kernel selection is DETERMINISTIC by default (round 4): the decisions come from the checked-in table e2fgvi_amd/tile_table.py
 # (generated on an MI355X by tools/make_tile_table.py from timed runs of the BASELINE configurations), looked up by layer
@@ -233,12 +256,140 @@ def _lazy(store, key, what, build):
     return obj
 
 
-class PackedConv:
+def _time_launches(launch, reps):
+    """device time in ms per launch of `reps` back-to-back `launch()` calls on the current stream (hip events); the one event
+    loop of table generation"""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        launch()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def _pack_weights(size_fn, pack_fn, src, dtype, what, *geom, extra=()):
+    """`src` (fp32 checkpoint weights) re-laid-out for one kernel: the library's size query `size_fn(*geom)`, a `dtype` tensor of
+    that many elements on src's device, filled by `pack_fn(src, dst, *geom, *extra, stream)`.  `what` names both in error messages."""
+    n = size_fn(*geom)
+    if n < 0:
+        _L.check(int(n), "packed_%s_size" % what)
+    t = torch.empty(int(n), dtype=dtype, device=src.device)
+    _L.check(pack_fn(_ptr(src), _ptr(t), *geom, *extra, _stream()), "pack_" + what)
+    return t
+
+
+def _image_chunks(N, per_img):
+    """(n0, n1) image ranges of a batch whose kernel addresses each tensor through a 32-bit buffer resource: a batch that spans
+    >= 4 GiB (`per_img` bytes per image in its largest tensor) is processed in chunks of images -- images are independent"""
+    step = max(1, N)
+    if N > 1 and N * per_img >= (1 << 32) - 1:
+        step = max(1, ((1 << 32) - 2) // per_img)
+    for n0 in range(0, N, step):
+        yield n0, min(N, n0 + step)
+
+
+class _ConvLayer:
+    """What the two conv / linear layer classes share: the layer geometry, the image chunks and the call descriptor's common
+    fields (ConvDesc and ConvXDesc agree on them by name)."""
+
+    def _init_layer(self, weight, bias, cpg, groups, stride, pad):
+        """geometry, bias and the defaults the engine overwrites; returns the fp32 OIHW weight (a Linear's [Cout, Cin] as 1x1)"""
+        if weight.dim() == 2:
+            weight = weight[:, :, None, None]
+        w = _chk(weight.detach().float().contiguous(), "weight")
+        self.Cout, cin_g, self.KH, self.KW = w.shape
+        self.cpg = [int(c) for c in cpg]
+        if sum(self.cpg) != cin_g:
+            raise ValueError("sum(cpg)=%d != weight input channels %d" % (sum(self.cpg), cin_g))
+        self.groups, self.stride, self.pad = groups, stride, pad
+        self.bias = None if bias is None else _chk(bias.detach().float().contiguous(), "bias")
+        self.name = "conv"         # layer name for launch traces (the engine sets the checkpoint key)
+        self.tune = False          # take the tile from the decision table (E2FGVI_AUTOTUNE=1: time the candidates per size class)
+        self.try_x3 = False        # fp32 layers: the split-bf16 kernels (PackedConvX x3, codes X3_BASE + tile) are alternatives
+        self.alt3 = None
+        return w
+
+    def out_hw(self, H, W):
+        return ((H + 2 * self.pad - self.KH) // self.stride + 1, (W + 2 * self.pad - self.KW) // self.stride + 1)
+
+    def _cpg_arr(self):
+        return (C.c_int32 * len(self.cpg))(*self.cpg)
+
+    def _srcs_out(self, sources, out, out_nchw, out_dtype):
+        """the sources as (tensor, channel offset) pairs, and `out` -- a fresh tensor if the caller gave none"""
+        srcs = [(s, 0) if isinstance(s, torch.Tensor) else s for s in sources]
+        if len(srcs) != len(self.cpg):
+            raise ValueError("expected %d sources, got %d" % (len(self.cpg), len(srcs)))
+        if out is None:
+            N, H, W, _ = srcs[0][0].shape
+            Ho, Wo = self.out_hw(H, W)
+            out = torch.empty((N, self.Cout, Ho, Wo) if out_nchw else (N, Ho, Wo, self.Cout),
+                              dtype=torch.float32 if out_nchw else out_dtype, device=srcs[0][0].device)
+        return srcs, out
+
+    def _x_alternative(self, **kw):
+        """this fp32 layer as a PackedConvX on fp32 operands (the build function of the _alt / _alt3 accessors)"""
+        alt = PackedConvX(self._w_raw, self.bias, self.cpg, groups=self.groups, stride=self.stride, pad=self.pad, dtype=torch.float32, **kw)
+        alt.name = self.name
+        return alt
+
+    def _fill(self, d, src_dtype, chk, srcs, out, out_coff, act, slope, out_nchw):
+        """validates sources (`src_dtype`) and out (by `chk`: _chk or _chk_any) and fills the fields ConvDesc and ConvXDesc have
+        in common; the residual's follow from _fill_residual"""
+        N, H, W, _ = srcs[0][0].shape
+        Ho, Wo = self.out_hw(H, W)
+        for i, (t, coff) in enumerate(srcs):
+            _chk(t, "source %d" % i, src_dtype)
+            if t.dim() != 4 or tuple(t.shape[:3]) != (N, H, W):
+                raise ValueError("source %d shape %s does not match [%d,%d,%d,*]" % (i, tuple(t.shape), N, H, W))
+            d.src[i], d.src_ld[i], d.src_coff[i], d.src_cpg[i] = t.data_ptr(), t.shape[3], coff, self.cpg[i]
+        d.nsrc = len(srcs)
+        d.N, d.H, d.W, d.Ho, d.Wo = N, H, W, Ho, Wo
+        d.KH, d.KW, d.stride, d.pad = self.KH, self.KW, self.stride, self.pad
+        d.groups, d.Cout = self.groups, self.Cout
+        d.bias = self.bias.data_ptr() if self.bias is not None else None
+        chk(out, "out")
+        if out_nchw:
+            if tuple(out.shape) != (N, self.Cout, Ho, Wo) or out.dtype != torch.float32:
+                raise ValueError(self._NCHW_ERROR % dict(got=tuple(out.shape), want=(N, self.Cout, Ho, Wo)))
+            d.dst_ld, d.dst_coff, d.dst_nchw = 0, 0, 1
+        else:
+            if out.dim() != 4 or tuple(out.shape[:3]) != (N, Ho, Wo):
+                raise ValueError("out shape %s != [%d,%d,%d,*]" % (tuple(out.shape), N, Ho, Wo))
+            d.dst_ld, d.dst_coff, d.dst_nchw = out.shape[3], out_coff, 0
+        d.dst = out.data_ptr()
+        d.act, d.slope, d.tile = act, slope, 0
+        return d
+
+    @staticmethod
+    def _fill_residual(d, chk, residual, res_coff):
+        if residual is not None:
+            chk(residual, "residual")
+            if residual.dim() != 4 or tuple(residual.shape[:3]) != (d.N, d.Ho, d.Wo):
+                raise ValueError("residual shape %s != [%d,%d,%d,*]" % (tuple(residual.shape), d.N, d.Ho, d.Wo))
+            d.residual, d.res_ld, d.res_coff = residual.data_ptr(), residual.shape[3], res_coff
+
+
+# what PackedConv._select hands to PackedConv._launch: the kernel family and tile to run (_decode), the static rule's (family,
+# tile) that a rejected alternative falls back to, whether the decision came from the table, whether the call is a Winograd one
+_Plan = collections.namedtuple("_Plan", "family tile static from_table use_wino")
+# one PackedConv call on its way through the steps: the C descriptor, the sources as (tensor, channel offset) pairs, the call's
+# other arguments by keyword (as PackedConvX.__call__ and both _desc take them) and the K / V planes to write, or None
+_Call = collections.namedtuple("_Call", "d srcs kw kv_planes")
+
+
+class PackedConv(_ConvLayer):
     """A conv / linear layer with weights re-laid-out once for the MFMA kernel.
 
     weight: torch OIHW ``[Cout, sum(cpg), KH, KW]`` (a Linear weight ``[Cout, Cin]`` is 1x1).
     cpg:    channels per group contributed by each source of the virtual input concat.
+
+    A call is four steps: _desc (the C descriptor), _select (static rule and decision table -> a _Plan; _tune times the
+    candidates for a new table row under E2FGVI_AUTOTUNE=1), _launch.
     """
+
+    _NCHW_ERROR = "NCHW out shape %(got)s != %(want)s"
 
     def __init__(self, weight, bias, cpg, groups=1, stride=1, pad=0, bk=None, precision="fp32", algo="igemm"):
         """precision: "fp32" only: fp32 tensors and fp32-level rounding -- the layer's own kernels are fp32 MFMA (bit-equivalent
@@ -248,41 +399,30 @@ class PackedConv:
         algo: "igemm" (implicit GEMM), "winograd" (fp32 F(2x2,3x3) only; 3x3 / stride 1 / pad 1, every cpg % 4 == 0,
         even H and W at call time, NHWC output) or "auto" (both packings; Winograd whenever a call qualifies)."""
         lib = _L.load()
-        if weight.dim() == 2:
-            weight = weight[:, :, None, None]
-        w = _chk(weight.detach().float().contiguous(), "weight")
-        self.Cout, cin_g, self.KH, self.KW = w.shape
-        self.cpg = [int(c) for c in cpg]
-        if sum(self.cpg) != cin_g:
-            raise ValueError("sum(cpg)=%d != weight input channels %d" % (sum(self.cpg), cin_g))
-        self.groups, self.stride, self.pad = groups, stride, pad
+        w = self._init_layer(weight, bias, cpg, groups, stride, pad)
         if precision != "fp32":
             raise ValueError("PackedConv is the fp32 layer; the bf16 data path uses PackedConvX")
         self.precision = precision
-        self.tune = False          # time TUNE_CANDIDATES on the first call of every new input size and keep the fastest
-        self.name = "conv"         # layer name for launch traces (the engine sets the checkpoint key)
         self.nopk = False          # True: the build without packed-fp32 VALU (side-stream launches beside bf16 MFMA tiles)
-        self.try_x3 = False        # True: time the split-bf16 kernel (PackedConvX x3) against this layer's fp32 kernel, keep the faster
-        self.alt = self.alt3 = None
+        self.alt = None
         self._w_raw = w            # for the alternative LDS-DMA kernels (built on the first tuned call)
         if algo not in ("igemm", "winograd", "auto"):
             raise ValueError("algo must be 'igemm', 'winograd' or 'auto'")
-        wino_ok = precision == "fp32" and (self.KH, self.KW, stride, pad) == (3, 3, 1, 1) and not any(c % 4 for c in self.cpg)
+        wino_ok = (self.KH, self.KW, stride, pad) == (3, 3, 1, 1) and not any(c % 4 for c in self.cpg)
         if algo == "winograd" and not wino_ok:
             raise ValueError("winograd needs fp32, 3x3 / stride 1 / pad 1 and channels per source in multiples of 4")
         if algo == "auto":
             algo = "auto" if wino_ok else "igemm"
         self.algo = algo
         self._w4 = {}              # fy -> packed F(fy x 4, 3x3) weights, built on first use
+        self._w3 = None            # packed weights of the split-bf16 Winograd kernel, built on first use
         self._w_oihw = w if algo in ("winograd", "auto") else None
         # every packing (implicit GEMM, Winograd F(2x2), F(2x4), the three-plane split ones, the LDS-DMA alternatives) is built from
         # _w_raw on the first call that runs it: with the kernel table (tile_table.py) a layer holds the packing of the kernel it
         # runs and nothing else; E2FGVI_AUTOTUNE=1 builds every candidate's (DESIGN.md, weight memory)
         self._own = {}
-        self.bias = None if bias is None else _chk(bias.detach().float().contiguous(), "bias")
-        arr = (C.c_int32 * len(self.cpg))(*self.cpg)
         if algo in ("winograd", "auto"):       # a geometry the library rejects raises here, not on the first call
-            _L.check(min(0, int(lib.e2fgvi_packed_winograd_weight_size(self.Cout, groups, len(self.cpg), arr))), "packed_winograd_weight_size")
+            _L.check(min(0, int(lib.e2fgvi_packed_winograd_weight_size(*self._wgeom()))), "packed_winograd_weight_size")
         if algo == "winograd":
             self.bk = 8
             return
@@ -292,8 +432,12 @@ class PackedConv:
             pad16 = sum((c + 15) // 16 * 16 for c in self.cpg)
             bk = 32 if pad32 <= 1.08 * sum(self.cpg) else (16 if pad16 <= 1.08 * sum(self.cpg) else 8)
         self.bk = bk
-        _L.check(min(0, int(lib.e2fgvi_packed_conv_weight_size(self.Cout, groups, self.KH, self.KW, len(self.cpg), arr, bk))),
+        _L.check(min(0, int(lib.e2fgvi_packed_conv_weight_size(self.Cout, groups, self.KH, self.KW, len(self.cpg), self._cpg_arr(), bk))),
                  "packed_conv_weight_size")
+
+    def _wgeom(self):
+        """the geometry arguments the Winograd packers share"""
+        return self.Cout, self.groups, len(self.cpg), self._cpg_arr()
 
     @property
     def wino_packed(self):
@@ -303,14 +447,8 @@ class PackedConv:
 
         def build():
             lib = _L.load()
-            arr = (C.c_int32 * len(self.cpg))(*self.cpg)
-            n = lib.e2fgvi_packed_winograd_weight_size(self.Cout, self.groups, len(self.cpg), arr)
-            if n < 0:
-                _L.check(int(n), "packed_winograd_weight_size")
-            t = torch.empty(int(n), dtype=torch.float32, device=self._w_raw.device)
-            _L.check(lib.e2fgvi_pack_winograd_weight(_ptr(self._w_raw), _ptr(t), self.Cout, self.groups, len(self.cpg), arr,
-                                                     _stream()), "pack_winograd_weight")
-            return t
+            return _pack_weights(lib.e2fgvi_packed_winograd_weight_size, lib.e2fgvi_pack_winograd_weight, self._w_raw, torch.float32,
+                                 "winograd_weight", *self._wgeom())
         return _lazy(self._own, "wino", self.name + " (Winograd F(2x2,3x3) weights)", build)
 
     @property
@@ -321,33 +459,21 @@ class PackedConv:
 
         def build():
             lib = _L.load()
-            arr = (C.c_int32 * len(self.cpg))(*self.cpg)
-            n = lib.e2fgvi_packed_conv_weight_size(self.Cout, self.groups, self.KH, self.KW, len(self.cpg), arr, self.bk)
-            if n < 0:
-                _L.check(int(n), "packed_conv_weight_size")
-            t = torch.empty(int(n), dtype=torch.float32, device=self._w_raw.device)
-            _L.check(lib.e2fgvi_pack_conv_weight(_ptr(self._w_raw), _ptr(t), self.Cout, self.groups, self.KH, self.KW,
-                                                 len(self.cpg), arr, self.bk, _stream()), "pack_conv_weight")
-            return t
+            return _pack_weights(lib.e2fgvi_packed_conv_weight_size, lib.e2fgvi_pack_conv_weight, self._w_raw, torch.float32,
+                                 "conv_weight", self.Cout, self.groups, self.KH, self.KW, len(self.cpg), self._cpg_arr(), self.bk)
         return _lazy(self._own, "igemm", self.name + " (implicit-GEMM weights)", build)
 
     def weight_bytes(self):
         """device bytes of the packings this layer holds right now (the checkpoint tensor _w_raw not counted)"""
-        ts = list(self._own.values()) + list(self._w4.values()) + ([self._w3] if getattr(self, "_w3", None) is not None else [])
+        ts = list(self._own.values()) + list(self._w4.values()) + ([self._w3] if self._w3 is not None else [])
         return sum(t.numel() * t.element_size() for t in ts) + sum(a.weight_bytes() for a in (self.alt, self.alt3) if a is not None)
 
     def _wino4(self, fy):
         """packed weights of the wide-tile Winograd kernel (conv_wino4.hip), built on first use"""
         def build():
             lib = _L.load()
-            arr = (C.c_int32 * len(self.cpg))(*self.cpg)
-            n = lib.e2fgvi_packed_winograd4_weight_size(self.Cout, self.groups, len(self.cpg), arr, fy)
-            if n < 0:
-                _L.check(int(n), "packed_winograd4_weight_size")
-            t = torch.empty(int(n), dtype=torch.float32, device=self._w_oihw.device)
-            _L.check(lib.e2fgvi_pack_winograd4_weight(_ptr(self._w_oihw), _ptr(t), self.Cout, self.groups, len(self.cpg), arr, fy,
-                                                      _stream()), "pack_winograd4_weight")
-            return t
+            return _pack_weights(lib.e2fgvi_packed_winograd4_weight_size, lib.e2fgvi_pack_winograd4_weight, self._w_oihw, torch.float32,
+                                 "winograd4_weight", *self._wgeom(), fy)
         return _lazy(self._w4, fy, self.name + " (Winograd F(%dx4,3x3) weights)" % fy, build)
 
     def _wino4_rule(self, N, H, W):
@@ -364,15 +490,7 @@ class PackedConv:
 
     def _alt(self):
         """the LDS-DMA fp32 kernel (conv_bf16x.hip, F32 variant) as a tuning alternative of the implicit GEMM"""
-        if getattr(self, "_w_raw", None) is None:
-            return self.alt
-
-        def build():
-            alt = PackedConvX(self._w_raw, self.bias, self.cpg, groups=self.groups, stride=self.stride, pad=self.pad,
-                              dtype=torch.float32)
-            alt.name = self.name
-            return alt
-        return _lazy(vars(self), "alt", self.name + " (LDS-DMA fp32 alternative)", build)
+        return _lazy(vars(self), "alt", self.name + " (LDS-DMA fp32 alternative)", self._x_alternative)
 
     def _wino_x3(self):
         """packed weights of the split-bf16 Winograd kernel (three bf16 planes of the transformed weights), built on first use"""
@@ -381,84 +499,41 @@ class PackedConv:
 
         def build():
             lib = _L.load()
-            arr = (C.c_int32 * len(self.cpg))(*self.cpg)
-            n = lib.e2fgvi_packed_winograd_weight_x3_size(self.Cout, self.groups, len(self.cpg), arr)
-            if n < 0:
-                _L.check(int(n), "packed_winograd_weight_x3_size")
-            t = torch.empty(int(n), dtype=torch.bfloat16, device=self._w_oihw.device)
-            _L.check(lib.e2fgvi_pack_winograd_weight_x3(_ptr(self._w_oihw), _ptr(t), self.Cout, self.groups, len(self.cpg), arr,
-                                                        _stream()), "pack_winograd_weight_x3")
-            return t
+            return _pack_weights(lib.e2fgvi_packed_winograd_weight_x3_size, lib.e2fgvi_pack_winograd_weight_x3, self._w_oihw,
+                                 torch.bfloat16, "winograd_weight_x3", *self._wgeom())
         return _lazy(vars(self), "_w3", self.name + " (split-operand Winograd weights)", build)
 
     def _alt3(self):
         """the same layer on the bf16 matrix pipe (three-way split operands, six exact bf16 MFMA terms per product)"""
-        if getattr(self, "_w_raw", None) is None or any(c % 4 for c in self.cpg):
+        if any(c % 4 for c in self.cpg):
             return self.alt3
+        return _lazy(vars(self), "alt3", self.name + " (split-operand GEMM alternative)", lambda: self._x_alternative(x3=True))
 
-        def build():
-            alt3 = PackedConvX(self._w_raw, self.bias, self.cpg, groups=self.groups, stride=self.stride, pad=self.pad,
-                               dtype=torch.float32, x3=True)
-            alt3.name = self.name
-            return alt3
-        return _lazy(vars(self), "alt3", self.name + " (split-operand GEMM alternative)", build)
-
-    def _autotune(self, lib, d, wino=False):
-        """Device time of every candidate tile code on this exact call (2 launches each, hip events); the launches
-        rewrite the same output, so the result of the call is unaffected."""
-        best, best_ms = 0, float("inf")
-        st = _stream()
-        d.tile = 0
-        fn = lib.e2fgvi_conv3x3_winograd if wino else lib.e2fgvi_conv2d_nhwc
-        d.wpacked = (self.wino_packed if wino else self.wpacked).data_ptr()
-        for _ in range(3):                                       # bring clocks / caches to steady state first
-            fn(C.byref(d), st)
-        for code in (WINO_CANDIDATES if wino else TUNE_CANDIDATES):
-            d.tile = code
-            if fn(C.byref(d), st) != 0:                          # not instantiated / not applicable to this packing
-                continue
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ms = float("inf")
-            for _ in range(TUNE_REPS):                               # best of TUNE_REPS measurements of 2 launches
-                e0.record()
-                for _ in range(2):
-                    fn(C.byref(d), st)
-                e1.record()
-                e1.synchronize()
-                ms = min(ms, e0.elapsed_time(e1))
-            if ms < best_ms:
-                best, best_ms = code, ms
-        d.tile = 0
-        return best
-
-    def out_hw(self, H, W):
-        return ((H + 2 * self.pad - self.KH) // self.stride + 1, (W + 2 * self.pad - self.KW) // self.stride + 1)
-
-    def _work(self, N, H, W, Ho, Wo, use_wino, tile):
+    def _work(self, d, use_wino, family, tile):
         """Launch-trace record: algorithmic MACs (direct convolution) and the MACs the matrix pipe is ISSUED.
         Winograd F(2x2,3x3): 16 multiplies per 2x2 outputs and input channel instead of 36, on pixel blocks of 16x16 /
         8x16 and 32 / 64-wide cout tiles (the tile rule of e2fgvi_conv3x3_winograd), input channels in chunks of 8.
         Implicit GEMM: output channels padded to 32, every source's channels to the K granule."""
+        N, H, W, Ho, Wo = d.N, d.H, d.W, d.Ho, d.Wo
         cin_g, cout_g, K2 = sum(self.cpg), self.Cout // self.groups, self.KH * self.KW
         macs = N * Ho * Wo * self.Cout * cin_g * K2
-        asked = int(tile)                      # the tile code handed to the launcher (W3_BASE + block shape for the split Winograd kernel)
-        if use_wino and tile in W4_CODES:
+        asked = int(tile)                      # the tile code handed to the launcher
+        if family == "w4":
             fy, bn = W4_CODES[tile]
             pix = N * (-(-H // (8 * fy)) * 8 * fy) * (-(-W // 16) * 16)
             cin_p = sum(-(-c // 8) * 8 for c in self.cpg)
             # (fy+2)*6 positions per fy x 4 pixels
             issued = pix * (-(-cout_g // bn) * bn) * self.groups * cin_p * (fy + 2) * 6 // (fy * 4)
             kern = "conv_wino4<F(%dx4),%d>" % (fy, bn)
-        elif use_wino and tile >= W3_BASE:
-            shape = tile - W3_BASE
-            shape %= 1000
+        elif family == "w3":
+            asked = W3_BASE + tile             # (W3_BASE + block shape for the split Winograd kernel)
+            shape = tile % 1000
             mt, bn = (2, shape) if shape < 100 else (1, shape - 100)
             pix = N * (-(-H // (8 * mt)) * 8 * mt) * (-(-W // 16) * 16)
             cin_p = -(-sum(-(-c // 8) for c in self.cpg) // 2) * 16           # 16-channel stages
             # 16 positions per 4 pixels, six bf16 MACs per product, in fp32-pipe equivalents (see PackedConvX's trace record)
             issued = int(pix * (-(-cout_g // bn) * bn) * self.groups * cin_p * 4 * 6 * 157.3 / 2500.0)
-            code = tile - W3_BASE
-            kern = ("conv_wino_x3w<%d>" % bn) if code >= 6000 else ("conv_wino_x3p4<%d>" % bn) if code >= 5000 else "conv_wino_x3<%d,%d>" % (mt, bn)
+            kern = ("conv_wino_x3w<%d>" % bn) if tile >= 6000 else ("conv_wino_x3p4<%d>" % bn) if tile >= 5000 else "conv_wino_x3<%d,%d>" % (mt, bn)
         elif use_wino:
             if not tile:
                 big = N * -(-H // 16) * -(-W // 16) * -(-cout_g // 64) * self.groups
@@ -485,196 +560,173 @@ class PackedConv:
         fp32 K / V columns); any other kernel writes the fp32 rows and e2fgvi_split3_kv makes the planes from them."""
         if out_dtype not in (None, torch.float32):
             raise ValueError("PackedConv writes fp32 results")
-        lib = _L.load()
-        d = _L.ConvDesc()
-        srcs = [(s, 0) if isinstance(s, torch.Tensor) else s for s in sources]
-        if len(srcs) != len(self.cpg):
-            raise ValueError("expected %d sources, got %d" % (len(self.cpg), len(srcs)))
+        srcs, out = self._srcs_out(sources, out, out_nchw, torch.float32)
         N, H, W, _ = srcs[0][0].shape
-        # the kernel addresses each source through a 32-bit buffer resource: batches whose sources span >= 4 GiB
-        # are processed in image chunks (images are independent)
-        per_img = max(H * W * t.shape[3] * 4 for t, _ in srcs)
-        if N > 1 and N * per_img >= (1 << 32) - 1:
-            step = max(1, ((1 << 32) - 2) // per_img)
-            Ho, Wo = self.out_hw(H, W)
-            if out is None:
-                out = (torch.empty((N, self.Cout, Ho, Wo), dtype=torch.float32, device=srcs[0][0].device) if out_nchw
-                       else empty_nhwc(N, Ho, Wo, self.Cout, srcs[0][0].device))
-            for n0 in range(0, N, step):
-                n1 = min(N, n0 + step)
-                self([(t[n0:n1], c) for t, c in srcs], out=out[n0:n1], out_coff=out_coff,
-                     residual=None if residual is None else residual[n0:n1], res_coff=res_coff, act=act, slope=slope,
-                     out_nchw=out_nchw, tile=tile)
-            if kv_planes is not None:
-                split3_kv(out.view(-1, out.shape[-1]), out=kv_planes)
-            return out
-        for i, (t, coff) in enumerate(srcs):
-            _chk(t, "source %d" % i)
-            if t.dim() != 4 or tuple(t.shape[:3]) != (N, H, W):
-                raise ValueError("source %d shape %s does not match [%d,%d,%d,*]" % (i, tuple(t.shape), N, H, W))
-            d.src[i] = t.data_ptr()
-            d.src_ld[i] = t.shape[3]
-            d.src_coff[i] = coff
-            d.src_cpg[i] = self.cpg[i]
-        d.nsrc = len(srcs)
-        Ho, Wo = self.out_hw(H, W)
-        d.N, d.H, d.W, d.Ho, d.Wo = N, H, W, Ho, Wo
-        d.KH, d.KW, d.stride, d.pad = self.KH, self.KW, self.stride, self.pad
-        d.groups, d.Cout, d.bk = self.groups, self.Cout, self.bk
-        use_wino = self.algo == "winograd" or (self.algo == "auto" and H % 2 == 0 and W % 2 == 0 and not out_nchw
-                                               and (tile in (0, 32, 64, 132, 164) or tile in W4_CODES
-                                                    or tile >= W3_BASE))
-        w3_tile = None                         # block shape of the split-bf16 Winograd kernel, when that is what runs
-        if use_wino and tile >= W3_BASE:
-            w3_tile, tile = tile - W3_BASE, 0
-        auto_tile = tile == 0 and w3_tile is None      # the caller leaves the kernel choice to the layer
-        if use_wino and tile == 0:
-            tile = self._wino4_rule(N, H, W)
-        w4 = W4_CODES.get(tile) if use_wino else None
-        d.wpacked = None                       # set by whatever launches: a layer packs the weights of the kernels it runs, only
-        d.bias = self.bias.data_ptr() if self.bias is not None else None
-        dev = srcs[0][0].device
-        if out is None:
-            out = (torch.empty((N, self.Cout, Ho, Wo), dtype=torch.float32, device=dev) if out_nchw
-                   else empty_nhwc(N, Ho, Wo, self.Cout, dev))
-        _chk(out, "out")
-        if out_nchw:
-            if tuple(out.shape) != (N, self.Cout, Ho, Wo):
-                raise ValueError("NCHW out shape %s != %s" % (tuple(out.shape), (N, self.Cout, Ho, Wo)))
-            d.dst_ld, d.dst_coff, d.dst_nchw = 0, 0, 1
+        kw = dict(out_coff=out_coff, res_coff=res_coff, act=act, slope=slope, out_nchw=out_nchw)
+        chunks = list(_image_chunks(N, max(H * W * t.shape[3] * 4 for t, _ in srcs)))
+        if len(chunks) > 1:
+            for n0, n1 in chunks:
+                self([(t[n0:n1], c) for t, c in srcs], out=out[n0:n1], residual=None if residual is None else residual[n0:n1],
+                     tile=tile, **kw)
         else:
-            if out.dim() != 4 or tuple(out.shape[:3]) != (N, Ho, Wo):
-                raise ValueError("out shape %s != [%d,%d,%d,*]" % (tuple(out.shape), N, Ho, Wo))
-            d.dst_ld, d.dst_coff, d.dst_nchw = out.shape[3], out_coff, 0
-        d.dst = out.data_ptr()
-        if residual is not None:
-            _chk(residual, "residual")
-            if residual.dim() != 4 or tuple(residual.shape[:3]) != (N, Ho, Wo):
-                raise ValueError("residual shape %s != [%d,%d,%d,*]" % (tuple(residual.shape), N, Ho, Wo))
-            d.residual, d.res_ld, d.res_coff = residual.data_ptr(), residual.shape[3], res_coff
-        d.act, d.slope, d.tile = act, slope, tile
-        tile0 = tile                                   # the static rule's kernel: what a rejected alternative falls back to
-        w4c = W4_CODES.get(tile) if use_wino else None
-
-        def launch_w3(shape):
-            t0, w0 = d.tile, d.wpacked
-            d.tile, d.wpacked = shape, self._wino_x3().data_ptr()
-            rc = lib.e2fgvi_conv3x3_winograd_x3(C.byref(d), _stream())
-            d.tile, d.wpacked = t0, w0
-            return rc, "conv3x3_winograd_x3"
-
-        def launch():
-            if w3_tile is not None:
-                return launch_w3(w3_tile)
-            d.wpacked = (self._wino4(w4c[0]) if w4c else self.wino_packed if use_wino else self.wpacked).data_ptr()
-            if w4c:
-                t0 = d.tile
-                d.tile = w4c[1]
-                rc = lib.e2fgvi_conv3x3_winograd4(C.byref(d), w4c[0], _stream())
-                d.tile = t0
-                return rc, "conv3x3_winograd4"
-            if use_wino:
-                return lib.e2fgvi_conv3x3_winograd(C.byref(d), _stream()), "conv3x3_winograd"
-            if self.nopk:
-                return lib.e2fgvi_conv2d_nhwc_nopk(C.byref(d), _stream()), "conv2d_nhwc_nopk"
-            return lib.e2fgvi_conv2d_nhwc(C.byref(d), _stream()), "conv2d_nhwc"
-
-        # (a layer of the side stream may take it too: conv_bf16x.o is one of the packed-math-free objects, build.NOPK_OBJECTS)
-        x3 = self.try_x3 and X3_ENABLED
-        if auto_tile and (tile == 0 or not self.tune) and (self.tune or x3) and self.precision == "fp32" and N * Ho * Wo >= 2048:
-            # one decision per (layer geometry, size class): row counts within a quarter octave share the tile, so the
-            # slightly different window lengths of a video (t = 17 ... 21 frames) do not each pay for a tuning pass
-            # (the fp32 baseline the alternatives are measured against is part of the key: a tuned layer and an untuned one of the
-            #  same geometry, or the F(2x4) / F(2x2) Winograd baselines, do not share a verdict)
-            key = (self.Cout, tuple(self.cpg), self.KH, self.KW, self.stride, self.pad, self.groups, self.bk,
-                   int(4.0 * math.log2(N * Ho * Wo)), residual is not None, act, use_wino, bool(self.tune), int(tile)) + (("x3",) if x3 else ())
-            best = _decision(key)
-            from_table = best is not None
-            if best is None and AUTOTUNE and not torch.cuda.is_current_stream_capturing() and (
-                    residual is None or residual.data_ptr() != out.data_ptr()):
-                best = self._autotune(lib, d, use_wino) if self.tune else d.tile
-                mine = None
-
-                def time_mine():
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    launch()
-                    t = float("inf")
-                    for _ in range(TUNE_REPS):
-                        e0.record()
-                        for _ in range(3):
-                            launch()
-                        e1.record()
-                        e1.synchronize()
-                        t = min(t, e0.elapsed_time(e1) / 3)
-                    return t
-                if self.tune and not use_wino and not self.nopk and self._alt() is not None:
-                    # the LDS-DMA fp32 kernel on the very same call: codes 2000 + its tile
-                    d.tile = best
-                    mine = time_mine()
-                    res = self.alt._time_tiles(self.alt._desc(srcs, out, out_coff, residual, res_coff, act, slope, None, out_nchw))
-                    if res and min(res.values()) < mine:
-                        best, mine = 2000 + min(res, key=res.get), min(res.values())
-                if x3 and self._alt3() is not None:
-                    # ... and the split-bf16 kernel: codes X3_BASE + its tile
-                    if mine is None:
-                        d.tile = best
-                        mine = time_mine()
-                    d3 = self.alt3._desc(srcs, out, out_coff, residual, res_coff, act, slope, None, out_nchw)
-                    if kv_planes is not None:            # timed as it will run: with the K / V planes written by the epilogue
-                        self.alt3._set_planes(d3, kv_planes, self.Cout - kv_planes.shape[2], N * Ho * Wo)
-                    res = self.alt3._time_tiles(d3)
-                    if res and min(res.values()) < X3_MARGIN * mine:
-                        best, mine = X3_BASE + min(res, key=res.get), min(res.values())
-                if x3 and use_wino and self._wino_x3() is not None:
-                    # ... and the Winograd kernel with split operands: codes W3_BASE + its block shape
-                    w3 = {}
-                    for shape in W3_CANDIDATES:
-                        if launch_w3(shape)[0] != 0:
-                            continue
-                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                        w3[shape] = float("inf")
-                        for _ in range(TUNE_REPS):
-                            e0.record()
-                            for _ in range(3):
-                                launch_w3(shape)
-                            e1.record()
-                            e1.synchronize()
-                            w3[shape] = min(w3[shape], e0.elapsed_time(e1) / 3)
-                    # the margin is for leaving the fp32 kernel; among the block shapes of the split kernel the fastest wins
-                    if w3 and min(w3.values()) < X3_MARGIN * mine:
-                        best, mine = W3_BASE + min(w3, key=w3.get), min(w3.values())
-                best = _remember(key, best)
-            try:
-                if best and best >= W3_BASE and self._wino_x3() is not None:
-                    w3_tile = best - W3_BASE
-                elif best and X3_BASE <= best < W3_BASE and self._alt3() is not None:
-                    return self.alt3(srcs, out=out, out_coff=out_coff, residual=residual, res_coff=res_coff, act=act, slope=slope,
-                                     tile=best - X3_BASE, out_nchw=out_nchw, planes=kv_planes,
-                                     split_from=(self.Cout - kv_planes.shape[2]) if kv_planes is not None else 0)
-                elif best and self.tune and 2000 <= best < 2100 and self._alt() is not None:
-                    r = self.alt(srcs, out=out, out_coff=out_coff, residual=residual, res_coff=res_coff, act=act, slope=slope,
-                                 tile=best - 2000, out_nchw=out_nchw)
-                    if kv_planes is not None:
-                        split3_kv(out.view(-1, out.shape[-1]), out=kv_planes)
-                    return r
-                elif self.tune and best is not None and best < 2000:
-                    d.tile = best
-            except _L.HipError:
-                # a decision taken at a neighbouring size class (or an older cache entry) that this call's shape rejects: the
-                # layer's own fp32 kernel runs instead
-                if not from_table:
-                    raise
-                w3_tile = None
-        if _L.TRACE is not None:
-            _L.annotate(**self._work(N, H, W, Ho, Wo, use_wino, d.tile if w3_tile is None else W3_BASE + w3_tile))
-        rc, what = launch()
-        if rc != 0 and (w3_tile is not None or d.tile != tile0):
-            w3_tile, d.tile = None, tile0          # a tabled block shape this call's geometry rejects: the static default
-            rc, what = launch()
-        _L.check(rc, what)
+            kw.update(out=out, residual=residual)
+            call = _Call(self._desc(srcs, **kw), srcs, kw, kv_planes)
+            if self._launch(call, self._select(call, tile)):
+                return out                         # the kernel's epilogue has written kv_planes
         if kv_planes is not None:
             split3_kv(out.view(-1, out.shape[-1]), out=kv_planes)
         return out
+
+    def _desc(self, srcs, out, out_coff, residual, res_coff, act, slope, out_nchw):
+        """the C descriptor of one call (srcs: list of (tensor, channel offset)); wpacked and tile are set by what launches: a
+        layer packs the weights of the kernels it runs, only"""
+        d = self._fill(_L.ConvDesc(), torch.float32, _chk, srcs, out, out_coff, act, slope, out_nchw)
+        self._fill_residual(d, _chk, residual, res_coff)
+        d.bk = self.bk
+        return d
+
+    def _select(self, call, tile):
+        """The kernel of this call as a _Plan: the caller's tile code, or (tile == 0) the static rule and, on layers that ask for it,
+        the decision table's row for (layer geometry, size class).  No launch, no timing -- except through _tune, which fills a
+        missing row under E2FGVI_AUTOTUNE=1."""
+        d, kw = call.d, call.kw
+        N, H, W, Ho, Wo = d.N, d.H, d.W, d.Ho, d.Wo
+        out, residual = kw["out"], kw["residual"]
+        use_wino = self.algo == "winograd" or (self.algo == "auto" and H % 2 == 0 and W % 2 == 0 and not kw["out_nchw"]
+                                               and (tile in (0, 32, 64, 132, 164) or _decode(tile)[0] in ("w4", "w3")))
+        asked = _decode(tile) if use_wino else ("own", tile)
+        # the static rule's kernel: what runs when nothing else is decided, and what a rejected alternative falls back to
+        static = self._wino4_rule(N, H, W) if use_wino and (tile == 0 or asked[0] == "w3") else tile
+        own = ("w4" if use_wino and static in W4_CODES else "own", static)
+        family, arg = asked if asked[0] == "w3" else own
+        plan = _Plan(family, arg, own, False, use_wino)
+        # (a layer of the side stream may take it too: conv_bf16x.o is one of the packed-math-free objects, build.NOPK_OBJECTS)
+        x3 = self.try_x3 and X3_ENABLED
+        if not (tile == 0 and (static == 0 or not self.tune) and (self.tune or x3) and N * Ho * Wo >= 2048):
+            return plan
+        # one decision per (layer geometry, size class): row counts within a quarter octave share the tile, so the
+        # slightly different window lengths of a video (t = 17 ... 21 frames) do not each pay for a tuning pass
+        # (the fp32 baseline the alternatives are measured against is part of the key: a tuned layer and an untuned one of the
+        #  same geometry, or the F(2x4) / F(2x2) Winograd baselines, do not share a verdict)
+        key = (self.Cout, tuple(self.cpg), self.KH, self.KW, self.stride, self.pad, self.groups, self.bk,
+               int(4.0 * math.log2(N * Ho * Wo)), residual is not None, kw["act"], use_wino, bool(self.tune), int(static)) + (("x3",) if x3 else ())
+        best = _decision(key)
+        from_table = best is not None
+        if best is None and AUTOTUNE and not torch.cuda.is_current_stream_capturing() and (
+                residual is None or residual.data_ptr() != out.data_ptr()):
+            best = _remember(key, self._tune(call, own, use_wino, x3))
+        family, arg = _decode(best or 0)
+        # the split kernels wherever the key asked for them; tiles of the own and the LDS-DMA kernel on tuned layers only (the own
+        # kernel's halo ids, from 10000, are for callers that name them: no table row does)
+        if family in ("w3", "x3") or (self.tune and (family == "dma" or (family == "own" and arg < DMA_BASE))):
+            plan = plan._replace(family=family, tile=arg)
+        return plan._replace(from_table=from_table)
+
+    def _tune(self, call, own, use_wino, x3):
+        """E2FGVI_AUTOTUNE=1, first eager call of a (geometry, size class): device time of every candidate kernel on this exact
+        call -- the launches rewrite the same output, so the result of the call is unaffected.  Returns the winner's tile code."""
+        d, srcs, kw, kv_planes = call
+        best = self._autotune(d, use_wino) if self.tune else own[1]
+        base = own if own[0] == "w4" else ("own", best)
+        mine = None
+
+        def time_mine():
+            self._run(d, *base, use_wino)
+            return min(_time_launches(lambda: self._run(d, *base, use_wino), 3) for _ in range(TUNE_REPS))
+        if self.tune and not use_wino and not self.nopk:
+            # the LDS-DMA fp32 kernel on the very same call: codes DMA_BASE + its tile
+            alt = self._alt()
+            mine = time_mine()
+            res = alt._time_tiles(alt._desc(srcs, out2=None, **kw))
+            if res and min(res.values()) < mine:
+                best, mine = DMA_BASE + min(res, key=res.get), min(res.values())
+        if x3 and self._alt3() is not None:
+            # ... and the split-bf16 kernel: codes X3_BASE + its tile
+            if mine is None:
+                mine = time_mine()
+            d3 = self.alt3._desc(srcs, out2=None, **kw)
+            if kv_planes is not None:            # timed as it will run: with the K / V planes written by the epilogue
+                self.alt3._set_planes(d3, kv_planes, self.Cout - kv_planes.shape[2], d.N * d.Ho * d.Wo)
+            res = self.alt3._time_tiles(d3)
+            if res and min(res.values()) < X3_MARGIN * mine:
+                best, mine = X3_BASE + min(res, key=res.get), min(res.values())
+        if x3 and use_wino and self._wino_x3() is not None:
+            # ... and the Winograd kernel with split operands: codes W3_BASE + its block shape
+            w3 = {}
+            for shape in W3_CANDIDATES:
+                def run():
+                    return self._run(d, "w3", shape, use_wino)[0]
+                if run() == 0:
+                    w3[shape] = min(_time_launches(run, 3) for _ in range(TUNE_REPS))
+            # the margin is for leaving the fp32 kernel; among the block shapes of the split kernel the fastest wins
+            if w3 and min(w3.values()) < X3_MARGIN * mine:
+                best, mine = W3_BASE + min(w3, key=w3.get), min(w3.values())
+        return best
+
+    def _autotune(self, d, wino):
+        """the fastest of the own kernel's candidate tile codes on this exact call (best of TUNE_REPS measurements of 2 launches)"""
+        lib = _L.load()
+        best, best_ms = 0, float("inf")
+        st = _stream()
+        fn = lib.e2fgvi_conv3x3_winograd if wino else lib.e2fgvi_conv2d_nhwc
+        d.tile, d.wpacked = 0, (self.wino_packed if wino else self.wpacked).data_ptr()
+        for _ in range(3):                                       # bring clocks / caches to steady state first
+            fn(C.byref(d), st)
+        for code in (WINO_CANDIDATES if wino else TUNE_CANDIDATES):
+            d.tile = code
+            if fn(C.byref(d), st) != 0:                          # not instantiated / not applicable to this packing
+                continue
+            ms = min(_time_launches(lambda: fn(C.byref(d), st), 2) for _ in range(TUNE_REPS))
+            if ms < best_ms:
+                best, best_ms = code, ms
+        return best
+
+    def _run(self, d, family, tile, use_wino):
+        """one launch of a kernel of this layer's own on descriptor `d`: (return code, entry point's name)"""
+        lib, st = _L.load(), _stream()
+        if family == "w3":
+            d.tile, d.wpacked = tile, self._wino_x3().data_ptr()
+            return lib.e2fgvi_conv3x3_winograd_x3(C.byref(d), st), "conv3x3_winograd_x3"
+        if family == "w4":
+            fy, d.tile = W4_CODES[tile]
+            d.wpacked = self._wino4(fy).data_ptr()
+            return lib.e2fgvi_conv3x3_winograd4(C.byref(d), fy, st), "conv3x3_winograd4"
+        d.tile = tile
+        d.wpacked = (self.wino_packed if use_wino else self.wpacked).data_ptr()
+        if use_wino:
+            return lib.e2fgvi_conv3x3_winograd(C.byref(d), st), "conv3x3_winograd"
+        if self.nopk:
+            return lib.e2fgvi_conv2d_nhwc_nopk(C.byref(d), st), "conv2d_nhwc_nopk"
+        return lib.e2fgvi_conv2d_nhwc(C.byref(d), st), "conv2d_nhwc"
+
+    def _launch(self, call, plan):
+        """runs `plan`, one trace record announced before the launch; True when the kernel's epilogue has written kv_planes (the
+        split-operand GEMM's does)"""
+        d, srcs, kw, kv_planes = call
+        family, tile = plan.family, plan.tile
+        try:
+            if family == "x3" and self._alt3() is not None:
+                self.alt3(srcs, tile=tile, planes=kv_planes, split_from=(self.Cout - kv_planes.shape[2]) if kv_planes is not None else 0,
+                          **kw)
+                return True
+            if family == "dma":
+                self._alt()(srcs, tile=tile, **kw)
+                return False
+            if family == "x3" or (family == "w3" and self._wino_x3() is None):
+                family, tile = plan.static
+        except _L.HipError:
+            # a decision taken at a neighbouring size class (or an older cache entry) that this call's shape rejects: the
+            # layer's own fp32 kernel runs instead
+            if not plan.from_table:
+                raise
+            family, tile = plan.static
+        if _L.TRACE is not None:
+            _L.annotate(**self._work(d, plan.use_wino, family, tile))
+        rc, what = self._run(d, family, tile, plan.use_wino)
+        if rc != 0 and (family, tile) != plan.static:
+            rc, what = self._run(d, *plan.static, plan.use_wino)       # a tabled block shape this call's geometry rejects: the static default
+        _L.check(rc, what)
+        return False
 
 
 HALF16 = (torch.bfloat16, torch.float16)     # the two element types of the 16-bit data path
@@ -707,7 +759,7 @@ def _chk_any(t, name):
     return t
 
 
-class PackedConvX:
+class PackedConvX(_ConvLayer):
     """Conv / linear layer on the LDS-DMA implicit-GEMM kernel (csrc/conv_bf16x.hip).
 
     dtype=torch.bfloat16 (default): the bf16 data path -- bf16 NHWC sources (virtual concat, channels per source in
@@ -719,20 +771,15 @@ class PackedConvX:
     Either way: fp32 epilogue (bias, fp32 / bf16 residual, activation or the DCN offset post-processing), bf16 or fp32
     result (NHWC, or fp32 NCHW), optional second bf16 copy (`out2`)."""
 
+    _NCHW_ERROR = "NCHW out must be fp32 %(want)s"
+
     def __init__(self, weight, bias, cpg, groups=1, stride=1, pad=0, dtype=torch.bfloat16, taps=None, x3=False):
         """taps: None = tap-packed K-steps whenever the layer qualifies (one bf16 source of <= 32 channels, no groups, more
         than one tap), False = never (A/B measurements).
         x3 (fp32 sources only): fp32 on the bf16 matrix pipe -- weights stored as three bf16 planes whose sum is the fp32
         weight, activations split the same way in registers, six exact bf16 MFMA terms per product (kernel MODE 2)"""
         lib = _L.load()
-        if weight.dim() == 2:
-            weight = weight[:, :, None, None]
-        w = _chk(weight.detach().float().contiguous(), "weight")
-        self.Cout, cin_g, self.KH, self.KW = w.shape
-        self.cpg = [int(c) for c in cpg]
-        if sum(self.cpg) != cin_g:
-            raise ValueError("sum(cpg)=%d != weight input channels %d" % (sum(self.cpg), cin_g))
-        self.groups, self.stride, self.pad = groups, stride, pad
+        w = self._init_layer(weight, bias, cpg, groups, stride, pad)
         self.dtype = dtype
         self.f32 = dtype == torch.float32
         self.x3 = bool(x3)
@@ -744,24 +791,18 @@ class PackedConvX:
         self._mode = mode = _L.DT_BF16X3 if self.x3 else _DT_CODE[dtype]      # the `mode` of e2fgvi_conv2d_x and of its packers
         conv2d_x = lib.e2fgvi_conv2d_x
         self._fn = lambda desc_ref, stream: conv2d_x(desc_ref, mode, stream)
-        wdtype = torch.bfloat16 if self.x3 else dtype
-        self.name = "conv"
-        self.tune = False          # time XTUNE_CANDIDATES on the first call of every new size class and keep the fastest
-        self.try_x3 = False        # (fp32 operands, with tune) also time the split-bf16 variant of this layer: codes X3_BASE + tile
-        self.alt3 = None
         self._w_raw = w if (self.f32 and not self.x3) else None
         self._taps_arg = taps
         # narrow single-source layers (SPyNet's 7x7 stacks, the encoder's first layer): K-steps that carry several taps
         # (fp32 operands: only on request -- the one fp32 user is the FFN's second Linear as a conv, engine.py)
         self.taps = (len(self.cpg) == 1 and groups == 1 and self.cpg[0] <= 56 and self.KW > 1
                      and (taps is True if self.f32 else taps is not False))
-        self._wdtype = wdtype
+        self._wdtype = torch.bfloat16 if self.x3 else dtype
         self._wp = None
-        self.bias = None if bias is None else _chk(bias.detach().float().contiguous(), "bias")
         if self._w_raw is None:
             self._wp = self._pack(w)       # bf16 layers and the split-operand ones: packed now, the fp32 tensor is not kept
-        else:
-            self._pack(w, dry=True)        # a geometry the library rejects raises here, not on the first call
+        else:                              # a geometry the library rejects raises here, not on the first call
+            _L.check(min(0, int(lib.e2fgvi_packed_conv_weight_x_size(*self._wgeom()))), "packed_conv_weight_x_size")
 
     @property
     def wpacked(self):
@@ -771,71 +812,34 @@ class PackedConvX:
     def weight_bytes(self):
         return (0 if self._wp is None else self._wp.numel() * self._wp.element_size()) + (self.alt3.weight_bytes() if self.alt3 is not None else 0)
 
-    def _pack(self, w, dry=False):
-        lib = _L.load()
-        wdtype = self._wdtype
-        arr = (C.c_int32 * len(self.cpg))(*self.cpg)
-        geom = (self._mode, int(self.taps), self.Cout, self.groups, self.KH, self.KW, len(self.cpg), arr)
-        n = lib.e2fgvi_packed_conv_weight_x_size(*geom)
-        if n < 0:
-            _L.check(int(n), "packed_conv_weight_x_size")
-        if dry:
-            return None
-        t = torch.empty(int(n), dtype=wdtype, device=w.device)
-        _L.check(lib.e2fgvi_pack_conv_weight_x(_ptr(w), _ptr(t), *geom, _stream()), "pack_conv_weight_x")
-        return t
+    def _wgeom(self):
+        return self._mode, int(self.taps), self.Cout, self.groups, self.KH, self.KW, len(self.cpg), self._cpg_arr()
 
-    def out_hw(self, H, W):
-        return ((H + 2 * self.pad - self.KH) // self.stride + 1, (W + 2 * self.pad - self.KW) // self.stride + 1)
+    def _pack(self, w):
+        lib = _L.load()
+        return _pack_weights(lib.e2fgvi_packed_conv_weight_x_size, lib.e2fgvi_pack_conv_weight_x, w, self._wdtype, "conv_weight_x",
+                             *self._wgeom())
 
     def _alt3(self):
         """this fp32 layer on the bf16 matrix pipe (x3=True), built on first use"""
         if self._w_raw is None:
             return self.alt3
-
-        def build():
-            alt3 = PackedConvX(self._w_raw, self.bias, self.cpg, groups=self.groups, stride=self.stride, pad=self.pad,
-                               dtype=torch.float32, taps=self._taps_arg, x3=True)
-            alt3.name = self.name
-            return alt3
-        return _lazy(vars(self), "alt3", self.name + " (split-operand GEMM alternative)", build)
+        return _lazy(vars(self), "alt3", self.name + " (split-operand GEMM alternative)",
+                     lambda: self._x_alternative(taps=self._taps_arg, x3=True))
 
     def _desc(self, srcs, out, out_coff, residual, res_coff, act, slope, out2, out_nchw):
         """the C descriptor of one call (srcs: list of (tensor, channel offset))"""
-        d = _L.ConvXDesc()
-        N, H, W, _ = srcs[0][0].shape
-        Ho, Wo = self.out_hw(H, W)
-        for i, (t, coff) in enumerate(srcs):
-            _chk(t, "source %d" % i, self.dtype)
-            if t.dim() != 4 or tuple(t.shape[:3]) != (N, H, W):
-                raise ValueError("source %d shape %s does not match [%d,%d,%d,*]" % (i, tuple(t.shape), N, H, W))
-            d.src[i], d.src_ld[i], d.src_coff[i], d.src_cpg[i] = t.data_ptr(), t.shape[3], coff, self.cpg[i]
-        d.nsrc = len(srcs)
-        d.N, d.H, d.W, d.Ho, d.Wo = N, H, W, Ho, Wo
-        d.KH, d.KW, d.stride, d.pad = self.KH, self.KW, self.stride, self.pad
-        d.groups, d.Cout = self.groups, self.Cout
+        d = self._fill(_L.ConvXDesc(), self.dtype, _chk_any, srcs, out, out_coff, act, slope, out_nchw)
         d.wpacked = None if self._wp is None else self._wp.data_ptr()      # an fp32 layer's own packing: set by what launches it
-        d.bias = self.bias.data_ptr() if self.bias is not None else None
-        _chk_any(out, "out")
-        if out_nchw:
-            if tuple(out.shape) != (N, self.Cout, Ho, Wo) or out.dtype != torch.float32:
-                raise ValueError("NCHW out must be fp32 %s" % ((N, self.Cout, Ho, Wo),))
-            d.dst, d.dst_ld, d.dst_coff, d.dst_dtype, d.dst_nchw = out.data_ptr(), 0, 0, _L.DT_F32, 1
-        else:
-            if out.dim() != 4 or tuple(out.shape[:3]) != (N, Ho, Wo):
-                raise ValueError("out shape %s != [%d,%d,%d,*]" % (tuple(out.shape), N, Ho, Wo))
-            d.dst, d.dst_ld, d.dst_coff, d.dst_dtype = out.data_ptr(), out.shape[3], out_coff, _dt(out)
+        d.dst_dtype = _dt(out)
         if out2 is not None:
             _chk(out2, "out2", torch.float16 if self.f16 else torch.bfloat16)
-            if out2.dim() != 4 or tuple(out2.shape[:3]) != (N, Ho, Wo):
-                raise ValueError("out2 shape %s != [%d,%d,%d,*]" % (tuple(out2.shape), N, Ho, Wo))
+            if out2.dim() != 4 or tuple(out2.shape[:3]) != (d.N, d.Ho, d.Wo):
+                raise ValueError("out2 shape %s != [%d,%d,%d,*]" % (tuple(out2.shape), d.N, d.Ho, d.Wo))
             d.dst2, d.dst2_ld, d.dst2_coff = out2.data_ptr(), out2.shape[3], 0
+        self._fill_residual(d, _chk_any, residual, res_coff)
         if residual is not None:
-            _chk_any(residual, "residual")
-            if residual.dim() != 4 or tuple(residual.shape[:3]) != (N, Ho, Wo):
-                raise ValueError("residual shape %s != [%d,%d,%d,*]" % (tuple(residual.shape), N, Ho, Wo))
-            d.residual, d.res_ld, d.res_coff, d.res_dtype = residual.data_ptr(), residual.shape[3], res_coff, _dt(residual)
-        d.act, d.slope, d.tile = act, slope, 0
+            d.res_dtype = _dt(residual)
         d.tap_packed = 1 if self.taps else 0
         return d
 
@@ -851,68 +855,36 @@ class PackedConvX:
 
     def __call__(self, sources, out=None, out_dtype=None, out_coff=0, residual=None, res_coff=0, act=ACT_NONE,
                  slope=0.0, out2=None, tile=0, out_nchw=False, planes=None, split_from=0):
-        """planes / split_from (fp32 results): see _set_planes -- the qkv Linear writes the attention's K / V operand planes"""
+        """planes / split_from (fp32 results): see _set_planes -- the qkv Linear writes the attention's K / V operand planes.
+        The steps of PackedConv.__call__: _desc, _select (_tune under E2FGVI_AUTOTUNE=1), launch."""
         if out_dtype is None:
             out_dtype = self.dtype
-        srcs = [(s, 0) if isinstance(s, torch.Tensor) else s for s in sources]
-        if len(srcs) != len(self.cpg):
-            raise ValueError("expected %d sources, got %d" % (len(self.cpg), len(srcs)))
+        srcs, out = self._srcs_out(sources, out, out_nchw, out_dtype)
         N, H, W, _ = srcs[0][0].shape
         Ho, Wo = self.out_hw(H, W)
-        dev = srcs[0][0].device
-        if out is None:
-            out = (torch.empty((N, self.Cout, Ho, Wo), dtype=torch.float32, device=dev) if out_nchw else
-                   torch.empty((N, Ho, Wo, self.Cout), dtype=out_dtype, device=dev))
-        per_img = max(H * W * t.shape[3] * (4 if self.f32 else 2) for t, _ in srcs)
-        if N > 1 and N * per_img >= (1 << 32) - 1:                 # 32-bit buffer resources: image chunks
+        kw = dict(out_coff=out_coff, res_coff=res_coff, act=act, slope=slope, out_nchw=out_nchw)
+        chunks = list(_image_chunks(N, max(H * W * t.shape[3] * (4 if self.f32 else 2) for t, _ in srcs)))
+        if len(chunks) > 1:
             if planes is not None:
                 raise ValueError("split planes: the batch spans >= 4 GiB (call in chunks)")
-            step = max(1, ((1 << 32) - 2) // per_img)
-            for n0 in range(0, N, step):
-                n1 = min(N, n0 + step)
-                self([(t[n0:n1], c) for t, c in srcs], out=out[n0:n1], out_coff=out_coff,
-                     residual=None if residual is None else residual[n0:n1], res_coff=res_coff, act=act, slope=slope,
-                     out2=None if out2 is None else out2[n0:n1], tile=tile, out_nchw=out_nchw)
+            for n0, n1 in chunks:
+                self([(t[n0:n1], c) for t, c in srcs], out=out[n0:n1], residual=None if residual is None else residual[n0:n1],
+                     out2=None if out2 is None else out2[n0:n1], tile=tile, **kw)
             return out
-        d = self._desc(srcs, out, out_coff, residual, res_coff, act, slope, out2, out_nchw)
+        kw.update(out=out, residual=residual, out2=out2)
+        d = self._desc(srcs, **kw)
         if planes is not None:
             self._set_planes(d, planes, split_from, N * Ho * Wo)
-        d.tile = tile
-        x3 = self.try_x3 and X3_ENABLED and self.f32 and not self.x3
         if tile == 0 and self.tune and N * Ho * Wo >= 2048:
-            key = (("x3" if self.x3 else ("x32+3" if x3 else "x32")) if self.f32 else "x", self.Cout, tuple(self.cpg), self.KH, self.KW, self.stride, self.pad, self.groups,
-                   int(4.0 * math.log2(N * Ho * Wo)), _dt_key(out), out_nchw, self.taps)
-            best = _decision(key)
-            if best is None and AUTOTUNE and not torch.cuda.is_current_stream_capturing() and (
-                    residual is None or residual.data_ptr() != out.data_ptr()):
-                res = self._time_tiles(d)
-                best = min(res, key=res.get) if res else 0
-                if x3 and self._alt3() is not None:
-                    res3 = self.alt3._time_tiles(self.alt3._desc(srcs, out, out_coff, residual, res_coff, act, slope, out2, out_nchw))
-                    if res3 and (not res or min(res3.values()) < X3_MARGIN * min(res.values())):
-                        best = X3_BASE + min(res3, key=res3.get)
-                best = _remember(key, best)
-            if best and best >= X3_BASE and self._alt3() is not None:
+            family, tile = self._select(d, srcs, kw)
+            if family == "x3":
                 try:
-                    return self.alt3(srcs, out=out, out_dtype=out_dtype, out_coff=out_coff, residual=residual, res_coff=res_coff, act=act,
-                                     slope=slope, out2=out2, tile=best - X3_BASE, out_nchw=out_nchw, planes=planes, split_from=split_from)
+                    return self.alt3(srcs, out_dtype=out_dtype, tile=tile, planes=planes, split_from=split_from, **kw)
                 except _L.HipError:                       # a neighbouring size class's tile that this shape rejects
-                    best = 0
-            d.tile = tile = (best or 0) if (best or 0) < X3_BASE else 0
+                    tile = 0
+        d.tile = tile
         if _L.TRACE is not None:
-            cin_g, cout_g, K2 = sum(self.cpg), self.Cout // self.groups, self.KH * self.KW
-            kc = 32 if self.f32 else 64
-            cin_p = sum(-(-c // kc) * kc for c in self.cpg)
-            if self.taps:                                   # K-steps of several taps: issued K = steps * 64
-                cin_p = -(-K2 * (self.cpg[0] // (4 if self.f32 else 8)) // 8) * kc / K2
-            _L.annotate(layer=self.name, kernel="conv_%s tile=%d%s" % (("f32x3" if self.x3 else "f32x") if self.f32 else
-                                                                      "f16x" if self.f16 else "bf16x", tile,
-                                                                      " taps" if self.taps else ""),
-                        shape="N%d %dx%d %d->%d k%d s%d g%d" % (N, H, W, cin_g * self.groups, self.Cout, self.KH, self.stride, self.groups),
-                        macs=N * Ho * Wo * self.Cout * cin_g * K2, tile=int(tile),
-                        # x3: six bf16 MACs per product, counted in fp32-pipe equivalents (a bf16 MAC occupies the matrix
-                        # pipe for 157.3 / 2500 of the time of an fp32 MAC): `issued / fp32 peak` stays matrix-pipe time
-                        issued=int(N * Ho * Wo * (-(-cout_g // 32) * 32) * self.groups * cin_p * K2 * (6 * 157.3 / 2500.0 if self.x3 else 1)))
+            _L.annotate(**self._work(d))
         d.wpacked = self.wpacked.data_ptr()
         rc = self._fn(C.byref(d), _stream())
         if rc != 0 and d.tile and self.tune:
@@ -921,6 +893,49 @@ class PackedConvX:
         _L.check(rc, "conv2d_x")
         return out
 
+    def _select(self, d, srcs, kw):
+        """(family, tile) of a call that leaves the tile to the layer: the decision table's row for (layer geometry, size class) --
+        "own" and a tile of this kernel, or "x3" and a tile of the split-operand alternative.  No launch, no timing -- except
+        through _tune, which fills a missing row under E2FGVI_AUTOTUNE=1."""
+        out, residual = kw["out"], kw["residual"]
+        x3 = self.try_x3 and X3_ENABLED and self.f32 and not self.x3
+        key = (("x3" if self.x3 else ("x32+3" if x3 else "x32")) if self.f32 else "x", self.Cout, tuple(self.cpg), self.KH, self.KW, self.stride, self.pad, self.groups,
+               int(4.0 * math.log2(d.N * d.Ho * d.Wo)), _dt_key(out), kw["out_nchw"], self.taps)
+        best = _decision(key)
+        if best is None and AUTOTUNE and not torch.cuda.is_current_stream_capturing() and (
+                residual is None or residual.data_ptr() != out.data_ptr()):
+            best = _remember(key, self._tune(d, srcs, kw, x3))
+        if _decode(best or 0)[0] in ("x3", "w3"):      # (a Winograd code counts from X3_BASE here: a tile the launcher rejects)
+            return ("x3", best - X3_BASE) if self._alt3() is not None else ("own", 0)
+        return "own", best or 0
+
+    def _tune(self, d, srcs, kw, x3):
+        """E2FGVI_AUTOTUNE=1: the fastest tile of this exact call, or X3_BASE + the split-operand alternative's where that is
+        faster by more than X3_MARGIN"""
+        res = self._time_tiles(d)
+        best = min(res, key=res.get) if res else 0
+        if x3 and self._alt3() is not None:
+            res3 = self.alt3._time_tiles(self.alt3._desc(srcs, **kw))
+            if res3 and (not res or min(res3.values()) < X3_MARGIN * min(res.values())):
+                best = X3_BASE + min(res3, key=res3.get)
+        return best
+
+    def _work(self, d):
+        """launch-trace record of the call `d` describes (see PackedConv._work)"""
+        N, H, W, Ho, Wo, tile = d.N, d.H, d.W, d.Ho, d.Wo, d.tile
+        cin_g, cout_g, K2 = sum(self.cpg), self.Cout // self.groups, self.KH * self.KW
+        kc = 32 if self.f32 else 64
+        cin_p = sum(-(-c // kc) * kc for c in self.cpg)
+        if self.taps:                                   # K-steps of several taps: issued K = steps * 64
+            cin_p = -(-K2 * (self.cpg[0] // (4 if self.f32 else 8)) // 8) * kc / K2
+        return dict(layer=self.name, kernel="conv_%s tile=%d%s" % (("f32x3" if self.x3 else "f32x") if self.f32 else
+                                                                   "f16x" if self.f16 else "bf16x", tile, " taps" if self.taps else ""),
+                    shape="N%d %dx%d %d->%d k%d s%d g%d" % (N, H, W, cin_g * self.groups, self.Cout, self.KH, self.stride, self.groups),
+                    macs=N * Ho * Wo * self.Cout * cin_g * K2, tile=int(tile),
+                    # x3: six bf16 MACs per product, counted in fp32-pipe equivalents (a bf16 MAC occupies the matrix
+                    # pipe for 157.3 / 2500 of the time of an fp32 MAC): `issued / fp32 peak` stays matrix-pipe time
+                    issued=int(N * Ho * Wo * (-(-cout_g // 32) * 32) * self.groups * cin_p * K2 * (_L.X3_PIPE if self.x3 else 1)))
+
     def _time_tiles(self, d, reps=3, rounds=2):
         """{tile code: best device time in ms} of every tile shape on this exact call (the launches rewrite the same
         output); best of `rounds` measurements of `reps` launches each"""
@@ -928,8 +943,11 @@ class PackedConvX:
         res = {}
         d.tile = 0
         d.wpacked = self.wpacked.data_ptr()
+
+        def run():
+            return self._fn(C.byref(d), st)
         for _ in range(2):
-            self._fn(C.byref(d), st)
+            run()
         for _ in range(rounds * TUNE_REPS):
             rowshift = (self.KH, self.KW, self.stride, self.pad) == (3, 3, 1, 1) and not self.f32 and not self.taps
             for code in XTUNE_CANDIDATES + (XTUNE_ROWSHIFT if rowshift else ()):
@@ -938,15 +956,8 @@ class PackedConvX:
                 if code in (12, 18) and self.Cout // self.groups > 64:
                     continue
                 d.tile = code
-                if self._fn(C.byref(d), st) != 0:
-                    continue
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(reps):
-                    self._fn(C.byref(d), st)
-                e1.record()
-                e1.synchronize()
-                res[code] = min(res.get(code, float("inf")), e0.elapsed_time(e1) / reps)
+                if run() == 0:
+                    res[code] = min(res.get(code, float("inf")), _time_launches(run, reps))
         d.tile = 0
         return res
 
@@ -1001,11 +1012,10 @@ class SoftCompGather:
             out = torch.empty((F_, H, W, self.C), dtype=out_dtype or self.dtype, device=tokens.device)
         if tuple(out.shape) != (F_, H, W, self.C):
             raise ValueError("out must be [%d,%d,%d,%d]" % (F_, H, W, self.C))
-        per_img = fh * fw * hid * tokens.element_size()
-        if F_ > 1 and F_ * per_img >= (1 << 32) - 1:                           # 32-bit buffer resources: frame chunks
-            step = max(1, ((1 << 32) - 2) // per_img)
-            for n0 in range(0, F_, step):
-                self(tokens[n0:n0 + step], out=out[n0:n0 + step])
+        chunks = list(_image_chunks(F_, fh * fw * hid * tokens.element_size()))
+        if len(chunks) > 1:
+            for n0, n1 in chunks:
+                self(tokens[n0:n1], out=out[n0:n1])
             return out
         bimg = self.bias_image(fh, fw)
         for py, px, pad_y, pad_x, layer in self.phases:
@@ -1078,13 +1088,11 @@ class PackedTailConv:
         self.Cout, self.Cin, self.KH, self.KW = w.shape
         if (self.KH, self.KW) != (3, 3):
             raise ValueError("PackedTailConv: 3x3 kernels only")
-        n = lib.e2fgvi_packed_tail_weight_size(self.Cout, self.Cin)
-        if n < 0:
-            _L.check(int(n), "packed_tail_weight_size")
         self.dtype = dtype
-        self.wpacked = torch.empty(int(n), dtype=dtype, device=w.device)
-        _L.check(lib.e2fgvi_pack_tail_weight(_ptr(w), _ptr(self.wpacked), self.Cout, self.Cin, _dt(self.wpacked), _stream()),
-                 "pack_tail_weight")
+        if dtype not in _DT_CODE:
+            raise TypeError("tensor must be float32, bfloat16 or float16, got %s" % dtype)
+        self.wpacked = _pack_weights(lib.e2fgvi_packed_tail_weight_size, lib.e2fgvi_pack_tail_weight, w, dtype, "tail_weight",
+                                     self.Cout, self.Cin, extra=(_DT_CODE[dtype],))
         self.bias = None if bias is None else _chk(bias.detach().float().contiguous(), "bias")
         self.name = "conv_tail"
 
@@ -1110,9 +1118,9 @@ class PackedTailConv:
 
 
 # ------------------------------------------------------------------------------------------ deformable conv
-# PackedDcn(mfma=...) -> (mfma_dtype of the C ABI, element type of the packed weights)
-_DCN_PACKING = {"fp32": (_L.DT_F32, torch.float32), "bf16": (_L.DT_BF16, torch.bfloat16), "fp16": (_L.DT_F16, torch.float16),
-                "x3": (_L.DT_BF16X3, torch.bfloat16)}
+# PackedDcn(mfma=...) -> (mfma_dtype of the C ABI, element type of the packed weights, kernel name of the trace record)
+_DCN_PACKING = {"fp32": (_L.DT_F32, torch.float32, "mdcn"), "bf16": (_L.DT_BF16, torch.bfloat16, "mdcn_bf16"),
+                "fp16": (_L.DT_F16, torch.float16, "mdcn_f16"), "x3": (_L.DT_BF16X3, torch.bfloat16, "mdcn_x3")}
 
 
 class PackedDcn:
@@ -1124,19 +1132,13 @@ class PackedDcn:
         lib = _L.load()
         if mfma not in _DCN_PACKING:
             raise ValueError("mfma must be 'fp32', 'bf16', 'fp16' or 'x3'")
-        self.mfma_bf16 = mfma == "bf16"
-        self.mfma_f16 = mfma == "fp16"            # the same on fp16 (fp16 sources, products and 16-bit result)
-        self.mfma_x3 = mfma == "x3"
+        self._mfma_dtype, wdtype, self._kernel = _DCN_PACKING[mfma]       # ("fp16": "bf16" on fp16 sources, products and 16-bit result)
+        self.mfma_bf16, self.mfma_f16, self.mfma_x3 = mfma == "bf16", mfma == "fp16", mfma == "x3"
         w = _chk(weight.detach().float().contiguous(), "weight")
         self.Cout, self.C, self.KH, self.KW = w.shape
         self.dg, self.stride, self.pad, self.dil = deform_groups, stride, pad, dil
-        code, wdtype = _DCN_PACKING[mfma]
-        n = lib.e2fgvi_packed_dcn_weight_size(code, self.Cout, self.C, self.KH, self.KW)
-        if n < 0:
-            _L.check(int(n), "packed_dcn_weight_size")
-        self.wpacked = torch.empty(int(n), dtype=wdtype, device=w.device)
-        _L.check(lib.e2fgvi_pack_dcn_weight(_ptr(w), _ptr(self.wpacked), code, self.Cout, self.C, self.KH, self.KW,
-                                            deform_groups, _stream()), "pack_dcn_weight")
+        self.wpacked = _pack_weights(lib.e2fgvi_packed_dcn_weight_size, lib.e2fgvi_pack_dcn_weight, w, wdtype, "dcn_weight",
+                                     self._mfma_dtype, self.Cout, self.C, self.KH, self.KW, extra=(deform_groups,))
         self.bias = None if bias is None else _chk(bias.detach().float().contiguous(), "bias")
         self.name = "dcn"
 
@@ -1195,17 +1197,25 @@ class PackedDcn:
             out = torch.empty((N, Ho, Wo, self.Cout), dtype=out_dtype, device=sources[0].device)
         _chk_any(out, "out")
         d.dst, d.dst_ld, d.dst_coff, d.tile, d.dst_dtype = out.data_ptr(), out.shape[3], 0, tile, _dt(out)
-        d.mfma_dtype = 2 if self.mfma_x3 else (_L.DT_BF16 if self.mfma_bf16 else _L.DT_F16 if self.mfma_f16 else _L.DT_F32)
+        d.mfma_dtype = self._mfma_dtype
         if _L.TRACE is not None:
             m = N * Ho * Wo * self.Cout * self.C * K
-            _L.annotate(layer=self.name, kernel="mdcn_x3" if self.mfma_x3 else ("mdcn_bf16" if self.mfma_bf16 else "mdcn_f16" if self.mfma_f16 else "mdcn"),
-                        shape="N%d %dx%d %d->%d dg%d" % (N, H, W, self.C, self.Cout, self.dg),
-                        macs=m, issued=int(m * 6 * 157.3 / 2500.0) if self.mfma_x3 else m)
+            _L.annotate(layer=self.name, kernel=self._kernel, shape="N%d %dx%d %d->%d dg%d" % (N, H, W, self.C, self.Cout, self.dg),
+                        macs=m, issued=int(m * 6 * 157.3 / 2500.0) if self._mfma_dtype == _L.DT_BF16X3 else m)
         _L.check(lib.e2fgvi_mdcn_nhwc(C.byref(d), _stream()), "mdcn_nhwc")
         return out
 
 
 # ------------------------------------------------------------------------------------------ attention
+def _attn_work(B, T, fh, fw, nkeys):
+    """launch-trace record of a focal attention call without its `layer` / `kernel`: algorithmic = the reference's [T*45] x [T*210]
+    score and PV products per (window, head); issued = the keys the kernel actually multiplies (zero-padded pooled slots are
+    handled analytically), in 32-key tiles, 32-query waves"""
+    qpad = -(-(45 * T) // 32) * 32
+    return dict(shape="B%d T%d grid %dx%d" % (B, T, fh, fw), macs=B * (fh // 5) * (fw // 9) * 4 * (45 * T) * (210 * T) * 128 * 2,
+                issued=B * 4 * qpad * 128 * 2 * sum(-(-(T * k) // 32) * 32 for k in nkeys.tolist()))
+
+
 def focal_attention(qkv, kv_pool, key_tab, nkeys, B, T, fh, fw, out=None, waves=0):
     lib = _L.load()
     _chk(qkv, "qkv"); _chk(kv_pool, "kv_pool")
@@ -1222,22 +1232,15 @@ def focal_attention(qkv, kv_pool, key_tab, nkeys, B, T, fh, fw, out=None, waves=
         out = torch.empty((rows, 512), dtype=torch.float32, device=qkv.device)
     _chk(out, "out")
     # 32-bit buffer addressing inside the kernel: batches whose qkv spans >= 4 GiB go clip by clip
-    if B > 1 and rows * 1536 * 4 >= (1 << 32) - 1:
-        rpc, ppc = T * fh * fw, T * nwin
-        step = max(1, ((1 << 32) - 2) // (rpc * 1536 * 4))
-        for b0 in range(0, B, step):
-            b1 = min(B, b0 + step)
+    rpc, ppc = T * fh * fw, T * nwin
+    chunks = list(_image_chunks(B, rpc * 1536 * 4))
+    if len(chunks) > 1:
+        for b0, b1 in chunks:
             focal_attention(qkv[b0 * rpc:b1 * rpc], kv_pool[b0 * ppc:b1 * ppc], key_tab, nkeys, b1 - b0, T, fh, fw,
                             out=out[b0 * rpc:b1 * rpc], waves=waves)
         return out
     if _L.TRACE is not None:
-        # algorithmic = the reference's [T*45] x [T*210] score and PV products per (window, head); issued = the keys the
-        # kernel actually multiplies (zero-padded pooled slots are handled analytically), in 32-key tiles, 32-query waves
-        nkl = nkeys.tolist()
-        alg = B * nwin * 4 * (45 * T) * (210 * T) * 128 * 2
-        qpad = -(-(45 * T) // 32) * 32
-        iss = B * 4 * qpad * 128 * 2 * sum(-(-(T * k) // 32) * 32 for k in nkl)
-        _L.annotate(layer="attention", kernel="focal_attn", shape="B%d T%d grid %dx%d" % (B, T, fh, fw), macs=alg, issued=iss)
+        _L.annotate(layer="attention", kernel="focal_attn", **_attn_work(B, T, fh, fw, nkeys))
     _L.check(lib.e2fgvi_focal_attention(_ptr(qkv), _ptr(kv_pool), _ptr(key_tab), key_tab.shape[1], _ptr(nkeys),
                                         _ptr(out), B, T, fh, fw, waves, _stream()), "focal_attention")
     return out
@@ -1277,13 +1280,10 @@ def focal_attention_x3(qkv, planes, key_tab, nkeys, B, T, fh, fw, out=None, wave
         out = torch.empty((rows, 512), dtype=torch.float32, device=qkv.device)
     _chk(out, "out")
     if _L.TRACE is not None:
-        nkl = nkeys.tolist()
-        alg = B * nwin * 4 * (45 * T) * (210 * T) * 128 * 2
-        qpad = -(-(45 * T) // 32) * 32
-        iss = B * 4 * qpad * 128 * 2 * sum(-(-(T * k) // 32) * 32 for k in nkl)
+        work = _attn_work(B, T, fh, fw, nkeys)
         # six bf16 MACs per product, in fp32-pipe equivalents (PackedConvX's trace record)
-        _L.annotate(layer="attention", kernel="focal_attn_x3", shape="B%d T%d grid %dx%d" % (B, T, fh, fw), macs=alg,
-                    issued=int(iss * 6 * 157.3 / 2500.0))
+        work["issued"] = int(work["issued"] * 6 * 157.3 / 2500.0)
+        _L.annotate(layer="attention", kernel="focal_attn_x3", **work)
     _L.check(lib.e2fgvi_focal_attention_x3(_ptr(qkv), _ptr(planes), _ptr(key_tab), key_tab.shape[1], _ptr(nkeys), _ptr(out),
                                            B, T, fh, fw, waves, _stream()), "focal_attention_x3")
     return out
@@ -1321,12 +1321,8 @@ def focal_attention_bf16(qkv, kv_pool, key_tab, nkeys, B, T, fh, fw, out=None, v
         out = torch.empty((rows, 512), dtype=dt, device=qkv.device)
     _chk(out, "out", dt)
     if _L.TRACE is not None:
-        nkl = nkeys.tolist()
-        alg = B * nwin * 4 * (45 * T) * (210 * T) * 128 * 2
-        qpad = -(-(45 * T) // 32) * 32
-        iss = B * 4 * qpad * 128 * 2 * sum(-(-(T * k) // 32) * 32 for k in nkl)
         _L.annotate(layer="attention", kernel="focal_attn_f16" if dt == torch.float16 else "focal_attn_bf16",
-                    shape="B%d T%d grid %dx%d" % (B, T, fh, fw), macs=alg, issued=iss)
+                    **_attn_work(B, T, fh, fw, nkeys))
     _L.check(lib.e2fgvi_focal_attention_16(_ptr(qkv), _ptr(kv_pool), _ptr(key_tab), key_tab.shape[1], _ptr(nkeys), _ptr(out),
                                            _dt(qkv), B, T, fh, fw, _stream()),
              "focal_attention_f16" if dt == torch.float16 else "focal_attention_bf16")
@@ -1482,12 +1478,42 @@ def window_pool(x, w45, bias1, BT, fh, fw, out=None):
     return out
 
 
-def ffn_fold(hid, F_, fh, fw, H, W, Cc):
+def _ffn_fold(hid, F_, fh, fw, H, W, Cc, gelu):
     lib = _L.load()
     _chk_any(hid, "hid")
     out = torch.empty((F_, H, W, Cc), dtype=hid.dtype, device=hid.device)
-    _L.check(lib.e2fgvi_ffn_fold(_ptr(hid), _ptr(out), _dt(hid), 0, F_, fh, fw, H, W, Cc, _stream()), "ffn_fold")
+    _L.check(lib.e2fgvi_ffn_fold(_ptr(hid), _ptr(out), _dt(hid), gelu, F_, fh, fw, H, W, Cc, _stream()),
+             "ffn_fold_gelu" if gelu else "ffn_fold")
     return out
+
+
+def ffn_fold(hid, F_, fh, fw, H, W, Cc):
+    return _ffn_fold(hid, F_, fh, fw, H, W, Cc, 0)
+
+
+def ffn_fold_gelu(hid, F_, fh, fw, H, W, Cc):
+    """GELU(fold(hid) / count): the FFN middle with the GELU in front of the (pure-gather) unfold -- see ffn_unfold"""
+    return _ffn_fold(hid, F_, fh, fw, H, W, Cc, 1)
+
+
+def _ffn_unfold(folded, fh, fw, out, gelu):
+    lib = _L.load()
+    _chk_any(folded, "folded")
+    F_, H, W, Cc = folded.shape
+    if out is None:
+        out = torch.empty((F_ * fh * fw, 49 * Cc), dtype=folded.dtype, device=folded.device)
+    _chk(out, "out", folded.dtype)
+    _L.check(lib.e2fgvi_ffn_unfold(_ptr(folded), _ptr(out), _dt(folded), gelu, F_, fh, fw, H, W, Cc, _stream()),
+             "ffn_unfold_gelu" if gelu else "ffn_unfold")
+    return out
+
+
+def ffn_unfold(folded, fh, fw, out=None):
+    return _ffn_unfold(folded, fh, fw, out, 0)
+
+
+def ffn_unfold_gelu(folded, fh, fw, out=None):
+    return _ffn_unfold(folded, fh, fw, out, 1)
 
 
 def to_planar16(x, out=None):
@@ -1499,37 +1525,6 @@ def to_planar16(x, out=None):
         out = torch.empty((Cc // 16, N, H, W, 16), dtype=dt, device=x.device)
     _chk(out, "out", dt)
     _L.check(_L.load().e2fgvi_nhwc_to_planar16(_ptr(x), _ptr(out), N * H * W, Cc, _stream()), "nhwc_to_planar16")
-    return out
-
-
-def ffn_unfold_gelu(folded, fh, fw, out=None):
-    lib = _L.load()
-    _chk_any(folded, "folded")
-    F_, H, W, Cc = folded.shape
-    if out is None:
-        out = torch.empty((F_ * fh * fw, 49 * Cc), dtype=folded.dtype, device=folded.device)
-    _chk(out, "out", folded.dtype)
-    _L.check(lib.e2fgvi_ffn_unfold(_ptr(folded), _ptr(out), _dt(folded), 1, F_, fh, fw, H, W, Cc, _stream()), "ffn_unfold_gelu")
-    return out
-
-
-def ffn_fold_gelu(hid, F_, fh, fw, H, W, Cc):
-    """GELU(fold(hid) / count): the FFN middle with the GELU in front of the (pure-gather) unfold -- see ffn_unfold"""
-    lib = _L.load()
-    _chk_any(hid, "hid")
-    out = torch.empty((F_, H, W, Cc), dtype=hid.dtype, device=hid.device)
-    _L.check(lib.e2fgvi_ffn_fold(_ptr(hid), _ptr(out), _dt(hid), 1, F_, fh, fw, H, W, Cc, _stream()), "ffn_fold_gelu")
-    return out
-
-
-def ffn_unfold(folded, fh, fw, out=None):
-    lib = _L.load()
-    _chk_any(folded, "folded")
-    F_, H, W, Cc = folded.shape
-    if out is None:
-        out = torch.empty((F_ * fh * fw, 49 * Cc), dtype=folded.dtype, device=folded.device)
-    _chk(out, "out", folded.dtype)
-    _L.check(lib.e2fgvi_ffn_unfold(_ptr(folded), _ptr(out), _dt(folded), 0, F_, fh, fw, H, W, Cc, _stream()), "ffn_unfold")
     return out
 
 

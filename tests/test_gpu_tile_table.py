@@ -20,7 +20,7 @@ pair, size class dropped, is one case, so a regenerated table is covered without
     stay untouched.
 
 No case is skipped.  A tabled kernel that rejected its small shape would get the smallest shape it accepts, with the reason in a
-comment in _shape(); today none does.  The two tests at the top need no GPU."""
+comment in _shape(); today none does.  The four tests at the top need no GPU."""
 import math
 
 import pytest
@@ -71,8 +71,8 @@ def code_family(code):
         return "w4"                                                                  # wide-tile fp32 Winograd
     if 2000 <= code < 2100:
         return "dma" if code > 2000 else None                                        # LDS-DMA fp32 GEMM, its tile
-    if 0 <= code < 200 or 10000 <= code < ops.X3_BASE:
-        return "own"                                                                 # the layer's own kernel, its tile (0: static)
+    if 0 <= code < 256 or 10000 <= code < ops.X3_BASE:
+        return "own"                                             # the layer's own kernel, its tile (0: static; 200 ... 255: implicit GEMM)
     return None
 
 
@@ -104,6 +104,39 @@ def test_every_code_of_the_table_decodes_to_a_known_family():
             allowed |= {"dma"} if tune and not use_wino else set()
             allowed |= ({"x3"} | ({"w3"} if use_wino else set())) if x3 else set()
         assert fam in allowed, "%r: code %d (%s) is ignored by the layer this key describes" % (key, code, fam)
+
+
+def test_decode_names_the_family_of_every_code():
+    """ops._decode, the dispatch's one decoder, against code_family above (an independent restatement) on every value of the
+    table and on every candidate the timed selection can record, its base added; the argument recombines to the code"""
+    base = {"own": 0, "w4": 0, "dma": 2000, "x3": ops.X3_BASE, "w3": ops.W3_BASE}
+    assert ops.DMA_BASE == 2000 and (ops.X3_BASE, ops.W3_BASE) == (30000, 40000) and ops.W4_CODES == {2464: (2, 64)}
+    codes = set(tile_table.TILES.values()) | set(ops.W4_CODES) | set(ops.TUNE_CANDIDATES) | set(ops.WINO_CANDIDATES)
+    codes |= set(ops.XTUNE_CANDIDATES) | set(ops.XTUNE_ROWSHIFT)                                   # tiles of a PackedConvX's own kernel
+    codes |= {2000 + t for t in ops.XTUNE_CANDIDATES if t < 100}                                   # ... as a tuned fp32 layer's alternative
+    codes |= {ops.X3_BASE + t for t in ops.XTUNE_CANDIDATES}                                       # ... on split operands
+    codes |= {ops.W3_BASE + s for s in ops.W3_CANDIDATES + (ops.W3_WIDE, ops.W3_WIDE_FALLBACK)}
+    assert len(codes) > 40
+    for code in sorted(codes):
+        fam, arg = ops._decode(code)
+        assert fam is not None and fam == code_family(code), "code %d: _decode says %s, code_family %s" % (code, fam, code_family(code))
+        assert base[fam] + arg == code, "code %d: (%s, %r) does not recombine" % (code, fam, arg)
+        assert fam != "w4" or arg in ops.W4_CODES
+    # 107 / 108, the ping-pong tiles, exist on split operands only: the fp32 LDS-DMA kernel answers EUNSUP, PackedConvX._time_tiles
+    # skips what it cannot launch, and so no timed selection records 2107 / 2108.  They are no code of the LDS-DMA family (2000 ... 2099):
+    # neither restatement calls them one, and a tuned layer ignores them (its own tiles end below 2000)
+    for code in (2000 + t for t in ops.XTUNE_CANDIDATES if t >= 100):
+        assert ops._decode(code)[0] != "dma" and code_family(code) is None, code
+
+
+def test_image_chunks_by_plain_arithmetic():
+    """the 4 GiB rule of the 32-bit buffer resources: batches below it are one chunk, others go in runs of whole images"""
+    chunks = lambda N, per_img: list(ops._image_chunks(N, per_img))
+    assert chunks(5, 2 ** 30) == [(0, 3), (3, 5)]
+    assert chunks(5, 2 ** 31) == [(0, 1), (1, 2), (2, 3), (3, 4), (4, 5)]
+    assert chunks(1, 2 ** 40) == [(0, 1)], "a single image is never split"
+    assert chunks(7, 100) == [(0, 7)] and chunks(3, (2 ** 32 - 2) // 3) == [(0, 3)], "N * per_img < 2^32 - 1: one chunk"
+    assert chunks(3, (2 ** 32 - 2) // 3 + 1) == [(0, 2), (2, 3)], "the first size past the limit"
 
 
 # --------------------------------------------------------------------------------------------------------- shapes and references
