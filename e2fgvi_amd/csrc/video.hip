@@ -85,11 +85,15 @@ __global__ void composite_kernel(const float* __restrict__ pred, const int* __re
 // fixed-point weights coeffs[o][*] (22 fraction bits, built by e2fgvi_amd/video.py::bicubic_tables like Pillow's
 // precompute_coeffs) and stores clamp((2^21 + sum) >> 22, 0, 255) from an int32 accumulator, as Pillow does per pass.
 // One block per output row (l, y) at a time, its threads along the row's x*3+c bytes: coalesced stores; the vertical pass
-// also reads rows coalesced, the horizontal one reads a row's bytes at stride 3 per tap (L1 hits).
+// also reads rows coalesced, the horizontal one reads a row's bytes at stride 3 per tap (L1 hits).  The horizontal pass takes a
+// row window: it reads rows [row0, row0 + nrows) of every frame (frames H rows apart) and writes [L,nrows,n_out,3] (frames nrows
+// rows apart) -- Pillow's ImagingResample runs its width pass only over the rows its height pass will read.  The vertical pass
+// and the whole-frame horizontal one have row0 = 0, nrows = H.
 template <bool VERTICAL>
 __global__ void resample_u8_kernel(const unsigned char* __restrict__ src, unsigned char* __restrict__ dst, int L, int H, int W,
-                                   int n_out, const int* __restrict__ bounds, const int* __restrict__ coeffs, int ksize) {
-    const int Ho = VERTICAL ? n_out : H;
+                                   int n_out, int row0, int nrows, const int* __restrict__ bounds, const int* __restrict__ coeffs,
+                                   int ksize) {
+    const int Ho = VERTICAL ? n_out : nrows;
     const int Wo = VERTICAL ? W : n_out;
     const int n_in = VERTICAL ? H : W;
     const int row = Wo * 3;
@@ -114,7 +118,7 @@ __global__ void resample_u8_kernel(const unsigned char* __restrict__ src, unsign
                 s = src + (l * H + first) * (long long)W * 3 + xc;
                 step = (long long)W * 3;
             } else {
-                s = src + (l * H + y) * (long long)W * 3 + first * 3 + (xc - 3 * x);
+                s = src + (l * H + row0 + y) * (long long)W * 3 + first * 3 + (xc - 3 * x);
                 step = 3;
             }
             int acc = 1 << 21;
@@ -206,6 +210,9 @@ int slab_copy(const void* cache, const void* rows, const int32_t* ids, int32_t n
 //     the tile (<= RT_H / scale + 4 rows).  A patch beyond the fixed LDS budget (a strongly shrinking axis) takes the direct
 //     path: the same arithmetic with the horizontal values recomputed from global memory per vertical tap.
 // Every table entry is clipped before it is used as an index, so the kernel stays in bounds whatever the tables hold.
+// With a box (left, upper, Bw, Bh) inside the frame the paste is confined to it: the tables index box-relative pixels (ytab / by /
+// cy have Bh entries, xtab / bx / cx have Bw), the grid stays tiled on the full frame, a pixel outside the box counts as "no hole"
+// and takes src -- so a tile wholly outside the box is a copied tile.  The whole frame is the box (0, 0, W, H).
 constexpr int RT_W = 128, RT_H = 8, RT_WB = RT_W * 3;
 constexpr int RT_ROWS = 24;                    // horizontal-pass rows kept in LDS (RT_ROWS * RT_WB bytes)
 constexpr int RT_PATCH = 8192;                 // bytes of `lo` staged in LDS
@@ -255,7 +262,7 @@ template <bool STAGED>
 __device__ __forceinline__ void restore_vpass(const unsigned char* __restrict__ lo_l, const unsigned char* __restrict__ src,
                                               unsigned char* __restrict__ out, const unsigned char* s_m, const unsigned char* s_h,
                                               int r0, long long frame_off, int h, int w, int W, int x0, int y0, int nb, int th,
-                                              const int* __restrict__ bx, const int* __restrict__ cx, int kx,
+                                              int left, int upper, int Bh, const int* __restrict__ bx, const int* __restrict__ cx, int kx,
                                               const int* __restrict__ by, const int* __restrict__ cy, int ky) {
     for (int u = threadIdx.x; u < th * (RT_WB / 4); u += NTH) {
         const int ty = u / (RT_WB / 4), xc0 = (u - ty * (RT_WB / 4)) * 4;
@@ -272,9 +279,11 @@ __device__ __forceinline__ void restore_vpass(const unsigned char* __restrict__ 
             for (int k = 0; k < 4; ++k)
                 if (k < n4) v[k] = src[off + k];
         }
-        int fy, ny;
-        clipped_taps(by, y, h, ky, fy, ny);
-        const int* kyp = cy + (long long)y * ky;
+        const bool inside = y >= upper && y - upper < Bh;      // a row outside the box has no hole pixel (s_m): no taps are read
+        const int iy = inside ? y - upper : 0;
+        int fy = 0, ny = 0;
+        if (inside) clipped_taps(by, iy, h, ky, fy, ny);
+        const int* kyp = cy + (long long)iy * ky;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int xc = xc0 + k, x = xc / 3, c = xc - 3 * x;
@@ -284,7 +293,7 @@ __device__ __forceinline__ void restore_vpass(const unsigned char* __restrict__ 
             for (int j = 0; j < ny; ++j) {
                 const int r = fy + j;
                 const int hv = STAGED ? (int)s_h[(r - r0) * RT_WB + xc]
-                                      : restore_hpass_global(lo_l + (long long)r * w * 3, w, bx, cx, kx, x0 + x, c);
+                                      : restore_hpass_global(lo_l + (long long)r * w * 3, w, bx, cx, kx, x0 + x - left, c);
                 acc += hv * kyp[j];
             }
             v[k] = pillow_clip8(acc);
@@ -301,8 +310,9 @@ __device__ __forceinline__ void restore_vpass(const unsigned char* __restrict__ 
 
 __global__ __launch_bounds__(NTH) void restore_u8_kernel(
     const unsigned char* __restrict__ lo, const unsigned char* __restrict__ mask, const unsigned char* __restrict__ src,
-    unsigned char* __restrict__ out, int L, int h, int w, int H, int W, const int* __restrict__ ytab, const int* __restrict__ xtab,
-    const int* __restrict__ bx, const int* __restrict__ cx, int kx, const int* __restrict__ by, const int* __restrict__ cy, int ky) {
+    unsigned char* __restrict__ out, int L, int h, int w, int H, int W, int left, int upper, int Bw, int Bh,
+    const int* __restrict__ ytab, const int* __restrict__ xtab, const int* __restrict__ bx, const int* __restrict__ cx, int kx,
+    const int* __restrict__ by, const int* __restrict__ cy, int ky) {
     __shared__ unsigned char s_m[RT_H * RT_W];
     __shared__ __align__(16) unsigned char s_patch[RT_PATCH];
     __shared__ __align__(16) unsigned char s_h[RT_ROWS * RT_WB];
@@ -318,8 +328,9 @@ __global__ __launch_bounds__(NTH) void restore_u8_kernel(
         for (int i = tid; i < RT_H * RT_W; i += NTH) {
             const int ty = i / RT_W, tx = i % RT_W;
             unsigned char m = 0;
-            if (ty < th && tx < tw) {
-                int my = ytab[y0 + ty], mx = xtab[x0 + tx];
+            const int iy = y0 + ty - upper, ix = x0 + tx - left;
+            if (ty < th && tx < tw && iy >= 0 && iy < Bh && ix >= 0 && ix < Bw) {
+                int my = ytab[iy], mx = xtab[ix];
                 my = my < 0 ? 0 : (my > h - 1 ? h - 1 : my);
                 mx = mx < 0 ? 0 : (mx > w - 1 ? w - 1 : mx);
                 m = ml[(long long)my * w + mx] != 0;
@@ -345,14 +356,14 @@ __global__ __launch_bounds__(NTH) void restore_u8_kernel(
         // rows [r0, r1) and columns [c0, c1) of lo that the tile's taps reach
         if (tid < 4) s_rng[tid] = (tid & 1) ? 0 : 0x7fffffff;
         __syncthreads();
-        if (tid < th) {
+        if (tid < th && y0 + tid >= upper && y0 + tid < upper + Bh) {
             int f, n;
-            clipped_taps(by, y0 + tid, h, ky, f, n);
+            clipped_taps(by, y0 + tid - upper, h, ky, f, n);
             if (n > 0) { atomicMin(&s_rng[0], f); atomicMax(&s_rng[1], f + n); }
         }
-        if (tid < tw) {
+        if (tid < tw && x0 + tid >= left && x0 + tid < left + Bw) {
             int f, n;
-            clipped_taps(bx, x0 + tid, w, kx, f, n);
+            clipped_taps(bx, x0 + tid - left, w, kx, f, n);
             if (n > 0) { atomicMin(&s_rng[2], f); atomicMax(&s_rng[3], f + n); }
         }
         __syncthreads();
@@ -370,9 +381,11 @@ __global__ __launch_bounds__(NTH) void restore_u8_kernel(
             __syncthreads();
             for (int i = tid; i < pr * nb; i += NTH) {
                 const int r = i / nb, xc = i - r * nb, x = xc / 3, c = xc - 3 * x;
+                const int ix = x0 + x - left;
+                if (ix < 0 || ix >= Bw) continue;       // a column outside the box: no hole pixel reads its s_h
                 int f, n;
-                clipped_taps(bx, x0 + x, w, kx, f, n);
-                const int* k = cx + (long long)(x0 + x) * kx;
+                clipped_taps(bx, ix, w, kx, f, n);
+                const int* k = cx + (long long)ix * kx;
                 const unsigned char* p = s_patch + r * pb + (f - c0) * 3 + c;        // n > 0 implies c0 <= f, f + n <= c0 + pc
                 int acc = 1 << 21;
 #pragma unroll 1
@@ -380,11 +393,86 @@ __global__ __launch_bounds__(NTH) void restore_u8_kernel(
                 s_h[r * RT_WB + xc] = pillow_clip8(acc);
             }
             __syncthreads();
-            restore_vpass<true>(lo_l, src, out, s_m, s_h, r0, frame_off, h, w, W, x0, y0, nb, th, bx, cx, kx, by, cy, ky);
+            restore_vpass<true>(lo_l, src, out, s_m, s_h, r0, frame_off, h, w, W, x0, y0, nb, th, left, upper, Bh, bx, cx, kx, by, cy, ky);
         } else {
-            restore_vpass<false>(lo_l, src, out, s_m, s_h, r0, frame_off, h, w, W, x0, y0, nb, th, bx, cx, kx, by, cy, ky);
+            restore_vpass<false>(lo_l, src, out, s_m, s_h, r0, frame_off, h, w, W, x0, y0, nb, th, left, upper, Bh, bx, cx, kx, by, cy, ky);
         }
         __syncthreads();                                // s_m, s_h are rewritten for the next frame
+    }
+}
+
+// Bounding box of the hole over a whole video (the crop region of video.hole_region): masks uint8 [L,Hm,Wm], any non-zero byte
+// is hole; box = (x0, y0, x1, y1), upper ends exclusive, starts at (0x7f7f7f7f, 0x7f7f7f7f, 0, 0) -- empty: x1 <= x0.  One pass,
+// HBM-bound: a wave owns a mask row at a time (rows = L * Hm, grid-strided) and reads it as 16-byte words between a byte head up
+// to the row's first 16-byte boundary and a byte tail (any pitch, any base), first / last non-zero byte of a word by ffs / clz;
+// the lanes' boxes are reduced within the wave (wave64 shuffles), the waves' within the block through LDS, and a block that saw
+// a hole pixel issues the four global atomicMin / atomicMax -- a block that saw none issues nothing.
+constexpr int BB_WAVES = NTH / 64;
+
+__device__ __forceinline__ void bbox_word(unsigned v, int x, int& lo, int& hi) {
+    if (v) {
+        const int a = x + ((__ffs((int)v) - 1) >> 3), b = x + ((31 - __clz((int)v)) >> 3) + 1;      // little endian: byte 0 is the lowest address
+        lo = a < lo ? a : lo;
+        hi = b > hi ? b : hi;
+    }
+}
+
+__global__ __launch_bounds__(NTH) void hole_bbox_kernel(const unsigned char* __restrict__ m, long long rows, int Hm, int Wm,
+                                                        int* __restrict__ box) {
+    __shared__ int s_box[BB_WAVES][4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int x0 = 0x7fffffff, y0 = 0x7fffffff, x1 = 0, y1 = 0;
+    const long long step = (long long)gridDim.x * BB_WAVES;
+    for (long long r = (long long)blockIdx.x * BB_WAVES + wave; r < rows; r += step) {
+        const unsigned char* p = m + r * Wm;
+        int head = (int)((16 - (int)((uintptr_t)p & 15)) & 15);
+        head = head < Wm ? head : Wm;
+        const int body = (Wm - head) / 16, t0 = head + body * 16;
+        int lo = 0x7fffffff, hi = 0;
+        for (int k = lane; k < head; k += 64)
+            if (p[k]) { lo = k < lo ? k : lo; hi = k + 1; }
+        const uint4* pv = reinterpret_cast<const uint4*>(p + head);
+        for (int k = lane; k < body; k += 64) {
+            const uint4 v = pv[k];
+            const int x = head + 16 * k;
+            bbox_word(v.x, x, lo, hi);
+            bbox_word(v.y, x + 4, lo, hi);
+            bbox_word(v.z, x + 8, lo, hi);
+            bbox_word(v.w, x + 12, lo, hi);
+        }
+        for (int k = t0 + lane; k < Wm; k += 64)
+            if (p[k]) { lo = k < lo ? k : lo; hi = k + 1; }
+        if (hi > lo) {
+            const int y = (int)(r % Hm);
+            x0 = lo < x0 ? lo : x0;
+            x1 = hi > x1 ? hi : x1;
+            y0 = y < y0 ? y : y0;
+            y1 = y + 1 > y1 ? y + 1 : y1;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const int a = __shfl_xor(x0, o, 64), b = __shfl_xor(y0, o, 64), c = __shfl_xor(x1, o, 64), d = __shfl_xor(y1, o, 64);
+        x0 = a < x0 ? a : x0;
+        y0 = b < y0 ? b : y0;
+        x1 = c > x1 ? c : x1;
+        y1 = d > y1 ? d : y1;
+    }
+    if (lane == 0) { s_box[wave][0] = x0; s_box[wave][1] = y0; s_box[wave][2] = x1; s_box[wave][3] = y1; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int i = 1; i < BB_WAVES; ++i) {
+            x0 = s_box[i][0] < x0 ? s_box[i][0] : x0;
+            y0 = s_box[i][1] < y0 ? s_box[i][1] : y0;
+            x1 = s_box[i][2] > x1 ? s_box[i][2] : x1;
+            y1 = s_box[i][3] > y1 ? s_box[i][3] : y1;
+        }
+        if (x1 > x0) {
+            atomicMin(box, x0);
+            atomicMin(box + 1, y0);
+            atomicMax(box + 2, x1);
+            atomicMax(box + 3, y1);
+        }
     }
 }
 
@@ -395,14 +483,16 @@ inline bool ranges_overlap(const void* a, long long na, const void* b, long long
 
 }  // namespace
 
-extern "C" int e2fgvi_restore_u8(const uint8_t* lo, const uint8_t* mask_lo, const uint8_t* src, uint8_t* out, int32_t L, int32_t h,
-                                 int32_t w, int32_t H, int32_t W, const int32_t* ytab, const int32_t* xtab, const int32_t* bounds_x,
-                                 const int32_t* coeffs_x, int32_t ksize_x, const int32_t* bounds_y, const int32_t* coeffs_y,
-                                 int32_t ksize_y, void* stream) {
+extern "C" int e2fgvi_restore_box_u8(const uint8_t* lo, const uint8_t* mask_lo, const uint8_t* src, uint8_t* out, int32_t L, int32_t h,
+                                     int32_t w, int32_t H, int32_t W, int32_t left, int32_t upper, int32_t Bw, int32_t Bh,
+                                     const int32_t* ytab, const int32_t* xtab, const int32_t* bounds_x, const int32_t* coeffs_x,
+                                     int32_t ksize_x, const int32_t* bounds_y, const int32_t* coeffs_y, int32_t ksize_y, void* stream) {
     E2_REQUIRE(lo && mask_lo && src && out && ytab && xtab && bounds_x && coeffs_x && bounds_y && coeffs_y, E2FGVI_EINVAL,
                "restore_u8: null pointer");
     E2_REQUIRE(L > 0 && h > 0 && w > 0 && H > 0 && W > 0 && ksize_x >= 1 && ksize_y >= 1, E2FGVI_EINVAL,
                "restore_u8: sizes and tap counts must be positive");
+    E2_REQUIRE(left >= 0 && upper >= 0 && Bw > 0 && Bh > 0 && Bw <= W - left && Bh <= H - upper, E2FGVI_EINVAL,
+               "restore_u8: the box (%d, %d) + %d x %d must be non-empty and lie inside the %d x %d frame", left, upper, Bw, Bh, W, H);
     E2_REQUIRE(W * 3LL <= 0x7fffffffLL && w * 3LL <= 0x7fffffffLL && (H + RT_H - 1) / RT_H <= 65535, E2FGVI_EINVAL,
                "restore_u8: frames too large");
     const long long n_out = (long long)L * H * W * 3, n_lo = (long long)L * h * w * 3;
@@ -410,9 +500,36 @@ extern "C" int e2fgvi_restore_u8(const uint8_t* lo, const uint8_t* mask_lo, cons
                    !ranges_overlap(out, n_out, mask_lo, n_lo / 3),
                E2FGVI_EINVAL, "restore_u8: out must not overlap src, lo or mask_lo");
     const dim3 grid((unsigned)((W + RT_W - 1) / RT_W), (unsigned)((H + RT_H - 1) / RT_H), (unsigned)(L < 1024 ? L : 1024));
-    hipLaunchKernelGGL(restore_u8_kernel, grid, dim3(NTH), 0, (hipStream_t)stream, lo, mask_lo, src, out, L, h, w, H, W, ytab, xtab,
-                       bounds_x, coeffs_x, ksize_x, bounds_y, coeffs_y, ksize_y);
+    hipLaunchKernelGGL(restore_u8_kernel, grid, dim3(NTH), 0, (hipStream_t)stream, lo, mask_lo, src, out, L, h, w, H, W, left, upper, Bw,
+                       Bh, ytab, xtab, bounds_x, coeffs_x, ksize_x, bounds_y, coeffs_y, ksize_y);
     E2_LAUNCH_CHECK("restore_u8");
+    return 0;
+}
+
+// the whole frame as the box: the same checks, the same kernel
+extern "C" int e2fgvi_restore_u8(const uint8_t* lo, const uint8_t* mask_lo, const uint8_t* src, uint8_t* out, int32_t L, int32_t h,
+                                 int32_t w, int32_t H, int32_t W, const int32_t* ytab, const int32_t* xtab, const int32_t* bounds_x,
+                                 const int32_t* coeffs_x, int32_t ksize_x, const int32_t* bounds_y, const int32_t* coeffs_y,
+                                 int32_t ksize_y, void* stream) {
+    E2_REQUIRE(H > 0 && W > 0, E2FGVI_EINVAL, "restore_u8: sizes and tap counts must be positive");
+    return e2fgvi_restore_box_u8(lo, mask_lo, src, out, L, h, w, H, W, 0, 0, W, H, ytab, xtab, bounds_x, coeffs_x, ksize_x, bounds_y,
+                                 coeffs_y, ksize_y, stream);
+}
+
+extern "C" int e2fgvi_hole_bbox(const uint8_t* masks, int32_t L, int32_t Hm, int32_t Wm, int32_t* box, void* stream) {
+    E2_REQUIRE(box && L >= 0 && Hm >= 0 && Wm >= 0, E2FGVI_EINVAL, "hole_bbox: bad arguments");
+    const long long rows = (long long)L * Hm;
+    E2_REQUIRE(masks || rows * Wm == 0, E2FGVI_EINVAL, "hole_bbox: null masks");
+    // the empty box (0x7f7f7f7f, 0x7f7f7f7f, 0, 0), on the stream of the launch that lowers / raises it
+    hipError_t e = hipMemsetAsync(box, 0x7f, 2 * sizeof(int32_t), (hipStream_t)stream);
+    if (e == hipSuccess) e = hipMemsetAsync(box + 2, 0, 2 * sizeof(int32_t), (hipStream_t)stream);
+    E2_REQUIRE(e == hipSuccess, (int)e, "hole_bbox: hipMemsetAsync failed: %s", hipGetErrorString(e));
+    if (rows * Wm == 0) return 0;
+    // a wave per row; enough blocks to fill the chip, the rest grid-strided
+    long long blocks = (rows + BB_WAVES - 1) / BB_WAVES;
+    blocks = blocks < 2048 ? blocks : 2048;
+    hipLaunchKernelGGL(hole_bbox_kernel, dim3((unsigned)blocks), dim3(NTH), 0, (hipStream_t)stream, masks, rows, Hm, Wm, box);
+    E2_LAUNCH_CHECK("hole_bbox");
     return 0;
 }
 
@@ -462,6 +579,21 @@ extern "C" int e2fgvi_composite(const float* pred, const int32_t* ids, const uin
     return 0;
 }
 
+extern "C" int e2fgvi_resample_rows_u8(const uint8_t* src, uint8_t* dst, int32_t L, int32_t H, int32_t W, int32_t n_out, int32_t row0,
+                                       int32_t rows, const int32_t* bounds, const int32_t* coeffs, int32_t ksize, void* stream) {
+    E2_REQUIRE(src && dst && bounds && coeffs && L > 0 && H > 0 && W > 0 && n_out > 0 && ksize > 0, E2FGVI_EINVAL,
+               "resample_rows_u8: bad arguments");
+    E2_REQUIRE(row0 >= 0 && rows > 0 && rows <= H - row0, E2FGVI_EINVAL, "resample_rows_u8: rows [%d, %d + %d) leave the %d rows of a frame",
+               row0, row0, rows, H);
+    E2_REQUIRE(W * 3LL <= 0x7fffffffLL && n_out * 3LL <= 0x7fffffffLL, E2FGVI_EINVAL, "resample_rows_u8: rows too wide");
+    const long long total = (long long)L * rows;
+    const unsigned grid = (unsigned)(total < (1LL << 20) ? total : (1LL << 20));     // the kernel strides over the rest
+    hipLaunchKernelGGL(resample_u8_kernel<false>, dim3(grid), dim3(NTH), 0, (hipStream_t)stream, src, dst, L, H, W, n_out, row0, rows,
+                       bounds, coeffs, ksize);
+    E2_LAUNCH_CHECK("resample_rows_u8");
+    return 0;
+}
+
 extern "C" int e2fgvi_resample_u8(const uint8_t* src, uint8_t* dst, int32_t L, int32_t H, int32_t W, int32_t n_out, int32_t axis,
                                   const int32_t* bounds, const int32_t* coeffs, int32_t ksize, void* stream) {
     E2_REQUIRE(src && dst && bounds && coeffs && L > 0 && H > 0 && W > 0 && n_out > 0 && ksize > 0, E2FGVI_EINVAL,
@@ -472,10 +604,10 @@ extern "C" int e2fgvi_resample_u8(const uint8_t* src, uint8_t* dst, int32_t L, i
     const long long rows = (long long)L * (axis == 1 ? n_out : H);
     const unsigned grid = (unsigned)(rows < (1LL << 20) ? rows : (1LL << 20));      // the kernel strides over the rest
     if (axis == 1)
-        hipLaunchKernelGGL(resample_u8_kernel<true>, dim3(grid), dim3(NTH), 0, (hipStream_t)stream, src, dst, L, H, W, n_out, bounds,
+        hipLaunchKernelGGL(resample_u8_kernel<true>, dim3(grid), dim3(NTH), 0, (hipStream_t)stream, src, dst, L, H, W, n_out, 0, H, bounds,
                            coeffs, ksize);
     else
-        hipLaunchKernelGGL(resample_u8_kernel<false>, dim3(grid), dim3(NTH), 0, (hipStream_t)stream, src, dst, L, H, W, n_out, bounds,
+        hipLaunchKernelGGL(resample_u8_kernel<false>, dim3(grid), dim3(NTH), 0, (hipStream_t)stream, src, dst, L, H, W, n_out, 0, H, bounds,
                            coeffs, ksize);
     E2_LAUNCH_CHECK("resample_u8");
     return 0;

@@ -1587,9 +1587,15 @@ def composite(pred, ids, first, frames_u8, masks01, comp):
     return comp
 
 
-def resample_u8(frames_u8, n_out, axis, bounds, coeffs):
+def _taps_of(span, n_out):
+    """ksize of video.bicubic_tables for `span` source pixels resized to n_out"""
+    return 2 * math.ceil(2.0 * max(span / n_out, 1.0)) + 1
+
+
+def resample_u8(frames_u8, n_out, axis, bounds, coeffs, span=None):
     """frames_u8 [L,H,W,3] uint8 -> uint8 with dimension `axis` (1: H, 2: W) resized to n_out: one bicubic pass of PIL's
-    Image.resize with the tables of video.bicubic_tables (bounds int32 [n_out,2], coeffs int32 [n_out,ksize])."""
+    Image.resize with the tables of video.bicubic_tables (bounds int32 [n_out,2], coeffs int32 [n_out,ksize]).  ``span``: the
+    number of source pixels the tables were built for when that is a box of the axis (bicubic_tables(box=)), not all of it."""
     lib = _L.load()
     _u8(frames_u8, "frames"); _chk(bounds, "bounds", torch.int32); _chk(coeffs, "coeffs", torch.int32)
     if frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
@@ -1603,8 +1609,10 @@ def resample_u8(frames_u8, n_out, axis, bounds, coeffs):
     L, H, W, _ = frames_u8.shape
     n_in = frames_u8.shape[axis]
     ksize = coeffs.shape[1]
-    if ksize != 2 * math.ceil(2.0 * max(n_in / n_out, 1.0)) + 1:
-        raise ValueError("coeffs of %d taps do not belong to a %d -> %d resize" % (ksize, n_in, n_out))
+    if span is not None and not 0 < span <= n_in:
+        raise ValueError("span must be in (0, %d], got %r" % (n_in, span))
+    if ksize != _taps_of(n_in if span is None else span, n_out):
+        raise ValueError("coeffs of %d taps do not belong to a %d -> %d resize" % (ksize, n_in if span is None else span, n_out))
     shape = (L, n_out, W, 3) if axis == 1 else (L, H, n_out, 3)
     out = torch.empty(shape, dtype=torch.uint8, device=frames_u8.device)
     _L.check(lib.e2fgvi_resample_u8(_ptr(frames_u8), _ptr(out), L, H, W, n_out, axis, _ptr(bounds), _ptr(coeffs), ksize, _stream()),
@@ -1612,11 +1620,48 @@ def resample_u8(frames_u8, n_out, axis, bounds, coeffs):
     return out
 
 
-def restore_u8(lo, mask_lo, src, ytab, xtab, bx, cx, by, cy, out=None):
+def resample_rows_u8(frames_u8, n_out, row0, rows, bounds, coeffs):
+    """The width pass of resample_u8 over rows [row0, row0 + rows) of every frame: frames_u8 [L,H,W,3] uint8 -> [L,rows,n_out,3].
+    bounds int32 [n_out,2] hold absolute source columns (video.bicubic_tables(W, n_out, box=(left, right)), or one-tap tables of
+    a crop), coeffs int32 [n_out,ksize], ksize >= 1 the tables' own; entries are clipped to the frame in the kernel."""
+    lib = _L.load()
+    _u8(frames_u8, "frames"); _chk(bounds, "bounds", torch.int32); _chk(coeffs, "coeffs", torch.int32)
+    if frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
+        raise ValueError("frames must be [L,H,W,3], got %s" % (tuple(frames_u8.shape),))
+    if bounds.device != frames_u8.device or coeffs.device != frames_u8.device:
+        raise ValueError("frames, bounds and coeffs must be on one device")
+    if bounds.dim() != 2 or tuple(bounds.shape) != (n_out, 2) or coeffs.dim() != 2 or coeffs.shape[0] != n_out or coeffs.shape[1] < 1:
+        raise ValueError("bounds must be [n_out,2] and coeffs [n_out,ksize] for n_out = %d" % n_out)
+    L, H, W, _ = frames_u8.shape
+    row0, rows = int(row0), int(rows)
+    if row0 < 0 or rows < 1 or row0 + rows > H:
+        raise ValueError("rows [%d, %d) are not rows of a %d-row frame" % (row0, row0 + rows, H))
+    out = torch.empty((L, rows, n_out, 3), dtype=torch.uint8, device=frames_u8.device)
+    _L.check(lib.e2fgvi_resample_rows_u8(_ptr(frames_u8), _ptr(out), L, H, W, n_out, row0, rows, _ptr(bounds), _ptr(coeffs),
+                                         coeffs.shape[1], _stream()), "resample_rows_u8")
+    return out
+
+
+def hole_bbox(masks_u8):
+    """masks_u8 [L,Hm,Wm] uint8 on the device (any non-zero byte is hole) -> device int32 [4] = (x0, y0, x1, y1), the hole's
+    bounding box over all frames, upper ends exclusive; x1 <= x0: no hole.  No host read (csrc/video.hip hole_bbox_kernel)."""
+    lib = _L.load()
+    _u8(masks_u8, "masks")
+    if masks_u8.dim() != 3:
+        raise ValueError("masks must be [L,Hm,Wm], got %s" % (tuple(masks_u8.shape),))
+    L, Hm, Wm = masks_u8.shape
+    out = torch.empty(4, dtype=torch.int32, device=masks_u8.device)
+    _L.check(lib.e2fgvi_hole_bbox(_ptr(masks_u8), L, Hm, Wm, _ptr(out), _stream()), "hole_bbox")
+    return out
+
+
+def restore_u8(lo, mask_lo, src, ytab, xtab, bx, cx, by, cy, out=None, box=None):
     """out = where(NEAREST(mask_lo) != 0, BICUBIC(lo), src) at the size of src, one fused launch (csrc/video.hip): lo [L,h,w,3]
     finished frames, mask_lo [L,h,w] of 0 / 1, src [L,H,W,3], all uint8; ytab int32 [H] / xtab int32 [W] from video.nearest_table;
     bx int32 [W,2], cx int32 [W,kx] and by int32 [H,2], cy int32 [H,ky] from video.bicubic_tables, or the one-tap identity for an
-    axis that keeps its size.  Returns a fresh uint8 [L,H,W,3] unless `out` is given; out must not overlap the inputs."""
+    axis that keeps its size.  Returns a fresh uint8 [L,H,W,3] unless `out` is given; out must not overlap the inputs.
+    ``box`` = (left, upper, right, lower) inside the frame confines the paste to that box: out is src outside it, the tables are
+    those of a resize to the box's size (right - left, lower - upper) and index box-relative pixels."""
     lib = _L.load()
     _u8(lo, "lo"); _u8(mask_lo, "mask_lo"); _u8(src, "src")
     tabs = (("ytab", ytab), ("xtab", xtab), ("bx", bx), ("cx", cx), ("by", by), ("cy", cy))
@@ -1626,7 +1671,16 @@ def restore_u8(lo, mask_lo, src, ytab, xtab, bx, cx, by, cy, out=None):
         raise ValueError("lo and src must be [L,.,.,3] and mask_lo [L,.,.], got %s, %s and %s"
                          % (tuple(lo.shape), tuple(src.shape), tuple(mask_lo.shape)))
     L, h, w, _ = lo.shape
-    H, W = src.shape[1], src.shape[2]
+    FH, FW = src.shape[1], src.shape[2]
+    if box is None:
+        left, upper, W, H = 0, 0, FW, FH
+    else:
+        if len(box) != 4:
+            raise ValueError("box must be (left, upper, right, lower), got %r" % (box,))
+        left, upper, right, lower = (int(v) for v in box)
+        if not (0 <= left < right <= FW and 0 <= upper < lower <= FH):
+            raise ValueError("box %r must be non-empty and lie inside the %d x %d frame" % (tuple(box), FW, FH))
+        W, H = right - left, lower - upper
     if src.shape[0] != L or tuple(mask_lo.shape) != (L, h, w) or min(L, h, w, H, W) < 1:
         raise ValueError("lo %s, mask_lo %s and src %s do not belong to one video" % (tuple(lo.shape), tuple(mask_lo.shape),
                                                                                        tuple(src.shape)))
@@ -1640,13 +1694,18 @@ def restore_u8(lo, mask_lo, src, ytab, xtab, bx, cx, by, cy, out=None):
         if c.shape[1] != 2 * math.ceil(2.0 * max(n_in / n_out, 1.0)) + 1 and not (n_in == n_out and c.shape[1] == 1):
             raise ValueError("c%s of %d taps does not belong to a %d -> %d resize" % (ax, c.shape[1], n_in, n_out))
     if out is None:
-        out = torch.empty((L, H, W, 3), dtype=torch.uint8, device=src.device)
+        out = torch.empty((L, FH, FW, 3), dtype=torch.uint8, device=src.device)
     else:
         _u8(out, "out")
-        if tuple(out.shape) != (L, H, W, 3) or out.device != src.device:
-            raise ValueError("out must be uint8 %s on the device of src" % ((L, H, W, 3),))
-    _L.check(lib.e2fgvi_restore_u8(_ptr(lo), _ptr(mask_lo), _ptr(src), _ptr(out), L, h, w, H, W, _ptr(ytab), _ptr(xtab), _ptr(bx),
-                                   _ptr(cx), cx.shape[1], _ptr(by), _ptr(cy), cy.shape[1], _stream()), "restore_u8")
+        if tuple(out.shape) != (L, FH, FW, 3) or out.device != src.device:
+            raise ValueError("out must be uint8 %s on the device of src" % ((L, FH, FW, 3),))
+    if box is None:
+        _L.check(lib.e2fgvi_restore_u8(_ptr(lo), _ptr(mask_lo), _ptr(src), _ptr(out), L, h, w, H, W, _ptr(ytab), _ptr(xtab), _ptr(bx),
+                                       _ptr(cx), cx.shape[1], _ptr(by), _ptr(cy), cy.shape[1], _stream()), "restore_u8")
+    else:
+        _L.check(lib.e2fgvi_restore_box_u8(_ptr(lo), _ptr(mask_lo), _ptr(src), _ptr(out), L, h, w, FH, FW, left, upper, W, H, _ptr(ytab),
+                                           _ptr(xtab), _ptr(bx), _ptr(cx), cx.shape[1], _ptr(by), _ptr(cy), cy.shape[1], _stream()),
+                 "restore_box_u8")
     return out
 
 

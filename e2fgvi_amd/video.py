@@ -8,6 +8,7 @@ everything after the upload runs in HIP kernels (csrc/video.hip) and only the fi
 arithmetic has no CPU path.
 """
 import math
+from fractions import Fraction
 
 import numpy as np
 import torch
@@ -128,13 +129,26 @@ def padded_size(h, w, mod_h=60, mod_w=108):
     return h + (mod_h - h % mod_h) % mod_h, w + (mod_w - w % mod_w) % mod_w
 
 
-def nearest_table(n_in, n_out):
+def _axis_box(n_in, box):
+    """(lo, hi) of a box along an axis of n_in pixels; None is the whole axis"""
+    if box is None:
+        return 0, int(n_in)
+    lo, hi = (int(v) for v in box)
+    if not 0 <= lo < hi <= n_in:
+        raise ValueError("box (%d, %d) must be non-empty and lie inside [0, %d]" % (lo, hi, n_in))
+    return lo, hi
+
+
+def nearest_table(n_in, n_out, box=None):
     """Source index of every output index of PIL's ``Image.resize(size, Image.NEAREST)`` (test.py:62).  Pillow's
     ImagingScaleAffine starts at 0.5 * scale and ADDS the scale once per output pixel in double precision, then
-    truncates; the running sum is reproduced literally (np.cumsum accumulates sequentially)."""
-    scale = float(n_in) / float(n_out)
+    truncates; the running sum is reproduced literally (np.cumsum accumulates sequentially).  ``box`` = (lo, hi) resizes that
+    part of the axis, ``resize(size, Image.NEAREST, box=...)``: the scale is (hi - lo) / n_out and the sum starts at
+    lo + 0.5 * scale; the indices stay absolute."""
+    lo, hi = _axis_box(n_in, box)
+    scale = float(hi - lo) / float(n_out)
     steps = np.full(n_out, scale, dtype=np.float64)
-    steps[0] = 0.0 + scale * 0.5
+    steps[0] = float(lo) + scale * 0.5
     pos = np.cumsum(steps)
     return np.minimum(pos.astype(np.int64), n_in - 1).astype(np.int32)
 
@@ -148,18 +162,23 @@ def _bicubic(x):
     return np.where(x < 1.0, near, np.where(x < 2.0, far, 0.0))
 
 
-def bicubic_tables(n_in, n_out):
+def bicubic_tables(n_in, n_out, box=None):
     """Taps of one axis of PIL's ``Image.resize(size)`` (BICUBIC, Pillow's default for RGB; test.py:97-104,
     core/dataset.py:115), computed like Pillow's precompute_coeffs + normalize_coeffs_8bpc in double precision.
     Returns ``bounds`` int32 [n_out,2] = (first source index, tap count) and ``coeffs`` int32 [n_out,ksize]: the
     normalised weights in fixed point with 22 fraction bits, rounded half away from zero, zero past the tap count.
-    Output o of a pass is clamp((2**21 + sum_j src[first + j] * coeffs[o,j]) >> 22, 0, 255) (csrc/video.hip)."""
-    scale = float(n_in) / float(n_out)
+    Output o of a pass is clamp((2**21 + sum_j src[first + j] * coeffs[o,j]) >> 22, 0, 255) (csrc/video.hip).
+    ``box`` = (lo, hi), integers with 0 <= lo < hi <= n_in, is that axis of ``Image.resize(size, box=...)``: the scale (and with it
+    ksize) follows (hi - lo) / n_out and the centres start at lo, but the first indices stay absolute and the taps are clipped to
+    the IMAGE, [0, n_in), not to the box (precompute_coeffs(inSize, in0, in1, ...)) -- the outputs at the box's edge weigh the pixels
+    around the box, which is why a box resize is not a crop followed by a resize."""
+    lo, hi = _axis_box(n_in, box)
+    scale = float(hi - lo) / float(n_out)
     fs = max(scale, 1.0)
     support = 2.0 * fs
     ksize = int(math.ceil(support)) * 2 + 1
     ss = 1.0 / fs
-    center = (np.arange(n_out, dtype=np.float64) + 0.5) * scale
+    center = float(lo) + (np.arange(n_out, dtype=np.float64) + 0.5) * scale
     xmin = np.maximum((center - support + 0.5).astype(np.int64), 0)          # astype truncates toward zero, like (int)
     xmax = np.minimum((center + support + 0.5).astype(np.int64), n_in) - xmin
     j = np.arange(ksize)
@@ -175,22 +194,129 @@ def bicubic_tables(n_in, n_out):
     return bounds, coeffs
 
 
-def resize_frames(frames_u8, size, device=None):
+REGION_GUARD = 8       # model pixels kept free on every side of the hole: the 4-pixel cross dilation and a few rows of context
+
+
+def _check_box(box, frame_wh):
+    """(left, upper, right, lower) as integers, non-empty and inside the (W, H) frame; ValueError otherwise"""
+    try:
+        vals = tuple(box)
+    except TypeError:
+        raise ValueError("a box is (left, upper, right, lower), got %r" % (box,)) from None
+    if len(vals) != 4 or any(int(v) != v for v in vals):
+        raise ValueError("a box is four integers (left, upper, right, lower), got %r" % (box,))
+    left, upper, right, lower = (int(v) for v in vals)
+    W, H = (int(v) for v in frame_wh)
+    if not (0 <= left < right <= W and 0 <= upper < lower <= H):
+        raise ValueError("box %r must be non-empty and lie inside the %d x %d frame" % ((left, upper, right, lower), W, H))
+    return left, upper, right, lower
+
+
+def _scale_box(box, from_wh, to_wh):
+    """a box of a from_wh image in the pixels of the same picture at to_wh: floor for the lower ends, ceil for the upper ends"""
+    (fw, fh), (tw, th) = from_wh, to_wh
+    if (fw, fh) == (tw, th):
+        return tuple(int(v) for v in box)
+    left, upper, right, lower = (int(v) for v in box)
+    return left * tw // fw, upper * th // fh, -((-right * tw) // fw), -((-lower * th) // fh)
+
+
+def plan_region(bbox, frame_wh, size, context=0.5):
+    """The crop region inpaint_video(region="hole") feeds the model: ``bbox`` = (x0, y0, x1, y1) of the hole in source pixels
+    (upper ends exclusive, None: no hole), ``frame_wh`` = (W, H), ``size`` = (w, h) of the model -> (left, upper, right, lower), PIL's
+    order; (0, 0, W, H) for no hole.  The box has the model's aspect, is centred on the hole and is s * size large, s the smallest
+    scale >= 1 at which the hole keeps ``context`` times its own extent on every side ((1 + 2 context) bw <= s w, and the same
+    for the height) and REGION_GUARD model pixels (bw <= s (w - 2 g)); it is then clamped to the frame:
+      Bw = min(W, ceil(s w)), Bh = min(H, ceil(s h)), left = clamp(floor((x0 + x1 - Bw) / 2), 0, W - Bw), upper alike.
+    So the box lies inside the frame, contains the hole, is never smaller than ``size`` on an axis unless the frame is (the model
+    is never fed an upscale the frame did not force), and s == 1 -- a hole small enough -- gives a box of exactly ``size``: both
+    resizes are then the identity and the hole is inpainted at source resolution.  Exact rational arithmetic: every host plans
+    the same box.  context < 0, a size with w or h <= 2 REGION_GUARD, or a bbox outside the frame raise ValueError."""
+    W, H = (int(v) for v in frame_wh)
+    w, h = (int(v) for v in size)
+    g = REGION_GUARD
+    if W <= 0 or H <= 0:
+        raise ValueError("frame_wh must be a positive (W, H), got %r" % (frame_wh,))
+    if w <= 2 * g or h <= 2 * g:
+        raise ValueError("size %r leaves no room for the %d-pixel guard on every side of the hole" % (size, g))
+    if not context >= 0:
+        raise ValueError("context must be >= 0, got %r" % (context,))
+    if bbox is None:
+        return 0, 0, W, H
+    x0, y0, x1, y1 = _check_box(bbox, (W, H))
+    bw, bh = x1 - x0, y1 - y0
+    c = 1 + 2 * Fraction(context)
+    s = max(Fraction(1), c * bw / w, c * bh / h, Fraction(bw, w - 2 * g), Fraction(bh, h - 2 * g))
+    Bw, Bh = min(W, math.ceil(s * w)), min(H, math.ceil(s * h))
+    left = min(max((x0 + x1 - Bw) // 2, 0), W - Bw)
+    upper = min(max((y0 + y1 - Bh) // 2, 0), H - Bh)
+    return left, upper, left + Bw, upper + Bh
+
+
+def _upload(a, device=None):
+    """a contiguous device tensor of an array or tensor (as it is when it is on the device already)"""
+    if isinstance(a, torch.Tensor) and a.is_cuda:
+        return a.contiguous() if device is None else a.to(device).contiguous()
+    return torch.as_tensor(np.ascontiguousarray(a)).to(device if device is not None else torch.device("cuda"))
+
+
+def hole_region(masks_u8, frame_wh, size, context=0.5, device=None):
+    """plan_region for the hole of a whole video: masks_u8 uint8 [L,Hm,Wm] (any non-zero byte is hole; an array, or a tensor that
+    is used where it is when on the device) -> the (left, upper, right, lower) box of the (W, H) frames that
+    inpaint_video(region="hole") resizes to ``size``.  The bounding box is taken on the device (ops.hole_bbox, one pass) and
+    costs one copy of four integers to the host; masks of another size than the frames have it mapped to frame pixels, floor
+    for the lower ends and ceil for the upper ends.  No hole pixel: the whole frame."""
+    m = _upload(masks_u8, device)
+    if m.dim() != 3:
+        raise ValueError("masks must be uint8 [L,Hm,Wm], got %s" % (tuple(m.shape),))
+    x0, y0, x1, y1 = (int(v) for v in ops.hole_bbox(m).cpu().tolist())
+    if x1 <= x0 or y1 <= y0:
+        return plan_region(None, frame_wh, size, context)
+    bbox = _scale_box((x0, y0, x1, y1), (m.shape[2], m.shape[1]), tuple(int(v) for v in frame_wh))
+    return plan_region(bbox, frame_wh, size, context)
+
+
+def resize_frames(frames_u8, size, device=None, box=None):
     """PIL ``Image.resize(size)`` of every frame on the device (BICUBIC, Pillow's default for RGB): test.py:97-104,127
     (resize_frames) and core/dataset.py:115, where evaluate.py's DAVIS / YouTube-VOS frames -- the ground truth of
     metrics.calc_psnr_and_ssim -- are resized to (432, 240).  ``size`` is (width, height), PIL's and test.py's order,
     not the (h, w) of prepare_masks.  frames_u8: uint8 [L,H,W,3], a numpy array or a tensor (uploaded unless it is on the
     device already).  Returns device uint8 [L,height,width,3], bit-exact with Pillow: the width pass first, then the
-    height pass, each only if that dimension changes; with neither the frames come back as uploaded (no copy)."""
-    if isinstance(frames_u8, torch.Tensor) and frames_u8.is_cuda:
-        x = frames_u8.contiguous() if device is None else frames_u8.to(device).contiguous()
-    else:
-        x = torch.as_tensor(np.ascontiguousarray(frames_u8)).to(device if device is not None else torch.device("cuda"))
-    if x.dim() != 4 or x.shape[3] != 3:
-        raise ValueError("frames must be uint8 [L,H,W,3], got %s" % (tuple(x.shape),))
+    height pass, each only if that dimension changes; with neither the frames come back as uploaded (no copy).
+
+    ``box`` = (left, upper, right, lower), integers inside the frame (ValueError otherwise), is ``Image.resize(size, box=box)``:
+    only that region is resized.  As in Pillow's ImagingResample an axis gets a pass if its size changes or the box does not
+    cover it, the width pass runs first and only over the source rows the height pass reads (its first bound to its last bound
+    plus count; ops.resample_rows_u8), and the height pass's bounds are shifted by that first row.  An axis whose box has the
+    output's length is a crop (bicubic taps at integer offsets are 0, 1, 0, 0): it takes one-tap tables, and as the height axis no
+    pass at all -- the width pass then runs over the box's rows alone."""
+    if len(frames_u8.shape) != 4 or frames_u8.shape[3] != 3:
+        raise ValueError("frames must be uint8 [L,H,W,3], got %s" % (tuple(frames_u8.shape),))
     w, h = (int(v) for v in size)
     if w <= 0 or h <= 0:
         raise ValueError("size must be a positive (width, height), got %r" % (size,))
+    H, W = (int(v) for v in frames_u8.shape[1:3])
+    if box is not None:
+        box = _check_box(box, (W, H))                   # from the shapes alone, before any upload
+    x = _upload(frames_u8, device)
+    if box is not None:
+        left, upper, right, lower = box
+        if box != (0, 0, W, H):
+            t = lambda a: torch.from_numpy(a).to(x.device)
+            need_w = not (left == 0 and right == W == w)
+            need_h = not (upper == 0 and lower == H == h)
+            by, cy = bicubic_tables(H, h, (upper, lower))
+            if need_w:
+                # the rows the height pass reads; for a crop along the height these are the box's rows and that pass is dropped
+                crop = lower - upper == h
+                first, last = (upper, lower) if crop else (int(by[0, 0]), int(by[-1, 0] + by[-1, 1]))
+                bx, cx = _axis_tables(W, w, (left, right))
+                x = ops.resample_rows_u8(x, w, first, last - first, t(bx), t(cx))
+                by = by - np.array([first, 0], np.int32)
+                need_h = not crop
+            if need_h:
+                x = ops.resample_u8(x, h, 1, t(by), t(cy), span=lower - upper)
+            return x
     for n_out, axis in ((w, 2), (h, 1)):
         if x.shape[axis] != n_out:
             bounds, coeffs = bicubic_tables(x.shape[axis], n_out)
@@ -198,26 +324,28 @@ def resize_frames(frames_u8, size, device=None):
     return x
 
 
-def _axis_tables(n_in, n_out):
-    """bicubic_tables, or the one-tap identity for an axis that keeps its size (Pillow runs no pass over it)"""
-    if n_in == n_out:
-        return np.stack([np.arange(n_out), np.ones(n_out)], 1).astype(np.int32), np.full((n_out, 1), 1 << 22, np.int32)
-    return bicubic_tables(n_in, n_out)
+def _axis_tables(n_in, n_out, box=None):
+    """bicubic_tables, or the one-tap identity for an axis (a box of it) that keeps its size: Pillow runs no pass over it, or one
+    whose taps are 0, 1, 0, 0"""
+    lo, hi = _axis_box(n_in, box)
+    if hi - lo == n_out:
+        return np.stack([lo + np.arange(n_out), np.ones(n_out)], 1).astype(np.int32), np.full((n_out, 1), 1 << 22, np.int32)
+    return bicubic_tables(n_in, n_out, box)
 
 
-def restore_frames(lo_u8, masks01_lo, src_u8, device=None):
+def restore_frames(lo_u8, masks01_lo, src_u8, device=None, box=None):
     """The finished frames back at the size of the caller's video: every frame of ``lo_u8`` (uint8 [L,h,w,3], what
     inpaint_video(size=...) returns) is upscaled like PIL ``Image.resize((W, H))`` (BICUBIC) and pasted into ``src_u8`` (uint8
     [L,H,W,3]) where the mask the model saw -- ``masks01_lo`` uint8 [L,h,w] of 0 / 1, prepare_masks's output -- is set after PIL's
     ``resize((W, H), Image.NEAREST)``; every other byte of the result is the byte of src_u8.  One fused launch (ops.restore_u8:
     tiles without a hole pixel are plain copies), bit-exact with the three PIL / numpy lines it replaces; with (H, W) == (h, w)
     it is where(mask, lo, src).  Arrays and tensors alike, uploaded unless on the device already.  Returns device uint8
-    [L,H,W,3]."""
-    def up(a):
-        if isinstance(a, torch.Tensor) and a.is_cuda:
-            return a.contiguous() if device is None else a.to(device).contiguous()
-        return torch.as_tensor(np.ascontiguousarray(a)).to(device if device is not None else torch.device("cuda"))
+    [L,H,W,3].
 
+    ``box`` = (left, upper, right, lower) inside the frame (ValueError otherwise) -- the region inpaint_video(region=...) cut out:
+    the result is src everywhere outside the box and, inside it, the same three PIL lines applied to the sub-image
+    src[upper:lower, left:right] with the box's size (right - left, lower - upper) for (W, H).  None is the whole frame."""
+    up = lambda a: _upload(a, device)
     for name, a, nd in (("lo", lo_u8, 4), ("masks", masks01_lo, 3), ("src", src_u8, 4)):
         shape = tuple(a.shape)
         if len(shape) != nd or (nd == 4 and shape[3] != 3):
@@ -227,25 +355,38 @@ def restore_frames(lo_u8, masks01_lo, src_u8, device=None):
                          % (lo_u8.shape[0], masks01_lo.shape[0], src_u8.shape[0]))
     if tuple(masks01_lo.shape[1:]) != tuple(lo_u8.shape[1:3]):
         raise ValueError("masks %s do not have the size of lo %s" % (tuple(masks01_lo.shape), tuple(lo_u8.shape)))
+    if box is not None:
+        box = _check_box(box, (src_u8.shape[2], src_u8.shape[1]))
+        if box == (0, 0, src_u8.shape[2], src_u8.shape[1]):
+            box = None
     lo, m, src = up(lo_u8), up(masks01_lo), up(src_u8)
     (h, w), (H, W) = lo.shape[1:3], src.shape[1:3]
+    if box is not None:
+        W, H = box[2] - box[0], box[3] - box[1]
     dev = src.device
     tabs = [nearest_table(h, H), nearest_table(w, W)] + list(_axis_tables(w, W)) + list(_axis_tables(h, H))
-    return ops.restore_u8(lo, m, src, *[torch.from_numpy(t).to(dev) for t in tabs])
+    return ops.restore_u8(lo, m, src, *[torch.from_numpy(t).to(dev) for t in tabs], box=box)
 
 
-def prepare_masks(masks_u8, size_hw, device, dilate=True):
-    """uint8 masks [L,Hin,Win] (any size, any non-zero = hole) -> device uint8 [L,H,W] of 0/1 like test.py:56-69."""
-    m = torch.as_tensor(np.ascontiguousarray(masks_u8)).to(device)
+def prepare_masks(masks_u8, size_hw, device, dilate=True, box=None):
+    """uint8 masks [L,Hin,Win] (any size, any non-zero = hole; an array, or a tensor that is used where it is when on the device)
+    -> device uint8 [L,H,W] of 0/1 like test.py:56-69.  ``box`` = (left, upper, right, lower) in mask pixels: only that region is
+    resized, ``resize((W, H), Image.NEAREST, box=box)``, and the dilation is clipped to the crop, as cv2.dilate of that result is."""
+    bx = by = None
+    if box is not None:
+        left, upper, right, lower = _check_box(box, (masks_u8.shape[2], masks_u8.shape[1]))
+        bx, by = (left, right), (upper, lower)
+    m = _upload(masks_u8, device)
     H, W = size_hw
-    ytab = torch.from_numpy(nearest_table(m.shape[1], H)).to(device)
-    xtab = torch.from_numpy(nearest_table(m.shape[2], W)).to(device)
+    ytab = torch.from_numpy(nearest_table(m.shape[1], H, by)).to(device)
+    xtab = torch.from_numpy(nearest_table(m.shape[2], W, bx)).to(device)
     return ops.mask_prepare(m, ytab, xtab, H, W, 4 if dilate else 0)
 
 
 @torch.no_grad()
 def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, num_ref=-1, dilate=True,
-                  device=None, pad=True, batch_windows=1, keep_float=False, in_flight=1, size=None, reuse=False, restore=False):
+                  device=None, pad=True, batch_windows=1, keep_float=False, in_flight=1, size=None, reuse=False, restore=False,
+                  region=None, context=0.5):
     """frames_u8: uint8 [L,H,W,3]; masks_u8: [L,Hm,Wm] (non-zero = hole; resized to the frames with NEAREST like
     read_mask).  Returns uint8 [L,H,W,3] composited frames, computed like test.py:129-179.
     ``model(masked[b,t,3,H',W'], n_local) -> (pred[b*t,3,H',W'], _)`` on the device.
@@ -280,7 +421,29 @@ def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, 
     saw (after the dilation) scaled up with NEAREST; every byte outside it is the caller's (restore_frames, one fused launch
     after the window loop of whichever driver ran).  The caller's frames stay on the device beside the resized ones and are not
     modified.  restore=True without size, or with keep_float=True (the paste works on the bytes test.py would have written),
-    raises ValueError."""
+    raises ValueError.
+
+    ``region`` (with ``size``; ValueError without): the model sees only a box of the source frames, resized to ``size`` like PIL
+    ``Image.resize(size, box=box)`` -- not a crop followed by a resize: the taps at the box's edge reach the pixels around it --
+    instead of the whole frame.  "hole": the box hole_region plans around the masks' bounding box over all frames, with
+    ``context`` times the hole's extent around it (plan_region; a hole small enough gets a box of exactly ``size`` and is
+    inpainted at source resolution); a video without a hole pixel, or a planned box that is the whole frame, takes the path and
+    returns the bytes of region=None.  (left, upper, right, lower): that box, in source-frame pixels, non-empty and inside the
+    frame (ValueError otherwise); hole pixels outside an explicit box are not inpainted -- they stay as they were in the source.
+    The masks are resized with the same box (mapped to mask pixels when their size differs: floor for the lower ends, ceil for
+    the upper ends) and uploaded once for both uses; everything between the resize and the paste is unchanged.  With
+    restore=True the result has the source's size: the box is pasted back (restore_frames(box=)) and every byte outside it is
+    the caller's.  Without restore the result is the region at ``size``; hole_region tells which box that was."""
+    box = None
+    if region is not None:
+        if size is None:
+            raise ValueError("region= names the part of the frames that size= resizes for the model: without size there is no "
+                             "region to cut")
+        if isinstance(region, str):
+            if region != "hole":
+                raise ValueError('region must be None, "hole" or (left, upper, right, lower), got %r' % (region,))
+        else:
+            box = _check_box(region, (frames_u8.shape[2], frames_u8.shape[1]))
     if restore:
         if size is None:
             raise ValueError("restore=True pastes the result back into frames that size= resized: without size there is nothing "
@@ -305,10 +468,20 @@ def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, 
     else:
         frames_d = torch.as_tensor(np.ascontiguousarray(frames_u8)).to(device)
     source = frames_d                                   # restore=True: kept beside the resized frames, only read
+    masks_d = _upload(masks_u8, device)                 # once: the bounding box and the mask preparation read the same tensor
+    mask_box = None
+    if region is not None:
+        frame_wh = (source.shape[2], source.shape[1])
+        if box is None:
+            box = hole_region(masks_d, frame_wh, size, context)
+        if box == (0, 0) + frame_wh:
+            box = None                                  # the whole frame: the path (and the bytes) of region=None
+        else:
+            mask_box = _scale_box(box, frame_wh, (masks_d.shape[2], masks_d.shape[1]))
     if size is not None:
-        frames_d = resize_frames(frames_d, size)        # on the caller's stream, before any stream below waits on it
+        frames_d = resize_frames(frames_d, size, box=box)   # on the caller's stream, before any stream below waits on it
     L, h, w, _ = frames_d.shape
-    masks01 = prepare_masks(masks_u8, (h, w), device, dilate)
+    masks01 = prepare_masks(masks_d, (h, w), device, dilate, box=mask_box)
     Hp, Wp = padded_size(h, w) if pad else (h, w)
     windows = plan_windows(L, neighbor_stride, ref_length, num_ref)
     # every host->device upload happens here, before the first forward: frame ids of each window and the
@@ -425,5 +598,5 @@ def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, 
     if keep_float:
         return comp
     if restore:
-        return restore_frames(ops.float_to_u8(comp), masks01, source).cpu().numpy()
+        return restore_frames(ops.float_to_u8(comp), masks01, source, box=box).cpu().numpy()
     return ops.float_to_u8(comp).cpu().numpy()

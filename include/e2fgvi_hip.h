@@ -55,6 +55,19 @@ int e2fgvi_composite(const float* pred, const int32_t* ids, const uint8_t* first
  * Pillow runs the W pass first and each pass only if that dimension changes. */
 int e2fgvi_resample_u8(const uint8_t* src, uint8_t* dst, int32_t L, int32_t H, int32_t W, int32_t n_out, int32_t axis,
                        const int32_t* bounds, const int32_t* coeffs, int32_t ksize, void* stream);
+/* The width pass of e2fgvi_resample_u8 (axis 2) over a row window: rows [row0, row0 + rows) of every frame of src [L,H,W,3] ->
+ * dst [L,rows,n_out,3] (frames H rows apart in src, `rows` apart in dst).  Pillow's ImagingResample runs the width pass of
+ * Image.resize(size, box=...) only over the source rows its height pass reads; the height pass then takes bounds relative to
+ * row0.  bounds hold absolute source columns (a box's taps reach past the box, not past the frame) and are clipped to [0, W) in
+ * the kernel; ksize >= 1 is the tables' own.  0 <= row0, row0 + rows <= H (E2FGVI_EINVAL). */
+int e2fgvi_resample_rows_u8(const uint8_t* src, uint8_t* dst, int32_t L, int32_t H, int32_t W, int32_t n_out, int32_t row0,
+                            int32_t rows, const int32_t* bounds, const int32_t* coeffs, int32_t ksize, void* stream);
+/* Bounding box of the hole of a whole video, for a driver that feeds the model only a region around it
+ * (video.inpaint_video(region="hole")): masks uint8 [L,Hm,Wm] as test.py:56-69 reads them (any non-zero byte is hole) ->
+ * box int32 [4] on the device = (x0, y0, x1, y1), upper ends exclusive; x1 <= x0 when no byte is set (the box is then
+ * (0x7f7f7f7f, 0x7f7f7f7f, 0, 0)).  One pass over the masks, 16-byte loads between a byte head and tail per row; box is
+ * initialised on `stream` in front of the launch.  L * Hm * Wm == 0 launches nothing and leaves the empty box. */
+int e2fgvi_hole_bbox(const uint8_t* masks, int32_t L, int32_t Hm, int32_t Wm, int32_t* box, void* stream);
 /* The paste-back that follows test.py:168-179 when test.py:97-104,127 resized the frames on the way in (the reference stops at
  * the resized video; a front end writes the result at source size): for every frame
  *   out = where(Image.fromarray(mask_lo * 255).resize((W, H), NEAREST) != 0, Image.fromarray(lo).resize((W, H)), src)
@@ -68,6 +81,15 @@ int e2fgvi_restore_u8(const uint8_t* lo, const uint8_t* mask_lo, const uint8_t* 
                       int32_t H, int32_t W, const int32_t* ytab, const int32_t* xtab, const int32_t* bounds_x,
                       const int32_t* coeffs_x, int32_t ksize_x, const int32_t* bounds_y, const int32_t* coeffs_y, int32_t ksize_y,
                       void* stream);
+/* e2fgvi_restore_u8 confined to a box of the frame -- left <= x < left + Bw, upper <= y < upper + Bh, inside W x H
+ * (E2FGVI_EINVAL otherwise): out = src outside the box and, on the sub-image src[upper:upper+Bh, left:left+Bw], the three lines
+ * above with (Bw, Bh) for (W, H).  The tables index box-relative pixels: ytab[Bh], xtab[Bw], bounds_x[Bw][2], coeffs_x[Bw][ksize_x],
+ * bounds_y[Bh][2], coeffs_y[Bh][ksize_y].  The same kernel (e2fgvi_restore_u8 is the box (0, 0, W, H)): tiles of `out` that lie
+ * outside the box are copied like tiles without a hole pixel. */
+int e2fgvi_restore_box_u8(const uint8_t* lo, const uint8_t* mask_lo, const uint8_t* src, uint8_t* out, int32_t L, int32_t h,
+                          int32_t w, int32_t H, int32_t W, int32_t left, int32_t upper, int32_t Bw, int32_t Bh, const int32_t* ytab,
+                          const int32_t* xtab, const int32_t* bounds_x, const int32_t* coeffs_x, int32_t ksize_x,
+                          const int32_t* bounds_y, const int32_t* coeffs_y, int32_t ksize_y, void* stream);
 /* ndarray.astype(uint8) of the blended frames (truncation) */
 int e2fgvi_float_to_u8(const float* src, uint8_t* dst, int64_t n, void* stream);
 /* model output [N,3,Hp,Wp] in (-1,1) -> uint8 NHWC [N,H,W,3] = uint8((pred+1)/2*255): the form the clip-sharded runner
