@@ -275,7 +275,7 @@ __global__ __launch_bounds__(64 * NW * KS) void focal_attn_kernel(const float* _
     if (wave_active) {
         float l = l_run + __shfl_xor(l_run, 32);
         const float nmask = (float)(T * (SLOTS - nv));
-        l += nmask * __builtin_amdgcn_exp2f(-100.f * LOG2E - m_run);
+        l = add_pad_mass(l, nmask, m_run);
         const float inv = 1.f / l;
         if (q_ok) {
             float* op = out + q_row * (NH * HD) + head * HD;
@@ -534,7 +534,7 @@ __global__ __launch_bounds__(64 * NW * KS) void focal_attn_v2_kernel(const float
     if (wave_active) {
         float l = l_run + __shfl_xor(l_run, 32);
         const float nmask = (float)(T * (SLOTS - nv));
-        l += nmask * __builtin_amdgcn_exp2f(-100.f * LOG2E - m_run);
+        l = add_pad_mass(l, nmask, m_run);
         const float inv = 1.f / l;
         bool ok;
         const long long row = query_row(ok);

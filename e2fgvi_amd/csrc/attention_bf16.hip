@@ -233,7 +233,7 @@ __global__ __launch_bounds__(64 * NW) void focal_attn_bf16_kernel(const typename
     if (wave_active) {
         float l = l_run + __shfl_xor(l_run, 32);
         const float nmask = (float)(T * (SLOTS - nv));
-        l += nmask * __builtin_amdgcn_exp2f(-100.f * LOG2E - m_run);
+        l = add_pad_mass(l, nmask, m_run);
         const float inv = 1.f / l;
         if (q_ok) {
             E16* op = out + q_row * (NH * HD) + head * HD;
@@ -547,7 +547,7 @@ __global__ __launch_bounds__(64 * NW, (QB == 1 ? 3 : 2)) void focal_attn_bf16_v2
         for (int j = 0; j < QB; ++j) {
             float l = l_run[j] + __shfl_xor(l_run[j], 32);
             const float nmask = (float)(T * (SLOTS - nv));
-            l += nmask * __builtin_amdgcn_exp2f(-100.f * LOG2E - m_run[j]);
+            l = add_pad_mass(l, nmask, m_run[j]);
             const float inv = 1.f / l;
             bool ok;
             const long long row = query_row(j, ok);

@@ -371,7 +371,7 @@ __global__ __launch_bounds__(64 * NW * KS, 1) void focal_attn_x3_kernel(const fl
     if (wave_active) {
         float l = l_run + __shfl_xor(l_run, 32);
         const float nmask = (float)(T * (SLOTS - nv));
-        l += nmask * __builtin_amdgcn_exp2f(-100.f * LOG2E - m_run);
+        l = add_pad_mass(l, nmask, m_run);
         const float inv = 1.f / l;
         bool ok;
         const long long row = query_row(ok);

@@ -87,6 +87,17 @@ __device__ __forceinline__ float e2_fast_tanh(float x) {
     return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(2.8853900817779268f * x));
 }
 
+// The focal attention's zero-padded pooled slots: `nmask` keys that score exactly -100 with V = 0, so they only add
+// nmask * e^(-100 - max) to a query's softmax denominator `l` (m_run: the running maximum in log2 units).  The branch is the
+// term's edge: for logits all below about -188.7 the exponent passes 128 and exp2 returns +inf -- with pads present l = inf and
+// the output is 0, as in the reference, where the pads then hold all the mass; without pads (an interior window, nmask == 0)
+// 0 * inf would turn the whole row into NaN where the shift-invariant softmax has an ordinary result.  The exponent is left
+// unclamped on purpose: a finite l in place of inf would give denormal-sized outputs where 0 came out before.
+__device__ __forceinline__ float add_pad_mass(float l, float nmask, float m_run) {
+    if (nmask > 0.f) l += nmask * __builtin_amdgcn_exp2f(-100.f * 1.4426950408889634f - m_run);
+    return l;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Exact three-way bf16 split of fp32 values, two at a time: x = hi + mid + lo in exact arithmetic, every piece a bf16 -- what the
 // split-operand ("x3") kernels feed to v_mfma_f32_32x32x16_bf16.  H / M / L hold the pieces of x0 in their low and
