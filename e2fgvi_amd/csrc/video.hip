@@ -11,14 +11,19 @@ inline unsigned blocks_for(long long n) { return (unsigned)((n + NTH - 1) / NTH)
 // Mask preparation (test.py:56-69): NEAREST resize to the frame size, binarise (> 0), 4x dilation with the 3x3 cross.
 // The source row / column of every output row / column comes in as a table (Pillow builds the same tables in
 // ImagingScaleAffine; the host mirrors its double arithmetic, e2fgvi_amd/video.py::nearest_table).
-__global__ void mask_prepare_kernel(const unsigned char* __restrict__ src, int Hin, int Win, const int* __restrict__ ytab,
-                                    const int* __restrict__ xtab, unsigned char* __restrict__ dst, int L, int H, int W, int iters) {
+// With `ids` (a window of a video) output frame l is made from frame ids[l] of the Lsrc source frames; an id outside [0, Lsrc)
+// gives an empty mask, so the kernel stays in bounds whatever the table holds.
+__global__ void mask_prepare_kernel(const unsigned char* __restrict__ src, int Lsrc, const int* __restrict__ ids, int Hin, int Win,
+                                    const int* __restrict__ ytab, const int* __restrict__ xtab, unsigned char* __restrict__ dst, int L,
+                                    int H, int W, int iters) {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (long long)L * H * W) return;
     const int x = (int)(idx % W);
     const int y = (int)((idx / W) % H);
     const int l = (int)(idx / ((long long)W * H));
-    const unsigned char* s = src + (long long)l * Hin * Win;
+    const int ls = ids ? ids[l] : l;
+    if (ls < 0 || ls >= Lsrc) { dst[idx] = 0; return; }
+    const unsigned char* s = src + (long long)ls * Hin * Win;
     // `iters` dilations with the 3x3 cross = OR over the L1 ball of that radius, clipped to the image
     // (cv2.dilate ignores out-of-image pixels; test.py:64-68)
     int hit = 0;
@@ -88,11 +93,13 @@ __global__ void composite_kernel(const float* __restrict__ pred, const int* __re
 // also reads rows coalesced, the horizontal one reads a row's bytes at stride 3 per tap (L1 hits).  The horizontal pass takes a
 // row window: it reads rows [row0, row0 + nrows) of every frame (frames H rows apart) and writes [L,nrows,n_out,3] (frames nrows
 // rows apart) -- Pillow's ImagingResample runs its width pass only over the rows its height pass will read.  The vertical pass
-// and the whole-frame horizontal one have row0 = 0, nrows = H.
+// and the whole-frame horizontal one have row0 = 0, nrows = H.  With `ids` output frame l reads frame ids[l] of the Lsrc source
+// frames (the frames of a window, picked out of the video by the pass itself: no source-size copy of them is made); an id
+// outside [0, Lsrc) gives a frame of zeros.
 template <bool VERTICAL>
-__global__ void resample_u8_kernel(const unsigned char* __restrict__ src, unsigned char* __restrict__ dst, int L, int H, int W,
-                                   int n_out, int row0, int nrows, const int* __restrict__ bounds, const int* __restrict__ coeffs,
-                                   int ksize) {
+__global__ void resample_u8_kernel(const unsigned char* __restrict__ src, int Lsrc, const int* __restrict__ ids,
+                                   unsigned char* __restrict__ dst, int L, int H, int W, int n_out, int row0, int nrows,
+                                   const int* __restrict__ bounds, const int* __restrict__ coeffs, int ksize) {
     const int Ho = VERTICAL ? n_out : nrows;
     const int Wo = VERTICAL ? W : n_out;
     const int n_in = VERTICAL ? H : W;
@@ -100,8 +107,12 @@ __global__ void resample_u8_kernel(const unsigned char* __restrict__ src, unsign
     const long long rows = (long long)L * Ho;
     for (long long r = blockIdx.x; r < rows; r += gridDim.x) {
         const int y = (int)(r % Ho);
-        const long long l = r / Ho;
+        const long long l = ids ? (long long)ids[r / Ho] : r / Ho;
         unsigned char* d = dst + r * row;
+        if (l < 0 || l >= Lsrc) {
+            for (int xc = threadIdx.x; xc < row; xc += blockDim.x) d[xc] = 0;
+            continue;
+        }
         for (int xc = threadIdx.x; xc < row; xc += blockDim.x) {
             const int x = xc / 3;
             const int o = VERTICAL ? y : x;
@@ -132,6 +143,21 @@ __global__ void resample_u8_kernel(const unsigned char* __restrict__ src, unsign
 __global__ void float_to_u8_kernel(const float* __restrict__ src, unsigned char* __restrict__ dst, long long n) {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx < n) dst[idx] = (unsigned char)(int)src[idx];
+}
+
+// ndarray.astype(float32) of uint8 frames: the source-size accumulator of inpaint_video(region="track") starts as the source.
+// Four bytes per thread: one 32-bit load and one 16-byte store when VEC (both bases aligned), the last n % 4 bytes one by one.
+template <bool VEC>
+__global__ void u8_to_float_kernel(const unsigned char* __restrict__ src, float* __restrict__ dst, long long n) {
+    const long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (i >= n) return;
+    if (VEC && i + 4 <= n) {
+        const unsigned q = *reinterpret_cast<const unsigned*>(src + i);
+        *reinterpret_cast<float4*>(dst + i) = make_float4((float)(q & 255u), (float)((q >> 8) & 255u), (float)((q >> 16) & 255u),
+                                                          (float)(q >> 24));
+    } else {
+        for (long long k = i; k < n && k < i + 4; ++k) dst[k] = (float)src[k];
+    }
 }
 
 // model output NCHW float in (-1,1) -> NHWC uint8 (what test.py:168-171 turns a prediction into), cropped to H x W
@@ -213,6 +239,12 @@ int slab_copy(const void* cache, const void* rows, const int32_t* ids, int32_t n
 // With a box (left, upper, Bw, Bh) inside the frame the paste is confined to it: the tables index box-relative pixels (ytab / by /
 // cy have Bh entries, xtab / bx / cx have Bw), the grid stays tiled on the full frame, a pixel outside the box counts as "no hole"
 // and takes src -- so a tile wholly outside the box is a copied tile.  The whole frame is the box (0, 0, W, H).
+// BLEND (inpaint_video(region="track"): two windows of one frame have different boxes, so their results meet at source size):
+// lo / mask hold n frames of a window, frame i belongs to frame ids[i] of the Lsrc frames of src and acc (an id outside
+// [0, Lsrc) is skipped), and the pasted frame img -- the same arithmetic, to the byte -- goes into the fp32 accumulator like
+// test.py:175-179 blends windows:  acc = first[i] ? img : acc * 0.5f + img * 0.5f.  Only the pixels of the `touch` rectangle
+// (tl, tu, Tw, Th), which contains the box, are written, and the grid covers only the tiles that rectangle reaches (the tile
+// grid stays aligned to the frame: tile (tx0 + blockIdx.x, ty0 + blockIdx.y)); between the box and the rim of touch img is src.
 constexpr int RT_W = 128, RT_H = 8, RT_WB = RT_W * 3;
 constexpr int RT_ROWS = 24;                    // horizontal-pass rows kept in LDS (RT_ROWS * RT_WB bytes)
 constexpr int RT_PATCH = 8192;                 // bytes of `lo` staged in LDS
@@ -258,9 +290,14 @@ __device__ __forceinline__ int restore_hpass_global(const unsigned char* __restr
     return pillow_clip8(acc);
 }
 
-template <bool STAGED>
+struct RestoreTouch { int tl, tu, Tw, Th; };
+
+__device__ __forceinline__ float blend_half(float a, float v, bool is_first) { return is_first ? v : a * 0.5f + v * 0.5f; }
+
+template <bool STAGED, bool BLEND>
 __device__ __forceinline__ void restore_vpass(const unsigned char* __restrict__ lo_l, const unsigned char* __restrict__ src,
-                                              unsigned char* __restrict__ out, const unsigned char* s_m, const unsigned char* s_h,
+                                              unsigned char* __restrict__ out, float* __restrict__ accum, bool is_first, RestoreTouch t,
+                                              const unsigned char* s_m, const unsigned char* s_h,
                                               int r0, long long frame_off, int h, int w, int W, int x0, int y0, int nb, int th,
                                               int left, int upper, int Bh, const int* __restrict__ bx, const int* __restrict__ cx, int kx,
                                               const int* __restrict__ by, const int* __restrict__ cy, int ky) {
@@ -298,7 +335,25 @@ __device__ __forceinline__ void restore_vpass(const unsigned char* __restrict__ 
             }
             v[k] = pillow_clip8(acc);
         }
-        if (n4 == 4 && ((uintptr_t)(out + off) & 3) == 0) {
+        if constexpr (BLEND) {
+            if (y < t.tu || y - t.tu >= t.Th) continue;
+            float* a = accum + off;
+            const int xa = x0 + xc0 / 3, xb = x0 + (xc0 + n4 - 1) / 3;          // the pixels of the first and the last byte
+            if (n4 == 4 && xa >= t.tl && xb - t.tl < t.Tw && ((uintptr_t)a & 15) == 0) {
+                float4 q = *reinterpret_cast<float4*>(a);
+                q.x = blend_half(q.x, (float)v[0], is_first);
+                q.y = blend_half(q.y, (float)v[1], is_first);
+                q.z = blend_half(q.z, (float)v[2], is_first);
+                q.w = blend_half(q.w, (float)v[3], is_first);
+                *reinterpret_cast<float4*>(a) = q;
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int x = x0 + (xc0 + k) / 3;
+                    if (k < n4 && x >= t.tl && x - t.tl < t.Tw) a[k] = blend_half(a[k], (float)v[k], is_first);
+                }
+            }
+        } else if (n4 == 4 && ((uintptr_t)(out + off) & 3) == 0) {
             *reinterpret_cast<unsigned*>(out + off) = (unsigned)v[0] | ((unsigned)v[1] << 8) | ((unsigned)v[2] << 16) | ((unsigned)v[3] << 24);
         } else {
 #pragma unroll
@@ -308,9 +363,11 @@ __device__ __forceinline__ void restore_vpass(const unsigned char* __restrict__ 
     }
 }
 
+template <bool BLEND>
 __global__ __launch_bounds__(NTH) void restore_u8_kernel(
     const unsigned char* __restrict__ lo, const unsigned char* __restrict__ mask, const unsigned char* __restrict__ src,
-    unsigned char* __restrict__ out, int L, int h, int w, int H, int W, int left, int upper, int Bw, int Bh,
+    unsigned char* __restrict__ out, float* __restrict__ accum, const int* __restrict__ ids, const unsigned char* __restrict__ first,
+    int Lsrc, int tx0, int ty0, RestoreTouch touch, int L, int h, int w, int H, int W, int left, int upper, int Bw, int Bh,
     const int* __restrict__ ytab, const int* __restrict__ xtab, const int* __restrict__ bx, const int* __restrict__ cx, int kx,
     const int* __restrict__ by, const int* __restrict__ cy, int ky) {
     __shared__ unsigned char s_m[RT_H * RT_W];
@@ -318,10 +375,14 @@ __global__ __launch_bounds__(NTH) void restore_u8_kernel(
     __shared__ __align__(16) unsigned char s_h[RT_ROWS * RT_WB];
     __shared__ int s_rng[4];
     const int tid = threadIdx.x;
-    const int x0 = blockIdx.x * RT_W, y0 = blockIdx.y * RT_H;
+    const int x0 = (tx0 + (int)blockIdx.x) * RT_W, y0 = (ty0 + (int)blockIdx.y) * RT_H;
     const int tw = W - x0 < RT_W ? W - x0 : RT_W, th = H - y0 < RT_H ? H - y0 : RT_H;
     const int nb = tw * 3;
+    if (tw <= 0 || th <= 0) return;
     for (int l = blockIdx.z; l < L; l += gridDim.z) {
+        const int fr = BLEND ? ids[l] : l;               // the frame of src / out / accum; block-uniform
+        if (BLEND && (fr < 0 || fr >= Lsrc)) continue;
+        const bool is_first = BLEND ? first[l] != 0 : true;
         // the tile's mask bits through the two NEAREST tables; any hole pixel?
         const unsigned char* ml = mask + (long long)l * h * w;
         int any = 0;
@@ -339,10 +400,20 @@ __global__ __launch_bounds__(NTH) void restore_u8_kernel(
             any |= m;
         }
         any = __syncthreads_or(any);
-        const long long frame_off = (long long)l * H * W * 3;
+        const long long frame_off = (long long)fr * H * W * 3;
         if (!any) {
             const int ty = tid >> 5, lane = tid & 31;
-            if (ty < th) {
+            if (BLEND) {
+                // img is src: 32 lanes along a row's bytes, consecutive floats of acc
+                const int y = y0 + ty;
+                if (ty < th && y >= touch.tu && y - touch.tu < touch.Th) {
+                    const long long off = frame_off + ((long long)y * W + x0) * 3;
+                    for (int k = lane; k < nb; k += 32) {
+                        const int x = x0 + k / 3;
+                        if (x >= touch.tl && x - touch.tl < touch.Tw) accum[off + k] = blend_half(accum[off + k], (float)src[off + k], is_first);
+                    }
+                }
+            } else if (ty < th) {
                 const long long off = frame_off + ((long long)(y0 + ty) * W + x0) * 3;
                 const unsigned char* s = src + off;
                 unsigned char* d = out + off;
@@ -393,9 +464,9 @@ __global__ __launch_bounds__(NTH) void restore_u8_kernel(
                 s_h[r * RT_WB + xc] = pillow_clip8(acc);
             }
             __syncthreads();
-            restore_vpass<true>(lo_l, src, out, s_m, s_h, r0, frame_off, h, w, W, x0, y0, nb, th, left, upper, Bh, bx, cx, kx, by, cy, ky);
+            restore_vpass<true, BLEND>(lo_l, src, out, accum, is_first, touch, s_m, s_h, r0, frame_off, h, w, W, x0, y0, nb, th, left, upper, Bh, bx, cx, kx, by, cy, ky);
         } else {
-            restore_vpass<false>(lo_l, src, out, s_m, s_h, r0, frame_off, h, w, W, x0, y0, nb, th, left, upper, Bh, bx, cx, kx, by, cy, ky);
+            restore_vpass<false, BLEND>(lo_l, src, out, accum, is_first, touch, s_m, s_h, r0, frame_off, h, w, W, x0, y0, nb, th, left, upper, Bh, bx, cx, kx, by, cy, ky);
         }
         __syncthreads();                                // s_m, s_h are rewritten for the next frame
     }
@@ -407,7 +478,14 @@ __global__ __launch_bounds__(NTH) void restore_u8_kernel(
 // to the row's first 16-byte boundary and a byte tail (any pitch, any base), first / last non-zero byte of a word by ffs / clz;
 // the lanes' boxes are reduced within the wave (wave64 shuffles), the waves' within the block through LDS, and a block that saw
 // a hole pixel issues the four global atomicMin / atomicMax -- a block that saw none issues nothing.
+// blockIdx.y picks one of several boxes, each over its own `rows` consecutive mask rows: one box over the L * Hm rows of the video
+// (hole_bbox), or a box per frame over its Hm rows (hole_bbox_frames, the per-window regions of video.plan_track).
 constexpr int BB_WAVES = NTH / 64;
+
+__global__ void bbox_init_kernel(int* __restrict__ box, long long n) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx < n) box[idx] = (idx & 3) < 2 ? 0x7f7f7f7f : 0;
+}
 
 __device__ __forceinline__ void bbox_word(unsigned v, int x, int& lo, int& hi) {
     if (v) {
@@ -420,6 +498,8 @@ __device__ __forceinline__ void bbox_word(unsigned v, int x, int& lo, int& hi) {
 __global__ __launch_bounds__(NTH) void hole_bbox_kernel(const unsigned char* __restrict__ m, long long rows, int Hm, int Wm,
                                                         int* __restrict__ box) {
     __shared__ int s_box[BB_WAVES][4];
+    m += (long long)blockIdx.y * rows * Wm;
+    box += 4 * (long long)blockIdx.y;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int x0 = 0x7fffffff, y0 = 0x7fffffff, x1 = 0, y1 = 0;
     const long long step = (long long)gridDim.x * BB_WAVES;
@@ -500,9 +580,47 @@ extern "C" int e2fgvi_restore_box_u8(const uint8_t* lo, const uint8_t* mask_lo, 
                    !ranges_overlap(out, n_out, mask_lo, n_lo / 3),
                E2FGVI_EINVAL, "restore_u8: out must not overlap src, lo or mask_lo");
     const dim3 grid((unsigned)((W + RT_W - 1) / RT_W), (unsigned)((H + RT_H - 1) / RT_H), (unsigned)(L < 1024 ? L : 1024));
-    hipLaunchKernelGGL(restore_u8_kernel, grid, dim3(NTH), 0, (hipStream_t)stream, lo, mask_lo, src, out, L, h, w, H, W, left, upper, Bw,
-                       Bh, ytab, xtab, bounds_x, coeffs_x, ksize_x, bounds_y, coeffs_y, ksize_y);
+    const RestoreTouch touch{0, 0, W, H};
+    hipLaunchKernelGGL(restore_u8_kernel<false>, grid, dim3(NTH), 0, (hipStream_t)stream, lo, mask_lo, src, out, (float*)nullptr,
+                       (const int*)nullptr, (const unsigned char*)nullptr, L, 0, 0, touch, L, h, w, H, W, left, upper,
+                       Bw, Bh, ytab, xtab, bounds_x, coeffs_x, ksize_x, bounds_y, coeffs_y, ksize_y);
     E2_LAUNCH_CHECK("restore_u8");
+    return 0;
+}
+
+extern "C" int e2fgvi_restore_blend(const uint8_t* lo, const uint8_t* mask_lo, const uint8_t* src, const int32_t* ids,
+                                    const uint8_t* first, float* acc, int32_t n, int32_t L, int32_t h, int32_t w, int32_t H, int32_t W,
+                                    int32_t left, int32_t upper, int32_t Bw, int32_t Bh, int32_t touch_left, int32_t touch_upper,
+                                    int32_t Tw, int32_t Th, const int32_t* ytab, const int32_t* xtab, const int32_t* bounds_x,
+                                    const int32_t* coeffs_x, int32_t ksize_x, const int32_t* bounds_y, const int32_t* coeffs_y,
+                                    int32_t ksize_y, void* stream) {
+    E2_REQUIRE(lo && mask_lo && src && ids && first && acc && ytab && xtab && bounds_x && coeffs_x && bounds_y && coeffs_y, E2FGVI_EINVAL,
+               "restore_blend: null pointer");
+    E2_REQUIRE(n > 0 && L > 0 && h > 0 && w > 0 && H > 0 && W > 0 && ksize_x >= 1 && ksize_y >= 1, E2FGVI_EINVAL,
+               "restore_blend: sizes and tap counts must be positive");
+    E2_REQUIRE(left >= 0 && upper >= 0 && Bw > 0 && Bh > 0 && Bw <= W - left && Bh <= H - upper, E2FGVI_EINVAL,
+               "restore_blend: the box (%d, %d) + %d x %d must be non-empty and lie inside the %d x %d frame", left, upper, Bw, Bh, W, H);
+    E2_REQUIRE(touch_left >= 0 && touch_upper >= 0 && Tw > 0 && Th > 0 && Tw <= W - touch_left && Th <= H - touch_upper &&
+                   touch_left <= left && touch_upper <= upper && Bw <= Tw - (left - touch_left) && Bh <= Th - (upper - touch_upper),
+               E2FGVI_EINVAL, "restore_blend: the touched rectangle (%d, %d) + %d x %d must lie inside the frame and contain the box",
+               touch_left, touch_upper, Tw, Th);
+    E2_REQUIRE(W * 3LL <= 0x7fffffffLL && w * 3LL <= 0x7fffffffLL && (H + RT_H - 1) / RT_H <= 65535, E2FGVI_EINVAL,
+               "restore_blend: frames too large");
+    E2_REQUIRE((uintptr_t)acc % sizeof(float) == 0, E2FGVI_EINVAL, "restore_blend: acc must be aligned to 4 bytes");
+    const long long n_src = (long long)L * H * W * 3, n_lo = (long long)n * h * w * 3;
+    E2_REQUIRE(!ranges_overlap(acc, n_src * 4, src, n_src) && !ranges_overlap(acc, n_src * 4, lo, n_lo) &&
+                   !ranges_overlap(acc, n_src * 4, mask_lo, n_lo / 3) && !ranges_overlap(acc, n_src * 4, ids, n * 4LL) &&
+                   !ranges_overlap(acc, n_src * 4, first, n),
+               E2FGVI_EINVAL, "restore_blend: acc must not overlap src, lo, mask_lo, ids or first");
+    // the tiles of the frame-aligned tile grid that the touched rectangle reaches
+    const int tx0 = touch_left / RT_W, ty0 = touch_upper / RT_H;
+    const int tx1 = (touch_left + Tw - 1) / RT_W, ty1 = (touch_upper + Th - 1) / RT_H;
+    const dim3 grid((unsigned)(tx1 - tx0 + 1), (unsigned)(ty1 - ty0 + 1), (unsigned)(n < 1024 ? n : 1024));
+    const RestoreTouch touch{touch_left, touch_upper, Tw, Th};
+    hipLaunchKernelGGL(restore_u8_kernel<true>, grid, dim3(NTH), 0, (hipStream_t)stream, lo, mask_lo, src, (unsigned char*)nullptr, acc,
+                       ids, first, L, tx0, ty0, touch, n, h, w, H, W, left, upper, Bw, Bh, ytab,
+                       xtab, bounds_x, coeffs_x, ksize_x, bounds_y, coeffs_y, ksize_y);
+    E2_LAUNCH_CHECK("restore_blend");
     return 0;
 }
 
@@ -533,6 +651,26 @@ extern "C" int e2fgvi_hole_bbox(const uint8_t* masks, int32_t L, int32_t Hm, int
     return 0;
 }
 
+extern "C" int e2fgvi_hole_bbox_frames(const uint8_t* masks, int32_t L, int32_t Hm, int32_t Wm, int32_t* boxes, void* stream) {
+    E2_REQUIRE(L >= 0 && Hm >= 0 && Wm >= 0, E2FGVI_EINVAL, "hole_bbox_frames: bad arguments");
+    if (L == 0) return 0;
+    E2_REQUIRE(boxes, E2FGVI_EINVAL, "hole_bbox_frames: null boxes");
+    E2_REQUIRE(masks || (long long)Hm * Wm == 0, E2FGVI_EINVAL, "hole_bbox_frames: null masks");
+    // every frame's box starts empty, (0x7f7f7f7f, 0x7f7f7f7f, 0, 0), on the stream of the launch that lowers / raises it
+    hipLaunchKernelGGL(bbox_init_kernel, dim3(blocks_for(4LL * L)), dim3(NTH), 0, (hipStream_t)stream, boxes, 4LL * L);
+    E2_LAUNCH_CHECK("hole_bbox_frames");
+    if ((long long)Hm * Wm == 0) return 0;
+    // a wave per row of a frame, a grid row per frame (65535 frames per launch)
+    const int bx = (Hm + BB_WAVES - 1) / BB_WAVES < 2048 ? (Hm + BB_WAVES - 1) / BB_WAVES : 2048;
+    for (int l0 = 0; l0 < L; l0 += 65535) {
+        const int nl = L - l0 < 65535 ? L - l0 : 65535;
+        hipLaunchKernelGGL(hole_bbox_kernel, dim3((unsigned)bx, (unsigned)nl), dim3(NTH), 0, (hipStream_t)stream,
+                           masks + (long long)l0 * Hm * Wm, (long long)Hm, Hm, Wm, boxes + 4LL * l0);
+        E2_LAUNCH_CHECK("hole_bbox_frames");
+    }
+    return 0;
+}
+
 extern "C" int e2fgvi_gather_slabs(const void* cache, int32_t slots, const int32_t* ids, int32_t n, int64_t slab_bytes, void* window,
                                    void* stream) {
     const int rc = slab_copy<false>(cache, window, ids, n, slots, slab_bytes, stream, "gather_slabs");
@@ -553,9 +691,21 @@ extern "C" int e2fgvi_mask_prepare(const uint8_t* masks, int32_t L, int32_t Hin,
                                    const int32_t* xtab, uint8_t* out, int32_t H, int32_t W, int32_t iterations, void* stream) {
     E2_REQUIRE(masks && ytab && xtab && out && L > 0 && Hin > 0 && Win > 0 && H > 0 && W > 0 && iterations >= 0 && iterations <= 64,
                E2FGVI_EINVAL, "mask_prepare: bad arguments");
-    hipLaunchKernelGGL(mask_prepare_kernel, dim3(blocks_for((long long)L * H * W)), dim3(NTH), 0, (hipStream_t)stream, masks, Hin,
-                       Win, ytab, xtab, out, L, H, W, iterations);
+    hipLaunchKernelGGL(mask_prepare_kernel, dim3(blocks_for((long long)L * H * W)), dim3(NTH), 0, (hipStream_t)stream, masks, L,
+                       (const int*)nullptr, Hin, Win, ytab, xtab, out, L, H, W, iterations);
     E2_LAUNCH_CHECK("mask_prepare");
+    return 0;
+}
+
+extern "C" int e2fgvi_mask_prepare_ids(const uint8_t* masks, int32_t L, const int32_t* ids, int32_t n, int32_t Hin, int32_t Win,
+                                       const int32_t* ytab, const int32_t* xtab, uint8_t* out, int32_t H, int32_t W, int32_t iterations,
+                                       void* stream) {
+    E2_REQUIRE(masks && ids && ytab && xtab && out && L > 0 && n > 0 && Hin > 0 && Win > 0 && H > 0 && W > 0 && iterations >= 0 &&
+                   iterations <= 64,
+               E2FGVI_EINVAL, "mask_prepare_ids: bad arguments");
+    hipLaunchKernelGGL(mask_prepare_kernel, dim3(blocks_for((long long)n * H * W)), dim3(NTH), 0, (hipStream_t)stream, masks, L, ids,
+                       Hin, Win, ytab, xtab, out, n, H, W, iterations);
+    E2_LAUNCH_CHECK("mask_prepare_ids");
     return 0;
 }
 
@@ -579,44 +729,83 @@ extern "C" int e2fgvi_composite(const float* pred, const int32_t* ids, const uin
     return 0;
 }
 
-extern "C" int e2fgvi_resample_rows_u8(const uint8_t* src, uint8_t* dst, int32_t L, int32_t H, int32_t W, int32_t n_out, int32_t row0,
-                                       int32_t rows, const int32_t* bounds, const int32_t* coeffs, int32_t ksize, void* stream) {
-    E2_REQUIRE(src && dst && bounds && coeffs && L > 0 && H > 0 && W > 0 && n_out > 0 && ksize > 0, E2FGVI_EINVAL,
-               "resample_rows_u8: bad arguments");
-    E2_REQUIRE(row0 >= 0 && rows > 0 && rows <= H - row0, E2FGVI_EINVAL, "resample_rows_u8: rows [%d, %d + %d) leave the %d rows of a frame",
+// the two resample entries and their variants with a frame table: Lsrc frames in src, output frame l from frame ids[l] (no
+// table: Lsrc == L, frame l)
+static int resample_rows(const char* what, const uint8_t* src, int32_t Lsrc, const int32_t* ids, uint8_t* dst, int32_t L, int32_t H,
+                         int32_t W, int32_t n_out, int32_t row0, int32_t rows, const int32_t* bounds, const int32_t* coeffs,
+                         int32_t ksize, void* stream) {
+    E2_REQUIRE(src && dst && bounds && coeffs && L > 0 && Lsrc > 0 && H > 0 && W > 0 && n_out > 0 && ksize > 0, E2FGVI_EINVAL,
+               "%s: bad arguments", what);
+    E2_REQUIRE(row0 >= 0 && rows > 0 && rows <= H - row0, E2FGVI_EINVAL, "%s: rows [%d, %d + %d) leave the %d rows of a frame", what,
                row0, row0, rows, H);
-    E2_REQUIRE(W * 3LL <= 0x7fffffffLL && n_out * 3LL <= 0x7fffffffLL, E2FGVI_EINVAL, "resample_rows_u8: rows too wide");
+    E2_REQUIRE(W * 3LL <= 0x7fffffffLL && n_out * 3LL <= 0x7fffffffLL, E2FGVI_EINVAL, "%s: rows too wide", what);
     const long long total = (long long)L * rows;
     const unsigned grid = (unsigned)(total < (1LL << 20) ? total : (1LL << 20));     // the kernel strides over the rest
-    hipLaunchKernelGGL(resample_u8_kernel<false>, dim3(grid), dim3(NTH), 0, (hipStream_t)stream, src, dst, L, H, W, n_out, row0, rows,
-                       bounds, coeffs, ksize);
-    E2_LAUNCH_CHECK("resample_rows_u8");
+    hipLaunchKernelGGL(resample_u8_kernel<false>, dim3(grid), dim3(NTH), 0, (hipStream_t)stream, src, Lsrc, ids, dst, L, H, W, n_out,
+                       row0, rows, bounds, coeffs, ksize);
+    E2_LAUNCH_CHECK(what);
     return 0;
+}
+
+static int resample_axis(const char* what, const uint8_t* src, int32_t Lsrc, const int32_t* ids, uint8_t* dst, int32_t L, int32_t H,
+                         int32_t W, int32_t n_out, int32_t axis, const int32_t* bounds, const int32_t* coeffs, int32_t ksize,
+                         void* stream) {
+    E2_REQUIRE(src && dst && bounds && coeffs && L > 0 && Lsrc > 0 && H > 0 && W > 0 && n_out > 0 && ksize > 0, E2FGVI_EINVAL,
+               "%s: bad arguments", what);
+    E2_REQUIRE(axis == 1 || axis == 2, E2FGVI_EINVAL, "%s: axis must be 1 (H) or 2 (W), got %d", what, axis);
+    const long long Wo = axis == 2 ? n_out : W;
+    E2_REQUIRE(W * 3LL <= 0x7fffffffLL && Wo * 3 <= 0x7fffffffLL, E2FGVI_EINVAL, "%s: rows too wide", what);
+    const long long rows = (long long)L * (axis == 1 ? n_out : H);
+    const unsigned grid = (unsigned)(rows < (1LL << 20) ? rows : (1LL << 20));      // the kernel strides over the rest
+    if (axis == 1)
+        hipLaunchKernelGGL(resample_u8_kernel<true>, dim3(grid), dim3(NTH), 0, (hipStream_t)stream, src, Lsrc, ids, dst, L, H, W, n_out, 0,
+                           H, bounds, coeffs, ksize);
+    else
+        hipLaunchKernelGGL(resample_u8_kernel<false>, dim3(grid), dim3(NTH), 0, (hipStream_t)stream, src, Lsrc, ids, dst, L, H, W, n_out, 0,
+                           H, bounds, coeffs, ksize);
+    E2_LAUNCH_CHECK(what);
+    return 0;
+}
+
+extern "C" int e2fgvi_resample_rows_u8(const uint8_t* src, uint8_t* dst, int32_t L, int32_t H, int32_t W, int32_t n_out, int32_t row0,
+                                       int32_t rows, const int32_t* bounds, const int32_t* coeffs, int32_t ksize, void* stream) {
+    return resample_rows("resample_rows_u8", src, L, nullptr, dst, L, H, W, n_out, row0, rows, bounds, coeffs, ksize, stream);
+}
+
+extern "C" int e2fgvi_resample_rows_ids_u8(const uint8_t* src, int32_t L, const int32_t* ids, int32_t n, uint8_t* dst, int32_t H,
+                                           int32_t W, int32_t n_out, int32_t row0, int32_t rows, const int32_t* bounds,
+                                           const int32_t* coeffs, int32_t ksize, void* stream) {
+    E2_REQUIRE(ids, E2FGVI_EINVAL, "resample_rows_ids_u8: null ids");
+    return resample_rows("resample_rows_ids_u8", src, L, ids, dst, n, H, W, n_out, row0, rows, bounds, coeffs, ksize, stream);
 }
 
 extern "C" int e2fgvi_resample_u8(const uint8_t* src, uint8_t* dst, int32_t L, int32_t H, int32_t W, int32_t n_out, int32_t axis,
                                   const int32_t* bounds, const int32_t* coeffs, int32_t ksize, void* stream) {
-    E2_REQUIRE(src && dst && bounds && coeffs && L > 0 && H > 0 && W > 0 && n_out > 0 && ksize > 0, E2FGVI_EINVAL,
-               "resample_u8: bad arguments");
-    E2_REQUIRE(axis == 1 || axis == 2, E2FGVI_EINVAL, "resample_u8: axis must be 1 (H) or 2 (W), got %d", axis);
-    const long long Wo = axis == 2 ? n_out : W;
-    E2_REQUIRE(W * 3LL <= 0x7fffffffLL && Wo * 3 <= 0x7fffffffLL, E2FGVI_EINVAL, "resample_u8: rows too wide");
-    const long long rows = (long long)L * (axis == 1 ? n_out : H);
-    const unsigned grid = (unsigned)(rows < (1LL << 20) ? rows : (1LL << 20));      // the kernel strides over the rest
-    if (axis == 1)
-        hipLaunchKernelGGL(resample_u8_kernel<true>, dim3(grid), dim3(NTH), 0, (hipStream_t)stream, src, dst, L, H, W, n_out, 0, H, bounds,
-                           coeffs, ksize);
-    else
-        hipLaunchKernelGGL(resample_u8_kernel<false>, dim3(grid), dim3(NTH), 0, (hipStream_t)stream, src, dst, L, H, W, n_out, 0, H, bounds,
-                           coeffs, ksize);
-    E2_LAUNCH_CHECK("resample_u8");
-    return 0;
+    return resample_axis("resample_u8", src, L, nullptr, dst, L, H, W, n_out, axis, bounds, coeffs, ksize, stream);
+}
+
+extern "C" int e2fgvi_resample_ids_u8(const uint8_t* src, int32_t L, const int32_t* ids, int32_t n, uint8_t* dst, int32_t H, int32_t W,
+                                      int32_t n_out, int32_t axis, const int32_t* bounds, const int32_t* coeffs, int32_t ksize,
+                                      void* stream) {
+    E2_REQUIRE(ids, E2FGVI_EINVAL, "resample_ids_u8: null ids");
+    return resample_axis("resample_ids_u8", src, L, ids, dst, n, H, W, n_out, axis, bounds, coeffs, ksize, stream);
 }
 
 extern "C" int e2fgvi_float_to_u8(const float* src, uint8_t* dst, int64_t n, void* stream) {
     E2_REQUIRE(src && dst && n > 0, E2FGVI_EINVAL, "float_to_u8: bad arguments");
     hipLaunchKernelGGL(float_to_u8_kernel, dim3(blocks_for(n)), dim3(NTH), 0, (hipStream_t)stream, src, dst, (long long)n);
     E2_LAUNCH_CHECK("float_to_u8");
+    return 0;
+}
+
+extern "C" int e2fgvi_u8_to_float(const uint8_t* src, float* dst, int64_t n, void* stream) {
+    E2_REQUIRE(src && dst && n > 0, E2FGVI_EINVAL, "u8_to_float: bad arguments");
+    const unsigned grid = blocks_for((n + 3) / 4);
+    if (((uintptr_t)src & 3) == 0 && ((uintptr_t)dst & 15) == 0)
+        hipLaunchKernelGGL(u8_to_float_kernel<true>, dim3(grid), dim3(NTH), 0, (hipStream_t)stream, src, dst, (long long)n);
+    else
+        hipLaunchKernelGGL(u8_to_float_kernel<false>, dim3(grid), dim3(NTH), 0, (hipStream_t)stream, src, dst, (long long)n);
+    E2_LAUNCH_CHECK("u8_to_float");
     return 0;
 }
 

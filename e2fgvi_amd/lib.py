@@ -117,6 +117,12 @@ SYMBOLS = {
     "e2fgvi_restore_box_u8": (C.c_int, [_fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _fp, _fp, _fp, _fp, _i32,
                                         _fp, _fp, _i32, _fp]),
     "e2fgvi_hole_bbox": (C.c_int, [_fp, _i32, _i32, _i32, _fp, _fp]),
+    "e2fgvi_hole_bbox_frames": (C.c_int, [_fp, _i32, _i32, _i32, _fp, _fp]),
+    "e2fgvi_mask_prepare_ids": (C.c_int, [_fp, _i32, _fp, _i32, _i32, _i32, _fp, _fp, _fp, _i32, _i32, _i32, _fp]),
+    "e2fgvi_resample_ids_u8": (C.c_int, [_fp, _i32, _fp, _i32, _fp, _i32, _i32, _i32, _i32, _fp, _fp, _i32, _fp]),
+    "e2fgvi_resample_rows_ids_u8": (C.c_int, [_fp, _i32, _fp, _i32, _fp, _i32, _i32, _i32, _i32, _i32, _fp, _fp, _i32, _fp]),
+    "e2fgvi_restore_blend": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp] + [_i32] * 14 + [_fp, _fp, _fp, _fp, _i32, _fp, _fp, _i32, _fp]),
+    "e2fgvi_u8_to_float": (C.c_int, [_fp, _fp, _i64, _fp]),
     "e2fgvi_float_to_u8": (C.c_int, [_fp, _fp, _i64, _fp]),
     "e2fgvi_pred_to_u8": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, _fp]),
     "e2fgvi_gather_slabs": (C.c_int, [_fp, _i32, _fp, _i32, _i64, _fp, _fp]),

@@ -1548,14 +1548,29 @@ def _u8(t, name):
     return _chk(t, name, torch.uint8)
 
 
-def mask_prepare(masks_u8, ytab, xtab, H, W, iterations=4):
-    """masks_u8 [L,Hin,Win] uint8 -> [L,H,W] uint8 of 0/1 (NEAREST resize by the given tables, > 0, cross dilation)."""
+def _frame_ids(ids, device):
+    """a device int32 table [n], n > 0, of frame numbers (range-checked in the kernels, not here: no host read)"""
+    _chk(ids, "ids", torch.int32)
+    if ids.dim() != 1 or ids.numel() == 0 or ids.device != device:
+        raise ValueError("ids must be a non-empty int32 [n] on the device of the frames")
+    return ids.numel()
+
+
+def mask_prepare(masks_u8, ytab, xtab, H, W, iterations=4, ids=None):
+    """masks_u8 [L,Hin,Win] uint8 -> [L,H,W] uint8 of 0/1 (NEAREST resize by the given tables, > 0, cross dilation).
+    ``ids`` device int32 [n]: -> [n,H,W], output frame l from masks_u8[ids[l]] (an id outside [0, L): an empty mask)."""
     lib = _L.load()
     _u8(masks_u8, "masks")
     _chk(ytab, "ytab", torch.int32); _chk(xtab, "xtab", torch.int32)
     L, Hin, Win = masks_u8.shape
     if ytab.numel() != H or xtab.numel() != W:
         raise ValueError("ytab / xtab must have H / W entries")
+    if ids is not None:
+        n = _frame_ids(ids, masks_u8.device)
+        out = torch.empty((n, H, W), dtype=torch.uint8, device=masks_u8.device)
+        _L.check(lib.e2fgvi_mask_prepare_ids(_ptr(masks_u8), L, _ptr(ids), n, Hin, Win, _ptr(ytab), _ptr(xtab), _ptr(out), H, W,
+                                             iterations, _stream()), "mask_prepare_ids")
+        return out
     out = torch.empty((L, H, W), dtype=torch.uint8, device=masks_u8.device)
     _L.check(lib.e2fgvi_mask_prepare(_ptr(masks_u8), L, Hin, Win, _ptr(ytab), _ptr(xtab), _ptr(out), H, W, iterations, _stream()),
              "mask_prepare")
@@ -1592,10 +1607,11 @@ def _taps_of(span, n_out):
     return 2 * math.ceil(2.0 * max(span / n_out, 1.0)) + 1
 
 
-def resample_u8(frames_u8, n_out, axis, bounds, coeffs, span=None):
+def resample_u8(frames_u8, n_out, axis, bounds, coeffs, span=None, ids=None):
     """frames_u8 [L,H,W,3] uint8 -> uint8 with dimension `axis` (1: H, 2: W) resized to n_out: one bicubic pass of PIL's
     Image.resize with the tables of video.bicubic_tables (bounds int32 [n_out,2], coeffs int32 [n_out,ksize]).  ``span``: the
-    number of source pixels the tables were built for when that is a box of the axis (bicubic_tables(box=)), not all of it."""
+    number of source pixels the tables were built for when that is a box of the axis (bicubic_tables(box=)), not all of it.
+    ``ids`` device int32 [n]: the result has n frames, frame l the pass over frames_u8[ids[l]] (an id outside [0, L): zeros)."""
     lib = _L.load()
     _u8(frames_u8, "frames"); _chk(bounds, "bounds", torch.int32); _chk(coeffs, "coeffs", torch.int32)
     if frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
@@ -1613,17 +1629,23 @@ def resample_u8(frames_u8, n_out, axis, bounds, coeffs, span=None):
         raise ValueError("span must be in (0, %d], got %r" % (n_in, span))
     if ksize != _taps_of(n_in if span is None else span, n_out):
         raise ValueError("coeffs of %d taps do not belong to a %d -> %d resize" % (ksize, n_in if span is None else span, n_out))
-    shape = (L, n_out, W, 3) if axis == 1 else (L, H, n_out, 3)
+    n = L if ids is None else _frame_ids(ids, frames_u8.device)
+    shape = (n, n_out, W, 3) if axis == 1 else (n, H, n_out, 3)
     out = torch.empty(shape, dtype=torch.uint8, device=frames_u8.device)
+    if ids is not None:
+        _L.check(lib.e2fgvi_resample_ids_u8(_ptr(frames_u8), L, _ptr(ids), n, _ptr(out), H, W, n_out, axis, _ptr(bounds), _ptr(coeffs),
+                                            ksize, _stream()), "resample_ids_u8")
+        return out
     _L.check(lib.e2fgvi_resample_u8(_ptr(frames_u8), _ptr(out), L, H, W, n_out, axis, _ptr(bounds), _ptr(coeffs), ksize, _stream()),
              "resample_u8")
     return out
 
 
-def resample_rows_u8(frames_u8, n_out, row0, rows, bounds, coeffs):
+def resample_rows_u8(frames_u8, n_out, row0, rows, bounds, coeffs, ids=None):
     """The width pass of resample_u8 over rows [row0, row0 + rows) of every frame: frames_u8 [L,H,W,3] uint8 -> [L,rows,n_out,3].
     bounds int32 [n_out,2] hold absolute source columns (video.bicubic_tables(W, n_out, box=(left, right)), or one-tap tables of
-    a crop), coeffs int32 [n_out,ksize], ksize >= 1 the tables' own; entries are clipped to the frame in the kernel."""
+    a crop), coeffs int32 [n_out,ksize], ksize >= 1 the tables' own; entries are clipped to the frame in the kernel.
+    ``ids`` device int32 [n]: -> [n,rows,n_out,3], frame l the pass over frames_u8[ids[l]] (an id outside [0, L): zeros)."""
     lib = _L.load()
     _u8(frames_u8, "frames"); _chk(bounds, "bounds", torch.int32); _chk(coeffs, "coeffs", torch.int32)
     if frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
@@ -1636,7 +1658,12 @@ def resample_rows_u8(frames_u8, n_out, row0, rows, bounds, coeffs):
     row0, rows = int(row0), int(rows)
     if row0 < 0 or rows < 1 or row0 + rows > H:
         raise ValueError("rows [%d, %d) are not rows of a %d-row frame" % (row0, row0 + rows, H))
-    out = torch.empty((L, rows, n_out, 3), dtype=torch.uint8, device=frames_u8.device)
+    n = L if ids is None else _frame_ids(ids, frames_u8.device)
+    out = torch.empty((n, rows, n_out, 3), dtype=torch.uint8, device=frames_u8.device)
+    if ids is not None:
+        _L.check(lib.e2fgvi_resample_rows_ids_u8(_ptr(frames_u8), L, _ptr(ids), n, _ptr(out), H, W, n_out, row0, rows, _ptr(bounds),
+                                                 _ptr(coeffs), coeffs.shape[1], _stream()), "resample_rows_ids_u8")
+        return out
     _L.check(lib.e2fgvi_resample_rows_u8(_ptr(frames_u8), _ptr(out), L, H, W, n_out, row0, rows, _ptr(bounds), _ptr(coeffs),
                                          coeffs.shape[1], _stream()), "resample_rows_u8")
     return out
@@ -1655,6 +1682,86 @@ def hole_bbox(masks_u8):
     return out
 
 
+def hole_bbox_frames(masks_u8):
+    """hole_bbox per frame: masks_u8 [L,Hm,Wm] uint8 on the device -> device int32 [L,4], row l = (x0, y0, x1, y1) of frame l in
+    hole_bbox's convention (upper ends exclusive; x1 <= x0: no hole in that frame).  One pass over the masks, no host read."""
+    lib = _L.load()
+    _u8(masks_u8, "masks")
+    if masks_u8.dim() != 3:
+        raise ValueError("masks must be [L,Hm,Wm], got %s" % (tuple(masks_u8.shape),))
+    L, Hm, Wm = masks_u8.shape
+    out = torch.empty((L, 4), dtype=torch.int32, device=masks_u8.device)
+    _L.check(lib.e2fgvi_hole_bbox_frames(_ptr(masks_u8), L, Hm, Wm, _ptr(out), _stream()), "hole_bbox_frames")
+    return out
+
+
+def _restore_geometry(lo, mask_lo, src, tabs, n, box):
+    """the shape checks restore_u8 and restore_blend share -> (h, w, FH, FW, left, upper, Bw, Bh); n: frames of lo / mask_lo"""
+    ytab, xtab, bx, cx, by, cy = (t for _, t in tabs)
+    if lo.dim() != 4 or lo.shape[3] != 3 or src.dim() != 4 or src.shape[3] != 3 or mask_lo.dim() != 3:
+        raise ValueError("lo and src must be [L,.,.,3] and mask_lo [L,.,.], got %s, %s and %s"
+                         % (tuple(lo.shape), tuple(src.shape), tuple(mask_lo.shape)))
+    h, w = lo.shape[1:3]
+    FH, FW = src.shape[1], src.shape[2]
+    if box is None:
+        left, upper, W, H = 0, 0, FW, FH
+    else:
+        if len(box) != 4:
+            raise ValueError("box must be (left, upper, right, lower), got %r" % (box,))
+        left, upper, right, lower = (int(v) for v in box)
+        if not (0 <= left < right <= FW and 0 <= upper < lower <= FH):
+            raise ValueError("box %r must be non-empty and lie inside the %d x %d frame" % (tuple(box), FW, FH))
+        W, H = right - left, lower - upper
+    if lo.shape[0] != n or tuple(mask_lo.shape) != (n, h, w) or min(n, src.shape[0], h, w, H, W) < 1:
+        raise ValueError("lo %s, mask_lo %s and src %s do not belong to one video" % (tuple(lo.shape), tuple(mask_lo.shape),
+                                                                                       tuple(src.shape)))
+    if any(t.device != lo.device for t in (mask_lo, src) + tuple(t for _, t in tabs)):
+        raise ValueError("lo, mask_lo, src and the tables must be on one device")
+    if ytab.dim() != 1 or ytab.numel() != H or xtab.dim() != 1 or xtab.numel() != W:
+        raise ValueError("ytab / xtab must have H = %d / W = %d entries" % (H, W))
+    for n_in, n_out, b, c, ax in ((w, W, bx, cx, "x"), (h, H, by, cy, "y")):
+        if tuple(b.shape) != (n_out, 2) or c.dim() != 2 or c.shape[0] != n_out:
+            raise ValueError("b%s must be [%d,2] and c%s [%d,ksize]" % (ax, n_out, ax, n_out))
+        if c.shape[1] != 2 * math.ceil(2.0 * max(n_in / n_out, 1.0)) + 1 and not (n_in == n_out and c.shape[1] == 1):
+            raise ValueError("c%s of %d taps does not belong to a %d -> %d resize" % (ax, c.shape[1], n_in, n_out))
+    return h, w, FH, FW, left, upper, W, H
+
+
+def restore_blend(lo, mask_lo, src, ids, first, acc, ytab, xtab, bx, cx, by, cy, box=None, touch=None):
+    """restore_u8 for the n frames of one window, blended into a source-size accumulator (csrc/video.hip, the BLEND epilogue of
+    restore_u8_kernel): lo [n,h,w,3] / mask_lo [n,h,w] uint8, src [L,H,W,3] uint8, ids int32 [n] (frame i of lo belongs to frame
+    ids[i] of src and acc; an id outside [0, L) is skipped), first uint8 [n], acc fp32 [L,H,W,3], updated in place:
+        acc[ids[i]] = img if first[i] else acc[ids[i]] * 0.5 + img * 0.5,     img = what restore_u8(box=) writes for that frame
+    inside ``box`` (None: the whole frame); the tables are restore_u8's.  Nothing outside the box is read or written and only its
+    tiles are launched.  ``touch`` = (left, upper, right, lower), a rectangle inside the frame that contains the box: the update
+    covers it instead -- img is src between the box and its rim -- for a frame whose acc may differ from src there (an earlier
+    window with another box).  acc must not overlap an input.  Returns acc."""
+    lib = _L.load()
+    _u8(lo, "lo"); _u8(mask_lo, "mask_lo"); _u8(src, "src"); _chk(ids, "ids", torch.int32); _u8(first, "first"); _chk(acc, "acc")
+    tabs = (("ytab", ytab), ("xtab", xtab), ("bx", bx), ("cx", cx), ("by", by), ("cy", cy))
+    for name, t in tabs:
+        _chk(t, name, torch.int32)
+    n = ids.numel()
+    if ids.dim() != 1 or first.dim() != 1 or first.numel() != n:
+        raise ValueError("ids must be int32 [n] and first uint8 [n], got %s and %s" % (tuple(ids.shape), tuple(first.shape)))
+    h, w, FH, FW, left, upper, Bw, Bh = _restore_geometry(lo, mask_lo, src, tabs, n, box)
+    if tuple(acc.shape) != tuple(src.shape) or any(t.device != src.device for t in (ids, first, acc)):
+        raise ValueError("acc must be fp32 %s, and ids, first and acc on the device of src" % (tuple(src.shape),))
+    if touch is None:
+        tl, tu, Tw, Th = left, upper, Bw, Bh
+    else:
+        if len(touch) != 4:
+            raise ValueError("touch must be (left, upper, right, lower), got %r" % (touch,))
+        tl, tu, tr, tb = (int(v) for v in touch)
+        if not (0 <= tl <= left and left + Bw <= tr <= FW and 0 <= tu <= upper and upper + Bh <= tb <= FH):
+            raise ValueError("touch %r must lie inside the %d x %d frame and contain the box" % (tuple(touch), FW, FH))
+        Tw, Th = tr - tl, tb - tu
+    _L.check(lib.e2fgvi_restore_blend(_ptr(lo), _ptr(mask_lo), _ptr(src), _ptr(ids), _ptr(first), _ptr(acc), n, src.shape[0], h, w, FH,
+                                      FW, left, upper, Bw, Bh, tl, tu, Tw, Th, _ptr(ytab), _ptr(xtab), _ptr(bx), _ptr(cx), cx.shape[1],
+                                      _ptr(by), _ptr(cy), cy.shape[1], _stream()), "restore_blend")
+    return acc
+
+
 def restore_u8(lo, mask_lo, src, ytab, xtab, bx, cx, by, cy, out=None, box=None):
     """out = where(NEAREST(mask_lo) != 0, BICUBIC(lo), src) at the size of src, one fused launch (csrc/video.hip): lo [L,h,w,3]
     finished frames, mask_lo [L,h,w] of 0 / 1, src [L,H,W,3], all uint8; ytab int32 [H] / xtab int32 [W] from video.nearest_table;
@@ -1667,32 +1774,10 @@ def restore_u8(lo, mask_lo, src, ytab, xtab, bx, cx, by, cy, out=None, box=None)
     tabs = (("ytab", ytab), ("xtab", xtab), ("bx", bx), ("cx", cx), ("by", by), ("cy", cy))
     for name, t in tabs:
         _chk(t, name, torch.int32)
-    if lo.dim() != 4 or lo.shape[3] != 3 or src.dim() != 4 or src.shape[3] != 3 or mask_lo.dim() != 3:
-        raise ValueError("lo and src must be [L,.,.,3] and mask_lo [L,.,.], got %s, %s and %s"
-                         % (tuple(lo.shape), tuple(src.shape), tuple(mask_lo.shape)))
-    L, h, w, _ = lo.shape
-    FH, FW = src.shape[1], src.shape[2]
-    if box is None:
-        left, upper, W, H = 0, 0, FW, FH
-    else:
-        if len(box) != 4:
-            raise ValueError("box must be (left, upper, right, lower), got %r" % (box,))
-        left, upper, right, lower = (int(v) for v in box)
-        if not (0 <= left < right <= FW and 0 <= upper < lower <= FH):
-            raise ValueError("box %r must be non-empty and lie inside the %d x %d frame" % (tuple(box), FW, FH))
-        W, H = right - left, lower - upper
-    if src.shape[0] != L or tuple(mask_lo.shape) != (L, h, w) or min(L, h, w, H, W) < 1:
-        raise ValueError("lo %s, mask_lo %s and src %s do not belong to one video" % (tuple(lo.shape), tuple(mask_lo.shape),
-                                                                                       tuple(src.shape)))
-    if any(t.device != lo.device for t in (mask_lo, src) + tuple(t for _, t in tabs)):
-        raise ValueError("lo, mask_lo, src and the tables must be on one device")
-    if ytab.dim() != 1 or ytab.numel() != H or xtab.dim() != 1 or xtab.numel() != W:
-        raise ValueError("ytab / xtab must have H = %d / W = %d entries" % (H, W))
-    for n_in, n_out, b, c, ax in ((w, W, bx, cx, "x"), (h, H, by, cy, "y")):
-        if tuple(b.shape) != (n_out, 2) or c.dim() != 2 or c.shape[0] != n_out:
-            raise ValueError("b%s must be [%d,2] and c%s [%d,ksize]" % (ax, n_out, ax, n_out))
-        if c.shape[1] != 2 * math.ceil(2.0 * max(n_in / n_out, 1.0)) + 1 and not (n_in == n_out and c.shape[1] == 1):
-            raise ValueError("c%s of %d taps does not belong to a %d -> %d resize" % (ax, c.shape[1], n_in, n_out))
+    if lo.dim() == 4 and src.dim() == 4 and src.shape[0] != lo.shape[0]:
+        raise ValueError("lo %s and src %s do not hold the same number of frames" % (tuple(lo.shape), tuple(src.shape)))
+    L = lo.shape[0]
+    h, w, FH, FW, left, upper, W, H = _restore_geometry(lo, mask_lo, src, tabs, L, box)
     if out is None:
         out = torch.empty((L, FH, FW, 3), dtype=torch.uint8, device=src.device)
     else:
@@ -1706,6 +1791,16 @@ def restore_u8(lo, mask_lo, src, ytab, xtab, bx, cx, by, cy, out=None, box=None)
         _L.check(lib.e2fgvi_restore_box_u8(_ptr(lo), _ptr(mask_lo), _ptr(src), _ptr(out), L, h, w, FH, FW, left, upper, W, H, _ptr(ytab),
                                            _ptr(xtab), _ptr(bx), _ptr(cx), cx.shape[1], _ptr(by), _ptr(cy), cy.shape[1], _stream()),
                  "restore_box_u8")
+    return out
+
+
+def u8_to_float(x):
+    """uint8 -> fp32, any shape (ndarray.astype(float32)): the start of restore_blend's accumulator"""
+    lib = _L.load()
+    _u8(x, "x")
+    out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    if x.numel():
+        _L.check(lib.e2fgvi_u8_to_float(_ptr(x), _ptr(out), x.numel(), _stream()), "u8_to_float")
     return out
 
 

@@ -276,7 +276,100 @@ def hole_region(masks_u8, frame_wh, size, context=0.5, device=None):
     return plan_region(bbox, frame_wh, size, context)
 
 
-def resize_frames(frames_u8, size, device=None, box=None):
+def plan_track(frame_boxes, windows, frame_wh, size, context=0.5):
+    """The crop regions of inpaint_video(region="track"), one per window of plan_windows: ``frame_boxes`` holds every frame's hole
+    bounding box (x0, y0, x1, y1) in source pixels, upper ends exclusive; None, or a box with x1 <= x0 or y1 <= y0, is a frame
+    without a hole.  Window k's box is plan_region of the union of the boxes of its NEIGHBOUR ids -- only their predictions are
+    kept (test.py:172-179), so the reference frames do not widen it -- and None when none of them has a hole pixel: that window
+    runs no forward.  Over the +-neighbor_stride frames of a window a moving hole stays small where its box over the whole video
+    (region="hole") tends to the whole frame.  Host logic only."""
+    out = []
+    for nb, _ in windows:
+        hit = [frame_boxes[j] for j in nb if frame_boxes[j] is not None and frame_boxes[j][2] > frame_boxes[j][0]
+               and frame_boxes[j][3] > frame_boxes[j][1]]
+        if not hit:
+            out.append(None)
+            continue
+        union = (min(int(b[0]) for b in hit), min(int(b[1]) for b in hit), max(int(b[2]) for b in hit), max(int(b[3]) for b in hit))
+        out.append(plan_region(union, frame_wh, size, context))
+    return out
+
+
+def _frame_boxes(masks_d, frame_wh):
+    """every frame's hole box in frame pixels (None: no hole) from device masks [L,Hm,Wm]: ops.hole_bbox_frames, one pass, and
+    one copy of 4 L integers to the host; masks of another size than the frames are mapped like hole_region maps its box"""
+    if masks_d.dim() != 3:
+        raise ValueError("masks must be uint8 [L,Hm,Wm], got %s" % (tuple(masks_d.shape),))
+    return _map_frame_boxes(ops.hole_bbox_frames(masks_d).cpu().tolist(), (masks_d.shape[2], masks_d.shape[1]), frame_wh)
+
+
+def _map_frame_boxes(raw, mask_wh, frame_wh):
+    """per-frame boxes in mask pixels (x1 <= x0: no hole) -> frame pixels, floor for the lower ends and ceil for the upper ends;
+    None for a frame without a hole"""
+    mask_wh, frame_wh = tuple(int(v) for v in mask_wh), tuple(int(v) for v in frame_wh)
+    return [_scale_box(b, mask_wh, frame_wh) if b[2] > b[0] and b[3] > b[1] else None for b in raw]
+
+
+def track_regions(masks_u8, frame_wh, size, neighbor_stride=5, ref_length=10, num_ref=-1, context=0.5, device=None):
+    """The boxes inpaint_video(region="track") uses for these masks, one (left, upper, right, lower) or None per window of
+    plan_windows (plan_track): masks_u8 uint8 [L,Hm,Wm], an array, or a tensor that is used where it is when on the device.  One
+    device pass over the masks and one host copy of 4 L integers, as hole_region reports the box of region="hole"."""
+    m = _upload(masks_u8, device)
+    boxes = _frame_boxes(m, frame_wh)
+    return plan_track(boxes, plan_windows(len(boxes), neighbor_stride, ref_length, num_ref), frame_wh, size, context)
+
+
+def _check_ids(ids, length):
+    """frame numbers for ids=: a sequence of integers in [0, length) (ValueError otherwise), or a device int32 tensor, which is
+    used as it is -- the kernels check its range (a frame of zeros for a bad id), the host never reads it"""
+    if isinstance(ids, torch.Tensor) and ids.is_cuda:
+        return ids
+    vals = [int(v) for v in (ids.tolist() if hasattr(ids, "tolist") else ids)]
+    if not vals or any(not 0 <= v < length for v in vals):
+        raise ValueError("ids must be a non-empty list of frame numbers in [0, %d), got %r" % (length, vals))
+    return vals
+
+
+def _resize_plan(frame_hw, size, box, device, gather=False):
+    """The passes of ``Image.resize(size, box=box)`` on [.,H,W,3] frames with their tables on the device: (width pass, height pass),
+    each None when Pillow runs none -- width = (first row, rows, bounds, coeffs) for ops.resample_rows_u8, height = (bounds, coeffs,
+    span) for ops.resample_u8.  See resize_frames for the rules.  ``gather``: the frames are picked by ids=, so a resize that is
+    the identity still runs the (one-tap) width pass, which then is the gather."""
+    H, W = frame_hw
+    w, h = size
+    left, upper, right, lower = box
+    t = lambda a: torch.from_numpy(a).to(device)
+    need_w = not (left == 0 and right == W == w)
+    need_h = not (upper == 0 and lower == H == h)
+    if gather and not need_w and not need_h:
+        need_w = True
+    by, cy = bicubic_tables(H, h, (upper, lower))
+    wpass = hpass = None
+    if need_w:
+        # the rows the height pass reads; for a crop along the height these are the box's rows and that pass is dropped
+        crop = lower - upper == h
+        first, last = (upper, lower) if crop else (int(by[0, 0]), int(by[-1, 0] + by[-1, 1]))
+        bx, cx = _axis_tables(W, w, (left, right))
+        wpass = (first, last - first, t(bx), t(cx))
+        by = by - np.array([first, 0], np.int32)
+        need_h = not crop
+    if need_h:
+        hpass = (t(by), t(cy), lower - upper)
+    return wpass, hpass
+
+
+def _resize_run(plan, x, size, ids=None):
+    """run _resize_plan's passes on device frames x; ids: a device int32 table of the frames to resize (the first pass reads them)"""
+    wpass, hpass = plan
+    if wpass is not None:
+        x = ops.resample_rows_u8(x, size[0], wpass[0], wpass[1], wpass[2], wpass[3], ids=ids)
+        ids = None
+    if hpass is not None:
+        x = ops.resample_u8(x, size[1], 1, hpass[0], hpass[1], span=hpass[2], ids=ids)
+    return x
+
+
+def resize_frames(frames_u8, size, device=None, box=None, ids=None):
     """PIL ``Image.resize(size)`` of every frame on the device (BICUBIC, Pillow's default for RGB): test.py:97-104,127
     (resize_frames) and core/dataset.py:115, where evaluate.py's DAVIS / YouTube-VOS frames -- the ground truth of
     metrics.calc_psnr_and_ssim -- are resized to (432, 240).  ``size`` is (width, height), PIL's and test.py's order,
@@ -289,7 +382,11 @@ def resize_frames(frames_u8, size, device=None, box=None):
     cover it, the width pass runs first and only over the source rows the height pass reads (its first bound to its last bound
     plus count; ops.resample_rows_u8), and the height pass's bounds are shifted by that first row.  An axis whose box has the
     output's length is a crop (bicubic taps at integer offsets are 0, 1, 0, 0): it takes one-tap tables, and as the height axis no
-    pass at all -- the width pass then runs over the box's rows alone."""
+    pass at all -- the width pass then runs over the box's rows alone.
+
+    ``ids``: frame numbers (a list, checked against L: ValueError; or a device int32 tensor, range-checked in the kernel) -- the
+    result holds the resize of frames_u8[ids[l]] for every l, in that order: the first pass reads the chosen frames straight out
+    of the video, so no copy of them at source size is made.  A resize that is the identity then is a gather (a one-tap pass)."""
     if len(frames_u8.shape) != 4 or frames_u8.shape[3] != 3:
         raise ValueError("frames must be uint8 [L,H,W,3], got %s" % (tuple(frames_u8.shape),))
     w, h = (int(v) for v in size)
@@ -298,25 +395,15 @@ def resize_frames(frames_u8, size, device=None, box=None):
     H, W = (int(v) for v in frames_u8.shape[1:3])
     if box is not None:
         box = _check_box(box, (W, H))                   # from the shapes alone, before any upload
+    if ids is not None:
+        ids = _check_ids(ids, frames_u8.shape[0])
     x = _upload(frames_u8, device)
-    if box is not None:
-        left, upper, right, lower = box
-        if box != (0, 0, W, H):
-            t = lambda a: torch.from_numpy(a).to(x.device)
-            need_w = not (left == 0 and right == W == w)
-            need_h = not (upper == 0 and lower == H == h)
-            by, cy = bicubic_tables(H, h, (upper, lower))
-            if need_w:
-                # the rows the height pass reads; for a crop along the height these are the box's rows and that pass is dropped
-                crop = lower - upper == h
-                first, last = (upper, lower) if crop else (int(by[0, 0]), int(by[-1, 0] + by[-1, 1]))
-                bx, cx = _axis_tables(W, w, (left, right))
-                x = ops.resample_rows_u8(x, w, first, last - first, t(bx), t(cx))
-                by = by - np.array([first, 0], np.int32)
-                need_h = not crop
-            if need_h:
-                x = ops.resample_u8(x, h, 1, t(by), t(cy), span=lower - upper)
-            return x
+    if ids is not None:
+        if not isinstance(ids, torch.Tensor):
+            ids = torch.tensor(ids, dtype=torch.int32, device=x.device)
+        return _resize_run(_resize_plan((H, W), (w, h), box or (0, 0, W, H), x.device, gather=True), x, (w, h), ids)
+    if box is not None and box != (0, 0, W, H):
+        return _resize_run(_resize_plan((H, W), (w, h), box, x.device), x, (w, h))
     for n_out, axis in ((w, 2), (h, 1)):
         if x.shape[axis] != n_out:
             bounds, coeffs = bicubic_tables(x.shape[axis], n_out)
@@ -363,24 +450,38 @@ def restore_frames(lo_u8, masks01_lo, src_u8, device=None, box=None):
     (h, w), (H, W) = lo.shape[1:3], src.shape[1:3]
     if box is not None:
         W, H = box[2] - box[0], box[3] - box[1]
-    dev = src.device
+    return ops.restore_u8(lo, m, src, *_restore_tables((h, w), (H, W), src.device), box=box)
+
+
+def _restore_tables(lo_hw, box_hw, device):
+    """ops.restore_u8's six tables on the device for lo of (h, w) pasted into a frame or a box of (H, W)"""
+    (h, w), (H, W) = lo_hw, box_hw
     tabs = [nearest_table(h, H), nearest_table(w, W)] + list(_axis_tables(w, W)) + list(_axis_tables(h, H))
-    return ops.restore_u8(lo, m, src, *[torch.from_numpy(t).to(dev) for t in tabs], box=box)
+    return [torch.from_numpy(t).to(device) for t in tabs]
 
 
-def prepare_masks(masks_u8, size_hw, device, dilate=True, box=None):
+def _mask_tables(mask_hw, size_hw, box, device):
+    """(ytab, xtab) of prepare_masks on the device; box = (left, upper, right, lower) in mask pixels, checked already, or None"""
+    bx, by = ((box[0], box[2]), (box[1], box[3])) if box is not None else (None, None)
+    return (torch.from_numpy(nearest_table(mask_hw[0], size_hw[0], by)).to(device),
+            torch.from_numpy(nearest_table(mask_hw[1], size_hw[1], bx)).to(device))
+
+
+def prepare_masks(masks_u8, size_hw, device, dilate=True, box=None, ids=None):
     """uint8 masks [L,Hin,Win] (any size, any non-zero = hole; an array, or a tensor that is used where it is when on the device)
     -> device uint8 [L,H,W] of 0/1 like test.py:56-69.  ``box`` = (left, upper, right, lower) in mask pixels: only that region is
-    resized, ``resize((W, H), Image.NEAREST, box=box)``, and the dilation is clipped to the crop, as cv2.dilate of that result is."""
-    bx = by = None
+    resized, ``resize((W, H), Image.NEAREST, box=box)``, and the dilation is clipped to the crop, as cv2.dilate of that result is.
+    ``ids``: frame numbers as for resize_frames -- the result holds the prepared masks_u8[ids[l]] for every l, in that order."""
     if box is not None:
-        left, upper, right, lower = _check_box(box, (masks_u8.shape[2], masks_u8.shape[1]))
-        bx, by = (left, right), (upper, lower)
+        box = _check_box(box, (masks_u8.shape[2], masks_u8.shape[1]))
+    if ids is not None:
+        ids = _check_ids(ids, masks_u8.shape[0])
     m = _upload(masks_u8, device)
+    if ids is not None and not isinstance(ids, torch.Tensor):
+        ids = torch.tensor(ids, dtype=torch.int32, device=m.device)
     H, W = size_hw
-    ytab = torch.from_numpy(nearest_table(m.shape[1], H, by)).to(device)
-    xtab = torch.from_numpy(nearest_table(m.shape[2], W, bx)).to(device)
-    return ops.mask_prepare(m, ytab, xtab, H, W, 4 if dilate else 0)
+    ytab, xtab = _mask_tables(m.shape[1:3], (H, W), box, device)
+    return ops.mask_prepare(m, ytab, xtab, H, W, 4 if dilate else 0, ids=ids)
 
 
 @torch.no_grad()
@@ -433,17 +534,44 @@ def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, 
     The masks are resized with the same box (mapped to mask pixels when their size differs: floor for the lower ends, ceil for
     the upper ends) and uploaded once for both uses; everything between the resize and the paste is unchanged.  With
     restore=True the result has the source's size: the box is pasted back (restore_frames(box=)) and every byte outside it is
-    the caller's.  Without restore the result is the region at ``size``; hole_region tells which box that was."""
+    the caller's.  Without restore the result is the region at ``size``; hole_region tells which box that was.
+
+    ``region`` = "track" (with ``size`` and restore=True) follows a moving hole: every window of plan_windows gets a box of its
+    own, planned like "hole" around the bounding box of the masks of the window's NEIGHBOUR frames alone (plan_track;
+    track_regions tells which boxes) -- over the +-neighbor_stride frames of a window a moving hole stays small where its box
+    over the whole video tends to the whole frame, so the model keeps seeing source resolution.  A window whose neighbour frames
+    hold no hole pixel runs no forward; a video without one returns the source and never calls the model.  Per window the
+    chosen frames and masks are resized straight out of the video (resize_frames(ids=), prepare_masks(ids=)), composited at the
+    model's size like test.py:172-174, pasted into their box of the source frame (restore_frames(box=)) and only then blended
+    0.5 / 0.5 with what earlier windows left for that frame (test.py:175-179) -- two windows of one frame have different boxes,
+    so their results meet at source size, in an fp32 [L,H,W,3] accumulator that starts as the source (ops.restore_blend).  Every
+    byte outside all boxes, or outside the pasted masks, is the caller's.  One window at a time: "track" without restore=True,
+    or with reuse=True, batch_windows > 1 or in_flight > 1, raises ValueError."""
     box = None
+    track = False
     if region is not None:
         if size is None:
             raise ValueError("region= names the part of the frames that size= resizes for the model: without size there is no "
                              "region to cut")
         if isinstance(region, str):
-            if region != "hole":
-                raise ValueError('region must be None, "hole" or (left, upper, right, lower), got %r' % (region,))
+            if region not in ("hole", "track"):
+                raise ValueError('region must be None, "hole", "track" or (left, upper, right, lower), got %r' % (region,))
+            track = region == "track"
         else:
             box = _check_box(region, (frames_u8.shape[2], frames_u8.shape[1]))
+    if track:
+        if not restore:
+            raise ValueError('region="track" gives every window a box of its own, so the windows\' results exist together only at '
+                             "the source size: restore must be True")
+        if reuse:
+            raise ValueError('region="track" resizes every window with another box, so no frame\'s encoder features or flows can be '
+                             "shared between windows: reuse must be False")
+        if batch_windows > 1:
+            raise ValueError('region="track" runs one window per forward (a window without a hole runs none): batch_windows must be '
+                             "1, got %d" % batch_windows)
+        if in_flight > 1:
+            raise ValueError('region="track" pastes and blends every window at source size in window order on one stream: in_flight '
+                             "must be 1, got %d" % in_flight)
     if restore:
         if size is None:
             raise ValueError("restore=True pastes the result back into frames that size= resized: without size there is nothing "
@@ -469,6 +597,9 @@ def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, 
         frames_d = torch.as_tensor(np.ascontiguousarray(frames_u8)).to(device)
     source = frames_d                                   # restore=True: kept beside the resized frames, only read
     masks_d = _upload(masks_u8, device)                 # once: the bounding box and the mask preparation read the same tensor
+    if track:
+        return _inpaint_track(model, source, masks_d, tuple(int(v) for v in size),
+                              plan_windows(source.shape[0], neighbor_stride, ref_length, num_ref), dilate, pad, context)
     mask_box = None
     if region is not None:
         frame_wh = (source.shape[2], source.shape[1])
@@ -600,3 +731,66 @@ def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, 
     if restore:
         return restore_frames(ops.float_to_u8(comp), masks01, source, box=box).cpu().numpy()
     return ops.float_to_u8(comp).cpu().numpy()
+
+
+def _touched(k, windows, boxes):
+    """The rectangle window k's paste-back must cover: its own box and the boxes of the earlier windows that kept a prediction for
+    one of its neighbour frames.  Such a frame's accumulator may differ from the source anywhere in those boxes -- the paste of a
+    wider box reaches further around the hole than a narrower one's guard band -- and test.py:175-179 blends the whole frame, so
+    0.5 acc + 0.5 src is owed there too.  Everywhere else acc is still the source and 0.5 v + 0.5 v == v: nothing to do."""
+    left, upper, right, lower = boxes[k]
+    mine = set(windows[k][0])
+    for j in range(k):
+        if boxes[j] is not None and mine.intersection(windows[j][0]):
+            left, upper = min(left, boxes[j][0]), min(upper, boxes[j][1])
+            right, lower = max(right, boxes[j][2]), max(lower, boxes[j][3])
+    return left, upper, right, lower
+
+
+def _inpaint_track(model, source, masks_d, size, windows, dilate, pad, context):
+    """inpaint_video(region="track") after the argument checks and the uploads: source uint8 [L,H,W,3] and masks_d uint8
+    [L,Hm,Wm] on the device -> uint8 array [L,H,W,3]"""
+    device = source.device
+    L, H, W, _ = source.shape
+    w, h = size
+    boxes = plan_track(_frame_boxes(masks_d, (W, H)), windows, (W, H), size, context)
+    run = [k for k, b in enumerate(boxes) if b is not None]
+    if not run:
+        return source.cpu().numpy()
+    Hp, Wp = padded_size(h, w) if pad else (h, w)
+    mask_hw = tuple(int(v) for v in masks_d.shape[1:3])
+    # every host->device upload happens here, before the first forward: per distinct box the tables of the frame resize, of the
+    # mask resize and of the paste-back (windows with equal boxes share them); per window its frame ids and first flags
+    tables = {}
+    for k in run:
+        if boxes[k] not in tables:
+            b = boxes[k]
+            mask_box = _scale_box(b, (W, H), (mask_hw[1], mask_hw[0]))
+            tables[b] = (_resize_plan((H, W), size, b, device, gather=True), _mask_tables(mask_hw, (h, w), mask_box, device),
+                         _restore_tables((h, w), (b[3] - b[1], b[2] - b[0]), device))
+    ids_dev, first_dev, touch = {}, {}, {}
+    seen = [False] * L
+    for k in run:
+        nb, rf = windows[k]
+        ids_dev[k] = torch.tensor(nb + rf, dtype=torch.int32, device=device)
+        first_dev[k] = torch.tensor([0 if seen[j] else 1 for j in nb], dtype=torch.uint8, device=device)
+        for j in nb:
+            seen[j] = True
+        touch[k] = _touched(k, windows, boxes)
+    t_max = max(len(windows[k][0]) + len(windows[k][1]) for k in run)
+    n_max = max(len(windows[k][0]) for k in run)
+    local = torch.arange(t_max, dtype=torch.int32, device=device)       # a window's frames are numbered 0 ... t - 1 once resized
+    ones = torch.ones(n_max, dtype=torch.uint8, device=device)
+    acc = ops.u8_to_float(source)
+    comp = torch.empty((n_max, h, w, 3), dtype=torch.float32, device=device)
+    for k in run:
+        n, t = len(windows[k][0]), len(windows[k][0]) + len(windows[k][1])
+        rplan, (ytab, xtab), rtabs = tables[boxes[k]]
+        fr = _resize_run(rplan, source, size, ids_dev[k])
+        m01 = ops.mask_prepare(masks_d, ytab, xtab, h, w, 4 if dilate else 0, ids=ids_dev[k])
+        pred, _ = model(ops.masked_clip(fr, m01, local[:t], Hp, Wp), n)
+        # test.py:172-174 at the model's size: every local frame is this window's first (and only) one in comp
+        ops.composite(pred.contiguous(), local[:n], ones[:n], fr, m01, comp)
+        ops.restore_blend(ops.float_to_u8(comp[:n]), m01[:n], source, ids_dev[k][:n], first_dev[k], acc, *rtabs, box=boxes[k],
+                          touch=touch[k])
+    return ops.float_to_u8(acc).cpu().numpy()

@@ -40,6 +40,12 @@ extern "C" {
  * 3x3 cross (cv2.dilate, out-of-image pixels ignored).  out: [L,H,W] of 0 / 1. */
 int e2fgvi_mask_prepare(const uint8_t* masks, int32_t L, int32_t Hin, int32_t Win, const int32_t* ytab, const int32_t* xtab,
                         uint8_t* out, int32_t H, int32_t W, int32_t iterations, void* stream);
+/* e2fgvi_mask_prepare of chosen frames (the frames of one window of video.inpaint_video(region="track")): out [n,H,W], frame l
+ * made from frame ids[l] of the L frames of masks; ids is a device table and is range-checked in the kernel -- an id outside
+ * [0, L) gives an empty mask. */
+int e2fgvi_mask_prepare_ids(const uint8_t* masks, int32_t L, const int32_t* ids, int32_t n, int32_t Hin, int32_t Win,
+                            const int32_t* ytab, const int32_t* xtab, uint8_t* out, int32_t H, int32_t W, int32_t iterations,
+                            void* stream);
 /* test.py:146-165: clip[ti][c][y][x] = (frames[ids[ti]]/255*2-1) * (1 - masks[ids[ti]]), fp32 NCHW [t,3,Hp,Wp], rows /
  * columns beyond H / W mirror the frame (cat([x, flip(x)])[:Hp]). */
 int e2fgvi_masked_clip(const uint8_t* frames, const uint8_t* masks, const int32_t* ids, int32_t t, int32_t H, int32_t W,
@@ -62,12 +68,24 @@ int e2fgvi_resample_u8(const uint8_t* src, uint8_t* dst, int32_t L, int32_t H, i
  * the kernel; ksize >= 1 is the tables' own.  0 <= row0, row0 + rows <= H (E2FGVI_EINVAL). */
 int e2fgvi_resample_rows_u8(const uint8_t* src, uint8_t* dst, int32_t L, int32_t H, int32_t W, int32_t n_out, int32_t row0,
                             int32_t rows, const int32_t* bounds, const int32_t* coeffs, int32_t ksize, void* stream);
+/* The two passes above on chosen frames: dst frame l (of n) is the pass over frame ids[l] of the L frames of src -- a window's
+ * frames are resized straight out of the video, no copy of them at source size is made.  ids is a device table, range-checked in
+ * the kernel: an id outside [0, L) gives a frame of zeros. */
+int e2fgvi_resample_ids_u8(const uint8_t* src, int32_t L, const int32_t* ids, int32_t n, uint8_t* dst, int32_t H, int32_t W,
+                           int32_t n_out, int32_t axis, const int32_t* bounds, const int32_t* coeffs, int32_t ksize, void* stream);
+int e2fgvi_resample_rows_ids_u8(const uint8_t* src, int32_t L, const int32_t* ids, int32_t n, uint8_t* dst, int32_t H, int32_t W,
+                                int32_t n_out, int32_t row0, int32_t rows, const int32_t* bounds, const int32_t* coeffs, int32_t ksize,
+                                void* stream);
 /* Bounding box of the hole of a whole video, for a driver that feeds the model only a region around it
  * (video.inpaint_video(region="hole")): masks uint8 [L,Hm,Wm] as test.py:56-69 reads them (any non-zero byte is hole) ->
  * box int32 [4] on the device = (x0, y0, x1, y1), upper ends exclusive; x1 <= x0 when no byte is set (the box is then
  * (0x7f7f7f7f, 0x7f7f7f7f, 0, 0)).  One pass over the masks, 16-byte loads between a byte head and tail per row; box is
  * initialised on `stream` in front of the launch.  L * Hm * Wm == 0 launches nothing and leaves the empty box. */
 int e2fgvi_hole_bbox(const uint8_t* masks, int32_t L, int32_t Hm, int32_t Wm, int32_t* box, void* stream);
+/* e2fgvi_hole_bbox per frame (video.inpaint_video(region="track") plans one region per window from them): boxes int32 [L][4] on
+ * the device, frame l's (x0, y0, x1, y1) in the same convention -- a frame without a hole keeps (0x7f7f7f7f, 0x7f7f7f7f, 0, 0).
+ * One pass over the masks, any pitch and base; L == 0 launches nothing. */
+int e2fgvi_hole_bbox_frames(const uint8_t* masks, int32_t L, int32_t Hm, int32_t Wm, int32_t* boxes, void* stream);
 /* The paste-back that follows test.py:168-179 when test.py:97-104,127 resized the frames on the way in (the reference stops at
  * the resized video; a front end writes the result at source size): for every frame
  *   out = where(Image.fromarray(mask_lo * 255).resize((W, H), NEAREST) != 0, Image.fromarray(lo).resize((W, H)), src)
@@ -90,6 +108,21 @@ int e2fgvi_restore_box_u8(const uint8_t* lo, const uint8_t* mask_lo, const uint8
                           int32_t w, int32_t H, int32_t W, int32_t left, int32_t upper, int32_t Bw, int32_t Bh, const int32_t* ytab,
                           const int32_t* xtab, const int32_t* bounds_x, const int32_t* coeffs_x, int32_t ksize_x,
                           const int32_t* bounds_y, const int32_t* coeffs_y, int32_t ksize_y, void* stream);
+/* e2fgvi_restore_box_u8 with test.py:175-179's blend of overlapping windows moved to source size: lo [n,h,w,3] / mask_lo [n,h,w]
+ * are the finished frames of ONE window, frame i belonging to frame ids[i] of the L frames of src [L,H,W,3] uint8 and acc
+ * [L,H,W,3] float.  With img = the frame e2fgvi_restore_box_u8 would write for it (the same tables, the same arithmetic),
+ *   acc[ids[i]] = first[i] ? img : acc[ids[i]] * 0.5f + img * 0.5f
+ * on the pixels of the touched rectangle (touch_left, touch_upper) + Tw x Th, which must contain the box and lie inside the frame
+ * (E2FGVI_EINVAL otherwise); between the box and the rim of that rectangle img is src.  Nothing else of acc is read or written and
+ * only the tiles the rectangle reaches are launched.  ids / first are device tables; an id outside [0, L) is skipped.  acc must
+ * not overlap any input (E2FGVI_EINVAL). */
+int e2fgvi_restore_blend(const uint8_t* lo, const uint8_t* mask_lo, const uint8_t* src, const int32_t* ids, const uint8_t* first,
+                         float* acc, int32_t n, int32_t L, int32_t h, int32_t w, int32_t H, int32_t W, int32_t left, int32_t upper,
+                         int32_t Bw, int32_t Bh, int32_t touch_left, int32_t touch_upper, int32_t Tw, int32_t Th, const int32_t* ytab,
+                         const int32_t* xtab, const int32_t* bounds_x, const int32_t* coeffs_x, int32_t ksize_x,
+                         const int32_t* bounds_y, const int32_t* coeffs_y, int32_t ksize_y, void* stream);
+/* ndarray.astype(float32) of uint8 values: the accumulator above starts as the source frames */
+int e2fgvi_u8_to_float(const uint8_t* src, float* dst, int64_t n, void* stream);
 /* ndarray.astype(uint8) of the blended frames (truncation) */
 int e2fgvi_float_to_u8(const float* src, uint8_t* dst, int64_t n, void* stream);
 /* model output [N,3,Hp,Wp] in (-1,1) -> uint8 NHWC [N,H,W,3] = uint8((pred+1)/2*255): the form the clip-sharded runner
