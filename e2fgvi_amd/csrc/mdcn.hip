@@ -303,7 +303,6 @@ __global__ __launch_bounds__(64 * WGM * WGN * KS) void mdcn_kernel(const DcnPara
             const int y0 = (int)fy, x0 = (int)fx, y1 = y0 + 1, x1 = x0 + 1;
             const float ly = py - fy, lx = px - fx, hy = 1.f - ly, hx = 1.f - lx;
             const bool vy0 = inside && y0 >= 0, vy1 = inside && y1 <= p.H - 1, vx0 = x0 >= 0, vx1 = x1 <= p.W - 1;
-            const float mm = inside ? mk : 0.f;
             // 24-bit multiplies (full rate): pixel indices and pixel strides are < 2^24 (checked on the host).  The products
             // are formed from the row y1 and column x1, which are >= 0 whenever the sample is inside; the y0 / x0 addresses
             // follow by subtraction (they may wrap when y0 or x0 is -1 -- those corners are replaced by the sentinel)
@@ -313,7 +312,11 @@ __global__ __launch_bounds__(64 * WGM * WGN * KS) void mdcn_kernel(const DcnPara
             const unsigned a11 = __umul24(r1 + (unsigned)x1, ld4) + ch;
             const unsigned a00 = a01 - ld4, a10 = a11 - ld4;
             const u32x4 ad = {(vy0 && vx0) ? a00 : OOBS, (vy0 && vx1) ? a01 : OOBS, (vy1 && vx0) ? a10 : OOBS, (vy1 && vx1) ? a11 : OOBS};
-            const f32x4 ww = {hy * hx * mm, hy * lx * mm, ly * hx * mm, ly * lx * mm};
+            // a sample outside the guard is dropped by SELECT, as mmcv skips it: a non-finite position (inf / nan offset) has
+            // ly = py - floorf(py) = NaN, and NaN weights times a zero mask -- or times the zeros its out-of-range corners
+            // read -- would make the whole output pixel NaN.  Inside samples form the same products as before, bit for bit.
+            const f32x4 wi = {hy * hx * mk, hy * lx * mk, ly * hx * mk, ly * lx * mk};
+            const f32x4 ww = inside ? wi : f32x4{0.f, 0.f, 0.f, 0.f};
             float* d = graw + (buf * SLOTS + ltid) * 8;
             *reinterpret_cast<u32x4*>(d) = ad;
             *reinterpret_cast<f32x4*>(d + 4) = ww;

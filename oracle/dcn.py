@@ -70,7 +70,8 @@ def deform_columns(x, offset, mask, kernel_size, stride, padding, dilation, defo
         ok = inside & (yy >= 0) & (yy <= H - 1) & (xx >= 0) & (xx <= W - 1)
         idx = (yy.clamp(0, H - 1) * W + xx.clamp(0, W - 1)).reshape(N, dg, 1, K * Ho * Wo)
         v = torch.gather(xf, 3, idx.expand(N, dg, cg, K * Ho * Wo))
-        wgt = (wgt * ok.to(x.dtype)).reshape(N, dg, 1, K * Ho * Wo)
+        # a select, not a product with 0 / 1: a non-finite position has NaN weights, and mmcv skips that sample (adds 0)
+        wgt = torch.where(ok, wgt, torch.zeros_like(wgt)).reshape(N, dg, 1, K * Ho * Wo)
         return v * wgt
 
     val = (corner(y0, x0, hy * hx) + corner(y0, x1, hy * lx) +

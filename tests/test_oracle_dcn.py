@@ -87,6 +87,24 @@ def test_torch_and_c_restatements_agree(mag, stride, pad, dil):
     assert _close(a, c, 1e-5)
 
 
+def test_nonfinite_offsets_drop_the_tap_in_both_restatements():
+    """mmcv's guard fails for a non-finite position and the tap adds 0: with one inf and one nan offset both restatements stay
+    finite and return exactly what they return with those offsets far outside (oracle/dcn.py once multiplied NaN weights by 0)"""
+    from oracle.dcn_c import modulated_deform_conv2d_c
+    N, C, H, W, Co, dg = 1, 32, 6, 7, 5, 2
+    x, w, b = _rand(20, N, C, H, W), _rand(21, Co, C, 3, 3) / 10, _rand(22, Co)
+    off = _rand(23, N, dg * 18, H, W)
+    msk = torch.sigmoid(_rand(24, N, dg * 9, H, W))
+    far = off.clone()
+    off[0, 8, 2, 3], far[0, 8, 2, 3] = float("inf"), 1e6           # dy of group 0, tap 4
+    off[0, 18 + 3, 4, 1], far[0, 18 + 3, 4, 1] = float("nan"), -1e6      # dx of group 1, tap 1
+    for fn in (modulated_deform_conv2d, modulated_deform_conv2d_c):
+        got = fn(x, off, msk, w, b, 1, 1, 1, 1, dg)
+        assert torch.isfinite(got).all(), fn.__name__
+        assert torch.equal(got, fn(x, far, msk, w, b, 1, 1, 1, 1, dg)), fn.__name__
+    assert _close(modulated_deform_conv2d(x, off, msk, w, b, 1, 1, 1, 1, dg), modulated_deform_conv2d_c(x, off, msk, w, b, 1, 1, 1, 1, dg), 1e-5)
+
+
 def test_exactly_on_border_and_outside():
     """py == -1 / py == H are outside (value 0); py in (H-1, H) uses only the last row (mmcv guard semantics)."""
     x = torch.ones(1, 16, 4, 4)
