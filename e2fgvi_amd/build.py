@@ -83,6 +83,7 @@ def build(force=False, verbose=False, nopk_all=False, lib=None, tag=None, define
             verify_wino_waits(objdir)
             verify_exit_reuse(objdir)
             verify_no_scratch(objdir)
+            verify_no_scratch(objdir, "video.o", "restore_u8_kernel", "paste-back")
     return out
 
 
@@ -123,10 +124,11 @@ def verify_isa(objdir=None):
                                            else "no gfx950 code object found"))
 
 
-def verify_no_scratch(objdir=None, obj="conv_bf16x.o", marker="ELb0ELi2ELb1EEE"):
+def verify_no_scratch(objdir=None, obj="conv_bf16x.o", marker="ELb0ELi2ELb1EEE", what="ping-pong"):
     """The ping-pong instantiations of conv_bf16x_kernel (template tail `false, 2, true`) keep 128 accumulator registers in place
     across four barriers per K-step; two ways of writing that loop made hipcc spill 414 registers or copy the kernel arguments to
-    scratch without a warning (csrc/conv_bf16x.hip, PP).  Fails the build when one of them has a private segment or a spill."""
+    scratch without a warning (csrc/conv_bf16x.hip, PP).  Fails the build when one of them has a private segment or a spill.
+    Also run over the four instantiations of restore_u8_kernel (video.o): the feathered ones hold five LDS phases in one kernel."""
     import re
     import shutil
     import tempfile
@@ -151,9 +153,9 @@ def verify_no_scratch(objdir=None, obj="conv_bf16x.o", marker="ELb0ELi2ELb1EEE")
         priv = int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", block).group(1))
         spill = int(re.search(r"\.vgpr_spill_count:\s+(\d+)", block).group(1))
         if priv or spill:
-            raise RuntimeError("%s: %s: private segment %d bytes, %d spilled VGPRs in a ping-pong kernel" % (obj, name.group(1)[:70], priv, spill))
+            raise RuntimeError("%s: %s: private segment %d bytes, %d spilled VGPRs in a %s kernel" % (obj, name.group(1)[:70], priv, spill, what))
     if not found:
-        raise RuntimeError("verify_no_scratch: no ping-pong instantiation found in %s (mangled-name marker changed?)" % obj)
+        raise RuntimeError("verify_no_scratch: no %s instantiation found in %s (mangled-name marker changed?)" % (what, obj))
     return found
 
 

@@ -294,13 +294,16 @@ struct RestoreTouch { int tl, tu, Tw, Th; };
 
 __device__ __forceinline__ float blend_half(float a, float v, bool is_first) { return is_first ? v : a * 0.5f + v * 0.5f; }
 
-template <bool STAGED, bool BLEND>
+// FEATHER (radius R >= 1): s_c holds c(p) of every tile pixel (0 outside the box) in place of the mask bits; the vertical pass
+// runs where c > 0 and its value `up` is ramped into src:  (c up + (n - c) src + n / 2) / n,  n = nx ny from the window's extent
+// clipped to the box.  c == n (every pixel of the pasted mask) keeps `up` itself.
+template <bool STAGED, bool BLEND, bool FEATHER>
 __device__ __forceinline__ void restore_vpass(const unsigned char* __restrict__ lo_l, const unsigned char* __restrict__ src,
                                               unsigned char* __restrict__ out, float* __restrict__ accum, bool is_first, RestoreTouch t,
-                                              const unsigned char* s_m, const unsigned char* s_h,
+                                              const unsigned char* s_m, const unsigned short* s_c, int R, const unsigned char* s_h,
                                               int r0, long long frame_off, int h, int w, int W, int x0, int y0, int nb, int th,
-                                              int left, int upper, int Bh, const int* __restrict__ bx, const int* __restrict__ cx, int kx,
-                                              const int* __restrict__ by, const int* __restrict__ cy, int ky) {
+                                              int left, int upper, int Bw, int Bh, const int* __restrict__ bx, const int* __restrict__ cx,
+                                              int kx, const int* __restrict__ by, const int* __restrict__ cy, int ky) {
     for (int u = threadIdx.x; u < th * (RT_WB / 4); u += NTH) {
         const int ty = u / (RT_WB / 4), xc0 = (u - ty * (RT_WB / 4)) * 4;
         if (xc0 >= nb) continue;
@@ -321,10 +324,16 @@ __device__ __forceinline__ void restore_vpass(const unsigned char* __restrict__ 
         int fy = 0, ny = 0;
         if (inside) clipped_taps(by, iy, h, ky, fy, ny);
         const int* kyp = cy + (long long)iy * ky;
+        const int wy = FEATHER ? (iy + R < Bh - 1 ? iy + R : Bh - 1) - (iy > R ? iy - R : 0) + 1 : 0;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int xc = xc0 + k, x = xc / 3, c = xc - 3 * x;
-            if (k >= n4 || !s_m[ty * RT_W + x]) continue;
+            int cnt = 0;
+            if constexpr (FEATHER) {
+                if (k >= n4 || !(cnt = s_c[ty * RT_W + x])) continue;
+            } else {
+                if (k >= n4 || !s_m[ty * RT_W + x]) continue;
+            }
             int acc = 1 << 21;
 #pragma unroll 1
             for (int j = 0; j < ny; ++j) {
@@ -333,7 +342,14 @@ __device__ __forceinline__ void restore_vpass(const unsigned char* __restrict__ 
                                       : restore_hpass_global(lo_l + (long long)r * w * 3, w, bx, cx, kx, x0 + x - left, c);
                 acc += hv * kyp[j];
             }
-            v[k] = pillow_clip8(acc);
+            if constexpr (FEATHER) {
+                const int ix = x0 + x - left;                      // c > 0 only inside the box
+                const int n = wy * ((ix + R < Bw - 1 ? ix + R : Bw - 1) - (ix > R ? ix - R : 0) + 1);
+                const int up = pillow_clip8(acc);
+                v[k] = cnt >= n ? (unsigned char)up : (unsigned char)((cnt * up + (n - cnt) * (int)v[k] + n / 2) / n);
+            } else {
+                v[k] = pillow_clip8(acc);
+            }
         }
         if constexpr (BLEND) {
             if (y < t.tu || y - t.tu >= t.Th) continue;
@@ -363,41 +379,159 @@ __device__ __forceinline__ void restore_vpass(const unsigned char* __restrict__ 
     }
 }
 
-template <bool BLEND>
+// The feathered paste (inpaint_video(feather=R), 1 <= R <= RF_MAX): inside the box, in box-relative pixels and with everything
+// outside the box counting as 0,
+//   M = NEAREST(mask),  D = M dilated by the (2R+1)^2 square,  c(p) = #{q in the box : |q - p| <= R, D(q)},  n(p) = #{q in the box :
+//   |q - p| <= R},   out = (c BICUBIC(lo) + (n - c) src + n / 2) / n;      out = src outside the box.
+// c is non-zero only within 2R of a pasted pixel, so a tile is a copied tile unless M has a pixel within 2R of it.  The NEAREST
+// tables are monotone: the tile and its 2R halo, clipped to the box, read one rectangle of the low-resolution mask,
+// ytab[first] .. ytab[last] x xtab[first] .. xtab[last].  That rectangle is staged in LDS and ORed for the block-uniform decision (for
+// a shrinking axis the rectangle holds pixels no output reads: such a tile blends, finds c == 0 and writes src); only a tile that
+// goes on expands it to M at source resolution -- and not even that when the rectangle holds nothing but hole pixels: c = n on the
+// whole tile then.  A rectangle beyond the LDS buffer (an axis that shrinks, or keeps its size at a
+// large R) is not staged: M is gathered through the tables straight away and ORed itself -- a bounded cost for any tables.
+// Then four separable passes of sliding window sums over 2R + 1 entries, LDS -> LDS with a barrier after each:
+//   M [RT_H + 4R][RT_W + 4R] -rows, > 0-> [RT_H + 4R][RT_W + 2R] -columns, > 0, inside the box-> D [RT_H + 2R][RT_W + 2R]
+//   -rows-> [RT_H + 2R][RT_W] -columns, inside the box-> c [RT_H][RT_W] (uint16: c <= 33^2),
+// in two buffers that afterwards hold the lo patch and its horizontal pass.
+constexpr int RF_MAX = 16;                                       // video.FEATHER_MAX
+constexpr int RF_W2 = RT_W + 4 * RF_MAX, RF_H2 = RT_H + 4 * RF_MAX, RF_W1 = RT_W + 2 * RF_MAX;
+constexpr int RF_BUF0 = RF_H2 * RF_W2, RF_BUF1 = RF_H2 * RF_W1;
+static_assert(RF_BUF0 >= RT_PATCH && RF_BUF1 >= RT_ROWS * RT_WB, "the window buffers are reused for the lo patch and its horizontal pass");
+static_assert(RF_BUF0 % 16 == 0 && RF_BUF1 % 16 == 0, "the buffers follow each other 16-byte aligned");
+static_assert(RF_W2 <= NTH, "a thread per column of the halo");
+
+// out[line][o] = fin(in[line][o] + ... + in[line][o + 2R], line, o) for o < n_out (ROWS), or the same along the columns of `in`
+// (line = column); a thread slides the window over RF_SEG consecutive outputs of one line
+constexpr int RF_SEG = 8;
+template <bool ROWS, typename T, typename F>
+__device__ __forceinline__ void window_sums(const unsigned char* in, int ipitch, T* out, int opitch, int lines, int n_out, int R, F fin) {
+    const int nseg = (n_out + RF_SEG - 1) / RF_SEG;
+    const int istep = ROWS ? 1 : ipitch, ostep = ROWS ? 1 : opitch;
+    for (int it = threadIdx.x; it < lines * nseg; it += NTH) {
+        const int line = ROWS ? it / nseg : it % lines;
+        const int o0 = (ROWS ? it % nseg : it / lines) * RF_SEG;
+        const unsigned char* p = in + (ROWS ? line * ipitch + o0 : o0 * ipitch + line);
+        T* q = out + (ROWS ? line * opitch + o0 : o0 * opitch + line);
+        const int n = n_out - o0 < RF_SEG ? n_out - o0 : RF_SEG;
+        int s = 0;
+        for (int k = 0; k <= 2 * R; ++k) s += p[k * istep];
+        q[0] = fin(s, line, o0);
+        for (int t = 1; t < n; ++t) {
+            s += (int)p[(t + 2 * R) * istep] - (int)p[(t - 1) * istep];
+            q[t * ostep] = fin(s, line, o0 + t);
+        }
+    }
+}
+
+// the clipped NEAREST table entries of the tile's halo, W2 columns from x0 - 2R and H2 rows from y0 - 2R; -1 outside the box
+__device__ __forceinline__ void feather_tables(int* s_xt, int* s_yt, const int* __restrict__ xtab, const int* __restrict__ ytab, int x0,
+                                               int y0, int R, int left, int upper, int Bw, int Bh, int w, int h) {
+    for (int i = threadIdx.x; i < RT_W + 4 * R; i += NTH) {
+        const int ix = x0 - 2 * R + i - left;
+        int mx = -1;
+        if (ix >= 0 && ix < Bw) { mx = xtab[ix]; mx = mx < 0 ? 0 : (mx > w - 1 ? w - 1 : mx); }
+        s_xt[i] = mx;
+    }
+    for (int i = threadIdx.x; i < RT_H + 4 * R; i += NTH) {
+        const int iy = y0 - 2 * R + i - upper;
+        int my = -1;
+        if (iy >= 0 && iy < Bh) { my = ytab[iy]; my = my < 0 ? 0 : (my > h - 1 ? h - 1 : my); }
+        s_yt[i] = my;
+    }
+    __syncthreads();
+}
+
+template <bool BLEND, bool FEATHER>
 __global__ __launch_bounds__(NTH) void restore_u8_kernel(
     const unsigned char* __restrict__ lo, const unsigned char* __restrict__ mask, const unsigned char* __restrict__ src,
     unsigned char* __restrict__ out, float* __restrict__ accum, const int* __restrict__ ids, const unsigned char* __restrict__ first,
     int Lsrc, int tx0, int ty0, RestoreTouch touch, int L, int h, int w, int H, int W, int left, int upper, int Bw, int Bh,
     const int* __restrict__ ytab, const int* __restrict__ xtab, const int* __restrict__ bx, const int* __restrict__ cx, int kx,
-    const int* __restrict__ by, const int* __restrict__ cy, int ky) {
+    const int* __restrict__ by, const int* __restrict__ cy, int ky, int R) {
+    // an instantiation keeps the arrays of its own path: s_m, s_patch, s_h, or with FEATHER the window buffers, s_c and the tables
     __shared__ unsigned char s_m[RT_H * RT_W];
     __shared__ __align__(16) unsigned char s_patch[RT_PATCH];
     __shared__ __align__(16) unsigned char s_h[RT_ROWS * RT_WB];
     __shared__ int s_rng[4];
+    __shared__ __align__(16) unsigned char s_buf0[RF_BUF0];
+    __shared__ __align__(16) unsigned char s_buf1[RF_BUF1];
+    __shared__ unsigned short s_c[RT_H * RT_W];
+    __shared__ int s_xt[RF_W2], s_yt[RF_H2];
     const int tid = threadIdx.x;
     const int x0 = (tx0 + (int)blockIdx.x) * RT_W, y0 = (ty0 + (int)blockIdx.y) * RT_H;
     const int tw = W - x0 < RT_W ? W - x0 : RT_W, th = H - y0 < RT_H ? H - y0 : RT_H;
     const int nb = tw * 3;
     if (tw <= 0 || th <= 0) return;
+    // FEATHER: the tile with its 2R halo is W2 x H2 pixels from (x0 - 2R, y0 - 2R)
+    const int W2 = RT_W + 4 * R, H2 = RT_H + 4 * R, W1 = RT_W + 2 * R, H1 = RT_H + 2 * R;
+    int rx0 = 0, ry0 = 0, rw = 0, rh = 0;
+    if constexpr (FEATHER) {
+        // the rectangle of the low-resolution mask between the entries of the halo's first and last column / row inside the box
+        const int gx0 = x0 - 2 * R > left ? x0 - 2 * R : left, gx1 = (x0 + RT_W + 2 * R < left + Bw ? x0 + RT_W + 2 * R : left + Bw) - 1;
+        const int gy0 = y0 - 2 * R > upper ? y0 - 2 * R : upper, gy1 = (y0 + RT_H + 2 * R < upper + Bh ? y0 + RT_H + 2 * R : upper + Bh) - 1;
+        if (gx0 <= gx1 && gy0 <= gy1) {
+            int a = xtab[gx0 - left], b = xtab[gx1 - left];
+            a = a < 0 ? 0 : (a > w - 1 ? w - 1 : a);
+            b = b < 0 ? 0 : (b > w - 1 ? w - 1 : b);
+            rx0 = a < b ? a : b;
+            rw = (a < b ? b : a) - rx0 + 1;
+            a = ytab[gy0 - upper], b = ytab[gy1 - upper];
+            a = a < 0 ? 0 : (a > h - 1 ? h - 1 : a);
+            b = b < 0 ? 0 : (b > h - 1 ? h - 1 : b);
+            ry0 = a < b ? a : b;
+            rh = (a < b ? b : a) - ry0 + 1;
+        }
+    }
+    const bool staged = (long long)rw * rh <= RF_BUF1;     // a halo with no pixel in the box: a staged rectangle of 0 bytes
+    // a copied tile with a staged rectangle never reads the halo's table entries: they wait for the first tile that goes on
+    bool tabs = false;
+    if (FEATHER && !staged) {
+        feather_tables(s_xt, s_yt, xtab, ytab, x0, y0, R, left, upper, Bw, Bh, w, h);
+        tabs = true;
+    }
     for (int l = blockIdx.z; l < L; l += gridDim.z) {
         const int fr = BLEND ? ids[l] : l;               // the frame of src / out / accum; block-uniform
         if (BLEND && (fr < 0 || fr >= Lsrc)) continue;
         const bool is_first = BLEND ? first[l] != 0 : true;
         // the tile's mask bits through the two NEAREST tables; any hole pixel?
         const unsigned char* ml = mask + (long long)l * h * w;
-        int any = 0;
-        for (int i = tid; i < RT_H * RT_W; i += NTH) {
-            const int ty = i / RT_W, tx = i % RT_W;
-            unsigned char m = 0;
-            const int iy = y0 + ty - upper, ix = x0 + tx - left;
-            if (ty < th && tx < tw && iy >= 0 && iy < Bh && ix >= 0 && ix < Bw) {
-                int my = ytab[iy], mx = xtab[ix];
-                my = my < 0 ? 0 : (my > h - 1 ? h - 1 : my);
-                mx = mx < 0 ? 0 : (mx > w - 1 ? w - 1 : mx);
-                m = ml[(long long)my * w + mx] != 0;
+        int any = 0, all = 1;
+        if constexpr (FEATHER) {
+            // ... any hole pixel within 2R of the tile?  nothing but hole pixels?
+            if (staged) {
+                for (int i = tid; i < rw * rh; i += NTH) {
+                    const int r = i / rw;
+                    const unsigned char m = ml[(long long)(ry0 + r) * w + rx0 + (i - r * rw)] != 0;
+                    s_buf1[i] = m;
+                    any |= m;
+                    all &= m;
+                }
+            } else if (tid < W2) {                      // a thread per column of the halo
+                const int mx = s_xt[tid];
+                for (int row = 0; row < H2; ++row) {
+                    const int my = s_yt[row];
+                    const bool in = my >= 0 && mx >= 0;
+                    const unsigned char m = in ? ml[(long long)my * w + mx] != 0 : 0;
+                    s_buf0[row * W2 + tid] = m;
+                    any |= m;
+                    all &= m | !in;
+                }
             }
-            s_m[i] = m;
-            any |= m;
+        } else {
+            for (int i = tid; i < RT_H * RT_W; i += NTH) {
+                const int ty = i / RT_W, tx = i % RT_W;
+                unsigned char m = 0;
+                const int iy = y0 + ty - upper, ix = x0 + tx - left;
+                if (ty < th && tx < tw && iy >= 0 && iy < Bh && ix >= 0 && ix < Bw) {
+                    int my = ytab[iy], mx = xtab[ix];
+                    my = my < 0 ? 0 : (my > h - 1 ? h - 1 : my);
+                    mx = mx < 0 ? 0 : (mx > w - 1 ? w - 1 : mx);
+                    m = ml[(long long)my * w + mx] != 0;
+                }
+                s_m[i] = m;
+                any |= m;
+            }
         }
         any = __syncthreads_or(any);
         const long long frame_off = (long long)fr * H * W * 3;
@@ -424,6 +558,46 @@ __global__ __launch_bounds__(NTH) void restore_u8_kernel(
             }
             continue;                                   // s_m is not read on this path: the next frame may overwrite it
         }
+        if (FEATHER && __syncthreads_and(all)) {
+            // every pixel of the halo inside the box is a hole pixel, so D = 1 and c = n on the tile: no window passes
+            for (int i = tid; i < RT_H * RT_W; i += NTH) {
+                const int ix = x0 + i % RT_W - left, iy = y0 + i / RT_W - upper;
+                s_c[i] = (ix >= 0 && ix < Bw && iy >= 0 && iy < Bh) ? 0xffff : 0;
+            }
+            __syncthreads();
+        } else if constexpr (FEATHER) {
+            if (staged) {
+                if (!tabs) {
+                    feather_tables(s_xt, s_yt, xtab, ytab, x0, y0, R, left, upper, Bw, Bh, w, h);
+                    tabs = true;
+                }
+                if (tid < W2) {                         // a thread per column of the halo
+                    const int mx = s_xt[tid], rx = mx - rx0;
+                    const bool okx = mx >= 0 && rx >= 0 && rx < rw;     // tables that are not monotone may leave the rectangle: 0 then
+                    for (int row = 0; row < H2; ++row) {
+                        const int my = s_yt[row], ry = my - ry0;
+                        s_buf0[row * W2 + tid] = (okx && my >= 0 && ry >= 0 && ry < rh) ? s_buf1[ry * rw + rx] : 0;
+                    }
+                }
+                __syncthreads();
+            }
+            window_sums<true>(s_buf0, W2, s_buf1, W1, H2, W1, R, [](int s, int, int) { return (unsigned char)(s > 0); });
+            __syncthreads();
+            window_sums<false>(s_buf1, W1, s_buf0, W1, W1, H1, R, [=](int s, int col, int row) {
+                const int ix = x0 - R + col - left, iy = y0 - R + row - upper;
+                return (unsigned char)(s > 0 && ix >= 0 && ix < Bw && iy >= 0 && iy < Bh);
+            });
+            __syncthreads();
+            window_sums<true>(s_buf0, W1, s_buf1, RT_W, H1, RT_W, R, [](int s, int, int) { return (unsigned char)s; });
+            __syncthreads();
+            window_sums<false>(s_buf1, RT_W, s_c, RT_W, RT_W, RT_H, R, [=](int s, int col, int row) {
+                const int ix = x0 + col - left, iy = y0 + row - upper;
+                return (unsigned short)((ix >= 0 && ix < Bw && iy >= 0 && iy < Bh) ? s : 0);
+            });
+            __syncthreads();                            // the two buffers are free: the lo patch and its horizontal pass go there
+        }
+        unsigned char* const s_patch_ = FEATHER ? s_buf0 : s_patch;
+        unsigned char* const s_h_ = FEATHER ? s_buf1 : s_h;
         // rows [r0, r1) and columns [c0, c1) of lo that the tile's taps reach
         if (tid < 4) s_rng[tid] = (tid & 1) ? 0 : 0x7fffffff;
         __syncthreads();
@@ -447,7 +621,7 @@ __global__ __launch_bounds__(NTH) void restore_u8_kernel(
             const int pb = pc * 3;
             for (int i = tid; i < pr * pb; i += NTH) {
                 const int r = i / pb;
-                s_patch[i] = lo_l[((long long)(r0 + r) * w + c0) * 3 + (i - r * pb)];
+                s_patch_[i] = lo_l[((long long)(r0 + r) * w + c0) * 3 + (i - r * pb)];
             }
             __syncthreads();
             for (int i = tid; i < pr * nb; i += NTH) {
@@ -457,16 +631,18 @@ __global__ __launch_bounds__(NTH) void restore_u8_kernel(
                 int f, n;
                 clipped_taps(bx, ix, w, kx, f, n);
                 const int* k = cx + (long long)ix * kx;
-                const unsigned char* p = s_patch + r * pb + (f - c0) * 3 + c;        // n > 0 implies c0 <= f, f + n <= c0 + pc
+                const unsigned char* p = s_patch_ + r * pb + (f - c0) * 3 + c;        // n > 0 implies c0 <= f, f + n <= c0 + pc
                 int acc = 1 << 21;
 #pragma unroll 1
                 for (int j = 0; j < n; ++j) acc += (int)p[3 * j] * k[j];
-                s_h[r * RT_WB + xc] = pillow_clip8(acc);
+                s_h_[r * RT_WB + xc] = pillow_clip8(acc);
             }
             __syncthreads();
-            restore_vpass<true, BLEND>(lo_l, src, out, accum, is_first, touch, s_m, s_h, r0, frame_off, h, w, W, x0, y0, nb, th, left, upper, Bh, bx, cx, kx, by, cy, ky);
+            restore_vpass<true, BLEND, FEATHER>(lo_l, src, out, accum, is_first, touch, s_m, s_c, R, s_h_, r0, frame_off, h, w, W, x0, y0, nb, th,
+                                                left, upper, Bw, Bh, bx, cx, kx, by, cy, ky);
         } else {
-            restore_vpass<false, BLEND>(lo_l, src, out, accum, is_first, touch, s_m, s_h, r0, frame_off, h, w, W, x0, y0, nb, th, left, upper, Bh, bx, cx, kx, by, cy, ky);
+            restore_vpass<false, BLEND, FEATHER>(lo_l, src, out, accum, is_first, touch, s_m, s_c, R, s_h_, r0, frame_off, h, w, W, x0, y0, nb, th,
+                                                 left, upper, Bw, Bh, bx, cx, kx, by, cy, ky);
         }
         __syncthreads();                                // s_m, s_h are rewritten for the next frame
     }
@@ -563,10 +739,11 @@ inline bool ranges_overlap(const void* a, long long na, const void* b, long long
 
 }  // namespace
 
-extern "C" int e2fgvi_restore_box_u8(const uint8_t* lo, const uint8_t* mask_lo, const uint8_t* src, uint8_t* out, int32_t L, int32_t h,
-                                     int32_t w, int32_t H, int32_t W, int32_t left, int32_t upper, int32_t Bw, int32_t Bh,
-                                     const int32_t* ytab, const int32_t* xtab, const int32_t* bounds_x, const int32_t* coeffs_x,
-                                     int32_t ksize_x, const int32_t* bounds_y, const int32_t* coeffs_y, int32_t ksize_y, void* stream) {
+// e2fgvi_restore_box_u8 (feather == 0) and e2fgvi_restore_feather_u8: the same checks, the kernel of their paste
+static int restore_box(const uint8_t* lo, const uint8_t* mask_lo, const uint8_t* src, uint8_t* out, int32_t L, int32_t h, int32_t w,
+                       int32_t H, int32_t W, int32_t left, int32_t upper, int32_t Bw, int32_t Bh, const int32_t* ytab,
+                       const int32_t* xtab, const int32_t* bounds_x, const int32_t* coeffs_x, int32_t ksize_x, const int32_t* bounds_y,
+                       const int32_t* coeffs_y, int32_t ksize_y, int32_t feather, void* stream) {
     E2_REQUIRE(lo && mask_lo && src && out && ytab && xtab && bounds_x && coeffs_x && bounds_y && coeffs_y, E2FGVI_EINVAL,
                "restore_u8: null pointer");
     E2_REQUIRE(L > 0 && h > 0 && w > 0 && H > 0 && W > 0 && ksize_x >= 1 && ksize_y >= 1, E2FGVI_EINVAL,
@@ -581,19 +758,42 @@ extern "C" int e2fgvi_restore_box_u8(const uint8_t* lo, const uint8_t* mask_lo, 
                E2FGVI_EINVAL, "restore_u8: out must not overlap src, lo or mask_lo");
     const dim3 grid((unsigned)((W + RT_W - 1) / RT_W), (unsigned)((H + RT_H - 1) / RT_H), (unsigned)(L < 1024 ? L : 1024));
     const RestoreTouch touch{0, 0, W, H};
-    hipLaunchKernelGGL(restore_u8_kernel<false>, grid, dim3(NTH), 0, (hipStream_t)stream, lo, mask_lo, src, out, (float*)nullptr,
-                       (const int*)nullptr, (const unsigned char*)nullptr, L, 0, 0, touch, L, h, w, H, W, left, upper,
-                       Bw, Bh, ytab, xtab, bounds_x, coeffs_x, ksize_x, bounds_y, coeffs_y, ksize_y);
+    if (feather)
+        hipLaunchKernelGGL((restore_u8_kernel<false, true>), grid, dim3(NTH), 0, (hipStream_t)stream, lo, mask_lo, src, out, (float*)nullptr,
+                           (const int*)nullptr, (const unsigned char*)nullptr, L, 0, 0, touch, L, h, w, H, W, left, upper,
+                           Bw, Bh, ytab, xtab, bounds_x, coeffs_x, ksize_x, bounds_y, coeffs_y, ksize_y, feather);
+    else
+        hipLaunchKernelGGL((restore_u8_kernel<false, false>), grid, dim3(NTH), 0, (hipStream_t)stream, lo, mask_lo, src, out, (float*)nullptr,
+                           (const int*)nullptr, (const unsigned char*)nullptr, L, 0, 0, touch, L, h, w, H, W, left, upper,
+                           Bw, Bh, ytab, xtab, bounds_x, coeffs_x, ksize_x, bounds_y, coeffs_y, ksize_y, 0);
     E2_LAUNCH_CHECK("restore_u8");
     return 0;
 }
 
-extern "C" int e2fgvi_restore_blend(const uint8_t* lo, const uint8_t* mask_lo, const uint8_t* src, const int32_t* ids,
-                                    const uint8_t* first, float* acc, int32_t n, int32_t L, int32_t h, int32_t w, int32_t H, int32_t W,
-                                    int32_t left, int32_t upper, int32_t Bw, int32_t Bh, int32_t touch_left, int32_t touch_upper,
-                                    int32_t Tw, int32_t Th, const int32_t* ytab, const int32_t* xtab, const int32_t* bounds_x,
-                                    const int32_t* coeffs_x, int32_t ksize_x, const int32_t* bounds_y, const int32_t* coeffs_y,
-                                    int32_t ksize_y, void* stream) {
+extern "C" int e2fgvi_restore_box_u8(const uint8_t* lo, const uint8_t* mask_lo, const uint8_t* src, uint8_t* out, int32_t L, int32_t h,
+                                     int32_t w, int32_t H, int32_t W, int32_t left, int32_t upper, int32_t Bw, int32_t Bh,
+                                     const int32_t* ytab, const int32_t* xtab, const int32_t* bounds_x, const int32_t* coeffs_x,
+                                     int32_t ksize_x, const int32_t* bounds_y, const int32_t* coeffs_y, int32_t ksize_y, void* stream) {
+    return restore_box(lo, mask_lo, src, out, L, h, w, H, W, left, upper, Bw, Bh, ytab, xtab, bounds_x, coeffs_x, ksize_x, bounds_y,
+                       coeffs_y, ksize_y, 0, stream);
+}
+
+extern "C" int e2fgvi_restore_feather_u8(const uint8_t* lo, const uint8_t* mask_lo, const uint8_t* src, uint8_t* out, int32_t L,
+                                         int32_t h, int32_t w, int32_t H, int32_t W, int32_t left, int32_t upper, int32_t Bw, int32_t Bh,
+                                         const int32_t* ytab, const int32_t* xtab, const int32_t* bounds_x, const int32_t* coeffs_x,
+                                         int32_t ksize_x, const int32_t* bounds_y, const int32_t* coeffs_y, int32_t ksize_y,
+                                         int32_t feather, void* stream) {
+    E2_REQUIRE(feather >= 1 && feather <= RF_MAX, E2FGVI_EINVAL, "restore_feather_u8: feather must be in [1, %d], got %d", RF_MAX, feather);
+    return restore_box(lo, mask_lo, src, out, L, h, w, H, W, left, upper, Bw, Bh, ytab, xtab, bounds_x, coeffs_x, ksize_x, bounds_y,
+                       coeffs_y, ksize_y, feather, stream);
+}
+
+// e2fgvi_restore_blend (feather == 0) and e2fgvi_restore_feather_blend: the same checks, the kernel of their paste
+static int restore_blend(const uint8_t* lo, const uint8_t* mask_lo, const uint8_t* src, const int32_t* ids, const uint8_t* first,
+                         float* acc, int32_t n, int32_t L, int32_t h, int32_t w, int32_t H, int32_t W, int32_t left, int32_t upper,
+                         int32_t Bw, int32_t Bh, int32_t touch_left, int32_t touch_upper, int32_t Tw, int32_t Th, const int32_t* ytab,
+                         const int32_t* xtab, const int32_t* bounds_x, const int32_t* coeffs_x, int32_t ksize_x, const int32_t* bounds_y,
+                         const int32_t* coeffs_y, int32_t ksize_y, int32_t feather, void* stream) {
     E2_REQUIRE(lo && mask_lo && src && ids && first && acc && ytab && xtab && bounds_x && coeffs_x && bounds_y && coeffs_y, E2FGVI_EINVAL,
                "restore_blend: null pointer");
     E2_REQUIRE(n > 0 && L > 0 && h > 0 && w > 0 && H > 0 && W > 0 && ksize_x >= 1 && ksize_y >= 1, E2FGVI_EINVAL,
@@ -617,11 +817,38 @@ extern "C" int e2fgvi_restore_blend(const uint8_t* lo, const uint8_t* mask_lo, c
     const int tx1 = (touch_left + Tw - 1) / RT_W, ty1 = (touch_upper + Th - 1) / RT_H;
     const dim3 grid((unsigned)(tx1 - tx0 + 1), (unsigned)(ty1 - ty0 + 1), (unsigned)(n < 1024 ? n : 1024));
     const RestoreTouch touch{touch_left, touch_upper, Tw, Th};
-    hipLaunchKernelGGL(restore_u8_kernel<true>, grid, dim3(NTH), 0, (hipStream_t)stream, lo, mask_lo, src, (unsigned char*)nullptr, acc,
-                       ids, first, L, tx0, ty0, touch, n, h, w, H, W, left, upper, Bw, Bh, ytab,
-                       xtab, bounds_x, coeffs_x, ksize_x, bounds_y, coeffs_y, ksize_y);
+    if (feather)
+        hipLaunchKernelGGL((restore_u8_kernel<true, true>), grid, dim3(NTH), 0, (hipStream_t)stream, lo, mask_lo, src, (unsigned char*)nullptr,
+                           acc, ids, first, L, tx0, ty0, touch, n, h, w, H, W, left, upper, Bw, Bh, ytab,
+                           xtab, bounds_x, coeffs_x, ksize_x, bounds_y, coeffs_y, ksize_y, feather);
+    else
+        hipLaunchKernelGGL((restore_u8_kernel<true, false>), grid, dim3(NTH), 0, (hipStream_t)stream, lo, mask_lo, src, (unsigned char*)nullptr, acc,
+                           ids, first, L, tx0, ty0, touch, n, h, w, H, W, left, upper, Bw, Bh, ytab,
+                           xtab, bounds_x, coeffs_x, ksize_x, bounds_y, coeffs_y, ksize_y, 0);
     E2_LAUNCH_CHECK("restore_blend");
     return 0;
+}
+
+extern "C" int e2fgvi_restore_blend(const uint8_t* lo, const uint8_t* mask_lo, const uint8_t* src, const int32_t* ids,
+                                    const uint8_t* first, float* acc, int32_t n, int32_t L, int32_t h, int32_t w, int32_t H, int32_t W,
+                                    int32_t left, int32_t upper, int32_t Bw, int32_t Bh, int32_t touch_left, int32_t touch_upper,
+                                    int32_t Tw, int32_t Th, const int32_t* ytab, const int32_t* xtab, const int32_t* bounds_x,
+                                    const int32_t* coeffs_x, int32_t ksize_x, const int32_t* bounds_y, const int32_t* coeffs_y,
+                                    int32_t ksize_y, void* stream) {
+    return restore_blend(lo, mask_lo, src, ids, first, acc, n, L, h, w, H, W, left, upper, Bw, Bh, touch_left, touch_upper, Tw, Th, ytab,
+                         xtab, bounds_x, coeffs_x, ksize_x, bounds_y, coeffs_y, ksize_y, 0, stream);
+}
+
+extern "C" int e2fgvi_restore_feather_blend(const uint8_t* lo, const uint8_t* mask_lo, const uint8_t* src, const int32_t* ids,
+                                            const uint8_t* first, float* acc, int32_t n, int32_t L, int32_t h, int32_t w, int32_t H,
+                                            int32_t W, int32_t left, int32_t upper, int32_t Bw, int32_t Bh, int32_t touch_left,
+                                            int32_t touch_upper, int32_t Tw, int32_t Th, const int32_t* ytab, const int32_t* xtab,
+                                            const int32_t* bounds_x, const int32_t* coeffs_x, int32_t ksize_x, const int32_t* bounds_y,
+                                            const int32_t* coeffs_y, int32_t ksize_y, int32_t feather, void* stream) {
+    E2_REQUIRE(feather >= 1 && feather <= RF_MAX, E2FGVI_EINVAL, "restore_feather_blend: feather must be in [1, %d], got %d", RF_MAX,
+               feather);
+    return restore_blend(lo, mask_lo, src, ids, first, acc, n, L, h, w, H, W, left, upper, Bw, Bh, touch_left, touch_upper, Tw, Th, ytab,
+                         xtab, bounds_x, coeffs_x, ksize_x, bounds_y, coeffs_y, ksize_y, feather, stream);
 }
 
 // the whole frame as the box: the same checks, the same kernel

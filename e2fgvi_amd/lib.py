@@ -122,6 +122,10 @@ SYMBOLS = {
     "e2fgvi_resample_ids_u8": (C.c_int, [_fp, _i32, _fp, _i32, _fp, _i32, _i32, _i32, _i32, _fp, _fp, _i32, _fp]),
     "e2fgvi_resample_rows_ids_u8": (C.c_int, [_fp, _i32, _fp, _i32, _fp, _i32, _i32, _i32, _i32, _i32, _fp, _fp, _i32, _fp]),
     "e2fgvi_restore_blend": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp] + [_i32] * 14 + [_fp, _fp, _fp, _fp, _i32, _fp, _fp, _i32, _fp]),
+    "e2fgvi_restore_feather_u8": (C.c_int, [_fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _fp, _fp, _fp, _fp,
+                                            _i32, _fp, _fp, _i32, _i32, _fp]),
+    "e2fgvi_restore_feather_blend": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp] + [_i32] * 14 + [_fp, _fp, _fp, _fp, _i32, _fp, _fp, _i32,
+                                                                                             _i32, _fp]),
     "e2fgvi_u8_to_float": (C.c_int, [_fp, _fp, _i64, _fp]),
     "e2fgvi_float_to_u8": (C.c_int, [_fp, _fp, _i64, _fp]),
     "e2fgvi_pred_to_u8": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, _fp]),

@@ -8,6 +8,7 @@ and raises on error -- there is no eager fallback.
 import collections
 import ctypes as C
 import math
+import numbers
 import os
 
 import torch
@@ -1727,7 +1728,17 @@ def _restore_geometry(lo, mask_lo, src, tabs, n, box):
     return h, w, FH, FW, left, upper, W, H
 
 
-def restore_blend(lo, mask_lo, src, ids, first, acc, ytab, xtab, bx, cx, by, cy, box=None, touch=None):
+FEATHER_MAX = 16       # csrc/video.hip RF_MAX: the largest radius the feathered paste keeps in LDS
+
+
+def _feather(feather):
+    """the radius as an int: an integer in [0, FEATHER_MAX], ValueError otherwise"""
+    if isinstance(feather, bool) or not isinstance(feather, numbers.Integral) or not 0 <= feather <= FEATHER_MAX:
+        raise ValueError("feather must be an integer in [0, %d], got %r" % (FEATHER_MAX, feather))
+    return int(feather)
+
+
+def restore_blend(lo, mask_lo, src, ids, first, acc, ytab, xtab, bx, cx, by, cy, box=None, touch=None, feather=0):
     """restore_u8 for the n frames of one window, blended into a source-size accumulator (csrc/video.hip, the BLEND epilogue of
     restore_u8_kernel): lo [n,h,w,3] / mask_lo [n,h,w] uint8, src [L,H,W,3] uint8, ids int32 [n] (frame i of lo belongs to frame
     ids[i] of src and acc; an id outside [0, L) is skipped), first uint8 [n], acc fp32 [L,H,W,3], updated in place:
@@ -1735,7 +1746,9 @@ def restore_blend(lo, mask_lo, src, ids, first, acc, ytab, xtab, bx, cx, by, cy,
     inside ``box`` (None: the whole frame); the tables are restore_u8's.  Nothing outside the box is read or written and only its
     tiles are launched.  ``touch`` = (left, upper, right, lower), a rectangle inside the frame that contains the box: the update
     covers it instead -- img is src between the box and its rim -- for a frame whose acc may differ from src there (an earlier
-    window with another box).  acc must not overlap an input.  Returns acc."""
+    window with another box).  ``feather`` = r in [1, FEATHER_MAX]: img is what restore_u8(feather=r) writes (the FEATHER form of the
+    kernel); 0 is the hard edge.  acc must not overlap an input.  Returns acc."""
+    feather = _feather(feather)
     lib = _L.load()
     _u8(lo, "lo"); _u8(mask_lo, "mask_lo"); _u8(src, "src"); _chk(ids, "ids", torch.int32); _u8(first, "first"); _chk(acc, "acc")
     tabs = (("ytab", ytab), ("xtab", xtab), ("bx", bx), ("cx", cx), ("by", by), ("cy", cy))
@@ -1756,19 +1769,29 @@ def restore_blend(lo, mask_lo, src, ids, first, acc, ytab, xtab, bx, cx, by, cy,
         if not (0 <= tl <= left and left + Bw <= tr <= FW and 0 <= tu <= upper and upper + Bh <= tb <= FH):
             raise ValueError("touch %r must lie inside the %d x %d frame and contain the box" % (tuple(touch), FW, FH))
         Tw, Th = tr - tl, tb - tu
-    _L.check(lib.e2fgvi_restore_blend(_ptr(lo), _ptr(mask_lo), _ptr(src), _ptr(ids), _ptr(first), _ptr(acc), n, src.shape[0], h, w, FH,
-                                      FW, left, upper, Bw, Bh, tl, tu, Tw, Th, _ptr(ytab), _ptr(xtab), _ptr(bx), _ptr(cx), cx.shape[1],
-                                      _ptr(by), _ptr(cy), cy.shape[1], _stream()), "restore_blend")
+    args = (_ptr(lo), _ptr(mask_lo), _ptr(src), _ptr(ids), _ptr(first), _ptr(acc), n, src.shape[0], h, w, FH, FW, left, upper, Bw, Bh,
+            tl, tu, Tw, Th, _ptr(ytab), _ptr(xtab), _ptr(bx), _ptr(cx), cx.shape[1], _ptr(by), _ptr(cy), cy.shape[1])
+    if feather:
+        _L.check(lib.e2fgvi_restore_feather_blend(*args, feather, _stream()), "restore_feather_blend")
+    else:
+        _L.check(lib.e2fgvi_restore_blend(*args, _stream()), "restore_blend")
     return acc
 
 
-def restore_u8(lo, mask_lo, src, ytab, xtab, bx, cx, by, cy, out=None, box=None):
+def restore_u8(lo, mask_lo, src, ytab, xtab, bx, cx, by, cy, out=None, box=None, feather=0):
     """out = where(NEAREST(mask_lo) != 0, BICUBIC(lo), src) at the size of src, one fused launch (csrc/video.hip): lo [L,h,w,3]
     finished frames, mask_lo [L,h,w] of 0 / 1, src [L,H,W,3], all uint8; ytab int32 [H] / xtab int32 [W] from video.nearest_table;
     bx int32 [W,2], cx int32 [W,kx] and by int32 [H,2], cy int32 [H,ky] from video.bicubic_tables, or the one-tap identity for an
     axis that keeps its size.  Returns a fresh uint8 [L,H,W,3] unless `out` is given; out must not overlap the inputs.
     ``box`` = (left, upper, right, lower) inside the frame confines the paste to that box: out is src outside it, the tables are
-    those of a resize to the box's size (right - left, lower - upper) and index box-relative pixels."""
+    those of a resize to the box's size (right - left, lower - upper) and index box-relative pixels.
+    ``feather`` = r in [1, FEATHER_MAX] ramps the pasted edge into src over r pixels, in the same launch (the FEATHER form of the
+    kernel), in integers: with M = NEAREST(mask_lo) != 0 and up = BICUBIC(lo) inside the box, everything outside it counting as 0,
+        D = M dilated by the (2r+1) x (2r+1) square,  c(p) = number of q in the box with |q - p| <= r (Chebyshev) and D(q),
+        n(p) = number of q in the box with |q - p| <= r,     out = (c * up + (n - c) * src + n // 2) // n.
+    Every pixel of M has c = n and gets up itself, every pixel farther than 2r from M is src, and the ramp is cut at the box's
+    edge.  0 is the hard edge above; anything else raises ValueError."""
+    feather = _feather(feather)
     lib = _L.load()
     _u8(lo, "lo"); _u8(mask_lo, "mask_lo"); _u8(src, "src")
     tabs = (("ytab", ytab), ("xtab", xtab), ("bx", bx), ("cx", cx), ("by", by), ("cy", cy))
@@ -1784,7 +1807,11 @@ def restore_u8(lo, mask_lo, src, ytab, xtab, bx, cx, by, cy, out=None, box=None)
         _u8(out, "out")
         if tuple(out.shape) != (L, FH, FW, 3) or out.device != src.device:
             raise ValueError("out must be uint8 %s on the device of src" % ((L, FH, FW, 3),))
-    if box is None:
+    if feather:
+        _L.check(lib.e2fgvi_restore_feather_u8(_ptr(lo), _ptr(mask_lo), _ptr(src), _ptr(out), L, h, w, FH, FW, left, upper, W, H,
+                                               _ptr(ytab), _ptr(xtab), _ptr(bx), _ptr(cx), cx.shape[1], _ptr(by), _ptr(cy), cy.shape[1],
+                                               feather, _stream()), "restore_feather_u8")
+    elif box is None:
         _L.check(lib.e2fgvi_restore_u8(_ptr(lo), _ptr(mask_lo), _ptr(src), _ptr(out), L, h, w, H, W, _ptr(ytab), _ptr(xtab), _ptr(bx),
                                        _ptr(cx), cx.shape[1], _ptr(by), _ptr(cy), cy.shape[1], _stream()), "restore_u8")
     else:

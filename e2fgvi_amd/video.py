@@ -194,6 +194,7 @@ def bicubic_tables(n_in, n_out, box=None):
     return bounds, coeffs
 
 
+FEATHER_MAX = ops.FEATHER_MAX      # the largest feather= radius (source pixels) of restore_frames / inpaint_video
 REGION_GUARD = 8       # model pixels kept free on every side of the hole: the 4-pixel cross dilation and a few rows of context
 
 
@@ -420,7 +421,18 @@ def _axis_tables(n_in, n_out, box=None):
     return bicubic_tables(n_in, n_out, box)
 
 
-def restore_frames(lo_u8, masks01_lo, src_u8, device=None, box=None):
+def _check_feather(feather):
+    """feather= as an int: an integer in [0, FEATHER_MAX]; ValueError otherwise"""
+    try:
+        ok = not isinstance(feather, bool) and int(feather) == feather and 0 <= feather <= FEATHER_MAX
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("feather must be an integer in [0, %d] (source pixels), got %r" % (FEATHER_MAX, feather))
+    return int(feather)
+
+
+def restore_frames(lo_u8, masks01_lo, src_u8, device=None, box=None, feather=0):
     """The finished frames back at the size of the caller's video: every frame of ``lo_u8`` (uint8 [L,h,w,3], what
     inpaint_video(size=...) returns) is upscaled like PIL ``Image.resize((W, H))`` (BICUBIC) and pasted into ``src_u8`` (uint8
     [L,H,W,3]) where the mask the model saw -- ``masks01_lo`` uint8 [L,h,w] of 0 / 1, prepare_masks's output -- is set after PIL's
@@ -431,7 +443,20 @@ def restore_frames(lo_u8, masks01_lo, src_u8, device=None, box=None):
 
     ``box`` = (left, upper, right, lower) inside the frame (ValueError otherwise) -- the region inpaint_video(region=...) cut out:
     the result is src everywhere outside the box and, inside it, the same three PIL lines applied to the sub-image
-    src[upper:lower, left:right] with the box's size (right - left, lower - upper) for (W, H).  None is the whole frame."""
+    src[upper:lower, left:right] with the box's size (right - left, lower - upper) for (W, H).  None is the whole frame.
+
+    ``feather`` = r, an integer in [0, FEATHER_MAX] (ValueError otherwise): the hard edge of the paste becomes a ramp of r source
+    pixels on either side of the pasted mask's contour, in the same launch and in integers.  With up and M the upscaled frame and
+    mask above, in box-relative pixels and with everything outside the box counting as 0:
+        D(p) = 1 iff some q with |q - p| <= r (Chebyshev) has M(q) = 1          -- M dilated by the (2r+1) x (2r+1) square
+        c(p) = the number of q in the box with |q - p| <= r and D(q) = 1
+        n(p) = the number of q in the box with |q - p| <= r                     -- (2r+1)^2 away from the box's edges
+        out  = (c * up + (n - c) * src + n // 2) // n per byte inside the box, src outside it.
+    Three guarantees follow: every pixel of M has c = n and gets exactly up -- no share of the source, so what was removed cannot
+    bleed back; every pixel farther than 2r from M is the byte of src; the ramp is cut at the box's edge (a planned box keeps
+    REGION_GUARD model pixels around the hole, so it cuts the ramp only where the frame ends).  r = 0 is the hard edge.  For the
+    ramp to hold the model's own prediction around the hole, lo should hold it there (inpaint_video(feather=) keeps it)."""
+    feather = _check_feather(feather)
     up = lambda a: _upload(a, device)
     for name, a, nd in (("lo", lo_u8, 4), ("masks", masks01_lo, 3), ("src", src_u8, 4)):
         shape = tuple(a.shape)
@@ -450,7 +475,7 @@ def restore_frames(lo_u8, masks01_lo, src_u8, device=None, box=None):
     (h, w), (H, W) = lo.shape[1:3], src.shape[1:3]
     if box is not None:
         W, H = box[2] - box[0], box[3] - box[1]
-    return ops.restore_u8(lo, m, src, *_restore_tables((h, w), (H, W), src.device), box=box)
+    return ops.restore_u8(lo, m, src, *_restore_tables((h, w), (H, W), src.device), box=box, feather=feather)
 
 
 def _restore_tables(lo_hw, box_hw, device):
@@ -487,7 +512,7 @@ def prepare_masks(masks_u8, size_hw, device, dilate=True, box=None, ids=None):
 @torch.no_grad()
 def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, num_ref=-1, dilate=True,
                   device=None, pad=True, batch_windows=1, keep_float=False, in_flight=1, size=None, reuse=False, restore=False,
-                  region=None, context=0.5):
+                  region=None, context=0.5, feather=0):
     """frames_u8: uint8 [L,H,W,3]; masks_u8: [L,Hm,Wm] (non-zero = hole; resized to the frames with NEAREST like
     read_mask).  Returns uint8 [L,H,W,3] composited frames, computed like test.py:129-179.
     ``model(masked[b,t,3,H',W'], n_local) -> (pred[b*t,3,H',W'], _)`` on the device.
@@ -546,7 +571,22 @@ def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, 
     0.5 / 0.5 with what earlier windows left for that frame (test.py:175-179) -- two windows of one frame have different boxes,
     so their results meet at source size, in an fp32 [L,H,W,3] accumulator that starts as the source (ops.restore_blend).  Every
     byte outside all boxes, or outside the pasted masks, is the caller's.  One window at a time: "track" without restore=True,
-    or with reuse=True, batch_windows > 1 or in_flight > 1, raises ValueError."""
+    or with reuse=True, batch_windows > 1 or in_flight > 1, raises ValueError.
+
+    ``feather`` = r > 0 (with restore=True; an integer in [0, FEATHER_MAX], ValueError otherwise or without restore): the paste
+    ramps the result into the caller's frames over r source pixels on either side of the pasted mask's contour instead of
+    switching at it (restore_frames(feather=) has the definition: the pasted mask keeps exactly the upscaled prediction, pixels
+    farther than 2r from it are the caller's bytes, the ramp is cut at the box).  The ramp needs the model's prediction AROUND the
+    hole, which test.py:172-174 discards, so every window is composited with an all-ones mask: the blended frames hold the
+    prediction everywhere, and the bicubic taps at the hole's inner edge read the prediction too, not the resized source -- the
+    result differs from feather=0 inside the hole's rim as well as in the ring.  Costs the all-ones mask, L h w bytes (n h w for
+    "track"); the fp32 [L,h,w,3] buffer of 12 L h w bytes is the one the windows are blended in either way.  Every driver
+    (sequential, in_flight, batch_windows, reuse, "track") blends in the same window order.  0 takes the path of a call without
+    the argument and allocates nothing."""
+    feather = _check_feather(feather)
+    if feather and not restore:
+        raise ValueError("feather= ramps the paste-back of restore=True into the source frames: without restore there is no seam "
+                         "to feather")
     box = None
     track = False
     if region is not None:
@@ -599,7 +639,7 @@ def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, 
     masks_d = _upload(masks_u8, device)                 # once: the bounding box and the mask preparation read the same tensor
     if track:
         return _inpaint_track(model, source, masks_d, tuple(int(v) for v in size),
-                              plan_windows(source.shape[0], neighbor_stride, ref_length, num_ref), dilate, pad, context)
+                              plan_windows(source.shape[0], neighbor_stride, ref_length, num_ref), dilate, pad, context, feather)
     mask_box = None
     if region is not None:
         frame_wh = (source.shape[2], source.shape[1])
@@ -625,6 +665,8 @@ def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, 
         for j in nb:
             seen[j] = True
     comp = torch.empty((L, h, w, 3), dtype=torch.float32, device=device)
+    # feather: the prediction is kept everywhere (test.py:172-174 with a mask of ones), the paste decides what of it is used
+    comp_masks = torch.ones_like(masks01) if feather else masks01
 
     def predict(group):
         x = torch.cat([ops.masked_clip(frames_d, masks01, ids_dev[i], Hp, Wp) for i in group], 0) if len(group) > 1 \
@@ -636,7 +678,7 @@ def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, 
 
     def composite(i, pred):
         n = len(windows[i][0])
-        ops.composite(pred.contiguous(), ids_dev[i][:n], first_dev[i], frames_d, masks01, comp)
+        ops.composite(pred.contiguous(), ids_dev[i][:n], first_dev[i], frames_d, comp_masks, comp)
 
     if reuse:
         eng = model.engine()
@@ -729,7 +771,7 @@ def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, 
     if keep_float:
         return comp
     if restore:
-        return restore_frames(ops.float_to_u8(comp), masks01, source, box=box).cpu().numpy()
+        return restore_frames(ops.float_to_u8(comp), masks01, source, box=box, feather=feather).cpu().numpy()
     return ops.float_to_u8(comp).cpu().numpy()
 
 
@@ -747,7 +789,7 @@ def _touched(k, windows, boxes):
     return left, upper, right, lower
 
 
-def _inpaint_track(model, source, masks_d, size, windows, dilate, pad, context):
+def _inpaint_track(model, source, masks_d, size, windows, dilate, pad, context, feather=0):
     """inpaint_video(region="track") after the argument checks and the uploads: source uint8 [L,H,W,3] and masks_d uint8
     [L,Hm,Wm] on the device -> uint8 array [L,H,W,3]"""
     device = source.device
@@ -783,6 +825,7 @@ def _inpaint_track(model, source, masks_d, size, windows, dilate, pad, context):
     ones = torch.ones(n_max, dtype=torch.uint8, device=device)
     acc = ops.u8_to_float(source)
     comp = torch.empty((n_max, h, w, 3), dtype=torch.float32, device=device)
+    keep_all = torch.ones((n_max, h, w), dtype=torch.uint8, device=device) if feather else None     # feather: the prediction everywhere
     for k in run:
         n, t = len(windows[k][0]), len(windows[k][0]) + len(windows[k][1])
         rplan, (ytab, xtab), rtabs = tables[boxes[k]]
@@ -790,7 +833,7 @@ def _inpaint_track(model, source, masks_d, size, windows, dilate, pad, context):
         m01 = ops.mask_prepare(masks_d, ytab, xtab, h, w, 4 if dilate else 0, ids=ids_dev[k])
         pred, _ = model(ops.masked_clip(fr, m01, local[:t], Hp, Wp), n)
         # test.py:172-174 at the model's size: every local frame is this window's first (and only) one in comp
-        ops.composite(pred.contiguous(), local[:n], ones[:n], fr, m01, comp)
+        ops.composite(pred.contiguous(), local[:n], ones[:n], fr, keep_all if feather else m01, comp)
         ops.restore_blend(ops.float_to_u8(comp[:n]), m01[:n], source, ids_dev[k][:n], first_dev[k], acc, *rtabs, box=boxes[k],
-                          touch=touch[k])
+                          touch=touch[k], feather=feather)
     return ops.float_to_u8(acc).cpu().numpy()

@@ -121,6 +121,24 @@ int e2fgvi_restore_blend(const uint8_t* lo, const uint8_t* mask_lo, const uint8_
                          int32_t Bw, int32_t Bh, int32_t touch_left, int32_t touch_upper, int32_t Tw, int32_t Th, const int32_t* ytab,
                          const int32_t* xtab, const int32_t* bounds_x, const int32_t* coeffs_x, int32_t ksize_x,
                          const int32_t* bounds_y, const int32_t* coeffs_y, int32_t ksize_y, void* stream);
+/* The feathered paste: e2fgvi_restore_box_u8 with the edge of the pasted mask ramped into the source over `feather` = r pixels,
+ * 1 <= r <= 16 (E2FGVI_EINVAL otherwise; r = 0 is e2fgvi_restore_box_u8 itself).  In box-relative pixels, everything outside the
+ * box counting as 0, with up = BICUBIC(lo) and M = NEAREST(mask_lo) as above:
+ *   D(p) = 1 iff some q with |q - p|_inf <= r has M(q) = 1;   c(p) = #{q in the box : |q - p|_inf <= r, D(q) = 1};
+ *   n(p) = #{q in the box : |q - p|_inf <= r};   out = (c * up + (n - c) * src + n / 2) / n  per byte (integers), out = src outside.
+ * A pixel of M has c = n and gets `up` itself; a pixel farther than 2 r from M is src; the ramp is cut at the box's edge. */
+int e2fgvi_restore_feather_u8(const uint8_t* lo, const uint8_t* mask_lo, const uint8_t* src, uint8_t* out, int32_t L, int32_t h,
+                              int32_t w, int32_t H, int32_t W, int32_t left, int32_t upper, int32_t Bw, int32_t Bh,
+                              const int32_t* ytab, const int32_t* xtab, const int32_t* bounds_x, const int32_t* coeffs_x,
+                              int32_t ksize_x, const int32_t* bounds_y, const int32_t* coeffs_y, int32_t ksize_y, int32_t feather,
+                              void* stream);
+/* e2fgvi_restore_blend with img = the frame e2fgvi_restore_feather_u8 would write; the same checks plus 1 <= feather <= 16 */
+int e2fgvi_restore_feather_blend(const uint8_t* lo, const uint8_t* mask_lo, const uint8_t* src, const int32_t* ids,
+                                 const uint8_t* first, float* acc, int32_t n, int32_t L, int32_t h, int32_t w, int32_t H, int32_t W,
+                                 int32_t left, int32_t upper, int32_t Bw, int32_t Bh, int32_t touch_left, int32_t touch_upper,
+                                 int32_t Tw, int32_t Th, const int32_t* ytab, const int32_t* xtab, const int32_t* bounds_x,
+                                 const int32_t* coeffs_x, int32_t ksize_x, const int32_t* bounds_y, const int32_t* coeffs_y,
+                                 int32_t ksize_y, int32_t feather, void* stream);
 /* ndarray.astype(float32) of uint8 values: the accumulator above starts as the source frames */
 int e2fgvi_u8_to_float(const uint8_t* src, float* dst, int64_t n, void* stream);
 /* ndarray.astype(uint8) of the blended frames (truncation) */
