@@ -6,6 +6,7 @@
 // Box sums come from fp64 summed-area tables: frames are uint8-valued (or k/2^j after the 0.5/0.5 blends), so every
 // partial sum is exact in fp64 -- the only rounding is in the final SSIM arithmetic.  Reductions are two-stage with a
 // fixed order (deterministic).
+// E_warp, the flow-warping temporal error of the same result table, follows below them (warp_error_partial_kernel).
 #include "common.h"
 
 namespace {
@@ -118,7 +119,160 @@ __global__ void metrics_final_kernel(const double* __restrict__ part, double* __
 
 constexpr int PART_BLOCKS = 256;
 
+// ------------------------------------------------------------------------------------------------ E_warp
+// The flow-warping temporal error (Lai et al., ECCV 2018; occlusion test of Ruder et al. 2016), fp64 on fp32 / uint8 inputs.
+// Pair t: A = frames[t], B = frames[t+1], f = fwd[t] (t -> t+1 on frame t's grid, pixels, channel 0 = x), g = bwd[t] (t+1 -> t
+// on frame t+1's grid).  For pixel p = (x, y):
+//   q = (x + f_x(p), y + f_y(p));  inside = 0 <= q_x <= W-1 and 0 <= q_y <= H-1, decided in floating point BEFORE any conversion
+//       to an integer (a flow of 1e30, inf or nan is simply outside);
+//   bil(T, q) = 4-corner bilinear sample, corners outside the image contribute 0 (flow_warp(padding_mode='zeros'), i.e.
+//       grid_sample(align_corners=True));  g_w = bil(g, q), B_w = bil(B, q);
+//   occluded        |f + g_w|^2 > 0.01 (|f|^2 + |g_w|^2) + 0.5;
+//   motion boundary |dx f|^2 + |dy f|^2 > 0.01 |f|^2 + 0.002, dx f = f(x+1,y) - f(x,y), dy f = f(x,y+1) - f(x,y), 0 on the last
+//       column / row;
+//   M(p) = inside, not occluded, no motion boundary, valid[t](p) != 0 (if given), and f(p), the neighbours of f used above and g_w
+//       finite.  Exclusion is a select: an excluded pixel's terms are never formed and multiplied by 0 (that is how the deformable
+//       conv once produced NaN).
+//   n_t = sum M;  e_t = sum_p M(p) sum_c ((A_c - B_w,c) / 255)^2 / n_t, 0 when n_t = 0.
+// One thread per pixel, the pair on the grid's y axis; wave reduction by shuffles, block reduction through LDS, one (sum, count)
+// partial per block; a second kernel adds each pair's partials in a fixed order.  No atomics: the same bits every run.  The count
+// is an integer until the last step (a double holds it exactly: H W < 2^31).
+__device__ __forceinline__ double we_load(const float* p) { return (double)*p; }
+__device__ __forceinline__ double we_load(const uint8_t* p) { return (double)*p; }
+
+__device__ __forceinline__ unsigned block_count(unsigned v, unsigned* red) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0) red[w] = v;
+    __syncthreads();
+    unsigned s = 0;
+    if (threadIdx.x == 0)
+        for (int i = 0; i < NTH / 64; ++i) s += red[i];
+    __syncthreads();
+    return s;          // valid in thread 0
+}
+
+template <typename T>
+__global__ void __launch_bounds__(NTH)
+warp_error_partial_kernel(const T* __restrict__ frames, const float* __restrict__ fwd, const float* __restrict__ bwd,
+                          const uint8_t* __restrict__ valid, double* __restrict__ part, int H, int W, int nblk) {
+    __shared__ double red[NTH / 64];
+    __shared__ unsigned redn[NTH / 64];
+    const int t = blockIdx.y;
+    const long long HW = (long long)H * W;
+    const long long idx = (long long)blockIdx.x * NTH + threadIdx.x;
+    double err = 0.0;
+    unsigned keep = 0;
+    if (idx < HW) {
+        const int x = (int)(idx % W), y = (int)(idx / W);
+        const float* f = fwd + ((long long)t * HW + idx) * 2;
+        const double fx = (double)f[0], fy = (double)f[1];
+        bool ok = isfinite(fx) && isfinite(fy);
+        double grad = 0.0;
+        if (x + 1 < W) {
+            const double rx = (double)f[2], ry = (double)f[3];
+            ok = ok && isfinite(rx) && isfinite(ry);
+            grad += (rx - fx) * (rx - fx) + (ry - fy) * (ry - fy);
+        }
+        if (y + 1 < H) {
+            const double lx = (double)f[2 * (long long)W], ly = (double)f[2 * (long long)W + 1];
+            ok = ok && isfinite(lx) && isfinite(ly);
+            grad += (lx - fx) * (lx - fx) + (ly - fy) * (ly - fy);
+        }
+        const double ff = fx * fx + fy * fy;
+        const double qx = (double)x + fx, qy = (double)y + fy;
+        // comparisons with a NaN are false: a non-finite q is outside
+        const bool inside = qx >= 0.0 && qx <= (double)(W - 1) && qy >= 0.0 && qy <= (double)(H - 1);
+        ok = ok && inside && !(grad > 0.01 * ff + 0.002);
+        if (valid) ok = ok && valid[(long long)t * HW + idx] != 0;
+        if (ok) {
+            // 0 <= q <= size - 1 holds here, so the conversions are in range; x0 + 1 can be W (q_x = W - 1): that corner is outside
+            const int x0 = (int)floor(qx), y0 = (int)floor(qy);
+            const double wx1 = qx - (double)x0, wy1 = qy - (double)y0;
+            const double wx0 = 1.0 - wx1, wy0 = 1.0 - wy1;
+            const bool hx = x0 + 1 < W, hy = y0 + 1 < H;
+            const double w00 = wy0 * wx0, w01 = wy0 * wx1, w10 = wy1 * wx0, w11 = wy1 * wx1;
+            const long long o00 = (long long)y0 * W + x0, o01 = o00 + 1, o10 = o00 + W, o11 = o10 + 1;
+            const float* g = bwd + (long long)t * HW * 2;
+            double gx = w00 * (double)g[o00 * 2], gy = w00 * (double)g[o00 * 2 + 1];
+            if (hx) { gx += w01 * (double)g[o01 * 2]; gy += w01 * (double)g[o01 * 2 + 1]; }
+            if (hy) { gx += w10 * (double)g[o10 * 2]; gy += w10 * (double)g[o10 * 2 + 1]; }
+            if (hx && hy) { gx += w11 * (double)g[o11 * 2]; gy += w11 * (double)g[o11 * 2 + 1]; }
+            const double sx = fx + gx, sy = fy + gy;
+            ok = isfinite(gx) && isfinite(gy) && !(sx * sx + sy * sy > 0.01 * (ff + gx * gx + gy * gy) + 0.5);
+            if (ok) {
+                const T* A = frames + ((long long)t * HW + idx) * 3;
+                const T* B = frames + (long long)(t + 1) * HW * 3;
+                double e = 0.0;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    double b = w00 * we_load(B + o00 * 3 + c);
+                    if (hx) b += w01 * we_load(B + o01 * 3 + c);
+                    if (hy) b += w10 * we_load(B + o10 * 3 + c);
+                    if (hx && hy) b += w11 * we_load(B + o11 * 3 + c);
+                    const double d = (we_load(A + c) - b) / 255.0;
+                    e += d * d;
+                }
+                err = e;
+                keep = 1;
+            }
+        }
+    }
+    const double s = block_sum(err, red);
+    const unsigned n = block_count(keep, redn);
+    if (threadIdx.x == 0) {
+        part[((long long)t * 2 + 0) * nblk + blockIdx.x] = s;
+        part[((long long)t * 2 + 1) * nblk + blockIdx.x] = (double)n;
+    }
+}
+
+// one block per pair: thread i adds partials i, i + NTH, ... in order, the block adds its threads in order
+__global__ void __launch_bounds__(NTH) warp_error_final_kernel(const double* __restrict__ part, double* __restrict__ out, int nblk) {
+    __shared__ double red[NTH / 64];
+    const int t = blockIdx.x;
+    double s = 0.0, n = 0.0;
+    for (int i = threadIdx.x; i < nblk; i += NTH) {
+        s += part[((long long)t * 2 + 0) * nblk + i];
+        n += part[((long long)t * 2 + 1) * nblk + i];          // integers below 2^31: exact in any order
+    }
+    s = block_sum(s, red);
+    n = block_sum(n, red);
+    if (threadIdx.x == 0) {
+        out[2 * t + 0] = n > 0.0 ? s / n : 0.0;
+        out[2 * t + 1] = n;
+    }
+}
+
 }  // namespace
+
+extern "C" int64_t e2fgvi_warp_error_workspace(int32_t L, int32_t H, int32_t W) {
+    if (L < 2 || H <= 0 || W <= 0 || (int64_t)H * W >= 2147483647LL - NTH) {
+        e2fgvi_set_error("warp_error_workspace: bad sizes");
+        return E2FGVI_EINVAL;
+    }
+    return (int64_t)(L - 1) * 2 * (int64_t)blocks_for((long long)H * W) * 8;
+}
+
+extern "C" int e2fgvi_warp_error(const void* frames, int32_t frame_dtype, const float* fwd, const float* bwd, const uint8_t* valid,
+                                 int32_t L, int32_t H, int32_t W, void* workspace, double* out, void* stream) {
+    E2_REQUIRE(frames && fwd && bwd && workspace && out, E2FGVI_EINVAL, "warp_error: null pointer");
+    E2_REQUIRE(L >= 2 && L <= 65536, E2FGVI_EINVAL, "warp_error: needs 2 <= L <= 65536 frames, got %d", L);
+    E2_REQUIRE(H > 0 && W > 0 && (int64_t)H * W < 2147483647LL - NTH, E2FGVI_EINVAL, "warp_error: bad sizes %d x %d", H, W);
+    E2_REQUIRE(frame_dtype == E2FGVI_F32 || frame_dtype == E2FGVI_U8, E2FGVI_EINVAL, "warp_error: frames must be E2FGVI_F32 or E2FGVI_U8");
+    E2_REQUIRE(((uintptr_t)workspace & 7) == 0, E2FGVI_EINVAL, "warp_error: workspace must be 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const int nblk = (int)blocks_for((long long)H * W);
+    double* part = (double*)workspace;
+    if (frame_dtype == E2FGVI_U8)
+        hipLaunchKernelGGL(warp_error_partial_kernel<uint8_t>, dim3(nblk, L - 1, 1), dim3(NTH), 0, st, (const uint8_t*)frames, fwd, bwd,
+                           valid, part, H, W, nblk);
+    else
+        hipLaunchKernelGGL(warp_error_partial_kernel<float>, dim3(nblk, L - 1, 1), dim3(NTH), 0, st, (const float*)frames, fwd, bwd,
+                           valid, part, H, W, nblk);
+    hipLaunchKernelGGL(warp_error_final_kernel, dim3(L - 1), dim3(NTH), 0, st, part, out, nblk);
+    E2_LAUNCH_CHECK("warp_error");
+    return 0;
+}
 
 extern "C" int64_t e2fgvi_psnr_ssim_workspace(int32_t N, int32_t H, int32_t W) {
     if (N <= 0 || H <= 0 || W <= 0) { e2fgvi_set_error("psnr_ssim_workspace: bad sizes"); return E2FGVI_EINVAL; }

@@ -378,16 +378,27 @@ class Engine:
         fwd, bwd = self.pair_flows(local, self._tables[key])
         return fwd.view(b, l_t - 1, h, w, 2), bwd.view(b, l_t - 1, h, w, 2)
 
-    def pair_flows(self, frames, pairs):
+    def pair_flows(self, frames, pairs, downscale=4):
         """SPyNet on explicit pairs of a flat list of frames (the body of flows(): flow_comp.py:84-169, one pair at a time and
         independent of every other pair).  frames: [n,3,H,W] in [-1,1]; pairs: int32 device [2, 2 P] as pair_table() builds it
-        (positions into `frames`).  Returns (forward, backward) NHWC fp32 [P, h, w, 2]: the flows i -> j and j -> i of pair (i, j)."""
+        (positions into `frames`).  Returns (forward, backward) NHWC fp32 [P, h, w, 2]: the flows i -> j and j -> i of pair (i, j).
+        downscale = 4: h, w = H / 4, W / 4, the forward's flows on the 1/4 downsample (e2fgvi.py:214-219); downscale = 1: the same
+        pyramid on the frames themselves, flows [P, H, W, 2] in pixels of the frames (metrics.video_flows); anything else raises
+        ValueError."""
         ops._chk(pairs, "pairs", torch.int32)
         if pairs.dim() != 2 or pairs.shape[0] != 2 or pairs.shape[1] % 2 or pairs.shape[1] == 0:
             raise ValueError("pairs must be int32 [2, 2 P] (Engine.pair_table), got %s" % (tuple(pairs.shape),))
+        if downscale not in (1, 4):
+            raise ValueError("downscale must be 4 (the forward's 1/4-size flows) or 1 (flows at the frames' own size), got %r"
+                             % (downscale,))
         n, c, H, W = frames.shape
-        h, w = H // 4, W // 4
-        small = ops.resize_bilinear(frames, (h, w), True, src_nchw=True, out_ld=4, scale=self.half, shift=self.half)
+        if downscale == 1:
+            # a same-size resize with align_corners=True is the identity: only the layout change and [-1,1] -> [0,1] remain
+            h, w = H, W
+            small = ops.nchw_to_nhwc(frames, ld=4, scale=0.5, shift=0.5)
+        else:
+            h, w = H // 4, W // 4
+            small = ops.resize_bilinear(frames, (h, w), True, src_nchw=True, out_ld=4, scale=self.half, shift=self.half)
         w_up = w if w % 32 == 0 else 32 * (w // 32 + 1)
         h_up = h if h % 32 == 0 else 32 * (h // 32 + 1)
         pyr = [ops.resize_bilinear(small, (h_up, w_up), False, channels=3, out_ld=4, scale=self.spy_scale,

@@ -15,6 +15,7 @@ ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH, ACT_DCNPOST = 0, 1, 2, 3, 4
 DT_F32, DT_BF16 = 0, 1
 DT_BF16X3 = 2                     # fp32 tensors, MFMA operands as three bf16 pieces (mode of conv2d_x / its packers, mfma_dtype of the deformable conv)
 DT_F16 = 3                        # IEEE half: the fp16 data path
+DT_U8 = 4                         # uint8 frames (e2fgvi_warp_error only)
 
 _fp = C.c_void_p   # device pointers travel as plain addresses
 
@@ -133,6 +134,8 @@ SYMBOLS = {
     "e2fgvi_scatter_slabs": (C.c_int, [_fp, _fp, _i32, _i64, _fp, _i32, _fp]),
     "e2fgvi_psnr_ssim_workspace": (_i64, [_i32, _i32, _i32]),
     "e2fgvi_psnr_ssim": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _fp, _fp, _fp]),
+    "e2fgvi_warp_error_workspace": (_i64, [_i32, _i32, _i32]),
+    "e2fgvi_warp_error": (C.c_int, [_fp, _i32, _fp, _fp, _fp, _i32, _i32, _i32, _fp, _fp, _fp]),
     "e2fgvi_softcomp_fold": (C.c_int, [_fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _fp]),
     "e2fgvi_focal_attention_16": (C.c_int, [_fp, _fp, _fp, _i32, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _fp]),
     "e2fgvi_focal_attention_16_variant": (C.c_int, [C.c_int]),

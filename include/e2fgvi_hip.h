@@ -168,6 +168,34 @@ int64_t e2fgvi_psnr_ssim_workspace(int32_t N, int32_t H, int32_t W);
 int e2fgvi_psnr_ssim(const float* img1, const float* img2, int32_t N, int32_t H, int32_t W, int32_t win_size,
                      void* workspace, double* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * E_warp, the flow-warping temporal error of the paper's result table (SURVEY.md lines 242-243; evaluate.py:142-151 saves its
+ * frames "for evaluating warping errors"), after Lai et al., ECCV 2018, with the occlusion test of Ruder et al. 2016.
+ *   frames [L,H,W,3]  of frame_dtype: E2FGVI_F32 (finite, in [0,255]) or E2FGVI_U8
+ *   fwd    [L-1,H,W,2] fp32: fwd[t] = flow from frame t to t+1 on frame t's grid, pixels, channel 0 = x
+ *   bwd    [L-1,H,W,2] fp32: bwd[t] = flow from frame t+1 to t on frame t+1's grid
+ *   valid  [L,H,W] uint8 or NULL
+ * For pair t, A = frames[t], B = frames[t+1], f = fwd[t], g = bwd[t], all arithmetic fp64, pixel p = (x, y):
+ *   q = (x + f_x(p), y + f_y(p));  inside = 0 <= q_x <= W-1 and 0 <= q_y <= H-1 (decided in floating point, before any
+ *       conversion to an integer: a flow of 1e30 is simply outside);
+ *   bil(T, q) = the 4-corner bilinear sample, corners outside the image contribute 0 (flow_comp.py:345-383 with
+ *       padding_mode='zeros': grid_sample(align_corners=True));  g_w = bil(g, q), B_w = bil(B, q);
+ *   occluded        |f + g_w|^2 > 0.01 (|f|^2 + |g_w|^2) + 0.5;
+ *   motion boundary |dx f|^2 + |dy f|^2 > 0.01 |f|^2 + 0.002 with the forward differences dx f = f(x+1,y) - f(x,y),
+ *       dy f = f(x,y+1) - f(x,y), a difference being 0 on the last column / row;
+ *   M(p) = inside, not occluded, not on a motion boundary, valid[t](p) != 0 (when valid is given) and f(p), f at the right and
+ *       lower neighbour used above and g_w all finite -- excluded pixels are dropped by select, never multiplied by 0;
+ *   n_t = sum M,  e_t = sum_p M(p) sum_c ((A_c - B_w,c) / 255)^2 / n_t,  e_t = 0 when n_t = 0.
+ * out: float64 [L-1][2] = (e_t, n_t); the video's score is the mean of e_t over the pairs with n_t > 0.  One launch over all
+ * pairs (one thread per pixel, one (sum, count) partial per block) and one that sums each pair's partials in a fixed order: no
+ * floating-point atomics, two runs return the same bits; the counts are exact.  workspace: e2fgvi_warp_error_workspace(L,H,W)
+ * bytes, caller-owned, 8-byte aligned.  H * W < 2^31 - 256.
+ * ------------------------------------------------------------------------------------------------ */
+#define E2FGVI_U8 4          /* uint8 frames (e2fgvi_warp_error only) */
+int64_t e2fgvi_warp_error_workspace(int32_t L, int32_t H, int32_t W);
+int e2fgvi_warp_error(const void* frames, int32_t frame_dtype, const float* fwd, const float* bwd, const uint8_t* valid, int32_t L,
+                      int32_t H, int32_t W, void* workspace, double* out, void* stream);
+
 /* conv_offset post-processing of SecondOrderDeformableAlignment (feat_prop.py:38-53) fused into the conv that produces
  * it: `residual` must point to the per-pixel flows [P,4] = (u1,v1,u2,v2) with res_ld = 4, `slope` = max_residue:
  * offset channels -> slope*tanh(v) + flow.flip, mask channels (last third) -> sigmoid(v) */
