@@ -732,6 +732,118 @@ __global__ __launch_bounds__(NTH) void hole_bbox_kernel(const unsigned char* __r
     }
 }
 
+// Scene cuts (video.detect_cuts): block-histogram difference of adjacent frames, integers only.  For a pixel (x, y) of frame t with
+// bytes R, G, B:  Y = (77 R + 150 G + 29 B + 128) >> 8,  bin = Y >> 2 (64 bins),  cell = ((4 y) / H) * 4 + (4 x) / W (a 4 x 4 grid);
+// hist[t][cell][bin] counts pixels and  out[t] = sum over cell, bin of |hist[t] - hist[t + 1]|,  0 <= t < L - 1.
+// Pass 1, HBM-bound: a workgroup owns a strip of whole rows inside ONE cell row of one frame -- contiguous bytes, and only the
+// 4 x 64 counters of that cell row.  The strip is read in 48-byte chunks (16 pixels) from the first 16-byte boundary on: three
+// 16-byte loads and the dword behind them, shifted by the strip's pixel phase (the boundary falls 0, 1 or 2 bytes into a pixel;
+// 48 is a multiple of 3, so every chunk has the same phase); the pixels in front of the first chunk and behind the last one that
+// lies wholly inside the strip are read byte by byte.  Nothing outside the strip's own bytes is read, whatever the base and
+// the row pitch.  A thread merges runs of equal counters among its 16 consecutive pixels in registers (a constant frame: one LDS
+// add of 16 per chunk), and the LDS counters exist SD_REP times, picked by lane: on a smooth image the 64 lanes of an add meet
+// on one counter 64 / SD_REP at a time instead of all at once.  The strip's non-zero counters then go to the frame's table with
+// integer global atomics -- sums of integers, the same in any arrival order; the entry zeroes the table in front of the launch.
+// Pass 2: a workgroup per pair of frames sums the 1024 absolute differences.
+constexpr int SD_CELLS = 16, SD_BINS = 64, SD_TABLE = SD_CELLS * SD_BINS;      // counters per frame
+constexpr int SD_ROW = 4 * SD_BINS;                                           // counters per cell row
+constexpr int SD_REP = 8;
+constexpr int SD_STRIP = 32768;                                               // bytes a workgroup aims for
+static_assert(SD_ROW == NTH, "a thread per counter of the cell row");
+
+__device__ __forceinline__ int sd_bin(unsigned r, unsigned g, unsigned b) { return (int)((77u * r + 150u * g + 29u * b + 128u) >> 10); }
+
+// first row of cell row c: the smallest y with (4 y) / H >= c
+__host__ __device__ inline int sd_row0(int c, int H) { return (int)(((long long)c * H + 3) / 4); }
+
+struct SdRun {
+    int cur, cnt;
+    __device__ __forceinline__ void add(unsigned* s, int idx) {
+        if (idx == cur) { ++cnt; return; }
+        if (cnt) atomicAdd(s + cur * SD_REP, (unsigned)cnt);
+        cur = idx;
+        cnt = 1;
+    }
+};
+
+__global__ __launch_bounds__(NTH) void scene_hist_kernel(const unsigned char* __restrict__ frames, unsigned* __restrict__ hist, int H,
+                                                         int W, int rows_per_strip, int nstrips) {
+    __shared__ unsigned s_hist[SD_ROW * SD_REP];
+    const int tid = threadIdx.x;
+    const int cy = blockIdx.x / nstrips, strip = blockIdx.x - cy * nstrips;
+    const long long ya = (long long)sd_row0(cy, H) + (long long)strip * rows_per_strip;
+    long long yb = ya + rows_per_strip;
+    yb = yb < sd_row0(cy + 1, H) ? yb : sd_row0(cy + 1, H);
+    if (ya >= yb) return;                               // block-uniform: an empty cell row (H < 4) or a strip past its end
+    for (int i = tid; i < SD_ROW * SD_REP; i += NTH) s_hist[i] = 0;
+    __syncthreads();
+    const long long t = blockIdx.y;
+    const unsigned char* p = frames + (t * H + ya) * W * 3;
+    const unsigned npix = (unsigned)((yb - ya) * W);    // < 2^32: a strip is a single row, or at most SD_STRIP bytes and a row
+    const long long nbytes = 3LL * npix;
+    const int c1 = (int)((1LL * W + 3) / 4), c2 = (int)((2LL * W + 3) / 4), c3 = (int)((3LL * W + 3) / 4);  // first column of cell columns 1, 2, 3
+    unsigned* const mine = s_hist + (tid & (SD_REP - 1));
+    // the 48-byte chunks: from the first 16-byte boundary, as many as lie inside the strip with the dword behind them
+    const int head = (int)((16 - (int)((uintptr_t)p & 15)) & 15);
+    const int shift = (3 - head % 3) % 3;               // bytes of the chunk in front of its first whole pixel
+    const unsigned nchunks = nbytes - head >= 52 ? (unsigned)((nbytes - head - 52) / 48 + 1) : 0u;
+    const unsigned pfirst = nchunks ? (unsigned)(head + shift) / 3u : npix;    // the pixels in front of the chunks: byte by byte
+    const unsigned ptail = nchunks ? pfirst + 16u * nchunks : npix;
+    for (unsigned k = tid; k < nchunks; k += NTH) {
+        const unsigned char* q = p + head + 48LL * k;
+        const uint4 a = *reinterpret_cast<const uint4*>(q), b = *reinterpret_cast<const uint4*>(q + 16),
+                    c = *reinterpret_cast<const uint4*>(q + 32);
+        const unsigned e = *reinterpret_cast<const unsigned*>(q + 48);
+        unsigned w[13] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w, e};
+#pragma unroll
+        for (int i = 0; i < 12; ++i) w[i] = __builtin_amdgcn_alignbyte(w[i + 1], w[i], (unsigned)shift);
+        int x = (int)((pfirst + 16u * k) % (unsigned)W);
+        SdRun run{-1, 0};
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const unsigned d0 = w[3 * g], d1 = w[3 * g + 1], d2 = w[3 * g + 2];
+            const int bins[4] = {sd_bin(d0 & 255u, (d0 >> 8) & 255u, (d0 >> 16) & 255u), sd_bin(d0 >> 24, d1 & 255u, (d1 >> 8) & 255u),
+                                 sd_bin((d1 >> 16) & 255u, d1 >> 24, d2 & 255u), sd_bin((d2 >> 8) & 255u, (d2 >> 16) & 255u, d2 >> 24)};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int cx = (x >= c1) + (x >= c2) + (x >= c3);
+                run.add(mine, cx * SD_BINS + bins[j]);
+                x = x + 1 == W ? 0 : x + 1;
+            }
+        }
+        atomicAdd(mine + run.cur * SD_REP, (unsigned)run.cnt);
+    }
+    const unsigned nslow = pfirst + (npix - ptail);
+    for (unsigned i = tid; i < nslow; i += NTH) {
+        const unsigned px = i < pfirst ? i : ptail + (i - pfirst);
+        const int x = (int)(px % (unsigned)W);
+        const int cx = (x >= c1) + (x >= c2) + (x >= c3);
+        const unsigned char* q = p + 3LL * px;
+        atomicAdd(mine + (cx * SD_BINS + sd_bin(q[0], q[1], q[2])) * SD_REP, 1u);
+    }
+    __syncthreads();
+    unsigned n = 0;
+#pragma unroll
+    for (int r = 0; r < SD_REP; ++r) n += s_hist[tid * SD_REP + r];
+    if (n) atomicAdd(hist + t * SD_TABLE + cy * SD_ROW + tid, n);
+}
+
+__global__ __launch_bounds__(NTH) void scene_diff_kernel(const unsigned* __restrict__ hist, long long* __restrict__ out) {
+    __shared__ long long s_sum[NTH / 64];
+    const unsigned* a = hist + (long long)blockIdx.x * SD_TABLE;
+    const unsigned* b = a + SD_TABLE;
+    long long s = 0;
+    for (int i = threadIdx.x; i < SD_TABLE; i += NTH) s += a[i] > b[i] ? a[i] - b[i] : b[i] - a[i];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if ((threadIdx.x & 63) == 0) s_sum[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int i = 1; i < NTH / 64; ++i) s += s_sum[i];
+        out[blockIdx.x] = s;
+    }
+}
+
 inline bool ranges_overlap(const void* a, long long na, const void* b, long long nb) {
     const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
     return pa < pb + (uintptr_t)nb && pb < pa + (uintptr_t)na;
@@ -1042,5 +1154,45 @@ extern "C" int e2fgvi_pred_to_u8(const float* pred, uint8_t* dst, int32_t N, int
     hipLaunchKernelGGL(pred_to_u8_kernel, dim3(blocks_for((long long)N * H * W * 3)), dim3(NTH), 0, (hipStream_t)stream, pred, dst, N,
                        H, W, Hp, Wp);
     E2_LAUNCH_CHECK("pred_to_u8");
+    return 0;
+}
+
+extern "C" int64_t e2fgvi_scene_diff_workspace(int32_t L, int32_t H, int32_t W) {
+    if (L < 2 || H < 1 || W < 1 || (int64_t)H * W >= (1LL << 31)) {
+        e2fgvi_set_error("scene_diff_workspace: needs L >= 2 frames of H, W >= 1 with H * W < 2^31, got %d x %d x %d", L, H, W);
+        return E2FGVI_EINVAL;
+    }
+    return (int64_t)L * SD_TABLE * (int64_t)sizeof(unsigned);
+}
+
+extern "C" int e2fgvi_scene_diff(const uint8_t* frames, int32_t L, int32_t H, int32_t W, void* workspace, int64_t* out, void* stream) {
+    E2_REQUIRE(frames && workspace && out, E2FGVI_EINVAL, "scene_diff: null pointer");
+    E2_REQUIRE(L >= 2, E2FGVI_EINVAL, "scene_diff: needs at least two frames, got %d", L);
+    E2_REQUIRE(H >= 1 && W >= 1 && (int64_t)H * W < (1LL << 31), E2FGVI_EINVAL,
+               "scene_diff: frames must have H, W >= 1 and H * W < 2^31, got %d x %d", H, W);
+    E2_REQUIRE(((uintptr_t)workspace & 3) == 0 && ((uintptr_t)out & 7) == 0, E2FGVI_EINVAL,
+               "scene_diff: workspace must be 4-byte aligned and out 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    unsigned* hist = (unsigned*)workspace;
+    // the tables the atomics add to start at zero on the stream of the launch: the workspace may hold anything
+    const hipError_t e = hipMemsetAsync(hist, 0, (size_t)L * SD_TABLE * sizeof(unsigned), st);
+    E2_REQUIRE(e == hipSuccess, (int)e, "scene_diff: hipMemsetAsync failed: %s", hipGetErrorString(e));
+    // strips of about SD_STRIP bytes, at least one row, inside a cell row (at most ceil(H / 4) rows); a grid row per frame
+    long long rps = (SD_STRIP + 3LL * W - 1) / (3LL * W);
+    const long long hmax = ((long long)H + 3) / 4;
+    rps = rps < 1 ? 1 : (rps > hmax ? hmax : rps);
+    const int nstrips = (int)((hmax + rps - 1) / rps);
+    for (int l0 = 0; l0 < L; l0 += 65535) {
+        const int nl = L - l0 < 65535 ? L - l0 : 65535;
+        hipLaunchKernelGGL(scene_hist_kernel, dim3(4u * (unsigned)nstrips, (unsigned)nl), dim3(NTH), 0, st,
+                           frames + (long long)l0 * H * W * 3, hist + (long long)l0 * SD_TABLE, H, W, (int)rps, nstrips);
+        E2_LAUNCH_CHECK("scene_diff");
+    }
+    for (int l0 = 0; l0 < L - 1; l0 += 1 << 30) {
+        const int nl = L - 1 - l0 < (1 << 30) ? L - 1 - l0 : (1 << 30);
+        hipLaunchKernelGGL(scene_diff_kernel, dim3((unsigned)nl), dim3(NTH), 0, st, hist + (long long)l0 * SD_TABLE,
+                           (long long*)out + l0);
+        E2_LAUNCH_CHECK("scene_diff");
+    }
     return 0;
 }

@@ -175,23 +175,32 @@ def video_flows(model, frames_u8, chunk=4):
     return fwd, bwd
 
 
-def evaluate_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, win_size=65, warp=False, flows=None, valid=None):
+def evaluate_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, win_size=65, warp=False, flows=None, valid=None,
+                   scenes=None):
     """evaluate.py:75-125 for one video on the device: the sliding-window completion (no mask dilation, no padding --
     the dataset delivers frames at the model's size with binary masks) followed by per-frame PSNR / SSIM of the blended
     frames against the originals.  Returns (psnr[L], ssim[L]) float64 numpy arrays; their means are the video's scores.
     warp=True returns (psnr, ssim, warp): warp the [L-1, 2] float64 array of warp_error's rows (e_t, n_t) for the blended float
     frames (warp_score gives the video's E_warp; read warp_error on comparing it with the paper's column).  The flows are
     flows=(fwd, bwd) when given -- any callable model works then -- and otherwise video_flows(model, frames_u8): those of the
-    ground-truth frames, as Lai et al. take them from the unprocessed video.  valid [L,H,W] uint8 is warp_error's."""
+    ground-truth frames, as Lai et al. take them from the unprocessed video.  valid [L,H,W] uint8 is warp_error's.
+    ``scenes`` is inpaint_video's (None, a list of cuts, or "auto"): the completion is windowed per scene, and with warp=True the
+    row of every pair that straddles a cut -- (c - 1, c) for a cut c -- is set to (0, 0), so warp_score skips it: a flow between two
+    shots means nothing.  warp_error itself is unchanged."""
     from . import video
     if warp and flows is None and not callable(getattr(model, "engine", None)):
         raise TypeError("warp=True without flows= takes them from the model's SPyNet (video_flows): that needs the InpaintGenerator, "
                         "got %s" % type(model).__name__)
+    if isinstance(scenes, str) and scenes == "auto":
+        scenes = video.detect_cuts(frames_u8)           # here, so that the rows dropped below are those of the cuts used
     comp = video.inpaint_video(model, frames_u8, masks_u8, neighbor_stride, ref_length, -1, dilate=False, pad=False,
-                               keep_float=True)
+                               keep_float=True, scenes=scenes)
     ori = torch.as_tensor(np.ascontiguousarray(frames_u8)).to(comp.device).float()
     r = psnr_ssim(ori, comp, win_size).cpu().numpy()
     if not warp:
         return r[:, 0], r[:, 1]
     fwd, bwd = flows if flows is not None else video_flows(model, frames_u8)
-    return r[:, 0], r[:, 1], warp_error(comp, fwd, bwd, valid).cpu().numpy()
+    rows = warp_error(comp, fwd, bwd, valid).cpu().numpy()
+    for c in scenes or ():
+        rows[int(c) - 1] = 0.0
+    return r[:, 0], r[:, 1], rows

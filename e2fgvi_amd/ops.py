@@ -1696,6 +1696,27 @@ def hole_bbox_frames(masks_u8):
     return out
 
 
+def scene_diff(frames_u8):
+    """frames_u8 [L,H,W,3] uint8 on the device, L >= 2 -> device int64 [L-1]: the block-histogram difference of every pair of
+    adjacent frames (csrc/video.hip scene_hist_kernel / scene_diff_kernel; include/e2fgvi_hip.h has the definition), an exact
+    integer in 0 .. 2 H W.  No host read; video.scene_scores normalises it, video.cuts_from_scores turns it into cuts."""
+    lib = _L.load()
+    _u8(frames_u8, "frames")
+    if frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
+        raise ValueError("frames must be [L,H,W,3], got %s" % (tuple(frames_u8.shape),))
+    L, H, W, _ = frames_u8.shape
+    if L < 2:
+        raise ValueError("scene_diff needs at least two frames, got %d" % L)
+    nbytes = lib.e2fgvi_scene_diff_workspace(L, H, W)
+    if nbytes < 0:
+        _L.check(int(nbytes), "scene_diff_workspace")
+    with torch.cuda.device(frames_u8.device):
+        work = torch.empty(int(nbytes) // 4, dtype=torch.int32, device=frames_u8.device)
+        out = torch.empty(L - 1, dtype=torch.int64, device=frames_u8.device)
+        _L.check(lib.e2fgvi_scene_diff(_ptr(frames_u8), L, H, W, _ptr(work), _ptr(out), _stream()), "scene_diff")
+    return out
+
+
 def _restore_geometry(lo, mask_lo, src, tabs, n, box):
     """the shape checks restore_u8 and restore_blend share -> (h, w, FH, FW, left, upper, Bw, Bh); n: frames of lo / mask_lo"""
     ytab, xtab, bx, cx, by, cy = (t for _, t in tabs)

@@ -34,8 +34,36 @@ def get_ref_index(f, neighbor_ids, length, ref_length=10, num_ref=-1):
     return ref_index
 
 
-def plan_windows(length, neighbor_stride=5, ref_length=10, num_ref=-1):
-    """The (neighbour ids, reference ids) of every window of test.py:146-153, in the reference's order."""
+def _check_scenes(scenes, length):
+    """scenes= as a list: strictly increasing integers in (0, length), each the first frame of a new scene; ValueError otherwise"""
+    try:
+        vals = list(scenes)
+        ok = all(not isinstance(v, (bool, np.bool_)) and int(v) == v for v in vals)
+    except (TypeError, ValueError):
+        vals, ok = [], False
+    if not ok or any(not 0 < int(v) < length for v in vals) or any(int(b) <= int(a) for a, b in zip(vals[:-1], vals[1:])):
+        raise ValueError("scenes must be a strictly increasing list of frame numbers in (0, %d), each the first frame of a new "
+                         "scene, got %r" % (length, scenes))
+    return [int(v) for v in vals]
+
+
+def plan_windows(length, neighbor_stride=5, ref_length=10, num_ref=-1, scenes=None):
+    """The (neighbour ids, reference ids) of every window of test.py:146-153, in the reference's order.
+    ``scenes``: a strictly increasing list of frame numbers in (0, length), each the first frame of a new scene (ValueError
+    otherwise; detect_cuts finds them) -- every scene [s, e) is planned as a video of its own, plan_windows(e - s, ...) with every id
+    shifted by s, and the result is the concatenation in scene order: neither the neighbours nor the references of a window leave its
+    scene, and get_ref_index sees the scene's length.  (With num_ref != -1 test.py:47-48 can name the frame one past the end of
+    the video -- ``range(start_idx, end_idx + 1, ref_length)`` with end_idx = length -- which in a scene would be the first frame of
+    the next one: such an id is dropped from a scene's plan.  A call on the scene's frames alone could not read it either.)
+    None or [] is the one-shot plan."""
+    if scenes is not None:
+        cuts = _check_scenes(scenes, length)
+        if cuts:
+            windows = []
+            for s, e in zip([0] + cuts, cuts + [length]):
+                windows += [([j + s for j in nb], [j + s for j in rf if j < e - s])
+                            for nb, rf in plan_windows(e - s, neighbor_stride, ref_length, num_ref)]
+            return windows
     windows = []
     for f in range(0, length, neighbor_stride):
         neighbor_ids = list(range(max(0, f - neighbor_stride), min(length, f + neighbor_stride + 1)))
@@ -311,13 +339,75 @@ def _map_frame_boxes(raw, mask_wh, frame_wh):
     return [_scale_box(b, mask_wh, frame_wh) if b[2] > b[0] and b[3] > b[1] else None for b in raw]
 
 
-def track_regions(masks_u8, frame_wh, size, neighbor_stride=5, ref_length=10, num_ref=-1, context=0.5, device=None):
+def track_regions(masks_u8, frame_wh, size, neighbor_stride=5, ref_length=10, num_ref=-1, context=0.5, device=None, scenes=None):
     """The boxes inpaint_video(region="track") uses for these masks, one (left, upper, right, lower) or None per window of
     plan_windows (plan_track): masks_u8 uint8 [L,Hm,Wm], an array, or a tensor that is used where it is when on the device.  One
-    device pass over the masks and one host copy of 4 L integers, as hole_region reports the box of region="hole"."""
+    device pass over the masks and one host copy of 4 L integers, as hole_region reports the box of region="hole".
+    ``scenes``: the list of cuts inpaint_video(scenes=) is called with (plan_windows(scenes=); the masks cannot tell where the
+    frames cut, so "auto" is not accepted here: pass detect_cuts's list) -- the windows, and with them the boxes, are then the ones
+    that call uses."""
+    if scenes is not None:
+        scenes = _check_scenes(scenes, int(masks_u8.shape[0]))      # from the shapes alone, before any upload
     m = _upload(masks_u8, device)
     boxes = _frame_boxes(m, frame_wh)
-    return plan_track(boxes, plan_windows(len(boxes), neighbor_stride, ref_length, num_ref), frame_wh, size, context)
+    return plan_track(boxes, plan_windows(len(boxes), neighbor_stride, ref_length, num_ref, scenes), frame_wh, size, context)
+
+
+SCENE_THRESHOLD = 0.35     # cuts_from_scores: DESIGN.md 3j has the measurements it was chosen from
+SCENE_MIN_LENGTH = 5       # frames; one window step of the default neighbor_stride
+
+
+def scene_scores(frames_u8, device=None):
+    """How much every pair of adjacent frames differs, for finding hard cuts: frames_u8 uint8 [L,H,W,3] (an array, or a tensor that
+    is used where it is when on the device) -> float64 array [L-1] in [0, 1], scores[t] between frames t and t + 1.  Per frame the
+    device counts a 64-bin histogram of the integer luma (77 R + 150 G + 29 B + 128) >> 8 in each cell of a 4 x 4 grid over the
+    frame; scores[t] is the sum of the absolute differences of the two frames' 1024 counters over its largest value 2 H W
+    (ops.scene_diff: one pass over the frames, exact integers, and one host copy of L - 1 of them).  Motion inside a cell leaves
+    the score alone, motion across cells and changes of brightness raise it: 0 for two frames with the same counters, 1 for two
+    that share no luma bin in any cell.  L < 2 returns an empty array without a launch."""
+    if len(frames_u8.shape) != 4 or frames_u8.shape[3] != 3:
+        raise ValueError("frames must be uint8 [L,H,W,3], got %s" % (tuple(frames_u8.shape),))
+    L, H, W = (int(v) for v in frames_u8.shape[:3])
+    if L < 2:
+        return np.zeros(0, np.float64)
+    x = _upload(frames_u8, device)
+    return ops.scene_diff(x).cpu().numpy().astype(np.float64) / (2.0 * H * W)
+
+
+def _check_cut_args(threshold, min_scene):
+    if isinstance(threshold, bool) or not 0 < threshold <= 1:
+        raise ValueError("threshold must be in (0, 1], got %r" % (threshold,))
+    if isinstance(min_scene, bool) or int(min_scene) != min_scene or min_scene < 1:
+        raise ValueError("min_scene must be an integer >= 1, got %r" % (min_scene,))
+
+
+def cuts_from_scores(scores, threshold=SCENE_THRESHOLD, min_scene=SCENE_MIN_LENGTH):
+    """scene_scores's array [L-1] -> the list of cuts, each the first frame of a new scene (what plan_windows(scenes=) takes).
+    Frame t + 1 is a candidate wherever scores[t] >= threshold; the candidates are walked in increasing order and a cut c is
+    accepted when the scene it ends has at least min_scene frames (c minus the previous accepted cut, or 0) and so has what is
+    left of the video (L - c).  So of the two high scores around a one-frame flash the second is dropped (the first as well when
+    the flash is among the first min_scene frames), and no scene is shorter than min_scene -- one window step at the default.
+    threshold outside (0, 1] or min_scene < 1 raise ValueError.  Pure host code."""
+    _check_cut_args(threshold, min_scene)
+    scores = np.asarray(scores, dtype=np.float64).reshape(-1)
+    L = scores.size + 1
+    cuts, prev = [], 0
+    for t in np.nonzero(scores >= threshold)[0].tolist():
+        c = t + 1
+        if c - prev >= min_scene and L - c >= min_scene:
+            cuts.append(c)
+            prev = c
+    return cuts
+
+
+def detect_cuts(frames_u8, threshold=SCENE_THRESHOLD, min_scene=SCENE_MIN_LENGTH, device=None):
+    """The hard cuts of a video: cuts_from_scores(scene_scores(frames_u8, device), threshold, min_scene) -- a list of frame numbers,
+    each the first frame of a new scene.  The default threshold lies between what motion scores (at most 0.37 for ten frames'
+    worth of the reference's example clip in one step, 0.09 between its adjacent frames) and what unrelated frames score (0.47
+    and more).  It finds HARD cuts: a fade or a dissolve spreads its change over many pairs, none of which need reach the
+    threshold, and is not detected."""
+    _check_cut_args(threshold, min_scene)               # before any device work
+    return cuts_from_scores(scene_scores(frames_u8, device), threshold, min_scene)
 
 
 def _check_ids(ids, length):
@@ -512,7 +602,7 @@ def prepare_masks(masks_u8, size_hw, device, dilate=True, box=None, ids=None):
 @torch.no_grad()
 def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, num_ref=-1, dilate=True,
                   device=None, pad=True, batch_windows=1, keep_float=False, in_flight=1, size=None, reuse=False, restore=False,
-                  region=None, context=0.5, feather=0):
+                  region=None, context=0.5, feather=0, scenes=None):
     """frames_u8: uint8 [L,H,W,3]; masks_u8: [L,Hm,Wm] (non-zero = hole; resized to the frames with NEAREST like
     read_mask).  Returns uint8 [L,H,W,3] composited frames, computed like test.py:129-179.
     ``model(masked[b,t,3,H',W'], n_local) -> (pred[b*t,3,H',W'], _)`` on the device.
@@ -582,7 +672,22 @@ def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, 
     result differs from feather=0 inside the hole's rim as well as in the ring.  Costs the all-ones mask, L h w bytes (n h w for
     "track"); the fp32 [L,h,w,3] buffer of 12 L h w bytes is the one the windows are blended in either way.  Every driver
     (sequential, in_flight, batch_windows, reuse, "track") blends in the same window order.  0 takes the path of a call without
-    the argument and allocates nothing."""
+    the argument and allocates nothing.
+
+    ``scenes``: where the video cuts from one shot to the next.  A list of frame numbers, strictly increasing and in (0, L), each the
+    first frame of a new scene (ValueError otherwise): the windows are planned per scene (plan_windows(scenes=)), so no window mixes
+    the frames of two shots, SPyNet sees no pair across a cut, nothing is propagated over one and the transformer's reference
+    frames are those of the hole's own shot -- every scene comes out as it would from a call of its own on its frames.  "auto":
+    the list detect_cuts finds with its defaults on the caller's frames as they come in, before any ``size`` resize -- one kernel
+    pair over the frames and one host copy of L - 1 integers before the windows are planned, as region="hole" reads its box back;
+    hard cuts only, no fades or dissolves.  Every driver takes its windows from that one list (sequential, in_flight, batch_windows --
+    windows of equal shape may share a forward across scenes: clips are independent --, reuse, whose plan then holds no pair
+    across a cut, and region="track").  region="hole" still plans ONE box over the whole video, not one per scene.  None (or [])
+    is the one-shot path of a call without the argument and launches nothing."""
+    if scenes is not None and not (isinstance(scenes, str) and scenes == "auto"):
+        if isinstance(scenes, str):
+            raise ValueError('scenes must be None, "auto" or a list of frame numbers, got %r' % (scenes,))
+        scenes = _check_scenes(scenes, int(frames_u8.shape[0]))             # from the shapes alone, before any device work
     feather = _check_feather(feather)
     if feather and not restore:
         raise ValueError("feather= ramps the paste-back of restore=True into the source frames: without restore there is no seam "
@@ -637,9 +742,11 @@ def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, 
         frames_d = torch.as_tensor(np.ascontiguousarray(frames_u8)).to(device)
     source = frames_d                                   # restore=True: kept beside the resized frames, only read
     masks_d = _upload(masks_u8, device)                 # once: the bounding box and the mask preparation read the same tensor
+    if isinstance(scenes, str):                         # "auto": on the frames at source size
+        scenes = detect_cuts(source)
     if track:
         return _inpaint_track(model, source, masks_d, tuple(int(v) for v in size),
-                              plan_windows(source.shape[0], neighbor_stride, ref_length, num_ref), dilate, pad, context, feather)
+                              plan_windows(source.shape[0], neighbor_stride, ref_length, num_ref, scenes), dilate, pad, context, feather)
     mask_box = None
     if region is not None:
         frame_wh = (source.shape[2], source.shape[1])
@@ -654,7 +761,7 @@ def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, 
     L, h, w, _ = frames_d.shape
     masks01 = prepare_masks(masks_d, (h, w), device, dilate, box=mask_box)
     Hp, Wp = padded_size(h, w) if pad else (h, w)
-    windows = plan_windows(L, neighbor_stride, ref_length, num_ref)
+    windows = plan_windows(L, neighbor_stride, ref_length, num_ref, scenes)
     # every host->device upload happens here, before the first forward: frame ids of each window and the
     # "first prediction of this frame" flags of the reference's comp_frames[idx] is None test (test.py:172-176)
     ids_dev = [torch.tensor(nb + rf, dtype=torch.int32, device=device) for nb, rf in windows]

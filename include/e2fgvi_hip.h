@@ -157,6 +157,17 @@ int e2fgvi_gather_slabs(const void* cache, int32_t slots, const int32_t* ids, in
 /* the mirror: cache[ids[i]] = rows[i] -- newly encoded frames / newly computed flows into their cache slots (ids distinct) */
 int e2fgvi_scatter_slabs(const void* rows, const int32_t* ids, int32_t n, int64_t slab_bytes, void* cache, int32_t slots,
                          void* stream);
+/* Scene cuts (video.detect_cuts; test.py treats its clip as one shot): the block-histogram difference of adjacent frames, in
+ * integers only.  frames uint8 [L,H,W,3]; for frame t and pixel (x, y) with bytes R, G, B
+ *   Y = (77 R + 150 G + 29 B + 128) >> 8 (0..255),  bin = Y >> 2 (64 bins),  cell = ((4 y) / H) * 4 + (4 x) / W (a 4 x 4 grid,
+ *   integer division; cells are empty when H < 4 or W < 4),  hist[t][cell][bin] = number of such pixels,
+ *   out[t] = sum over cell, bin of |hist[t][cell][bin] - hist[t+1][cell][bin]|,  0 <= t < L - 1:  0 .. 2 H W.
+ * out int64 [L-1] on the device.  One pass over the frames (16-byte loads between byte heads and tails: any base, any row pitch)
+ * builds the tables in `workspace` -- e2fgvi_scene_diff_workspace(L,H,W) bytes, caller-owned, 4-byte aligned, its contents on
+ * entry do not matter: it is zeroed on `stream` -- with integer atomics, a second launch sums the differences per pair: exact,
+ * and the same in every run.  L >= 2, H, W >= 1, H * W < 2^31 (E2FGVI_EINVAL otherwise, from both entries). */
+int64_t e2fgvi_scene_diff_workspace(int32_t L, int32_t H, int32_t W);
+int e2fgvi_scene_diff(const uint8_t* frames, int32_t L, int32_t H, int32_t W, void* workspace, int64_t* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * evaluate.py metrics (core/metrics.py:20-56): per image pair of fp32 NHWC [N,H,W,3] frames in
