@@ -83,6 +83,7 @@ def build(force=False, verbose=False, nopk_all=False, lib=None, tag=None, define
             verify_wino_waits(objdir)
             verify_exit_reuse(objdir)
             verify_no_scratch(objdir)
+            verify_no_scratch(objdir, "conv_bf16x.o", "conv_halo_x3_kernel", "split-operand halo")
             verify_no_scratch(objdir, "video.o", "restore_u8_kernel", "paste-back")
     return out
 

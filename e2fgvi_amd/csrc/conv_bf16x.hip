@@ -814,6 +814,233 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_bf16x_kernel(const ConvXP
 #endif
 }
 
+// ---- halo-staged split-operand variant (tile codes 51 / 52) ------------------------------------------------------
+// The implicit-GEMM form above gathers every input pixel of a KxK stride-1 layer K*K times from L2 and splits it into its three
+// bf16 pieces every time; on the 7x7 layers of SPyNet's upper levels (32 -> 64 and 64 -> 32 channels) that fill is what the
+// kernel waits for.  Here -- the split-operand form of conv_halo_kernel (conv.hip) -- a workgroup owns a TH x 16 pixel tile of
+// ONE image and every output channel: per 16-channel block the (TH+K-1) x (16+K-1) input patch is loaded once (fp32, as
+// load_patch of conv_halo_kernel does), split ONCE (e2_split8) and kept in LDS as three bf16 planes; all K*K taps take their A
+// operands from it at a shifted pixel offset: one ds_read_b128 per plane, row tile and tap, no per-tap address arithmetic.
+//   LDS: [plane hi, mid, lo][patch pixel][2 halves of 8 bf16]; the 16-byte half hh of a pixel of patch row py sits in slot
+//   hh ^ (py & 1).  A 16-lane group of ds_read_b128 covers 8 consecutive pixels of each of the two rows of a 2x16-pixel
+//   sub-tile: 32-byte pixels put 8 consecutive pixels on the 8 even (or 8 odd) 16-byte slots of the 256-byte bank row, and the
+//   row parity sends the second row to the other 8 -- conflict-free without padding (a padded pitch of 48 bytes is 2-way
+//   conflicted for 22-pixel rows, and costs the second resident workgroup).
+//   Lane map: conv_halo_kernel's -- lane (i, h) of sub-tile t is output pixel (2 t + (i >> 4), i & 15) -- on
+//   v_mfma_f32_32x32x16_bf16: the lane holds channels 8 h ... 8 h + 7 of the block.
+// Weights: the layer's split-operand packing ([K-step = (tap, 32 channels)][plane][4 k-octets][Npad][8 bf16]) visited in
+// (block, tap) order; a lane loads its B fragments (k-octet 2 u + h of column i, three planes) straight into the operand
+// registers, ahead of the MFMAs that use them (as mdcn.hip does): the waves of a column share the lines through L1, so the tap
+// loop has no barrier at all.  The patch is single-buffered: the next block's patch is in flight (registers) during
+// the taps and stored between two barriers per block -- four blocks for 64 channels.
+// Six terms per product in compute()'s order, smallest first.  The sums run in (block, tap) order: results differ from the
+// implicit-GEMM tiles in their last bits.  Plain HIP: builtin buffer loads, __syncthreads, compiler-managed waits.
+// A wave owns TM 2x16-pixel sub-tiles x 32 output channels; a workgroup is WGM x (BN / 32) waves.  Two waves per SIMD at least: the
+// register budget is set for it.
+template <int KK_, int TH, int BN, int WGM>
+__global__ __launch_bounds__(64 * WGM * (BN / 32)) __attribute__((amdgpu_waves_per_eu(2))) void conv_halo_x3_kernel(const ConvXParams p) {
+    constexpr int TW = 16;
+    constexpr int PH = TH + KK_ - 1, PW = TW + KK_ - 1, NPIX = PH * PW;
+    constexpr int WGN = BN / 32;                                // waves along the output channels: 32 columns each
+    constexpr int NT = 64 * WGM * WGN;
+    constexpr int TM = (TH / 2) / WGM, TN = 1;
+    constexpr int PITCH = 32;                                   // bytes of a patch pixel in one plane: 16 bf16
+    constexpr int PLANE = NPIX * PITCH;
+    constexpr int P_ITEMS = NPIX * 2;                           // (patch pixel, 8-channel half)
+    constexpr int P_IT = (P_ITEMS + NT - 1) / NT;
+    constexpr unsigned OOB = 0xFFFFFFFFu;
+    static_assert(TM >= 1 && 2 * TM * WGM == TH && TN >= 1 && 3 * PLANE <= 160 * 1024, "tile");
+
+    __shared__ __attribute__((aligned(16))) unsigned char smem[3 * PLANE];
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int wm = wave / WGN, wn = wave % WGN;
+    const int tiles_x = (p.Wo + TW - 1) / TW, tiles_y = (p.Ho + TH - 1) / TH;
+    int sp = xcd_remap(blockIdx.x, p.N * tiles_y * tiles_x);
+    const int txi = sp % tiles_x;
+    sp /= tiles_x;
+    const int tyi = sp % tiles_y;
+    const int img = sp / tiles_y;
+    const int y0 = tyi * TH, x0 = txi * TW;
+
+    // patch staging: this thread's items: input pixel index or "outside", LDS byte offset inside a plane
+    const int hh = tid & 1;                                     // (NT is even: every item of a thread is the same half)
+    int pp_pix[P_IT], pp_lds[P_IT];
+#pragma unroll
+    for (int it = 0; it < P_IT; ++it) {
+        const int f = tid + it * NT;
+        const int pp = f >> 1;
+        const int py = pp / PW, px = pp - py * PW;
+        const int iy = y0 - p.pad + py, ix = x0 - p.pad + px;
+        const bool ok = (P_ITEMS % NT == 0 || f < P_ITEMS) && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
+        pp_pix[it] = ok ? (img * p.H + iy) * p.W + ix : -1;
+        pp_lds[it] = pp * PITCH + ((hh ^ (py & 1)) << 4);
+    }
+    const __amdgpu_buffer_rsrc_t arsrc = make_rsrc(p.src[0], p.src_bytes[0]);
+    const unsigned ld4 = (unsigned)p.ld[0] * 4u;
+    const unsigned chan = (unsigned)p.coff[0] * 4u + (unsigned)hh * 32u;
+    const int cpg = p.cpg[0];
+    const int nblk = cpg >> 4;                                  // 16-channel blocks (host: cpg % 16 == 0)
+
+    f32x4 rp[P_IT][2];
+    auto load_patch = [&](int blk) {                            // blk >= nblk: everything reads as zero
+#pragma unroll
+        for (int it = 0; it < P_IT; ++it) {
+            const bool ok = blk < nblk && pp_pix[it] >= 0;
+            const unsigned off = (unsigned)pp_pix[it] * ld4 + chan + (unsigned)blk * 64u;
+            rp[it][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(arsrc, (int)(ok ? off : OOB), 0, 0));
+            rp[it][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(arsrc, (int)(ok ? off + 16u : OOB), 0, 0));
+        }
+    };
+    auto store_patch = [&]() {                                  // split once: three planes
+#pragma unroll
+        for (int it = 0; it < P_IT; ++it) {
+            if (P_ITEMS % NT == 0 || (tid + it * NT) < P_ITEMS) {
+                bf16x8 sh, sm, sl;
+                split8(rp[it][0], rp[it][1], sh, sm, sl);
+                *reinterpret_cast<bf16x8*>(smem + pp_lds[it]) = sh;
+                *reinterpret_cast<bf16x8*>(smem + PLANE + pp_lds[it]) = sm;
+                *reinterpret_cast<bf16x8*>(smem + 2 * PLANE + pp_lds[it]) = sl;
+            }
+        }
+    };
+
+    // MFMA A operand: lane (i, h) of sub-tile (wm*TM + tm) is output pixel (2*(wm*TM + tm) + (i >> 4), i & 15) of the tile; its
+    // patch row for kernel row ky is that + ky, so the slot of its half is h ^ (i >> 4) ^ (ky & 1): one base per parity of ky
+    const int i = lane & 31, h = lane >> 5;
+    int a_base[TM];                                             // (ky even; odd: the other slot, ^ 16)
+#pragma unroll
+    for (int tm = 0; tm < TM; ++tm) a_base[tm] = ((2 * (wm * TM + tm) + (i >> 4)) * PW + (i & 15)) * PITCH + ((h ^ (i >> 4)) << 4);
+
+    // weights: this lane's fixed byte offset (k-octet h of column wn*32 + i of plane 0 of a K-step), OOB past Npad; the K-step,
+    // the plane and the 16-channel unit inside the step go through the scalar offset
+    const __amdgpu_buffer_rsrc_t wrsrc = make_rsrc(p.w, p.wgroup_bytes);
+    unsigned b_voff[TN];
+#pragma unroll
+    for (int tn = 0; tn < TN; ++tn) b_voff[tn] = (wn * 32 + i) < p.Npad ? (unsigned)((h * p.Npad + wn * 32 + i) * 16) : OOB;
+    const unsigned oct_bytes = (unsigned)p.Npad * 16u;          // one k-octet of one plane
+    const int spt = (cpg + 31) >> 5;                            // K-steps per tap of the packing
+    auto load_b = [&](bf16x8 (&b)[TN][3], int tap, int blk) {   // blk >= nblk: zeros (never multiplied)
+        const unsigned soff = ((unsigned)((tap * spt + (blk >> 1)) * 12 + 2 * (blk & 1))) * oct_bytes;
+#pragma unroll
+        for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+            for (int pl = 0; pl < 3; ++pl)
+                b[tn][pl] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(
+                    wrsrc, (int)(blk < nblk ? b_voff[tn] : OOB), (int)(soff + (unsigned)pl * 4u * oct_bytes), 0));
+    };
+
+    f32x16 acc[TM][TN];
+#pragma unroll
+    for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+        for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[tm][tn][r] = 0.f;
+
+    auto load_a = [&](bf16x8 (&a)[TM][3], const int (&row)[TM], int kx) {
+#pragma unroll
+        for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+            for (int pl = 0; pl < 3; ++pl) a[tm][pl] = *reinterpret_cast<const bf16x8*>(smem + pl * PLANE + row[tm] + kx * PITCH);
+    };
+
+    bf16x8 bq[TN][3], bn[TN][3], bn2[TN][3], aq[TM][3], an[TM][3];
+    load_patch(0);
+    load_b(bq, 0, 0);
+    load_b(bn, 1, 0);
+    store_patch();
+    __syncthreads();
+
+    // The weights of a tap are fetched two taps ahead of its MFMAs (L2 latency), its A fragments one tap ahead (LDS latency); the
+    // fences keep hipcc from sinking the loads to their first use (it did: a buffer load, s_waitcnt vmcnt(0), its MFMA -- the whole
+    // L2 latency in every tap).
+    for (int blk = 0; blk < nblk; ++blk) {
+        load_patch(blk + 1);                                    // the next block's patch is in flight during this block's taps
+        load_a(aq, a_base, 0);
+#pragma unroll 1
+        for (int ky = 0; ky < KK_; ++ky) {
+            // this kernel row's patch row and the next one's (past the last row: the last again, read and not used)
+            const int kyn = ky + 1 < KK_ ? ky + 1 : ky;
+            int a_row[TM], a_nxt[TM];
+#pragma unroll
+            for (int tm = 0; tm < TM; ++tm) {
+                a_row[tm] = (a_base[tm] ^ ((ky & 1) << 4)) + ky * (PW * PITCH);
+                a_nxt[tm] = (a_base[tm] ^ ((kyn & 1) << 4)) + kyn * (PW * PITCH);
+            }
+#pragma unroll
+            for (int kx = 0; kx < KK_; ++kx) {
+                // the weights two taps on: (blk, tap + 2) or (blk + 1, tap + 2 - K*K); the next tap's A fragments (the next
+                // block's follow its barrier)
+                const int tap2 = ky * KK_ + kx + 2;
+                const bool wrap = tap2 >= KK_ * KK_;
+                load_b(bn2, wrap ? tap2 - KK_ * KK_ : tap2, wrap ? blk + 1 : blk);
+                if (kx + 1 < KK_) load_a(an, a_row, kx + 1);
+                else load_a(an, a_nxt, 0);
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int tn = 0; tn < TN; ++tn) {
+                    const bf16x8 bh = bq[tn][0], bm = bq[tn][1], bl = bq[tn][2];
+                    bf16x8 ah[TM], am[TM], al[TM];
+#pragma unroll
+                    for (int tm = 0; tm < TM; ++tm) { ah[tm] = aq[tm][0]; am[tm] = aq[tm][1]; al[tm] = aq[tm][2]; }
+                    // smallest terms first; the TM accumulators of a term are independent
+#pragma unroll
+                    for (int tm = 0; tm < TM; ++tm) acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[tm], bh, acc[tm][tn], 0, 0, 0);
+#pragma unroll
+                    for (int tm = 0; tm < TM; ++tm) acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[tm], bl, acc[tm][tn], 0, 0, 0);
+#pragma unroll
+                    for (int tm = 0; tm < TM; ++tm) acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[tm], bm, acc[tm][tn], 0, 0, 0);
+#pragma unroll
+                    for (int tm = 0; tm < TM; ++tm) acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[tm], bh, acc[tm][tn], 0, 0, 0);
+#pragma unroll
+                    for (int tm = 0; tm < TM; ++tm) acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[tm], bm, acc[tm][tn], 0, 0, 0);
+#pragma unroll
+                    for (int tm = 0; tm < TM; ++tm) acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[tm], bh, acc[tm][tn], 0, 0, 0);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int pl = 0; pl < 3; ++pl) {
+#pragma unroll
+                    for (int tn = 0; tn < TN; ++tn) { bq[tn][pl] = bn[tn][pl]; bn[tn][pl] = bn2[tn][pl]; }
+#pragma unroll
+                    for (int tm = 0; tm < TM; ++tm) aq[tm][pl] = an[tm][pl];
+                }
+            }
+        }
+        if (blk + 1 < nblk) {                                   // (uniform) the patch is single-buffered: every reader is done, then
+            __syncthreads();                                    // the next block's pieces replace it
+            store_patch();
+            __syncthreads();
+        }
+    }
+
+    // ---- epilogue: conv_halo_kernel's (bias, fp32 residual, activation, fp32 NHWC store)
+    const float* res = reinterpret_cast<const float*>(p.res);
+    float* dst = reinterpret_cast<float*>(p.dst);
+#pragma unroll
+    for (int tn = 0; tn < TN; ++tn) {
+        const int co = wn * 32 + i;
+        if (co >= p.Cout_g) continue;                           // padded columns are never stored
+        const float bv = p.bias ? p.bias[co] : 0.f;
+#pragma unroll
+        for (int tm = 0; tm < TM; ++tm) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = (r & 3) + 8 * (r >> 2) + 4 * h;            // pixel of the 2x16 sub-tile
+                const int oy = y0 + 2 * (wm * TM + tm) + (row >> 4), ox = x0 + (row & 15);
+                if (oy >= p.Ho || ox >= p.Wo) continue;
+                const long long m = ((long long)img * p.Ho + oy) * p.Wo + ox;
+                float v = acc[tm][tn][r] + bv;
+                if (res) v += res[m * p.res_ld + p.res_coff + co];
+                v = apply_act(v, p.act, p.slope);
+                dst[m * p.dst_ld + p.dst_coff + co] = v;
+            }
+        }
+    }
+}
+
 struct PackX {
     int Cout, groups, KH, KW, nsrc;
     int cpg[E2FGVI_MAX_SRC];
@@ -943,6 +1170,29 @@ int launch_x(ConvXParams& p, int groups, hipStream_t st, int mode = 0) {
     E2_LAUNCH_CHECK("conv2d_x");
     return 0;
     }
+}
+
+// the halo-staged split-operand kernel (tiles 51: 16x16-pixel tiles, 52: 8x16): what it does not cover answers EUNSUP, and the
+// layer falls back to the tile it had
+template <int TH, int WGM>
+int launch_halo_x3(ConvXParams& p, const e2fgvi_convx_desc* d, hipStream_t st, int mode) {
+    const bool ok = mode == 2 && !d->tap_packed && d->KH == 7 && d->KW == 7 && d->stride == 1 && d->pad == 3 && d->groups == 1 &&
+                    d->nsrc == 1 && d->src_cpg[0] % 16 == 0 && d->Cout <= 64 && !d->out_grid && !d->res_bcast && !d->dst_nchw &&
+                    !d->dst2 && d->dst_dtype == E2FGVI_F32 && (!d->residual || d->res_dtype == E2FGVI_F32) &&
+                    d->act != E2FGVI_ACT_DCNPOST;
+    if (!ok) {
+        e2fgvi_set_error("conv2d_x: the halo tiles (51, 52) take split-operand 7x7 stride-1 pad-3 layers: one fp32 source of a multiple "
+                         "of 16 channels, no groups, at most 64 output channels, plain packing, fp32 NHWC result and residual");
+        return E2FGVI_EUNSUP;
+    }
+    p.tilesM = p.N * cdiv(p.Ho, TH) * cdiv(p.Wo, 16);
+    p.tilesN = 1;
+    if (p.Cout_g <= 32)
+        hipLaunchKernelGGL((conv_halo_x3_kernel<7, TH, 32, WGM>), dim3(p.tilesM, 1, 1), dim3(64 * WGM), 0, st, p);
+    else
+        hipLaunchKernelGGL((conv_halo_x3_kernel<7, TH, 64, WGM>), dim3(p.tilesM, 1, 1), dim3(128 * WGM), 0, st, p);
+    E2_LAUNCH_CHECK("conv2d_x");
+    return 0;
 }
 
 }  // namespace
@@ -1146,6 +1396,9 @@ static int conv2d_x(const e2fgvi_convx_desc* d, void* stream, int mode) {
         // split-operand mode with the two halves of the workgroup half a step apart (kernel comment, PP)
         case 107: return launch_x<256, 256, 4, 2, false, true>(p, d->groups, st, mode);
         case 108: return launch_x<256, 192, 4, 2, false, true>(p, d->groups, st, mode);
+        // split-operand 7x7 stride-1 layers from an LDS halo patch: split once per patch, not once per tap (conv_halo_x3_kernel)
+        case 51: return launch_halo_x3<16, 4>(p, d, st, mode);
+        case 52: return launch_halo_x3<8, 2>(p, d, st, mode);
         // 3x3 stride-1 pad-1 layers: the three horizontal taps share one A stage (row-shifted reads)
         case 11: return launch_x<128, 128, 2, 2, true>(p, d->groups, st, mode);
         case 12: return launch_x<128, 64, 2, 2, true>(p, d->groups, st, mode);

@@ -53,7 +53,11 @@ W4_CODES = {2464: (2, 64)}
 _W4_MINPIX = 20000          # output pixels from which PackedConv._wino4_rule hands a qualifying layer to F(2x4)
 # bf16 data path (conv_bf16x): 128x128, 64x128, 256x128 and 256x256 (8 waves), 128x64, 64x64, 128x32 tiles; tile codes +10
 # are the row-shift variants for 3x3 stride-1 pad-1 layers (the three horizontal taps share one A stage).
-XTUNE_CANDIDATES = (1, 4, 6, 7, 8, 2, 5, 3, 107, 108)     # 107 / 108: the ping-pong forms of 7 / 8, split-operand layers only (others: EUNSUP, skipped)
+# 107 / 108: the ping-pong forms of 7 / 8, split-operand layers only (others: EUNSUP, skipped)
+# 51 / 52: split-operand 7x7 stride-1 layers from an LDS halo patch (conv_bf16x.hip conv_halo_x3_kernel: 16x16- and 8x16-pixel tiles);
+#          timed only where PackedConvX._halo_x3 says the geometry qualifies (SPyNet's 32 -> 64 and 64 -> 32 layers), EUNSUP anywhere else
+XTUNE_CANDIDATES = (1, 4, 6, 7, 8, 2, 5, 3, 107, 108, 51, 52)
+XTUNE_HALO = (51, 52)
 XTUNE_ROWSHIFT = (11, 16, 17, 12, 13, 18)
 # fp32 layers on the bf16 matrix pipe by exact operand splitting (conv_bf16x.hip MODE 2, PackedConvX(x3=True)): a tuning
 # alternative of every fp32 layer that asks for it (PackedConv.try_x3 / PackedConvX.try_x3); taken when its best tile beats
@@ -937,6 +941,12 @@ class PackedConvX(_ConvLayer):
                     # pipe for 157.3 / 2500 of the time of an fp32 MAC): `issued / fp32 peak` stays matrix-pipe time
                     issued=int(N * Ho * Wo * (-(-cout_g // 32) * 32) * self.groups * cin_p * K2 * (_L.X3_PIPE if self.x3 else 1)))
 
+    def _halo_x3(self):
+        """whether the halo tiles (XTUNE_HALO) take this layer: split operands, 7x7 stride 1 pad 3, one source of a multiple of 16
+        channels in the plain packing, no groups, at most 64 output channels (the launcher checks the call's epilogue itself)"""
+        return (self.x3 and not self.taps and (self.KH, self.KW, self.stride, self.pad, self.groups) == (7, 7, 1, 3, 1)
+                and len(self.cpg) == 1 and self.cpg[0] % 16 == 0 and self.Cout <= 64)
+
     def _time_tiles(self, d, reps=3, rounds=2):
         """{tile code: best device time in ms} of every tile shape on this exact call (the launches rewrite the same
         output); best of `rounds` measurements of `reps` launches each"""
@@ -952,6 +962,8 @@ class PackedConvX(_ConvLayer):
         for _ in range(rounds * TUNE_REPS):
             rowshift = (self.KH, self.KW, self.stride, self.pad) == (3, 3, 1, 1) and not self.f32 and not self.taps
             for code in XTUNE_CANDIDATES + (XTUNE_ROWSHIFT if rowshift else ()):
+                if code in XTUNE_HALO and not self._halo_x3():
+                    continue
                 if code % 10 == 3 and self.Cout // self.groups > 64:  # 32-wide tiles only make sense for narrow layers
                     continue
                 if code in (12, 18) and self.Cout // self.groups > 64:

@@ -473,7 +473,10 @@ int e2fgvi_cast(const void* src, int32_t src_dtype, void* dst, int32_t dst_dtype
  *                 products of a*b the six largest are accumulated by v_mfma_f32_32x32x16_bf16 in fp32 (the three dropped ones
  *                 are < 2^-22 |a*b| together): fp32-level rounding at 2.7x the fp32 MFMA rate.  Tile codes 1..8 and 107 / 108
  *                 (the 256x256 / 256x192 tiles with the two halves of the workgroup one K-half-step apart: same bits as 7 / 8,
- *                 not for tap-packed weights).
+ *                 not for tap-packed weights), and 51 / 52: 7x7 stride-1 pad-3 layers from an LDS halo patch (16x16- / 8x16-pixel
+ *                 tiles, the patch split once per 16-channel block instead of once per tap; sums in (block, tap) order): one source
+ *                 of a multiple of 16 channels, groups = 1, Cout <= 64, plain packing, fp32 NHWC dst and residual, no
+ *                 ACT_DCNPOST / dst2 / out_grid -- E2FGVI_EUNSUP otherwise.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct {
     const void* src[E2FGVI_MAX_SRC];   /* NHWC sources of the virtual concat, of the mode's source type         */
