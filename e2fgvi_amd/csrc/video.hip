@@ -844,6 +844,328 @@ __global__ __launch_bounds__(NTH) void scene_diff_kernel(const unsigned* __restr
     }
 }
 
+// Connected components of the hole's footprint (video.hole_regions: one crop region per group of holes).  U[y][x] = 1 iff some
+// frame's mask byte at (x, y) is non-zero; labels[y][x] = 0 where U is 0, else the number 1 .. K of the pixel's 8-connected
+// component, components numbered in raster order of their first pixel -- exact integers that do not depend on the order in which
+// threads or atomics ran.  Six launches whatever the masks hold, no host read between them:
+//   1 footprint   a thread ORs 16 consecutive pixels over the L frames (the L Hm Wm bytes that dominate the traffic): per frame the
+//                 two aligned 16-byte words around its bytes, shifted by the frame's phase (v_alignbyte_b32; wave-uniform), so any
+//                 base and pitch work; the chunks at the two ends of the buffer and the last partial chunk go byte by byte
+//   2 tiles       a workgroup labels an LB_TW x LB_TH tile in LDS with a union-find; `labels` holds the forest afterwards:
+//                 labels[i] = raster index of the tile-local root, -1 for background
+//   3 borders     a thread per pixel of a tile's first row / first column unites it with its neighbours in the row above / the
+//                 column to the left (the diagonal ones across a tile corner included), lock-free on the global forest
+//   4 flatten     every pixel finds its root; a block of LB_SEG consecutive pixels counts its roots and ranks them in raster order
+//   5 scan        one workgroup turns the blocks' counts into exclusive offsets and writes K
+//   6 relabel     labels[i] = offset[block of root] + rank[root] + 1
+// The forest keeps parent[i] <= i and entries only ever decrease: a union links the larger root under the smaller with atomicMin
+// and goes on from the value that returns, a find halves its path with atomicMin.  Every loop walks to strictly smaller indices, so
+// it ends by itself: no thread ever waits for another thread's write.  A root is therefore the smallest raster index of its set,
+// which is what makes the numbering canonical.  Loads that race with those atomics may return an older parent: still an
+// ancestor in the same set, so finds and unions stay correct.
+// Which unions are needed: with the runs of a row joined (H: left neighbour), pixel p needs V (up) unless left and up-left are
+// both set, and when up is not set UL unless left is set and UR unless right is set -- the rest follows by transitivity.  A tile
+// does these for the neighbours it holds (a neighbour outside counts as not set, which only adds unions), the border pass does
+// H / V / UL / UR across tile edges in the conservative form: the straight neighbour if set, else the two diagonal ones.
+constexpr int LB_TW = 64, LB_TH = 32, LB_TILE = LB_TW * LB_TH;     // ops.LABEL_TILE_W / LABEL_TILE_H
+constexpr int LB_PER = 4, LB_SEG = NTH * LB_PER;                    // consecutive pixels per thread / per block of the flatten pass
+constexpr int LB_SLOTS = 256, LB_PROBES = 8;                        // label_boxes_kernel's LDS table
+static_assert(LB_TW == 64 && NTH == 256, "a wave per tile row: the runs of a row come from one ballot");
+
+__device__ __forceinline__ unsigned nz_bytes(unsigned v) {         // 1 in every byte of v that is not zero
+    return ((((v & 0x7f7f7f7fu) + 0x7f7f7f7fu) | v) >> 7) & 0x01010101u;
+}
+
+__global__ __launch_bounds__(NTH) void hole_footprint_kernel(const unsigned char* __restrict__ m, int L, long long N,
+                                                             unsigned char* __restrict__ foot) {
+    const long long i0 = ((long long)blockIdx.x * NTH + threadIdx.x) * 16;
+    if (i0 >= N) return;
+    const unsigned char* const end = m + (long long)L * N;
+    const bool whole = i0 + 16 <= N;
+    unsigned a[4] = {0u, 0u, 0u, 0u};
+#pragma unroll 2
+    for (int l = 0; l < L; ++l) {
+        const unsigned char* p = m + (long long)l * N + i0;
+        const int sh = (int)((uintptr_t)p & 15);
+        const unsigned char* q = p - sh;
+        // both words lie inside the buffer: they may hold bytes of the neighbouring chunks or frames, which are shifted out
+        if (whole && q >= m && q + (sh ? 32 : 16) <= end) {
+            const uint4 lo = *reinterpret_cast<const uint4*>(q);
+            if (sh == 0) {
+                a[0] |= lo.x; a[1] |= lo.y; a[2] |= lo.z; a[3] |= lo.w;
+            } else {
+                const uint4 hi = *reinterpret_cast<const uint4*>(q + 16);
+                unsigned s0, s1, s2, s3, s4;
+                switch (sh >> 2) {
+                    case 0: s0 = lo.x; s1 = lo.y; s2 = lo.z; s3 = lo.w; s4 = hi.x; break;
+                    case 1: s0 = lo.y; s1 = lo.z; s2 = lo.w; s3 = hi.x; s4 = hi.y; break;
+                    case 2: s0 = lo.z; s1 = lo.w; s2 = hi.x; s3 = hi.y; s4 = hi.z; break;
+                    default: s0 = lo.w; s1 = hi.x; s2 = hi.y; s3 = hi.z; s4 = hi.w; break;
+                }
+                const unsigned b = (unsigned)(sh & 3);
+                a[0] |= __builtin_amdgcn_alignbyte(s1, s0, b);
+                a[1] |= __builtin_amdgcn_alignbyte(s2, s1, b);
+                a[2] |= __builtin_amdgcn_alignbyte(s3, s2, b);
+                a[3] |= __builtin_amdgcn_alignbyte(s4, s3, b);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 16; ++k)
+                if (i0 + k < N) a[k >> 2] |= (unsigned)p[k] << (8 * (k & 3));
+        }
+    }
+    if (whole) {
+        *reinterpret_cast<uint4*>(foot + i0) = make_uint4(nz_bytes(a[0]), nz_bytes(a[1]), nz_bytes(a[2]), nz_bytes(a[3]));
+    } else {
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+            if (i0 + k < N) foot[i0 + k] = (unsigned char)(((a[k >> 2] >> (8 * (k & 3))) & 255u) != 0u);
+    }
+}
+
+// the forest in LDS (a tile) and in global memory (the image): the same two loops
+__device__ __forceinline__ int lb_load(const int* p, int i) { return *(const volatile int*)(p + i); }                    // LDS
+__device__ __forceinline__ int lb_load_g(const int* p, int i) { return __hip_atomic_load(p + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+template <bool GLOBAL>
+__device__ __forceinline__ int lb_find(int* p, int x) {
+    int q = GLOBAL ? lb_load_g(p, x) : lb_load(p, x);
+    while (q != x) {                                    // q < x: p[i] <= i
+        const int g = GLOBAL ? lb_load_g(p, q) : lb_load(p, q);
+        if (g != q) atomicMin(p + x, g);                // path halving; g < q < x is an ancestor of x
+        x = q;
+        q = g;
+    }
+    return x;
+}
+
+template <bool GLOBAL>
+__device__ __forceinline__ void lb_unite(int* p, int a, int b) {
+    for (;;) {
+        a = lb_find<GLOBAL>(p, a);
+        b = lb_find<GLOBAL>(p, b);
+        if (a == b) return;
+        if (a < b) { const int t = a; a = b; b = t; }
+        const int old = atomicMin(p + a, b);            // the larger root under the smaller
+        if (old == a) return;                           // a was still a root: linked
+        a = old;                                        // someone linked a under old < a meanwhile: old's set and b's are still to be united
+    }
+}
+
+__global__ __launch_bounds__(NTH) void label_tile_kernel(const unsigned char* __restrict__ foot, int* __restrict__ labels, int Hm,
+                                                         int Wm, int ntx) {
+    __shared__ int s_p[LB_TILE];
+    const int ty = (int)(blockIdx.x / (unsigned)ntx), tx = (int)(blockIdx.x - (unsigned)ty * (unsigned)ntx);
+    const int x0 = tx * LB_TW, y0 = ty * LB_TH;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int x = x0 + lane;
+    // a pixel starts under the first pixel of its run in the tile row: H is done
+    for (int r = wave; r < LB_TH; r += NTH / 64) {
+        const int y = y0 + r;
+        const bool f = y < Hm && x < Wm && foot[(long long)y * Wm + x] != 0;
+        const unsigned long long z = ~__ballot(f) & ((1ull << lane) - 1ull);      // background lanes below this one
+        s_p[r * LB_TW + lane] = f ? r * LB_TW + (z ? 64 - __clzll((long long)z) : 0) : -1;
+    }
+    __syncthreads();
+    for (int r = wave ? wave : NTH / 64; r < LB_TH; r += NTH / 64) {               // rows 1 .. LB_TH - 1
+        const int i = r * LB_TW + lane;
+        if (lb_load(s_p, i) < 0) continue;
+        const bool up = lb_load(s_p, i - LB_TW) >= 0;
+        const bool left = lane > 0 && lb_load(s_p, i - 1) >= 0, right = lane < LB_TW - 1 && lb_load(s_p, i + 1) >= 0;
+        const bool ul = lane > 0 && lb_load(s_p, i - LB_TW - 1) >= 0, ur = lane < LB_TW - 1 && lb_load(s_p, i - LB_TW + 1) >= 0;
+        if (up) {
+            if (!(left && ul)) lb_unite<false>(s_p, i, i - LB_TW);
+        } else {
+            if (ul && !left) lb_unite<false>(s_p, i, i - LB_TW - 1);
+            if (ur && !right) lb_unite<false>(s_p, i, i - LB_TW + 1);
+        }
+    }
+    __syncthreads();
+    for (int r = wave; r < LB_TH; r += NTH / 64) {
+        const int y = y0 + r;
+        if (y >= Hm || x >= Wm) continue;
+        const int i = r * LB_TW + lane;
+        int root = -1;
+        if (lb_load(s_p, i) >= 0) {
+            const int t = lb_find<false>(s_p, i);       // the smallest tile index of the set, so its smallest raster index too
+            root = (int)((long long)(y0 + t / LB_TW) * Wm + x0 + t % LB_TW);
+        }
+        labels[(long long)y * Wm + x] = root;
+    }
+}
+
+__global__ __launch_bounds__(NTH) void label_border_kernel(int* __restrict__ labels, int Hm, int Wm, long long nrow, long long total) {
+    const long long t = (long long)blockIdx.x * NTH + threadIdx.x;
+    if (t >= total) return;
+    if (t < nrow) {                                     // pixel (x, y) of the first row of a tile row, y > 0
+        const int b = (int)(t / Wm), x = (int)(t - (long long)b * Wm);
+        const int i = (int)((long long)(b + 1) * LB_TH * Wm + x);
+        if (lb_load_g(labels, i) < 0) return;
+        const int up = i - Wm;
+        if (lb_load_g(labels, up) >= 0) {
+            lb_unite<true>(labels, i, up);
+        } else {
+            if (x > 0 && lb_load_g(labels, up - 1) >= 0) lb_unite<true>(labels, i, up - 1);
+            if (x + 1 < Wm && lb_load_g(labels, up + 1) >= 0) lb_unite<true>(labels, i, up + 1);
+        }
+    } else {                                            // pixel (x, y) of the first column of a tile column, x > 0
+        const long long u = t - nrow;
+        const int b = (int)(u / Hm), y = (int)(u - (long long)b * Hm);
+        const int i = (int)((long long)y * Wm + (long long)(b + 1) * LB_TW);
+        if (lb_load_g(labels, i) < 0) return;
+        const int lf = i - 1;
+        if (lb_load_g(labels, lf) >= 0) {
+            lb_unite<true>(labels, i, lf);
+        } else {
+            if (y > 0 && lb_load_g(labels, lf - Wm) >= 0) lb_unite<true>(labels, i, lf - Wm);
+            if (y + 1 < Hm && lb_load_g(labels, lf + Wm) >= 0) lb_unite<true>(labels, i, lf + Wm);
+        }
+    }
+}
+
+// exclusive scan of one value per thread over the block (wave64 shuffles, the waves' totals through LDS); total: the block's sum
+__device__ __forceinline__ int block_scan_excl(int v, int* s_w, int& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int n = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += n;
+    }
+    __syncthreads();                                    // s_w may still be read from the previous call
+    if (lane == 63) s_w[wave] = inc;
+    __syncthreads();
+    int before = 0;
+    total = 0;
+#pragma unroll
+    for (int w = 0; w < NTH / 64; ++w) {
+        if (w < wave) before += s_w[w];
+        total += s_w[w];
+    }
+    return before + inc - v;
+}
+
+__global__ __launch_bounds__(NTH) void label_flatten_kernel(int* __restrict__ labels, int* __restrict__ rank, int* __restrict__ counts,
+                                                            long long N) {
+    __shared__ int s_w[NTH / 64];
+    const long long i0 = (long long)blockIdx.x * LB_SEG + (long long)threadIdx.x * LB_PER;
+    bool is_root[LB_PER];
+    int c = 0;
+#pragma unroll
+    for (int k = 0; k < LB_PER; ++k) {
+        const long long i = i0 + k;
+        is_root[k] = false;
+        if (i < N) {
+            const int t = lb_load_g(labels, (int)i);
+            if (t >= 0) {
+                const int r = lb_find<true>(labels, t);
+                labels[i] = r;                          // no union runs in this pass: r is the root for good
+                is_root[k] = r == (int)i;
+            }
+        }
+        c += is_root[k];
+    }
+    int total;
+    int e = block_scan_excl(c, s_w, total);
+#pragma unroll
+    for (int k = 0; k < LB_PER; ++k)
+        if (is_root[k]) rank[i0 + k] = e++;
+    if (threadIdx.x == 0) counts[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(NTH) void label_scan_kernel(int* __restrict__ counts, long long nblk, int* __restrict__ count) {
+    __shared__ int s_w[NTH / 64];
+    int carry = 0;
+    for (long long base = 0; base < nblk; base += NTH) {
+        const long long i = base + threadIdx.x;
+        const int v = i < nblk ? counts[i] : 0;
+        int total;
+        const int e = block_scan_excl(v, s_w, total);
+        if (i < nblk) counts[i] = carry + e;
+        carry += total;
+    }
+    if (threadIdx.x == 0) *count = carry;
+}
+
+__global__ void label_number_kernel(int* __restrict__ labels, const int* __restrict__ rank, const int* __restrict__ offs, long long N) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    const int r = labels[i];
+    labels[i] = r < 0 ? 0 : offs[r / LB_SEG] + rank[r] + 1;
+}
+
+// Bounding boxes and areas of labelled components: boxes[k-1] = (x0, y0, x1, y1, area) of label k, upper ends exclusive.  A
+// workgroup owns a tile, a wave a row of it at a time: a run of equal labels is one entry (its first lane's, found with a shuffle
+// and a ballot), entries of one label meet in an LDS table (open addressing, at most LB_PROBES probes -- a run that finds no slot
+// goes to global memory itself), and every used slot issues five global atomics at the end.  A label outside [1, K] is skipped, so
+// the kernel stays in bounds whatever the labels hold.
+__global__ void label_boxes_init_kernel(int* __restrict__ boxes, long long n) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx < n) boxes[idx] = idx % 5 < 2 ? 0x7fffffff : 0;
+}
+
+__device__ __forceinline__ void label_box_add(int* b, int x0, int y0, int x1, int y1, int area) {
+    atomicMin(b, x0);
+    atomicMin(b + 1, y0);
+    atomicMax(b + 2, x1);
+    atomicMax(b + 3, y1);
+    atomicAdd(b + 4, area);
+}
+
+__global__ __launch_bounds__(NTH) void label_boxes_kernel(const int* __restrict__ labels, int Hm, int Wm, int ntx, int K,
+                                                          int* __restrict__ boxes) {
+    __shared__ int s_key[LB_SLOTS];
+    __shared__ int s_box[LB_SLOTS][5];
+    for (int i = threadIdx.x; i < LB_SLOTS; i += NTH) {
+        s_key[i] = 0;
+        s_box[i][0] = s_box[i][1] = 0x7fffffff;
+        s_box[i][2] = s_box[i][3] = s_box[i][4] = 0;
+    }
+    __syncthreads();
+    const int ty = (int)(blockIdx.x / (unsigned)ntx), tx = (int)(blockIdx.x - (unsigned)ty * (unsigned)ntx);
+    const int x0 = tx * LB_TW, y0 = ty * LB_TH;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int x = x0 + lane;
+    for (int r = wave; r < LB_TH; r += NTH / 64) {
+        const int y = y0 + r;
+        int lab = y < Hm && x < Wm ? labels[(long long)y * Wm + x] : 0;
+        if (lab < 0 || lab > K) lab = 0;
+        const int prev = __shfl_up(lab, 1, 64);
+        const bool first = lane == 0 || prev != lab;
+        const unsigned long long starts = __ballot(first);
+        if (!first || !lab) continue;
+        const unsigned long long later = lane == 63 ? 0ull : starts >> (lane + 1);
+        const int len = later ? __ffsll((long long)later) : 64 - lane;
+        int h = (int)(((unsigned)lab * 0x9E3779B1u) >> 24);
+        bool done = false;
+        for (int pr = 0; pr < LB_PROBES && !done; ++pr) {
+            const int old = atomicCAS(&s_key[h], 0, lab);
+            if (old == 0 || old == lab) {
+                label_box_add(s_box[h], x, y, x + len, y + 1, len);
+                done = true;
+            }
+            h = (h + 1) & (LB_SLOTS - 1);
+        }
+        if (!done) label_box_add(boxes + 5LL * (lab - 1), x, y, x + len, y + 1, len);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < LB_SLOTS; i += NTH)
+        if (s_key[i]) label_box_add(boxes + 5LL * (s_key[i] - 1), s_box[i][0], s_box[i][1], s_box[i][2], s_box[i][3], s_box[i][4]);
+}
+
+// the workspace of e2fgvi_hole_label for N pixels: rank int32 [N] | footprint uint8 [N] | counts int32 [ceil(N / LB_SEG)], each
+// part starting at a multiple of 16 bytes
+struct LabelWork { long long rank, foot, counts, bytes, nblk; };
+inline LabelWork label_work(long long N) {
+    LabelWork w;
+    w.nblk = (N + LB_SEG - 1) / LB_SEG;
+    w.rank = 0;
+    w.foot = (4 * N + 15) / 16 * 16;
+    w.counts = w.foot + (N + 15) / 16 * 16;
+    w.bytes = w.counts + (4 * w.nblk + 15) / 16 * 16;
+    return w;
+}
+
 inline bool ranges_overlap(const void* a, long long na, const void* b, long long nb) {
     const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
     return pa < pb + (uintptr_t)nb && pb < pa + (uintptr_t)na;
@@ -1194,5 +1516,72 @@ extern "C" int e2fgvi_scene_diff(const uint8_t* frames, int32_t L, int32_t H, in
                            (long long*)out + l0);
         E2_LAUNCH_CHECK("scene_diff");
     }
+    return 0;
+}
+
+static bool label_size_ok(const char* what, int32_t Hm, int32_t Wm) {
+    if (Hm >= 1 && Wm >= 1 && (int64_t)Hm * Wm < (1LL << 31)) return true;
+    e2fgvi_set_error("%s: needs Hm, Wm >= 1 with Hm * Wm < 2^31, got %d x %d", what, Hm, Wm);
+    return false;
+}
+
+extern "C" int64_t e2fgvi_hole_label_workspace(int32_t Hm, int32_t Wm) {
+    if (!label_size_ok("hole_label_workspace", Hm, Wm)) return E2FGVI_EINVAL;
+    return (int64_t)label_work((long long)Hm * Wm).bytes;
+}
+
+extern "C" int e2fgvi_hole_label(const uint8_t* masks, int32_t L, int32_t Hm, int32_t Wm, void* workspace, int32_t* labels,
+                                 int32_t* count, void* stream) {
+    E2_REQUIRE(workspace && labels && count, E2FGVI_EINVAL, "hole_label: null pointer");
+    E2_REQUIRE(L >= 0, E2FGVI_EINVAL, "hole_label: the number of frames must be >= 0, got %d", L);
+    if (!label_size_ok("hole_label", Hm, Wm)) return E2FGVI_EINVAL;
+    E2_REQUIRE(masks || L == 0, E2FGVI_EINVAL, "hole_label: null masks");
+    E2_REQUIRE(((uintptr_t)workspace & 15) == 0 && ((uintptr_t)labels & 3) == 0 && ((uintptr_t)count & 3) == 0, E2FGVI_EINVAL,
+               "hole_label: workspace must be 16-byte aligned, labels and count 4-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const long long N = (long long)Hm * Wm;
+    if (L == 0) {                                       // no frame, no hole
+        hipError_t e = hipMemsetAsync(labels, 0, (size_t)N * sizeof(int32_t), st);
+        if (e == hipSuccess) e = hipMemsetAsync(count, 0, sizeof(int32_t), st);
+        E2_REQUIRE(e == hipSuccess, (int)e, "hole_label: hipMemsetAsync failed: %s", hipGetErrorString(e));
+        return 0;
+    }
+    const LabelWork w = label_work(N);
+    int* rank = (int*)((char*)workspace + w.rank);
+    unsigned char* foot = (unsigned char*)workspace + w.foot;
+    int* counts = (int*)((char*)workspace + w.counts);
+    // every launch below writes all it later reads: the workspace may hold anything.  Their number depends on (Hm, Wm) alone.
+    hipLaunchKernelGGL(hole_footprint_kernel, dim3(blocks_for((N + 15) / 16)), dim3(NTH), 0, st, masks, L, N, foot);
+    E2_LAUNCH_CHECK("hole_label");
+    const int ntx = (Wm + LB_TW - 1) / LB_TW, nty = (Hm + LB_TH - 1) / LB_TH;
+    hipLaunchKernelGGL(label_tile_kernel, dim3((unsigned)((long long)ntx * nty)), dim3(NTH), 0, st, foot, labels, Hm, Wm, ntx);
+    E2_LAUNCH_CHECK("hole_label");
+    const long long nrow = (long long)((Hm - 1) / LB_TH) * Wm, total = nrow + (long long)((Wm - 1) / LB_TW) * Hm;
+    if (total > 0) {
+        hipLaunchKernelGGL(label_border_kernel, dim3(blocks_for(total)), dim3(NTH), 0, st, labels, Hm, Wm, nrow, total);
+        E2_LAUNCH_CHECK("hole_label");
+    }
+    hipLaunchKernelGGL(label_flatten_kernel, dim3((unsigned)w.nblk), dim3(NTH), 0, st, labels, rank, counts, N);
+    E2_LAUNCH_CHECK("hole_label");
+    hipLaunchKernelGGL(label_scan_kernel, dim3(1), dim3(NTH), 0, st, counts, w.nblk, count);
+    E2_LAUNCH_CHECK("hole_label");
+    hipLaunchKernelGGL(label_number_kernel, dim3(blocks_for(N)), dim3(NTH), 0, st, labels, rank, counts, N);
+    E2_LAUNCH_CHECK("hole_label");
+    return 0;
+}
+
+extern "C" int e2fgvi_label_boxes(const int32_t* labels, int32_t Hm, int32_t Wm, int32_t K, int32_t* boxes, void* stream) {
+    E2_REQUIRE(K >= 0, E2FGVI_EINVAL, "label_boxes: the number of components must be >= 0, got %d", K);
+    if (!label_size_ok("label_boxes", Hm, Wm)) return E2FGVI_EINVAL;
+    if (K == 0) return 0;
+    E2_REQUIRE(labels && boxes, E2FGVI_EINVAL, "label_boxes: null pointer");
+    E2_REQUIRE(((uintptr_t)labels & 3) == 0 && ((uintptr_t)boxes & 3) == 0, E2FGVI_EINVAL,
+               "label_boxes: labels and boxes must be 4-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(label_boxes_init_kernel, dim3(blocks_for(5LL * K)), dim3(NTH), 0, st, boxes, 5LL * K);
+    E2_LAUNCH_CHECK("label_boxes");
+    const int ntx = (Wm + LB_TW - 1) / LB_TW, nty = (Hm + LB_TH - 1) / LB_TH;
+    hipLaunchKernelGGL(label_boxes_kernel, dim3((unsigned)((long long)ntx * nty)), dim3(NTH), 0, st, labels, Hm, Wm, ntx, K, boxes);
+    E2_LAUNCH_CHECK("label_boxes");
     return 0;
 }

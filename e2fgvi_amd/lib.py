@@ -134,6 +134,9 @@ SYMBOLS = {
     "e2fgvi_scatter_slabs": (C.c_int, [_fp, _fp, _i32, _i64, _fp, _i32, _fp]),
     "e2fgvi_scene_diff_workspace": (_i64, [_i32, _i32, _i32]),
     "e2fgvi_scene_diff": (C.c_int, [_fp, _i32, _i32, _i32, _fp, _fp, _fp]),
+    "e2fgvi_hole_label_workspace": (_i64, [_i32, _i32]),
+    "e2fgvi_hole_label": (C.c_int, [_fp, _i32, _i32, _i32, _fp, _fp, _fp, _fp]),
+    "e2fgvi_label_boxes": (C.c_int, [_fp, _i32, _i32, _i32, _fp, _fp]),
     "e2fgvi_psnr_ssim_workspace": (_i64, [_i32, _i32, _i32]),
     "e2fgvi_psnr_ssim": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _fp, _fp, _fp]),
     "e2fgvi_warp_error_workspace": (_i64, [_i32, _i32, _i32]),

@@ -1729,6 +1729,39 @@ def scene_diff(frames_u8):
     return out
 
 
+LABEL_TILE_W, LABEL_TILE_H = 64, 32        # csrc/video.hip LB_TW, LB_TH: the tile one workgroup labels in LDS
+
+
+def hole_components(masks_u8):
+    """masks_u8 [L,Hm,Wm] uint8 on the device (any non-zero byte is hole) -> (labels, boxes), both on the device: labels int32
+    [Hm,Wm] is 0 outside the footprint of the masks (the OR over the frames) and elsewhere the number 1 .. K of the pixel's
+    8-connected component, numbered in raster order of the components' first pixels (scipy.ndimage.label's order; the integers
+    do not depend on how the threads ran); boxes int32 [K,5], row k - 1 = (x0, y0, x1, y1, area) of component k, upper ends
+    exclusive as for hole_bbox.  One host read, of K, to size the table (csrc/video.hip label_*_kernel; include/e2fgvi_hip.h has
+    the definition)."""
+    lib = _L.load()
+    _u8(masks_u8, "masks")
+    if masks_u8.dim() != 3:
+        raise ValueError("masks must be [L,Hm,Wm], got %s" % (tuple(masks_u8.shape),))
+    L, Hm, Wm = masks_u8.shape
+    dev = masks_u8.device
+    if Hm * Wm == 0:
+        return torch.zeros((Hm, Wm), dtype=torch.int32, device=dev), torch.zeros((0, 5), dtype=torch.int32, device=dev)
+    nbytes = lib.e2fgvi_hole_label_workspace(Hm, Wm)
+    if nbytes < 0:
+        _L.check(int(nbytes), "hole_label_workspace")
+    with torch.cuda.device(dev):
+        work = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+        labels = torch.empty((Hm, Wm), dtype=torch.int32, device=dev)
+        count = torch.empty(1, dtype=torch.int32, device=dev)
+        _L.check(lib.e2fgvi_hole_label(_ptr(masks_u8), L, Hm, Wm, _ptr(work), _ptr(labels), _ptr(count), _stream()), "hole_label")
+        K = int(count.item())
+        boxes = torch.empty((K, 5), dtype=torch.int32, device=dev)
+        if K:
+            _L.check(lib.e2fgvi_label_boxes(_ptr(labels), Hm, Wm, K, _ptr(boxes), _stream()), "label_boxes")
+    return labels, boxes
+
+
 def _restore_geometry(lo, mask_lo, src, tabs, n, box):
     """the shape checks restore_u8 and restore_blend share -> (h, w, FH, FW, left, upper, Bw, Bh); n: frames of lo / mask_lo"""
     ytab, xtab, bx, cx, by, cy = (t for _, t in tabs)

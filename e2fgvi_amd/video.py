@@ -305,6 +305,115 @@ def hole_region(masks_u8, frame_wh, size, context=0.5, device=None):
     return plan_region(bbox, frame_wh, size, context)
 
 
+HOLE_COMPONENTS_MAX = 1024     # plan_holes: a footprint in more pieces than this is planned as one hole
+
+
+def _check_max_regions(max_regions):
+    """max_regions= as an int: an integer >= 1; ValueError otherwise (bools and non-integers included)"""
+    try:
+        ok = not isinstance(max_regions, (bool, np.bool_)) and int(max_regions) == max_regions and max_regions >= 1
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("max_regions must be an integer >= 1, got %r" % (max_regions,))
+    return int(max_regions)
+
+
+def _union_box(boxes):
+    return (min(b[0] for b in boxes), min(b[1] for b in boxes), max(b[2] for b in boxes), max(b[3] for b in boxes))
+
+
+def plan_holes(boxes, frame_wh, size, context=0.5, max_regions=4):
+    """The crop regions of inpaint_video(region="holes"): ``boxes`` holds the bounding box (x0, y0, x1, y1) of every connected
+    component of the hole in source pixels, upper ends exclusive, component k (numbered from 1) at boxes[k - 1] -- what
+    ops.hole_components reports, mapped to frame pixels -> [(region, [component numbers]), ...], one entry per group of components
+    that share a pass of the model, ordered by their lowest component number; region = (left, upper, right, lower) is plan_region of
+    the union of the group's boxes.  Every component starts as a group of its own.  Overlap step, repeated until no two regions
+    share a pixel: plan every group's region; the connected sets of the "regions overlap" relation become one group each.  Cap
+    step, while more than ``max_regions`` groups remain: the pair g < h whose union box has the smallest area is merged (ties: the
+    lowest g, then the lowest h), and the overlap step runs again.  So the regions are pairwise disjoint, each contains all of its
+    components and none contains a pixel of another group's component; max_regions = 1 is plan_region of the union of all boxes.
+    More than HOLE_COMPONENTS_MAX components plan one group around all of them: a footprint that fragmented has no holes worth
+    passes of their own, and the planner stays O(K^2) on a bounded K.  Exact integer and rational arithmetic, host code only.
+    max_regions not an integer >= 1 (a bool or 1.5 included), or an argument plan_region refuses, raise ValueError."""
+    max_regions = _check_max_regions(max_regions)
+    frame_wh = tuple(int(v) for v in frame_wh)
+    plan_region(None, frame_wh, size, context)                      # the checks that do not depend on a box
+    gbox = [_check_box(b, frame_wh) for b in boxes]
+    groups = [[k + 1] for k in range(len(gbox))]
+    if not groups:
+        return []
+    if len(groups) > HOLE_COMPONENTS_MAX:
+        groups, gbox = [[k for g in groups for k in g]], [_union_box(gbox)]
+    planned = {}
+
+    def region(b):
+        if b not in planned:
+            planned[b] = plan_region(b, frame_wh, size, context)
+        return planned[b]
+
+    def merge(sets):
+        """sets: lists of group indices -> the groups and boxes after each set became one group, ordered by lowest component"""
+        new = sorted((sorted(k for g in s for k in groups[g]), _union_box([gbox[g] for g in s])) for s in sets)
+        return [g for g, _ in new], [b for _, b in new]
+
+    while True:
+        while len(groups) > 1:                                      # the overlap step
+            R = np.array([region(b) for b in gbox], dtype=np.int64)
+            hit = (R[:, None, 0] < R[None, :, 2]) & (R[None, :, 0] < R[:, None, 2]) & \
+                  (R[:, None, 1] < R[None, :, 3]) & (R[None, :, 1] < R[:, None, 3])
+            np.fill_diagonal(hit, False)
+            if not hit.any():
+                break
+            seen, sets = set(), []
+            for g in range(len(groups)):
+                if g in seen:
+                    continue
+                seen.add(g)
+                todo, cur = [g], []
+                while todo:
+                    a = todo.pop()
+                    cur.append(a)
+                    for b in np.nonzero(hit[a])[0].tolist():
+                        if b not in seen:
+                            seen.add(b)
+                            todo.append(b)
+                sets.append(cur)
+            groups, gbox = merge(sets)
+        if len(groups) <= max_regions:
+            break
+        B = np.array(gbox, dtype=np.int64)                          # the cap step
+        area = (np.maximum(B[:, None, 2], B[None, :, 2]) - np.minimum(B[:, None, 0], B[None, :, 0])) * \
+               (np.maximum(B[:, None, 3], B[None, :, 3]) - np.minimum(B[:, None, 1], B[None, :, 1]))
+        area[np.tril_indices(len(groups))] = np.iinfo(np.int64).max
+        g, h = divmod(int(np.argmin(area)), len(groups))            # the first minimum in row-major order: lowest g, then lowest h
+        groups, gbox = merge([[g, h]] + [[k] for k in range(len(groups)) if k not in (g, h)])
+    return [(region(b), g) for g, b in zip(groups, gbox)]
+
+
+def hole_regions(masks_u8, frame_wh, size, context=0.5, max_regions=4, device=None):
+    """The boxes inpaint_video(region="holes") uses for these masks, as hole_region and track_regions report theirs: masks_u8 uint8
+    [L,Hm,Wm] (an array, or a tensor that is used where it is when on the device) -> [(left, upper, right, lower), ...] of the
+    (W, H) frames, pairwise disjoint, [] without a hole pixel.  The footprint of the masks over all frames is labelled on the
+    device (ops.hole_components: 8-connected components and their boxes; one host read of their number and one of the table),
+    every component's box goes from mask pixels to frame pixels like hole_region's (floor for the lower ends, ceil for the upper
+    ends), and plan_holes groups them."""
+    max_regions = _check_max_regions(max_regions)
+    frame_wh = tuple(int(v) for v in frame_wh)
+    plan_region(None, frame_wh, size, context)                      # from the arguments alone, before any upload
+    m = _upload(masks_u8, device)
+    if m.dim() != 3:
+        raise ValueError("masks must be uint8 [L,Hm,Wm], got %s" % (tuple(m.shape),))
+    mask_wh = (int(m.shape[2]), int(m.shape[1]))
+    _, table = ops.hole_components(m)
+    if table.shape[0] == 0:
+        return []
+    if table.shape[0] > HOLE_COMPONENTS_MAX:                        # one group around all of them: the box of region="hole"
+        return [hole_region(m, frame_wh, size, context)]
+    boxes = [_scale_box(row[:4], mask_wh, frame_wh) for row in table.cpu().tolist()]
+    return [r for r, _ in plan_holes(boxes, frame_wh, size, context, max_regions)]
+
+
 def plan_track(frame_boxes, windows, frame_wh, size, context=0.5):
     """The crop regions of inpaint_video(region="track"), one per window of plan_windows: ``frame_boxes`` holds every frame's hole
     bounding box (x0, y0, x1, y1) in source pixels, upper ends exclusive; None, or a box with x1 <= x0 or y1 <= y0, is a frame
@@ -602,7 +711,7 @@ def prepare_masks(masks_u8, size_hw, device, dilate=True, box=None, ids=None):
 @torch.no_grad()
 def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, num_ref=-1, dilate=True,
                   device=None, pad=True, batch_windows=1, keep_float=False, in_flight=1, size=None, reuse=False, restore=False,
-                  region=None, context=0.5, feather=0, scenes=None):
+                  region=None, context=0.5, feather=0, scenes=None, max_regions=4):
     """frames_u8: uint8 [L,H,W,3]; masks_u8: [L,Hm,Wm] (non-zero = hole; resized to the frames with NEAREST like
     read_mask).  Returns uint8 [L,H,W,3] composited frames, computed like test.py:129-179.
     ``model(masked[b,t,3,H',W'], n_local) -> (pred[b*t,3,H',W'], _)`` on the device.
@@ -683,7 +792,19 @@ def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, 
     hard cuts only, no fades or dissolves.  Every driver takes its windows from that one list (sequential, in_flight, batch_windows --
     windows of equal shape may share a forward across scenes: clips are independent --, reuse, whose plan then holds no pair
     across a cut, and region="track").  region="hole" still plans ONE box over the whole video, not one per scene.  None (or [])
-    is the one-shot path of a call without the argument and launches nothing."""
+    is the one-shot path of a call without the argument and launches nothing.
+
+    ``region`` = "holes" (with ``size`` and restore=True; ValueError otherwise) inpaints separate holes separately: a logo in a
+    corner and a subtitle band have a bounding box that is nearly the whole frame, so "hole" would show the model a shrunk frame.
+    The footprint of the masks over all frames is split into its 8-connected components on the device and plan_holes groups them
+    into at most ``max_regions`` (an integer >= 1, ValueError otherwise) pairwise disjoint boxes B_1 .. B_G (hole_regions tells
+    which).  The result is the caller's frames with the bytes inside every B_g replaced by the bytes inside B_g of
+    inpaint_video(..., region=B_g, restore=True) with every other option as given -- every pass reads the caller's frames, never
+    another pass's result, so their order does not matter.  The frames and masks are uploaded once, scenes="auto" is detected
+    once, and every pass pastes into the previous pass's frames, where its own box still holds the source.  It splits in space as
+    "track" splits in time, and works with in_flight, batch_windows, reuse, feather, scenes and dilate, since each pass is the
+    explicit-box path.  The cost is G passes of the model over the video.  No hole pixel: the source comes back and the model is
+    never called.  G = 1 (max_regions = 1 always) takes the path of region="hole" and returns its bytes."""
     if scenes is not None and not (isinstance(scenes, str) and scenes == "auto"):
         if isinstance(scenes, str):
             raise ValueError('scenes must be None, "auto" or a list of frame numbers, got %r' % (scenes,))
@@ -693,15 +814,16 @@ def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, 
         raise ValueError("feather= ramps the paste-back of restore=True into the source frames: without restore there is no seam "
                          "to feather")
     box = None
-    track = False
+    track = holes = False
     if region is not None:
         if size is None:
             raise ValueError("region= names the part of the frames that size= resizes for the model: without size there is no "
                              "region to cut")
         if isinstance(region, str):
-            if region not in ("hole", "track"):
-                raise ValueError('region must be None, "hole", "track" or (left, upper, right, lower), got %r' % (region,))
+            if region not in ("hole", "track", "holes"):
+                raise ValueError('region must be None, "hole", "track", "holes" or (left, upper, right, lower), got %r' % (region,))
             track = region == "track"
+            holes = region == "holes"
         else:
             box = _check_box(region, (frames_u8.shape[2], frames_u8.shape[1]))
     if track:
@@ -717,6 +839,11 @@ def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, 
         if in_flight > 1:
             raise ValueError('region="track" pastes and blends every window at source size in window order on one stream: in_flight '
                              "must be 1, got %d" % in_flight)
+    if holes:
+        max_regions = _check_max_regions(max_regions)
+        if not restore:
+            raise ValueError('region="holes" gives every group of holes a box of its own, so the passes\' results exist together only '
+                             "at the source size: restore must be True")
     if restore:
         if size is None:
             raise ValueError("restore=True pastes the result back into frames that size= resized: without size there is nothing "
@@ -747,15 +874,41 @@ def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, 
     if track:
         return _inpaint_track(model, source, masks_d, tuple(int(v) for v in size),
                               plan_windows(source.shape[0], neighbor_stride, ref_length, num_ref, scenes), dilate, pad, context, feather)
-    mask_box = None
+    run = lambda b, paste=None: _inpaint_box(model, source, masks_d, b, size, scenes, neighbor_stride, ref_length, num_ref, dilate, pad,
+                                             batch_windows, keep_float, in_flight, reuse, restore, feather, paste)
     if region is not None:
         frame_wh = (source.shape[2], source.shape[1])
-        if box is None:
+        if holes:
+            regions = hole_regions(masks_d, frame_wh, size, context, max_regions)
+            if not regions:
+                return source.cpu().numpy()
+            if len(regions) > 1:
+                # a pass pastes its box into the frames the pass before it returned: the boxes are disjoint, so inside its own box
+                # those still are the source, which is all the paste reads of them there (the ramp of feather= included)
+                out = source
+                for b in regions:
+                    out = run(b, out)
+                return out.cpu().numpy()
+            box = regions[0]                            # one group: the box and the path of region="hole"
+        elif box is None:
             box = hole_region(masks_d, frame_wh, size, context)
         if box == (0, 0) + frame_wh:
             box = None                                  # the whole frame: the path (and the bytes) of region=None
-        else:
-            mask_box = _scale_box(box, frame_wh, (masks_d.shape[2], masks_d.shape[1]))
+    out = run(box)
+    return out if keep_float else out.cpu().numpy()
+
+
+def _inpaint_box(model, source, masks_d, box, size, scenes, neighbor_stride, ref_length, num_ref, dilate, pad, batch_windows,
+                 keep_float, in_flight, reuse, restore, feather, paste=None):
+    """inpaint_video after the argument checks, the uploads and the choice of the box: source uint8 [L,H,W,3] and masks_d uint8
+    [L,Hm,Wm] on the device, ``box`` None (the whole frame) or a checked box that is not the whole frame, ``scenes`` None or a
+    checked list -> the device tensor of the result: fp32 [L,h,w,3] with keep_float, else uint8.  ``paste`` (with restore): the
+    frames the box is pasted into in place of the source -- region="holes" hands every pass the frames of the pass before."""
+    device = source.device
+    frames_d = source
+    mask_box = None
+    if box is not None:
+        mask_box = _scale_box(box, (source.shape[2], source.shape[1]), (masks_d.shape[2], masks_d.shape[1]))
     if size is not None:
         frames_d = resize_frames(frames_d, size, box=box)   # on the caller's stream, before any stream below waits on it
     L, h, w, _ = frames_d.shape
@@ -878,8 +1031,8 @@ def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, 
     if keep_float:
         return comp
     if restore:
-        return restore_frames(ops.float_to_u8(comp), masks01, source, box=box, feather=feather).cpu().numpy()
-    return ops.float_to_u8(comp).cpu().numpy()
+        return restore_frames(ops.float_to_u8(comp), masks01, source if paste is None else paste, box=box, feather=feather)
+    return ops.float_to_u8(comp)
 
 
 def _touched(k, windows, boxes):

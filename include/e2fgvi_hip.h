@@ -168,6 +168,25 @@ int e2fgvi_scatter_slabs(const void* rows, const int32_t* ids, int32_t n, int64_
  * and the same in every run.  L >= 2, H, W >= 1, H * W < 2^31 (E2FGVI_EINVAL otherwise, from both entries). */
 int64_t e2fgvi_scene_diff_workspace(int32_t L, int32_t H, int32_t W);
 int e2fgvi_scene_diff(const uint8_t* frames, int32_t L, int32_t H, int32_t W, void* workspace, int64_t* out, void* stream);
+/* Connected components of the hole's footprint (video.hole_regions / inpaint_video(region="holes"): holes far apart get a crop
+ * region each).  masks uint8 [L,Hm,Wm], any non-zero byte is hole:
+ *   U[y][x] = 1 iff masks[l][y][x] != 0 for some l;   labels[y][x] = 0 where U is 0, elsewhere the number 1 .. K of the pixel's
+ *   8-connected component of U, the components numbered in raster order of their first pixel (smallest y * Wm + x);  count[0] = K.
+ * The numbering is canonical: the integers do not depend on the order in which threads or atomics ran, and they are the ones
+ * scipy.ndimage.label(U, np.ones((3, 3))) gives.  labels int32 [Hm][Wm] and count int32 [1] on the device, 4-byte aligned.
+ * L == 0 (masks may be null) or masks without a hole pixel give labels of 0 and K = 0.  Hm, Wm >= 1 and Hm * Wm < 2^31
+ * (E2FGVI_EINVAL otherwise, from all three entries).  `workspace`: e2fgvi_hole_label_workspace(Hm, Wm) bytes, caller-owned,
+ * 16-byte aligned (an int32 rank per pixel, the footprint bytes, a counter per 1024 pixels, each part a multiple of 16 bytes),
+ * its contents on entry do not matter.  A fixed number of launches for a given (Hm, Wm), no host read: the OR over
+ * the frames, a union-find per tile in LDS, a lock-free merge across the tile borders, flatten, a scan of the roots, the dense
+ * numbers.  The forest keeps parent[i] <= i and only ever lowers an entry (atomicMin), so no thread waits for another. */
+int64_t e2fgvi_hole_label_workspace(int32_t Hm, int32_t Wm);
+int e2fgvi_hole_label(const uint8_t* masks, int32_t L, int32_t Hm, int32_t Wm, void* workspace, int32_t* labels, int32_t* count,
+                      void* stream);
+/* The table of the components above: boxes int32 [K][5] on the device, boxes[k-1] = (x0, y0, x1, y1, area) of the pixels with
+ * labels[y][x] == k, upper ends exclusive as for e2fgvi_hole_bbox.  K >= 0 is what e2fgvi_hole_label counted (K == 0 launches
+ * nothing); a label outside [1, K] is skipped.  Runs and tiles are reduced in registers and LDS in front of the global atomics. */
+int e2fgvi_label_boxes(const int32_t* labels, int32_t Hm, int32_t Wm, int32_t K, int32_t* boxes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * evaluate.py metrics (core/metrics.py:20-56): per image pair of fp32 NHWC [N,H,W,3] frames in
