@@ -85,6 +85,8 @@ def build(force=False, verbose=False, nopk_all=False, lib=None, tag=None, define
             verify_no_scratch(objdir)
             verify_no_scratch(objdir, "conv_bf16x.o", "conv_halo_x3_kernel", "split-operand halo")
             verify_no_scratch(objdir, "video.o", "restore_u8_kernel", "paste-back")
+            verify_no_scratch(objdir, "video.o", "overlay_stats_kernel", "overlay sums")
+            verify_overlay_prefetch(objdir)
     return out
 
 
@@ -129,7 +131,8 @@ def verify_no_scratch(objdir=None, obj="conv_bf16x.o", marker="ELb0ELi2ELb1EEE",
     """The ping-pong instantiations of conv_bf16x_kernel (template tail `false, 2, true`) keep 128 accumulator registers in place
     across four barriers per K-step; two ways of writing that loop made hipcc spill 414 registers or copy the kernel arguments to
     scratch without a warning (csrc/conv_bf16x.hip, PP).  Fails the build when one of them has a private segment or a spill.
-    Also run over the four instantiations of restore_u8_kernel (video.o): the feathered ones hold five LDS phases in one kernel."""
+    Also run over the four instantiations of restore_u8_kernel (video.o): the feathered ones hold five LDS phases in one kernel;
+    and over the four of overlay_stats_kernel, which keeps 24 sums and the next frame's 9 words in registers across its frame loop."""
     import re
     import shutil
     import tempfile
@@ -258,6 +261,53 @@ def verify_wino_waits(objdir=None, objects=("conv_wino.o", "conv_wino_x3.o", "co
     if not loops:
         raise RuntimeError("verify_wino_waits: no K loop with marked waits found (disassembly format changed?)")
     return loops
+
+
+def verify_overlay_prefetch(objdir=None, obj="video.o", items=3):
+    """overlay_stats_kernel (csrc/video.hip) asks for the next frame's bytes in front of its one barrier per frame and uses them
+    only at the top of the next trip: the loads must be in flight across the barrier and the sums behind it.  Written with the
+    loads inside divergent branches, hipcc waited for every one of them on the spot (``s_waitcnt vmcnt(0)`` behind each load, in
+    front of the barrier) without a word.  For the two instantiations that load four pixels at once (template tail `false`) this
+    check finds the frame loop -- the innermost backward branch around the ``s_barrier`` and the loads -- and requires that its
+    ``global_load_dwordx3`` are OV_ITEMS = 3, that the path from the first of them over the back edge to the barrier holds no other
+    branch, and that no ``s_waitcnt`` on that path names vmcnt.  Returns the number of kernels checked; raises RuntimeError."""
+    objdir = objdir or os.path.join(CSRC, "build")
+    if not os.path.exists(OBJDUMP):
+        return 0
+    found = 0
+    for name, ins in _kernels(device_isa(os.path.join(objdir, obj))).items():
+        if "overlay_stats_kernel" not in name or "ELb0EEE" not in name:
+            continue
+        found += 1
+        what = "%s: %s" % (obj, name[:70])
+        addr_to_idx = {a: i for i, (a, _, _) in enumerate(ins)}
+        bars = [i for i, (_, mn, _) in enumerate(ins) if mn == "s_barrier"]
+        if len(bars) != 1:
+            raise RuntimeError("%s: %d barriers where the frame loop has one" % (what, len(bars)))
+        bar, spans = bars[0], []
+        for i, (a, mn, ops_) in enumerate(ins):
+            if mn.startswith("s_cbranch") or mn == "s_branch":
+                off = int(ops_.split()[0])                 # unsigned 16-bit word offset from the next instruction
+                tgt = addr_to_idx.get(a + 4 + 4 * (off - 65536 if off >= 32768 else off))
+                # the last frame of a chunk goes back to the barrier without loads: that back edge is not the one looked for
+                if tgt is not None and tgt <= bar <= i and any(ins[k][1] == "global_load_dwordx3" for k in range(tgt, i + 1)):
+                    spans.append((i - tgt, tgt, i))
+        if not spans:
+            raise RuntimeError("%s: no backward branch around the barrier (disassembly format changed?)" % what)
+        _, lo, hi = min(spans)
+        loads = [i for i in range(lo, hi + 1) if ins[i][1] == "global_load_dwordx3"]
+        if len(loads) != items or loads[0] < bar:
+            raise RuntimeError("%s: %d global_load_dwordx3 in the frame loop, the first %s the barrier; expected %d behind it"
+                               % (what, len(loads), "in front of" if loads and loads[0] < bar else "behind", items))
+        path = ins[loads[0]:hi] + ins[lo:bar]
+        for a, mn, ops_ in path:
+            if mn.startswith("s_cbranch") or mn == "s_branch" or mn == "s_endpgm":
+                raise RuntimeError("%s: a branch at 0x%x between the frame loop's loads and its barrier" % (what, a))
+            if mn == "s_waitcnt" and "vmcnt" in ops_:
+                raise RuntimeError("%s: s_waitcnt %s at 0x%x waits for the next frame's loads in front of the barrier" % (what, ops_, a))
+    if found != 2:
+        raise RuntimeError("verify_overlay_prefetch: %d instantiations of overlay_stats_kernel<., false> in %s, expected 2" % (found, obj))
+    return found
 
 
 def _vregs(text):

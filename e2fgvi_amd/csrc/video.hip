@@ -844,6 +844,217 @@ __global__ __launch_bounds__(NTH) void scene_diff_kernel(const unsigned* __restr
     }
 }
 
+// Static overlays (video.overlay_mask): per-pixel sums of the luma gradient over the frames, integers only.  With the scene
+// detector's luma Y = (77 R + 150 G + 29 B + 128) >> 8 and clamped borders
+//   gx = Y[y][min(x+1, W-1)] - Y[y][max(x-1, 0)],  gy = Y[min(y+1, H-1)][x] - Y[max(y-1, 0)][x]   per frame,
+//   stats[0] = Sx = sum gx,  stats[1] = Sy = sum gy,  stats[2] = M = sum (|gx| + |gy|)   over the L frames, int32 [3][H][W].
+// One read of the frames: a workgroup owns an OV_TW x OV_TH pixel tile and a chunk of consecutive frames.  Per frame the tile's
+// luma with its one-pixel halo goes to LDS as bytes: a work item is four consecutive pixels of a halo row, 12 bytes read with one
+// load at whatever alignment the pixels have (no byte outside the frame's row is read); an item that hangs over the frame's left
+// or right edge loads the nearest four pixels of its row instead and a byte permute of the four lumas repeats the edge column
+// (frames narrower than four pixels have an instantiation of their own that reads byte by byte).  Which item a thread has does
+// not depend on the frame, so offsets and permutes are worked out once in front of the frame loop and every load in the loop is
+// unconditional: a frame's three loads leave back to back, before the barrier, and are waited for only at the top of the next
+// trip, behind the barrier and the sums of this one (the build checks the generated code for that: build.py
+// verify_overlay_prefetch).  The luma tile is double buffered (one barrier per frame), and a thread keeps the three sums of its
+// eight pixels -- one column, eight rows: a wave stores whole 256-byte rows -- in registers across the chunk.  Chunks of one tile
+// meet in the planes with integer global atomic adds (the entry zeroes the planes first); a single chunk stores.  Sums of
+// integers: exact in any arrival order.
+constexpr int OV_TW = 64, OV_TH = 32;                              // the pixel tile of a workgroup
+constexpr int OV_PER = OV_TH / (NTH / OV_TW);                      // rows per thread: 8
+constexpr int OV_GROUPS = (OV_TW + 2 + 3) / 4;                     // four-pixel items per halo row: 17
+constexpr int OV_ITEMS = ((OV_TH + 2) * OV_GROUPS + NTH - 1) / NTH;  // items per thread: 3
+constexpr int OV_PITCH = OV_GROUPS * 4;                            // bytes per luma row in LDS (17 dwords: odd)
+constexpr int OV_CHUNK = 8;                                        // ops.OVERLAY_CHUNK: no chunk of frames is shorter (unless L is)
+constexpr int OV_BLOCKS = 2048;                                    // workgroups the chunking aims for (8 per CU)
+constexpr int OV_LMAX = 1 << 22;                                   // M <= 510 L stays below 2^31
+constexpr int OV_RMAX = 16;                                        // ops.OVERLAY_RADIUS_MAX
+static_assert(OV_TW == 64 && NTH % OV_TW == 0 && OV_TH % (NTH / OV_TW) == 0, "a lane per tile column");
+
+struct OvRaw { unsigned d0, d1, d2; };                             // four pixels: 12 bytes in memory order
+
+// frames narrower than four pixels (OvItem::narrow): the item's four pixels byte by byte at clamped columns
+__device__ __forceinline__ OvRaw ov_load_narrow(const unsigned char* __restrict__ row, int gx0, int W) {
+    unsigned b[12];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        int x = gx0 + j;
+        x = x < 0 ? 0 : (x > W - 1 ? W - 1 : x);
+        const unsigned char* q = row + 3LL * x;
+        b[3 * j] = q[0]; b[3 * j + 1] = q[1]; b[3 * j + 2] = q[2];
+    }
+    OvRaw v;
+    v.d0 = b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24);
+    v.d1 = b[4] | (b[5] << 8) | (b[6] << 16) | (b[7] << 24);
+    v.d2 = b[8] | (b[9] << 8) | (b[10] << 16) | (b[11] << 24);
+    return v;
+}
+
+// the four lumas, pixel j in byte j: a pixel's three bytes are brought into one dword (v_alignbyte_b32) and weighed by one
+// v_dot4_u32_u8 with the rounding 128 as its addend; the fourth byte of the dword meets a weight of 0
+__device__ __forceinline__ unsigned ov_luma4(const OvRaw& v) {
+    constexpr unsigned K = 77u | (150u << 8) | (29u << 16);
+    const unsigned y0 = __builtin_amdgcn_udot4(v.d0, K, 128u, false) >> 8;
+    const unsigned y1 = __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(v.d1, v.d0, 3u), K, 128u, false) >> 8;
+    const unsigned y2 = __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(v.d2, v.d1, 2u), K, 128u, false) >> 8;
+    const unsigned y3 = __builtin_amdgcn_udot4(v.d2, K << 8, 128u, false) >> 8;
+    return y0 | (y1 << 8) | (y2 << 16) | (y3 << 24);
+}
+
+template <bool ATOMIC, bool NARROW>
+__global__ __launch_bounds__(NTH) void overlay_stats_kernel(const unsigned char* __restrict__ frames, int* __restrict__ stats, int L,
+                                                            int H, int W, int ntx) {
+    __shared__ unsigned s_y[2][(OV_TH + 2) * OV_GROUPS];
+    const int tid = threadIdx.x;
+    const int ty = blockIdx.x / ntx, tx = blockIdx.x - ty * ntx;
+    const int x0 = tx * OV_TW, y0 = ty * OV_TH;
+    const int tw = W - x0 < OV_TW ? W - x0 : OV_TW, th = H - y0 < OV_TH ? H - y0 : OV_TH;   // the tile's pixels inside the frame
+    const int ngrp = (tw + 2 + 3) / 4, nitems = (th + 2) * ngrp;   // the halo rows and items this tile needs
+    // the chunks split the L frames evenly: chunk c of n takes frames [c L / n, (c + 1) L / n), lengths that differ by one at most
+    const int l0 = (int)((long long)blockIdx.y * L / gridDim.y), l1 = (int)(((long long)blockIdx.y + 1) * L / gridDim.y);
+    if (l0 >= l1) return;                               // block-uniform; the entry plans no more chunks than frames
+    const long long fbytes = 3LL * H * W;
+    // this thread's items.  off: the byte in a frame where the item's load starts -- the item's own first pixel, or, for an item
+    // that hangs over the frame's left or right edge, the nearest four pixels that lie in its row (W >= 4); sel: which of the four
+    // loaded pixels each of the item's pixels is (v_perm_b32 on the four lumas), 0 1 2 3 unless a column was clamped; slot: its
+    // dword in LDS.  A thread without a k-th item loads the frame's first four pixels and stores nothing: every load below is
+    // unconditional, so the three of a frame leave back to back and nothing waits for them in front of the barrier.
+    long long off[OV_ITEMS];
+    unsigned sel[OV_ITEMS];
+    int gx0[OV_ITEMS], slot[OV_ITEMS];
+    bool have[OV_ITEMS];
+#pragma unroll
+    for (int k = 0; k < OV_ITEMS; ++k) {
+        const int i = tid + k * NTH;
+        have[k] = i < nitems;
+        const int r = have[k] ? i / ngrp : 0, g = have[k] ? i - r * ngrp : 0;
+        int yy = have[k] ? y0 - 1 + r : 0;
+        yy = yy < 0 ? 0 : (yy > H - 1 ? H - 1 : yy);
+        gx0[k] = have[k] ? x0 - 1 + 4 * g : 0;
+        slot[k] = r * OV_GROUPS + g;
+        off[k] = 3LL * yy * W;
+        sel[k] = 0x03020100u;
+        if (!NARROW) {
+            int w0 = gx0[k] < 0 ? 0 : gx0[k];
+            w0 = w0 > W - 4 ? W - 4 : w0;
+            off[k] += 3LL * w0;
+            sel[k] = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                int x = gx0[k] + j;
+                x = x < 0 ? 0 : (x > W - 1 ? W - 1 : x);
+                sel[k] |= (unsigned)(x - w0) << (8 * j);
+            }
+        }
+    }
+    const int lx = tid & (OV_TW - 1), ly0 = (tid / OV_TW) * OV_PER;
+    int sx[OV_PER], sy[OV_PER], sm[OV_PER];
+#pragma unroll
+    for (int i = 0; i < OV_PER; ++i) sx[i] = sy[i] = sm[i] = 0;
+    OvRaw raw[OV_ITEMS];
+    const unsigned char* f = frames + (long long)l0 * fbytes;
+    auto load = [&](int k) {
+        if (NARROW) return ov_load_narrow(f + off[k], gx0[k], W);
+        OvRaw v;
+        __builtin_memcpy(&v, f + off[k], 12);           // one global_load_dwordx3 at any alignment
+        return v;
+    };
+#pragma unroll
+    for (int k = 0; k < OV_ITEMS; ++k) raw[k] = load(k);
+    for (int l = l0; l < l1; ++l) {
+        unsigned* const buf = s_y[(l - l0) & 1];
+#pragma unroll
+        for (int k = 0; k < OV_ITEMS; ++k) {
+            const unsigned y = ov_luma4(raw[k]);
+            if (have[k]) buf[slot[k]] = __builtin_amdgcn_perm(y, y, sel[k]);
+        }
+        if (l + 1 < l1) {                               // block-uniform; in flight across the barrier and the sums below
+            f += fbytes;
+#pragma unroll
+            for (int k = 0; k < OV_ITEMS; ++k) raw[k] = load(k);
+        }
+        __syncthreads();
+        // pixel (ly, lx) of the tile is byte (ly + 1, lx + 1) of the halo tile; a thread outside the frame reads bytes of the array
+        // that nobody wrote and drops the sums below
+        const unsigned char* yb = reinterpret_cast<const unsigned char*>(buf) + ly0 * OV_PITCH + lx;
+        int up = yb[1], mid = yb[OV_PITCH + 1];
+#pragma unroll
+        for (int i = 0; i < OV_PER; ++i) {
+            const unsigned char* q = yb + (i + 1) * OV_PITCH;
+            const int down = q[OV_PITCH + 1];
+            const int gx = (int)q[2] - (int)q[0], gy = down - up;
+            sx[i] += gx;
+            sy[i] += gy;
+            sm[i] += (gx < 0 ? -gx : gx) + (gy < 0 ? -gy : gy);
+            up = mid;
+            mid = down;
+        }
+        // the buffer written two frames on is this one: every thread has passed the next frame's barrier by then, after these reads
+    }
+    if (lx >= tw) return;
+    const long long N = (long long)H * W;
+#pragma unroll
+    for (int i = 0; i < OV_PER; ++i) {
+        if (ly0 + i >= th) break;
+        int* p = stats + (long long)(y0 + ly0 + i) * W + x0 + lx;
+        if (ATOMIC) {
+            atomicAdd(p, sx[i]);
+            atomicAdd(p + N, sy[i]);
+            atomicAdd(p + 2 * N, sm[i]);
+        } else {
+            p[0] = sx[i];
+            p[N] = sy[i];
+            p[2 * N] = sm[i];
+        }
+    }
+}
+
+// The persistent-edge map of those sums, dilated: E[y][x] = 1 iff M >= g_min L and 256 (|Sx| + |Sy|) >= coherence M (64-bit
+// products), D = E dilated by the (2 r + 1) x (2 r + 1) box clipped at the frame (outside counts as 0), count = the number of
+// set pixels of D.  A workgroup owns an OV_TW x OV_TH tile: E of the tile and its r-pixel halo goes to LDS as bytes, a row pass ORs
+// 2 r + 1 neighbours, a column pass ORs 2 r + 1 rows of that; a wave counts its set pixels with a ballot and adds them once.
+__global__ __launch_bounds__(NTH) void overlay_edges_kernel(const int* __restrict__ stats, int L, int H, int W, int g_min, int coherence,
+                                                            int radius, int ntx, unsigned char* __restrict__ out, int* __restrict__ count) {
+    __shared__ unsigned char s_e[OV_TH + 2 * OV_RMAX][OV_TW + 2 * OV_RMAX];
+    __shared__ unsigned char s_h[OV_TH + 2 * OV_RMAX][OV_TW];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int ty = blockIdx.x / ntx, tx = blockIdx.x - ty * ntx;
+    const int x0 = tx * OV_TW, y0 = ty * OV_TH;
+    const int hh = OV_TH + 2 * radius, hw = OV_TW + 2 * radius, win = 2 * radius + 1;
+    const long long N = (long long)H * W;
+    const long long need = (long long)g_min * L;
+    for (int r = wave; r < hh; r += NTH / 64) {
+        const int y = y0 - radius + r;
+        for (int c = lane; c < hw; c += 64) {
+            const int x = x0 - radius + c;
+            unsigned char e = 0;
+            if (y >= 0 && y < H && x >= 0 && x < W) {
+                const long long i = (long long)y * W + x;
+                const long long a = stats[i], b = stats[i + N], m = stats[i + 2 * N];
+                e = m >= need && 256LL * ((a < 0 ? -a : a) + (b < 0 ? -b : b)) >= (long long)coherence * m;
+            }
+            s_e[r][c] = e;
+        }
+    }
+    __syncthreads();
+    for (int r = wave; r < hh; r += NTH / 64) {
+        unsigned v = 0;
+        for (int k = 0; k < win; ++k) v |= s_e[r][lane + k];
+        s_h[r][lane] = (unsigned char)v;
+    }
+    __syncthreads();
+    int n = 0;
+    for (int i = 0; i < OV_PER; ++i) {
+        const int ly = wave * OV_PER + i;
+        unsigned v = 0;
+        for (int k = 0; k < win; ++k) v |= s_h[ly + k][lane];
+        const bool in = y0 + ly < H && x0 + lane < W;
+        if (in) out[(long long)(y0 + ly) * W + x0 + lane] = (unsigned char)v;
+        n += __popcll(__ballot(in && v));
+    }
+    if (lane == 0 && n) atomicAdd(count, n);
+}
+
 // Connected components of the hole's footprint (video.hole_regions: one crop region per group of holes).  U[y][x] = 1 iff some
 // frame's mask byte at (x, y) is non-zero; labels[y][x] = 0 where U is 0, else the number 1 .. K of the pixel's 8-connected
 // component, components numbered in raster order of their first pixel -- exact integers that do not depend on the order in which
@@ -1516,6 +1727,57 @@ extern "C" int e2fgvi_scene_diff(const uint8_t* frames, int32_t L, int32_t H, in
                            (long long*)out + l0);
         E2_LAUNCH_CHECK("scene_diff");
     }
+    return 0;
+}
+
+extern "C" int e2fgvi_overlay_stats(const uint8_t* frames, int32_t L, int32_t H, int32_t W, int32_t* stats, void* stream) {
+    E2_REQUIRE(frames && stats, E2FGVI_EINVAL, "overlay_stats: null pointer");
+    E2_REQUIRE(L >= 1 && L <= OV_LMAX, E2FGVI_EINVAL, "overlay_stats: needs 1 <= L <= 2^22 frames (the sums are int32), got %d", L);
+    E2_REQUIRE(H >= 1 && W >= 1 && (int64_t)H * W < (1LL << 31), E2FGVI_EINVAL,
+               "overlay_stats: frames must have H, W >= 1 and H * W < 2^31, got %d x %d", H, W);
+    E2_REQUIRE(((uintptr_t)stats & 3) == 0, E2FGVI_EINVAL, "overlay_stats: stats must be 4-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    // the chunking, from the shape alone: as many chunks as bring the grid to about OV_BLOCKS workgroups, but no more than leave
+    // every chunk OV_CHUNK frames or more (a chunk costs three atomic adds per pixel whatever its length); the kernel splits the
+    // frames evenly, so a chunk holds floor or ceil of L / nchunks frames
+    const int ntx = (W + OV_TW - 1) / OV_TW, nty = (H + OV_TH - 1) / OV_TH;
+    const long long ntiles = (long long)ntx * nty;
+    const long long want = (OV_BLOCKS + ntiles - 1) / ntiles, most = L / OV_CHUNK > 1 ? L / OV_CHUNK : 1;
+    const int nchunks = (int)(want > most ? most : want);
+    const dim3 grid((unsigned)ntiles, (unsigned)nchunks);
+    const bool narrow = W < 4;                          // no room for a four-pixel load in a row: the byte-wise instantiation
+    if (nchunks == 1) {
+        if (narrow) hipLaunchKernelGGL((overlay_stats_kernel<false, true>), grid, dim3(NTH), 0, st, frames, stats, L, H, W, ntx);
+        else hipLaunchKernelGGL((overlay_stats_kernel<false, false>), grid, dim3(NTH), 0, st, frames, stats, L, H, W, ntx);
+    } else {
+        // the planes the atomics add to start at zero on the stream of the launch
+        const hipError_t e = hipMemsetAsync(stats, 0, 3 * (size_t)H * W * sizeof(int32_t), st);
+        E2_REQUIRE(e == hipSuccess, (int)e, "overlay_stats: hipMemsetAsync failed: %s", hipGetErrorString(e));
+        if (narrow) hipLaunchKernelGGL((overlay_stats_kernel<true, true>), grid, dim3(NTH), 0, st, frames, stats, L, H, W, ntx);
+        else hipLaunchKernelGGL((overlay_stats_kernel<true, false>), grid, dim3(NTH), 0, st, frames, stats, L, H, W, ntx);
+    }
+    E2_LAUNCH_CHECK("overlay_stats");
+    return 0;
+}
+
+extern "C" int e2fgvi_overlay_edges(const int32_t* stats, int32_t L, int32_t H, int32_t W, int32_t g_min, int32_t coherence,
+                                    int32_t radius, uint8_t* out, int32_t* count, void* stream) {
+    E2_REQUIRE(stats && out && count, E2FGVI_EINVAL, "overlay_edges: null pointer");
+    E2_REQUIRE(L >= 1 && L <= OV_LMAX, E2FGVI_EINVAL, "overlay_edges: needs 1 <= L <= 2^22 frames, got %d", L);
+    E2_REQUIRE(H >= 1 && W >= 1 && (int64_t)H * W < (1LL << 31), E2FGVI_EINVAL,
+               "overlay_edges: the map must have H, W >= 1 and H * W < 2^31, got %d x %d", H, W);
+    E2_REQUIRE(g_min >= 1, E2FGVI_EINVAL, "overlay_edges: g_min must be >= 1, got %d", g_min);
+    E2_REQUIRE(coherence >= 1 && coherence <= 256, E2FGVI_EINVAL, "overlay_edges: coherence must be in [1, 256], got %d", coherence);
+    E2_REQUIRE(radius >= 0 && radius <= OV_RMAX, E2FGVI_EINVAL, "overlay_edges: radius must be in [0, %d], got %d", OV_RMAX, radius);
+    E2_REQUIRE(((uintptr_t)stats & 3) == 0 && ((uintptr_t)count & 3) == 0, E2FGVI_EINVAL,
+               "overlay_edges: stats and count must be 4-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const hipError_t e = hipMemsetAsync(count, 0, sizeof(int32_t), st);
+    E2_REQUIRE(e == hipSuccess, (int)e, "overlay_edges: hipMemsetAsync failed: %s", hipGetErrorString(e));
+    const int ntx = (W + OV_TW - 1) / OV_TW, nty = (H + OV_TH - 1) / OV_TH;
+    hipLaunchKernelGGL(overlay_edges_kernel, dim3((unsigned)((long long)ntx * nty)), dim3(NTH), 0, st, stats, L, H, W, g_min, coherence,
+                       radius, ntx, out, count);
+    E2_LAUNCH_CHECK("overlay_edges");
     return 0;
 }
 

@@ -1762,6 +1762,56 @@ def hole_components(masks_u8):
     return labels, boxes
 
 
+OVERLAY_TILE_W, OVERLAY_TILE_H = 64, 32    # csrc/video.hip OV_TW, OV_TH: the pixel tile of a workgroup of both overlay kernels
+OVERLAY_CHUNK = 8                          # csrc/video.hip OV_CHUNK: overlay_stats splits L frames into at most L // 8 chunks of
+                                           # equal length (to within one frame), so none is shorter; fewer than 16 frames are one chunk
+OVERLAY_FRAMES_MAX = 1 << 22               # csrc/video.hip OV_LMAX: more frames would overflow the int32 sums
+OVERLAY_RADIUS_MAX = 16                    # csrc/video.hip OV_RMAX: the largest dilation radius overlay_edges keeps in LDS
+
+
+def overlay_stats(frames_u8):
+    """frames_u8 [L,H,W,3] uint8 on the device, 1 <= L <= OVERLAY_FRAMES_MAX -> device int32 [3,H,W] = (Sx, Sy, M): per pixel the
+    sums over the frames of the luma gradient's two components and of |gx| + |gy|, central differences of the scene detector's
+    integer luma with clamped borders (csrc/video.hip overlay_stats_kernel; include/e2fgvi_hip.h has the definition).  One pass
+    over the frames, exact integers that do not depend on how the threads ran, no host read; overlay_edges thresholds them."""
+    lib = _L.load()
+    _u8(frames_u8, "frames")
+    if frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
+        raise ValueError("frames must be [L,H,W,3], got %s" % (tuple(frames_u8.shape),))
+    L, H, W, _ = frames_u8.shape
+    if not 1 <= L <= OVERLAY_FRAMES_MAX:
+        raise ValueError("overlay_stats needs between 1 and %d frames, got %d" % (OVERLAY_FRAMES_MAX, L))
+    if H * W == 0:
+        raise ValueError("overlay_stats needs frames with pixels, got %d x %d" % (H, W))
+    with torch.cuda.device(frames_u8.device):
+        out = torch.empty((3, H, W), dtype=torch.int32, device=frames_u8.device)
+        _L.check(lib.e2fgvi_overlay_stats(_ptr(frames_u8), L, H, W, _ptr(out), _stream()), "overlay_stats")
+    return out
+
+
+def overlay_edges(stats, L, g_min, coherence, radius):
+    """stats: overlay_stats's int32 [3,H,W] of L frames -> (D, count), both on the device.  A pixel is a persistent edge when
+    M >= g_min L and 256 (|Sx| + |Sy|) >= coherence M (64-bit integers); D uint8 [H,W] is 1 where the (2 radius + 1)-pixel box
+    around the pixel, clipped at the frame, holds a persistent edge and 0 elsewhere; count int32 [1] is the number of set pixels
+    of D.  Threshold and dilation are one launch (csrc/video.hip overlay_edges_kernel), no host read.  g_min >= 1, coherence in
+    [1, 256], radius in [0, OVERLAY_RADIUS_MAX], L in [1, OVERLAY_FRAMES_MAX]: integers (ValueError otherwise, bools included)."""
+    lib = _L.load()
+    _chk(stats, "stats", torch.int32)
+    if stats.dim() != 3 or stats.shape[0] != 3 or stats.shape[1] * stats.shape[2] == 0:
+        raise ValueError("stats must be [3,H,W] with H, W >= 1, got %s" % (tuple(stats.shape),))
+    for name, v, lo, hi in (("L", L, 1, OVERLAY_FRAMES_MAX), ("g_min", g_min, 1, 2 ** 31 - 1), ("coherence", coherence, 1, 256),
+                            ("radius", radius, 0, OVERLAY_RADIUS_MAX)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not lo <= v <= hi:
+            raise ValueError("%s must be an integer in [%d, %d], got %r" % (name, lo, hi, v))
+    _, H, W = stats.shape
+    with torch.cuda.device(stats.device):
+        out = torch.empty((H, W), dtype=torch.uint8, device=stats.device)
+        count = torch.empty(1, dtype=torch.int32, device=stats.device)
+        _L.check(lib.e2fgvi_overlay_edges(_ptr(stats), int(L), H, W, int(g_min), int(coherence), int(radius), _ptr(out), _ptr(count),
+                                          _stream()), "overlay_edges")
+    return out, count
+
+
 def _restore_geometry(lo, mask_lo, src, tabs, n, box):
     """the shape checks restore_u8 and restore_blend share -> (h, w, FH, FW, left, upper, Bw, Bh); n: frames of lo / mask_lo"""
     ytab, xtab, bx, cx, by, cy = (t for _, t in tabs)

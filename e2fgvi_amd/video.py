@@ -519,6 +519,89 @@ def detect_cuts(frames_u8, threshold=SCENE_THRESHOLD, min_scene=SCENE_MIN_LENGTH
     return cuts_from_scores(scene_scores(frames_u8, device), threshold, min_scene)
 
 
+OVERLAY_G_MIN = 32             # overlay_mask's defaults: DESIGN.md 3l has the measurements they were chosen from
+OVERLAY_COHERENCE = 224
+OVERLAY_RADIUS = 3
+OVERLAY_MIN_AREA = 256
+OVERLAY_MAX_FRACTION = 0.25
+
+
+def _check_overlay_args(g_min, coherence, radius, min_area, max_fraction):
+    def integer(v, lo, hi):
+        try:
+            return not isinstance(v, (bool, np.bool_)) and int(v) == v and lo <= v and (hi is None or v <= hi)
+        except (TypeError, ValueError):
+            return False
+    if not integer(g_min, 1, 2 ** 31 - 1):
+        raise ValueError("g_min must be an integer >= 1, got %r" % (g_min,))
+    if not integer(coherence, 1, 256):
+        raise ValueError("coherence must be an integer in (0, 256], got %r" % (coherence,))
+    if not integer(radius, 0, ops.OVERLAY_RADIUS_MAX):
+        raise ValueError("radius must be an integer in [0, %d], got %r" % (ops.OVERLAY_RADIUS_MAX, radius))
+    if not integer(min_area, 1, None):
+        raise ValueError("min_area must be an integer >= 1, got %r" % (min_area,))
+    try:
+        ok = not isinstance(max_fraction, (bool, np.bool_)) and 0 < max_fraction <= 1
+    except TypeError:
+        ok = False
+    if not ok:
+        raise ValueError("max_fraction must be in (0, 1], got %r" % (max_fraction,))
+    return int(g_min), int(coherence), int(radius), int(min_area)
+
+
+def _overlay_mask_device(x, g_min, coherence, radius, min_area, max_fraction):
+    """overlay_mask after the argument checks and the upload: x uint8 [L,H,W,3] on the device with L, H, W >= 1 -> device uint8
+    [H,W] of 0 / 255"""
+    L, H, W = (int(v) for v in x.shape[:3])
+    D, count = ops.overlay_edges(ops.overlay_stats(x), L, g_min, coherence, radius)
+    n = int(count.item())
+    if n > max_fraction * H * W:
+        raise ValueError("overlay_mask: %d of %d pixels (%.2f of the frame, more than max_fraction = %g) keep an edge over all %d "
+                         "frames -- a locked-off camera or too little motion makes the scenery itself static, and the mask would be a "
+                         "mask of the scenery: paint the mask by hand" % (n, H * W, n / float(H * W), max_fraction, L))
+    if n == 0:
+        return torch.zeros((H, W), dtype=torch.uint8, device=x.device)
+    # the components of the complement that touch no frame edge lie inside a contour: a ring's or a solid logo's inside
+    labels, table = ops.hole_components((1 - D).unsqueeze(0))
+    inner = (table[:, 0] > 0) & (table[:, 1] > 0) & (table[:, 2] < W) & (table[:, 3] < H)
+    filled = D | torch.cat([inner.new_zeros(1), inner]).to(torch.uint8)[labels.long()]
+    labels, table = ops.hole_components(filled.unsqueeze(0))
+    keep = table[:, 4] >= min_area
+    return torch.cat([keep.new_zeros(1), keep]).to(torch.uint8)[labels.long()] * 255
+
+
+def overlay_mask(frames_u8, g_min=OVERLAY_G_MIN, coherence=OVERLAY_COHERENCE, radius=OVERLAY_RADIUS, min_area=OVERLAY_MIN_AREA,
+                 max_fraction=OVERLAY_MAX_FRACTION, device=None):
+    """The mask of what stays put while the video moves -- a station logo, a watermark, a fixed caption -- from the frames alone:
+    frames_u8 uint8 [L,H,W,3] (an array, or a tensor that is used where it is when on the device) -> uint8 array [H,W] of 0 / 255,
+    the same hole for every frame (np.broadcast_to(mask, (L, H, W)) is what inpaint_video takes; masks_u8="overlay" does that).
+
+    Per pixel the device sums the gradient of the integer luma over the frames, (Sx, Sy), and its magnitude M = sum |gx| + |gy|
+    (ops.overlay_stats, one pass over the frames).  A pixel is a persistent edge when M >= g_min L -- an edge of mean strength
+    g_min -- and 256 (|Sx| + |Sy|) >= coherence M -- the edge kept its direction: an overlay's contour does, frame after frame,
+    also when the overlay is half transparent, while the gradients of moving content at a fixed pixel point anywhere and cancel.
+    The edge map is dilated by a (2 radius + 1)-pixel box (ops.overlay_edges), the components of its complement that touch no frame
+    edge are added -- the inside of a ring or of a solid logo -- and components of fewer than min_area pixels are dropped (8-connected
+    both times, ops.hole_components).  Exact integers: the same mask in every run.  One host read of the edge count and two of
+    component counts.
+
+    Known limit: a locked-off camera, or a pan too short for the scenery's edges to move off their pixels, makes the background
+    static too.  When more than max_fraction of the frame is set after the dilation the function raises ValueError saying so
+    instead of returning a mask of the scenery.  Faint overlays (recall falls below alpha 0.5) and overlays that
+    change -- subtitles, clocks -- are not found: they are not static.
+    g_min >= 1, 0 < coherence <= 256, 0 <= radius <= 16, min_area >= 1: integers; 0 < max_fraction <= 1; no bools (ValueError,
+    before any device work).  L = 0 raises ValueError; H W = 0 returns an empty array without a launch."""
+    g_min, coherence, radius, min_area = _check_overlay_args(g_min, coherence, radius, min_area, max_fraction)
+    if len(frames_u8.shape) != 4 or frames_u8.shape[3] != 3:
+        raise ValueError("frames must be uint8 [L,H,W,3], got %s" % (tuple(frames_u8.shape),))
+    L, H, W = (int(v) for v in frames_u8.shape[:3])
+    if L < 1:
+        raise ValueError("overlay_mask needs at least one frame, got %d" % L)
+    if H * W == 0:
+        return np.zeros((H, W), np.uint8)
+    return _overlay_mask_device(_upload(frames_u8, device), g_min, coherence, radius, min_area, max_fraction).cpu().numpy()
+
+
 def _check_ids(ids, length):
     """frame numbers for ids=: a sequence of integers in [0, length) (ValueError otherwise), or a device int32 tensor, which is
     used as it is -- the kernels check its range (a frame of zeros for a bad id), the host never reads it"""
@@ -716,6 +799,12 @@ def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, 
     read_mask).  Returns uint8 [L,H,W,3] composited frames, computed like test.py:129-179.
     ``model(masked[b,t,3,H',W'], n_local) -> (pred[b*t,3,H',W'], _)`` on the device.
 
+    ``masks_u8`` = "overlay" in place of masks: the hole is what stays put while the video moves (a station logo, a watermark, a
+    fixed caption), found on the device in the caller's frames as they come in, before any ``size`` resize, as scenes="auto" finds
+    its cuts: the result is the bytes of the call with np.broadcast_to(overlay_mask(frames_u8), (L, H, W)) for masks and every
+    other option as given (overlay_mask has the definition, the defaults and the limits; it raises ValueError when the scenery
+    itself is static).  No overlay found: the path of masks without a hole pixel.  Any other string raises ValueError.
+
     ``size`` = (width, height) resizes the uploaded frames on the device first, as test.py:97-104,127 does with PIL
     (resize_frames: bicubic, bit-exact); the masks are then NEAREST-resized straight to that size and the returned frames
     have it.  test.py uses (432, 240) for ``e2fgvi`` and (--width, --height) for ``e2fgvi_hq`` with --set_size.
@@ -805,6 +894,9 @@ def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, 
     "track" splits in time, and works with in_flight, batch_windows, reuse, feather, scenes and dilate, since each pass is the
     explicit-box path.  The cost is G passes of the model over the video.  No hole pixel: the source comes back and the model is
     never called.  G = 1 (max_regions = 1 always) takes the path of region="hole" and returns its bytes."""
+    overlay = isinstance(masks_u8, str)
+    if overlay and masks_u8 != "overlay":
+        raise ValueError('masks_u8 must be uint8 [L,Hm,Wm] masks or "overlay", got %r' % (masks_u8,))
     if scenes is not None and not (isinstance(scenes, str) and scenes == "auto"):
         if isinstance(scenes, str):
             raise ValueError('scenes must be None, "auto" or a list of frame numbers, got %r' % (scenes,))
@@ -868,7 +960,13 @@ def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, 
     else:
         frames_d = torch.as_tensor(np.ascontiguousarray(frames_u8)).to(device)
     source = frames_d                                   # restore=True: kept beside the resized frames, only read
-    masks_d = _upload(masks_u8, device)                 # once: the bounding box and the mask preparation read the same tensor
+    if overlay:                                         # on the frames at source size; the same hole in every frame
+        if source.shape[0] < 1 or source.shape[1] * source.shape[2] == 0:
+            raise ValueError('masks_u8="overlay" needs frames to find the overlay in, got %s' % (tuple(source.shape),))
+        masks_d = _overlay_mask_device(source, OVERLAY_G_MIN, OVERLAY_COHERENCE, OVERLAY_RADIUS, OVERLAY_MIN_AREA,
+                                       OVERLAY_MAX_FRACTION).unsqueeze(0).expand(source.shape[:3]).contiguous()
+    else:
+        masks_d = _upload(masks_u8, device)             # once: the bounding box and the mask preparation read the same tensor
     if isinstance(scenes, str):                         # "auto": on the frames at source size
         scenes = detect_cuts(source)
     if track:

@@ -187,6 +187,26 @@ int e2fgvi_hole_label(const uint8_t* masks, int32_t L, int32_t Hm, int32_t Wm, v
  * labels[y][x] == k, upper ends exclusive as for e2fgvi_hole_bbox.  K >= 0 is what e2fgvi_hole_label counted (K == 0 launches
  * nothing); a label outside [1, K] is skipped.  Runs and tiles are reduced in registers and LDS in front of the global atomics. */
 int e2fgvi_label_boxes(const int32_t* labels, int32_t Hm, int32_t Wm, int32_t K, int32_t* boxes, void* stream);
+/* Static overlays (video.overlay_mask: the mask of a station logo, a watermark or a fixed caption, from the frames themselves), in
+ * integers only.  frames uint8 [L,H,W,3]; with the luma of the scene detector and borders clamped, per frame
+ *   Y = (77 R + 150 G + 29 B + 128) >> 8,
+ *   gx = Y[y][min(x+1, W-1)] - Y[y][max(x-1, 0)],   gy = Y[min(y+1, H-1)][x] - Y[max(y-1, 0)][x],
+ * and over the L frames, per pixel,  Sx = sum gx,  Sy = sum gy,  M = sum (|gx| + |gy|):
+ *   stats int32 [3][H][W] = (Sx, Sy, M) on the device, 4-byte aligned, its contents on entry do not matter.
+ * An overlay's contour keeps the direction of its gradient frame after frame, also when the overlay is half transparent, so
+ * |sum G| stays close to sum |G|; the gradients of moving content change direction at a fixed pixel and cancel.
+ * One pass over the frames; the frames are split into chunks by a rule of (L, H, W) alone and the chunks meet with integer
+ * atomics: exact, and the same in every run.  1 <= L <= 2^22 (M <= 510 L fits int32), H, W >= 1, H * W < 2^31 (E2FGVI_EINVAL
+ * otherwise). */
+int e2fgvi_overlay_stats(const uint8_t* frames, int32_t L, int32_t H, int32_t W, int32_t* stats, void* stream);
+/* The persistent edges of those sums, dilated.  A pixel is a persistent edge when
+ *   M >= g_min * L   and   256 * (|Sx| + |Sy|) >= coherence * M        (both in 64 bits: the left side passes 2^31 from L = 16449 on);
+ * out uint8 [H][W] = D, 1 where a persistent edge lies in the pixel's (2 radius + 1) x (2 radius + 1) box and 0 elsewhere -- the
+ * box is clipped at the frame: outside counts as no edge -- and count int32 [1] (4-byte aligned) = the number of set pixels of D,
+ * both on the device, one launch.  L as for e2fgvi_overlay_stats (the number of frames the sums were taken over), g_min >= 1,
+ * 1 <= coherence <= 256, 0 <= radius <= 16 (E2FGVI_EINVAL otherwise). */
+int e2fgvi_overlay_edges(const int32_t* stats, int32_t L, int32_t H, int32_t W, int32_t g_min, int32_t coherence, int32_t radius,
+                         uint8_t* out, int32_t* count, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * evaluate.py metrics (core/metrics.py:20-56): per image pair of fp32 NHWC [N,H,W,3] frames in
