@@ -30,8 +30,8 @@ UNITS = [("error.hip", "error.o", []), ("conv.hip", "conv.o", []), ("conv.hip", 
          ("conv_bf16x.hip", "conv_bf16x.o", NOPK), ("conv_wino.hip", "conv_wino.o", NOPK), ("conv_wino.hip", "conv_wino_x3.o", NOPK + ["-DE2_WINO_X3=1"]), ("conv_wino4.hip", "conv_wino4.o", NOPK), ("conv_tail.hip", "conv_tail.o", NOPK),
          ("mdcn.hip", "mdcn.o", NOPK), ("attention.hip", "attention.o", []),
          ("attention_bf16.hip", "attention_bf16.o", NOPK), ("attention_x3.hip", "attention_x3.o", NOPK), ("misc.hip", "misc.o", NOPK),
-         ("video.hip", "video.o", NOPK), ("metrics.hip", "metrics.o", NOPK)]
-NOPK_OBJECTS = ("conv_nopk.o", "conv_bf16x.o", "conv_wino.o", "conv_wino4.o", "conv_wino_x3.o", "conv_tail.o", "mdcn.o", "attention_bf16.o", "attention_x3.o", "misc.o", "video.o", "metrics.o")
+         ("video.hip", "video.o", NOPK), ("yuv.hip", "yuv.o", NOPK), ("metrics.hip", "metrics.o", NOPK)]
+NOPK_OBJECTS = ("conv_nopk.o", "conv_bf16x.o", "conv_wino.o", "conv_wino4.o", "conv_wino_x3.o", "conv_tail.o", "mdcn.o", "attention_bf16.o", "attention_x3.o", "misc.o", "video.o", "yuv.o", "metrics.o")
 OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 
 
@@ -87,6 +87,7 @@ def build(force=False, verbose=False, nopk_all=False, lib=None, tag=None, define
             verify_no_scratch(objdir, "video.o", "restore_u8_kernel", "paste-back")
             verify_no_scratch(objdir, "video.o", "overlay_stats_kernel", "overlay sums")
             verify_overlay_prefetch(objdir)
+            verify_no_pk_u8(objdir)
     return out
 
 
@@ -125,6 +126,23 @@ def verify_isa(objdir=None):
         if bad or not isa:
             raise RuntimeError("%s: %s" % (obj, "%d packed-fp32 instructions in a unit that must have none" % len(bad) if isa
                                            else "no gfx950 code object found"))
+
+
+def verify_no_pk_u8(objdir=None):
+    """No unit may hold v_ashr_pk_u8_i32 / v_ashr_pk_i8_i32 (gfx950: shift two int32, clamp each to a byte, pack the pair into the
+    low half of the destination).  hipcc forms it from two clipped shifts that are packed into one word with other bytes and ORs
+    those bytes on top of the result; on the chip the bytes ORed on top came out wrong in csrc/yuv.hip's decoder (its store_bytes
+    has the account and the empty asm that keeps the pattern from forming).  Returns the number of objects read."""
+    import re
+    objdir = objdir or os.path.join(CSRC, "build")
+    if not os.path.exists(OBJDUMP):
+        return 0
+    for _, obj, _ in UNITS:
+        found = re.findall(r"v_ashr_pk_[ui]8_i32", device_isa(os.path.join(objdir, obj)))
+        if found:
+            raise RuntimeError("%s: %d v_ashr_pk_u8_i32 / v_ashr_pk_i8_i32 instructions: the bytes packed beside their result come out "
+                               "wrong on the chip (csrc/yuv.hip store_bytes)" % (obj, len(found)))
+    return len(UNITS)
 
 
 def verify_no_scratch(objdir=None, obj="conv_bf16x.o", marker="ELb0ELi2ELb1EEE", what="ping-pong"):

@@ -139,6 +139,8 @@ SYMBOLS = {
     "e2fgvi_label_boxes": (C.c_int, [_fp, _i32, _i32, _i32, _fp, _fp]),
     "e2fgvi_overlay_stats": (C.c_int, [_fp, _i32, _i32, _i32, _fp, _fp]),
     "e2fgvi_overlay_edges": (C.c_int, [_fp, _i32, _i32, _i32, _i32, _i32, _i32, _fp, _fp, _fp]),
+    "e2fgvi_yuv420_to_rgb": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i32), _fp]),
+    "e2fgvi_rgb_to_yuv420": (C.c_int, [_fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, C.POINTER(_i32), _fp]),
     "e2fgvi_psnr_ssim_workspace": (_i64, [_i32, _i32, _i32]),
     "e2fgvi_psnr_ssim": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _i32, _fp, _fp, _fp]),
     "e2fgvi_warp_error_workspace": (_i64, [_i32, _i32, _i32]),

@@ -1812,6 +1812,77 @@ def overlay_edges(stats, L, g_min, coherence, radius):
     return out, count
 
 
+YUV_LAYOUTS = {"nv12": 0, "i420": 1}       # E2FGVI_YUV_* / E2FGVI_CHROMA_* of include/e2fgvi_hip.h
+YUV_CHROMA = {"left": 0, "nearest": 1}
+
+
+def yuv_frame_hw(shape):
+    """(H, W) of 4:2:0 frames [L,3H/2,W]; ValueError unless the rows divide by 3 and H and W are even (from the shape alone)"""
+    if len(shape) != 3:
+        raise ValueError("4:2:0 frames must be [L,3H/2,W], got %s" % (tuple(shape),))
+    rows, W = int(shape[1]), int(shape[2])
+    if rows % 3:
+        raise ValueError("4:2:0 frames [L,3H/2,W] need a row count divisible by 3, got %d" % rows)
+    H = rows // 3 * 2
+    if H % 2 or W % 2:
+        raise ValueError("4:2:0 frames need even H and W, got %d x %d" % (H, W))
+    return H, W
+
+
+def _yuv_args(layout, coef, n):
+    if layout not in YUV_LAYOUTS:
+        raise ValueError('layout must be "nv12" or "i420", got %r' % (layout,))
+    vals = [int(v) for v in coef]
+    if len(vals) != n or any(isinstance(v, bool) or not isinstance(v, numbers.Integral) for v in coef):
+        raise ValueError("coef must be %d integers, got %r" % (n, coef))
+    return YUV_LAYOUTS[layout], (C.c_int32 * n)(*vals)
+
+
+def yuv420_to_rgb(x, layout, chroma, coef):
+    """x uint8 [L,3H/2,W] on the device, ``layout`` "nv12" / "i420", ``chroma`` "left" / "nearest", ``coef`` the six integers
+    (cy, crv, cgu, cgv, cbu, yo) -> uint8 [L,H,W,3] RGB on the device: one launch on the caller's stream (csrc/yuv.hip
+    yuv420_to_rgb_kernel; include/e2fgvi_hip.h has the definition), no host read."""
+    lib = _L.load()
+    _u8(x, "frames")
+    H, W = yuv_frame_hw(x.shape)
+    lay, cf = _yuv_args(layout, coef, 6)
+    if chroma not in YUV_CHROMA:
+        raise ValueError('chroma must be "left" or "nearest", got %r' % (chroma,))
+    L = x.shape[0]
+    with torch.cuda.device(x.device):
+        out = torch.empty((L, H, W, 3), dtype=torch.uint8, device=x.device)
+        _L.check(lib.e2fgvi_yuv420_to_rgb(_ptr(x), _ptr(out), L, H, W, lay, YUV_CHROMA[chroma], cf, _stream()), "yuv420_to_rgb")
+    return out
+
+
+def rgb_to_yuv420(rgb, layout, coef, like=None, like_rgb=None):
+    """rgb uint8 [L,H,W,3] on the device, H and W even, ``coef`` the ten integers (yr, yg, yb, ur, ug, ub, vr, vg, vb, yo) -> uint8
+    [L,3H/2,W] in ``layout`` on the device.  With ``like`` [L,3H/2,W] and ``like_rgb`` [L,H,W,3] (both or neither) the paste form:
+    the luma byte of a pixel whose three bytes equal like_rgb's and the chroma pair of a block of four such pixels are like's, the
+    rest is encoded.  One launch either way (csrc/yuv.hip rgb_to_yuv420_kernel), every output byte written once, no host read."""
+    lib = _L.load()
+    _u8(rgb, "rgb")
+    if rgb.dim() != 4 or rgb.shape[3] != 3:
+        raise ValueError("rgb must be [L,H,W,3], got %s" % (tuple(rgb.shape),))
+    L, H, W, _ = rgb.shape
+    if H % 2 or W % 2:
+        raise ValueError("4:2:0 frames need even H and W, got %d x %d" % (H, W))
+    lay, cf = _yuv_args(layout, coef, 10)
+    if (like is None) != (like_rgb is None):
+        raise ValueError("like and like_rgb come together")
+    if like is not None:
+        _u8(like, "like"); _u8(like_rgb, "like_rgb")
+        if tuple(like.shape) != (L, H // 2 * 3, W) or like_rgb.shape != rgb.shape or like.device != rgb.device \
+                or like_rgb.device != rgb.device:
+            raise ValueError("like must be [L,3H/2,W] and like_rgb [L,H,W,3] on the device of rgb %s, got %s and %s"
+                             % (tuple(rgb.shape), tuple(like.shape), tuple(like_rgb.shape)))
+    with torch.cuda.device(rgb.device):
+        out = torch.empty((L, H // 2 * 3, W), dtype=torch.uint8, device=rgb.device)
+        _L.check(lib.e2fgvi_rgb_to_yuv420(_ptr(rgb), _ptr(like_rgb), _ptr(like), _ptr(out), L, H, W, lay, cf, _stream()),
+                 "rgb_to_yuv420")
+    return out
+
+
 def _restore_geometry(lo, mask_lo, src, tabs, n, box):
     """the shape checks restore_u8 and restore_blend share -> (h, w, FH, FW, left, upper, Bw, Bh); n: frames of lo / mask_lo"""
     ytab, xtab, bx, cx, by, cy = (t for _, t in tabs)

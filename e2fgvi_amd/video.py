@@ -7,6 +7,7 @@ blending of overlapping predictions) -- without cv2 / torchvision / PIL: frames 
 everything after the upload runs in HIP kernels (csrc/video.hip) and only the finished uint8 frames are copied back.  The window planning below is host logic; the byte
 arithmetic has no CPU path.
 """
+import collections
 import math
 from fractions import Fraction
 
@@ -602,6 +603,102 @@ def overlay_mask(frames_u8, g_min=OVERLAY_G_MIN, coherence=OVERLAY_COHERENCE, ra
     return _overlay_mask_device(_upload(frames_u8, device), g_min, coherence, radius, min_area, max_fraction).cpu().numpy()
 
 
+YuvFormat = collections.namedtuple("YuvFormat", "layout matrix full_range chroma")
+YUV_MATRICES = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}         # (Kr, Kb)
+
+
+def yuv_format(layout="nv12", matrix="bt709", full_range=False, chroma="left"):
+    """The description of 8-bit 4:2:0 YUV frames [L,3H/2,W] (H rows of luma, then the chroma of the frame), immutable:
+    ``layout`` "nv12" (H/2 rows of W/2 interleaved (U, V) pairs: hardware decoders) or "i420" (the U plane, then the V plane:
+    yuv420p from a raw pipe); ``matrix`` "bt601" or "bt709"; ``full_range`` False (luma 16-235, chroma 16-240) or True (0-255);
+    ``chroma`` how the decoder brings chroma to the pixels: "left" (MPEG-2 / H.264 siting: co-sited with the even columns, midway
+    between the rows, one rounding of the 2-D taps) or "nearest" (the sample of the pixel's 2x2 block).  Anything else raises
+    ValueError.  Wherever a format is taken a bare "nv12" / "i420" means that layout with these defaults."""
+    if layout not in ops.YUV_LAYOUTS:
+        raise ValueError('layout must be "nv12" or "i420", got %r' % (layout,))
+    if matrix not in YUV_MATRICES:
+        raise ValueError('matrix must be "bt601" or "bt709", got %r' % (matrix,))
+    if chroma not in ops.YUV_CHROMA:
+        raise ValueError('chroma must be "left" or "nearest", got %r' % (chroma,))
+    if not isinstance(full_range, (bool, np.bool_)):
+        raise ValueError("full_range must be True or False, got %r" % (full_range,))
+    return YuvFormat(layout, matrix, bool(full_range), chroma)
+
+
+def _as_yuv_format(fmt):
+    if isinstance(fmt, YuvFormat):
+        return yuv_format(*fmt)
+    if isinstance(fmt, str):
+        return yuv_format(fmt)
+    raise ValueError('a pixel format is a yuv_format(...) or a layout string "nv12" / "i420", got %r' % (fmt,))
+
+
+def yuv_coefficients(matrix, full_range):
+    """The Q14 integers the conversion kernels take as arguments: (decode, encode) = ((cy, crv, cgu, cgv, cbu), (yr, yg, yb, ur, ug,
+    ub, vr, vg, vb)), each round(c * 16384) of the float64 constant from (Kr, Kb) of ``matrix``, Kg = 1 - Kr - Kb, with the luma
+    scale 255/219 and the chroma scale 255/224 for limited range and 1 for full range (the luma offset is 16 or 0):
+    R = cy (Y - yo) + crv (V - 128) ..., Y = yo + yr R + yg G + yb B, U = 128 + ur R + ug G + ub B ..."""
+    if matrix not in YUV_MATRICES:
+        raise ValueError('matrix must be "bt601" or "bt709", got %r' % (matrix,))
+    kr, kb = YUV_MATRICES[matrix]
+    kg = 1.0 - kr - kb
+    ys, cs = (1.0, 1.0) if full_range else (255.0 / 219.0, 255.0 / 224.0)
+    q = lambda c: int(round(c * 16384.0))
+    dec = (q(ys), q(2.0 * (1.0 - kr) * cs), q(2.0 * kb * (1.0 - kb) / kg * cs), q(2.0 * kr * (1.0 - kr) / kg * cs),
+           q(2.0 * (1.0 - kb) * cs))
+    cu, cv = 0.5 / (1.0 - kb) / cs, 0.5 / (1.0 - kr) / cs
+    enc = (q(kr / ys), q(kg / ys), q(kb / ys), q(-kr * cu), q(-kg * cu), q((1.0 - kb) * cu),
+           q((1.0 - kr) * cv), q(-kg * cv), q(-kb * cv))
+    return dec, enc
+
+
+def _yuv_offset(fmt):
+    return 0 if fmt.full_range else 16
+
+
+def _decode_yuv(x, fmt):
+    return ops.yuv420_to_rgb(x, fmt.layout, fmt.chroma, yuv_coefficients(fmt.matrix, fmt.full_range)[0] + (_yuv_offset(fmt),))
+
+
+def _encode_yuv(rgb, fmt, like=None, like_rgb=None):
+    return ops.rgb_to_yuv420(rgb, fmt.layout, yuv_coefficients(fmt.matrix, fmt.full_range)[1] + (_yuv_offset(fmt),), like, like_rgb)
+
+
+def yuv420_to_rgb(frames_yuv, fmt="nv12", device=None):
+    """4:2:0 YUV frames uint8 [L,3H/2,W] in the format ``fmt`` (a yuv_format(...) or a layout string) -> uint8 [L,H,W,3] RGB, one
+    launch on the device (ops.yuv420_to_rgb; include/e2fgvi_hip.h has the integer definition, tests/yuv_cases.py restates it in
+    numpy).  A numpy array is uploaded and the result copied back; a device tensor comes back as a device tensor.  The row count
+    must divide by 3 and H and W be even (ValueError, from the shape alone)."""
+    fmt = _as_yuv_format(fmt)
+    ops.yuv_frame_hw(tuple(frames_yuv.shape))
+    out = _decode_yuv(_upload(frames_yuv, device), fmt)
+    return out if isinstance(frames_yuv, torch.Tensor) and frames_yuv.is_cuda else out.cpu().numpy()
+
+
+def rgb_to_yuv420(frames_u8, fmt="nv12", device=None, like=None):
+    """uint8 [L,H,W,3] RGB frames, H and W even (ValueError) -> uint8 [L,3H/2,W] in the format ``fmt``: luma per pixel, chroma from
+    the box average of each 2x2 block with one rounding (a constant colour round-trips; not the exact inverse of "left" siting).
+    ``like`` = YUV frames [L,3H/2,W] of the same format: the paste form -- with like_rgb = yuv420_to_rgb(like, fmt), the luma
+    byte of a pixel whose RGB bytes equal like_rgb's and the chroma pair of a 2x2 block of such pixels are ``like``'s, so frames
+    that were decoded, edited in places and encoded again keep the caller's bytes everywhere else; an unchanged pixel in a
+    changed block keeps its luma byte and gets the block's re-encoded chroma, which is inherent to 4:2:0.  One launch (two with
+    ``like``: its decoding).  Numpy in, numpy out; a device tensor comes back as a device tensor."""
+    fmt = _as_yuv_format(fmt)
+    if len(frames_u8.shape) != 4 or frames_u8.shape[3] != 3:
+        raise ValueError("frames must be uint8 [L,H,W,3], got %s" % (tuple(frames_u8.shape),))
+    if frames_u8.shape[1] % 2 or frames_u8.shape[2] % 2:
+        raise ValueError("4:2:0 frames need even H and W, got %d x %d" % (frames_u8.shape[1], frames_u8.shape[2]))
+    if like is not None and tuple(like.shape) != (frames_u8.shape[0], frames_u8.shape[1] // 2 * 3, frames_u8.shape[2]):
+        raise ValueError("like must be the [L,3H/2,W] frames of %s, got %s" % (tuple(frames_u8.shape), tuple(like.shape)))
+    x = _upload(frames_u8, device)
+    if like is not None:
+        like = _upload(like, x.device)
+        out = _encode_yuv(x, fmt, like, _decode_yuv(like, fmt))
+    else:
+        out = _encode_yuv(x, fmt)
+    return out if isinstance(frames_u8, torch.Tensor) and frames_u8.is_cuda else out.cpu().numpy()
+
+
 def _check_ids(ids, length):
     """frame numbers for ids=: a sequence of integers in [0, length) (ValueError otherwise), or a device int32 tensor, which is
     used as it is -- the kernels check its range (a frame of zeros for a bad id), the host never reads it"""
@@ -794,7 +891,7 @@ def prepare_masks(masks_u8, size_hw, device, dilate=True, box=None, ids=None):
 @torch.no_grad()
 def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, num_ref=-1, dilate=True,
                   device=None, pad=True, batch_windows=1, keep_float=False, in_flight=1, size=None, reuse=False, restore=False,
-                  region=None, context=0.5, feather=0, scenes=None, max_regions=4):
+                  region=None, context=0.5, feather=0, scenes=None, max_regions=4, pixel_format=None):
     """frames_u8: uint8 [L,H,W,3]; masks_u8: [L,Hm,Wm] (non-zero = hole; resized to the frames with NEAREST like
     read_mask).  Returns uint8 [L,H,W,3] composited frames, computed like test.py:129-179.
     ``model(masked[b,t,3,H',W'], n_local) -> (pred[b*t,3,H',W'], _)`` on the device.
@@ -893,14 +990,33 @@ def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, 
     once, and every pass pastes into the previous pass's frames, where its own box still holds the source.  It splits in space as
     "track" splits in time, and works with in_flight, batch_windows, reuse, feather, scenes and dilate, since each pass is the
     explicit-box path.  The cost is G passes of the model over the video.  No hole pixel: the source comes back and the model is
-    never called.  G = 1 (max_regions = 1 always) takes the path of region="hole" and returns its bytes."""
+    never called.  G = 1 (max_regions = 1 always) takes the path of region="hole" and returns its bytes.
+
+    ``pixel_format``: a yuv_format(...) or a layout string ("nv12", "i420": that layout with yuv_format's other defaults) -- the
+    frames come in as uint8 [L,3H/2,W] 4:2:0 YUV, what decoders produce and encoders take, and the result comes back as
+    [L,3h/2,w] in the same format.  The frames are decoded once after the upload (yuv420_to_rgb: one launch) and everything above
+    runs on the decoded RGB as if the caller had passed it -- "overlay", scenes="auto", every region and every driver; the masks
+    stay [L,Hm,Wm].  A result of the source's size (no ``size``, or restore=True) is encoded by the paste form of rgb_to_yuv420
+    with the caller's upload for ``like``: a luma byte whose pixel, and a chroma pair whose four pixels, the driver left as they
+    were decoded are the caller's bytes, so a frame the driver did not touch comes back identical in all its 3HW/2 bytes and
+    every changed byte lies within one 2x2 block of a changed pixel.  A result of another size (``size`` without restore) is
+    encoded plainly, and ``size`` must then be even in both dimensions (ValueError).  keep_float=True with a pixel_format raises
+    ValueError.  None is the RGB path above, byte for byte, with no launch added."""
+    fmt = None if pixel_format is None else _as_yuv_format(pixel_format)
+    shape = tuple(frames_u8.shape)
+    if fmt is not None:                                 # the frame size the checks below speak of is the decoded one
+        if keep_float:
+            raise ValueError("pixel_format= returns uint8 YUV frames: keep_float must be False")
+        shape = (shape[0],) + ops.yuv_frame_hw(shape) + (3,)
+        if size is not None and not restore and (int(size[0]) % 2 or int(size[1]) % 2):
+            raise ValueError("pixel_format= returns 4:2:0 frames of (width, height) = size, which must both be even, got %r" % (size,))
     overlay = isinstance(masks_u8, str)
     if overlay and masks_u8 != "overlay":
         raise ValueError('masks_u8 must be uint8 [L,Hm,Wm] masks or "overlay", got %r' % (masks_u8,))
     if scenes is not None and not (isinstance(scenes, str) and scenes == "auto"):
         if isinstance(scenes, str):
             raise ValueError('scenes must be None, "auto" or a list of frame numbers, got %r' % (scenes,))
-        scenes = _check_scenes(scenes, int(frames_u8.shape[0]))             # from the shapes alone, before any device work
+        scenes = _check_scenes(scenes, int(shape[0]))                       # from the shapes alone, before any device work
     feather = _check_feather(feather)
     if feather and not restore:
         raise ValueError("feather= ramps the paste-back of restore=True into the source frames: without restore there is no seam "
@@ -917,7 +1033,7 @@ def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, 
             track = region == "track"
             holes = region == "holes"
         else:
-            box = _check_box(region, (frames_u8.shape[2], frames_u8.shape[1]))
+            box = _check_box(region, (shape[2], shape[1]))
     if track:
         if not restore:
             raise ValueError('region="track" gives every window a box of its own, so the windows\' results exist together only at '
@@ -959,6 +1075,9 @@ def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, 
         frames_d = frames_u8.to(device).contiguous()
     else:
         frames_d = torch.as_tensor(np.ascontiguousarray(frames_u8)).to(device)
+    like = None
+    if fmt is not None:                                 # decoded once; the caller's bytes stay for the paste on the way out
+        like, frames_d = frames_d, _decode_yuv(frames_d, fmt)
     source = frames_d                                   # restore=True: kept beside the resized frames, only read
     if overlay:                                         # on the frames at source size; the same hole in every frame
         if source.shape[0] < 1 or source.shape[1] * source.shape[2] == 0:
@@ -969,31 +1088,41 @@ def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, 
         masks_d = _upload(masks_u8, device)             # once: the bounding box and the mask preparation read the same tensor
     if isinstance(scenes, str):                         # "auto": on the frames at source size
         scenes = detect_cuts(source)
+    out = _inpaint_planned(model, source, masks_d, size, scenes, track, holes, box, region is not None, neighbor_stride, ref_length,
+                           num_ref, dilate, pad, batch_windows, keep_float, in_flight, reuse, restore, context, feather, max_regions)
+    if fmt is not None:                                 # the source's size: the paste form, the caller's bytes where nothing changed
+        out = _encode_yuv(out, fmt, like, source) if size is None or restore else _encode_yuv(out, fmt)
+    return out if keep_float else out.cpu().numpy()
+
+
+def _inpaint_planned(model, source, masks_d, size, scenes, track, holes, box, region, neighbor_stride, ref_length, num_ref, dilate, pad,
+                     batch_windows, keep_float, in_flight, reuse, restore, context, feather, max_regions):
+    """inpaint_video after the argument checks, the uploads and the detectors: picks the driver and the box(es) and returns the
+    result as a device tensor (uint8, or fp32 with keep_float) -- the one host copy of a call is inpaint_video's"""
     if track:
         return _inpaint_track(model, source, masks_d, tuple(int(v) for v in size),
                               plan_windows(source.shape[0], neighbor_stride, ref_length, num_ref, scenes), dilate, pad, context, feather)
     run = lambda b, paste=None: _inpaint_box(model, source, masks_d, b, size, scenes, neighbor_stride, ref_length, num_ref, dilate, pad,
                                              batch_windows, keep_float, in_flight, reuse, restore, feather, paste)
-    if region is not None:
+    if region:
         frame_wh = (source.shape[2], source.shape[1])
         if holes:
             regions = hole_regions(masks_d, frame_wh, size, context, max_regions)
             if not regions:
-                return source.cpu().numpy()
+                return source
             if len(regions) > 1:
                 # a pass pastes its box into the frames the pass before it returned: the boxes are disjoint, so inside its own box
                 # those still are the source, which is all the paste reads of them there (the ramp of feather= included)
                 out = source
                 for b in regions:
                     out = run(b, out)
-                return out.cpu().numpy()
+                return out
             box = regions[0]                            # one group: the box and the path of region="hole"
         elif box is None:
             box = hole_region(masks_d, frame_wh, size, context)
         if box == (0, 0) + frame_wh:
             box = None                                  # the whole frame: the path (and the bytes) of region=None
-    out = run(box)
-    return out if keep_float else out.cpu().numpy()
+    return run(box)
 
 
 def _inpaint_box(model, source, masks_d, box, size, scenes, neighbor_stride, ref_length, num_ref, dilate, pad, batch_windows,
@@ -1149,14 +1278,14 @@ def _touched(k, windows, boxes):
 
 def _inpaint_track(model, source, masks_d, size, windows, dilate, pad, context, feather=0):
     """inpaint_video(region="track") after the argument checks and the uploads: source uint8 [L,H,W,3] and masks_d uint8
-    [L,Hm,Wm] on the device -> uint8 array [L,H,W,3]"""
+    [L,Hm,Wm] on the device -> uint8 [L,H,W,3] on the device"""
     device = source.device
     L, H, W, _ = source.shape
     w, h = size
     boxes = plan_track(_frame_boxes(masks_d, (W, H)), windows, (W, H), size, context)
     run = [k for k, b in enumerate(boxes) if b is not None]
     if not run:
-        return source.cpu().numpy()
+        return source
     Hp, Wp = padded_size(h, w) if pad else (h, w)
     mask_hw = tuple(int(v) for v in masks_d.shape[1:3])
     # every host->device upload happens here, before the first forward: per distinct box the tables of the frame resize, of the
@@ -1194,4 +1323,4 @@ def _inpaint_track(model, source, masks_d, size, windows, dilate, pad, context, 
         ops.composite(pred.contiguous(), local[:n], ones[:n], fr, keep_all if feather else m01, comp)
         ops.restore_blend(ops.float_to_u8(comp[:n]), m01[:n], source, ids_dev[k][:n], first_dev[k], acc, *rtabs, box=boxes[k],
                           touch=touch[k], feather=feather)
-    return ops.float_to_u8(acc).cpu().numpy()
+    return ops.float_to_u8(acc)

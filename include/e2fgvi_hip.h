@@ -208,6 +208,38 @@ int e2fgvi_overlay_stats(const uint8_t* frames, int32_t L, int32_t H, int32_t W,
 int e2fgvi_overlay_edges(const int32_t* stats, int32_t L, int32_t H, int32_t W, int32_t g_min, int32_t coherence, int32_t radius,
                          uint8_t* out, int32_t* count, void* stream);
 
+/* Pixel formats (video.yuv420_to_rgb / rgb_to_yuv420, inpaint_video(pixel_format=)): 8-bit 4:2:0 YUV frames as decoders hand them
+ * over, in place of the chain of float torch expressions -- several passes over source-size frames, two roundings and a chroma
+ * resampling of every byte -- a caller of the RGB-only driver has to write around it.  A frame is 3 H W / 2 contiguous bytes, H and W
+ * even: H rows of W luma bytes, then E2FGVI_YUV_NV12: H/2 rows of W/2 interleaved (U, V) pairs; E2FGVI_YUV_I420: the H/2 x W/2 U
+ * plane, then the V plane.  yuv uint8 [L][3H/2][W], rgb uint8 [L][H][W][3], both on the device, neither need be aligned (8-byte
+ * loads and stores where W % 8 == 0 and every base is a multiple of 8, bytes otherwise).  All arithmetic is int32, >> the floor
+ * shift, clip to [0, 255].  Chroma at pixel (y, x) from the plane C[j][i], indices clamped to the plane:
+ *   E2FGVI_CHROMA_NEAREST: C' = C[y >> 1][x >> 1];
+ *   E2FGVI_CHROMA_LEFT (MPEG-2 / H.264 siting): C' = (sum wv wh C + 4) >> 3 with horizontal taps {i: 2} at x = 2i and
+ *   {i: 1, i+1: 1} at x = 2i+1, vertical taps {j-1: 1, j: 3} at y = 2j and {j: 3, j+1: 1} at y = 2j+1.
+ * coef: HOST int32 [6] = (cy, crv, cgu, cgv, cbu, yo) in Q14 (video.yuv_coefficients), read before the call returns:
+ *   yy = cy (Y - yo), u = U' - 128, v = V' - 128;
+ *   R = clip((yy + crv v + 8192) >> 14), G = clip((yy - cgu u - cgv v + 8192) >> 14), B = clip((yy + cbu u + 8192) >> 14).
+ * Odd H or W, an unknown layout or chroma mode: E2FGVI_EINVAL; L H W = 0 launches nothing; H W < 2^31. */
+#define E2FGVI_YUV_NV12 0
+#define E2FGVI_YUV_I420 1
+#define E2FGVI_CHROMA_LEFT 0
+#define E2FGVI_CHROMA_NEAREST 1
+int e2fgvi_yuv420_to_rgb(const uint8_t* yuv, uint8_t* rgb, int32_t L, int32_t H, int32_t W, int32_t layout, int32_t chroma,
+                         const int32_t* coef, void* stream);
+/* The way back, replacing the same chain of float expressions on the result.  coef: HOST int32 [10] = (yr, yg, yb, ur, ug, ub, vr,
+ * vg, vb, yo) in Q14; with SR, SG, SB the sums over the four pixels of block (j, i) -- the box average, one rounding:
+ *   Y(y, x) = clip(yo + ((yr R + yg G + yb B + 8192) >> 14)),
+ *   U(j, i) = clip(128 + ((ur SR + ug SG + ub SB + 32768) >> 16)),   V likewise with (vr, vg, vb).
+ * like / like_rgb (both or neither; NULL: the plain encode): the caller's YUV frames [L][3H/2][W] and what they decoded to
+ * [L][H][W][3].  A pixel is unchanged when its three bytes of rgb equal those of like_rgb; an unchanged pixel's luma byte is like's,
+ * and a chroma sample whose four pixels are all unchanged is like's pair of bytes; everything else is encoded from rgb (an
+ * unchanged pixel in a changed block keeps its luma and gets the block's new chroma).  One launch either way, every byte of yuv
+ * written once; yuv must not overlap an input.  Errors as above. */
+int e2fgvi_rgb_to_yuv420(const uint8_t* rgb, const uint8_t* like_rgb, const uint8_t* like, uint8_t* yuv, int32_t L, int32_t H,
+                         int32_t W, int32_t layout, const int32_t* coef, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * evaluate.py metrics (core/metrics.py:20-56): per image pair of fp32 NHWC [N,H,W,3] frames in
  * [0,255]: out[2n] = PSNR (inf when identical), out[2n+1] = SSIM as skimage compare_ssim(data_range=255,
