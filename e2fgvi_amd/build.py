@@ -30,8 +30,10 @@ UNITS = [("error.hip", "error.o", []), ("conv.hip", "conv.o", []), ("conv.hip", 
          ("conv_bf16x.hip", "conv_bf16x.o", NOPK), ("conv_wino.hip", "conv_wino.o", NOPK), ("conv_wino.hip", "conv_wino_x3.o", NOPK + ["-DE2_WINO_X3=1"]), ("conv_wino4.hip", "conv_wino4.o", NOPK), ("conv_tail.hip", "conv_tail.o", NOPK),
          ("mdcn.hip", "mdcn.o", NOPK), ("attention.hip", "attention.o", []),
          ("attention_bf16.hip", "attention_bf16.o", NOPK), ("attention_x3.hip", "attention_x3.o", NOPK), ("misc.hip", "misc.o", NOPK),
-         ("video.hip", "video.o", NOPK), ("yuv.hip", "yuv.o", NOPK), ("metrics.hip", "metrics.o", NOPK)]
-NOPK_OBJECTS = ("conv_nopk.o", "conv_bf16x.o", "conv_wino.o", "conv_wino4.o", "conv_wino_x3.o", "conv_tail.o", "mdcn.o", "attention_bf16.o", "attention_x3.o", "misc.o", "video.o", "yuv.o", "metrics.o")
+         ("video.hip", "video.o", NOPK), ("yuv.hip", "yuv.o", NOPK), ("metrics.hip", "metrics.o", NOPK),
+         # fp64 in the order written: the numpy restatement matches the step bit for bit only without fused multiply-adds
+         ("mask_track.hip", "mask_track.o", NOPK + ["-ffp-contract=off"])]
+NOPK_OBJECTS = ("conv_nopk.o", "conv_bf16x.o", "conv_wino.o", "conv_wino4.o", "conv_wino_x3.o", "conv_tail.o", "mdcn.o", "attention_bf16.o", "attention_x3.o", "misc.o", "video.o", "yuv.o", "metrics.o", "mask_track.o")
 OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 
 
@@ -88,6 +90,7 @@ def build(force=False, verbose=False, nopk_all=False, lib=None, tag=None, define
             verify_no_scratch(objdir, "video.o", "overlay_stats_kernel", "overlay sums")
             verify_overlay_prefetch(objdir)
             verify_no_pk_u8(objdir)
+            verify_no_fma64(objdir)
     return out
 
 
@@ -126,6 +129,22 @@ def verify_isa(objdir=None):
         if bad or not isa:
             raise RuntimeError("%s: %s" % (obj, "%d packed-fp32 instructions in a unit that must have none" % len(bad) if isa
                                            else "no gfx950 code object found"))
+
+
+def verify_no_fma64(objdir=None, obj="mask_track.o"):
+    """mask_track_step_kernel (csrc/mask_track.hip) does its fp64 arithmetic in the order written, one rounding per operation: the
+    numpy restatement of the tests matches it bit for bit.  The unit is built with -ffp-contract=off; a fused multiply-add in its
+    code would mean the flag was lost (or an expression was rewritten into fma()).  Returns the number of fp64 multiplies read."""
+    import re
+    objdir = objdir or os.path.join(CSRC, "build")
+    if not os.path.exists(OBJDUMP):
+        return 0
+    isa = device_isa(os.path.join(objdir, obj))
+    fused = re.findall(r"v_fma(?:c|ak|mk)?_f64", isa)
+    if fused or not isa:
+        raise RuntimeError("%s: %s" % (obj, "%d fused fp64 multiply-adds in a unit that must round every operation" % len(fused) if isa
+                                       else "no gfx950 code object found"))
+    return len(re.findall(r"v_mul_f64", isa))
 
 
 def verify_no_pk_u8(objdir=None):

@@ -1812,7 +1812,49 @@ def overlay_edges(stats, L, g_min, coherence, radius):
     return out, count
 
 
-YUV_LAYOUTS = {"nv12": 0, "i420": 1}       # E2FGVI_YUV_* / E2FGVI_CHROMA_* of include/e2fgvi_hip.h
+def mask_track_step(planes, fwd, bwd, jobs, check=True):
+    """One step of carrying binary masks along a video's flows (csrc/mask_track.hip; include/e2fgvi_hip.h has the definition;
+    video.propagate_masks runs the chains): planes uint8 [2,L,H,W] of 0 / 1, L >= 2, plane 0 carried forward in time and plane 1
+    backward, updated in place; fwd, bwd fp32 [L-1,H,W,2] in metrics.warp_error's convention; jobs int32 [n,2] of (pair t, dir):
+    dir 0 writes plane 0 frame t+1 from frame t, pulled along bwd[t] and checked against fwd[t]; dir 1 writes plane 1 frame t from
+    frame t+1, pulled along fwd[t] and checked against bwd[t].  One launch runs all n jobs; no job of a call may write a frame of a
+    plane that another reads or writes (video.plan_mask_chains).  check=False switches the forward / backward consistency test
+    off.  Device tensors, or anything torch.as_tensor accepts (uploaded first); wrong dtypes, shapes that do not fit,
+    non-contiguous inputs and tensors on different devices raise ValueError.  Returns the planes on the device (the tensor that
+    was passed when it was there already).  The same inputs give the same bits in every run."""
+    lib = _L.load()
+    if not isinstance(check, (bool, numbers.Integral)) or check not in (0, 1):
+        raise ValueError("check must be a bool (or 0 / 1), got %r" % (check,))
+    check = int(check)
+    named = (("planes", planes), ("fwd", fwd), ("bwd", bwd), ("jobs", jobs))
+    device = next((t.device for _, t in named if isinstance(t, torch.Tensor) and t.is_cuda), "cuda")
+    up = [t if isinstance(t, torch.Tensor) and t.is_cuda else torch.as_tensor(t).to(device) for _, t in named]
+    pl, fw, bw, jb = up
+    for t, nm, dt in ((pl, "planes", torch.uint8), (fw, "fwd", torch.float32), (bw, "bwd", torch.float32), (jb, "jobs", torch.int32)):
+        if t.dtype != dt:
+            raise ValueError("%s must be %s, got %s" % (nm, dt, t.dtype))
+    if pl.dim() != 4 or pl.shape[0] != 2:
+        raise ValueError("planes must be [2,L,H,W], got %s" % (tuple(pl.shape),))
+    _, L, H, W = pl.shape
+    if L < 2:
+        raise ValueError("mask_track_step needs at least two frames, got planes %s" % (tuple(pl.shape),))
+    for t, nm in ((fw, "fwd"), (bw, "bwd")):
+        if tuple(t.shape) != (L - 1, H, W, 2):
+            raise ValueError("%s must be [%d,%d,%d,2] for planes %s, got %s" % (nm, L - 1, H, W, tuple(pl.shape), tuple(t.shape)))
+    if jb.dim() != 2 or jb.shape[1] != 2:
+        raise ValueError("jobs must be int32 [n,2] of (pair, dir), got %s" % (tuple(jb.shape),))
+    for t, nm in ((pl, "planes"), (fw, "fwd"), (bw, "bwd"), (jb, "jobs")):
+        if not t.is_contiguous():
+            raise ValueError("%s must be contiguous" % nm)
+        if t.device != pl.device:
+            raise ValueError("%s is on %s, the planes on %s" % (nm, t.device, pl.device))
+    with torch.cuda.device(pl.device):
+        _L.check(lib.e2fgvi_mask_track_step(_ptr(pl), _ptr(fw), _ptr(bw), _ptr(jb), jb.shape[0], L, H, W, check, _stream()),
+                 "mask_track_step")
+    return pl
+
+
+YUV_LAYOUTS = {"nv12": 0, "i420": 1}     # E2FGVI_YUV_* / E2FGVI_CHROMA_* of include/e2fgvi_hip.h
 YUV_CHROMA = {"left": 0, "nearest": 1}
 
 

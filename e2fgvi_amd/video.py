@@ -603,6 +603,154 @@ def overlay_mask(frames_u8, g_min=OVERLAY_G_MIN, coherence=OVERLAY_COHERENCE, ra
     return _overlay_mask_device(_upload(frames_u8, device), g_min, coherence, radius, min_area, max_fraction).cpu().numpy()
 
 
+def _is_int(v):
+    return not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, np.integer))
+
+
+def _check_keys(keys, length, name="keys"):
+    """key frame numbers as a list: at least one, strictly increasing integers in [0, length); ValueError that names the argument"""
+    try:
+        vals = list(keys)
+    except TypeError:
+        vals = None
+    if (not vals or not all(_is_int(v) for v in vals) or any(not 0 <= int(v) < length for v in vals)
+            or any(int(b) <= int(a) for a, b in zip(vals[:-1], vals[1:]))):
+        raise ValueError("%s must be a strictly increasing list of at least one frame number in [0, %d), got %r" % (name, length, keys))
+    return [int(v) for v in vals]
+
+
+def _check_reach(reach):
+    if reach is not None and (not _is_int(reach) or reach < 1):
+        raise ValueError("reach must be None or an integer >= 1, got %r" % (reach,))
+    return None if reach is None else int(reach)
+
+
+def plan_mask_chains(length, keys, scenes=None, reach=None):
+    """The launches that carry key masks through a video of ``length`` frames (propagate_masks): a list of steps, each a list of
+    jobs (pair t, dir) for ops.mask_track_step -- dir 0 writes frame t+1 of the forward plane from frame t, dir 1 writes frame t of
+    the backward plane from frame t+1.  ``keys``: the frames that have a mask, strictly increasing integers in [0, length), at
+    least one; ``scenes``: as plan_windows takes them; ``reach``: None, or the largest number of steps (an integer >= 1) a mask is
+    carried away from its key.  ValueError otherwise.
+    The forward chain of key k runs k -> k+1 -> ...; it stops before the next key, before a cut, at the last frame and after
+    ``reach`` steps; the backward chain mirrors it.  All chains advance in lockstep: step s holds the s-th job of every chain that
+    is still alive, so the number of launches is the length of the longest chain, not the length of the video.  Within a step no
+    job writes a frame of a plane that another job of the step reads or writes (the chains of a plane lie between different keys);
+    no job crosses a cut or writes a key frame; every frame within reach of a key of its scene is written exactly once in each plane
+    in which it can be reached."""
+    if not _is_int(length) or length < 1:
+        raise ValueError("length must be an integer >= 1, got %r" % (length,))
+    length = int(length)
+    keys = _check_keys(keys, length)
+    cuts = set(_check_scenes(scenes, length)) if scenes is not None else set()
+    reach = _check_reach(reach)
+    keyset = set(keys)
+    chains = []
+    for k in keys:
+        fw, f = [], k                                   # f: the frame the next job reads
+        while f + 1 < length and f + 1 not in keyset and f + 1 not in cuts and (reach is None or len(fw) < reach):
+            fw.append((f, 0))
+            f += 1
+        bw, f = [], k
+        while f - 1 >= 0 and f - 1 not in keyset and f not in cuts and (reach is None or len(bw) < reach):
+            bw.append((f - 1, 1))
+            f -= 1
+        chains += [fw, bw]
+    return [[c[s] for c in chains if len(c) > s] for s in range(max(len(c) for c in chains))]
+
+
+def _propagate_masks_device(model, x, key_masks, keys, steps, flows, size, check):
+    """propagate_masks after the argument checks and the upload of the frames: x uint8 [L,H,W,3] on the device, steps the plan of
+    plan_mask_chains -> device uint8 [L,h,w] of 0 / 1"""
+    from . import metrics
+    # the job tables of all steps in one upload, and the key frames' numbers, in front of the first launch
+    table = torch.tensor([j for s in steps for j in s], dtype=torch.int32).reshape(-1, 2).to(x.device)
+    key_ids = torch.tensor(keys, dtype=torch.int64).to(x.device)
+    if size is not None:
+        x = resize_frames(x, size)
+    L, h, w = (int(v) for v in x.shape[:3])
+    if h * w == 0:
+        return torch.zeros((L, h, w), dtype=torch.uint8, device=x.device)
+    km = prepare_masks(key_masks, (h, w), x.device, dilate=False)
+    with torch.cuda.device(x.device):
+        planes = torch.zeros((2, L, h, w), dtype=torch.uint8, device=x.device)
+        planes[:, key_ids] = km
+        if steps:
+            if flows is None:
+                fwd, bwd = metrics.video_flows(model, x)
+            else:
+                fwd, bwd = (metrics._device_tensor(f, x.device) for f in flows)
+            at = 0
+            for s in steps:
+                ops.mask_track_step(planes, fwd, bwd, table[at:at + len(s)], check)
+                at += len(s)
+        return planes[0] | planes[1]
+
+
+def _check_propagate_args(model, shape, key_masks, keys, flows, size, scenes, reach, check, name="keys"):
+    """the checks of propagate_masks from the arguments and the shapes alone (shape: that of the RGB frames) -> (keys, steps)"""
+    if len(shape) != 4 or shape[3] != 3:
+        raise ValueError("frames must be uint8 [L,H,W,3], got %s" % (tuple(shape),))
+    L = int(shape[0])
+    if L < 1:
+        raise ValueError("frames: at least one frame is needed, got %s" % (tuple(shape),))
+    keys = _check_keys(keys, L, name)
+    if len(getattr(key_masks, "shape", ())) != 3 or key_masks.shape[0] != len(keys):
+        raise ValueError("key_masks must be uint8 [K,Hm,Wm] with one mask for each of the K = %d frames of %s, got %s"
+                         % (len(keys), name, tuple(getattr(key_masks, "shape", ())) or type(key_masks).__name__))
+    if not isinstance(check, (bool, np.bool_)):
+        raise ValueError("check must be a bool, got %r" % (check,))
+    if size is not None:
+        try:
+            ok = len(size) == 2 and all(_is_int(v) and v > 0 for v in size)
+        except TypeError:
+            ok = False
+        if not ok:
+            raise ValueError("size must be None or a positive (width, height), got %r" % (size,))
+    if isinstance(scenes, str):
+        raise ValueError("scenes must be None or a list of frame numbers, got %r" % (scenes,))
+    steps = plan_mask_chains(L, keys, scenes, reach)
+    if flows is None:
+        if not callable(getattr(model, "engine", None)):
+            raise TypeError("without flows= the masks follow the flows of the model's SPyNet (metrics.video_flows): that needs the "
+                            "InpaintGenerator, got %s" % type(model).__name__)
+    else:
+        w, h = (int(v) for v in size) if size is not None else (int(shape[2]), int(shape[1]))
+        try:
+            shapes = [tuple(f.shape) for f in flows]
+        except (TypeError, AttributeError):
+            shapes = None
+        if shapes is None or len(shapes) != 2 or (L >= 2 and any(s != (L - 1, h, w, 2) for s in shapes)):
+            raise ValueError("flows must be (fwd, bwd), both fp32 [%d,%d,%d,2] (the frames' size after size=), got %r"
+                             % (L - 1, h, w, shapes if shapes is not None else flows))
+    return keys, steps
+
+
+@torch.no_grad()
+def propagate_masks(model, frames_u8, key_masks, keys, flows=None, size=None, scenes=None, reach=None, check=True, device=None):
+    """Masks for every frame from masks painted on a few: frames_u8 uint8 [L,H,W,3], key_masks [K,Hm,Wm] (any non-zero byte is
+    hole, any size: NEAREST-resized to the frames and binarised like prepare_masks(dilate=False)) for the frames ``keys`` (K
+    strictly increasing frame numbers) -> uint8 numpy [L,h,w] of 0 / 1, everything after the upload on the device.
+    ``size`` = (width, height) resizes the frames first (resize_frames) and the result has that size.  The flows between adjacent
+    frames are the net's own (metrics.video_flows(model, frames): ``model`` must be the generator, TypeError otherwise) or
+    ``flows`` = (fwd, bwd), fp32 [L-1,h,w,2] in metrics.warp_error's convention -- ``model`` may then be None.
+    Each key mask is carried away from its key frame in both directions, one frame per step (ops.mask_track_step has the
+    definition): the pixel p of the next frame takes the mask's bilinear sample at q = p + g(p), g the flow from the next frame
+    back, and is set when the sample is >= 0.5 and -- ``check`` -- the flow from the mask's frame at q leads back to p (the
+    forward / backward test of warp_error).  Without that test the flows of background that the object has just uncovered, which
+    point anywhere, leave a trail behind a moving object; with it the mask loses a one-pixel rim in the first step and then holds
+     -- inpaint_video's dilation covers the rim.  The chains are planned by plan_mask_chains (``scenes``: cuts, as
+    plan_windows takes them: nothing is carried over one; ``reach``: the largest number of frames a mask is carried) and advance in
+    lockstep, one launch per step; the job tables are uploaded before the first launch.  The result is the union of the forward
+    and the backward plane: a key frame returns exactly its binarised mask, a frame between two keys the union of what both
+    brought (for removal a missed object pixel costs more than an extra hole pixel), a frame out of reach or in a scene without a
+    key is empty.  Argument errors are ValueErrors that name the argument, raised before any device work."""
+    shape = tuple(frames_u8.shape)
+    keys, steps = _check_propagate_args(model, shape, key_masks, keys, flows, size, scenes, reach, check)
+    if device is None:
+        device = next(model.parameters()).device if hasattr(model, "parameters") else None
+    return _propagate_masks_device(model, _upload(frames_u8, device), key_masks, keys, steps, flows, size, bool(check)).cpu().numpy()
+
+
 YuvFormat = collections.namedtuple("YuvFormat", "layout matrix full_range chroma")
 YUV_MATRICES = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}         # (Kr, Kb)
 
@@ -891,7 +1039,7 @@ def prepare_masks(masks_u8, size_hw, device, dilate=True, box=None, ids=None):
 @torch.no_grad()
 def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, num_ref=-1, dilate=True,
                   device=None, pad=True, batch_windows=1, keep_float=False, in_flight=1, size=None, reuse=False, restore=False,
-                  region=None, context=0.5, feather=0, scenes=None, max_regions=4, pixel_format=None):
+                  region=None, context=0.5, feather=0, scenes=None, max_regions=4, pixel_format=None, mask_keys=None):
     """frames_u8: uint8 [L,H,W,3]; masks_u8: [L,Hm,Wm] (non-zero = hole; resized to the frames with NEAREST like
     read_mask).  Returns uint8 [L,H,W,3] composited frames, computed like test.py:129-179.
     ``model(masked[b,t,3,H',W'], n_local) -> (pred[b*t,3,H',W'], _)`` on the device.
@@ -1001,7 +1149,18 @@ def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, 
     were decoded are the caller's bytes, so a frame the driver did not touch comes back identical in all its 3HW/2 bytes and
     every changed byte lies within one 2x2 block of a changed pixel.  A result of another size (``size`` without restore) is
     encoded plainly, and ``size`` must then be even in both dimensions (ValueError).  keep_float=True with a pixel_format raises
-    ValueError.  None is the RGB path above, byte for byte, with no launch added."""
+    ValueError.  None is the RGB path above, byte for byte, with no launch added.
+
+    ``mask_keys``: a list of K frame numbers (strictly increasing, in [0, L); ValueError otherwise) -- ``masks_u8`` then holds only
+    the K masks [K,Hm,Wm] painted on those frames, and the driver follows the object itself: after the upload and the decode of a
+    pixel_format, and after scenes="auto" has been resolved, the masks of all L frames are made on the device by propagate_masks'
+    device form -- along the flows of the model's own SPyNet, on the source frames at ``size`` when it is given and at their own
+    size otherwise, nothing carried over a cut -- and the call proceeds exactly as if the caller had passed those [L,h,w] masks:
+    the result is the bytes of inpaint_video(model, frames, propagate_masks(model, frames, masks, keys, size=size, scenes=cuts),
+    ...) with every other option (region, restore, feather, reuse, in_flight, pixel_format, dilate: the 4-pixel dilation covers
+    the rim the consistency test costs) as given.  ``model`` must be the generator (an object with ``engine()``; TypeError
+    otherwise); mask_keys with masks_u8="overlay" raises ValueError.  None is the path of a call without the argument, byte for
+    byte, with no launch added."""
     fmt = None if pixel_format is None else _as_yuv_format(pixel_format)
     shape = tuple(frames_u8.shape)
     if fmt is not None:                                 # the frame size the checks below speak of is the decoded one
@@ -1017,6 +1176,12 @@ def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, 
         if isinstance(scenes, str):
             raise ValueError('scenes must be None, "auto" or a list of frame numbers, got %r' % (scenes,))
         scenes = _check_scenes(scenes, int(shape[0]))                       # from the shapes alone, before any device work
+    if mask_keys is not None:
+        if overlay:
+            raise ValueError('mask_keys= names the frames whose masks are given: with masks_u8="overlay" there are none')
+        auto = isinstance(scenes, str)
+        mask_keys, _ = _check_propagate_args(model, shape, masks_u8, mask_keys, None, size, None if auto else scenes, None, True,
+                                             "mask_keys")
     feather = _check_feather(feather)
     if feather and not restore:
         raise ValueError("feather= ramps the paste-back of restore=True into the source frames: without restore there is no seam "
@@ -1088,6 +1253,9 @@ def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, 
         masks_d = _upload(masks_u8, device)             # once: the bounding box and the mask preparation read the same tensor
     if isinstance(scenes, str):                         # "auto": on the frames at source size
         scenes = detect_cuts(source)
+    if mask_keys is not None:                           # the masks of all frames from the K that were given, with the resolved cuts
+        masks_d = _propagate_masks_device(model, source, masks_d, mask_keys, plan_mask_chains(int(source.shape[0]), mask_keys, scenes),
+                                          None, size, True)
     out = _inpaint_planned(model, source, masks_d, size, scenes, track, holes, box, region is not None, neighbor_stride, ref_length,
                            num_ref, dilate, pad, batch_windows, keep_float, in_flight, reuse, restore, context, feather, max_regions)
     if fmt is not None:                                 # the source's size: the paste form, the caller's bytes where nothing changed

@@ -277,6 +277,24 @@ int e2fgvi_psnr_ssim(const float* img1, const float* img2, int32_t N, int32_t H,
 int64_t e2fgvi_warp_error_workspace(int32_t L, int32_t H, int32_t W);
 int e2fgvi_warp_error(const void* frames, int32_t frame_dtype, const float* fwd, const float* bwd, const uint8_t* valid, int32_t L,
                       int32_t H, int32_t W, void* workspace, double* out, void* stream);
+/* Masks from keyframes (video.propagate_masks, inpaint_video(mask_keys=)): one step of pulling a binary mask along those flows.
+ *   planes [2,L,H,W] uint8 of 0 / 1, read and written: plane 0 is carried forward in time, plane 1 backward
+ *   fwd, bwd [L-1,H,W,2] fp32 as above, 8-byte aligned;  jobs int32 [n][2] = (pair t, dir) on the device
+ * dir 0 reads plane 0 frame t and writes plane 0 frame t+1 with the pull flow g = bwd[t] and the check flow c = fwd[t];
+ * dir 1 reads plane 1 frame t+1 and writes plane 1 frame t with g = fwd[t] and c = bwd[t].  One launch runs all n jobs (in slabs
+ * of 65535); within a call no job may write a frame of a plane that another job reads or writes (video.plan_mask_chains); a job
+ * outside [0, L-1) x {0, 1} writes nothing.  Destination pixel p = (x, y), source mask M, fp64 on the fp32 / uint8 inputs in the
+ * order written, no fused multiply-add:
+ *   q = (x + g_x(p), y + g_y(p));  inside = g(p) finite, 0 <= q_x <= W-1 and 0 <= q_y <= H-1 (in floating point, before any
+ *       conversion to an integer);  s = bil(M, q), c_w = bil(c, q) with the sampler above, corners added in the order (y0, x0),
+ *       (y0, x0+1), (y0+1, x0), (y0+1, x0+1);
+ *   inconsistent = c_w not finite, or  sx sx + sy sy > 0.01 ((g_x g_x + g_y g_y) + (c_wx c_wx + c_wy c_wy)) + 0.5,  s = g + c_w;
+ *   dst(p) = 1 iff inside and s >= 0.5 and (check == 0 or not inconsistent): a tie s == 0.5 is inside the mask.
+ * Excluded pixels are dropped by select; c is gathered only for pixels that passed `inside` and s >= 0.5.  No atomics: the same
+ * inputs give the same bits.  L >= 2, n, H, W >= 0, check in {0, 1}, H * W < 2^31 - 256 (E2FGVI_EINVAL otherwise); n == 0 or
+ * H * W == 0 returns 0 without a launch and without looking at the pointers; a null pointer with work is E2FGVI_EINVAL. */
+int e2fgvi_mask_track_step(uint8_t* planes, const float* fwd, const float* bwd, const int32_t* jobs, int32_t n, int32_t L, int32_t H,
+                           int32_t W, int32_t check, void* stream);
 
 /* conv_offset post-processing of SecondOrderDeformableAlignment (feat_prop.py:38-53) fused into the conv that produces
  * it: `residual` must point to the per-pixel flows [P,4] = (u1,v1,u2,v2) with res_ld = 4, `slope` = max_residue:
