@@ -429,6 +429,24 @@ class Engine:
         flow = ops.resize_bilinear(flow, (h, w), False, scale=sc)
         return flow[:nf], flow[nf:]
 
+    def start_pair_flows(self, frames, pairs, fork=True):
+        """pair_flows(frames, pairs) beside whatever the caller issues next on the current stream (the encoder on new frames, in the
+        video driver's reuse=True): returns collect() -> (forward, backward), to be called once, on the same stream, when the flows
+        are needed.  With a fork -- ``fork`` and an eager forward (_fork_ok) -- SPyNet is issued now on the current stream's side
+        stream, which waits for the current stream first, and collect() makes the current stream wait for the side stream.  Without
+        one nothing is issued now and collect() computes the flows on the current stream."""
+        if not (fork and self._fork_ok()):
+            return lambda: self.pair_flows(frames, pairs)
+        main, side = torch.cuda.current_stream(self.device), self._side_stream()
+        side.wait_stream(main)
+        with torch.cuda.stream(side):
+            flows = self.pair_flows(frames, pairs)
+
+        def collect():
+            main.wait_stream(side)
+            return flows
+        return collect
+
     # ------------------------------------------------------------------ encoder
     def encode(self, frames, join=None):
         """join: called in front of encoder.layers.<join_at> (16 at one clip: the fork's other branch, SPyNet, overlaps layers 0 .. 14;

@@ -17,6 +17,25 @@ import torch
 from . import ops
 
 
+def _integer(v, lo=None, hi=None, bools=(bool, np.bool_), typed=False):
+    """Whether ``v`` is an integer in [lo, hi] (None: no bound on that side) -- the one body behind every integer argument check;
+    the caller raises with its own message.  An instance of ``bools`` is no integer.  ``typed``: only an int or a numpy integer
+    is one (2.0 is not); otherwise whatever equals its own int() is (2.0 is, 2.5 and "2" are not)."""
+    try:
+        if isinstance(v, bools) or not (isinstance(v, (int, np.integer)) if typed else int(v) == v):
+            return False
+        return (lo is None or lo <= v) and (hi is None or v <= hi)
+    except (TypeError, ValueError):
+        return False
+
+
+def _check_mask_shape(m):
+    """masks as [L,Hm,Wm] (an array or a tensor); ValueError otherwise"""
+    if len(m.shape) != 3:
+        raise ValueError("masks must be uint8 [L,Hm,Wm], got %s" % (tuple(m.shape),))
+    return m
+
+
 def get_ref_index(f, neighbor_ids, length, ref_length=10, num_ref=-1):
     """test.py:39-53"""
     ref_index = []
@@ -296,9 +315,7 @@ def hole_region(masks_u8, frame_wh, size, context=0.5, device=None):
     inpaint_video(region="hole") resizes to ``size``.  The bounding box is taken on the device (ops.hole_bbox, one pass) and
     costs one copy of four integers to the host; masks of another size than the frames have it mapped to frame pixels, floor
     for the lower ends and ceil for the upper ends.  No hole pixel: the whole frame."""
-    m = _upload(masks_u8, device)
-    if m.dim() != 3:
-        raise ValueError("masks must be uint8 [L,Hm,Wm], got %s" % (tuple(m.shape),))
+    m = _check_mask_shape(_upload(masks_u8, device))
     x0, y0, x1, y1 = (int(v) for v in ops.hole_bbox(m).cpu().tolist())
     if x1 <= x0 or y1 <= y0:
         return plan_region(None, frame_wh, size, context)
@@ -311,11 +328,7 @@ HOLE_COMPONENTS_MAX = 1024     # plan_holes: a footprint in more pieces than thi
 
 def _check_max_regions(max_regions):
     """max_regions= as an int: an integer >= 1; ValueError otherwise (bools and non-integers included)"""
-    try:
-        ok = not isinstance(max_regions, (bool, np.bool_)) and int(max_regions) == max_regions and max_regions >= 1
-    except (TypeError, ValueError):
-        ok = False
-    if not ok:
+    if not _integer(max_regions, 1):
         raise ValueError("max_regions must be an integer >= 1, got %r" % (max_regions,))
     return int(max_regions)
 
@@ -402,9 +415,7 @@ def hole_regions(masks_u8, frame_wh, size, context=0.5, max_regions=4, device=No
     max_regions = _check_max_regions(max_regions)
     frame_wh = tuple(int(v) for v in frame_wh)
     plan_region(None, frame_wh, size, context)                      # from the arguments alone, before any upload
-    m = _upload(masks_u8, device)
-    if m.dim() != 3:
-        raise ValueError("masks must be uint8 [L,Hm,Wm], got %s" % (tuple(m.shape),))
+    m = _check_mask_shape(_upload(masks_u8, device))
     mask_wh = (int(m.shape[2]), int(m.shape[1]))
     _, table = ops.hole_components(m)
     if table.shape[0] == 0:
@@ -437,8 +448,7 @@ def plan_track(frame_boxes, windows, frame_wh, size, context=0.5):
 def _frame_boxes(masks_d, frame_wh):
     """every frame's hole box in frame pixels (None: no hole) from device masks [L,Hm,Wm]: ops.hole_bbox_frames, one pass, and
     one copy of 4 L integers to the host; masks of another size than the frames are mapped like hole_region maps its box"""
-    if masks_d.dim() != 3:
-        raise ValueError("masks must be uint8 [L,Hm,Wm], got %s" % (tuple(masks_d.shape),))
+    _check_mask_shape(masks_d)
     return _map_frame_boxes(ops.hole_bbox_frames(masks_d).cpu().tolist(), (masks_d.shape[2], masks_d.shape[1]), frame_wh)
 
 
@@ -528,18 +538,13 @@ OVERLAY_MAX_FRACTION = 0.25
 
 
 def _check_overlay_args(g_min, coherence, radius, min_area, max_fraction):
-    def integer(v, lo, hi):
-        try:
-            return not isinstance(v, (bool, np.bool_)) and int(v) == v and lo <= v and (hi is None or v <= hi)
-        except (TypeError, ValueError):
-            return False
-    if not integer(g_min, 1, 2 ** 31 - 1):
+    if not _integer(g_min, 1, 2 ** 31 - 1):
         raise ValueError("g_min must be an integer >= 1, got %r" % (g_min,))
-    if not integer(coherence, 1, 256):
+    if not _integer(coherence, 1, 256):
         raise ValueError("coherence must be an integer in (0, 256], got %r" % (coherence,))
-    if not integer(radius, 0, ops.OVERLAY_RADIUS_MAX):
+    if not _integer(radius, 0, ops.OVERLAY_RADIUS_MAX):
         raise ValueError("radius must be an integer in [0, %d], got %r" % (ops.OVERLAY_RADIUS_MAX, radius))
-    if not integer(min_area, 1, None):
+    if not _integer(min_area, 1):
         raise ValueError("min_area must be an integer >= 1, got %r" % (min_area,))
     try:
         ok = not isinstance(max_fraction, (bool, np.bool_)) and 0 < max_fraction <= 1
@@ -603,24 +608,20 @@ def overlay_mask(frames_u8, g_min=OVERLAY_G_MIN, coherence=OVERLAY_COHERENCE, ra
     return _overlay_mask_device(_upload(frames_u8, device), g_min, coherence, radius, min_area, max_fraction).cpu().numpy()
 
 
-def _is_int(v):
-    return not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, np.integer))
-
-
 def _check_keys(keys, length, name="keys"):
     """key frame numbers as a list: at least one, strictly increasing integers in [0, length); ValueError that names the argument"""
     try:
         vals = list(keys)
     except TypeError:
         vals = None
-    if (not vals or not all(_is_int(v) for v in vals) or any(not 0 <= int(v) < length for v in vals)
+    if (not vals or not all(_integer(v, typed=True) for v in vals) or any(not 0 <= int(v) < length for v in vals)
             or any(int(b) <= int(a) for a, b in zip(vals[:-1], vals[1:]))):
         raise ValueError("%s must be a strictly increasing list of at least one frame number in [0, %d), got %r" % (name, length, keys))
     return [int(v) for v in vals]
 
 
 def _check_reach(reach):
-    if reach is not None and (not _is_int(reach) or reach < 1):
+    if reach is not None and not _integer(reach, 1, typed=True):
         raise ValueError("reach must be None or an integer >= 1, got %r" % (reach,))
     return None if reach is None else int(reach)
 
@@ -637,7 +638,7 @@ def plan_mask_chains(length, keys, scenes=None, reach=None):
     job writes a frame of a plane that another job of the step reads or writes (the chains of a plane lie between different keys);
     no job crosses a cut or writes a key frame; every frame within reach of a key of its scene is written exactly once in each plane
     in which it can be reached."""
-    if not _is_int(length) or length < 1:
+    if not _integer(length, 1, typed=True):
         raise ValueError("length must be an integer >= 1, got %r" % (length,))
     length = int(length)
     keys = _check_keys(keys, length)
@@ -701,7 +702,7 @@ def _check_propagate_args(model, shape, key_masks, keys, flows, size, scenes, re
         raise ValueError("check must be a bool, got %r" % (check,))
     if size is not None:
         try:
-            ok = len(size) == 2 and all(_is_int(v) and v > 0 for v in size)
+            ok = len(size) == 2 and all(_integer(v, 1, typed=True) for v in size)
         except TypeError:
             ok = False
         if not ok:
@@ -950,11 +951,7 @@ def _axis_tables(n_in, n_out, box=None):
 
 def _check_feather(feather):
     """feather= as an int: an integer in [0, FEATHER_MAX]; ValueError otherwise"""
-    try:
-        ok = not isinstance(feather, bool) and int(feather) == feather and 0 <= feather <= FEATHER_MAX
-    except (TypeError, ValueError):
-        ok = False
-    if not ok:
+    if not _integer(feather, 0, FEATHER_MAX, bools=bool):
         raise ValueError("feather must be an integer in [0, %d] (source pixels), got %r" % (FEATHER_MAX, feather))
     return int(feather)
 
@@ -1034,6 +1031,88 @@ def prepare_masks(masks_u8, size_hw, device, dilate=True, box=None, ids=None):
     H, W = size_hw
     ytab, xtab = _mask_tables(m.shape[1:3], (H, W), box, device)
     return ops.mask_prepare(m, ytab, xtab, H, W, 4 if dilate else 0, ids=ids)
+
+
+# What a call of inpaint_video asks for, checked and normalised (_check_call) -- the drivers below take it whole.  ``fmt``: the
+# YuvFormat of pixel_format= or None; ``overlay``: masks_u8 == "overlay"; ``scenes``: None, "auto" or the checked list (the
+# drivers get the resolved cuts beside the record); ``region``: None (the whole frame), "box" (``box``: the checked explicit box),
+# "hole", "holes" or "track" (``box`` None: planned from the masks); everything else: the argument of that name.
+_Call = collections.namedtuple("_Call", "fmt overlay scenes mask_keys feather region box max_regions size restore keep_float reuse "
+                                        "batch_windows in_flight neighbor_stride ref_length num_ref dilate pad context")
+
+
+def _check_call(shape, masks_u8, model, *, neighbor_stride, ref_length, num_ref, dilate, pad, batch_windows, keep_float, in_flight,
+                size, reuse, restore, region, context, feather, scenes, max_regions, pixel_format, mask_keys):
+    """Every argument check of inpaint_video, from the arguments and ``shape`` (that of the frames as they come in) alone -- no
+    tensor is made and no device touched -> the _Call of the call.  When a call breaks several rules the first one below raises."""
+    fmt = None if pixel_format is None else _as_yuv_format(pixel_format)
+    if fmt is not None:                                 # the frame size the checks below speak of is the decoded one
+        if keep_float:
+            raise ValueError("pixel_format= returns uint8 YUV frames: keep_float must be False")
+        shape = (shape[0],) + ops.yuv_frame_hw(shape) + (3,)
+        if size is not None and not restore and (int(size[0]) % 2 or int(size[1]) % 2):
+            raise ValueError("pixel_format= returns 4:2:0 frames of (width, height) = size, which must both be even, got %r" % (size,))
+    overlay = isinstance(masks_u8, str)
+    if overlay and masks_u8 != "overlay":
+        raise ValueError('masks_u8 must be uint8 [L,Hm,Wm] masks or "overlay", got %r' % (masks_u8,))
+    if scenes is not None and not (isinstance(scenes, str) and scenes == "auto"):
+        if isinstance(scenes, str):
+            raise ValueError('scenes must be None, "auto" or a list of frame numbers, got %r' % (scenes,))
+        scenes = _check_scenes(scenes, int(shape[0]))                       # from the shapes alone, before any device work
+    if mask_keys is not None:
+        if overlay:
+            raise ValueError('mask_keys= names the frames whose masks are given: with masks_u8="overlay" there are none')
+        auto = isinstance(scenes, str)
+        mask_keys, _ = _check_propagate_args(model, shape, masks_u8, mask_keys, None, size, None if auto else scenes, None, True,
+                                             "mask_keys")
+    feather = _check_feather(feather)
+    if feather and not restore:
+        raise ValueError("feather= ramps the paste-back of restore=True into the source frames: without restore there is no seam "
+                         "to feather")
+    box = None
+    if region is not None:
+        if size is None:
+            raise ValueError("region= names the part of the frames that size= resizes for the model: without size there is no "
+                             "region to cut")
+        if isinstance(region, str):
+            if region not in ("hole", "track", "holes"):
+                raise ValueError('region must be None, "hole", "track", "holes" or (left, upper, right, lower), got %r' % (region,))
+        else:
+            region, box = "box", _check_box(region, (shape[2], shape[1]))
+    if region == "track":
+        if not restore:
+            raise ValueError('region="track" gives every window a box of its own, so the windows\' results exist together only at '
+                             "the source size: restore must be True")
+        if reuse:
+            raise ValueError('region="track" resizes every window with another box, so no frame\'s encoder features or flows can be '
+                             "shared between windows: reuse must be False")
+        if batch_windows > 1:
+            raise ValueError('region="track" runs one window per forward (a window without a hole runs none): batch_windows must be '
+                             "1, got %d" % batch_windows)
+        if in_flight > 1:
+            raise ValueError('region="track" pastes and blends every window at source size in window order on one stream: in_flight '
+                             "must be 1, got %d" % in_flight)
+    if region == "holes":
+        max_regions = _check_max_regions(max_regions)
+        if not restore:
+            raise ValueError('region="holes" gives every group of holes a box of its own, so the passes\' results exist together only '
+                             "at the source size: restore must be True")
+    if restore:
+        if size is None:
+            raise ValueError("restore=True pastes the result back into frames that size= resized: without size there is nothing "
+                             "to restore")
+        if keep_float:
+            raise ValueError("restore=True returns uint8 frames at the source size: keep_float must be False")
+    if reuse:
+        if batch_windows > 1:
+            raise ValueError("reuse=True runs one window per forward: batch_windows must be 1, got %d" % batch_windows)
+        if in_flight > 1:
+            raise ValueError("reuse=True runs one window at a time: in_flight must be 1, got %d" % in_flight)
+        if not callable(getattr(model, "engine", None)):
+            raise TypeError("reuse=True needs the InpaintGenerator (its engine runs the encoder, SPyNet and the rest of the "
+                            "forward as separate pieces), got %s" % type(model).__name__)
+    return _Call(fmt, overlay, scenes, mask_keys, feather, region, box, max_regions, size, restore, keep_float, reuse, batch_windows,
+                 in_flight, neighbor_stride, ref_length, num_ref, dilate, pad, context)
 
 
 @torch.no_grad()
@@ -1161,121 +1240,48 @@ def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, 
     the rim the consistency test costs) as given.  ``model`` must be the generator (an object with ``engine()``; TypeError
     otherwise); mask_keys with masks_u8="overlay" raises ValueError.  None is the path of a call without the argument, byte for
     byte, with no launch added."""
-    fmt = None if pixel_format is None else _as_yuv_format(pixel_format)
-    shape = tuple(frames_u8.shape)
-    if fmt is not None:                                 # the frame size the checks below speak of is the decoded one
-        if keep_float:
-            raise ValueError("pixel_format= returns uint8 YUV frames: keep_float must be False")
-        shape = (shape[0],) + ops.yuv_frame_hw(shape) + (3,)
-        if size is not None and not restore and (int(size[0]) % 2 or int(size[1]) % 2):
-            raise ValueError("pixel_format= returns 4:2:0 frames of (width, height) = size, which must both be even, got %r" % (size,))
-    overlay = isinstance(masks_u8, str)
-    if overlay and masks_u8 != "overlay":
-        raise ValueError('masks_u8 must be uint8 [L,Hm,Wm] masks or "overlay", got %r' % (masks_u8,))
-    if scenes is not None and not (isinstance(scenes, str) and scenes == "auto"):
-        if isinstance(scenes, str):
-            raise ValueError('scenes must be None, "auto" or a list of frame numbers, got %r' % (scenes,))
-        scenes = _check_scenes(scenes, int(shape[0]))                       # from the shapes alone, before any device work
-    if mask_keys is not None:
-        if overlay:
-            raise ValueError('mask_keys= names the frames whose masks are given: with masks_u8="overlay" there are none')
-        auto = isinstance(scenes, str)
-        mask_keys, _ = _check_propagate_args(model, shape, masks_u8, mask_keys, None, size, None if auto else scenes, None, True,
-                                             "mask_keys")
-    feather = _check_feather(feather)
-    if feather and not restore:
-        raise ValueError("feather= ramps the paste-back of restore=True into the source frames: without restore there is no seam "
-                         "to feather")
-    box = None
-    track = holes = False
-    if region is not None:
-        if size is None:
-            raise ValueError("region= names the part of the frames that size= resizes for the model: without size there is no "
-                             "region to cut")
-        if isinstance(region, str):
-            if region not in ("hole", "track", "holes"):
-                raise ValueError('region must be None, "hole", "track", "holes" or (left, upper, right, lower), got %r' % (region,))
-            track = region == "track"
-            holes = region == "holes"
-        else:
-            box = _check_box(region, (shape[2], shape[1]))
-    if track:
-        if not restore:
-            raise ValueError('region="track" gives every window a box of its own, so the windows\' results exist together only at '
-                             "the source size: restore must be True")
-        if reuse:
-            raise ValueError('region="track" resizes every window with another box, so no frame\'s encoder features or flows can be '
-                             "shared between windows: reuse must be False")
-        if batch_windows > 1:
-            raise ValueError('region="track" runs one window per forward (a window without a hole runs none): batch_windows must be '
-                             "1, got %d" % batch_windows)
-        if in_flight > 1:
-            raise ValueError('region="track" pastes and blends every window at source size in window order on one stream: in_flight '
-                             "must be 1, got %d" % in_flight)
-    if holes:
-        max_regions = _check_max_regions(max_regions)
-        if not restore:
-            raise ValueError('region="holes" gives every group of holes a box of its own, so the passes\' results exist together only '
-                             "at the source size: restore must be True")
-    if restore:
-        if size is None:
-            raise ValueError("restore=True pastes the result back into frames that size= resized: without size there is nothing "
-                             "to restore")
-        if keep_float:
-            raise ValueError("restore=True returns uint8 frames at the source size: keep_float must be False")
-    if reuse:
-        if batch_windows > 1:
-            raise ValueError("reuse=True runs one window per forward: batch_windows must be 1, got %d" % batch_windows)
-        if in_flight > 1:
-            raise ValueError("reuse=True runs one window at a time: in_flight must be 1, got %d" % in_flight)
-        if not callable(getattr(model, "engine", None)):
-            raise TypeError("reuse=True needs the InpaintGenerator (its engine runs the encoder, SPyNet and the rest of the "
-                            "forward as separate pieces), got %s" % type(model).__name__)
+    call = _check_call(tuple(frames_u8.shape), masks_u8, model, neighbor_stride=neighbor_stride, ref_length=ref_length, num_ref=num_ref,
+                       dilate=dilate, pad=pad, batch_windows=batch_windows, keep_float=keep_float, in_flight=in_flight, size=size,
+                       reuse=reuse, restore=restore, region=region, context=context, feather=feather, scenes=scenes,
+                       max_regions=max_regions, pixel_format=pixel_format, mask_keys=mask_keys)
     if device is None:
         device = next(model.parameters()).device if hasattr(model, "parameters") else torch.device("cuda")
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError("inpaint_video runs on the MI355X (cuda) device only; there is no CPU path")
-    if isinstance(frames_u8, torch.Tensor) and frames_u8.is_cuda:
-        frames_d = frames_u8.to(device).contiguous()
-    else:
-        frames_d = torch.as_tensor(np.ascontiguousarray(frames_u8)).to(device)
+    source = _upload(frames_u8, device)                 # restore=True: kept beside the resized frames, only read
     like = None
-    if fmt is not None:                                 # decoded once; the caller's bytes stay for the paste on the way out
-        like, frames_d = frames_d, _decode_yuv(frames_d, fmt)
-    source = frames_d                                   # restore=True: kept beside the resized frames, only read
-    if overlay:                                         # on the frames at source size; the same hole in every frame
+    if call.fmt is not None:                            # decoded once; the caller's bytes stay for the paste on the way out
+        like, source = source, _decode_yuv(source, call.fmt)
+    if call.overlay:                                    # on the frames at source size; the same hole in every frame
         if source.shape[0] < 1 or source.shape[1] * source.shape[2] == 0:
             raise ValueError('masks_u8="overlay" needs frames to find the overlay in, got %s' % (tuple(source.shape),))
         masks_d = _overlay_mask_device(source, OVERLAY_G_MIN, OVERLAY_COHERENCE, OVERLAY_RADIUS, OVERLAY_MIN_AREA,
                                        OVERLAY_MAX_FRACTION).unsqueeze(0).expand(source.shape[:3]).contiguous()
     else:
         masks_d = _upload(masks_u8, device)             # once: the bounding box and the mask preparation read the same tensor
-    if isinstance(scenes, str):                         # "auto": on the frames at source size
-        scenes = detect_cuts(source)
-    if mask_keys is not None:                           # the masks of all frames from the K that were given, with the resolved cuts
-        masks_d = _propagate_masks_device(model, source, masks_d, mask_keys, plan_mask_chains(int(source.shape[0]), mask_keys, scenes),
-                                          None, size, True)
-    out = _inpaint_planned(model, source, masks_d, size, scenes, track, holes, box, region is not None, neighbor_stride, ref_length,
-                           num_ref, dilate, pad, batch_windows, keep_float, in_flight, reuse, restore, context, feather, max_regions)
-    if fmt is not None:                                 # the source's size: the paste form, the caller's bytes where nothing changed
-        out = _encode_yuv(out, fmt, like, source) if size is None or restore else _encode_yuv(out, fmt)
-    return out if keep_float else out.cpu().numpy()
+    cuts = detect_cuts(source) if call.scenes == "auto" else call.scenes       # "auto": on the frames at source size
+    if call.mask_keys is not None:                      # the masks of all frames from the K that were given, with the resolved cuts
+        masks_d = _propagate_masks_device(model, source, masks_d, call.mask_keys,
+                                          plan_mask_chains(int(source.shape[0]), call.mask_keys, cuts), None, call.size, True)
+    out = _inpaint_planned(model, source, masks_d, cuts, call)
+    if call.fmt is not None:                            # the source's size: the paste form, the caller's bytes where nothing changed
+        out = _encode_yuv(out, call.fmt, like, source) if call.size is None or call.restore else _encode_yuv(out, call.fmt)
+    return out if call.keep_float else out.cpu().numpy()
 
 
-def _inpaint_planned(model, source, masks_d, size, scenes, track, holes, box, region, neighbor_stride, ref_length, num_ref, dilate, pad,
-                     batch_windows, keep_float, in_flight, reuse, restore, context, feather, max_regions):
-    """inpaint_video after the argument checks, the uploads and the detectors: picks the driver and the box(es) and returns the
-    result as a device tensor (uint8, or fp32 with keep_float) -- the one host copy of a call is inpaint_video's"""
-    if track:
-        return _inpaint_track(model, source, masks_d, tuple(int(v) for v in size),
-                              plan_windows(source.shape[0], neighbor_stride, ref_length, num_ref, scenes), dilate, pad, context, feather)
-    run = lambda b, paste=None: _inpaint_box(model, source, masks_d, b, size, scenes, neighbor_stride, ref_length, num_ref, dilate, pad,
-                                             batch_windows, keep_float, in_flight, reuse, restore, feather, paste)
-    if region:
+def _inpaint_planned(model, source, masks_d, scenes, call):
+    """inpaint_video after the argument checks, the uploads and the detectors (``scenes``: the resolved cuts): picks the driver and
+    the box(es) and returns the result as a device tensor (uint8, or fp32 with keep_float) -- the one host copy of a call is
+    inpaint_video's"""
+    if call.region == "track":
+        windows = plan_windows(source.shape[0], call.neighbor_stride, call.ref_length, call.num_ref, scenes)
+        return _inpaint_track(model, source, masks_d, windows, call)
+    box = call.box
+    if call.region is not None:
         frame_wh = (source.shape[2], source.shape[1])
-        if holes:
-            regions = hole_regions(masks_d, frame_wh, size, context, max_regions)
+        if call.region == "holes":
+            regions = hole_regions(masks_d, frame_wh, call.size, call.context, call.max_regions)
             if not regions:
                 return source
             if len(regions) > 1:
@@ -1283,18 +1289,124 @@ def _inpaint_planned(model, source, masks_d, size, scenes, track, holes, box, re
                 # those still are the source, which is all the paste reads of them there (the ramp of feather= included)
                 out = source
                 for b in regions:
-                    out = run(b, out)
+                    out = _inpaint_box(model, source, masks_d, b, scenes, call, paste=out)
                 return out
             box = regions[0]                            # one group: the box and the path of region="hole"
-        elif box is None:
-            box = hole_region(masks_d, frame_wh, size, context)
+        elif call.region == "hole":
+            box = hole_region(masks_d, frame_wh, call.size, call.context)
         if box == (0, 0) + frame_wh:
             box = None                                  # the whole frame: the path (and the bytes) of region=None
-    return run(box)
+    return _inpaint_box(model, source, masks_d, box, scenes, call)
 
 
-def _inpaint_box(model, source, masks_d, box, size, scenes, neighbor_stride, ref_length, num_ref, dilate, pad, batch_windows,
-                 keep_float, in_flight, reuse, restore, feather, paste=None):
+def _window_tables(windows, length, device, run=None):
+    """(ids_dev, first_dev), one entry per window: the int32 frame ids ``nb + rf`` and the uint8 "first prediction of this frame"
+    flags of the reference's ``comp_frames[idx] is None`` test (test.py:172-176) for ``nb``.  ``run``: the windows that run, in
+    order (None: all of them) -- a skipped window gets None for both and marks no frame as seen.  Uploads: call it before the first
+    forward."""
+    ids_dev, first_dev = [None] * len(windows), [None] * len(windows)
+    seen = [False] * length
+    for k in range(len(windows)) if run is None else run:
+        nb, rf = windows[k]
+        ids_dev[k] = torch.tensor(nb + rf, dtype=torch.int32, device=device)
+        first_dev[k] = torch.tensor([0 if seen[j] else 1 for j in nb], dtype=torch.uint8, device=device)
+        for j in nb:
+            seen[j] = True
+    return ids_dev, first_dev
+
+
+def _run_sequential(n_windows, predict, composite):
+    """like the reference: every window is composited right after its forward, nothing is kept; no stream, no event"""
+    for i in range(n_windows):
+        composite(i, predict([i])[0])
+
+
+def _run_in_flight(n_windows, predict, composite, in_flight, device):
+    """the forwards of ``in_flight`` consecutive windows on as many streams, the compositing on the caller's in window order"""
+    cur = torch.cuda.current_stream(device)
+    streams = [torch.cuda.Stream(device=device) for _ in range(in_flight)]
+    for st in streams:
+        st.wait_stream(cur)                             # the uploads, the mask preparation
+    queue = []                                          # (window, its local predictions, event) in window order
+    for i in range(n_windows):
+        st = streams[i % in_flight]
+        with torch.cuda.stream(st):
+            p = predict([i])[0]
+            ev = torch.cuda.Event()
+            ev.record(st)
+        p.record_stream(cur)                            # allocated on st, read by the compositing kernel on cur
+        queue.append((i, p, ev))
+        if len(queue) == in_flight:
+            j, pj, evj = queue.pop(0)
+            cur.wait_event(evj)
+            composite(j, pj)
+    for j, pj, evj in queue:
+        cur.wait_event(evj)
+        composite(j, pj)
+
+
+def _run_batched(windows, predict, composite, batch_windows):
+    """up to ``batch_windows`` windows of equal shape (local frames, reference frames) per forward"""
+    by_shape = {}
+    for i, (nb, rf) in enumerate(windows):
+        by_shape.setdefault((len(nb), len(rf)), []).append(i)
+    groups = sorted((idx[k:k + batch_windows] for idx in by_shape.values() for k in range(0, len(idx), batch_windows)),
+                    key=lambda g: g[0])
+    # the 0.5/0.5 blend is order dependent: predictions are composited in the reference's window order as soon as
+    # all earlier windows are done; a window that has to wait keeps only its local frames (a copy, so the batch
+    # output with the reference frames' predictions is released)
+    pending, nxt = {}, 0
+    for grp in groups:
+        for i, p in zip(grp, predict(grp)):
+            if i == nxt:
+                composite(i, p)
+                nxt += 1
+            else:
+                pending[i] = p.clone()
+        while nxt in pending:
+            composite(nxt, pending.pop(nxt))
+            nxt += 1
+    assert not pending and nxt == len(windows)
+
+
+def _run_reuse(eng, windows, frames_d, masks01, padded_hw, composite):
+    """every frame through the encoder once and every adjacent pair through SPyNet once (plan_reuse), one window at a time"""
+    device = frames_d.device
+    Hp, Wp = padded_hw
+    h4, w4 = Hp // 4, Wp // 4
+    plan = plan_reuse(windows)
+    i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=device) if len(v) else None
+    # the plan's tables are uploads too: all of them before the first forward
+    tabs = [dict(clip=i32(p["clip"]), new_slots=i32(p["new_slots"]), enc_slots=i32(p["enc_slots"]),
+                 pairs=eng.pair_table(p["pair_pos"]) if p["pairs"] else None, new_pair_slots=i32(p["new_pair_slots"]),
+                 flow_slots=i32(p["flow_slots"])) for p in plan.windows]
+    enc_cache = torch.empty((plan.slots, h4, w4, 128), dtype=eng.dtype, device=device)
+    fwd_cache = torch.empty((max(plan.pair_slots, 1), h4, w4, 2), dtype=torch.float32, device=device)
+    bwd_cache = torch.empty_like(fwd_cache)
+    for i, (p, tb) in enumerate(zip(plan.windows, tabs)):
+        n = len(p["neighbors"])
+        if p["clip"]:
+            x = ops.masked_clip(frames_d, masks01, tb["clip"], Hp, Wp)[0]
+            # the new pairs' SPyNet beside the new frames' encoder; without new frames there is nothing to run it beside
+            flows = eng.start_pair_flows(x, tb["pairs"], fork=bool(p["encode"])) if p["pairs"] else None
+            if p["encode"]:
+                ops.scatter_slabs(eng.encode_frames(x[:len(p["encode"])]), tb["new_slots"], enc_cache)
+            if flows is not None:
+                fwd, bwd = flows()
+                ops.scatter_slabs(fwd, tb["new_pair_slots"], fwd_cache)
+                ops.scatter_slabs(bwd, tb["new_pair_slots"], bwd_cache)
+        # the window's tensors are copies: propagation overwrites the local frames' features in place
+        feats = ops.gather_slabs(enc_cache, tb["enc_slots"])
+        if n > 1:
+            fl = (ops.gather_slabs(fwd_cache, tb["flow_slots"]).view(1, n - 1, h4, w4, 2),
+                  ops.gather_slabs(bwd_cache, tb["flow_slots"]).view(1, n - 1, h4, w4, 2))
+        else:
+            fl = (torch.empty((1, 0, h4, w4, 2), dtype=torch.float32, device=device),) * 2
+        pred, _ = eng.forward(None, n, given=(fl, feats), decode_local=True)
+        composite(i, pred)
+
+
+def _inpaint_box(model, source, masks_d, box, scenes, call, paste=None):
     """inpaint_video after the argument checks, the uploads and the choice of the box: source uint8 [L,H,W,3] and masks_d uint8
     [L,Hm,Wm] on the device, ``box`` None (the whole frame) or a checked box that is not the whole frame, ``scenes`` None or a
     checked list -> the device tensor of the result: fp32 [L,h,w,3] with keep_float, else uint8.  ``paste`` (with restore): the
@@ -1304,24 +1416,16 @@ def _inpaint_box(model, source, masks_d, box, size, scenes, neighbor_stride, ref
     mask_box = None
     if box is not None:
         mask_box = _scale_box(box, (source.shape[2], source.shape[1]), (masks_d.shape[2], masks_d.shape[1]))
-    if size is not None:
-        frames_d = resize_frames(frames_d, size, box=box)   # on the caller's stream, before any stream below waits on it
+    if call.size is not None:
+        frames_d = resize_frames(frames_d, call.size, box=box)  # on the caller's stream, before any stream below waits on it
     L, h, w, _ = frames_d.shape
-    masks01 = prepare_masks(masks_d, (h, w), device, dilate, box=mask_box)
-    Hp, Wp = padded_size(h, w) if pad else (h, w)
-    windows = plan_windows(L, neighbor_stride, ref_length, num_ref, scenes)
-    # every host->device upload happens here, before the first forward: frame ids of each window and the
-    # "first prediction of this frame" flags of the reference's comp_frames[idx] is None test (test.py:172-176)
-    ids_dev = [torch.tensor(nb + rf, dtype=torch.int32, device=device) for nb, rf in windows]
-    seen = [False] * L
-    first_dev = []
-    for nb, _ in windows:
-        first_dev.append(torch.tensor([0 if seen[j] else 1 for j in nb], dtype=torch.uint8, device=device))
-        for j in nb:
-            seen[j] = True
+    masks01 = prepare_masks(masks_d, (h, w), device, call.dilate, box=mask_box)
+    Hp, Wp = padded_size(h, w) if call.pad else (h, w)
+    windows = plan_windows(L, call.neighbor_stride, call.ref_length, call.num_ref, scenes)
+    ids_dev, first_dev = _window_tables(windows, L, device)     # every host->device upload happens here, before the first forward
     comp = torch.empty((L, h, w, 3), dtype=torch.float32, device=device)
     # feather: the prediction is kept everywhere (test.py:172-174 with a mask of ones), the paste decides what of it is used
-    comp_masks = torch.ones_like(masks01) if feather else masks01
+    comp_masks = torch.ones_like(masks01) if call.feather else masks01
 
     def predict(group):
         x = torch.cat([ops.masked_clip(frames_d, masks01, ids_dev[i], Hp, Wp) for i in group], 0) if len(group) > 1 \
@@ -1335,98 +1439,18 @@ def _inpaint_box(model, source, masks_d, box, size, scenes, neighbor_stride, ref
         n = len(windows[i][0])
         ops.composite(pred.contiguous(), ids_dev[i][:n], first_dev[i], frames_d, comp_masks, comp)
 
-    if reuse:
-        eng = model.engine()
-        h4, w4 = Hp // 4, Wp // 4
-        plan = plan_reuse(windows)
-        i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=device) if len(v) else None
-        # the plan's tables are uploads too: all of them before the first forward
-        tabs = [dict(clip=i32(p["clip"]), new_slots=i32(p["new_slots"]), enc_slots=i32(p["enc_slots"]),
-                     pairs=eng.pair_table(p["pair_pos"]) if p["pairs"] else None, new_pair_slots=i32(p["new_pair_slots"]),
-                     flow_slots=i32(p["flow_slots"])) for p in plan.windows]
-        enc_cache = torch.empty((plan.slots, h4, w4, 128), dtype=eng.dtype, device=device)
-        fwd_cache = torch.empty((max(plan.pair_slots, 1), h4, w4, 2), dtype=torch.float32, device=device)
-        bwd_cache = torch.empty_like(fwd_cache)
-        for i, (p, tb) in enumerate(zip(plan.windows, tabs)):
-            n = len(p["neighbors"])
-            if p["clip"]:
-                x = ops.masked_clip(frames_d, masks01, tb["clip"], Hp, Wp)[0]
-                flows = None
-                main = torch.cuda.current_stream(device)
-                fork = bool(p["pairs"]) and bool(p["encode"]) and eng._fork_ok()
-                if fork:                                # the new pairs' SPyNet beside the new frames' encoder, as in Engine.forward
-                    side = eng._side_stream()
-                    side.wait_stream(main)
-                    with torch.cuda.stream(side):
-                        flows = eng.pair_flows(x, tb["pairs"])
-                if p["encode"]:
-                    ops.scatter_slabs(eng.encode_frames(x[:len(p["encode"])]), tb["new_slots"], enc_cache)
-                if fork:
-                    main.wait_stream(side)
-                elif p["pairs"]:
-                    flows = eng.pair_flows(x, tb["pairs"])
-                if flows is not None:
-                    ops.scatter_slabs(flows[0], tb["new_pair_slots"], fwd_cache)
-                    ops.scatter_slabs(flows[1], tb["new_pair_slots"], bwd_cache)
-            # the window's tensors are copies: propagation overwrites the local frames' features in place
-            feats = ops.gather_slabs(enc_cache, tb["enc_slots"])
-            if n > 1:
-                fl = (ops.gather_slabs(fwd_cache, tb["flow_slots"]).view(1, n - 1, h4, w4, 2),
-                      ops.gather_slabs(bwd_cache, tb["flow_slots"]).view(1, n - 1, h4, w4, 2))
-            else:
-                fl = (torch.empty((1, 0, h4, w4, 2), dtype=torch.float32, device=device),) * 2
-            pred, _ = eng.forward(None, n, given=(fl, feats), decode_local=True)
-            composite(i, pred)
-    elif batch_windows <= 1 and in_flight > 1:
-        cur = torch.cuda.current_stream(device)
-        streams = [torch.cuda.Stream(device=device) for _ in range(in_flight)]
-        for st in streams:
-            st.wait_stream(cur)                         # the uploads, the mask preparation
-        queue = []                                      # (window, its local predictions, event) in window order
-        for i in range(len(windows)):
-            st = streams[i % in_flight]
-            with torch.cuda.stream(st):
-                p = predict([i])[0]
-                ev = torch.cuda.Event()
-                ev.record(st)
-            p.record_stream(cur)                        # allocated on st, read by the compositing kernel on cur
-            queue.append((i, p, ev))
-            if len(queue) == in_flight:
-                j, pj, evj = queue.pop(0)
-                cur.wait_event(evj)
-                composite(j, pj)
-        for j, pj, evj in queue:
-            cur.wait_event(evj)
-            composite(j, pj)
-    elif batch_windows <= 1:
-        # like the reference: every window is composited right after its forward, nothing is kept
-        for i in range(len(windows)):
-            composite(i, predict([i])[0])
+    if call.reuse:
+        _run_reuse(model.engine(), windows, frames_d, masks01, (Hp, Wp), composite)
+    elif call.batch_windows > 1:
+        _run_batched(windows, predict, composite, call.batch_windows)
+    elif call.in_flight > 1:
+        _run_in_flight(len(windows), predict, composite, call.in_flight, device)
     else:
-        by_shape = {}
-        for i, (nb, rf) in enumerate(windows):
-            by_shape.setdefault((len(nb), len(rf)), []).append(i)
-        groups = sorted((idx[k:k + batch_windows] for idx in by_shape.values() for k in range(0, len(idx), batch_windows)),
-                        key=lambda g: g[0])
-        # the 0.5/0.5 blend is order dependent: predictions are composited in the reference's window order as soon as
-        # all earlier windows are done; a window that has to wait keeps only its local frames (a copy, so the batch
-        # output with the reference frames' predictions is released)
-        pending, nxt = {}, 0
-        for grp in groups:
-            for i, p in zip(grp, predict(grp)):
-                if i == nxt:
-                    composite(i, p)
-                    nxt += 1
-                else:
-                    pending[i] = p.clone()
-            while nxt in pending:
-                composite(nxt, pending.pop(nxt))
-                nxt += 1
-        assert not pending and nxt == len(windows)
-    if keep_float:
+        _run_sequential(len(windows), predict, composite)
+    if call.keep_float:
         return comp
-    if restore:
-        return restore_frames(ops.float_to_u8(comp), masks01, source if paste is None else paste, box=box, feather=feather)
+    if call.restore:
+        return restore_frames(ops.float_to_u8(comp), masks01, source if paste is None else paste, box=box, feather=call.feather)
     return ops.float_to_u8(comp)
 
 
@@ -1444,17 +1468,18 @@ def _touched(k, windows, boxes):
     return left, upper, right, lower
 
 
-def _inpaint_track(model, source, masks_d, size, windows, dilate, pad, context, feather=0):
+def _inpaint_track(model, source, masks_d, windows, call):
     """inpaint_video(region="track") after the argument checks and the uploads: source uint8 [L,H,W,3] and masks_d uint8
     [L,Hm,Wm] on the device -> uint8 [L,H,W,3] on the device"""
     device = source.device
     L, H, W, _ = source.shape
+    size, dilate, feather = tuple(int(v) for v in call.size), call.dilate, call.feather
     w, h = size
-    boxes = plan_track(_frame_boxes(masks_d, (W, H)), windows, (W, H), size, context)
+    boxes = plan_track(_frame_boxes(masks_d, (W, H)), windows, (W, H), size, call.context)
     run = [k for k, b in enumerate(boxes) if b is not None]
     if not run:
         return source
-    Hp, Wp = padded_size(h, w) if pad else (h, w)
+    Hp, Wp = padded_size(h, w) if call.pad else (h, w)
     mask_hw = tuple(int(v) for v in masks_d.shape[1:3])
     # every host->device upload happens here, before the first forward: per distinct box the tables of the frame resize, of the
     # mask resize and of the paste-back (windows with equal boxes share them); per window its frame ids and first flags
@@ -1465,15 +1490,8 @@ def _inpaint_track(model, source, masks_d, size, windows, dilate, pad, context, 
             mask_box = _scale_box(b, (W, H), (mask_hw[1], mask_hw[0]))
             tables[b] = (_resize_plan((H, W), size, b, device, gather=True), _mask_tables(mask_hw, (h, w), mask_box, device),
                          _restore_tables((h, w), (b[3] - b[1], b[2] - b[0]), device))
-    ids_dev, first_dev, touch = {}, {}, {}
-    seen = [False] * L
-    for k in run:
-        nb, rf = windows[k]
-        ids_dev[k] = torch.tensor(nb + rf, dtype=torch.int32, device=device)
-        first_dev[k] = torch.tensor([0 if seen[j] else 1 for j in nb], dtype=torch.uint8, device=device)
-        for j in nb:
-            seen[j] = True
-        touch[k] = _touched(k, windows, boxes)
+    ids_dev, first_dev = _window_tables(windows, L, device, run)
+    touch = {k: _touched(k, windows, boxes) for k in run}
     t_max = max(len(windows[k][0]) + len(windows[k][1]) for k in run)
     n_max = max(len(windows[k][0]) for k in run)
     local = torch.arange(t_max, dtype=torch.int32, device=device)       # a window's frames are numbered 0 ... t - 1 once resized
