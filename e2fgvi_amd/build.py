@@ -32,8 +32,9 @@ UNITS = [("error.hip", "error.o", []), ("conv.hip", "conv.o", []), ("conv.hip", 
          ("attention_bf16.hip", "attention_bf16.o", NOPK), ("attention_x3.hip", "attention_x3.o", NOPK), ("misc.hip", "misc.o", NOPK),
          ("video.hip", "video.o", NOPK), ("yuv.hip", "yuv.o", NOPK), ("metrics.hip", "metrics.o", NOPK),
          # fp64 in the order written: the numpy restatement matches the step bit for bit only without fused multiply-adds
-         ("mask_track.hip", "mask_track.o", NOPK + ["-ffp-contract=off"])]
-NOPK_OBJECTS = ("conv_nopk.o", "conv_bf16x.o", "conv_wino.o", "conv_wino4.o", "conv_wino_x3.o", "conv_tail.o", "mdcn.o", "attention_bf16.o", "attention_x3.o", "misc.o", "video.o", "yuv.o", "metrics.o", "mask_track.o")
+         ("mask_track.hip", "mask_track.o", NOPK + ["-ffp-contract=off"]),
+         ("defects.hip", "defects.o", NOPK)]
+NOPK_OBJECTS = ("conv_nopk.o", "conv_bf16x.o", "conv_wino.o", "conv_wino4.o", "conv_wino_x3.o", "conv_tail.o", "mdcn.o", "attention_bf16.o", "attention_x3.o", "misc.o", "video.o", "yuv.o", "metrics.o", "mask_track.o", "defects.o")
 OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 
 
@@ -88,6 +89,7 @@ def build(force=False, verbose=False, nopk_all=False, lib=None, tag=None, define
             verify_no_scratch(objdir, "conv_bf16x.o", "conv_halo_x3_kernel", "split-operand halo")
             verify_no_scratch(objdir, "video.o", "restore_u8_kernel", "paste-back")
             verify_no_scratch(objdir, "video.o", "overlay_stats_kernel", "overlay sums")
+            verify_no_scratch(objdir, "defects.o", "defect_", "dust and dirt")
             verify_overlay_prefetch(objdir)
             verify_no_pk_u8(objdir)
             verify_no_fma64(objdir)
@@ -169,7 +171,8 @@ def verify_no_scratch(objdir=None, obj="conv_bf16x.o", marker="ELb0ELi2ELb1EEE",
     across four barriers per K-step; two ways of writing that loop made hipcc spill 414 registers or copy the kernel arguments to
     scratch without a warning (csrc/conv_bf16x.hip, PP).  Fails the build when one of them has a private segment or a spill.
     Also run over the four instantiations of restore_u8_kernel (video.o): the feathered ones hold five LDS phases in one kernel;
-    and over the four of overlay_stats_kernel, which keeps 24 sums and the next frame's 9 words in registers across its frame loop."""
+    and over the four of overlay_stats_kernel, which keeps 24 sums and the next frame's 9 words in registers across its frame loop;
+    and over the four kernels of defects.o (the candidate kernel unrolls up to 2 x 36 gathers for each of a thread's four pixels)."""
     import re
     import shutil
     import tempfile

@@ -1854,6 +1854,100 @@ def mask_track_step(planes, fwd, bwd, jobs, check=True):
     return pl
 
 
+DEFECT_THRESHOLD_MAX = 254                 # csrc/defects.hip: tau, slack, support and radius outside these are E2FGVI_EINVAL
+DEFECT_SLACK_MAX = 2
+DEFECT_RADIUS_MAX = 16                     # csrc/defects.hip DF_RMAX: the largest dilation radius defect_clean keeps in LDS
+
+
+def _defect_inputs(named, first):
+    """mask_track_step's checks for the defect entries: ``named`` = ((name, value, dtype), ...) -> the tensors on the device of the
+    first one that is there already (anything else through torch.as_tensor and uploaded); a wrong dtype, a non-contiguous input and
+    a tensor on another device than ``first`` raise ValueError"""
+    device = next((t.device for _, t, _ in named if isinstance(t, torch.Tensor) and t.is_cuda), "cuda")
+    up = [t if isinstance(t, torch.Tensor) and t.is_cuda else torch.as_tensor(t).to(device) for _, t, _ in named]
+    for t, (nm, _, dt) in zip(up, named):
+        if t.dtype != dt:
+            raise ValueError("%s must be %s, got %s" % (nm, dt, t.dtype))
+        if not t.is_contiguous():
+            raise ValueError("%s must be contiguous" % nm)
+        if t.device != up[0].device:
+            raise ValueError("%s is on %s, the %s on %s" % (nm, t.device, first, up[0].device))
+    return up
+
+
+def _defect_int(name, v, lo, hi):
+    if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not lo <= v <= hi:
+        raise ValueError("%s must be an integer in [%d, %d], got %r" % (name, lo, hi, v))
+    return int(v)
+
+
+def defect_candidates(frames, fwd, bwd, ids, threshold, slack, out=None):
+    """The candidates of the dust-and-dirt detector (csrc/defects.hip; include/e2fgvi_hip.h has the definition; video.detect_defects
+    is the caller): frames uint8 [L,H,W,3]; fwd, bwd fp32 [L-1,H,W,2] in metrics.warp_error's convention; ids int32 [n], the centre
+    frames to do (distinct; one outside [1, L-2] writes nothing) -> device uint8 [L,H,W] of 0 / 1: a pixel of a listed frame is 1
+    when its integer luma lies more than ``threshold`` above the largest or below the smallest luma of the pixels around its
+    motion-compensated position in BOTH neighbouring frames (``slack`` more pixels on every side of the 2 x 2 the bilinear sample
+    would read).  One launch, no host read.  ``out``: a device uint8 [L,H,W] to write the listed frames into (its other frames stay
+    as they are); without it a buffer of zeros.  threshold in [0, 254], slack in [0, 2]: integers, no bools.  Device tensors, or
+    anything torch.as_tensor accepts (uploaded first); wrong dtypes, shapes that do not fit, non-contiguous inputs and tensors on
+    different devices raise ValueError.  There is no CPU path.  The same inputs give the same bits in every run."""
+    lib = _L.load()
+    threshold = _defect_int("threshold", threshold, 0, DEFECT_THRESHOLD_MAX)
+    slack = _defect_int("slack", slack, 0, DEFECT_SLACK_MAX)
+    named = [("frames", frames, torch.uint8), ("fwd", fwd, torch.float32), ("bwd", bwd, torch.float32), ("ids", ids, torch.int32)]
+    if out is not None:
+        named.append(("out", out, torch.uint8))
+    up = _defect_inputs(named, "frames")
+    fr, fw, bw, idt = up[:4]
+    if fr.dim() != 4 or fr.shape[3] != 3:
+        raise ValueError("frames must be [L,H,W,3], got %s" % (tuple(fr.shape),))
+    L, H, W, _ = fr.shape
+    if idt.dim() != 1:
+        raise ValueError("ids must be int32 [n], got %s" % (tuple(idt.shape),))
+    for t, nm in ((fw, "fwd"), (bw, "bwd")):
+        if L >= 1 and tuple(t.shape) != (L - 1, H, W, 2):
+            raise ValueError("%s must be [%d,%d,%d,2] for frames %s, got %s" % (nm, L - 1, H, W, tuple(fr.shape), tuple(t.shape)))
+    if out is not None and tuple(up[4].shape) != (L, H, W):
+        raise ValueError("out must be [%d,%d,%d], got %s" % (L, H, W, tuple(up[4].shape)))
+    with torch.cuda.device(fr.device):
+        cand = up[4] if out is not None else torch.zeros((L, H, W), dtype=torch.uint8, device=fr.device)
+        _L.check(lib.e2fgvi_defect_candidates(_ptr(fr), _ptr(fw), _ptr(bw), _ptr(idt), idt.shape[0], L, H, W, threshold, slack,
+                                              _ptr(cand), _stream()), "defect_candidates")
+    return cand
+
+
+def defect_clean(cand, ids, support, radius, out=None):
+    """The support test and the dilation of the dust-and-dirt detector, one launch (csrc/defects.hip defect_clean_kernel;
+    include/e2fgvi_hip.h has the definition): cand uint8 [L,H,W] (any non-zero byte is a candidate), ids int32 [n] as for
+    defect_candidates -> (masks, counts) on the device: in a listed frame a candidate stays when the 3 x 3 box around it, clipped
+    at the frame, holds at least ``support`` candidates (itself included), masks uint8 [L,H,W] is 255 where the (2 radius + 1)-pixel
+    box around the pixel holds one that stayed and 0 elsewhere, and counts int32 [L] is the number of set pixels of the frame -- 0
+    for a frame that is not listed.  ``out``: a device uint8 [L,H,W] to write the listed frames' masks into (its other frames stay
+    as they are); without it a buffer of zeros.  support in [1, 9], radius in [0, DEFECT_RADIUS_MAX]: integers, no bools.  The
+    checks of defect_candidates; no host read; exact integers, the same in every run."""
+    lib = _L.load()
+    support = _defect_int("support", support, 1, 9)
+    radius = _defect_int("radius", radius, 0, DEFECT_RADIUS_MAX)
+    named = [("cand", cand, torch.uint8), ("ids", ids, torch.int32)]
+    if out is not None:
+        named.append(("out", out, torch.uint8))
+    up = _defect_inputs(named, "candidates")
+    cd, idt = up[:2]
+    if cd.dim() != 3:
+        raise ValueError("cand must be [L,H,W], got %s" % (tuple(cd.shape),))
+    L, H, W = cd.shape
+    if idt.dim() != 1:
+        raise ValueError("ids must be int32 [n], got %s" % (tuple(idt.shape),))
+    if out is not None and tuple(up[2].shape) != (L, H, W):
+        raise ValueError("out must be [%d,%d,%d], got %s" % (L, H, W, tuple(up[2].shape)))
+    with torch.cuda.device(cd.device):
+        masks = up[2] if out is not None else torch.zeros((L, H, W), dtype=torch.uint8, device=cd.device)
+        counts = torch.zeros(L, dtype=torch.int32, device=cd.device)
+        _L.check(lib.e2fgvi_defect_clean(_ptr(cd), _ptr(idt), idt.shape[0], L, H, W, support, radius, _ptr(masks), _ptr(counts),
+                                         _stream()), "defect_clean")
+    return masks, counts
+
+
 YUV_LAYOUTS = {"nv12": 0, "i420": 1}     # E2FGVI_YUV_* / E2FGVI_CHROMA_* of include/e2fgvi_hip.h
 YUV_CHROMA = {"left": 0, "nearest": 1}
 

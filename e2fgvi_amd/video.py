@@ -687,6 +687,30 @@ def _propagate_masks_device(model, x, key_masks, keys, steps, flows, size, check
         return planes[0] | planes[1]
 
 
+def _check_size(size):
+    """size= of the functions that resize the frames first: None or a positive (width, height); ValueError otherwise"""
+    if size is not None:
+        try:
+            ok = len(size) == 2 and all(_integer(v, 1, typed=True) for v in size)
+        except TypeError:
+            ok = False
+        if not ok:
+            raise ValueError("size must be None or a positive (width, height), got %r" % (size,))
+
+
+def _check_flows(flows, shape, size):
+    """flows= as (fwd, bwd), both [L-1,h,w,2] for frames of ``shape`` after size=, from the shapes alone; ValueError otherwise"""
+    L = int(shape[0])
+    w, h = (int(v) for v in size) if size is not None else (int(shape[2]), int(shape[1]))
+    try:
+        shapes = [tuple(f.shape) for f in flows]
+    except (TypeError, AttributeError):
+        shapes = None
+    if shapes is None or len(shapes) != 2 or (L >= 2 and any(s != (L - 1, h, w, 2) for s in shapes)):
+        raise ValueError("flows must be (fwd, bwd), both fp32 [%d,%d,%d,2] (the frames' size after size=), got %r"
+                         % (L - 1, h, w, shapes if shapes is not None else flows))
+
+
 def _check_propagate_args(model, shape, key_masks, keys, flows, size, scenes, reach, check, name="keys"):
     """the checks of propagate_masks from the arguments and the shapes alone (shape: that of the RGB frames) -> (keys, steps)"""
     if len(shape) != 4 or shape[3] != 3:
@@ -700,13 +724,7 @@ def _check_propagate_args(model, shape, key_masks, keys, flows, size, scenes, re
                          % (len(keys), name, tuple(getattr(key_masks, "shape", ())) or type(key_masks).__name__))
     if not isinstance(check, (bool, np.bool_)):
         raise ValueError("check must be a bool, got %r" % (check,))
-    if size is not None:
-        try:
-            ok = len(size) == 2 and all(_integer(v, 1, typed=True) for v in size)
-        except TypeError:
-            ok = False
-        if not ok:
-            raise ValueError("size must be None or a positive (width, height), got %r" % (size,))
+    _check_size(size)
     if isinstance(scenes, str):
         raise ValueError("scenes must be None or a list of frame numbers, got %r" % (scenes,))
     steps = plan_mask_chains(L, keys, scenes, reach)
@@ -715,14 +733,7 @@ def _check_propagate_args(model, shape, key_masks, keys, flows, size, scenes, re
             raise TypeError("without flows= the masks follow the flows of the model's SPyNet (metrics.video_flows): that needs the "
                             "InpaintGenerator, got %s" % type(model).__name__)
     else:
-        w, h = (int(v) for v in size) if size is not None else (int(shape[2]), int(shape[1]))
-        try:
-            shapes = [tuple(f.shape) for f in flows]
-        except (TypeError, AttributeError):
-            shapes = None
-        if shapes is None or len(shapes) != 2 or (L >= 2 and any(s != (L - 1, h, w, 2) for s in shapes)):
-            raise ValueError("flows must be (fwd, bwd), both fp32 [%d,%d,%d,2] (the frames' size after size=), got %r"
-                             % (L - 1, h, w, shapes if shapes is not None else flows))
+        _check_flows(flows, shape, size)
     return keys, steps
 
 
@@ -750,6 +761,129 @@ def propagate_masks(model, frames_u8, key_masks, keys, flows=None, size=None, sc
     if device is None:
         device = next(model.parameters()).device if hasattr(model, "parameters") else None
     return _propagate_masks_device(model, _upload(frames_u8, device), key_masks, keys, steps, flows, size, bool(check)).cpu().numpy()
+
+
+DEFECT_THRESHOLD = 16          # detect_defects's defaults: DESIGN.md 3p has the measurements they were chosen from
+DEFECT_SLACK = 0
+DEFECT_SUPPORT = 3
+DEFECT_RADIUS = 1
+DEFECT_MAX_FRACTION = 0.02
+
+
+def plan_defect_frames(length, scenes=None):
+    """The centre frames detect_defects can judge in a video of ``length`` frames: those whose two neighbours lie in the same scene,
+    in increasing order -- never frame 0 or the last one, and neither the last frame of a scene nor the first of the next
+    (``scenes``: cuts as plan_windows takes them, ValueError otherwise).  A test against one neighbour alone cannot tell dirt from
+    motion, so the other frames get an empty mask.  Fewer than three frames: [].  Host logic only."""
+    if not _integer(length, 0, typed=True):
+        raise ValueError("length must be an integer >= 0, got %r" % (length,))
+    length = int(length)
+    cuts = set(_check_scenes(scenes, length)) if scenes is not None else set()
+    return [t for t in range(1, length - 1) if t not in cuts and t + 1 not in cuts]
+
+
+def _check_defect_args(threshold, slack, support, radius, max_fraction):
+    for name, v, lo, hi in (("threshold", threshold, 0, ops.DEFECT_THRESHOLD_MAX), ("slack", slack, 0, ops.DEFECT_SLACK_MAX),
+                            ("support", support, 1, 9), ("radius", radius, 0, ops.DEFECT_RADIUS_MAX)):
+        if not _integer(v, lo, hi):
+            raise ValueError("%s must be an integer in [%d, %d], got %r" % (name, lo, hi, v))
+    try:
+        ok = not isinstance(max_fraction, (bool, np.bool_)) and 0 < max_fraction <= 1
+    except TypeError:
+        ok = False
+    if not ok:
+        raise ValueError("max_fraction must be in (0, 1], got %r" % (max_fraction,))
+    return int(threshold), int(slack), int(support), int(radius), float(max_fraction)
+
+
+def _detect_defects_device(model, x, ids, flows, size, threshold, slack, support, radius, max_fraction):
+    """detect_defects after the argument checks and the upload of the frames: x uint8 [L,H,W,3] on the device, ids the centre
+    frames of plan_defect_frames -> (masks, counts): device uint8 [L,h,w] of 0 / 255 with the frames over the guard cleared, and
+    device int32 [L], the counts as they were before the guard.  No host read."""
+    from . import metrics
+    ids_d = torch.tensor(ids, dtype=torch.int32).to(x.device) if ids else None      # in front of the first launch
+    if size is not None:
+        x = resize_frames(x, size)
+    L, h, w = (int(v) for v in x.shape[:3])
+    if ids_d is None or h * w == 0:
+        return torch.zeros((L, h, w), dtype=torch.uint8, device=x.device), torch.zeros(L, dtype=torch.int32, device=x.device)
+    with torch.cuda.device(x.device):
+        if flows is None:
+            fwd, bwd = metrics.video_flows(model, x)
+        else:
+            fwd, bwd = (metrics._device_tensor(f, x.device) for f in flows)
+        cand = ops.defect_candidates(x, fwd, bwd, ids_d, threshold, slack)
+        masks, counts = ops.defect_clean(cand, ids_d, support, radius)
+        # the frame guard, on the device: a frame that differs from both neighbours nearly everywhere is no dirt
+        keep = (counts <= int(math.floor(max_fraction * h * w))).to(torch.uint8)
+        return masks * keep[:, None, None], counts
+
+
+def _check_detect_args(model, shape, flows, size, scenes, return_counts):
+    """the checks of detect_defects from the arguments and the shapes alone (shape: that of the RGB frames) -> the centre frames"""
+    if len(shape) != 4 or shape[3] != 3:
+        raise ValueError("frames must be uint8 [L,H,W,3], got %s" % (tuple(shape),))
+    L = int(shape[0])
+    if not isinstance(return_counts, (bool, np.bool_)):
+        raise ValueError("return_counts must be a bool, got %r" % (return_counts,))
+    _check_size(size)
+    if isinstance(scenes, str):
+        raise ValueError("scenes must be None or a list of frame numbers, got %r" % (scenes,))
+    ids = plan_defect_frames(L, scenes)
+    if flows is None:
+        if not callable(getattr(model, "engine", None)):
+            raise TypeError("without flows= the neighbours are reached along the flows of the model's SPyNet (metrics.video_flows): "
+                            "that needs the InpaintGenerator, got %s" % type(model).__name__)
+    else:
+        _check_flows(flows, shape, size)
+    return ids
+
+
+@torch.no_grad()
+def detect_defects(model, frames_u8, flows=None, size=None, scenes=None, threshold=DEFECT_THRESHOLD, slack=DEFECT_SLACK,
+                   support=DEFECT_SUPPORT, radius=DEFECT_RADIUS, max_fraction=DEFECT_MAX_FRACTION, return_counts=False, device=None):
+    """Masks of what lives on one frame only -- dust, dirt, blotches, sparkle, drop-outs of film and tape -- from the frames alone:
+    frames_u8 uint8 [L,H,W,3] -> uint8 numpy [L,h,w] of 0 / 255 (what inpaint_video takes; masks_u8="defects" does this with the
+    defaults), everything after the upload on the device.  ``size`` = (width, height) resizes the frames first (resize_frames) and
+    the result has that size.  The flows between adjacent frames are the net's own (metrics.video_flows(model, frames): ``model``
+    must be the generator, TypeError otherwise) or ``flows`` = (fwd, bwd), fp32 [L-1,h,w,2] in metrics.warp_error's convention --
+    ``model`` may then be None.
+
+    A motion-compensated temporal spike test in envelope form (ops.defect_candidates has the definition): a pixel of frame t is a
+    candidate when its integer luma -- the scene detector's -- lies more than ``threshold`` levels above the largest, or below the
+    smallest, luma among the pixels its flow points between in frame t-1 AND in frame t+1 (the 2 x 2 pixels a bilinear sample
+    would read, ``slack`` more on every side).  The textbook test against the bilinear sample itself flags every local extremum
+    of fine texture, because the interpolation smooths both neighbours (8172 against 494 pixels on a clean video).
+    Brighter than both or darker than both: an occlusion or uncovered background differs from one side only.  A candidate stays
+    when the 3 x 3 box around it holds at least ``support`` candidates, and what stays is dilated by a (2 radius + 1)-pixel box
+    (ops.defect_clean).  Exact integers after one floor: the same bytes in every run.
+
+    Frames without both neighbours in their scene -- the first and the last, and the two around every cut of ``scenes`` (a list of
+    cuts as plan_windows takes them; detect_cuts finds them) -- get an empty mask (plan_defect_frames): a one-sided test cannot
+    tell dirt from motion.  The frame guard, on the device: a frame whose count of set pixels exceeds floor(max_fraction h w) is a
+    flash, a dropped frame, an unnamed cut or failed motion compensation, not dirt, and its mask is cleared.  With
+    ``return_counts`` the result is (masks, counts), counts the int32 [L] numbers of set pixels BEFORE the guard, so a cleared
+    frame still shows.  L < 3 or no eligible frame: empty masks without a launch and without computing flows.
+
+    Known limits: defects that last longer than one frame (vertical line scratches, flicker) are no temporal spikes and are not
+    found; an object that appears for a single frame is dirt to this test; a blotch bends the very flow that is supposed to see
+    past it, and what a trained SPyNet does around one has not been measured here.
+    threshold in [0, 254], slack in [0, 2], support in [1, 9], radius in [0, 16]: integers; 0 < max_fraction <= 1; return_counts a
+    bool; no bools elsewhere; a string for ``scenes`` is refused.  Argument errors are ValueErrors that name the argument, raised
+    before any device work."""
+    shape = tuple(frames_u8.shape)
+    threshold, slack, support, radius, max_fraction = _check_defect_args(threshold, slack, support, radius, max_fraction)
+    ids = _check_detect_args(model, shape, flows, size, scenes, return_counts)
+    if not ids:
+        w, h = (int(v) for v in size) if size is not None else (shape[2], shape[1])
+        masks, counts = np.zeros((shape[0], h, w), np.uint8), np.zeros(shape[0], np.int32)
+    else:
+        if device is None:
+            device = next(model.parameters()).device if hasattr(model, "parameters") else None
+        masks, counts = _detect_defects_device(model, _upload(frames_u8, device), ids, flows, size, threshold, slack, support, radius,
+                                               max_fraction)
+        masks, counts = masks.cpu().numpy(), counts.cpu().numpy()
+    return (masks, counts) if return_counts else masks
 
 
 YuvFormat = collections.namedtuple("YuvFormat", "layout matrix full_range chroma")
@@ -1036,9 +1170,11 @@ def prepare_masks(masks_u8, size_hw, device, dilate=True, box=None, ids=None):
 # What a call of inpaint_video asks for, checked and normalised (_check_call) -- the drivers below take it whole.  ``fmt``: the
 # YuvFormat of pixel_format= or None; ``overlay``: masks_u8 == "overlay"; ``scenes``: None, "auto" or the checked list (the
 # drivers get the resolved cuts beside the record); ``region``: None (the whole frame), "box" (``box``: the checked explicit box),
-# "hole", "holes" or "track" (``box`` None: planned from the masks); everything else: the argument of that name.
+# "hole", "holes" or "track" (``box`` None: planned from the masks); ``defects``: masks_u8 == "defects" (the last field, False
+# when left out); everything else: the argument of that name.
 _Call = collections.namedtuple("_Call", "fmt overlay scenes mask_keys feather region box max_regions size restore keep_float reuse "
-                                        "batch_windows in_flight neighbor_stride ref_length num_ref dilate pad context")
+                                        "batch_windows in_flight neighbor_stride ref_length num_ref dilate pad context defects",
+                               defaults=(False,))
 
 
 def _check_call(shape, masks_u8, model, *, neighbor_stride, ref_length, num_ref, dilate, pad, batch_windows, keep_float, in_flight,
@@ -1052,9 +1188,16 @@ def _check_call(shape, masks_u8, model, *, neighbor_stride, ref_length, num_ref,
         shape = (shape[0],) + ops.yuv_frame_hw(shape) + (3,)
         if size is not None and not restore and (int(size[0]) % 2 or int(size[1]) % 2):
             raise ValueError("pixel_format= returns 4:2:0 frames of (width, height) = size, which must both be even, got %r" % (size,))
-    overlay = isinstance(masks_u8, str)
+    defects = isinstance(masks_u8, str) and masks_u8 == "defects"
+    overlay = isinstance(masks_u8, str) and not defects
     if overlay and masks_u8 != "overlay":
-        raise ValueError('masks_u8 must be uint8 [L,Hm,Wm] masks or "overlay", got %r' % (masks_u8,))
+        raise ValueError('masks_u8 must be uint8 [L,Hm,Wm] masks, "overlay" or "defects", got %r' % (masks_u8,))
+    if defects:
+        if mask_keys is not None:
+            raise ValueError('mask_keys= names the frames whose masks are given: with masks_u8="defects" there are none')
+        if not callable(getattr(model, "engine", None)):
+            raise TypeError('masks_u8="defects" reaches the neighbouring frames along the flows of the model\'s SPyNet '
+                            "(metrics.video_flows): that needs the InpaintGenerator, got %s" % type(model).__name__)
     if scenes is not None and not (isinstance(scenes, str) and scenes == "auto"):
         if isinstance(scenes, str):
             raise ValueError('scenes must be None, "auto" or a list of frame numbers, got %r' % (scenes,))
@@ -1112,7 +1255,7 @@ def _check_call(shape, masks_u8, model, *, neighbor_stride, ref_length, num_ref,
             raise TypeError("reuse=True needs the InpaintGenerator (its engine runs the encoder, SPyNet and the rest of the "
                             "forward as separate pieces), got %s" % type(model).__name__)
     return _Call(fmt, overlay, scenes, mask_keys, feather, region, box, max_regions, size, restore, keep_float, reuse, batch_windows,
-                 in_flight, neighbor_stride, ref_length, num_ref, dilate, pad, context)
+                 in_flight, neighbor_stride, ref_length, num_ref, dilate, pad, context, defects)
 
 
 @torch.no_grad()
@@ -1127,7 +1270,16 @@ def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, 
     fixed caption), found on the device in the caller's frames as they come in, before any ``size`` resize, as scenes="auto" finds
     its cuts: the result is the bytes of the call with np.broadcast_to(overlay_mask(frames_u8), (L, H, W)) for masks and every
     other option as given (overlay_mask has the definition, the defaults and the limits; it raises ValueError when the scenery
-    itself is static).  No overlay found: the path of masks without a hole pixel.  Any other string raises ValueError.
+    itself is static).  No overlay found: the path of masks without a hole pixel.
+
+    ``masks_u8`` = "defects" in place of masks: the holes are what lives on one frame only -- dust, dirt, blotches, sparkle and
+    drop-outs of film and tape -- found on the device by detect_defects' device form with its defaults, in the frames at their own
+    size (a speck is a few source pixels and would vanish at the model's size), after the upload, the decode of a pixel_format and
+    the resolution of scenes="auto", along the flows of the model's own SPyNet and with the resolved cuts.  From there the call is,
+    byte for byte, the call with detect_defects(model, frames_u8, scenes=cuts) for masks and every other option as given
+    (detect_defects has the definition, the defaults and the limits; callers who tune the detector call it and pass the masks).
+    ``model`` must be the generator (TypeError otherwise); mask_keys with "defects" raises ValueError.  Any other string raises
+    ValueError.
 
     ``size`` = (width, height) resizes the uploaded frames on the device first, as test.py:97-104,127 does with PIL
     (resize_frames: bicubic, bit-exact); the masks are then NEAREST-resized straight to that size and the returned frames
@@ -1258,9 +1410,12 @@ def inpaint_video(model, frames_u8, masks_u8, neighbor_stride=5, ref_length=10, 
             raise ValueError('masks_u8="overlay" needs frames to find the overlay in, got %s' % (tuple(source.shape),))
         masks_d = _overlay_mask_device(source, OVERLAY_G_MIN, OVERLAY_COHERENCE, OVERLAY_RADIUS, OVERLAY_MIN_AREA,
                                        OVERLAY_MAX_FRACTION).unsqueeze(0).expand(source.shape[:3]).contiguous()
-    else:
+    elif not call.defects:
         masks_d = _upload(masks_u8, device)             # once: the bounding box and the mask preparation read the same tensor
     cuts = detect_cuts(source) if call.scenes == "auto" else call.scenes       # "auto": on the frames at source size
+    if call.defects:                                    # on the frames at source size, with the resolved cuts
+        masks_d = _detect_defects_device(model, source, plan_defect_frames(int(source.shape[0]), cuts), None, None, DEFECT_THRESHOLD,
+                                         DEFECT_SLACK, DEFECT_SUPPORT, DEFECT_RADIUS, DEFECT_MAX_FRACTION)[0]
     if call.mask_keys is not None:                      # the masks of all frames from the K that were given, with the resolved cuts
         masks_d = _propagate_masks_device(model, source, masks_d, call.mask_keys,
                                           plan_mask_chains(int(source.shape[0]), call.mask_keys, cuts), None, call.size, True)

@@ -295,6 +295,32 @@ int e2fgvi_warp_error(const void* frames, int32_t frame_dtype, const float* fwd,
  * H * W == 0 returns 0 without a launch and without looking at the pointers; a null pointer with work is E2FGVI_EINVAL. */
 int e2fgvi_mask_track_step(uint8_t* planes, const float* fwd, const float* bwd, const int32_t* jobs, int32_t n, int32_t L, int32_t H,
                            int32_t W, int32_t check, void* stream);
+/* Dust and dirt (video.detect_defects, inpaint_video(masks_u8="defects")): a motion-compensated temporal spike test over those
+ * flows, in envelope form -- exact integers after one floor.
+ *   frames uint8 [L,H,W,3];  fwd, bwd [L-1,H,W,2] fp32 as above, 8-byte aligned;  ids int32 [n] on the device: the centre frames
+ *   to do, distinct;  Y = (77 R + 150 G + 29 B + 128) >> 8, the scene detector's luma, formed where the RGB bytes are gathered.
+ * Centre frame t with 1 <= t <= L-2 (an id outside writes nothing), pixel p = (x, y), neighbour A = frame t-1 with g = bwd[t-1],
+ * neighbour B = frame t+1 with g = fwd[t], both on frame t's grid.  Per neighbour N:
+ *   q = (x + g_x(p), y + g_y(p)) in fp64;  inside_N = g(p) finite, 0 <= q_x <= W-1 and 0 <= q_y <= H-1 (in floating point, before
+ *       any conversion to an integer: 1e30 or a NaN is simply outside);  (x0, y0) = floor(q);
+ *   lo_N, hi_N = min, max of Y_N over the pixels (x0 + i, y0 + j) with -slack <= i, j <= 1 + slack that lie in the frame.
+ *   cand[t](p) = 1 iff inside_A and inside_B and ((Y_t(p) > hi_A + tau and Y_t(p) > hi_B + tau) or
+ *                                                 (Y_t(p) < lo_A - tau and Y_t(p) < lo_B - tau)), else 0: strict comparisons,
+ *       brighter than both envelopes or darker than both -- one neighbour is never enough.
+ * The candidate entry writes cand uint8 [L,H,W] for the listed frames only, one launch over all n frames (in slabs of 65535).
+ * The cleaning entry reads cand (any non-zero byte is a candidate) of the listed frames and writes for them
+ *   n3(p) = the number of candidates in the 3 x 3 box around p, clipped at the frame, p included;  K = cand and n3 >= support;
+ *   D(p) = 1 iff some K lies in the (2 radius + 1)-pixel box around p, clipped at the frame;  out[t] = 255 D;
+ * and counts int32 [L]: sum D for a listed frame and 0 for every other (the entry clears all L first; integer atomics, exact).
+ * Support test and dilation are one launch over a (2 radius + 3)-pixel stencil staged in LDS.  The same inputs give the same
+ * bits in every run; nothing is read on the host.  n, L, H, W >= 0, L >= 3 when n > 0, H * W < 2^31 - 256, tau in [0, 254],
+ * slack in [0, 2], support in [1, 9], radius in [0, 16] (E2FGVI_EINVAL otherwise, from the arguments alone); n == 0 or
+ * H * W == 0 returns 0 without a launch and without looking at the pointers; a null or misaligned pointer with work is
+ * E2FGVI_EINVAL (fwd, bwd 8-byte, ids and counts 4-byte aligned). */
+int e2fgvi_defect_candidates(const uint8_t* frames, const float* fwd, const float* bwd, const int32_t* ids, int32_t n, int32_t L,
+                             int32_t H, int32_t W, int32_t tau, int32_t slack, uint8_t* cand, void* stream);
+int e2fgvi_defect_clean(const uint8_t* cand, const int32_t* ids, int32_t n, int32_t L, int32_t H, int32_t W, int32_t support,
+                        int32_t radius, uint8_t* out, int32_t* counts, void* stream);
 
 /* conv_offset post-processing of SecondOrderDeformableAlignment (feat_prop.py:38-53) fused into the conv that produces
  * it: `residual` must point to the per-pixel flows [P,4] = (u1,v1,u2,v2) with res_ld = 4, `slope` = max_residue:
