@@ -5,6 +5,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import helper_cases as K
 from tests.util import assert_close, fp32_tol, gen as _gen, nchw, nhwc
 
 pytestmark = pytest.mark.gpu
@@ -423,6 +424,9 @@ def test_spynet_level_input(dev):
                                  torch.tensor(supp_idx, dtype=torch.int32, device=dev), nhwc(flow_prev).to(dev))
     # grid_sample on the CPU side normalises / un-normalises the coordinates (~1e-6 px of jitter on |flow| ~ 6 px): measured 1.1e-5
     assert_close(out.cpu(), nhwc(ref), 4e-5, "spynet level input")
+    # ... and the float64 restatement in pixel coordinates, at the bound derived from this case's tensors (tests/helper_cases.py)
+    case = dict(kind="spynet", exact=False, pyr=nhwc(pyr), ref_idx=ref_idx, supp_idx=supp_idx, flow_prev=nhwc(flow_prev))
+    K.check(out, K.reference(case)[0], K.allowed(case)[0], "spynet level input, restatement")
     out0 = ops.spynet_level_input(p4, torch.tensor(ref_idx, dtype=torch.int32, device=dev),
                                   torch.tensor(supp_idx, dtype=torch.int32, device=dev), None)
     ref0 = torch.cat([pyr[ref_idx], pyr[supp_idx], torch.zeros(6, 2, h, w)], 1)
@@ -447,10 +451,18 @@ def test_prop_cond(dev):
     # grid_sample on the CPU side goes through normalise/unnormalise of the coordinates: ~1e-6 px of jitter
     assert_close(cond.cpu(), nhwc(torch.cat([c1, c2], 1)), 3e-4, "cond")
     assert_close(fl.cpu(), nhwc(torch.cat([f_n1, f_n2], 1)), 3e-4, "flows")
+    # ... and the float64 restatement in pixel coordinates, at the bound derived from this case's tensors (tests/helper_cases.py)
+    case = dict(kind="prop_cond", exact=False, fp=nhwc(fp), f2=nhwc(f2), flows=fl_nhwc.cpu(), ia=i - 1, ib=i - 2)
+    rc, ra = K.reference(case), K.allowed(case)
+    K.check(cond, rc[0], ra[0], "cond, restatement")
+    K.check(fl, rc[1], ra[1], "flows, restatement")
     cond1, fl1 = ops.prop_cond(nhwc(fp).to(dev), None, fl_nhwc[0, 0], None, (lt - 1) * h * w * 2)
     c1b = O.flow_warp(fp, flows[:, 0].permute(0, 2, 3, 1))
     assert_close(cond1.cpu(), nhwc(torch.cat([c1b, torch.zeros_like(c1b)], 1)), 3e-4, "cond i=1")
     assert_close(fl1.cpu(), nhwc(torch.cat([flows[:, 0], torch.zeros_like(flows[:, 0])], 1)), 1e-6, "flows i=1")
+    case = dict(case, ia=0, ib=None)
+    K.check(cond1, K.reference(case)[0], K.allowed(case)[0], "cond i=1, restatement")
+    assert torch.equal(fl1.cpu(), K.reference(case)[1].float()), "flows i=1: flow_n1 is a copy, flow_n2 zero"
 
 
 def test_layernorm_and_pool(dev):
