@@ -33,8 +33,10 @@ UNITS = [("error.hip", "error.o", []), ("conv.hip", "conv.o", []), ("conv.hip", 
          ("video.hip", "video.o", NOPK), ("yuv.hip", "yuv.o", NOPK), ("metrics.hip", "metrics.o", NOPK),
          # fp64 in the order written: the numpy restatement matches the step bit for bit only without fused multiply-adds
          ("mask_track.hip", "mask_track.o", NOPK + ["-ffp-contract=off"]),
-         ("defects.hip", "defects.o", NOPK)]
-NOPK_OBJECTS = ("conv_nopk.o", "conv_bf16x.o", "conv_wino.o", "conv_wino4.o", "conv_wino_x3.o", "conv_tail.o", "mdcn.o", "attention_bf16.o", "attention_x3.o", "misc.o", "video.o", "yuv.o", "metrics.o", "mask_track.o", "defects.o")
+         ("defects.hip", "defects.o", NOPK),
+         # the same: the restatement of tests/pixel_track_cases.py matches the origins bit for bit
+         ("pixel_track.hip", "pixel_track.o", NOPK + ["-ffp-contract=off"])]
+NOPK_OBJECTS = ("conv_nopk.o", "conv_bf16x.o", "conv_wino.o", "conv_wino4.o", "conv_wino_x3.o", "conv_tail.o", "mdcn.o", "attention_bf16.o", "attention_x3.o", "misc.o", "video.o", "yuv.o", "metrics.o", "mask_track.o", "defects.o", "pixel_track.o")
 OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 
 
@@ -90,9 +92,11 @@ def build(force=False, verbose=False, nopk_all=False, lib=None, tag=None, define
             verify_no_scratch(objdir, "video.o", "restore_u8_kernel", "paste-back")
             verify_no_scratch(objdir, "video.o", "overlay_stats_kernel", "overlay sums")
             verify_no_scratch(objdir, "defects.o", "defect_", "dust and dirt")
+            verify_no_scratch(objdir, "pixel_track.o", "pixel_", "pixel propagation")
             verify_overlay_prefetch(objdir)
             verify_no_pk_u8(objdir)
             verify_no_fma64(objdir)
+            verify_no_fma64(objdir, "pixel_track.o")
     return out
 
 
@@ -135,7 +139,7 @@ def verify_isa(objdir=None):
 
 def verify_no_fma64(objdir=None, obj="mask_track.o"):
     """mask_track_step_kernel (csrc/mask_track.hip) does its fp64 arithmetic in the order written, one rounding per operation: the
-    numpy restatement of the tests matches it bit for bit.  The unit is built with -ffp-contract=off; a fused multiply-add in its
+    numpy restatement of the tests matches it bit for bit (and so do the two kernels of csrc/pixel_track.hip, obj="pixel_track.o").  The unit is built with -ffp-contract=off; a fused multiply-add in its
     code would mean the flag was lost (or an expression was rewritten into fma()).  Returns the number of fp64 multiplies read."""
     import re
     objdir = objdir or os.path.join(CSRC, "build")
@@ -172,7 +176,8 @@ def verify_no_scratch(objdir=None, obj="conv_bf16x.o", marker="ELb0ELi2ELb1EEE",
     scratch without a warning (csrc/conv_bf16x.hip, PP).  Fails the build when one of them has a private segment or a spill.
     Also run over the four instantiations of restore_u8_kernel (video.o): the feathered ones hold five LDS phases in one kernel;
     and over the four of overlay_stats_kernel, which keeps 24 sums and the next frame's 9 words in registers across its frame loop;
-    and over the four kernels of defects.o (the candidate kernel unrolls up to 2 x 36 gathers for each of a thread's four pixels)."""
+    and over the four kernels of defects.o (the candidate kernel unrolls up to 2 x 36 gathers for each of a thread's four pixels);
+    and over the two of pixel_track.o (the fill keeps the weights, offsets and flags of four corners in small arrays)."""
     import re
     import shutil
     import tempfile

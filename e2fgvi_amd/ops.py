@@ -1948,7 +1948,78 @@ def defect_clean(cand, ids, support, radius, out=None):
     return masks, counts
 
 
-YUV_LAYOUTS = {"nv12": 0, "i420": 1}     # E2FGVI_YUV_* / E2FGVI_CHROMA_* of include/e2fgvi_hip.h
+PIXEL_REACH_MAX = 254                      # csrc/pixel_track.hip: the largest age a byte of the planes can hold
+
+
+def pixel_track_step(hole, age, origin, fwd, bwd, jobs, reach=PIXEL_REACH_MAX, check=True):
+    """One step of carrying, for every hole pixel, the place its colour can be seen at along a video's flows
+    (csrc/pixel_track.hip; include/e2fgvi_hip.h has the definition; video.propagate_pixels runs the chains): hole uint8 [L,H,W] of
+    0 / 1, L >= 2; age uint8 [2,L,H,W] (255 = not reached, 0 = known, a = reached after a steps; both planes start as 255 * hole;
+    plane 0 travels forward in time, plane 1 backward) and origin fp32 [2,L,H,W,2], both updated in place at hole pixels only; fwd,
+    bwd fp32 [L-1,H,W,2] in metrics.warp_error's convention; jobs int32 [n,2] of (pair t, dir): dir 0 writes plane 0 frame t+1 from
+    frame t, pulled along bwd[t] and checked against fwd[t]; dir 1 writes plane 1 frame t from frame t+1, pulled along fwd[t] and
+    checked against bwd[t].  One launch runs all n jobs; no job of a call may write a frame of a plane that another reads or writes
+    (video.plan_pixel_chains).  ``reach``: the largest age, an integer in [1, 254]; check=False switches the forward / backward
+    consistency test off.  age and origin must be device tensors (they are written); the others device tensors or anything
+    torch.as_tensor accepts (uploaded first); wrong dtypes, shapes that do not fit, non-contiguous inputs and tensors on different
+    devices raise ValueError.  Returns (age, origin).  The same inputs give the same bits in every run."""
+    lib = _L.load()
+    reach = _defect_int("reach", reach, 1, PIXEL_REACH_MAX)
+    if not isinstance(check, (bool, numbers.Integral)) or check not in (0, 1):
+        raise ValueError("check must be a bool (or 0 / 1), got %r" % (check,))
+    for nm, t in (("age", age), ("origin", origin)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda):
+            raise ValueError("%s is written in place: it must be a device tensor, got %s" % (nm, type(t).__name__))
+    named = (("age", age, torch.uint8), ("hole", hole, torch.uint8), ("origin", origin, torch.float32), ("fwd", fwd, torch.float32),
+             ("bwd", bwd, torch.float32), ("jobs", jobs, torch.int32))
+    ag, ho, og, fw, bw, jb = _defect_inputs(named, "age")
+    if ag.dim() != 4 or ag.shape[0] != 2:
+        raise ValueError("age must be [2,L,H,W], got %s" % (tuple(ag.shape),))
+    _, L, H, W = ag.shape
+    if L < 2:
+        raise ValueError("pixel_track_step needs at least two frames, got age %s" % (tuple(ag.shape),))
+    for t, nm, shape in ((ho, "hole", (L, H, W)), (og, "origin", (2, L, H, W, 2)), (fw, "fwd", (L - 1, H, W, 2)),
+                         (bw, "bwd", (L - 1, H, W, 2))):
+        if tuple(t.shape) != shape:
+            raise ValueError("%s must be %s for age %s, got %s" % (nm, list(shape), tuple(ag.shape), tuple(t.shape)))
+    if jb.dim() != 2 or jb.shape[1] != 2:
+        raise ValueError("jobs must be int32 [n,2] of (pair, dir), got %s" % (tuple(jb.shape),))
+    with torch.cuda.device(ag.device):
+        _L.check(lib.e2fgvi_pixel_track_step(_ptr(ho), _ptr(ag), _ptr(og), _ptr(fw), _ptr(bw), _ptr(jb), jb.shape[0], L, H, W, reach,
+                                             int(check), _stream()), "pixel_track_step")
+    return ag, og
+
+
+def pixel_fill(src, hole, age, origin, out, return_source=False):
+    """The colours of the hole pixels pixel_track_step reached, one launch over all frames (csrc/pixel_track.hip
+    pixel_fill_kernel; include/e2fgvi_hip.h has the definition): src uint8 [L,H,W,3], the frames the colours are read from; hole
+    uint8 [L,H,W] of 0 / 1; age uint8 [2,L,H,W] and origin fp32 [2,L,H,W,2] as the steps left them; out uint8 [L,H,W,3], a device
+    tensor updated in place: a hole pixel gets one bilinear sample of src[f] at its origin, from the plane of the smaller age (a tie:
+    plane 0) whose four corners are known pixels of that frame, and keeps its bytes when neither plane has one; no other byte is
+    written.  Returns out, or with ``return_source`` (out, source): device uint8 [L,H,W] of 0 (no hole pixel), 1 (plane 0), 2
+    (plane 1), 3 (a hole pixel left as it was).  The checks of pixel_track_step; no host read; the same bits in every run."""
+    lib = _L.load()
+    if not (isinstance(out, torch.Tensor) and out.is_cuda):
+        raise ValueError("out is written in place: it must be a device tensor, got %s" % type(out).__name__)
+    named = (("out", out, torch.uint8), ("src", src, torch.uint8), ("hole", hole, torch.uint8), ("age", age, torch.uint8),
+             ("origin", origin, torch.float32))
+    ou, sr, ho, ag, og = _defect_inputs(named, "out")
+    if ou.dim() != 4 or ou.shape[3] != 3:
+        raise ValueError("out must be [L,H,W,3], got %s" % (tuple(ou.shape),))
+    L, H, W, _ = ou.shape
+    for t, nm, shape in ((sr, "src", (L, H, W, 3)), (ho, "hole", (L, H, W)), (ag, "age", (2, L, H, W)), (og, "origin", (2, L, H, W, 2))):
+        if tuple(t.shape) != shape:
+            raise ValueError("%s must be %s for out %s, got %s" % (nm, list(shape), tuple(ou.shape), tuple(t.shape)))
+    if sr.data_ptr() == ou.data_ptr() and sr.numel():
+        raise ValueError("src and out must be different buffers: out is written while src is read")
+    with torch.cuda.device(ou.device):
+        source = torch.empty((L, H, W), dtype=torch.uint8, device=ou.device) if return_source else None
+        _L.check(lib.e2fgvi_pixel_fill(_ptr(sr), _ptr(ho), _ptr(ag), _ptr(og), _ptr(ou), _ptr(source) if return_source else None,
+                                       L, H, W, _stream()), "pixel_fill")
+    return (ou, source) if return_source else ou
+
+
+YUV_LAYOUTS = {"nv12": 0, "i420": 1}     # E2FGVI_YUV_*/ E2FGVI_CHROMA_* of include/e2fgvi_hip.h
 YUV_CHROMA = {"left": 0, "nearest": 1}
 
 

@@ -763,6 +763,168 @@ def propagate_masks(model, frames_u8, key_masks, keys, flows=None, size=None, sc
     return _propagate_masks_device(model, _upload(frames_u8, device), key_masks, keys, steps, flows, size, bool(check)).cpu().numpy()
 
 
+def _paste_tables(frame_hw, size):
+    """(ytab, xtab) of paste_mask: the row and the column of the model-size mask that restore_frames' NEAREST upscale reads for
+    every row and column of the (H, W) frame; ``size`` = (width, height) of the model's frames"""
+    H, W = (int(v) for v in frame_hw)
+    w, h = (int(v) for v in size)
+    return nearest_table(h, H), nearest_table(w, W)
+
+
+def paste_mask(masks_u8, frame_hw, size=None, dilate=True, device=None):
+    """The pixels inpaint_video(size=size, restore=True, feather=0) pastes over the whole (H, W) = ``frame_hw`` frame: masks_u8
+    uint8 [L,Hm,Wm] (any non-zero byte is hole; an array, or a tensor that is used where it is when on the device) -> device uint8
+    [L,H,W] of 0 / 1.  It is prepare_masks(masks_u8, (h, w), dilate=dilate) at the model's ``size`` = (w, h) followed by
+    restore_frames' NEAREST upscale (nearest_table) to the frame; with size=None it is prepare_masks at the frame's own size."""
+    _check_mask_shape(masks_u8)
+    _check_size(size)
+    H, W = (int(v) for v in frame_hw)
+    if device is None:
+        device = masks_u8.device if isinstance(masks_u8, torch.Tensor) and masks_u8.is_cuda else torch.device("cuda")
+    if size is None:
+        return prepare_masks(masks_u8, (H, W), device, dilate)
+    w, h = (int(v) for v in size)
+    lo = prepare_masks(masks_u8, (h, w), device, dilate)
+    ytab, xtab = (torch.from_numpy(t.astype(np.int64)).to(lo.device) for t in _paste_tables((H, W), size))
+    return lo.index_select(1, ytab).index_select(2, xtab).contiguous()
+
+
+def plan_pixel_chains(length, scenes=None):
+    """The launches that carry known pixels into the holes of a video of ``length`` frames (propagate_pixels): a list of steps, each
+    a list of jobs (pair t, dir) for ops.pixel_track_step -- dir 0 writes frame t+1 of the forward plane from frame t, dir 1 writes
+    frame t of the backward plane from frame t+1.  ``scenes``: cuts as plan_windows takes them.  ValueError otherwise.
+    Every scene [a, b) has one forward chain a -> a+1 -> ... -> b-1 and one backward chain b-1 -> ... -> a, and all chains advance
+    in lockstep: step k holds (a + k, 0) while a + k <= b - 2 and (b - 2 - k, 1) while b - 2 - k >= a, so the number of launches is
+    the longest scene minus one, not the length of the video.  Within a step no job writes a frame of a plane that another job of
+    the step reads or writes; no job crosses a cut; every pair inside a scene appears exactly once in each direction."""
+    if not _integer(length, 1, typed=True):
+        raise ValueError("length must be an integer >= 1, got %r" % (length,))
+    length = int(length)
+    cuts = _check_scenes(scenes, length) if scenes is not None else []
+    bounds = list(zip([0] + cuts, cuts + [length]))
+    steps = []
+    for k in range(max(b - a for a, b in bounds) - 1):
+        step = []
+        for a, b in bounds:
+            if a + k <= b - 2:
+                step += [(a + k, 0), (b - 2 - k, 1)]
+        steps.append(step)
+    return steps
+
+
+def _check_pixel_args(model, shape, masks_u8, filled_u8, flows, size, dilate, scenes, reach, check, return_source):
+    """the checks of propagate_pixels from the arguments and the shapes alone (shape: that of the frames) -> (steps, reach)"""
+    if len(shape) != 4 or shape[3] != 3:
+        raise ValueError("frames must be uint8 [L,H,W,3], got %s" % (tuple(shape),))
+    L = int(shape[0])
+    if L < 1:
+        raise ValueError("frames: at least one frame is needed, got %s" % (tuple(shape),))
+    if tuple(getattr(filled_u8, "shape", ())) != tuple(shape):
+        raise ValueError("filled_u8 must be uint8 %s, what inpaint_video(restore=True) returned for the frames, got %s"
+                         % (list(shape), tuple(getattr(filled_u8, "shape", ())) or type(filled_u8).__name__))
+    if len(getattr(masks_u8, "shape", ())) != 3 or masks_u8.shape[0] != L:
+        raise ValueError("masks must be uint8 [%d,Hm,Wm], one for each frame, got %s"
+                         % (L, tuple(getattr(masks_u8, "shape", ())) or type(masks_u8).__name__))
+    for name, v in (("dilate", dilate), ("check", check), ("return_source", return_source)):
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError("%s must be a bool, got %r" % (name, v))
+    _check_size(size)
+    if isinstance(scenes, str):
+        raise ValueError("scenes must be None or a list of frame numbers, got %r" % (scenes,))
+    steps = plan_pixel_chains(L, scenes)
+    if reach is not None and not _integer(reach, 1, ops.PIXEL_REACH_MAX, typed=True):
+        raise ValueError("reach must be None or an integer in [1, %d], got %r" % (ops.PIXEL_REACH_MAX, reach))
+    if flows is None:
+        if not callable(getattr(model, "engine", None)):
+            raise TypeError("without flows= the pixels follow the flows of the model's SPyNet (metrics.video_flows): that needs the "
+                            "InpaintGenerator, got %s" % type(model).__name__)
+    else:
+        _check_flows(flows, shape, None)                # at the frames' own size: size= is the model's, not the flows'
+    return steps, ops.PIXEL_REACH_MAX if reach is None else int(reach)
+
+
+def _propagate_pixels_device(model, x, masks_u8, filled, steps, flows, size, dilate, reach, check, return_source):
+    """propagate_pixels after the argument checks and the uploads: x and filled uint8 [L,H,W,3] on the device -> (out, source or
+    None) on the device; ``filled`` is not written"""
+    from . import metrics
+    L, H, W = (int(v) for v in x.shape[:3])
+    # the job tables of all steps in one upload, in front of the first launch
+    table = torch.tensor([j for s in steps for j in s], dtype=torch.int32).reshape(-1, 2).to(x.device)
+    out = filled.clone()
+    with torch.cuda.device(x.device):
+        if H * W == 0:
+            return out, torch.zeros((L, H, W), dtype=torch.uint8, device=x.device) if return_source else None
+        hole = paste_mask(masks_u8, (H, W), size, dilate, x.device)
+        # nothing to fetch from (every scene a single frame), or -- the one host read -- no hole pixel: no flows and no launch
+        if not steps or not bool(hole.any()):
+            return out, hole * 3 if return_source else None
+        if flows is None:
+            fwd, bwd = metrics.video_flows(model, filled)
+        else:
+            fwd, bwd = (metrics._device_tensor(f, x.device) for f in flows)
+        age = (hole * 255).unsqueeze(0).repeat(2, 1, 1, 1)
+        origin = torch.empty((2, L, H, W, 2), dtype=torch.float32, device=x.device)
+        at = 0
+        for s in steps:
+            ops.pixel_track_step(hole, age, origin, fwd, bwd, table[at:at + len(s)], reach, check)
+            at += len(s)
+        if return_source:
+            return ops.pixel_fill(x, hole, age, origin, out, True)
+        return ops.pixel_fill(x, hole, age, origin, out), None
+
+
+@torch.no_grad()
+def propagate_pixels(model, frames_u8, masks_u8, filled_u8, flows=None, size=None, dilate=True, scenes=None, reach=None, check=True,
+                     return_source=False, device=None):
+    """Real pixels for the holes of a restored video: what inpaint_video(..., size=size, restore=True) pasted into the hole is a
+    low-resolution prediction upscaled to the frame; most of those pixels can be SEEN in another frame of the caller's video --
+    behind a logo while the camera pans, behind an object that moves on -- and this function fetches them from there at full
+    resolution, along the optical flow, and leaves the prediction only where nothing real can be reached.
+        out = inpaint_video(net, frames, masks, size=(432, 240), restore=True)
+        out = propagate_pixels(net, frames, masks, out, size=(432, 240))
+    frames_u8 uint8 [L,H,W,3], the caller's frames; masks_u8 [L,Hm,Wm] and ``size`` / ``dilate`` as inpaint_video got them;
+    filled_u8 uint8 [L,H,W,3], what inpaint_video returned -> uint8 [L,H,W,3]: a numpy array, or a device tensor when filled_u8 is
+    one; with ``return_source`` (out, source), source uint8 [L,H,W] of 0 (no hole pixel), 1 (fetched forward in time, from an
+    earlier frame), 2 (from a later frame), 3 (a hole pixel left as it was).  Everything after the upload runs on the device.
+
+    hole = paste_mask(masks_u8, (H, W), size, dilate): exactly the pixels the restore pasted.  The flows between adjacent frames
+    are those of the COMPLETED frames -- the caller's frames have the unwanted object in them --: metrics.video_flows(model,
+    filled_u8) (``model`` must be the generator, TypeError otherwise) or ``flows`` = (fwd, bwd), fp32 [L-1,H,W,2] at the frames'
+    size in metrics.warp_error's convention -- ``model`` may then be None.  What travels along them is not a colour but a
+    coordinate (ops.pixel_track_step has the definition): every hole pixel p of frame d looks where its flow points in the
+    neighbouring frame, q = p + g(p), takes the nearest pixel there, and when that one is known -- no hole pixel, or a hole pixel
+    that was reached itself -- and, with ``check``, the flow back from q agrees (the forward / backward test of warp_error), p
+    inherits its origin shifted by the sub-pixel rest of q, and its age plus one.  Both directions in time are carried, one frame per
+    step, the chains of all scenes in lockstep (plan_pixel_chains; ``scenes``: cuts as plan_windows takes them, None or a list);
+    ``reach``: the largest number of frames a pixel is fetched over, None = 254, the most a byte holds.  The job tables are uploaded
+    before the first launch.  At the end ops.pixel_fill reads every reached pixel's colour ONCE, a bilinear sample of the caller's
+    frame at the origin, from the direction with the smaller age whose four corners are known pixels of that frame: the sharpness
+    of a fetched pixel does not depend on how far it travelled.
+
+    The guarantees: a byte outside the hole is filled_u8's byte; a hole byte is either filled_u8's byte (source 3) or one
+    bilinear sample of four known pixels -- outside the hole -- of one of the caller's frames; nothing is carried over a cut.
+    With feather > 0 the ramp outside the hole still contains the prediction, which this function does not touch: feather and
+    propagation are better not combined.  The hole is that of a paste over the whole frame: region= calls are not covered.
+    A video without a hole pixel (found with one host read), or a single frame, runs no launch and returns filled_u8's bytes.
+    The planes cost 18 bytes per pixel and frame of device memory.
+    dilate, check and return_source are bools, reach None or an integer in [1, 254], a string for ``scenes`` is refused: argument
+    errors are ValueErrors that name the argument, raised before any device work.  There is no CPU path."""
+    shape = tuple(frames_u8.shape)
+    steps, reach = _check_pixel_args(model, shape, masks_u8, filled_u8, flows, size, dilate, scenes, reach, check, return_source)
+    as_tensor = isinstance(filled_u8, torch.Tensor) and filled_u8.is_cuda
+    if device is None:
+        device = filled_u8.device if as_tensor else next(model.parameters()).device if hasattr(model, "parameters") \
+            else torch.device("cuda")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("propagate_pixels runs on the MI355X (cuda) device only; there is no CPU path")
+    out, source = _propagate_pixels_device(model, _upload(frames_u8, device), masks_u8, _upload(filled_u8, device), steps, flows, size,
+                                           bool(dilate), reach, bool(check), bool(return_source))
+    if not as_tensor:
+        out, source = out.cpu().numpy(), source.cpu().numpy() if source is not None else None
+    return (out, source) if return_source else out
+
+
 DEFECT_THRESHOLD = 16          # detect_defects's defaults: DESIGN.md 3p has the measurements they were chosen from
 DEFECT_SLACK = 0
 DEFECT_SUPPORT = 3

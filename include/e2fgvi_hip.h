@@ -321,6 +321,46 @@ int e2fgvi_defect_candidates(const uint8_t* frames, const float* fwd, const floa
                              int32_t H, int32_t W, int32_t tau, int32_t slack, uint8_t* cand, void* stream);
 int e2fgvi_defect_clean(const uint8_t* cand, const int32_t* ids, int32_t n, int32_t L, int32_t H, int32_t W, int32_t support,
                         int32_t radius, uint8_t* out, int32_t* counts, void* stream);
+/* Real pixels for restored holes (video.propagate_pixels): for every hole pixel, where in which frame its colour can be seen,
+ * carried along those flows, and one bilinear read of that colour at the end.  Coordinates travel, not colours.
+ *   hole   uint8 [L,H,W] of 0 / 1;  fwd, bwd [L-1,H,W,2] fp32 as above, 8-byte aligned;  jobs int32 [n][2] = (pair t, dir)
+ *   age    uint8 [2,L,H,W]: 255 = not reached, 0 = a known pixel, a = reached after a steps; the caller sets both planes to
+ *          255 * hole.  Plane 0 travels forward in time, plane 1 backward.
+ *   origin fp32 [2,L,H,W,2] = (x, y), 8-byte aligned, uninitialised: meaningful only where 1 <= age <= 254 (a pixel of age 0 is
+ *          its own origin).  The origin of a reached pixel of frame d lies in frame d - age (plane 0) or d + age (plane 1).
+ * The step.  dir 0: source frame s = t, destination d = t+1, pull flow g = bwd[t], check flow c = fwd[t], plane 0;  dir 1: s = t+1,
+ * d = t, g = fwd[t], c = bwd[t], plane 1.  One launch runs all n jobs (in slabs of 65535); within a call no job may write a frame of
+ * a plane that another job reads or writes (video.plan_pixel_chains); a job outside [0, L-1) x {0, 1} writes nothing.  For a
+ * destination pixel p = (x, y) with hole[d](p) == 1 -- no other pixel is touched -- fp64 on the fp32 / uint8 inputs in the order
+ * written, no fused multiply-add:
+ *   q = (x + g_x(p), y + g_y(p));  inside = g(p) finite, 0 <= q_x <= W-1 and 0 <= q_y <= H-1 (in floating point, before any
+ *       conversion to an integer);
+ *   c* = (floor(q_x + 0.5), floor(q_y + 0.5)), the nearest pixel, a half goes up;  a = age[dir, s](c*);
+ *   c_w = bil(c, q) with the sampler and the corner order of e2fgvi_mask_track_step, and `inconsistent` exactly its test;
+ *   reached = inside and a != 255 and a + 1 <= reach and (check == 0 or not inconsistent);
+ *   reached:  age[dir, d](p) = a + 1 and origin[dir, d](p) = O_c + (q - c*) per component, the difference first, then the sum, the
+ *       sum rounded to fp32 by the store;  O_c = c* when a == 0, else origin[dir, s](c*) widened to fp64;
+ *   otherwise age[dir, d](p) = 255.
+ * A thread owns four consecutive pixels and is done after one dword when none of their hole bytes is set.  L >= 2, n, H, W >= 0,
+ * reach in [1, 254], check in {0, 1}, H * W < 2^31 - 256 (E2FGVI_EINVAL otherwise); n == 0 or H * W == 0 returns 0 without a launch
+ * and without looking at the pointers; a null or misaligned pointer with work is E2FGVI_EINVAL (fwd, bwd, origin 8-byte, jobs
+ * 4-byte aligned).
+ * The fill, one launch over all frames.  src uint8 [L,H,W,3]: the frames the colours are read from;  out uint8 [L,H,W,3]: read and
+ * written, only hole pixels are written;  source uint8 [L,H,W] or NULL.  For a pixel p with hole[t](p) == 1:
+ *   the candidates are the two planes in the order of their ages at p, a tie goes to plane 0, a plane of age 255 is none;
+ *   a candidate of age a names the frame f = t - a (plane 0) or t + a (plane 1) and the point O = origin[plane, t](p) (O = p when
+ *       a == 0);  it holds iff 0 <= f < L, O is finite with 0 <= O_x <= W-1 and 0 <= O_y <= H-1, and every one of the four
+ *       bilinear corners of O with a non-zero weight lies in the image and has hole[f] == 0;
+ *   the first candidate that holds gives out[t](p)[ch] = min(255, floor(bil(src[f], O)[ch] + 0.5)); when none holds out keeps its
+ *       bytes;
+ *   source[t](p) = 1 (plane 0), 2 (plane 1) or 3 (left as it was), and 0 where hole is not 1.
+ * L, H, W >= 0, H * W < 2^31 - 256 (E2FGVI_EINVAL otherwise); L == 0 or H * W == 0 returns 0 without a launch and without looking at
+ * the pointers; a null pointer with work (source excepted) or a misaligned origin is E2FGVI_EINVAL.  Neither entry has atomics: the
+ * same inputs give the same bits in every run. */
+int e2fgvi_pixel_track_step(const uint8_t* hole, uint8_t* age, float* origin, const float* fwd, const float* bwd, const int32_t* jobs,
+                            int32_t n, int32_t L, int32_t H, int32_t W, int32_t reach, int32_t check, void* stream);
+int e2fgvi_pixel_fill(const uint8_t* src, const uint8_t* hole, const uint8_t* age, const float* origin, uint8_t* out, uint8_t* source,
+                      int32_t L, int32_t H, int32_t W, void* stream);
 
 /* conv_offset post-processing of SecondOrderDeformableAlignment (feat_prop.py:38-53) fused into the conv that produces
  * it: `residual` must point to the per-pixel flows [P,4] = (u1,v1,u2,v2) with res_ld = 4, `slope` = max_residue:
