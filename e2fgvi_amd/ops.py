@@ -2019,6 +2019,164 @@ def pixel_fill(src, hole, age, origin, out, return_source=False):
     return (ou, source) if return_source else ou
 
 
+GRAIN_MIN_BLOCKS = 32                      # measured blocks a scene, and a band of it, needs for a level of its own
+GRAIN_SCALE_MAX = (1 << 22) - 1            # csrc/grain.hip GR_SCALE_MAX: 510 * scale + 2^15 stays below 2^31
+GRAIN_STRENGTH_Q8_MAX = 1024               # strength 4 in 1 / 256
+
+
+def grain_blocks(frames, hole=None):
+    """The block sums the grain is measured from, one launch over all frames (csrc/grain.hip grain_blocks_kernel;
+    include/e2fgvi_hip.h has the definition; video.match_grain is the caller): frames uint8 [L,H,W,3]; hole uint8 [L,H,W] or None
+    (any non-zero byte is hole) -> (energy int32 [L,Hb,Wb,3], band uint8 [L,Hb,Wb]) on the device, Hb = max(0, (H - 2) // 8), Wb
+    likewise: per 8 x 8 block of the frame's interior and channel the sum of the squared 5-point Laplacian, and the block's luma
+    band 0..7 -- 255 (not measured) when a byte of the block is 0 or 255 or a pixel of its 10 x 10 footprint is hole.  Every entry
+    is written; no host read; exact integers, the same in every run.  Device tensors, or anything torch.as_tensor accepts (uploaded
+    first); wrong dtypes, shapes that do not fit, non-contiguous inputs and tensors on different devices raise ValueError."""
+    lib = _L.load()
+    named = [("frames", frames, torch.uint8)]
+    if hole is not None:
+        named.append(("hole", hole, torch.uint8))
+    up = _defect_inputs(named, "frames")
+    fr = up[0]
+    if fr.dim() != 4 or fr.shape[3] != 3:
+        raise ValueError("frames must be [L,H,W,3], got %s" % (tuple(fr.shape),))
+    L, H, W, _ = fr.shape
+    if hole is not None and tuple(up[1].shape) != (L, H, W):
+        raise ValueError("hole must be [%d,%d,%d] for frames %s, got %s" % (L, H, W, tuple(fr.shape), tuple(up[1].shape)))
+    Hb, Wb = max(0, (H - 2) // 8), max(0, (W - 2) // 8)
+    with torch.cuda.device(fr.device):
+        energy = torch.empty((L, Hb, Wb, 3), dtype=torch.int32, device=fr.device)
+        band = torch.empty((L, Hb, Wb), dtype=torch.uint8, device=fr.device)
+        _L.check(lib.e2fgvi_grain_blocks(_ptr(fr), _ptr(up[1]) if hole is not None else None, L, H, W, _ptr(energy), _ptr(band),
+                                         _stream()), "grain_blocks")
+    return energy, band
+
+
+def _grain_q8(strength_q8):
+    return _defect_int("strength_q8", strength_q8, 0, GRAIN_STRENGTH_Q8_MAX)
+
+
+def grain_lut_from_scale(scale, strength_q8=256):
+    """The table grain_apply reads, from the strengths at the eight band centres (include/e2fgvi_hip.h, "lut"): scale integer
+    [S,8,3] on the device, entries >= 0 -> int32 [S,256,3]: linear between the centres 16 + 32 k of the luma bands, flat outside
+    them, times strength_q8 / 256 (an integer in [0, 1024]) rounded, at most GRAIN_SCALE_MAX.  Integer torch ops, no host read."""
+    q8 = _grain_q8(strength_q8)
+    if not (isinstance(scale, torch.Tensor) and scale.is_cuda) or scale.dim() != 3 or tuple(scale.shape[1:]) != (8, 3) \
+            or scale.dtype not in (torch.int32, torch.int64):
+        raise ValueError("scale must be a device tensor int32 / int64 [S,8,3], got %s"
+                         % ((tuple(scale.shape), scale.dtype) if isinstance(scale, torch.Tensor) else type(scale).__name__,))
+    return _grain_table(scale, q8)
+
+
+def _grain_table(scale, q8):
+    """grain_lut_from_scale after the checks"""
+    sc = scale.to(torch.int64)
+    u = torch.arange(256, device=sc.device, dtype=torch.int64) - 16
+    k, f = (u >> 5).clamp(0, 6), (u & 31).view(1, 256, 1)
+    mid = (sc[:, k] * (32 - f) + sc[:, k + 1] * f + 16) >> 5
+    lut = torch.where((u < 0).view(1, 256, 1), sc[:, :1], torch.where((u >= 224).view(1, 256, 1), sc[:, 7:], mid))
+    return ((lut * q8 + 128) >> 8).clamp(max=GRAIN_SCALE_MAX).to(torch.int32)
+
+
+def grain_lut(energy, band, scene_of, n_scenes, strength_q8=256):
+    """The grain levels of every scene from grain_blocks' sums, and the table grain_apply reads (include/e2fgvi_hip.h, "Levels"):
+    energy int32 [L,Hb,Wb,3], band uint8 [L,Hb,Wb], scene_of int32 [L] (a frame whose entry is outside [0, n_scenes) is in no
+    scene) -> (lut int32 [S,256,3], scale int32 [S,8,3]) on the device, S = n_scenes.  Per scene and channel the lower quartile --
+    the element at index (n - 1) // 4 of the ascending energies -- of the measured blocks of every band that has
+    GRAIN_MIN_BLOCKS of them, and of all the scene's measured blocks (the scene's level; fewer than GRAIN_MIN_BLOCKS: all zeros);
+    a band without its blocks borrows from the nearest band that has them (a tie: the darker; none: the scene's level); clamp to
+    [level >> 2, level << 2]; scale = isqrt(E * 196611 * 19 // 20480).
+    Everything on the device with no host read: ONE sort of int64 keys (group << 27 | energy -- an energy is below 2^27 -- with
+    the groups (scene, band, channel), then (scene, channel) for the scene's level, then one group for what is not measured),
+    searchsorted for the ends of the groups, a gather at each group's quartile position, and float64 sqrt with an integer +-1
+    correction for the isqrt (its argument stays below 2^53).  strength_q8: an integer in [0, 1024].  The checks of grain_blocks."""
+    q8 = _grain_q8(strength_q8)
+    S = _defect_int("n_scenes", n_scenes, 0, 1 << 20)
+    en, bd, so = _defect_inputs((("energy", energy, torch.int32), ("band", band, torch.uint8), ("scene_of", scene_of, torch.int32)),
+                                "energy")
+    if en.dim() != 4 or en.shape[3] != 3:
+        raise ValueError("energy must be [L,Hb,Wb,3], got %s" % (tuple(en.shape),))
+    L = en.shape[0]
+    if tuple(bd.shape) != tuple(en.shape[:3]):
+        raise ValueError("band must be %s for energy %s, got %s" % (list(en.shape[:3]), tuple(en.shape), tuple(bd.shape)))
+    if tuple(so.shape) != (L,):
+        raise ValueError("scene_of must be int32 [%d], got %s" % (L, tuple(so.shape)))
+    with torch.cuda.device(en.device):
+        scale = _grain_levels(en, bd, so, S)
+        return _grain_table(scale, q8), scale
+
+
+def _grain_levels(en, bd, so, S):
+    """grain_lut after the checks: the scale int32 [S,8,3]; integer torch ops on the tensors' device"""
+    L, dev, i64 = en.shape[0], en.device, torch.int64
+    if S == 0 or en.numel() == 0:                    # known from the shapes: nothing is measured
+        return torch.zeros((S, 8, 3), dtype=torch.int32, device=dev)
+    s = so.to(i64).view(L, 1, 1, 1)
+    k = bd.to(i64).unsqueeze(-1)
+    c = torch.arange(3, device=dev, dtype=i64).view(1, 1, 1, 3)
+    ok = (k < 8) & (s >= 0) & (s < S)
+    n_band, n_all = S * 24, S * 27                   # the first group of the scenes' levels; the group of the rest
+    e = en.to(i64).clamp(0, (1 << 27) - 1)
+    g_band = torch.where(ok, (s * 8 + k) * 3 + c, n_all)
+    g_scene = torch.where(ok, n_band + s * 3 + c, n_all)
+    keys = torch.cat([((g_band << 27) | e).reshape(-1), ((g_scene << 27) | e).reshape(-1)]).sort().values
+    ends = torch.searchsorted(keys, torch.arange(n_all + 1, device=dev, dtype=i64) << 27)
+    start, n = ends[:-1], ends[1:] - ends[:-1]
+    at = (start + (n - 1).clamp(min=0) // 4).clamp(max=keys.numel() - 1)
+    q = torch.where(n >= GRAIN_MIN_BLOCKS, keys[at] & ((1 << 27) - 1), torch.zeros_like(n))
+    have = (n >= GRAIN_MIN_BLOCKS)
+    E, has = q[:n_band].view(S, 8, 3), have[:n_band].view(S, 8, 3)
+    G, scene_has = q[n_band:].view(S, 1, 3), have[n_band:].view(S, 1, 3)
+    # the band to read: the nearest that has its blocks, the darker of two equally near (cost 2 |j - k| + (j > k))
+    j = torch.arange(8, device=dev, dtype=i64)
+    cost = 2 * (j.view(1, 8) - j.view(8, 1)).abs() + (j.view(1, 8) > j.view(8, 1)).to(i64)               # [k, j]
+    cost = torch.where(has[:, :, 0].reshape(S, 1, 8), cost.view(1, 8, 8), torch.full_like(cost, 1000).view(1, 8, 8))
+    pick = cost.argmin(dim=2)                                                                          # [S, k]
+    E = torch.where(has.any(dim=1, keepdim=True), torch.gather(E, 1, pick.view(S, 8, 1).expand(S, 8, 3)), G.expand(S, 8, 3))
+    E = torch.minimum(torch.maximum(E, G >> 2), G << 2)
+    E = torch.where(scene_has, E, torch.zeros_like(E))
+    v = E * (196611 * 19) // (1280 * 16)
+    r = v.to(torch.float64).sqrt().floor().to(i64)
+    r = torch.where(r * r > v, r - 1, r)
+    r = torch.where((r + 1) * (r + 1) <= v, r + 1, r)
+    return r.to(torch.int32)
+
+
+def grain_apply(filled, where, lut, scene_of, seed, out=None):
+    """Synthetic grain over the pixels of ``where``, one launch over all frames (csrc/grain.hip grain_apply_kernel;
+    include/e2fgvi_hip.h has the definition): filled uint8 [L,H,W,3]; where uint8 [L,H,W] (any non-zero byte is set); lut int32
+    [S,256,3] as grain_lut made it; scene_of int32 [L]; seed an integer in [0, 2^32) -> device uint8 [L,H,W,3]: at a pixel of
+    ``where`` in a frame with 0 <= scene_of[t] < S every channel gets the counter-based noise n (zero mean, variance 21845) of
+    (seed, t, x, y, c) times lut[scene_of[t], luma of the filled pixel, c] / 65536, rounded, and is clamped to a byte; every other
+    byte is filled's.  ``out``: a device uint8 [L,H,W,3] to write, which may be ``filled`` itself (in place); without it a new
+    buffer.  The checks of grain_blocks; no host read; no atomics: the same arguments give the same bytes in every run."""
+    lib = _L.load()
+    seed = _defect_int("seed", seed, 0, (1 << 32) - 1)
+    if out is not None and not (isinstance(out, torch.Tensor) and out.is_cuda):
+        raise ValueError("out is written: it must be a device tensor, got %s" % type(out).__name__)
+    named = [("filled", filled, torch.uint8), ("where", where, torch.uint8), ("lut", lut, torch.int32), ("scene_of", scene_of, torch.int32)]
+    if out is not None:
+        named.insert(0, ("out", out, torch.uint8))
+    up = _defect_inputs(named, "out" if out is not None else "filled")
+    fl, wh, lu, so = up[-4:]
+    if fl.dim() != 4 or fl.shape[3] != 3:
+        raise ValueError("filled must be [L,H,W,3], got %s" % (tuple(fl.shape),))
+    L, H, W, _ = fl.shape
+    if tuple(wh.shape) != (L, H, W):
+        raise ValueError("where must be [%d,%d,%d] for filled %s, got %s" % (L, H, W, tuple(fl.shape), tuple(wh.shape)))
+    if lu.dim() != 3 or tuple(lu.shape[1:]) != (256, 3):
+        raise ValueError("lut must be int32 [S,256,3], got %s" % (tuple(lu.shape),))
+    if tuple(so.shape) != (L,):
+        raise ValueError("scene_of must be int32 [%d], got %s" % (L, tuple(so.shape)))
+    if out is not None and tuple(up[0].shape) != (L, H, W, 3):
+        raise ValueError("out must be [%d,%d,%d,3], got %s" % (L, H, W, tuple(up[0].shape)))
+    with torch.cuda.device(fl.device):
+        ou = up[0] if out is not None else torch.empty_like(fl)
+        _L.check(lib.e2fgvi_grain_apply(_ptr(fl), _ptr(wh), _ptr(lu) if lu.numel() else None, _ptr(so), lu.shape[0], seed, L, H, W,
+                                        _ptr(ou), _stream()), "grain_apply")
+    return ou
+
+
 YUV_LAYOUTS = {"nv12": 0, "i420": 1}     # E2FGVI_YUV_*/ E2FGVI_CHROMA_* of include/e2fgvi_hip.h
 YUV_CHROMA = {"left": 0, "nearest": 1}
 

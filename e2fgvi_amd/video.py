@@ -925,6 +925,149 @@ def propagate_pixels(model, frames_u8, masks_u8, filled_u8, flows=None, size=Non
     return (out, source) if return_source else out
 
 
+GRAIN_STRENGTH_MAX = 4.0       # match_grain: strength in [0, 4] (ops.GRAIN_STRENGTH_Q8_MAX / 256)
+GRAIN_SIGMA_MAX = 255.0        # the largest sigma levels= may name, in grey levels
+_GRAIN_VARIANCE = 21845.0      # of the unit noise: the sum of four independent bytes (include/e2fgvi_hip.h)
+_GRAIN_SCALE_PER_SIGMA = 65536.0 / math.sqrt(_GRAIN_VARIANCE)
+_GRAIN_SIGMA_PER_SCALE = math.sqrt(_GRAIN_VARIANCE) / 65536.0
+
+
+def _is_u8(a, also_bool=False):
+    return str(getattr(a, "dtype", "")) in (("uint8", "torch.uint8", "bool", "torch.bool") if also_bool else ("uint8", "torch.uint8"))
+
+
+def _check_grain_args(frames_u8, filled_u8, where, hole, scenes, strength, seed, levels, return_levels):
+    """the checks of match_grain from the arguments and the shapes alone -> (scene_of int32 [L], the number of scenes, strength in
+    1 / 256, the scale int64 [S,8,3] of levels= or None)"""
+    shape = tuple(getattr(filled_u8, "shape", ()))
+    if len(shape) != 4 or shape[3] != 3 or not _is_u8(filled_u8):
+        raise ValueError("filled_u8 must be uint8 [L,H,W,3], got %s %s" % (getattr(filled_u8, "dtype", type(filled_u8).__name__), shape))
+    L = int(shape[0])
+    if frames_u8 is None:
+        if levels is None:
+            raise ValueError("frames_u8 may be None only with levels=: the grain is measured from the frames")
+    elif tuple(getattr(frames_u8, "shape", ())) != shape or not _is_u8(frames_u8):
+        raise ValueError("frames_u8 must be uint8 %s, the frames filled_u8 was made from, got %s %s"
+                         % (list(shape), getattr(frames_u8, "dtype", type(frames_u8).__name__), tuple(getattr(frames_u8, "shape", ()))))
+    for name, m in (("where", where), ("hole", hole)):
+        if m is None and name == "hole":
+            continue
+        if tuple(getattr(m, "shape", ())) != shape[:3] or not _is_u8(m, also_bool=True):
+            raise ValueError("%s must be uint8 or bool %s, got %s %s"
+                             % (name, list(shape[:3]), getattr(m, "dtype", type(m).__name__), tuple(getattr(m, "shape", ()))))
+    if isinstance(scenes, str):
+        raise ValueError("scenes must be None or a list of frame numbers, got %r" % (scenes,))
+    cuts = _check_scenes(scenes, L) if scenes is not None else []
+    try:
+        ok = isinstance(strength, (int, float, np.integer, np.floating)) and not isinstance(strength, (bool, np.bool_)) \
+            and 0.0 <= float(strength) <= GRAIN_STRENGTH_MAX
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("strength must be a number in [0, %g], got %r" % (GRAIN_STRENGTH_MAX, strength))
+    if not _integer(seed, 0, (1 << 32) - 1, typed=True):
+        raise ValueError("seed must be an integer in [0, 2^32), got %r" % (seed,))
+    if not isinstance(return_levels, (bool, np.bool_)):
+        raise ValueError("return_levels must be a bool, got %r" % (return_levels,))
+    S = len(cuts) + 1
+    scale = None
+    if levels is not None:
+        try:
+            sig = np.asarray(levels.cpu() if isinstance(levels, torch.Tensor) else levels, dtype=np.float64)
+        except (TypeError, ValueError):
+            sig = np.zeros(0)
+        if sig.shape not in ((8, 3), (S, 8, 3)) or not np.isfinite(sig).all() or (sig < 0).any() or (sig > GRAIN_SIGMA_MAX).any():
+            raise ValueError("levels must be None or sigma in grey levels, finite floats in [0, %g] of shape [8,3] or [%d,8,3] (one "
+                             "per scene), got %s" % (GRAIN_SIGMA_MAX, S, sig.shape if sig.size else type(levels).__name__))
+        scale = np.broadcast_to(np.floor(sig * _GRAIN_SCALE_PER_SIGMA + 0.5).astype(np.int64), (S, 8, 3)).copy()
+    scene_of = np.zeros(L, np.int32)
+    for c in cuts:
+        scene_of[c:] += 1
+    return scene_of, S, int(math.floor(256.0 * float(strength) + 0.5)), scale
+
+
+def _grain_plane(m, device):
+    """where / hole on the device as uint8 (a bool plane becomes 0 / 1)"""
+    if isinstance(m, torch.Tensor):
+        return _upload(m.to(torch.uint8) if m.dtype == torch.bool else m, device)
+    m = np.asarray(m)
+    return _upload(m.view(np.uint8) if m.dtype == np.bool_ else m, device)
+
+
+def _match_grain_device(x, filled, where, hole, scene_of, n_scenes, q8, seed, scale, want_levels):
+    """match_grain after the argument checks and the uploads of the frames and planes -> (out, scale int [S,8,3]) on the device;
+    ``filled`` is not written"""
+    dev = filled.device
+    # every table in front of the first launch
+    so = torch.from_numpy(scene_of).to(dev)
+    scale_d = torch.from_numpy(scale).to(dev) if scale is not None else None
+    L, H, W = (int(v) for v in filled.shape[:3])
+    with torch.cuda.device(dev):
+        # no grain asked for, nothing to lay it on or -- the one host read -- no pixel of ``where``: no launch
+        idle = q8 == 0 or L == 0 or H * W == 0 or not bool(where.any())
+        if idle and not (want_levels and scale_d is None and L > 0):
+            return filled.clone(), scale_d if scale_d is not None else torch.zeros((n_scenes, 8, 3), dtype=torch.int32, device=dev)
+        if scale_d is None:
+            energy, band = ops.grain_blocks(x, where if hole is None else hole)
+            lut, scale_d = ops.grain_lut(energy, band, so, n_scenes, q8)
+        else:
+            lut = ops.grain_lut_from_scale(scale_d, q8)
+        return (filled.clone() if idle else ops.grain_apply(filled, where, lut, so, seed)), scale_d
+
+
+@torch.no_grad()
+def match_grain(frames_u8, filled_u8, where, hole=None, scenes=None, strength=1.0, seed=0, levels=None, return_levels=False,
+                device=None):
+    """Film grain for the pixels a restoration filled in: what inpaint_video(restore=True) pastes is a smooth upscaled prediction,
+    and inside grainy footage -- film, tape, high-ISO video -- a grainless patch is what a viewer sees first.  This measures the
+    grain of the caller's frames and lays synthetic grain of the same strength over the pixels of ``where``:
+        out = inpaint_video(net, frames, masks, size=(432, 240), restore=True)
+        out, src = propagate_pixels(net, frames, masks, out, size=(432, 240), return_source=True)
+        out = match_grain(frames, out, where=(src == 3), hole=paste_mask(masks, frames.shape[1:3], (432, 240)))
+    frames_u8 uint8 [L,H,W,3], the caller's frames; filled_u8 uint8 [L,H,W,3], the restored video; where, hole uint8 or bool
+    [L,H,W], non-zero = set: ``where`` the pixels that get grain, ``hole`` the pixels that say nothing about the grain (the
+    unwanted object), None = ``where`` -> uint8 [L,H,W,3]: a numpy array, or a device tensor when filled_u8 is one.  Everything
+    after the upload runs on the device: two launches (ops.grain_blocks, ops.grain_apply) with ops.grain_lut between them, no host
+    read between the launches; scene_of and every other table is uploaded before the first.  Integers throughout
+    (include/e2fgvi_hip.h has the definition): the same arguments give the same bytes in every run.
+
+    The measurement: per 8 x 8 block and channel the energy of the 5-point Laplacian -- blocks with a clipped byte (0 or 255) or a
+    ``hole`` pixel in their 10 x 10 footprint are left out --, per scene and luma band of 32 levels the lower quartile of it, which
+    keeps the flat blocks and drops the textured ones.  A band with fewer than 32 blocks borrows from the nearest band that has
+    them, and no band lies more than a factor 2 in sigma from the scene's own quartile.  ``scenes``: None or a list of cuts as
+    plan_windows takes them (frames between two cuts share a film stock and are pooled).  The synthesis: counter-based white
+    noise, a hash of (seed, frame, pixel, channel), near-Gaussian, scaled by the level at the filled pixel's luma (linear between
+    the band centres) times ``strength`` in [0, 4]; grain differs per frame and per channel.  ``seed``: an integer in [0, 2^32).
+    ``levels``: sigma in grey levels, floats in [0, 255] of shape [8,3] (band, channel) or [S,8,3] (one per scene), in place of the
+    measurement -- frames_u8 may then be None, and neither borrowing nor the clamp is applied; the scale is floor(sigma 65536 /
+    sqrt(21845) + 0.5).  ``return_levels``: the result is (out, sigma), sigma float64 [S,8,3], the levels that were used (after
+    borrowing and clamp) -- a numpy array, or a device tensor when filled_u8 is one.
+
+    The guarantees: a byte outside ``where`` is filled_u8's byte; nothing is measured across a cut; a scene with nothing to
+    measure (fewer than 32 blocks) is returned unchanged.  strength == 0, no frame, or no pixel in ``where`` (found with one host
+    read) runs no launch and returns filled_u8's bytes -- with return_levels the measurement still runs.
+    Known limits: the grain is white, where scanned grain is spatially correlated -- its high-frequency part is
+    what is measured and matched; a band made of fine texture alone reads its texture as grain, which the clamp bounds and
+    ``levels`` / ``return_levels`` let the caller correct; flat letterbox bars pull a dark band to 0: pass them in ``hole``; a pixel
+    propagate_pixels fetched has lost part of its grain to the bilinear sample, and is left alone by where=(source == 3).
+    Argument errors are ValueErrors that name the argument, raised before any device work.  There is no CPU path."""
+    scene_of, n_scenes, q8, scale = _check_grain_args(frames_u8, filled_u8, where, hole, scenes, strength, seed, levels, return_levels)
+    as_tensor = isinstance(filled_u8, torch.Tensor) and filled_u8.is_cuda
+    if device is None:
+        device = filled_u8.device if as_tensor else torch.device("cuda")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("match_grain runs on the MI355X (cuda) device only; there is no CPU path")
+    filled = _upload(filled_u8, device)
+    x = _upload(frames_u8, device) if frames_u8 is not None and scale is None else None
+    out, scale_d = _match_grain_device(x, filled, _grain_plane(where, device), None if hole is None else _grain_plane(hole, device),
+                                       scene_of, n_scenes, q8, int(seed), scale, bool(return_levels))
+    sigma = scale_d.to(torch.float64) * _GRAIN_SIGMA_PER_SCALE if return_levels else None
+    if not as_tensor:
+        out, sigma = out.cpu().numpy(), sigma.cpu().numpy() if sigma is not None else None
+    return (out, sigma) if return_levels else out
+
+
 DEFECT_THRESHOLD = 16          # detect_defects's defaults: DESIGN.md 3p has the measurements they were chosen from
 DEFECT_SLACK = 0
 DEFECT_SUPPORT = 3

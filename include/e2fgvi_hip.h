@@ -361,6 +361,39 @@ int e2fgvi_pixel_track_step(const uint8_t* hole, uint8_t* age, float* origin, co
                             int32_t n, int32_t L, int32_t H, int32_t W, int32_t reach, int32_t check, void* stream);
 int e2fgvi_pixel_fill(const uint8_t* src, const uint8_t* hole, const uint8_t* age, const float* origin, uint8_t* out, uint8_t* source,
                       int32_t L, int32_t H, int32_t W, void* stream);
+/* Film grain for restored holes (video.match_grain): the grain of the caller's frames is measured block by block, turned into a
+ * table of strengths per scene, luma and channel, and synthetic grain of that strength is laid over the pixels a restoration
+ * filled in.  All arithmetic is integer.  Y = (77 R + 150 G + 29 B + 128) >> 8, the scene detector's luma.
+ *   frames, filled, out uint8 [L,H,W,3];  hole, where uint8 [L,H,W], non-zero = set;  scene_of int32 [L] on the device.
+ * Blocks.  Hb = max(0, (H - 2) / 8), Wb likewise; block (by, bx) covers y in [1 + 8 by, 9 + 8 by), x in [1 + 8 bx, 9 + 8 bx).
+ *   r = 4 p - p(x-1) - p(x+1) - p(y-1) - p(y+1) per pixel and channel;  energy[t,by,bx,c] = sum r^2 over the 64 pixels (<= 6.7e7);
+ *   band[t,by,bx] = (sum Y >> 6) >> 5 in 0..7, or 255 = not measured when one of the block's 192 bytes is 0 or 255 (clipped) or a
+ *   pixel of its 10 x 10 footprint y in [8 by, 8 by + 10), x in [8 bx, 8 bx + 10) has hole != 0 (hole may be NULL: none has).
+ *   energy int32 [L,Hb,Wb,3] and band uint8 [L,Hb,Wb] are written whole, every entry once (energy also where band is 255).
+ * Levels (ops.grain_lut, between the two launches, on the device; GRAIN_MIN_BLOCKS = 32).  A frame belongs to scene scene_of[t]
+ * when that is in [0, n_scenes), to none otherwise.  Per scene s and channel c, over the measured blocks (band != 255) of its
+ * frames: quartile(list) = the element at index (n - 1) / 4 of the n energies in ascending order.
+ *   G[s,c] = quartile of all measured blocks of the scene; fewer than 32 of them: every level of the scene is 0.
+ *   E[s,k,c] = quartile of those with band == k when they are >= 32; otherwise that of the nearest band that has 32 (a tie: the
+ *       darker band), and G[s,c] when no band has;  then E is clamped to [G >> 2, G << 2].
+ *   S[s,k,c] = isqrt(E * 196611 * 19 / (1280 * 16)), integer division:  1280 = 64 pixels x 20, the variance gain of r on white
+ *       noise;  19 / 16 undoes the bias of the quartile;  196611 = (2^32 - 1) / 21845 with 21845 the variance of n below.
+ *   lut[s,y,c] for y in 0..255, linear between the band centres 16 + 32 k:  u = y - 16;  u < 0: S[0];  u >= 224: S[7];  otherwise
+ *       k = u >> 5, f = u & 31, (S[k] (32 - f) + S[k+1] f + 16) >> 5;  then lut = min((lut q8 + 128) >> 8, GRAIN_SCALE_MAX = 2^22 - 1)
+ *       with q8 = round(256 strength).
+ * Synthesis, counter-based.  mix(x) in uint32: x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16.
+ *   h = mix(mix(seed + 0x9E3779B9 t) ^ ((y W + x) 3 + c)), everything mod 2^32;  n = the sum of h's four bytes - 510: zero mean,
+ *   variance 21845.  Where where != 0 and frame t has a scene:
+ *   out = clamp(filled + ((n g + 32768) >> 16), 0, 255), the shift arithmetic, g = lut[scene_of[t], Y(filled pixel), c] read as 0
+ *   when negative and as GRAIN_SCALE_MAX when larger;  every other byte of out is filled's.  out may be filled itself.
+ * No atomics in either entry: the same inputs give the same bits in every run.  L, H, W, n_scenes >= 0, H * W < 2^31 - 256
+ * (E2FGVI_EINVAL otherwise); L == 0 or no block (blocks), L == 0 or H * W == 0 (apply) returns 0 without a launch and without
+ * looking at the pointers; a null pointer with work (hole excepted, and lut when n_scenes == 0) or an energy, lut or scene_of that
+ * is not 4-byte aligned is E2FGVI_EINVAL. */
+int e2fgvi_grain_blocks(const uint8_t* frames, const uint8_t* hole, int32_t L, int32_t H, int32_t W, int32_t* energy, uint8_t* band,
+                        void* stream);
+int e2fgvi_grain_apply(const uint8_t* filled, const uint8_t* where, const int32_t* lut, const int32_t* scene_of, int32_t n_scenes,
+                       uint32_t seed, int32_t L, int32_t H, int32_t W, uint8_t* out, void* stream);
 
 /* conv_offset post-processing of SecondOrderDeformableAlignment (feat_prop.py:38-53) fused into the conv that produces
  * it: `residual` must point to the per-pixel flows [P,4] = (u1,v1,u2,v2) with res_ld = 4, `slope` = max_residue:
