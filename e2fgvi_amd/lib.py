@@ -152,6 +152,9 @@ SYMBOLS = {
     "e2fgvi_pixel_fill": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _i32, _i32, _i32, _fp]),
     "e2fgvi_grain_blocks": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _fp, _fp, _fp]),
     "e2fgvi_grain_apply": (C.c_int, [_fp, _fp, _fp, _fp, _i32, C.c_uint32, _i32, _i32, _i32, _fp, _fp]),
+    "e2fgvi_line_sums": (C.c_int, [_fp, _i32, _i32, _i32, _i32, _fp, _fp]),
+    "e2fgvi_line_columns": (C.c_int, [_fp] + [_i32] * 9 + [_fp] * 6),
+    "e2fgvi_line_paint": (C.c_int, [_fp] * 4 + [_i32] * 8 + [_fp] * 4),
     "e2fgvi_softcomp_fold": (C.c_int, [_fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _fp]),
     "e2fgvi_focal_attention_16": (C.c_int, [_fp, _fp, _fp, _i32, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _fp]),
     "e2fgvi_focal_attention_16_variant": (C.c_int, [C.c_int]),

@@ -2177,6 +2177,120 @@ def grain_apply(filled, where, lut, scene_of, seed, out=None):
     return ou
 
 
+LINE_ROWS_MIN, LINE_ROWS_MAX = 4, 64       # csrc/line_scratch.hip: parameters outside these ranges are E2FGVI_EINVAL
+LINE_TAU_MAX = 254
+LINE_GAP_MAX = 4
+LINE_SIDE_MAX = 8
+LINE_DRIFT_MAX = 2
+LINE_SPAN_MAX = 4
+LINE_RADIUS_MAX = 16                       # csrc/line_scratch.hip LN_RMAX: the largest paint radius line_paint keeps in LDS
+
+
+def line_sums(frames, rows):
+    """The band sums of the line-scratch detector, one launch over all frames (csrc/line_scratch.hip line_sums_kernel;
+    include/e2fgvi_hip.h has the definition; video.detect_line_scratches is the caller): frames uint8 [L,H,W,3] -> device int32
+    [L, H // rows, W]: the scene detector's integer luma summed over each band of ``rows`` rows; the H mod rows rows at the bottom
+    are in no band.  rows in [LINE_ROWS_MIN, LINE_ROWS_MAX]: an integer, no bool.  Device tensors, or anything torch.as_tensor
+    accepts (uploaded first); a wrong dtype or shape and a non-contiguous input raise ValueError.  There is no CPU path and no
+    host read; the same input gives the same bits in every run."""
+    lib = _L.load()
+    rows = _defect_int("rows", rows, LINE_ROWS_MIN, LINE_ROWS_MAX)
+    fr, = _defect_inputs([("frames", frames, torch.uint8)], "frames")
+    if fr.dim() != 4 or fr.shape[3] != 3:
+        raise ValueError("frames must be [L,H,W,3], got %s" % (tuple(fr.shape),))
+    L, H, W, _ = fr.shape
+    with torch.cuda.device(fr.device):
+        S = torch.empty((L, H // rows, W), dtype=torch.int32, device=fr.device)
+        _L.check(lib.e2fgvi_line_sums(_ptr(fr), L, H, W, rows, _ptr(S), _stream()), "line_sums")
+    return S
+
+
+def line_columns(S, rows, tau, gap, side, drift, coverage):
+    """The cross-section test and the height count of the line-scratch detector, one launch (csrc/line_scratch.hip
+    line_columns_kernel; include/e2fgvi_hip.h has the definition): S int32 [L,nb,W] as line_sums made it with the same ``rows`` ->
+    (cand, cnt, col, b0, b1) on the device.  cand uint8 [L,nb,W]: bit 0 set where S lies more than tau rows above the largest S
+    of the ``side`` columns beyond a gap of ``gap`` columns on either side, bit 1 where it lies more than that below the smallest;
+    a column with a side column outside the frame has neither.  Per polarity p (0 bright, 1 dark) and column, over the bands in
+    which a candidate lies within ``drift`` columns: cnt int32 [L,2,W] their number, col uint8 [L,2,W] = cnt 100 >= coverage nb,
+    b0 and b1 int32 [L,2,W] the first and the last of them (nb and -1 without one).  tau in [0, LINE_TAU_MAX], gap in [0,
+    LINE_GAP_MAX], side in [1, LINE_SIDE_MAX], drift in [0, LINE_DRIFT_MAX], coverage in [1, 100]: integers, no bools.  The checks
+    of line_sums; no host read; exact integers, the same in every run."""
+    lib = _L.load()
+    rows = _defect_int("rows", rows, LINE_ROWS_MIN, LINE_ROWS_MAX)
+    tau = _defect_int("tau", tau, 0, LINE_TAU_MAX)
+    gap = _defect_int("gap", gap, 0, LINE_GAP_MAX)
+    side = _defect_int("side", side, 1, LINE_SIDE_MAX)
+    drift = _defect_int("drift", drift, 0, LINE_DRIFT_MAX)
+    coverage = _defect_int("coverage", coverage, 1, 100)
+    sm, = _defect_inputs([("S", S, torch.int32)], "S")
+    if sm.dim() != 3:
+        raise ValueError("S must be int32 [L,nb,W], got %s" % (tuple(sm.shape),))
+    L, nb, W = sm.shape
+    dev = sm.device
+    with torch.cuda.device(dev):
+        cand = torch.empty((L, nb, W), dtype=torch.uint8, device=dev)
+        if nb:                                          # the launch writes every entry
+            cnt, b0, b1 = (torch.empty((L, 2, W), dtype=torch.int32, device=dev) for _ in range(3))
+            col = torch.empty((L, 2, W), dtype=torch.uint8, device=dev)
+        else:                                           # no band, no launch: these are the answer
+            cnt = torch.zeros((L, 2, W), dtype=torch.int32, device=dev)
+            col = torch.zeros((L, 2, W), dtype=torch.uint8, device=dev)
+            b0, b1 = torch.zeros_like(cnt), torch.full_like(cnt, -1)
+        # the entry takes the frame's height: nb rows gives nb bands and no remainder
+        _L.check(lib.e2fgvi_line_columns(_ptr(sm), L, nb * rows, W, rows, tau, gap, side, drift, coverage, _ptr(cand), _ptr(cnt),
+                                         _ptr(col), _ptr(b0), _ptr(b1), _stream()), "line_columns")
+    return cand, cnt, col, b0, b1
+
+
+def line_paint(col, b0, b1, scene, H, rows, drift, span, persist, radius, out=None):
+    """The persistence test and the painting of the line-scratch detector (csrc/line_scratch.hip line_keep_kernel and
+    line_paint_kernel, two launches; include/e2fgvi_hip.h has the definition): col uint8 [L,2,W], b0 and b1 int32 [L,2,W] as
+    line_columns made them; scene int32 [L], equal entries = one scene; H the frames' height -> (keep, counts, masks) on the
+    device.  keep uint8 [L,2,W]: a column of ``col`` stays when, of the frames within ``span`` of its own in its scene, at least
+    min(persist, their number) have a column of ``col`` within ``drift`` columns; counts int32 [L] the kept columns per frame,
+    both polarities added; masks uint8 [L,H,W]: 255 in the rows of the bands b0 .. b1 of a kept column (the H mod rows rows at
+    the bottom go with the last band) and the columns within ``radius`` of it, 0 elsewhere.  ``out``: a device uint8 [L,H,W] to
+    write the masks into; every byte is written.  span in [0, LINE_SPAN_MAX], persist in [1, 2 span + 1], radius in [0,
+    LINE_RADIUS_MAX], drift and rows as above: integers, no bools.  The checks of line_sums; no host read; exact integers."""
+    lib = _L.load()
+    rows = _defect_int("rows", rows, LINE_ROWS_MIN, LINE_ROWS_MAX)
+    drift = _defect_int("drift", drift, 0, LINE_DRIFT_MAX)
+    span = _defect_int("span", span, 0, LINE_SPAN_MAX)
+    persist = _defect_int("persist", persist, 1, 2 * span + 1)
+    radius = _defect_int("radius", radius, 0, LINE_RADIUS_MAX)
+    H = _defect_int("H", H, 0, (1 << 31) - 1)
+    if out is not None and not (isinstance(out, torch.Tensor) and out.is_cuda):
+        raise ValueError("out is written: it must be a device tensor, got %s" % type(out).__name__)
+    named = [("col", col, torch.uint8), ("b0", b0, torch.int32), ("b1", b1, torch.int32), ("scene", scene, torch.int32)]
+    if out is not None:
+        named.append(("out", out, torch.uint8))
+    up = _defect_inputs(named, "col")
+    cl, f0, f1, sc = up[:4]
+    if cl.dim() != 3 or cl.shape[1] != 2:
+        raise ValueError("col must be uint8 [L,2,W], got %s" % (tuple(cl.shape),))
+    L, _, W = cl.shape
+    for t, nm in ((f0, "b0"), (f1, "b1")):
+        if tuple(t.shape) != (L, 2, W):
+            raise ValueError("%s must be int32 [%d,2,%d], got %s" % (nm, L, W, tuple(t.shape)))
+    if tuple(sc.shape) != (L,):
+        raise ValueError("scene must be int32 [%d], got %s" % (L, tuple(sc.shape)))
+    if out is not None and tuple(up[4].shape) != (L, H, W):
+        raise ValueError("out must be [%d,%d,%d], got %s" % (L, H, W, tuple(up[4].shape)))
+    dev = cl.device
+    with torch.cuda.device(dev):
+        work = L > 0 and W > 0 and H // rows > 0
+        if out is not None:
+            masks = up[4] if work else up[4].zero_()
+        else:
+            masks = (torch.empty if work else torch.zeros)((L, H, W), dtype=torch.uint8, device=dev)
+        # with work the entry clears counts and writes every entry of keep
+        keep = (torch.empty if work else torch.zeros)((L, 2, W), dtype=torch.uint8, device=dev)
+        counts = (torch.empty if work else torch.zeros)(L, dtype=torch.int32, device=dev)
+        _L.check(lib.e2fgvi_line_paint(_ptr(cl), _ptr(f0), _ptr(f1), _ptr(sc), L, H, W, rows, drift, span, persist, radius, _ptr(keep),
+                                       _ptr(counts), _ptr(masks), _stream()), "line_paint")
+    return keep, counts, masks
+
+
 YUV_LAYOUTS = {"nv12": 0, "i420": 1}     # E2FGVI_YUV_*/ E2FGVI_CHROMA_* of include/e2fgvi_hip.h
 YUV_CHROMA = {"left": 0, "nearest": 1}
 

@@ -1171,7 +1171,7 @@ def detect_defects(model, frames_u8, flows=None, size=None, scenes=None, thresho
     frame still shows.  L < 3 or no eligible frame: empty masks without a launch and without computing flows.
 
     Known limits: defects that last longer than one frame (vertical line scratches, flicker) are no temporal spikes and are not
-    found; an object that appears for a single frame is dirt to this test; a blotch bends the very flow that is supposed to see
+    found (detect_line_scratches finds the scratches); an object that appears for a single frame is dirt to this test; a blotch bends the very flow that is supposed to see
     past it, and what a trained SPyNet does around one has not been measured here.
     threshold in [0, 254], slack in [0, 2], support in [1, 9], radius in [0, 16]: integers; 0 < max_fraction <= 1; return_counts a
     bool; no bools elsewhere; a string for ``scenes`` is refused.  Argument errors are ValueErrors that name the argument, raised
@@ -1191,7 +1191,96 @@ def detect_defects(model, frames_u8, flows=None, size=None, scenes=None, thresho
     return (masks, counts) if return_counts else masks
 
 
-YuvFormat = collections.namedtuple("YuvFormat", "layout matrix full_range chroma")
+LINE_ROWS = 16                 # detect_line_scratches's defaults: DESIGN.md 3s has the measurements they were chosen from
+LINE_TAU = 6
+LINE_GAP = 2
+LINE_SIDE = 3
+LINE_DRIFT = 1
+LINE_COVERAGE = 50
+LINE_SPAN = 2
+LINE_PERSIST = 3
+LINE_RADIUS = 2
+
+
+def _check_line_args(frames_u8, scenes, rows, tau, gap, side, drift, coverage, span, persist, radius, return_counts):
+    """the checks of detect_line_scratches from the arguments and the shapes alone -> (scene_of int32 [L], the nine integers)"""
+    shape = tuple(getattr(frames_u8, "shape", ()))
+    if len(shape) != 4 or shape[3] != 3 or not _is_u8(frames_u8):
+        raise ValueError("frames must be uint8 [L,H,W,3], got %s %s" % (getattr(frames_u8, "dtype", type(frames_u8).__name__), shape))
+    L = int(shape[0])
+    if isinstance(scenes, str):
+        raise ValueError("scenes must be None or a list of frame numbers, got %r" % (scenes,))
+    cuts = _check_scenes(scenes, L) if scenes is not None else []
+    ranges = (("rows", rows, ops.LINE_ROWS_MIN, ops.LINE_ROWS_MAX), ("tau", tau, 0, ops.LINE_TAU_MAX), ("gap", gap, 0, ops.LINE_GAP_MAX),
+              ("side", side, 1, ops.LINE_SIDE_MAX), ("drift", drift, 0, ops.LINE_DRIFT_MAX), ("coverage", coverage, 1, 100),
+              ("span", span, 0, ops.LINE_SPAN_MAX))
+    for name, v, lo, hi in ranges + (("persist", persist, 1, 2 * int(span) + 1 if _integer(span, 0, ops.LINE_SPAN_MAX) else 1),
+                                     ("radius", radius, 0, ops.LINE_RADIUS_MAX)):
+        if not _integer(v, lo, hi):
+            raise ValueError("%s must be an integer in [%d, %d], got %r" % (name, lo, hi, v))
+    if not isinstance(return_counts, (bool, np.bool_)):
+        raise ValueError("return_counts must be a bool, got %r" % (return_counts,))
+    scene_of = np.zeros(L, np.int32)
+    for c in cuts:
+        scene_of[c:] += 1
+    return scene_of, tuple(int(v) for v in (rows, tau, gap, side, drift, coverage, span, persist, radius))
+
+
+def _detect_line_scratches_device(x, scene_of, rows, tau, gap, side, drift, coverage, span, persist, radius):
+    """detect_line_scratches after the argument checks and the upload of the frames: x uint8 [L,H,W,3] on the device -> (masks
+    uint8 [L,H,W] of 0 / 255, counts int32 [L]) on the device.  Four launches, no host read."""
+    so = torch.from_numpy(scene_of).to(x.device)        # in front of the first launch
+    with torch.cuda.device(x.device):
+        S = ops.line_sums(x, rows)
+        _, _, col, b0, b1 = ops.line_columns(S, rows, tau, gap, side, drift, coverage)
+        _, counts, masks = ops.line_paint(col, b0, b1, so, int(x.shape[1]), rows, drift, span, persist, radius)
+    return masks, counts
+
+
+@torch.no_grad()
+def detect_line_scratches(frames_u8, scenes=None, rows=LINE_ROWS, tau=LINE_TAU, gap=LINE_GAP, side=LINE_SIDE, drift=LINE_DRIFT,
+                          coverage=LINE_COVERAGE, span=LINE_SPAN, persist=LINE_PERSIST, radius=LINE_RADIUS, return_counts=False,
+                          device=None):
+    """Masks of vertical line scratches -- the bright or dark stripe one to three pixels wide that a particle in the gate cuts
+    over most of the frame's height, in nearly the same column for seconds -- from the frames alone: frames_u8 uint8 [L,H,W,3]
+    (an array or a tensor) -> uint8 numpy [L,H,W] of 0 / 255, what inpaint_video takes; np.maximum joins them with
+    detect_defects's.  It needs no model and no flows; everything after the upload runs on the device, in four launches
+    (ops.line_sums, ops.line_columns, ops.line_paint) without a host read.  Integers throughout (include/e2fgvi_hip.h has the
+    definition): the same arguments give the same bytes in every run.
+
+    A scratch lasts, so detect_defects's temporal test is blind to it and the cue is spatial.  The integer luma -- the scene
+    detector's -- is summed over bands of ``rows`` rows.  In a band a column is a bright candidate when its sum lies more than
+    ``tau`` grey levels per row above the LARGEST sum among the ``side`` columns beyond a gap of ``gap`` columns on either side,
+    and a dark one when it lies more than that below the smallest (the envelope form, as in detect_defects: against a median or
+    a mean of the sides every edge of the scenery is a candidate on its brighter side); a column whose side columns
+    do not all lie in the frame is never one.  A column has the height when candidates of one polarity lie within ``drift``
+    columns of it in at least ``coverage`` per cent of the bands, and it is kept when that holds, within ``drift`` columns, on
+    at least ``persist`` of the frames within ``span`` of its own -- all of them when fewer exist: a single frame votes alone.
+    ``scenes``: None or a list of cuts as plan_windows takes them (detect_cuts finds them); nothing votes across a cut.  A kept
+    column is painted from its first to its last band with a candidate (a last band takes the H mod rows rows below it along),
+    ``radius`` columns to either side.  With ``return_counts`` the result is (masks, counts), counts the int32 [L] numbers of
+    kept columns, both polarities added.  H < rows, or no frame: empty masks.
+
+    Known limits: a real thin vertical structure that moves less than about its own width plus 2 drift per frame
+    -- a pole in a locked-off shot -- looks the same to a spatial test, persistence only rejects what moves faster; a scratch over
+    less than ``coverage`` per cent of the height, or slanted by more than +-drift columns over it, is not found; nor is flicker.
+    Letterbox bars and logos have edges that read as scratches where they are vertical; there is no ``hole`` argument yet to
+    keep them out.
+    rows in [4, 64], tau in [0, 254], gap in [0, 4], side in [1, 8], drift in [0, 2], coverage in [1, 100], span in [0, 4],
+    persist in [1, 2 span + 1], radius in [0, 16]: integers, no bools; return_counts a bool; a string for ``scenes`` is refused.
+    Argument errors are ValueErrors that name the argument, raised before any device work.  There is no CPU path."""
+    scene_of, params = _check_line_args(frames_u8, scenes, rows, tau, gap, side, drift, coverage, span, persist, radius, return_counts)
+    if device is None:
+        device = frames_u8.device if isinstance(frames_u8, torch.Tensor) and frames_u8.is_cuda else torch.device("cuda")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("detect_line_scratches runs on the MI355X (cuda) device only; there is no CPU path")
+    masks, counts = _detect_line_scratches_device(_upload(frames_u8, device), scene_of, *params)
+    masks, counts = masks.cpu().numpy(), counts.cpu().numpy()
+    return (masks, counts) if return_counts else masks
+
+
+YuvFormat =collections.namedtuple("YuvFormat", "layout matrix full_range chroma")
 YUV_MATRICES = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}         # (Kr, Kb)
 
 

@@ -394,6 +394,39 @@ int e2fgvi_grain_blocks(const uint8_t* frames, const uint8_t* hole, int32_t L, i
                         void* stream);
 int e2fgvi_grain_apply(const uint8_t* filled, const uint8_t* where, const int32_t* lut, const int32_t* scene_of, int32_t n_scenes,
                        uint32_t seed, int32_t L, int32_t H, int32_t W, uint8_t* out, void* stream);
+/* Vertical line scratches (video.detect_line_scratches): a column that stands out against both its sides, over most of the frame's
+ * height, frame after frame -- the persistent film defect a temporal test cannot see.  All arithmetic is integer.
+ *   frames uint8 [L,H,W,3];  Y = (77 R + 150 G + 29 B + 128) >> 8, the scene detector's luma;  scene int32 [L] on the device: two
+ *   frames are in one scene when their entries are equal.  Parameters rows, tau, gap, side, drift, coverage (per cent), span,
+ *   persist, radius.  Polarity p = 0 is bright, p = 1 dark; the two never mix in any step.
+ * 1. Band sums.  nb = H / rows;  S[t,b,x] = the sum of Y over the rows b rows .. b rows + rows - 1, int32 [L,nb,W].  The H mod rows
+ *    rows at the bottom are in no band and are not read; they are only painted (5).
+ * 2. Cross-section test, in envelope form.  The side columns of x are x-gap-side .. x-gap-1 and x+gap+1 .. x+gap+side; a column
+ *    with a side column outside the frame is never a candidate.  bright[t,b,x] = S > (the largest S of the sides) + tau rows,
+ *    dark[t,b,x] = S < (the smallest) - tau rows: strict.  cand uint8 [L,nb,W] = bright | dark << 1.
+ * 3. Height.  near_p[t,b,x] = the OR of the candidates of polarity p at the columns x-drift .. x+drift that lie in the frame;
+ *    cnt[t,p,x] = the number of bands with near_p;  col[t,p,x] = cnt 100 >= coverage nb;  b0, b1[t,p,x] = the first and the last
+ *    band with near_p, nb and -1 when there is none.  cnt, b0, b1 int32 [L,2,W], col uint8 [L,2,W] of 0 / 1.
+ * 4. Persistence.  coln[t,p,x] = the OR of col over x-drift .. x+drift in the frame;  votes[t,p,x] = the number of frames u with
+ *    t-span <= u <= t+span, 0 <= u < L, scene[u] == scene[t] and coln[u,p,x];  avail[t] = the number of such frames u;
+ *    keep[t,p,x] = col[t,p,x] and votes >= min(persist, avail), uint8 [L,2,W] of 0 / 1;  counts[t] = the sum of keep over p and x,
+ *    int32 [L] (the paint entry clears all L first; integer atomics, exact).
+ * 5. Paint.  P[t,b,x] = some kept column xx of either polarity with |xx - x| <= radius and b0[t,p,xx] <= b <= b1[t,p,xx];
+ *    masks[t,y,x] = 255 P[t, min(y / rows, nb - 1), x], uint8 [L,H,W]: the remainder rows go with the last band.
+ * e2fgvi_line_sums does 1, e2fgvi_line_columns 2 and 3, e2fgvi_line_paint 4 and 5 (col may hold any non-zero byte for 1).  The
+ * sums entry reads every frame byte of a band once and the paint entry writes every mask byte once; every entry of every output is
+ * written.  The same inputs give the same bits in every run; nothing is read on the host.  L, H, W >= 0, H * W < 2^31 - 256, rows
+ * in [4, 64], tau in [0, 254], gap in [0, 4], side in [1, 8], drift in [0, 2], coverage in [1, 100], span in [0, 4], persist in
+ * [1, 2 span + 1], radius in [0, 16] (E2FGVI_EINVAL otherwise, from the arguments alone); L == 0, H * W == 0 or nb == 0 returns 0
+ * without a launch and without looking at the pointers (counts is then not cleared either); a null pointer with work, or an int32
+ * array that is not 4-byte aligned, is E2FGVI_EINVAL.  Frames are launched in slabs of 65535. */
+int e2fgvi_line_sums(const uint8_t* frames, int32_t L, int32_t H, int32_t W, int32_t rows, int32_t* S, void* stream);
+int e2fgvi_line_columns(const int32_t* S, int32_t L, int32_t H, int32_t W, int32_t rows, int32_t tau, int32_t gap, int32_t side,
+                        int32_t drift, int32_t coverage, uint8_t* cand, int32_t* cnt, uint8_t* col, int32_t* b0, int32_t* b1,
+                        void* stream);
+int e2fgvi_line_paint(const uint8_t* col, const int32_t* b0, const int32_t* b1, const int32_t* scene, int32_t L, int32_t H, int32_t W,
+                      int32_t rows, int32_t drift, int32_t span, int32_t persist, int32_t radius, uint8_t* keep, int32_t* counts,
+                      uint8_t* masks, void* stream);
 
 /* conv_offset post-processing of SecondOrderDeformableAlignment (feat_prop.py:38-53) fused into the conv that produces
  * it: `residual` must point to the per-pixel flows [P,4] = (u1,v1,u2,v2) with res_ld = 4, `slope` = max_residue:
