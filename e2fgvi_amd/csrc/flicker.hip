@@ -1,0 +1,317 @@
+// Deflicker (video.deflicker): per frame a tone curve that moves its luma quantiles onto their mean over the frames around it.
+// Pure integers; include/e2fgvi_hip.h has the definition, tests/flicker_cases.py restates it in numpy, word for word and byte for
+// byte.
+//   frames uint8 [L][H][W][3], read as N = H W pixels per frame;  Y = (77 R + 150 G + 29 B + 128) >> 8 (the scene detector's luma)
+//
+// The histogram pass.  hist[t][v] = the pixels of frame t with Y == v, int32 [L][256].  A workgroup owns FL_HPX = 8192 consecutive
+// pixels of one frame; a thread takes FL_HIT = 8 groups of four pixels, 1024 pixels apart -- three dwords each when the frame starts
+// on a dword (a group is 12 bytes, so every group of the frame is aligned when the first is), twelve bytes otherwise; the last
+// group of a frame may be short and is read by bytes.  All the dwords of a thread are asked for before the first is used.  Every
+// frame byte is read once.  Counts go to LDS with integer atomics, FL_HC = 8 copies of the 256 bins side by side (word 8 v + tid % 8:
+// eight lanes that hit one bin hit eight banks); four equal lumas in a group -- the flat frame, where every lane of every wave
+// hits one bin -- are one atomic of 4.  After the barrier thread v adds its bin's copies and, if the sum is not zero, adds it to
+// hist[t][v] with one integer global atomic.  The entry clears all L 256 words on the stream first, so every word is written.
+// Integer atomics: exact, the same in every run.  A bin holds up to N <= 2^26.
+//
+// The curves pass is ONE launch: workgroup t, thread v.  The nodes of the other frames of the window are not read from Q (that
+// would need a launch of its own in front): the workgroup recomputes them from hist, frame by frame over its window of at most 2
+// FL_SPAN_MAX + 1 = 17 frames -- a 256-wide inclusive scan of the row (wave shuffles, the four wave totals through LDS) into LDS,
+// then thread k < 32 finds the smallest level with C > r_k by bisection and adds its node to a register.  256 words and three
+// barriers per frame of the window; recomputing costs L (2 span + 1) KB of L2 reads in all.  The frame's own scan, row and nodes
+// stay in LDS for the 256 shifts.  64-bit where the definition says so (and in r_k: 63 N passes 2^31).
+//
+// The apply pass.  A workgroup stages the frame's 256 shifts in LDS and owns FL_APX = 4096 consecutive pixels; a thread takes four
+// groups of four pixels, loaded as in the histogram pass when both the frame and its output start on a dword.  The shift is looked
+// up once per pixel and added to its three bytes, clipped to [0, 255]; twelve bytes go out as three dwords (or byte by byte): each
+// output byte is written once, by the thread that read the input byte, so out == frames is in order.
+#include "common.h"
+
+namespace {
+
+constexpr int FL_NTH = 256;
+constexpr int FL_PX = 4;                  // pixels per group
+constexpr int FL_HIT = 8;                 // groups per thread of the histogram kernel
+constexpr int FL_HPX = FL_NTH * FL_PX * FL_HIT;
+// A/B switches (build.build_variant("tag", "-DFL_COPIES=1")); profiles/flicker.txt has what they measured
+#ifndef FL_COPIES
+#define FL_COPIES 8
+#endif
+#ifndef FL_MERGE4
+#define FL_MERGE4 1
+#endif
+constexpr int FL_HC = FL_COPIES;          // copies of the histogram in LDS: a power of two
+constexpr int FL_AIT = 4;                 // groups per thread of the apply kernel
+constexpr int FL_APX = FL_NTH * FL_PX * FL_AIT;
+constexpr int FL_FRAMES_MAX = 65535;      // frames per launch (the grid's y axis); more are launched in slabs
+constexpr int FL_K = 32;                  // quantile nodes per frame
+constexpr int FL_SPAN_MAX = 8, FL_SHIFT_MAX = 64;
+constexpr long long FL_N_MAX = 1LL << 26;
+
+__device__ __forceinline__ int fl_luma(unsigned r, unsigned g, unsigned b) { return (int)((77u * r + 150u * g + 29u * b + 128u) >> 8); }
+
+// the four lumas of a group of four pixels held in three dwords
+__device__ __forceinline__ void fl_luma4(unsigned w0, unsigned w1, unsigned w2, int (&y)[FL_PX]) {
+    y[0] = fl_luma(w0 & 255u, (w0 >> 8) & 255u, (w0 >> 16) & 255u);
+    y[1] = fl_luma(w0 >> 24, w1 & 255u, (w1 >> 8) & 255u);
+    y[2] = fl_luma((w1 >> 16) & 255u, w1 >> 24, w2 & 255u);
+    y[3] = fl_luma((w2 >> 8) & 255u, (w2 >> 16) & 255u, w2 >> 24);
+}
+
+__global__ void __launch_bounds__(FL_NTH)
+flicker_hist_kernel(const uint8_t* __restrict__ frames, int t0, int N, int* __restrict__ hist) {
+    __shared__ int s_h[256 * FL_HC];
+    const int t = t0 + (int)blockIdx.y;
+    const int tid = (int)threadIdx.x;
+    for (int i = tid; i < 256 * FL_HC; i += FL_NTH) s_h[i] = 0;
+    __syncthreads();
+    const uint8_t* fr = frames + (long long)t * N * 3;
+    const int p0 = (int)blockIdx.x * FL_HPX + tid * FL_PX;        // < 2^26 + 8192: blockIdx.x < ceil(N / FL_HPX)
+    int* mine = s_h + (tid & (FL_HC - 1));
+    // the same for every thread of the frame: a group is 12 bytes
+    if (((uintptr_t)fr & 3) == 0) {
+        unsigned w[FL_HIT][3];
+#pragma unroll
+        for (int k = 0; k < FL_HIT; ++k) {
+            const int p = p0 + k * FL_NTH * FL_PX;
+            w[k][0] = w[k][1] = w[k][2] = 0;
+            if (p + FL_PX <= N) {                                  // the twelve bytes lie in frame t
+                const unsigned* q = reinterpret_cast<const unsigned*>(fr + (long long)p * 3);
+                w[k][0] = q[0];
+                w[k][1] = q[1];
+                w[k][2] = q[2];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < FL_HIT; ++k) {
+            const int p = p0 + k * FL_NTH * FL_PX;
+            if (p + FL_PX <= N) {
+                int y[FL_PX];
+                fl_luma4(w[k][0], w[k][1], w[k][2], y);
+                if (FL_MERGE4 && y[0] == y[1] && y[1] == y[2] && y[2] == y[3]) {
+                    atomicAdd(mine + y[0] * FL_HC, FL_PX);
+                } else {
+#pragma unroll
+                    for (int j = 0; j < FL_PX; ++j) atomicAdd(mine + y[j] * FL_HC, 1);
+                }
+            } else {
+                for (int j = 0; p + j < N; ++j) {                  // the short group at the end of the frame
+                    const uint8_t* q = fr + (long long)(p + j) * 3;
+                    atomicAdd(mine + fl_luma(q[0], q[1], q[2]) * FL_HC, 1);
+                }
+            }
+        }
+    } else {
+        for (int k = 0; k < FL_HIT; ++k) {
+            const int p = p0 + k * FL_NTH * FL_PX;
+            for (int j = 0; j < FL_PX && p + j < N; ++j) {
+                const uint8_t* q = fr + (long long)(p + j) * 3;
+                atomicAdd(mine + fl_luma(q[0], q[1], q[2]) * FL_HC, 1);
+            }
+        }
+    }
+    __syncthreads();
+    int sum = 0;
+#pragma unroll
+    for (int c = 0; c < FL_HC; ++c) sum += s_h[tid * FL_HC + ((c + tid) & (FL_HC - 1))];
+    if (sum) atomicAdd(hist + (long long)t * 256 + tid, sum);
+}
+
+// the inclusive scan of one value per thread over the workgroup's 256 threads; s_w holds the four wave totals.  Two barriers; the
+// caller puts one more between two calls (s_w is read here after the first and written again in the next call).
+__device__ __forceinline__ int fl_scan256(int v, int* s_w) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) {
+        const int o = __shfl_up(v, s, 64);
+        if (lane >= s) v += o;
+    }
+    if (lane == 63) s_w[wave] = v;
+    __syncthreads();
+    int base = 0;
+#pragma unroll
+    for (int w = 0; w < FL_NTH / 64 - 1; ++w)
+        if (w < wave) base += s_w[w];
+    return v + base;
+}
+
+// Q of one frame's node k from its scan in LDS (s_c[v] = C[v]) : the smallest v with C[v] > r by bisection; a row that does not sum
+// to N (the contract) still ends at some v <= 255, and an empty bin there divides by 1
+__device__ __forceinline__ int fl_node(const int* s_c, int k, int N) {
+    const long long r = ((long long)(2 * k + 1) * N) / (2 * FL_K);
+    int lo = 0, hi = 255;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if ((long long)s_c[mid] > r) hi = mid;
+        else lo = mid + 1;
+    }
+    const int below = lo ? s_c[lo - 1] : 0;
+    const int h = s_c[lo] - below;
+    long long frac = (16 * (r - below)) / (h > 0 ? h : 1);
+    frac = frac < 0 ? 0 : (frac > 15 ? 15 : frac);                 // in 0 .. 15 already when the row sums to N
+    return 16 * lo + (int)frac;
+}
+
+__global__ void __launch_bounds__(FL_NTH)
+flicker_curves_kernel(const int* __restrict__ hist, const int* __restrict__ scene, int L, int N, int span, int max_shift,
+                      int* __restrict__ Q, short* __restrict__ d) {
+    __shared__ int s_c[2][256];            // [0]: the scan of the window's frame at hand, [1]: the scan of frame t
+    __shared__ int s_w[FL_NTH / 64];
+    __shared__ int s_s[FL_K];              // the node shifts of frame t
+    const int t = (int)blockIdx.x;
+    const int y = (int)threadIdx.x;
+    const int sc = scene[t];
+    const int u0 = max(t - span, 0), u1 = min(t + span, L - 1);
+    int qsum = 0, n = 0, qt = 0, ht = 0;
+    for (int u = u0; u <= u1; ++u) {
+        if (scene[u] != sc) continue;                              // the same for the whole workgroup
+        const int h = hist[(long long)u * 256 + y];
+        const int c = fl_scan256(h, s_w);
+        const int which = u == t ? 1 : 0;
+        s_c[which][y] = c;
+        if (which) ht = h;
+        __syncthreads();
+        if (y < FL_K) {
+            const int q = fl_node(s_c[which], y, N);
+            qsum += q;
+            if (which) qt = q;
+        }
+        ++n;
+        __syncthreads();                                           // s_c[0] and s_w are written again in the next trip
+    }
+    if (y < FL_K) {
+        const int T = (2 * qsum + n) / (2 * n);                    // n >= 1: frame t is in its own window
+        s_s[y] = min(max(T - qt, -16 * max_shift), 16 * max_shift);
+        Q[(long long)t * FL_K + y] = qt;
+    }
+    __syncthreads();
+    const int below = y ? s_c[1][y - 1] : 0;
+    const long long c2 = 2LL * below + ht;
+    long long phi = (c2 * (FL_K * 128)) / N - 128;
+    phi = phi < 0 ? 0 : (phi > (FL_K - 1) * 256 ? (FL_K - 1) * 256 : phi);
+    const int k0 = (int)phi >> 8, f = (int)phi & 255, k1 = min(k0 + 1, FL_K - 1);
+    const int d16 = (s_s[k0] * (256 - f) + s_s[k1] * f + 128) >> 8;
+    d[(long long)t * 256 + y] = (short)((d16 + 8) >> 4);
+}
+
+// hipcc turns two clipped values packed side by side into v_ashr_pk_u8_i32, whose neighbouring bytes came out wrong on the chip
+// (csrc/yuv.hip store_bytes has the account, build.verify_no_pk_u8 the check): the empty asm keeps the clip a v_med3_i32
+__device__ __forceinline__ unsigned fl_byte(int v) {
+    v = min(max(v, 0), 255);
+    asm volatile("" : "+v"(v));
+    return (unsigned)v;
+}
+
+__global__ void __launch_bounds__(FL_NTH)
+flicker_apply_kernel(const uint8_t* frames, const short* __restrict__ d, int t0, int N, uint8_t* out) {
+    __shared__ int s_d[256];
+    const int t = t0 + (int)blockIdx.y;
+    const int tid = (int)threadIdx.x;
+    s_d[tid] = d[(long long)t * 256 + tid];
+    __syncthreads();
+    const uint8_t* fr = frames + (long long)t * N * 3;
+    uint8_t* fo = out + (long long)t * N * 3;
+    const int p0 = (int)blockIdx.x * FL_APX + tid * FL_PX;
+    const bool aligned = (((uintptr_t)fr | (uintptr_t)fo) & 3) == 0;       // the same for every thread of the frame
+    unsigned w[FL_AIT][3];
+    // frames and out may be the same buffer (no __restrict__): a thread reads the bytes of its groups before it writes any of them
+    if (aligned) {
+#pragma unroll
+        for (int k = 0; k < FL_AIT; ++k) {
+            const int p = p0 + k * FL_NTH * FL_PX;
+            w[k][0] = w[k][1] = w[k][2] = 0;
+            if (p + FL_PX <= N) {                                  // the twelve bytes lie in frame t
+                const unsigned* q = reinterpret_cast<const unsigned*>(fr + (long long)p * 3);
+                w[k][0] = q[0];
+                w[k][1] = q[1];
+                w[k][2] = q[2];
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < FL_AIT; ++k) {
+        const int p = p0 + k * FL_NTH * FL_PX;
+        if (aligned && p + FL_PX <= N) {
+            int y[FL_PX];
+            fl_luma4(w[k][0], w[k][1], w[k][2], y);
+            unsigned b[12];
+#pragma unroll
+            for (int i = 0; i < 12; ++i) b[i] = fl_byte((int)((w[k][i >> 2] >> (8 * (i & 3))) & 255u) + s_d[y[i / 3]]);
+            unsigned* o = reinterpret_cast<unsigned*>(fo + (long long)p * 3);
+#pragma unroll
+            for (int i = 0; i < 3; ++i) o[i] = b[4 * i] | (b[4 * i + 1] << 8) | (b[4 * i + 2] << 16) | (b[4 * i + 3] << 24);
+        } else {
+            for (int j = 0; j < FL_PX && p + j < N; ++j) {
+                const uint8_t* q = fr + (long long)(p + j) * 3;
+                const int r = q[0], g = q[1], bl = q[2];
+                const int s = s_d[fl_luma(r, g, bl)];
+                uint8_t* o = fo + (long long)(p + j) * 3;
+                o[0] = (uint8_t)min(max(r + s, 0), 255);
+                o[1] = (uint8_t)min(max(g + s, 0), 255);
+                o[2] = (uint8_t)min(max(bl + s, 0), 255);
+            }
+        }
+    }
+}
+
+int fl_check_sizes(const char* who, int32_t L, int32_t H, int32_t W) {
+    E2_REQUIRE(L >= 0 && H >= 0 && W >= 0, E2FGVI_EINVAL, "%s: negative size (L = %d, H = %d, W = %d)", who, L, H, W);
+    E2_REQUIRE((int64_t)H * W <= FL_N_MAX, E2FGVI_EINVAL, "%s: needs H * W <= 2^26, got %d x %d", who, H, W);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int e2fgvi_flicker_hist(const uint8_t* frames, int32_t* hist, int32_t L, int32_t H, int32_t W, void* stream) {
+    if (int rc = fl_check_sizes("flicker_hist", L, H, W)) return rc;
+    const int N = H * W;
+    if (L == 0 || N == 0) return 0;                                // no pixel: no launch, and the pointers are not looked at
+    E2_REQUIRE(frames && hist, E2FGVI_EINVAL, "flicker_hist: null pointer");
+    E2_REQUIRE(((uintptr_t)hist & 3) == 0, E2FGVI_EINVAL, "flicker_hist: hist must be 4-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(hist, 0, sizeof(int32_t) * 256 * (size_t)L, st);
+    E2_REQUIRE(e == hipSuccess, (int)e, "flicker_hist: hipMemsetAsync failed: %s", hipGetErrorString(e));
+    const unsigned nblk = (unsigned)((N + FL_HPX - 1) / FL_HPX);
+    for (int t0 = 0; t0 < L; t0 += FL_FRAMES_MAX) {
+        const dim3 grid(nblk, (unsigned)(L - t0 < FL_FRAMES_MAX ? L - t0 : FL_FRAMES_MAX), 1);
+        hipLaunchKernelGGL(flicker_hist_kernel, grid, dim3(FL_NTH), 0, st, frames, t0, N, hist);
+        E2_LAUNCH_CHECK("flicker_hist");
+    }
+    return 0;
+}
+
+extern "C" int e2fgvi_flicker_curves(const int32_t* hist, const int32_t* scene, int32_t* Q, int16_t* d, int32_t L, int32_t N,
+                                     int32_t span, int32_t max_shift, void* stream) {
+    E2_REQUIRE(L >= 0 && N >= 0, E2FGVI_EINVAL, "flicker_curves: negative size (L = %d, N = %d)", L, N);
+    E2_REQUIRE(N <= FL_N_MAX, E2FGVI_EINVAL, "flicker_curves: needs N <= 2^26, got %d", N);
+    E2_REQUIRE(span >= 0 && span <= FL_SPAN_MAX, E2FGVI_EINVAL, "flicker_curves: span must be in [0, %d], got %d", FL_SPAN_MAX, span);
+    E2_REQUIRE(max_shift >= 1 && max_shift <= FL_SHIFT_MAX, E2FGVI_EINVAL, "flicker_curves: max_shift must be in [1, %d], got %d",
+               FL_SHIFT_MAX, max_shift);
+    if (L == 0 || N == 0) return 0;                                // no pixel: no launch, and the pointers are not looked at
+    E2_REQUIRE(hist && scene && Q && d, E2FGVI_EINVAL, "flicker_curves: null pointer");
+    E2_REQUIRE((((uintptr_t)hist | (uintptr_t)scene | (uintptr_t)Q) & 3) == 0 && ((uintptr_t)d & 1) == 0, E2FGVI_EINVAL,
+               "flicker_curves: hist, scene and Q must be 4-byte aligned, d 2-byte aligned");
+    hipLaunchKernelGGL(flicker_curves_kernel, dim3((unsigned)L), dim3(FL_NTH), 0, (hipStream_t)stream, hist, scene, L, N, span,
+                       max_shift, Q, d);
+    E2_LAUNCH_CHECK("flicker_curves");
+    return 0;
+}
+
+extern "C" int e2fgvi_flicker_apply(const uint8_t* frames, const int16_t* d, uint8_t* out, int32_t L, int32_t H, int32_t W,
+                                    void* stream) {
+    if (int rc = fl_check_sizes("flicker_apply", L, H, W)) return rc;
+    const int N = H * W;
+    if (L == 0 || N == 0) return 0;                                // no pixel: no launch, and the pointers are not looked at
+    E2_REQUIRE(frames && d && out, E2FGVI_EINVAL, "flicker_apply: null pointer");
+    E2_REQUIRE(((uintptr_t)d & 1) == 0, E2FGVI_EINVAL, "flicker_apply: d must be 2-byte aligned");
+    const uint64_t bytes = (uint64_t)L * (uint64_t)N * 3, a = (uint64_t)(uintptr_t)frames, b = (uint64_t)(uintptr_t)out;
+    E2_REQUIRE(a == b || a + bytes <= b || b + bytes <= a, E2FGVI_EINVAL,
+               "flicker_apply: out must be frames itself or not overlap it");
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned nblk = (unsigned)((N + FL_APX - 1) / FL_APX);
+    for (int t0 = 0; t0 < L; t0 += FL_FRAMES_MAX) {
+        const dim3 grid(nblk, (unsigned)(L - t0 < FL_FRAMES_MAX ? L - t0 : FL_FRAMES_MAX), 1);
+        hipLaunchKernelGGL(flicker_apply_kernel, grid, dim3(FL_NTH), 0, st, frames, d, t0, N, out);
+        E2_LAUNCH_CHECK("flicker_apply");
+    }
+    return 0;
+}

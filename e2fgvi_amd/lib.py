@@ -155,6 +155,9 @@ SYMBOLS = {
     "e2fgvi_line_sums": (C.c_int, [_fp, _i32, _i32, _i32, _i32, _fp, _fp]),
     "e2fgvi_line_columns": (C.c_int, [_fp] + [_i32] * 9 + [_fp] * 6),
     "e2fgvi_line_paint": (C.c_int, [_fp] * 4 + [_i32] * 8 + [_fp] * 4),
+    "e2fgvi_flicker_hist": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _fp]),
+    "e2fgvi_flicker_curves": (C.c_int, [_fp] * 4 + [_i32] * 4 + [_fp]),
+    "e2fgvi_flicker_apply": (C.c_int, [_fp, _fp, _fp, _i32, _i32, _i32, _fp]),
     "e2fgvi_softcomp_fold": (C.c_int, [_fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _fp]),
     "e2fgvi_focal_attention_16": (C.c_int, [_fp, _fp, _fp, _i32, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _fp]),
     "e2fgvi_focal_attention_16_variant": (C.c_int, [C.c_int]),

@@ -2291,7 +2291,97 @@ def line_paint(col, b0, b1, scene, H, rows, drift, span, persist, radius, out=No
     return keep, counts, masks
 
 
-YUV_LAYOUTS = {"nv12": 0, "i420": 1}     # E2FGVI_YUV_*/ E2FGVI_CHROMA_* of include/e2fgvi_hip.h
+FLICKER_SPAN_MAX = 8                       # csrc/flicker.hip: parameters outside these ranges are E2FGVI_EINVAL
+FLICKER_SHIFT_MAX = 64
+FLICKER_NODES = 32                         # quantile nodes per frame (FL_K)
+FLICKER_PIXELS_MAX = 1 << 26               # H W of a frame: a histogram bin is an int32 and the curve's products stay in 64 bits
+
+
+def _flicker_frames(fr, name="frames"):
+    if fr.dim() != 4 or fr.shape[3] != 3:
+        raise ValueError("%s must be [L,H,W,3], got %s" % (name, tuple(fr.shape)))
+    if fr.shape[1] * fr.shape[2] > FLICKER_PIXELS_MAX:
+        raise ValueError("%s must have H W <= 2^26, got %d x %d" % (name, fr.shape[1], fr.shape[2]))
+    return tuple(int(v) for v in fr.shape[:3])
+
+
+def flicker_hist(frames, out=None):
+    """The luma histograms of the deflicker, one launch over all frames (csrc/flicker.hip flicker_hist_kernel; include/e2fgvi_hip.h
+    has the definition; video.deflicker is the caller): frames uint8 [L,H,W,3] -> device int32 [L,256], the number of pixels of
+    each frame per level of the scene detector's integer luma.  ``out``: a device int32 [L,256] to write into; every word is
+    written (the entry clears the rows first).  Device tensors, or anything torch.as_tensor accepts (uploaded first); a wrong
+    dtype or shape, more than 2^26 pixels a frame and a non-contiguous input raise ValueError.  There is no CPU path and no host
+    read; integer atomics: the same input gives the same bits in every run."""
+    lib = _L.load()
+    if out is not None and not (isinstance(out, torch.Tensor) and out.is_cuda):
+        raise ValueError("out is written: it must be a device tensor, got %s" % type(out).__name__)
+    named = [("frames", frames, torch.uint8)] + ([("out", out, torch.int32)] if out is not None else [])
+    up = _defect_inputs(named, "frames")
+    fr = up[0]
+    L, H, W = _flicker_frames(fr)
+    if out is not None and tuple(up[1].shape) != (L, 256):
+        raise ValueError("out must be int32 [%d,256], got %s" % (L, tuple(up[1].shape)))
+    with torch.cuda.device(fr.device):
+        work = L > 0 and H * W > 0
+        if out is not None:
+            hist = up[1] if work else up[1].zero_()
+        else:
+            hist = (torch.empty if work else torch.zeros)((L, 256), dtype=torch.int32, device=fr.device)
+        _L.check(lib.e2fgvi_flicker_hist(_ptr(fr), _ptr(hist), L, H, W, _stream()), "flicker_hist")
+    return hist
+
+
+def flicker_curves(hist, scene, N, span, max_shift):
+    """The nodes and the tone curves of the deflicker, one launch (csrc/flicker.hip flicker_curves_kernel; include/e2fgvi_hip.h has
+    the definition): hist int32 [L,256] as flicker_hist made it, every row summing to ``N`` = H W (the contract; it is not
+    checked, which would be a host read); scene int32 [L], equal entries = one scene -> (Q, d) on the device.  Q int32
+    [L,FLICKER_NODES]: the 32 luma quantiles (2k + 1) / 64 of each frame in 1/16 levels.  d int16 [L,256]: per frame and luma
+    level the shift that moves the frame's nodes onto their rounded mean over the frames within ``span`` of it in its scene,
+    clamped to +-``max_shift`` levels at the nodes and interpolated between them.  N in [0, 2^26], span in [0,
+    FLICKER_SPAN_MAX], max_shift in [1, FLICKER_SHIFT_MAX]: integers, no bools.  The checks of flicker_hist; no host read; exact
+    integers, the same in every run."""
+    lib = _L.load()
+    N = _defect_int("N", N, 0, FLICKER_PIXELS_MAX)
+    span = _defect_int("span", span, 0, FLICKER_SPAN_MAX)
+    max_shift = _defect_int("max_shift", max_shift, 1, FLICKER_SHIFT_MAX)
+    hs, sc = _defect_inputs([("hist", hist, torch.int32), ("scene", scene, torch.int32)], "hist")
+    if hs.dim() != 2 or hs.shape[1] != 256:
+        raise ValueError("hist must be int32 [L,256], got %s" % (tuple(hs.shape),))
+    L = int(hs.shape[0])
+    if tuple(sc.shape) != (L,):
+        raise ValueError("scene must be int32 [%d], got %s" % (L, tuple(sc.shape)))
+    with torch.cuda.device(hs.device):
+        work = L > 0 and N > 0                           # with work the launch writes every entry
+        Q = (torch.empty if work else torch.zeros)((L, FLICKER_NODES), dtype=torch.int32, device=hs.device)
+        d = (torch.empty if work else torch.zeros)((L, 256), dtype=torch.int16, device=hs.device)
+        _L.check(lib.e2fgvi_flicker_curves(_ptr(hs), _ptr(sc), _ptr(Q), _ptr(d), L, N, span, max_shift, _stream()), "flicker_curves")
+    return Q, d
+
+
+def flicker_apply(frames, d, out=None):
+    """The tone curves applied, one launch (csrc/flicker.hip flicker_apply_kernel; include/e2fgvi_hip.h has the definition): frames
+    uint8 [L,H,W,3], d int16 [L,256] as flicker_curves made it -> device uint8 [L,H,W,3]: every pixel moved by the shift of its
+    luma, the same for its three bytes, each clipped to [0, 255].  ``out``: a device uint8 [L,H,W,3] to write into -- ``frames``
+    itself for in place, otherwise one that does not overlap it (the entry refuses any other overlap); every byte is written once.
+    The checks of flicker_hist; no host read; exact integers."""
+    lib = _L.load()
+    if out is not None and not (isinstance(out, torch.Tensor) and out.is_cuda):
+        raise ValueError("out is written: it must be a device tensor, got %s" % type(out).__name__)
+    named = [("frames", frames, torch.uint8), ("d", d, torch.int16)] + ([("out", out, torch.uint8)] if out is not None else [])
+    up = _defect_inputs(named, "frames")
+    fr, dd = up[:2]
+    L, H, W = _flicker_frames(fr)
+    if tuple(dd.shape) != (L, 256):
+        raise ValueError("d must be int16 [%d,256], got %s" % (L, tuple(dd.shape)))
+    if out is not None and tuple(up[2].shape) != tuple(fr.shape):
+        raise ValueError("out must be %s, got %s" % (list(fr.shape), tuple(up[2].shape)))
+    with torch.cuda.device(fr.device):
+        ou = up[2] if out is not None else torch.empty_like(fr)
+        _L.check(lib.e2fgvi_flicker_apply(_ptr(fr), _ptr(dd), _ptr(ou), L, H, W, _stream()), "flicker_apply")
+    return ou
+
+
+YUV_LAYOUTS ={"nv12": 0, "i420": 1}     # E2FGVI_YUV_*/ E2FGVI_CHROMA_* of include/e2fgvi_hip.h
 YUV_CHROMA = {"left": 0, "nearest": 1}
 
 

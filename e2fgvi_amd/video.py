@@ -1171,7 +1171,7 @@ def detect_defects(model, frames_u8, flows=None, size=None, scenes=None, thresho
     frame still shows.  L < 3 or no eligible frame: empty masks without a launch and without computing flows.
 
     Known limits: defects that last longer than one frame (vertical line scratches, flicker) are no temporal spikes and are not
-    found (detect_line_scratches finds the scratches); an object that appears for a single frame is dirt to this test; a blotch bends the very flow that is supposed to see
+    found (detect_line_scratches finds the scratches, deflicker takes the flicker out beforehand); an object that appears for a single frame is dirt to this test; a blotch bends the very flow that is supposed to see
     past it, and what a trained SPyNet does around one has not been measured here.
     threshold in [0, 254], slack in [0, 2], support in [1, 9], radius in [0, 16]: integers; 0 < max_fraction <= 1; return_counts a
     bool; no bools elsewhere; a string for ``scenes`` is refused.  Argument errors are ValueErrors that name the argument, raised
@@ -1263,7 +1263,8 @@ def detect_line_scratches(frames_u8, scenes=None, rows=LINE_ROWS, tau=LINE_TAU, 
 
     Known limits: a real thin vertical structure that moves less than about its own width plus 2 drift per frame
     -- a pole in a locked-off shot -- looks the same to a spatial test, persistence only rejects what moves faster; a scratch over
-    less than ``coverage`` per cent of the height, or slanted by more than +-drift columns over it, is not found; nor is flicker.
+    less than ``coverage`` per cent of the height, or slanted by more than +-drift columns over it, is not found; nor is flicker (deflicker
+    takes it out beforehand).
     Letterbox bars and logos have edges that read as scratches where they are vertical; there is no ``hole`` argument yet to
     keep them out.
     rows in [4, 64], tau in [0, 254], gap in [0, 4], side in [1, 8], drift in [0, 2], coverage in [1, 100], span in [0, 4],
@@ -1278,6 +1279,90 @@ def detect_line_scratches(frames_u8, scenes=None, rows=LINE_ROWS, tau=LINE_TAU, 
     masks, counts = _detect_line_scratches_device(_upload(frames_u8, device), scene_of, *params)
     masks, counts = masks.cpu().numpy(), counts.cpu().numpy()
     return (masks, counts) if return_counts else masks
+
+
+FLICKER_SPAN = 4               # deflicker's defaults: DESIGN.md 3t has the measurements they were judged on
+FLICKER_MAX_SHIFT = 32
+
+
+def _check_flicker_args(frames_u8, scenes, span, max_shift, return_curves):
+    """the checks of deflicker from the arguments and the shapes alone -> (scene_of int32 [L], span, max_shift)"""
+    shape = tuple(getattr(frames_u8, "shape", ()))
+    if len(shape) != 4 or shape[3] != 3 or not _is_u8(frames_u8):
+        raise ValueError("frames must be uint8 [L,H,W,3], got %s %s" % (getattr(frames_u8, "dtype", type(frames_u8).__name__), shape))
+    L = int(shape[0])
+    if int(shape[1]) * int(shape[2]) > ops.FLICKER_PIXELS_MAX:
+        raise ValueError("frames must have H W <= 2^26, got %d x %d" % (shape[1], shape[2]))
+    if isinstance(scenes, str):
+        raise ValueError("scenes must be None or a list of frame numbers, got %r" % (scenes,))
+    cuts = _check_scenes(scenes, L) if scenes is not None else []
+    for name, v, lo, hi in (("span", span, 0, ops.FLICKER_SPAN_MAX), ("max_shift", max_shift, 1, ops.FLICKER_SHIFT_MAX)):
+        if not _integer(v, lo, hi):
+            raise ValueError("%s must be an integer in [%d, %d], got %r" % (name, lo, hi, v))
+    if not isinstance(return_curves, (bool, np.bool_)):
+        raise ValueError("return_curves must be a bool, got %r" % (return_curves,))
+    scene_of = np.zeros(L, np.int32)
+    for c in cuts:
+        scene_of[c:] += 1
+    return scene_of, int(span), int(max_shift)
+
+
+def _deflicker_device(x, scene_of, span, max_shift):
+    """deflicker after the argument checks and the upload of the frames: x uint8 [L,H,W,3] on the device -> (out uint8 [L,H,W,3], d
+    int16 [L,256]) on the device.  Three launches, no host read.  Nothing to do (span 0, no frame, no pixel): x itself and zeros."""
+    L, H, W = (int(v) for v in x.shape[:3])
+    if span == 0 or L == 0 or H * W == 0:
+        return x, torch.zeros((L, 256), dtype=torch.int16, device=x.device)
+    so = torch.from_numpy(scene_of).to(x.device)        # in front of the first launch
+    with torch.cuda.device(x.device):
+        hist = ops.flicker_hist(x)
+        _, d = ops.flicker_curves(hist, so, H * W, span, max_shift)
+        out = ops.flicker_apply(x, d)
+    return out, d
+
+
+@torch.no_grad()
+def deflicker(frames_u8, scenes=None, span=FLICKER_SPAN, max_shift=FLICKER_MAX_SHIFT, return_curves=False, device=None):
+    """Takes exposure flicker out of a video -- the frame-to-frame changes of brightness and contrast of old film and tape -- as
+    the first step of a restoration chain, in front of detect_defects, detect_line_scratches and inpaint_video, all of which
+    assume that a thing keeps its brightness from frame to frame: frames_u8 uint8 [L,H,W,3] (an array or a tensor) -> uint8
+    [L,H,W,3], a numpy array, or a device tensor when the input is one (which is used where it is).  With ``return_curves`` the
+    result is (out, d), d the int16 [L,256] shift per frame and luma level.  It needs no model and no flows; everything after the
+    upload runs on the device, in three launches (ops.flicker_hist, ops.flicker_curves, ops.flicker_apply) without a host read.
+    Integers throughout (include/e2fgvi_hip.h has the definition): the same arguments give the same bytes in every run.
+
+    Per frame the histogram of the integer luma -- the scene detector's -- is taken and from it 32 quantile nodes, the luma below
+    which (2k + 1) / 64 of the pixels lie, in 1/16 levels with the position inside the level's bin.  The target of a node is its
+    rounded mean over the frames within ``span`` of the frame in its scene; the node's shift is target minus node, clamped to
+    +-``max_shift`` levels.  A luma level gets the shift of its own quantile -- the middle of its bin in the frame's cumulative
+    histogram -- interpolated between the two nodes around it, rounded to whole levels, and every pixel is moved by the shift of
+    its luma, the same for its three channels, each clipped to [0, 255].  ``scenes``: None or a list of cuts as plan_windows takes
+    them (detect_cuts finds them); nothing is averaged across a cut.
+
+    What follows from that: where no channel clips the luma of the result is exactly the pixel's luma plus its shift (the luma
+    weights add up to 256); a byte at a level whose shift is 0 is the caller's byte; a frame alone in its window -- a scene of
+    one frame -- comes back unchanged; a video whose frames all have the same histogram comes back byte for byte; span == 0, no
+    frame or no pixel runs no launch and returns the caller's bytes.
+
+    Known limits: the shift is additive in RGB, so a strong correction changes saturation slightly; clipped
+    highlights move with their level and stay flat; the ends of a scene average fewer frames and follow their own flicker more;
+    moving scenery changes the histograms too, so a clean video comes back changed by a few levels (on the 25 frames of
+    tests/golden/tennis25.npz, a panning camera, 44 % of the pixels by at most 3 levels); flicker that varies over the frame is
+    not corrected, the curve is one per frame; there is no ``hole`` argument: a large object entering the frame reads as a
+    brightness change.
+    span in [0, 8], max_shift in [1, 64]: integers, no bools; return_curves a bool; a string for ``scenes`` is refused; H W <=
+    2^26.  Argument errors are ValueErrors that name the argument, raised before any device work.  There is no CPU path."""
+    scene_of, span, max_shift = _check_flicker_args(frames_u8, scenes, span, max_shift, return_curves)
+    on_device = isinstance(frames_u8, torch.Tensor) and frames_u8.is_cuda
+    if device is None:
+        device = frames_u8.device if on_device else torch.device("cuda")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("deflicker runs on the MI355X (cuda) device only; there is no CPU path")
+    out, d = _deflicker_device(_upload(frames_u8, device), scene_of, span, max_shift)
+    if not on_device:
+        out, d = out.cpu().numpy(), d.cpu().numpy()
+    return (out, d) if return_curves else out
 
 
 YuvFormat =collections.namedtuple("YuvFormat", "layout matrix full_range chroma")

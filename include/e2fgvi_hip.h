@@ -427,6 +427,35 @@ int e2fgvi_line_columns(const int32_t* S, int32_t L, int32_t H, int32_t W, int32
 int e2fgvi_line_paint(const uint8_t* col, const int32_t* b0, const int32_t* b1, const int32_t* scene, int32_t L, int32_t H, int32_t W,
                       int32_t rows, int32_t drift, int32_t span, int32_t persist, int32_t radius, uint8_t* keep, int32_t* counts,
                       uint8_t* masks, void* stream);
+/* Deflicker (video.deflicker): per frame one tone curve -- a shift per luma level -- that moves the frame's luma quantiles onto
+ * their mean over the frames around it in its scene.  All arithmetic is integer; every division is a floor of non-negative numbers
+ * and >> of a negative number is the arithmetic shift (a floor as well).
+ *   frames uint8 [L,H,W,3];  N = H W, 1 <= N <= 2^26;  scene int32 [L] on the device: two frames are in one scene when their
+ *   entries are equal.  Parameters span in [0, 8], max_shift in [1, 64].  K = 32.
+ * 1. Luma.  Y = (77 R + 150 G + 29 B + 128) >> 8, the scene detector's and the line-scratch detector's.
+ * 2. Histogram.  hist[t][v] = the number of pixels of frame t with Y == v, int32 [L][256];  C[t][v] = hist[t][0] + ... +
+ *    hist[t][v], C[t][-1] = 0.
+ * 3. Nodes, K quantiles per frame in 1/16 levels.  r_k = ((2k + 1) N) / (2K);  v = the smallest level with C[t][v] > r_k;
+ *    Q[t][k] = 16 v + (16 (r_k - C[t][v-1])) / hist[t][v], int32 [L][32], in 0 .. 4095.
+ * 4. Target.  W_t = {u : |u - t| <= span, 0 <= u < L, scene[u] == scene[t]}, n = |W_t| >= 1;
+ *    T[t][k] = (2 (the sum of Q[u][k] over u in W_t) + n) / (2n);  s[t][k] = clamp(T[t][k] - Q[t][k], -16 max_shift, 16 max_shift).
+ * 5. Curve.  For level y: c2 = 2 C[t][y-1] + hist[t][y];  phi = clamp((c2 K 128) / N - 128, 0, (K - 1) 256) (64-bit: c2 K 128
+ *    reaches 2^39; the quotient is taken first, the subtraction may go below zero and is clamped);  k0 = phi >> 8, f = phi & 255,
+ *    k1 = min(k0 + 1, K - 1);  d16 = (s[t][k0] (256 - f) + s[t][k1] f + 128) >> 8;  d[t][y] = (d16 + 8) >> 4, int16 [L][256].
+ * 6. Apply.  out[t,i,j,c] = clamp(frames[t,i,j,c] + d[t][Y(frames[t,i,j])], 0, 255): one shift per pixel, the same for its three
+ *    channels.  Because 77 + 150 + 29 = 256 the luma of the result is exactly Y + d wherever no channel clips.
+ * e2fgvi_flicker_hist does 1 and 2: it clears all L 256 words on the stream and adds with integer atomics (exact, the same in
+ * every run); every frame byte is read once.  e2fgvi_flicker_curves does 3 to 5 in one launch, a workgroup per frame that
+ * recomputes the nodes of its window from hist; its contract is that every row of hist sums to N (a row that does not gives some
+ * curve and no fault); it writes Q[t] and d[t] of every frame.  e2fgvi_flicker_apply does 6; every output byte is written once;
+ * out may be frames itself (in place), any other overlap of the two ranges is E2FGVI_EINVAL.  Nothing is read on the host.
+ * L, H, W, N >= 0, H W <= 2^26, N <= 2^26, span and max_shift in their ranges (E2FGVI_EINVAL otherwise, from the arguments alone);
+ * L == 0, H W == 0 or N == 0 returns 0 without a launch and without looking at the pointers; a null pointer with work, an int32
+ * array that is not 4-byte aligned or a d that is not 2-byte aligned is E2FGVI_EINVAL.  Frames are launched in slabs of 65535. */
+int e2fgvi_flicker_hist(const uint8_t* frames, int32_t* hist, int32_t L, int32_t H, int32_t W, void* stream);
+int e2fgvi_flicker_curves(const int32_t* hist, const int32_t* scene, int32_t* Q, int16_t* d, int32_t L, int32_t N, int32_t span,
+                          int32_t max_shift, void* stream);
+int e2fgvi_flicker_apply(const uint8_t* frames, const int16_t* d, uint8_t* out, int32_t L, int32_t H, int32_t W, void* stream);
 
 /* conv_offset post-processing of SecondOrderDeformableAlignment (feat_prop.py:38-53) fused into the conv that produces
  * it: `residual` must point to the per-pixel flows [P,4] = (u1,v1,u2,v2) with res_ld = 4, `slope` = max_residue:
