@@ -1569,6 +1569,60 @@ def _frame_ids(ids, device):
     return ids.numel()
 
 
+def _int_arg(name, v, lo, hi):
+    """``v`` as an int: an integer in [lo, hi], no bool; ValueError that names the argument otherwise"""
+    if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not lo <= v <= hi:
+        raise ValueError("%s must be an integer in [%d, %d], got %r" % (name, lo, hi, v))
+    return int(v)
+
+
+def _flag_arg(check):
+    """check= as 0 / 1: a bool, or the integer 0 or 1; ValueError otherwise"""
+    if not isinstance(check, (bool, numbers.Integral)) or check not in (0, 1):
+        raise ValueError("check must be a bool (or 0 / 1), got %r" % (check,))
+    return int(check)
+
+
+def _device_inputs(named, first, written=()):
+    """``named`` = ((name, value, dtype), ...) -> the tensors on the device of the first one that is there already (anything else
+    through torch.as_tensor and uploaded); a wrong dtype, a non-contiguous input, a tensor on another device than the first (the
+    message calls it ``first``) and a name of ``written`` that is no device tensor raise ValueError"""
+    for nm, t, _ in named:
+        if nm in written and not (isinstance(t, torch.Tensor) and t.is_cuda):
+            raise ValueError("%s is written: it must be a device tensor, got %s" % (nm, type(t).__name__))
+    device = next((t.device for _, t, _ in named if isinstance(t, torch.Tensor) and t.is_cuda), "cuda")
+    up = [t if isinstance(t, torch.Tensor) and t.is_cuda else torch.as_tensor(t).to(device) for _, t, _ in named]
+    for t, (nm, _, dt) in zip(up, named):
+        if t.dtype != dt:
+            raise ValueError("%s must be %s, got %s" % (nm, dt, t.dtype))
+        if not t.is_contiguous():
+            raise ValueError("%s must be contiguous" % nm)
+        if t.device != up[0].device:
+            raise ValueError("%s is on %s, the %s on %s" % (nm, t.device, first, up[0].device))
+    return up
+
+
+def _alloc(work, shape, dtype, device, out=None):
+    """the buffer a launch fills: empty when the launch writes every entry (``work``), zeros when there is no work and the zeros
+    are the answer; ``out`` when given, zeroed when there is no work"""
+    if out is not None:
+        return out if work else out.zero_()
+    return (torch.empty if work else torch.zeros)(shape, dtype=dtype, device=device)
+
+
+def _frames_shape(t, name):
+    """(L, H, W) of ``t`` as [L,H,W,3]; ValueError that names it otherwise"""
+    if t.dim() != 4 or t.shape[3] != 3:
+        raise ValueError("%s must be [L,H,W,3], got %s" % (name, tuple(t.shape)))
+    return tuple(t.shape[:3])
+
+
+def _scene_table(t, name, L):
+    """a scene table is int32 [L] (the dtype is _device_inputs'); ValueError that names it otherwise"""
+    if tuple(t.shape) != (L,):
+        raise ValueError("%s must be int32 [%d], got %s" % (name, L, tuple(t.shape)))
+
+
 def mask_prepare(masks_u8, ytab, xtab, H, W, iterations=4, ids=None):
     """masks_u8 [L,Hin,Win] uint8 -> [L,H,W] uint8 of 0/1 (NEAREST resize by the given tables, > 0, cross dilation).
     ``ids`` device int32 [n]: -> [n,H,W], output frame l from masks_u8[ids[l]] (an id outside [0, L): an empty mask)."""
@@ -1776,9 +1830,7 @@ def overlay_stats(frames_u8):
     over the frames, exact integers that do not depend on how the threads ran, no host read; overlay_edges thresholds them."""
     lib = _L.load()
     _u8(frames_u8, "frames")
-    if frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
-        raise ValueError("frames must be [L,H,W,3], got %s" % (tuple(frames_u8.shape),))
-    L, H, W, _ = frames_u8.shape
+    L, H, W = _frames_shape(frames_u8, "frames")
     if not 1 <= L <= OVERLAY_FRAMES_MAX:
         raise ValueError("overlay_stats needs between 1 and %d frames, got %d" % (OVERLAY_FRAMES_MAX, L))
     if H * W == 0:
@@ -1799,16 +1851,16 @@ def overlay_edges(stats, L, g_min, coherence, radius):
     _chk(stats, "stats", torch.int32)
     if stats.dim() != 3 or stats.shape[0] != 3 or stats.shape[1] * stats.shape[2] == 0:
         raise ValueError("stats must be [3,H,W] with H, W >= 1, got %s" % (tuple(stats.shape),))
-    for name, v, lo, hi in (("L", L, 1, OVERLAY_FRAMES_MAX), ("g_min", g_min, 1, 2 ** 31 - 1), ("coherence", coherence, 1, 256),
-                            ("radius", radius, 0, OVERLAY_RADIUS_MAX)):
-        if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not lo <= v <= hi:
-            raise ValueError("%s must be an integer in [%d, %d], got %r" % (name, lo, hi, v))
+    L = _int_arg("L", L, 1, OVERLAY_FRAMES_MAX)
+    g_min = _int_arg("g_min", g_min, 1, 2 ** 31 - 1)
+    coherence = _int_arg("coherence", coherence, 1, 256)
+    radius = _int_arg("radius", radius, 0, OVERLAY_RADIUS_MAX)
     _, H, W = stats.shape
     with torch.cuda.device(stats.device):
         out = torch.empty((H, W), dtype=torch.uint8, device=stats.device)
         count = torch.empty(1, dtype=torch.int32, device=stats.device)
-        _L.check(lib.e2fgvi_overlay_edges(_ptr(stats), int(L), H, W, int(g_min), int(coherence), int(radius), _ptr(out), _ptr(count),
-                                          _stream()), "overlay_edges")
+        _L.check(lib.e2fgvi_overlay_edges(_ptr(stats), L, H, W, g_min, coherence, radius, _ptr(out), _ptr(count), _stream()),
+                 "overlay_edges")
     return out, count
 
 
@@ -1823,16 +1875,9 @@ def mask_track_step(planes, fwd, bwd, jobs, check=True):
     non-contiguous inputs and tensors on different devices raise ValueError.  Returns the planes on the device (the tensor that
     was passed when it was there already).  The same inputs give the same bits in every run."""
     lib = _L.load()
-    if not isinstance(check, (bool, numbers.Integral)) or check not in (0, 1):
-        raise ValueError("check must be a bool (or 0 / 1), got %r" % (check,))
-    check = int(check)
-    named = (("planes", planes), ("fwd", fwd), ("bwd", bwd), ("jobs", jobs))
-    device = next((t.device for _, t in named if isinstance(t, torch.Tensor) and t.is_cuda), "cuda")
-    up = [t if isinstance(t, torch.Tensor) and t.is_cuda else torch.as_tensor(t).to(device) for _, t in named]
-    pl, fw, bw, jb = up
-    for t, nm, dt in ((pl, "planes", torch.uint8), (fw, "fwd", torch.float32), (bw, "bwd", torch.float32), (jb, "jobs", torch.int32)):
-        if t.dtype != dt:
-            raise ValueError("%s must be %s, got %s" % (nm, dt, t.dtype))
+    check = _flag_arg(check)
+    named = (("planes", planes, torch.uint8), ("fwd", fwd, torch.float32), ("bwd", bwd, torch.float32), ("jobs", jobs, torch.int32))
+    pl, fw, bw, jb = _device_inputs(named, "planes")
     if pl.dim() != 4 or pl.shape[0] != 2:
         raise ValueError("planes must be [2,L,H,W], got %s" % (tuple(pl.shape),))
     _, L, H, W = pl.shape
@@ -1843,11 +1888,6 @@ def mask_track_step(planes, fwd, bwd, jobs, check=True):
             raise ValueError("%s must be [%d,%d,%d,2] for planes %s, got %s" % (nm, L - 1, H, W, tuple(pl.shape), tuple(t.shape)))
     if jb.dim() != 2 or jb.shape[1] != 2:
         raise ValueError("jobs must be int32 [n,2] of (pair, dir), got %s" % (tuple(jb.shape),))
-    for t, nm in ((pl, "planes"), (fw, "fwd"), (bw, "bwd"), (jb, "jobs")):
-        if not t.is_contiguous():
-            raise ValueError("%s must be contiguous" % nm)
-        if t.device != pl.device:
-            raise ValueError("%s is on %s, the planes on %s" % (nm, t.device, pl.device))
     with torch.cuda.device(pl.device):
         _L.check(lib.e2fgvi_mask_track_step(_ptr(pl), _ptr(fw), _ptr(bw), _ptr(jb), jb.shape[0], L, H, W, check, _stream()),
                  "mask_track_step")
@@ -1857,28 +1897,6 @@ def mask_track_step(planes, fwd, bwd, jobs, check=True):
 DEFECT_THRESHOLD_MAX = 254                 # csrc/defects.hip: tau, slack, support and radius outside these are E2FGVI_EINVAL
 DEFECT_SLACK_MAX = 2
 DEFECT_RADIUS_MAX = 16                     # csrc/defects.hip DF_RMAX: the largest dilation radius defect_clean keeps in LDS
-
-
-def _defect_inputs(named, first):
-    """mask_track_step's checks for the defect entries: ``named`` = ((name, value, dtype), ...) -> the tensors on the device of the
-    first one that is there already (anything else through torch.as_tensor and uploaded); a wrong dtype, a non-contiguous input and
-    a tensor on another device than ``first`` raise ValueError"""
-    device = next((t.device for _, t, _ in named if isinstance(t, torch.Tensor) and t.is_cuda), "cuda")
-    up = [t if isinstance(t, torch.Tensor) and t.is_cuda else torch.as_tensor(t).to(device) for _, t, _ in named]
-    for t, (nm, _, dt) in zip(up, named):
-        if t.dtype != dt:
-            raise ValueError("%s must be %s, got %s" % (nm, dt, t.dtype))
-        if not t.is_contiguous():
-            raise ValueError("%s must be contiguous" % nm)
-        if t.device != up[0].device:
-            raise ValueError("%s is on %s, the %s on %s" % (nm, t.device, first, up[0].device))
-    return up
-
-
-def _defect_int(name, v, lo, hi):
-    if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not lo <= v <= hi:
-        raise ValueError("%s must be an integer in [%d, %d], got %r" % (name, lo, hi, v))
-    return int(v)
 
 
 def defect_candidates(frames, fwd, bwd, ids, threshold, slack, out=None):
@@ -1892,16 +1910,14 @@ def defect_candidates(frames, fwd, bwd, ids, threshold, slack, out=None):
     anything torch.as_tensor accepts (uploaded first); wrong dtypes, shapes that do not fit, non-contiguous inputs and tensors on
     different devices raise ValueError.  There is no CPU path.  The same inputs give the same bits in every run."""
     lib = _L.load()
-    threshold = _defect_int("threshold", threshold, 0, DEFECT_THRESHOLD_MAX)
-    slack = _defect_int("slack", slack, 0, DEFECT_SLACK_MAX)
+    threshold = _int_arg("threshold", threshold, 0, DEFECT_THRESHOLD_MAX)
+    slack = _int_arg("slack", slack, 0, DEFECT_SLACK_MAX)
     named = [("frames", frames, torch.uint8), ("fwd", fwd, torch.float32), ("bwd", bwd, torch.float32), ("ids", ids, torch.int32)]
     if out is not None:
         named.append(("out", out, torch.uint8))
-    up = _defect_inputs(named, "frames")
+    up = _device_inputs(named, "frames")
     fr, fw, bw, idt = up[:4]
-    if fr.dim() != 4 or fr.shape[3] != 3:
-        raise ValueError("frames must be [L,H,W,3], got %s" % (tuple(fr.shape),))
-    L, H, W, _ = fr.shape
+    L, H, W = _frames_shape(fr, "frames")
     if idt.dim() != 1:
         raise ValueError("ids must be int32 [n], got %s" % (tuple(idt.shape),))
     for t, nm in ((fw, "fwd"), (bw, "bwd")):
@@ -1926,12 +1942,12 @@ def defect_clean(cand, ids, support, radius, out=None):
     as they are); without it a buffer of zeros.  support in [1, 9], radius in [0, DEFECT_RADIUS_MAX]: integers, no bools.  The
     checks of defect_candidates; no host read; exact integers, the same in every run."""
     lib = _L.load()
-    support = _defect_int("support", support, 1, 9)
-    radius = _defect_int("radius", radius, 0, DEFECT_RADIUS_MAX)
+    support = _int_arg("support", support, 1, 9)
+    radius = _int_arg("radius", radius, 0, DEFECT_RADIUS_MAX)
     named = [("cand", cand, torch.uint8), ("ids", ids, torch.int32)]
     if out is not None:
         named.append(("out", out, torch.uint8))
-    up = _defect_inputs(named, "candidates")
+    up = _device_inputs(named, "candidates")
     cd, idt = up[:2]
     if cd.dim() != 3:
         raise ValueError("cand must be [L,H,W], got %s" % (tuple(cd.shape),))
@@ -1964,15 +1980,11 @@ def pixel_track_step(hole, age, origin, fwd, bwd, jobs, reach=PIXEL_REACH_MAX, c
     torch.as_tensor accepts (uploaded first); wrong dtypes, shapes that do not fit, non-contiguous inputs and tensors on different
     devices raise ValueError.  Returns (age, origin).  The same inputs give the same bits in every run."""
     lib = _L.load()
-    reach = _defect_int("reach", reach, 1, PIXEL_REACH_MAX)
-    if not isinstance(check, (bool, numbers.Integral)) or check not in (0, 1):
-        raise ValueError("check must be a bool (or 0 / 1), got %r" % (check,))
-    for nm, t in (("age", age), ("origin", origin)):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda):
-            raise ValueError("%s is written in place: it must be a device tensor, got %s" % (nm, type(t).__name__))
+    reach = _int_arg("reach", reach, 1, PIXEL_REACH_MAX)
+    check = _flag_arg(check)
     named = (("age", age, torch.uint8), ("hole", hole, torch.uint8), ("origin", origin, torch.float32), ("fwd", fwd, torch.float32),
              ("bwd", bwd, torch.float32), ("jobs", jobs, torch.int32))
-    ag, ho, og, fw, bw, jb = _defect_inputs(named, "age")
+    ag, ho, og, fw, bw, jb = _device_inputs(named, "age", written=("age", "origin"))
     if ag.dim() != 4 or ag.shape[0] != 2:
         raise ValueError("age must be [2,L,H,W], got %s" % (tuple(ag.shape),))
     _, L, H, W = ag.shape
@@ -1986,7 +1998,7 @@ def pixel_track_step(hole, age, origin, fwd, bwd, jobs, reach=PIXEL_REACH_MAX, c
         raise ValueError("jobs must be int32 [n,2] of (pair, dir), got %s" % (tuple(jb.shape),))
     with torch.cuda.device(ag.device):
         _L.check(lib.e2fgvi_pixel_track_step(_ptr(ho), _ptr(ag), _ptr(og), _ptr(fw), _ptr(bw), _ptr(jb), jb.shape[0], L, H, W, reach,
-                                             int(check), _stream()), "pixel_track_step")
+                                             check, _stream()), "pixel_track_step")
     return ag, og
 
 
@@ -1999,14 +2011,10 @@ def pixel_fill(src, hole, age, origin, out, return_source=False):
     written.  Returns out, or with ``return_source`` (out, source): device uint8 [L,H,W] of 0 (no hole pixel), 1 (plane 0), 2
     (plane 1), 3 (a hole pixel left as it was).  The checks of pixel_track_step; no host read; the same bits in every run."""
     lib = _L.load()
-    if not (isinstance(out, torch.Tensor) and out.is_cuda):
-        raise ValueError("out is written in place: it must be a device tensor, got %s" % type(out).__name__)
     named = (("out", out, torch.uint8), ("src", src, torch.uint8), ("hole", hole, torch.uint8), ("age", age, torch.uint8),
              ("origin", origin, torch.float32))
-    ou, sr, ho, ag, og = _defect_inputs(named, "out")
-    if ou.dim() != 4 or ou.shape[3] != 3:
-        raise ValueError("out must be [L,H,W,3], got %s" % (tuple(ou.shape),))
-    L, H, W, _ = ou.shape
+    ou, sr, ho, ag, og = _device_inputs(named, "out", written=("out",))
+    L, H, W = _frames_shape(ou, "out")
     for t, nm, shape in ((sr, "src", (L, H, W, 3)), (ho, "hole", (L, H, W)), (ag, "age", (2, L, H, W)), (og, "origin", (2, L, H, W, 2))):
         if tuple(t.shape) != shape:
             raise ValueError("%s must be %s for out %s, got %s" % (nm, list(shape), tuple(ou.shape), tuple(t.shape)))
@@ -2036,11 +2044,9 @@ def grain_blocks(frames, hole=None):
     named = [("frames", frames, torch.uint8)]
     if hole is not None:
         named.append(("hole", hole, torch.uint8))
-    up = _defect_inputs(named, "frames")
+    up = _device_inputs(named, "frames")
     fr = up[0]
-    if fr.dim() != 4 or fr.shape[3] != 3:
-        raise ValueError("frames must be [L,H,W,3], got %s" % (tuple(fr.shape),))
-    L, H, W, _ = fr.shape
+    L, H, W = _frames_shape(fr, "frames")
     if hole is not None and tuple(up[1].shape) != (L, H, W):
         raise ValueError("hole must be [%d,%d,%d] for frames %s, got %s" % (L, H, W, tuple(fr.shape), tuple(up[1].shape)))
     Hb, Wb = max(0, (H - 2) // 8), max(0, (W - 2) // 8)
@@ -2053,7 +2059,7 @@ def grain_blocks(frames, hole=None):
 
 
 def _grain_q8(strength_q8):
-    return _defect_int("strength_q8", strength_q8, 0, GRAIN_STRENGTH_Q8_MAX)
+    return _int_arg("strength_q8", strength_q8, 0, GRAIN_STRENGTH_Q8_MAX)
 
 
 def grain_lut_from_scale(scale, strength_q8=256):
@@ -2091,16 +2097,15 @@ def grain_lut(energy, band, scene_of, n_scenes, strength_q8=256):
     searchsorted for the ends of the groups, a gather at each group's quartile position, and float64 sqrt with an integer +-1
     correction for the isqrt (its argument stays below 2^53).  strength_q8: an integer in [0, 1024].  The checks of grain_blocks."""
     q8 = _grain_q8(strength_q8)
-    S = _defect_int("n_scenes", n_scenes, 0, 1 << 20)
-    en, bd, so = _defect_inputs((("energy", energy, torch.int32), ("band", band, torch.uint8), ("scene_of", scene_of, torch.int32)),
+    S = _int_arg("n_scenes", n_scenes, 0, 1 << 20)
+    en, bd, so = _device_inputs((("energy", energy, torch.int32), ("band", band, torch.uint8), ("scene_of", scene_of, torch.int32)),
                                 "energy")
     if en.dim() != 4 or en.shape[3] != 3:
         raise ValueError("energy must be [L,Hb,Wb,3], got %s" % (tuple(en.shape),))
     L = en.shape[0]
     if tuple(bd.shape) != tuple(en.shape[:3]):
         raise ValueError("band must be %s for energy %s, got %s" % (list(en.shape[:3]), tuple(en.shape), tuple(bd.shape)))
-    if tuple(so.shape) != (L,):
-        raise ValueError("scene_of must be int32 [%d], got %s" % (L, tuple(so.shape)))
+    _scene_table(so, "scene_of", L)
     with torch.cuda.device(en.device):
         scale = _grain_levels(en, bd, so, S)
         return _grain_table(scale, q8), scale
@@ -2151,23 +2156,18 @@ def grain_apply(filled, where, lut, scene_of, seed, out=None):
     byte is filled's.  ``out``: a device uint8 [L,H,W,3] to write, which may be ``filled`` itself (in place); without it a new
     buffer.  The checks of grain_blocks; no host read; no atomics: the same arguments give the same bytes in every run."""
     lib = _L.load()
-    seed = _defect_int("seed", seed, 0, (1 << 32) - 1)
-    if out is not None and not (isinstance(out, torch.Tensor) and out.is_cuda):
-        raise ValueError("out is written: it must be a device tensor, got %s" % type(out).__name__)
+    seed = _int_arg("seed", seed, 0, (1 << 32) - 1)
     named = [("filled", filled, torch.uint8), ("where", where, torch.uint8), ("lut", lut, torch.int32), ("scene_of", scene_of, torch.int32)]
     if out is not None:
         named.insert(0, ("out", out, torch.uint8))
-    up = _defect_inputs(named, "out" if out is not None else "filled")
+    up = _device_inputs(named, "out" if out is not None else "filled", written=("out",))
     fl, wh, lu, so = up[-4:]
-    if fl.dim() != 4 or fl.shape[3] != 3:
-        raise ValueError("filled must be [L,H,W,3], got %s" % (tuple(fl.shape),))
-    L, H, W, _ = fl.shape
+    L, H, W = _frames_shape(fl, "filled")
     if tuple(wh.shape) != (L, H, W):
         raise ValueError("where must be [%d,%d,%d] for filled %s, got %s" % (L, H, W, tuple(fl.shape), tuple(wh.shape)))
     if lu.dim() != 3 or tuple(lu.shape[1:]) != (256, 3):
         raise ValueError("lut must be int32 [S,256,3], got %s" % (tuple(lu.shape),))
-    if tuple(so.shape) != (L,):
-        raise ValueError("scene_of must be int32 [%d], got %s" % (L, tuple(so.shape)))
+    _scene_table(so, "scene_of", L)
     if out is not None and tuple(up[0].shape) != (L, H, W, 3):
         raise ValueError("out must be [%d,%d,%d,3], got %s" % (L, H, W, tuple(up[0].shape)))
     with torch.cuda.device(fl.device):
@@ -2194,11 +2194,9 @@ def line_sums(frames, rows):
     accepts (uploaded first); a wrong dtype or shape and a non-contiguous input raise ValueError.  There is no CPU path and no
     host read; the same input gives the same bits in every run."""
     lib = _L.load()
-    rows = _defect_int("rows", rows, LINE_ROWS_MIN, LINE_ROWS_MAX)
-    fr, = _defect_inputs([("frames", frames, torch.uint8)], "frames")
-    if fr.dim() != 4 or fr.shape[3] != 3:
-        raise ValueError("frames must be [L,H,W,3], got %s" % (tuple(fr.shape),))
-    L, H, W, _ = fr.shape
+    rows = _int_arg("rows", rows, LINE_ROWS_MIN, LINE_ROWS_MAX)
+    fr, = _device_inputs([("frames", frames, torch.uint8)], "frames")
+    L, H, W = _frames_shape(fr, "frames")
     with torch.cuda.device(fr.device):
         S = torch.empty((L, H // rows, W), dtype=torch.int32, device=fr.device)
         _L.check(lib.e2fgvi_line_sums(_ptr(fr), L, H, W, rows, _ptr(S), _stream()), "line_sums")
@@ -2216,26 +2214,23 @@ def line_columns(S, rows, tau, gap, side, drift, coverage):
     LINE_GAP_MAX], side in [1, LINE_SIDE_MAX], drift in [0, LINE_DRIFT_MAX], coverage in [1, 100]: integers, no bools.  The checks
     of line_sums; no host read; exact integers, the same in every run."""
     lib = _L.load()
-    rows = _defect_int("rows", rows, LINE_ROWS_MIN, LINE_ROWS_MAX)
-    tau = _defect_int("tau", tau, 0, LINE_TAU_MAX)
-    gap = _defect_int("gap", gap, 0, LINE_GAP_MAX)
-    side = _defect_int("side", side, 1, LINE_SIDE_MAX)
-    drift = _defect_int("drift", drift, 0, LINE_DRIFT_MAX)
-    coverage = _defect_int("coverage", coverage, 1, 100)
-    sm, = _defect_inputs([("S", S, torch.int32)], "S")
+    rows = _int_arg("rows", rows, LINE_ROWS_MIN, LINE_ROWS_MAX)
+    tau = _int_arg("tau", tau, 0, LINE_TAU_MAX)
+    gap = _int_arg("gap", gap, 0, LINE_GAP_MAX)
+    side = _int_arg("side", side, 1, LINE_SIDE_MAX)
+    drift = _int_arg("drift", drift, 0, LINE_DRIFT_MAX)
+    coverage = _int_arg("coverage", coverage, 1, 100)
+    sm, = _device_inputs([("S", S, torch.int32)], "S")
     if sm.dim() != 3:
         raise ValueError("S must be int32 [L,nb,W], got %s" % (tuple(sm.shape),))
     L, nb, W = sm.shape
     dev = sm.device
     with torch.cuda.device(dev):
         cand = torch.empty((L, nb, W), dtype=torch.uint8, device=dev)
-        if nb:                                          # the launch writes every entry
-            cnt, b0, b1 = (torch.empty((L, 2, W), dtype=torch.int32, device=dev) for _ in range(3))
-            col = torch.empty((L, 2, W), dtype=torch.uint8, device=dev)
-        else:                                           # no band, no launch: these are the answer
-            cnt = torch.zeros((L, 2, W), dtype=torch.int32, device=dev)
-            col = torch.zeros((L, 2, W), dtype=torch.uint8, device=dev)
-            b0, b1 = torch.zeros_like(cnt), torch.full_like(cnt, -1)
+        # with a band the launch writes every entry; without one there is no launch and zeros (b1: -1) are the answer
+        cnt, b0 = (_alloc(nb, (L, 2, W), torch.int32, dev) for _ in range(2))
+        b1 = torch.empty_like(cnt) if nb else torch.full_like(cnt, -1)
+        col = _alloc(nb, (L, 2, W), torch.uint8, dev)
         # the entry takes the frame's height: nb rows gives nb bands and no remainder
         _L.check(lib.e2fgvi_line_columns(_ptr(sm), L, nb * rows, W, rows, tau, gap, side, drift, coverage, _ptr(cand), _ptr(cnt),
                                          _ptr(col), _ptr(b0), _ptr(b1), _stream()), "line_columns")
@@ -2253,18 +2248,16 @@ def line_paint(col, b0, b1, scene, H, rows, drift, span, persist, radius, out=No
     write the masks into; every byte is written.  span in [0, LINE_SPAN_MAX], persist in [1, 2 span + 1], radius in [0,
     LINE_RADIUS_MAX], drift and rows as above: integers, no bools.  The checks of line_sums; no host read; exact integers."""
     lib = _L.load()
-    rows = _defect_int("rows", rows, LINE_ROWS_MIN, LINE_ROWS_MAX)
-    drift = _defect_int("drift", drift, 0, LINE_DRIFT_MAX)
-    span = _defect_int("span", span, 0, LINE_SPAN_MAX)
-    persist = _defect_int("persist", persist, 1, 2 * span + 1)
-    radius = _defect_int("radius", radius, 0, LINE_RADIUS_MAX)
-    H = _defect_int("H", H, 0, (1 << 31) - 1)
-    if out is not None and not (isinstance(out, torch.Tensor) and out.is_cuda):
-        raise ValueError("out is written: it must be a device tensor, got %s" % type(out).__name__)
+    rows = _int_arg("rows", rows, LINE_ROWS_MIN, LINE_ROWS_MAX)
+    drift = _int_arg("drift", drift, 0, LINE_DRIFT_MAX)
+    span = _int_arg("span", span, 0, LINE_SPAN_MAX)
+    persist = _int_arg("persist", persist, 1, 2 * span + 1)
+    radius = _int_arg("radius", radius, 0, LINE_RADIUS_MAX)
+    H = _int_arg("H", H, 0, (1 << 31) - 1)
     named = [("col", col, torch.uint8), ("b0", b0, torch.int32), ("b1", b1, torch.int32), ("scene", scene, torch.int32)]
     if out is not None:
         named.append(("out", out, torch.uint8))
-    up = _defect_inputs(named, "col")
+    up = _device_inputs(named, "col", written=("out",))
     cl, f0, f1, sc = up[:4]
     if cl.dim() != 3 or cl.shape[1] != 2:
         raise ValueError("col must be uint8 [L,2,W], got %s" % (tuple(cl.shape),))
@@ -2272,20 +2265,16 @@ def line_paint(col, b0, b1, scene, H, rows, drift, span, persist, radius, out=No
     for t, nm in ((f0, "b0"), (f1, "b1")):
         if tuple(t.shape) != (L, 2, W):
             raise ValueError("%s must be int32 [%d,2,%d], got %s" % (nm, L, W, tuple(t.shape)))
-    if tuple(sc.shape) != (L,):
-        raise ValueError("scene must be int32 [%d], got %s" % (L, tuple(sc.shape)))
+    _scene_table(sc, "scene", L)
     if out is not None and tuple(up[4].shape) != (L, H, W):
         raise ValueError("out must be [%d,%d,%d], got %s" % (L, H, W, tuple(up[4].shape)))
     dev = cl.device
     with torch.cuda.device(dev):
         work = L > 0 and W > 0 and H // rows > 0
-        if out is not None:
-            masks = up[4] if work else up[4].zero_()
-        else:
-            masks = (torch.empty if work else torch.zeros)((L, H, W), dtype=torch.uint8, device=dev)
+        masks = _alloc(work, (L, H, W), torch.uint8, dev, up[4] if out is not None else None)
         # with work the entry clears counts and writes every entry of keep
-        keep = (torch.empty if work else torch.zeros)((L, 2, W), dtype=torch.uint8, device=dev)
-        counts = (torch.empty if work else torch.zeros)(L, dtype=torch.int32, device=dev)
+        keep = _alloc(work, (L, 2, W), torch.uint8, dev)
+        counts = _alloc(work, L, torch.int32, dev)
         _L.check(lib.e2fgvi_line_paint(_ptr(cl), _ptr(f0), _ptr(f1), _ptr(sc), L, H, W, rows, drift, span, persist, radius, _ptr(keep),
                                        _ptr(counts), _ptr(masks), _stream()), "line_paint")
     return keep, counts, masks
@@ -2298,11 +2287,10 @@ FLICKER_PIXELS_MAX = 1 << 26               # H W of a frame: a histogram bin is 
 
 
 def _flicker_frames(fr, name="frames"):
-    if fr.dim() != 4 or fr.shape[3] != 3:
-        raise ValueError("%s must be [L,H,W,3], got %s" % (name, tuple(fr.shape)))
-    if fr.shape[1] * fr.shape[2] > FLICKER_PIXELS_MAX:
-        raise ValueError("%s must have H W <= 2^26, got %d x %d" % (name, fr.shape[1], fr.shape[2]))
-    return tuple(int(v) for v in fr.shape[:3])
+    L, H, W = _frames_shape(fr, name)
+    if H * W > FLICKER_PIXELS_MAX:
+        raise ValueError("%s must have H W <= 2^26, got %d x %d" % (name, H, W))
+    return L, H, W
 
 
 def flicker_hist(frames, out=None):
@@ -2313,20 +2301,14 @@ def flicker_hist(frames, out=None):
     dtype or shape, more than 2^26 pixels a frame and a non-contiguous input raise ValueError.  There is no CPU path and no host
     read; integer atomics: the same input gives the same bits in every run."""
     lib = _L.load()
-    if out is not None and not (isinstance(out, torch.Tensor) and out.is_cuda):
-        raise ValueError("out is written: it must be a device tensor, got %s" % type(out).__name__)
     named = [("frames", frames, torch.uint8)] + ([("out", out, torch.int32)] if out is not None else [])
-    up = _defect_inputs(named, "frames")
+    up = _device_inputs(named, "frames", written=("out",))
     fr = up[0]
     L, H, W = _flicker_frames(fr)
     if out is not None and tuple(up[1].shape) != (L, 256):
         raise ValueError("out must be int32 [%d,256], got %s" % (L, tuple(up[1].shape)))
     with torch.cuda.device(fr.device):
-        work = L > 0 and H * W > 0
-        if out is not None:
-            hist = up[1] if work else up[1].zero_()
-        else:
-            hist = (torch.empty if work else torch.zeros)((L, 256), dtype=torch.int32, device=fr.device)
+        hist = _alloc(L > 0 and H * W > 0, (L, 256), torch.int32, fr.device, up[1] if out is not None else None)
         _L.check(lib.e2fgvi_flicker_hist(_ptr(fr), _ptr(hist), L, H, W, _stream()), "flicker_hist")
     return hist
 
@@ -2341,19 +2323,18 @@ def flicker_curves(hist, scene, N, span, max_shift):
     FLICKER_SPAN_MAX], max_shift in [1, FLICKER_SHIFT_MAX]: integers, no bools.  The checks of flicker_hist; no host read; exact
     integers, the same in every run."""
     lib = _L.load()
-    N = _defect_int("N", N, 0, FLICKER_PIXELS_MAX)
-    span = _defect_int("span", span, 0, FLICKER_SPAN_MAX)
-    max_shift = _defect_int("max_shift", max_shift, 1, FLICKER_SHIFT_MAX)
-    hs, sc = _defect_inputs([("hist", hist, torch.int32), ("scene", scene, torch.int32)], "hist")
+    N = _int_arg("N", N, 0, FLICKER_PIXELS_MAX)
+    span = _int_arg("span", span, 0, FLICKER_SPAN_MAX)
+    max_shift = _int_arg("max_shift", max_shift, 1, FLICKER_SHIFT_MAX)
+    hs, sc = _device_inputs([("hist", hist, torch.int32), ("scene", scene, torch.int32)], "hist")
     if hs.dim() != 2 or hs.shape[1] != 256:
         raise ValueError("hist must be int32 [L,256], got %s" % (tuple(hs.shape),))
     L = int(hs.shape[0])
-    if tuple(sc.shape) != (L,):
-        raise ValueError("scene must be int32 [%d], got %s" % (L, tuple(sc.shape)))
+    _scene_table(sc, "scene", L)
     with torch.cuda.device(hs.device):
         work = L > 0 and N > 0                           # with work the launch writes every entry
-        Q = (torch.empty if work else torch.zeros)((L, FLICKER_NODES), dtype=torch.int32, device=hs.device)
-        d = (torch.empty if work else torch.zeros)((L, 256), dtype=torch.int16, device=hs.device)
+        Q = _alloc(work, (L, FLICKER_NODES), torch.int32, hs.device)
+        d = _alloc(work, (L, 256), torch.int16, hs.device)
         _L.check(lib.e2fgvi_flicker_curves(_ptr(hs), _ptr(sc), _ptr(Q), _ptr(d), L, N, span, max_shift, _stream()), "flicker_curves")
     return Q, d
 
@@ -2365,10 +2346,8 @@ def flicker_apply(frames, d, out=None):
     itself for in place, otherwise one that does not overlap it (the entry refuses any other overlap); every byte is written once.
     The checks of flicker_hist; no host read; exact integers."""
     lib = _L.load()
-    if out is not None and not (isinstance(out, torch.Tensor) and out.is_cuda):
-        raise ValueError("out is written: it must be a device tensor, got %s" % type(out).__name__)
     named = [("frames", frames, torch.uint8), ("d", d, torch.int16)] + ([("out", out, torch.uint8)] if out is not None else [])
-    up = _defect_inputs(named, "frames")
+    up = _device_inputs(named, "frames", written=("out",))
     fr, dd = up[:2]
     L, H, W = _flicker_frames(fr)
     if tuple(dd.shape) != (L, 256):

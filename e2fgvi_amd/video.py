@@ -473,6 +473,120 @@ def track_regions(masks_u8, frame_wh, size, neighbor_stride=5, ref_length=10, nu
     return plan_track(boxes, plan_windows(len(boxes), neighbor_stride, ref_length, num_ref, scenes), frame_wh, size, context)
 
 
+# What the tools below share ("the shape of a tool"): every check that needs the arguments and the shapes alone, the
+# choice of the device, the tables that go up in front of the first launch, and the form of the result.
+def _is_u8(a, also_bool=False):
+    return str(getattr(a, "dtype", "")) in (("uint8", "torch.uint8", "bool", "torch.bool") if also_bool else ("uint8", "torch.uint8"))
+
+
+def _check_frames(frames, dtype, name="frames"):
+    """``frames`` -- the frames, or their shape where a check has no more -- as uint8 [L,H,W,3] -> the shape as a tuple.  ``dtype``:
+    whether the element type is looked at as well (match_grain, detect_line_scratches, deflicker) or the shape alone (the
+    others, which leave the element type to the upload and the kernels' wrappers).  ValueError that names ``name`` otherwise."""
+    shape = tuple(frames) if isinstance(frames, tuple) else tuple(getattr(frames, "shape", ()))
+    if len(shape) != 4 or shape[3] != 3 or (dtype and not _is_u8(frames)):
+        raise ValueError("%s must be uint8 [L,H,W,3], got %s %s"
+                         % (name, getattr(frames, "dtype", type(frames).__name__) if dtype else "shape", shape))
+    return shape
+
+
+def _scene_cuts(scenes, length):
+    """scenes= of a tool as the list of cuts: None is no cut, a list is _check_scenes's, and a string is refused ("auto" is
+    inpaint_video's alone)"""
+    if isinstance(scenes, str):
+        raise ValueError("scenes must be None or a list of frame numbers, got %r" % (scenes,))
+    return [] if scenes is None else _check_scenes(scenes, length)
+
+
+def _scene_table(cuts, length):
+    """the scene number of every frame, int32 [length], from the list of cuts"""
+    scene_of = np.zeros(length, np.int32)
+    for c in cuts:
+        scene_of[c:] += 1
+    return scene_of
+
+
+def _check_ranges(*rows):
+    """rows of (name, value, lo, hi) -> the values as ints; one that is no integer in [lo, hi] (a bool is none, 2.0 is one) raises
+    a ValueError that names it"""
+    for name, v, lo, hi in rows:
+        if not _integer(v, lo, hi):
+            raise ValueError("%s must be an integer in [%d, %d], got %r" % (name, lo, hi, v))
+    return tuple(int(v) for _, v, _, _ in rows)
+
+
+def _check_flags(**flags):
+    """name=value of the arguments that must be bools (True and False alone, not 0 / 1); ValueError that names the first that is not"""
+    for name, v in flags.items():
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError("%s must be a bool, got %r" % (name, v))
+
+
+def _check_fraction(max_fraction):
+    """max_fraction= as a float in (0, 1]; ValueError otherwise (bools included)"""
+    try:
+        ok = not isinstance(max_fraction, (bool, np.bool_)) and 0 < max_fraction <= 1
+    except TypeError:
+        ok = False
+    if not ok:
+        raise ValueError("max_fraction must be in (0, 1], got %r" % (max_fraction,))
+    return float(max_fraction)
+
+
+def _check_flow_source(model, flows, shape, size, follow):
+    """Where a tool's flows come from, from the arguments alone: ``flows`` = (fwd, bwd) must fit frames of ``shape`` after ``size``
+    (_check_flows, ValueError); without them the model's SPyNet computes them, so ``model`` must be the generator (TypeError;
+    ``follow`` says what the tool does along the flows)."""
+    if flows is not None:
+        _check_flows(flows, shape, size)
+    elif not callable(getattr(model, "engine", None)):
+        raise TypeError("without flows= %s the flows of the model's SPyNet (metrics.video_flows): that needs the "
+                        "InpaintGenerator, got %s" % (follow, type(model).__name__))
+
+
+def _device_flows(model, frames, flows):
+    """(fwd, bwd) on the device of ``frames``: the caller's ``flows``, or the net's own between these frames"""
+    from . import metrics
+    if flows is None:
+        return metrics.video_flows(model, frames)
+    return tuple(metrics._device_tensor(f, frames.device) for f in flows)
+
+
+def _tool_device(tool, device, like=None, model=None):
+    """The device a tool runs on: ``device`` when given, else that of ``like`` when it is a device tensor, else that of the model's
+    parameters, else the default cuda device.  Anything but a cuda device is a RuntimeError that names the tool."""
+    if device is None:
+        if isinstance(like, torch.Tensor) and like.is_cuda:
+            device = like.device
+        else:
+            device = next(model.parameters()).device if hasattr(model, "parameters") else torch.device("cuda")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("%s runs on the MI355X (cuda) device only; there is no CPU path" % tool)
+    return device
+
+
+def _like_input(like, *results):
+    """the results as the caller gets them: device tensors when ``like``, the input that decides, is one, numpy arrays otherwise
+    (None stays None)"""
+    if isinstance(like, torch.Tensor) and like.is_cuda:
+        return results
+    return tuple(r.cpu().numpy() if r is not None else None for r in results)
+
+
+def _job_table(steps, device):
+    """the jobs of all steps of a chain plan as one device int32 [n,2]: one upload, made in front of the first launch"""
+    return torch.tensor([j for s in steps for j in s], dtype=torch.int32).reshape(-1, 2).to(device)
+
+
+def _step_jobs(table, steps):
+    """_job_table's rows step by step, in the plan's order"""
+    at = 0
+    for s in steps:
+        yield table[at:at + len(s)]
+        at += len(s)
+
+
 SCENE_THRESHOLD = 0.35     # cuts_from_scores: DESIGN.md 3j has the measurements it was chosen from
 SCENE_MIN_LENGTH = 5       # frames; one window step of the default neighbor_stride
 
@@ -485,9 +599,7 @@ def scene_scores(frames_u8, device=None):
     (ops.scene_diff: one pass over the frames, exact integers, and one host copy of L - 1 of them).  Motion inside a cell leaves
     the score alone, motion across cells and changes of brightness raise it: 0 for two frames with the same counters, 1 for two
     that share no luma bin in any cell.  L < 2 returns an empty array without a launch."""
-    if len(frames_u8.shape) != 4 or frames_u8.shape[3] != 3:
-        raise ValueError("frames must be uint8 [L,H,W,3], got %s" % (tuple(frames_u8.shape),))
-    L, H, W = (int(v) for v in frames_u8.shape[:3])
+    L, H, W = (int(v) for v in _check_frames(tuple(frames_u8.shape), False)[:3])
     if L < 2:
         return np.zeros(0, np.float64)
     x = _upload(frames_u8, device)
@@ -538,21 +650,12 @@ OVERLAY_MAX_FRACTION = 0.25
 
 
 def _check_overlay_args(g_min, coherence, radius, min_area, max_fraction):
-    if not _integer(g_min, 1, 2 ** 31 - 1):
-        raise ValueError("g_min must be an integer >= 1, got %r" % (g_min,))
-    if not _integer(coherence, 1, 256):
-        raise ValueError("coherence must be an integer in (0, 256], got %r" % (coherence,))
-    if not _integer(radius, 0, ops.OVERLAY_RADIUS_MAX):
-        raise ValueError("radius must be an integer in [0, %d], got %r" % (ops.OVERLAY_RADIUS_MAX, radius))
-    if not _integer(min_area, 1):
+    g_min, coherence, radius = _check_ranges(("g_min", g_min, 1, 2 ** 31 - 1), ("coherence", coherence, 1, 256),
+                                             ("radius", radius, 0, ops.OVERLAY_RADIUS_MAX))
+    if not _integer(min_area, 1):                       # its own: an area has no upper bound
         raise ValueError("min_area must be an integer >= 1, got %r" % (min_area,))
-    try:
-        ok = not isinstance(max_fraction, (bool, np.bool_)) and 0 < max_fraction <= 1
-    except TypeError:
-        ok = False
-    if not ok:
-        raise ValueError("max_fraction must be in (0, 1], got %r" % (max_fraction,))
-    return int(g_min), int(coherence), int(radius), int(min_area)
+    _check_fraction(max_fraction)
+    return g_min, coherence, radius, int(min_area)
 
 
 def _overlay_mask_device(x, g_min, coherence, radius, min_area, max_fraction):
@@ -598,9 +701,7 @@ def overlay_mask(frames_u8, g_min=OVERLAY_G_MIN, coherence=OVERLAY_COHERENCE, ra
     g_min >= 1, 0 < coherence <= 256, 0 <= radius <= 16, min_area >= 1: integers; 0 < max_fraction <= 1; no bools (ValueError,
     before any device work).  L = 0 raises ValueError; H W = 0 returns an empty array without a launch."""
     g_min, coherence, radius, min_area = _check_overlay_args(g_min, coherence, radius, min_area, max_fraction)
-    if len(frames_u8.shape) != 4 or frames_u8.shape[3] != 3:
-        raise ValueError("frames must be uint8 [L,H,W,3], got %s" % (tuple(frames_u8.shape),))
-    L, H, W = (int(v) for v in frames_u8.shape[:3])
+    L, H, W = (int(v) for v in _check_frames(tuple(frames_u8.shape), False)[:3])
     if L < 1:
         raise ValueError("overlay_mask needs at least one frame, got %d" % L)
     if H * W == 0:
@@ -662,9 +763,8 @@ def plan_mask_chains(length, keys, scenes=None, reach=None):
 def _propagate_masks_device(model, x, key_masks, keys, steps, flows, size, check):
     """propagate_masks after the argument checks and the upload of the frames: x uint8 [L,H,W,3] on the device, steps the plan of
     plan_mask_chains -> device uint8 [L,h,w] of 0 / 1"""
-    from . import metrics
     # the job tables of all steps in one upload, and the key frames' numbers, in front of the first launch
-    table = torch.tensor([j for s in steps for j in s], dtype=torch.int32).reshape(-1, 2).to(x.device)
+    table = _job_table(steps, x.device)
     key_ids = torch.tensor(keys, dtype=torch.int64).to(x.device)
     if size is not None:
         x = resize_frames(x, size)
@@ -676,14 +776,9 @@ def _propagate_masks_device(model, x, key_masks, keys, steps, flows, size, check
         planes = torch.zeros((2, L, h, w), dtype=torch.uint8, device=x.device)
         planes[:, key_ids] = km
         if steps:
-            if flows is None:
-                fwd, bwd = metrics.video_flows(model, x)
-            else:
-                fwd, bwd = (metrics._device_tensor(f, x.device) for f in flows)
-            at = 0
-            for s in steps:
-                ops.mask_track_step(planes, fwd, bwd, table[at:at + len(s)], check)
-                at += len(s)
+            fwd, bwd = _device_flows(model, x, flows)
+            for jobs in _step_jobs(table, steps):
+                ops.mask_track_step(planes, fwd, bwd, jobs, check)
         return planes[0] | planes[1]
 
 
@@ -713,27 +808,17 @@ def _check_flows(flows, shape, size):
 
 def _check_propagate_args(model, shape, key_masks, keys, flows, size, scenes, reach, check, name="keys"):
     """the checks of propagate_masks from the arguments and the shapes alone (shape: that of the RGB frames) -> (keys, steps)"""
-    if len(shape) != 4 or shape[3] != 3:
-        raise ValueError("frames must be uint8 [L,H,W,3], got %s" % (tuple(shape),))
-    L = int(shape[0])
+    L = int(_check_frames(tuple(shape), False)[0])
     if L < 1:
         raise ValueError("frames: at least one frame is needed, got %s" % (tuple(shape),))
     keys = _check_keys(keys, L, name)
     if len(getattr(key_masks, "shape", ())) != 3 or key_masks.shape[0] != len(keys):
         raise ValueError("key_masks must be uint8 [K,Hm,Wm] with one mask for each of the K = %d frames of %s, got %s"
                          % (len(keys), name, tuple(getattr(key_masks, "shape", ())) or type(key_masks).__name__))
-    if not isinstance(check, (bool, np.bool_)):
-        raise ValueError("check must be a bool, got %r" % (check,))
+    _check_flags(check=check)
     _check_size(size)
-    if isinstance(scenes, str):
-        raise ValueError("scenes must be None or a list of frame numbers, got %r" % (scenes,))
-    steps = plan_mask_chains(L, keys, scenes, reach)
-    if flows is None:
-        if not callable(getattr(model, "engine", None)):
-            raise TypeError("without flows= the masks follow the flows of the model's SPyNet (metrics.video_flows): that needs the "
-                            "InpaintGenerator, got %s" % type(model).__name__)
-    else:
-        _check_flows(flows, shape, size)
+    steps = plan_mask_chains(L, keys, _scene_cuts(scenes, L), reach)
+    _check_flow_source(model, flows, shape, size, "the masks follow")
     return keys, steps
 
 
@@ -814,9 +899,7 @@ def plan_pixel_chains(length, scenes=None):
 
 def _check_pixel_args(model, shape, masks_u8, filled_u8, flows, size, dilate, scenes, reach, check, return_source):
     """the checks of propagate_pixels from the arguments and the shapes alone (shape: that of the frames) -> (steps, reach)"""
-    if len(shape) != 4 or shape[3] != 3:
-        raise ValueError("frames must be uint8 [L,H,W,3], got %s" % (tuple(shape),))
-    L = int(shape[0])
+    L = int(_check_frames(tuple(shape), False)[0])
     if L < 1:
         raise ValueError("frames: at least one frame is needed, got %s" % (tuple(shape),))
     if tuple(getattr(filled_u8, "shape", ())) != tuple(shape):
@@ -825,31 +908,22 @@ def _check_pixel_args(model, shape, masks_u8, filled_u8, flows, size, dilate, sc
     if len(getattr(masks_u8, "shape", ())) != 3 or masks_u8.shape[0] != L:
         raise ValueError("masks must be uint8 [%d,Hm,Wm], one for each frame, got %s"
                          % (L, tuple(getattr(masks_u8, "shape", ())) or type(masks_u8).__name__))
-    for name, v in (("dilate", dilate), ("check", check), ("return_source", return_source)):
-        if not isinstance(v, (bool, np.bool_)):
-            raise ValueError("%s must be a bool, got %r" % (name, v))
+    _check_flags(dilate=dilate, check=check, return_source=return_source)
     _check_size(size)
-    if isinstance(scenes, str):
-        raise ValueError("scenes must be None or a list of frame numbers, got %r" % (scenes,))
-    steps = plan_pixel_chains(L, scenes)
+    steps = plan_pixel_chains(L, _scene_cuts(scenes, L))
     if reach is not None and not _integer(reach, 1, ops.PIXEL_REACH_MAX, typed=True):
         raise ValueError("reach must be None or an integer in [1, %d], got %r" % (ops.PIXEL_REACH_MAX, reach))
-    if flows is None:
-        if not callable(getattr(model, "engine", None)):
-            raise TypeError("without flows= the pixels follow the flows of the model's SPyNet (metrics.video_flows): that needs the "
-                            "InpaintGenerator, got %s" % type(model).__name__)
-    else:
-        _check_flows(flows, shape, None)                # at the frames' own size: size= is the model's, not the flows'
+    # the flows at the frames' own size: size= is the model's, not the flows'
+    _check_flow_source(model, flows, shape, None, "the pixels follow")
     return steps, ops.PIXEL_REACH_MAX if reach is None else int(reach)
 
 
 def _propagate_pixels_device(model, x, masks_u8, filled, steps, flows, size, dilate, reach, check, return_source):
     """propagate_pixels after the argument checks and the uploads: x and filled uint8 [L,H,W,3] on the device -> (out, source or
     None) on the device; ``filled`` is not written"""
-    from . import metrics
     L, H, W = (int(v) for v in x.shape[:3])
     # the job tables of all steps in one upload, in front of the first launch
-    table = torch.tensor([j for s in steps for j in s], dtype=torch.int32).reshape(-1, 2).to(x.device)
+    table = _job_table(steps, x.device)
     out = filled.clone()
     with torch.cuda.device(x.device):
         if H * W == 0:
@@ -858,16 +932,11 @@ def _propagate_pixels_device(model, x, masks_u8, filled, steps, flows, size, dil
         # nothing to fetch from (every scene a single frame), or -- the one host read -- no hole pixel: no flows and no launch
         if not steps or not bool(hole.any()):
             return out, hole * 3 if return_source else None
-        if flows is None:
-            fwd, bwd = metrics.video_flows(model, filled)
-        else:
-            fwd, bwd = (metrics._device_tensor(f, x.device) for f in flows)
+        fwd, bwd = _device_flows(model, filled, flows)    # of the completed frames, not of x
         age = (hole * 255).unsqueeze(0).repeat(2, 1, 1, 1)
         origin = torch.empty((2, L, H, W, 2), dtype=torch.float32, device=x.device)
-        at = 0
-        for s in steps:
-            ops.pixel_track_step(hole, age, origin, fwd, bwd, table[at:at + len(s)], reach, check)
-            at += len(s)
+        for jobs in _step_jobs(table, steps):
+            ops.pixel_track_step(hole, age, origin, fwd, bwd, jobs, reach, check)
         if return_source:
             return ops.pixel_fill(x, hole, age, origin, out, True)
         return ops.pixel_fill(x, hole, age, origin, out), None
@@ -911,17 +980,10 @@ def propagate_pixels(model, frames_u8, masks_u8, filled_u8, flows=None, size=Non
     errors are ValueErrors that name the argument, raised before any device work.  There is no CPU path."""
     shape = tuple(frames_u8.shape)
     steps, reach = _check_pixel_args(model, shape, masks_u8, filled_u8, flows, size, dilate, scenes, reach, check, return_source)
-    as_tensor = isinstance(filled_u8, torch.Tensor) and filled_u8.is_cuda
-    if device is None:
-        device = filled_u8.device if as_tensor else next(model.parameters()).device if hasattr(model, "parameters") \
-            else torch.device("cuda")
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError("propagate_pixels runs on the MI355X (cuda) device only; there is no CPU path")
+    device = _tool_device("propagate_pixels", device, filled_u8, model)
     out, source = _propagate_pixels_device(model, _upload(frames_u8, device), masks_u8, _upload(filled_u8, device), steps, flows, size,
                                            bool(dilate), reach, bool(check), bool(return_source))
-    if not as_tensor:
-        out, source = out.cpu().numpy(), source.cpu().numpy() if source is not None else None
+    out, source = _like_input(filled_u8, out, source)
     return (out, source) if return_source else out
 
 
@@ -932,16 +994,10 @@ _GRAIN_SCALE_PER_SIGMA = 65536.0 / math.sqrt(_GRAIN_VARIANCE)
 _GRAIN_SIGMA_PER_SCALE = math.sqrt(_GRAIN_VARIANCE) / 65536.0
 
 
-def _is_u8(a, also_bool=False):
-    return str(getattr(a, "dtype", "")) in (("uint8", "torch.uint8", "bool", "torch.bool") if also_bool else ("uint8", "torch.uint8"))
-
-
 def _check_grain_args(frames_u8, filled_u8, where, hole, scenes, strength, seed, levels, return_levels):
     """the checks of match_grain from the arguments and the shapes alone -> (scene_of int32 [L], the number of scenes, strength in
     1 / 256, the scale int64 [S,8,3] of levels= or None)"""
-    shape = tuple(getattr(filled_u8, "shape", ()))
-    if len(shape) != 4 or shape[3] != 3 or not _is_u8(filled_u8):
-        raise ValueError("filled_u8 must be uint8 [L,H,W,3], got %s %s" % (getattr(filled_u8, "dtype", type(filled_u8).__name__), shape))
+    shape = _check_frames(filled_u8, True, "filled_u8")
     L = int(shape[0])
     if frames_u8 is None:
         if levels is None:
@@ -955,9 +1011,7 @@ def _check_grain_args(frames_u8, filled_u8, where, hole, scenes, strength, seed,
         if tuple(getattr(m, "shape", ())) != shape[:3] or not _is_u8(m, also_bool=True):
             raise ValueError("%s must be uint8 or bool %s, got %s %s"
                              % (name, list(shape[:3]), getattr(m, "dtype", type(m).__name__), tuple(getattr(m, "shape", ()))))
-    if isinstance(scenes, str):
-        raise ValueError("scenes must be None or a list of frame numbers, got %r" % (scenes,))
-    cuts = _check_scenes(scenes, L) if scenes is not None else []
+    cuts = _scene_cuts(scenes, L)
     try:
         ok = isinstance(strength, (int, float, np.integer, np.floating)) and not isinstance(strength, (bool, np.bool_)) \
             and 0.0 <= float(strength) <= GRAIN_STRENGTH_MAX
@@ -967,8 +1021,7 @@ def _check_grain_args(frames_u8, filled_u8, where, hole, scenes, strength, seed,
         raise ValueError("strength must be a number in [0, %g], got %r" % (GRAIN_STRENGTH_MAX, strength))
     if not _integer(seed, 0, (1 << 32) - 1, typed=True):
         raise ValueError("seed must be an integer in [0, 2^32), got %r" % (seed,))
-    if not isinstance(return_levels, (bool, np.bool_)):
-        raise ValueError("return_levels must be a bool, got %r" % (return_levels,))
+    _check_flags(return_levels=return_levels)
     S = len(cuts) + 1
     scale = None
     if levels is not None:
@@ -980,10 +1033,7 @@ def _check_grain_args(frames_u8, filled_u8, where, hole, scenes, strength, seed,
             raise ValueError("levels must be None or sigma in grey levels, finite floats in [0, %g] of shape [8,3] or [%d,8,3] (one "
                              "per scene), got %s" % (GRAIN_SIGMA_MAX, S, sig.shape if sig.size else type(levels).__name__))
         scale = np.broadcast_to(np.floor(sig * _GRAIN_SCALE_PER_SIGMA + 0.5).astype(np.int64), (S, 8, 3)).copy()
-    scene_of = np.zeros(L, np.int32)
-    for c in cuts:
-        scene_of[c:] += 1
-    return scene_of, S, int(math.floor(256.0 * float(strength) + 0.5)), scale
+    return _scene_table(cuts, L), S, int(math.floor(256.0 * float(strength) + 0.5)), scale
 
 
 def _grain_plane(m, device):
@@ -1052,19 +1102,12 @@ def match_grain(frames_u8, filled_u8, where, hole=None, scenes=None, strength=1.
     propagate_pixels fetched has lost part of its grain to the bilinear sample, and is left alone by where=(source == 3).
     Argument errors are ValueErrors that name the argument, raised before any device work.  There is no CPU path."""
     scene_of, n_scenes, q8, scale = _check_grain_args(frames_u8, filled_u8, where, hole, scenes, strength, seed, levels, return_levels)
-    as_tensor = isinstance(filled_u8, torch.Tensor) and filled_u8.is_cuda
-    if device is None:
-        device = filled_u8.device if as_tensor else torch.device("cuda")
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError("match_grain runs on the MI355X (cuda) device only; there is no CPU path")
+    device = _tool_device("match_grain", device, filled_u8)
     filled = _upload(filled_u8, device)
     x = _upload(frames_u8, device) if frames_u8 is not None and scale is None else None
     out, scale_d = _match_grain_device(x, filled, _grain_plane(where, device), None if hole is None else _grain_plane(hole, device),
                                        scene_of, n_scenes, q8, int(seed), scale, bool(return_levels))
-    sigma = scale_d.to(torch.float64) * _GRAIN_SIGMA_PER_SCALE if return_levels else None
-    if not as_tensor:
-        out, sigma = out.cpu().numpy(), sigma.cpu().numpy() if sigma is not None else None
+    out, sigma = _like_input(filled_u8, out, scale_d.to(torch.float64) * _GRAIN_SIGMA_PER_SCALE if return_levels else None)
     return (out, sigma) if return_levels else out
 
 
@@ -1088,24 +1131,15 @@ def plan_defect_frames(length, scenes=None):
 
 
 def _check_defect_args(threshold, slack, support, radius, max_fraction):
-    for name, v, lo, hi in (("threshold", threshold, 0, ops.DEFECT_THRESHOLD_MAX), ("slack", slack, 0, ops.DEFECT_SLACK_MAX),
-                            ("support", support, 1, 9), ("radius", radius, 0, ops.DEFECT_RADIUS_MAX)):
-        if not _integer(v, lo, hi):
-            raise ValueError("%s must be an integer in [%d, %d], got %r" % (name, lo, hi, v))
-    try:
-        ok = not isinstance(max_fraction, (bool, np.bool_)) and 0 < max_fraction <= 1
-    except TypeError:
-        ok = False
-    if not ok:
-        raise ValueError("max_fraction must be in (0, 1], got %r" % (max_fraction,))
-    return int(threshold), int(slack), int(support), int(radius), float(max_fraction)
+    ints = _check_ranges(("threshold", threshold, 0, ops.DEFECT_THRESHOLD_MAX), ("slack", slack, 0, ops.DEFECT_SLACK_MAX),
+                         ("support", support, 1, 9), ("radius", radius, 0, ops.DEFECT_RADIUS_MAX))
+    return ints + (_check_fraction(max_fraction),)
 
 
 def _detect_defects_device(model, x, ids, flows, size, threshold, slack, support, radius, max_fraction):
     """detect_defects after the argument checks and the upload of the frames: x uint8 [L,H,W,3] on the device, ids the centre
     frames of plan_defect_frames -> (masks, counts): device uint8 [L,h,w] of 0 / 255 with the frames over the guard cleared, and
     device int32 [L], the counts as they were before the guard.  No host read."""
-    from . import metrics
     ids_d = torch.tensor(ids, dtype=torch.int32).to(x.device) if ids else None      # in front of the first launch
     if size is not None:
         x = resize_frames(x, size)
@@ -1113,10 +1147,7 @@ def _detect_defects_device(model, x, ids, flows, size, threshold, slack, support
     if ids_d is None or h * w == 0:
         return torch.zeros((L, h, w), dtype=torch.uint8, device=x.device), torch.zeros(L, dtype=torch.int32, device=x.device)
     with torch.cuda.device(x.device):
-        if flows is None:
-            fwd, bwd = metrics.video_flows(model, x)
-        else:
-            fwd, bwd = (metrics._device_tensor(f, x.device) for f in flows)
+        fwd, bwd = _device_flows(model, x, flows)
         cand = ops.defect_candidates(x, fwd, bwd, ids_d, threshold, slack)
         masks, counts = ops.defect_clean(cand, ids_d, support, radius)
         # the frame guard, on the device: a frame that differs from both neighbours nearly everywhere is no dirt
@@ -1126,21 +1157,11 @@ def _detect_defects_device(model, x, ids, flows, size, threshold, slack, support
 
 def _check_detect_args(model, shape, flows, size, scenes, return_counts):
     """the checks of detect_defects from the arguments and the shapes alone (shape: that of the RGB frames) -> the centre frames"""
-    if len(shape) != 4 or shape[3] != 3:
-        raise ValueError("frames must be uint8 [L,H,W,3], got %s" % (tuple(shape),))
-    L = int(shape[0])
-    if not isinstance(return_counts, (bool, np.bool_)):
-        raise ValueError("return_counts must be a bool, got %r" % (return_counts,))
+    L = int(_check_frames(tuple(shape), False)[0])
+    _check_flags(return_counts=return_counts)
     _check_size(size)
-    if isinstance(scenes, str):
-        raise ValueError("scenes must be None or a list of frame numbers, got %r" % (scenes,))
-    ids = plan_defect_frames(L, scenes)
-    if flows is None:
-        if not callable(getattr(model, "engine", None)):
-            raise TypeError("without flows= the neighbours are reached along the flows of the model's SPyNet (metrics.video_flows): "
-                            "that needs the InpaintGenerator, got %s" % type(model).__name__)
-    else:
-        _check_flows(flows, shape, size)
+    ids = plan_defect_frames(L, _scene_cuts(scenes, L))
+    _check_flow_source(model, flows, shape, size, "the neighbours are reached along")
     return ids
 
 
@@ -1171,8 +1192,9 @@ def detect_defects(model, frames_u8, flows=None, size=None, scenes=None, thresho
     frame still shows.  L < 3 or no eligible frame: empty masks without a launch and without computing flows.
 
     Known limits: defects that last longer than one frame (vertical line scratches, flicker) are no temporal spikes and are not
-    found (detect_line_scratches finds the scratches, deflicker takes the flicker out beforehand); an object that appears for a single frame is dirt to this test; a blotch bends the very flow that is supposed to see
-    past it, and what a trained SPyNet does around one has not been measured here.
+    found (detect_line_scratches finds the scratches, deflicker takes the flicker out beforehand); an object that appears for a
+    single frame is dirt to this test; a blotch bends the very flow that is supposed to see past it, and what a trained SPyNet
+    does around one has not been measured here.
     threshold in [0, 254], slack in [0, 2], support in [1, 9], radius in [0, 16]: integers; 0 < max_fraction <= 1; return_counts a
     bool; no bools elsewhere; a string for ``scenes`` is refused.  Argument errors are ValueErrors that name the argument, raised
     before any device work."""
@@ -1204,26 +1226,15 @@ LINE_RADIUS = 2
 
 def _check_line_args(frames_u8, scenes, rows, tau, gap, side, drift, coverage, span, persist, radius, return_counts):
     """the checks of detect_line_scratches from the arguments and the shapes alone -> (scene_of int32 [L], the nine integers)"""
-    shape = tuple(getattr(frames_u8, "shape", ()))
-    if len(shape) != 4 or shape[3] != 3 or not _is_u8(frames_u8):
-        raise ValueError("frames must be uint8 [L,H,W,3], got %s %s" % (getattr(frames_u8, "dtype", type(frames_u8).__name__), shape))
-    L = int(shape[0])
-    if isinstance(scenes, str):
-        raise ValueError("scenes must be None or a list of frame numbers, got %r" % (scenes,))
-    cuts = _check_scenes(scenes, L) if scenes is not None else []
-    ranges = (("rows", rows, ops.LINE_ROWS_MIN, ops.LINE_ROWS_MAX), ("tau", tau, 0, ops.LINE_TAU_MAX), ("gap", gap, 0, ops.LINE_GAP_MAX),
-              ("side", side, 1, ops.LINE_SIDE_MAX), ("drift", drift, 0, ops.LINE_DRIFT_MAX), ("coverage", coverage, 1, 100),
-              ("span", span, 0, ops.LINE_SPAN_MAX))
-    for name, v, lo, hi in ranges + (("persist", persist, 1, 2 * int(span) + 1 if _integer(span, 0, ops.LINE_SPAN_MAX) else 1),
-                                     ("radius", radius, 0, ops.LINE_RADIUS_MAX)):
-        if not _integer(v, lo, hi):
-            raise ValueError("%s must be an integer in [%d, %d], got %r" % (name, lo, hi, v))
-    if not isinstance(return_counts, (bool, np.bool_)):
-        raise ValueError("return_counts must be a bool, got %r" % (return_counts,))
-    scene_of = np.zeros(L, np.int32)
-    for c in cuts:
-        scene_of[c:] += 1
-    return scene_of, tuple(int(v) for v in (rows, tau, gap, side, drift, coverage, span, persist, radius))
+    L = int(_check_frames(frames_u8, True)[0])
+    cuts = _scene_cuts(scenes, L)
+    params = _check_ranges(("rows", rows, ops.LINE_ROWS_MIN, ops.LINE_ROWS_MAX), ("tau", tau, 0, ops.LINE_TAU_MAX),
+                           ("gap", gap, 0, ops.LINE_GAP_MAX), ("side", side, 1, ops.LINE_SIDE_MAX), ("drift", drift, 0, ops.LINE_DRIFT_MAX),
+                           ("coverage", coverage, 1, 100), ("span", span, 0, ops.LINE_SPAN_MAX))
+    # its own: the bound of persist follows span, which the row above has checked
+    params += _check_ranges(("persist", persist, 1, 2 * params[6] + 1), ("radius", radius, 0, ops.LINE_RADIUS_MAX))
+    _check_flags(return_counts=return_counts)
+    return _scene_table(cuts, L), params
 
 
 def _detect_line_scratches_device(x, scene_of, rows, tau, gap, side, drift, coverage, span, persist, radius):
@@ -1263,19 +1274,15 @@ def detect_line_scratches(frames_u8, scenes=None, rows=LINE_ROWS, tau=LINE_TAU, 
 
     Known limits: a real thin vertical structure that moves less than about its own width plus 2 drift per frame
     -- a pole in a locked-off shot -- looks the same to a spatial test, persistence only rejects what moves faster; a scratch over
-    less than ``coverage`` per cent of the height, or slanted by more than +-drift columns over it, is not found; nor is flicker (deflicker
-    takes it out beforehand).
+    less than ``coverage`` per cent of the height, or slanted by more than +-drift columns over it, is not found; nor is flicker
+    (deflicker takes it out beforehand).
     Letterbox bars and logos have edges that read as scratches where they are vertical; there is no ``hole`` argument yet to
     keep them out.
     rows in [4, 64], tau in [0, 254], gap in [0, 4], side in [1, 8], drift in [0, 2], coverage in [1, 100], span in [0, 4],
     persist in [1, 2 span + 1], radius in [0, 16]: integers, no bools; return_counts a bool; a string for ``scenes`` is refused.
     Argument errors are ValueErrors that name the argument, raised before any device work.  There is no CPU path."""
     scene_of, params = _check_line_args(frames_u8, scenes, rows, tau, gap, side, drift, coverage, span, persist, radius, return_counts)
-    if device is None:
-        device = frames_u8.device if isinstance(frames_u8, torch.Tensor) and frames_u8.is_cuda else torch.device("cuda")
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError("detect_line_scratches runs on the MI355X (cuda) device only; there is no CPU path")
+    device = _tool_device("detect_line_scratches", device, frames_u8)
     masks, counts = _detect_line_scratches_device(_upload(frames_u8, device), scene_of, *params)
     masks, counts = masks.cpu().numpy(), counts.cpu().numpy()
     return (masks, counts) if return_counts else masks
@@ -1287,24 +1294,14 @@ FLICKER_MAX_SHIFT = 32
 
 def _check_flicker_args(frames_u8, scenes, span, max_shift, return_curves):
     """the checks of deflicker from the arguments and the shapes alone -> (scene_of int32 [L], span, max_shift)"""
-    shape = tuple(getattr(frames_u8, "shape", ()))
-    if len(shape) != 4 or shape[3] != 3 or not _is_u8(frames_u8):
-        raise ValueError("frames must be uint8 [L,H,W,3], got %s %s" % (getattr(frames_u8, "dtype", type(frames_u8).__name__), shape))
+    shape = _check_frames(frames_u8, True)
     L = int(shape[0])
-    if int(shape[1]) * int(shape[2]) > ops.FLICKER_PIXELS_MAX:
+    if int(shape[1]) * int(shape[2]) > ops.FLICKER_PIXELS_MAX:         # its own: a histogram bin is an int32
         raise ValueError("frames must have H W <= 2^26, got %d x %d" % (shape[1], shape[2]))
-    if isinstance(scenes, str):
-        raise ValueError("scenes must be None or a list of frame numbers, got %r" % (scenes,))
-    cuts = _check_scenes(scenes, L) if scenes is not None else []
-    for name, v, lo, hi in (("span", span, 0, ops.FLICKER_SPAN_MAX), ("max_shift", max_shift, 1, ops.FLICKER_SHIFT_MAX)):
-        if not _integer(v, lo, hi):
-            raise ValueError("%s must be an integer in [%d, %d], got %r" % (name, lo, hi, v))
-    if not isinstance(return_curves, (bool, np.bool_)):
-        raise ValueError("return_curves must be a bool, got %r" % (return_curves,))
-    scene_of = np.zeros(L, np.int32)
-    for c in cuts:
-        scene_of[c:] += 1
-    return scene_of, int(span), int(max_shift)
+    cuts = _scene_cuts(scenes, L)
+    span, max_shift = _check_ranges(("span", span, 0, ops.FLICKER_SPAN_MAX), ("max_shift", max_shift, 1, ops.FLICKER_SHIFT_MAX))
+    _check_flags(return_curves=return_curves)
+    return _scene_table(cuts, L), span, max_shift
 
 
 def _deflicker_device(x, scene_of, span, max_shift):
@@ -1353,15 +1350,8 @@ def deflicker(frames_u8, scenes=None, span=FLICKER_SPAN, max_shift=FLICKER_MAX_S
     span in [0, 8], max_shift in [1, 64]: integers, no bools; return_curves a bool; a string for ``scenes`` is refused; H W <=
     2^26.  Argument errors are ValueErrors that name the argument, raised before any device work.  There is no CPU path."""
     scene_of, span, max_shift = _check_flicker_args(frames_u8, scenes, span, max_shift, return_curves)
-    on_device = isinstance(frames_u8, torch.Tensor) and frames_u8.is_cuda
-    if device is None:
-        device = frames_u8.device if on_device else torch.device("cuda")
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError("deflicker runs on the MI355X (cuda) device only; there is no CPU path")
-    out, d = _deflicker_device(_upload(frames_u8, device), scene_of, span, max_shift)
-    if not on_device:
-        out, d = out.cpu().numpy(), d.cpu().numpy()
+    device = _tool_device("deflicker", device, frames_u8)
+    out, d = _like_input(frames_u8, *_deflicker_device(_upload(frames_u8, device), scene_of, span, max_shift))
     return (out, d) if return_curves else out
 
 
