@@ -38,8 +38,9 @@ UNITS = [("error.hip", "error.o", []), ("conv.hip", "conv.o", []), ("conv.hip", 
          ("pixel_track.hip", "pixel_track.o", NOPK + ["-ffp-contract=off"]),
          ("grain.hip", "grain.o", NOPK),
          ("line_scratch.hip", "line_scratch.o", NOPK),
-         ("flicker.hip", "flicker.o", NOPK)]
-NOPK_OBJECTS = ("conv_nopk.o", "conv_bf16x.o", "conv_wino.o", "conv_wino4.o", "conv_wino_x3.o", "conv_tail.o", "mdcn.o", "attention_bf16.o", "attention_x3.o", "misc.o", "video.o", "yuv.o", "metrics.o", "mask_track.o", "defects.o", "pixel_track.o", "grain.o", "line_scratch.o", "flicker.o")
+         ("flicker.hip", "flicker.o", NOPK),
+         ("weave.hip", "weave.o", NOPK)]
+NOPK_OBJECTS = ("conv_nopk.o", "conv_bf16x.o", "conv_wino.o", "conv_wino4.o", "conv_wino_x3.o", "conv_tail.o", "mdcn.o", "attention_bf16.o", "attention_x3.o", "misc.o", "video.o", "yuv.o", "metrics.o", "mask_track.o", "defects.o", "pixel_track.o", "grain.o", "line_scratch.o", "flicker.o", "weave.o")
 OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 
 
@@ -99,6 +100,7 @@ def build(force=False, verbose=False, nopk_all=False, lib=None, tag=None, define
             verify_no_scratch(objdir, "grain.o", "grain_", "film grain")
             verify_no_scratch(objdir, "line_scratch.o", "line_", "line scratch")
             verify_no_scratch(objdir, "flicker.o", "flicker_", "deflicker")
+            verify_no_scratch(objdir, "weave.o", "weave_", "weave stabiliser")
             verify_overlay_prefetch(objdir)
             verify_no_pk_u8(objdir)
             verify_no_fma64(objdir)
@@ -186,7 +188,8 @@ def verify_no_scratch(objdir=None, obj="conv_bf16x.o", marker="ELb0ELi2ELb1EEE",
     and over the two of pixel_track.o (the fill keeps the weights, offsets and flags of four corners in small arrays);
     and over the two of grain.o (the blocks pass keeps the 42 bytes of a thread's four Laplacians in small arrays);
     and over the four of line_scratch.o (the per-polarity counters of the columns pass are small arrays indexed in unrolled loops);
-    and over the three of flicker.o (the histogram and the apply kernel hold the dwords of all of a thread's groups at once)."""
+    and over the three of flicker.o (the histogram and the apply kernel hold the dwords of all of a thread's groups at once);
+    and over the five of weave.o (the apply kernel shifts the dwords of two tap rows into place in small arrays)."""
     import re
     import shutil
     import tempfile

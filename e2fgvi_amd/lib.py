@@ -158,6 +158,10 @@ SYMBOLS = {
     "e2fgvi_flicker_hist": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _fp]),
     "e2fgvi_flicker_curves": (C.c_int, [_fp] * 4 + [_i32] * 4 + [_fp]),
     "e2fgvi_flicker_apply": (C.c_int, [_fp, _fp, _fp, _i32, _i32, _i32, _fp]),
+    "e2fgvi_weave_profiles": (C.c_int, [_fp, _fp, _fp, _i32, _i32, _i32, _fp]),
+    "e2fgvi_weave_match": (C.c_int, [_fp] * 4 + [_i32] * 5 + [_fp]),
+    "e2fgvi_weave_path": (C.c_int, [_fp] * 3 + [_i32] * 4 + [_fp]),
+    "e2fgvi_weave_apply": (C.c_int, [_fp] * 4 + [_i32] * 4 + [_fp]),
     "e2fgvi_softcomp_fold": (C.c_int, [_fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _fp]),
     "e2fgvi_focal_attention_16": (C.c_int, [_fp, _fp, _fp, _i32, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _fp]),
     "e2fgvi_focal_attention_16_variant": (C.c_int, [C.c_int]),

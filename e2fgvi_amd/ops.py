@@ -2360,6 +2360,118 @@ def flicker_apply(frames, d, out=None):
     return ou
 
 
+WEAVE_BANDS = 8                            # csrc/weave.hip: bands per axis (WV_NB)
+WEAVE_RADIUS_MAX = 32                      # parameters outside these ranges are E2FGVI_EINVAL
+WEAVE_SPAN_MAX = 16
+WEAVE_SHIFT_MAX = 64
+WEAVE_TEX_MAX = 65535
+WEAVE_SIDE_MAX = 4096                      # H and W of the profiles and the match: a profile lives in LDS
+
+
+def _weave_sides(H, W, name="frames"):
+    if H > WEAVE_SIDE_MAX or W > WEAVE_SIDE_MAX:
+        raise ValueError("%s must have H and W <= %d, got %d x %d" % (name, WEAVE_SIDE_MAX, H, W))
+
+
+def weave_profiles(frames):
+    """The banded luma profiles of the weave stabiliser, one pass over the frames (csrc/weave.hip weave_profiles_kernel;
+    include/e2fgvi_hip.h has the definition; video.stabilize is the caller): frames uint8 [L,H,W,3] -> (col, row) on the device,
+    col int32 [L,WEAVE_BANDS,W] the sum of the integer luma over the rows of each band per column, row int32 [L,WEAVE_BANDS,H]
+    the sum over the columns of each band per row.  Device tensors, or anything torch.as_tensor accepts (uploaded first); a wrong
+    dtype or shape, a side above WEAVE_SIDE_MAX and a non-contiguous input raise ValueError.  There is no CPU path and no host
+    read; integer atomics: the same input gives the same bits in every run."""
+    lib = _L.load()
+    fr, = _device_inputs([("frames", frames, torch.uint8)], "frames")
+    L, H, W = _frames_shape(fr, "frames")
+    _weave_sides(H, W)
+    with torch.cuda.device(fr.device):
+        work = L > 0 and H > 0 and W > 0                 # with work the entry writes every word
+        col = _alloc(work, (L, WEAVE_BANDS, W), torch.int32, fr.device)
+        row = _alloc(work, (L, WEAVE_BANDS, H), torch.int32, fr.device)
+        _L.check(lib.e2fgvi_weave_profiles(_ptr(fr), _ptr(col), _ptr(row), L, H, W, _stream()), "weave_profiles")
+    return col, row
+
+
+def weave_match(col, row, scene, radius, tex):
+    """The motion of every pair of adjacent frames from their profiles, one launch (csrc/weave.hip weave_match_kernel;
+    include/e2fgvi_hip.h has the definition): col int32 [L,8,W] and row int32 [L,8,H] as weave_profiles made them, scene int32
+    [L], equal entries = one scene -> device int32 [L,4] = (mx, my, nx, ny): the motion of frame t against frame t - 1 in 1/16 px
+    per axis -- the lower median over the valid bands, 0 when fewer than half are valid -- and the number of valid bands per axis.
+    radius in [1, WEAVE_RADIUS_MAX], tex in [0, WEAVE_TEX_MAX]: integers, no bools.  No host read; exact integers."""
+    lib = _L.load()
+    radius = _int_arg("radius", radius, 1, WEAVE_RADIUS_MAX)
+    tex = _int_arg("tex", tex, 0, WEAVE_TEX_MAX)
+    cl, rw, sc = _device_inputs([("col", col, torch.int32), ("row", row, torch.int32), ("scene", scene, torch.int32)], "col")
+    if cl.dim() != 3 or cl.shape[1] != WEAVE_BANDS:
+        raise ValueError("col must be int32 [L,%d,W], got %s" % (WEAVE_BANDS, tuple(cl.shape)))
+    L, _, W = (int(v) for v in cl.shape)
+    if rw.dim() != 3 or tuple(rw.shape[:2]) != (L, WEAVE_BANDS):
+        raise ValueError("row must be int32 [%d,%d,H], got %s" % (L, WEAVE_BANDS, tuple(rw.shape)))
+    H = int(rw.shape[2])
+    _weave_sides(H, W, "col and row")
+    _scene_table(sc, "scene", L)
+    with torch.cuda.device(cl.device):
+        motion = _alloc(L > 0 and H > 0 and W > 0, (L, 4), torch.int32, cl.device)
+        _L.check(lib.e2fgvi_weave_match(_ptr(cl), _ptr(rw), _ptr(sc), _ptr(motion), L, H, W, radius, tex, _stream()), "weave_match")
+    return motion
+
+
+def weave_path(motion, scene, span, max_shift, subpixel=True):
+    """The correction of every frame from the pair motions, one launch (csrc/weave.hip weave_path_kernel; include/e2fgvi_hip.h
+    has the definition): motion int32 [L,4] as weave_match made it, scene int32 [L] -> device int32 [L,2] = (cx, cy) in 1/16 px:
+    the rounded mean of the path over the symmetric window of up to ``span`` frames either side inside the frame's segment, minus
+    the path, clamped to +-``max_shift`` px; whole pixels without ``subpixel``.  span in [0, WEAVE_SPAN_MAX], max_shift in [1,
+    WEAVE_SHIFT_MAX]: integers, no bools; subpixel a bool.  No host read; exact integers."""
+    lib = _L.load()
+    span = _int_arg("span", span, 0, WEAVE_SPAN_MAX)
+    max_shift = _int_arg("max_shift", max_shift, 1, WEAVE_SHIFT_MAX)
+    if not isinstance(subpixel, bool):
+        raise ValueError("subpixel must be a bool, got %r" % (subpixel,))
+    mo, sc = _device_inputs([("motion", motion, torch.int32), ("scene", scene, torch.int32)], "motion")
+    if mo.dim() != 2 or mo.shape[1] != 4:
+        raise ValueError("motion must be int32 [L,4], got %s" % (tuple(mo.shape),))
+    L = int(mo.shape[0])
+    _scene_table(sc, "scene", L)
+    with torch.cuda.device(mo.device):
+        shift = _alloc(L > 0, (L, 2), torch.int32, mo.device)
+        _L.check(lib.e2fgvi_weave_path(_ptr(mo), _ptr(sc), _ptr(shift), L, span, max_shift, int(subpixel), _stream()), "weave_path")
+    return shift
+
+
+def weave_apply(frames, shift, out=None, mask=None, return_mask=False):
+    """Frames moved by a shift per frame, one launch (csrc/weave.hip weave_apply_kernel; include/e2fgvi_hip.h has the definition):
+    frames uint8 [L,H,W,3] or [L,H,W], shift int32 [L,2] = (cx, cy) in 1/16 px (entries beyond +-16 WEAVE_SHIFT_MAX are clamped
+    to it) -> device uint8 of the same shape: the picture moved by (cx, cy) / 16 px, bilinear in 1/16 px with taps clamped to the
+    frame; a whole-pixel shift copies bytes.  With ``return_mask`` (or a ``mask`` to write into) the result is (out, mask), mask
+    uint8 [L,H,W], 255 where a tap of non-zero weight lay outside the frame.  ``out`` / ``mask``: device tensors to write into,
+    which must not overlap ``frames`` (the entry refuses it: a shifted read is not in order); every byte is written.  A wrong
+    dtype or shape, H W > 2^26 and a non-contiguous input raise ValueError.  No host read; exact integers."""
+    lib = _L.load()
+    named = [("frames", frames, torch.uint8), ("shift", shift, torch.int32)]
+    named += [(nm, v, torch.uint8) for nm, v in (("out", out), ("mask", mask)) if v is not None]
+    up = dict(zip([n[0] for n in named], _device_inputs(named, "frames", written=("out", "mask"))))
+    fr, sh = up["frames"], up["shift"]
+    if fr.dim() not in (3, 4) or (fr.dim() == 4 and fr.shape[3] != 3):
+        raise ValueError("frames must be [L,H,W,3] or [L,H,W], got %s" % (tuple(fr.shape),))
+    L, H, W = (int(v) for v in fr.shape[:3])
+    if H * W > FLICKER_PIXELS_MAX:
+        raise ValueError("frames must have H W <= 2^26, got %d x %d" % (H, W))
+    if tuple(sh.shape) != (L, 2):
+        raise ValueError("shift must be int32 [%d,2], got %s" % (L, tuple(sh.shape)))
+    if "out" in up and tuple(up["out"].shape) != tuple(fr.shape):
+        raise ValueError("out must be %s, got %s" % (list(fr.shape), tuple(up["out"].shape)))
+    if "mask" in up and tuple(up["mask"].shape) != (L, H, W):
+        raise ValueError("mask must be [%d,%d,%d], got %s" % (L, H, W, tuple(up["mask"].shape)))
+    with torch.cuda.device(fr.device):
+        ou = up["out"] if "out" in up else torch.empty_like(fr)
+        mk = up.get("mask")
+        if mk is None and return_mask:
+            mk = _alloc(L * H * W > 0, (L, H, W), torch.uint8, fr.device)
+        _L.check(lib.e2fgvi_weave_apply(_ptr(fr), _ptr(sh), _ptr(ou), _ptr(mk), L, H, W, 3 if fr.dim() == 4 else 1, _stream()),
+                 "weave_apply")
+    return (ou, mk) if mk is not None else ou
+
+
 YUV_LAYOUTS ={"nv12": 0, "i420": 1}     # E2FGVI_YUV_*/ E2FGVI_CHROMA_* of include/e2fgvi_hip.h
 YUV_CHROMA = {"left": 0, "nearest": 1}
 

@@ -1355,6 +1355,110 @@ def deflicker(frames_u8, scenes=None, span=FLICKER_SPAN, max_shift=FLICKER_MAX_S
     return (out, d) if return_curves else out
 
 
+WEAVE_SPAN = 4                 # stabilize's defaults: DESIGN.md 3v has the measurements they were judged on
+WEAVE_RADIUS = 16
+WEAVE_MAX_SHIFT = 16
+WEAVE_TEX = 2
+
+
+def _check_stabilize_args(frames_u8, scenes, span, radius, max_shift, tex, subpixel, return_shifts, return_mask):
+    """the checks of stabilize from the arguments and the shapes alone -> (scene_of int32 [L], span, radius, max_shift, tex)"""
+    shape = _check_frames(frames_u8, True)
+    L, H, W = (int(v) for v in shape[:3])
+    if H > ops.WEAVE_SIDE_MAX or W > ops.WEAVE_SIDE_MAX:                 # its own: a profile lives in LDS
+        raise ValueError("frames must have H and W <= %d, got %d x %d" % (ops.WEAVE_SIDE_MAX, H, W))
+    cuts = _scene_cuts(scenes, L)
+    span, radius, max_shift, tex = _check_ranges(("span", span, 0, ops.WEAVE_SPAN_MAX), ("radius", radius, 1, ops.WEAVE_RADIUS_MAX),
+                                                 ("max_shift", max_shift, 1, ops.WEAVE_SHIFT_MAX), ("tex", tex, 0, ops.WEAVE_TEX_MAX))
+    _check_flags(subpixel=subpixel, return_shifts=return_shifts, return_mask=return_mask)
+    return _scene_table(cuts, L), span, radius, max_shift, tex
+
+
+def _stabilize_device(x, scene_of, span, radius, max_shift, tex, subpixel, want_mask):
+    """stabilize after the argument checks and the upload of the frames: x uint8 [L,H,W,3] on the device -> (out uint8 [L,H,W,3],
+    shifts int32 [L,2], motion int32 [L,4], mask uint8 [L,H,W] or None) on the device.  Four launches, no host read.  Nothing to
+    do (span 0, no frame, no pixel): x itself and zeros."""
+    L, H, W = (int(v) for v in x.shape[:3])
+    if span == 0 or L == 0 or H * W == 0:
+        zeros = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=x.device)
+        return x, zeros(L, 2), zeros(L, 4), (torch.zeros((L, H, W), dtype=torch.uint8, device=x.device) if want_mask else None)
+    so = torch.from_numpy(scene_of).to(x.device)        # in front of the first launch
+    with torch.cuda.device(x.device):
+        col, row = ops.weave_profiles(x)
+        motion = ops.weave_match(col, row, so, radius, tex)
+        shifts = ops.weave_path(motion, so, span, max_shift, bool(subpixel))
+        got = ops.weave_apply(x, shifts, return_mask=want_mask)
+    out, mask = got if want_mask else (got, None)
+    return out, shifts, motion, mask
+
+
+@torch.no_grad()
+def stabilize(frames_u8, scenes=None, span=WEAVE_SPAN, radius=WEAVE_RADIUS, max_shift=WEAVE_MAX_SHIFT, tex=WEAVE_TEX, subpixel=True,
+              return_shifts=False, return_mask=False, device=None):
+    """Takes film weave out of a video -- the gate weave and telecine jitter that move every frame of old film by a fraction of a
+    pixel up to a few pixels, at random -- and leaves the camera's own motion alone: frames_u8 uint8 [L,H,W,3] (an array or a
+    tensor) -> uint8 [L,H,W,3], a numpy array, or a device tensor when the input is one (which is used where it is).  The result
+    is (out[, shifts, motion][, mask]): ``return_shifts`` adds shifts int32 [L,2], the correction (cx, cy) of every frame in 1/16
+    px, and motion int32 [L,4] = (mx, my, nx, ny), the measured motion of frame t against t - 1 in 1/16 px and the number of
+    bands it was measured on per axis; ``return_mask`` adds mask uint8 [L,H,W], 255 on the pixels the move exposed (filled from
+    the clamped border).  It needs no model and no flows; everything after the upload runs on the device, in four launches
+    (ops.weave_profiles, ops.weave_match, ops.weave_path, ops.weave_apply) without a host read.  Integers throughout
+    (include/e2fgvi_hip.h has the definition): the same arguments give the same bytes in every run.
+
+    Per frame the integer luma -- the scene detector's -- is summed along the columns and along the rows inside each of 8 bands
+    per axis.  The motion of a pair of frames is measured per axis and band: the shift s in [-radius, radius] at which the sum of
+    absolute differences of the two gradient profiles is smallest, refined to 1/16 px with the parabola through the costs at s -
+    1, s, s + 1 (an exact match, cost 0, is a whole-pixel motion).  A band counts when it has texture (``tex`` per element), its
+    best shift lies strictly inside the search range and the parabola opens upward; the pair's motion is the lower median of the
+    bands that count -- which keeps a moving object out of the estimate -- and the pair is trusted when at least 4 of 8 count.
+    The path p of an axis is the running sum of the motion inside a segment, a run of frames not broken by a cut (``scenes``:
+    None or a list of cuts as plan_windows takes them) or by an untrusted pair.  Frame t is moved by the rounded mean of p over
+    the symmetric window of k = min(span, frames to the segment's start, frames to its end) frames either side, minus p_t,
+    clamped to +-``max_shift`` px, with a bilinear tap in 1/16 px and the taps clamped to the frame.
+
+    What follows from that: a pan at constant speed comes back byte for byte (the symmetric mean of a straight path is the path;
+    "constant" is the measured motion -- across the pan's axis it is 0 give or take 1/16 px, which ``subpixel=False`` rounds away);
+    the first and last frame of a segment are unchanged; an untrusted pair (a flat frame, a flash, a motion beyond ``radius``)
+    breaks the window like a cut, so nothing is averaged across a motion that was not measured; a frame whose correction is 0
+    has the caller's bytes; span == 0, no frame or no pixel runs no launch and returns the caller's bytes.
+
+    Known limits: translation only, no rotation and no zoom; a sub-pixel move is a bilinear blend and softens
+    the picture slightly -- ``subpixel=False`` rounds the correction to whole pixels and keeps every byte; a pair that is
+    trusted but wrong bends the path around it, by at most ``max_shift``; the mean of white weave over 2 span + 1 frames remains
+    by construction; frames of less than 4 radius + 2 pixels on an axis are not measured on it.
+    Chaining: ``mask`` is the hole inpaint_video fills for a full-frame result (apply_shifts moves masks painted on the source
+    video by the same shifts); stabilize comes after deflicker -- brightness changes read as texture changes -- and in front of
+    detect_defects, detect_line_scratches and inpaint_video, which assume that the picture stands still.
+    span in [0, 16], radius in [1, 32], max_shift in [1, 64], tex in [0, 65535]: integers, no bools; subpixel, return_shifts and
+    return_mask bools; a string for ``scenes`` is refused; H, W <= 4096.  Argument errors are ValueErrors that name the
+    argument, raised before any device work.  There is no CPU path."""
+    scene_of, span, radius, max_shift, tex = _check_stabilize_args(frames_u8, scenes, span, radius, max_shift, tex, subpixel,
+                                                                   return_shifts, return_mask)
+    device = _tool_device("stabilize", device, frames_u8)
+    out, shifts, motion, mask = _like_input(frames_u8, *_stabilize_device(_upload(frames_u8, device), scene_of, span, radius,
+                                                                          max_shift, tex, subpixel, return_mask))
+    result = (out,) + ((shifts, motion) if return_shifts else ()) + ((mask,) if return_mask else ())
+    return result if len(result) > 1 else out
+
+
+@torch.no_grad()
+def apply_shifts(frames_u8, shifts, device=None):
+    """Moves frames, or masks painted on the unstabilised video, by the shifts stabilize(return_shifts=True) returned: frames_u8
+    uint8 [L,H,W,3] or [L,H,W] (an array or a tensor), shifts int32 [L,2] in 1/16 px -> uint8 of the same shape, a numpy array, or
+    a device tensor when the input is one.  The apply kernel alone (ops.weave_apply), one launch; a mask of 0 / 255 moved by a
+    sub-pixel shift has intermediate values at its edges.  Argument errors are ValueErrors that name the argument, raised before
+    any device work.  There is no CPU path."""
+    shape = tuple(getattr(frames_u8, "shape", ()))
+    if len(shape) not in (3, 4) or (len(shape) == 4 and shape[3] != 3) or not _is_u8(frames_u8):
+        raise ValueError("frames must be uint8 [L,H,W,3] or [L,H,W], got %s %s" % (getattr(frames_u8, "dtype", type(frames_u8).__name__), shape))
+    if tuple(getattr(shifts, "shape", ())) != (shape[0], 2) or str(getattr(shifts, "dtype", "")) not in ("int32", "torch.int32"):
+        raise ValueError("shifts must be int32 [%d,2], got %s %s" % (shape[0], getattr(shifts, "dtype", type(shifts).__name__),
+                                                                    tuple(getattr(shifts, "shape", ()))))
+    device = _tool_device("apply_shifts", device, frames_u8)
+    out, = _like_input(frames_u8, ops.weave_apply(_upload(frames_u8, device), _upload(shifts, device)))
+    return out
+
+
 YuvFormat =collections.namedtuple("YuvFormat", "layout matrix full_range chroma")
 YUV_MATRICES = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}         # (Kr, Kb)
 

@@ -456,6 +456,43 @@ int e2fgvi_flicker_hist(const uint8_t* frames, int32_t* hist, int32_t L, int32_t
 int e2fgvi_flicker_curves(const int32_t* hist, const int32_t* scene, int32_t* Q, int16_t* d, int32_t L, int32_t N, int32_t span,
                           int32_t max_shift, void* stream);
 int e2fgvi_flicker_apply(const uint8_t* frames, const int16_t* d, uint8_t* out, int32_t L, int32_t H, int32_t W, void* stream);
+/* Weave stabiliser (video.stabilize): the translation of the picture from frame to frame -- gate weave, telecine jitter -- measured
+ * from banded luma profiles, a path smoothed over a symmetric window, and the frames moved back onto it.  All arithmetic is
+ * integer; "floor" is the floor for either sign, >> of a negative number is the arithmetic shift and & 15 its non-negative rest.
+ *   frames uint8 [L,H,W,3];  scene int32 [L] on the device: two frames are in one scene when their entries are equal.
+ *   NB = 8 bands per axis.  Parameters radius R in [1, 32], tex in [0, 65535], span in [0, 16], max_shift in [1, 64].
+ * 1. Profiles of Y = (77 R + 150 G + 29 B + 128) >> 8.  col[t][b][x] = the sum of Y over the rows [bH/8, (b+1)H/8) of column x,
+ *    int32 [L][8][W];  row[t][b][y] = the sum over the columns [bW/8, (b+1)W/8) of row y, int32 [L][8][H] (floor divisions; a band
+ *    may be empty).  The gradient of a profile P of length n is g[i] = P[i+1] - P[i-1], 0 at i = 0 and i = n - 1.
+ * 2. Motion of the pair (t-1, t), per axis (x: col, n = W, bands over the rows; y: row, n = H) and band.  The window is i in
+ *    [R+1, n-R-1);  cost(s) = the sum over the window of |g_t[i+s] - g_{t-1}[i]|, s in [-R, R], 64-bit.  The best s has the smallest
+ *    cost; ties go to the smallest |s|, then to the negative one.  With c-, c0, c+ the costs at s-1, s, s+1: den = c- - 2 c0 + c+,
+ *    delta = floor((16 (c- - c+) + den) / (2 den)), and delta = 0 when c0 == 0.  The band is valid when it is not empty, the window
+ *    has at least 2R elements, -R < s < R, den > 0 and the window's sum of |g_{t-1}| is at least tex times its length; its motion
+ *    is 16 s + delta, in 1/16 px.  The pair's motion on the axis is the lower median of the valid bands' when at least NB/2 are
+ *    valid (the pair is trusted), else 0.  Frame 0 and the first frame of a scene: motion 0, no valid band.
+ *    motion int32 [L][4] = mx, my, nx, ny: the motion and the number of valid bands per axis.
+ * 3. Path.  Frame t starts a segment on an axis when t == 0, scene[t] != scene[t-1] or n_axis[t] < NB/2.  p_t = the sum of the
+ *    motion from the segment's second frame to t;  k_t = min(span, t - first, last - t);  q_t = floor((2 S + n) / (2n)), S the sum
+ *    of p over [t-k_t, t+k_t], n = 2 k_t + 1, 64-bit;  c_t = clamp(q_t - p_t, -16 max_shift, 16 max_shift).  Without subpixel
+ *    c_t = ((c_t + 8) >> 4) << 4.  shift int32 [L][2] = cx, cy in 1/16 px.
+ * 4. Apply, C = 1 or 3 bytes a pixel.  cx, cy clamped to +-16 * 64.  X = 16 x - cx, x0 = X >> 4, fx = X & 15, likewise y; the taps
+ *    a, b, c, d = (x0, y0), (x0+1, y0), (x0, y0+1), (x0+1, y0+1), coordinates clamped to the frame;  out = ((16-fx)(16-fy) a +
+ *    fx (16-fy) b + (16-fx) fy c + fx fy d + 128) >> 8 per channel;  mask[t][y][x] = 255 where a tap of non-zero weight lies
+ *    outside the frame before clamping, else 0.  A whole-pixel shift copies bytes, a zero shift returns the input.
+ * e2fgvi_weave_profiles does 1 in one pass (it clears col on the stream and adds with integer atomics; every word of col and row
+ * is written, every frame byte read once); e2fgvi_weave_match does 2 in one launch, e2fgvi_weave_path 3, e2fgvi_weave_apply 4
+ * (mask may be null; out and mask must not overlap frames or each other: E2FGVI_EINVAL).  Nothing is read on the host.  Sizes >=
+ * 0; H, W <= 4096 for profiles and match, H W <= 2^26 for apply; parameters in their ranges, subpixel 0 or 1 (E2FGVI_EINVAL
+ * otherwise, from the arguments alone); L, H or W == 0 returns 0 without a launch and without looking at the pointers; a null
+ * pointer with work or an int32 array that is not 4-byte aligned is E2FGVI_EINVAL.  Frames are launched in slabs of 65535. */
+int e2fgvi_weave_profiles(const uint8_t* frames, int32_t* col, int32_t* row, int32_t L, int32_t H, int32_t W, void* stream);
+int e2fgvi_weave_match(const int32_t* col, const int32_t* row, const int32_t* scene, int32_t* motion, int32_t L, int32_t H,
+                       int32_t W, int32_t radius, int32_t tex, void* stream);
+int e2fgvi_weave_path(const int32_t* motion, const int32_t* scene, int32_t* shift, int32_t L, int32_t span, int32_t max_shift,
+                      int32_t subpixel, void* stream);
+int e2fgvi_weave_apply(const uint8_t* frames, const int32_t* shift, uint8_t* out, uint8_t* mask, int32_t L, int32_t H, int32_t W,
+                       int32_t C, void* stream);
 
 /* conv_offset post-processing of SecondOrderDeformableAlignment (feat_prop.py:38-53) fused into the conv that produces
  * it: `residual` must point to the per-pixel flows [P,4] = (u1,v1,u2,v2) with res_ld = 4, `slope` = max_residue:
