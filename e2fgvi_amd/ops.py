@@ -2472,6 +2472,57 @@ def weave_apply(frames, shift, out=None, mask=None, return_mask=False):
     return (ou, mk) if mk is not None else ou
 
 
+INTERLACE_EDGES_MAX = 2                    # csrc/interlace.hip: parameters outside these ranges are E2FGVI_EINVAL
+INTERLACE_MODES = {"field": 0, "first": 1, "second": 2}    # mode: field rate; frame rate, the first / the second field kept
+
+
+def interlace_scores(frames, scene):
+    """The field-order scores of the deinterlacer, one launch over all frames (csrc/interlace.hip interlace_scores_kernel;
+    include/e2fgvi_hip.h has the definition; video.detect_interlace is the caller): frames uint8 [L,H,W,3], scene int32 [L], equal
+    entries = one scene -> device int64 [L,2]: D[t][q] sets the rows of parity q of frame t + 1 against their neighbours in frame
+    t, 0 for the last frame of a scene and when H < 4.  Device tensors, or anything torch.as_tensor accepts (uploaded first); a
+    wrong dtype or shape, more than 2^26 pixels a frame and a non-contiguous input raise ValueError.  There is no CPU path and no
+    host read; integer atomics: the same input gives the same bits in every run."""
+    lib = _L.load()
+    fr, sc = _device_inputs([("frames", frames, torch.uint8), ("scene", scene, torch.int32)], "frames")
+    L, H, W = _flicker_frames(fr)
+    _scene_table(sc, "scene", L)
+    with torch.cuda.device(fr.device):
+        D = _alloc(L > 0 and H > 0 and W > 0, (L, 2), torch.int64, fr.device)     # with work the entry clears every word
+        _L.check(lib.e2fgvi_interlace_scores(_ptr(fr), _ptr(sc), _ptr(D), L, H, W, _stream()), "interlace_scores")
+    return D
+
+
+def deinterlace(frames, scene, tff, mode, guard, edges, out=None):
+    """The two fields of every frame as pictures of their own, one launch (csrc/interlace.hip interlace_fields_kernel;
+    include/e2fgvi_hip.h has the definition; video.deinterlace is the caller): frames uint8 [L,H,W,3], scene int32 [L] -> device
+    uint8 [2L,H,W,3] (mode 0, field rate) or [L,H,W,3] (mode 1: the first field kept, mode 2: the second).  A kept row is copied;
+    a missing row is the line average of the rows around it, along the direction ``edges`` allows, clamped to within diff of the
+    mean of the two fields of its own parity nearest in time.  tff and guard bools, mode in [0, 2], edges in [0,
+    INTERLACE_EDGES_MAX]: integers, no bools.  ``out``: a device tensor of the result's shape to write into, which must not
+    overlap ``frames`` (the entry refuses it); every byte is written once.  The checks of interlace_scores; no host read; exact
+    integers."""
+    lib = _L.load()
+    for nm, v in (("tff", tff), ("guard", guard)):
+        if not isinstance(v, bool):
+            raise ValueError("%s must be a bool, got %r" % (nm, v))
+    mode = _int_arg("mode", mode, 0, 2)
+    edges = _int_arg("edges", edges, 0, INTERLACE_EDGES_MAX)
+    named = [("frames", frames, torch.uint8), ("scene", scene, torch.int32)] + ([("out", out, torch.uint8)] if out is not None else [])
+    up = _device_inputs(named, "frames", written=("out",))
+    fr, sc = up[:2]
+    L, H, W = _flicker_frames(fr)
+    _scene_table(sc, "scene", L)
+    shape = (2 * L if mode == 0 else L, H, W, 3)
+    if out is not None and tuple(up[2].shape) != shape:
+        raise ValueError("out must be %s, got %s" % (list(shape), tuple(up[2].shape)))
+    with torch.cuda.device(fr.device):
+        ou = up[2] if out is not None else torch.empty(shape, dtype=torch.uint8, device=fr.device)
+        _L.check(lib.e2fgvi_deinterlace(_ptr(fr), _ptr(sc), _ptr(ou), L, H, W, int(tff), mode, int(guard), edges, _stream()),
+                 "deinterlace")
+    return ou
+
+
 YUV_LAYOUTS ={"nv12": 0, "i420": 1}     # E2FGVI_YUV_*/ E2FGVI_CHROMA_* of include/e2fgvi_hip.h
 YUV_CHROMA = {"left": 0, "nearest": 1}
 

@@ -1459,6 +1459,144 @@ def apply_shifts(frames_u8, shifts, device=None):
     return out
 
 
+INTERLACE_MARGIN = 5           # field_order_from_scores: per cent; DESIGN.md 3w has the ratios it was chosen from
+INTERLACE_EDGES = 0            # deinterlace's default: DESIGN.md 3w has the measurements it was judged on
+
+
+def _check_interlace_frames(frames_u8, scenes):
+    """the checks that detect_interlace and deinterlace share, from the arguments and the shapes alone -> (scene_of int32 [L], cuts)"""
+    shape = _check_frames(frames_u8, True)
+    if int(shape[1]) * int(shape[2]) > ops.FLICKER_PIXELS_MAX:
+        raise ValueError("frames must have H W <= 2^26, got %d x %d" % (shape[1], shape[2]))
+    cuts = _scene_cuts(scenes, int(shape[0]))
+    return _scene_table(cuts, int(shape[0])), cuts
+
+
+def field_order_from_scores(D, scenes=None, margin=INTERLACE_MARGIN):
+    """detect_interlace's scores D int64 [L,2] -> (verdict, votes): votes int8 [L], +1 where the pair (t, t + 1) says top field
+    first -- 100 D[t][0] < (100 - margin) D[t][1]: the bottom field of t is nearer to the top field of t + 1 than the top field of
+    t is to the bottom field of t + 1 -- -1 where 100 D[t][1] < (100 - margin) D[t][0], 0 otherwise and for a scene's last frame.
+    With pairs the number of frames that have a successor in their scene, n+ and n- the numbers of +1 and -1 votes, the verdict is
+    "progressive" when 4 (n+ + n-) < pairs or pairs == 0, else "tff" when n+ > 2 n-, else "bff" when n- > 2 n+, else "mixed".
+    ``scenes``: None or a list of cuts as plan_windows takes them; margin an integer in [1, 50] (per cent), no bool.  ValueError
+    that names the argument otherwise.  Pure host code, exact integers."""
+    shape = tuple(getattr(D, "shape", ()))
+    if len(shape) != 2 or shape[1] != 2 or str(getattr(D, "dtype", "")) not in ("int64", "torch.int64"):
+        raise ValueError("D must be int64 [L,2], got %s %s" % (getattr(D, "dtype", type(D).__name__), shape))
+    L = int(shape[0])
+    scene_of = _scene_table(_scene_cuts(scenes, L), L)
+    margin, = _check_ranges(("margin", margin, 1, 50))
+    d = (D.cpu().numpy() if isinstance(D, torch.Tensor) else np.asarray(D)).astype(np.int64)     # at most 2^36: the products fit
+    votes = np.zeros(L, np.int8)
+    paired = np.zeros(L, bool)
+    paired[:max(L - 1, 0)] = scene_of[1:] == scene_of[:-1]
+    votes[paired & (100 * d[:, 0] < (100 - margin) * d[:, 1])] = 1
+    votes[paired & (100 * d[:, 1] < (100 - margin) * d[:, 0])] = -1
+    pairs, up, down = int(paired.sum()), int((votes == 1).sum()), int((votes == -1).sum())
+    if pairs == 0 or 4 * (up + down) < pairs:
+        return "progressive", votes
+    return ("tff" if up > 2 * down else "bff" if down > 2 * up else "mixed"), votes
+
+
+@torch.no_grad()
+def detect_interlace(frames_u8, scenes=None, margin=INTERLACE_MARGIN, return_scores=False, device=None):
+    """Says whether a video is interlaced and in which field order: frames_u8 uint8 [L,H,W,3] (an array or a tensor, which is used
+    where it is when on the device) -> "tff", "bff", "progressive" or "mixed"; with ``return_scores`` (verdict, D, votes), D int64
+    [L,2] and votes int8 [L] as numpy arrays.  One launch (ops.interlace_scores) over all frames, then one host read of D;
+    field_order_from_scores has the rule, include/e2fgvi_hip.h the scores: D[t][0] sets the odd rows of frame t against the even
+    rows of frame t + 1 between them, D[t][1] the even rows of t against the odd rows of t + 1 -- of the two field pairs the one
+    that is half a frame period apart differs less than the one that is one and a half apart, and on progressive video the two are
+    equal up to texture.  "mixed": the pairs disagree (an edit of two sources; 3:2 pulldown votes in a pattern of its own).  A
+    video that stands still has no field order to measure and reads as "progressive".  ``scenes``: None or a list of cuts; no pair
+    is scored across one.  margin an integer in [1, 50], return_scores a bool, a string for ``scenes`` is refused, H W <= 2^26:
+    ValueErrors that name the argument, raised before any device work.  There is no CPU path."""
+    scene_of, cuts = _check_interlace_frames(frames_u8, scenes)
+    margin, = _check_ranges(("margin", margin, 1, 50))
+    _check_flags(return_scores=return_scores)
+    device = _tool_device("detect_interlace", device, frames_u8)
+    x = _upload(frames_u8, device)
+    L, H, W = (int(v) for v in x.shape[:3])
+    if L == 0 or H * W == 0:
+        D = np.zeros((L, 2), np.int64)
+    else:
+        so = torch.from_numpy(scene_of).to(x.device)        # in front of the launch
+        with torch.cuda.device(x.device):
+            D = ops.interlace_scores(x, so).cpu().numpy()
+    verdict, votes = field_order_from_scores(D, cuts, margin)
+    return (verdict, D, votes) if return_scores else verdict
+
+
+def _check_deinterlace_args(frames_u8, order, rate, keep, scenes, guard, edges):
+    """the checks of deinterlace from the arguments and the shapes alone -> (scene_of int32 [L], cuts, mode, edges)"""
+    scene_of, cuts = _check_interlace_frames(frames_u8, scenes)
+    if not isinstance(order, str) or order not in ("tff", "bff", "auto"):
+        raise ValueError('order must be "tff", "bff" or "auto", got %r' % (order,))
+    if not isinstance(rate, str) or rate not in ("field", "frame"):
+        raise ValueError('rate must be "field" or "frame", got %r' % (rate,))
+    if not isinstance(keep, str) or keep not in ("first", "second") or (rate == "field" and keep != "first"):
+        raise ValueError('keep must be "first" or "second", and "first" with rate="field" (both fields are kept), got %r' % (keep,))
+    _check_flags(guard=guard)
+    edges, = _check_ranges(("edges", edges, 0, ops.INTERLACE_EDGES_MAX))
+    return scene_of, cuts, ops.INTERLACE_MODES["field" if rate == "field" else keep], edges
+
+
+def _deinterlace_device(x, scene_of, tff, mode, guard, edges):
+    """deinterlace after the argument checks and the upload of the frames: x uint8 [L,H,W,3] on the device -> uint8 [2L,H,W,3]
+    (mode 0) or [L,H,W,3] on the device.  One launch, no host read; no frame or no pixel: no launch."""
+    L, H, W = (int(v) for v in x.shape[:3])
+    if L == 0 or H * W == 0:
+        return torch.zeros((2 * L if mode == 0 else L, H, W, 3), dtype=torch.uint8, device=x.device)
+    so = torch.from_numpy(scene_of).to(x.device)            # in front of the launch
+    with torch.cuda.device(x.device):
+        return ops.deinterlace(x, so, bool(tff), mode, bool(guard), edges)
+
+
+@torch.no_grad()
+def deinterlace(frames_u8, order="tff", rate="field", keep="first", scenes=None, guard=True, edges=INTERLACE_EDGES, device=None):
+    """Makes progressive pictures of interlaced video -- tape, where a frame is two fields 1/50 or 1/60 s apart on alternating
+    rows and everything that moves has combs -- as the first step of a restoration chain, in front of deflicker (and so of
+    stabilize, detect_defects, detect_line_scratches, match_grain and inpaint_video, all of which assume that a frame is one
+    instant): frames_u8 uint8 [L,H,W,3] (an array or a tensor) -> uint8 [2L,H,W,3] at ``rate="field"`` (every field becomes a
+    picture, in the order shown) or [L,H,W,3] at ``rate="frame"`` (``keep="first"`` or ``"second"``: the field of each frame that
+    is kept), a numpy array, or a device tensor when the input is one (which is used where it is).  It needs no model and no
+    flows; with ``order`` "tff" or "bff" everything after the upload is one launch (ops.deinterlace) without a host read.
+    ``order="auto"`` runs detect_interlace first -- one more launch and one host read of its scores -- and raises a ValueError
+    that names ``order`` when the verdict is "progressive" or "mixed".  Integers throughout (include/e2fgvi_hip.h has the
+    definition): the same arguments give the same bytes in every run.
+
+    A kept row is copied.  A missing row is interpolated between the rows above and below it in its own field -- with ``edges``
+    1 or 2 along the best of the directions within that many columns -- and the result is clamped to within diff of d, the mean
+    of the two fields of the missing parity nearest in time, one before and one after; diff is the largest of three temporal
+    luma differences around the pixel, so where the picture stands still the pixel is the temporal mean (full vertical detail)
+    and where it moves it is the spatial interpolation.  ``guard`` widens diff by the vertical change of the temporal prediction
+    over rows y - 2 .. y + 2, which keeps a clamp that is too tight from leaving combs.  ``scenes``: None or a list of cuts as
+    plan_windows takes them (detect_cuts finds them); no field is taken from across a cut, and the cuts of the field-rate result
+    are ``[2 c for c in cuts]``.
+
+    What follows from that: the kept rows are the caller's bytes; the rate="frame" results are the even (keep="first") and the
+    odd (keep="second") pictures of the rate="field" result; a video deinterlaced scene by scene and joined is the call with
+    ``scenes``; with ``guard=False`` a video that stands still comes back with every frame twice, byte for byte; no frame or
+    no pixel runs no launch.
+
+    Known limits: 3:2 pulldown is not undone (inverse telecine is another tool); masks painted on the interlaced
+    frames are not converted -- paint them on the result; a fast pan is no better than line averaging (about half a decibel
+    worse on the panning tests/golden/tennis25.npz); ``guard=True`` changes static detail: a video that stands still does not
+    come back byte for byte (on the locked-off test clip it scores 36.2 dB where guard=False scores 39.6, under the pan 29.0
+    where guard=False scores 28.2); ``edges`` > 0 did not pay on 240-line material, hence the default.
+    order "tff", "bff" or "auto"; rate "field" or "frame"; keep "first" or "second", and with rate="field" only its default
+    "first"; guard a bool; edges an integer in [0, 2], no bool; a string for ``scenes`` is refused; H W <= 2^26.  Argument errors
+    are ValueErrors that name the argument, raised before any device work.  There is no CPU path."""
+    scene_of, cuts, mode, edges = _check_deinterlace_args(frames_u8, order, rate, keep, scenes, guard, edges)
+    device = _tool_device("deinterlace", device, frames_u8)
+    x = _upload(frames_u8, device)
+    if order == "auto":
+        order = detect_interlace(x, cuts or None)
+        if order not in ("tff", "bff"):
+            raise ValueError('order="auto": the video reads as %s, not as interlaced in one field order; name the order' % order)
+    out, = _like_input(frames_u8, _deinterlace_device(x, scene_of, order == "tff", mode, guard, edges))
+    return out
+
+
 YuvFormat =collections.namedtuple("YuvFormat", "layout matrix full_range chroma")
 YUV_MATRICES = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}         # (Kr, Kb)
 

@@ -493,6 +493,45 @@ int e2fgvi_weave_path(const int32_t* motion, const int32_t* scene, int32_t* shif
                       int32_t subpixel, void* stream);
 int e2fgvi_weave_apply(const uint8_t* frames, const int32_t* shift, uint8_t* out, uint8_t* mask, int32_t L, int32_t H, int32_t W,
                        int32_t C, void* stream);
+/* Deinterlacer (video.deinterlace, video.detect_interlace): an interlaced frame is two fields, half a frame period apart, on
+ * alternating rows; each field becomes a picture of its own, and the field order is measured.  All arithmetic is integer and >> of
+ * a negative number is the arithmetic shift.
+ *   frames uint8 [L,H,W,3];  scene int32 [L] on the device: two frames are in one scene when their entries are equal.
+ *   Y = (77 R + 150 G + 29 B + 128) >> 8, the luma of the other tools.  Row parity 0 is the top field;  tff in {0, 1}: the field
+ *   shown first has parity first = tff ? 0 : 1.  A neighbour frame t-1 or t+1 that lies outside the video or in another scene is
+ *   replaced by frame t itself.  Parameters mode in [0, 2], guard in {0, 1}, edges in [0, 2].
+ * Deinterlace.  Frame t gives two pictures: O[2t] keeps the rows of parity first, O[2t+1] those of parity 1 - first; a kept row is
+ * copied.  With P, C, N the frames t-1, t, t+1: for O[2t] A = P, B = C, for O[2t+1] A = C, B = N -- the two fields of the missing
+ * parity nearest in time, one before and one after.  For a picture that keeps parity p, a missing row y (y & 1 != p) and column x:
+ *   up = y-1 if y-1 >= 0, else y+1;  dn = y+1 if y+1 <= H-1, else y-1.  With H == 1 there is neither: out = (A[y] + B[y]) >> 1 per
+ *   channel and nothing else applies.  Columns are clamped to [0, W-1] wherever x plus an offset is written.
+ * 1. c = Y_C[up][x], e = Y_C[dn][x], dY = (Y_A[y][x] + Y_B[y][x]) >> 1.
+ * 2. t0 = |Y_A[y][x] - Y_B[y][x]|;  t1 = (|Y_P[up][x] - c| + |Y_P[dn][x] - e|) >> 1;  t2 = (|Y_N[up][x] - c| + |Y_N[dn][x] - e|) >> 1;
+ *    diff = max(t0 >> 1, t1, t2).
+ * 3. Direction.  score(j) = the sum over k in {-1, 0, 1} of |Y_C[up][x+k+j] - Y_C[dn][x+k-j]|.  best = score(0) - 1, J = 0.  For
+ *    sgn = -1, then sgn = +1: if edges >= 1 and score(sgn) < best, take it: best = score(sgn), J = sgn; only if it was taken, and
+ *    edges >= 2, and score(2 sgn) < best: best = score(2 sgn), J = 2 sgn.  The + side compares against the best so far, the -
+ *    side's result included.
+ * 4. Guard, when guard == 1 and y-2 >= 0 and y+2 <= H-1 (otherwise it is skipped, not clamped).  b = (Y_A[y-2][x] + Y_B[y-2][x]) >> 1,
+ *    f likewise at y+2;  mx = max(dY - e, dY - c, min(b - c, f - e));  mn = min(dY - e, dY - c, max(b - c, f - e));
+ *    diff = max(diff, mn, -mx).
+ * 5. Per channel: sp = (C[up][x+J] + C[dn][x-J]) >> 1;  d = (A[y][x] + B[y][x]) >> 1;  out = clamp(sp, d - diff, d + diff).  All
+ *    decisions are taken on luma, so they are the same for a pixel's three channels.
+ * mode 0: field rate, out [2L,H,W,3] = O;  mode 1: frame rate, first field kept, out[t] = O[2t];  mode 2: frame rate, second field
+ * kept, out[t] = O[2t+1].  Every output byte is written once.
+ * Scores.  m = (H - 2) / 2 (floor); the rows are y in [1, 2m]: as many even rows as odd ones, none when H < 4.  For t with t+1 in
+ * the same scene D[t][q] = the sum, over the rows of parity q and all columns, of |2 Y_{t+1}[y][x] - Y_t[y-1][x] - Y_t[y+1][x]|;
+ * D int64 [L][2], D[t] = 0 for the last frame of a scene.  D[t][0] sets the bottom field of t against the top field of t+1 -- half
+ * a frame period apart under top-field-first, one and a half under bottom-field-first -- and D[t][1] is the mirror; on progressive
+ * video the two are equal up to texture.
+ * e2fgvi_interlace_scores clears D on the stream and adds with integer atomics (exact, the same in every run); every frame byte is
+ * read at most twice.  e2fgvi_deinterlace is one launch; out must not overlap frames (E2FGVI_EINVAL).  Nothing is read on the host.
+ * Sizes >= 0, H W <= 2^26, parameters in their ranges (E2FGVI_EINVAL otherwise, from the arguments alone); L, H or W == 0 returns 0
+ * without a launch and without looking at the pointers; a null pointer with work, a scene that is not 4-byte aligned or a D that is
+ * not 8-byte aligned is E2FGVI_EINVAL.  Frames are launched in slabs of 65535. */
+int e2fgvi_interlace_scores(const uint8_t* frames, const int32_t* scene, int64_t* D, int32_t L, int32_t H, int32_t W, void* stream);
+int e2fgvi_deinterlace(const uint8_t* frames, const int32_t* scene, uint8_t* out, int32_t L, int32_t H, int32_t W, int32_t tff,
+                       int32_t mode, int32_t guard, int32_t edges, void* stream);
 
 /* conv_offset post-processing of SecondOrderDeformableAlignment (feat_prop.py:38-53) fused into the conv that produces
  * it: `residual` must point to the per-pixel flows [P,4] = (u1,v1,u2,v2) with res_ld = 4, `slope` = max_residue:
