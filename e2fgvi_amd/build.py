@@ -40,8 +40,9 @@ UNITS = [("error.hip", "error.o", []), ("conv.hip", "conv.o", []), ("conv.hip", 
          ("line_scratch.hip", "line_scratch.o", NOPK),
          ("flicker.hip", "flicker.o", NOPK),
          ("weave.hip", "weave.o", NOPK),
-         ("interlace.hip", "interlace.o", NOPK)]
-NOPK_OBJECTS = ("conv_nopk.o", "conv_bf16x.o", "conv_wino.o", "conv_wino4.o", "conv_wino_x3.o", "conv_tail.o", "mdcn.o", "attention_bf16.o", "attention_x3.o", "misc.o", "video.o", "yuv.o", "metrics.o", "mask_track.o", "defects.o", "pixel_track.o", "grain.o", "line_scratch.o", "flicker.o", "weave.o", "interlace.o")
+         ("interlace.hip", "interlace.o", NOPK),
+         ("denoise.hip", "denoise.o", NOPK)]
+NOPK_OBJECTS = ("conv_nopk.o", "conv_bf16x.o", "conv_wino.o", "conv_wino4.o", "conv_wino_x3.o", "conv_tail.o", "mdcn.o", "attention_bf16.o", "attention_x3.o", "misc.o", "video.o", "yuv.o", "metrics.o", "mask_track.o", "defects.o", "pixel_track.o", "grain.o", "line_scratch.o", "flicker.o", "weave.o", "interlace.o", "denoise.o")
 OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 
 
@@ -103,6 +104,7 @@ def build(force=False, verbose=False, nopk_all=False, lib=None, tag=None, define
             verify_no_scratch(objdir, "flicker.o", "flicker_", "deflicker")
             verify_no_scratch(objdir, "weave.o", "weave_", "weave stabiliser")
             verify_no_scratch(objdir, "interlace.o", "interlace_", "deinterlacer")
+            verify_no_scratch(objdir, "denoise.o", "denoise_", "temporal denoiser")
             verify_overlay_prefetch(objdir)
             verify_no_pk_u8(objdir)
             verify_no_fma64(objdir)
@@ -192,7 +194,8 @@ def verify_no_scratch(objdir=None, obj="conv_bf16x.o", marker="ELb0ELi2ELb1EEE",
     and over the four of line_scratch.o (the per-polarity counters of the columns pass are small arrays indexed in unrolled loops);
     and over the three of flicker.o (the histogram and the apply kernel hold the dwords of all of a thread's groups at once);
     and over the five of weave.o (the apply kernel shifts the dwords of two tap rows into place in small arrays);
-    and over the three of interlace.o (the fields kernel holds the dwords and the luma of up to twelve groups in small arrays)."""
+    and over the three of interlace.o (the fields kernel holds the dwords and the luma of up to twelve groups in small arrays);
+    and over the four of denoise.o (the filter kernel keeps the 7 x 5 three-byte runs of a neighbour's luma window in a small array)."""
     import re
     import shutil
     import tempfile

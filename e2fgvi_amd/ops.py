@@ -2523,6 +2523,55 @@ def deinterlace(frames, scene, tff, mode, guard, edges, out=None):
     return ou
 
 
+DENOISE_STRENGTH_MAX = 64                  # csrc/denoise.hip: parameters outside these ranges are E2FGVI_EINVAL
+DENOISE_SEARCH_MAX = 2
+DENOISE_PIXELS_MAX = 2 ** 31 - 256 - 1
+
+
+def denoise_work_bytes(L, H, W):
+    """the bytes of the luma workspace e2fgvi_denoise asks for (include/e2fgvi_hip.h): a plane a frame with a ring of four pixels
+    and rows padded to a dword plus one"""
+    return L * (H + 8) * (((W + 11) & ~3) + 4)
+
+
+def denoise(frames, fwd, bwd, scene, strength, search, max_change, out=None):
+    """The motion-compensated temporal denoiser (csrc/denoise.hip; include/e2fgvi_hip.h has the definition; video.denoise is the
+    caller): frames uint8 [L,H,W,3]; fwd, bwd fp32 [L-1,H,W,2] in metrics.warp_error's convention; scene int32 [L], equal entries
+    = one scene -> device uint8 [L,H,W,3]: every pixel the mean of itself (weight 256) and of the (2 search + 1)^2 pixels around
+    the place its flow points at in the frame before and in the frame after, each weighted by max(0, 256 - SAD / (9 strength)
+    256) of the 3 x 3 luma patches, and moved by ``max_change`` levels at the most.  One call of the entry: a luma pass into a
+    workspace allocated here (denoise_work_bytes: about a byte a pixel) and the filter pass, no host read.  strength in [1, 64], search in [0, 2], max_change in [0, 255]:
+    integers, no bools.  ``out``: a device tensor of the frames' shape to write into, which must not overlap ``frames`` (the entry
+    refuses it); every byte is written once.  Device tensors, or anything torch.as_tensor accepts (uploaded first); wrong dtypes,
+    shapes that do not fit, non-contiguous inputs and tensors on different devices raise ValueError.  There is no CPU path.
+    Exact integers: the same inputs give the same bytes in every run."""
+    lib = _L.load()
+    strength = _int_arg("strength", strength, 1, DENOISE_STRENGTH_MAX)
+    search = _int_arg("search", search, 0, DENOISE_SEARCH_MAX)
+    max_change = _int_arg("max_change", max_change, 0, 255)
+    named = [("frames", frames, torch.uint8), ("fwd", fwd, torch.float32), ("bwd", bwd, torch.float32), ("scene", scene, torch.int32)]
+    if out is not None:
+        named.append(("out", out, torch.uint8))
+    up = _device_inputs(named, "frames", written=("out",))
+    fr, fw, bw, sc = up[:4]
+    L, H, W = _frames_shape(fr, "frames")
+    if H * W > DENOISE_PIXELS_MAX:
+        raise ValueError("frames must have H W < 2^31 - 256, got %d x %d" % (H, W))
+    _scene_table(sc, "scene", L)
+    for t, nm in ((fw, "fwd"), (bw, "bwd")):
+        if L >= 1 and tuple(t.shape) != (L - 1, H, W, 2):
+            raise ValueError("%s must be [%d,%d,%d,2] for frames %s, got %s" % (nm, L - 1, H, W, tuple(fr.shape), tuple(t.shape)))
+    if out is not None and tuple(up[4].shape) != (L, H, W, 3):
+        raise ValueError("out must be [%d,%d,%d,3], got %s" % (L, H, W, tuple(up[4].shape)))
+    with torch.cuda.device(fr.device):
+        ou = up[4] if out is not None else torch.empty_like(fr)
+        nwork = denoise_work_bytes(L, H, W) if L >= 2 and H * W > 0 else 0
+        work = torch.empty(nwork, dtype=torch.uint8, device=fr.device)
+        _L.check(lib.e2fgvi_denoise(_ptr(fr), _ptr(fw), _ptr(bw), _ptr(sc), _ptr(ou), _ptr(work), nwork, L, H, W, strength, search,
+                                    max_change, _stream()), "denoise")
+    return ou
+
+
 YUV_LAYOUTS ={"nv12": 0, "i420": 1}     # E2FGVI_YUV_*/ E2FGVI_CHROMA_* of include/e2fgvi_hip.h
 YUV_CHROMA = {"left": 0, "nearest": 1}
 

@@ -1597,6 +1597,73 @@ def deinterlace(frames_u8, order="tff", rate="field", keep="first", scenes=None,
     return out
 
 
+DENOISE_STRENGTH = 8           # denoise's defaults: DESIGN.md 3x has the measurements they were judged on
+DENOISE_SEARCH = 1
+
+
+def _check_denoise_args(model, frames_u8, flows, scenes, strength, search, max_change):
+    """the checks of denoise from the arguments and the shapes alone -> (scene_of int32 [L], strength, search, max_change)"""
+    shape = _check_frames(frames_u8, True)
+    if int(shape[1]) * int(shape[2]) > ops.DENOISE_PIXELS_MAX:
+        raise ValueError("frames must have H W < 2^31 - 256, got %d x %d" % (shape[1], shape[2]))
+    cuts = _scene_cuts(scenes, int(shape[0]))
+    params = _check_ranges(("strength", strength, 1, ops.DENOISE_STRENGTH_MAX), ("search", search, 0, ops.DENOISE_SEARCH_MAX),
+                           ("max_change", max_change, 0, 255))
+    _check_flow_source(model, flows, shape, None, "the neighbours are reached along")
+    return (_scene_table(cuts, int(shape[0])),) + params
+
+
+def _denoise_device(model, x, flows, scene_of, strength, search, max_change):
+    """denoise after the argument checks and the upload of the frames: x uint8 [L,H,W,3] on the device -> uint8 [L,H,W,3] on the
+    device.  The flows, then one call of ops.denoise; no host read."""
+    so = torch.from_numpy(scene_of).to(x.device)            # in front of the first launch
+    with torch.cuda.device(x.device):
+        fwd, bwd = _device_flows(model, x, flows)
+        return ops.denoise(x, fwd, bwd, so, strength, search, max_change)
+
+
+@torch.no_grad()
+def denoise(model, frames_u8, flows=None, scenes=None, strength=DENOISE_STRENGTH, search=DENOISE_SEARCH, max_change=255, device=None):
+    """Takes noise -- tape noise, sensor noise, film grain where it is not wanted -- out of a video along its motion, as the step
+    after stabilize and in front of detect_defects, detect_line_scratches and inpaint_video, which all read noise as signal:
+    frames_u8 uint8 [L,H,W,3] (an array or a tensor) -> uint8 [L,H,W,3], a numpy array, or a device tensor when the input is one
+    (which is used where it is).  The flows between adjacent frames are the net's own (metrics.video_flows(model, frames):
+    ``model`` must be the generator, TypeError otherwise) or ``flows`` = (fwd, bwd), fp32 [L-1,H,W,2] in metrics.warp_error's
+    convention -- ``model`` may then be None; detect_defects, propagate_masks and propagate_pixels take the same pair.  Everything
+    after the upload runs on the device (ops.denoise), without a host read.  Exact integers after one floor (include/e2fgvi_hip.h
+    has the definition): the same arguments give the same bytes in every run.
+
+    A pixel becomes the weighted mean of itself, with weight 256, and of the (2 search + 1)^2 pixels around the place its flow
+    points at -- rounded to a pixel -- in the frame before and in the frame after.  A candidate's weight is 256 minus 256 times
+    the sum of absolute luma differences between the 3 x 3 patch around it and the 3 x 3 patch around the pixel, over 9
+    ``strength``, and 0 from there on: ``strength`` is the mean luma difference per tap at which a candidate stops counting,
+    about 1.6 times the sigma of the noise (8 for sigma 5, 16 for sigma 10).  ``search`` = 1 or 2 makes up for
+    flows that are off by that many pixels, at (2 search + 1)^2 times the work and a little smoothing of fine texture;
+    ``search`` = 0 trusts the flows.  No byte moves by more than ``max_change`` levels.  ``scenes``: None or a list of cuts as
+    plan_windows takes them (detect_cuts finds them); nothing is taken from across a cut.  All decisions are on luma, so a
+    pixel's three channels share their weights.
+
+    What follows from that: with max_change == 0, or every frame in a scene of its own, the result is the input; a video denoised
+    scene by scene and joined is the call with ``scenes``; a flat noiseless still video comes back byte for byte at every
+    setting, a textured one at search == 0; and at the default strength a blotch of 80 luma levels on one frame of such a video
+    is neither spread nor removed -- that is the detectors' job.  No frame, no pixel, max_change == 0 or every frame alone in its
+    scene computes no flows and runs no launch.
+
+    Known limits: two neighbours only -- a second pass over the result with the same ``flows`` is the caller's
+    choice; the net's flows are computed on the noisy frames; what the step does for the detectors downstream has not been
+    measured; there is no real noisy tape among the fixtures, the figures are for Gaussian noise laid over a clean clip.
+    strength in [1, 64], search in [0, 2], max_change in [0, 255]: integers, no bools; a string for ``scenes`` is refused;
+    H W < 2^31 - 256.  Argument errors are ValueErrors that name the argument, raised before any device work.  There is no CPU
+    path."""
+    scene_of, strength, search, max_change = _check_denoise_args(model, frames_u8, flows, scenes, strength, search, max_change)
+    L, H, W = (int(v) for v in frames_u8.shape[:3])
+    if L == 0 or H * W == 0 or max_change == 0 or not bool((scene_of[1:] == scene_of[:-1]).any()):
+        return frames_u8.clone() if isinstance(frames_u8, torch.Tensor) else np.array(frames_u8)
+    device = _tool_device("denoise", device, frames_u8, model)
+    out, = _like_input(frames_u8, _denoise_device(model, _upload(frames_u8, device), flows, scene_of, strength, search, max_change))
+    return out
+
+
 YuvFormat =collections.namedtuple("YuvFormat", "layout matrix full_range chroma")
 YUV_MATRICES = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}         # (Kr, Kb)
 

@@ -532,6 +532,34 @@ int e2fgvi_weave_apply(const uint8_t* frames, const int32_t* shift, uint8_t* out
 int e2fgvi_interlace_scores(const uint8_t* frames, const int32_t* scene, int64_t* D, int32_t L, int32_t H, int32_t W, void* stream);
 int e2fgvi_deinterlace(const uint8_t* frames, const int32_t* scene, uint8_t* out, int32_t L, int32_t H, int32_t W, int32_t tff,
                        int32_t mode, int32_t guard, int32_t edges, void* stream);
+/* Temporal denoiser (video.denoise): a pixel becomes the weighted mean of itself and of the pixels its flows point at in the frame
+ * before and the frame after, each weighted by how well the 3 x 3 luma patch around it matches the pixel's own.  All integers after
+ * one floor; >> of a negative number is the arithmetic shift, / of integers the floor.
+ *   frames uint8 [L,H,W,3];  fwd, bwd fp32 [L-1,H,W,2], 8-byte aligned, in e2fgvi_defect_candidates' convention;  scene int32 [L]:
+ *   two frames are in one scene when their entries are equal.  Y = (77 R + 150 G + 29 B + 128) >> 8.
+ *   Parameters h = strength in [1, 64], s = search in [0, 2], limit = max_change in [0, 255];  m = (65536 + (9 h) / 2) / (9 h).
+ * For centre frame t and pixel p = (x, y) there are two neighbours: A is frame t-1 with g = bwd[t-1], B is frame t+1 with g = fwd[t],
+ * both read on frame t's grid.  A neighbour outside the video or in another scene contributes nothing.  Per neighbour N that exists:
+ * 1. q = (x + g_x(p), y + g_y(p)) in fp64;  inside = g(p) finite and 0 <= q_x <= W-1 and 0 <= q_y <= H-1, decided in floating
+ *    point before any conversion;  r = floor(q + 0.5).  A pixel that is not inside takes nothing from N.
+ * 2. The candidates are c = r + (i, j), -s <= i, j <= s, whose centre lies in the frame (one that does not is dropped, not clamped).
+ * 3. SAD(c) = the sum over u, v in {-1, 0, 1} of |Y_t(clamp(p + (u, v))) - Y_N(clamp(c + (u, v)))|, taps clamped to the frame on
+ *    both sides.
+ * 4. w(c) = max(0, 256 - ((SAD(c) m) >> 8)).
+ * Wsum = 256 + the sum of w(c) over both neighbours' candidates;  per channel k: acc_k = 256 C_k(p) + the sum of w(c) N_k(c);
+ * o_k = (acc_k + (Wsum >> 1)) / Wsum;  out_k = clamp(o_k, C_k(p) - limit, C_k(p) + limit).  All decisions are on luma, so a
+ * pixel's three channels share their weights.  Every output byte is written once; out must not overlap frames (E2FGVI_EINVAL).
+ * All intermediates fit int32: SAD m < 2^25, Wsum <= 13056, acc < 2^22.
+ * work: a device buffer of at least L (H + 8) (((W + 11) & ~3) + 4) bytes, 4-byte aligned, that overlaps neither frames nor out:
+ * the entry writes the luma of every frame into it first (one launch) and the filter reads it (one launch); its contents
+ * afterwards are not part of the contract.  work_bytes is its size.  Nothing is read on the host.
+ * Sizes >= 0, H W < 2^31 - 256, parameters in their ranges (E2FGVI_EINVAL otherwise, from the arguments alone); L, H or W == 0
+ * returns 0 without a launch and without looking at the pointers; a null or misaligned pointer with work, or a work buffer that
+ * is too small, is E2FGVI_EINVAL.  L == 1 has no neighbour: out = frames, and fwd, bwd and work are not looked at.  Frames are
+ * launched in slabs of 65535. */
+int e2fgvi_denoise(const uint8_t* frames, const float* fwd, const float* bwd, const int32_t* scene, uint8_t* out, uint8_t* work,
+                   int64_t work_bytes, int32_t L, int32_t H, int32_t W, int32_t strength, int32_t search, int32_t max_change,
+                   void* stream);
 
 /* conv_offset post-processing of SecondOrderDeformableAlignment (feat_prop.py:38-53) fused into the conv that produces
  * it: `residual` must point to the per-pixel flows [P,4] = (u1,v1,u2,v2) with res_ld = 4, `slope` = max_residue:
