@@ -282,6 +282,7 @@ extern "C" int64_t e2fgvi_psnr_ssim_workspace(int32_t N, int32_t H, int32_t W) {
 extern "C" int e2fgvi_psnr_ssim(const float* img1, const float* img2, int32_t N, int32_t H, int32_t W, int32_t win_size,
                                 void* workspace, double* out, void* stream) {
     E2_REQUIRE(img1 && img2 && workspace && out && N > 0 && H > 0 && W > 0, E2FGVI_EINVAL, "psnr_ssim: bad arguments");
+    E2_REQUIRE(N <= 65535, E2FGVI_EINVAL, "psnr_ssim: at most 65535 image pairs per call (the grid's y axis), got %d", N);
     E2_REQUIRE(win_size >= 3 && (win_size & 1) && win_size <= H && win_size <= W, E2FGVI_EINVAL,
                "psnr_ssim: win_size must be odd, >= 3 and <= min(H, W)");
     E2_REQUIRE(((uintptr_t)workspace & 7) == 0, E2FGVI_EINVAL, "psnr_ssim: workspace must be 8-byte aligned");

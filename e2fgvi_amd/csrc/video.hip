@@ -6,7 +6,17 @@
 namespace {
 
 constexpr int NTH = 256;
-inline unsigned blocks_for(long long n) { return (unsigned)((n + NTH - 1) / NTH); }
+// A launch holds fewer than 2^32 threads: the runtime keeps 32 bits of their number and runs `threads mod 2^32` of them without an
+// error (float_to_u8 of 2^32 + 624 704 floats converted the first 624 896).  So the grid of a thread-per-element kernel is capped
+// below that and its threads stride over what is left; up to 2^32 - 256 elements that is one element a thread, as before.
+constexpr long long GRID_BLOCKS_MAX = (1LL << 24) - 1;
+inline unsigned blocks_for(long long n) {
+    const long long b = (n + NTH - 1) / NTH;
+    return (unsigned)(b < GRID_BLOCKS_MAX ? b : GRID_BLOCKS_MAX);
+}
+// for (long long idx : the elements of this thread): the first is the thread's number in the grid, the step the grid's threads
+#define E2_GRID_STRIDE(idx, n) \
+    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < (n); idx += (long long)gridDim.x * blockDim.x)
 
 // Mask preparation (test.py:56-69): NEAREST resize to the frame size, binarise (> 0), 4x dilation with the 3x3 cross.
 // The source row / column of every output row / column comes in as a table (Pillow builds the same tables in
@@ -16,49 +26,49 @@ inline unsigned blocks_for(long long n) { return (unsigned)((n + NTH - 1) / NTH)
 __global__ void mask_prepare_kernel(const unsigned char* __restrict__ src, int Lsrc, const int* __restrict__ ids, int Hin, int Win,
                                     const int* __restrict__ ytab, const int* __restrict__ xtab, unsigned char* __restrict__ dst, int L,
                                     int H, int W, int iters) {
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (long long)L * H * W) return;
-    const int x = (int)(idx % W);
-    const int y = (int)((idx / W) % H);
-    const int l = (int)(idx / ((long long)W * H));
-    const int ls = ids ? ids[l] : l;
-    if (ls < 0 || ls >= Lsrc) { dst[idx] = 0; return; }
-    const unsigned char* s = src + (long long)ls * Hin * Win;
-    // `iters` dilations with the 3x3 cross = OR over the L1 ball of that radius, clipped to the image
-    // (cv2.dilate ignores out-of-image pixels; test.py:64-68)
-    int hit = 0;
-    for (int dy = -iters; dy <= iters && !hit; ++dy) {
-        const int yy = y + dy;
-        if (yy < 0 || yy >= H) continue;
-        const long long row = (long long)ytab[yy] * Win;
-        const int r = iters - (dy < 0 ? -dy : dy);
-        for (int dx = -r; dx <= r; ++dx) {
-            const int xx = x + dx;
-            if (xx < 0 || xx >= W) continue;
-            if (s[row + xtab[xx]] != 0) { hit = 1; break; }
+    E2_GRID_STRIDE(idx, (long long)L * H * W) {
+        const int x = (int)(idx % W);
+        const int y = (int)((idx / W) % H);
+        const int l = (int)(idx / ((long long)W * H));
+        const int ls = ids ? ids[l] : l;
+        if (ls < 0 || ls >= Lsrc) { dst[idx] = 0; continue; }
+        const unsigned char* s = src + (long long)ls * Hin * Win;
+        // `iters` dilations with the 3x3 cross = OR over the L1 ball of that radius, clipped to the image
+        // (cv2.dilate ignores out-of-image pixels; test.py:64-68)
+        int hit = 0;
+        for (int dy = -iters; dy <= iters && !hit; ++dy) {
+            const int yy = y + dy;
+            if (yy < 0 || yy >= H) continue;
+            const long long row = (long long)ytab[yy] * Win;
+            const int r = iters - (dy < 0 ? -dy : dy);
+            for (int dx = -r; dx <= r; ++dx) {
+                const int xx = x + dx;
+                if (xx < 0 || xx >= W) continue;
+                if (s[row + xtab[xx]] != 0) { hit = 1; break; }
+            }
         }
+        dst[idx] = (unsigned char)hit;
     }
-    dst[idx] = (unsigned char)hit;
 }
 
 // masked, normalised, mirror-padded clip (test.py:146-165): out[ti][c][y][x] = (frame/255*2-1) * (1 - mask), rows / columns
 // past the frame take the flipped image (cat([x, flip(x)])[: h + pad])
 __global__ void masked_clip_kernel(const unsigned char* __restrict__ frames, const unsigned char* __restrict__ masks,
                                    const int* __restrict__ ids, float* __restrict__ out, int t, int H, int W, int Hp, int Wp) {
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (long long)t * 3 * Hp * Wp) return;
-    const int x = (int)(idx % Wp);
-    long long r = idx / Wp;
-    const int y = (int)(r % Hp);
-    r /= Hp;
-    const int c = (int)(r % 3);
-    const int ti = (int)(r / 3);
-    const int sy = y < H ? y : 2 * H - 1 - y;
-    const int sx = x < W ? x : 2 * W - 1 - x;
-    const long long pix = ((long long)ids[ti] * H + sy) * W + sx;
-    const float v = ((float)frames[pix * 3 + c] / 255.0f) * 2.0f - 1.0f;
-    const float m = (float)masks[pix];
-    out[idx] = v * (1.0f - m);
+    E2_GRID_STRIDE(idx, (long long)t * 3 * Hp * Wp) {
+        const int x = (int)(idx % Wp);
+        long long r = idx / Wp;
+        const int y = (int)(r % Hp);
+        r /= Hp;
+        const int c = (int)(r % 3);
+        const int ti = (int)(r / 3);
+        const int sy = y < H ? y : 2 * H - 1 - y;
+        const int sx = x < W ? x : 2 * W - 1 - x;
+        const long long pix = ((long long)ids[ti] * H + sy) * W + sx;
+        const float v = ((float)frames[pix * 3 + c] / 255.0f) * 2.0f - 1.0f;
+        const float m = (float)masks[pix];
+        out[idx] = v * (1.0f - m);
+    }
 }
 
 // compositing + 0.5/0.5 blending of overlapping windows (test.py:168-179):
@@ -66,23 +76,23 @@ __global__ void masked_clip_kernel(const unsigned char* __restrict__ frames, con
 __global__ void composite_kernel(const float* __restrict__ pred, const int* __restrict__ ids, const unsigned char* __restrict__ first,
                                  const unsigned char* __restrict__ frames, const unsigned char* __restrict__ masks,
                                  float* __restrict__ comp, int n, int H, int W, int Hp, int Wp) {
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (long long)n * H * W * 3) return;
-    const int c = (int)(idx % 3);
-    long long r = idx / 3;
-    const int x = (int)(r % W);
-    r /= W;
-    const int y = (int)(r % H);
-    const int i = (int)(r / H);
-    const int f = ids[i];
-    const long long pix = ((long long)f * H + y) * W + x;
-    unsigned char img = frames[pix * 3 + c];
-    if (masks[pix]) {
-        const float p = pred[(((long long)i * 3 + c) * Hp + y) * Wp + x];
-        img = (unsigned char)(int)(((p + 1.0f) / 2.0f) * 255.0f);
+    E2_GRID_STRIDE(idx, (long long)n * H * W * 3) {
+        const int c = (int)(idx % 3);
+        long long r = idx / 3;
+        const int x = (int)(r % W);
+        r /= W;
+        const int y = (int)(r % H);
+        const int i = (int)(r / H);
+        const int f = ids[i];
+        const long long pix = ((long long)f * H + y) * W + x;
+        unsigned char img = frames[pix * 3 + c];
+        if (masks[pix]) {
+            const float p = pred[(((long long)i * 3 + c) * Hp + y) * Wp + x];
+            img = (unsigned char)(int)(((p + 1.0f) / 2.0f) * 255.0f);
+        }
+        const float v = (float)img;
+        comp[pix * 3 + c] = first[i] ? v : comp[pix * 3 + c] * 0.5f + v * 0.5f;
     }
-    const float v = (float)img;
-    comp[pix * 3 + c] = first[i] ? v : comp[pix * 3 + c] * 0.5f + v * 0.5f;
 }
 
 // Frame resize (test.py:97-104,127, core/dataset.py:115): one separable pass of Pillow's 8-bit BICUBIC resample along H
@@ -141,37 +151,37 @@ __global__ void resample_u8_kernel(const unsigned char* __restrict__ src, int Ls
 }
 
 __global__ void float_to_u8_kernel(const float* __restrict__ src, unsigned char* __restrict__ dst, long long n) {
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx < n) dst[idx] = (unsigned char)(int)src[idx];
+    E2_GRID_STRIDE(idx, n) dst[idx] = (unsigned char)(int)src[idx];
 }
 
 // ndarray.astype(float32) of uint8 frames: the source-size accumulator of inpaint_video(region="track") starts as the source.
 // Four bytes per thread: one 32-bit load and one 16-byte store when VEC (both bases aligned), the last n % 4 bytes one by one.
 template <bool VEC>
 __global__ void u8_to_float_kernel(const unsigned char* __restrict__ src, float* __restrict__ dst, long long n) {
-    const long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-    if (i >= n) return;
-    if (VEC && i + 4 <= n) {
-        const unsigned q = *reinterpret_cast<const unsigned*>(src + i);
-        *reinterpret_cast<float4*>(dst + i) = make_float4((float)(q & 255u), (float)((q >> 8) & 255u), (float)((q >> 16) & 255u),
-                                                          (float)(q >> 24));
-    } else {
-        for (long long k = i; k < n && k < i + 4; ++k) dst[k] = (float)src[k];
+    E2_GRID_STRIDE(g, (n + 3) / 4) {
+        const long long i = g * 4;
+        if (VEC && i + 4 <= n) {
+            const unsigned q = *reinterpret_cast<const unsigned*>(src + i);
+            *reinterpret_cast<float4*>(dst + i) = make_float4((float)(q & 255u), (float)((q >> 8) & 255u), (float)((q >> 16) & 255u),
+                                                              (float)(q >> 24));
+        } else {
+            for (long long k = i; k < n && k < i + 4; ++k) dst[k] = (float)src[k];
+        }
     }
 }
 
 // model output NCHW float in (-1,1) -> NHWC uint8 (what test.py:168-171 turns a prediction into), cropped to H x W
 __global__ void pred_to_u8_kernel(const float* __restrict__ pred, unsigned char* __restrict__ dst, int N, int H, int W, int Hp, int Wp) {
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (long long)N * H * W * 3) return;
-    const int c = (int)(idx % 3);
-    long long r = idx / 3;
-    const int x = (int)(r % W);
-    r /= W;
-    const int y = (int)(r % H);
-    const int n = (int)(r / H);
-    const float p = pred[(((long long)n * 3 + c) * Hp + y) * Wp + x];
-    dst[idx] = (unsigned char)(int)(((p + 1.0f) / 2.0f) * 255.0f);
+    E2_GRID_STRIDE(idx, (long long)N * H * W * 3) {
+        const int c = (int)(idx % 3);
+        long long r = idx / 3;
+        const int x = (int)(r % W);
+        r /= W;
+        const int y = (int)(r % H);
+        const int n = (int)(r / H);
+        const float p = pred[(((long long)n * 3 + c) * Hp + y) * Wp + x];
+        dst[idx] = (unsigned char)(int)(((p + 1.0f) / 2.0f) * 255.0f);
+    }
 }
 
 // Frame slabs between a cache and a window (test.py:152: the frames of a window are picked by id out of the whole video;
@@ -659,8 +669,7 @@ __global__ __launch_bounds__(NTH) void restore_u8_kernel(
 constexpr int BB_WAVES = NTH / 64;
 
 __global__ void bbox_init_kernel(int* __restrict__ box, long long n) {
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx < n) box[idx] = (idx & 3) < 2 ? 0x7f7f7f7f : 0;
+    E2_GRID_STRIDE(idx, n) box[idx] = (idx & 3) < 2 ? 0x7f7f7f7f : 0;
 }
 
 __device__ __forceinline__ void bbox_word(unsigned v, int x, int& lo, int& hi) {

@@ -295,7 +295,7 @@ extern "C" int e2fgvi_yuv420_to_rgb(const uint8_t* yuv, uint8_t* rgb, int32_t L,
     const YuvDec c = {coef[0], coef[1], coef[2], coef[3], coef[4], coef[5]};
     const int nsx = (W + YUV_PX - 1) / YUV_PX, ngr = (H / 2 + YUV_ROWS - 1) / YUV_ROWS;
     const long long total = (long long)L * ngr * nsx, blocks = (total + NTH - 1) / NTH;
-    E2_REQUIRE(blocks < (1LL << 31), E2FGVI_EINVAL, "yuv420_to_rgb: %d frames of %d x %d are too many for one launch", L, H, W);
+    E2_REQUIRE(blocks < (1LL << 24), E2FGVI_EINVAL, "yuv420_to_rgb: %d frames of %d x %d are too many for one launch", L, H, W);   // < 2^32 threads
     const dim3 grid((unsigned)blocks), block(NTH);
     hipStream_t st = (hipStream_t)stream;
     const int i420 = layout == E2FGVI_YUV_I420;
@@ -319,7 +319,7 @@ extern "C" int e2fgvi_rgb_to_yuv420(const uint8_t* rgb, const uint8_t* like_rgb,
     const YuvEnc c = {coef[0], coef[1], coef[2], coef[3], coef[4], coef[5], coef[6], coef[7], coef[8], coef[9]};
     const int nsx = (W + YUV_PX - 1) / YUV_PX;
     const long long total = (long long)L * (H / 2) * nsx, blocks = (total + NTH - 1) / NTH;
-    E2_REQUIRE(blocks < (1LL << 31), E2FGVI_EINVAL, "rgb_to_yuv420: %d frames of %d x %d are too many for one launch", L, H, W);
+    E2_REQUIRE(blocks < (1LL << 24), E2FGVI_EINVAL, "rgb_to_yuv420: %d frames of %d x %d are too many for one launch", L, H, W);   // < 2^32 threads
     const dim3 grid((unsigned)blocks), block(NTH);
     hipStream_t st = (hipStream_t)stream;
     const int i420 = layout == E2FGVI_YUV_I420;

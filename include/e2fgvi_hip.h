@@ -245,6 +245,7 @@ int e2fgvi_rgb_to_yuv420(const uint8_t* rgb, const uint8_t* like_rgb, const uint
  * [0,255]: out[2n] = PSNR (inf when identical), out[2n+1] = SSIM as skimage compare_ssim(data_range=255,
  * multichannel=True, win_size) computes it (uniform window, sample covariance, K1 .01, K2 .03, crop (win-1)/2).
  * fp64 like the reference.  workspace: e2fgvi_psnr_ssim_workspace(N,H,W) bytes, caller-owned.
+ * N <= 65535 pairs per call (they ride on the grid's y axis); more is E2FGVI_EINVAL.
  * ------------------------------------------------------------------------------------------------ */
 int64_t e2fgvi_psnr_ssim_workspace(int32_t N, int32_t H, int32_t W);
 int e2fgvi_psnr_ssim(const float* img1, const float* img2, int32_t N, int32_t H, int32_t W, int32_t win_size,

@@ -125,16 +125,21 @@ def test_resample_u8_checks_its_arguments(dev):
 
 @pytest.mark.gpu
 def test_resize_frames_beyond_2gib(dev):
-    """a source of more than 2**31 bytes (360 frames of 1920x1080): 64-bit indexing; first, middle and last frame == PIL"""
-    L, H, W, size = 360, 1080, 1920, (1296, 720)
+    """a source of more than 2**32 bytes (700 frames of 1920x1080): 64-bit indexing; the first frame, the frames that hold byte
+    offsets 2**31 and 2**32 of the source, their neighbours and the last frame == PIL"""
+    L, H, W, size = 700, 1080, 1920, (1296, 720)
     g = torch.Generator(device=dev).manual_seed(5)
     src = torch.randint(0, 256, (L, H, W, 3), dtype=torch.uint8, device=dev, generator=g)
-    assert src.numel() > 2 ** 31
+    frame = H * W * 3
+    at31, at32 = 2 ** 31 // frame, 2 ** 32 // frame
+    assert src.numel() > 2 ** 32 + 2 * frame and 2 ** 32 % frame != 0 and at32 < L - 2
     src[:, : H // 2, : W // 2] = 128                                  # a flat quadrant next to the noise
     out = video.resize_frames(src, size)
     assert tuple(out.shape) == (L, 720, 1296, 3)
-    for i in (0, L // 2, L - 1):
+    for i in (0, at31, at31 + 1, L // 2, at32 - 1, at32, at32 + 1, L - 1):
         assert np.array_equal(out[i].cpu().numpy(), _pil(src[i].cpu().numpy(), size)), i
+    # the frame a 32-bit offset would read in the place of the one at 2**32 is another picture
+    assert not torch.equal(src[at32 + 1], src[0]) and not torch.equal(out[at32 + 1], out[0])
     del src, out
     torch.cuda.empty_cache()
 
