@@ -41,8 +41,10 @@ UNITS = [("error.hip", "error.o", []), ("conv.hip", "conv.o", []), ("conv.hip", 
          ("flicker.hip", "flicker.o", NOPK),
          ("weave.hip", "weave.o", NOPK),
          ("interlace.hip", "interlace.o", NOPK),
-         ("denoise.hip", "denoise.o", NOPK)]
-NOPK_OBJECTS = ("conv_nopk.o", "conv_bf16x.o", "conv_wino.o", "conv_wino4.o", "conv_wino_x3.o", "conv_tail.o", "mdcn.o", "attention_bf16.o", "attention_x3.o", "misc.o", "video.o", "yuv.o", "metrics.o", "mask_track.o", "defects.o", "pixel_track.o", "grain.o", "line_scratch.o", "flicker.o", "weave.o", "interlace.o", "denoise.o")
+         ("denoise.hip", "denoise.o", NOPK),
+         # the same: the restatement of tests/interpolate_cases.py matches the trajectories bit for bit
+         ("interpolate.hip", "interpolate.o", NOPK + ["-ffp-contract=off"])]
+NOPK_OBJECTS = ("conv_nopk.o", "conv_bf16x.o", "conv_wino.o", "conv_wino4.o", "conv_wino_x3.o", "conv_tail.o", "mdcn.o", "attention_bf16.o", "attention_x3.o", "misc.o", "video.o", "yuv.o", "metrics.o", "mask_track.o", "defects.o", "pixel_track.o", "grain.o", "line_scratch.o", "flicker.o", "weave.o", "interlace.o", "denoise.o", "interpolate.o")
 OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 
 
@@ -105,10 +107,12 @@ def build(force=False, verbose=False, nopk_all=False, lib=None, tag=None, define
             verify_no_scratch(objdir, "weave.o", "weave_", "weave stabiliser")
             verify_no_scratch(objdir, "interlace.o", "interlace_", "deinterlacer")
             verify_no_scratch(objdir, "denoise.o", "denoise_", "temporal denoiser")
+            verify_no_scratch(objdir, "interpolate.o", "interpolate_", "frame interpolation")
             verify_overlay_prefetch(objdir)
             verify_no_pk_u8(objdir)
             verify_no_fma64(objdir)
             verify_no_fma64(objdir, "pixel_track.o")
+            verify_no_fma64(objdir, "interpolate.o")
     return out
 
 
@@ -151,7 +155,8 @@ def verify_isa(objdir=None):
 
 def verify_no_fma64(objdir=None, obj="mask_track.o"):
     """mask_track_step_kernel (csrc/mask_track.hip) does its fp64 arithmetic in the order written, one rounding per operation: the
-    numpy restatement of the tests matches it bit for bit (and so do the two kernels of csrc/pixel_track.hip, obj="pixel_track.o").  The unit is built with -ffp-contract=off; a fused multiply-add in its
+    numpy restatement of the tests matches it bit for bit (and so do the two kernels of csrc/pixel_track.hip, obj="pixel_track.o",
+    and the kernel of csrc/interpolate.hip, obj="interpolate.o", which for that reason takes its quotients k / d from a table).  The unit is built with -ffp-contract=off; a fused multiply-add in its
     code would mean the flag was lost (or an expression was rewritten into fma()).  Returns the number of fp64 multiplies read."""
     import re
     objdir = objdir or os.path.join(CSRC, "build")
@@ -195,7 +200,8 @@ def verify_no_scratch(objdir=None, obj="conv_bf16x.o", marker="ELb0ELi2ELb1EEE",
     and over the three of flicker.o (the histogram and the apply kernel hold the dwords of all of a thread's groups at once);
     and over the five of weave.o (the apply kernel shifts the dwords of two tap rows into place in small arrays);
     and over the three of interlace.o (the fields kernel holds the dwords and the luma of up to twelve groups in small arrays);
-    and over the four of denoise.o (the filter kernel keeps the 7 x 5 three-byte runs of a neighbour's luma window in a small array)."""
+    and over the four of denoise.o (the filter kernel keeps the 7 x 5 three-byte runs of a neighbour's luma window in a small array);
+    and over the one of interpolate.o (it runs two fp64 fixed-point searches and up to four colour taps for each of a thread's four pixels)."""
     import re
     import shutil
     import tempfile

@@ -165,6 +165,7 @@ SYMBOLS = {
     "e2fgvi_interlace_scores": (C.c_int, [_fp] * 3 + [_i32] * 3 + [_fp]),
     "e2fgvi_deinterlace": (C.c_int, [_fp] * 3 + [_i32] * 7 + [_fp]),
     "e2fgvi_denoise": (C.c_int, [_fp] * 6 + [_i64] + [_i32] * 6 + [_fp]),
+    "e2fgvi_interpolate": (C.c_int, [_fp] * 6 + [_i32] * 8 + [_fp]),
     "e2fgvi_softcomp_fold": (C.c_int, [_fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _fp]),
     "e2fgvi_focal_attention_16": (C.c_int, [_fp, _fp, _fp, _i32, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _fp]),
     "e2fgvi_focal_attention_16_variant": (C.c_int, [C.c_int]),

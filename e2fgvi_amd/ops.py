@@ -2572,6 +2572,80 @@ def denoise(frames, fwd, bwd, scene, strength, search, max_change, out=None):
     return ou
 
 
+INTERPOLATE_ITERATIONS_MAX = 8             # csrc/interpolate.hip: parameters outside these ranges are E2FGVI_EINVAL
+INTERPOLATE_TOLERANCE_MAX = 255
+INTERPOLATE_MATCH_MAX = 765
+INTERPOLATE_D_MAX = 64
+INTERPOLATE_PIXELS_MAX = DENOISE_PIXELS_MAX
+
+
+def interpolate_jobs_ok(jobs, L, P):
+    """whether every row (ia, ib, fi, k, d) of a host job table lies in its ranges for L frames and P flow pairs (rows that do
+    not are skipped by the kernel: csrc/interpolate.hip)"""
+    return all(0 <= ia < L and 0 <= ib < L and 0 <= fi < P and 1 <= d <= INTERPOLATE_D_MAX and 0 <= k <= d
+               for ia, ib, fi, k, d in jobs)
+
+
+def interpolate(frames, fwd, bwd, jobs, iterations, tolerance, match, out=None, source=None):
+    """Frames at fractional times between frames, gathered along the flows (csrc/interpolate.hip; include/e2fgvi_hip.h has the
+    definition; video.retime and video.replace_frames are the callers): frames uint8 [L,H,W,3]; fwd, bwd fp32 [P,H,W,2], P flow
+    pairs in metrics.warp_error's convention; jobs int32 [n,5] of (ia, ib, fi, k, d): output frame j is the picture at time k / d
+    between frames[ia] and frames[ib], with fwd[fi] the motion ia -> ib on ia's grid and bwd[fi] the motion back on ib's grid
+    -> device uint8 [n,H,W,3], and with ``source`` (True, or a device uint8 [n,H,W] to write into) the pair (out, source):
+    5 = a copy (k == 0 or k == d), 1 / 2 = both ends seen and matched, found from ia's / ib's side, 3 / 4 = seen in ia / ib alone,
+    0 = no trajectory reached the pixel and it is the cross-fade.  One call of the entry, all jobs in one launch per 65535, no host
+    read.  iterations in [0, 8] fixed-point steps, tolerance in [0, 255] sixteenths of a pixel, match in [0, 765] grey levels summed
+    over the channels: integers, no bools.  A job outside its ranges (d in [1, 64], k in [0, d]) writes nothing on the device; a job
+    table that is given on the host is checked here and refused (ValueError).  ``out``: a device tensor [n,H,W,3] to write into,
+    which must not overlap ``frames`` (the entry refuses it).  Device tensors, or anything torch.as_tensor accepts (uploaded first);
+    wrong dtypes, shapes that do not fit, non-contiguous inputs and tensors on different devices raise ValueError.  There is no CPU
+    path.  No atomics: the same inputs give the same bytes in every run."""
+    lib = _L.load()
+    iterations = _int_arg("iterations", iterations, 0, INTERPOLATE_ITERATIONS_MAX)
+    tolerance = _int_arg("tolerance", tolerance, 0, INTERPOLATE_TOLERANCE_MAX)
+    match = _int_arg("match", match, 0, INTERPOLATE_MATCH_MAX)
+    want_source = source is not None and source is not False
+    host_jobs = None
+    if not (isinstance(jobs, torch.Tensor) and jobs.is_cuda):          # a table on the host: its ranges are checked below
+        host_jobs = torch.as_tensor(jobs)
+        if not hasattr(jobs, "dtype") and host_jobs.dtype == torch.int64:
+            jobs = host_jobs.to(torch.int32)                            # rows of Python ints; the ranges are checked on host_jobs
+    named = [("frames", frames, torch.uint8), ("fwd", fwd, torch.float32), ("bwd", bwd, torch.float32), ("jobs", jobs, torch.int32)]
+    if out is not None:
+        named.append(("out", out, torch.uint8))
+    if want_source and source is not True:
+        named.append(("source", source, torch.uint8))
+    up = _device_inputs(named, "frames", written=("out", "source"))
+    fr, fw, bw, jb = up[:4]
+    L, H, W = _frames_shape(fr, "frames")
+    if H * W > INTERPOLATE_PIXELS_MAX:
+        raise ValueError("frames must have H W < 2^31 - 256, got %d x %d" % (H, W))
+    if fw.dim() != 4 or tuple(fw.shape[1:]) != (H, W, 2):
+        raise ValueError("fwd must be [P,%d,%d,2] for frames %s, got %s" % (H, W, tuple(fr.shape), tuple(fw.shape)))
+    P = fw.shape[0]
+    if tuple(bw.shape) != (P, H, W, 2):
+        raise ValueError("bwd must be [%d,%d,%d,2] like fwd, got %s" % (P, H, W, tuple(bw.shape)))
+    if jb.dim() != 2 or jb.shape[1] != 5:
+        raise ValueError("jobs must be int32 [n,5] of (ia, ib, fi, k, d), got %s" % (tuple(jb.shape),))
+    n = jb.shape[0]
+    if host_jobs is not None and not interpolate_jobs_ok(host_jobs.tolist(), L, P):
+        raise ValueError("jobs: every row (ia, ib, fi, k, d) needs ia, ib in [0, %d), fi in [0, %d), d in [1, %d] and k in [0, d]"
+                         % (L, P, INTERPOLATE_D_MAX))
+    rest = up[4:]
+    if out is not None and tuple(rest[0].shape) != (n, H, W, 3):
+        raise ValueError("out must be [%d,%d,%d,3], got %s" % (n, H, W, tuple(rest[0].shape)))
+    if want_source and source is not True and tuple(rest[-1].shape) != (n, H, W):
+        raise ValueError("source must be [%d,%d,%d], got %s" % (n, H, W, tuple(rest[-1].shape)))
+    with torch.cuda.device(fr.device):
+        ou = rest[0] if out is not None else torch.empty((n, H, W, 3), dtype=torch.uint8, device=fr.device)
+        so = None
+        if want_source:
+            so = rest[-1] if source is not True else torch.empty((n, H, W), dtype=torch.uint8, device=fr.device)
+        _L.check(lib.e2fgvi_interpolate(_ptr(fr), _ptr(fw), _ptr(bw), _ptr(jb), _ptr(ou), _ptr(so), n, L, P, H, W, iterations,
+                                        tolerance, match, _stream()), "interpolate")
+    return (ou, so) if want_source else ou
+
+
 YUV_LAYOUTS ={"nv12": 0, "i420": 1}     # E2FGVI_YUV_*/ E2FGVI_CHROMA_* of include/e2fgvi_hip.h
 YUV_CHROMA = {"left": 0, "nearest": 1}
 

@@ -1664,6 +1664,251 @@ def denoise(model, frames_u8, flows=None, scenes=None, strength=DENOISE_STRENGTH
     return out
 
 
+INTERPOLATE_ITERATIONS = 3     # retime's and replace_frames' defaults: DESIGN.md 3y has the measurements they were judged on
+INTERPOLATE_TOLERANCE = 8
+INTERPOLATE_MATCH = 96
+
+
+def _check_rate(rate):
+    """rate= as (num, den): an integer m is (m, 1); both in [1, INTERPOLATE_D_MAX]; ValueError otherwise"""
+    pair = (rate, 1) if _integer(rate, typed=True) else rate
+    try:
+        ok = len(pair) == 2 and all(_integer(v, 1, ops.INTERPOLATE_D_MAX, typed=True) for v in pair)
+    except TypeError:
+        ok = False
+    if not ok:
+        raise ValueError("rate must be an integer or (num, den), each in [1, %d], got %r" % (ops.INTERPOLATE_D_MAX, rate))
+    return int(pair[0]), int(pair[1])
+
+
+def plan_retime(length, rate, scenes=None):
+    """The output frames of retime for a video of ``length`` frames, host logic: ``rate`` is an integer m (m frames for one) or
+    (num, den); output frame j shows the source time j den / num, and there are (length - 1) num // den + 1 of them.  Returns
+    (jobs, pairs): jobs is a list of rows (ia, ib, fi, k, d) for ops.interpolate -- frame j lies in the pair t = j den // num at
+    the fraction k / d = (j den mod num) / num and is the row (t, t + 1, fi, k, d), or (t, t, 0, 0, d) when k == 0 -- and pairs is
+    the increasing list of the pairs t that are interpolated, fi the place of t in it: the only pairs whose flows are needed.
+    ``scenes``: None or a list of cuts as plan_windows takes them; a pair that straddles a cut is not interpolated, its frames are
+    copies of the nearer frame: the earlier one while 2 k < d, else the later one."""
+    length = int(length)
+    if length < 0:
+        raise ValueError("length must be >= 0, got %d" % length)
+    num, den = _check_rate(rate)
+    cuts = set(_scene_cuts(scenes, length))
+    rows = []
+    for j in range((length - 1) * num // den + 1 if length else 0):
+        t, k = divmod(j * den, num)
+        if k and t + 1 in cuts:
+            t, k = (t, 0) if 2 * k < num else (t + 1, 0)
+        rows.append((t, k))
+    pairs = sorted({t for t, k in rows if k})
+    fi = {t: i for i, t in enumerate(pairs)}
+    return [(t, t + 1, fi[t], k, num) if k else (t, t, 0, 0, num) for t, k in rows], pairs
+
+
+def _check_bad(bad, length):
+    """bad= as a sorted list of frame numbers: integers in [0, length), each once (an empty list is one); ValueError otherwise"""
+    try:
+        vals = list(bad.tolist() if hasattr(bad, "tolist") else bad)
+        ok = not isinstance(bad, str) and all(_integer(v, 0, length - 1, typed=True) for v in vals) and len(set(vals)) == len(vals)
+    except TypeError:
+        vals, ok = [], False
+    if not ok:
+        raise ValueError("bad must be a list of frame numbers in [0, %d), each once, got %r" % (length, bad))
+    return sorted(int(v) for v in vals)
+
+
+def plan_replace(length, bad, scenes=None):
+    """The runs of frames replace_frames rebuilds in a video of ``length`` frames, host logic: a list of (a, c, ids), one for each
+    maximal run ``ids`` of consecutive frames of ``bad`` inside a scene, with a the good frame in front of it and c the good
+    frame behind it.  With both, frame i of the run is ops.interpolate's row (a, c, r, i - a, c - a), r counting the runs that
+    have both: the picture at the time (i - a) / (c - a) between a and c.  A run that touches its scene's start or end has one
+    good neighbour -- the other is None -- and becomes copies of it.  A scene without a good frame and a run of more than 63
+    frames (c - a may not pass ops.INTERPOLATE_D_MAX) are ValueErrors."""
+    length = int(length)
+    bad = _check_bad(bad, length)
+    cuts = _scene_cuts(scenes, length)
+    isbad = set(bad)
+    runs = []
+    for s0, s1 in zip([0] + cuts, cuts + [length]):
+        i = s0
+        while i < s1:
+            if i not in isbad:
+                i += 1
+                continue
+            e = i
+            while e + 1 < s1 and e + 1 in isbad:
+                e += 1
+            a, c = (i - 1 if i > s0 else None), (e + 1 if e + 1 < s1 else None)
+            if a is None and c is None:
+                raise ValueError("bad: the scene of frames %d to %d has no good frame to rebuild it from" % (s0, s1 - 1))
+            if e - i + 1 > ops.INTERPOLATE_D_MAX - 1:
+                raise ValueError("bad: frames %d to %d are a run of %d, more than %d" % (i, e, e - i + 1, ops.INTERPOLATE_D_MAX - 1))
+            runs.append((a, c, list(range(i, e + 1))))
+            i = e + 1
+    return runs
+
+
+def _replace_jobs(length, runs):
+    """ops.interpolate's rows for all ``length`` frames from plan_replace's runs: a good frame is a copy of itself"""
+    rows = [(i, i, 0, 0, 1) for i in range(length)]
+    r = 0
+    for a, c, ids in runs:
+        for i in ids:
+            rows[i] = (a, c, r, i - a, c - a) if a is not None and c is not None else ((a, a, 0, 0, 1) if c is None else (c, c, 0, 0, 1))
+        r += a is not None and c is not None
+    return rows
+
+
+def _check_interpolate_args(frames_u8, iterations, tolerance, match, return_source):
+    """the checks retime and replace_frames share, from the arguments and the shapes alone -> (shape, iterations, tolerance, match)"""
+    shape = _check_frames(frames_u8, False)
+    if int(shape[1]) * int(shape[2]) > ops.INTERPOLATE_PIXELS_MAX:
+        raise ValueError("frames must have H W < 2^31 - 256, got %d x %d" % (shape[1], shape[2]))
+    params = _check_ranges(("iterations", iterations, 0, ops.INTERPOLATE_ITERATIONS_MAX),
+                           ("tolerance", tolerance, 0, ops.INTERPOLATE_TOLERANCE_MAX), ("match", match, 0, ops.INTERPOLATE_MATCH_MAX))
+    _check_flags(return_source=return_source)
+    return (shape,) + params
+
+
+def _copy_of(frames_u8, return_source):
+    """the result of a call that has nothing to interpolate: a copy of the frames (and source = 5 everywhere), nothing launched;
+    in _like_input's form: a device tensor for a device tensor, numpy arrays for anything else"""
+    if isinstance(frames_u8, torch.Tensor) and frames_u8.is_cuda:
+        out, src = frames_u8.clone(), torch.full(tuple(frames_u8.shape[:3]), 5, dtype=torch.uint8, device=frames_u8.device)
+    else:
+        out = np.array(frames_u8.numpy() if isinstance(frames_u8, torch.Tensor) else frames_u8)
+        src = np.full(tuple(out.shape[:3]), 5, np.uint8)
+    return (out, src) if return_source else out
+
+
+def _interpolate_device(x, fwd, bwd, rows, settings, return_source, like):
+    """one call of ops.interpolate over the rows (the table goes up first) -> the result as the caller gets it"""
+    jobs = torch.tensor(rows, dtype=torch.int32).reshape(-1, 5).to(x.device)
+    if fwd is None:                                                     # copies alone: a pair that no row reads
+        fwd = bwd = torch.empty((1,) + tuple(x.shape[1:3]) + (2,), dtype=torch.float32, device=x.device)
+    res = ops.interpolate(x, fwd, bwd, jobs, *settings, source=True if return_source else None)
+    out = _like_input(like, *(res if return_source else (res,)))
+    return out if return_source else out[0]
+
+
+def _pair_runs(pairs):
+    """an increasing list of pair numbers as [first, last] runs of consecutive ones"""
+    runs = []
+    for t in pairs:
+        if runs and runs[-1][1] == t - 1:
+            runs[-1][1] = t
+        else:
+            runs.append([t, t])
+    return runs
+
+
+@torch.no_grad()
+def retime(model, frames_u8, rate=2, flows=None, scenes=None, iterations=INTERPOLATE_ITERATIONS, tolerance=INTERPOLATE_TOLERANCE,
+           match=INTERPOLATE_MATCH, return_source=False, device=None):
+    """Changes a video's frame rate -- silent film shot at 16 fps to 24, a tape transfer at 25 to 50 -- by making the frames that
+    were never shot, along the motion, where repeating frames judders and cross-fading them ghosts: frames_u8 uint8 [L,H,W,3] (an
+    array or a tensor) -> uint8 [n,H,W,3], a numpy array, or a device tensor when the input is one (which is used where it is).
+    ``rate`` is an integer m (m frames for one: 2 doubles the rate) or (num, den), each in [1, 64] -- (3, 2) takes 16 fps to 24,
+    (1, 2) drops every other frame: output frame j shows the source time j den / num, n = (L - 1) num // den + 1 (plan_retime).
+    A frame that falls on a source frame is that frame, byte for byte.  The flows between adjacent frames are the net's own
+    (metrics.video_flows, only for the pairs a new frame falls in: ``model`` must be the generator, TypeError otherwise) or
+    ``flows`` = (fwd, bwd), fp32 [L-1,H,W,2] in metrics.warp_error's convention -- ``model`` may then be None.  ``scenes``: None
+    or a list of cuts as plan_windows takes them (detect_cuts finds them); nothing is interpolated across a cut, the frames
+    that fall there are copies of the nearer frame.  One upload, the flows, one call of ops.interpolate, no host read; no
+    atomics, so the same arguments give the same bytes in every run (include/e2fgvi_hip.h has the definition).
+
+    A new frame at the fraction k / d between frames A and B: every pixel p asks both frames which of their pixels passes
+    through p at that time -- from A along fwd, from B along bwd, each by ``iterations`` fixed-point steps q <- p - lambda flow(q)
+    -- and a side has landed when q + lambda flow(q) comes back to p within ``tolerance`` sixteenths of a pixel.  A side whose far
+    end lies in the other frame and shows the same colour, to within ``match`` grey levels summed over the channels, is
+    two-ended: the pixel is the mix of its two ends, the better-matching side's first.  Otherwise a side that has landed gives
+    its near end alone -- the place is visible in one frame only, at an occlusion or a frame border -- and where nothing landed
+    the pixel is the cross-fade.  With return_source=True the result is (frames, source), source uint8 [n,H,W]: 5 = a copied
+    frame, 1 / 2 = two-ended from the earlier / later frame's side, 3 / 4 = the earlier / later frame alone, 0 = the cross-fade.
+    source == 0 is the mask to hand to inpaint_video: what no trajectory reached.
+
+    rate == 1 and L < 2 return a copy without a launch.  Known limits: the motion between two frames is taken as a
+    translation of each pixel, linear in time; a thin object that moves by more than its own width can vanish from the middle
+    frame, because both sides then see consistent background; flows computed on damaged neighbours are as good as those
+    neighbours.  iterations in [0, 8], tolerance in [0, 255], match in [0, 765]: integers, no bools; a string for ``scenes`` is
+    refused; H W < 2^31 - 256.  Argument errors are ValueErrors that name the argument, raised before any device work.  There is no
+    CPU path."""
+    shape, iterations, tolerance, match = _check_interpolate_args(frames_u8, iterations, tolerance, match, return_source)
+    L = int(shape[0])
+    rows, pairs = plan_retime(L, rate, scenes)
+    if pairs:
+        _check_flow_source(model, flows, shape, None, "the new frames are made along")
+        if flows is not None and any(str(f.dtype).replace("torch.", "") != "float32" for f in flows):
+            raise ValueError("flows must be (fwd, bwd), both float32, got %s" % ([str(f.dtype) for f in flows],))
+    if L < 2 or (not pairs and [r[0] for r in rows] == list(range(L))):  # every frame is its own copy: rate 1 (or (m, m))
+        return _copy_of(frames_u8, return_source)
+    device = _tool_device("retime", device, frames_u8, model)
+    x = _upload(frames_u8, device)
+    fwd = bwd = None
+    with torch.cuda.device(x.device):
+        if pairs and flows is not None:
+            fwd, bwd = _device_flows(model, x, flows)
+            if len(pairs) != L - 1:
+                at = torch.tensor(pairs, dtype=torch.int64).to(x.device)
+                fwd, bwd = fwd.index_select(0, at), bwd.index_select(0, at)
+        elif pairs:
+            parts = [_device_flows(model, x[a:b + 2], None) for a, b in _pair_runs(pairs)]
+            fwd, bwd = (parts[0][i] if len(parts) == 1 else torch.cat([p[i] for p in parts]) for i in (0, 1))
+        return _interpolate_device(x, fwd, bwd, rows, (iterations, tolerance, match), return_source, frames_u8)
+
+
+@torch.no_grad()
+def replace_frames(model, frames_u8, bad, flows=None, scenes=None, iterations=INTERPOLATE_ITERATIONS, tolerance=INTERPOLATE_TOLERANCE,
+                   match=INTERPOLATE_MATCH, return_source=False, device=None):
+    """Rebuilds whole frames that are ruined -- a torn frame, a splice, a drop-out over the full picture, a flash: what
+    detect_defects refuses on purpose and inpaint_video has no context for -- from their good neighbours along the motion:
+    frames_u8 uint8 [L,H,W,3] (an array or a tensor), ``bad`` a list of frame numbers -> uint8 [L,H,W,3], a numpy array, or a
+    device tensor when the input is one.  Every frame not in ``bad`` is byte for byte the caller's.  A run of bad frames between
+    the good frames a and c is bridged linearly in time: frame i is the picture at the time (i - a) / (c - a) between a and c,
+    made as retime makes a new frame (see there for ``iterations``, ``tolerance``, ``match`` and the source codes).  A run at the
+    start or the end of its scene has one good neighbour and becomes copies of it; a scene without a good frame and a run of more
+    than 63 frames are ValueErrors (plan_replace).  The flows between a and c are the net's own (metrics.video_flows of the two
+    frames as a video: ``model`` must be the generator, TypeError otherwise) or ``flows`` = a list of (fwd, bwd), fp32 [H,W,2] each
+    in metrics.warp_error's convention, one for every run with two good neighbours, in plan_replace's order -- ``model`` may then
+    be None.  ``scenes``: None or a list of cuts; nothing is rebuilt from across a cut.  One upload, the flows, one call of
+    ops.interpolate, no host read; the same arguments give the same bytes in every run.
+
+    With return_source=True the result is (frames, source), source uint8 [L,H,W]: 5 for every frame that is a copy, retime's codes
+    in the rebuilt ones.  source == 0 is the mask to hand to inpaint_video: what no trajectory reached.  An empty ``bad`` returns
+    a copy without a launch.  Finding the bad frames is the caller's job.  Known limits: retime's -- translation-like
+    motion between the two good frames only, thin fast objects can vanish, flows computed on damaged neighbours are as good as
+    those neighbours -- and a run of bad frames is bridged linearly in time, whatever the motion did in between.  Argument errors
+    are ValueErrors that name the argument, raised before any device work.  There is no CPU path."""
+    shape, iterations, tolerance, match = _check_interpolate_args(frames_u8, iterations, tolerance, match, return_source)
+    L, H, W = (int(v) for v in shape[:3])
+    runs = plan_replace(L, bad, scenes)
+    bridged = [(a, c) for a, c, _ in runs if a is not None and c is not None]
+    if flows is not None:
+        try:
+            shapes = [tuple((str(f.dtype).replace("torch.", ""),) + tuple(f.shape) for f in pair) for pair in flows]
+        except (TypeError, AttributeError):
+            shapes = None
+        if shapes is None or len(shapes) != len(bridged) or any(s != (("float32", H, W, 2),) * 2 for s in shapes):
+            raise ValueError("flows must be a list of (fwd, bwd), both float32 [%d,%d,2], one for each of the %d runs of bad frames with "
+                             "two good neighbours, got %r" % (H, W, len(bridged), shapes if shapes is not None else flows))
+    elif bridged and not callable(getattr(model, "engine", None)):
+        raise TypeError("without flows= the frames are rebuilt along the flows of the model's SPyNet (metrics.video_flows): that needs "
+                        "the InpaintGenerator, got %s" % type(model).__name__)
+    if not runs:
+        return _copy_of(frames_u8, return_source)
+    device = _tool_device("replace_frames", device, frames_u8, model)
+    x = _upload(frames_u8, device)
+    fwd = bwd = None
+    with torch.cuda.device(x.device):
+        if bridged and flows is not None:
+            from . import metrics
+            fwd, bwd = (torch.stack([metrics._device_tensor(pair[i], x.device) for pair in flows]) for i in (0, 1))
+        elif bridged:
+            parts = [_device_flows(model, torch.stack([x[a], x[c]]), None) for a, c in bridged]
+            fwd, bwd = (parts[0][i] if len(parts) == 1 else torch.cat([p[i] for p in parts]) for i in (0, 1))
+        return _interpolate_device(x, fwd, bwd, _replace_jobs(L, runs), (iterations, tolerance, match), return_source, frames_u8)
+
+
 YuvFormat =collections.namedtuple("YuvFormat", "layout matrix full_range chroma")
 YUV_MATRICES = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}         # (Kr, Kb)
 

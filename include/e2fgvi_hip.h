@@ -561,6 +561,44 @@ int e2fgvi_deinterlace(const uint8_t* frames, const int32_t* scene, uint8_t* out
 int e2fgvi_denoise(const uint8_t* frames, const float* fwd, const float* bwd, const int32_t* scene, uint8_t* out, uint8_t* work,
                    int64_t work_bytes, int32_t L, int32_t H, int32_t W, int32_t strength, int32_t search, int32_t max_change,
                    void* stream);
+/* Frames between frames (video.retime, video.replace_frames): the picture at the time k / d between two frames, gathered along the
+ * two flows between them.  No atomics: the same inputs give the same bytes.
+ *   frames uint8 [L,H,W,3];  fwd, bwd fp32 [P,H,W,2], 8-byte aligned, P flow pairs in e2fgvi_warp_error's convention (pixels,
+ *   channel 0 = x);  jobs int32 [n,5] on the device, one row (ia, ib, fi, k, d) per output frame: A = frames[ia], B = frames[ib],
+ *   f = fwd[fi] the motion A -> B on A's grid, g = bwd[fi] the motion B -> A on B's grid;  out uint8 [n,H,W,3];  source uint8
+ *   [n,H,W] or NULL.  Parameters iterations in [0, 8], tol = tolerance in [0, 255] (1/16 px), match in [0, 765].
+ * A job with ia or ib outside [0, L), fi outside [0, P), d outside [1, 64] or k outside [0, d] writes nothing.
+ * k == 0: out = A, source = 5.  k == d: out = B, source = 5.  Otherwise tau = (double)k / (double)d, sigma = (double)(d - k) /
+ * (double)d, and every output pixel p = (x, y) gets two candidate trajectories through it: side A = side(S = A, E = B, h = f,
+ * lambda = tau) and side B = side(S = B, E = A, h = g, lambda = sigma).  All coordinate arithmetic is fp64 on the fp32 inputs, in
+ * the order written, one rounding per operation (no fused multiply-add).  side(S, E, h, lambda):
+ * 1. inside(q): q finite and 0 <= q_x <= W-1 and 0 <= q_y <= H-1, decided in floating point before any conversion to an integer.
+ * 2. bil(h, q), for inside(q): with (x0, y0) = floor(q), w1 = q - (x0, y0), w0 = 1 - w1 per axis, the corners' weights w00 = wy0 wx0,
+ *    w01 = wy0 wx1, w10 = wy1 wx0, w11 = wy1 wx1 (01 is the corner to the right, 10 the one below); the sample is w00 h00, + w01 h01,
+ *    + w10 h10, + w11 h11 in that order, a corner outside the image left out (e2fgvi_mask_track_step's sample).
+ * 3. h0 = h(p);  q = (x - lambda h0_x, y - lambda h0_y), the product first.
+ * 4. `iterations` times: the side fails unless inside(q);  hq = bil(h, q);  the side fails unless hq is finite;
+ *    q = (x - lambda hq_x, y - lambda hq_y).
+ * 5. The side fails unless inside(q) and hq = bil(h, q) is finite.  r = ((q_x + lambda hq_x) - x, (q_y + lambda hq_y) - y);
+ *    landed = r_x r_x + r_y r_y <= (double)(tol tol) / 256.0.
+ * 6. e = (q_x + hq_x, q_y + hq_y);  two_ended = landed and inside(e).
+ * 7. Integers from here on.  tap16(T, q): Q = floor(q 16 + 0.5) per component, xi = Q_x >> 4, fx = Q_x & 15, likewise y; the right
+ *    and lower corner indices are clamped to W-1 and H-1 (their weight is 0 there); per channel
+ *    ((16 - fy) ((16 - fx) c00 + fx c01) + fy ((16 - fx) c10 + fx c11) + 128) >> 8.  s = tap16(S, q), and t = tap16(E, e) when two_ended.
+ * 8. cost = the sum over the channels of |s - t|;  matched = two_ended and cost <= match.
+ * 9. The matched colour: side A ((d - k) s + k t + d / 2) / d, side B ((d - k) t + k s + d / 2) / d, integer divisions.
+ * Per pixel: A matched and (B not matched or cost_A <= cost_B): A's matched colour, source 1.  Otherwise B matched: B's matched
+ * colour, source 2.  Neither matched: A landed and (B not landed or 2 k <= d): s_A alone, source 3; otherwise B landed: s_B alone,
+ * source 4 (3 and 4: a place seen in one frame only, at an occlusion or a frame border); nothing landed: the cross-fade
+ * ((d - k) A(p) + k B(p) + d / 2) / d per channel, source 0.  A non-finite flow only ever fails a side, by select.
+ * One launch per 65535 jobs (the job is the grid's y axis); offsets are 64-bit; every byte of an in-range job's frame is written
+ * once; out and source must overlap neither frames, fwd, bwd or jobs nor each other (E2FGVI_EINVAL).  Nothing is read on the host.  Sizes >= 0, H W < 2^31 - 256, parameters in
+ * their ranges (E2FGVI_EINVAL otherwise, from the arguments alone); n, H or W == 0 returns 0 without a launch and without looking
+ * at the pointers; a null pointer with work (frames with L > 0, fwd and bwd with P > 0, jobs, out), flows that are not 8-byte
+ * aligned or jobs that are not 4-byte aligned are E2FGVI_EINVAL. */
+int e2fgvi_interpolate(const uint8_t* frames, const float* fwd, const float* bwd, const int32_t* jobs, uint8_t* out, uint8_t* source,
+                       int32_t n, int32_t L, int32_t P, int32_t H, int32_t W, int32_t iterations, int32_t tolerance, int32_t match,
+                       void* stream);
 
 /* conv_offset post-processing of SecondOrderDeformableAlignment (feat_prop.py:38-53) fused into the conv that produces
  * it: `residual` must point to the per-pixel flows [P,4] = (u1,v1,u2,v2) with res_ld = 4, `slope` = max_residue:
