@@ -621,6 +621,17 @@ const char* e2fgvi_last_error(void);
 int e2fgvi_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
+ * Operands are slices.  Every float entry point below takes its operands as slices of larger tensors: a pixel stride (*_ld), a
+ * first channel (*_coff), a channel count (cpg, Cout, src_c, channels), a row range.  For all of them:
+ *   - a kernel's result depends on no byte outside the declared slices of its operands: a channel, pixel or row next to a slice
+ *     may hold anything, Inf and NaN included (nothing outside a slice is loaded and then multiplied by 0);
+ *   - a kernel changes no byte outside the declared slice of its destinations (second outputs and planes included);
+ *   - pad channels inside a declared slice (the fourth / last five channels of NHWC4 / NHWC8 frames, channels 4..7 of flows8) are
+ *     the producer's to zero: the kernels that write such tensors write the zeros, a consumer may multiply them by weights.
+ * tests/test_gpu_slices.py holds every entry point to it, in NaN-poisoned arenas, at the tiles of its own tests.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* ------------------------------------------------------------------------------------------------
  * Implicit-GEMM convolution / linear layer on fp32 MFMA (v_mfma_f32_32x32x2_f32).
  * Replaces torch.nn.functional.conv2d / linear at: encoder model/e2fgvi.py:75-109, decoder
  * :143-150, SPyNet 7x7 stacks model/modules/flow_comp.py:180-215, conv_offset / backbone / fusion
