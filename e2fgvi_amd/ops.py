@@ -2360,6 +2360,101 @@ def flicker_apply(frames, d, out=None):
     return ou
 
 
+FLICKER_GRID_MAX = 8                       # csrc/flicker_local.hip: cells per axis (FLL_G_MAX)
+
+
+def _flicker_grid(grid, H=None, W=None):
+    """``grid`` as (gy, gx): a tuple or list of two integers in [1, FLICKER_GRID_MAX], no bools, and -- where there are pixels --
+    no more cells than pixels along either axis; ValueError that names it otherwise"""
+    if not isinstance(grid, (tuple, list)) or len(grid) != 2:
+        raise ValueError("grid must be a tuple of two integers in [1, %d], got %r" % (FLICKER_GRID_MAX, grid))
+    gy, gx = (_int_arg("grid", g, 1, FLICKER_GRID_MAX) for g in grid)
+    if H and W and (H < gy or W < gx):
+        raise ValueError("grid %d x %d has more cells than frames of %d x %d have rows or columns" % (gy, gx, H, W))
+    return gy, gx
+
+
+def _flicker_cells(t, name, what, L, last):
+    """(gy, gx) of ``t`` as [L,gy,gx,last]; ValueError that names it otherwise"""
+    if (t.dim() != 4 or t.shape[3] != last or (L is not None and t.shape[0] != L)
+            or not all(1 <= g <= FLICKER_GRID_MAX for g in t.shape[1:3])):
+        raise ValueError("%s must be %s [%s,gy,gx,%d] with gy and gx in [1, %d], got %s"
+                         % (name, what, "L" if L is None else L, last, FLICKER_GRID_MAX, tuple(t.shape)))
+    return int(t.shape[1]), int(t.shape[2])
+
+
+def flicker_local_hist(frames, grid, out=None):
+    """The luma histograms of the local deflicker, one launch over all frames (csrc/flicker_local.hip flicker_local_hist_kernel;
+    include/e2fgvi_hip.h has the definition; video.deflicker_local is the caller): frames uint8 [L,H,W,3], grid = (gy, gx) ->
+    device int32 [L,gy,gx,256], the number of pixels per luma level of each cell -- rows [(i H) // gy, ((i + 1) H) // gy) x columns
+    [(j W) // gx, ((j + 1) W) // gx) -- of each frame; summed over the cells they are flicker_hist's.  ``out``: a device int32
+    [L,gy,gx,256] to write into; every word is written (the entry clears them first).  The checks of flicker_hist, and grid: two
+    integers in [1, FLICKER_GRID_MAX] with H >= gy and W >= gx.  No CPU path, no host read; integer atomics: the same bits in
+    every run."""
+    lib = _L.load()
+    named = [("frames", frames, torch.uint8)] + ([("out", out, torch.int32)] if out is not None else [])
+    up = _device_inputs(named, "frames", written=("out",))
+    fr = up[0]
+    L, H, W = _flicker_frames(fr)
+    gy, gx = _flicker_grid(grid, H, W)
+    if out is not None and tuple(up[1].shape) != (L, gy, gx, 256):
+        raise ValueError("out must be int32 [%d,%d,%d,256], got %s" % (L, gy, gx, tuple(up[1].shape)))
+    with torch.cuda.device(fr.device):
+        hist = _alloc(L > 0 and H * W > 0, (L, gy, gx, 256), torch.int32, fr.device, up[1] if out is not None else None)
+        _L.check(lib.e2fgvi_flicker_local_hist(_ptr(fr), _ptr(hist), L, H, W, gy, gx, _stream()), "flicker_local_hist")
+    return hist
+
+
+def flicker_local_curves(hist, scene, H, W, span, max_shift):
+    """The nodes and the tone curves of the local deflicker, one launch (csrc/flicker_local.hip flicker_local_curves_kernel;
+    include/e2fgvi_hip.h has the definition): hist int32 [L,gy,gx,256] as flicker_local_hist made it of frames of ``H`` x ``W``,
+    every row summing to its cell's pixels (the contract; it is not checked, which would be a host read); scene int32 [L], equal
+    entries = one scene -> (Q, d16) on the device.  Q int32 [L,gy,gx,FLICKER_NODES]: the 32 luma quantiles of each cell in 1/16
+    levels.  d16 int16 [L,gy,gx,256]: per cell and luma level flicker_curves' shift of that cell's rows, in 1/16 levels (not rounded
+    to whole ones: flicker_local_apply blends first).  H W in [0, 2^26] with H >= gy and W >= gx where there are pixels; span and
+    max_shift as flicker_curves takes them.  No host read; exact integers, the same in every run."""
+    lib = _L.load()
+    H, W = _int_arg("H", H, 0, FLICKER_PIXELS_MAX), _int_arg("W", W, 0, FLICKER_PIXELS_MAX)
+    if H * W > FLICKER_PIXELS_MAX:
+        raise ValueError("H W must be <= 2^26, got %d x %d" % (H, W))
+    span = _int_arg("span", span, 0, FLICKER_SPAN_MAX)
+    max_shift = _int_arg("max_shift", max_shift, 1, FLICKER_SHIFT_MAX)
+    hs, sc = _device_inputs([("hist", hist, torch.int32), ("scene", scene, torch.int32)], "hist")
+    gy, gx = _flicker_cells(hs, "hist", "int32", None, 256)
+    _flicker_grid((gy, gx), H, W)
+    L = int(hs.shape[0])
+    _scene_table(sc, "scene", L)
+    with torch.cuda.device(hs.device):
+        work = L > 0 and H * W > 0                       # with work the launch writes every entry
+        Q = _alloc(work, (L, gy, gx, FLICKER_NODES), torch.int32, hs.device)
+        d16 = _alloc(work, (L, gy, gx, 256), torch.int16, hs.device)
+        _L.check(lib.e2fgvi_flicker_local_curves(_ptr(hs), _ptr(sc), _ptr(Q), _ptr(d16), L, H, W, gy, gx, span, max_shift, _stream()),
+                 "flicker_local_curves")
+    return Q, d16
+
+
+def flicker_local_apply(frames, d16, out=None):
+    """The cells' tone curves blended and applied, one launch (csrc/flicker_local.hip flicker_local_apply_kernel;
+    include/e2fgvi_hip.h has the definition): frames uint8 [L,H,W,3], d16 int16 [L,gy,gx,256] as flicker_local_curves made it ->
+    device uint8 [L,H,W,3]: every pixel moved by the shifts of its luma in the four cells around it, blended by its position between
+    their centres and rounded to whole levels once, the same for its three bytes, each clipped to [0, 255].  ``out`` as
+    flicker_apply takes it (``frames`` itself for in place); every byte is written once.  The checks of flicker_local_hist; no host
+    read; exact integers."""
+    lib = _L.load()
+    named = [("frames", frames, torch.uint8), ("d16", d16, torch.int16)] + ([("out", out, torch.uint8)] if out is not None else [])
+    up = _device_inputs(named, "frames", written=("out",))
+    fr, dd = up[:2]
+    L, H, W = _flicker_frames(fr)
+    gy, gx = _flicker_cells(dd, "d16", "int16", L, 256)
+    _flicker_grid((gy, gx), H, W)
+    if out is not None and tuple(up[2].shape) != tuple(fr.shape):
+        raise ValueError("out must be %s, got %s" % (list(fr.shape), tuple(up[2].shape)))
+    with torch.cuda.device(fr.device):
+        ou = up[2] if out is not None else torch.empty_like(fr)
+        _L.check(lib.e2fgvi_flicker_local_apply(_ptr(fr), _ptr(dd), _ptr(ou), L, H, W, gy, gx, _stream()), "flicker_local_apply")
+    return ou
+
+
 WEAVE_BANDS = 8                            # csrc/weave.hip: bands per axis (WV_NB)
 WEAVE_RADIUS_MAX = 32                      # parameters outside these ranges are E2FGVI_EINVAL
 WEAVE_SPAN_MAX = 16

@@ -1346,13 +1346,81 @@ def deflicker(frames_u8, scenes=None, span=FLICKER_SPAN, max_shift=FLICKER_MAX_S
     moving scenery changes the histograms too, so a clean video comes back changed by a few levels (on the 25 frames of
     tests/golden/tennis25.npz, a panning camera, 44 % of the pixels by at most 3 levels); flicker that varies over the frame is
     not corrected, the curve is one per frame; there is no ``hole`` argument: a large object entering the frame reads as a
-    brightness change.
+    brightness change.  deflicker_local has a curve per cell of a grid, for flicker that does vary over the frame.
     span in [0, 8], max_shift in [1, 64]: integers, no bools; return_curves a bool; a string for ``scenes`` is refused; H W <=
     2^26.  Argument errors are ValueErrors that name the argument, raised before any device work.  There is no CPU path."""
     scene_of, span, max_shift = _check_flicker_args(frames_u8, scenes, span, max_shift, return_curves)
     device = _tool_device("deflicker", device, frames_u8)
     out, d = _like_input(frames_u8, *_deflicker_device(_upload(frames_u8, device), scene_of, span, max_shift))
     return (out, d) if return_curves else out
+
+
+FLICKER_GRID = (2, 2)          # deflicker_local's default: DESIGN.md 3z has the measurements it was judged on
+
+
+def _check_flicker_local_args(frames_u8, scenes, grid, span, max_shift, return_curves):
+    """the checks of deflicker_local from the arguments and the shapes alone -> (scene_of int32 [L], (gy, gx), span, max_shift)"""
+    scene_of, span, max_shift = _check_flicker_args(frames_u8, scenes, span, max_shift, return_curves)
+    if not isinstance(grid, (tuple, list)) or len(grid) != 2 or not all(_integer(g, 1, ops.FLICKER_GRID_MAX) for g in grid):
+        raise ValueError("grid must be a tuple of two integers in [1, %d], got %r" % (ops.FLICKER_GRID_MAX, grid))
+    gy, gx = (int(g) for g in grid)
+    H, W = (int(v) for v in frames_u8.shape[1:3])
+    if H * W > 0 and (H < gy or W < gx):                               # every cell has a pixel
+        raise ValueError("grid %d x %d has more cells than frames of %d x %d have rows or columns" % (gy, gx, H, W))
+    return scene_of, (gy, gx), span, max_shift
+
+
+def _flicker_local_device(x, scene_of, grid, span, max_shift):
+    """deflicker_local after the argument checks and the upload of the frames: x uint8 [L,H,W,3] on the device -> (out uint8
+    [L,H,W,3], d16 int16 [L,gy,gx,256]) on the device.  Three launches, no host read.  Nothing to do (span 0, no frame, no pixel):
+    x itself and zeros."""
+    L, H, W = (int(v) for v in x.shape[:3])
+    if span == 0 or L == 0 or H * W == 0:
+        return x, torch.zeros((L,) + tuple(grid) + (256,), dtype=torch.int16, device=x.device)
+    so = torch.from_numpy(scene_of).to(x.device)        # in front of the first launch
+    with torch.cuda.device(x.device):
+        hist = ops.flicker_local_hist(x, grid)
+        _, d16 = ops.flicker_local_curves(hist, so, H, W, span, max_shift)
+        out = ops.flicker_local_apply(x, d16)
+    return out, d16
+
+
+@torch.no_grad()
+def deflicker_local(frames_u8, scenes=None, grid=FLICKER_GRID, span=FLICKER_SPAN, max_shift=FLICKER_MAX_SHIFT, return_curves=False,
+                    device=None):
+    """Takes flicker that varies over the frame out of a video -- one side of the gate brighter than the other, an uneven shutter,
+    a print that has faded in patches -- where deflicker, with its one curve per frame, leaves it in: frames_u8 uint8 [L,H,W,3]
+    (an array or a tensor) -> uint8 [L,H,W,3], a numpy array, or a device tensor when the input is one (which is used where it
+    is).  With ``return_curves`` the result is (out, d16), d16 the int16 [L,gy,gx,256] shift per frame, cell and luma level in
+    1/16 levels.  It stands where deflicker stands in a restoration chain, needs no model and no flows, and runs in three launches
+    (ops.flicker_local_hist, ops.flicker_local_curves, ops.flicker_local_apply) without a host read.  Integers throughout
+    (include/e2fgvi_hip.h has the definition): the same arguments give the same bytes in every run.
+
+    ``grid`` = (gy, gx) cuts the frame into gy x gx cells, cell (i, j) the rows [(i H) // gy, ((i + 1) H) // gy) and the columns
+    [(j W) // gx, ((j + 1) W) // gx).  Every cell gets deflicker's curve of its own pixels -- its luma histogram, 32 quantile
+    nodes, their rounded mean over the frames within ``span`` of the frame in its scene, the shift clamped to +-``max_shift``
+    levels and interpolated to every luma level -- kept in 1/16 levels.  A pixel is moved by the shifts of its luma in the four
+    cells whose centres surround it, blended bilinearly by its position between those centres in 1/256 of a cell and rounded to
+    whole levels once, the same for its three channels, each clipped to [0, 255].  ``scenes``, ``span`` and ``max_shift`` are
+    deflicker's.
+
+    What follows from that: grid=(1, 1) gives deflicker's bytes; a pixel in front of the first cell centre or behind the last gets
+    that cell's curve alone; a frame alone in its window comes back unchanged; a video whose frames all have the same cell
+    histograms comes back byte for byte; span == 0, no frame or no pixel runs no launch and returns the caller's bytes.
+
+    Known limits: a cell's histogram changes when scenery moves through it, and the smaller the cell the more, so
+    a clean video comes back changed more than by deflicker -- a finer grid buys flicker suppression with exactly this.  On the 25
+    frames of tests/golden/tennis25.npz, a panning camera, without any flicker: (1, 1) changes no pixel by more than 3 levels,
+    (2, 2) 1.6 % of them and one by 15, (3, 4) 8.8 % and one by 31, (4, 6) 13.5 % and one by 32; under a planted flicker that tilts
+    across the frame (2, 2) leaves 0.37 of the roughness deflicker leaves, (3, 4) 0.28.  That is why the default is (2, 2).  There is
+    no motion gate and no ``hole`` argument; the other limits are deflicker's.
+    grid: a tuple or list of two integers in [1, 8], no bools, with H >= gy and W >= gx; span in [0, 8], max_shift in [1, 64];
+    return_curves a bool; H W <= 2^26.  Argument errors are ValueErrors that name the argument, raised before any device work.
+    There is no CPU path."""
+    scene_of, grid, span, max_shift = _check_flicker_local_args(frames_u8, scenes, grid, span, max_shift, return_curves)
+    device = _tool_device("deflicker_local", device, frames_u8)
+    out, d16 = _like_input(frames_u8, *_flicker_local_device(_upload(frames_u8, device), scene_of, grid, span, max_shift))
+    return (out, d16) if return_curves else out
 
 
 WEAVE_SPAN = 4                 # stabilize's defaults: DESIGN.md 3v has the measurements they were judged on

@@ -457,6 +457,45 @@ int e2fgvi_flicker_hist(const uint8_t* frames, int32_t* hist, int32_t L, int32_t
 int e2fgvi_flicker_curves(const int32_t* hist, const int32_t* scene, int32_t* Q, int16_t* d, int32_t L, int32_t N, int32_t span,
                           int32_t max_shift, void* stream);
 int e2fgvi_flicker_apply(const uint8_t* frames, const int16_t* d, uint8_t* out, int32_t L, int32_t H, int32_t W, void* stream);
+/* Local deflicker (video.deflicker_local): the deflicker above cell by cell on a grid of gy x gx cells, the cells' curves blended
+ * between the cell centres -- for flicker that varies over the frame.  All arithmetic is integer; every division is a floor of
+ * non-negative numbers unless said otherwise and >> of a negative number is the arithmetic shift (a floor as well).
+ *   frames uint8 [L,H,W,3];  1 <= gy, gx <= 8, H >= gy, W >= gx, H W <= 2^26;  scene, span, max_shift and K = 32 as above.
+ * 0. Cells.  Cell (i, j) owns the rows [(i H) / gy, ((i + 1) H) / gy) and the columns [(j W) / gx, ((j + 1) W) / gx);  n_ij is
+ *    its number of pixels, >= 1.
+ * 1. Luma.  Y as above.
+ * 2. Histograms.  hist[t][i][j][v] = the number of pixels of cell (i, j) of frame t with Y == v, int32 [L][gy][gx][256].
+ * 3. Nodes.  Q[t][i][j][k] = the deflicker's node k (3 above) of the row hist[t][i][j] with N = n_ij, int32 [L][gy][gx][32].
+ * 4. Shifts per node.  s[k] = the deflicker's (4 above) of the rows hist[u][i][j], u in W_t: the cell's own nodes, their rounded
+ *    mean over the frames within span of t in t's scene, the difference clamped to +-16 max_shift.
+ * 5. Shifts per level.  d16[t][i][j][y] = (s[k0] (256 - f) + s[k1] f + 128) >> 8 with phi, k0, k1 and f as in 5 above from the
+ *    cell's own cumulative histogram and N = n_ij: the deflicker's shift in 1/16 levels, WITHOUT its last step (d16 + 8) >> 4.
+ *    int16 [L][gy][gx][256], |d16| <= 16 max_shift <= 1024.
+ * 6. Apply.  Positions are measured between the cell centres in 1/256 of a cell.  Row r:  v = clamp(((2r + 1) gy 128) / H - 128,
+ *    0, (gy - 1) 256) (the quotient first, the difference may go below zero and is clamped);  i0 = v >> 8, fy = v & 255,
+ *    i1 = min(i0 + 1, gy - 1).  Column x likewise with gx and W: u, j0, fx, j1.  For a pixel of luma Y, with a = d16[t][i0][j0][Y],
+ *    b = d16[t][i0][j1][Y], c = d16[t][i1][j0][Y], e = d16[t][i1][j1][Y]:
+ *      D = ((a (256 - fx) + b fx) (256 - fy) + (c (256 - fx) + e fx) fy + 32768) >> 16;   d = (D + 8) >> 4;
+ *      out[t,r,x,ch] = clamp(frames[t,r,x,ch] + d, 0, 255), the same d for the three channels.
+ *    |a (256 - fx) + b fx| <= 2^18 and the sum in front of the shift stays below 2^27: int32 holds everything.  A pixel in front of
+ *    the first cell centre, or behind the last, has f = 0 on that axis and gets that cell's curve alone; gy = gx = 1 gives the
+ *    deflicker's bytes (D = a, d its d).
+ * e2fgvi_flicker_local_hist does 1 and 2: it clears all L gy gx 256 words on the stream and adds with integer atomics (exact,
+ * the same in every run); every frame byte is read once.  e2fgvi_flicker_local_curves does 3 to 5 in one launch, a workgroup per
+ * frame and cell that recomputes the nodes of its window from hist; its contract is that hist[t][i][j] sums to n_ij (a row that
+ * does not gives some curve and no fault); it writes every entry of Q and d16.  e2fgvi_flicker_local_apply does 6; every output
+ * byte is written once, by the thread that read the input byte: out may be frames itself (in place), any other overlap of the two
+ * ranges is E2FGVI_EINVAL.  Nothing is read on the host.
+ * L, H, W >= 0, H W <= 2^26, gy and gx in [1, 8], span and max_shift in their ranges (E2FGVI_EINVAL otherwise, from the arguments
+ * alone);  L == 0 or H W == 0 returns 0 without a launch and without looking at the pointers;  with work, H < gy or W < gx, a null
+ * pointer, an int32 array that is not 4-byte aligned or a d16 that is not 2-byte aligned is E2FGVI_EINVAL.  Frames are launched
+ * in slabs of 65535. */
+int e2fgvi_flicker_local_hist(const uint8_t* frames, int32_t* hist, int32_t L, int32_t H, int32_t W, int32_t gy, int32_t gx,
+                              void* stream);
+int e2fgvi_flicker_local_curves(const int32_t* hist, const int32_t* scene, int32_t* Q, int16_t* d16, int32_t L, int32_t H, int32_t W,
+                                int32_t gy, int32_t gx, int32_t span, int32_t max_shift, void* stream);
+int e2fgvi_flicker_local_apply(const uint8_t* frames, const int16_t* d16, uint8_t* out, int32_t L, int32_t H, int32_t W, int32_t gy,
+                               int32_t gx, void* stream);
 /* Weave stabiliser (video.stabilize): the translation of the picture from frame to frame -- gate weave, telecine jitter -- measured
  * from banded luma profiles, a path smoothed over a symmetric window, and the frames moved back onto it.  All arithmetic is
  * integer; "floor" is the floor for either sign, >> of a negative number is the arithmetic shift and & 15 its non-negative rest.
