@@ -40,12 +40,13 @@ UNITS = [("error.hip", "error.o", []), ("conv.hip", "conv.o", []), ("conv.hip", 
          ("line_scratch.hip", "line_scratch.o", NOPK),
          ("flicker.hip", "flicker.o", NOPK),
          ("flicker_local.hip", "flicker_local.o", NOPK),
+         ("color.hip", "color.o", NOPK),
          ("weave.hip", "weave.o", NOPK),
          ("interlace.hip", "interlace.o", NOPK),
          ("denoise.hip", "denoise.o", NOPK),
          # the same: the restatement of tests/interpolate_cases.py matches the trajectories bit for bit
          ("interpolate.hip", "interpolate.o", NOPK + ["-ffp-contract=off"])]
-NOPK_OBJECTS = ("conv_nopk.o", "conv_bf16x.o", "conv_wino.o", "conv_wino4.o", "conv_wino_x3.o", "conv_tail.o", "mdcn.o", "attention_bf16.o", "attention_x3.o", "misc.o", "video.o", "yuv.o", "metrics.o", "mask_track.o", "defects.o", "pixel_track.o", "grain.o", "line_scratch.o", "flicker.o", "flicker_local.o", "weave.o", "interlace.o", "denoise.o", "interpolate.o")
+NOPK_OBJECTS = ("conv_nopk.o", "conv_bf16x.o", "conv_wino.o", "conv_wino4.o", "conv_wino_x3.o", "conv_tail.o", "mdcn.o", "attention_bf16.o", "attention_x3.o", "misc.o", "video.o", "yuv.o", "metrics.o", "mask_track.o", "defects.o", "pixel_track.o", "grain.o", "line_scratch.o", "flicker.o", "flicker_local.o", "color.o", "weave.o", "interlace.o", "denoise.o", "interpolate.o")
 OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 
 
@@ -107,6 +108,7 @@ def build(force=False, verbose=False, nopk_all=False, lib=None, tag=None, define
             verify_no_scratch(objdir, "line_scratch.o", "line_", "line scratch")
             verify_no_scratch(objdir, "flicker.o", "flicker_", "deflicker")
             verify_no_scratch(objdir, "flicker_local.o", "flicker_local_", "local deflicker")
+            verify_no_scratch(objdir, "color.o", "color_", "colour restoration")
             verify_no_scratch(objdir, "weave.o", "weave_", "weave stabiliser")
             verify_no_scratch(objdir, "interlace.o", "interlace_", "deinterlacer")
             verify_no_scratch(objdir, "denoise.o", "denoise_", "temporal denoiser")
@@ -202,6 +204,7 @@ def verify_no_scratch(objdir=None, obj="conv_bf16x.o", marker="ELb0ELi2ELb1EEE",
     and over the four of line_scratch.o (the per-polarity counters of the columns pass are small arrays indexed in unrolled loops);
     and over the three of flicker.o (the histogram and the apply kernel hold the dwords of all of a thread's groups at once);
     and over the three of flicker_local.o (the same, and the apply kernel the four cell offsets and weights of a thread's pixels);
+    and over the four of color.o (the histogram and the apply kernel hold the dwords of all of a thread's groups at once);
     and over the five of weave.o (the apply kernel shifts the dwords of two tap rows into place in small arrays);
     and over the three of interlace.o (the fields kernel holds the dwords and the luma of up to twelve groups in small arrays);
     and over the four of denoise.o (the filter kernel keeps the 7 x 5 three-byte runs of a neighbour's luma window in a small array);

@@ -161,7 +161,11 @@ SYMBOLS = {
     "e2fgvi_flicker_local_hist": (C.c_int, [_fp, _fp] + [_i32] * 5 + [_fp]),
     "e2fgvi_flicker_local_curves": (C.c_int, [_fp] * 4 + [_i32] * 7 + [_fp]),
     "e2fgvi_flicker_local_apply": (C.c_int, [_fp] * 3 + [_i32] * 5 + [_fp]),
-    "e2fgvi_weave_profiles": (C.c_int, [_fp, _fp, _fp, _i32, _i32, _i32, _fp]),
+    "e2fgvi_color_hist": (C.c_int, [_fp, _fp, _i32, _i32, _i32, _fp]),
+    "e2fgvi_color_nodes": (C.c_int, [_fp] * 4 + [_i32] * 5 + [_fp]),
+    "e2fgvi_color_lut": (C.c_int, [_fp] * 4 + [_i32] * 6 + [_fp]),
+    "e2fgvi_color_apply": (C.c_int, [_fp] * 4 + [_i32] * 4 + [_fp]),
+    "e2fgvi_weave_profiles":(C.c_int, [_fp, _fp, _fp, _i32, _i32, _i32, _fp]),
     "e2fgvi_weave_match": (C.c_int, [_fp] * 4 + [_i32] * 5 + [_fp]),
     "e2fgvi_weave_path": (C.c_int, [_fp] * 3 + [_i32] * 4 + [_fp]),
     "e2fgvi_weave_apply": (C.c_int, [_fp] * 4 + [_i32] * 4 + [_fp]),

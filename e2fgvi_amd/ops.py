@@ -2455,6 +2455,129 @@ def flicker_local_apply(frames, d16, out=None):
     return ou
 
 
+COLOR_NODES = FLICKER_NODES + 2            # csrc/color.hip: 32 quantiles, the black and the white point (COL_Q)
+COLOR_CLIP_MAX = 250                       # per mille; parameters outside these ranges are E2FGVI_EINVAL
+COLOR_GAIN_MIN, COLOR_GAIN_MAX = 256, 4096
+COLOR_KEEP, COLOR_LEVELS, COLOR_MATCH = 0, 1, 2
+
+
+def color_hist(frames, out=None):
+    """The channel histograms of the colour restoration, one launch over all frames (csrc/color.hip color_hist_kernel;
+    include/e2fgvi_hip.h has the definition; video.restore_color is the caller): frames uint8 [L,H,W,3] -> device int32 [L,3,256],
+    the number of pixels of each frame per channel and byte value.  ``out``: a device int32 [L,3,256] to write into; every word is
+    written (the entry clears them first).  Device tensors, or anything torch.as_tensor accepts (uploaded first); a wrong dtype or
+    shape, more than 2^26 pixels a frame and a non-contiguous input raise ValueError.  There is no CPU path and no host read;
+    integer atomics: the same input gives the same bits in every run."""
+    lib = _L.load()
+    named = [("frames", frames, torch.uint8)] + ([("out", out, torch.int32)] if out is not None else [])
+    up = _device_inputs(named, "frames", written=("out",))
+    fr = up[0]
+    L, H, W = _flicker_frames(fr)
+    if out is not None and tuple(up[1].shape) != (L, 3, 256):
+        raise ValueError("out must be int32 [%d,3,256], got %s" % (L, tuple(up[1].shape)))
+    with torch.cuda.device(fr.device):
+        hist = _alloc(L > 0 and H * W > 0, (L, 3, 256), torch.int32, fr.device, up[1] if out is not None else None)
+        _L.check(lib.e2fgvi_color_hist(_ptr(fr), _ptr(hist), L, H, W, _stream()), "color_hist")
+    return hist
+
+
+def color_nodes(hist, starts, ids, clip=(5, 5)):
+    """The quantile nodes of groups of frames, one launch (csrc/color.hip color_nodes_kernel; include/e2fgvi_hip.h has the
+    definition): hist int32 [L,3,256] as color_hist made it; starts int32 [G+1] and ids int32 [M], the groups in CSR form -- group
+    g pools the histograms of the frames ids[starts[g] : starts[g+1]] -> device int32 [G,3,COLOR_NODES]: per group and channel the
+    32 quantiles (2k + 1) / 64 of the pooled histogram, then its black point, below which ``clip[0]`` per mille of the pixels
+    lie, and its white point, above which ``clip[1]`` per mille lie; all in 1/16 levels.  An id outside [0, L) is skipped, starts
+    are read clamped to [0, M], and a group without a pixel gets zeros (range-checked in the kernel, not here: no host read).
+    clip: two integers in [0, COLOR_CLIP_MAX], no bools.  The checks of color_hist; exact integers, the same in every run."""
+    lib = _L.load()
+    if not isinstance(clip, (tuple, list)) or len(clip) != 2:
+        raise ValueError("clip must be a tuple of two integers in [0, %d], got %r" % (COLOR_CLIP_MAX, clip))
+    lo, hi = (_int_arg("clip", v, 0, COLOR_CLIP_MAX) for v in clip)
+    hs, st, ii = _device_inputs([("hist", hist, torch.int32), ("starts", starts, torch.int32), ("ids", ids, torch.int32)], "hist")
+    if hs.dim() != 3 or tuple(hs.shape[1:]) != (3, 256):
+        raise ValueError("hist must be int32 [L,3,256], got %s" % (tuple(hs.shape),))
+    if st.dim() != 1 or st.numel() < 1:
+        raise ValueError("starts must be int32 [G+1], got %s" % (tuple(st.shape),))
+    if ii.dim() != 1:
+        raise ValueError("ids must be int32 [M], got %s" % (tuple(ii.shape),))
+    L, G, M = int(hs.shape[0]), int(st.numel()) - 1, int(ii.numel())
+    with torch.cuda.device(hs.device):
+        Q = _alloc(G > 0, (G, 3, COLOR_NODES), torch.int32, hs.device)        # with a group the launch writes every entry
+        _L.check(lib.e2fgvi_color_nodes(_ptr(hs), _ptr(st), _ptr(ii), _ptr(Q), L, G, M, lo, hi, _stream()), "color_nodes")
+    return Q
+
+
+def _color_target(target):
+    """``target`` as (lo_t, hi_t): None is the automatic one (-1, -1), else two integers 0 <= lo_t < hi_t <= 255, no bools"""
+    if target is None:
+        return -1, -1
+    if not isinstance(target, (tuple, list)) or len(target) != 2:
+        raise ValueError("target must be None or a tuple of two integers 0 <= lo < hi <= 255, got %r" % (target,))
+    lo_t, hi_t = (_int_arg("target", v, 0, 255) for v in target)
+    if lo_t >= hi_t:
+        raise ValueError("target must be None or a tuple of two integers 0 <= lo < hi <= 255, got %r" % (target,))
+    return lo_t, hi_t
+
+
+def color_lut(Q, mode, T=None, target=None, min_range=32, max_gain=768, strength=256):
+    """The byte tables of groups of frames, one launch (csrc/color.hip color_lut_kernel; include/e2fgvi_hip.h has the
+    definition): Q int32 [G,3,COLOR_NODES] as color_nodes made it, mode int32 [G] -> device uint8 [G,3,256], per group and channel
+    the byte every byte value becomes.  mode COLOR_KEEP (and any other value): the identity.  COLOR_LEVELS: the channel's black
+    and white point are brought onto ``target`` = (lo, hi) in levels -- None: onto the smallest black and the largest white point
+    of the group's usable channels --, a straight line about the centre of the range whose gain is cut at ``max_gain`` / 256; a
+    channel whose range is narrower than ``min_range`` levels is not usable and keeps its bytes.  COLOR_MATCH: the channel's 32
+    quantiles are moved onto those of ``T`` (int32 [G,3,COLOR_NODES], another color_nodes result; None: Q itself), straight lines
+    between them and slope 1 beyond the first and the last.  ``strength`` / 256 of the way from the identity is gone.  min_range in
+    [1, 255], max_gain in [COLOR_GAIN_MIN, COLOR_GAIN_MAX], strength in [0, 256]: integers, no bools.  The checks of color_hist;
+    no host read; exact integers, the same in every run."""
+    lib = _L.load()
+    lo_t, hi_t = _color_target(target)
+    min_range = _int_arg("min_range", min_range, 1, 255)
+    max_gain = _int_arg("max_gain", max_gain, COLOR_GAIN_MIN, COLOR_GAIN_MAX)
+    strength = _int_arg("strength", strength, 0, 256)
+    named = [("Q", Q, torch.int32), ("mode", mode, torch.int32)] + ([("T", T, torch.int32)] if T is not None else [])
+    up = _device_inputs(named, "Q")
+    qq, md = up[:2]
+    if qq.dim() != 3 or tuple(qq.shape[1:]) != (3, COLOR_NODES):
+        raise ValueError("Q must be int32 [G,3,%d], got %s" % (COLOR_NODES, tuple(qq.shape)))
+    G = int(qq.shape[0])
+    if tuple(md.shape) != (G,):
+        raise ValueError("mode must be int32 [%d], got %s" % (G, tuple(md.shape)))
+    if T is not None and tuple(up[2].shape) != tuple(qq.shape):
+        raise ValueError("T must be int32 %s, got %s" % (list(qq.shape), tuple(up[2].shape)))
+    tt = up[2] if T is not None else qq
+    with torch.cuda.device(qq.device):
+        lut = torch.empty((G, 3, 256), dtype=torch.uint8, device=qq.device)  # with a group the launch writes every entry
+        _L.check(lib.e2fgvi_color_lut(_ptr(qq), _ptr(tt), _ptr(md), _ptr(lut), G, lo_t, hi_t, min_range, max_gain, strength, _stream()),
+                 "color_lut")
+    return lut
+
+
+def color_apply(frames, lut, group, out=None):
+    """The byte tables applied, one launch (csrc/color.hip color_apply_kernel; include/e2fgvi_hip.h has the definition): frames
+    uint8 [L,H,W,3], lut uint8 [G,3,256] as color_lut made it (or the caller's own), group int32 [L] -> device uint8 [L,H,W,3]:
+    byte c of every pixel of frame t looked up in lut[group[t]][c]; a frame whose group is outside [0, G) is copied (checked in the
+    kernel, not here: no host read).  ``out``: a device uint8 [L,H,W,3] to write into -- ``frames`` itself for in place, otherwise
+    one that does not overlap it (the entry refuses any other overlap); every byte is written once.  The checks of color_hist; no
+    host read; exact integers."""
+    lib = _L.load()
+    named = [("frames", frames, torch.uint8), ("lut", lut, torch.uint8), ("group", group, torch.int32)]
+    named += [("out", out, torch.uint8)] if out is not None else []
+    up = _device_inputs(named, "frames", written=("out",))
+    fr, lt, gr = up[:3]
+    L, H, W = _flicker_frames(fr)
+    if lt.dim() != 3 or tuple(lt.shape[1:]) != (3, 256):
+        raise ValueError("lut must be uint8 [G,3,256], got %s" % (tuple(lt.shape),))
+    if tuple(gr.shape) != (L,):
+        raise ValueError("group must be int32 [%d], got %s" % (L, tuple(gr.shape)))
+    if out is not None and tuple(up[3].shape) != tuple(fr.shape):
+        raise ValueError("out must be %s, got %s" % (list(fr.shape), tuple(up[3].shape)))
+    with torch.cuda.device(fr.device):
+        ou = up[3] if out is not None else torch.empty_like(fr)
+        _L.check(lib.e2fgvi_color_apply(_ptr(fr), _ptr(lt), _ptr(gr), _ptr(ou), L, H, W, int(lt.shape[0]), _stream()), "color_apply")
+    return ou
+
+
 WEAVE_BANDS = 8                            # csrc/weave.hip: bands per axis (WV_NB)
 WEAVE_RADIUS_MAX = 32                      # parameters outside these ranges are E2FGVI_EINVAL
 WEAVE_SPAN_MAX = 16

@@ -1423,6 +1423,182 @@ def deflicker_local(frames_u8, scenes=None, grid=FLICKER_GRID, span=FLICKER_SPAN
     return (out, d16) if return_curves else out
 
 
+COLOR_CLIP = (5, 5)            # restore_color's defaults: DESIGN.md 3aa has the measurements they were judged on
+COLOR_MIN_RANGE = 32
+COLOR_MAX_GAIN = 768
+COLOR_STRENGTH = 256
+
+
+def _check_pair(name, v, lo, hi):
+    """``v`` as a pair of integers in [lo, hi] (a tuple or a list, no bools); ValueError that names the argument"""
+    if not isinstance(v, (tuple, list)) or len(v) != 2 or not all(_integer(x, lo, hi) for x in v):
+        raise ValueError("%s must be a tuple of two integers in [%d, %d], got %r" % (name, lo, hi, v))
+    return int(v[0]), int(v[1])
+
+
+def _check_restore_color_args(frames_u8, scenes, graded, keys, otherwise, clip, target, min_range, max_gain, strength, return_curves):
+    """the checks of restore_color from the arguments and the shapes alone -> the plan, a dict: scene_of int32 [L] (the group of
+    every frame), S the number of scenes, mode int32 [S], (starts, ids) the CSR groups pooled from the frames' histograms, one per
+    scene, gstarts / gids those pooled from the graded frames' (None without ``graded``; with ``graded`` and no keys one group of
+    all of them), and the parameters as ints"""
+    shape = _check_frames(frames_u8, True)
+    L = int(shape[0])
+    if int(shape[1]) * int(shape[2]) > ops.FLICKER_PIXELS_MAX:         # its own: a histogram bin is an int32
+        raise ValueError("frames must have H W <= 2^26, got %d x %d" % (shape[1], shape[2]))
+    cuts = _scene_cuts(scenes, L)
+    if otherwise not in ("levels", "keep"):
+        raise ValueError("otherwise must be \"levels\" or \"keep\", got %r" % (otherwise,))
+    clip = _check_pair("clip", clip, 0, ops.COLOR_CLIP_MAX)
+    if target is not None:
+        target = _check_pair("target", target, 0, 255)
+        if target[0] >= target[1]:
+            raise ValueError("target must be None or (lo, hi) with 0 <= lo < hi <= 255, got %r" % (target,))
+    min_range, max_gain, strength = _check_ranges(("min_range", min_range, 1, 255),
+                                                  ("max_gain", max_gain, ops.COLOR_GAIN_MIN, ops.COLOR_GAIN_MAX),
+                                                  ("strength", strength, 0, 256))
+    _check_flags(return_curves=return_curves)
+    if graded is None:
+        if keys is not None:
+            raise ValueError("keys needs graded: the key frames as the colourist wants them")
+    else:
+        gshape = _check_frames(graded, True, "graded")
+        n = int(gshape[0])
+        if n < 1 or int(gshape[1]) * int(gshape[2]) < 1 or int(gshape[1]) * int(gshape[2]) > ops.FLICKER_PIXELS_MAX:
+            raise ValueError("graded must hold at least one frame of 1 <= h w <= 2^26 pixels, got %s" % (gshape,))
+        if keys is not None:
+            keys = _check_keys(keys, L)
+            if len(keys) != n:
+                raise ValueError("keys must name one frame for each of the %d graded frames, got %d" % (n, len(keys)))
+    scene_of = _scene_table(cuts, L)
+    bounds = [0] + cuts + [L]
+    S = len(bounds) - 1
+    own = [list(range(bounds[s], bounds[s + 1])) for s in range(S)]
+    mode = [ops.COLOR_LEVELS] * S
+    groups, ggroups = own, None
+    if graded is not None and keys is None:
+        mode, ggroups = [ops.COLOR_MATCH] * S, [list(range(n))]
+    elif graded is not None:
+        held = [[i for i, k in enumerate(keys) if bounds[s] <= k < bounds[s + 1]] for s in range(S)]
+        mode = [ops.COLOR_MATCH if h else (ops.COLOR_LEVELS if otherwise == "levels" else ops.COLOR_KEEP) for h in held]
+        groups = [[keys[i] for i in h] if h else o for h, o in zip(held, own)]
+        ggroups = held
+
+    def csr(gs):
+        return (np.cumsum([0] + [len(g) for g in gs]).astype(np.int32), np.array([t for g in gs for t in g], np.int32).reshape(-1))
+
+    plan = dict(scene_of=scene_of, S=S, mode=np.array(mode, np.int32), clip=clip, target=target, min_range=min_range,
+                max_gain=max_gain, strength=strength, gstarts=None, gids=None)
+    plan["starts"], plan["ids"] = csr(groups)
+    if ggroups is not None:
+        plan["gstarts"], plan["gids"] = csr(ggroups)
+    return plan
+
+
+def _identity_curves(S, device):
+    return torch.arange(256, dtype=torch.uint8, device=device).repeat(S, 3, 1)
+
+
+def _restore_color_device(x, graded, plan):
+    """restore_color after the argument checks and the upload of the frames: x uint8 [L,H,W,3] and graded (uint8 [n,h,w,3] or None)
+    on the device -> (out uint8 [L,H,W,3], luts uint8 [S,3,256]) on the device.  The tables of the plan go up in one piece in
+    front of the first launch; four launches (six with ``graded``), no host read.  Nothing to do (strength 0, no frame, no pixel):
+    x itself and identity tables."""
+    L, H, W = (int(v) for v in x.shape[:3])
+    S = plan["S"]
+    if plan["strength"] == 0 or L == 0 or H * W == 0:
+        return x, _identity_curves(S, x.device)
+    parts = [plan[k] for k in ("starts", "ids", "mode", "scene_of")] + ([plan["gstarts"], plan["gids"]] if graded is not None else [])
+    table = torch.from_numpy(np.concatenate(parts)).to(x.device)        # one upload, in front of the first launch
+    starts, ids, mode, group, *rest = torch.split(table, [len(p) for p in parts])
+    with torch.cuda.device(x.device):
+        Q = ops.color_nodes(ops.color_hist(x), starts, ids, plan["clip"])
+        T = None
+        if graded is not None:
+            T = ops.color_nodes(ops.color_hist(graded), rest[0], rest[1], plan["clip"])
+            if T.shape[0] != S:                                         # no keys: the one pool of all graded frames, for every scene
+                T = T.expand(S, 3, ops.COLOR_NODES).contiguous()
+        luts = ops.color_lut(Q, mode, T, plan["target"], plan["min_range"], plan["max_gain"], plan["strength"])
+        out = ops.color_apply(x, luts, group)
+    return out, luts
+
+
+@torch.no_grad()
+def restore_color(frames_u8, scenes=None, graded=None, keys=None, otherwise="levels", clip=COLOR_CLIP, target=None,
+                  min_range=COLOR_MIN_RANGE, max_gain=COLOR_MAX_GAIN, strength=COLOR_STRENGTH, return_curves=False, device=None):
+    """Restores faded colour -- dye layers that have faded at different rates, a tape whose chroma has drifted: blacks gone red or
+    magenta, one channel with 60 % of its range left beside one with 90 % -- with one monotone tone curve per scene and channel,
+    where every other tool here moves the three channels of a pixel together: frames_u8 uint8 [L,H,W,3] (an array or a tensor) ->
+    uint8 [L,H,W,3], a numpy array, or a device tensor when the input is one (which is used where it is).  With ``return_curves``
+    the result is (out, luts), luts the uint8 [S,3,256] byte tables, one set per scene, which apply_color takes.  In a restoration
+    chain it stands after deflicker and in front of detect_defects and detect_line_scratches, whose thresholds are absolute
+    levels and see less on a print that has lost a third of its contrast.  It needs no model and no flows; everything after the
+    upload runs on the device (ops.color_hist, ops.color_nodes, ops.color_lut, ops.color_apply: four launches, six with ``graded``)
+    without a host read.  Integers throughout (include/e2fgvi_hip.h has the definition): the same arguments give the same bytes in
+    every run.
+
+    The channel histograms of a set of frames are pooled, and from the pool 32 quantile nodes per channel and a black and a white
+    point, below and above which ``clip`` = (lo, hi) per mille of the pixels lie, in 1/16 levels.  ``scenes``: None or a list of
+    cuts as plan_windows takes them (detect_cuts finds them); every scene gets curves of its own and nothing is pooled across a cut.
+      Without ``graded`` -- automatic levels, a first pass: the pool is the scene's own frames, and every channel's black and white
+    point are brought onto ``target`` = (lo, hi) in levels, or with None onto the darkest black and the brightest white point of
+    the scene's channels.  The curve is a straight line about the centre of the channel's range; a gain above ``max_gain`` / 256 is
+    cut, and a channel whose range is narrower than ``min_range`` levels (a flat frame, a title card) is left alone.
+      With ``graded`` and ``keys`` -- "grade one frame, the scene follows": graded uint8 [n,h,w,3] of any size, graded[i] frame
+    keys[i] as the colourist wants it.  A scene that holds keys pools its key frames and, apart, their graded versions, and its
+    curves move the 32 quantiles of the one onto those of the other, straight lines between them and slope 1 beyond the first and
+    the last.  A scene without a key follows ``otherwise``: "levels" as above, "keep" leaves it alone.
+      With ``graded`` alone -- a better print, a reference still: every scene's own quantiles are moved onto those of all graded
+    frames pooled.
+    ``strength`` / 256 of the way from the caller's bytes to the curve is gone; 0, no frame or no pixel runs no launch and returns
+    the caller's bytes.
+
+    Known limits: there is one grade per scene and no drift inside a scene, so a fade that progresses along a
+    reel needs cuts where it changes; the curves are per channel, so a cast that differs between shadows and highlights is
+    followed but crosstalk between the dye layers is not; automatic levels assume that every scene holds something near black
+    and something near white in every channel, and change a clean video too -- the 25 frames of tests/golden/tennis25.npz come
+    back at 41.68 dB against themselves, no byte by more than 8 levels, 9.4 % of them by more than 3 -- which is the price of the
+    automatic mode; a key frame has to show the scene's range, since beyond its first and last quantile the curve only shifts.
+    clip: two integers in [0, 250]; target: None or 0 <= lo < hi <= 255; min_range in [1, 255], max_gain in [256, 4096],
+    strength in [0, 256]: integers, no bools; otherwise "levels" or "keep"; keys strictly increasing frame numbers, one per graded
+    frame, and not without ``graded``; return_curves a bool; a string for ``scenes`` is refused; H W <= 2^26.  Argument errors are
+    ValueErrors that name the argument, raised before any device work.  There is no CPU path."""
+    plan = _check_restore_color_args(frames_u8, scenes, graded, keys, otherwise, clip, target, min_range, max_gain, strength,
+                                     return_curves)
+    device = _tool_device("restore_color", device, frames_u8)
+    x = _upload(frames_u8, device)
+    out, luts = _like_input(frames_u8, *_restore_color_device(x, None if graded is None else _upload(graded, x.device), plan))
+    return (out, luts) if return_curves else out
+
+
+def _check_apply_color_args(frames_u8, luts, scenes):
+    """the checks of apply_color from the arguments and the shapes alone -> scene_of int32 [L]"""
+    shape = _check_frames(frames_u8, True)
+    L = int(shape[0])
+    if int(shape[1]) * int(shape[2]) > ops.FLICKER_PIXELS_MAX:
+        raise ValueError("frames must have H W <= 2^26, got %d x %d" % (shape[1], shape[2]))
+    cuts = _scene_cuts(scenes, L)
+    lshape = tuple(getattr(luts, "shape", ()))
+    if lshape != (len(cuts) + 1, 3, 256) or not _is_u8(luts):
+        raise ValueError("luts must be uint8 [%d,3,256], one set of tables per scene, got %s %s"
+                         % (len(cuts) + 1, getattr(luts, "dtype", type(luts).__name__), lshape))
+    return _scene_table(cuts, L)
+
+
+@torch.no_grad()
+def apply_color(frames_u8, luts, scenes=None, device=None):
+    """Applies byte tables per scene and channel -- restore_color(return_curves=True)'s, corrected ones, or the caller's own:
+    frames_u8 uint8 [L,H,W,3], luts uint8 [S,3,256] with S the number of scenes that ``scenes`` (None or a list of cuts) makes ->
+    uint8 [L,H,W,3] as restore_color returns it; byte c of every pixel of a frame of scene s becomes luts[s][c][byte].  One launch
+    (ops.color_apply), none without a frame or a pixel; no host read.  Argument errors are ValueErrors that name the argument,
+    raised before any device work.  There is no CPU path."""
+    scene_of = _check_apply_color_args(frames_u8, luts, scenes)
+    device = _tool_device("apply_color", device, frames_u8)
+    x = _upload(frames_u8, device)
+    if x.numel() == 0:
+        return _like_input(frames_u8, x)[0]
+    return _like_input(frames_u8, ops.color_apply(x, _upload(luts, x.device), torch.from_numpy(scene_of).to(x.device)))[0]
+
+
 WEAVE_SPAN = 4                 # stabilize's defaults: DESIGN.md 3v has the measurements they were judged on
 WEAVE_RADIUS = 16
 WEAVE_MAX_SHIFT = 16

@@ -496,6 +496,49 @@ int e2fgvi_flicker_local_curves(const int32_t* hist, const int32_t* scene, int32
                                 int32_t gy, int32_t gx, int32_t span, int32_t max_shift, void* stream);
 int e2fgvi_flicker_local_apply(const uint8_t* frames, const int16_t* d16, uint8_t* out, int32_t L, int32_t H, int32_t W, int32_t gy,
                                int32_t gx, void* stream);
+/* Colour restoration (video.restore_color, video.apply_color): per group of frames and channel one monotone byte table, from the
+ * channel histograms pooled over the group and their quantile nodes.  All arithmetic is integer; // is the floor also for a
+ * negative numerator and >> of a negative number is the arithmetic shift.  Values with a 16 in them are in 1/16 levels.  K = 32.
+ *   frames uint8 [L,H,W,3], H W <= 2^26.
+ * 1. Histograms.  hist[t][c][v] = the number of pixels of frame t whose channel c equals v, int32 [L][3][256].
+ * 2. Pools.  A group g is a list of frames in CSR form: starts int32 [G+1], ids int32 [M]; group g owns ids[starts[g] :
+ *    starts[g+1]].  P_g[c][v] = the sum of hist[t][c][v] over the group's ids, in 64 bits;  N = the sum of a row;  C[v] = P[0] +
+ *    ... + P[v], C[-1] = 0.  An id outside [0, L) is skipped.  starts is read clamped to [0, M]; a group whose range is empty or
+ *    reversed has N = 0.
+ * 3. Nodes.  Q[g][c][0..33], int32 [G][3][34].  node(r): v = the smallest level with C[v] > r;  node(r) = 16 v + (16 (r -
+ *    C[v-1])) // P[v].  Q[k] = node(((2k + 1) N) // 64) for k < 32;  the black point Q[32] = node((lo N) // 1000);  the white
+ *    point Q[33] = node(N - 1 - (hi N) // 1000);  lo and hi in [0, 250], per mille.  N may reach 2^50: everything is 64-bit.  A
+ *    group with N = 0 gets zeros.
+ * 4. Table of group g, channel c, level v, uint8 [G][3][256].  x = 16 v;  mode int32 [G].
+ *      mode 0 (keep), and any other value:  o = x.
+ *      mode 1 (levels):  b = Q[g][c][32], w = Q[g][c][33];  channel c is usable when w - b >= 16 min_range.  With an automatic
+ *        target (lo_t < 0) B is the smallest b and Wt the largest w over the usable channels of g (no usable channel: every
+ *        table is the identity); otherwise B = 16 lo_t, Wt = 16 hi_t.  c not usable: o = x.  c usable: den = w - b,
+ *        num = min(Wt - B, (max_gain den) >> 8) -- a gain above max_gain / 256 is cut, and the centre of the range stays on the
+ *        centre of the target --, o = ((B + Wt) den + (2x - b - w) num + den) // (2 den).
+ *      mode 2 (match):  q[k] = Q[g][c][k], t[k] = clamp(T[g][c][k], 0, 4095), k < 32, T laid out as Q.  x <= q[0]: o = x + t[0] -
+ *        q[0].  Otherwise x >= q[31]: o = x + t[31] - q[31].  Otherwise k = the largest index with q[k] <= x, den = q[k+1] - q[k]
+ *        (above zero by the choice of k, whatever q holds), o = t[k] + (2 (x - q[k]) (t[k+1] - t[k]) + den) // (2 den).
+ *    o' = x + (((o - x) strength + 128) >> 8), strength in [0, 256];  lut[g][c][v] = clamp((o' + 8) >> 4, 0, 255).
+ * 5. Apply.  out[t,i,j,c] = lut[group[t]][c][frames[t,i,j,c]], group int32 [L]; a frame with group[t] outside [0, G) is copied.
+ * e2fgvi_color_hist does 1: it clears all L 768 words on the stream and adds with integer atomics (exact, the same in every run);
+ * every frame byte is read once.  e2fgvi_color_nodes does 2 and 3, a workgroup per group and channel, and writes every entry of
+ * Q.  e2fgvi_color_lut does 4 and writes every entry of lut; its Q is e2fgvi_color_nodes' (values in 0 .. 4095; others give some
+ * table and no fault); T is never null when G > 0 (Q itself where nothing is matched).  e2fgvi_color_apply does 5; every output
+ * byte is written once, by the thread that read the input byte: out may be frames itself (in place), any other overlap of the
+ * two ranges is E2FGVI_EINVAL.  Nothing is read on the host.
+ * L, H, W, G, M >= 0, H W <= 2^26, lo and hi in [0, 250], min_range in [1, 255], max_gain in [256, 4096], strength in [0, 256], the
+ * target lo_t = hi_t = -1 or 0 <= lo_t < hi_t <= 255 (E2FGVI_EINVAL otherwise, from the arguments alone).  No work -- L == 0 or
+ * H W == 0 for hist and apply, G == 0 for nodes and lut -- returns 0 without a launch and without looking at the pointers; with
+ * work a null pointer (hist of no frame, ids of no id and lut of no group may be null) or an int32 array that is not 4-byte
+ * aligned is E2FGVI_EINVAL.  Frames are launched in slabs of 65535. */
+int e2fgvi_color_hist(const uint8_t* frames, int32_t* hist, int32_t L, int32_t H, int32_t W, void* stream);
+int e2fgvi_color_nodes(const int32_t* hist, const int32_t* starts, const int32_t* ids, int32_t* Q, int32_t L, int32_t G, int32_t M,
+                       int32_t lo, int32_t hi, void* stream);
+int e2fgvi_color_lut(const int32_t* Q, const int32_t* T, const int32_t* mode, uint8_t* lut, int32_t G, int32_t lo_t, int32_t hi_t,
+                     int32_t min_range, int32_t max_gain, int32_t strength, void* stream);
+int e2fgvi_color_apply(const uint8_t* frames, const uint8_t* lut, const int32_t* group, uint8_t* out, int32_t L, int32_t H, int32_t W,
+                       int32_t G, void* stream);
 /* Weave stabiliser (video.stabilize): the translation of the picture from frame to frame -- gate weave, telecine jitter -- measured
  * from banded luma profiles, a path smoothed over a symmetric window, and the frames moved back onto it.  All arithmetic is
  * integer; "floor" is the floor for either sign, >> of a negative number is the arithmetic shift and & 15 its non-negative rest.
