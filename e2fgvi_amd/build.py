@@ -43,10 +43,11 @@ UNITS = [("error.hip", "error.o", []), ("conv.hip", "conv.o", []), ("conv.hip", 
          ("color.hip", "color.o", NOPK),
          ("weave.hip", "weave.o", NOPK),
          ("interlace.hip", "interlace.o", NOPK),
+         ("telecine.hip", "telecine.o", NOPK),
          ("denoise.hip", "denoise.o", NOPK),
          # the same: the restatement of tests/interpolate_cases.py matches the trajectories bit for bit
          ("interpolate.hip", "interpolate.o", NOPK + ["-ffp-contract=off"])]
-NOPK_OBJECTS = ("conv_nopk.o", "conv_bf16x.o", "conv_wino.o", "conv_wino4.o", "conv_wino_x3.o", "conv_tail.o", "mdcn.o", "attention_bf16.o", "attention_x3.o", "misc.o", "video.o", "yuv.o", "metrics.o", "mask_track.o", "defects.o", "pixel_track.o", "grain.o", "line_scratch.o", "flicker.o", "flicker_local.o", "color.o", "weave.o", "interlace.o", "denoise.o", "interpolate.o")
+NOPK_OBJECTS = ("conv_nopk.o", "conv_bf16x.o", "conv_wino.o", "conv_wino4.o", "conv_wino_x3.o", "conv_tail.o", "mdcn.o", "attention_bf16.o", "attention_x3.o", "misc.o", "video.o", "yuv.o", "metrics.o", "mask_track.o", "defects.o", "pixel_track.o", "grain.o", "line_scratch.o", "flicker.o", "flicker_local.o", "color.o", "weave.o", "interlace.o", "telecine.o", "denoise.o", "interpolate.o")
 OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 
 
@@ -111,6 +112,7 @@ def build(force=False, verbose=False, nopk_all=False, lib=None, tag=None, define
             verify_no_scratch(objdir, "color.o", "color_", "colour restoration")
             verify_no_scratch(objdir, "weave.o", "weave_", "weave stabiliser")
             verify_no_scratch(objdir, "interlace.o", "interlace_", "deinterlacer")
+            verify_no_scratch(objdir, "telecine.o", "telecine_", "inverse telecine")
             verify_no_scratch(objdir, "denoise.o", "denoise_", "temporal denoiser")
             verify_no_scratch(objdir, "interpolate.o", "interpolate_", "frame interpolation")
             verify_overlay_prefetch(objdir)
@@ -207,6 +209,7 @@ def verify_no_scratch(objdir=None, obj="conv_bf16x.o", marker="ELb0ELi2ELb1EEE",
     and over the four of color.o (the histogram and the apply kernel hold the dwords of all of a thread's groups at once);
     and over the five of weave.o (the apply kernel shifts the dwords of two tap rows into place in small arrays);
     and over the three of interlace.o (the fields kernel holds the dwords and the luma of up to twelve groups in small arrays);
+    and over the two of telecine.o (the scores kernel holds the 36 dwords of a row of three frames and the luma of four rows of 16 pixels);
     and over the four of denoise.o (the filter kernel keeps the 7 x 5 three-byte runs of a neighbour's luma window in a small array);
     and over the one of interpolate.o (it runs two fp64 fixed-point searches and up to four colour taps for each of a thread's four pixels)."""
     import re

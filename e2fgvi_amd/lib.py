@@ -171,6 +171,8 @@ SYMBOLS = {
     "e2fgvi_weave_apply": (C.c_int, [_fp] * 4 + [_i32] * 4 + [_fp]),
     "e2fgvi_interlace_scores": (C.c_int, [_fp] * 3 + [_i32] * 3 + [_fp]),
     "e2fgvi_deinterlace": (C.c_int, [_fp] * 3 + [_i32] * 7 + [_fp]),
+    "e2fgvi_telecine_scores": (C.c_int, [_fp] * 3 + [_i32] * 3 + [_fp]),
+    "e2fgvi_field_weave": (C.c_int, [_fp] * 3 + [_i32] * 5 + [_fp]),
     "e2fgvi_denoise": (C.c_int, [_fp] * 6 + [_i64] + [_i32] * 6 + [_fp]),
     "e2fgvi_interpolate": (C.c_int, [_fp] * 6 + [_i32] * 8 + [_fp]),
     "e2fgvi_softcomp_fold": (C.c_int, [_fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _fp]),

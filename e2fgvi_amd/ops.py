@@ -2741,6 +2741,58 @@ def deinterlace(frames, scene, tff, mode, guard, edges, out=None):
     return ou
 
 
+def telecine_scores(frames, scene):
+    """The field-matching scores of the inverse telecine, one launch over all frames (csrc/telecine.hip telecine_scores_kernel;
+    include/e2fgvi_hip.h has the definition; video.telecine_scores is the caller): frames uint8 [L,H,W,3], scene int32 [L], equal
+    entries = one scene -> device int64 [L,2,3,16]: M[t][q][j][cell] sets the rows of parity q of frame t - 1, t or t + 1 (j = 0,
+    1, 2; a frame outside the video or the scene is t itself) against their neighbours in frame t, cell by cell of the scene
+    detector's 4 x 4 grid; 0 when H < 4.  The inputs and the checks of interlace_scores.  There is no CPU path and no host read;
+    integer atomics: the same input gives the same bits in every run."""
+    lib = _L.load()
+    fr, sc = _device_inputs([("frames", frames, torch.uint8), ("scene", scene, torch.int32)], "frames")
+    L, H, W = _flicker_frames(fr)
+    _scene_table(sc, "scene", L)
+    with torch.cuda.device(fr.device):
+        M = _alloc(L > 0 and H > 0 and W > 0, (L, 2, 3, 16), torch.int64, fr.device)     # with work the entry clears every word
+        _L.check(lib.e2fgvi_telecine_scores(_ptr(fr), _ptr(sc), _ptr(M), L, H, W, _stream()), "telecine_scores")
+    return M
+
+
+def field_weave(frames, jobs, keep, out=None):
+    """Frames put together from the fields of two frames each, one launch (csrc/telecine.hip telecine_weave_kernel;
+    include/e2fgvi_hip.h has the definition; video.inverse_telecine is the caller): frames uint8 [L,H,W,3], ``jobs`` [n][2] = (a, b)
+    on the HOST (a list or an integer array) -> device uint8 [n,H,W,3]: the rows of parity ``keep`` (0 or 1, an integer, no bool) of
+    out[i] are the rows of frames[a_i], the others those of frames[b_i].  An id outside [0, L) is a ValueError, raised in front of
+    the upload of the jobs (the kernel clamps ids all the same).  ``out``: a device tensor of the result's shape to write into,
+    which must not overlap ``frames`` (the entry refuses it); every byte is written once.  The checks of interlace_scores; no host
+    read; no job or no pixel: no launch."""
+    lib = _L.load()
+    keep = _int_arg("keep", keep, 0, 1)
+    if isinstance(jobs, torch.Tensor) and jobs.is_cuda:
+        raise ValueError("jobs must be on the host (a list or an integer array [n][2]), got a device tensor")
+    jb = torch.as_tensor(jobs)
+    if jb.numel() == 0:
+        jb = torch.zeros((0, 2), dtype=torch.int64)
+    if jb.dim() != 2 or jb.shape[1] != 2 or jb.dtype not in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64):
+        raise ValueError("jobs must be integers [n][2], got %s %s" % (jb.dtype, tuple(jb.shape)))
+    named = [("frames", frames, torch.uint8)] + ([("out", out, torch.uint8)] if out is not None else [])
+    up = _device_inputs(named, "frames", written=("out",))
+    fr = up[0]
+    L, H, W = _flicker_frames(fr)
+    n = int(jb.shape[0])
+    if n and (int(jb.min()) < 0 or int(jb.max()) >= L):
+        raise ValueError("jobs must name frames in [0, %d), got %d .. %d" % (L, int(jb.min()), int(jb.max())))
+    shape = (n, H, W, 3)
+    if out is not None and tuple(up[1].shape) != shape:
+        raise ValueError("out must be %s, got %s" % (list(shape), tuple(up[1].shape)))
+    with torch.cuda.device(fr.device):
+        ou = up[1] if out is not None else torch.empty(shape, dtype=torch.uint8, device=fr.device)
+        if n and H * W:
+            jd = jb.to(torch.int32).contiguous().to(fr.device)
+            _L.check(lib.e2fgvi_field_weave(_ptr(fr), _ptr(jd), _ptr(ou), L, n, H, W, keep, _stream()), "field_weave")
+    return ou
+
+
 DENOISE_STRENGTH_MAX = 64                  # csrc/denoise.hip: parameters outside these ranges are E2FGVI_EINVAL
 DENOISE_SEARCH_MAX = 2
 DENOISE_PIXELS_MAX = 2 ** 31 - 256 - 1

@@ -1841,6 +1841,228 @@ def deinterlace(frames_u8, order="tff", rate="field", keep="first", scenes=None,
     return out
 
 
+TELECINE_MARGIN = 10           # matches_from_scores: per cent; checked on planted clips only (DESIGN.md 3ab has the ratios)
+_TELECINE_PATTERN = (0, 0, 1, 1, 0)        # the frames of a 3:2 cycle whose other field lies in a neighbour
+
+
+def _scene_spans(cuts, length):
+    """the scenes as [(first, behind the last), ...] from the list of cuts; none when there is no frame"""
+    edges = [0] + list(cuts) + [length]
+    return [(a, b) for a, b in zip(edges[:-1], edges[1:]) if b > a]
+
+
+def _check_telecine_args(keep, margin, cadence):
+    """keep=, margin= and cadence= of the telecine tools -> (the parity of the kept field, margin)"""
+    if not isinstance(keep, str) or keep not in ("top", "bottom"):
+        raise ValueError('keep must be "top" or "bottom", got %r' % (keep,))
+    if cadence is not None and (not isinstance(cadence, str) or cadence != "3:2"):
+        raise ValueError('cadence must be "3:2" or None, got %r' % (cadence,))
+    margin, = _check_ranges(("margin", margin, 1, 50))
+    return (0 if keep == "top" else 1), margin
+
+
+def matches_from_scores(M, keep="top", scenes=None, margin=TELECINE_MARGIN, cadence="3:2"):
+    """telecine_scores' M int64 [L,2,3,16] -> (k, orphan, locks): k int8 [L], the frame t + k[t] holds the field that belongs to the
+    kept field of frame t (0: its own other field); orphan bool [L], frames whose partner is not on the tape; locks, per scene
+    (d, phi, agree, disagree) or None.  The kept field has parity p = 0 for ``keep="top"``, 1 for "bottom"; q = 1 - p.
+
+    Match per frame: with c = M[t][q][1] and x = M[t][q][0] (k = -1), x = M[t][q][2] (k = +1): gain(k) = the sum of c - x over the
+    cells where 100 x < (100 - margin) c; k[t] = -1 if gain(-1) > gain(+1), +1 if gain(+1) > gain(-1), 0 otherwise.
+    Lock, with ``cadence="3:2"``: every scene [s, e) is tested against d in {-1, +1} and phi in 0 .. 4, pattern[t] = d (0, 0, 1,
+    1, 0)[(t - s + phi) % 5]; agree / disagree = the frames with k != 0 that equal / do not equal the pattern; the best hypothesis
+    has the largest agree - disagree, then the larger agree, then d = -1 before +1, then the smaller phi; the scene locks when agree
+    >= 4 and 10 disagree <= agree, and then takes the pattern for EVERY frame -- those that gave no evidence (static stretches,
+    flat frames) too.  A pattern entry that points outside the scene (-1 at its first frame, +1 at its last) is set to 0 and the
+    frame is flagged orphan.  A scene that does not lock keeps its raw matches, entries that point outside it set to 0 without a
+    flag; ``cadence=None`` skips the lock everywhere.
+    ``scenes``: None or a list of cuts as plan_windows takes them; margin an integer in [1, 50] (per cent), no bool.  ValueError
+    that names the argument otherwise.  Pure host code, exact integers."""
+    shape = tuple(getattr(M, "shape", ()))
+    if len(shape) != 4 or shape[1:] != (2, 3, 16) or str(getattr(M, "dtype", "")) not in ("int64", "torch.int64"):
+        raise ValueError("M must be int64 [L,2,3,16], got %s %s" % (getattr(M, "dtype", type(M).__name__), shape))
+    L = int(shape[0])
+    cuts = _scene_cuts(scenes, L)
+    p, margin = _check_telecine_args(keep, margin, cadence)
+    m = (M.cpu().numpy() if isinstance(M, torch.Tensor) else np.asarray(M)).astype(np.int64)[:, 1 - p]     # at most 2^36: the products fit
+    c = m[:, 1]
+    gain = [np.where(100 * m[:, j] < (100 - margin) * c, c - m[:, j], 0).sum(axis=1) for j in (0, 2)]
+    k = np.zeros(L, np.int8)
+    k[gain[0] > gain[1]] = -1
+    k[gain[1] > gain[0]] = 1
+    orphan = np.zeros(L, bool)
+    locks = []
+    for s, e in _scene_spans(cuts, L):
+        raw, best = k[s:e].astype(np.int64), None
+        decided = raw != 0
+        for d in ((-1, 1) if cadence else ()):
+            for phi in range(5):
+                pattern = d * np.array([_TELECINE_PATTERN[(i + phi) % 5] for i in range(e - s)], np.int64)
+                agree = int((decided & (raw == pattern)).sum())
+                disagree = int(decided.sum()) - agree
+                if best is None or (agree - disagree, agree) > (best[2] - best[3], best[2]):
+                    best = (d, phi, agree, disagree, pattern)
+        if best is not None and best[2] >= 4 and 10 * best[3] <= best[2]:
+            locks.append(best[:4])
+            k[s:e] = best[4]
+            orphan[s] = k[s] == -1
+            orphan[e - 1] |= k[e - 1] == 1
+        else:
+            locks.append(None)
+        if k[s] == -1:
+            k[s] = 0
+        if k[e - 1] == 1:
+            k[e - 1] = 0
+    return k, orphan, locks
+
+
+def plan_inverse_telecine(k, orphan, scenes=None):
+    """matches_from_scores' k int8 [L] and orphan bool [L] -> (jobs, cuts_out): jobs = [(t, t + k[t]), ...] for every frame that is
+    kept, in order -- the rows of the kept parity come from frame t, the others from frame t + k[t] -- and cuts_out, the cuts of
+    the result: cuts_out[i] = the number of kept frames in front of cut i.  Frame t is dropped when t - 1 is in its scene, k[t - 1]
+    - k[t] == 1 and neither of the two is an orphan: such a pair takes its second field from the same source frame and its first
+    fields matched that same field, so the two are one film frame twice.  The rule assumes no cadence: it drops one frame in five
+    of 3:2 material and nothing of 2:2 material or of progressive video.  k integers in [-1, 1], orphan bools, ``scenes`` None or
+    a list of cuts: ValueError that names the argument otherwise.  Pure host code."""
+    ka, oa = np.asarray(k), np.asarray(orphan)
+    if ka.ndim != 1 or ka.dtype.kind != "i" or (ka.size and (ka.min() < -1 or ka.max() > 1)):
+        raise ValueError("k must be integers [L] in [-1, 1], got %s %s" % (ka.dtype, ka.shape))
+    if oa.shape != ka.shape or oa.dtype != np.bool_:
+        raise ValueError("orphan must be bool [%d], got %s %s" % (len(ka), oa.dtype, oa.shape))
+    L = len(ka)
+    cuts = _scene_cuts(scenes, L)
+    scene_of = _scene_table(cuts, L)
+    ka = ka.astype(np.int64)
+    kept = np.ones(L, bool)
+    if L > 1:
+        kept[1:] = ~((scene_of[1:] == scene_of[:-1]) & (ka[:-1] - ka[1:] == 1) & ~oa[:-1] & ~oa[1:])
+    jobs = [(int(t), int(t + ka[t])) for t in np.flatnonzero(kept)]
+    return jobs, [int(kept[:c].sum()) for c in cuts]
+
+
+def _check_telecine_frames(frames_u8, scenes, keep, margin, cadence="3:2"):
+    """the checks the telecine tools share, from the arguments and the shapes alone -> (scene_of int32 [L], cuts, p, margin)"""
+    scene_of, cuts = _check_interlace_frames(frames_u8, scenes)
+    return (scene_of, cuts) + _check_telecine_args(keep, margin, cadence)
+
+
+def _telecine_scores_device(x, scene_of):
+    """telecine_scores after the argument checks and the upload of the frames: x uint8 [L,H,W,3] on the device -> M as numpy int64
+    [L,2,3,16].  One launch and one host read; no frame or no pixel: neither."""
+    L, H, W = (int(v) for v in x.shape[:3])
+    if L == 0 or H * W == 0:
+        return np.zeros((L, 2, 3, 16), np.int64)
+    so = torch.from_numpy(scene_of).to(x.device)            # in front of the launch
+    with torch.cuda.device(x.device):
+        return ops.telecine_scores(x, so).cpu().numpy()
+
+
+@torch.no_grad()
+def telecine_scores(frames_u8, scenes=None, device=None):
+    """The field-matching scores of detect_telecine and inverse_telecine: frames_u8 uint8 [L,H,W,3] (an array or a tensor, which is
+    used where it is when on the device) -> M int64 [L,2,3,16] as a numpy array.  One launch (ops.telecine_scores) and one host
+    read; include/e2fgvi_hip.h has the definition: M[t][q][j][cell] sets the rows of parity q of frame t - 1, t, t + 1 (j = 0, 1,
+    2; a frame outside the video or across a cut is t itself) against their neighbours in frame t, in each cell of the scene
+    detector's 4 x 4 grid.  ``scenes``: None or a list of cuts (a string is refused); H W <= 2^26: ValueErrors that name the
+    argument, raised before any device work.  There is no CPU path."""
+    scene_of, _ = _check_interlace_frames(frames_u8, scenes)
+    device = _tool_device("telecine_scores", device, frames_u8)
+    return _telecine_scores_device(_upload(frames_u8, device), scene_of)
+
+
+@torch.no_grad()
+def detect_telecine(frames_u8, scenes=None, keep="top", margin=TELECINE_MARGIN, return_scores=False, device=None):
+    """Says whether a video carries 3:2 pulldown: frames_u8 uint8 [L,H,W,3] (an array or a tensor) -> "3:2" when at least one scene
+    locks to the cadence and no scene with four or more decided frames (k != 0) fails to, "none" when no frame has k != 0,
+    "mixed" otherwise; with ``return_scores`` (verdict, M, k, locks), M int64 [L,2,3,16] and k int8 [L] as numpy arrays.  One
+    launch (ops.telecine_scores), one host read of M; matches_from_scores has the rule.  keep "top" or "bottom"; margin an
+    integer in [1, 50], return_scores a bool, a string for ``scenes`` is refused, H W <= 2^26: ValueErrors that name the
+    argument, raised before any device work.  There is no CPU path."""
+    scene_of, cuts, _, margin = _check_telecine_frames(frames_u8, scenes, keep, margin)
+    _check_flags(return_scores=return_scores)
+    device = _tool_device("detect_telecine", device, frames_u8)
+    M = _telecine_scores_device(_upload(frames_u8, device), scene_of)
+    k, _, locks = matches_from_scores(M, keep, cuts, margin)
+    spans = _scene_spans(cuts, len(k))
+    failed = any(lock is None and int((k[s:e] != 0).sum()) >= 4 for lock, (s, e) in zip(locks, spans))
+    verdict = "3:2" if any(locks) and not failed else "none" if not k.any() else "mixed"
+    return (verdict, M, k, locks) if return_scores else verdict
+
+
+def _check_inverse_telecine_args(frames_u8, scenes, keep, margin, cadence, orphans, order, return_plan):
+    """the checks of inverse_telecine from the arguments and the shapes alone -> (scene_of, cuts, p, margin, the deinterlacer's mode
+    for the orphans or None)"""
+    scene_of, cuts, p, margin = _check_telecine_frames(frames_u8, scenes, keep, margin, cadence)
+    if not isinstance(orphans, str) or orphans not in ("keep", "deinterlace"):
+        raise ValueError('orphans must be "keep" or "deinterlace", got %r' % (orphans,))
+    if not (order is None or (isinstance(order, str) and order in ("tff", "bff"))) or (orphans == "deinterlace" and order is None):
+        raise ValueError('order must be "tff" or "bff" (and one of them with orphans="deinterlace") or None, got %r' % (order,))
+    _check_flags(return_plan=return_plan)
+    mode = None
+    if orphans == "deinterlace":                             # the field of parity p is the first one under tff when p == 0
+        mode = ops.INTERLACE_MODES["first" if (order == "tff") == (p == 0) else "second"]
+    return scene_of, cuts, p, margin, mode
+
+
+def _inverse_telecine_device(x, scene_of, cuts, keep, margin, cadence, order, mode):
+    """inverse_telecine after the argument checks and the upload of the frames: x uint8 [L,H,W,3] on the device -> (uint8 [n,H,W,3]
+    on the device, the plan).  The scores launch, one host read, the host rules, one upload of the jobs, the weave launch; with
+    ``mode`` one deinterlacer launch per orphan over the three frames around it."""
+    L = int(x.shape[0])
+    k, orphan, locks = matches_from_scores(_telecine_scores_device(x, scene_of), keep, cuts, margin, cadence)
+    jobs, cuts_out = plan_inverse_telecine(k, orphan, cuts)
+    with torch.cuda.device(x.device):
+        out = ops.field_weave(x, jobs, 0 if keep == "top" else 1)
+        if mode is not None:
+            for i, (t, _) in enumerate(jobs):
+                if orphan[t]:
+                    lo = t - 1 if t > 0 and scene_of[t - 1] == scene_of[t] else t
+                    hi = t + 1 if t + 1 < L and scene_of[t + 1] == scene_of[t] else t
+                    out[i] = _deinterlace_device(x[lo:hi + 1], np.zeros(hi + 1 - lo, np.int32), order == "tff", mode, True, INTERLACE_EDGES)[t - lo]
+    plan = dict(matches=k, orphan=orphan, source=np.array(jobs, np.int32).reshape(-1, 2), cuts=cuts_out, locks=locks)
+    return out, plan
+
+
+@torch.no_grad()
+def inverse_telecine(frames_u8, scenes=None, keep="top", margin=TELECINE_MARGIN, cadence="3:2", orphans="keep", order=None,
+                     return_plan=False, device=None):
+    """Undoes 3:2 pulldown -- film on tape, where of every five video frames three are whole film frames and two hold fields of two
+    different film frames, combed wherever anything moves -- as the first step of a restoration chain, where deinterlace is the
+    wrong repair (it halves the vertical detail of frames that are whole on the tape and keeps the judder): the fields are put
+    back together and the repeats dropped, and what comes back is the film's own frames, byte for byte.  frames_u8 uint8
+    [L,H,W,3] (an array or a tensor) -> uint8 [n,H,W,3], n <= L, a numpy array, or a device tensor when the input is one (which
+    is used where it is).  It needs no model and no flows: the scores launch (ops.telecine_scores), one host read of M, the host
+    rules (matches_from_scores, plan_inverse_telecine), one upload of the jobs and the weave launch (ops.field_weave).  Integers
+    throughout (include/e2fgvi_hip.h has the definition): the same arguments give the same bytes in every run.
+
+    ``keep`` "top" or "bottom": the field of every frame that stays where it is; the other rows of output frame t come from
+    frame t + k[t], k in {-1, 0, +1}.  ``margin`` (per cent) is how much less a neighbour's field must comb than the frame's own,
+    cell by cell of a 4 x 4 grid, to be taken; ``cadence="3:2"`` locks every scene to the best of the ten 3:2 patterns when the
+    decided frames agree with it, so that frames without evidence (static stretches, flat frames) are matched too;
+    ``cadence=None`` takes the raw matches.  ``scenes``: None or a list of cuts as plan_windows takes them (detect_cuts finds
+    them); no field is taken from across a cut and no frame dropped across one.  An orphan -- a scene's first or last frame whose
+    partner field is not on the tape -- stays as it is, combed, with ``orphans="keep"``; ``orphans="deinterlace"`` needs
+    ``order`` "tff" or "bff" and replaces it by ``deinterlace(frames, order, rate="frame", keep=<the kept field>, scenes=scenes)[t]``
+    (computed on frames t - 1 .. t + 1 of its scene, which is all that picture depends on).  ``return_plan=True`` returns (frames,
+    plan), plan a dict of ``matches`` (k int8 [L]), ``orphan`` (bool [L]), ``source`` (int32 [n,2], the frames (t, t + k[t])
+    behind every output frame), ``cuts`` (of the result) and ``locks`` (per scene (d, phi, agree, disagree) or None).
+
+    What follows from that: a progressive or static video comes back as it was; every output row is a caller's row (orphans
+    deinterlaced apart); a video processed scene by scene and joined is the call with ``scenes``; no frame or no pixel runs no
+    launch.
+
+    Known limits (DESIGN.md 3ab): only 3:2 locks -- 2:2 with a field shift is matched but never locked, 2:3:3:2 is not locked;
+    field-blended conversions cannot be undone; an orphan stays combed unless ``orphans="deinterlace"``; video-originated
+    inserts inside film are left as they are; the margin was checked on planted clips only, not on real tape.
+    keep "top" or "bottom"; margin an integer in [1, 50], no bool; cadence "3:2" or None; orphans "keep" or "deinterlace"; order
+    None, "tff" or "bff"; return_plan a bool; a string for ``scenes`` is refused; H W <= 2^26.  Argument errors are ValueErrors
+    that name the argument, raised before any device work.  There is no CPU path."""
+    scene_of, cuts, _, margin, mode = _check_inverse_telecine_args(frames_u8, scenes, keep, margin, cadence, orphans, order, return_plan)
+    device = _tool_device("inverse_telecine", device, frames_u8)
+    out, plan = _inverse_telecine_device(_upload(frames_u8, device), scene_of, cuts, keep, margin, cadence, order, mode)
+    out, = _like_input(frames_u8, out)
+    return (out, plan) if return_plan else out
+
+
 DENOISE_STRENGTH = 8           # denoise's defaults: DESIGN.md 3x has the measurements they were judged on
 DENOISE_SEARCH = 1
 

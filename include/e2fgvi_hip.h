@@ -615,6 +615,30 @@ int e2fgvi_weave_apply(const uint8_t* frames, const int32_t* shift, uint8_t* out
 int e2fgvi_interlace_scores(const uint8_t* frames, const int32_t* scene, int64_t* D, int32_t L, int32_t H, int32_t W, void* stream);
 int e2fgvi_deinterlace(const uint8_t* frames, const int32_t* scene, uint8_t* out, int32_t L, int32_t H, int32_t W, int32_t tff,
                        int32_t mode, int32_t guard, int32_t edges, void* stream);
+/* Inverse telecine (video.inverse_telecine, video.detect_telecine): video made from 24 fps film by 3:2 pulldown holds, in two of
+ * every five frames, the fields of two different film frames; the scores say for every frame which neighbour its other field
+ * fits, and the weave puts the fields back together.  All arithmetic is integer.
+ *   frames uint8 [L,H,W,3];  scene int32 [L] on the device: two frames are in one scene when their entries are equal.
+ *   Y = (77 R + 150 G + 29 B + 128) >> 8, the luma of the other tools.
+ * Scores.  M int64 [L][2][3][16].  For frame t, row parity q -- the parity of the rows that would be taken from another frame -- and
+ * candidate j in {0, 1, 2}, which stands for the source s = t-1, t, t+1; a source that lies outside the video or in another scene
+ * is replaced by t itself.  m = (H - 2) / 2 (floor); the rows are y in [1, 2m] with (y & 1) == q, over all columns x: the rows of
+ * the interlace scores, none when H < 4.  cell = ((4 y) / H) * 4 + (4 x) / W, the scene detector's 4 x 4 grid.
+ *   M[t][q][j][cell] = the sum of |2 Y_s[y][x] - Y_t[y-1][x] - Y_t[y+1][x]|
+ * -- how badly the field of parity q of frame s combs against the other field of frame t, cell by cell.  Wherever t has a successor
+ * in its scene the sum over the cells of M[t][q][2] is D[t][q] of e2fgvi_interlace_scores; where a candidate was replaced by t,
+ * M[t][q][j] == M[t][q][1].
+ * e2fgvi_telecine_scores clears M on the stream and adds with integer atomics, one per (q, j, cell) and workgroup (exact, the same
+ * in every run).  Frames are launched in slabs of 65535.
+ * Weave.  jobs int32 [n][2] = (a, b) on the device, keep in {0, 1}, out uint8 [n,H,W,3]: the rows of parity keep of out[i] are the
+ * rows of frames[a_i], the other rows those of frames[b_i].  One launch; every output byte is written once; ids are clamped to
+ * [0, L-1], so none reads outside frames (the callers refuse them first); out must not overlap frames (E2FGVI_EINVAL).
+ * Nothing is read on the host.  Sizes >= 0, H W <= 2^26, keep in {0, 1} (E2FGVI_EINVAL otherwise, from the arguments alone); L, H or
+ * W == 0 (scores), n, H or W == 0 (weave) returns 0 without a launch and without looking at the pointers; a null pointer with work,
+ * a scene or jobs that is not 4-byte aligned, an M that is not 8-byte aligned and jobs with L == 0 are E2FGVI_EINVAL. */
+int e2fgvi_telecine_scores(const uint8_t* frames, const int32_t* scene, int64_t* M, int32_t L, int32_t H, int32_t W, void* stream);
+int e2fgvi_field_weave(const uint8_t* frames, const int32_t* jobs, uint8_t* out, int32_t L, int32_t n, int32_t H, int32_t W,
+                       int32_t keep, void* stream);
 /* Temporal denoiser (video.denoise): a pixel becomes the weighted mean of itself and of the pixels its flows point at in the frame
  * before and the frame after, each weighted by how well the 3 x 3 luma patch around it matches the pixel's own.  All integers after
  * one floor; >> of a negative number is the arithmetic shift, / of integers the floor.
