@@ -47,7 +47,48 @@ UNITS = [("error.hip", "error.o", []), ("conv.hip", "conv.o", []), ("conv.hip", 
          ("denoise.hip", "denoise.o", NOPK),
          # the same: the restatement of tests/interpolate_cases.py matches the trajectories bit for bit
          ("interpolate.hip", "interpolate.o", NOPK + ["-ffp-contract=off"])]
-NOPK_OBJECTS = ("conv_nopk.o", "conv_bf16x.o", "conv_wino.o", "conv_wino4.o", "conv_wino_x3.o", "conv_tail.o", "mdcn.o", "attention_bf16.o", "attention_x3.o", "misc.o", "video.o", "yuv.o", "metrics.o", "mask_track.o", "defects.o", "pixel_track.o", "grain.o", "line_scratch.o", "flicker.o", "flicker_local.o", "color.o", "weave.o", "interlace.o", "telecine.o", "denoise.o", "interpolate.o")
+NOPK_OBJECTS = tuple(obj for _, obj, extra in UNITS if "-packed-fp32-ops" in extra)
+# Build-time checks of the generated code, object by object: (object, mangled-name marker of the kernels meant, what they are called
+# in a message, whether its fp64 must be unfused).  Every kernel with the marker must be free of scratch -- no private segment, no
+# spilled register (verify_no_scratch); an object whose fp64 arithmetic the tests restate bit for bit in numpy, one rounding per
+# operation, is built with -ffp-contract=off and must hold no fused fp64 multiply-add (verify_no_fma64).
+KERNEL_CHECKS = [
+    # the ping-pong instantiations (template tail `false, 2, true`) keep 128 accumulator registers in place across four barriers per
+    # K-step; two ways of writing that loop made hipcc spill 414 registers or copy the kernel arguments to scratch without a warning
+    ("conv_bf16x.o", "ELb0ELi2ELb1EEE", "ping-pong", False),
+    ("conv_bf16x.o", "conv_halo_x3_kernel", "split-operand halo", False),
+    # four instantiations: the feathered ones hold five LDS phases in one kernel
+    ("video.o", "restore_u8_kernel", "paste-back", False),
+    # four: 24 sums and the next frame's 9 words in registers across the frame loop
+    ("video.o", "overlay_stats_kernel", "overlay sums", False),
+    # mask_track_step_kernel does its fp64 arithmetic in the order written; it has no scratch check
+    ("mask_track.o", None, None, True),
+    # four kernels: the candidate kernel unrolls up to 2 x 36 gathers for each of a thread's four pixels
+    ("defects.o", "defect_", "dust and dirt", False),
+    # two: the fill keeps the weights, offsets and flags of four corners in small arrays
+    ("pixel_track.o", "pixel_", "pixel propagation", True),
+    # two: the blocks pass keeps the 42 bytes of a thread's four Laplacians in small arrays
+    ("grain.o", "grain_", "film grain", False),
+    # four: the per-polarity counters of the columns pass are small arrays indexed in unrolled loops
+    ("line_scratch.o", "line_", "line scratch", False),
+    # three: the histogram and the apply kernel hold the dwords of all of a thread's groups at once
+    ("flicker.o", "flicker_", "deflicker", False),
+    # three: the same, and the apply kernel the four cell offsets and weights of a thread's pixels
+    ("flicker_local.o", "flicker_local_", "local deflicker", False),
+    # four: the histogram and the apply kernel hold the dwords of all of a thread's groups at once
+    ("color.o", "color_", "colour restoration", False),
+    # five: the apply kernel shifts the dwords of two tap rows into place in small arrays
+    ("weave.o", "weave_", "weave stabiliser", False),
+    # three: the fields kernel holds the dwords and the luma of up to twelve groups in small arrays
+    ("interlace.o", "interlace_", "deinterlacer", False),
+    # two: the scores kernel holds the 36 dwords of a row of three frames and the luma of four rows of 16 pixels
+    ("telecine.o", "telecine_", "inverse telecine", False),
+    # four: the filter kernel keeps the 7 x 5 three-byte runs of a neighbour's luma window in a small array
+    ("denoise.o", "denoise_", "temporal denoiser", False),
+    # one: two fp64 fixed-point searches and up to four colour taps for each of a thread's four pixels; its quotients k / d come from
+    # a table so that no division is contracted
+    ("interpolate.o", "interpolate_", "frame interpolation", True),
+]
 OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 
 
@@ -74,8 +115,8 @@ def build(force=False, verbose=False, nopk_all=False, lib=None, tag=None, define
     os.makedirs(objdir, exist_ok=True)
     out = lib or (os.path.join(CSRC, "libe2fgvi_hip_%s.so" % tag) if tag else
                   os.path.join(CSRC, "libe2fgvi_hip_nopk.so") if nopk_all else LIB)
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "flicker_common.h"), os.path.join(HERE, "..", "include", "e2fgvi_hip.h"),
-               os.path.abspath(__file__)]
+    headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h"))
+    headers += [os.path.join(HERE, "..", "include", "e2fgvi_hip.h"), os.path.abspath(__file__)]
     jobs = []
     for src, obj, extra in UNITS:
         sp, op = os.path.join(CSRC, src), os.path.join(objdir, obj)
@@ -99,27 +140,14 @@ def build(force=False, verbose=False, nopk_all=False, lib=None, tag=None, define
         if not nopk_all:
             verify_wino_waits(objdir)
             verify_exit_reuse(objdir)
-            verify_no_scratch(objdir)
-            verify_no_scratch(objdir, "conv_bf16x.o", "conv_halo_x3_kernel", "split-operand halo")
-            verify_no_scratch(objdir, "video.o", "restore_u8_kernel", "paste-back")
-            verify_no_scratch(objdir, "video.o", "overlay_stats_kernel", "overlay sums")
-            verify_no_scratch(objdir, "defects.o", "defect_", "dust and dirt")
-            verify_no_scratch(objdir, "pixel_track.o", "pixel_", "pixel propagation")
-            verify_no_scratch(objdir, "grain.o", "grain_", "film grain")
-            verify_no_scratch(objdir, "line_scratch.o", "line_", "line scratch")
-            verify_no_scratch(objdir, "flicker.o", "flicker_", "deflicker")
-            verify_no_scratch(objdir, "flicker_local.o", "flicker_local_", "local deflicker")
-            verify_no_scratch(objdir, "color.o", "color_", "colour restoration")
-            verify_no_scratch(objdir, "weave.o", "weave_", "weave stabiliser")
-            verify_no_scratch(objdir, "interlace.o", "interlace_", "deinterlacer")
-            verify_no_scratch(objdir, "telecine.o", "telecine_", "inverse telecine")
-            verify_no_scratch(objdir, "denoise.o", "denoise_", "temporal denoiser")
-            verify_no_scratch(objdir, "interpolate.o", "interpolate_", "frame interpolation")
+            for obj, marker, what, _ in KERNEL_CHECKS:
+                if marker:
+                    verify_no_scratch(objdir, obj, marker, what)
             verify_overlay_prefetch(objdir)
             verify_no_pk_u8(objdir)
-            verify_no_fma64(objdir)
-            verify_no_fma64(objdir, "pixel_track.o")
-            verify_no_fma64(objdir, "interpolate.o")
+            for obj, _, _, unfused in KERNEL_CHECKS:
+                if unfused:
+                    verify_no_fma64(objdir, obj)
     return out
 
 
@@ -180,8 +208,8 @@ def verify_no_fma64(objdir=None, obj="mask_track.o"):
 def verify_no_pk_u8(objdir=None):
     """No unit may hold v_ashr_pk_u8_i32 / v_ashr_pk_i8_i32 (gfx950: shift two int32, clamp each to a byte, pack the pair into the
     low half of the destination).  hipcc forms it from two clipped shifts that are packed into one word with other bytes and ORs
-    those bytes on top of the result; on the chip the bytes ORed on top came out wrong in csrc/yuv.hip's decoder (its store_bytes
-    has the account and the empty asm that keeps the pattern from forming).  Returns the number of objects read."""
+    those bytes on top of the result; on the chip the bytes ORed on top came out wrong in csrc/yuv.hip's decoder (csrc/frame_bytes.h
+    fb_byte has the account and the empty asm that keeps the pattern from forming).  Returns the number of objects read."""
     import re
     objdir = objdir or os.path.join(CSRC, "build")
     if not os.path.exists(OBJDUMP):
@@ -190,28 +218,14 @@ def verify_no_pk_u8(objdir=None):
         found = re.findall(r"v_ashr_pk_[ui]8_i32", device_isa(os.path.join(objdir, obj)))
         if found:
             raise RuntimeError("%s: %d v_ashr_pk_u8_i32 / v_ashr_pk_i8_i32 instructions: the bytes packed beside their result come out "
-                               "wrong on the chip (csrc/yuv.hip store_bytes)" % (obj, len(found)))
+                               "wrong on the chip (csrc/frame_bytes.h fb_byte)" % (obj, len(found)))
     return len(UNITS)
 
 
 def verify_no_scratch(objdir=None, obj="conv_bf16x.o", marker="ELb0ELi2ELb1EEE", what="ping-pong"):
-    """The ping-pong instantiations of conv_bf16x_kernel (template tail `false, 2, true`) keep 128 accumulator registers in place
-    across four barriers per K-step; two ways of writing that loop made hipcc spill 414 registers or copy the kernel arguments to
-    scratch without a warning (csrc/conv_bf16x.hip, PP).  Fails the build when one of them has a private segment or a spill.
-    Also run over the four instantiations of restore_u8_kernel (video.o): the feathered ones hold five LDS phases in one kernel;
-    and over the four of overlay_stats_kernel, which keeps 24 sums and the next frame's 9 words in registers across its frame loop;
-    and over the four kernels of defects.o (the candidate kernel unrolls up to 2 x 36 gathers for each of a thread's four pixels);
-    and over the two of pixel_track.o (the fill keeps the weights, offsets and flags of four corners in small arrays);
-    and over the two of grain.o (the blocks pass keeps the 42 bytes of a thread's four Laplacians in small arrays);
-    and over the four of line_scratch.o (the per-polarity counters of the columns pass are small arrays indexed in unrolled loops);
-    and over the three of flicker.o (the histogram and the apply kernel hold the dwords of all of a thread's groups at once);
-    and over the three of flicker_local.o (the same, and the apply kernel the four cell offsets and weights of a thread's pixels);
-    and over the four of color.o (the histogram and the apply kernel hold the dwords of all of a thread's groups at once);
-    and over the five of weave.o (the apply kernel shifts the dwords of two tap rows into place in small arrays);
-    and over the three of interlace.o (the fields kernel holds the dwords and the luma of up to twelve groups in small arrays);
-    and over the two of telecine.o (the scores kernel holds the 36 dwords of a row of three frames and the luma of four rows of 16 pixels);
-    and over the four of denoise.o (the filter kernel keeps the 7 x 5 three-byte runs of a neighbour's luma window in a small array);
-    and over the one of interpolate.o (it runs two fp64 fixed-point searches and up to four colour taps for each of a thread's four pixels)."""
+    """Fails the build when a kernel of ``obj`` whose mangled name holds ``marker`` has a private segment or a spilled register:
+    hipcc spills, or copies kernel arguments to scratch, without a warning.  KERNEL_CHECKS lists the objects this runs over on every
+    build and why each is there.  Returns the number of kernels read; none found is an error too."""
     import re
     import shutil
     import tempfile

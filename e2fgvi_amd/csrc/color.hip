@@ -26,12 +26,14 @@
 // picked by a shift) or, with -DCOL_PACKED=0, three byte tables (ds_read_u8); profiles/color.txt has what both measured.  Bytes
 // are put together into dwords in registers; each output byte is written once, by the thread that read the input byte, so
 // out == frames is in order.
-#include "flicker_common.h"          // the group of four pixels and the constants
+#include "frame_bytes.h"
 
 namespace {
 
+constexpr int COL_NTH = 256;
+constexpr int COL_K = 32;                 // quantile nodes per group and channel, as the deflicker's
 constexpr int COL_HIT = 8;                // groups per thread of the histogram kernel
-constexpr int COL_HPX = FL_NTH * FL_PX * COL_HIT;
+constexpr int COL_HPX = COL_NTH * FB_PX * COL_HIT;
 // A/B switches (build.build_variant("tag", "-DCOL_COPIES=1")); profiles/color.txt has what they measured
 #ifndef COL_COPIES
 #define COL_COPIES 8
@@ -44,55 +46,47 @@ constexpr int COL_HPX = FL_NTH * FL_PX * COL_HIT;
 #endif
 constexpr int COL_HC = COL_COPIES;        // copies of each histogram in LDS: a power of two
 constexpr int COL_AIT = 4;                // groups per thread of the apply kernel
-constexpr int COL_APX = FL_NTH * FL_PX * COL_AIT;
-constexpr int COL_Q = FL_K + 2;           // nodes per group and channel: 32 quantiles, the black and the white point
+constexpr int COL_APX = COL_NTH * FB_PX * COL_AIT;
+constexpr int COL_Q = COL_K + 2;          // nodes per group and channel: 32 quantiles, the black and the white point
 constexpr int COL_CLIP_MAX = 250;         // per mille
 constexpr int COL_GAIN_MIN = 256, COL_GAIN_MAX = 4096;
 
-// byte i (0 .. 11) of a group of four pixels held in three dwords
-__device__ __forceinline__ int col_get(const unsigned (&w)[3], int i) { return (int)((w[i >> 2] >> (8 * (i & 3))) & 255u); }
-
-__global__ void __launch_bounds__(FL_NTH)
+__global__ void __launch_bounds__(COL_NTH)
 color_hist_kernel(const uint8_t* __restrict__ frames, int t0, int N, int* __restrict__ hist) {
     __shared__ int s_h[3 * 256 * COL_HC];
     const int t = t0 + (int)blockIdx.y;
     const int tid = (int)threadIdx.x;
-    for (int i = tid; i < 3 * 256 * COL_HC; i += FL_NTH) s_h[i] = 0;
+    for (int i = tid; i < 3 * 256 * COL_HC; i += COL_NTH) s_h[i] = 0;
     __syncthreads();
     const uint8_t* fr = frames + (long long)t * N * 3;
-    const int p0 = (int)blockIdx.x * COL_HPX + tid * FL_PX;       // < 2^26 + 8192: blockIdx.x < ceil(N / COL_HPX)
+    const int p0 = (int)blockIdx.x * COL_HPX + tid * FB_PX;       // < 2^26 + 8192: blockIdx.x < ceil(N / COL_HPX)
     int* mine = s_h + (tid & (COL_HC - 1));
     // the same for every thread of the frame: a group is 12 bytes
     if (((uintptr_t)fr & 3) == 0) {
         unsigned w[COL_HIT][3];
 #pragma unroll
         for (int k = 0; k < COL_HIT; ++k) {
-            const int p = p0 + k * FL_NTH * FL_PX;
+            const int p = p0 + k * COL_NTH * FB_PX;
             w[k][0] = w[k][1] = w[k][2] = 0;
-            if (p + FL_PX <= N) {                                  // the twelve bytes lie in frame t
-                const unsigned* q = reinterpret_cast<const unsigned*>(fr + (long long)p * 3);
-                w[k][0] = q[0];
-                w[k][1] = q[1];
-                w[k][2] = q[2];
-            }
+            if (p + FB_PX <= N) fb_load_dwords(fr + (long long)p * 3, w[k]);       // the twelve bytes lie in frame t
         }
 #pragma unroll
         for (int k = 0; k < COL_HIT; ++k) {
-            const int p = p0 + k * FL_NTH * FL_PX;
-            if (p + FL_PX <= N) {
+            const int p = p0 + k * COL_NTH * FB_PX;
+            if (p + FB_PX <= N) {
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
-                    int v[FL_PX];
+                    int v[FB_PX];
 #pragma unroll
-                    for (int j = 0; j < FL_PX; ++j) v[j] = col_get(w[k], 3 * j + c);
+                    for (int j = 0; j < FB_PX; ++j) v[j] = fb_get(w[k], 3 * j + c);
 #pragma unroll
-                    for (int j = 0; j < FL_PX; ++j) {
+                    for (int j = 0; j < FB_PX; ++j) {
                         if (COL_MERGE) {
                             // the first of the equal bytes counts for all of them
                             bool seen = false;
                             int n = 1;
 #pragma unroll
-                            for (int i = 0; i < FL_PX; ++i) {
+                            for (int i = 0; i < FB_PX; ++i) {
                                 if (i < j) seen = seen || v[i] == v[j];
                                 if (i > j) n += v[i] == v[j] ? 1 : 0;
                             }
@@ -111,8 +105,8 @@ color_hist_kernel(const uint8_t* __restrict__ frames, int t0, int N, int* __rest
         }
     } else {
         for (int k = 0; k < COL_HIT; ++k) {
-            const int p = p0 + k * FL_NTH * FL_PX;
-            for (int j = 0; j < FL_PX && p + j < N; ++j) {
+            const int p = p0 + k * COL_NTH * FB_PX;
+            for (int j = 0; j < FB_PX && p + j < N; ++j) {
                 const uint8_t* q = fr + (long long)(p + j) * 3;
                 for (int c = 0; c < 3; ++c) atomicAdd(mine + (c * 256 + q[c]) * COL_HC, 1);
             }
@@ -140,7 +134,7 @@ __device__ __forceinline__ long long col_scan256(long long v, long long* s_w) {
     __syncthreads();
     long long base = 0;
 #pragma unroll
-    for (int w = 0; w < FL_NTH / 64 - 1; ++w)
+    for (int w = 0; w < COL_NTH / 64 - 1; ++w)
         if (w < wave) base += s_w[w];
     return v + base;
 }
@@ -160,11 +154,11 @@ __device__ __forceinline__ int col_node(const long long* s_c, long long r) {
     return 16 * lo + (int)frac;
 }
 
-__global__ void __launch_bounds__(FL_NTH)
+__global__ void __launch_bounds__(COL_NTH)
 color_nodes_kernel(const int* __restrict__ hist, const int* __restrict__ starts, const int* __restrict__ ids, int L, int M, int lo,
                    int hi, int* __restrict__ Q) {
     __shared__ long long s_c[256];
-    __shared__ long long s_w[FL_NTH / 64];
+    __shared__ long long s_w[COL_NTH / 64];
     const int g = (int)(blockIdx.x / 3), c = (int)(blockIdx.x % 3);
     const int v = (int)threadIdx.x;
     const int i0 = min(max(starts[g], 0), M), i1 = min(max(starts[g + 1], 0), M);
@@ -179,8 +173,8 @@ color_nodes_kernel(const int* __restrict__ hist, const int* __restrict__ starts,
         const long long n = s_c[255];
         int q = 0;
         if (n > 0) {
-            const long long r = v < FL_K ? ((long long)(2 * v + 1) * n) / (2 * FL_K)
-                              : v == FL_K ? ((long long)lo * n) / 1000 : n - 1 - ((long long)hi * n) / 1000;
+            const long long r = v < COL_K ? ((long long)(2 * v + 1) * n) / (2 * COL_K)
+                              : v == COL_K ? ((long long)lo * n) / 1000 : n - 1 - ((long long)hi * n) / 1000;
             q = col_node(s_c, r);
         }
         Q[((long long)g * 3 + c) * COL_Q + v] = q;
@@ -193,7 +187,7 @@ __device__ __forceinline__ long long col_floor_div(long long a, long long b) {
     return (a % b != 0 && a < 0) ? q - 1 : q;
 }
 
-__global__ void __launch_bounds__(FL_NTH)
+__global__ void __launch_bounds__(COL_NTH)
 color_lut_kernel(const int* __restrict__ Q, const int* __restrict__ T, const int* __restrict__ mode, int lo_t, int hi_t, int min_range,
                  int max_gain, int strength, uint8_t* __restrict__ lut) {
     const int g = (int)blockIdx.x, v = (int)threadIdx.x;
@@ -205,8 +199,8 @@ color_lut_kernel(const int* __restrict__ Q, const int* __restrict__ T, const int
     bool usable[3], any = false;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        b[c] = Qg[c * COL_Q + FL_K];
-        w[c] = Qg[c * COL_Q + FL_K + 1];
+        b[c] = Qg[c * COL_Q + COL_K];
+        w[c] = Qg[c * COL_Q + COL_K + 1];
         usable[c] = w[c] - b[c] >= 16LL * min_range;
         if (usable[c]) {
             B = any ? (b[c] < B ? b[c] : B) : b[c];
@@ -232,13 +226,13 @@ color_lut_kernel(const int* __restrict__ Q, const int* __restrict__ T, const int
         } else if (md == 2) {
             const int* q = Qg + c * COL_Q;
             const int* tt = Tg + c * COL_Q;
-            const long long q0 = q[0], q31 = q[FL_K - 1];
+            const long long q0 = q[0], q31 = q[COL_K - 1];
             if (x <= q0) {
                 o = x + min(max(tt[0], 0), 4095) - q0;
             } else if (x >= q31) {
-                o = x + min(max(tt[FL_K - 1], 0), 4095) - q31;
+                o = x + min(max(tt[COL_K - 1], 0), 4095) - q31;
             } else {
-                int k = FL_K - 2;                                  // the largest index with q[k] <= x: q[0] < x, so there is one
+                int k = COL_K - 2;                                  // the largest index with q[k] <= x: q[0] < x, so there is one
                 while (k > 0 && (long long)q[k] > x) --k;
                 int k1 = k + 1;                                    // and q[k + 1] > x by the choice of k
                 const long long den = (long long)q[k1] - q[k];
@@ -259,7 +253,7 @@ __device__ __forceinline__ unsigned col_look(const unsigned* s_t, int c, int v) 
 __device__ __forceinline__ unsigned col_look(const uint8_t* s_t, int c, int v) { return s_t[c * 256 + v]; }
 #endif
 
-__global__ void __launch_bounds__(FL_NTH)
+__global__ void __launch_bounds__(COL_NTH)
 color_apply_kernel(const uint8_t* frames, const uint8_t* __restrict__ lut, const int* __restrict__ group, int t0, int N, int G,
                    uint8_t* out) {
 #if COL_PACKED
@@ -287,35 +281,30 @@ color_apply_kernel(const uint8_t* frames, const uint8_t* __restrict__ lut, const
     __syncthreads();
     const uint8_t* fr = frames + (long long)t * N * 3;
     uint8_t* fo = out + (long long)t * N * 3;
-    const int p0 = (int)blockIdx.x * COL_APX + tid * FL_PX;
+    const int p0 = (int)blockIdx.x * COL_APX + tid * FB_PX;
     const bool aligned = (((uintptr_t)fr | (uintptr_t)fo) & 3) == 0;       // the same for every thread of the frame
     unsigned w[COL_AIT][3];
     // frames and out may be the same buffer (no __restrict__): a thread reads the bytes of its groups before it writes any of them
     if (aligned) {
 #pragma unroll
         for (int k = 0; k < COL_AIT; ++k) {
-            const int p = p0 + k * FL_NTH * FL_PX;
+            const int p = p0 + k * COL_NTH * FB_PX;
             w[k][0] = w[k][1] = w[k][2] = 0;
-            if (p + FL_PX <= N) {                                  // the twelve bytes lie in frame t
-                const unsigned* q = reinterpret_cast<const unsigned*>(fr + (long long)p * 3);
-                w[k][0] = q[0];
-                w[k][1] = q[1];
-                w[k][2] = q[2];
-            }
+            if (p + FB_PX <= N) fb_load_dwords(fr + (long long)p * 3, w[k]);       // the twelve bytes lie in frame t
         }
     }
 #pragma unroll
     for (int k = 0; k < COL_AIT; ++k) {
-        const int p = p0 + k * FL_NTH * FL_PX;
-        if (aligned && p + FL_PX <= N) {
+        const int p = p0 + k * COL_NTH * FB_PX;
+        if (aligned && p + FB_PX <= N) {
             unsigned b[12];
 #pragma unroll
-            for (int i = 0; i < 12; ++i) b[i] = col_look(s_t, i % 3, col_get(w[k], i));
+            for (int i = 0; i < 12; ++i) b[i] = col_look(s_t, i % 3, fb_get(w[k], i));
             unsigned* o = reinterpret_cast<unsigned*>(fo + (long long)p * 3);
 #pragma unroll
             for (int i = 0; i < 3; ++i) o[i] = b[4 * i] | (b[4 * i + 1] << 8) | (b[4 * i + 2] << 16) | (b[4 * i + 3] << 24);
         } else {
-            for (int j = 0; j < FL_PX && p + j < N; ++j) {
+            for (int j = 0; j < FB_PX && p + j < N; ++j) {
                 const uint8_t* q = fr + (long long)(p + j) * 3;
                 const int r = q[0], gr = q[1], bl = q[2];
                 uint8_t* o = fo + (long long)(p + j) * 3;
@@ -327,16 +316,10 @@ color_apply_kernel(const uint8_t* frames, const uint8_t* __restrict__ lut, const
     }
 }
 
-int col_check_sizes(const char* who, int32_t L, int32_t H, int32_t W) {
-    E2_REQUIRE(L >= 0 && H >= 0 && W >= 0, E2FGVI_EINVAL, "%s: negative size (L = %d, H = %d, W = %d)", who, L, H, W);
-    E2_REQUIRE((int64_t)H * W <= FL_N_MAX, E2FGVI_EINVAL, "%s: needs H * W <= 2^26, got %d x %d", who, H, W);
-    return 0;
-}
-
 }  // namespace
 
 extern "C" int e2fgvi_color_hist(const uint8_t* frames, int32_t* hist, int32_t L, int32_t H, int32_t W, void* stream) {
-    if (int rc = col_check_sizes("color_hist", L, H, W)) return rc;
+    if (int rc = fb_check_sizes("color_hist", L, H, W)) return rc;
     const int N = H * W;
     if (L == 0 || N == 0) return 0;                                // no pixel: no launch, and the pointers are not looked at
     E2_REQUIRE(frames && hist, E2FGVI_EINVAL, "color_hist: null pointer");
@@ -345,12 +328,9 @@ extern "C" int e2fgvi_color_hist(const uint8_t* frames, int32_t* hist, int32_t L
     hipError_t e = hipMemsetAsync(hist, 0, sizeof(int32_t) * 3 * 256 * (size_t)L, st);
     E2_REQUIRE(e == hipSuccess, (int)e, "color_hist: hipMemsetAsync failed: %s", hipGetErrorString(e));
     const unsigned nblk = (unsigned)((N + COL_HPX - 1) / COL_HPX);
-    for (int t0 = 0; t0 < L; t0 += FL_FRAMES_MAX) {
-        const dim3 grid(nblk, (unsigned)(L - t0 < FL_FRAMES_MAX ? L - t0 : FL_FRAMES_MAX), 1);
-        hipLaunchKernelGGL(color_hist_kernel, grid, dim3(FL_NTH), 0, st, frames, t0, N, hist);
-        E2_LAUNCH_CHECK("color_hist");
-    }
-    return 0;
+    return fb_slabs("color_hist", L, [&](int t0, unsigned n) {
+        hipLaunchKernelGGL(color_hist_kernel, dim3(nblk, n), dim3(COL_NTH), 0, st, frames, t0, N, hist);
+    });
 }
 
 extern "C" int e2fgvi_color_nodes(const int32_t* hist, const int32_t* starts, const int32_t* ids, int32_t* Q, int32_t L, int32_t G,
@@ -364,7 +344,7 @@ extern "C" int e2fgvi_color_nodes(const int32_t* hist, const int32_t* starts, co
     E2_REQUIRE(starts && Q && (hist || L == 0 || M == 0) && (ids || M == 0), E2FGVI_EINVAL, "color_nodes: null pointer");
     E2_REQUIRE((((uintptr_t)hist | (uintptr_t)starts | (uintptr_t)ids | (uintptr_t)Q) & 3) == 0, E2FGVI_EINVAL,
                "color_nodes: hist, starts, ids and Q must be 4-byte aligned");
-    hipLaunchKernelGGL(color_nodes_kernel, dim3((unsigned)G * 3u), dim3(FL_NTH), 0, (hipStream_t)stream, hist, starts, ids, L, M, lo, hi,
+    hipLaunchKernelGGL(color_nodes_kernel, dim3((unsigned)G * 3u), dim3(COL_NTH), 0, (hipStream_t)stream, hist, starts, ids, L, M, lo, hi,
                        Q);
     E2_LAUNCH_CHECK("color_nodes");
     return 0;
@@ -383,7 +363,7 @@ extern "C" int e2fgvi_color_lut(const int32_t* Q, const int32_t* T, const int32_
     E2_REQUIRE(Q && T && mode && lut, E2FGVI_EINVAL, "color_lut: null pointer");
     E2_REQUIRE((((uintptr_t)Q | (uintptr_t)T | (uintptr_t)mode) & 3) == 0, E2FGVI_EINVAL,
                "color_lut: Q, T and mode must be 4-byte aligned");
-    hipLaunchKernelGGL(color_lut_kernel, dim3((unsigned)G), dim3(FL_NTH), 0, (hipStream_t)stream, Q, T, mode, lo_t, hi_t, min_range,
+    hipLaunchKernelGGL(color_lut_kernel, dim3((unsigned)G), dim3(COL_NTH), 0, (hipStream_t)stream, Q, T, mode, lo_t, hi_t, min_range,
                        max_gain, strength, lut);
     E2_LAUNCH_CHECK("color_lut");
     return 0;
@@ -391,20 +371,17 @@ extern "C" int e2fgvi_color_lut(const int32_t* Q, const int32_t* T, const int32_
 
 extern "C" int e2fgvi_color_apply(const uint8_t* frames, const uint8_t* lut, const int32_t* group, uint8_t* out, int32_t L, int32_t H,
                                   int32_t W, int32_t G, void* stream) {
-    if (int rc = col_check_sizes("color_apply", L, H, W)) return rc;
+    if (int rc = fb_check_sizes("color_apply", L, H, W)) return rc;
     E2_REQUIRE(G >= 0, E2FGVI_EINVAL, "color_apply: negative size (G = %d)", G);
     const int N = H * W;
     if (L == 0 || N == 0) return 0;                                // no pixel: no launch, and the pointers are not looked at
     E2_REQUIRE(frames && group && out && (lut || G == 0), E2FGVI_EINVAL, "color_apply: null pointer");
     E2_REQUIRE(((uintptr_t)group & 3) == 0, E2FGVI_EINVAL, "color_apply: group must be 4-byte aligned");
-    const uint64_t bytes = (uint64_t)L * (uint64_t)N * 3, a = (uint64_t)(uintptr_t)frames, b = (uint64_t)(uintptr_t)out;
-    E2_REQUIRE(a == b || a + bytes <= b || b + bytes <= a, E2FGVI_EINVAL, "color_apply: out must be frames itself or not overlap it");
+    E2_REQUIRE(fb_same_or_disjoint(frames, out, (uint64_t)L * (uint64_t)N * 3), E2FGVI_EINVAL,
+               "color_apply: out must be frames itself or not overlap it");
     hipStream_t st = (hipStream_t)stream;
     const unsigned nblk = (unsigned)((N + COL_APX - 1) / COL_APX);
-    for (int t0 = 0; t0 < L; t0 += FL_FRAMES_MAX) {
-        const dim3 grid(nblk, (unsigned)(L - t0 < FL_FRAMES_MAX ? L - t0 : FL_FRAMES_MAX), 1);
-        hipLaunchKernelGGL(color_apply_kernel, grid, dim3(FL_NTH), 0, st, frames, lut, group, t0, N, G, out);
-        E2_LAUNCH_CHECK("color_apply");
-    }
-    return 0;
+    return fb_slabs("color_apply", L, [&](int t0, unsigned n) {
+        hipLaunchKernelGGL(color_apply_kernel, dim3(nblk, n), dim3(COL_NTH), 0, st, frames, lut, group, t0, N, G, out);
+    });
 }

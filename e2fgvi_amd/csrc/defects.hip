@@ -20,13 +20,12 @@
 // 2 radius + 1 neighbours along the rows, then along the columns
 // (csrc/video.hip overlay_edges_kernel is the precedent); a wave counts its set pixels with a ballot and adds them once.  Integer
 // atomics: the counts are exact and the same in every run.
-#include "common.h"
+#include "frame_bytes.h"
 
 namespace {
 
 constexpr int DF_NTH = 256;
 constexpr int DF_PX = 4;              // pixels per thread of the candidate kernel
-constexpr int DF_JOBS_MAX = 65535;    // jobs per launch (the grid's y axis); more are launched in slabs
 constexpr int DF_TW = 64, DF_TH = 32; // the clean kernel's tile
 constexpr int DF_PER = DF_TH / (DF_NTH / 64);
 constexpr int DF_RMAX = 16;           // largest dilation radius the LDS tiles hold
@@ -41,7 +40,7 @@ constexpr int DF_BPP = E2_DEFECT_BPP;
 
 __device__ __forceinline__ int df_luma(const uint8_t* p) {
     if constexpr (DF_BPP == 1) return (int)p[0];
-    else return (77 * (int)p[0] + 150 * (int)p[1] + 29 * (int)p[2] + 128) >> 8;
+    else return fb_luma(p[0], p[1], p[2]);
 }
 
 // min / max of a neighbour's luma over the envelope of p's sample position; false: the position is outside (or the flow not finite)
@@ -188,6 +187,7 @@ defect_clean_kernel(const uint8_t* __restrict__ cand, const int* __restrict__ id
     if (lane == 0 && n) atomicAdd(counts + t, n);
 }
 
+// (the unit's own: its message names the jobs, and it takes frames of up to 2^31 - 256 pixels where fb_check_sizes stops at 2^26)
 int df_check_sizes(const char* who, int32_t n, int32_t L, int32_t H, int32_t W) {
     E2_REQUIRE(n >= 0 && L >= 0 && H >= 0 && W >= 0, E2FGVI_EINVAL, "%s: negative size (n = %d, L = %d, H = %d, W = %d)", who, n, L, H, W);
     E2_REQUIRE(n == 0 || L >= 3, E2FGVI_EINVAL, "%s: a centre frame needs both neighbours: L >= 3, got %d", who, L);
@@ -208,19 +208,11 @@ extern "C" int e2fgvi_defect_candidates(const uint8_t* frames, const float* fwd,
                "defect_candidates: fwd and bwd must be 8-byte aligned, ids 4-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const int wq = (W + DF_PX - 1) / DF_PX;
-    const dim3 blk(DF_NTH);
     const unsigned nblk = (unsigned)(((long long)H * wq + DF_NTH - 1) / DF_NTH);
-    for (int j0 = 0; j0 < n; j0 += DF_JOBS_MAX) {
-        const dim3 grid(nblk, (unsigned)(n - j0 < DF_JOBS_MAX ? n - j0 : DF_JOBS_MAX), 1);
-        if (slack == 0)
-            hipLaunchKernelGGL(defect_candidates_kernel<0>, grid, blk, 0, st, frames, fwd, bwd, ids + j0, L, H, W, wq, tau, cand);
-        else if (slack == 1)
-            hipLaunchKernelGGL(defect_candidates_kernel<1>, grid, blk, 0, st, frames, fwd, bwd, ids + j0, L, H, W, wq, tau, cand);
-        else
-            hipLaunchKernelGGL(defect_candidates_kernel<2>, grid, blk, 0, st, frames, fwd, bwd, ids + j0, L, H, W, wq, tau, cand);
-        E2_LAUNCH_CHECK("defect_candidates");
-    }
-    return 0;
+    auto kernel = slack == 0 ? defect_candidates_kernel<0> : slack == 1 ? defect_candidates_kernel<1> : defect_candidates_kernel<2>;
+    return fb_slabs("defect_candidates", n, [&](int j0, unsigned nj) {          // slabs of jobs: the centre frames ids[j0 ...]
+        hipLaunchKernelGGL(kernel, dim3(nblk, nj), dim3(DF_NTH), 0, st, frames, fwd, bwd, ids + j0, L, H, W, wq, tau, cand);
+    });
 }
 
 extern "C" int e2fgvi_defect_clean(const uint8_t* cand, const int32_t* ids, int32_t n, int32_t L, int32_t H, int32_t W, int32_t support,
@@ -236,10 +228,8 @@ extern "C" int e2fgvi_defect_clean(const uint8_t* cand, const int32_t* ids, int3
     hipError_t e = hipMemsetAsync(counts, 0, sizeof(int32_t) * (size_t)L, st);
     E2_REQUIRE(e == hipSuccess, (int)e, "defect_clean: hipMemsetAsync failed: %s", hipGetErrorString(e));
     const int ntx = (W + DF_TW - 1) / DF_TW, nty = (H + DF_TH - 1) / DF_TH;
-    for (int j0 = 0; j0 < n; j0 += DF_JOBS_MAX) {
-        const dim3 grid((unsigned)((long long)ntx * nty), (unsigned)(n - j0 < DF_JOBS_MAX ? n - j0 : DF_JOBS_MAX), 1);
-        hipLaunchKernelGGL(defect_clean_kernel, grid, dim3(DF_NTH), 0, st, cand, ids + j0, L, H, W, support, radius, ntx, out, counts);
-        E2_LAUNCH_CHECK("defect_clean");
-    }
-    return 0;
+    return fb_slabs("defect_clean", n, [&](int j0, unsigned nj) {
+        hipLaunchKernelGGL(defect_clean_kernel, dim3((unsigned)((long long)ntx * nty), nj), dim3(DF_NTH), 0, st, cand, ids + j0, L, H, W,
+                           support, radius, ntx, out, counts);
+    });
 }

@@ -20,7 +20,7 @@
 // (profiles/denoise.txt): a second workspace plane that held a pixel's R, G, B and luma as one word made a candidate
 // one load where it is two and the filter 9 % faster, but the luma pass twice as slow and the workspace five times as large;
 // it was taken out.
-#include "common.h"
+#include "frame_bytes.h"
 
 namespace {
 
@@ -29,7 +29,6 @@ constexpr int DN_TX = 64;                 // pixels per tile row: a wave
 constexpr int DN_TY = DN_NTH / DN_TX;     // rows per tile
 constexpr int DN_PAD = 4;                 // the ring of the luma plane: >= DN_SEARCH_MAX + 1, and a multiple of four
 constexpr int DN_SEARCH_MAX = 2;
-constexpr int DN_FRAMES_MAX = 65535;      // frames per launch (the grid's y axis); more are launched in slabs
 
 // bytes in a row of the luma plane: the frame, the ring, up to a dword, and one more dword so that a third aligned dword of a
 // seven-byte run stays in the row
@@ -49,7 +48,7 @@ denoise_luma_kernel(const uint8_t* __restrict__ frames, uint8_t* __restrict__ pl
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const uint8_t* p = src + 3LL * dn_clamp(c4 * 4 + k - DN_PAD, 0, W - 1);
-        v |= ((77u * p[0] + 150u * p[1] + 29u * p[2] + 128u) >> 8) << (8 * k);
+        v |= (unsigned)fb_luma(p[0], p[1], p[2]) << (8 * k);
     }
     reinterpret_cast<unsigned*>(plane + ((long long)t * (H + 2 * DN_PAD) + row) * (4LL * sq))[c4] = v;
 }
@@ -162,11 +161,6 @@ denoise_filter_kernel(const uint8_t* __restrict__ frames, const uint8_t* __restr
     o[2] = (uint8_t)dn_clamp(dn_div(acc[2] + half, wsum, rd), c2 - limit, c2 + limit);
 }
 
-bool dn_disjoint(const void* p, uint64_t pn, const void* q, uint64_t qn) {
-    const uint64_t a = (uint64_t)(uintptr_t)p, b = (uint64_t)(uintptr_t)q;
-    return a + pn <= b || b + qn <= a;
-}
-
 }  // namespace
 
 extern "C" int e2fgvi_denoise(const uint8_t* frames, const float* fwd, const float* bwd, const int32_t* scene, uint8_t* out,
@@ -181,7 +175,7 @@ extern "C" int e2fgvi_denoise(const uint8_t* frames, const float* fwd, const flo
     E2_REQUIRE(frames && scene && out, E2FGVI_EINVAL, "denoise: null pointer");
     E2_REQUIRE(((uintptr_t)scene & 3) == 0, E2FGVI_EINVAL, "denoise: scene must be 4-byte aligned");
     const uint64_t fb = 3ull * (uint64_t)H * (uint64_t)W * (uint64_t)L;
-    E2_REQUIRE(dn_disjoint(frames, fb, out, fb), E2FGVI_EINVAL, "denoise: out must not overlap frames (a pixel reads three frames)");
+    E2_REQUIRE(fb_disjoint(frames, fb, out, fb), E2FGVI_EINVAL, "denoise: out must not overlap frames (a pixel reads three frames)");
     const long long stride = dn_stride(W);
     const int64_t need = (int64_t)L * (H + 2 * DN_PAD) * stride;
     if (L >= 2) {                                       // a single frame has no neighbour: no flows and no luma are read
@@ -190,7 +184,7 @@ extern "C" int e2fgvi_denoise(const uint8_t* frames, const float* fwd, const flo
                    "denoise: fwd and bwd must be 8-byte aligned, work 4-byte aligned");
         E2_REQUIRE(work_bytes >= need, E2FGVI_EINVAL, "denoise: work must hold L (H + 8) ((W + 11) / 4 * 4 + 4) = %lld bytes, got %lld",
                    (long long)need, (long long)work_bytes);
-        E2_REQUIRE(dn_disjoint(work, (uint64_t)need, out, fb) && dn_disjoint(work, (uint64_t)need, frames, fb), E2FGVI_EINVAL,
+        E2_REQUIRE(fb_disjoint(work, (uint64_t)need, out, fb) && fb_disjoint(work, (uint64_t)need, frames, fb), E2FGVI_EINVAL,
                    "denoise: work must not overlap frames or out");
     }
     hipStream_t st = (hipStream_t)stream;
@@ -200,17 +194,13 @@ extern "C" int e2fgvi_denoise(const uint8_t* frames, const float* fwd, const flo
     const unsigned ntile = (unsigned)((int64_t)ntx * cdiv(H, DN_TY));                   // at most 2^31 / 4 + 2^31 / 64
     auto kernel = search == 0 ? denoise_filter_kernel<0> : search == 1 ? denoise_filter_kernel<1> : denoise_filter_kernel<2>;
     if (L >= 2) {
-        for (int t0 = 0; t0 < L; t0 += DN_FRAMES_MAX) {
-            const dim3 grid(nluma, (unsigned)(L - t0 < DN_FRAMES_MAX ? L - t0 : DN_FRAMES_MAX), 1);
-            hipLaunchKernelGGL(denoise_luma_kernel, grid, dim3(DN_NTH), 0, st, frames, work, t0, H, W, sq);
-            E2_LAUNCH_CHECK("denoise");
-        }
+        const int rc = fb_slabs("denoise", L, [&](int t0, unsigned n) {
+            hipLaunchKernelGGL(denoise_luma_kernel, dim3(nluma, n), dim3(DN_NTH), 0, st, frames, work, t0, H, W, sq);
+        });
+        if (rc) return rc;
     }
-    for (int t0 = 0; t0 < L; t0 += DN_FRAMES_MAX) {
-        const dim3 grid(ntile, (unsigned)(L - t0 < DN_FRAMES_MAX ? L - t0 : DN_FRAMES_MAX), 1);
-        hipLaunchKernelGGL(kernel, grid, dim3(DN_NTH), 0, st, frames, (const uint8_t*)work, fwd, bwd, scene, out, t0, L, H, W, ntx, m,
-                           max_change);
-        E2_LAUNCH_CHECK("denoise");
-    }
-    return 0;
+    return fb_slabs("denoise", L, [&](int t0, unsigned n) {
+        hipLaunchKernelGGL(kernel, dim3(ntile, n), dim3(DN_NTH), 0, st, frames, (const uint8_t*)work, fwd, bwd, scene, out, t0, L, H, W,
+                           ntx, m, max_change);
+    });
 }

@@ -24,12 +24,12 @@
 // groups of four pixels, loaded as in the histogram pass when both the frame and its output start on a dword.  The shift is looked
 // up once per pixel and added to its three bytes, clipped to [0, 255]; twelve bytes go out as three dwords (or byte by byte): each
 // output byte is written once, by the thread that read the input byte, so out == frames is in order.
-#include "flicker_common.h"          // the luma, the group, the scan, the nodes and the curves of one row: shared with flicker_local.hip
+#include "flicker_common.h"          // the scan, the nodes and the curves of one row: shared with flicker_local.hip
 
 namespace {
 
 constexpr int FL_HIT = 8;                 // groups per thread of the histogram kernel
-constexpr int FL_HPX = FL_NTH * FL_PX * FL_HIT;
+constexpr int FL_HPX = FL_NTH * FB_PX * FL_HIT;
 // A/B switches (build.build_variant("tag", "-DFL_COPIES=1")); profiles/flicker.txt has what they measured
 #ifndef FL_COPIES
 #define FL_COPIES 8
@@ -39,7 +39,7 @@ constexpr int FL_HPX = FL_NTH * FL_PX * FL_HIT;
 #endif
 constexpr int FL_HC = FL_COPIES;          // copies of the histogram in LDS: a power of two
 constexpr int FL_AIT = 4;                 // groups per thread of the apply kernel
-constexpr int FL_APX = FL_NTH * FL_PX * FL_AIT;
+constexpr int FL_APX = FL_NTH * FB_PX * FL_AIT;
 
 __global__ void __launch_bounds__(FL_NTH)
 flicker_hist_kernel(const uint8_t* __restrict__ frames, int t0, int N, int* __restrict__ hist) {
@@ -49,47 +49,42 @@ flicker_hist_kernel(const uint8_t* __restrict__ frames, int t0, int N, int* __re
     for (int i = tid; i < 256 * FL_HC; i += FL_NTH) s_h[i] = 0;
     __syncthreads();
     const uint8_t* fr = frames + (long long)t * N * 3;
-    const int p0 = (int)blockIdx.x * FL_HPX + tid * FL_PX;        // < 2^26 + 8192: blockIdx.x < ceil(N / FL_HPX)
+    const int p0 = (int)blockIdx.x * FL_HPX + tid * FB_PX;        // < 2^26 + 8192: blockIdx.x < ceil(N / FL_HPX)
     int* mine = s_h + (tid & (FL_HC - 1));
     // the same for every thread of the frame: a group is 12 bytes
     if (((uintptr_t)fr & 3) == 0) {
         unsigned w[FL_HIT][3];
 #pragma unroll
         for (int k = 0; k < FL_HIT; ++k) {
-            const int p = p0 + k * FL_NTH * FL_PX;
+            const int p = p0 + k * FL_NTH * FB_PX;
             w[k][0] = w[k][1] = w[k][2] = 0;
-            if (p + FL_PX <= N) {                                  // the twelve bytes lie in frame t
-                const unsigned* q = reinterpret_cast<const unsigned*>(fr + (long long)p * 3);
-                w[k][0] = q[0];
-                w[k][1] = q[1];
-                w[k][2] = q[2];
-            }
+            if (p + FB_PX <= N) fb_load_dwords(fr + (long long)p * 3, w[k]);       // the twelve bytes lie in frame t
         }
 #pragma unroll
         for (int k = 0; k < FL_HIT; ++k) {
-            const int p = p0 + k * FL_NTH * FL_PX;
-            if (p + FL_PX <= N) {
-                int y[FL_PX];
-                fl_luma4(w[k][0], w[k][1], w[k][2], y);
+            const int p = p0 + k * FL_NTH * FB_PX;
+            if (p + FB_PX <= N) {
+                int y[FB_PX];
+                fb_luma4_shifts(w[k], y);       // not fb_luma4: frame_bytes.h says why
                 if (FL_MERGE4 && y[0] == y[1] && y[1] == y[2] && y[2] == y[3]) {
-                    atomicAdd(mine + y[0] * FL_HC, FL_PX);
+                    atomicAdd(mine + y[0] * FL_HC, FB_PX);
                 } else {
 #pragma unroll
-                    for (int j = 0; j < FL_PX; ++j) atomicAdd(mine + y[j] * FL_HC, 1);
+                    for (int j = 0; j < FB_PX; ++j) atomicAdd(mine + y[j] * FL_HC, 1);
                 }
             } else {
                 for (int j = 0; p + j < N; ++j) {                  // the short group at the end of the frame
                     const uint8_t* q = fr + (long long)(p + j) * 3;
-                    atomicAdd(mine + fl_luma(q[0], q[1], q[2]) * FL_HC, 1);
+                    atomicAdd(mine + fb_luma(q[0], q[1], q[2]) * FL_HC, 1);
                 }
             }
         }
     } else {
         for (int k = 0; k < FL_HIT; ++k) {
-            const int p = p0 + k * FL_NTH * FL_PX;
-            for (int j = 0; j < FL_PX && p + j < N; ++j) {
+            const int p = p0 + k * FL_NTH * FB_PX;
+            for (int j = 0; j < FB_PX && p + j < N; ++j) {
                 const uint8_t* q = fr + (long long)(p + j) * 3;
-                atomicAdd(mine + fl_luma(q[0], q[1], q[2]) * FL_HC, 1);
+                atomicAdd(mine + fb_luma(q[0], q[1], q[2]) * FL_HC, 1);
             }
         }
     }
@@ -115,40 +110,35 @@ flicker_apply_kernel(const uint8_t* frames, const short* __restrict__ d, int t0,
     __syncthreads();
     const uint8_t* fr = frames + (long long)t * N * 3;
     uint8_t* fo = out + (long long)t * N * 3;
-    const int p0 = (int)blockIdx.x * FL_APX + tid * FL_PX;
+    const int p0 = (int)blockIdx.x * FL_APX + tid * FB_PX;
     const bool aligned = (((uintptr_t)fr | (uintptr_t)fo) & 3) == 0;       // the same for every thread of the frame
     unsigned w[FL_AIT][3];
     // frames and out may be the same buffer (no __restrict__): a thread reads the bytes of its groups before it writes any of them
     if (aligned) {
 #pragma unroll
         for (int k = 0; k < FL_AIT; ++k) {
-            const int p = p0 + k * FL_NTH * FL_PX;
+            const int p = p0 + k * FL_NTH * FB_PX;
             w[k][0] = w[k][1] = w[k][2] = 0;
-            if (p + FL_PX <= N) {                                  // the twelve bytes lie in frame t
-                const unsigned* q = reinterpret_cast<const unsigned*>(fr + (long long)p * 3);
-                w[k][0] = q[0];
-                w[k][1] = q[1];
-                w[k][2] = q[2];
-            }
+            if (p + FB_PX <= N) fb_load_dwords(fr + (long long)p * 3, w[k]);       // the twelve bytes lie in frame t
         }
     }
 #pragma unroll
     for (int k = 0; k < FL_AIT; ++k) {
-        const int p = p0 + k * FL_NTH * FL_PX;
-        if (aligned && p + FL_PX <= N) {
-            int y[FL_PX];
-            fl_luma4(w[k][0], w[k][1], w[k][2], y);
+        const int p = p0 + k * FL_NTH * FB_PX;
+        if (aligned && p + FB_PX <= N) {
+            int y[FB_PX];
+            fb_luma4_shifts(w[k], y);       // not fb_luma4: frame_bytes.h says why
             unsigned b[12];
 #pragma unroll
-            for (int i = 0; i < 12; ++i) b[i] = fl_byte((int)((w[k][i >> 2] >> (8 * (i & 3))) & 255u) + s_d[y[i / 3]]);
+            for (int i = 0; i < 12; ++i) b[i] = fb_byte(fb_get(w[k], i) + s_d[y[i / 3]]);
             unsigned* o = reinterpret_cast<unsigned*>(fo + (long long)p * 3);
 #pragma unroll
             for (int i = 0; i < 3; ++i) o[i] = b[4 * i] | (b[4 * i + 1] << 8) | (b[4 * i + 2] << 16) | (b[4 * i + 3] << 24);
         } else {
-            for (int j = 0; j < FL_PX && p + j < N; ++j) {
+            for (int j = 0; j < FB_PX && p + j < N; ++j) {
                 const uint8_t* q = fr + (long long)(p + j) * 3;
                 const int r = q[0], g = q[1], bl = q[2];
-                const int s = s_d[fl_luma(r, g, bl)];
+                const int s = s_d[fb_luma(r, g, bl)];
                 uint8_t* o = fo + (long long)(p + j) * 3;
                 o[0] = (uint8_t)min(max(r + s, 0), 255);
                 o[1] = (uint8_t)min(max(g + s, 0), 255);
@@ -158,16 +148,10 @@ flicker_apply_kernel(const uint8_t* frames, const short* __restrict__ d, int t0,
     }
 }
 
-int fl_check_sizes(const char* who, int32_t L, int32_t H, int32_t W) {
-    E2_REQUIRE(L >= 0 && H >= 0 && W >= 0, E2FGVI_EINVAL, "%s: negative size (L = %d, H = %d, W = %d)", who, L, H, W);
-    E2_REQUIRE((int64_t)H * W <= FL_N_MAX, E2FGVI_EINVAL, "%s: needs H * W <= 2^26, got %d x %d", who, H, W);
-    return 0;
-}
-
 }  // namespace
 
 extern "C" int e2fgvi_flicker_hist(const uint8_t* frames, int32_t* hist, int32_t L, int32_t H, int32_t W, void* stream) {
-    if (int rc = fl_check_sizes("flicker_hist", L, H, W)) return rc;
+    if (int rc = fb_check_sizes("flicker_hist", L, H, W)) return rc;
     const int N = H * W;
     if (L == 0 || N == 0) return 0;                                // no pixel: no launch, and the pointers are not looked at
     E2_REQUIRE(frames && hist, E2FGVI_EINVAL, "flicker_hist: null pointer");
@@ -176,18 +160,15 @@ extern "C" int e2fgvi_flicker_hist(const uint8_t* frames, int32_t* hist, int32_t
     hipError_t e = hipMemsetAsync(hist, 0, sizeof(int32_t) * 256 * (size_t)L, st);
     E2_REQUIRE(e == hipSuccess, (int)e, "flicker_hist: hipMemsetAsync failed: %s", hipGetErrorString(e));
     const unsigned nblk = (unsigned)((N + FL_HPX - 1) / FL_HPX);
-    for (int t0 = 0; t0 < L; t0 += FL_FRAMES_MAX) {
-        const dim3 grid(nblk, (unsigned)(L - t0 < FL_FRAMES_MAX ? L - t0 : FL_FRAMES_MAX), 1);
-        hipLaunchKernelGGL(flicker_hist_kernel, grid, dim3(FL_NTH), 0, st, frames, t0, N, hist);
-        E2_LAUNCH_CHECK("flicker_hist");
-    }
-    return 0;
+    return fb_slabs("flicker_hist", L, [&](int t0, unsigned n) {
+        hipLaunchKernelGGL(flicker_hist_kernel, dim3(nblk, n), dim3(FL_NTH), 0, st, frames, t0, N, hist);
+    });
 }
 
 extern "C" int e2fgvi_flicker_curves(const int32_t* hist, const int32_t* scene, int32_t* Q, int16_t* d, int32_t L, int32_t N,
                                      int32_t span, int32_t max_shift, void* stream) {
     E2_REQUIRE(L >= 0 && N >= 0, E2FGVI_EINVAL, "flicker_curves: negative size (L = %d, N = %d)", L, N);
-    E2_REQUIRE(N <= FL_N_MAX, E2FGVI_EINVAL, "flicker_curves: needs N <= 2^26, got %d", N);
+    E2_REQUIRE(N <= FB_N_MAX, E2FGVI_EINVAL, "flicker_curves: needs N <= 2^26, got %d", N);
     E2_REQUIRE(span >= 0 && span <= FL_SPAN_MAX, E2FGVI_EINVAL, "flicker_curves: span must be in [0, %d], got %d", FL_SPAN_MAX, span);
     E2_REQUIRE(max_shift >= 1 && max_shift <= FL_SHIFT_MAX, E2FGVI_EINVAL, "flicker_curves: max_shift must be in [1, %d], got %d",
                FL_SHIFT_MAX, max_shift);
@@ -203,20 +184,16 @@ extern "C" int e2fgvi_flicker_curves(const int32_t* hist, const int32_t* scene, 
 
 extern "C" int e2fgvi_flicker_apply(const uint8_t* frames, const int16_t* d, uint8_t* out, int32_t L, int32_t H, int32_t W,
                                     void* stream) {
-    if (int rc = fl_check_sizes("flicker_apply", L, H, W)) return rc;
+    if (int rc = fb_check_sizes("flicker_apply", L, H, W)) return rc;
     const int N = H * W;
     if (L == 0 || N == 0) return 0;                                // no pixel: no launch, and the pointers are not looked at
     E2_REQUIRE(frames && d && out, E2FGVI_EINVAL, "flicker_apply: null pointer");
     E2_REQUIRE(((uintptr_t)d & 1) == 0, E2FGVI_EINVAL, "flicker_apply: d must be 2-byte aligned");
-    const uint64_t bytes = (uint64_t)L * (uint64_t)N * 3, a = (uint64_t)(uintptr_t)frames, b = (uint64_t)(uintptr_t)out;
-    E2_REQUIRE(a == b || a + bytes <= b || b + bytes <= a, E2FGVI_EINVAL,
+    E2_REQUIRE(fb_same_or_disjoint(frames, out, (uint64_t)L * (uint64_t)N * 3), E2FGVI_EINVAL,
                "flicker_apply: out must be frames itself or not overlap it");
     hipStream_t st = (hipStream_t)stream;
     const unsigned nblk = (unsigned)((N + FL_APX - 1) / FL_APX);
-    for (int t0 = 0; t0 < L; t0 += FL_FRAMES_MAX) {
-        const dim3 grid(nblk, (unsigned)(L - t0 < FL_FRAMES_MAX ? L - t0 : FL_FRAMES_MAX), 1);
-        hipLaunchKernelGGL(flicker_apply_kernel, grid, dim3(FL_NTH), 0, st, frames, d, t0, N, out);
-        E2_LAUNCH_CHECK("flicker_apply");
-    }
-    return 0;
+    return fb_slabs("flicker_apply", L, [&](int t0, unsigned n) {
+        hipLaunchKernelGGL(flicker_apply_kernel, dim3(nblk, n), dim3(FL_NTH), 0, st, frames, d, t0, N, out);
+    });
 }

@@ -1,27 +1,14 @@
-// What the deflicker (flicker.hip) and the local deflicker (flicker_local.hip) share: the luma, the group of four pixels, the clip
-// to a byte, and the curves of one histogram row -- scan, nodes by bisection, the window's mean, the shift per level.  Device code
-// only, internal linkage: neither object exports anything from here.  include/e2fgvi_hip.h has the definition.
+// What the deflicker (flicker.hip) and the local deflicker (flicker_local.hip) share beyond frame_bytes.h: the curves of one
+// histogram row -- scan, nodes by bisection, the window's mean, the shift per level.  Device code only, internal linkage: neither
+// object exports anything from here.  include/e2fgvi_hip.h has the definition.
 #pragma once
-#include "common.h"
+#include "frame_bytes.h"
 
 namespace {
 
 constexpr int FL_NTH = 256;
-constexpr int FL_PX = 4;                  // pixels per group
-constexpr int FL_FRAMES_MAX = 65535;      // frames per launch (the grid's y axis); more are launched in slabs
 constexpr int FL_K = 32;                  // quantile nodes per frame
 constexpr int FL_SPAN_MAX = 8, FL_SHIFT_MAX = 64;
-constexpr long long FL_N_MAX = 1LL << 26;
-
-__device__ __forceinline__ int fl_luma(unsigned r, unsigned g, unsigned b) { return (int)((77u * r + 150u * g + 29u * b + 128u) >> 8); }
-
-// the four lumas of a group of four pixels held in three dwords
-__device__ __forceinline__ void fl_luma4(unsigned w0, unsigned w1, unsigned w2, int (&y)[FL_PX]) {
-    y[0] = fl_luma(w0 & 255u, (w0 >> 8) & 255u, (w0 >> 16) & 255u);
-    y[1] = fl_luma(w0 >> 24, w1 & 255u, (w1 >> 8) & 255u);
-    y[2] = fl_luma((w1 >> 16) & 255u, w1 >> 24, w2 & 255u);
-    y[3] = fl_luma((w2 >> 8) & 255u, (w2 >> 16) & 255u, w2 >> 24);
-}
 
 // the inclusive scan of one value per thread over the workgroup's 256 threads; s_w holds the four wave totals.  Two barriers; the
 // caller puts one more between two calls (s_w is read here after the first and written again in the next call).
@@ -105,14 +92,6 @@ __device__ __forceinline__ void fl_curves_row(const int* __restrict__ hist, cons
     const int k0 = (int)phi >> 8, f = (int)phi & 255, k1 = min(k0 + 1, FL_K - 1);
     const int d16 = (s_s[k0] * (256 - f) + s_s[k1] * f + 128) >> 8;
     d[mine * 256 + y] = (short)(WHOLE ? (d16 + 8) >> 4 : d16);
-}
-
-// hipcc turns two clipped values packed side by side into v_ashr_pk_u8_i32, whose neighbouring bytes came out wrong on the chip
-// (csrc/yuv.hip store_bytes has the account, build.verify_no_pk_u8 the check): the empty asm keeps the clip a v_med3_i32
-__device__ __forceinline__ unsigned fl_byte(int v) {
-    v = min(max(v, 0), 255);
-    asm volatile("" : "+v"(v));
-    return (unsigned)v;
 }
 
 }  // namespace

@@ -35,10 +35,10 @@ namespace {
 
 constexpr int FLL_G_MAX = 8;               // cells per axis
 constexpr int FLL_HIT = 8;                 // groups per thread of the histogram kernel
-constexpr int FLL_HPX = FL_NTH * FL_PX * FLL_HIT;
+constexpr int FLL_HPX = FL_NTH * FB_PX * FLL_HIT;
 constexpr int FLL_HWORDS = 8192;           // words of LDS of the histogram kernel: gx cells x 256 bins x C copies
 constexpr int FLL_AIT = 8;                 // groups per thread of the apply kernel
-constexpr int FLL_APX = FL_NTH * FL_PX * FLL_AIT;
+constexpr int FLL_APX = FL_NTH * FB_PX * FLL_AIT;
 constexpr int FLL_NONE = 0x7fffffff;       // a column bound that no column reaches
 
 struct FllRows { int at[FLL_G_MAX + 1]; };     // run i is the rows [at[i], at[i + 1])
@@ -75,65 +75,60 @@ flicker_local_hist_kernel(const uint8_t* __restrict__ frames, int t0, int N, int
     const int tid = (int)threadIdx.x;
     int lo, hi, chunk;
     const int i = fll_run(rows, nchunk, W, lo, hi, chunk);
-    const int first = (lo & ~(FL_PX - 1)) + chunk * FLL_HPX;      // < 2^26 + 8192
+    const int first = (lo & ~(FB_PX - 1)) + chunk * FLL_HPX;      // < 2^26 + 8192
     if (first >= hi) return;                                       // the same for the whole workgroup
     const int shift = gx <= 4 ? 3 : 2, copies = 1 << shift;        // gx 256 copies <= FLL_HWORDS
     for (int k = tid; k < gx * 256 * copies; k += FL_NTH) s_h[k] = 0;
     __syncthreads();
     const uint8_t* fr = frames + (long long)t * N * 3;
-    const int p0 = first + tid * FL_PX;
+    const int p0 = first + tid * FB_PX;
     int* mine = s_h + (tid & (copies - 1));
-    const int step = (FL_NTH * FL_PX) % W;
+    const int step = (FL_NTH * FB_PX) % W;
     int x = p0 % W;
     // one pixel, which may lie outside the run
     auto one = [&](int p, int xx) {
         if (p < lo || p >= hi) return;
         if (xx >= W) xx = p % W;
         const uint8_t* q = fr + (long long)p * 3;
-        atomicAdd(mine + ((fll_cell(cols, xx) * 256 + fl_luma(q[0], q[1], q[2])) << shift), 1);
+        atomicAdd(mine + ((fll_cell(cols, xx) * 256 + fb_luma(q[0], q[1], q[2])) << shift), 1);
     };
     if (((uintptr_t)fr & 3) == 0) {                                // the same for every thread of the frame: a group is 12 bytes
         unsigned w[FLL_HIT][3];
 #pragma unroll
         for (int k = 0; k < FLL_HIT; ++k) {
-            const int p = p0 + k * FL_NTH * FL_PX;
+            const int p = p0 + k * FL_NTH * FB_PX;
             w[k][0] = w[k][1] = w[k][2] = 0;
-            if (p >= lo && p + FL_PX <= hi) {                      // the twelve bytes lie in the run
-                const unsigned* q = reinterpret_cast<const unsigned*>(fr + (long long)p * 3);
-                w[k][0] = q[0];
-                w[k][1] = q[1];
-                w[k][2] = q[2];
-            }
+            if (p >= lo && p + FB_PX <= hi) fb_load_dwords(fr + (long long)p * 3, w[k]);       // the twelve bytes lie in the run
         }
 #pragma unroll
         for (int k = 0; k < FLL_HIT; ++k) {
-            const int p = p0 + k * FL_NTH * FL_PX;
-            if (p >= lo && p + FL_PX <= hi) {
-                int y[FL_PX];
-                fl_luma4(w[k][0], w[k][1], w[k][2], y);
-                if (x + FL_PX <= W) {                              // the group lies in one row
-                    const int ja = fll_cell(cols, x), jb = fll_cell(cols, x + FL_PX - 1);
+            const int p = p0 + k * FL_NTH * FB_PX;
+            if (p >= lo && p + FB_PX <= hi) {
+                int y[FB_PX];
+                fb_luma4(w[k], y);
+                if (x + FB_PX <= W) {                              // the group lies in one row
+                    const int ja = fll_cell(cols, x), jb = fll_cell(cols, x + FB_PX - 1);
                     if (ja == jb && y[0] == y[1] && y[1] == y[2] && y[2] == y[3]) {
-                        atomicAdd(mine + ((ja * 256 + y[0]) << shift), FL_PX);
+                        atomicAdd(mine + ((ja * 256 + y[0]) << shift), FB_PX);
                     } else {
 #pragma unroll
-                        for (int j = 0; j < FL_PX; ++j)
+                        for (int j = 0; j < FB_PX; ++j)
                             atomicAdd(mine + (((ja == jb ? ja : fll_cell(cols, x + j)) * 256 + y[j]) << shift), 1);
                     }
                 } else {
 #pragma unroll
-                    for (int j = 0; j < FL_PX; ++j) atomicAdd(mine + ((fll_cell(cols, (p + j) % W) * 256 + y[j]) << shift), 1);
+                    for (int j = 0; j < FB_PX; ++j) atomicAdd(mine + ((fll_cell(cols, (p + j) % W) * 256 + y[j]) << shift), 1);
                 }
             } else {
-                for (int j = 0; j < FL_PX; ++j) one(p + j, x + j);
+                for (int j = 0; j < FB_PX; ++j) one(p + j, x + j);
             }
             x += step;
             x -= x >= W ? W : 0;
         }
     } else {
         for (int k = 0; k < FLL_HIT; ++k) {
-            const int p = p0 + k * FL_NTH * FL_PX;
-            for (int j = 0; j < FL_PX; ++j) one(p + j, x + j);
+            const int p = p0 + k * FL_NTH * FB_PX;
+            for (int j = 0; j < FB_PX; ++j) one(p + j, x + j);
             x += step;
             x -= x >= W ? W : 0;
         }
@@ -181,7 +176,7 @@ flicker_local_apply_kernel(const uint8_t* frames, const short* __restrict__ d16,
     const int tid = (int)threadIdx.x;
     int lo, hi, chunk;
     const int i0 = fll_run(bands, nchunk, W, lo, hi, chunk), i1 = min(i0 + 1, gy - 1);
-    const int first = (lo & ~(FL_PX - 1)) + chunk * FLL_APX;
+    const int first = (lo & ~(FB_PX - 1)) + chunk * FLL_APX;
     if (first >= hi) return;                                       // the same for the whole workgroup
     for (int j = 0; j < gx; ++j) {
         const unsigned a = (unsigned short)d16[(((long long)t * gy + i0) * gx + j) * 256 + tid];
@@ -191,7 +186,7 @@ flicker_local_apply_kernel(const uint8_t* frames, const short* __restrict__ d16,
     __syncthreads();
     const uint8_t* fr = frames + (long long)t * N * 3;
     uint8_t* fo = out + (long long)t * N * 3;
-    const int p0 = first + tid * FL_PX;
+    const int p0 = first + tid * FB_PX;
     const bool aligned = (((uintptr_t)fr | (uintptr_t)fo) & 3) == 0;       // the same for every thread of the frame
     const int cx = 128 * gx, cy = 128 * gy;
     const int dq = (2 * cx) / W, dr = (2 * cx) - dq * W;           // what one column further adds to u's quotient and rest
@@ -200,34 +195,29 @@ flicker_local_apply_kernel(const uint8_t* frames, const short* __restrict__ d16,
     if (aligned) {
 #pragma unroll
         for (int k = 0; k < FLL_AIT; ++k) {
-            const int p = p0 + k * FL_NTH * FL_PX;
+            const int p = p0 + k * FL_NTH * FB_PX;
             w[k][0] = w[k][1] = w[k][2] = 0;
-            if (p >= lo && p + FL_PX <= hi) {                      // the twelve bytes lie in the band
-                const unsigned* q = reinterpret_cast<const unsigned*>(fr + (long long)p * 3);
-                w[k][0] = q[0];
-                w[k][1] = q[1];
-                w[k][2] = q[2];
-            }
+            if (p >= lo && p + FB_PX <= hi) fb_load_dwords(fr + (long long)p * 3, w[k]);       // the twelve bytes lie in the band
         }
     }
 #pragma unroll
     for (int k = 0; k < FLL_AIT; ++k) {
-        const int p = p0 + k * FL_NTH * FL_PX;
-        if (p >= hi || p + FL_PX <= lo) continue;
+        const int p = p0 + k * FL_NTH * FB_PX;
+        if (p >= hi || p + FB_PX <= lo) continue;
         // the row and the column of the group's first pixel and their positions; fy is taken inside band i0
         int r = p / W, x = p - r * W, qx, rx, qy, ry;
         fll_divide(x, cx, W, qx, rx);
         fll_divide(min(r, H - 1), cy, H, qy, ry);
         int fy = fll_pos(qy, gy) - 256 * i0;
-        const bool whole = aligned && p >= lo && p + FL_PX <= hi;
-        int y[FL_PX], s[FL_PX];
-        if (whole) fl_luma4(w[k][0], w[k][1], w[k][2], y);
+        const bool whole = aligned && p >= lo && p + FB_PX <= hi;
+        int y[FB_PX], s[FB_PX];
+        if (whole) fb_luma4(w[k], y);
 #pragma unroll
-        for (int j = 0; j < FL_PX; ++j) {
+        for (int j = 0; j < FB_PX; ++j) {
             const bool in = p + j >= lo && p + j < hi;
             if (!whole && in) {
                 const uint8_t* q = fr + (long long)(p + j) * 3;
-                y[j] = fl_luma(q[0], q[1], q[2]);
+                y[j] = fb_luma(q[0], q[1], q[2]);
             }
             if (whole || in) {
                 const int u = fll_pos(qx, gx), j0 = u >> 8, fx = u & 255, j1 = min(j0 + 1, gx - 1);
@@ -256,13 +246,13 @@ flicker_local_apply_kernel(const uint8_t* frames, const short* __restrict__ d16,
         if (whole) {
             unsigned b[12];
 #pragma unroll
-            for (int m = 0; m < 12; ++m) b[m] = fl_byte((int)((w[k][m >> 2] >> (8 * (m & 3))) & 255u) + s[m / 3]);
+            for (int m = 0; m < 12; ++m) b[m] = fb_byte(fb_get(w[k], m) + s[m / 3]);
             unsigned* o = reinterpret_cast<unsigned*>(fo + (long long)p * 3);
 #pragma unroll
             for (int m = 0; m < 3; ++m) o[m] = b[4 * m] | (b[4 * m + 1] << 8) | (b[4 * m + 2] << 16) | (b[4 * m + 3] << 24);
         } else {
 #pragma unroll
-            for (int j = 0; j < FL_PX; ++j) {
+            for (int j = 0; j < FB_PX; ++j) {
                 if (p + j < lo || p + j >= hi) continue;
                 const uint8_t* q = fr + (long long)(p + j) * 3;
                 const int rr = q[0], g = q[1], bl = q[2];
@@ -287,8 +277,7 @@ int fll_first(int n, int g, long long want) {
 }
 
 int fll_check(const char* who, int32_t L, int32_t H, int32_t W, int32_t gy, int32_t gx) {
-    E2_REQUIRE(L >= 0 && H >= 0 && W >= 0, E2FGVI_EINVAL, "%s: negative size (L = %d, H = %d, W = %d)", who, L, H, W);
-    E2_REQUIRE((int64_t)H * W <= FL_N_MAX, E2FGVI_EINVAL, "%s: needs H * W <= 2^26, got %d x %d", who, H, W);
+    if (int rc = fb_check_sizes(who, L, H, W)) return rc;
     E2_REQUIRE(gy >= 1 && gy <= FLL_G_MAX && gx >= 1 && gx <= FLL_G_MAX, E2FGVI_EINVAL, "%s: gy and gx must be in [1, %d], got %d x %d",
                who, FLL_G_MAX, gy, gx);
     return 0;
@@ -304,7 +293,7 @@ int fll_check_cells(const char* who, int32_t H, int32_t W, int32_t gy, int32_t g
 unsigned fll_chunks(const FllRows& rows, int g, int W, int piece) {
     long long most = 0;
     for (int i = 0; i < g; ++i) most = most > rows.at[i + 1] - rows.at[i] ? most : rows.at[i + 1] - rows.at[i];
-    return (unsigned)((most * W + (FL_PX - 1) + piece - 1) / piece);
+    return (unsigned)((most * W + (FB_PX - 1) + piece - 1) / piece);
 }
 
 }  // namespace
@@ -325,12 +314,10 @@ extern "C" int e2fgvi_flicker_local_hist(const uint8_t* frames, int32_t* hist, i
     for (int i = 0; i <= FLL_G_MAX; ++i) rows.at[i] = i <= gy ? (int)(((long long)i * H) / gy) : H;
     for (int j = 0; j < FLL_G_MAX - 1; ++j) cols.at[j] = j + 1 < gx ? (int)(((long long)(j + 1) * W) / gx) : FLL_NONE;
     const unsigned nchunk = fll_chunks(rows, gy, W, FLL_HPX);
-    for (int t0 = 0; t0 < L; t0 += FL_FRAMES_MAX) {
-        const dim3 grid(nchunk * (unsigned)gy, (unsigned)(L - t0 < FL_FRAMES_MAX ? L - t0 : FL_FRAMES_MAX), 1);
-        hipLaunchKernelGGL(flicker_local_hist_kernel, grid, dim3(FL_NTH), 0, st, frames, t0, N, W, gy, gx, (int)nchunk, rows, cols, hist);
-        E2_LAUNCH_CHECK("flicker_local_hist");
-    }
-    return 0;
+    return fb_slabs("flicker_local_hist", L, [&](int t0, unsigned n) {
+        hipLaunchKernelGGL(flicker_local_hist_kernel, dim3(nchunk * (unsigned)gy, n), dim3(FL_NTH), 0, st, frames, t0, N, W, gy, gx,
+                           (int)nchunk, rows, cols, hist);
+    });
 }
 
 extern "C" int e2fgvi_flicker_local_curves(const int32_t* hist, const int32_t* scene, int32_t* Q, int16_t* d16, int32_t L, int32_t H,
@@ -361,8 +348,7 @@ extern "C" int e2fgvi_flicker_local_apply(const uint8_t* frames, const int16_t* 
     if (int rc = fll_check_cells("flicker_local_apply", H, W, gy, gx)) return rc;
     E2_REQUIRE(frames && d16 && out, E2FGVI_EINVAL, "flicker_local_apply: null pointer");
     E2_REQUIRE(((uintptr_t)d16 & 1) == 0, E2FGVI_EINVAL, "flicker_local_apply: d16 must be 2-byte aligned");
-    const uint64_t bytes = (uint64_t)L * (uint64_t)N * 3, a = (uint64_t)(uintptr_t)frames, b = (uint64_t)(uintptr_t)out;
-    E2_REQUIRE(a == b || a + bytes <= b || b + bytes <= a, E2FGVI_EINVAL,
+    E2_REQUIRE(fb_same_or_disjoint(frames, out, (uint64_t)L * (uint64_t)N * 3), E2FGVI_EINVAL,
                "flicker_local_apply: out must be frames itself or not overlap it");
     // band b: the rows whose position v lies in [256 b, 256 (b + 1)), the last band to the end
     FllRows bands;
@@ -370,10 +356,8 @@ extern "C" int e2fgvi_flicker_local_apply(const uint8_t* frames, const int16_t* 
     for (int i = 1; i <= FLL_G_MAX; ++i) bands.at[i] = i < gy ? fll_first(H, gy, 256LL * i + 128) : H;
     hipStream_t st = (hipStream_t)stream;
     const unsigned nchunk = fll_chunks(bands, gy, W, FLL_APX);
-    for (int t0 = 0; t0 < L; t0 += FL_FRAMES_MAX) {
-        const dim3 grid(nchunk * (unsigned)gy, (unsigned)(L - t0 < FL_FRAMES_MAX ? L - t0 : FL_FRAMES_MAX), 1);
-        hipLaunchKernelGGL(flicker_local_apply_kernel, grid, dim3(FL_NTH), 0, st, frames, d16, t0, N, H, W, gy, gx, (int)nchunk, bands, out);
-        E2_LAUNCH_CHECK("flicker_local_apply");
-    }
-    return 0;
+    return fb_slabs("flicker_local_apply", L, [&](int t0, unsigned n) {
+        hipLaunchKernelGGL(flicker_local_apply_kernel, dim3(nchunk * (unsigned)gy, n), dim3(FL_NTH), 0, st, frames, d16, t0, N, H, W, gy,
+                           gx, (int)nchunk, bands, out);
+    });
 }

@@ -18,16 +18,17 @@
 //   out = clamp(p + ((n lut[scene_of[t]][Y(p)][c] + 32768) >> 16), 0, 255)    (n lut + 32768 fits int32: 510 (2^22 - 1) + 2^15 < 2^31)
 // and every other byte is copied.  The thread reads its twelve bytes before it writes them and touches no other pixel: in place
 // (out == filled) is allowed.  A frame whose scene_of[t] is outside [0, n_scenes) is copied.
-#include "common.h"
+#include "frame_bytes.h"
 
 namespace {
 
 constexpr int GR_NTH = 256;
-constexpr int GR_PX = 4;                 // pixels per thread, both kernels
+constexpr int GR_PX = FB_PX;             // pixels per thread, both kernels
 constexpr int GR_GROUP = GR_NTH / 16;    // blocks per workgroup of the blocks kernel, side by side
-constexpr int GR_FRAMES_MAX = 65535;     // frames per launch (the grid's y axis); more are launched in slabs
 constexpr int GR_SCALE_MAX = (1 << 22) - 1;
 
+// fb_luma in signed arithmetic: with the unsigned form hipcc indexes the apply kernel's table another way (785 instructions for 788),
+// a change of generated code that nobody has timed
 __device__ __forceinline__ int gr_luma(int r, int g, int b) { return (77 * r + 150 * g + 29 * b + 128) >> 8; }
 
 __device__ __forceinline__ unsigned gr_mix(unsigned x) {
@@ -161,6 +162,7 @@ grain_apply_kernel(const uint8_t* filled, const uint8_t* __restrict__ where, con
         if (k < nx * 3) O[k] = (uint8_t)v[k];
 }
 
+// (the unit's own: it takes frames of up to 2^31 - 256 pixels where fb_check_sizes stops at 2^26)
 int gr_check_sizes(const char* who, int32_t L, int32_t H, int32_t W) {
     E2_REQUIRE(L >= 0 && H >= 0 && W >= 0, E2FGVI_EINVAL, "%s: negative size (L = %d, H = %d, W = %d)", who, L, H, W);
     E2_REQUIRE((int64_t)H * W < 2147483647LL - 256, E2FGVI_EINVAL, "%s: needs H * W < 2^31 - 256, got %d x %d", who, H, W);
@@ -178,12 +180,10 @@ extern "C" int e2fgvi_grain_blocks(const uint8_t* frames, const uint8_t* hole, i
     E2_REQUIRE(((uintptr_t)energy & 3) == 0, E2FGVI_EINVAL, "grain_blocks: energy must be 4-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const int ngx = (Wb + GR_GROUP - 1) / GR_GROUP;
-    for (int t0 = 0; t0 < L; t0 += GR_FRAMES_MAX) {
-        const dim3 grid((unsigned)((long long)ngx * Hb), (unsigned)(L - t0 < GR_FRAMES_MAX ? L - t0 : GR_FRAMES_MAX), 1);
-        hipLaunchKernelGGL(grain_blocks_kernel, grid, dim3(GR_NTH), 0, st, frames, hole, t0, H, W, Hb, Wb, ngx, energy, band);
-        E2_LAUNCH_CHECK("grain_blocks");
-    }
-    return 0;
+    return fb_slabs("grain_blocks", L, [&](int t0, unsigned n) {
+        hipLaunchKernelGGL(grain_blocks_kernel, dim3((unsigned)((long long)ngx * Hb), n), dim3(GR_NTH), 0, st, frames, hole, t0, H, W, Hb,
+                           Wb, ngx, energy, band);
+    });
 }
 
 extern "C" int e2fgvi_grain_apply(const uint8_t* filled, const uint8_t* where, const int32_t* lut, const int32_t* scene_of,
@@ -197,11 +197,8 @@ extern "C" int e2fgvi_grain_apply(const uint8_t* filled, const uint8_t* where, c
     hipStream_t st = (hipStream_t)stream;
     const int wq = (W + GR_PX - 1) / GR_PX;
     const unsigned nblk = (unsigned)(((long long)H * wq + GR_NTH - 1) / GR_NTH);
-    for (int t0 = 0; t0 < L; t0 += GR_FRAMES_MAX) {
-        const dim3 grid(nblk, (unsigned)(L - t0 < GR_FRAMES_MAX ? L - t0 : GR_FRAMES_MAX), 1);
-        hipLaunchKernelGGL(grain_apply_kernel, grid, dim3(GR_NTH), 0, st, filled, where, lut, scene_of, n_scenes, (unsigned)seed, t0, H,
-                           W, wq, out);
-        E2_LAUNCH_CHECK("grain_apply");
-    }
-    return 0;
+    return fb_slabs("grain_apply", L, [&](int t0, unsigned n) {
+        hipLaunchKernelGGL(grain_apply_kernel, dim3(nblk, n), dim3(GR_NTH), 0, st, filled, where, lut, scene_of, n_scenes, (unsigned)seed,
+                           t0, H, W, wq, out);
+    });
 }

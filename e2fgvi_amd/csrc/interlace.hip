@@ -31,75 +31,23 @@
 // first and last luma rows every thread leaves in LDS.  So every frame byte is read at most twice: once as frame t and once as
 // frame t + 1.  The sums are 64-bit per thread, added over the wave with shuffles, over the workgroup in LDS and into D with one
 // integer atomic per parity (the entry clears D on the stream first): exact, the same in every run.
-#include "common.h"
+#include "frame_bytes.h"
 
 namespace {
 
 constexpr int IL_NTH = 256;
-constexpr int IL_PX = 4;                  // pixels per group
+constexpr int IL_PX = FB_PX;              // pixels per group
 constexpr int IL_TX = 64;                 // groups per tile row: a wave
 constexpr int IL_TY = IL_NTH / IL_TX;     // threads above each other in a tile
 constexpr int IL_R = 4;                   // rows per thread of the fields kernel: a tile is IL_TY * IL_R = 16 rows
 constexpr int IL_WR = IL_R + 4;           // the rows a thread reads of each frame: two above and two below its own
 constexpr int IL_SC = 16;                 // groups of columns per workgroup of the scores kernel
 constexpr int IL_SR = IL_NTH / IL_SC;     // runs of rows per workgroup of the scores kernel
-constexpr int IL_FRAMES_MAX = 65535;      // frames per launch (the grid's y axis); more are launched in slabs
-constexpr long long IL_N_MAX = 1LL << 26;
-
-__device__ __forceinline__ int il_luma(unsigned r, unsigned g, unsigned b) { return (int)((77u * r + 150u * g + 29u * b + 128u) >> 8); }
-
-// the n <= 4 pixels at p as three words (the bytes behind the n-th pixel are 0): dwords when the group is whole and on a dword
-__device__ __forceinline__ void il_load(const uint8_t* p, int n, unsigned (&w)[3]) {
-    if (n == IL_PX && ((uintptr_t)p & 3) == 0) {
-        const unsigned* q = reinterpret_cast<const unsigned*>(p);
-        w[0] = q[0];
-        w[1] = q[1];
-        w[2] = q[2];
-    } else {
-        w[0] = w[1] = w[2] = 0;
-#pragma unroll
-        for (int i = 0; i < 3 * IL_PX; ++i)
-            if (i < 3 * n) w[i >> 2] |= (unsigned)p[i] << (8 * (i & 3));
-    }
-}
-
-__device__ __forceinline__ void il_store(uint8_t* p, int n, const unsigned (&w)[3]) {
-    if (n == IL_PX && ((uintptr_t)p & 3) == 0) {
-        unsigned* q = reinterpret_cast<unsigned*>(p);
-        q[0] = w[0];
-        q[1] = w[1];
-        q[2] = w[2];
-    } else {
-#pragma unroll
-        for (int i = 0; i < 3 * IL_PX; ++i)
-            if (i < 3 * n) p[i] = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
-    }
-}
-
-// the luma of the four pixels of a group: a pixel's three bytes are moved to the bottom (or left at the top) of a word and
-// multiplied by the three weights in one v_dot4_u32_u8, the fourth weight being 0: 10 instructions where shifts and masks take 32
-__device__ __forceinline__ void il_luma4(const unsigned (&w)[3], int (&y)[IL_PX]) {
-    constexpr unsigned K = 77u | (150u << 8) | (29u << 16);
-    y[0] = (int)(__builtin_amdgcn_udot4(w[0], K, 128u, false) >> 8);
-    y[1] = (int)(__builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(w[1], w[0], 3), K, 128u, false) >> 8);
-    y[2] = (int)(__builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(w[2], w[1], 2), K, 128u, false) >> 8);
-    y[3] = (int)(__builtin_amdgcn_udot4(w[2], K << 8, 128u, false) >> 8);
-}
 
 // (a + b) >> 1 of the four bytes of two words at once
 __device__ __forceinline__ unsigned il_avg4(unsigned a, unsigned b) { return (a & b) + (((a ^ b) & 0xFEFEFEFEu) >> 1); }
 
-__device__ __forceinline__ int il_byte(const unsigned (&w)[3], int i) { return (int)((w[i >> 2] >> (8 * (i & 3))) & 255u); }
-
-__device__ __forceinline__ int il_luma_at(const uint8_t* row, int x) { return il_luma(row[3 * x], row[3 * x + 1], row[3 * x + 2]); }
-
-// three dwords of a group that is whole and on a dword
-__device__ __forceinline__ void il_load_dwords(const uint8_t* p, unsigned (&w)[3]) {
-    const unsigned* q = reinterpret_cast<const unsigned*>(p);
-    w[0] = q[0];
-    w[1] = q[1];
-    w[2] = q[2];
-}
+__device__ __forceinline__ int il_luma_at(const uint8_t* row, int x) { return fb_luma(row[3 * x], row[3 * x + 1], row[3 * x + 2]); }
 
 template <bool EDGES, int FIRST>
 __global__ void __launch_bounds__(IL_NTH)
@@ -126,9 +74,9 @@ interlace_fields_kernel(const uint8_t* __restrict__ frames, const int* __restric
             const int row = y0 - 2 + w;
             cw[w][0] = cw[w][1] = cw[w][2] = pw[w][0] = pw[w][1] = pw[w][2] = nw[w][0] = nw[w][1] = nw[w][2] = 0;
             if (row >= 0 && row < H) {
-                il_load_dwords(C + row * rowb + col, cw[w]);
-                il_load_dwords(P + row * rowb + col, pw[w]);
-                il_load_dwords(N + row * rowb + col, nw[w]);
+                fb_load_dwords(C + row * rowb + col, cw[w]);
+                fb_load_dwords(P + row * rowb + col, pw[w]);
+                fb_load_dwords(N + row * rowb + col, nw[w]);
             }
         }
     } else {
@@ -137,18 +85,18 @@ interlace_fields_kernel(const uint8_t* __restrict__ frames, const int* __restric
             const int row = y0 - 2 + w;
             cw[w][0] = cw[w][1] = cw[w][2] = pw[w][0] = pw[w][1] = pw[w][2] = nw[w][0] = nw[w][1] = nw[w][2] = 0;
             if (row >= 0 && row < H) {
-                il_load(C + row * rowb + col, n, cw[w]);
-                il_load(P + row * rowb + col, n, pw[w]);
-                il_load(N + row * rowb + col, n, nw[w]);
+                fb_load(C + row * rowb + col, n, cw[w]);
+                fb_load(P + row * rowb + col, n, pw[w]);
+                fb_load(N + row * rowb + col, n, nw[w]);
             }
         }
     }
     int cl[IL_WR][IL_PX], pl[IL_WR][IL_PX], nl[IL_WR][IL_PX];          // (what a row does not need is never computed)
 #pragma unroll
     for (int w = 0; w < IL_WR; ++w) {
-        il_luma4(cw[w], cl[w]);
-        il_luma4(pw[w], pl[w]);
-        il_luma4(nw[w], nl[w]);
+        fb_luma4(cw[w], cl[w]);
+        fb_luma4(pw[w], pl[w]);
+        fb_luma4(nw[w], nl[w]);
     }
 #pragma unroll
     for (int r = 0; r < IL_R; ++r) {
@@ -156,7 +104,7 @@ interlace_fields_kernel(const uint8_t* __restrict__ frames, const int* __restric
         if (y >= H) break;
         const int kp = ((r & 1) == FIRST) ? 0 : 1, mp = 1 - kp;        // the picture that keeps row y, and the one that misses it
         const int off = y * rowb + col;
-        if (mode == 0 || kp == mode - 1) il_store(out + (mode == 0 ? 2LL * t + kp : (long long)t) * FB + off, n, cw[w]);
+        if (mode == 0 || kp == mode - 1) fb_store(out + (mode == 0 ? 2LL * t + kp : (long long)t) * FB + off, n, cw[w]);
         if (!(mode == 0 || mp == mode - 1)) continue;
         uint8_t* dst = out + (mode == 0 ? 2LL * t + mp : (long long)t) * FB + off;
         // A and B are C and X in either order, and every use of them is symmetric: X = P for the first picture, N for the second
@@ -166,7 +114,7 @@ interlace_fields_kernel(const uint8_t* __restrict__ frames, const int* __restric
 #pragma unroll
         for (int i = 0; i < 3; ++i) dw[i] = il_avg4(xw[w][i], cw[w][i]);
         if (H == 1) {                                                   // no row above or below: the temporal mean alone
-            il_store(dst, n, dw);
+            fb_store(dst, n, dw);
             continue;
         }
         const bool top = y == 0, bot = y == H - 1;                      // up = y + 1 at the top, dn = y - 1 at the bottom
@@ -238,18 +186,18 @@ interlace_fields_kernel(const uint8_t* __restrict__ frames, const int* __restric
 #pragma unroll
         for (int i = 0; i < 3 * IL_PX; ++i) {
             const int px = i / 3, ch = i - 3 * px;
-            int s = il_byte(sp, i);
+            int s = fb_get(sp, i);
             if constexpr (EDGES) {
                 if (J[px] != 0 && px < n) {
                     const int xa = min(max(x0 + px + J[px], 0), W - 1), xb = min(max(x0 + px - J[px], 0), W - 1);
                     s = ((int)rup[3 * xa + ch] + (int)rdn[3 * xb + ch]) >> 1;
                 }
             }
-            const int d = il_byte(dw, i);
+            const int d = fb_get(dw, i);
             const int v = min(max(s, d - diff[px]), d + diff[px]);      // diff >= 0 and d in [0, 255]: v is a byte
             o[i >> 2] |= (unsigned)v << (8 * (i & 3));
         }
-        il_store(dst, n, o);
+        fb_store(dst, n, o);
     }
 }
 
@@ -284,10 +232,10 @@ interlace_scores_kernel(const uint8_t* __restrict__ frames, const int* __restric
         for (int r = a; r < b; ++r) {
             unsigned wc[3], wn[3];
             int yc[IL_PX], yn[IL_PX];
-            il_load(C + (long long)r * rowb, n, wc);
-            il_load(N + (long long)r * rowb, n, wn);
-            il_luma4(wc, yc);
-            il_luma4(wn, yn);
+            fb_load(C + (long long)r * rowb, n, wc);
+            fb_load(N + (long long)r * rowb, n, wn);
+            fb_luma4(wc, yc);
+            fb_luma4(wn, yn);
             if (r == a) {
 #pragma unroll
                 for (int i = 0; i < IL_PX; ++i) s_first[run][cgi][i] = yc[i];
@@ -352,22 +300,11 @@ interlace_scores_kernel(const uint8_t* __restrict__ frames, const int* __restric
     }
 }
 
-int il_check_sizes(const char* who, int32_t L, int32_t H, int32_t W) {
-    E2_REQUIRE(L >= 0 && H >= 0 && W >= 0, E2FGVI_EINVAL, "%s: negative size (L = %d, H = %d, W = %d)", who, L, H, W);
-    E2_REQUIRE((int64_t)H * W <= IL_N_MAX, E2FGVI_EINVAL, "%s: needs H * W <= 2^26, got %d x %d", who, H, W);
-    return 0;
-}
-
-bool il_disjoint(const void* p, uint64_t pn, const void* q, uint64_t qn) {
-    const uint64_t a = (uint64_t)(uintptr_t)p, b = (uint64_t)(uintptr_t)q;
-    return a + pn <= b || b + qn <= a;
-}
-
 }  // namespace
 
 extern "C" int e2fgvi_interlace_scores(const uint8_t* frames, const int32_t* scene, int64_t* D, int32_t L, int32_t H, int32_t W,
                                        void* stream) {
-    if (int rc = il_check_sizes("interlace_scores", L, H, W)) return rc;
+    if (int rc = fb_check_sizes("interlace_scores", L, H, W)) return rc;
     if (L == 0 || H == 0 || W == 0) return 0;                      // no pixel: no launch, and the pointers are not looked at
     E2_REQUIRE(frames && scene && D, E2FGVI_EINVAL, "interlace_scores: null pointer");
     E2_REQUIRE(((uintptr_t)scene & 3) == 0 && ((uintptr_t)D & 7) == 0, E2FGVI_EINVAL,
@@ -377,18 +314,15 @@ extern "C" int e2fgvi_interlace_scores(const uint8_t* frames, const int32_t* sce
     E2_REQUIRE(e == hipSuccess, (int)e, "interlace_scores: hipMemsetAsync failed: %s", hipGetErrorString(e));
     if (H < 4 || L < 2) return 0;                                  // no row is scored, or no pair: the zeros are the answer
     const unsigned nblk = (unsigned)cdiv(cdiv(W, IL_PX), IL_SC);
-    for (int t0 = 0; t0 < L - 1; t0 += IL_FRAMES_MAX) {
-        const dim3 grid(nblk, (unsigned)(L - 1 - t0 < IL_FRAMES_MAX ? L - 1 - t0 : IL_FRAMES_MAX), 1);
-        hipLaunchKernelGGL(interlace_scores_kernel, grid, dim3(IL_NTH), 0, st, frames, scene, reinterpret_cast<unsigned long long*>(D),
-                           t0, L, H, W);
-        E2_LAUNCH_CHECK("interlace_scores");
-    }
-    return 0;
+    return fb_slabs("interlace_scores", L - 1, [&](int t0, unsigned n) {               // the L - 1 pairs
+        hipLaunchKernelGGL(interlace_scores_kernel, dim3(nblk, n), dim3(IL_NTH), 0, st, frames, scene,
+                           reinterpret_cast<unsigned long long*>(D), t0, L, H, W);
+    });
 }
 
 extern "C" int e2fgvi_deinterlace(const uint8_t* frames, const int32_t* scene, uint8_t* out, int32_t L, int32_t H, int32_t W,
                                   int32_t tff, int32_t mode, int32_t guard, int32_t edges, void* stream) {
-    if (int rc = il_check_sizes("deinterlace", L, H, W)) return rc;
+    if (int rc = fb_check_sizes("deinterlace", L, H, W)) return rc;
     E2_REQUIRE(tff == 0 || tff == 1, E2FGVI_EINVAL, "deinterlace: tff must be 0 or 1, got %d", tff);
     E2_REQUIRE(mode >= 0 && mode <= 2, E2FGVI_EINVAL, "deinterlace: mode must be in [0, 2], got %d", mode);
     E2_REQUIRE(guard == 0 || guard == 1, E2FGVI_EINVAL, "deinterlace: guard must be 0 or 1, got %d", guard);
@@ -397,16 +331,13 @@ extern "C" int e2fgvi_deinterlace(const uint8_t* frames, const int32_t* scene, u
     E2_REQUIRE(frames && scene && out, E2FGVI_EINVAL, "deinterlace: null pointer");
     E2_REQUIRE(((uintptr_t)scene & 3) == 0, E2FGVI_EINVAL, "deinterlace: scene must be 4-byte aligned");
     const uint64_t fb = 3ull * (uint64_t)H * (uint64_t)W;
-    E2_REQUIRE(il_disjoint(frames, fb * (uint64_t)L, out, fb * (uint64_t)L * (mode == 0 ? 2 : 1)), E2FGVI_EINVAL,
+    E2_REQUIRE(fb_disjoint(frames, fb * (uint64_t)L, out, fb * (uint64_t)L * (mode == 0 ? 2 : 1)), E2FGVI_EINVAL,
                "deinterlace: out must not overlap frames (a picture reads three frames)");
     hipStream_t st = (hipStream_t)stream;
     const unsigned nblk = (unsigned)(cdiv(cdiv(W, IL_PX), IL_TX) * cdiv(H, IL_TY * IL_R));       // at most 2^26 / 4 + 2^22 tiles
     auto kernel = edges > 0 ? (tff ? interlace_fields_kernel<true, 0> : interlace_fields_kernel<true, 1>)
                             : (tff ? interlace_fields_kernel<false, 0> : interlace_fields_kernel<false, 1>);
-    for (int t0 = 0; t0 < L; t0 += IL_FRAMES_MAX) {
-        const dim3 grid(nblk, (unsigned)(L - t0 < IL_FRAMES_MAX ? L - t0 : IL_FRAMES_MAX), 1);
-        hipLaunchKernelGGL(kernel, grid, dim3(IL_NTH), 0, st, frames, scene, out, t0, L, H, W, mode, guard, edges);
-        E2_LAUNCH_CHECK("deinterlace");
-    }
-    return 0;
+    return fb_slabs("deinterlace", L, [&](int t0, unsigned n) {
+        hipLaunchKernelGGL(kernel, dim3(nblk, n), dim3(IL_NTH), 0, st, frames, scene, out, t0, L, H, W, mode, guard, edges);
+    });
 }

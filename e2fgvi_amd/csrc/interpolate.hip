@@ -17,13 +17,12 @@
 // A thread owns four pixels: in a job with k == 0 or k == d four adjacent ones, whose twelve bytes it copies as dwords where the
 // addresses allow; in a new frame every 64th of its wave's 256, so that a wave's loads and stores are runs of adjacent pixels.
 // The job is the grid's y axis; a job outside its ranges writes nothing.  What binds the kernel is in profiles/interpolate.txt.
-#include "common.h"
+#include "frame_bytes.h"          // the launch in slabs and the overlap test
 
 namespace {
 
 constexpr int IP_NTH = 256;
 constexpr int IP_PX = 4;              // pixels per thread
-constexpr int IP_SLAB = 65535;        // jobs per launch (the grid's y axis); more are launched in slabs
 constexpr int IP_D_MAX = 64;
 constexpr int IP_ITER_MAX = 8;
 
@@ -243,11 +242,6 @@ interpolate_kernel(const uint8_t* __restrict__ frames, const float* __restrict__
     }
 }
 
-bool ip_disjoint(const void* p, uint64_t pn, const void* q, uint64_t qn) {
-    const uint64_t a = (uint64_t)(uintptr_t)p, b = (uint64_t)(uintptr_t)q;
-    return a + pn <= b || b + qn <= a;
-}
-
 }  // namespace
 
 extern "C" int e2fgvi_interpolate(const uint8_t* frames, const float* fwd, const float* bwd, const int32_t* jobs, uint8_t* out,
@@ -268,26 +262,23 @@ extern "C" int e2fgvi_interpolate(const uint8_t* frames, const float* fwd, const
     E2_REQUIRE(P == 0 || (fwd && bwd), E2FGVI_EINVAL, "interpolate: null pointer");
     E2_REQUIRE(((uintptr_t)fwd & 7) == 0 && ((uintptr_t)bwd & 7) == 0, E2FGVI_EINVAL, "interpolate: fwd and bwd must be 8-byte aligned");
     const uint64_t px = (uint64_t)H * (uint64_t)W;
-    E2_REQUIRE(ip_disjoint(frames, 3ull * px * (uint64_t)L, out, 3ull * px * (uint64_t)n), E2FGVI_EINVAL,
+    E2_REQUIRE(fb_disjoint(frames, 3ull * px * (uint64_t)L, out, 3ull * px * (uint64_t)n), E2FGVI_EINVAL,
                "interpolate: out must not overlap frames (a pixel reads two frames)");
     // nothing that is written may lie on anything that is read, or on the other output: threads of other pixels and jobs read on
     const uint64_t ob = 3ull * px * (uint64_t)n, sb = px * (uint64_t)n, hb = 8ull * px * (uint64_t)P, jn = 20ull * (uint64_t)n;
-    E2_REQUIRE(ip_disjoint(fwd, hb, out, ob) && ip_disjoint(bwd, hb, out, ob) && ip_disjoint(jobs, jn, out, ob), E2FGVI_EINVAL,
+    E2_REQUIRE(fb_disjoint(fwd, hb, out, ob) && fb_disjoint(bwd, hb, out, ob) && fb_disjoint(jobs, jn, out, ob), E2FGVI_EINVAL,
                "interpolate: out must not overlap fwd, bwd or jobs");
     if (source) {
-        E2_REQUIRE(ip_disjoint(frames, 3ull * px * (uint64_t)L, source, sb) && ip_disjoint(out, ob, source, sb) &&
-                       ip_disjoint(fwd, hb, source, sb) && ip_disjoint(bwd, hb, source, sb) && ip_disjoint(jobs, jn, source, sb),
+        E2_REQUIRE(fb_disjoint(frames, 3ull * px * (uint64_t)L, source, sb) && fb_disjoint(out, ob, source, sb) &&
+                       fb_disjoint(fwd, hb, source, sb) && fb_disjoint(bwd, hb, source, sb) && fb_disjoint(jobs, jn, source, sb),
                    E2FGVI_EINVAL, "interpolate: source must not overlap frames, fwd, bwd, jobs or out");
     }
     hipStream_t st = (hipStream_t)stream;
     // a workgroup's 256 threads own 1024 adjacent pixels: H W < 2^31, so the grid's x axis is below 2^21
     const unsigned nblk = (unsigned)(((long long)H * W + (long long)IP_NTH * IP_PX - 1) / ((long long)IP_NTH * IP_PX));
     const double bound = (double)(tolerance * tolerance) / 256.0;
-    for (int j0 = 0; j0 < n; j0 += IP_SLAB) {
-        const int nj = n - j0 < IP_SLAB ? n - j0 : IP_SLAB;
-        hipLaunchKernelGGL(interpolate_kernel, dim3(nblk, (unsigned)nj, 1), dim3(IP_NTH), 0, st, frames, fwd, bwd, jobs, out, source, j0,
-                           L, P, H, W, iterations, bound, match);
-        E2_LAUNCH_CHECK("interpolate");
-    }
-    return 0;
+    return fb_slabs("interpolate", n, [&](int j0, unsigned nj) {
+        hipLaunchKernelGGL(interpolate_kernel, dim3(nblk, nj), dim3(IP_NTH), 0, st, frames, fwd, bwd, jobs, out, source, j0, L, P, H, W,
+                           iterations, bound, match);
+    });
 }

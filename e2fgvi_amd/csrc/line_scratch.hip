@@ -24,21 +24,18 @@
 // takes the H % rows rows below it along).  It stages, for its columns and `radius` more on either side, whether a kept column of
 // either polarity spans the band (b0 <= b <= b1), in LDS -- a tile without one is zeros and ends there --, ORs 2 radius + 1 of them
 // per pixel, and every wave writes the same dword per lane down its share of the band's rows: each mask byte is written once.
-#include "common.h"
+#include "frame_bytes.h"
 
 namespace {
 
 constexpr int LN_NTH = 256;
-constexpr int LN_PX = 4;                  // pixels per thread of the sums and the paint kernel
-constexpr int LN_FRAMES_MAX = 65535;      // frames per launch (the grid's y axis); more are launched in slabs
+constexpr int LN_PX = FB_PX;              // pixels per thread of the sums and the paint kernel
 constexpr int LN_ROWS_MIN = 4, LN_ROWS_MAX = 64;
 constexpr int LN_GAP_MAX = 4, LN_SIDE_MAX = 8, LN_DRIFT_MAX = 2, LN_SPAN_MAX = 4;
 constexpr int LN_RMAX = 16;               // largest paint radius the LDS row holds
 constexpr int LN_CW = LN_NTH - 2 * LN_DRIFT_MAX;     // columns a workgroup of the columns kernel owns
 constexpr int LN_CB = 4;                  // bands per trip of the columns kernel
 constexpr int LN_TW = 64 * LN_PX;         // columns of a paint tile: a wave's row
-
-__device__ __forceinline__ int ln_luma(unsigned r, unsigned g, unsigned b) { return (int)((77u * r + 150u * g + 29u * b + 128u) >> 8); }
 
 __global__ void __launch_bounds__(LN_NTH)
 line_sums_kernel(const uint8_t* __restrict__ frames, int t0, int H, int W, int rows, int nb, int wq, int* __restrict__ S) {
@@ -56,18 +53,18 @@ line_sums_kernel(const uint8_t* __restrict__ frames, int t0, int H, int W, int r
     if (nx == LN_PX && ((uintptr_t)p & 3) == 0 && (pitch & 3) == 0) {
 #pragma unroll 4
         for (int r = 0; r < rows; ++r, p += pitch) {
-            const unsigned* q = reinterpret_cast<const unsigned*>(p);
-            const unsigned w0 = q[0], w1 = q[1], w2 = q[2];
-            s[0] += ln_luma(w0 & 255u, (w0 >> 8) & 255u, (w0 >> 16) & 255u);
-            s[1] += ln_luma(w0 >> 24, w1 & 255u, (w1 >> 8) & 255u);
-            s[2] += ln_luma((w1 >> 16) & 255u, w1 >> 24, w2 & 255u);
-            s[3] += ln_luma((w2 >> 8) & 255u, (w2 >> 16) & 255u, w2 >> 24);
+            unsigned w[3];
+            int y[LN_PX];
+            fb_load_dwords(p, w);
+            fb_luma4(w, y);
+#pragma unroll
+            for (int j = 0; j < LN_PX; ++j) s[j] += y[j];
         }
     } else {
         for (int r = 0; r < rows; ++r, p += pitch) {
 #pragma unroll
             for (int j = 0; j < LN_PX; ++j)
-                if (j < nx) s[j] += ln_luma(p[j * 3], p[j * 3 + 1], p[j * 3 + 2]);
+                if (j < nx) s[j] += fb_luma(p[j * 3], p[j * 3 + 1], p[j * 3 + 2]);
         }
     }
     int* D = S + ((long long)t * nb + b) * W + xb;
@@ -236,6 +233,7 @@ line_paint_kernel(const uint8_t* __restrict__ keep, const int* __restrict__ b0, 
     }
 }
 
+// (the unit's own: it takes frames of up to 2^31 - 256 pixels where fb_check_sizes stops at 2^26)
 int ln_check_sizes(const char* who, int32_t L, int32_t H, int32_t W, int32_t rows) {
     E2_REQUIRE(L >= 0 && H >= 0 && W >= 0, E2FGVI_EINVAL, "%s: negative size (L = %d, H = %d, W = %d)", who, L, H, W);
     E2_REQUIRE((int64_t)H * W < 2147483647LL - 256, E2FGVI_EINVAL, "%s: needs H * W < 2^31 - 256, got %d x %d", who, H, W);
@@ -258,12 +256,9 @@ extern "C" int e2fgvi_line_sums(const uint8_t* frames, int32_t L, int32_t H, int
     hipStream_t st = (hipStream_t)stream;
     const int wq = (W + LN_PX - 1) / LN_PX;
     const unsigned nblk = (unsigned)(((long long)nb * wq + LN_NTH - 1) / LN_NTH);
-    for (int t0 = 0; t0 < L; t0 += LN_FRAMES_MAX) {
-        const dim3 grid(nblk, (unsigned)(L - t0 < LN_FRAMES_MAX ? L - t0 : LN_FRAMES_MAX), 1);
-        hipLaunchKernelGGL(line_sums_kernel, grid, dim3(LN_NTH), 0, st, frames, t0, H, W, rows, nb, wq, S);
-        E2_LAUNCH_CHECK("line_sums");
-    }
-    return 0;
+    return fb_slabs("line_sums", L, [&](int t0, unsigned n) {
+        hipLaunchKernelGGL(line_sums_kernel, dim3(nblk, n), dim3(LN_NTH), 0, st, frames, t0, H, W, rows, nb, wq, S);
+    });
 }
 
 extern "C" int e2fgvi_line_columns(const int32_t* S, int32_t L, int32_t H, int32_t W, int32_t rows, int32_t tau, int32_t gap,
@@ -282,13 +277,10 @@ extern "C" int e2fgvi_line_columns(const int32_t* S, int32_t L, int32_t H, int32
                "line_columns: S, cnt, b0 and b1 must be 4-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const unsigned ntx = (unsigned)((W + LN_CW - 1) / LN_CW);
-    for (int t0 = 0; t0 < L; t0 += LN_FRAMES_MAX) {
-        const dim3 grid(ntx, (unsigned)(L - t0 < LN_FRAMES_MAX ? L - t0 : LN_FRAMES_MAX), 1);
-        hipLaunchKernelGGL(line_columns_kernel, grid, dim3(LN_NTH), 0, st, S, t0, nb, W, tau * rows, gap, side, drift, coverage, cand,
-                           cnt, col, b0, b1);
-        E2_LAUNCH_CHECK("line_columns");
-    }
-    return 0;
+    return fb_slabs("line_columns", L, [&](int t0, unsigned n) {
+        hipLaunchKernelGGL(line_columns_kernel, dim3(ntx, n), dim3(LN_NTH), 0, st, S, t0, nb, W, tau * rows, gap, side, drift, coverage,
+                           cand, cnt, col, b0, b1);
+    });
 }
 
 extern "C" int e2fgvi_line_paint(const uint8_t* col, const int32_t* b0, const int32_t* b1, const int32_t* scene, int32_t L, int32_t H,
@@ -309,14 +301,13 @@ extern "C" int e2fgvi_line_paint(const uint8_t* col, const int32_t* b0, const in
     E2_REQUIRE(e == hipSuccess, (int)e, "line_paint: hipMemsetAsync failed: %s", hipGetErrorString(e));
     const unsigned nkx = (unsigned)((W + LN_NTH - 1) / LN_NTH);
     const int ntx = (W + LN_TW - 1) / LN_TW;
-    for (int t0 = 0; t0 < L; t0 += LN_FRAMES_MAX) {
-        const unsigned nt = (unsigned)(L - t0 < LN_FRAMES_MAX ? L - t0 : LN_FRAMES_MAX);
-        hipLaunchKernelGGL(line_keep_kernel, dim3(nkx, nt, 1), dim3(LN_NTH), 0, st, col, scene, t0, L, W, drift, span, persist, keep,
-                           counts);
-        E2_LAUNCH_CHECK("line_paint");
-        hipLaunchKernelGGL(line_paint_kernel, dim3((unsigned)((long long)ntx * nb), nt, 1), dim3(LN_NTH), 0, st, keep, b0, b1, t0, H, W,
-                           rows, nb, radius, ntx, masks);
-        E2_LAUNCH_CHECK("line_paint");
-    }
-    return 0;
+    // every slab's columns are kept before the first is painted: a frame's paint reads its own keep row alone
+    const int rc = fb_slabs("line_paint", L, [&](int t0, unsigned n) {
+        hipLaunchKernelGGL(line_keep_kernel, dim3(nkx, n), dim3(LN_NTH), 0, st, col, scene, t0, L, W, drift, span, persist, keep, counts);
+    });
+    if (rc) return rc;
+    return fb_slabs("line_paint", L, [&](int t0, unsigned n) {
+        hipLaunchKernelGGL(line_paint_kernel, dim3((unsigned)((long long)ntx * nb), n), dim3(LN_NTH), 0, st, keep, b0, b1, t0, H, W, rows,
+                           nb, radius, ntx, masks);
+    });
 }

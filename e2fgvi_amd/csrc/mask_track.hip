@@ -21,13 +21,12 @@
 // rows that are not dword-aligned).  The job is the grid's y axis; a job outside [0, L-1) x {0, 1} writes nothing.  No atomics: the
 // same inputs give the same bits.  Within a launch no job may write a frame of a plane that another job reads or writes
 // (video.plan_mask_chains guarantees it).
-#include "common.h"
+#include "frame_bytes.h"          // the launch in slabs
 
 namespace {
 
 constexpr int MT_NTH = 256;
 constexpr int MT_PX = 4;              // pixels per thread
-constexpr int MT_JOBS_MAX = 65535;    // jobs per launch (the grid's y axis); more are launched in slabs
 
 __device__ __forceinline__ unsigned mt_pixel(const uint8_t* M, const float* __restrict__ g, const float* __restrict__ c,
                                              int x, int y, int H, int W, int check) {
@@ -104,11 +103,8 @@ extern "C" int e2fgvi_mask_track_step(uint8_t* planes, const float* fwd, const f
     hipStream_t st = (hipStream_t)stream;
     const int wq = (W + MT_PX - 1) / MT_PX;
     const unsigned nblk = (unsigned)(((long long)H * wq + MT_NTH - 1) / MT_NTH);
-    for (int j0 = 0; j0 < n; j0 += MT_JOBS_MAX) {
-        const int nj = n - j0 < MT_JOBS_MAX ? n - j0 : MT_JOBS_MAX;
-        hipLaunchKernelGGL(mask_track_step_kernel, dim3(nblk, (unsigned)nj, 1), dim3(MT_NTH), 0, st, planes, fwd, bwd,
-                           jobs + 2LL * j0, L, H, W, wq, check);
-        E2_LAUNCH_CHECK("mask_track_step");
-    }
-    return 0;
+    return fb_slabs("mask_track_step", n, [&](int j0, unsigned nj) {
+        hipLaunchKernelGGL(mask_track_step_kernel, dim3(nblk, nj), dim3(MT_NTH), 0, st, planes, fwd, bwd, jobs + 2LL * j0, L, H, W, wq,
+                           check);
+    });
 }

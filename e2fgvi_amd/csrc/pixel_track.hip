@@ -28,13 +28,12 @@
 // job outside [0, L-1) x {0, 1} writes nothing.  No atomics: the same inputs give the same bits.  Within a launch no job may write
 // a frame of a plane that another job reads or writes (video.plan_pixel_chains guarantees it).
 // The fill: one launch over all frames, see pixel_fill_kernel.
-#include "common.h"
+#include "frame_bytes.h"          // the launch in slabs
 
 namespace {
 
 constexpr int PT_NTH = 256;
 constexpr int PT_PX = 4;              // pixels per thread
-constexpr int PT_SLAB = 65535;        // jobs / frames per launch (the grid's y axis); more are launched in slabs
 
 // the hole bytes of a thread's nx pixels at h, one per byte of the result
 __device__ __forceinline__ unsigned pt_hole_bytes(const uint8_t* h, int nx) {
@@ -226,13 +225,10 @@ extern "C" int e2fgvi_pixel_track_step(const uint8_t* hole, uint8_t* age, float*
     hipStream_t st = (hipStream_t)stream;
     const int wq = (W + PT_PX - 1) / PT_PX;
     const unsigned nblk = (unsigned)(((long long)H * wq + PT_NTH - 1) / PT_NTH);
-    for (int j0 = 0; j0 < n; j0 += PT_SLAB) {
-        const int nj = n - j0 < PT_SLAB ? n - j0 : PT_SLAB;
-        hipLaunchKernelGGL(pixel_track_step_kernel, dim3(nblk, (unsigned)nj, 1), dim3(PT_NTH), 0, st, hole, age, origin, fwd, bwd,
-                           jobs + 2LL * j0, L, H, W, wq, reach, check);
-        E2_LAUNCH_CHECK("pixel_track_step");
-    }
-    return 0;
+    return fb_slabs("pixel_track_step", n, [&](int j0, unsigned nj) {
+        hipLaunchKernelGGL(pixel_track_step_kernel, dim3(nblk, nj), dim3(PT_NTH), 0, st, hole, age, origin, fwd, bwd, jobs + 2LL * j0, L,
+                           H, W, wq, reach, check);
+    });
 }
 
 extern "C" int e2fgvi_pixel_fill(const uint8_t* src, const uint8_t* hole, const uint8_t* age, const float* origin, uint8_t* out,
@@ -245,11 +241,7 @@ extern "C" int e2fgvi_pixel_fill(const uint8_t* src, const uint8_t* hole, const 
     hipStream_t st = (hipStream_t)stream;
     const int wq = (W + PT_PX - 1) / PT_PX;
     const unsigned nblk = (unsigned)(((long long)H * wq + PT_NTH - 1) / PT_NTH);
-    for (int t0 = 0; t0 < L; t0 += PT_SLAB) {
-        const int nt = L - t0 < PT_SLAB ? L - t0 : PT_SLAB;
-        hipLaunchKernelGGL(pixel_fill_kernel, dim3(nblk, (unsigned)nt, 1), dim3(PT_NTH), 0, st, src, hole, age, origin, out, source,
-                           t0, L, H, W, wq);
-        E2_LAUNCH_CHECK("pixel_fill");
-    }
-    return 0;
+    return fb_slabs("pixel_fill", L, [&](int t0, unsigned nt) {
+        hipLaunchKernelGGL(pixel_fill_kernel, dim3(nblk, nt), dim3(PT_NTH), 0, st, src, hole, age, origin, out, source, t0, L, H, W, wq);
+    });
 }

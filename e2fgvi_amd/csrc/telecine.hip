@@ -23,7 +23,7 @@
 // 256 apart: a whole piece that lies inside one row is one 16-byte load from the frame that row comes from and one aligned
 // 16-byte store; a head, a tail and a piece that spans two rows go byte by byte, each byte from the frame of its own row.  Every
 // byte is written once; frame ids are clamped to [0, L - 1], so no id reads outside the frames.
-#include "common.h"
+#include "frame_bytes.h"
 
 namespace {
 
@@ -31,8 +31,6 @@ constexpr int TC_NTH = 256;
 constexpr int TC_PX = 16;                 // pixels per group: 48 bytes, three 16-byte loads
 constexpr int TC_WAVES = TC_NTH / 64;     // runs of rows per workgroup
 constexpr int TC_ROWS = 32 * TC_WAVES;    // rows of a cell row per workgroup, at most: a run has at most 32 rows
-constexpr int TC_FRAMES_MAX = 65535;      // frames per launch (the grid's y axis); more are launched in slabs
-constexpr long long TC_N_MAX = 1LL << 26;
 constexpr int TC_PIECES = 4;              // 16-byte pieces per thread of the weave
 
 struct TcGroup {                          // the 48 bytes of a group
@@ -55,17 +53,15 @@ __device__ __forceinline__ void tc_load(const uint8_t* p, int n, bool wide, TcGr
     }
 }
 
-// the luma of the 16 pixels of a group, four at a time from three dwords: a pixel's three bytes are moved to the bottom (or left
-// at the top) of a word and multiplied by the three weights in one v_dot4_u32_u8, the fourth weight being 0 (csrc/interlace.hip)
+// the luma of the 16 pixels of a group, four at a time from three dwords
 __device__ __forceinline__ void tc_luma16(const TcGroup& g, int n, int (&y)[TC_PX]) {
-    constexpr unsigned K = 77u | (150u << 8) | (29u << 16);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const unsigned a = g.w[3 * k], b = g.w[3 * k + 1], c = g.w[3 * k + 2];
-        y[4 * k + 0] = (int)(__builtin_amdgcn_udot4(a, K, 128u, false) >> 8);
-        y[4 * k + 1] = (int)(__builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(b, a, 3), K, 128u, false) >> 8);
-        y[4 * k + 2] = (int)(__builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(c, b, 2), K, 128u, false) >> 8);
-        y[4 * k + 3] = (int)(__builtin_amdgcn_udot4(c, K << 8, 128u, false) >> 8);
+    for (int k = 0; k < TC_PX / FB_PX; ++k) {
+        const unsigned w[3] = {g.w[3 * k], g.w[3 * k + 1], g.w[3 * k + 2]};
+        int y4[FB_PX];
+        fb_luma4(w, y4);
+#pragma unroll
+        for (int j = 0; j < FB_PX; ++j) y[FB_PX * k + j] = y4[j];
     }
     if (n < TC_PX) {                                                    // a short group: the pixels behind it belong to another cell
 #pragma unroll
@@ -183,7 +179,7 @@ telecine_scores_kernel(const uint8_t* __restrict__ frames, const int* __restrict
 __global__ void __launch_bounds__(TC_NTH)
 telecine_weave_kernel(const uint8_t* __restrict__ frames, const int* __restrict__ jobs, uint8_t* __restrict__ out, int n, int L, int H,
                       int W, int keep) {
-    const long long i = (long long)blockIdx.z * TC_FRAMES_MAX + blockIdx.y;
+    const long long i = (long long)blockIdx.z * FB_FRAMES_MAX + blockIdx.y;
     if (i >= n) return;
     const long long FB = 3LL * H * W;
     const int fb = (int)FB, rowb = 3 * W;                               // at most 3 * 2^26
@@ -213,22 +209,11 @@ telecine_weave_kernel(const uint8_t* __restrict__ frames, const int* __restrict_
     }
 }
 
-int tc_check_sizes(const char* who, int32_t L, int32_t H, int32_t W) {
-    E2_REQUIRE(L >= 0 && H >= 0 && W >= 0, E2FGVI_EINVAL, "%s: negative size (L = %d, H = %d, W = %d)", who, L, H, W);
-    E2_REQUIRE((int64_t)H * W <= TC_N_MAX, E2FGVI_EINVAL, "%s: needs H * W <= 2^26, got %d x %d", who, H, W);
-    return 0;
-}
-
-bool tc_disjoint(const void* p, uint64_t pn, const void* q, uint64_t qn) {
-    const uint64_t a = (uint64_t)(uintptr_t)p, b = (uint64_t)(uintptr_t)q;
-    return a + pn <= b || b + qn <= a;
-}
-
 }  // namespace
 
 extern "C" int e2fgvi_telecine_scores(const uint8_t* frames, const int32_t* scene, int64_t* M, int32_t L, int32_t H, int32_t W,
                                       void* stream) {
-    if (int rc = tc_check_sizes("telecine_scores", L, H, W)) return rc;
+    if (int rc = fb_check_sizes("telecine_scores", L, H, W)) return rc;
     if (L == 0 || H == 0 || W == 0) return 0;                      // no pixel: no launch, and the pointers are not looked at
     E2_REQUIRE(frames && scene && M, E2FGVI_EINVAL, "telecine_scores: null pointer");
     E2_REQUIRE(((uintptr_t)scene & 3) == 0 && ((uintptr_t)M & 7) == 0, E2FGVI_EINVAL,
@@ -242,18 +227,15 @@ extern "C" int e2fgvi_telecine_scores(const uint8_t* frames, const int32_t* scen
     const int band = cdiv(H, 4);                                   // the rows of a cell row, at most
     const int nbx = cdiv(groups, 64), nchunk = cdiv(band, TC_ROWS), per = cdiv(band, nchunk * TC_WAVES);     // per <= 32
     const unsigned nblk = 4u * (unsigned)nchunk * (unsigned)nbx;   // at most 4 (2^26 / 128 + 1) (2^26 / 1024 + 2)-ish, far below 2^31
-    for (int t0 = 0; t0 < L; t0 += TC_FRAMES_MAX) {
-        const dim3 grid(nblk, (unsigned)(L - t0 < TC_FRAMES_MAX ? L - t0 : TC_FRAMES_MAX), 1);
-        hipLaunchKernelGGL(telecine_scores_kernel, grid, dim3(TC_NTH), 0, st, frames, scene, reinterpret_cast<unsigned long long*>(M),
-                           t0, L, H, W, nbx, nchunk, per);
-        E2_LAUNCH_CHECK("telecine_scores");
-    }
-    return 0;
+    return fb_slabs("telecine_scores", L, [&](int t0, unsigned n) {
+        hipLaunchKernelGGL(telecine_scores_kernel, dim3(nblk, n), dim3(TC_NTH), 0, st, frames, scene,
+                           reinterpret_cast<unsigned long long*>(M), t0, L, H, W, nbx, nchunk, per);
+    });
 }
 
 extern "C" int e2fgvi_field_weave(const uint8_t* frames, const int32_t* jobs, uint8_t* out, int32_t L, int32_t n, int32_t H, int32_t W,
                                   int32_t keep, void* stream) {
-    if (int rc = tc_check_sizes("field_weave", L, H, W)) return rc;
+    if (int rc = fb_check_sizes("field_weave", L, H, W)) return rc;
     E2_REQUIRE(n >= 0, E2FGVI_EINVAL, "field_weave: negative size (n = %d)", n);
     E2_REQUIRE(keep == 0 || keep == 1, E2FGVI_EINVAL, "field_weave: keep must be 0 or 1, got %d", keep);
     if (n == 0 || H == 0 || W == 0) return 0;                      // no byte to write: no launch, and the pointers are not looked at
@@ -261,11 +243,12 @@ extern "C" int e2fgvi_field_weave(const uint8_t* frames, const int32_t* jobs, ui
     E2_REQUIRE(frames && jobs && out, E2FGVI_EINVAL, "field_weave: null pointer");
     E2_REQUIRE(((uintptr_t)jobs & 3) == 0, E2FGVI_EINVAL, "field_weave: jobs must be 4-byte aligned");
     const uint64_t fb = 3ull * (uint64_t)H * (uint64_t)W;
-    E2_REQUIRE(tc_disjoint(frames, fb * (uint64_t)L, out, fb * (uint64_t)n), E2FGVI_EINVAL,
+    E2_REQUIRE(fb_disjoint(frames, fb * (uint64_t)L, out, fb * (uint64_t)n), E2FGVI_EINVAL,
                "field_weave: out must not overlap frames (a row is read while another is written)");
     const unsigned pieces = (unsigned)(fb / 16 + 2);               // a head, the whole pieces, a tail: at most
-    const dim3 grid((pieces + TC_NTH * TC_PIECES - 1) / (TC_NTH * TC_PIECES), (unsigned)(n < TC_FRAMES_MAX ? n : TC_FRAMES_MAX),
-                    (unsigned)cdiv(n, TC_FRAMES_MAX));
+    // one launch, the slabs of jobs on the grid's z axis (the kernel puts y and z together): no loop for fb_slabs to take over
+    const dim3 grid((pieces + TC_NTH * TC_PIECES - 1) / (TC_NTH * TC_PIECES), (unsigned)(n < FB_FRAMES_MAX ? n : FB_FRAMES_MAX),
+                    (unsigned)cdiv(n, FB_FRAMES_MAX));
     hipLaunchKernelGGL(telecine_weave_kernel, grid, dim3(TC_NTH), 0, (hipStream_t)stream, frames, jobs, out, n, L, H, W, keep);
     E2_LAUNCH_CHECK("field_weave");
     return 0;

@@ -1,7 +1,7 @@
 // Byte-side kernels of the sliding-window video driver: everything test.py does to the
 // uint8 frames and masks around the model call, on the device.  HBM-bound integer / byte work: one thread per output
 // element, coalesced along the innermost (channel / x) index; results are bit-exact with the numpy / PIL reference.
-#include "common.h"
+#include "frame_bytes.h"
 
 namespace {
 
@@ -760,7 +760,8 @@ constexpr int SD_REP = 8;
 constexpr int SD_STRIP = 32768;                                               // bytes a workgroup aims for
 static_assert(SD_ROW == NTH, "a thread per counter of the cell row");
 
-__device__ __forceinline__ int sd_bin(unsigned r, unsigned g, unsigned b) { return (int)((77u * r + 150u * g + 29u * b + 128u) >> 10); }
+// the top six bits of the luma
+__device__ __forceinline__ int sd_bin(unsigned r, unsigned g, unsigned b) { return fb_luma(r, g, b) >> 2; }
 
 // first row of cell row c: the smallest y with (4 y) / H >= c
 __host__ __device__ inline int sd_row0(int c, int H) { return (int)(((long long)c * H + 3) / 4); }
@@ -899,15 +900,12 @@ __device__ __forceinline__ OvRaw ov_load_narrow(const unsigned char* __restrict_
     return v;
 }
 
-// the four lumas, pixel j in byte j: a pixel's three bytes are brought into one dword (v_alignbyte_b32) and weighed by one
-// v_dot4_u32_u8 with the rounding 128 as its addend; the fourth byte of the dword meets a weight of 0
+// the four lumas, pixel j in byte j
 __device__ __forceinline__ unsigned ov_luma4(const OvRaw& v) {
-    constexpr unsigned K = 77u | (150u << 8) | (29u << 16);
-    const unsigned y0 = __builtin_amdgcn_udot4(v.d0, K, 128u, false) >> 8;
-    const unsigned y1 = __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(v.d1, v.d0, 3u), K, 128u, false) >> 8;
-    const unsigned y2 = __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(v.d2, v.d1, 2u), K, 128u, false) >> 8;
-    const unsigned y3 = __builtin_amdgcn_udot4(v.d2, K << 8, 128u, false) >> 8;
-    return y0 | (y1 << 8) | (y2 << 16) | (y3 << 24);
+    const unsigned w[3] = {v.d0, v.d1, v.d2};
+    int y[FB_PX];
+    fb_luma4(w, y);
+    return (unsigned)y[0] | ((unsigned)y[1] << 8) | ((unsigned)y[2] << 16) | ((unsigned)y[3] << 24);
 }
 
 template <bool ATOMIC, bool NARROW>
@@ -1541,15 +1539,12 @@ extern "C" int e2fgvi_hole_bbox_frames(const uint8_t* masks, int32_t L, int32_t 
     hipLaunchKernelGGL(bbox_init_kernel, dim3(blocks_for(4LL * L)), dim3(NTH), 0, (hipStream_t)stream, boxes, 4LL * L);
     E2_LAUNCH_CHECK("hole_bbox_frames");
     if ((long long)Hm * Wm == 0) return 0;
-    // a wave per row of a frame, a grid row per frame (65535 frames per launch)
+    // a wave per row of a frame, a grid row per frame
     const int bx = (Hm + BB_WAVES - 1) / BB_WAVES < 2048 ? (Hm + BB_WAVES - 1) / BB_WAVES : 2048;
-    for (int l0 = 0; l0 < L; l0 += 65535) {
-        const int nl = L - l0 < 65535 ? L - l0 : 65535;
-        hipLaunchKernelGGL(hole_bbox_kernel, dim3((unsigned)bx, (unsigned)nl), dim3(NTH), 0, (hipStream_t)stream,
-                           masks + (long long)l0 * Hm * Wm, (long long)Hm, Hm, Wm, boxes + 4LL * l0);
-        E2_LAUNCH_CHECK("hole_bbox_frames");
-    }
-    return 0;
+    return fb_slabs("hole_bbox_frames", L, [&](int l0, unsigned nl) {
+        hipLaunchKernelGGL(hole_bbox_kernel, dim3((unsigned)bx, nl), dim3(NTH), 0, (hipStream_t)stream, masks + (long long)l0 * Hm * Wm,
+                           (long long)Hm, Hm, Wm, boxes + 4LL * l0);
+    });
 }
 
 extern "C" int e2fgvi_gather_slabs(const void* cache, int32_t slots, const int32_t* ids, int32_t n, int64_t slab_bytes, void* window,
@@ -1724,12 +1719,11 @@ extern "C" int e2fgvi_scene_diff(const uint8_t* frames, int32_t L, int32_t H, in
     const long long hmax = ((long long)H + 3) / 4;
     rps = rps < 1 ? 1 : (rps > hmax ? hmax : rps);
     const int nstrips = (int)((hmax + rps - 1) / rps);
-    for (int l0 = 0; l0 < L; l0 += 65535) {
-        const int nl = L - l0 < 65535 ? L - l0 : 65535;
-        hipLaunchKernelGGL(scene_hist_kernel, dim3(4u * (unsigned)nstrips, (unsigned)nl), dim3(NTH), 0, st,
-                           frames + (long long)l0 * H * W * 3, hist + (long long)l0 * SD_TABLE, H, W, (int)rps, nstrips);
-        E2_LAUNCH_CHECK("scene_diff");
-    }
+    const int rc = fb_slabs("scene_diff", L, [&](int l0, unsigned nl) {
+        hipLaunchKernelGGL(scene_hist_kernel, dim3(4u * (unsigned)nstrips, nl), dim3(NTH), 0, st, frames + (long long)l0 * H * W * 3,
+                           hist + (long long)l0 * SD_TABLE, H, W, (int)rps, nstrips);
+    });
+    if (rc) return rc;
     for (int l0 = 0; l0 < L - 1; l0 += 1 << 30) {
         const int nl = L - 1 - l0 < (1 << 30) ? L - 1 - l0 : (1 << 30);
         hipLaunchKernelGGL(scene_diff_kernel, dim3((unsigned)nl), dim3(NTH), 0, st, hist + (long long)l0 * SD_TABLE,

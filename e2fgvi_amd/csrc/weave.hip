@@ -32,24 +32,20 @@
 // groups that span two rows and the last group of a frame go byte by byte with clamped taps -- not where they are met, which
 // holds up the wave of every row's end: they are listed in LDS and done after a barrier by a thread per (group, pixel, channel).
 // profiles/weave.txt has what each of these steps measured.
-#include "common.h"
+#include "frame_bytes.h"
 
 namespace {
 
 constexpr int WV_NTH = 256;
 constexpr int WV_NB = 8;                  // bands per axis
-constexpr int WV_PX = 4;                  // pixels per group
+constexpr int WV_PX = FB_PX;              // pixels per group
 constexpr int WV_RS = 32;                 // rows per workgroup of the profiles kernel
 constexpr int WV_UN = 4;                  // groups of a thread in flight in the profiles kernel
 constexpr int WV_RC = 8;                  // copies of the row sums in LDS: a power of two
 constexpr int WV_AIT = 4;                 // groups per thread of the apply kernel
 constexpr int WV_APX = WV_NTH * WV_PX * WV_AIT;
-constexpr int WV_FRAMES_MAX = 65535;      // frames per launch (the grid's y axis); more are launched in slabs
 constexpr int WV_SIDE_MAX = 4096;         // H and W of the profiles and the match: a profile lives in LDS
 constexpr int WV_RADIUS_MAX = 32, WV_SPAN_MAX = 16, WV_SHIFT_MAX = 64, WV_TEX_MAX = 65535;
-constexpr long long WV_N_MAX = 1LL << 26;
-
-__device__ __forceinline__ int wv_luma(unsigned r, unsigned g, unsigned b) { return (int)((77u * r + 150u * g + 29u * b + 128u) >> 8); }
 
 __global__ void __launch_bounds__(WV_NTH)
 weave_profiles_kernel(const uint8_t* __restrict__ frames, int t0, int H, int W, int nchunk, int* __restrict__ col,
@@ -84,12 +80,7 @@ weave_profiles_kernel(const uint8_t* __restrict__ frames, int t0, int H, int W, 
         for (int k = 0; k < WV_UN; ++k) {
             const int p = (base + k * WV_NTH + tid) * WV_PX;
             w[k][0] = w[k][1] = w[k][2] = 0;
-            if (aligned && p >= P0 && p + WV_PX <= P1) {           // the twelve bytes are the run's
-                const unsigned* q = reinterpret_cast<const unsigned*>(fr + (long long)p * 3);
-                w[k][0] = q[0];
-                w[k][1] = q[1];
-                w[k][2] = q[2];
-            }
+            if (aligned && p >= P0 && p + WV_PX <= P1) fb_load_dwords(fr + (long long)p * 3, w[k]);       // the twelve bytes are the run's
         }
 #pragma unroll
         for (int k = 0; k < WV_UN; ++k) {
@@ -102,10 +93,7 @@ weave_profiles_kernel(const uint8_t* __restrict__ frames, int t0, int H, int W, 
             const int p = g * WV_PX;
             if (aligned && p >= P0 && p + WV_PX <= P1) {
                 int y[WV_PX];
-                y[0] = wv_luma(w[k][0] & 255u, (w[k][0] >> 8) & 255u, (w[k][0] >> 16) & 255u);
-                y[1] = wv_luma(w[k][0] >> 24, w[k][1] & 255u, (w[k][1] >> 8) & 255u);
-                y[2] = wv_luma((w[k][1] >> 16) & 255u, w[k][1] >> 24, w[k][2] & 255u);
-                y[3] = wv_luma((w[k][2] >> 8) & 255u, (w[k][2] >> 16) & 255u, w[k][2] >> 24);
+                fb_luma4(w[k], y);
                 if (x + WV_PX <= W && s_band[x] == s_band[x + WV_PX - 1]) {          // one row, one band
 #pragma unroll
                     for (int j = 0; j < WV_PX; ++j) atomicAdd(s_col + x + j, y[j]);
@@ -123,7 +111,7 @@ weave_profiles_kernel(const uint8_t* __restrict__ frames, int t0, int H, int W, 
                     const int pp = p + j;
                     if (pp >= P0 && pp < P1) {
                         const uint8_t* q = fr + (long long)pp * 3;
-                        const int y = wv_luma(q[0], q[1], q[2]);
+                        const int y = fb_luma(q[0], q[1], q[2]);
                         atomicAdd(s_col + x, y);
                         atomicAdd(mine + ((yr - r0) * WV_NB + (int)s_band[x]) * WV_RC, y);
                     }
@@ -385,17 +373,11 @@ weave_apply_kernel(const uint8_t* __restrict__ frames, const int* __restrict__ s
 }
 
 int wv_check_sizes(const char* who, int32_t L, int32_t H, int32_t W, bool sides) {
-    E2_REQUIRE(L >= 0 && H >= 0 && W >= 0, E2FGVI_EINVAL, "%s: negative size (L = %d, H = %d, W = %d)", who, L, H, W);
-    if (sides)
+    // a profile lives in LDS: a side beyond WV_SIDE_MAX is refused as such, however many pixels the frame has (4096^2 < 2^26, so
+    // the shared check then only refuses a negative size, which it names first as before)
+    if (sides && L >= 0 && H >= 0 && W >= 0)
         E2_REQUIRE(H <= WV_SIDE_MAX && W <= WV_SIDE_MAX, E2FGVI_EINVAL, "%s: needs H and W <= %d, got %d x %d", who, WV_SIDE_MAX, H, W);
-    else
-        E2_REQUIRE((int64_t)H * W <= WV_N_MAX, E2FGVI_EINVAL, "%s: needs H * W <= 2^26, got %d x %d", who, H, W);
-    return 0;
-}
-
-bool wv_disjoint(const void* p, uint64_t pn, const void* q, uint64_t qn) {
-    const uint64_t a = (uint64_t)(uintptr_t)p, b = (uint64_t)(uintptr_t)q;
-    return a + pn <= b || b + qn <= a;
+    return fb_check_sizes(who, L, H, W);
 }
 
 }  // namespace
@@ -410,12 +392,10 @@ extern "C" int e2fgvi_weave_profiles(const uint8_t* frames, int32_t* col, int32_
     hipError_t e = hipMemsetAsync(col, 0, sizeof(int32_t) * WV_NB * (size_t)W * (size_t)L, st);
     E2_REQUIRE(e == hipSuccess, (int)e, "weave_profiles: hipMemsetAsync failed: %s", hipGetErrorString(e));
     const int nchunk = cdiv(cdiv(H, WV_NB), WV_RS);                // a band has at most ceil(H / 8) rows
-    for (int t0 = 0; t0 < L; t0 += WV_FRAMES_MAX) {
-        const dim3 grid((unsigned)(WV_NB * nchunk), (unsigned)(L - t0 < WV_FRAMES_MAX ? L - t0 : WV_FRAMES_MAX), 1);
-        hipLaunchKernelGGL(weave_profiles_kernel, grid, dim3(WV_NTH), 0, st, frames, t0, H, W, nchunk, col, row);
-        E2_LAUNCH_CHECK("weave_profiles");
-    }
-    return 0;
+    return fb_slabs("weave_profiles", L, [&](int t0, unsigned n) {
+        hipLaunchKernelGGL(weave_profiles_kernel, dim3((unsigned)(WV_NB * nchunk), n), dim3(WV_NTH), 0, st, frames, t0, H, W, nchunk, col,
+                           row);
+    });
 }
 
 extern "C" int e2fgvi_weave_match(const int32_t* col, const int32_t* row, const int32_t* scene, int32_t* motion, int32_t L,
@@ -461,17 +441,14 @@ extern "C" int e2fgvi_weave_apply(const uint8_t* frames, const int32_t* shift, u
     E2_REQUIRE(frames && shift && out, E2FGVI_EINVAL, "weave_apply: null pointer");
     E2_REQUIRE(((uintptr_t)shift & 3) == 0, E2FGVI_EINVAL, "weave_apply: shift must be 4-byte aligned");
     const uint64_t px = (uint64_t)L * (uint64_t)N;
-    E2_REQUIRE(wv_disjoint(frames, px * C, out, px * C), E2FGVI_EINVAL,
+    E2_REQUIRE(fb_disjoint(frames, px * C, out, px * C), E2FGVI_EINVAL,
                "weave_apply: out must not overlap frames (a shifted read is not in order)");
-    E2_REQUIRE(!mask || (wv_disjoint(frames, px * C, mask, px) && wv_disjoint(out, px * C, mask, px)), E2FGVI_EINVAL,
+    E2_REQUIRE(!mask || (fb_disjoint(frames, px * C, mask, px) && fb_disjoint(out, px * C, mask, px)), E2FGVI_EINVAL,
                "weave_apply: mask must not overlap frames or out");
     hipStream_t st = (hipStream_t)stream;
     const unsigned nblk = (unsigned)((N + WV_APX - 1) / WV_APX);
-    for (int t0 = 0; t0 < L; t0 += WV_FRAMES_MAX) {
-        const dim3 grid(nblk, (unsigned)(L - t0 < WV_FRAMES_MAX ? L - t0 : WV_FRAMES_MAX), 1);
-        if (C == 3) hipLaunchKernelGGL(weave_apply_kernel<3>, grid, dim3(WV_NTH), 0, st, frames, shift, t0, L, H, W, out, mask);
-        else hipLaunchKernelGGL(weave_apply_kernel<1>, grid, dim3(WV_NTH), 0, st, frames, shift, t0, L, H, W, out, mask);
-        E2_LAUNCH_CHECK("weave_apply");
-    }
-    return 0;
+    auto kernel = C == 3 ? weave_apply_kernel<3> : weave_apply_kernel<1>;
+    return fb_slabs("weave_apply", L, [&](int t0, unsigned n) {
+        hipLaunchKernelGGL(kernel, dim3(nblk, n), dim3(WV_NTH), 0, st, frames, shift, t0, L, H, W, out, mask);
+    });
 }

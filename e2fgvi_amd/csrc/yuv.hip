@@ -5,7 +5,7 @@
 // the loads and stores are 8 bytes wide.  W is only even and a tensor may be a view, so the wide instantiation runs only where the
 // host finds W % 8 == 0 and 8-byte aligned bases (then every row, plane and frame starts on a multiple of 4, every strip's luma
 // and RGB bytes on a multiple of 8); everything else takes the byte-wise instantiation of the same body.
-#include "common.h"
+#include "frame_bytes.h"
 
 namespace {
 
@@ -42,24 +42,13 @@ __device__ __forceinline__ void load_bytes(const unsigned char* __restrict__ p, 
     }
 }
 
-// Two clipped shifts side by side in a word are what hipcc turns into one v_ashr_pk_u8_i32 (new on gfx950: shift two int32, clamp
-// each to a byte, pack them into the low half of the destination), and it ORs the word's other two bytes on top of the result as if
-// the upper half were zero.  On the chip exactly those two bytes came out wrong (bits set that neither operand has) while the
-// packed pair was right, in the decoder's 8-byte instantiation, the only code here that had the instruction; the byte-wise
-// instantiation and a host build of the same body were right.  The empty asm ends the pattern: the clip stays a v_med3_i32 and
-// the bytes are packed with shifts and ORs.  build.verify_no_pk_u8 fails the build if the instruction comes back.
-__device__ __forceinline__ unsigned opaque_byte(int v) {
-    asm volatile("" : "+v"(v));
-    return (unsigned)v;
-}
-
-// v[0 .. n) (values in [0, 255]) -> n bytes at p, same conditions
+// v[0 .. n) (values in [0, 255]) -> n bytes at p, same conditions; the bytes of a word go through fb_byte (frame_bytes.h has why)
 template <bool AL, int N>
 __device__ __forceinline__ void store_bytes(unsigned char* __restrict__ p, int n, const int (&u)[N]) {
     unsigned v[N];
     if constexpr (AL) {
 #pragma unroll
-        for (int k = 0; k < N; ++k) v[k] = opaque_byte(u[k]);
+        for (int k = 0; k < N; ++k) v[k] = fb_byte(u[k]);
     } else {
 #pragma unroll
         for (int k = 0; k < N; ++k) v[k] = (unsigned)u[k];

@@ -41,15 +41,18 @@ import torch
 from e2fgvi_amd import lib, metrics, ops, video
 from oracle import metrics_ref
 from tests import big_video as B
+from tests import color_cases as CL
 from tests import defect_cases as DF
 from tests import denoise_cases as DN
 from tests import flicker_cases as FL
+from tests import flicker_local_cases as FLL
 from tests import grain_cases as GR
 from tests import interlace_cases as IL
 from tests import line_scratch_cases as LN
 from tests import mask_key_cases as MK
 from tests import pixel_track_cases as PT
 from tests import scene_diff_cases as SD
+from tests import telecine_cases as TC
 from tests import warp_error_cases as WE
 from tests import weave_cases as WV
 from tests import yuv_cases as YV
@@ -670,6 +673,134 @@ def test_scene_diff_more_frames_than_a_launch_takes(dev):
         assert want[SLAB - 1:].any()
         got = ops.scene_diff(_dev(fr, dev)).cpu().numpy()
         assert got.dtype == np.int64 and np.array_equal(got, want), int((got != want).sum())
+
+
+def _stretches(margin):
+    """(a, b, cuts, lo, hi): where the restatement walks the frames in Python it runs on frames [a, b) alone -- the start of the video,
+    and its last 30 frames with the slab boundary and the cut among them; `cuts` is the cut as that stretch numbers it.  Frames
+    [lo, hi) of a stretch read no frame outside it when a frame reads `margin` frames either side."""
+    for a, b in ((0, 24), (L_B - 30, L_B)):
+        yield a, b, ([CUT_B - a] if a < CUT_B < b else None), (a + margin if a else a), (b - margin if b < L_B else b)
+
+
+def _tiny_frames(seed, spread=None):
+    """uint8 [L_B,4,4,3]: noise, or with `spread` a level per frame and noise of that spread around it"""
+    rng = np.random.RandomState(seed)
+    if spread is None:
+        return rng.randint(0, 256, (L_B, 4, 4, 3)).astype(np.uint8)
+    return np.clip(rng.randint(40, 216, (L_B, 1, 1, 1)) + rng.randint(-spread, spread + 1, (L_B, 4, 4, 3)), 0, 255).astype(np.uint8)
+
+
+def test_flicker_local_more_frames_than_a_launch_takes(dev):
+    """65 540 frames of 4 x 4 on a grid of 2 x 2: flicker_local_hist and flicker_local_apply launch the frames in slabs;
+    flicker_local_curves is one launch.  Histograms and curves against the restatement on the stretches, the output on the whole
+    video (the restatement's blend is one fancy index) with the device's curves."""
+    with B.measured("flicker_local slabs", dev):
+        grid, span, max_shift = (2, 2), 4, 32
+        fr = _tiny_frames(93, spread=30)
+        so = FL.scene_of_np(L_B, [CUT_B])
+        x = _dev(fr, dev)
+        hist = ops.flicker_local_hist(x, grid)
+        Q, d16 = ops.flicker_local_curves(hist, _dev(so, dev), 4, 4, span, max_shift)
+        hist, Q, d16 = hist.cpu().numpy(), Q.cpu().numpy(), d16.cpu().numpy()
+        for a, b, _, lo, hi in _stretches(span):
+            wh = FLL.hist_np(fr[a:b], grid)
+            assert np.array_equal(hist[a:b], wh), (a, b)
+            wq, wd = FLL.curves_np(wh, so[a:b], 4, 4, span, max_shift)
+            assert np.array_equal(Q[lo:hi], wq[lo - a:hi - a]) and np.array_equal(d16[lo:hi], wd[lo - a:hi - a]), (a, b)
+            assert wd[lo - a:hi - a].any()
+        assert (hist.sum(axis=(1, 2, 3)) == 16).all() and d16[SLAB].any() and d16[CUT_B].any()
+        want = FLL.apply_np(fr, d16)
+        assert not np.array_equal(want[SLAB:], fr[SLAB:])
+        got = ops.flicker_local_apply(x, _dev(d16, dev)).cpu().numpy()
+        assert np.array_equal(got, want), int((got != want).sum())
+
+
+def test_color_more_frames_than_a_launch_takes(dev):
+    """65 540 frames of 4 x 4: color_hist and color_apply launch the frames in slabs.  Both against the restatement on the whole
+    video; the tables are the caller's own, one either side of the cut, and two frames are in no group and copied."""
+    with B.measured("color slabs", dev):
+        fr = _tiny_frames(94)
+        x = _dev(fr, dev)
+        got = ops.color_hist(x).cpu().numpy()
+        want = CL.hist_np(fr)
+        assert np.array_equal(got, want), int((got != want).sum())
+        lut = np.random.RandomState(95).randint(0, 256, (2, 3, 256)).astype(np.uint8)
+        group = FL.scene_of_np(L_B, [CUT_B]).astype(np.int32)
+        group[5], group[SLAB + 1] = -1, 2
+        want = CL.apply_np(fr, lut, group)
+        assert np.array_equal(want[SLAB + 1], fr[SLAB + 1]) and not np.array_equal(want[SLAB], fr[SLAB])
+        got = ops.color_apply(x, _dev(lut, dev), _dev(group, dev)).cpu().numpy()
+        assert np.array_equal(got, want), int((got != want).sum())
+
+
+def test_weave_more_frames_than_a_launch_takes(dev):
+    """65 540 frames of 4 x 4: weave_profiles and weave_apply launch the frames in slabs.  The profiles against the restatement on
+    the whole video, the moved frames and their masks, a shift of its own per frame, on the stretches."""
+    with B.measured("weave slabs", dev):
+        fr = _tiny_frames(96)
+        x = _dev(fr, dev)
+        col, row = ops.weave_profiles(x)
+        wc, wr = WV.profiles_np(fr)
+        assert wc[SLAB:].any() and np.array_equal(col.cpu().numpy(), wc) and np.array_equal(row.cpu().numpy(), wr)
+        shifts = np.random.RandomState(97).randint(-40, 41, (L_B, 2)).astype(np.int32)
+        out, mask = ops.weave_apply(x, _dev(shifts, dev), return_mask=True)
+        out, mask = out.cpu().numpy(), mask.cpu().numpy()
+        for a, b, _, lo, hi in _stretches(0):
+            wo, wm = WV.apply_np(fr[a:b], shifts[a:b])
+            assert not np.array_equal(wo, fr[a:b]) and wm.any() and not wm.all()
+            assert np.array_equal(out[a:b], wo) and np.array_equal(mask[a:b], wm), (a, b)
+
+
+def test_interlace_more_frames_than_a_launch_takes(dev):
+    """65 540 frames of 4 x 4: interlace_scores launches the 65 539 pairs in slabs and deinterlace the frames; pair 65 534 sets the
+    last frame of the first slab against the first of the second, and a picture of frame 65 535 reads frames 65 534 and 65 536."""
+    with B.measured("interlace slabs", dev):
+        tff, mode, guard, edges = INTERLACE_SETTING
+        fr = _tiny_frames(98)
+        x, scene = _dev(fr, dev), _dev(IL.scene_of_np(L_B, [CUT_B]), dev)
+        D = ops.interlace_scores(x, scene).cpu().numpy()
+        out = ops.deinterlace(x, scene, bool(tff), mode, bool(guard), edges).cpu().numpy()
+        assert out.shape[0] == 2 * L_B
+        for a, b, cuts, lo, hi in _stretches(1):
+            wd = IL.scores_np(fr[a:b], cuts)
+            assert wd[:-1].any() and np.array_equal(D[a:hi], wd[:hi - a]), (a, b)     # the last pair of a stretch reads the frame behind it
+            want = IL.deinterlace_np(fr[a:b], cuts, tff, mode, guard, edges)
+            assert not np.array_equal(want[1::2], fr[a:b])
+            assert np.array_equal(out[2 * lo:2 * hi], want[2 * (lo - a):2 * (hi - a)]), (a, b)
+        assert not D[CUT_B - 1].any() and not D[L_B - 1].any() and D[SLAB - 1].any() and D[SLAB].any()
+
+
+def test_telecine_more_frames_than_a_launch_takes(dev):
+    """65 540 frames of 4 x 4: telecine_scores launches the frames in slabs; field_weave carries 65 540 jobs over 16 frames on the
+    grid's y and z axes, against the restatement on all of them."""
+    with B.measured("telecine slabs", dev):
+        fr = _tiny_frames(99)
+        M = ops.telecine_scores(_dev(fr, dev), _dev(IL.scene_of_np(L_B, [CUT_B]), dev)).cpu().numpy()
+        for a, b, cuts, lo, hi in _stretches(1):
+            wm = TC.scores_np(fr[a:b], cuts)
+            assert wm[lo - a:hi - a].any() and np.array_equal(M[lo:hi], wm[lo - a:hi - a]), (a, b)
+        jobs = np.random.RandomState(100).randint(0, 16, (L_B, 2))
+        want = TC.weave_np(fr[:16], jobs, 1)
+        assert not np.array_equal(want[SLAB:], fr[:16][jobs[SLAB:, 0]])
+        got = ops.field_weave(_dev(fr[:16], dev), jobs, 1).cpu().numpy()
+        assert np.array_equal(got, want), int((got != want).sum())
+
+
+def test_denoise_more_frames_than_a_launch_takes(dev):
+    """65 540 frames of 4 x 4 with flows on halves: the luma pass and the filter pass launch the frames in slabs; frame 65 535
+    averages over frames 65 534 and 65 536, frame 65 537 begins a scene."""
+    with B.measured("denoise slabs", dev):
+        rng = np.random.RandomState(101)
+        fr = np.clip(rng.randint(60, 200, (1, 4, 4, 3)) + rng.randint(-6, 7, (L_B, 4, 4, 3)), 0, 255).astype(np.uint8)
+        fwd = (rng.randint(-2, 3, (L_B - 1, 4, 4, 2)) * 0.5).astype(np.float32)
+        bwd = (rng.randint(-2, 3, (L_B - 1, 4, 4, 2)) * 0.5).astype(np.float32)
+        so = DN.scene_of_np(L_B, [CUT_B])
+        got = ops.denoise(_dev(fr, dev), _dev(fwd, dev), _dev(bwd, dev), _dev(so, dev), *DENOISE_SETTING).cpu().numpy()
+        for a, b, _, lo, hi in _stretches(1):
+            want = DN.reference(fr[a:b], fwd[a:b - 1], bwd[a:b - 1], so[a:b], *DENOISE_SETTING)
+            assert not np.array_equal(want[lo - a:hi - a], fr[lo:hi])
+            assert np.array_equal(got[lo:hi], want[lo - a:hi - a]), (a, b)
 
 
 # ------------------------------------------------------------------------------------------------ limits that are refusals

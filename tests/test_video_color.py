@@ -338,10 +338,13 @@ def test_header_and_binding_declare_the_entries():
 
 
 def test_source_has_no_floating_point():
-    src = open(os.path.join(ROOT, "e2fgvi_amd", "csrc", "color.hip")).read()
-    code = "\n".join(line.split("//")[0] for line in src.splitlines())
-    assert not re.search(r"\b(float|double|half)\b", code) and not re.search(r"\d\.\d*f?\b", code)
-    assert '#include "flicker_common.h"' in code
+    code = {}
+    for name in ("color.hip", "frame_bytes.h"):
+        src = open(os.path.join(ROOT, "e2fgvi_amd", "csrc", name)).read()
+        code[name] = "\n".join(line.split("//")[0] for line in src.splitlines())
+        assert not re.search(r"\b(float|double|half)\b", code[name]) and not re.search(r"\d\.\d*f?\b", code[name]), name
+    # the group of four pixels comes from the header of the byte-frame kernels, and nothing of the deflicker's is borrowed
+    assert '#include "frame_bytes.h"' in code["color.hip"] and "flicker_common.h" not in code["color.hip"]
 
 
 def test_built_object_has_no_scratch():

@@ -227,7 +227,8 @@ def test_header_and_binding_declare_the_entry():
     from e2fgvi_amd import build
     unit = [u for u in build.UNITS if u[0] == "denoise.hip"]
     assert len(unit) == 1 and unit[0][1] == "denoise.o" and unit[0][1] in build.NOPK_OBJECTS and unit[0][2] == build.NOPK
-    assert 'verify_no_scratch(objdir, "denoise.o", "denoise_", "temporal denoiser")' in inspect.getsource(build.build)
+    # the row of the table build() walks: verify_no_scratch over the unit's kernels on every build
+    assert ("denoise.o", "denoise_", "temporal denoiser", False) in build.KERNEL_CHECKS and "for obj, marker, what, _ in KERNEL_CHECKS" in inspect.getsource(build.build)
     for word in ("floor(q + 0.5)", "is dropped, not clamped", "256 + the sum of w(c)", "(Wsum >> 1)", "(65536 + (9 h) / 2) / (9 h)"):
         assert word in " ".join(header.split()), word
 

@@ -266,7 +266,7 @@ def test_header_binding_and_build_declare_the_entries():
 
 
 def test_source_has_no_floating_point():
-    for name in ("flicker_local.hip", "flicker_common.h"):
+    for name in ("flicker_local.hip", "flicker_common.h", "frame_bytes.h"):
         src = open(os.path.join(ROOT, "e2fgvi_amd", "csrc", name)).read()
         code = "\n".join(line.split("//")[0] for line in src.splitlines())
         assert not re.search(r"\b(float|double|half)\b", code) and not re.search(r"\d\.\d*f?\b", code), name

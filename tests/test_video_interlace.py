@@ -277,7 +277,8 @@ def test_header_and_binding_declare_the_entries():
     from e2fgvi_amd import build
     unit = [u for u in build.UNITS if u[0] == "interlace.hip"]
     assert len(unit) == 1 and unit[0][1] == "interlace.o" and unit[0][1] in build.NOPK_OBJECTS and unit[0][2] == build.NOPK
-    assert 'verify_no_scratch(objdir, "interlace.o", "interlace_", "deinterlacer")' in inspect.getsource(build.build)
+    # the row of the table build() walks: verify_no_scratch over the unit's kernels on every build
+    assert ("interlace.o", "interlace_", "deinterlacer", False) in build.KERNEL_CHECKS and "for obj, marker, what, _ in KERNEL_CHECKS" in inspect.getsource(build.build)
 
 
 def test_source_has_no_floating_point():

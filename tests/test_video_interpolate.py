@@ -326,8 +326,9 @@ def test_header_and_binding_declare_the_entry():
     assert len(unit) == 1 and unit[0][1] == "interpolate.o" and unit[0][1] in build.NOPK_OBJECTS
     assert unit[0][2] == build.NOPK + ["-ffp-contract=off"]
     src = inspect.getsource(build.build)
-    assert 'verify_no_scratch(objdir, "interpolate.o", "interpolate_", "frame interpolation")' in src
-    assert 'verify_no_fma64(objdir, "interpolate.o")' in src
+    # the row of the table build() walks: verify_no_scratch over the unit's kernel and, its last field, verify_no_fma64 over the object
+    assert ("interpolate.o", "interpolate_", "frame interpolation", True) in build.KERNEL_CHECKS
+    assert "verify_no_scratch(objdir, obj, marker, what)" in src and "verify_no_fma64(objdir, obj)" in src and src.count("in KERNEL_CHECKS") == 2
     for word in ("the product first", "(double)(tol tol) / 256.0", "floor(q 16 + 0.5)", "cost_A <= cost_B", "2 k <= d", "writes nothing"):
         assert word in " ".join(header.split()), word
 

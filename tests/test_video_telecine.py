@@ -382,7 +382,8 @@ def test_header_and_binding_declare_the_entries():
     from e2fgvi_amd import build
     unit = [u for u in build.UNITS if u[0] == "telecine.hip"]
     assert len(unit) == 1 and unit[0][1] == "telecine.o" and unit[0][1] in build.NOPK_OBJECTS and unit[0][2] == build.NOPK
-    assert 'verify_no_scratch(objdir, "telecine.o", "telecine_", "inverse telecine")' in inspect.getsource(build.build)
+    # the row of the table build() walks: verify_no_scratch over the unit's kernels on every build
+    assert ("telecine.o", "telecine_", "inverse telecine", False) in build.KERNEL_CHECKS and "for obj, marker, what, _ in KERNEL_CHECKS" in inspect.getsource(build.build)
 
 
 def test_source_has_no_floating_point():
